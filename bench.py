@@ -2,6 +2,7 @@
 """bench.py — B-spline trajectories/s of the batched ViGO solve on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py ... --dump-outputs DIR                 (also write the last timed step's results to DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over one batch that is already resident in HBM:
@@ -60,6 +61,9 @@ def parse():
                     help="N = 1 only: create the RCCL process group anyway (world size 1) and make exactly the collective calls "
                          "the N > 1 path makes — broadcast of the packed snapshot, all_reduce MIN/MAX on fp64 device tensors, barrier — "
                          "so RCCL's library load, dtypes and ops are exercised on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the SolveResult arrays, rank 0) "
+                         "as DIR/<name>.npy in float64, at most 64 MB in all (a seeded sample of trajectories beyond that)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="rehearsal of the N > 1 rank logic on a one-GPU box: every rank uses cuda:0 and the collectives "
                          "go over gloo (host-staged); timings are meaningless, the printed line is marked")
@@ -168,6 +172,27 @@ def pmc_view(precision, name, kern_ms, waves, simds, lib_build_id, suffix=""):
         out["memory_wait_of_wave_lifetime"] = cnt["SQ_WAIT_INST_ANY"] / cnt["SQ_WAVE_CYCLES"]
         out["wait_inst_any_wave_cycles"] = cnt["SQ_WAIT_INST_ANY"]
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res):
+    """res: the SolveResult of the last timed step.  Every array as float64 (integers exactly), one file per field;
+    when the whole batch exceeds DUMP_LIMIT_BYTES, the same seeded sample of trajectories from every field, and its
+    indices in sample_index.npy."""
+    import numpy as np
+    arrays = {k: getattr(res, k).cpu().numpy().astype(np.float64) for k in ("ctrl", "x", "status", "fx", "iters", "evals")}
+    B = arrays["status"].shape[0]
+    per_traj = sum(a.nbytes for a in arrays.values()) // B
+    budget = DUMP_LIMIT_BYTES - 4096                       # the .npy headers
+    if B * per_traj > budget:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=budget // (per_traj + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def main():
@@ -320,6 +345,8 @@ def main():
     elapsed, kern_ms, res, (ctrl0, goff, gpv, work, step) = timed_solves(v, batch, args.steps, args.warmup)
     iters = res.iters.cpu().numpy()      # of the timed configuration (the side measurements below overwrite res)
     evals = res.evals.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
     build_id = v._lib.vigo_build_id().decode()

@@ -1,7 +1,8 @@
 """Generates tests/golden/*.npz.  Run in the authoring container (needs /root/reference for the
 verbatim lbfgs.hpp shim oracle/_ref/libref_lbfgs.so):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            (all three files)
+    python tests/golden/make_golden.py checks     (lbfgs_ref_checks.npz only)
 
 lbfgs_ref.npz   small ViGO problems solved by the REFERENCE's own lbfgs_optimize
                 (solver/lbfgs.hpp, compiled verbatim) driving the oracle's cost restatement:
@@ -10,6 +11,11 @@ lbfgs_ref.npz   small ViGO problems solved by the REFERENCE's own lbfgs_optimize
 fixtures.npz    literal inputs of the reference's manual test programs
                 (src/test/testBsplineFit.cpp:5-24, src/test/testBspline.cpp:64-78,
                 src/test/waypoint.yaml + testTrajSolver.cpp:72-84) — data only.
+lbfgs_ref_checks.npz  the REFERENCE's lbfgs_optimize on the problems of tests/test_oracle_lbfgs.py's
+                test_oracle_bitwise_equals_verbatim_reference (per trajectory: status, evaluation count,
+                fx, sha-256 of x and of optData_.controlPoints; sha-256 of the seeded inputs) and
+                test_generic_objectives_and_parameter_errors_match_reference (status, evaluations, fx, x;
+                the codes of the parameter errors), so those tests hold where the shim cannot be built.
 The fixtures are data (inputs and expected outputs); no reference source text is stored.
 """
 import ctypes as C
@@ -48,7 +54,36 @@ def ref_solve(P, N, ctrl0, goff, gpv, gunk, obs, w, want_trace=True):
     return dict(status=st, x=x, fx=fx.value, evals=ev.value, ctrl=ctrl, trace=np.array(trace, dtype=np.float64).reshape(-1, 2))
 
 
+def checks():
+    import test_oracle_lbfgs as t
+    R = ol.ref()
+    assert R is not None, "oracle/_ref/libref_lbfgs.so missing (needs /root/reference)"
+    world = synth.make_box_world(synth.SEED_BASE + 2, n=128, n_boxes=60, centre_range=5.5, z_range=2.0)   # conftest small_world
+    out = {}
+    for (N, n_obs, iters) in t.VERBATIM_CASES:
+        key = f"v{N}_{n_obs}_{iters}"
+        P, b, probs = t.verbatim_problems(world, N, n_obs, iters)
+        rs = [ref_solve(P, N, ctrl0, goff, b.guide_pv, b.guide_unk, obs, w, want_trace=False) for ctrl0, goff, obs, w in probs]
+        out[key + "_inputs"] = t.digest(b.ctrl, b.guide_off, b.guide_pv, b.guide_unk, b.obs, b.obs_off)
+        out[key + "_status"] = np.array([r["status"] for r in rs], dtype=np.int64)
+        out[key + "_evals"] = np.array([r["evals"] for r in rs], dtype=np.int64)
+        out[key + "_fx"] = np.array([r["fx"] for r in rs])
+        out[key + "_x"] = np.stack([t.digest(r["x"]) for r in rs])
+        out[key + "_ctrl"] = np.stack([t.digest(r["ctrl"]) for r in rs])
+    gen = [t.generic_solve(R, fn, n, x0, t.generic_params(m, iters, geps)) for fn, n, x0, m, iters, geps in t.GENERIC_RUNS]
+    out["generic_status"] = np.array([r[0] for r in gen], dtype=np.int64)
+    out["generic_evals"] = np.array([r[1] for r in gen], dtype=np.int64)
+    out["generic_fx"] = np.array([r[2] for r in gen])
+    for k, r in enumerate(gen):
+        out[f"generic_x{k}"] = r[3]
+    out["bad_status"] = np.array([t.generic_solve(R, t.quad, 6, 1.0, t.bad_params(f, v))[0] for f, v in t.BAD_PARAMS], dtype=np.int64)
+    np.savez_compressed(os.path.join(HERE, "lbfgs_ref_checks.npz"), **out)
+    print("wrote lbfgs_ref_checks.npz; statuses", {k: np.unique(v).tolist() for k, v in out.items() if k.endswith("_status")})
+
+
 def main():
+    if sys.argv[1:] == ["checks"]:
+        return checks()
     world = synth.make_box_world(synth.SEED_BASE + 2, n=128, n_boxes=60, centre_range=5.5, z_range=2.0)
     out = {}
     cases = [(12, 0, 50), (20, 2, 50), (32, 0, 50), (32, 1, 200), (40, 0, 50), (64, 2, 50)]
@@ -91,6 +126,7 @@ def main():
     fx["waypoints"] = np.array([[0, 0, 1], [1, 1, 1], [2, 0, 1], [4, 10, 1]], dtype=np.float64)
     np.savez_compressed(os.path.join(HERE, "fixtures.npz"), **fx)
     print("wrote fixtures.npz")
+    checks()
 
 
 if __name__ == "__main__":
