@@ -88,7 +88,7 @@ def main():
         merged.update(collect(d, kernel))
     fetch_kib = merged.get("FETCH_SIZE", (0.0, 0))[0]
     write_kib = merged.get("WRITE_SIZE", (0.0, 0))[0]
-    try:    # the library's own identity: content hashes of its sources (include/vigo.h vigo_build_id; loading it starts no GPU work)
+    try:    # the library's own identity: digests of its compiled code (include/vigo.h vigo_build_id; loading it starts no GPU work)
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         from trajectory_planner_amd import _lib
         build_id = _lib.load().vigo_build_id().decode()

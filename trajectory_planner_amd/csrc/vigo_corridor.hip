@@ -21,7 +21,6 @@
 // A tile too large for the LDS budget falls back to lookups in the packed planes (L2).
 #include <type_traits>
 
-#include "vigo_corridor.hpp"
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_grid.hpp"
@@ -507,11 +506,9 @@ __global__ void __launch_bounds__(64) k_corridor_clocks(int S, const int32_t* __
 //   PASS 1  the walk of rounds 1-2 for those: every thread over chunks of 16 consecutive samples.
 // DEG7: the planner's degree (cfg polynomial_degree: 7), unrolled.
 // (four waves per SIMD = at most 128 VGPRs)
-#ifndef VIGO_CORRIDOR_WPS
-#define VIGO_CORRIDOR_WPS 4
-#endif
+constexpr int kCorridorWps = 4;
 template <int PASS, bool DEG7>
-__global__ void __launch_bounds__(kBlock, VIGO_CORRIDOR_WPS) k_corridor(GridView g, CorridorArgs A) {
+__global__ void __launch_bounds__(kBlock, kCorridorWps) k_corridor(GridView g, CorridorArgs A) {
     extern __shared__ __align__(16) uint32_t tile_words[];
     __shared__ double cf[3 * (kMaxDeg + 1)];
     __shared__ int s_min[3], s_max[3];
@@ -1165,16 +1162,16 @@ int launch_esdf_brick(hipStream_t s, int nx, int ny, int nz, const float* src, f
 }
 
 int launch_corridor_check2(hipStream_t s, const GridView& g, int S, int deg, const double* coeffs,
-                          const int32_t* n_samp, const double* delT, const double box[3],
-                          double map_res, uint8_t* out_flag, int32_t* out_first, int32_t* out_count, int* todo, void* clock_ws) {
+                           const int32_t* n_samp, const double* delT, const double box[3],
+                           double map_res, uint8_t* out_flag, int32_t* out_first, int32_t* out_count, int* todo, void* clock_ws) {
     if (S <= 0) return hipSuccess;
     CorridorArgs A{};
     A.S = S; A.deg = deg;
     A.coeffs = coeffs; A.n_samp = n_samp; A.delT = delT;
     A.sweep = SweepConst{{box[0], box[1], box[2]}, map_res, 1.0 / g.res};
     A.out_flag = out_flag; A.out_first = out_first; A.out_count = out_count;
-    // with the first pass' static LDS (21.6 KB): VIGO_CORRIDOR_WPS workgroups per CU (18 KB of tile for four)
-    const int tile_bytes = (160 * 1024 / VIGO_CORRIDOR_WPS - 22 * 1024) & ~255;
+    // with the first pass' static LDS (21.6 KB): kCorridorWps workgroups per CU (18 KB of tile for four)
+    const int tile_bytes = (160 * 1024 / kCorridorWps - 22 * 1024) & ~255;
     A.tile_words_cap = tile_bytes / 4;
     A.todo = todo;
     A.clocks = static_cast<const ClockTable*>(clock_ws);

@@ -122,9 +122,14 @@ int launch_traj_dynamic_collision(hipStream_t s, int B, int N, const double* ctr
 int launch_fill_sample_times(hipStream_t s, double dt, int T, double* times);
 int launch_ctrl_occupancy(hipStream_t s, const GridView& g, int B, int N, const double* ctrl,
                           uint8_t* out_pt, uint8_t* out_line);
-int launch_corridor_check(hipStream_t s, const GridView& g, int S, int deg, const double* coeffs,
-                          const int32_t* n_samp, const double* delT, const double box[3],
-                          double map_res, uint8_t* out_flag, int32_t* out_first, int32_t* out_count);
+// the corridor checker's two passes (vigo_corridor.hip, k_corridor).  todo: S ints of device scratch (which segments the
+// first pass left to the second); clock_ws: corridor_clock_ws_bytes(S) bytes of device scratch, 8-byte aligned, for the
+// segments' sample-clock tables, or NULL (every workgroup then builds its own).  (The "2" stays: the call's text is
+// part of the error vigo_corridor_check reports when the launch fails.)
+size_t corridor_clock_ws_bytes(int S);
+int launch_corridor_check2(hipStream_t s, const GridView& g, int S, int deg, const double* coeffs, const int32_t* n_samp,
+                           const double* delT, const double box[3], double map_res, uint8_t* out_flag, int32_t* out_first,
+                           int32_t* out_count, int* todo, void* clock_ws);
 int launch_box_points(hipStream_t s, const GridView& g, int64_t M, const double* pts, const double box[3],
                       double map_res, uint8_t* out);
 // polyTrajSolver::getTrajectory for S segments: sample k of segment s at out[(s * stride + k) * 3] (fp64 and/or float)

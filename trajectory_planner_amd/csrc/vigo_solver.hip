@@ -29,10 +29,6 @@
 
 #include "vigo_internal.hpp"
 
-#ifndef VIGO_DOUBLE_ADD
-#define VIGO_DOUBLE_ADD 1
-#endif
-
 namespace vigo {
 namespace {
 
@@ -138,18 +134,6 @@ __device__ __forceinline__ double dpp_f64(double v) {
     const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double xor16_sum(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-__device__ __forceinline__ double xor32_sum(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
 // The xor-16 level needs the value twice (v_permlane16_swap exchanges rows between TWO registers and clobbers
 // both).  Instead of copying the result of the row_mirror level (two v_mov_b32), that level's add is issued twice:
 // one VALU slot instead of two.  The second add is an asm statement so that it is not merged with the first (the
@@ -183,7 +167,7 @@ __device__ __forceinline__ void group_sum(double (&v)[K]) {
     for (int q = 0; q < K; ++q) v[q] += dpp_f64<0x4E>(v[q]);   // quad_perm:[2,3,0,1]
 #pragma unroll
     for (int q = 0; q < K; ++q) v[q] += dpp_f64<0x141>(v[q]);  // row_half_mirror
-    if (GROUP >= 32 && VIGO_DOUBLE_ADD) {
+    if (GROUP >= 32) {
 #pragma unroll
         for (int q = 0; q < K; ++q) {
             const double t = dpp_f64<0x140>(v[q]);             // row_mirror
@@ -198,14 +182,6 @@ __device__ __forceinline__ void group_sum(double (&v)[K]) {
     }
 #pragma unroll
     for (int q = 0; q < K; ++q) v[q] += dpp_f64<0x140>(v[q]);  // row_mirror
-    if (GROUP >= 32) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = xor16_sum(v[q]);
-    }
-    if (GROUP == 64) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = xor32_sum(v[q]);
-    }
 }
 template <int GROUP>
 __device__ __forceinline__ double group_sum1(double v) {
@@ -873,26 +849,6 @@ __device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd
 // Control flow: an outer trip per L-BFGS iteration (trip 0 = the initial evaluation) with ONE
 // evaluation site inside the line-search loop, so the two groups of a wave re-converge at every
 // iteration boundary and run the (dominant) two-loop recursion together.
-#ifndef VIGO_TWOLOOP_WIN
-#define VIGO_TWOLOOP_WIN 2
-#endif
-#ifndef VIGO_DOUBLE_ADD
-#define VIGO_DOUBLE_ADD 1
-#endif
-#ifndef VIGO_TWOLOOP_STEADY
-#define VIGO_TWOLOOP_STEADY 1
-#endif
-#ifndef VIGO_TWOLOOP_MARKSTEIN
-#define VIGO_TWOLOOP_MARKSTEIN 1
-#endif
-// dev switch, measured and left off (profiles/README.md, round 3): 1 = the byte offsets of the 14 ring slots by AGE worked
-// out once per two-loop (14 x {sub, wrap}, pinned in SGPRs) and each of the 28 fetches taking its offset from that table
-// by a static index, instead of a running offset stepped and wrapped before every fetch (4 SALU instructions per fetch).
-// The step loses its 4 SALU instructions and gains 4 s_nop: they had been sitting in the wait states the DPP moves of
-// the butterfly need after the add that feeds them.  +2 % at B = 1024, +3 % on the full-chip batches.
-#ifndef VIGO_RING_TABLE
-#define VIGO_RING_TABLE 0
-#endif
 // dev builds only (-DVIGO_PROFILE_SECTIONS=1, tools/exp_sections.py): shader-clock totals of the sections of an
 // iteration, written over out_x[b][0..9] — never defined in the shipped library
 #ifndef VIGO_PROFILE_SECTIONS
@@ -919,7 +875,7 @@ __device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd
 // OBS == false: the instantiation the launcher picks for calls without an obstacle list (A.obs == nullptr): no staging
 // code, no obstacle loop, six sums per evaluation instead of seven — the same bits, fewer live registers
 // RH = history pairs besides the newest that stay in registers (ages 1 .. RH; 0 for more than one point per lane: all in
-// LDS): 1 normally; 4 or 5 in the level instantiations launched on batches that fill the chip (VIGO_LEVEL_RH below):
+// LDS): 1 normally; 4 or 5 in the level instantiations launched on batches that fill the chip (kLevelRH below):
 // fewer ring slots in LDS are more resident waves per CU
 template <typename T, int GROUP, int PPL, bool FAST, int WPS = 1, bool OBS = true, int D = 3, int RH = (PPL == 1 ? 1 : 0)>
 __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevConst* __restrict__ Kp) {
@@ -1218,7 +1174,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 #pragma unroll
             for (int a = 0; a < D; ++a) d[q][a] = -g[q][a];
 
-        constexpr int kWin = VIGO_TWOLOOP_WIN;
+        constexpr int kWin = 2;
         T Ps[kWin][PPL][3], Py[kWin][PPL][3];
         YS Pys[kWin];
         auto fetch = [&](int age, T (&s_)[PPL][3], T (&y_)[PPL][3], YS& ys_) {
@@ -1256,7 +1212,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         // alphas stay in registers.  Same operations in the same order as the general path.
         auto two_loop = [&](auto steady_tag) -> bool {
             constexpr bool STEADY = decltype(steady_tag)::value;
-            constexpr bool MARK = STEADY && !FAST && VIGO_TWOLOOP_MARKSTEIN;
+            constexpr bool MARK = STEADY && !FAST;
             double amin = 1.0, amax = 1.0;
             // (general path: every live lane of the wave is in the same iteration, so the number of pairs is taken
             // through an SGPR — `age < bnd` becomes a scalar branch instead of a compare + exec-mask block per step)
@@ -1289,29 +1245,16 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
                 curB += stepB;
                 if (curB >= kRing * stepB) curB -= kRing * stepB;
             };
-            // (VIGO_RING_TABLE) ringT[i] = byte offset of the pair of age RH + 1 + i
-            int ringT[kRing];
-            if (STEADY && VIGO_RING_TABLE) {
-                int c = curB;
-#pragma unroll
-                for (int i = 0; i < kRing; ++i) {
-                    ringT[i] = c;
-                    // (an opaque SGPR value: otherwise the chain above is re-materialised at every use)
-                    asm volatile("" : "+s"(ringT[i]));
-                    c -= stepB;
-                    if (c < 0) c += kRing * stepB;
-                }
-            }
-            // the pair of age `age` (a literal after unrolling) into a window slot; the running offset (table off) relies
-            // on the two loops asking for the ages in ring order
+            // the pair of age `age` (a literal after unrolling) into a window slot; the running offset relies on the two
+            // loops asking for the ages in ring order.  (Measured and left off, profiles/README.md, round 3: the byte
+            // offsets of the 14 ring slots by AGE worked out once per two-loop, pinned in SGPRs, and each of the 28
+            // fetches taking its offset from that table by a static index, instead of this running offset stepped and
+            // wrapped before every fetch (4 SALU instructions per fetch).  The step loses its 4 SALU instructions and
+            // gains 4 s_nop: they had been sitting in the wait states the DPP moves of the butterfly need after the add
+            // that feeds them.  +2 % at B = 1024, +3 % on the full-chip batches.)
             auto ring_fetch_age = [&](int age, bool newer_next, T (&s_)[PPL][3], T (&y_)[PPL][3], YS& ys_) {
-                if (VIGO_RING_TABLE) {
-                    curB = ringT[(age - kFirstRing >= 0 && age - kFirstRing < kRing) ? age - kFirstRing : 0];
-                    ring_fetch(s_, y_, ys_);
-                } else {
-                    ring_fetch(s_, y_, ys_);
-                    if (newer_next) ring_newer(); else ring_older();
-                }
+                ring_fetch(s_, y_, ys_);
+                if (newer_next) ring_newer(); else ring_older();
             };
 #pragma unroll
             for (int q = 0; q < PPL; ++q)
@@ -1351,10 +1294,8 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
                 // loop starts fetching at age kMaxMem - 1 - kWin.  The compiler must not keep the
                 // first loop's 14 pairs alive in AGPRs for it (24 register moves per pair cost more
                 // VALU slots than three ds_read_b128): LDS is declared clobbered here.
-                if (!VIGO_RING_TABLE) {
 #pragma unroll
-                    for (int i = 0; i < kWin + 1; ++i) ring_newer();
-                }
+                for (int i = 0; i < kWin + 1; ++i) ring_newer();
                 asm volatile("" ::: "memory");
             }
             {
@@ -1394,7 +1335,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
             return bad;
         };
         VIGO_TICK(t_upd);
-        if (VIGO_TWOLOOP_STEADY && PPL == 1 && bound == kMaxMem && !__any(last != __builtin_amdgcn_readfirstlane(last))) {
+        if (PPL == 1 && bound == kMaxMem && !__any(last != __builtin_amdgcn_readfirstlane(last))) {
             if (__any(two_loop(std::true_type{}))) {
                 // a dividend outside the range Markstein's sequence is proven for (or a NaN): the same
                 // recursion again from d = -g on the general path, which divides for real
@@ -1577,21 +1518,12 @@ static int raise_dynamic_lds(LaunchState& L, int slot, KernelT kernel) {
     return (int)hipSuccess;
 }
 
-// dev switch: 0 = never launch the level (D = 2) instantiation
-#ifndef VIGO_LEVEL_KERNEL
-#define VIGO_LEVEL_KERNEL 1
-#endif
 // History pairs besides the newest that the level kernel keeps in registers on batches with more waves than SIMDs
 // (1 = as everywhere), where LDS decides how many waves a CU holds.  N <= 32 (two trajectories per wave): 4 pairs,
 // 24.4 -> 19.3 KB, six -> EIGHT waves per CU (256 VGPRs, no spills): 1.74 -> 1.47 ms at 16 384 x 32 (2 pairs: 1.60,
 // 3: 1.61, 5: 1.54).  32 < N <= 64 (one per wave): 5 pairs, 26.8 -> 19.2 KB, six -> eight: 1.85 -> 1.54 ms at 8192 x 64
 // (4 pairs, seven waves: 1.71; 6 pairs: 1.57).  Same arithmetic, same bits.
-#ifndef VIGO_LEVEL_RH
-#define VIGO_LEVEL_RH 4
-#endif
-#ifndef VIGO_LEVEL_RH64
-#define VIGO_LEVEL_RH64 5
-#endif
+constexpr int kLevelRH = 4, kLevelRH64 = 5;
 template <typename T, int GROUP, int PPL, bool FAST, bool OBS>
 static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevConst& k, const DevConst* kd, LaunchState& L) {
     const int tpb = kWave / GROUP;
@@ -1615,7 +1547,7 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
     // of level trajectories do.  The order matters: each launch decides from the control points it finds; a level
     // trajectory's z is untouched by the first launch, so the second still sees it level and skips it — the other way
     // round, a trajectory just outside the band that the general solve smooths into it would be solved a second time.
-    constexpr bool kHasLevel = VIGO_LEVEL_KERNEL && PPL == 1 && !OBS;
+    constexpr bool kHasLevel = PPL == 1 && !OBS;
     const bool two = kHasLevel && !k.plan_in_z && !k.strict_z;
     a.level_waves_elsewhere = two ? 1 : 0;
     const size_t lds = optimize_lds_bytes<T, GROUP, FAST, 3>(a.N, k.mem_size, PPL, a.obs != nullptr);
@@ -1625,9 +1557,9 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
         if (two) {
             const size_t lds2 = optimize_lds_bytes<T, GROUP, FAST, 2>(a.N, k.mem_size, PPL, false);
             const int slot2 = 48 + arith * 4 + shape * 2;
-            // fp64, two trajectories per wave, more waves than SIMDs: keep VIGO_LEVEL_RH pairs besides the newest in
+            // fp64, two trajectories per wave, more waves than SIMDs: keep kLevelRH pairs besides the newest in
             // registers when that buys a further resident wave per CU (N = 32, m = 16: 24.4 -> 22.7 KB, six -> seven)
-            constexpr int kRH = GROUP == 32 ? VIGO_LEVEL_RH : VIGO_LEVEL_RH64;
+            constexpr int kRH = GROUP == 32 ? kLevelRH : kLevelRH64;
             constexpr bool kHasRH = std::is_same<T, double>::value && kRH > 1;
             bool done = false;
             if constexpr (kHasRH) {
@@ -1692,7 +1624,7 @@ int launch_optimize(hipStream_t s, const SolveArgs& a, const DevConst& k, const 
     // than SIMDs (8 % slower there): those keep the general kernel, which treats a missing list as no obstacles.
     // (Only where the level instantiation cannot apply — z planning on: with it, level waves go to the D = 2 kernel, 20 %
     // faster than either, and the corner is not worth keeping them from it.)
-    if (precision == VIGO_PREC_F64_FAST && a.N > 32 && a.N <= 64 && L.simd_count > 0 && a.B > L.simd_count && (k.plan_in_z || k.strict_z || !VIGO_LEVEL_KERNEL))
+    if (precision == VIGO_PREC_F64_FAST && a.N > 32 && a.N <= 64 && L.simd_count > 0 && a.B > L.simd_count && (k.plan_in_z || k.strict_z))
         return launch_optimize_with_obstacles(s, a, k, kd, precision, L);
     return launch_optimize_o<false>(s, a, k, kd, precision, L);
 }
