@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <numeric>
 #include <stdexcept>
+#include <string>
 
 int main() {
     std::atomic<long> bad{0};
@@ -52,7 +53,8 @@ int main() {
         if (std::accumulate(out.begin(), out.end(), 0) != 300) ++bad;
     }
     // the companion threads of makePlanBatch: jobs started and awaited in turn from two caller threads, each with its own
-    // companions, the jobs themselves running parallelFor on the companion's own pool; a throwing job ends cleanly
+    // companions, the jobs themselves running parallelFor on the companion's own pool; the exception of a throwing job
+    // arrives from that job's wait(), once, while the other companions finish theirs, and the companion takes the next job
     {
         auto user = [&](int seed) {
             vigo_host::Companion comp[3];
@@ -63,9 +65,24 @@ int main() {
                         std::vector<int> out(200 + 10 * k, 0);
                         vigo_host::parallelFor(out.size(), [&](size_t i) { out[i] = (int)i + rep + seed; });
                         sums[k] = std::accumulate(out.begin(), out.end(), 0L);
-                        if (rep == 7 && k == 1) throw std::runtime_error("job failed");
+                        if (rep == 7 && k == 1) throw std::runtime_error("job failed " + std::to_string(seed));
                     });
-                for (int k = 0; k < 3; ++k) comp[k].wait();
+                for (int k = 0; k < 3; ++k) {
+                    int caught = 0;
+                    try {
+                        comp[k].wait();
+                    } catch (const std::runtime_error& e) {
+                        caught = e.what() == "job failed " + std::to_string(seed) ? 1 : 2;
+                    }
+                    if (caught != (rep == 7 && k == 1 ? 1 : 0)) ++bad;
+                }
+                if (rep == 7) {
+                    try {
+                        comp[1].wait();              // (rethrown once: nothing left to rethrow)
+                    } catch (...) {
+                        ++bad;
+                    }
+                }
                 for (int k = 0; k < 3; ++k) {
                     const long n = 200 + 10 * k;
                     if (sums[k] != n * (n - 1) / 2 + n * (rep + seed)) ++bad;

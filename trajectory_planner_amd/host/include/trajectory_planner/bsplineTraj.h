@@ -200,6 +200,15 @@ private:
      * planners' control points, weights, failCount, collisionSeg_.  false: device failure (nothing usable) */
     static bool deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds);
     static void gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& col, std::vector<uint8_t>& dyn);
+    /* the steps of makePlanBatch: the split into pipelined parts; for one part the prologue (steps 1-3), the rebound loop
+     * on the device or driven from the host, the move of finished planners out of the loop, the epilogue (steps 5-6) */
+    struct PlanBatch;
+    static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold);
+    static void planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb);
+    static void reboundOnDevice(PlanBatch& pb, bool timing);
+    static void reboundFromHost(PlanBatch& pb, bool timing);
+    static void retireFinished(PlanBatch& pb);
+    static void planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result);
 };
 }  // namespace trajPlanner
 #endif

@@ -1,0 +1,76 @@
+// batchLayout.h — internal to the host facades: bsplineTraj's optData flattened into the batch layouts of include/vigo.h
+// (control points column by column; guide pairs and dynamic obstacles as CSR lists, offsets + flat list), and the order
+// in which planners are grouped into device batches.
+#ifndef VIGO_HOST_BATCH_LAYOUT_H
+#define VIGO_HOST_BATCH_LAYOUT_H
+#include <trajectory_planner/bsplineTraj.h>
+
+#include <array>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace vigo_host {
+
+// The guide pairs (point, direction: 6 doubles) of control points 0 .. N-1 in push order, appended to pv; after each
+// control point the running pair count is appended to off (N offsets).  A control point without a guide list (guidePoints
+// shorter than N, as clear() leaves it) has no pairs.
+inline void appendGuides(const trajPlanner::optData& od, int N, std::vector<int32_t>& off, std::vector<double>& pv) {
+    for (int i = 0; i < N; ++i) {
+        const size_t cnt = i < (int)od.guidePoints.size() ? od.guidePoints[i].size() : 0;
+        for (size_t j = 0; j < cnt; ++j) {
+            for (int q = 0; q < 3; ++q) pv.push_back(od.guidePoints[i][j](q));
+            for (int q = 0; q < 3; ++q) pv.push_back(od.guideDirections[i][j](q));
+        }
+        off.push_back((int32_t)(pv.size() / 6));
+    }
+}
+
+// the dynamic obstacles (position, velocity, size: 9 doubles each) appended to obs
+inline void appendObstacles(const trajPlanner::optData& od, std::vector<double>& obs) {
+    for (size_t j = 0; j < od.dynamicObstaclesPos.size(); ++j) {
+        for (int q = 0; q < 3; ++q) obs.push_back(od.dynamicObstaclesPos[j](q));
+        for (int q = 0; q < 3; ++q) obs.push_back(od.dynamicObstaclesVel[j](q));
+        for (int q = 0; q < 3; ++q) obs.push_back(od.dynamicObstaclesSize[j](q));
+    }
+}
+
+// B trajectories of N control points each, added one planner at a time
+struct HostBatch {
+    int B = 0, N;
+    std::vector<double> ctrl, gpv, obs, weights;
+    std::vector<int32_t> goff{0}, ooff{0};
+    explicit HostBatch(int n) : N(n) {}
+    // controlPoints: 3 x N column by column; w: (distance, smoothness, feasibility, dynamic)
+    void add(const double* controlPoints, const trajPlanner::optData& od, const std::array<double, 4>& w) {
+        ctrl.insert(ctrl.end(), controlPoints, controlPoints + 3 * N);
+        appendGuides(od, N, goff, gpv);
+        appendObstacles(od, obs);
+        ooff.push_back((int32_t)(obs.size() / 9));
+        weights.insert(weights.end(), w.begin(), w.end());
+        ++B;
+    }
+    size_t guides() const { return gpv.size() / 6; }
+};
+
+// fn(members) for every group of the indices [0, n): the lead is the first index not in a group yet, the members are
+// every index from the lead on that is not in a group yet and for which same(lead, index) holds, in increasing order.
+// This order decides what goes into each device batch.  An index for which same(index, index) fails is in no group.
+template <typename Same, typename Fn>
+void forEachGroup(size_t n, Same same, Fn fn) {
+    std::vector<bool> grouped(n, false);
+    std::vector<size_t> members;
+    for (size_t a = 0; a < n; ++a) {
+        if (grouped[a]) continue;
+        members.clear();
+        for (size_t b = a; b < n; ++b)
+            if (!grouped[b] && same(a, b)) {
+                members.push_back(b);
+                grouped[b] = true;
+            }
+        if (!members.empty()) fn(members);
+    }
+}
+
+}  // namespace vigo_host
+#endif  /* VIGO_HOST_BATCH_LAYOUT_H */

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <atomic>
 #include <condition_variable>
@@ -22,6 +23,7 @@
 #include <set>
 
 #include "../../../include/vigo.h"
+#include "batchLayout.h"
 #include "devbuf.h"
 #include "workerPool.h"
 
@@ -30,7 +32,6 @@ using std::endl;
 
 namespace {
 
-using vigo_host::DevBuf;
 using vigo_host::StagingBuf;
 
 using vigo_host::parallelFor;
@@ -340,16 +341,14 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
         ready[i] = okv[i] && fitPts[i].size() > 3;
     }
     g_prevPathLength.store(prev);
-    std::vector<bool> doneMask(planners.size(), false);
-    for (size_t a = 0; a < planners.size(); ++a) {
-        if (doneMask[a] || !ready[a]) continue;
-        const int K = (int)fitPts[a].size();
-        const double ts = planners[a]->controlPointsTs_;
-        std::vector<size_t> grp;
-        for (size_t b = a; b < planners.size(); ++b)
-            if (!doneMask[b] && ready[b] && (int)fitPts[b].size() == K && planners[b]->controlPointsTs_ == ts) { grp.push_back(b); doneMask[b] = true; }
-        bsplineTraj* lead = planners[a];
-        if (K + 2 > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) continue;
+    auto sameFit = [&](size_t a, size_t b) {
+        return ready[a] && ready[b] && fitPts[a].size() == fitPts[b].size() && planners[a]->controlPointsTs_ == planners[b]->controlPointsTs_;
+    };
+    vigo_host::forEachGroup(planners.size(), sameFit, [&](const std::vector<size_t>& grp) {
+        bsplineTraj* lead = planners[grp[0]];
+        const int K = (int)fitPts[grp[0]].size();
+        const double ts = lead->controlPointsTs_;
+        if (K + 2 > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
         const int B = (int)grp.size();
         std::vector<double> pts((size_t)B * K * 3), cond((size_t)B * 12), ctrl((size_t)B * (K + 2) * 3);
         for (int b = 0; b < B; ++b) {
@@ -359,12 +358,12 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
                 for (int q = 0; q < 3; ++q) cond[((size_t)b * 4 + i) * 3 + q] = startEndConditions[grp[b]][i](q);
         }
         static thread_local StagingBuf dPts, dCond, dCtrl;
-        if (!dPts.upload(pts.data(), pts.size() * 8) || !dCond.upload(cond.data(), cond.size() * 8) || !dCtrl.alloc(ctrl.size() * 8)) continue;
+        if (!dPts.upload(pts.data(), pts.size() * 8) || !dCond.upload(cond.data(), cond.size() * 8) || !dCtrl.alloc(ctrl.size() * 8)) return;
         if (vigo_bspline_fit(lead->dev_, B, K, ts, (const double*)dPts.p, (const double*)dCond.p, (double*)dCtrl.p) != VIGO_OK) {
             cout << "[BsplineTraj]: vigo_bspline_fit failed: " << vigo_last_error(lead->dev_) << endl;
-            continue;
+            return;
         }
-        if (!vigo_host::threadSync() || !dCtrl.download(ctrl.data(), ctrl.size() * 8)) continue;
+        if (!vigo_host::threadSync() || !dCtrl.download(ctrl.data(), ctrl.size() * 8)) return;
         parallelFor((size_t)B, [&](size_t b) {
             Eigen::MatrixXd controlPoints;
             controlPoints.resize(3, K + 2);
@@ -372,7 +371,7 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
             planners[grp[b]]->installControlPoints(controlPoints, fitPts[grp[b]]);
         });
         for (int b = 0; b < B; ++b) ok[grp[b]] = true;
-    }
+    });
     return ok;
 }
 
@@ -653,134 +652,117 @@ bool bsplineTraj::isReguideRequired(std::vector<std::pair<int, int>>& reguideCol
 // ---- device calls ---------------------------------------------------------------------
 
 namespace {
-// flattens the planners' optData into the batch layouts of include/vigo.h
-struct HostBatch {
-    int B = 0, N = 0;
-    std::vector<double> ctrl, gpv, obs, weights;
-    std::vector<int32_t> goff, ooff;
+using vigo_host::HostBatch;
+
+// device pointers to a HostBatch's lists; an empty guide or obstacle list is null (vigo.h: "no guides" / "no obstacles")
+struct DeviceBatch {
+    double* ctrl;
+    const int32_t* goff;
+    const double* gpv;
+    const uint8_t* gunk;
+    const int32_t* ooff;
+    const double* obs;
+    double* weights;
 };
+
+// hb into the calling thread's staging buffers, then map_->isUnknown(guidePoint) (BT.cpp:841) for its guides, hoisted
+// out of the solve.  The buffers live across calls (hipMalloc/hipFree per rebound round cost more than the round's
+// kernels): the thread's next upload overwrites them, so what a call reads back is read back before that.
+bool uploadBatch(vigo_handle_t h, const HostBatch& hb, DeviceBatch& d) {
+    static thread_local StagingBuf dCtrl, dGoff, dGpv, dGunk, dOoff, dObs, dW;
+    const size_t G = hb.guides();
+    if (!dCtrl.upload(hb.ctrl.data(), hb.ctrl.size() * 8) || !dGoff.upload(hb.goff.data(), hb.goff.size() * 4) ||
+        !dGpv.upload(hb.gpv.data(), hb.gpv.size() * 8) || !dGunk.alloc(G) || !dOoff.upload(hb.ooff.data(), hb.ooff.size() * 4) ||
+        !dObs.upload(hb.obs.data(), hb.obs.size() * 8) || !dW.upload(hb.weights.data(), hb.weights.size() * 8))
+        return false;
+    if (G && vigo_guides_unknown(h, (int64_t)G, (const double*)dGpv.p, (uint8_t*)dGunk.p) != VIGO_OK) return false;
+    d = {(double*)dCtrl.p, (const int32_t*)dGoff.p, G ? (const double*)dGpv.p : nullptr, G ? (const uint8_t*)dGunk.p : nullptr,
+         (const int32_t*)dOoff.p, hb.obs.empty() ? nullptr : (const double*)dObs.p, (double*)dW.p};
+    return true;
+}
+
+// vigo_cost_grad of the one trajectory in hb; grad receives its 3 (N - 6) free scalars
+bool costGrad(vigo_handle_t h, const HostBatch& hb, double& cost, double* grad) {
+    static thread_local StagingBuf dCost, dGrad;
+    const size_t n = 3 * (size_t)(hb.N - 2 * bsplineDegree);
+    DeviceBatch d;
+    if (!uploadBatch(h, hb, d) || !dCost.alloc(8) || !dGrad.alloc(n * 8)) return false;
+    if (vigo_cost_grad(h, 1, hb.N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, (double*)dCost.p, (double*)dGrad.p, nullptr) != VIGO_OK)
+        return false;
+    return vigo_host::threadSync() && dCost.download(&cost, 8) && dGrad.download(grad, n * 8);
+}
 }  // namespace
 
 void bsplineTraj::solveBatch(const std::vector<bsplineTraj*>& ps) {
     // groups of equal N share a launch (vigo_optimize takes one N per call)
-    std::vector<bool> doneMask(ps.size(), false);
-    for (size_t a = 0; a < ps.size(); ++a) {
-        if (doneMask[a]) continue;
-        const int N = ps[a]->optData_.controlPoints.cols();
-        std::vector<bsplineTraj*> grp;
-        for (size_t b = a; b < ps.size(); ++b)
-            if (!doneMask[b] && ps[a]->sameBatchKey(*ps[b])) { grp.push_back(ps[b]); doneMask[b] = true; }
-        bsplineTraj* lead = grp[0];
-        for (auto* p : grp) p->lastStatus_ = VIGO_ERR_HIP;
-        if (N < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) continue;
-        HostBatch hb;
-        hb.B = (int)grp.size();
-        hb.N = N;
-        hb.goff.push_back(0);
-        hb.ooff.push_back(0);
-        for (auto* p : grp) {
-            const double* c = p->optData_.controlPoints.data();
-            hb.ctrl.insert(hb.ctrl.end(), c, c + 3 * N);
-            for (int i = 0; i < N; ++i) {
-                const size_t cnt = i < (int)p->optData_.guidePoints.size() ? p->optData_.guidePoints[i].size() : 0;
-                for (size_t j = 0; j < cnt; ++j) {
-                    const Eigen::Vector3d& g = p->optData_.guidePoints[i][j];
-                    const Eigen::Vector3d& v = p->optData_.guideDirections[i][j];
-                    for (int q = 0; q < 3; ++q) hb.gpv.push_back(g(q));
-                    for (int q = 0; q < 3; ++q) hb.gpv.push_back(v(q));
-                }
-                hb.goff.push_back((int32_t)(hb.gpv.size() / 6));
-            }
-            for (size_t j = 0; j < p->optData_.dynamicObstaclesPos.size(); ++j) {
-                for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesPos[j](q));
-                for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesVel[j](q));
-                for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesSize[j](q));
-            }
-            hb.ooff.push_back((int32_t)(hb.obs.size() / 9));
-            hb.weights.push_back(p->weightDistance_);
-            hb.weights.push_back(p->weightSmoothness_);
-            hb.weights.push_back(p->weightFeasibility_);
-            hb.weights.push_back(p->weightDynamicObstacle_);
+    auto same = [&](size_t a, size_t b) { return ps[a]->sameBatchKey(*ps[b]); };
+    vigo_host::forEachGroup(ps.size(), same, [&](const std::vector<size_t>& grp) {
+        bsplineTraj* lead = ps[grp[0]];
+        const int N = lead->optData_.controlPoints.cols();
+        for (size_t k : grp) ps[k]->lastStatus_ = VIGO_ERR_HIP;
+        if (N < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
+        HostBatch hb(N);
+        for (size_t k : grp) {
+            const bsplineTraj* p = ps[k];
+            hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
         }
-        const size_t G = hb.gpv.size() / 6;
-        // device staging buffers live across calls (one set per host thread): hipMalloc/hipFree per
-        // rebound round cost more than the round's kernels
-        static thread_local StagingBuf dCtrl, dGoff, dGpv, dGunk, dOoff, dObs, dW, dStatus;
-        bool ok = dCtrl.upload(hb.ctrl.data(), hb.ctrl.size() * 8) && dGoff.upload(hb.goff.data(), hb.goff.size() * 4) &&
-                  dGpv.upload(hb.gpv.data(), hb.gpv.size() * 8) && dGunk.alloc(G) && dOoff.upload(hb.ooff.data(), hb.ooff.size() * 4) &&
-                  dObs.upload(hb.obs.data(), hb.obs.size() * 8) && dW.upload(hb.weights.data(), hb.weights.size() * 8) &&
-                  dStatus.alloc(hb.B * 4);
-        if (!ok) continue;
-        vigo_handle_t h = lead->dev_;
-        // map_->isUnknown(guidePoint), BT.cpp:841, hoisted out of the solve
-        if (G && vigo_guides_unknown(h, (int64_t)G, (const double*)dGpv.p, (uint8_t*)dGunk.p) != VIGO_OK) continue;
-        if (vigo_optimize(h, hb.B, N, (double*)dCtrl.p, (const int32_t*)dGoff.p, G ? (const double*)dGpv.p : nullptr,
-                          G ? (const uint8_t*)dGunk.p : nullptr, (const int32_t*)dOoff.p,
-                          hb.obs.empty() ? nullptr : (const double*)dObs.p, 0, (const double*)dW.p, nullptr,
-                          (int32_t*)dStatus.p, nullptr, nullptr, nullptr) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_optimize failed: " << vigo_last_error(h) << endl;
-            continue;
+        static thread_local StagingBuf dStatus;
+        DeviceBatch d;
+        if (!uploadBatch(lead->dev_, hb, d) || !dStatus.alloc(hb.B * 4)) return;
+        if (vigo_optimize(lead->dev_, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr, (int32_t*)dStatus.p, nullptr,
+                          nullptr, nullptr) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_optimize failed: " << vigo_last_error(lead->dev_) << endl;
+            return;
         }
         std::vector<int32_t> status(hb.B);
-        if (!vigo_host::threadSync() || !dCtrl.download(hb.ctrl.data(), hb.ctrl.size() * 8) ||
+        if (!vigo_host::threadSync() || !vigo_host::download(hb.ctrl.data(), d.ctrl, hb.ctrl.size() * 8) ||
             !dStatus.download(status.data(), status.size() * 4))
-            continue;
+            return;
         for (int b = 0; b < hb.B; ++b) {
             // optData_.controlPoints = the last evaluated point, as costFunction leaves it (BT.cpp:803)
-            std::memcpy(grp[b]->optData_.controlPoints.data(), hb.ctrl.data() + (size_t)b * 3 * N, sizeof(double) * 3 * N);
-            grp[b]->lastStatus_ = status[b];
+            std::memcpy(ps[grp[b]]->optData_.controlPoints.data(), hb.ctrl.data() + (size_t)b * 3 * N, sizeof(double) * 3 * N);
+            ps[grp[b]]->lastStatus_ = status[b];
         }
-    }
+    });
 }
 
 void bsplineTraj::gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& col, std::vector<uint8_t>& dyn) {
     col.assign(ps.size(), 1);
     dyn.assign(ps.size(), 0);
-    std::vector<bool> doneMask(ps.size(), false);
-    for (size_t a = 0; a < ps.size(); ++a) {
-        if (doneMask[a]) continue;
-        const int N = ps[a]->optData_.controlPoints.cols();
-        std::vector<size_t> idx;
-        for (size_t b = a; b < ps.size(); ++b)
-            if (!doneMask[b] && ps[a]->sameBatchKey(*ps[b])) {
-                idx.push_back(b);
-                doneMask[b] = true;
-            }
-        bsplineTraj* lead = ps[a];
-        if (N < 4 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) continue;
+    auto same = [&](size_t a, size_t b) { return ps[a]->sameBatchKey(*ps[b]); };
+    vigo_host::forEachGroup(ps.size(), same, [&](const std::vector<size_t>& idx) {
+        bsplineTraj* lead = ps[idx[0]];
+        const int N = lead->optData_.controlPoints.cols();
+        if (N < 4 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
         std::vector<double> ctrl, obs;
         std::vector<int32_t> ooff{0};
         for (size_t b : idx) {
             const double* c = ps[b]->optData_.controlPoints.data();
             ctrl.insert(ctrl.end(), c, c + 3 * N);
-            for (size_t j = 0; j < ps[b]->optData_.dynamicObstaclesPos.size(); ++j) {
-                for (int q = 0; q < 3; ++q) obs.push_back(ps[b]->optData_.dynamicObstaclesPos[j](q));
-                for (int q = 0; q < 3; ++q) obs.push_back(ps[b]->optData_.dynamicObstaclesVel[j](q));
-                for (int q = 0; q < 3; ++q) obs.push_back(ps[b]->optData_.dynamicObstaclesSize[j](q));
-            }
+            vigo_host::appendObstacles(ps[b]->optData_, obs);
             ooff.push_back((int32_t)(obs.size() / 9));
         }
         const int B = (int)idx.size();
         static thread_local StagingBuf dCtrl, dFlag, dDyn, dOoff, dObs;
         if (!dCtrl.upload(ctrl.data(), ctrl.size() * 8) || !dFlag.alloc(B) || !dDyn.alloc(B) ||
             !dOoff.upload(ooff.data(), ooff.size() * 4) || !dObs.upload(obs.data(), obs.size() * 8))
-            continue;
+            return;
         const double dt = lead->map_->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
-        if (vigo_traj_collision(lead->dev_, B, N, (const double*)dCtrl.p, dt, (uint8_t*)dFlag.p, nullptr) != VIGO_OK) continue;
+        if (vigo_traj_collision(lead->dev_, B, N, (const double*)dCtrl.p, dt, (uint8_t*)dFlag.p, nullptr) != VIGO_OK) return;
         std::vector<uint8_t> f(B), d(B, 0);
         if (!obs.empty()) {
             if (vigo_traj_dynamic_collision(lead->dev_, B, N, (const double*)dCtrl.p, dt, (const int32_t*)dOoff.p,
                                             (const double*)dObs.p, 0, (uint8_t*)dDyn.p) != VIGO_OK)
-                continue;
+                return;
         }
-        if (!vigo_host::threadSync() || !dFlag.download(f.data(), B)) continue;
-        if (!obs.empty() && !dDyn.download(d.data(), B)) continue;
+        if (!vigo_host::threadSync() || !dFlag.download(f.data(), B)) return;
+        if (!obs.empty() && !dDyn.download(d.data(), B)) return;
         for (int b = 0; b < B; ++b) {
             col[idx[b]] = f[b];
             // BT.cpp:621-626: the dynamic gate only runs when the planner has obstacles
             dyn[idx[b]] = ps[idx[b]]->optData_.dynamicObstaclesPos.empty() ? 0 : d[b];
         }
-    }
+    });
 }
 
 namespace {
@@ -792,42 +774,16 @@ bool bsplineTraj::deviceResidentRebound() { return g_deviceResidentRebound.load(
 // BT.cpp:611-685 between two A* calls, on the device, for one group of planners (one batch): upload the planners'
 // state, queue the rounds (vigo_rebound_rounds), bring back what the host part of the loop needs.
 bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds) {
-    if (grp.empty()) return true;
     bsplineTraj* lead = grp[0];
     const int N = lead->optData_.controlPoints.cols();
     std::vector<int> prevStatus(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) { prevStatus[k] = grp[k]->lastStatus_; grp[k]->lastStatus_ = VIGO_ERR_HIP; }
     if (N < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return false;
-    HostBatch hb;
-    hb.B = (int)grp.size();
-    hb.N = N;
-    hb.goff.push_back(0);
-    hb.ooff.push_back(0);
+    HostBatch hb(N);
     std::vector<vigo_rebound_state_t> state(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) {
         bsplineTraj* p = grp[k];
-        const double* c = p->optData_.controlPoints.data();
-        hb.ctrl.insert(hb.ctrl.end(), c, c + 3 * N);
-        for (int i = 0; i < N; ++i) {
-            const size_t cnt = i < (int)p->optData_.guidePoints.size() ? p->optData_.guidePoints[i].size() : 0;
-            for (size_t j = 0; j < cnt; ++j) {
-                const Eigen::Vector3d& g = p->optData_.guidePoints[i][j];
-                const Eigen::Vector3d& v = p->optData_.guideDirections[i][j];
-                for (int q = 0; q < 3; ++q) hb.gpv.push_back(g(q));
-                for (int q = 0; q < 3; ++q) hb.gpv.push_back(v(q));
-            }
-            hb.goff.push_back((int32_t)(hb.gpv.size() / 6));
-        }
-        for (size_t j = 0; j < p->optData_.dynamicObstaclesPos.size(); ++j) {
-            for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesPos[j](q));
-            for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesVel[j](q));
-            for (int q = 0; q < 3; ++q) hb.obs.push_back(p->optData_.dynamicObstaclesSize[j](q));
-        }
-        hb.ooff.push_back((int32_t)(hb.obs.size() / 9));
-        hb.weights.push_back(p->weightDistance_);
-        hb.weights.push_back(p->weightSmoothness_);
-        hb.weights.push_back(p->weightFeasibility_);
-        hb.weights.push_back(p->weightDynamicObstacle_);
+        hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
         vigo_rebound_state_t& st = state[k];
         std::memset(&st, 0, sizeof(st));
         st.status = VIGO_RB_ACTIVE;
@@ -844,31 +800,26 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
             for (int q = 0; q < st.n_seg; ++q) { st.seg[2 * q] = p->collisionSeg_[q].first; st.seg[2 * q + 1] = p->collisionSeg_[q].second; }
         }
     }
-    const size_t G = hb.gpv.size() / 6;
-    static thread_local StagingBuf dCtrl, dGoff, dGpv, dGunk, dOoff, dObs, dW, dState;
-    bool ok = dCtrl.upload(hb.ctrl.data(), hb.ctrl.size() * 8) && dGoff.upload(hb.goff.data(), hb.goff.size() * 4) &&
-              dGpv.upload(hb.gpv.data(), hb.gpv.size() * 8) && dGunk.alloc(G) && dOoff.upload(hb.ooff.data(), hb.ooff.size() * 4) &&
-              dObs.upload(hb.obs.data(), hb.obs.size() * 8) && dW.upload(hb.weights.data(), hb.weights.size() * 8) &&
-              dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t));
-    if (!ok) return false;
+    static thread_local StagingBuf dState;
+    DeviceBatch d;
+    if (!uploadBatch(lead->dev_, hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t))) return false;
     vigo_handle_t h = lead->dev_;
-    if (G && vigo_guides_unknown(h, (int64_t)G, (const double*)dGpv.p, (uint8_t*)dGunk.p) != VIGO_OK) return false;
     const double dt = lead->map_->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
-    if (vigo_rebound_rounds(h, hb.B, N, (double*)dCtrl.p, (const int32_t*)dGoff.p, G ? (const double*)dGpv.p : nullptr,
-                            G ? (const uint8_t*)dGunk.p : nullptr, (const int32_t*)dOoff.p, hb.obs.empty() ? nullptr : (const double*)dObs.p, 0,
-                            (double*)dW.p, dt, lead->notCheckRatio_, maxRounds, (vigo_rebound_state_t*)dState.p) != VIGO_OK) {
+    if (vigo_rebound_rounds(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, dt, lead->notCheckRatio_, maxRounds,
+                            (vigo_rebound_state_t*)dState.p) != VIGO_OK) {
         cout << "[BsplineTraj]: vigo_rebound_rounds failed: " << vigo_last_error(h) << endl;
         return false;
     }
-    if (!vigo_host::threadSync() || !dCtrl.download(hb.ctrl.data(), hb.ctrl.size() * 8) ||
-        !dW.download(hb.weights.data(), hb.weights.size() * 8) || !dState.download(state.data(), state.size() * sizeof(vigo_rebound_state_t)))
+    // everything is read back here: the solveBatch of the overflow planners below reuses the staging buffers
+    if (!vigo_host::threadSync() || !vigo_host::download(hb.ctrl.data(), d.ctrl, hb.ctrl.size() * 8) ||
+        !vigo_host::download(hb.weights.data(), d.weights, hb.weights.size() * 8) ||
+        !dState.download(state.data(), state.size() * sizeof(vigo_rebound_state_t)))
         return false;
-    std::vector<bsplineTraj*> overflow;
-    std::vector<size_t> overflowAt;
+    std::vector<size_t> overflow;
     for (size_t k = 0; k < grp.size(); ++k) {
         bsplineTraj* p = grp[k];
         const vigo_rebound_state_t& st = state[k];
-        if (st.rounds == 0 && st.status == VIGO_RB_NEEDS_HOST) { overflow.push_back(p); overflowAt.push_back(k); continue; }
+        if (st.rounds == 0 && st.status == VIGO_RB_NEEDS_HOST) { overflow.push_back(k); continue; }
         // optData_.controlPoints = the last evaluated point, as costFunction leaves it (BT.cpp:803)
         std::memcpy(p->optData_.controlPoints.data(), hb.ctrl.data() + k * 3 * N, sizeof(double) * 3 * N);
         p->weightDistance_ = hb.weights[4 * k + 0];
@@ -883,9 +834,9 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
         rb[k]->gateDynamic = st.gate_dynamic != 0;
     }
     // planners the device state cannot represent: one host-driven round (solve if owed, gate; the caller steps)
-    for (size_t q = 0; q < overflow.size(); ++q) {
-        std::vector<bsplineTraj*> one{overflow[q]};
-        Rebound& r = *rb[overflowAt[q]];
+    for (size_t k : overflow) {
+        std::vector<bsplineTraj*> one{grp[k]};
+        Rebound& r = *rb[k];
         if (r.needOptimize) solveBatch(one);
         std::vector<uint8_t> col, dyn;
         gateBatch(one, col, dyn);
@@ -908,34 +859,10 @@ double bsplineTraj::costFunction(const double* x, double* grad, const int n) {
     const int N = optData_.controlPoints.cols();
     if (n != 3 * (N - 2 * bsplineDegree) || !syncDevice()) return std::nan("");
     std::memcpy(optData_.controlPoints.data() + 3 * bsplineDegree, x, n * sizeof(double));  // BT.cpp:803
-    std::vector<double> gpv, obs;
-    std::vector<int32_t> goff{0};
-    for (int i = 0; i < N; ++i) {
-        for (size_t j = 0; j < optData_.guidePoints[i].size(); ++j) {
-            for (int q = 0; q < 3; ++q) gpv.push_back(optData_.guidePoints[i][j](q));
-            for (int q = 0; q < 3; ++q) gpv.push_back(optData_.guideDirections[i][j](q));
-        }
-        goff.push_back((int32_t)(gpv.size() / 6));
-    }
-    for (size_t j = 0; j < optData_.dynamicObstaclesPos.size(); ++j) {
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesPos[j](q));
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesVel[j](q));
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesSize[j](q));
-    }
-    const size_t G = gpv.size() / 6;
-    DevBuf dCtrl, dGoff, dGpv, dGunk, dObs, dCost, dGrad;
-    if (!dCtrl.upload(optData_.controlPoints.data(), 3 * N * 8) || !dGoff.upload(goff.data(), goff.size() * 4) ||
-        !dGpv.upload(gpv.data(), gpv.size() * 8) || !dGunk.alloc(G) || !dObs.upload(obs.data(), obs.size() * 8) ||
-        !dCost.alloc(8) || !dGrad.alloc((size_t)n * 8))
-        return std::nan("");
-    if (G && vigo_guides_unknown(dev_, (int64_t)G, (const double*)dGpv.p, (uint8_t*)dGunk.p) != VIGO_OK) return std::nan("");
-    if (vigo_cost_grad(dev_, 1, N, (const double*)dCtrl.p, (const int32_t*)dGoff.p, G ? (const double*)dGpv.p : nullptr,
-                       G ? (const uint8_t*)dGunk.p : nullptr, nullptr, obs.empty() ? nullptr : (const double*)dObs.p,
-                       (int)(obs.size() / 9), nullptr, (double*)dCost.p, (double*)dGrad.p, nullptr) != VIGO_OK)
-        return std::nan("");
+    HostBatch hb(N);
+    hb.add(optData_.controlPoints.data(), optData_, {weightDistance_, weightSmoothness_, weightFeasibility_, weightDynamicObstacle_});
     double cost = 0;
-    if (!vigo_host::threadSync() || !dCost.download(&cost, 8) || !dGrad.download(grad, (size_t)n * 8)) return std::nan("");
-    return cost;
+    return costGrad(dev_, hb, cost, grad) ? cost : std::nan("");
 }
 
 // BT.cpp:796-800: the lbfgs_evaluate_t-shaped entry (instance pointer first)
@@ -951,35 +878,13 @@ bool bsplineTraj::termCost(int term, const Eigen::MatrixXd& controlPoints, doubl
     const int N = controlPoints.cols();
     gradient = Eigen::MatrixXd::Zero(3, N);
     if (N < 7 || N > VIGO_MAX_CTRL_POINTS || (int)optData_.guidePoints.size() < N || !syncDevice()) return false;
-    std::vector<double> gpv, obs, w(4, 0.0);
+    std::array<double, 4> w{};
     w[term] = 1.0;
-    std::vector<int32_t> goff{0};
-    for (int i = 0; i < N; ++i) {
-        for (size_t j = 0; j < optData_.guidePoints[i].size(); ++j) {
-            for (int q = 0; q < 3; ++q) gpv.push_back(optData_.guidePoints[i][j](q));
-            for (int q = 0; q < 3; ++q) gpv.push_back(optData_.guideDirections[i][j](q));
-        }
-        goff.push_back((int32_t)(gpv.size() / 6));
-    }
-    for (size_t j = 0; j < optData_.dynamicObstaclesPos.size(); ++j) {
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesPos[j](q));
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesVel[j](q));
-        for (int q = 0; q < 3; ++q) obs.push_back(optData_.dynamicObstaclesSize[j](q));
-    }
-    const size_t G = gpv.size() / 6;
-    const int n = 3 * (N - 2 * bsplineDegree);
-    DevBuf dCtrl, dGoff, dGpv, dGunk, dObs, dW, dCost, dGrad;
-    if (!dCtrl.upload(controlPoints.data(), 3 * N * 8) || !dGoff.upload(goff.data(), goff.size() * 4) || !dGpv.upload(gpv.data(), gpv.size() * 8) ||
-        !dGunk.alloc(G) || !dObs.upload(obs.data(), obs.size() * 8) || !dW.upload(w.data(), 32) || !dCost.alloc(8) || !dGrad.alloc((size_t)n * 8))
-        return false;
-    if (G && vigo_guides_unknown(dev_, (int64_t)G, (const double*)dGpv.p, (uint8_t*)dGunk.p) != VIGO_OK) return false;
-    if (vigo_cost_grad(dev_, 1, N, (const double*)dCtrl.p, (const int32_t*)dGoff.p, G ? (const double*)dGpv.p : nullptr,
-                       G ? (const uint8_t*)dGunk.p : nullptr, nullptr, obs.empty() ? nullptr : (const double*)dObs.p, (int)(obs.size() / 9),
-                       (const double*)dW.p, (double*)dCost.p, (double*)dGrad.p, nullptr) != VIGO_OK)
-        return false;
-    std::vector<double> g(n);
-    if (!vigo_host::threadSync() || !dCost.download(&cost, 8) || !dGrad.download(g.data(), (size_t)n * 8)) return false;
-    std::memcpy(gradient.data() + 3 * bsplineDegree, g.data(), (size_t)n * 8);
+    HostBatch hb(N);
+    hb.add(controlPoints.data(), optData_, w);
+    std::vector<double> g(3 * (N - 2 * bsplineDegree));
+    if (!costGrad(dev_, hb, cost, g.data())) return false;
+    std::memcpy(gradient.data() + 3 * bsplineDegree, g.data(), g.size() * 8);
     return true;
 }
 // BT.cpp:823-932, :934-950, :952-999, :1001-1064
@@ -1104,57 +1009,85 @@ thread_local bool t_insidePipeline = false;
 }  // namespace
 void bsplineTraj::setBatchPipelineThreshold(size_t planners) { g_pipelineThreshold.store(planners); }
 
+// one unsplit makePlanBatch call: per planner (index into the call's planners) its loop state and result; the planners
+// still in the loop, in call order, with their indices
+struct bsplineTraj::PlanBatch {
+    std::vector<Rebound> rb;
+    std::vector<bool> result;
+    std::vector<bsplineTraj*> active;
+    std::vector<size_t> activeIdx;
+    std::atomic<long long> nsSeg{0}, nsAstar{0}, nsGuide{0};   // prologue CPU time summed over the worker threads
+    explicit PlanBatch(size_t P) : rb(P), result(P, false) {}
+};
+
 // BT.cpp:333-385 for many planners at once: host prologue per planner, then the rebound loops in
 // lock-step so each optimize() round is one launch over all still-active planners.
 std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners) {
     const size_t P = planners.size();
-    // A large batch runs as two to four pipelined parts of >= threshold / 2 planners, all but the first on companion
-    // host threads with their own handles and HIP streams: while one part waits for its device rounds (a chain of
-    // single-wave solves, ~10 ms per 1024 planners) the others' host work (A*, guide assignment) and device rounds
-    // proceed — what a caller otherwise gets only by planning from several threads of its own.  Planners are independent
-    // (per-trajectory results do not depend on which batch carries them), so the plans are those of the unsplit call.
     const size_t threshold = g_pipelineThreshold.load();
-    if (!t_insidePipeline && threshold > 0 && P >= threshold && P >= 2) {
-        constexpr size_t kMaxParts = 4;
-        static thread_local Companion companions[kMaxParts - 1];
-        const size_t per = threshold / 2 > 0 ? threshold / 2 : 1;
-        const size_t parts = std::min(kMaxParts, std::max<size_t>(2, P / per));
-        std::vector<std::vector<bsplineTraj*>> piece(parts);
-        std::vector<std::vector<bool>> res(parts);
-        for (size_t k = 0; k < parts; ++k) {
-            const size_t lo = P * k / parts, hi = P * (k + 1) / parts;
-            piece[k].assign(planners.begin() + lo, planners.begin() + hi);
-            res[k].assign(hi - lo, false);
-        }
-        for (size_t k = 1; k < parts; ++k) {
-            companions[k - 1].start([&piece, &res, k]() {
-                t_insidePipeline = true;
-                res[k] = bsplineTraj::makePlanBatch(piece[k]);
-            });
-        }
-        t_insidePipeline = true;
-        try {
-            res[0] = bsplineTraj::makePlanBatch(piece[0]);
-        } catch (...) {
-            t_insidePipeline = false;
-            for (size_t k = 1; k < parts; ++k) companions[k - 1].wait();
-            throw;
-        }
-        t_insidePipeline = false;
-        for (size_t k = 1; k < parts; ++k) companions[k - 1].wait();
-        std::vector<bool> all;
-        for (size_t k = 0; k < parts; ++k) all.insert(all.end(), res[k].begin(), res[k].end());
-        return all;
-    }
-    std::vector<bool> result(P, false);
-    std::vector<Rebound> rb(P);
-    std::vector<bsplineTraj*> active;
-    std::vector<size_t> activeIdx;
-    // steps 1-3 (collision segments, A*, guide assignment) touch only the planner's own state and the
-    // read-only map: the planners are spread over the host cores
+    if (!t_insidePipeline && threshold > 0 && P >= threshold && P >= 2) return makePlanPipelined(planners, threshold);
+    PlanBatch pb(P);
+    const bool timing = getenv("VIGO_FACADE_TIMING") != nullptr;
     const double tp0 = wallSeconds();
+    planPrologue(planners, pb);
+    const double tp1 = wallSeconds();
+    // step 4: rebound loops.  The 30 ms budget of BT.cpp:633 is per makePlan() call in the
+    // reference; a batch keeps it per round so one slow planner cannot starve the others.
+    if (deviceResidentRebound()) reboundOnDevice(pb, timing);
+    else reboundFromHost(pb, timing);
+    const double tp2 = wallSeconds();
+    planEpilogue(planners, pb.result);
+    if (timing) {
+        cout << "[BsplineTraj]: prologue CPU time summed over the workers: findCollisionSeg " << pb.nsSeg.load() * 1e-6 << " ms, A* "
+             << pb.nsAstar.load() * 1e-6 << " ms, guide assignment " << pb.nsGuide.load() * 1e-6 << " ms" << endl;
+        cout << "[BsplineTraj]: makePlanBatch of " << P << ": prologue " << (tp1 - tp0) * 1e3 << " ms, rebound loop " << (tp2 - tp1) * 1e3
+             << " ms, epilogue " << (wallSeconds() - tp2) * 1e3 << " ms" << endl;
+    }
+    return pb.result;
+}
+
+// A large batch runs as two to four pipelined parts of >= threshold / 2 planners, all but the first on companion
+// host threads with their own handles and HIP streams: while one part waits for its device rounds (a chain of
+// single-wave solves, ~10 ms per 1024 planners) the others' host work (A*, guide assignment) and device rounds
+// proceed — what a caller otherwise gets only by planning from several threads of its own.  Planners are independent
+// (per-trajectory results do not depend on which batch carries them), so the plans are those of the unsplit call.
+std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold) {
+    constexpr size_t kMaxParts = 4;
+    static thread_local Companion companions[kMaxParts - 1];
+    const size_t P = planners.size();
+    const size_t per = threshold / 2 > 0 ? threshold / 2 : 1;
+    const size_t parts = std::min(kMaxParts, std::max<size_t>(2, P / per));
+    std::vector<std::vector<bsplineTraj*>> piece(parts);
+    std::vector<std::vector<bool>> res(parts);
+    for (size_t k = 0; k < parts; ++k) {
+        const size_t lo = P * k / parts, hi = P * (k + 1) / parts;
+        piece[k].assign(planners.begin() + lo, planners.begin() + hi);
+        res[k].assign(hi - lo, false);
+    }
+    for (size_t k = 1; k < parts; ++k) {
+        companions[k - 1].start([&piece, &res, k]() {
+            t_insidePipeline = true;
+            res[k] = bsplineTraj::makePlanBatch(piece[k]);
+        });
+    }
+    // the jobs hold piece and res: every part has ended before an exception leaves (the first one in part order)
+    std::exception_ptr err;
+    t_insidePipeline = true;
+    try { res[0] = bsplineTraj::makePlanBatch(piece[0]); } catch (...) { err = std::current_exception(); }
+    t_insidePipeline = false;
+    for (size_t k = 1; k < parts; ++k)
+        try { companions[k - 1].wait(); } catch (...) { if (!err) err = std::current_exception(); }
+    if (err) std::rethrow_exception(err);
+    std::vector<bool> all;
+    for (size_t k = 0; k < parts; ++k) all.insert(all.end(), res[k].begin(), res[k].end());
+    return all;
+}
+
+// steps 1-3 (collision segments, A*, guide assignment) touch only the planner's own state and the read-only map: the
+// planners are spread over the host cores.  Those that get through enter the rebound loop.
+void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb) {
+    const size_t P = planners.size();
     std::vector<uint8_t> prepared(P, 0);
-    std::atomic<long long> nsSeg{0}, nsAstar{0}, nsGuide{0};   // (summed over the worker threads; printed with VIGO_FACADE_TIMING)
     parallelFor(P, [&](size_t i) {
         bsplineTraj* p = planners[i];
         if (!p->init_ || !p->map_) return;
@@ -1163,11 +1096,11 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
         const double t1 = wallSeconds();
         const bool found = p->pathSearch(p->collisionSeg_, p->astarPaths_);         // step 2
         const double t2 = wallSeconds();
-        nsSeg += (long long)((t1 - t0) * 1e9);
-        nsAstar += (long long)((t2 - t1) * 1e9);
+        pb.nsSeg += (long long)((t1 - t0) * 1e9);
+        pb.nsAstar += (long long)((t2 - t1) * 1e9);
         if (!found) return;
         p->assignGuidePointsSemiCircle(p->astarPaths_, p->collisionSeg_);           // step 3
-        nsGuide += (long long)((wallSeconds() - t2) * 1e9);
+        pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
         prepared[i] = 1;
     });
     for (size_t i = 0; i < P; ++i) {
@@ -1177,93 +1110,73 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
             cout << "[BsplineTraj]: Fail because of A* failure." << endl;
             continue;
         }
-        p->reboundBegin(rb[i]);
-        active.push_back(p);
-        activeIdx.push_back(i);
+        p->reboundBegin(pb.rb[i]);
+        pb.active.push_back(p);
+        pb.activeIdx.push_back(i);
     }
-    const double tp1 = wallSeconds();
-    // step 4: rebound loops.  The 30 ms budget of BT.cpp:633 is per makePlan() call in the
-    // reference; a batch keeps it per round so one slow planner cannot starve the others.
-    const bool timing = getenv("VIGO_FACADE_TIMING") != nullptr;
-    if (deviceResidentRebound()) {
-        // The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,
-        // weight doubling and re-solve are queued for up to kRounds rounds without a host round trip; the host only sees
-        // the planners that are done, need A* (re-guide, or failCount >= 4) or ran out of queued rounds.
-        const int kRounds = 4;   // failCount reaches 4 after at most four device rounds: then every round needs A*
-        const double t0 = wallSeconds();
-        const double budget = 0.03 * std::max<size_t>(1, active.size());
-        while (!active.empty()) {
-            const double tr0 = wallSeconds();
-            // one device batch per group of planners the lead's handle state fits
-            std::vector<bool> grouped(active.size(), false);
-            std::vector<uint8_t> devOk(active.size(), 0);
+}
+
+// The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,
+// weight doubling and re-solve are queued for up to kRounds rounds without a host round trip; the host only sees
+// the planners that are done, need A* (re-guide, or failCount >= 4) or ran out of queued rounds.
+void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
+    const int kRounds = 4;   // failCount reaches 4 after at most four device rounds: then every round needs A*
+    std::vector<bsplineTraj*>& active = pb.active;
+    auto same = [&](size_t a, size_t b) { return active[a]->sameBatchKey(*active[b]); };
+    const double t0 = wallSeconds();
+    const double budget = 0.03 * std::max<size_t>(1, active.size());
+    while (!active.empty()) {
+        const double tr0 = wallSeconds();
+        // one device batch per group of planners the lead's handle state fits
+        std::vector<uint8_t> devOk(active.size(), 0);
+        vigo_host::forEachGroup(active.size(), same, [&](const std::vector<size_t>& members) {
+            std::vector<bsplineTraj*> grp;
+            std::vector<Rebound*> grb;
+            for (size_t m : members) {
+                grp.push_back(active[m]);
+                grb.push_back(&pb.rb[pb.activeIdx[m]]);
+            }
+            const bool ok = deviceRounds(grp, grb, kRounds);
+            for (size_t m : members) devOk[m] = ok ? 1 : 0;
+        });
+        const double tr1 = wallSeconds();
+        const bool timedOut = wallSeconds() - t0 > budget;
+        if (timedOut) {
+            // BT.cpp:633-637: out of time.  The reference tests the budget right after the gates: the planners still
+            // in the loop get one more gate (a trajectory that is collision free by now succeeds), the rest fail.
+            // (gateBatch forms the same device batches as the rounds above)
+            std::vector<uint8_t> col, dyn;
+            gateBatch(active, col, dyn);
             for (size_t a = 0; a < active.size(); ++a) {
-                if (grouped[a]) continue;
-                std::vector<bsplineTraj*> grp;
-                std::vector<Rebound*> grb;
-                std::vector<size_t> members;
-                for (size_t b = a; b < active.size(); ++b)
-                    if (!grouped[b] && active[a]->sameBatchKey(*active[b])) {
-                        grp.push_back(active[b]);
-                        grb.push_back(&rb[activeIdx[b]]);
-                        members.push_back(b);
-                        grouped[b] = true;
-                    }
-                const bool ok = deviceRounds(grp, grb, kRounds);
-                for (size_t m : members) devOk[m] = ok ? 1 : 0;
+                Rebound& r = pb.rb[pb.activeIdx[a]];
+                if (r.devStatus == VIGO_RB_DONE) continue;
+                r.devStatus = (!col[a] && !dyn[a] && devOk[a]) ? VIGO_RB_DONE : VIGO_RB_NEEDS_HOST;
+                r.gateStatic = col[a] != 0;
+                r.gateDynamic = dyn[a] != 0;
             }
-            const double tr1 = wallSeconds();
-            const bool timedOut = wallSeconds() - t0 > budget;
-            if (timedOut) {
-                // BT.cpp:633-637: out of time.  The reference tests the budget right after the gates: the planners still
-                // in the loop get one more gate (a trajectory that is collision free by now succeeds), the rest fail.
-                std::vector<bool> g2(active.size(), false);
-                for (size_t a = 0; a < active.size(); ++a) {
-                    if (g2[a]) continue;
-                    std::vector<bsplineTraj*> grp;
-                    std::vector<size_t> members;
-                    for (size_t b = a; b < active.size(); ++b)
-                        if (!g2[b] && active[a]->sameBatchKey(*active[b])) { grp.push_back(active[b]); members.push_back(b); g2[b] = true; }
-                    std::vector<uint8_t> col, dyn;
-                    gateBatch(grp, col, dyn);
-                    for (size_t m = 0; m < members.size(); ++m) {
-                        Rebound& r = rb[activeIdx[members[m]]];
-                        if (r.devStatus == VIGO_RB_DONE) continue;
-                        r.devStatus = (!col[m] && !dyn[m] && devOk[members[m]]) ? VIGO_RB_DONE : VIGO_RB_NEEDS_HOST;
-                        r.gateStatic = col[m] != 0;
-                        r.gateDynamic = dyn[m] != 0;
-                    }
-                }
-            }
-            size_t nHost = 0;
-            for (size_t a = 0; a < active.size(); ++a) nHost += rb[activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
-            parallelFor(active.size(), [&](size_t a) {
-                Rebound& r = rb[activeIdx[a]];
-                bsplineTraj* p = active[a];
-                if (!devOk[a]) { p->reboundFinish(r, false); return; }             // no device: nothing to plan with
-                if (r.devStatus == VIGO_RB_DONE) p->reboundFinish(r, true);          // BT.cpp:628-631
-                else if (r.devStatus == VIGO_RB_NEEDS_HOST) p->reboundStep(r, r.gateStatic, r.gateDynamic, timedOut);   // A* and the rest of the pass
-                // (still active: its next step is the gate, or the optimize() the device left for the next call)
-            });
-            std::vector<bsplineTraj*> next;
-            std::vector<size_t> nextIdx;
-            for (size_t a = 0; a < active.size(); ++a) {
-                Rebound& r = rb[activeIdx[a]];
-                if (r.done) {
-                    result[activeIdx[a]] = r.ok;
-                    if (!r.ok) cout << "[BsplineTraj]: Fail because of optimizer not finding a solution." << endl;
-                } else {
-                    next.push_back(active[a]);
-                    nextIdx.push_back(activeIdx[a]);
-                }
-            }
-            if (timing)
-                cout << "[BsplineTraj]:   device rounds (<= " << kRounds << ") of " << active.size() << ": " << (tr1 - tr0) * 1e3 << " ms, host step of "
-                     << nHost << " planners " << (wallSeconds() - tr1) * 1e3 << " ms, " << next.size() << " continue" << endl;
-            active.swap(next);
-            activeIdx.swap(nextIdx);
         }
-    } else {
+        size_t nHost = 0;
+        for (size_t a = 0; a < active.size(); ++a) nHost += pb.rb[pb.activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
+        parallelFor(active.size(), [&](size_t a) {
+            Rebound& r = pb.rb[pb.activeIdx[a]];
+            bsplineTraj* p = active[a];
+            if (!devOk[a]) { p->reboundFinish(r, false); return; }             // no device: nothing to plan with
+            if (r.devStatus == VIGO_RB_DONE) p->reboundFinish(r, true);          // BT.cpp:628-631
+            else if (r.devStatus == VIGO_RB_NEEDS_HOST) p->reboundStep(r, r.gateStatic, r.gateDynamic, timedOut);   // A* and the rest of the pass
+            // (still active: its next step is the gate, or the optimize() the device left for the next call)
+        });
+        const size_t n = active.size();
+        retireFinished(pb);
+        if (timing)
+            cout << "[BsplineTraj]:   device rounds (<= " << kRounds << ") of " << n << ": " << (tr1 - tr0) * 1e3 << " ms, host step of "
+                 << nHost << " planners " << (wallSeconds() - tr1) * 1e3 << " ms, " << active.size() << " continue" << endl;
+    }
+}
+
+// The same loop driven round by round from the host (gates, one pass of the loop body, solve); the reference the
+// device-resident loop is tested against.
+void bsplineTraj::reboundFromHost(PlanBatch& pb, bool timing) {
+    std::vector<bsplineTraj*>& active = pb.active;
     double tr0 = wallSeconds();
     solveBatch(active);
     if (timing) cout << "[BsplineTraj]:   first solve of " << active.size() << ": " << (wallSeconds() - tr0) * 1e3 << " ms" << endl;
@@ -1275,46 +1188,49 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
         gateBatch(active, col, dyn);
         const double tr1 = wallSeconds();
         const bool timedOut = wallSeconds() - t0 > budget;
-        std::vector<bsplineTraj*> next, solve;
-        std::vector<size_t> nextIdx;
         // one pass of the loop body per planner (validation outcome -> re-guide / weight doubling, BT.cpp:619-681):
         // planner-local, incl. the A* of a re-guide, so spread over the host cores
-        parallelFor(active.size(), [&](size_t a) { active[a]->reboundStep(rb[activeIdx[a]], col[a] != 0, dyn[a] != 0, timedOut); });
-        for (size_t a = 0; a < active.size(); ++a) {
-            Rebound& r = rb[activeIdx[a]];
-            if (r.done) {
-                result[activeIdx[a]] = r.ok;
-                if (!r.ok) cout << "[BsplineTraj]: Fail because of optimizer not finding a solution." << endl;
-            } else {
-                next.push_back(active[a]);
-                nextIdx.push_back(activeIdx[a]);
-                if (r.needOptimize) solve.push_back(active[a]);
-            }
-        }
+        parallelFor(active.size(), [&](size_t a) { active[a]->reboundStep(pb.rb[pb.activeIdx[a]], col[a] != 0, dyn[a] != 0, timedOut); });
+        const size_t n = active.size();
+        retireFinished(pb);
+        std::vector<bsplineTraj*> solve;
+        for (size_t a = 0; a < active.size(); ++a)
+            if (pb.rb[pb.activeIdx[a]].needOptimize) solve.push_back(active[a]);
         const double tr2 = wallSeconds();
         solveBatch(solve);
         if (timing)
-            cout << "[BsplineTraj]:   round of " << active.size() << ": gates " << (tr1 - tr0) * 1e3 << " ms, rebound step " << (tr2 - tr1) * 1e3
+            cout << "[BsplineTraj]:   round of " << n << ": gates " << (tr1 - tr0) * 1e3 << " ms, rebound step " << (tr2 - tr1) * 1e3
                  << " ms, solve of " << solve.size() << " " << (wallSeconds() - tr2) * 1e3 << " ms" << endl;
-        active.swap(next);
-        activeIdx.swap(nextIdx);
     }
+}
+
+// the planners whose loop has ended leave the active set; their result is the loop's
+void bsplineTraj::retireFinished(PlanBatch& pb) {
+    std::vector<bsplineTraj*> next;
+    std::vector<size_t> nextIdx;
+    for (size_t a = 0; a < pb.active.size(); ++a) {
+        const Rebound& r = pb.rb[pb.activeIdx[a]];
+        if (r.done) {
+            pb.result[pb.activeIdx[a]] = r.ok;
+            if (!r.ok) cout << "[BsplineTraj]: Fail because of optimizer not finding a solution." << endl;
+        } else {
+            next.push_back(pb.active[a]);
+            nextIdx.push_back(pb.activeIdx[a]);
+        }
     }
-    const double tp2 = wallSeconds();
+    pb.active.swap(next);
+    pb.activeIdx.swap(nextIdx);
+}
+
+// steps 5-6 for the planners that succeeded
+void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result) {
     std::vector<uint8_t> okv(result.begin(), result.end());
-    parallelFor(P, [&](size_t i) {
+    parallelFor(planners.size(), [&](size_t i) {
         if (!okv[i]) return;
         bsplineTraj* p = planners[i];
         p->bspline_ = trajPlanner::bspline(bsplineDegree, p->optData_.controlPoints, p->controlPointsTs_);  // step 5
         p->linearFeasibilityReparam();                                                                  // step 6
     });
-    if (getenv("VIGO_FACADE_TIMING"))
-        cout << "[BsplineTraj]: prologue CPU time summed over the workers: findCollisionSeg " << nsSeg.load() * 1e-6 << " ms, A* " << nsAstar.load() * 1e-6
-             << " ms, guide assignment " << nsGuide.load() * 1e-6 << " ms" << endl;
-    if (getenv("VIGO_FACADE_TIMING"))
-        cout << "[BsplineTraj]: makePlanBatch of " << P << ": prologue " << (tp1 - tp0) * 1e3 << " ms, rebound loop " << (tp2 - tp1) * 1e3
-             << " ms, epilogue " << (wallSeconds() - tp2) * 1e3 << " ms" << endl;
-    return result;
 }
 
 // BT.cpp:754-793 — including the function-static previous goal distance shared by all instances

@@ -11,10 +11,12 @@
 #include <trajectory_planner/polyTrajOctomap.h>
 #include <trajectory_planner/polyTrajSolver.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <mutex>
 
+#include "batchLayout.h"
 #include "workerPool.h"
 
 extern "C" {
@@ -97,17 +99,12 @@ int vigo_host_bspline_prologue(const unsigned char* vox, const int* dims, const 
     if (2 * (int)seg.size() > cap) return -2;
     *n_seg = (int)seg.size();
     for (size_t i = 0; i < seg.size(); ++i) { seg_out[2 * i] = seg[i].first; seg_out[2 * i + 1] = seg[i].second; }
-    const trajPlanner::optData& od = bt.getOptData();
-    int g = 0;
-    for (int i = 0; i < N; ++i) {
-        guide_off[i] = g;
-        for (size_t j = 0; j < od.guidePoints[i].size(); ++j) {
-            if (6 * (g + 1) > cap) return -2;
-            for (int k = 0; k < 3; ++k) { guide_out[6 * g + k] = od.guidePoints[i][j](k); guide_out[6 * g + 3 + k] = od.guideDirections[i][j](k); }
-            ++g;
-        }
-    }
-    guide_off[N] = g;
+    std::vector<int32_t> off{0};
+    std::vector<double> pv;
+    vigo_host::appendGuides(bt.getOptData(), N, off, pv);
+    if ((long long)pv.size() > cap) return -2;
+    std::copy(off.begin(), off.end(), guide_off);
+    std::copy(pv.begin(), pv.end(), guide_out);
     int q = 0;
     for (size_t i = 0; i < paths.size(); ++i) {
         path_off[i] = q;
@@ -283,20 +280,6 @@ void initPool(PlannerPool& pool, const unsigned char* vox, const int* dims, cons
     pool.nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
     pool.nh.setParam("bspline_traj/max_path_length", 1000.0);
 }
-
-// guide pairs of one planner, control point by control point in push order, into one trajectory's slot of the
-// per-trajectory staging (cnt[N], pairs appended to pv)
-void collectGuides(const trajPlanner::optData& od, int N, std::vector<int>& cnt, std::vector<double>& pv) {
-    cnt.assign(N, 0);
-    pv.clear();
-    for (int i = 0; i < N; ++i) {
-        cnt[i] = (int)od.guidePoints[i].size();
-        for (size_t j = 0; j < od.guidePoints[i].size(); ++j) {
-            for (int k = 0; k < 3; ++k) pv.push_back(od.guidePoints[i][j](k));
-            for (int k = 0; k < 3; ++k) pv.push_back(od.guideDirections[i][j](k));
-        }
-    }
-}
 }  // namespace
 
 extern "C" {
@@ -314,13 +297,13 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
     if (n < 0 || N < 7 || (!path_xyz && !ctrl_in)) return -1;
     PlannerPool pool;
     initPool(pool, vox, dims, origin, res, cfg);
-    std::vector<std::vector<int>> cnt(n);
+    std::vector<std::vector<int32_t>> off(n);     // per planner: N + 1 offsets of its own pairs
     std::vector<std::vector<double>> pv(n);
     vigo_host::parallelFor((size_t)n, [&](size_t t) {
         auto bt = pool.take();
         status[t] = 0;
         n_seg[t] = 0;
-        cnt[t].assign(N, 0);
+        off[t].assign(1, 0);
         bool have = true;
         if (ctrl_in) {
             Eigen::MatrixXd c(3, N);
@@ -349,14 +332,17 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
             } else {
                 bt->assignGuidePointsSemiCircle(paths, seg);
                 n_seg[t] = (int)seg.size();
-                collectGuides(bt->getOptData(), N, cnt[t], pv[t]);
+                vigo_host::appendGuides(bt->getOptData(), N, off[t], pv[t]);
             }
         }
+        off[t].resize((size_t)N + 1, 0);              // (no pairs: the prologue did not get that far)
         pool.give(std::move(bt));
     });
     long long g = 0;
-    for (int t = 0; t < n; ++t)
-        for (int i = 0; i < N; ++i) { guide_off[(size_t)t * N + i] = (int)g; g += cnt[t][i]; }
+    for (int t = 0; t < n; ++t) {
+        for (int i = 0; i < N; ++i) guide_off[(size_t)t * N + i] = (int)(g + off[t][i]);
+        g += off[t][N];
+    }
     guide_off[(size_t)n * N] = (int)g;
     if (g > cap_pairs) return -2;
     long long w = 0;

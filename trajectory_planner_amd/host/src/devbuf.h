@@ -30,6 +30,10 @@ inline hipStream_t threadStream() {
     return s[d];
 }
 inline bool threadSync() { return hipStreamSynchronize(threadStream()) == hipSuccess; }
+// device -> host on the thread's stream, complete on return
+inline bool download(void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, threadStream()) == hipSuccess && threadSync();
+}
 
 // RAII device buffer; every HIP failure is reported to the caller as `false`
 struct DevBuf {
@@ -62,9 +66,7 @@ struct DevBuf {
         dev = cur;
         return true;
     }
-    bool download(void* dst, size_t bytes) const {
-        return hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, threadStream()) == hipSuccess && threadSync();
-    }
+    bool download(void* dst, size_t bytes) const { return vigo_host::download(dst, p, bytes); }
 };
 
 // thread-lifetime staging buffer (declare `static thread_local`): grows on demand, is reused by every later call

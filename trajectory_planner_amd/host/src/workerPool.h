@@ -119,7 +119,7 @@ private:
 
 // A further host thread kept by a caller of bsplineTraj::makePlanBatch for the batches it splits into pipelined parts: it
 // lives as long as the calling thread, so its HIP stream, staging buffers and worker pool (all thread_local) are created
-// once.  start() hands it one job, wait() returns when that job has run (an exception inside a job ends the job).
+// once.  start() hands it one job, wait() returns when that job has run and rethrows the exception that ended it, if any.
 // tools/tsan_worker_pool.sh runs it under ThreadSanitizer.
 class Companion {
 public:
@@ -141,8 +141,14 @@ public:
         cv_.notify_all();
     }
     void wait() {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [this]() { return !busy_; });
+        std::exception_ptr err;
+        {
+            std::unique_lock<std::mutex> lk(m_);
+            cv_.wait(lk, [this]() { return !busy_; });
+            err = error_;
+            error_ = nullptr;
+        }
+        if (err) std::rethrow_exception(err);
     }
 
 private:
@@ -156,9 +162,11 @@ private:
                 job = std::move(job_);
                 job_ = nullptr;
             }
-            try { job(); } catch (...) { }      // (makePlanBatch reports failure through its result vector)
+            std::exception_ptr err;
+            try { job(); } catch (...) { err = std::current_exception(); }     // handed to wait()
             {
                 std::lock_guard<std::mutex> lk(m_);
+                error_ = std::move(err);     // (no reference stays on this thread once wait() can see it)
                 busy_ = false;
             }
             cv_.notify_all();
@@ -168,6 +176,7 @@ private:
     std::condition_variable cv_;
     std::function<void()> job_;
     bool busy_ = false, stop_ = false;
+    std::exception_ptr error_;           // thrown by the job wait() has not yet returned from
     std::thread th_;
 };
 

@@ -124,6 +124,16 @@ int main() {
         for (int k = 0; k < n; ++k) gerr = std::fmax(gerr, std::fabs(gd.data()[9 + k] + gs.data()[9 + k] + gf.data()[9 + k] + go.data()[9 + k] - g[k]));
         CHECK(std::fabs(cd + cs + cf + co - f0) <= 1e-12 * std::fmax(1.0, f0) && gerr <= 1e-12 * std::fmax(1.0, f0) && cs > 0, "getDistance/Smoothness/Feasibility/DynamicObstacleCost sum to costFunction");
         CHECK(bsplineTraj::solverCostFunction(&bst, x.data(), gp.data(), n) == f0, "solverCostFunction is the lbfgs_evaluate_t-shaped costFunction");
+        // clear() leaves no guide lists at all, setControlPoints() N empty ones: both mean "no guides"
+        std::vector<double> gc(n), ge(n);
+        bst.clear();
+        const double fc = bst.costFunction(x.data(), gc.data(), n);
+        bst.setControlPoints(c1);
+        const double fe = bst.costFunction(x.data(), ge.data(), n);
+        bool finite = std::isfinite(fc);
+        for (double v : gc) finite = finite && std::isfinite(v);
+        CHECK(finite && std::memcmp(&fc, &fe, sizeof(double)) == 0 && std::memcmp(gc.data(), ge.data(), sizeof(double) * n) == 0,
+              "costFunction without guide lists (after clear()) == with N empty guide lists (bit for bit)");
     }
 
     // a goal inside an obstacle is refused (BT.cpp:291-295)
