@@ -40,6 +40,12 @@ int main(int argc, char** argv) {
         const bool ok = s.solve();
         if (ok) { std::vector<pose> tr; s.getTrajectory(tr, 0.1); if (tr.empty()) ++fails; }
     }
+    // a piecewise polynomial whose coefficients do not fit its knots: the default pose, nothing read past the short vector
+    {
+        const std::vector<double> knots{0.0, 3.0, 6.0}, shortX(10, 1.0), full(16, 1.0);
+        for (double t = 0; t <= 6.0; t += 0.5)
+            if (polyTrajSolver::evalPiecewise(7, knots, shortX, full, full, t).x != 0) ++fails;
+    }
     // B-spline fit + evaluation
     for (int K = 4; K < 70; K += 7) {
         std::vector<Eigen::Vector3d> pts, cond(4, Eigen::Vector3d(0.1, -0.2, 0.0));

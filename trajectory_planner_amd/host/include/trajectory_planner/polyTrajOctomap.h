@@ -52,9 +52,16 @@ private:
     int lastIterations_ = 0;
     bool syncDevice();
     bool sweepPoints(const std::vector<pose>& pts, std::vector<uint8_t>& flags);
+    bool sweepXyz(const std::vector<double>& xyz, std::vector<uint8_t>& flags);
     void pwlPlan(std::vector<pose>& trajectory, double delT);
-    pose extPose(double t);
     const std::vector<double>& timeKnots();
+    /* the planning loop of PO.cpp:259-545 in steps, driven by planOnHost and makePlanBatch (polyTrajOctomap.cpp) */
+    struct PlanState;
+    PlanState begin(bool addingWaypoints);
+    void solveOnHost(PlanState& s);
+    bool advance(PlanState& s, const uint8_t* flags, size_t n, double delT);
+    void finish(std::vector<pose>& trajectory, double delT);
+    void planOnHost(bool addingWaypoints, std::vector<pose>& trajectory, double delT);
 
 public:
     polyTrajOctomap();
@@ -75,15 +82,17 @@ public:
     void setSolution(int polyDegree, const std::vector<double>& xSol, const std::vector<double>& ySol,
                      const std::vector<double>& zSol, const std::vector<double>& timeKnot);
 
-    /* makePlan() of many planners in lock-step (corridor-constraint mode, PO.cpp:388-545): per round ONE
-     * vigo_minsnap launch solves every active planner's QP and ONE vigo_box_collision_points launch sweeps
-     * every sample of every candidate trajectory; corridor bookkeeping and the PWL fallback stay per planner.
+    /* makePlan() of many planners in lock-step, both modes (adding waypoints PO.cpp:259-386, corridor constraint
+     * PO.cpp:388-545): per round ONE vigo_minsnap launch per (waypoint count, mode) solves the active planners' QPs
+     * and ONE vigo_box_collision_points launch sweeps every sample of every candidate trajectory; the bookkeeping
+     * (shrunk corridors, inserted waypoints) and the PWL fallback stay per planner.
      * trajectories[i] receives planner i's samples (delT = its sample_delta_time). */
     static std::vector<bool> makePlanBatch(const std::vector<polyTrajOctomap*>& planners, std::vector<std::vector<pose>>& trajectories);
     void makePlan();
     void makePlan(nav_msgs::Path& trajectory, double delT = 0.1);
     void makePlan(std::vector<pose>& trajectory, double delT = 0.1);
-    /* the two planning loops, public in the reference as well (PO.h:100-103) */
+    /* the two planning loops, public in the reference as well (PO.h:100-103): each the whole method of PO.cpp:259-545
+     * (single-waypoint case, loop, verdict, PWL fallback); makePlan() picks one by `mode` */
     void makePlanAddingWaypoint(std::vector<pose>& trajectory, double delT);
     void makePlanCorridorConstraint(std::vector<pose>& trajectory, double delT);
     void makePlanAddingWaypoint() { std::vector<pose> t; makePlanAddingWaypoint(t, delT_); }            // PO.cpp:259-322

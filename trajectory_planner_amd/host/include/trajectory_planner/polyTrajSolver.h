@@ -82,6 +82,17 @@ public:
     const std::vector<double>& getSolution(int axis) const { return axis == 0 ? xSol_ : (axis == 1 ? ySol_ : zSol_); }
     int getPolyDegree() const { return polyDegree_; }
     void getCorridor(std::vector<std::vector<std::pair<double, pose>>>& segToTimePose, std::vector<double>& corridorSizeVec) const;
+
+    /* a piecewise polynomial of degree `deg` over time knots `knots`: per axis (deg+1) coefficients per segment, in
+     * un-normalised local time.  coefficientsFit: every axis holds (deg+1) x (knots-1) of them.  evalPiecewise
+     * (PS.cpp:1026-1056): the pose at t, the default pose outside the knots or when the coefficients do not fit.
+     * samplePiecewise (PS.cpp:1125-1137): a pose every delT from 0 while t < knots.back(), then `last`. */
+    static bool coefficientsFit(int deg, const std::vector<double>& knots, const std::vector<double>& x, const std::vector<double>& y,
+                                const std::vector<double>& z);
+    static pose evalPiecewise(int deg, const std::vector<double>& knots, const std::vector<double>& x, const std::vector<double>& y,
+                              const std::vector<double>& z, double t);
+    static void samplePiecewise(int deg, const std::vector<double>& knots, const std::vector<double>& x, const std::vector<double>& y,
+                                const std::vector<double>& z, double delT, const pose& last, std::vector<pose>& trajectory);
 };
 }  // namespace trajPlanner
 #endif

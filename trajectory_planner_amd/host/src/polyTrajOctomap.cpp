@@ -108,24 +108,38 @@ const std::vector<double>& polyTrajOctomap::timeKnots() {
     return pwlKnots_;
 }
 
+static void appendXyz(const std::vector<pose>& pts, std::vector<double>& xyz) {
+    for (const pose& q : pts) { xyz.push_back(q.x); xyz.push_back(q.y); xyz.push_back(q.z); }
+}
+
 bool polyTrajOctomap::sweepPoints(const std::vector<pose>& pts, std::vector<uint8_t>& flags) {
     flags.assign(pts.size(), 1);
     if (pts.empty()) return true;
     if (!syncDevice()) return false;
-    std::vector<double> xyz(pts.size() * 3);
-    for (size_t i = 0; i < pts.size(); ++i) { xyz[3 * i] = pts[i].x; xyz[3 * i + 1] = pts[i].y; xyz[3 * i + 2] = pts[i].z; }
+    std::vector<double> xyz;
+    appendXyz(pts, xyz);
+    const bool ok = sweepXyz(xyz, flags);
+    if (!ok) cout << "[Trajectory Planner INFO]: device box sweep failed: " << vigo_last_error(dev_) << endl;
+    return ok;
+}
+
+// ONE vigo_box_collision_points launch over xyz triples on the synced handle: flags[i] = 1 where the collision box at
+// sample i meets an occupied voxel (all 1 if the launch or a copy fails)
+bool polyTrajOctomap::sweepXyz(const std::vector<double>& xyz, std::vector<uint8_t>& flags) {
+    const size_t n = xyz.size() / 3;
+    flags.assign(n, 1);
+    if (n == 0) return true;
     static thread_local vigo_host::StagingBuf dP, dF;      // reused by every sweep of this thread
-    bool ok = dP.upload(xyz.data(), xyz.size() * 8) && dF.alloc(pts.size());
     const double box[3] = {collisionBox_[0], collisionBox_[1], collisionBox_[2]};
-    ok = ok && vigo_box_collision_points(dev_, (int64_t)pts.size(), (const double*)dP.p, box, mapRes_, (uint8_t*)dF.p) == VIGO_OK;
-    ok = ok && dF.download(flags.data(), pts.size());
+    const bool ok = dP.upload(xyz.data(), n * 24) && dF.alloc(n) &&
+                    vigo_box_collision_points(dev_, (int64_t)n, (const double*)dP.p, box, mapRes_, (uint8_t*)dF.p) == VIGO_OK &&
+                    dF.download(flags.data(), n);
     // A pose at NaN or infinity: the reference's sweep makes no pass there (the lattice count is the conversion of a
     // NaN, INT_MIN on x86 — the device entry point follows that, include/vigo.h) and would publish the trajectory.  The
     // facade refuses such a pose instead: a degenerate min-snap solution (coincident waypoints) then falls back to the
     // piecewise-linear plan like any colliding one.
-    for (size_t i = 0; i < pts.size(); ++i)
-        if (!(std::isfinite(pts[i].x) && std::isfinite(pts[i].y) && std::isfinite(pts[i].z))) flags[i] = 1;
-    if (!ok && dev_) cout << "[Trajectory Planner INFO]: device box sweep failed: " << vigo_last_error(dev_) << endl;
+    for (size_t i = 0; i < n; ++i)
+        if (!(std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]))) flags[i] = 1;
     return ok;
 }
 
@@ -154,16 +168,13 @@ bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, st
     return has;
 }
 
-// PO.cpp:634-656: t accumulates delT per sample; first time-knot interval containing t (inclusive)
-bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, double delT, std::set<int>& collisionSeg) {
-    collisionSeg.clear();
-    std::vector<uint8_t> f;
-    sweepPoints(trajectory, f);
-    const std::vector<double>& knots = timeKnots();
+// PO.cpp:634-656: t accumulates delT per sample; a colliding sample blames the first time-knot interval containing t
+// (inclusive)
+static bool collisionSegments(const uint8_t* flags, size_t n, const std::vector<double>& knots, double delT, std::set<int>& collisionSeg) {
     double t = 0;
     bool has = false;
-    for (size_t k = 0; k < trajectory.size(); ++k) {
-        if (f[k]) {
+    for (size_t k = 0; k < n; ++k) {
+        if (flags[k]) {
             has = true;
             for (size_t i = 0; i + 1 < knots.size(); ++i)
                 if (t >= knots[i] && t <= knots[i + 1]) { collisionSeg.insert((int)i); break; }
@@ -173,9 +184,18 @@ bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, do
     return has;
 }
 
+bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, double delT, std::set<int>& collisionSeg) {
+    collisionSeg.clear();
+    std::vector<uint8_t> f;
+    sweepPoints(trajectory, f);
+    return collisionSegments(f.data(), f.size(), timeKnots(), delT, collisionSeg);
+}
+
 // ---- the fallback of PO.cpp:308-318, :373-383, :528-541: a fresh pwlTraj over the waypoints (its own 1.0 m/s and
-// 0.5 rad/s, piecewiseLinearTraj.h:20-21 — not the planner's desired velocity), sampled at delT ----
+// 0.5 rad/s, piecewiseLinearTraj.h:20-21 — not the planner's desired velocity), sampled at delT; it replaces the
+// min-snap polynomial as the plan ----
 void polyTrajOctomap::pwlPlan(std::vector<pose>& trajectory, double delT) {
+    trajSolver_.reset();
     pwlTrajSolver_.reset(new pwlTraj(nh_));
     trajectory.clear();
     pwlKnots_.clear();
@@ -185,124 +205,122 @@ void polyTrajOctomap::pwlPlan(std::vector<pose>& trajectory, double delT) {
     pwlKnots_ = pwlTrajSolver_->getTimeKnot();
 }
 
-// polyTrajSolver::getPose on an externally supplied polynomial (PS.cpp:1026-1056)
-pose polyTrajOctomap::extPose(double t) {
-    pose p;
-    for (size_t i = 0; i + 1 < extKnots_.size(); ++i) {
-        if (t >= extKnots_[i] && t <= extKnots_[i + 1]) {
-            t = (double)(t - extKnots_[i]);
-            const int c0 = (extDegree_ + 1) * (int)i;
-            double x = 0, y = 0, z = 0;
-            for (int d = 0; d < extDegree_ + 1; ++d) {
-                x += xSol_[c0 + d] * std::pow(t, d);
-                y += ySol_[c0 + d] * std::pow(t, d);
-                z += zSol_[c0 + d] * std::pow(t, d);
-            }
-            if (t == 0) t = 0.01;
-            double dx = 0, dy = 0;
-            for (int d = 0; d < extDegree_ + 1; ++d) {
-                dx += d * xSol_[c0 + d] * std::pow(t, d - 1);
-                dy += d * ySol_[c0 + d] * std::pow(t, d - 1);
-            }
-            p.x = x; p.y = y; p.z = z; p.yaw = std::atan2(dy, dx);
-            break;
-        }
-    }
-    return p;
-}
+// ---- the planning loop of PO.cpp:259-545: per round the QP (solveOnHost, or the device QP in makePlanBatch), the
+// samples at delT, their box sweep, then advance(); the two callers keep their own time limits ----
+struct polyTrajOctomap::PlanState {
+    bool addingWaypoints;               // PO.cpp:259-386; else the corridor constraint, PO.cpp:388-545
+    std::vector<double> corridor;       // corridor radius per segment (corridor mode)
+    int iters = 0;
+    double t0 = 0;
+};
 
-// PO.cpp:472-545
-void polyTrajOctomap::makePlanCorridorConstraint(std::vector<pose>& trajectory, double delT) {
-    this->setDefaultInit();
+polyTrajOctomap::PlanState polyTrajOctomap::begin(bool addingWaypoints) {
+    setDefaultInit();
     trajSolver_.reset(new polyTrajSolver(polyDegree_, diffDegree_, continuityDegree_, desiredVel_));
     trajSolver_->updatePath(path_);
     trajSolver_->updateInitVel(initVel_[0], initVel_[1], initVel_[2]);
     trajSolver_->updateInitAcc(initAcc_[0], initAcc_[1], initAcc_[2]);
-    std::vector<double> corridorSizeVec(path_.size() - 1, initR_);
-    int countIter = 0;
-    bool valid = false;
-    const double t0 = nowSec();
-    while (!valid) {
-        if (nowSec() - t0 >= timeout_) { cout << "[Trajectory Planner INFO]: Timeout." << endl; break; }
-        trajSolver_->setCorridorConstraint(corridorSizeVec, corridorRes_);
-        if (softConstraint_) trajSolver_->setSoftConstraint(softConstraintRadius_, softConstraintRadius_, 0);   // PO.cpp:290-292, :354-356, :426-428
-        trajSolver_->solve();
-        // an infeasible corridor keeps the previous polynomial, like the reference; with none to keep (the very
-        // first corridor was infeasible, and shrinking it cannot help) there is nothing to sample: not found
-        if (!trajSolver_->hasSolution()) break;
-        trajSolver_->getTrajectory(trajectory, delT);
-        std::set<int> collisionSeg;
-        valid = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
-        if (!valid)
-            this->adjustCorridorSize(collisionSeg, corridorSizeVec);
-        ++countIter;
-        if (countIter > maxIter_) break;
-    }
-    lastIterations_ = countIter;
-    findValidTraj_ = valid;
+    PlanState s;
+    s.addingWaypoints = addingWaypoints;
+    if (!addingWaypoints) s.corridor.assign(path_.size() - 1, initR_);
+    s.t0 = nowSec();
+    findValidTraj_ = false;
+    lastIterations_ = 0;
+    return s;
 }
 
-// PO.cpp:259-386
-void polyTrajOctomap::makePlanAddingWaypoint(std::vector<pose>& trajectory, double delT) {
-    this->setDefaultInit();
-    trajSolver_.reset(new polyTrajSolver(polyDegree_, diffDegree_, continuityDegree_, desiredVel_));
-    trajSolver_->updateInitVel(initVel_[0], initVel_[1], initVel_[2]);
-    trajSolver_->updateInitAcc(initAcc_[0], initAcc_[1], initAcc_[2]);
-    trajSolver_->updatePath(path_);
-    int countIter = 0;
-    bool valid = false;
-    const double t0 = nowSec();
-    while (!valid) {
-        if (nowSec() - t0 >= timeout_) { cout << "[Trajectory Planner INFO]: Timeout." << endl; break; }
-        if (softConstraint_) trajSolver_->setSoftConstraint(softConstraintRadius_, softConstraintRadius_, 0);   // PO.cpp:290-292, :354-356, :426-428
-        trajSolver_->solve();
-        if (!trajSolver_->hasSolution()) break;   // degenerate path (e.g. coincident waypoints): nothing to sample
-        trajSolver_->getTrajectory(trajectory, delT);
-        std::set<int> collisionSeg;
-        valid = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
-        if (!valid) {
-            this->insertWaypoint(collisionSeg);
-            trajSolver_->updatePath(path_);   // (the reference never refreshes the solver's path here)
-        }
-        ++countIter;
-        if (countIter > maxIter_) break;
-    }
-    lastIterations_ = countIter;
-    findValidTraj_ = valid;
+// the round's corridor boxes (PO.cpp:421-424), the soft waypoint boxes (PO.cpp:290-292, :354-356, :426-428), the QP.
+// An infeasible corridor keeps the previous polynomial, like the reference.
+void polyTrajOctomap::solveOnHost(PlanState& s) {
+    if (!s.addingWaypoints) trajSolver_->setCorridorConstraint(s.corridor, corridorRes_);
+    if (softConstraint_) trajSolver_->setSoftConstraint(softConstraintRadius_, softConstraintRadius_, 0);
+    trajSolver_->solve();
 }
 
-void polyTrajOctomap::makePlan(std::vector<pose>& trajectory, double delT) {
-    this->findValidTraj_ = false;
-    if (this->path_.empty()) return;
-    if (this->path_.size() == 1) { trajectory = this->path_; this->findValidTraj_ = true; return; }
-    if (!extKnots_.empty() && !trajSolver_) {
-        // an installed polynomial: one pass of the loop body (sample -> device sweep)
-        trajectory.clear();
-        for (double t = 0; t < extKnots_.back(); t += delT) trajectory.push_back(extPose(t));
-        trajectory.push_back(path_.back());
-        std::set<int> collisionSeg;
-        findValidTraj_ = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
-        return;
+// the sweep flags of this round's n samples: no collision ends the loop with a valid trajectory; otherwise insert
+// waypoints in the colliding segments (PO.cpp:178-186; the solver's path is refreshed, which the reference omits) or
+// shrink their corridors (PO.cpp:188-192).  False once the planner stops: valid, or past the iteration limit.
+bool polyTrajOctomap::advance(PlanState& s, const uint8_t* flags, size_t n, double delT) {
+    std::set<int> collisionSeg;
+    const bool collides = collisionSegments(flags, n, trajSolver_->getTimeKnot(), delT, collisionSeg);
+    if (collides && s.addingWaypoints) {
+        insertWaypoint(collisionSeg);
+        trajSolver_->updatePath(path_);
+    } else if (collides) {
+        adjustCorridorSize(collisionSeg, s.corridor);
     }
-    if (mode_) makePlanAddingWaypoint(trajectory, delT);
-    else makePlanCorridorConstraint(trajectory, delT);
+    lastIterations_ = ++s.iters;
+    findValidTraj_ = !collides;
+    return collides && s.iters <= maxIter_;
+}
+
+// PO.cpp:371-383, :531-542
+void polyTrajOctomap::finish(std::vector<pose>& trajectory, double delT) {
     if (findValidTraj_) {
         cout << "[Trajectory Planner INFO]: Found valid trajectory!" << endl;
     } else {
         cout << "[Trajectory Planner INFO]: Not found. Return the best. Please consider piecewise linear trajectory!!" << endl;
-        trajSolver_.reset();
         pwlPlan(trajectory, delT);
     }
 }
 
-// makePlan() of many planners in lock-step, BOTH planning loops (adding waypoints PO.cpp:259-386, corridor constraint
-// PO.cpp:388-545).  Per round: the active planners are grouped by (waypoint count, mode) and every group's QPs are
-// ONE vigo_minsnap launch (corridor boxes for the corridor mode, none for the adding-waypoint mode, whose paths grow
-// as waypoints are inserted: the groups are re-formed every round); then every sample of every candidate trajectory
-// goes through ONE vigo_box_collision_points launch; the per-planner bookkeeping (shrink the corridor of the
-// colliding segments / insert waypoints there, iteration and time limits, the PWL fallback) stays on the host.
-// A path that outgrows the device QP (more than 11 waypoints) is solved by the host QP of the same algorithm
-// inside the same round.
+// makePlanAddingWaypoint / makePlanCorridorConstraint: PO.cpp:323-386, :472-545
+void polyTrajOctomap::planOnHost(bool addingWaypoints, std::vector<pose>& trajectory, double delT) {
+    findValidTraj_ = false;
+    if (path_.empty()) return;
+    if (path_.size() == 1) { trajectory = path_; findValidTraj_ = true; return; }
+    PlanState s = begin(addingWaypoints);
+    std::vector<uint8_t> flags;
+    do {
+        if (nowSec() - s.t0 >= timeout_) { cout << "[Trajectory Planner INFO]: Timeout." << endl; break; }
+        solveOnHost(s);
+        // with no polynomial to keep (the very first corridor was infeasible, and shrinking it cannot help; a degenerate
+        // path such as coincident waypoints) there is nothing to sample: not found
+        if (!trajSolver_->hasSolution()) break;
+        trajSolver_->getTrajectory(trajectory, delT);
+        sweepPoints(trajectory, flags);   // a failed sweep leaves every flag set: the loop goes on
+    } while (advance(s, flags.data(), flags.size(), delT));
+    finish(trajectory, delT);
+}
+
+void polyTrajOctomap::makePlanAddingWaypoint(std::vector<pose>& trajectory, double delT) { planOnHost(true, trajectory, delT); }
+void polyTrajOctomap::makePlanCorridorConstraint(std::vector<pose>& trajectory, double delT) { planOnHost(false, trajectory, delT); }
+
+void polyTrajOctomap::makePlan(std::vector<pose>& trajectory, double delT) {
+    const bool installed = !extKnots_.empty() && !trajSolver_;
+    if (!installed || path_.size() < 2) {
+        if (mode_) makePlanAddingWaypoint(trajectory, delT);
+        else makePlanCorridorConstraint(trajectory, delT);
+        return;
+    }
+    // an installed polynomial: one pass of the loop body (sample -> device sweep); one whose coefficients do not fit
+    // its knots is no plan
+    findValidTraj_ = false;
+    trajectory.clear();
+    if (!polyTrajSolver::coefficientsFit(extDegree_, extKnots_, xSol_, ySol_, zSol_)) return;
+    polyTrajSolver::samplePiecewise(extDegree_, extKnots_, xSol_, ySol_, zSol_, delT, path_.back(), trajectory);
+    std::set<int> collisionSeg;
+    findValidTraj_ = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
+}
+
+// one planner's block [K][3][8] of vigo_minsnap's coefficients, installed as the solver's per-axis solution
+static void installDeviceSolution(polyTrajSolver& solver, const double* co, int K) {
+    const int D = 8;
+    std::vector<double> axis[3];
+    for (int c = 0; c < 3; ++c) {
+        axis[c].resize((size_t)K * D);
+        for (int sgm = 0; sgm < K; ++sgm)
+            for (int d = 0; d < D; ++d) axis[c][sgm * D + d] = co[((size_t)sgm * 3 + c) * D + d];
+    }
+    solver.installSolution(axis[0], axis[1], axis[2]);
+}
+
+// makePlan() of many planners in lock-step: the planning loop above, with the QPs of each round grouped by (waypoint
+// count, mode) into ONE vigo_minsnap launch per group (corridor boxes for the corridor mode, none for the adding-
+// waypoint mode, whose paths grow as waypoints are inserted: the groups are re-formed every round), and every sample of
+// every candidate trajectory swept by ONE vigo_box_collision_points launch.  A path that outgrows the device QP (more
+// than 11 waypoints) is solved by the host QP inside the same round.  Time limit: timeout x (planners in the batch),
+// checked after a colliding round.  A failed device call ends the batch: every planner not yet valid falls back.
 std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctomap*>& ps, std::vector<std::vector<pose>>& trajectories) {
     const size_t P = ps.size();
     std::vector<bool> result(P, false);
@@ -335,131 +353,79 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
     polyTrajOctomap* lead = ps[grp[0]];
     if (!lead->syncDevice()) return result;
     const int D = 8, kMaxDevWaypoints = 11;
-    struct State { std::vector<double> corridor; int iters = 0; bool active = true; double t0 = 0; };
     const size_t G = grp.size();
-    std::vector<State> st(G);
-    for (size_t g = 0; g < G; ++g) {
-        polyTrajOctomap* p = ps[grp[g]];
-        p->setDefaultInit();
-        p->trajSolver_.reset(new polyTrajSolver(p->polyDegree_, p->diffDegree_, p->continuityDegree_, p->desiredVel_));
-        p->trajSolver_->updatePath(p->path_);
-        if (!p->mode_) st[g].corridor.assign(p->path_.size() - 1, p->initR_);
-        st[g].t0 = nowSec();
-    }
-    static thread_local vigo_host::StagingBuf bWp, bCor, bCo, bKn, bSt, bPts, bFl;   // reused by every batch of this thread
+    std::vector<PlanState> st;
+    std::vector<bool> active(G, true);
+    for (size_t g = 0; g < G; ++g) st.push_back(ps[grp[g]]->begin(ps[grp[g]]->mode_));
+    static thread_local vigo_host::StagingBuf bWp, bCor, bCo, bKn, bSt;   // reused by every batch of this thread
     bool ok = true;
     while (ok) {
         std::vector<size_t> act;
-        for (size_t g = 0; g < G; ++g) if (st[g].active) act.push_back(g);
+        for (size_t g = 0; g < G; ++g) if (active[g]) act.push_back(g);
         if (act.empty()) break;
         // ---- the QPs: one launch per (waypoint count, mode) among the active planners ----
         std::vector<bool> solved(G, false);
         for (size_t a0 = 0; a0 < act.size() && ok; ++a0) {
             const size_t g0 = act[a0];
             if (solved[g0]) continue;
+            solved[g0] = true;
             polyTrajOctomap* p0 = ps[grp[g0]];
             const int W = (int)p0->path_.size(), K = W - 1;
-            if (W > kMaxDevWaypoints) {                       // beyond the device QP: the host QP, same algorithm
-                // (corridor mode: the boxes of this round before every solve, like makePlanCorridorConstraint — PO.cpp:421-424;
-                // an infeasible corridor keeps the previous polynomial there as here)
-                if (!p0->mode_) p0->trajSolver_->setCorridorConstraint(st[g0].corridor, p0->corridorRes_);
-                p0->trajSolver_->solve();
-                solved[g0] = true;
-                continue;
-            }
-            std::vector<size_t> members;
-            for (size_t a = a0; a < act.size(); ++a) {
-                polyTrajOctomap* q = ps[grp[act[a]]];
-                if (!solved[act[a]] && (int)q->path_.size() == W && q->mode_ == p0->mode_) { members.push_back(act[a]); solved[act[a]] = true; }
+            const bool adding = st[g0].addingWaypoints;
+            if (W > kMaxDevWaypoints) { p0->solveOnHost(st[g0]); continue; }   // beyond the device QP: the host QP, same algorithm
+            std::vector<size_t> members{g0};
+            for (size_t a = a0 + 1; a < act.size(); ++a) {
+                const size_t g = act[a];
+                if (!solved[g] && (int)ps[grp[g]]->path_.size() == W && st[g].addingWaypoints == adding) { members.push_back(g); solved[g] = true; }
             }
             const int T = (int)members.size();
             std::vector<double> hWp, hCor, hCo((size_t)T * K * 3 * D);
             std::vector<int32_t> hSt(T);
             for (size_t g : members) {
-                for (const pose& q : ps[grp[g]]->path_) { hWp.push_back(q.x); hWp.push_back(q.y); hWp.push_back(q.z); }
-                if (!p0->mode_) hCor.insert(hCor.end(), st[g].corridor.begin(), st[g].corridor.end());
+                appendXyz(ps[grp[g]]->path_, hWp);
+                if (!adding) hCor.insert(hCor.end(), st[g].corridor.begin(), st[g].corridor.end());
             }
-            ok = bWp.upload(hWp.data(), hWp.size() * 8) && (p0->mode_ || bCor.upload(hCor.data(), hCor.size() * 8)) &&
+            ok = bWp.upload(hWp.data(), hWp.size() * 8) && (adding || bCor.upload(hCor.data(), hCor.size() * 8)) &&
                  bCo.alloc(hCo.size() * 8) && bKn.alloc((size_t)T * W * 8) && bSt.alloc((size_t)T * 4) &&
                  vigo_minsnap(lead->dev_, T, W, 7, lead->diffDegree_, lead->continuityDegree_, lead->desiredVel_, lead->corridorRes_,
-                              (const double*)bWp.p, p0->mode_ ? nullptr : (const double*)bCor.p, nullptr, (double*)bCo.p, (double*)bKn.p,
+                              (const double*)bWp.p, adding ? nullptr : (const double*)bCor.p, nullptr, (double*)bCo.p, (double*)bKn.p,
                               (int32_t*)bSt.p) == VIGO_OK &&
                  bCo.download(hCo.data(), hCo.size() * 8) && bSt.download(hSt.data(), (size_t)T * 4);
-            if (!ok) break;
-            // install the solutions (an infeasible corridor keeps the previous one, like the reference)
-            for (int a = 0; a < T; ++a) {
-                if (hSt[a] != 0) continue;
-                std::vector<double> xs(K * D), ys(K * D), zs(K * D);
-                for (int sgm = 0; sgm < K; ++sgm)
-                    for (int d = 0; d < D; ++d) {
-                        xs[sgm * D + d] = hCo[(((size_t)a * K + sgm) * 3 + 0) * D + d];
-                        ys[sgm * D + d] = hCo[(((size_t)a * K + sgm) * 3 + 1) * D + d];
-                        zs[sgm * D + d] = hCo[(((size_t)a * K + sgm) * 3 + 2) * D + d];
-                    }
-                ps[grp[members[a]]]->trajSolver_->installSolution(xs, ys, zs);
-            }
+            // an infeasible corridor keeps the previous polynomial, like the reference
+            for (int a = 0; ok && a < T; ++a)
+                if (hSt[a] == 0) installDeviceSolution(*ps[grp[members[a]]]->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
         }
         if (!ok) break;
         // ---- sample every candidate, sweep all samples at once ----
-        const int T = (int)act.size();
+        const size_t T = act.size();
         std::vector<double> pts;
         std::vector<size_t> first(T + 1, 0);
-        for (int a = 0; a < T; ++a) {
-            polyTrajOctomap* p = ps[grp[act[a]]];
-            if (!p->trajSolver_->hasSolution()) {      // nothing to sample (first corridor infeasible, degenerate path): not found
-                trajectories[grp[act[a]]].clear();
-                st[act[a]].active = false;
-                first[a + 1] = pts.size() / 3;
-                continue;
-            }
-            p->trajSolver_->getTrajectory(trajectories[grp[act[a]]], p->delT_);
-            for (const pose& q : trajectories[grp[act[a]]]) { pts.push_back(q.x); pts.push_back(q.y); pts.push_back(q.z); }
-            first[a + 1] = pts.size() / 3;
-        }
-        const size_t M = pts.size() / 3;
-        std::vector<uint8_t> flags(M, 1);
-        const double box[3] = {lead->collisionBox_[0], lead->collisionBox_[1], lead->collisionBox_[2]};
-        if (M) {
-            ok = bPts.upload(pts.data(), M * 24) && bFl.alloc(M) &&
-                 vigo_box_collision_points(lead->dev_, (int64_t)M, (const double*)bPts.p, box, lead->mapRes_, (uint8_t*)bFl.p) == VIGO_OK &&
-                 bFl.download(flags.data(), M);
-            if (!ok) break;
-            for (size_t k = 0; k < M; ++k)             // a pose at NaN or infinity is refused (see sweepPoints)
-                if (!(std::isfinite(pts[3 * k]) && std::isfinite(pts[3 * k + 1]) && std::isfinite(pts[3 * k + 2]))) flags[k] = 1;
-        }
-        for (int a = 0; a < T; ++a) {
+        for (size_t a = 0; a < T; ++a) {
             const size_t g = act[a];
             polyTrajOctomap* p = ps[grp[g]];
-            if (!st[g].active) continue;               // retired above without a polynomial
-            const std::vector<double>& knots = p->trajSolver_->getTimeKnot();
-            std::set<int> collisionSeg;   // PO.cpp:634-656
-            double t = 0;
-            bool has = false;
-            for (size_t k = first[a]; k < first[a + 1]; ++k) {
-                if (flags[k]) {
-                    has = true;
-                    for (size_t i = 0; i + 1 < knots.size(); ++i)
-                        if (t >= knots[i] && t <= knots[i + 1]) { collisionSeg.insert((int)i); break; }
-                }
-                t += p->delT_;
+            std::vector<pose>& traj = trajectories[grp[g]];
+            if (p->trajSolver_->hasSolution()) {
+                p->trajSolver_->getTrajectory(traj, p->delT_);
+                appendXyz(traj, pts);
+            } else {                                   // nothing to sample (see planOnHost): not found
+                traj.clear();
+                active[g] = false;
             }
-            ++st[g].iters;
-            if (!has) { p->findValidTraj_ = true; st[g].active = false; }
-            else {
-                if (p->mode_) {
-                    p->insertWaypoint(collisionSeg);               // PO.cpp:178-186
-                    p->trajSolver_->updatePath(p->path_);
-                } else {
-                    for (int sgm : collisionSeg) st[g].corridor[sgm] *= p->fs_;   // adjustCorridorSize, PO.cpp:188-192
-                }
-                if (st[g].iters > p->maxIter_ || nowSec() - st[g].t0 >= p->timeout_ * (double)G) st[g].active = false;
-            }
-            p->lastIterations_ = st[g].iters;
+            first[a + 1] = pts.size() / 3;
+        }
+        std::vector<uint8_t> flags;
+        ok = lead->sweepXyz(pts, flags);
+        for (size_t a = 0; ok && a < T; ++a) {
+            const size_t g = act[a];
+            polyTrajOctomap* p = ps[grp[g]];
+            if (!active[g]) continue;                  // retired above without a polynomial
+            if (!p->advance(st[g], flags.data() + first[a], first[a + 1] - first[a], p->delT_) || nowSec() - st[g].t0 >= p->timeout_ * (double)G)
+                active[g] = false;
         }
     }
     for (size_t g = 0; g < G; ++g) {
         polyTrajOctomap* p = ps[grp[g]];
-        if (!p->findValidTraj_) { p->trajSolver_.reset(); p->pwlPlan(trajectories[grp[g]], p->delT_); }   // PO.cpp:459-467
+        if (!p->findValidTraj_) p->pwlPlan(trajectories[grp[g]], p->delT_);
         result[grp[g]] = p->findValidTraj_;
     }
     return result;
@@ -497,7 +463,7 @@ geometry_msgs::PoseStamped polyTrajOctomap::getPose(double t) {
         none.header.frame_id = "map";
         return none;
     }
-    pose p = trajSolver_ ? trajSolver_->getPose(t) : extPose(t);
+    pose p = trajSolver_ ? trajSolver_->getPose(t) : polyTrajSolver::evalPiecewise(extDegree_, extKnots_, xSol_, ySol_, zSol_, t);
     geometry_msgs::PoseStamped ps;
     ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
     ps.pose.orientation = quaternion_from_rpy(0, 0, p.yaw);

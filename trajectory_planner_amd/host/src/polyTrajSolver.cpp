@@ -620,26 +620,34 @@ void polyTrajSolver::installSolution(const std::vector<double>& x, const std::ve
     solved_ = true;
 }
 
+bool polyTrajSolver::coefficientsFit(int deg, const std::vector<double>& knots, const std::vector<double>& x, const std::vector<double>& y,
+                                     const std::vector<double>& z) {
+    if (deg < 0 || knots.empty()) return false;
+    const size_t n = (size_t)(deg + 1) * (knots.size() - 1);
+    return x.size() == n && y.size() == n && z.size() == n;
+}
+
 // PS.cpp:1026-1056
-pose polyTrajSolver::getPose(double t) {
+pose polyTrajSolver::evalPiecewise(int deg, const std::vector<double>& knots, const std::vector<double>& xs, const std::vector<double>& ys,
+                                   const std::vector<double>& zs, double t) {
     pose p;
-    if (!hasSolution()) return p;
-    for (size_t i = 0; i + 1 < desiredTime_.size(); ++i) {
-        const double startTime = desiredTime_[i], endTime = desiredTime_[i + 1];
+    if (!coefficientsFit(deg, knots, xs, ys, zs)) return p;
+    for (size_t i = 0; i + 1 < knots.size(); ++i) {
+        const double startTime = knots[i], endTime = knots[i + 1];
         if (t >= startTime && t <= endTime) {
             t = (double)(t - startTime);
-            const int c0 = (polyDegree_ + 1) * (int)i;
+            const int c0 = (deg + 1) * (int)i;
             double x = 0, y = 0, z = 0;
-            for (int d = 0; d < polyDegree_ + 1; ++d) {
-                x += xSol_[c0 + d] * std::pow(t, d);
-                y += ySol_[c0 + d] * std::pow(t, d);
-                z += zSol_[c0 + d] * std::pow(t, d);
+            for (int d = 0; d < deg + 1; ++d) {
+                x += xs[c0 + d] * std::pow(t, d);
+                y += ys[c0 + d] * std::pow(t, d);
+                z += zs[c0 + d] * std::pow(t, d);
             }
             if (t == 0) t = 0.01;
             double dx = 0, dy = 0;
-            for (int d = 0; d < polyDegree_ + 1; ++d) {
-                dx += d * xSol_[c0 + d] * std::pow(t, d - 1);
-                dy += d * ySol_[c0 + d] * std::pow(t, d - 1);
+            for (int d = 0; d < deg + 1; ++d) {
+                dx += d * xs[c0 + d] * std::pow(t, d - 1);
+                dy += d * ys[c0 + d] * std::pow(t, d - 1);
             }
             p.x = x; p.y = y; p.z = z; p.yaw = std::atan2(dy, dx);
             break;
@@ -647,6 +655,18 @@ pose polyTrajSolver::getPose(double t) {
     }
     return p;
 }
+
+// PS.cpp:1125-1137
+void polyTrajSolver::samplePiecewise(int deg, const std::vector<double>& knots, const std::vector<double>& x, const std::vector<double>& y,
+                                     const std::vector<double>& z, double delT, const pose& last, std::vector<pose>& trajectory) {
+    trajectory.clear();
+    const double endTime = knots.back();
+    for (double t = 0; t < endTime; t += delT) trajectory.push_back(evalPiecewise(deg, knots, x, y, z, t));
+    trajectory.push_back(last);
+}
+
+// (with a solution of the current path its coefficients fit the knots, so the evaluator's check is hasSolution())
+pose polyTrajSolver::getPose(double t) { return evalPiecewise(polyDegree_, desiredTime_, xSol_, ySol_, zSol_, t); }
 
 // PS.cpp:1080-1100.  (Outside every segment the reference returns an uninitialised vector; here it is zero.)
 Eigen::Vector3d polyTrajSolver::getVel(double t) {
@@ -691,12 +711,8 @@ Eigen::Vector3d polyTrajSolver::getAcc(double t) {
     return acc;
 }
 
-// PS.cpp:1125-1137
 void polyTrajSolver::getTrajectory(std::vector<pose>& trajectory, double delT) {
-    trajectory.clear();
-    const double endTime = desiredTime_.back();
-    for (double t = 0; t < endTime; t += delT) trajectory.push_back(getPose(t));
-    trajectory.push_back(path_.back());
+    samplePiecewise(polyDegree_, desiredTime_, xSol_, ySol_, zSol_, delT, path_.back(), trajectory);
 }
 
 std::vector<double>& polyTrajSolver::getTimeKnot() { return desiredTime_; }

@@ -716,6 +716,54 @@ int main() {
         poly.updatePath(std::vector<trajPlanner::pose>{{1, 2, 1}, {nan, 2, 1}, {3, 2, 1}});
         poly.makePlan(traj, 0.1);
         CHECK(!poly.isValid() || traj.empty(), "a NaN waypoint never yields a valid min-snap plan");
+        {   // the public per-mode loops carry the guards of PO.cpp:323-545 themselves
+            trajPlanner::polyTrajOctomap empty(nh);
+            empty.setMap(map);
+            bool threw = false;
+            try { empty.makePlanCorridorConstraint(); empty.makePlanAddingWaypoint(); } catch (...) { threw = true; }
+            CHECK(!threw && !empty.isValid(), "makePlanCorridorConstraint / makePlanAddingWaypoint without a path plan nothing");
+        }
+        {   // a polynomial whose coefficients do not fit its knots (8 x 2 per axis) is no plan, and is never read past its end
+            poly.updatePath(std::vector<trajPlanner::pose>{{-3, 2.5, 1}, {0, 2.5, 1}, {3, 2.5, 1}});
+            std::vector<double> shortX(10, 0), full(16, 0);
+            poly.setSolution(7, shortX, full, full, {0.0, 3.0, 6.0});
+            traj.assign(3, trajPlanner::pose(1, 1, 1));
+            poly.makePlan(traj, 0.1);
+            const geometry_msgs::PoseStamped q = poly.getPose(4.0);   // segment 1: past the end of the short x vector
+            CHECK(traj.empty() && !poly.isValid() && q.pose.position.x == 0 && q.pose.position.y == 0,
+                  "setSolution with too few coefficients: an empty trajectory, isValid() false, the default pose");
+        }
+        {   // a planner whose first corridor is infeasible (8 cm around the corners, tests/test_host_plumbing.py) reports 0
+            // iterations and the piecewise-linear fallback from makePlanBatch as from makePlan, whatever it planned before
+            ros::NodeHandle nhc;
+            nhc.setParam("collision_box", std::vector<double>{0.4, 0.4, 0.2});
+            nhc.setParam("map_resolution", 0.2);
+            nhc.setParam("sample_delta_time", 0.1);
+            nhc.setParam("mode", 0.0);
+            nhc.setParam("initial_radius", 0.08);
+            nhc.setParam("corridor_res", 8.0);
+            nhc.setParam("traj_timeout", 5.0);
+            trajPlanner::polyTrajOctomap batched(nhc), alone(nhc);
+            batched.setMap(map);
+            alone.setMap(map);
+            std::vector<trajPlanner::pose> t0, t1;
+            batched.updatePath(std::vector<trajPlanner::pose>{{-3, 2.5, 1}, {-2.5, 2.5, 1}, {-2, 2.5, 1}});   // feasible at 8 cm
+            batched.makePlan(t0, 0.1);
+            const int before = batched.getIterations();
+            const std::vector<trajPlanner::pose> tight{{0, 0, 1}, {2, 0.2, 1}, {3, 2.5, 1.2}, {5.5, 3, 1}};
+            batched.updatePath(tight);
+            alone.updatePath(tight);
+            std::vector<trajPlanner::polyTrajOctomap*> one{&batched};
+            std::vector<std::vector<trajPlanner::pose>> tb;
+            const std::vector<bool> rb = trajPlanner::polyTrajOctomap::makePlanBatch(one, tb);
+            alone.makePlan(t1, 0.1);
+            bool same = tb.size() == 1 && tb[0].size() == t1.size() && !t1.empty();
+            for (size_t i = 0; same && i < t1.size(); ++i) same = tb[0][i].x == t1[i].x && tb[0][i].y == t1[i].y && tb[0][i].z == t1[i].z;
+            std::printf("INFO infeasible first corridor: %d iterations before, %d after makePlanBatch, %d after makePlan\n", before,
+                        batched.getIterations(), alone.getIterations());
+            CHECK(before >= 1 && batched.getIterations() == 0 && alone.getIterations() == 0 && !rb[0] && !alone.isValid() && same,
+                  "makePlanBatch: an infeasible first corridor gives 0 iterations and the piecewise-linear fallback, as makePlan does");
+        }
         std::vector<trajPlanner::polyTrajOctomap*> pnone;
         std::vector<std::vector<trajPlanner::pose>> tn;
         CHECK(trajPlanner::polyTrajOctomap::makePlanBatch(pnone, tn).empty(), "polyTrajOctomap::makePlanBatch of nothing");
