@@ -367,7 +367,7 @@ int vigo_minsnap(vigo_handle_t h, int T, int W, int deg, int diff, int cont, dou
  *   box[3], map_res               collision_box / map_resolution (cfg/planner_interactive.yaml)
  *   out_flag uint8[S]; out_first int32[S] first colliding sample index or -1;
  *   out_count int32[S] number of colliding samples (may be NULL)
- * Every sample's verdict is the reference walk's; how they are reached is not (csrc/vigo_corridor.hip): segments of
+ * Every sample's verdict is the reference walk's; how they are reached is not (csrc/vigo_corridor_core.hpp): segments of
  * more than 512 samples are cut into spans of 32 or 16 samples, and a span is decided by ONE evaluation when the kernel
  * can prove that all its samples see the same voxel keys (an interval that holds every sample's float position, taken
  * through the reference's own monotone expressions at both ends); spans it cannot decide are cut in four, and what
@@ -382,6 +382,67 @@ int vigo_corridor_check(vigo_handle_t h, int S, int deg, const double* coeffs,
                         const int32_t* n_samp, const double* delT,
                         const double box[3], double map_res,
                         uint8_t* out_flag, int32_t* out_first, int32_t* out_count);
+
+/*
+ * Replaces: polyTrajOctomap::checkCollisionTraj(trajectory, delT, collisionSeg) (PO.cpp:634-656) on the trajectory
+ * polyTrajSolver::getTrajectory returns (PS.cpp:1125-1137, getPose :1026-1056), positions only, for T WHOLE trajectories
+ * at once — what vigo_corridor_check (independent segments, each on its own clock) does not do.
+ *   seg_off   int32[T+1]         CSR: trajectory t owns segments seg_off[t] .. seg_off[t+1]-1 (K_t of them)
+ *   coeffs    double[S][3][deg+1] vigo_corridor_check's layout (segment i of trajectory t is row seg_off[t] + i)
+ *   knots     double[S+T]        trajectory t's K_t + 1 time knots start at seg_off[t] + t
+ *   delT      double[T]          sample step
+ *   endpoint  double[T][3]       the sample getTrajectory appends (the last waypoint, path_.back())
+ * (A group of vigo_minsnap outputs, [T][W-1][3][8] coefficients and [T][W] knots, concatenated, is this layout.)
+ * The rules, for one trajectory with knots k[0..K]:
+ *   1 clock      samples t_0 = 0, t_{j+1} = fl(t_j + delT) while t_j < k[K] (PS.cpp:1129: accumulated, not j * delT); n of them
+ *   2 segment    sample j lies in the FIRST i with k[i] <= t_j <= k[i+1] (an inner knot belongs to the earlier segment) and
+ *                is evaluated there at fl(t_j - k[i]) with pow as vigo_exact_pow; a t_j in no interval (t_j < k[0]) is the
+ *                default pose (0, 0, 0) (PS.cpp:1026-1056)
+ *   3 endpoint   sample n is the endpoint as given; its clock for attribution is t_n >= k[K] (in practice: attributed only
+ *                when t_n == k[K])
+ *   4 test       every pose through pose2Octomap's float cast and the box sweep (PO.cpp:547-589), as vigo_corridor_check
+ *   5 blame      a colliding sample puts its segment (rule 2 on its clock) into collisionSeg; one in no interval makes the
+ *                trajectory collide but blames no segment (PO.cpp:640-651)
+ * Outputs (device memory, stream-ordered like the other corridor entries):
+ *   out_status int32[T]  VIGO_TRAJ_* below; a rejected trajectory gets n 0, flag 0, first -1, count 0 and no segments
+ *                        (the call still returns VIGO_OK)
+ *   out_n      int32[T]  the length of the list getTrajectory returns: n + 1 (samples plus endpoint)
+ *   out_flag   uint8[T]  checkCollisionTraj's result
+ *   out_first  int32[T]  the first colliding index in that list, or -1
+ *   out_count  int32[T]  colliding entries of the list (may be NULL)
+ *   out_seg    uint8[S]  1 when segment s is in collisionSeg
+ * A pose at NaN or infinity (fp64): does NOT collide (x86, as vigo_corridor_check); with VIGO_TRAJ_NONFINITE_COLLIDES in
+ * flags it collides and is blamed like any other sample (the host facade's rule).
+ * How: a thread per trajectory finds the runs of consecutive samples each segment takes (binary searches over the exact
+ * clock, vigo_traj_sample_runs below) and the trajectory's clock table; the segments' runs go through vigo_corridor_check's
+ * two passes with the certified spans (a workgroup per run, DESIGN.md §3.4 for the span bound on the subtracted clock);
+ * a thread per trajectory reduces the runs in segment order, the leading default-pose run and the endpoint.
+ * Scratch: 2.6 KB per trajectory for at most VIGO_TRAJ_CHUNK trajectories (10.6 MB; more trajectories are taken
+ * VIGO_TRAJ_CHUNK at a time inside the call) plus 25 bytes per segment for all S at once — the per-segment part is NOT
+ * chunked: it grows with S like the caller's own coefficient array (192 bytes per degree-7 segment), at 13 % of it.
+ * Errors: as vigo_corridor_check (handle, NULLs, deg in [0, 15], the box, a grid, its origin on the key lattice).
+ */
+#define VIGO_TRAJ_NONFINITE_COLLIDES 1
+#define VIGO_TRAJ_CHUNK 4096
+enum {
+    VIGO_TRAJ_OK = 0,
+    VIGO_TRAJ_BAD_KNOTS = 1,     /* a knot not finite, or knots decreasing                                        */
+    VIGO_TRAJ_BAD_DELT = 2,      /* delT not a finite number > 0                                                  */
+    VIGO_TRAJ_STALL = 3,         /* the clock stops advancing below k[K] (the reference's loop never ends)        */
+    VIGO_TRAJ_TOO_LONG = 4,      /* more than INT32_MAX - 1 samples                                               */
+    VIGO_TRAJ_BAD_OFFSETS = 5    /* seg_off is not non-decreasing within [0, S]: every trajectory gets this       */
+};
+int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                             const double* knots, const double* delT, const double* endpoint, const double box[3],
+                             double map_res, int flags, int32_t* out_status, int32_t* out_n, uint8_t* out_flag,
+                             int32_t* out_first, int32_t* out_count, uint8_t* out_seg);
+
+/* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
+ * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and
+ *   run_first, run_len  int32[K]  segment i's samples are run_first[i] .. run_first[i] + run_len[i] - 1
+ *   *n_total            n + 1, the list length (0 on rejection)
+ * Samples 0 .. run_first[0] - 1 (all n when K = 0) precede k[0]: the leading default-pose run. */
+int vigo_traj_sample_runs(int K, const double* knots, double delT, int32_t* run_first, int32_t* run_len, int32_t* n_total);
 
 /*
  * Replaces: polyTrajOctomap::checkCollision(point3d) (PO.cpp:547-568) for M already-sampled

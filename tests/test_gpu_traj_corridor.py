@@ -1,0 +1,388 @@
+"""-m gpu: vigo_traj_corridor_check (whole trajectories) against a Python restatement of its five rules (include/vigo.h)
+over the oracle's own sampler (vgo_poly_pos, correctly rounded pow) and box sweep (vgo_box_collision), integer for
+integer; against the facade's present route (host sampling, vigo_box_collision_points, the collisionSegments rule);
+on vigo_minsnap output straight from device memory; at config-3 size; and on hostile arguments."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib as ol
+from gpu_util import to_dev
+from trajectory_planner_amd import synth
+from trajectory_planner_amd._lib import load
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BOX = np.array([0.4, 0.4, 0.2])
+RES = 0.2
+
+
+def small_world(seed=7, n=96, res=0.1):
+    rng = np.random.default_rng(seed)
+    vox = np.zeros((n, n, 40), dtype=np.uint8)
+    for _ in range(60):
+        c = rng.integers(4, n - 4, size=2)
+        s = rng.integers(1, 4, size=2)
+        vox[c[0] - s[0]:c[0] + s[0], c[1] - s[1]:c[1] + s[1], 0:rng.integers(10, 40)] |= 4
+    unk = rng.random((n // 8, n // 8, 5)) < 0.08
+    vox[np.repeat(np.repeat(np.repeat(unk, 8, 0), 8, 1), 8, 2)] |= 2
+    return synth.World(vox, np.array([-4.8, -4.8, -0.5]), res, np.zeros((0, 6)))
+
+
+def wide_world(seed=7, n=256, res=0.1):
+    """room for chained trajectories of up to 12 segments: 25.6 m square, 60 pillars"""
+    rng = np.random.default_rng(seed)
+    vox = np.zeros((n, n, 40), dtype=np.uint8)
+    for _ in range(60):
+        c = rng.integers(4, n - 4, size=2)
+        s = rng.integers(1, 4, size=2)
+        vox[c[0] - s[0]:c[0] + s[0], c[1] - s[1]:c[1] + s[1], 0:rng.integers(10, 40)] |= 4
+    return synth.World(vox, np.array([-12.8, -12.8, -0.5]), res, np.zeros((0, 6)))
+
+
+def restate(g, seg_off, coeffs, knots, delT, endpoint, nonfinite, exact=True, device_sweep=None):
+    """The five rules in Python: (status, n, flag, first, count, seg mask).  Statuses other than 0 come from
+    vigo_traj_sample_runs (pinned against the literal loop by tests/test_traj_runs.py): the loop cannot run there.
+    exact=False, device_sweep=Vigo: the facade's present route instead (libm pow, vigo_box_collision_points)."""
+    O = ol.oracle()
+    T = len(seg_off) - 1
+    S, _, d1 = coeffs.shape
+    deg = d1 - 1
+    out = dict(status=np.zeros(T, np.int32), n=np.zeros(T, np.int32), flag=np.zeros(T, np.uint8),
+               first=np.full(T, -1, np.int32), count=np.zeros(T, np.int32), seg=np.zeros(S, np.uint8))
+    box = np.ascontiguousarray(BOX)
+    p = np.zeros(3)
+    with ol.pow_mode(exact):
+        for t in range(T):
+            a, b = int(seg_off[t]), int(seg_off[t + 1])
+            K = b - a
+            k = [float(x) for x in knots[a + t:a + t + K + 1]]
+            d = float(delT[t])
+            st = runs_status(k, d)
+            out["status"][t] = st
+            if st:
+                continue
+            poses, segs = [], []
+            tt = 0.0
+            while tt < k[-1]:                                  # rule 1
+                s = next((i for i in range(K) if k[i] <= tt <= k[i + 1]), -1)   # rule 2
+                if s < 0:
+                    poses.append((0.0, 0.0, 0.0))
+                else:
+                    c = np.ascontiguousarray(coeffs[a + s])
+                    O.vgo_poly_pos(deg, ol._d(c[0]), ol._d(c[1]), ol._d(c[2]), tt - k[s], ol._d(p))
+                    poses.append(tuple(p))
+                segs.append(s)
+                tt += d
+            poses.append(tuple(float(x) for x in endpoint[t]))   # rule 3
+            segs.append(next((i for i in range(K) if k[i] <= tt <= k[i + 1]), -1))
+            if device_sweep is not None:
+                hit = device_sweep.box_collision_points(to_dev(np.array(poses), device_sweep.device), BOX, RES).cpu().numpy()
+            else:
+                hit = [O.vgo_box_collision(C.byref(g), q[0], q[1], q[2], ol._d(box), RES) for q in poses]   # rule 4
+            first, count = -1, 0
+            for j, (q, s) in enumerate(zip(poses, segs)):
+                h = bool(hit[j]) or (nonfinite and not all(math.isfinite(x) for x in q))
+                if h:
+                    count += 1
+                    first = j if first < 0 else first
+                    if s >= 0:
+                        out["seg"][a + s] = 1                  # rule 5
+            out["n"][t] = len(poses)
+            out["flag"][t] = count > 0
+            out["first"][t] = first
+            out["count"][t] = count
+    return out
+
+
+def runs_status(k, d):
+    kk = np.ascontiguousarray(k, dtype=np.float64)
+    K = len(kk) - 1
+    buf = np.zeros(max(K, 1), np.int32)
+    n = C.c_int32()
+    return load().vigo_traj_sample_runs(K, kk.ctypes.data_as(C.c_void_p), float(d), buf.ctypes.data_as(C.c_void_p),
+                                        buf.ctypes.data_as(C.c_void_p), C.byref(n))
+
+
+def device(v, seg_off, coeffs, knots, delT, endpoint, nonfinite):
+    r = v.traj_corridor_check(to_dev(seg_off, v.device), to_dev(coeffs, v.device), to_dev(knots, v.device),
+                              to_dev(delT, v.device), to_dev(endpoint, v.device), BOX, RES, nonfinite_collides=nonfinite)
+    return dict(zip(("status", "n", "flag", "first", "count", "seg"), (x.cpu().numpy() for x in r)))
+
+
+def assert_same(got, ref, ctx=""):
+    for key in ("status", "n", "flag", "first", "count", "seg"):
+        assert np.array_equal(got[key], ref[key]), (ctx, key, np.nonzero(got[key] != ref[key])[0][:10],
+                                                    got[key][:16], ref[key][:16])
+
+
+def pack(trajs):
+    """[(knots, coeffs [K,3,d+1], delT, endpoint)] -> the entry's CSR layout"""
+    seg_off = np.cumsum([0] + [len(c) for _, c, _, _ in trajs]).astype(np.int32)
+    coeffs = np.concatenate([c for _, c, _, _ in trajs]) if seg_off[-1] else np.zeros((0, 3, 8))
+    knots = np.concatenate([np.asarray(k, np.float64) for k, _, _, _ in trajs])
+    delT = np.array([d for _, _, d, _ in trajs], np.float64)
+    endpoint = np.array([e for _, _, _, e in trajs], np.float64)
+    return seg_off, np.ascontiguousarray(coeffs, dtype=np.float64), knots, delT, endpoint
+
+
+def random_trajs(seed, T, deg, n_samples, kmax=12):
+    rng = np.random.default_rng(seed)
+    out = []
+    for t in range(T):
+        K = int(rng.integers(1, kmax + 1))
+        so, co, kn, dl, ep = synth.make_corridor_trajectories(seed * 1000 + t, 1, K, deg, extent_lo=(-4, -4, 0.6),
+                                                              extent_hi=(4, 4, 1.6), n_samples=n_samples)
+        out.append((kn, co, float(dl[0]), ep[0]))
+    return out
+
+
+@pytest.mark.parametrize("deg", [3, 5, 7])
+def test_seeded_worlds_match_the_restatement(vigo_handle, deg):
+    v = vigo_handle
+    w = wide_world()
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    args = pack(random_trajs(100 + deg, 24, deg, 60))
+    for nf in (False, True):
+        assert_same(device(v, *args, nf), restate(g, *args, nf), (deg, nf))
+    assert 0 < device(v, *args, False)["flag"].mean() < 1
+
+
+def edge_trajs(deg=7):
+    rng = np.random.default_rng(3)
+
+    def co(K, scale=1.0):
+        c = rng.uniform(-0.3, 0.3, size=(K, 3, deg + 1)) * scale
+        c[:, :, 0] = rng.uniform([-3, -3, 0.7], [3, 3, 1.5], size=(K, 3))
+        c[:, :, 2:] *= 0.1
+        return c
+    e = lambda: rng.uniform([-3, -3, 0.7], [3, 3, 1.5])
+    T = []
+    T.append(([0.0, 0.5, 1.25, 2.0], co(3), 0.25, e()))          # samples on knots, t_n == k[K]
+    T.append(([0.0, 0.6, 1.3], co(2), 0.25, e()))                # t_n > k[K]
+    T.append(([0.0, 0.0, 0.5, 1.0], co(3), 0.25, e()))           # zero-length first segment
+    T.append(([0.0, 0.5, 0.5, 1.0], co(3), 0.25, e()))           # ... inner
+    T.append(([0.0, 0.5, 1.0, 1.0], co(3), 0.25, e()))           # ... last, endpoint blamed on segment 1
+    T.append(([0.35, 1.0, 2.2], co(2), 0.1, e()))                # k[0] > 0: leading default-pose run
+    T.append(([2.0, 3.0], co(1), 0.01, e()))
+    T.append(([-1.0, 0.5, 2.0], co(2), 0.1, e()))                # k[0] < 0
+    T.append(([0.0, 0.0], co(1), 0.1, e()))                      # no sample, endpoint only (t_0 = 0 == k[K])
+    T.append(([0.0, 0.3, 0.9], co(2), 0.1, (0.0, 0.0, 0.0)))     # endpoint at the default pose
+    c = co(2); c[1, 0, 3] = np.nan
+    T.append(([0.0, 0.4, 0.9], c, 0.05, e()))                    # NaN coefficient in segment 1
+    c = co(2); c[0, 2, 1] = np.inf
+    T.append(([0.0, 0.4, 0.9], c, 0.05, e()))                    # infinite coefficient
+    c = co(1); c[0, 0, 7] = 1e300
+    T.append(([0.0, 40.0], c, 0.5, e()))                         # overflow to inf in fp64 late in the segment
+    c = co(1); c[0, 1, 0] = 1e39
+    T.append(([0.0, 1.0], c, 0.1, e()))                          # finite fp64, infinite float: x86 says no collision
+    T.append(([0.0, 0.4, 0.9], co(2), 0.05, (np.nan, 0.0, 1.0)))  # NaN endpoint
+    T.append(([0.0, 0.4, 0.9], co(2), 0.05, (np.inf, 0.0, 1.0)))
+    T.append(([0.0, 1e-301, 2e-301], co(2), 1e-305, e()))        # delT below 2^-1000: no clock table (walk)
+    T.append(([0.0, float("nan"), 1.0], co(2), 0.1, e()))       # rejected: NaN knot
+    T.append(([0.0, 1.0, 0.5], co(2), 0.1, e()))                 # decreasing
+    T.append(([0.0, 1.0], co(1), 0.0, e()))                      # delT 0, < 0, NaN
+    T.append(([0.0, 1.0], co(1), -0.1, e()))
+    T.append(([0.0, 1.0], co(1), float("nan"), e()))
+    T.append(([0.0, 1.0], co(1), 1e-300, e()))                   # stalling clock
+    T.append(([0.0, 30.0, 60.0], co(2, 0.02), 0.004, e()))     # long: certified spans (7500 samples per segment)
+    T.append(([0.0, 1.0, 2.0, 3.0, 4.0], co(4, 0.05), 2.0 ** -12, e()))   # 4096 samples per segment, on the knots
+    return T
+
+
+def test_edge_cases_match_the_restatement(vigo_handle):
+    v = vigo_handle
+    w = small_world(11)
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    args = pack(edge_trajs())
+    for nf in (False, True):
+        got, ref = device(v, *args, nf), restate(g, *args, nf)
+        assert_same(got, ref, nf)
+    assert list(got["status"][17:23]) == [1, 1, 2, 2, 2, 3]
+    # the default pose collides in another world: the leading run is counted whole, blames nothing
+    vox = w.voxels.copy()
+    vox[46:50, 46:50, 3:7] |= 4                                   # around (0, 0, 0)
+    w2 = synth.World(vox, w.origin, w.res, w.boxes)
+    v.set_grid(to_dev(w2.voxels, v.device), w2.origin, w2.res)
+    g2, keep2 = ol.make_grid(w2)
+    assert_same(device(v, *args, True), restate(g2, *args, True), "default pose")
+
+
+def test_agrees_with_the_facade_route(vigo_handle):
+    """host sampling (libm pow), vigo_box_collision_points and the collisionSegments rule: the same flags and segment sets
+    (the two differ only in pow's rounding; a difference here is a finding, not a tolerance)"""
+    v = vigo_handle
+    w = wide_world(5)
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    args = pack(random_trajs(7, 32, 7, 40))
+    got = device(v, *args, True)
+    ref = restate(g, *args, True, exact=False, device_sweep=v)
+    for key in ("flag", "seg", "n"):
+        assert np.array_equal(got[key], ref[key]), key
+
+
+def maze():
+    m = np.load(os.path.join(ROOT, "tests", "golden", "maze_config1.npz"))
+    nx, ny, nz = (int(x) for x in m["dims"])
+    nvox = nx * ny * nz
+    occ = np.unpackbits(m["occ_bits"])[:nvox].reshape(nx, ny, nz)
+    unk = np.unpackbits(m["unk_bits"])[:nvox].reshape(nx, ny, nz)
+    return synth.World((occ * 5 + unk * 2).astype(np.uint8), np.asarray(m["origin"], np.float64), float(m["res"][0]),
+                       np.zeros((0, 6))), m["waypoints"]
+
+
+def test_minsnap_output_straight_from_device_memory(vigo_handle):
+    v = vigo_handle
+    w, wp0 = maze()
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    rng = np.random.default_rng(9)
+    T, W = 12, 8
+    wp = np.repeat(wp0[None], T, 0) + np.concatenate([np.zeros((1, W, 3)), rng.normal(0, 0.3, size=(T - 1, W, 3))])
+    coeffs, knots, status = v.minsnap(to_dev(wp, v.device), to_dev(np.full((T, W - 1), 0.5), v.device))
+    seg_off = to_dev((np.arange(T + 1) * (W - 1)).astype(np.int32), v.device)
+    delT = to_dev(np.full(T, 0.1), v.device)
+    endpoint = to_dev(wp[:, -1], v.device)
+    r = v.traj_corridor_check(seg_off, coeffs.reshape(-1, 3, 8), knots.reshape(-1), delT, endpoint, BOX, RES,
+                              nonfinite_collides=True)
+    got = dict(zip(("status", "n", "flag", "first", "count", "seg"), (x.cpu().numpy() for x in r)))
+    args = (seg_off.cpu().numpy(), coeffs.reshape(-1, 3, 8).cpu().numpy(), knots.reshape(-1).cpu().numpy(),
+            delT.cpu().numpy(), wp[:, -1])
+    assert_same(got, restate(g, *args, True))
+    assert status.cpu().numpy()[0] == 0 and got["flag"][0] == 0         # the maze plan is collision free
+
+
+def test_config3_size_sampled_restatement_and_determinism(vigo_handle):
+    v = vigo_handle
+    rng = np.random.default_rng(3)
+    vox = np.zeros((256, 256, 64), dtype=np.uint8)
+    for _ in range(300):
+        c = rng.integers(8, 248, size=2)
+        s = rng.integers(1, 6, size=2)
+        vox[c[0] - s[0]:c[0] + s[0], c[1] - s[1]:c[1] + s[1], 0:rng.integers(10, 64)] |= 4
+    w = synth.World(vox, np.array([-12.8, -12.8, -1.0]), 0.1, np.zeros((0, 6)))
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    args = synth.make_corridor_trajectories(33, 512, 8, extent_lo=(-10, -10, 0.5), extent_hi=(10, 10, 2.5), n_samples=10000)
+    dev_args = [to_dev(a, v.device) for a in args]
+    r1 = [x.cpu().numpy() for x in v.traj_corridor_check(*dev_args, BOX, RES, nonfinite_collides=True)]
+    s2 = torch.cuda.Stream(v.device)
+    s2.wait_stream(torch.cuda.current_stream(v.device))
+    with torch.cuda.stream(s2):
+        v.use_current_stream()
+        r2 = [x.cpu().numpy() for x in v.traj_corridor_check(*dev_args, BOX, RES, nonfinite_collides=True)]
+    torch.cuda.synchronize()
+    v.use_current_stream()
+    for a, b in zip(r1, r2):
+        assert np.array_equal(a, b)
+    got = dict(zip(("status", "n", "flag", "first", "count", "seg"), r1))
+    assert (got["status"] == 0).all() and 0 < got["flag"].mean() < 1
+    # the restatement on a seeded sample of trajectories (80 000 samples each in Python: keep it small)
+    seg_off, coeffs, knots, delT, endpoint = args
+    for t in np.random.default_rng(1).choice(512, 3, replace=False):
+        a, b = seg_off[t], seg_off[t + 1]
+        sub = (np.array([0, b - a], np.int32), coeffs[a:b], knots[a + t:b + t + 1], delT[t:t + 1], endpoint[t:t + 1])
+        ref = restate(g, *sub, True)
+        for key in ("status", "n", "flag", "first", "count"):
+            assert got[key][t] == ref[key][0], (t, key)
+        assert np.array_equal(got["seg"][a:b], ref["seg"]), t
+
+
+def test_hostile_arguments(vigo_handle):
+    v = vigo_handle
+    lib = load()
+    h = v._h
+    d = v.device
+    seg_off, coeffs, knots, delT, endpoint = (to_dev(a, d) for a in pack(edge_trajs()[:3]))
+    T, S = 3, coeffs.shape[0]
+    outs = [torch.zeros(T, dtype=torch.int32, device=d), torch.zeros(T, dtype=torch.int32, device=d),
+            torch.zeros(T, dtype=torch.uint8, device=d), torch.zeros(T, dtype=torch.int32, device=d),
+            torch.zeros(T, dtype=torch.int32, device=d), torch.zeros(S, dtype=torch.uint8, device=d)]
+    P = lambda x: C.c_void_p(x.data_ptr())
+    box = (C.c_double * 3)(*BOX)
+
+    def call(h=h, T=T, S=S, deg=7, so=seg_off, flags=0, box=box, res=RES, outp=None):
+        o = [P(x) for x in outs] if outp is None else outp
+        return lib.vigo_traj_corridor_check(h, T, S, deg, P(so) if so is not None else None, P(coeffs), P(knots), P(delT),
+                                            P(endpoint), box, res, flags, *o)
+    # before a grid
+    assert call() == -5
+    w = small_world()
+    v.set_grid(to_dev(w.voxels, d), w.origin, w.res)
+    assert call() == 0
+    assert call(h=None) == -1
+    assert call(T=-1) == -1 and call(S=-1) == -1
+    assert call(deg=16) == -1 and call(deg=-1) == -1
+    assert call(so=None) == -1
+    assert call(flags=2) == -1
+    assert call(res=0.0) == -1 and call(res=float("nan")) == -1
+    assert call(box=None) == -1
+    assert call(box=(C.c_double * 3)(1e9, 1, 1)) == -6
+    o = [P(x) for x in outs]
+    o[5] = None
+    assert call(outp=o) == -1                                   # out_seg NULL with segments
+    o = [P(x) for x in outs]
+    o[4] = None
+    assert call(outp=o) == 0                                    # out_count may be NULL
+    # offsets that are no CSR: every trajectory rejected, nothing read out of range
+    for bad in ([0, 3, 2, 9], [-1, 3, 6, 9], [0, 3, 6, 10 ** 6], [0, 6, 3, 9]):
+        so = to_dev(np.array(bad, np.int32), d)
+        assert call(so=so) == 0
+        torch.cuda.synchronize()
+        assert outs[0].cpu().tolist() == [5, 5, 5] and outs[2].sum() == 0 and outs[5].sum() == 0
+    # shape checks of the wrapper
+    with pytest.raises(ValueError):
+        v.traj_corridor_check(seg_off, coeffs, knots[:-1], delT, endpoint, BOX, RES)
+    with pytest.raises(ValueError):
+        v.traj_corridor_check(seg_off, coeffs, knots, delT[:-1], endpoint, BOX, RES)
+    # T = 0
+    st, n, flag, first, count, seg = v.traj_corridor_check(seg_off[:1], coeffs, knots[:S], delT[:0], endpoint[:0], BOX, RES)
+    assert seg.sum() == 0
+
+
+def test_more_trajectories_than_one_chunk(vigo_handle):
+    """T > VIGO_TRAJ_CHUNK (4096): the trajectories are taken a chunk at a time inside the call (clock-table slots per
+    chunk, run state for all segments, one out_seg clear).  4100 trajectories of 1-2 segments and a few samples each; a
+    seeded subset, the chunk boundary included, against the restatement, and the whole against per-chunk calls."""
+    v = vigo_handle
+    w = small_world(13)
+    v.set_grid(to_dev(w.voxels, v.device), w.origin, w.res)
+    g, keep = ol.make_grid(w)
+    rng = np.random.default_rng(17)
+    trajs = []
+    for t in range(4100):
+        K = int(rng.integers(1, 3))
+        c = rng.uniform(-0.3, 0.3, size=(K, 3, 8)) * 0.1
+        c[:, :, 0] = rng.uniform([-3, -3, 0.7], [3, 3, 1.5], size=(K, 3))
+        c[:, :, 1] = rng.uniform(-1, 1, size=(K, 3))
+        knots = np.concatenate([[0.0], np.cumsum(rng.uniform(0.05, 0.4, size=K))])
+        trajs.append((knots, c, 0.05, rng.uniform([-3, -3, 0.7], [3, 3, 1.5])))
+    args = pack(trajs)
+    got = device(v, *args, True)
+    assert (got["status"] == 0).all() and 0 < got["flag"].mean() < 1
+    pick = sorted(set(rng.choice(4100, 40, replace=False).tolist()) | {4094, 4095, 4096, 4097, 4099})
+    seg_off, coeffs, knots, delT, endpoint = args
+    for t in pick:
+        a, b = seg_off[t], seg_off[t + 1]
+        sub = (np.array([0, b - a], np.int32), coeffs[a:b], knots[a + t:b + t + 1], delT[t:t + 1], endpoint[t:t + 1])
+        ref = restate(g, *sub, True)
+        for key in ("status", "n", "flag", "first", "count"):
+            assert got[key][t] == ref[key][0], (t, key)
+        assert np.array_equal(got["seg"][a:b], ref["seg"]), t
+    # the same trajectories in two calls of at most one chunk each
+    cut = 2050
+    s_cut = seg_off[cut]
+    first = pack(trajs[:cut])
+    second = pack(trajs[cut:])
+    r1, r2 = device(v, *first, True), device(v, *second, True)
+    for key in ("status", "n", "flag", "first", "count"):
+        assert np.array_equal(got[key], np.concatenate([r1[key], r2[key]])), key
+    assert np.array_equal(got["seg"], np.concatenate([r1["seg"], r2["seg"]])) and s_cut == len(r1["seg"])

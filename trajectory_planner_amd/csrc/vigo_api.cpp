@@ -10,6 +10,7 @@
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_internal.hpp"
+#include "vigo_traj_runs.hpp"
 
 using vigo::DevConst;
 using vigo::GridView;
@@ -180,6 +181,20 @@ double vigo_clock_table_time(double delT, int64_t k_last, int64_t k) {
     if (C.n <= 0) return NAN;
     if (k == k_last && vigo::clock_at(C, (int)k) != t_last) return NAN;     // (the builder's own last value)
     return vigo::clock_at(C, (int)k);
+}
+int vigo_traj_sample_runs(int K, const double* knots, double delT, int32_t* run_first, int32_t* run_len, int32_t* n_total) {
+    if (K < 0 || !knots || !n_total || (K > 0 && (!run_first || !run_len))) return VIGO_ERR_INVALID_ARG;
+    *n_total = 0;
+    int st = vigo::traj_knots_status(K, knots);
+    int64_t n = 0;
+    if (st == vigo::kTrajOk) st = vigo::traj_sample_count(knots[K], delT, &n);
+    if (st != vigo::kTrajOk) return st;
+    vigo::ClockTable C;                                  // the table k_traj_runs builds, and its searches
+    (void)vigo::build_clock_table(delT, (int)n, C);
+    int32_t lead, end_seg;
+    vigo::traj_runs(K, knots, delT, n, &C, &lead, run_first, run_len, 1, &end_seg);
+    *n_total = (int32_t)(n + 1);
+    return VIGO_OK;
 }
 double vigo_exact_pow_dd(double t, int d, int* ambiguous) {
     // the first tier as the sampler kernels run it: t^0 = 1, t^1 = t, then the running double-double product
@@ -656,6 +671,32 @@ int vigo_corridor_check(vigo_handle_t h, int S, int deg, const double* coeffs, c
     VIGO_HIP(h, (hipError_t)vigo::launch_corridor_check2(h->stream, h->grid, S, deg, coeffs, n_samp, delT, box, map_res, out_flag,
                                                          out_first, out_count, reinterpret_cast<int*>(ws),
                                                          clock_bytes ? ws + todo_bytes : nullptr));
+    return VIGO_OK;
+}
+
+int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                             const double* knots, const double* delT, const double* endpoint, const double box[3], double map_res,
+                             int flags, int32_t* out_status, int32_t* out_n, uint8_t* out_flag, int32_t* out_first,
+                             int32_t* out_count, uint8_t* out_seg) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (T < 0 || S < 0 || deg < 0 || deg > 15 || !box || !(map_res > 0) || (flags & ~VIGO_TRAJ_NONFINITE_COLLIDES) ||
+        (T > 0 && (!seg_off || !knots || !delT || !endpoint || !out_status || !out_n || !out_flag || !out_first)) ||
+        (S > 0 && (!coeffs || !out_seg)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_corridor_check: bad argument");
+    if (!sweep_box_ok(box, map_res)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_traj_corridor_check: collision box not finite or more than 32768 lattice points per pose");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_corridor_check before vigo_set_grid");
+    for (int a = 0; a < 3; ++a) {
+        double q = h->grid.origin[a] / h->grid.res;
+        if (fabs(q - floor(q + 0.5)) > 1e-6)
+            return fail(h, VIGO_ERR_UNSUPPORTED, "corridor checker needs a grid origin that is a multiple of res (octomap keys)");
+    }
+    if (T == 0 && S == 0) return VIGO_OK;
+    const int chunk = T < VIGO_TRAJ_CHUNK ? (T > 0 ? T : 1) : VIGO_TRAJ_CHUNK;
+    int rc = ensure_scratch(h, vigo::traj_ws_bytes(S, chunk));
+    if (rc != VIGO_OK) return rc;
+    VIGO_HIP(h, (hipError_t)vigo::launch_traj_corridor(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, delT, endpoint, box,
+                                                       map_res, (flags & VIGO_TRAJ_NONFINITE_COLLIDES) ? 1 : 0, out_status, out_n,
+                                                       out_flag, out_first, out_count, out_seg, h->scratch, chunk));
     return VIGO_OK;
 }
 

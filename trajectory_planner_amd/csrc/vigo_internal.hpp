@@ -122,7 +122,7 @@ int launch_traj_dynamic_collision(hipStream_t s, int B, int N, const double* ctr
 int launch_fill_sample_times(hipStream_t s, double dt, int T, double* times);
 int launch_ctrl_occupancy(hipStream_t s, const GridView& g, int B, int N, const double* ctrl,
                           uint8_t* out_pt, uint8_t* out_line);
-// the corridor checker's two passes (vigo_corridor.hip, k_corridor).  todo: S ints of device scratch (which segments the
+// the corridor checker's two passes (vigo_corridor_core.hpp, k_corridor).  todo: S ints of device scratch (which segments the
 // first pass left to the second); clock_ws: corridor_clock_ws_bytes(S) bytes of device scratch, 8-byte aligned, for the
 // segments' sample-clock tables, or NULL (every workgroup then builds its own).  (The "2" stays: the call's text is
 // part of the error vigo_corridor_check reports when the launch fails.)
@@ -130,6 +130,13 @@ size_t corridor_clock_ws_bytes(int S);
 int launch_corridor_check2(hipStream_t s, const GridView& g, int S, int deg, const double* coeffs, const int32_t* n_samp,
                            const double* delT, const double box[3], double map_res, uint8_t* out_flag, int32_t* out_first,
                            int32_t* out_count, int* todo, void* clock_ws);
+// whole trajectories (vigo_traj_corridor_check): ws = traj_ws_bytes(S, T_chunk) bytes of device scratch, 8-byte aligned;
+// the trajectories are taken T_chunk at a time (clock tables per chunk, per-segment state for all S)
+size_t traj_ws_bytes(int S, int T_chunk);
+int launch_traj_corridor(hipStream_t s, const GridView& g, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                         const double* knots, const double* delT, const double* endpoint, const double box[3], double map_res,
+                         int nonfinite, int32_t* out_status, int32_t* out_n, uint8_t* out_flag, int32_t* out_first,
+                         int32_t* out_count, uint8_t* out_seg, void* ws, int T_chunk);
 int launch_box_points(hipStream_t s, const GridView& g, int64_t M, const double* pts, const double box[3],
                       double map_res, uint8_t* out);
 // polyTrajSolver::getTrajectory for S segments: sample k of segment s at out[(s * stride + k) * 3] (fp64 and/or float)

@@ -5,7 +5,7 @@
 //
 // These gates look each sample up directly in the packed planes (L2 hits): a trajectory makes
 // ~120-240 lookups scattered over a 7 m path, fewer words than staging its bounding volume in
-// LDS would read.  The LDS-tiled path is the corridor checker (vigo_corridor.hip), where one
+// LDS would read.  The LDS-tiled path is the corridor checker (vigo_corridor_core.hpp), where one
 // segment makes ~10^5 lookups inside a small volume.
 #include "vigo_exact_time.hpp"
 #include "vigo_grid.hpp"

@@ -4,7 +4,7 @@
  *
  * makePlan(): waypoint path -> min-snap QP (polyTrajSolver, host) -> sampled trajectory -> box-sweep
  * collision check of every sample on the DEVICE (vigo_box_collision_points, the batched
- * checkCollision of PO.cpp:547-589) -> shrink the colliding segments' corridors or insert
+ * checkCollision of PO.cpp:547-589; makePlanBatch checks whole trajectories with vigo_traj_corridor_check) -> shrink the colliding segments' corridors or insert
  * waypoints -> repeat (PO.cpp:259-545); piecewise-linear fallback when no valid trajectory is found.
  * Differences to the reference: the map arrives through setMap() (a dense mapManager::occMap, e.g.
  * from loadOctomapBt) instead of the /octomap_binary service (PO.cpp:133-145); no RViz publisher
@@ -59,7 +59,8 @@ private:
     struct PlanState;
     PlanState begin(bool addingWaypoints);
     void solveOnHost(PlanState& s);
-    bool advance(PlanState& s, const uint8_t* flags, size_t n, double delT);
+    bool advance(PlanState& s, bool collides, const std::set<int>& collisionSeg);
+    bool advanceOnFlags(PlanState& s, const std::vector<uint8_t>& flags, double delT);
     void finish(std::vector<pose>& trajectory, double delT);
     void planOnHost(bool addingWaypoints, std::vector<pose>& trajectory, double delT);
 
@@ -84,7 +85,8 @@ public:
 
     /* makePlan() of many planners in lock-step, both modes (adding waypoints PO.cpp:259-386, corridor constraint
      * PO.cpp:388-545): per round ONE vigo_minsnap launch per (waypoint count, mode) solves the active planners' QPs
-     * and ONE vigo_box_collision_points launch sweeps every sample of every candidate trajectory; the bookkeeping
+     * and ONE vigo_traj_corridor_check launch checks every candidate trajectory whole (samples, box sweep, colliding
+     * segments; the trajectories returned are sampled on the host once, at the end); the bookkeeping
      * (shrunk corridors, inserted waypoints) and the PWL fallback stay per planner.
      * trajectories[i] receives planner i's samples (delT = its sample_delta_time). */
     static std::vector<bool> makePlanBatch(const std::vector<polyTrajOctomap*>& planners, std::vector<std::vector<pose>>& trajectories);

@@ -246,6 +246,74 @@ int vigo_host_poly_plan(int nx, int ny, int nz, const double* origin, double res
     return 0;
 }
 
+// polyTrajOctomap::makePlanBatch of P planners on one map, and for comparison each planner's twin planned alone with
+// makePlan(): cfg as vigo_host_poly_plan (its `mode` entry is replaced by mode[i]); path i is wp[wp_off[i] ..
+// wp_off[i+1]) (xyz triples).  Per planner (batch, then solo): info[4] = valid, iterations, final path length (waypoints),
+// samples; traj [P][traj_cap][3] (first traj_cap samples).  secs_out[2]: seconds of makePlanBatch, of the P solo plans.
+// solo_traj / solo_info / secs_out may be NULL (no twins then).  -1 on bad arguments.
+int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
+                              const int32_t* wp_off, const double* wp, const double* cfg, const int32_t* mode, int traj_cap,
+                              double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out, double* secs_out) {
+    if (P < 0 || !wp_off || !wp || !cfg || !mode || traj_cap < 0 || !traj_out || !info_out) return -1;
+    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    auto make = [&](int i) {
+        ros::NodeHandle nh;
+        nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
+        nh.setParam("map_resolution", cfg[3]);
+        nh.setParam("sample_delta_time", cfg[4]);
+        nh.setParam("desired_velocity", cfg[5]);
+        nh.setParam("initial_radius", cfg[6]);
+        nh.setParam("shrinking_factor", cfg[7]);
+        nh.setParam("corridor_res", cfg[8]);
+        nh.setParam("maximum_iteration_num", cfg[9]);
+        nh.setParam("traj_timeout", cfg[10]);
+        nh.setParam("mode", (double)mode[i]);
+        nh.setParam("polynomial_degree", 7.0);
+        nh.setParam("differential_degree", 4.0);
+        nh.setParam("continuity_degree", 4.0);
+        std::unique_ptr<trajPlanner::polyTrajOctomap> p(new trajPlanner::polyTrajOctomap(nh));
+        p->setMap(map);
+        std::vector<trajPlanner::pose> path;
+        for (int k = wp_off[i]; k < wp_off[i + 1]; ++k) path.push_back(trajPlanner::pose(wp[3 * k], wp[3 * k + 1], wp[3 * k + 2]));
+        p->updatePath(path);
+        return p;
+    };
+    auto report = [&](trajPlanner::polyTrajOctomap& p, const std::vector<trajPlanner::pose>& traj, int i, double* tr, double* info) {
+        const int n = (int)traj.size() < traj_cap ? (int)traj.size() : traj_cap;
+        for (int k = 0; k < n; ++k) {
+            double* o = tr + ((size_t)i * traj_cap + k) * 3;
+            o[0] = traj[k].x; o[1] = traj[k].y; o[2] = traj[k].z;
+        }
+        info[4 * i] = p.isValid() ? 1.0 : 0.0;
+        info[4 * i + 1] = p.getIterations();
+        info[4 * i + 2] = (double)p.getPath().size();
+        info[4 * i + 3] = (double)traj.size();
+    };
+    std::vector<std::unique_ptr<trajPlanner::polyTrajOctomap>> own;
+    std::vector<trajPlanner::polyTrajOctomap*> ps;
+    for (int i = 0; i < P; ++i) { own.push_back(make(i)); ps.push_back(own.back().get()); }
+    if (P > 0 && ps[0]->checkCollision(ps[0]->getPath().front())) { /* first device call: handle and map snapshot */ }
+    std::vector<std::vector<trajPlanner::pose>> trajs;
+    auto t0 = std::chrono::steady_clock::now();
+    trajPlanner::polyTrajOctomap::makePlanBatch(ps, trajs);
+    if (secs_out) secs_out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 0; i < P; ++i) report(*ps[i], trajs[i], i, traj_out, info_out);
+    if (!solo_traj_out || !solo_info_out) return 0;
+    double solo_secs = 0.0;
+    for (int i = 0; i < P; ++i) {
+        auto p = make(i);
+        std::vector<trajPlanner::pose> traj;
+        if (p->checkCollision(p->getPath().front())) { /* handle and snapshot outside the timed call */ }
+        t0 = std::chrono::steady_clock::now();
+        p->makePlan(traj, cfg[4]);
+        solo_secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        report(*p, traj, i, solo_traj_out, solo_info_out);
+    }
+    if (secs_out) secs_out[1] = solo_secs;
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- the same prologue for MANY paths on ONE map (the workload generator of bench.py / tests: product code, no oracle) ----

@@ -237,12 +237,11 @@ void polyTrajOctomap::solveOnHost(PlanState& s) {
     trajSolver_->solve();
 }
 
-// the sweep flags of this round's n samples: no collision ends the loop with a valid trajectory; otherwise insert
-// waypoints in the colliding segments (PO.cpp:178-186; the solver's path is refreshed, which the reference omits) or
-// shrink their corridors (PO.cpp:188-192).  False once the planner stops: valid, or past the iteration limit.
-bool polyTrajOctomap::advance(PlanState& s, const uint8_t* flags, size_t n, double delT) {
-    std::set<int> collisionSeg;
-    const bool collides = collisionSegments(flags, n, trajSolver_->getTimeKnot(), delT, collisionSeg);
+// this round's verdict (checkCollisionTraj, PO.cpp:634-656: does any sample collide, which segments are to blame): no
+// collision ends the loop with a valid trajectory; otherwise insert waypoints in the colliding segments (PO.cpp:178-186;
+// the solver's path is refreshed, which the reference omits) or shrink their corridors (PO.cpp:188-192).  False once the
+// planner stops: valid, or past the iteration limit.
+bool polyTrajOctomap::advance(PlanState& s, bool collides, const std::set<int>& collisionSeg) {
     if (collides && s.addingWaypoints) {
         insertWaypoint(collisionSeg);
         trajSolver_->updatePath(path_);
@@ -264,6 +263,13 @@ void polyTrajOctomap::finish(std::vector<pose>& trajectory, double delT) {
     }
 }
 
+// advance() on per-sample sweep flags of a host-sampled trajectory (collisionSegments, PO.cpp:634-656)
+bool polyTrajOctomap::advanceOnFlags(PlanState& s, const std::vector<uint8_t>& flags, double delT) {
+    std::set<int> collisionSeg;
+    const bool collides = collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT, collisionSeg);
+    return advance(s, collides, collisionSeg);
+}
+
 // makePlanAddingWaypoint / makePlanCorridorConstraint: PO.cpp:323-386, :472-545
 void polyTrajOctomap::planOnHost(bool addingWaypoints, std::vector<pose>& trajectory, double delT) {
     findValidTraj_ = false;
@@ -279,7 +285,7 @@ void polyTrajOctomap::planOnHost(bool addingWaypoints, std::vector<pose>& trajec
         if (!trajSolver_->hasSolution()) break;
         trajSolver_->getTrajectory(trajectory, delT);
         sweepPoints(trajectory, flags);   // a failed sweep leaves every flag set: the loop goes on
-    } while (advance(s, flags.data(), flags.size(), delT));
+    } while (advanceOnFlags(s, flags, delT));
     finish(trajectory, delT);
 }
 
@@ -317,8 +323,10 @@ static void installDeviceSolution(polyTrajSolver& solver, const double* co, int 
 
 // makePlan() of many planners in lock-step: the planning loop above, with the QPs of each round grouped by (waypoint
 // count, mode) into ONE vigo_minsnap launch per group (corridor boxes for the corridor mode, none for the adding-
-// waypoint mode, whose paths grow as waypoints are inserted: the groups are re-formed every round), and every sample of
-// every candidate trajectory swept by ONE vigo_box_collision_points launch.  A path that outgrows the device QP (more
+// waypoint mode, whose paths grow as waypoints are inserted: the groups are re-formed every round), and every
+// candidate trajectory checked whole — samples, box sweep and segment attribution of checkCollisionTraj, PO.cpp:634-656
+// — by ONE vigo_traj_corridor_check launch (a trajectory it rejects is sampled and swept on the host that round).  The
+// returned trajectories are sampled on the host once, after the loop.  A path that outgrows the device QP (more
 // than 11 waypoints) is solved by the host QP inside the same round.  Time limit: timeout x (planners in the batch),
 // checked after a colliding round.  A failed device call ends the batch: every planner not yet valid falls back.
 std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctomap*>& ps, std::vector<std::vector<pose>>& trajectories) {
@@ -396,36 +404,74 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
                 if (hSt[a] == 0) installDeviceSolution(*ps[grp[members[a]]]->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
         }
         if (!ok) break;
-        // ---- sample every candidate, sweep all samples at once ----
-        const size_t T = act.size();
-        std::vector<double> pts;
-        std::vector<size_t> first(T + 1, 0);
-        for (size_t a = 0; a < T; ++a) {
-            const size_t g = act[a];
+        // ---- every candidate's whole trajectory checked by ONE vigo_traj_corridor_check launch: the installed
+        // polynomials (device-QP coefficients as downloaded, host-QP ones, kept ones) with the solver's own knots, the
+        // step and the appended last waypoint; only the verdicts come back ----
+        std::vector<size_t> chk;
+        std::vector<int32_t> segOff(1, 0);
+        std::vector<double> hCo, hKn, hDt, hEp;
+        for (size_t g : act) {
             polyTrajOctomap* p = ps[grp[g]];
-            std::vector<pose>& traj = trajectories[grp[g]];
-            if (p->trajSolver_->hasSolution()) {
+            if (!p->trajSolver_->hasSolution()) {      // nothing to check (see planOnHost): not found
+                trajectories[grp[g]].clear();
+                active[g] = false;
+                continue;
+            }
+            const std::vector<double>& kn = p->trajSolver_->getTimeKnot();
+            const int K = (int)kn.size() - 1;
+            for (int sgm = 0; sgm < K; ++sgm)
+                for (int c = 0; c < 3; ++c) {
+                    const std::vector<double>& sol = p->trajSolver_->getSolution(c);
+                    hCo.insert(hCo.end(), sol.begin() + (size_t)sgm * D, sol.begin() + (size_t)(sgm + 1) * D);
+                }
+            hKn.insert(hKn.end(), kn.begin(), kn.end());
+            hDt.push_back(p->delT_);
+            hEp.push_back(p->path_.back().x); hEp.push_back(p->path_.back().y); hEp.push_back(p->path_.back().z);
+            segOff.push_back(segOff.back() + K);
+            chk.push_back(g);
+        }
+        const int Tc = (int)chk.size(), S = segOff.back();
+        if (Tc == 0) continue;
+        static thread_local vigo_host::StagingBuf cOff, cCo, cKn, cDt, cEp, cSt, cN, cFl, cFi, cSeg;
+        std::vector<int32_t> hStat(Tc);
+        std::vector<uint8_t> hFlag(Tc), hSeg(S);
+        const double box[3] = {lead->collisionBox_[0], lead->collisionBox_[1], lead->collisionBox_[2]};
+        ok = cOff.upload(segOff.data(), segOff.size() * 4) && cCo.upload(hCo.data(), hCo.size() * 8) &&
+             cKn.upload(hKn.data(), hKn.size() * 8) && cDt.upload(hDt.data(), hDt.size() * 8) && cEp.upload(hEp.data(), hEp.size() * 8) &&
+             cSt.alloc((size_t)Tc * 4) && cN.alloc((size_t)Tc * 4) && cFl.alloc((size_t)Tc) && cFi.alloc((size_t)Tc * 4) &&
+             cSeg.alloc((size_t)S) &&
+             vigo_traj_corridor_check(lead->dev_, Tc, S, 7, (const int32_t*)cOff.p, (const double*)cCo.p, (const double*)cKn.p,
+                                      (const double*)cDt.p, (const double*)cEp.p, box, lead->mapRes_, VIGO_TRAJ_NONFINITE_COLLIDES,
+                                      (int32_t*)cSt.p, (int32_t*)cN.p, (uint8_t*)cFl.p, (int32_t*)cFi.p, nullptr,
+                                      (uint8_t*)cSeg.p) == VIGO_OK &&
+             cSt.download(hStat.data(), (size_t)Tc * 4) && cFl.download(hFlag.data(), (size_t)Tc) && cSeg.download(hSeg.data(), (size_t)S);
+        if (!ok) cout << "[Trajectory Planner INFO]: device trajectory check failed: " << vigo_last_error(lead->dev_) << endl;
+        for (int a = 0; ok && a < Tc; ++a) {
+            const size_t g = chk[a];
+            polyTrajOctomap* p = ps[grp[g]];
+            bool more;
+            if (hStat[a] != VIGO_TRAJ_OK) {            // a trajectory the device entry rejects: sampled and swept on the host
+                std::vector<pose>& traj = trajectories[grp[g]];
+                std::vector<uint8_t> flags;
+                std::vector<double> pts;
                 p->trajSolver_->getTrajectory(traj, p->delT_);
                 appendXyz(traj, pts);
-            } else {                                   // nothing to sample (see planOnHost): not found
-                traj.clear();
-                active[g] = false;
+                lead->sweepXyz(pts, flags);            // a failed sweep leaves every flag set: the loop goes on
+                more = p->advanceOnFlags(st[g], flags, p->delT_);
+            } else {
+                std::set<int> collisionSeg;
+                for (int sgm = 0; sgm < segOff[a + 1] - segOff[a]; ++sgm)
+                    if (hSeg[segOff[a] + sgm]) collisionSeg.insert(sgm);
+                more = p->advance(st[g], hFlag[a] != 0, collisionSeg);
             }
-            first[a + 1] = pts.size() / 3;
-        }
-        std::vector<uint8_t> flags;
-        ok = lead->sweepXyz(pts, flags);
-        for (size_t a = 0; ok && a < T; ++a) {
-            const size_t g = act[a];
-            polyTrajOctomap* p = ps[grp[g]];
-            if (!active[g]) continue;                  // retired above without a polynomial
-            if (!p->advance(st[g], flags.data() + first[a], first[a + 1] - first[a], p->delT_) || nowSec() - st[g].t0 >= p->timeout_ * (double)G)
-                active[g] = false;
+            if (!more || nowSec() - st[g].t0 >= p->timeout_ * (double)G) active[g] = false;
         }
     }
+    // the returned trajectories: sampled once, from the polynomial that was found valid; the PWL fallback otherwise
     for (size_t g = 0; g < G; ++g) {
         polyTrajOctomap* p = ps[grp[g]];
-        if (!p->findValidTraj_) p->pwlPlan(trajectories[grp[g]], p->delT_);
+        if (p->findValidTraj_) p->trajSolver_->getTrajectory(trajectories[grp[g]], p->delT_);
+        else p->pwlPlan(trajectories[grp[g]], p->delT_);
         result[grp[g]] = p->findValidTraj_;
     }
     return result;

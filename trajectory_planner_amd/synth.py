@@ -238,6 +238,28 @@ def make_corridor_segments(seed: int, S: int, deg: int = 7, extent_lo=(-8.0, -8.
     return np.ascontiguousarray(coeffs), n_samp, np.ascontiguousarray(delT), dur
 
 
+def make_corridor_trajectories(seed: int, T: int, K: int, deg: int = 7, extent_lo=(-8.0, -8.0, 0.5),
+                               extent_hi=(8.0, 8.0, 1.5), n_samples: int = 10000):
+    """Whole trajectories for vigo_traj_corridor_check: T x K config-3-like segments (make_corridor_segments) chained end
+    to end (segment i + 1 starts where segment i ends), knots at the cumulative durations from 0, one delT per trajectory
+    (its mean segment duration / n_samples), endpoint = the end of the last segment.
+    -> (seg_off i32[T+1], coeffs [T*K,3,deg+1], knots [T*(K+1)], delT [T], endpoint [T,3])"""
+    coeffs, _, _, dur = make_corridor_segments(seed, T * K, deg, extent_lo, extent_hi, n_samples)
+    coeffs = coeffs.reshape(T, K, 3, deg + 1)
+    dur = dur.reshape(T, K)
+    for i in range(1, K):                                  # chain: p_i(0) = p_{i-1}(dur_{i-1})
+        prev = coeffs[:, i - 1]
+        end = (prev * dur[:, i - 1, None, None] ** np.arange(deg + 1)).sum(-1)
+        coeffs[:, i, :, 0] = end
+    last = coeffs[:, K - 1]
+    endpoint = (last * dur[:, K - 1, None, None] ** np.arange(deg + 1)).sum(-1)
+    knots = np.concatenate([np.zeros((T, 1)), np.cumsum(dur, axis=1)], axis=1)
+    delT = dur.mean(axis=1) / n_samples
+    seg_off = (np.arange(T + 1) * K).astype(np.int32)
+    return (seg_off, np.ascontiguousarray(coeffs.reshape(T * K, 3, deg + 1)), np.ascontiguousarray(knots.reshape(-1)),
+            np.ascontiguousarray(delT), np.ascontiguousarray(endpoint))
+
+
 def sphere_esdf(n: int, res: float, centre, radius: float):
     """Analytic signed distance to a sphere sampled at voxel centres (float32 [n,n,n])."""
     origin = np.array([-n * res / 2] * 3)
