@@ -347,13 +347,22 @@ int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl,
  *   conds      double[T][4][3] init vel, end vel, init acc, end acc (PS.h updateInitVel/...); NULL = 0
  *   out_coeffs double[T][W-1][3][deg+1]   == the `coeffs` layout of vigo_corridor_check (S = T*(W-1))
  *   out_knots  double[T][W]    desiredTime_ (PS.cpp:125-138)
- *   out_status int32[T]        0 solved, -1 numerical failure (coincident waypoints, > 1024 boxes),
+ *   out_status int32[T]        0 solved, -1 numerical failure (coincident waypoints, > 1024 boxes, a singular
+ *                              reduced Hessian: diff 5..7 where the minimiser is not unique),
  *                              -2 infeasible corridor (the reference keeps a stale solution silently)
  * deg must be 7; 2 <= W <= 11; diff/cont as polynomial/continuity degrees of cfg/planner*.yaml.
  */
 int vigo_minsnap(vigo_handle_t h, int T, int W, int deg, int diff, int cont, double desired_vel,
                  double corridor_res, const double* waypoints, const double* corridor,
                  const double* conds, double* out_coeffs, double* out_knots, int32_t* out_status);
+
+/*
+ * 1 when vigo_minsnap takes paths of W waypoints at these degrees, 0 when it refuses them
+ * (VIGO_ERR_UNSUPPORTED / VIGO_ERR_UNSUPPORTED_N): one wavefront holds the equality rows, at most
+ * 40 free coefficients remain, and every matrix fits in 160 KiB of LDS.  Host only, needs no GPU;
+ * vigo_minsnap decides with this same function.
+ */
+int vigo_minsnap_supported(int W, int deg, int diff, int cont);
 
 
 /*

@@ -4,8 +4,11 @@ check (KKT conditions) for a candidate solution."""
 import numpy as np
 
 
-def minsnap_matrices(wp, deg, diff, cont, vel):
-    """numpy statement of the QP (normalised time) for the equality-constrained case"""
+def minsnap_matrices(wp, deg, diff, cont, vel, conds=None):
+    """numpy statement of the QP (normalised time) for the equality-constrained case.  conds [4][3]: right-hand
+    sides of the endpoint rows -- initial velocity, final velocity, initial acceleration, final acceleration, as
+    derivatives in normalised segment time (PS.cpp, vigo_minsnap); None = zeros"""
+    cd = np.zeros((4, 3)) if conds is None else np.asarray(conds, dtype=np.float64).reshape(4, 3)
     K = len(wp) - 1
     D = deg + 1
     T = np.concatenate([[0], np.cumsum(np.linalg.norm(np.diff(wp, axis=0), axis=1) / vel)])
@@ -44,8 +47,8 @@ def minsnap_matrices(wp, deg, diff, cont, vel):
     for i in range(K - 1):
         row([(i * D + d, dv(d, 0, 1.0)) for d in range(D)] + [((i + 1) * D + d, -dv(d, 0, 0.0)) for d in range(D)], np.zeros(3))
     for order in (1, 2):
-        row([(d, dv(d, order, 0.0)) for d in range(D)], np.zeros(3))
-        row([(last + d, dv(d, order, 1.0)) for d in range(D)], np.zeros(3))
+        row([(d, dv(d, order, 0.0)) for d in range(D)], cd[2 * order - 2])
+        row([(last + d, dv(d, order, 1.0)) for d in range(D)], cd[2 * order - 1])
         for i in range(K - 1):
             dl, dr = T[i + 1] - T[i], T[i + 2] - T[i + 1]
             row([(i * D + d, dv(d, order, 1.0) * dr ** order) for d in range(D)] +
@@ -56,6 +59,45 @@ def minsnap_matrices(wp, deg, diff, cont, vel):
             row([(i * D + d, dv(d, order, 1.0) * dr ** order) for d in range(D)] +
                 [((i + 1) * D + d, -dv(d, order, 0.0) * dl ** order) for d in range(D)], np.zeros(3))
     return P, np.array(rows), np.array(rhs), T
+
+
+def closed_form(P, A, b):
+    """the equality-constrained optimum per axis: least-squares solution of the KKT system, [3, n].  The rows of A are
+    scaled to unit infinity norm and P to a unit largest entry first (same minimiser): the continuity rows carry
+    dt^order factors, up to ~1e8 at long segments and high continuity degree, and P's entries reach ~1e5, which the
+    unscaled system loses to rounding (lstsq then misses waypoints by up to 1e-3 at continuity degree 6)"""
+    s = np.abs(A).max(axis=1)
+    A, b = A / s[:, None], b / s[:, None]
+    P = P / np.abs(P).max()
+    n, m = P.shape[0], A.shape[0]
+    KKT = np.block([[P, A.T], [A, np.zeros((m, m))]])
+    rhs = np.concatenate([np.zeros((n, 3)), b], axis=0)
+    return np.linalg.lstsq(KKT, rhs, rcond=None)[0][:n].T
+
+
+def assert_matches_closed_form(c, wp, diff, cont, vel, conds=None, deg=7, n_eval=25):
+    """coefficients c [3, K*(deg+1)] in un-normalised local time (host layout) against the closed form: equality rows
+    1e-10 relative to each row's own scale (continuity rows carry dt^order factors), objective 1e-7, trajectory 1e-6"""
+    P, A, b, Tk = minsnap_matrices(wp, deg, diff, cont, vel, conds)
+    D = deg + 1
+    K = len(wp) - 1
+    sol = closed_form(P, A, b)
+    scale = np.concatenate([(Tk[s + 1] - Tk[s]) ** np.arange(D) for s in range(K)])
+    ts = np.linspace(0, Tk[-1], n_eval)
+    seg = np.clip(np.searchsorted(Tk, ts, side="right") - 1, 0, K - 1)
+    lt = ts - Tk[seg]
+    for a in range(3):
+        x = c[a] * scale
+        res = (np.abs(A @ x - b[:, a]) / np.abs(A).max(axis=1)).max()
+        assert res < 1e-10, (a, res)
+        obj, ref = x @ P @ x, sol[a] @ P @ sol[a]
+        assert abs(obj - ref) <= 1e-7 * max(1.0, ref), (a, obj, ref)
+        for i in range(n_eval):
+            s = seg[i]
+            pk = (sol[a, s * D:(s + 1) * D] / (Tk[s + 1] - Tk[s]) ** np.arange(D)) @ (lt[i] ** np.arange(D))
+            got = c[a, s * D:(s + 1) * D] @ (lt[i] ** np.arange(D))
+            assert abs(got - pk) < 1e-6 * max(1.0, abs(pk)), (a, ts[i], got, pk)
+    return Tk
 
 
 def evaluate(coeffs, knots, t, deg=7):
@@ -111,3 +153,19 @@ def kkt_violation(P, Aeq, beq, C, lo, hi, x, active_tol=1e-7):
     scale = max(1.0, np.abs(P @ x).max())
     _, resid = nnls(G, -(P @ x), maxiter=50 * G.shape[1])
     return prim, resid / scale
+
+
+def eq_kkt_violation(P, Aeq, beq, x):
+    """the KKT conditions of  min 1/2 x'Px  s.t.  Aeq x = beq  at x, for any minimiser, unique or not: (primal
+    infeasibility relative to each row's scale, reduced gradient Z'Px relative to max|P| max|x|) with Z an orthonormal
+    basis of null(Aeq) from the SVD of the row-scaled matrix.  Unlike kkt_violation this needs no multipliers, which
+    the dt^order factors of the continuity rows make ill-determined at high continuity degree, and it scales the
+    gradient by what rounding leaves of it: at differential degree 5..7 the optimum's |Px| is often 1e-13 of
+    |P||x|, so a solution exact to 1e-12 still shows a gradient of 1e-6 relative to |Px|"""
+    s = np.abs(Aeq).max(axis=1)
+    prim = (np.abs(Aeq @ x - beq) / s).max()
+    _, sv, Vt = np.linalg.svd(Aeq / s[:, None])
+    rank = int((sv > sv[0] * 1e-13).sum())
+    Z = Vt[rank:].T
+    g = P @ x
+    return prim, np.abs(Z.T @ g).max(initial=0.0) / max(np.abs(P).max() * np.abs(x).max(), 1e-300)

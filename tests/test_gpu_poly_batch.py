@@ -1,7 +1,9 @@
 """-m gpu: polyTrajOctomap::makePlanBatch (whole trajectories checked by vigo_traj_corridor_check) against each planner's
 twin planned alone with makePlan() (host sampling, vigo_box_collision_points, the collisionSegments rule), through
-vigo_host_poly_plan_batch: on the maze fixture and on seeded pillar worlds, 32 planners mixing both modes and a path of
-more than 11 waypoints (host QP).  Every sample of a valid trajectory is re-checked with a numpy box sweep."""
+vigo_host_poly_plan_batch_ex: on the maze fixture and on seeded pillar worlds, 32 planners mixing both modes and a path of
+more than 11 waypoints (host QP); the reference's shipped degrees (continuity 3, jerk); path shapes the device QP refuses
+(continuity 2 at 11 waypoints) and corridors of more than its 1024 boxes, which the batch solves on the host as its solo
+twin does.  Every sample of a valid trajectory is re-checked with a numpy box sweep."""
 import ctypes as C
 import os
 
@@ -37,10 +39,10 @@ def numpy_box_sweep(vox, origin, res, pts, box, step):
     return hit
 
 
-def plan_batch(vox, origin, res, paths, modes, cfg):
+def plan_batch(vox, origin, res, paths, modes, cfg, diff=4, cont=4):
     L = C.CDLL(LIB)
-    L.vigo_host_poly_plan_batch.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_void_p, C.c_int, _ip, _dp, _dp,
-                                            _ip, C.c_int, _dp, _dp, _dp, _dp, _dp]
+    L.vigo_host_poly_plan_batch_ex.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_void_p, C.c_int, _ip, _dp, _dp,
+                                               _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
     P = len(paths)
     off = np.cumsum([0] + [len(p) for p in paths]).astype(np.int32)
     wp = np.ascontiguousarray(np.concatenate(paths), dtype=np.float64)
@@ -51,10 +53,11 @@ def plan_batch(vox, origin, res, paths, modes, cfg):
     tr, info = np.zeros((P, CAP, 3)), np.zeros((P, 4))
     str_, sinfo = np.zeros((P, CAP, 3)), np.zeros((P, 4))
     secs = np.zeros(2)
-    rc = L.vigo_host_poly_plan_batch(vox.shape[0], vox.shape[1], vox.shape[2], org.ctypes.data_as(_dp), res, v.ctypes.data_as(C.c_void_p),
-                                     P, off.ctypes.data_as(_ip), wp.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), md.ctypes.data_as(_ip),
-                                     CAP, tr.ctypes.data_as(_dp), info.ctypes.data_as(_dp), str_.ctypes.data_as(_dp),
-                                     sinfo.ctypes.data_as(_dp), secs.ctypes.data_as(_dp))
+    rc = L.vigo_host_poly_plan_batch_ex(vox.shape[0], vox.shape[1], vox.shape[2], org.ctypes.data_as(_dp), res,
+                                        v.ctypes.data_as(C.c_void_p), P, off.ctypes.data_as(_ip), wp.ctypes.data_as(_dp),
+                                        cf.ctypes.data_as(_dp), md.ctypes.data_as(_ip), diff, cont, CAP, tr.ctypes.data_as(_dp),
+                                        info.ctypes.data_as(_dp), str_.ctypes.data_as(_dp), sinfo.ctypes.data_as(_dp),
+                                        secs.ctypes.data_as(_dp))
     assert rc == 0
     return tr, info, str_, sinfo, secs
 
@@ -95,15 +98,15 @@ def random_paths(rng, P, lo, hi, long_every=16):
 CFG = [0.4, 0.4, 0.2, 0.2, 0.1, 1.0, 0.5, 0.8, 8.0, 5, 100.0, 0.0]
 
 
-def check(vox, origin, res, paths, modes):
-    tr, info, str_, sinfo, secs = plan_batch(vox, origin, res, paths, modes, CFG)
+def check(vox, origin, res, paths, modes, cfg=CFG, diff=4, cont=4):
+    tr, info, str_, sinfo, secs = plan_batch(vox, origin, res, paths, modes, cfg, diff, cont)
     assert np.array_equal(info[:, :3], sinfo[:, :3]), np.nonzero((info[:, :3] != sinfo[:, :3]).any(1))[0]
     assert np.array_equal(info[:, 3], sinfo[:, 3])
     for i in range(len(paths)):
         n = min(int(info[i, 3]), CAP)
         assert np.abs(tr[i, :n] - str_[i, :n]).max(initial=0.0) <= 1e-9, i
         if info[i, 0]:
-            hits = numpy_box_sweep(vox, origin, res, tr[i, :n], CFG[:3], CFG[3])
+            hits = numpy_box_sweep(vox, origin, res, tr[i, :n], cfg[:3], cfg[3])
             assert not hits.any(), (i, int(hits.sum()))
     return info, secs
 
@@ -131,3 +134,74 @@ def test_batch_equals_solo_on_pillar_worlds(seed):
     info, secs = check(vox, origin, res, paths, modes)
     assert 0 < info[:, 0].sum() and (info[:, 1] > 1).any()     # some valid plans, some that took more than one round
     assert (info[:, 2] > 11).any()                              # a path of more than 11 waypoints (host QP) took part
+
+
+def test_reference_degrees_on_the_maze():
+    """cfg/planner.yaml ships continuity_degree 3; differential_degree 3 (jerk) is its other documented choice"""
+    vox, origin, res, wp = maze()
+    rng = np.random.default_rng(22)
+    paths = [wp] + [wp + np.concatenate([np.zeros((1, 3)), rng.normal(0, 0.1, size=(len(wp) - 2, 3)) * [1, 1, 0.2],
+                                         np.zeros((1, 3))]) for _ in range(15)]
+    info, _ = check(vox, origin, res, paths, [i % 2 for i in range(16)], diff=3, cont=3)
+    assert info[:, 0].any()
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_reference_degrees_on_pillar_worlds(seed):
+    vox, origin, res = pillar_world(seed)
+    rng = np.random.default_rng(200 + seed)
+    paths = random_paths(rng, 16, [-5, -5, 0.8], [5, 5, 1.6], long_every=8)
+    modes = list(rng.integers(0, 2, size=16))
+    info, _ = check(vox, origin, res, paths, modes, diff=3, cont=3)
+    assert 0 < info[:, 0].sum() and (info[:, 1] > 1).any()
+
+
+def test_shapes_the_device_qp_refuses_are_solved_on_the_host():
+    """continuity 2 at 11 waypoints needs 179 KiB of LDS: vigo_minsnap refuses it (vigo_minsnap_supported), and the
+    batch must solve such a group on the host instead of giving up on every planner"""
+    from trajectory_planner_amd import _lib
+    assert not _lib.load().vigo_minsnap_supported(11, 7, 4, 2) and _lib.load().vigo_minsnap_supported(10, 7, 4, 2)
+    vox, origin, res = pillar_world(4)
+    rng = np.random.default_rng(44)
+    paths = []
+    for i in range(12):
+        W = 11 if i < 6 else int(rng.integers(4, 9))
+        a, b = rng.uniform([-5, -5, 0.8], [5, 5, 1.6], size=(2, 3))
+        p = a + np.linspace(0, 1, W)[:, None] * (b - a)
+        p[1:-1] += rng.normal(0, 0.15, size=(W - 2, 3)) * [1, 1, 0.3]
+        paths.append(p)
+    modes = [i % 2 for i in range(12)]                        # 11-waypoint paths in both modes
+    info, _ = check(vox, origin, res, paths, modes, cont=2)
+    assert info[:, 0].any() and (info[:, 1] >= 1).all()
+
+
+def spiral(W, r, step_deg, a0=0.0):
+    a = np.deg2rad(a0 + np.arange(W) * step_deg)
+    return np.stack([r * np.cos(a), r * np.sin(a), np.linspace(0.9, 1.5, W)], 1)
+
+
+def test_more_than_1024_corridor_boxes_are_solved_on_the_host():
+    """at desired_velocity 0.25 a 38 m path of 11 waypoints has ~1200 corridor boxes: the device QP reports -1 (kMaxBox,
+    pinned in tests/test_gpu_minsnap_params.py), the host QP has no such limit, and the batch must solve that planner on
+    the host in the same round, as its solo twin does.  A planner whose first corridor is infeasible (device status -2:
+    a zig-zag of 10 m legs) keeps today's behaviour: no polynomial, the fallback -- as alone."""
+    from minsnap_ref import corridor_rows, minsnap_matrices
+    from test_minsnap_params import host_solve
+    cfg = list(CFG)
+    cfg[5] = 0.25                                             # desired_velocity
+    vox, origin, res = pillar_world(5)
+    big = [spiral(11, 5.5, 40), spiral(11, 5.0, 40, 15)]
+    zigzag = np.array([[-5.0, -4.0, 1.2], [5.0, -2.0, 1.2], [-5.0, 0.0, 1.2]])
+    rng = np.random.default_rng(55)
+    paths = big + [zigzag] + random_paths(rng, 8, [-5, -5, 0.8], [5, 5, 1.6], long_every=100)
+    modes = [0, 0, 0] + [i % 2 for i in range(8)]
+    # the premises: the spirals have more boxes than the device QP takes and a feasible first corridor; the zig-zag's
+    # first corridor is infeasible (with fewer than 1024 boxes)
+    for p, feasible in ((big[0], True), (big[1], True), (zigzag, False)):
+        cor = np.full(len(p) - 1, cfg[6])
+        _, _, _, Tk = minsnap_matrices(p, 7, 4, 4, cfg[5])
+        assert (len(corridor_rows(p, Tk, cor, cfg[8])[0]) > 1024) == feasible
+        assert (host_solve(p, 4, 4, cfg[5], None, cor, cfg[8])[0] == 0) == feasible
+    info, _ = check(vox, origin, res, paths, modes, cfg=cfg)
+    assert (info[:2, 1] >= 1).all()                           # the spirals were planned, not dropped in round 1
+    assert info[2, 0] == 0 and info[2, 1] == 0                # the infeasible zig-zag: no polynomial, like its solo twin

@@ -10,8 +10,9 @@
 //      shared by the three axes;
 //   3. the corridor boxes (two inequalities per box and axis) are handled by the Goldfarb-Idnani
 //      dual active-set iteration on the reduced problem; an infeasible corridor is reported.
-// One 64-lane workgroup per path, all matrices in LDS (59 KB at 7 segments, 114 KB at 10), no HBM traffic
-// besides the waypoints in and the coefficients out.  This is dense fp64 linear algebra on
+// One 64-lane workgroup per path, all matrices in LDS (at cont = 4: 76 KiB at 7 segments, 137 KiB at 10; the
+// largest accepted shape, cont = 3 at 10 segments, takes 155 KiB; minsnap_supported is the envelope), no HBM
+// traffic besides the waypoints in and the coefficients out.  This is dense fp64 linear algebra on
 // 56..80-dimensional systems — latency-bound small-matrix work, no MFMA-sized contraction.
 // The host restatement of the same algorithm is trajectory_planner_amd/host/src/polyTrajSolver.cpp.
 #include "vigo_internal.hpp"
@@ -24,6 +25,8 @@ constexpr int kMaxSeg = 10;    // segments per path supported on the device
 constexpr int kMaxBox = 1024;  // corridor boxes per path
 constexpr int kMaxFree = 40;   // free coefficients after the elimination (2 per segment at cont = 4)
 constexpr int kLanes = 64;
+constexpr double kHessPivotRel = 1e-9;    // reduced-Hessian pivots below this x its largest diagonal entry: singular
+constexpr size_t kMaxLds = 160 * 1024;   // dynamic + static LDS of one workgroup
 
 struct MinsnapArgs {
     int T, W, deg, diff, cont;
@@ -323,6 +326,32 @@ __global__ void __launch_bounds__(kLanes) k_minsnap(MinsnapArgs A) {
     }
     __syncthreads();
 
+    // ---- corridor boxes, PS.cpp:985-1012: centres on the straight leg at normalised times 0, dt, 2dt, .. <= 1 ----
+    if (cor && lane == 0) {
+        int nb = 0;
+        bool overflow = false;
+        for (int i = 0; i < K && !overflow; ++i) {
+            if (cor[i] == 0.0) continue;
+            const double duration = knots[i + 1] - knots[i];
+            const int num = (int)ceil(duration * A.corridor_res);
+            const double dt = 1.0 / num;
+            for (double tt = 0; tt <= 1.0; tt += dt) {
+                if (nb >= kMaxBox) { overflow = true; break; }
+                boxSeg[nb] = i;
+                boxT[nb] = tt;
+                ++nb;
+            }
+        }
+        s_nb = nb;
+        if (overflow) s_status = -1;
+    }
+    __syncthreads();
+    const int nb = s_nb;
+    if (s_status != 0) {
+        if (lane == 0) A.out_status[t] = s_status;
+        return;
+    }
+
     if (nf > 0) {
         // ---- reduced problem: PZ = P Z, H = Z'PZ, c = Z'(P x0) ----
         for (int idx = lane; idx < n * nf; idx += kLanes) {
@@ -353,10 +382,14 @@ __global__ void __launch_bounds__(kLanes) k_minsnap(MinsnapArgs A) {
         }
         __syncthreads();
         // right-looking Cholesky across the lanes (Hinv holds L for now): column j is scaled, then
-        // every lane updates its share of the trailing triangle
+        // every lane updates its share of the trailing triangle.  A singular H (differential degree 7 at two
+        // waypoints, say: the minimiser is not unique) leaves a pivot of rounding size, up to ~3e-12 of its diagonal,
+        // and a factor that is garbage; regular ones stay above ~4e-6.  Same threshold as the host solver.
+        double pivTol = 0.0;
+        for (int j = 0; j < nf; ++j) pivTol = fmax(pivTol, kHessPivotRel * Hinv[j * nf + j]);
         for (int j = 0; j < nf && s_status == 0; ++j) {
             const double djj = Hinv[j * nf + j];
-            if (!(djj > 0)) { if (lane == 0) s_status = -1; }
+            if (!(djj > pivTol)) { if (lane == 0) s_status = -1; }
             const double dj = sqrt(djj);
             __syncthreads();
             if (s_status != 0) break;
@@ -385,31 +418,6 @@ __global__ void __launch_bounds__(kLanes) k_minsnap(MinsnapArgs A) {
         for (int idx = lane; idx < nf * nf; idx += kLanes) Hinv[idx] = H[idx];
         __syncthreads();
 
-        // ---- corridor boxes, PS.cpp:985-1012: centres on the straight leg at normalised times 0, dt, 2dt, .. <= 1 ----
-        if (cor && lane == 0) {
-            int nb = 0;
-            bool overflow = false;
-            for (int i = 0; i < K && !overflow; ++i) {
-                if (cor[i] == 0.0) continue;
-                const double duration = knots[i + 1] - knots[i];
-                const int num = (int)ceil(duration * A.corridor_res);
-                const double dt = 1.0 / num;
-                for (double tt = 0; tt <= 1.0; tt += dt) {
-                    if (nb >= kMaxBox) { overflow = true; break; }
-                    boxSeg[nb] = i;
-                    boxT[nb] = tt;
-                    ++nb;
-                }
-            }
-            s_nb = nb;
-            if (overflow) s_status = -1;
-        }
-        __syncthreads();
-        const int nb = s_nb;
-        if (s_status != 0) {
-            if (lane == 0) A.out_status[t] = s_status;
-            return;
-        }
         // ---- per axis: Goldfarb-Idnani dual active set on  min 1/2 w'Hw + c'w,  a_k'w >= b_k ----
         // constraint k: box k>>1, side k&1 (0: lower bound, 1: upper bound)
         const int nc = 2 * nb;
@@ -647,6 +655,20 @@ __global__ void __launch_bounds__(kLanes) k_minsnap(MinsnapArgs A) {
             __syncthreads();
         }
     } else {
+        // fully determined (nf == 0): x0 is the only candidate; every box is verified, as the host solver does
+        int viol = 0;
+        for (int idx = lane; idx < nb * 3; idx += kLanes) {
+            const int b = idx / 3, axis = idx % 3, seg = boxSeg[b];
+            const double tt = boxT[b];
+            double val = 0.0;
+            for (int d = D - 1; d >= 0; --d) val = val * tt + x0[(seg * D + d) * 3 + axis];
+            const double cen = wpl[3 * seg + axis] + (wpl[3 * (seg + 1) + axis] - wpl[3 * seg + axis]) * tt;
+            if (val < cen - cor[seg] - 1e-9 || val > cen + cor[seg] + 1e-9) viol = 1;
+        }
+        if (__any(viol)) {
+            if (lane == 0) A.out_status[t] = -2;
+            return;
+        }
         for (int idx = lane; idx < n * 3; idx += kLanes) {
             const int i = idx / 3, axis = idx % 3;
             const int seg = i / D, d = i % D;
@@ -666,6 +688,15 @@ __global__ void __launch_bounds__(kLanes) k_minsnap(MinsnapArgs A) {
 size_t minsnap_lds_bytes(int W, int cont) { return (size_t)make_layout(W - 1, cont).total * sizeof(double) + 1024; }
 int minsnap_max_waypoints() { return kMaxSeg + 1; }
 
+// the shapes k_minsnap takes: one lane per equality row, at most kMaxFree free coefficients, everything in LDS
+bool minsnap_supported(int W, int deg, int diff, int cont) {
+    if (deg != kD - 1 || diff < 1 || diff > deg || W < 2 || W > kMaxSeg + 1 || cont < 2) return false;
+    const int K = W - 1;
+    if (K > 1 && cont > kLanes) return false;   // more than kLanes continuity rows alone (and no int overflow below)
+    const Layout L = make_layout(K, cont);
+    return L.me <= kLanes && L.nf >= 0 && L.nf <= kMaxFree && minsnap_lds_bytes(W, cont) <= kMaxLds;
+}
+
 int launch_minsnap(hipStream_t s, int T, int W, int deg, int diff, int cont, double vel, double corridor_res,
                    const double* wp, const double* corridor, const double* conds, double* out_coeffs, double* out_knots,
                    int32_t* out_status, LaunchState& L) {
@@ -673,7 +704,7 @@ int launch_minsnap(hipStream_t s, int T, int W, int deg, int diff, int cont, dou
     MinsnapArgs a{T, W, deg, diff, cont, vel, corridor_res, wp, corridor, conds, out_coeffs, out_knots, out_status};
     const size_t lds = minsnap_lds_bytes(W, cont) - 1024;
     if (!L.minsnap_attr_set) {   // per handle = per device (LaunchState), not a function static
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_minsnap), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);  // minus the static __shared__ scalars
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_minsnap), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds - 1024);  // minus the static __shared__ scalars
         if (e != hipSuccess) return (int)e;
         L.minsnap_attr_set = true;
     }

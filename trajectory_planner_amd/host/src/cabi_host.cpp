@@ -134,20 +134,32 @@ int vigo_host_astar(const unsigned char* vox, const int* dims, const double* ori
     return (int)path.size();
 }
 
-// min-snap through n_wp waypoints (xyz triples); corridor == NULL: equality-constrained only.
-// coeffs_out: 3 * (n_wp-1) * (deg+1) doubles (x block, y block, z block), knots_out: n_wp doubles.
-int vigo_host_minsnap(int n_wp, const double* wp, int deg, int diff, int cont, double vel, const double* corridor,
-                      double corridor_res, double* coeffs_out, double* knots_out) {
+// min-snap through n_wp waypoints (xyz triples); corridor == NULL: equality-constrained only.  conds: [4][3] initial
+// velocity, final velocity, initial acceleration, final acceleration (normalised-time derivatives, vigo_minsnap's
+// layout); NULL = zeros.  coeffs_out: 3 * (n_wp-1) * (deg+1) doubles (x block, y block, z block), knots_out: n_wp doubles.
+int vigo_host_minsnap_conds(int n_wp, const double* wp, int deg, int diff, int cont, double vel, const double* corridor,
+                            double corridor_res, const double* conds, double* coeffs_out, double* knots_out) {
     std::vector<trajPlanner::pose> path;
     for (int i = 0; i < n_wp; ++i) path.push_back(trajPlanner::pose(wp[3 * i], wp[3 * i + 1], wp[3 * i + 2]));
     trajPlanner::polyTrajSolver s(deg, diff, cont, vel);
     s.updatePath(path);
+    if (conds) {
+        s.updateInitVel(conds[0], conds[1], conds[2]);
+        s.updateEndVel(conds[3], conds[4], conds[5]);
+        s.updateInitAcc(conds[6], conds[7], conds[8]);
+        s.updateEndAcc(conds[9], conds[10], conds[11]);
+    }
     if (corridor) s.setCorridorConstraint(std::vector<double>(corridor, corridor + n_wp - 1), corridor_res);
     if (!s.solve()) return -1;
     const int n = (n_wp - 1) * (deg + 1);
     for (int a = 0; a < 3; ++a) std::memcpy(coeffs_out + (size_t)a * n, s.getSolution(a).data(), sizeof(double) * n);
     std::memcpy(knots_out, s.getTimeKnot().data(), sizeof(double) * n_wp);
     return 0;
+}
+
+int vigo_host_minsnap(int n_wp, const double* wp, int deg, int diff, int cont, double vel, const double* corridor,
+                      double corridor_res, double* coeffs_out, double* knots_out) {
+    return vigo_host_minsnap_conds(n_wp, wp, deg, diff, cont, vel, corridor, corridor_res, nullptr, coeffs_out, knots_out);
 }
 
 // trajPlanner::pwlTraj over n_wp poses (x, y, z, yaw): updatePath(path[, desired_vel], use_yaw), makePlan(traj, delT).
@@ -250,10 +262,12 @@ int vigo_host_poly_plan(int nx, int ny, int nz, const double* origin, double res
 // makePlan(): cfg as vigo_host_poly_plan (its `mode` entry is replaced by mode[i]); path i is wp[wp_off[i] ..
 // wp_off[i+1]) (xyz triples).  Per planner (batch, then solo): info[4] = valid, iterations, final path length (waypoints),
 // samples; traj [P][traj_cap][3] (first traj_cap samples).  secs_out[2]: seconds of makePlanBatch, of the P solo plans.
-// solo_traj / solo_info / secs_out may be NULL (no twins then).  -1 on bad arguments.
-int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
-                              const int32_t* wp_off, const double* wp, const double* cfg, const int32_t* mode, int traj_cap,
-                              double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out, double* secs_out) {
+// solo_traj / solo_info / secs_out may be NULL (no twins then).  diff / cont: differential_degree / continuity_degree of
+// every planner.  -1 on bad arguments.
+int vigo_host_poly_plan_batch_ex(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
+                                 const int32_t* wp_off, const double* wp, const double* cfg, const int32_t* mode, int diff, int cont,
+                                 int traj_cap, double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out,
+                                 double* secs_out) {
     if (P < 0 || !wp_off || !wp || !cfg || !mode || traj_cap < 0 || !traj_out || !info_out) return -1;
     auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
     std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
@@ -270,8 +284,8 @@ int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, doub
         nh.setParam("traj_timeout", cfg[10]);
         nh.setParam("mode", (double)mode[i]);
         nh.setParam("polynomial_degree", 7.0);
-        nh.setParam("differential_degree", 4.0);
-        nh.setParam("continuity_degree", 4.0);
+        nh.setParam("differential_degree", (double)diff);
+        nh.setParam("continuity_degree", (double)cont);
         std::unique_ptr<trajPlanner::polyTrajOctomap> p(new trajPlanner::polyTrajOctomap(nh));
         p->setMap(map);
         std::vector<trajPlanner::pose> path;
@@ -312,6 +326,13 @@ int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, doub
     }
     if (secs_out) secs_out[1] = solo_secs;
     return 0;
+}
+
+int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
+                              const int32_t* wp_off, const double* wp, const double* cfg, const int32_t* mode, int traj_cap,
+                              double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out, double* secs_out) {
+    return vigo_host_poly_plan_batch_ex(nx, ny, nz, origin, res, voxels, P, wp_off, wp, cfg, mode, 4, 4, traj_cap, traj_out, info_out,
+                                        solo_traj_out, solo_info_out, secs_out);
 }
 
 }  // extern "C"

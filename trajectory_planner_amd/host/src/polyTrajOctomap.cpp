@@ -326,9 +326,10 @@ static void installDeviceSolution(polyTrajSolver& solver, const double* co, int 
 // waypoint mode, whose paths grow as waypoints are inserted: the groups are re-formed every round), and every
 // candidate trajectory checked whole — samples, box sweep and segment attribution of checkCollisionTraj, PO.cpp:634-656
 // — by ONE vigo_traj_corridor_check launch (a trajectory it rejects is sampled and swept on the host that round).  The
-// returned trajectories are sampled on the host once, after the loop.  A path that outgrows the device QP (more
-// than 11 waypoints) is solved by the host QP inside the same round.  Time limit: timeout x (planners in the batch),
-// checked after a colliding round.  A failed device call ends the batch: every planner not yet valid falls back.
+// returned trajectories are sampled on the host once, after the loop.  A path shape the device QP does not take (more
+// than 11 waypoints, or more rows or LDS than the continuity degree leaves room for: vigo_minsnap_supported) and a
+// device QP status of -1 are solved by the host QP inside the same round.  Time limit: timeout x (planners in the
+// batch), checked after a colliding round.  A failed device call ends the batch: every planner not yet valid falls back.
 std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctomap*>& ps, std::vector<std::vector<pose>>& trajectories) {
     const size_t P = ps.size();
     std::vector<bool> result(P, false);
@@ -360,7 +361,7 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
     if (grp.empty()) return result;
     polyTrajOctomap* lead = ps[grp[0]];
     if (!lead->syncDevice()) return result;
-    const int D = 8, kMaxDevWaypoints = 11;
+    const int D = 8;
     const size_t G = grp.size();
     std::vector<PlanState> st;
     std::vector<bool> active(G, true);
@@ -380,7 +381,9 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
             polyTrajOctomap* p0 = ps[grp[g0]];
             const int W = (int)p0->path_.size(), K = W - 1;
             const bool adding = st[g0].addingWaypoints;
-            if (W > kMaxDevWaypoints) { p0->solveOnHost(st[g0]); continue; }   // beyond the device QP: the host QP, same algorithm
+            // a shape beyond the device QP (more than 11 waypoints, or too many rows / too little LDS for this continuity
+            // degree, vigo_minsnap_supported): the host QP, same algorithm
+            if (!vigo_minsnap_supported(W, 7, lead->diffDegree_, lead->continuityDegree_)) { p0->solveOnHost(st[g0]); continue; }
             std::vector<size_t> members{g0};
             for (size_t a = a0 + 1; a < act.size(); ++a) {
                 const size_t g = act[a];
@@ -399,9 +402,13 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
                               (const double*)bWp.p, adding ? nullptr : (const double*)bCor.p, nullptr, (double*)bCo.p, (double*)bKn.p,
                               (int32_t*)bSt.p) == VIGO_OK &&
                  bCo.download(hCo.data(), hCo.size() * 8) && bSt.download(hSt.data(), (size_t)T * 4);
-            // an infeasible corridor keeps the previous polynomial, like the reference
-            for (int a = 0; ok && a < T; ++a)
-                if (hSt[a] == 0) installDeviceSolution(*ps[grp[members[a]]]->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
+            // an infeasible corridor (-2) keeps the previous polynomial, like the reference; a numerical failure of the
+            // device QP (-1: more than 1024 corridor boxes, say) is solved by the host QP, which has no such limit
+            for (int a = 0; ok && a < T; ++a) {
+                const size_t g = members[a];
+                if (hSt[a] == 0) installDeviceSolution(*ps[grp[g]]->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
+                else if (hSt[a] == -1) ps[grp[g]]->solveOnHost(st[g]);
+            }
         }
         if (!ok) break;
         // ---- every candidate's whole trajectory checked by ONE vigo_traj_corridor_check launch: the installed

@@ -11,11 +11,17 @@
 namespace trajPlanner {
 
 // ---- small dense helpers (row-major) ------------------------------------------------------
-static bool cholesky(std::vector<double>& M, int n) {  // in place, lower
+constexpr double kHessPivotRel = 1e-9;    // the reduced Hessian's pivot threshold (vigo_minsnap.hip: the same)
+// in place, lower.  A pivot must exceed relTol x the largest diagonal entry: a reduced Hessian that is singular (a
+// differential degree above what the continuity rows leave determined, such as 7 at two waypoints) has a pivot of
+// rounding size, up to ~3e-12 of its diagonal, where the factor would be garbage; regular ones stay above ~4e-6
+static bool cholesky(std::vector<double>& M, int n, double relTol = 0.0) {
+    double tol = 0.0;
+    for (int j = 0; j < n; ++j) tol = std::max(tol, relTol * M[(size_t)j * n + j]);
     for (int j = 0; j < n; ++j) {
         double d = M[(size_t)j * n + j];
         for (int k = 0; k < j; ++k) d -= M[(size_t)j * n + k] * M[(size_t)j * n + k];
-        if (!(d > 0)) return false;
+        if (!(d > tol)) return false;
         d = std::sqrt(d);
         M[(size_t)j * n + j] = d;
         for (int i = j + 1; i < n; ++i) {
@@ -288,7 +294,7 @@ struct ReducedQP {
             }
         for (int a = 0; a < nf; ++a)
             for (int b = 0; b < a; ++b) H[(size_t)a * nf + b] = H[(size_t)b * nf + a] = 0.5 * (H[(size_t)a * nf + b] + H[(size_t)b * nf + a]);
-        if (!cholesky(H, nf)) return -1;
+        if (!cholesky(H, nf, kHessPivotRel)) return -1;                 // singular: the minimiser is not unique
         Hinv.assign((size_t)nf * nf, 0.0);
         std::vector<double> col(nf);
         for (int k = 0; k < nf; ++k) {
