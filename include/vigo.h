@@ -62,8 +62,9 @@ typedef enum {
     VIGO_ERR_UNSUPPORTED = -6    /* parameter combination not implemented             */
 } vigo_status_t;
 
-/* vigo_optimize additionally needs mem_size * (N-6) * 48 B (fp64) of LDS <= 160 KiB:
- * N <= 219 at mem_size 16; larger N returns VIGO_ERR_UNSUPPORTED_N. */
+/* vigo_optimize additionally needs its L-BFGS history in the 160 KiB LDS of a CU: for N > 128 (fp64 and fp64
+ * fast) mem_size * ((N-5) * 48 + 16) B, plus the alphas and the obstacle table.  That holds N <= 216 at mem_size 16
+ * (every N at mem_size <= 8, and every N in fp32); larger N returns VIGO_ERR_UNSUPPORTED_N. */
 enum { VIGO_MAX_CTRL_POINTS = 256, VIGO_MAX_MEM_SIZE = 16 };
 
 /* arithmetic mode of the solver / cost kernels */

@@ -22,13 +22,18 @@ def rel_err_per_traj(a, ref):
 
 
 class emulation:
-    """context manager: oracle in device-emulation mode for N control points"""
+    """context manager: oracle in device-emulation mode for N control points (fast=True: of VIGO_PREC_F64_FAST)"""
 
-    def __init__(self, N):
+    def __init__(self, N, fast=False):
         self.g, self.ppl = ol.emulation_shape(N)
+        self.fast = fast
 
     def __enter__(self):
+        if self.fast:
+            ol.oracle().vgo_set_emulation_fast(1)
         ol.set_emulation(self.g, self.ppl)
 
     def __exit__(self, *a):
         ol.set_emulation(0)
+        if self.fast:
+            ol.oracle().vgo_set_emulation_fast(0)
