@@ -447,6 +447,31 @@ int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32
                              double map_res, int flags, int32_t* out_status, int32_t* out_n, uint8_t* out_flag,
                              int32_t* out_first, int32_t* out_count, uint8_t* out_seg);
 
+/*
+ * Replaces: polyTrajOccMap::checkCollisionTraj(trajectory, delT, collisionSeg) (PM.cpp:524-546) on the trajectory
+ * polyTrajSolver::getTrajectory returns, for T whole trajectories at once: vigo_traj_corridor_check with another test.
+ *   seg_off, coeffs, knots, delT, endpoint   as vigo_traj_corridor_check (vigo_minsnap output concatenated is this layout)
+ * The rules: 1 clock, 2 segment, 3 endpoint and 5 blame are vigo_traj_corridor_check's, word for word (the sample at
+ * fl(t_j - k[i]) with pow as vigo_exact_pow: the fp64 pose vigo_poly_sample returns); rule 4 is replaced by
+ *   4' test      the fp64 pose as sampled, no float cast and no box: voxel floor((p - origin) / res) of the handle's grid
+ *                (as vigo_query_points); the sample collides iff bit 0 (inflated-occupied) AND bit 1 (unknown) are both
+ *                set there (PM.cpp:532, isInflatedOccupied && isUnknown).  Outside the grid every bit is set, so a pose
+ *                outside collides — a NaN or infinite coordinate included (x86 and the oracle agree: no flags argument).
+ *                The default pose (0, 0, 0) of samples before k[0] is tested like any other.
+ * Outputs: out_status, out_n, out_flag, out_first, out_count (may be NULL), out_seg exactly as vigo_traj_corridor_check;
+ * status and n of a trajectory are the same in both entries.
+ * How: the first and last kernels of vigo_traj_corridor_check (csrc/vigo_traj_core.hpp); between them a wave per run of
+ * samples, lanes striding the run, each pose looked up in the two bit planes, a 64-bit ballot per 64 samples for the
+ * run's flag, first hit and count.  No atomics on results.
+ * Scratch: vigo_traj_corridor_check's (the same layout, taken VIGO_TRAJ_CHUNK trajectories at a time).
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle, T < 0, S < 0, deg outside [0, 15], NULL arrays (out_count may be NULL;
+ * coeffs and out_seg may be NULL when S = 0; every per-trajectory array when T = 0); VIGO_ERR_NO_GRID before a grid.
+ * The grid origin need not lie on the key lattice (no octomap keys here).
+ */
+int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                          const double* knots, const double* delT, const double* endpoint, int32_t* out_status,
+                          int32_t* out_n, uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg);
+
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and
  *   run_first, run_len  int32[K]  segment i's samples are run_first[i] .. run_first[i] + run_len[i] - 1

@@ -700,6 +700,24 @@ int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32
     return VIGO_OK;
 }
 
+int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                          const double* knots, const double* delT, const double* endpoint, int32_t* out_status, int32_t* out_n,
+                          uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (T < 0 || S < 0 || deg < 0 || deg > 15 ||
+        (T > 0 && (!seg_off || !knots || !delT || !endpoint || !out_status || !out_n || !out_flag || !out_first)) ||
+        (S > 0 && (!coeffs || !out_seg)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_point_check: bad argument");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_point_check before vigo_set_grid");
+    if (T == 0 && S == 0) return VIGO_OK;
+    const int chunk = T < VIGO_TRAJ_CHUNK ? (T > 0 ? T : 1) : VIGO_TRAJ_CHUNK;
+    int rc = ensure_scratch(h, vigo::traj_ws_bytes(S, chunk));
+    if (rc != VIGO_OK) return rc;
+    VIGO_HIP(h, (hipError_t)vigo::launch_traj_point(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, delT, endpoint, out_status,
+                                                    out_n, out_flag, out_first, out_count, out_seg, h->scratch, chunk));
+    return VIGO_OK;
+}
+
 int vigo_poly_sample(vigo_handle_t h, int S, int deg, const double* coeffs, const int32_t* n_samp, const double* delT,
                      int stride, double* out_pos, float* out_pos_f32) {
     if (!h) return VIGO_ERR_INVALID_ARG;

@@ -137,6 +137,10 @@ int launch_traj_corridor(hipStream_t s, const GridView& g, int T, int S, int deg
                          const double* knots, const double* delT, const double* endpoint, const double box[3], double map_res,
                          int nonfinite, int32_t* out_status, int32_t* out_n, uint8_t* out_flag, int32_t* out_first,
                          int32_t* out_count, uint8_t* out_seg, void* ws, int T_chunk);
+// whole trajectories, point test (vigo_traj_point_check): the same workspace (traj_ws_bytes) and chunking
+int launch_traj_point(hipStream_t s, const GridView& g, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                      const double* knots, const double* delT, const double* endpoint, int32_t* out_status, int32_t* out_n,
+                      uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg, void* ws, int T_chunk);
 int launch_box_points(hipStream_t s, const GridView& g, int64_t M, const double* pts, const double box[3],
                       double map_res, uint8_t* out);
 // polyTrajSolver::getTrajectory for S segments: sample k of segment s at out[(s * stride + k) * 3] (fp64 and/or float)

@@ -2,159 +2,38 @@
 // trajectories, the checker of vigo_corridor_core.hpp in its trajectory mode (k_corridor<PASS, DEG7, true>).  A separate
 // translation unit, so that the instantiations vigo_corridor_check launches keep their code.
 #include "vigo_corridor_core.hpp"
-#include "vigo_internal.hpp"
-#include "vigo_traj_runs.hpp"
+#include "vigo_traj_core.hpp"
 
 namespace vigo {
 namespace {
 
 // ---- whole trajectories (vigo_traj_corridor_check): checkCollisionTraj of polyTrajOctomap, PO.cpp:634-656 ---------------
-// Three kernels around k_corridor<PASS, DEG7, true>: k_traj_runs (a thread per trajectory: status, sample count, clock
-// table, the segments' runs — vigo_traj_runs.hpp), the two passes (a workgroup per run), k_traj_finish (a thread per
-// trajectory: the leading default-pose run, the runs in segment order, the endpoint, the attribution).  No atomics on
-// results: every output has one writer.
-struct TrajWork {
-    const int32_t* seg_off;
-    const double* knots;
-    const double* delT;
-    const double* endpoint;
-    int T, S;
-    int t_lo, t_hi;
+// k_corridor<PASS, DEG7, true> (a workgroup per run) between the shared stages of vigo_traj_core.hpp: k_traj_runs before
+// it, k_traj_finish with the box sweep after it.
+
+// pose2Octomap's float cast and the box sweep (PO.cpp:547-589); a pose at NaN / infinity collides only with
+// VIGO_TRAJ_NONFINITE_COLLIDES
+struct BoxHit {
+    GridView g;
+    SweepConst C;
     int nonfinite;
-    const int* csr_bad;          // set by k_traj_csr: seg_off is no CSR over [0, S], every trajectory is rejected
-    ClockTable* clocks;          // [t_hi - t_lo]
-    int32_t* slot_status;        // [t_hi - t_lo] each
-    int32_t* slot_n;
-    int32_t* slot_lead;
-    int32_t* slot_end_seg;
-    int32_t* run_first;          // [S] each
-    int32_t* run_len;
-    int32_t* seg_traj;
-    int* todo;
-    uint8_t* run_flag;
-    int32_t* run_hit;            // first colliding sample of the run, local index, or -1
-    int32_t* run_count;
+    __device__ bool operator()(double x, double y, double z) const {
+        const bool finite = isfinite(x) && isfinite(y) && isfinite(z);
+        return (nonfinite && !finite) || box_sweep(g, C, (float)x, (float)y, (float)z, nullptr, nullptr);
+    }
 };
-
-__global__ void k_traj_csr(int T, int S, const int32_t* __restrict__ seg_off, int* bad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > T) return;
-    const int a = seg_off[i];
-    if (a < 0 || a > S || (i < T && a > seg_off[i + 1])) atomicOr(bad, 1);
-}
-
-__global__ void __launch_bounds__(64) k_traj_runs(TrajWork W) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    const int t = W.t_lo + slot;
-    if (t >= W.t_hi) return;
-    ClockTable& C = W.clocks[slot];
-    C.n = -1;
-    W.slot_n[slot] = 0;
-    W.slot_lead[slot] = 0;
-    W.slot_end_seg[slot] = -1;
-    if (*W.csr_bad) { W.slot_status[slot] = kTrajBadOffsets; return; }   // (segments left alone: nobody owns them)
-    const int a = W.seg_off[t], K = W.seg_off[t + 1] - a;
-    const double* k = W.knots + a + t;
-    const double d = W.delT[t];
-    int st = traj_knots_status(K, k);
-    int64_t n = 0;
-    if (st == kTrajOk) st = traj_sample_count(k[K], d, &n);
-    W.slot_status[slot] = st;
-    for (int i = 0; i < K; ++i) {
-        W.seg_traj[a + i] = t;
-        W.run_first[a + i] = 0;
-        W.run_len[a + i] = 0;
-        W.todo[a + i] = 0;
-        W.run_flag[a + i] = 0;
-        W.run_hit[a + i] = -1;
-        W.run_count[a + i] = 0;
-    }
-    if (st != kTrajOk) return;
-    (void)build_clock_table(d, (int)n, C);
-    int32_t lead, end_seg;
-    traj_runs(K, k, d, n, &C, &lead, W.run_first + a, W.run_len + a, 1, &end_seg);
-    W.slot_n[slot] = (int32_t)n;
-    W.slot_lead[slot] = lead;
-    W.slot_end_seg[slot] = end_seg;
-}
-
-__global__ void __launch_bounds__(64) k_traj_finish(GridView g, SweepConst C, TrajWork W, int32_t* __restrict__ out_status,
-                                                    int32_t* __restrict__ out_n, uint8_t* __restrict__ out_flag,
-                                                    int32_t* __restrict__ out_first, int32_t* __restrict__ out_count,
-                                                    uint8_t* __restrict__ out_seg) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    const int t = W.t_lo + slot;
-    if (t >= W.t_hi) return;
-    const int st = W.slot_status[slot];
-    out_status[t] = st;
-    int first = -1, count = 0;
-    if (st == kTrajOk) {
-        const int n = W.slot_n[slot], lead = W.slot_lead[slot];
-        // the leading run: samples before k[0], all at the default pose — one box check decides them all (no segment)
-        if (lead > 0 && box_sweep(g, C, 0.0f, 0.0f, 0.0f, nullptr, nullptr)) { first = 0; count = lead; }
-        const int a = W.seg_off[t], b = W.seg_off[t + 1];
-        for (int sg = a; sg < b; ++sg) {                      // runs in segment order = ascending sample indices
-            if (!W.run_flag[sg]) continue;
-            if (first < 0) first = W.run_first[sg] + W.run_hit[sg];
-            count += W.run_count[sg];
-            out_seg[sg] = 1;
-        }
-        // the endpoint (sample n): the last waypoint as given, attributed when its clock equals k[K]
-        const double* e = W.endpoint + (size_t)t * 3;
-        const bool finite = isfinite(e[0]) && isfinite(e[1]) && isfinite(e[2]);
-        if ((W.nonfinite && !finite) || box_sweep(g, C, (float)e[0], (float)e[1], (float)e[2], nullptr, nullptr)) {
-            if (first < 0) first = n;
-            ++count;
-            if (W.slot_end_seg[slot] >= 0) out_seg[a + W.slot_end_seg[slot]] = 1;
-        }
-        out_n[t] = n + 1;
-    } else {
-        out_n[t] = 0;
-    }
-    out_flag[t] = (uint8_t)(count > 0);
-    out_first[t] = first;
-    if (out_count) out_count[t] = count;
-}
 
 }  // namespace
 
-size_t traj_ws_bytes(int S, int T_chunk) {
-    const size_t seg = (size_t)S * (6 * sizeof(int32_t) + 1);
-    return (size_t)T_chunk * (sizeof(ClockTable) + 4 * sizeof(int32_t)) + seg + 64;
-}
+size_t traj_ws_bytes(int S, int T_chunk) { return traj_work_bytes(S, T_chunk); }
 
 int launch_traj_corridor(hipStream_t s, const GridView& g, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
                          const double* knots, const double* delT, const double* endpoint, const double box[3], double map_res,
                          int nonfinite, int32_t* out_status, int32_t* out_n, uint8_t* out_flag, int32_t* out_first,
                          int32_t* out_count, uint8_t* out_seg, void* ws, int T_chunk) {
-    if (S > 0) {
-        hipError_t e = hipMemsetAsync(out_seg, 0, (size_t)S, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (T <= 0) return hipSuccess;
-    // workspace: [T_chunk] clock tables, [T_chunk] x 4 per-trajectory ints, [S] x 6 per-segment ints, [S] flags, the CSR flag
-    char* p = static_cast<char*>(ws);
-    TrajWork W{};
-    W.seg_off = seg_off; W.knots = knots; W.delT = delT; W.endpoint = endpoint;
-    W.T = T; W.S = S; W.nonfinite = nonfinite;
-    W.clocks = reinterpret_cast<ClockTable*>(p); p += (size_t)T_chunk * sizeof(ClockTable);
-    W.slot_status = reinterpret_cast<int32_t*>(p); p += (size_t)T_chunk * 4;
-    W.slot_n = reinterpret_cast<int32_t*>(p); p += (size_t)T_chunk * 4;
-    W.slot_lead = reinterpret_cast<int32_t*>(p); p += (size_t)T_chunk * 4;
-    W.slot_end_seg = reinterpret_cast<int32_t*>(p); p += (size_t)T_chunk * 4;
-    W.run_first = reinterpret_cast<int32_t*>(p); p += (size_t)S * 4;
-    W.run_len = reinterpret_cast<int32_t*>(p); p += (size_t)S * 4;
-    W.seg_traj = reinterpret_cast<int32_t*>(p); p += (size_t)S * 4;
-    W.todo = reinterpret_cast<int*>(p); p += (size_t)S * 4;
-    W.run_hit = reinterpret_cast<int32_t*>(p); p += (size_t)S * 4;
-    W.run_count = reinterpret_cast<int32_t*>(p); p += (size_t)S * 4;
-    int* bad = reinterpret_cast<int*>(p); p += 4;
-    W.run_flag = reinterpret_cast<uint8_t*>(p);
-    W.csr_bad = bad;
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), s);
-    if (e == hipSuccess && S > 0) e = hipMemsetAsync(W.seg_traj, 0xff, (size_t)S * 4, s);   // -1: no trajectory (yet)
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_traj_csr, dim3((T + 1 + 255) / 256), dim3(256), 0, s, T, S, seg_off, bad);
+    TrajWork W;
+    hipError_t e = traj_prepare(s, ws, T, S, T_chunk, seg_off, knots, delT, endpoint, out_seg, W);
+    if (e != hipSuccess || T <= 0) return (int)e;
 
     const SweepConst sweep{{box[0], box[1], box[2]}, map_res, 1.0 / g.res};
     CorridorArgs A{};
@@ -183,8 +62,8 @@ int launch_traj_corridor(hipStream_t s, const GridView& g, int T, int S, int deg
                 hipLaunchKernelGGL((k_corridor<1, false, true>), dim3(S), dim3(kBlock), tile_bytes, s, g, A);
             }
         }
-        hipLaunchKernelGGL(k_traj_finish, dim3(nb), dim3(64), 0, s, g, sweep, W, out_status, out_n, out_flag, out_first,
-                           out_count, out_seg);
+        hipLaunchKernelGGL(k_traj_finish<BoxHit>, dim3(nb), dim3(64), 0, s, BoxHit{g, sweep, nonfinite}, W, out_status, out_n,
+                           out_flag, out_first, out_count, out_seg);
     }
     return (int)hipGetLastError();
 }

@@ -11,7 +11,7 @@
 //   segment i  t_j in (k[i], k[i+1]]   for i >= 1   (a sample exactly on an inner knot belongs to the earlier segment)
 // and every run boundary is a binary search over the exact clock.  The endpoint (sample n) has clock t_n >= k[K]; it is
 // attributed only when t_n == k[K], to the first segment whose end knot is k[K].
-// Compiled for host (vigo_traj_sample_runs, the tests) and device (k_traj_runs in vigo_traj_corridor.hip) alike.
+// Compiled for host (vigo_traj_sample_runs, the tests) and device (k_traj_runs in vigo_traj_core.hpp) alike.
 #pragma once
 
 #include "vigo_exact_time.hpp"

@@ -8,11 +8,13 @@
 #include <trajectory_planner/octomapBt.h>
 #include <trajectory_planner/path_search/astarOcc.h>
 #include <trajectory_planner/piecewiseLinearTraj.h>
+#include <trajectory_planner/polyTrajOccMap.h>
 #include <trajectory_planner/polyTrajOctomap.h>
 #include <trajectory_planner/polyTrajSolver.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 
@@ -198,6 +200,36 @@ int vigo_host_minsnap_soft(int n_wp, const double* wp, int deg, int diff, int co
     return 0;
 }
 
+// corridors, soft waypoint boxes and end conditions together, in polyTrajOccMap's call order (setCorridorConstraint,
+// then setSoftConstraint, PM.cpp:356-358): corridor / soft[3] / conds may each be NULL (not set); outputs as
+// vigo_host_minsnap_conds, knots always, an axis's coefficients only when its QP was solved.  Returns the mask of the
+// solved axes (bit a = axis a; 7 = all): solve() keeps the stale polynomial of an axis that fails, per axis.
+int vigo_host_minsnap_full(int n_wp, const double* wp, int deg, int diff, int cont, double vel, const double* corridor,
+                           double corridor_res, const double* soft, const double* conds, double* coeffs_out, double* knots_out) {
+    std::vector<trajPlanner::pose> path;
+    for (int i = 0; i < n_wp; ++i) path.push_back(trajPlanner::pose(wp[3 * i], wp[3 * i + 1], wp[3 * i + 2]));
+    trajPlanner::polyTrajSolver s(deg, diff, cont, vel);
+    s.updatePath(path);
+    if (conds) {
+        s.updateInitVel(conds[0], conds[1], conds[2]);
+        s.updateEndVel(conds[3], conds[4], conds[5]);
+        s.updateInitAcc(conds[6], conds[7], conds[8]);
+        s.updateEndAcc(conds[9], conds[10], conds[11]);
+    }
+    if (corridor) s.setCorridorConstraint(std::vector<double>(corridor, corridor + n_wp - 1), corridor_res);
+    if (soft) s.setSoftConstraint(soft[0], soft[1], soft[2]);
+    std::memcpy(knots_out, s.getTimeKnot().data(), sizeof(double) * n_wp);
+    s.solve();
+    const size_t n = (size_t)(n_wp - 1) * (deg + 1);
+    int mask = 0;
+    for (int a = 0; a < 3; ++a)
+        if (s.getSolution(a).size() == n) {
+            std::memcpy(coeffs_out + a * n, s.getSolution(a).data(), sizeof(double) * n);
+            mask |= 1 << a;
+        }
+    return mask;
+}
+
 // the same solve, then polyTrajSolver::getPose / getVel / getAcc at n_t times: out[n_t][9] = position, velocity, acceleration
 int vigo_host_minsnap_eval(int n_wp, const double* wp, int deg, int diff, int cont, double vel, int n_t, const double* t,
                            double* out) {
@@ -333,6 +365,207 @@ int vigo_host_poly_plan_batch(int nx, int ny, int nz, const double* origin, doub
                               double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out, double* secs_out) {
     return vigo_host_poly_plan_batch_ex(nx, ny, nz, origin, res, voxels, P, wp_off, wp, cfg, mode, 4, 4, traj_cap, traj_out, info_out,
                                         solo_traj_out, solo_info_out, secs_out);
+}
+
+// ---- trajPlanner::polyTrajOccMap (bspline_node's seed planner) ----
+// cfg[16]: the poly_traj/ keys in PM.cpp's order — polynomial_degree, differential_degree, continuity_degree,
+// desired_velocity, desired_acceleration, initial_radius, timeout, corridor_res, shrinking_factor, soft_constraint,
+// constraint_radius, sample_delta_time, maximum_iteration_num, use_pwl_failsafe — then the arguments of
+// updateDesiredVel and updateDesiredAcc calls made after construction.  NaN: the key is not set (PM.cpp's default) /
+// the call is not made.  conds: [4][3] start vel, end vel, start acc, end acc through updatePath(path, conditions), or
+// NULL (the defaults, zero).
+static std::unique_ptr<trajPlanner::polyTrajOccMap> makeOccPlanner(const std::shared_ptr<mapManager::occMap>& map, const double* cfg,
+                                                                    int n_wp, const double* wp, const double* conds) {
+    static const char* keys[14] = {"polynomial_degree", "differential_degree", "continuity_degree", "desired_velocity",
+                                   "desired_acceleration", "initial_radius", "timeout", "corridor_res", "shrinking_factor",
+                                   "soft_constraint", "constraint_radius", "sample_delta_time", "maximum_iteration_num",
+                                   "use_pwl_failsafe"};
+    ros::NodeHandle nh;
+    for (int k = 0; k < 14; ++k)
+        if (!std::isnan(cfg[k])) nh.setParam(std::string("poly_traj/") + keys[k], cfg[k]);
+    std::unique_ptr<trajPlanner::polyTrajOccMap> p(new trajPlanner::polyTrajOccMap(nh));
+    p->setMap(map);
+    if (!std::isnan(cfg[14])) p->updateDesiredVel(cfg[14]);
+    if (!std::isnan(cfg[15])) p->updateDesiredAcc(cfg[15]);
+    nav_msgs::Path path;
+    for (int i = 0; i < n_wp; ++i) {
+        geometry_msgs::PoseStamped ps;
+        ps.pose.position.x = wp[3 * i]; ps.pose.position.y = wp[3 * i + 1]; ps.pose.position.z = wp[3 * i + 2];
+        path.poses.push_back(ps);
+    }
+    if (conds) {
+        std::vector<Eigen::Vector3d> c;
+        for (int k = 0; k < 4; ++k) c.push_back(Eigen::Vector3d(conds[3 * k], conds[3 * k + 1], conds[3 * k + 2]));
+        p->updatePath(path, c);
+    } else {
+        p->updatePath(path);
+    }
+    return p;
+}
+
+static std::shared_ptr<mapManager::occMap> denseMap(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels) {
+    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    return map;
+}
+
+static void copyXyz(const std::vector<trajPlanner::pose>& traj, int cap, double* out) {
+    const int n = (int)traj.size() < cap ? (int)traj.size() : cap;
+    for (int k = 0; k < n; ++k) { out[3 * k] = traj[k].x; out[3 * k + 1] = traj[k].y; out[3 * k + 2] = traj[k].z; }
+}
+
+// One polyTrajOccMap on a dense byte grid, planned alone on the host (no GPU).  mode 1: makePlan(trajectory, true),
+// 0: makePlan(trajectory, false), 2: makePlan(trajectory) (no bool).  traj_out: the first traj_cap samples (xyz);
+// gt_dt > 0: getTrajectory(gt_dt) afterwards into gt_out (first traj_cap poses).  info_out[8]: makePlan's result,
+// iterations (QP solves), samples, getDuration(), seconds of makePlan, getTrajectory poses, getPos(getDuration()) x / y.
+int vigo_host_occ_plan(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int n_wp,
+                       const double* wp, const double* cfg, const double* conds, int mode, int traj_cap, double* traj_out,
+                       double gt_dt, double* gt_out, double* info_out) {
+    if (n_wp < 0 || (n_wp > 0 && !wp) || !cfg || traj_cap < 0 || (traj_cap > 0 && !traj_out) || !info_out) return -1;
+    auto p = makeOccPlanner(denseMap(nx, ny, nz, origin, res, voxels), cfg, n_wp, wp, conds);
+    std::vector<trajPlanner::pose> traj;
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool r = mode == 2 ? p->makePlan(traj) : p->makePlan(traj, mode != 0);
+    info_out[4] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    copyXyz(traj, traj_cap, traj_out);
+    info_out[0] = r ? 1.0 : 0.0;
+    info_out[1] = p->getIterations();
+    info_out[2] = (double)traj.size();
+    info_out[3] = p->getDuration();
+    info_out[5] = 0.0;
+    if (gt_dt > 0 && gt_out) {
+        const nav_msgs::Path g = p->getTrajectory(gt_dt);
+        info_out[5] = (double)g.poses.size();
+        const int n = (int)g.poses.size() < traj_cap ? (int)g.poses.size() : traj_cap;
+        for (int k = 0; k < n; ++k) {
+            gt_out[3 * k] = g.poses[k].pose.position.x; gt_out[3 * k + 1] = g.poses[k].pose.position.y; gt_out[3 * k + 2] = g.poses[k].pose.position.z;
+        }
+    }
+    const Eigen::Vector3d e = p->getPos(p->getDuration());
+    info_out[6] = e(0);
+    info_out[7] = e(1);
+    return 0;
+}
+
+// polyTrajOccMap::makePlanBatch of P planners on one map (path i = wp[wp_off[i] .. wp_off[i+1]), cfg [P][16] and conds
+// [P][4][3] as vigo_host_occ_plan, conds may be NULL), and each planner's twin planned alone with makePlan(trajectory,
+// corridor).  Per planner (batch, then solo): info[5] = verdict, iterations, samples, getDuration(), getPos(getDuration()).x;
+// traj [P][traj_cap][3].  secs_out[2]: seconds of makePlanBatch, of the P solo plans.  solo_* / secs_out may be NULL.
+int vigo_host_occ_plan_batch(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
+                             const int32_t* wp_off, const double* wp, const double* cfg, const double* conds, int corridor,
+                             int traj_cap, double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out,
+                             double* secs_out) {
+    if (P < 0 || !wp_off || !wp || !cfg || traj_cap < 0 || !traj_out || !info_out) return -1;
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    auto make = [&](int i) {
+        return makeOccPlanner(map, cfg + 16 * (size_t)i, wp_off[i + 1] - wp_off[i], wp + 3 * (size_t)wp_off[i],
+                              conds ? conds + 12 * (size_t)i : nullptr);
+    };
+    auto report = [&](trajPlanner::polyTrajOccMap& p, bool r, const std::vector<trajPlanner::pose>& traj, int i, double* tr, double* info) {
+        copyXyz(traj, traj_cap, tr + (size_t)i * traj_cap * 3);
+        info[5 * i] = r ? 1.0 : 0.0;
+        info[5 * i + 1] = p.getIterations();
+        info[5 * i + 2] = (double)traj.size();
+        info[5 * i + 3] = p.getDuration();
+        info[5 * i + 4] = p.getPos(p.getDuration())(0);
+    };
+    std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> own;
+    std::vector<trajPlanner::polyTrajOccMap*> ps;
+    for (int i = 0; i < P; ++i) { own.push_back(make(i)); ps.push_back(own.back().get()); }
+    std::vector<std::vector<trajPlanner::pose>> trajs;
+    auto t0 = std::chrono::steady_clock::now();
+    const std::vector<bool> r = trajPlanner::polyTrajOccMap::makePlanBatch(ps, corridor != 0, &trajs);
+    if (secs_out) secs_out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 0; i < P; ++i) report(*ps[i], r[i], trajs[i], i, traj_out, info_out);
+    if (!solo_traj_out || !solo_info_out) return 0;
+    double solo_secs = 0.0;
+    for (int i = 0; i < P; ++i) {
+        auto p = make(i);
+        std::vector<trajPlanner::pose> traj;
+        t0 = std::chrono::steady_clock::now();
+        const bool ri = p->makePlan(traj, corridor != 0);
+        solo_secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        report(*p, ri, traj, i, solo_traj_out, solo_info_out);
+    }
+    if (secs_out) secs_out[1] = solo_secs;
+    return 0;
+}
+
+// bspline_node's per-click sequence (src/bspline_node.cpp:317-378) for P start/goal pairs se[P][2][3] on one map: the
+// polyTrajOccMap seeds (makePlanBatch(false), or each planner's makePlan(false) when solo), getTrajectory(dt) and the
+// inputPathCheck search (dt from getInitTs(), x 0.8, at most 50 ms), then bsplineTraj::updatePathBatch and
+// makePlanBatch (solo: updatePath and makePlan per planner).  poly_cfg[16] as vigo_host_occ_plan; bsp_cfg[6]:
+// distance_threshold, min_height, max_height, max_obstacle_size[3] (bspline_traj/ keys), velocity and acceleration
+// limits of both planners from poly_cfg's desired_velocity / desired_acceleration.  Outputs per pair: the seed
+// (adjustedInputPolyTraj) seed_out[P][seed_cap][3] with seed_n[P] poses and seed_dt[P]; status[P] = 0 updatePath refused
+// the seed, 1 updated but makePlan failed, 2 planned.
+int vigo_host_occ_seed_chain(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P,
+                             const double* se, const double* poly_cfg, const double* bsp_cfg, int solo, int seed_cap,
+                             double* seed_out, int32_t* seed_n, double* seed_dt, int32_t* status) {
+    if (P < 0 || !se || !poly_cfg || !bsp_cfg || seed_cap < 0 || !seed_out || !seed_n || !seed_dt || !status) return -1;
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    const double vel = std::isnan(poly_cfg[3]) ? 1.0 : poly_cfg[3], acc = std::isnan(poly_cfg[4]) ? 1.0 : poly_cfg[4];
+    ros::NodeHandle bnh;
+    bnh.setParam("bspline_traj/distance_threshold", bsp_cfg[0]);
+    bnh.setParam("bspline_traj/min_height", bsp_cfg[1]);
+    bnh.setParam("bspline_traj/max_height", bsp_cfg[2]);
+    bnh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{bsp_cfg[3], bsp_cfg[4], bsp_cfg[5]});
+    bnh.setParam("bspline_traj/max_path_length", 1000.0);
+    const std::vector<Eigen::Vector3d> cond(4, Eigen::Vector3d(0, 0, 0));
+    std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> polys;
+    std::vector<std::unique_ptr<trajPlanner::bsplineTraj>> bsps;
+    std::vector<trajPlanner::polyTrajOccMap*> pp;
+    std::vector<trajPlanner::bsplineTraj*> bp;
+    for (int i = 0; i < P; ++i) {
+        double c[16];
+        std::copy(poly_cfg, poly_cfg + 16, c);
+        c[14] = vel;   // polyTraj->updateDesiredVel(desiredVel); updateDesiredAcc(desiredAcc) (bspline_node.cpp:223-224)
+        c[15] = acc;
+        const double zero[12] = {};
+        polys.push_back(makeOccPlanner(map, c, 2, se + 6 * (size_t)i, zero));   // updatePath(waypointsMsg, startEndConditions)
+        pp.push_back(polys.back().get());
+        bsps.emplace_back(new trajPlanner::bsplineTraj(bnh));
+        bsps.back()->setMap(map);
+        bsps.back()->updateMaxVel(vel);
+        bsps.back()->updateMaxAcc(acc);
+        bp.push_back(bsps.back().get());
+    }
+    if (solo) for (auto* p : pp) p->makePlan(false);
+    else trajPlanner::polyTrajOccMap::makePlanBatch(pp, false);
+    std::vector<nav_msgs::Path> seeds(P);
+    for (int i = 0; i < P; ++i) {
+        double dt = bp[i]->getInitTs(), finalTime = 0.0;
+        const auto t0 = std::chrono::steady_clock::now();
+        while (ros::ok()) {
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= 0.05) break;
+            const nav_msgs::Path input = pp[i]->getTrajectory(dt);
+            if (bp[i]->inputPathCheck(input, seeds[i], dt, finalTime)) break;
+            dt *= 0.8;
+        }
+        seed_dt[i] = dt;
+        seed_n[i] = (int32_t)seeds[i].poses.size();
+        const int n = seed_n[i] < seed_cap ? seed_n[i] : seed_cap;
+        for (int k = 0; k < n; ++k) {
+            double* o = seed_out + ((size_t)i * seed_cap + k) * 3;
+            o[0] = seeds[i].poses[k].pose.position.x; o[1] = seeds[i].poses[k].pose.position.y; o[2] = seeds[i].poses[k].pose.position.z;
+        }
+    }
+    std::vector<bool> up(P), planned(P, false);
+    if (solo) {
+        for (int i = 0; i < P; ++i) {
+            up[i] = bp[i]->updatePath(seeds[i], cond);
+            if (up[i]) planned[i] = bp[i]->makePlan();
+        }
+    } else {
+        up = trajPlanner::bsplineTraj::updatePathBatch(bp, seeds, std::vector<std::vector<Eigen::Vector3d>>(P, cond));
+        std::vector<trajPlanner::bsplineTraj*> ready;
+        std::vector<int> idx;
+        for (int i = 0; i < P; ++i) if (up[i]) { ready.push_back(bp[i]); idx.push_back(i); }
+        const std::vector<bool> r = trajPlanner::bsplineTraj::makePlanBatch(ready);
+        for (size_t k = 0; k < idx.size(); ++k) planned[idx[k]] = r[k];
+    }
+    for (int i = 0; i < P; ++i) status[i] = !up[i] ? 0 : planned[i] ? 2 : 1;
+    return 0;
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 
 #include "../../../include/vigo.h"
 #include "devbuf.h"
+#include "polyBatch.h"
 
 using std::cout;
 using std::endl;
@@ -108,9 +109,7 @@ const std::vector<double>& polyTrajOctomap::timeKnots() {
     return pwlKnots_;
 }
 
-static void appendXyz(const std::vector<pose>& pts, std::vector<double>& xyz) {
-    for (const pose& q : pts) { xyz.push_back(q.x); xyz.push_back(q.y); xyz.push_back(q.z); }
-}
+using vigo_host::appendXyz;
 
 bool polyTrajOctomap::sweepPoints(const std::vector<pose>& pts, std::vector<uint8_t>& flags) {
     flags.assign(pts.size(), 1);
@@ -309,17 +308,7 @@ void polyTrajOctomap::makePlan(std::vector<pose>& trajectory, double delT) {
     findValidTraj_ = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
 }
 
-// one planner's block [K][3][8] of vigo_minsnap's coefficients, installed as the solver's per-axis solution
-static void installDeviceSolution(polyTrajSolver& solver, const double* co, int K) {
-    const int D = 8;
-    std::vector<double> axis[3];
-    for (int c = 0; c < 3; ++c) {
-        axis[c].resize((size_t)K * D);
-        for (int sgm = 0; sgm < K; ++sgm)
-            for (int d = 0; d < D; ++d) axis[c][sgm * D + d] = co[((size_t)sgm * 3 + c) * D + d];
-    }
-    solver.installSolution(axis[0], axis[1], axis[2]);
-}
+using vigo_host::installDeviceSolution;
 
 // makePlan() of many planners in lock-step: the planning loop above, with the QPs of each round grouped by (waypoint
 // count, mode) into ONE vigo_minsnap launch per group (corridor boxes for the corridor mode, none for the adding-

@@ -410,6 +410,33 @@ class Vigo:
             C.c_void_p(count.data_ptr()), C.c_void_p(seg.data_ptr())), "vigo_traj_corridor_check")
         return status, n, flag, first, count, seg
 
+    def traj_point_check(self, seg_off, coeffs, knots, delT, endpoint):
+        """vigo_traj_point_check: traj_corridor_check's arguments and outputs, the test being the point lookup of
+        polyTrajOccMap (bits 0 and 1 of the pose's voxel both set) -> (status, n, flag, first, count, seg)"""
+        _shape(seg_off, (None,), "seg_off")
+        T = seg_off.shape[0] - 1
+        if T < 0:
+            raise ValueError("seg_off: needs T + 1 >= 1 entries")
+        _shape(coeffs, (None, 3, None), "coeffs")
+        S, _, d1 = coeffs.shape
+        _shape(knots, (S + T,), "knots")
+        _shape(delT, (T,), "delT")
+        _shape(endpoint, (T, 3), "endpoint")
+        d = self.device
+        status = torch.empty(T, dtype=torch.int32, device=d)
+        n = torch.empty(T, dtype=torch.int32, device=d)
+        flag = torch.empty(T, dtype=torch.uint8, device=d)
+        first = torch.empty(T, dtype=torch.int32, device=d)
+        count = torch.empty(T, dtype=torch.int32, device=d)
+        seg = torch.empty(S, dtype=torch.uint8, device=d)
+        self._check(self._lib.vigo_traj_point_check(
+            self._h, T, S, d1 - 1, _ptr(seg_off, torch.int32, "seg_off", d), _ptr(coeffs, torch.float64, "coeffs", d),
+            _ptr(knots, torch.float64, "knots", d), _ptr(delT, torch.float64, "delT", d),
+            _ptr(endpoint, torch.float64, "endpoint", d), C.c_void_p(status.data_ptr()), C.c_void_p(n.data_ptr()),
+            C.c_void_p(flag.data_ptr()), C.c_void_p(first.data_ptr()), C.c_void_p(count.data_ptr()),
+            C.c_void_p(seg.data_ptr())), "vigo_traj_point_check")
+        return status, n, flag, first, count, seg
+
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
         (pos f64 [S,stride,3] or None, pos f32 [S,stride,3] or None); rows k >= n_samp[s] are left untouched (zero)."""
