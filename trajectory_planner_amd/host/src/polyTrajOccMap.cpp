@@ -6,7 +6,6 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include <chrono>
 #include <cmath>
 #include <iostream>
 
@@ -18,8 +17,6 @@ using std::cout;
 using std::endl;
 
 namespace trajPlanner {
-
-static double nowSec() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // PM.cpp:10-18
 polyTrajOccMap::polyTrajOccMap(const ros::NodeHandle& nh) : nh_(nh) {
@@ -161,7 +158,7 @@ polyTrajOccMap::PlanState polyTrajOccMap::begin() {
     trajSolver_->updateEndAcc(endAcc_.linear.x, endAcc_.linear.y, endAcc_.linear.z);
     PlanState s;
     s.corridor.assign(path_.size() - 1, initR_);
-    s.t0 = nowSec();
+    s.t0 = vigo_host::nowSec();
     findValidTraj_ = false;
     lastIterations_ = 0;
     return s;
@@ -229,7 +226,7 @@ bool polyTrajOccMap::makePlan(std::vector<pose>& trajectory, bool corridorConstr
     PlanState s = begin();
     bool valid = false;
     while (ros::ok() && !valid) {
-        if (nowSec() - s.t0 >= timeout_) {   // PM.cpp:349-353: tested at the top of each round
+        if (vigo_host::nowSec() - s.t0 >= timeout_) {   // PM.cpp:349-353: tested at the top of each round
             cout << "[minSnapTraj]: Timeout!" << endl;
             break;
         }
@@ -250,24 +247,17 @@ bool polyTrajOccMap::makePlan(std::vector<pose>& trajectory, bool corridorConstr
     return valid;
 }
 
-// PM.cpp:524-546: t accumulates delT per sample; a sample collides when the map says inflated-occupied AND unknown (a
-// reference quirk, SURVEY Appendix B, kept); it blames the first time-knot interval containing t (inclusive)
+// PM.cpp:524-546: a sample collides when the map says inflated-occupied AND unknown (a reference quirk, SURVEY Appendix B,
+// kept); the blame is collisionSegments' (polyBatch.h)
 bool polyTrajOccMap::checkCollisionTraj(const std::vector<pose>& trajectory, double delT, std::set<int>& collisionSeg) {
     collisionSeg.clear();
     if (!trajSolver_) return false;
-    const std::vector<double> timeKnot = trajSolver_->getTimeKnot();
-    double t = 0;
-    bool hasCollision = false;
+    std::vector<uint8_t> flags;
     for (const pose& p : trajectory) {
         const Eigen::Vector3d pEig(p.x, p.y, p.z);
-        if (map_ && map_->isInflatedOccupied(pEig) && map_->isUnknown(pEig)) {
-            hasCollision = true;
-            for (size_t i = 0; i + 1 < timeKnot.size(); ++i)
-                if (t >= timeKnot[i] && t <= timeKnot[i + 1]) { collisionSeg.insert((int)i); break; }
-        }
-        t += delT;
+        flags.push_back(map_ && map_->isInflatedOccupied(pEig) && map_->isUnknown(pEig));
     }
-    return hasCollision;
+    return vigo_host::collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT, collisionSeg);
 }
 
 // PM.cpp:548-552
@@ -309,20 +299,17 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
         for (size_t i : grp) result[i] = ps[i]->makePlan(out[i], corridorConstraint);
         return result;
     }
-    const int D = 8;
     const size_t G = grp.size();
     std::vector<PlanState> st;
     std::vector<bool> active(G, true), valid(G, false);
     for (size_t g = 0; g < G; ++g) st.push_back(ps[grp[g]]->begin());
-    static thread_local vigo_host::StagingBuf bWp, bCor, bCnd, bCo, bKn, bSt;
-    static thread_local vigo_host::StagingBuf cOff, cCo, cKn, cDt, cEp, cSt, cN, cFl, cFi, cSeg;
     bool ok = true;
     while (ok) {
         std::vector<size_t> act;
         for (size_t g = 0; g < G; ++g) {
             if (!active[g]) continue;
             polyTrajOccMap* p = ps[grp[g]];
-            if (nowSec() - st[g].t0 >= p->timeout_ * (double)G) {   // PM.cpp:349-353
+            if (vigo_host::nowSec() - st[g].t0 >= p->timeout_ * (double)G) {   // PM.cpp:349-353
                 cout << "[minSnapTraj]: Timeout!" << endl;
                 active[g] = false;
                 continue;
@@ -337,7 +324,7 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
             if (solved[g0]) continue;
             solved[g0] = true;
             polyTrajOccMap* p0 = ps[grp[g0]];
-            const int W = (int)p0->path_.size(), K = W - 1;
+            const int W = (int)p0->path_.size();
             if (p0->softConstraint_ || !vigo_minsnap_supported(W, 7, p0->diffDegree_, p0->continuityDegree_)) {
                 p0->solveOnHost(corridorConstraint, st[g0]);
                 continue;
@@ -353,30 +340,18 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
                     solved[g] = true;
                 }
             }
-            const int T = (int)members.size();
-            std::vector<double> hWp, hCor, hCnd, hCo((size_t)T * K * 3 * D);
-            std::vector<int32_t> hSt(T);
+            std::vector<vigo_host::QpMember> qp;
             for (size_t g : members) {
                 const polyTrajOccMap* p = ps[grp[g]];
-                vigo_host::appendXyz(p->path_, hWp);
-                if (corridorConstraint) hCor.insert(hCor.end(), st[g].corridor.begin(), st[g].corridor.end());
-                for (const geometry_msgs::Twist* c : {&p->initVel_, &p->endVel_, &p->initAcc_, &p->endAcc_}) {
-                    hCnd.push_back(c->linear.x); hCnd.push_back(c->linear.y); hCnd.push_back(c->linear.z);
-                }
+                qp.push_back({&p->path_, corridorConstraint ? &st[g].corridor : nullptr, {&p->initVel_, &p->endVel_, &p->initAcc_, &p->endAcc_}, 0, {}});
             }
-            ok = bWp.upload(hWp.data(), hWp.size() * 8) && (!corridorConstraint || bCor.upload(hCor.data(), hCor.size() * 8)) &&
-                 bCnd.upload(hCnd.data(), hCnd.size() * 8) && bCo.alloc(hCo.size() * 8) && bKn.alloc((size_t)T * W * 8) &&
-                 bSt.alloc((size_t)T * 4) &&
-                 vigo_minsnap(lead->dev_, T, W, 7, p0->diffDegree_, p0->continuityDegree_, p0->desiredVel_, p0->corridorRes_,
-                              (const double*)bWp.p, corridorConstraint ? (const double*)bCor.p : nullptr, (const double*)bCnd.p,
-                              (double*)bCo.p, (double*)bKn.p, (int32_t*)bSt.p) == VIGO_OK &&
-                 bCo.download(hCo.data(), hCo.size() * 8) && bSt.download(hSt.data(), (size_t)T * 4);
-            for (int a = 0; ok && a < T; ++a) {
+            ok = vigo_host::minsnapGroupOnDevice(lead->dev_, p0->diffDegree_, p0->continuityDegree_, p0->desiredVel_, p0->corridorRes_, qp);
+            for (size_t a = 0; ok && a < members.size(); ++a) {
                 const size_t g = members[a];
                 polyTrajOccMap* p = ps[grp[g]];
-                if (hSt[a] == 0) {
+                if (qp[a].status == 0) {
                     if (corridorConstraint) p->trajSolver_->setCorridorConstraint(st[g].corridor, p->corridorRes_);
-                    vigo_host::installDeviceSolution(*p->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
+                    p->trajSolver_->installSolution(qp[a].sol[0], qp[a].sol[1], qp[a].sol[2]);
                 } else {
                     p->solveOnHost(corridorConstraint, st[g]);   // -1 numerical, -2 infeasible: the host QP decides
                 }
@@ -384,9 +359,7 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
         }
         if (!ok) break;
         // ---- without corridors: one solve, valid without any check (PM.cpp:373-377) ----
-        std::vector<size_t> chk;
-        std::vector<int32_t> segOff(1, 0);
-        std::vector<double> hCo, hKn, hDt, hEp;
+        std::vector<vigo_host::TrajCheck> cand;
         for (size_t g : act) {
             polyTrajOccMap* p = ps[grp[g]];
             active[g] = corridorConstraint;
@@ -399,49 +372,25 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
                 valid[g] = true;
                 continue;
             }
-            const std::vector<double>& kn = p->trajSolver_->getTimeKnot();
-            const int K = (int)kn.size() - 1;
-            for (int sgm = 0; sgm < K; ++sgm)
-                for (int c = 0; c < 3; ++c) {
-                    const std::vector<double>& sol = p->trajSolver_->getSolution(c);
-                    hCo.insert(hCo.end(), sol.begin() + (size_t)sgm * D, sol.begin() + (size_t)(sgm + 1) * D);
-                }
-            hKn.insert(hKn.end(), kn.begin(), kn.end());
-            hDt.push_back(p->delT_);
-            hEp.push_back(p->path_.back().x); hEp.push_back(p->path_.back().y); hEp.push_back(p->path_.back().z);
-            segOff.push_back(segOff.back() + K);
-            chk.push_back(g);
+            cand.push_back({g, p->trajSolver_.get(), p->delT_, p->path_.back(), 0, false, {}});
         }
-        const int Tc = (int)chk.size(), S = segOff.back();
-        if (Tc == 0) continue;
         // ---- every candidate checked whole by ONE vigo_traj_point_check launch; verdicts and segment masks come back ----
-        std::vector<int32_t> hStat(Tc);
-        std::vector<uint8_t> hFlag(Tc), hSeg(S);
-        ok = cOff.upload(segOff.data(), segOff.size() * 4) && cCo.upload(hCo.data(), hCo.size() * 8) &&
-             cKn.upload(hKn.data(), hKn.size() * 8) && cDt.upload(hDt.data(), hDt.size() * 8) && cEp.upload(hEp.data(), hEp.size() * 8) &&
-             cSt.alloc((size_t)Tc * 4) && cN.alloc((size_t)Tc * 4) && cFl.alloc((size_t)Tc) && cFi.alloc((size_t)Tc * 4) &&
-             cSeg.alloc((size_t)S) &&
-             vigo_traj_point_check(lead->dev_, Tc, S, 7, (const int32_t*)cOff.p, (const double*)cCo.p, (const double*)cKn.p,
-                                   (const double*)cDt.p, (const double*)cEp.p, (int32_t*)cSt.p, (int32_t*)cN.p, (uint8_t*)cFl.p,
-                                   (int32_t*)cFi.p, nullptr, (uint8_t*)cSeg.p) == VIGO_OK &&
-             cSt.download(hStat.data(), (size_t)Tc * 4) && cFl.download(hFlag.data(), (size_t)Tc) && cSeg.download(hSeg.data(), (size_t)S);
+        ok = vigo_host::checkTrajectoriesOnDevice(cand, [&](int T, int S, const int32_t* segOff, const double* co, const double* kn,
+                                                            const double* dt, const double* ep, int32_t* status, int32_t* n,
+                                                            uint8_t* flag, int32_t* first, uint8_t* seg) {
+            return vigo_traj_point_check(lead->dev_, T, S, 7, segOff, co, kn, dt, ep, status, n, flag, first, nullptr, seg) == VIGO_OK;
+        });
         if (!ok) cout << "[minSnapTraj]: device trajectory check failed: " << vigo_last_error(lead->dev_) << endl;
-        for (int a = 0; ok && a < Tc; ++a) {
-            const size_t g = chk[a];
+        for (size_t a = 0; ok && a < cand.size(); ++a) {
+            const size_t g = cand[a].who;
             polyTrajOccMap* p = ps[grp[g]];
-            std::set<int> collisionSeg;
-            bool collides;
-            if (hStat[a] != VIGO_TRAJ_OK) {        // a trajectory the device entry rejects: sampled and checked on the host
+            if (cand[a].status != VIGO_TRAJ_OK) {   // a trajectory the device entry rejects: sampled and checked on the host
                 std::vector<pose> traj;
                 p->trajSolver_->getTrajectory(traj, p->delT_);
-                collides = p->checkCollisionTraj(traj, p->delT_, collisionSeg);
-            } else {
-                collides = hFlag[a] != 0;
-                for (int sgm = 0; sgm < segOff[a + 1] - segOff[a]; ++sgm)
-                    if (hSeg[segOff[a] + sgm]) collisionSeg.insert(sgm);
+                cand[a].collides = p->checkCollisionTraj(traj, p->delT_, cand[a].segments);   // (clears the segments first)
             }
-            valid[g] = !collides;
-            active[g] = p->advance(st[g], collides, collisionSeg);
+            valid[g] = !cand[a].collides;
+            active[g] = p->advance(st[g], cand[a].collides, cand[a].segments);
         }
     }
     // the returned trajectories: sampled once, from the last polynomial (the reference returns the last candidate when
@@ -458,15 +407,7 @@ std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap
 
 // PM.cpp:554-571
 void polyTrajOccMap::trajMsgConverter(const std::vector<pose>& trajectoryTemp, nav_msgs::Path& trajectory) {
-    trajectory.poses.clear();
-    for (const pose& p : trajectoryTemp) {
-        geometry_msgs::PoseStamped ps;
-        ps.header.frame_id = "map";
-        ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
-        ps.pose.orientation = quaternion_from_rpy(0, 0, p.yaw);
-        trajectory.poses.push_back(ps);
-    }
-    trajectory.header.frame_id = "map";
+    vigo_host::posesToPathMsg(trajectoryTemp, trajectory);
 }
 
 // PM.cpp:434-446: the polynomial sampled every dt while t <= getDuration() (with use_pwl_failsafe and no valid

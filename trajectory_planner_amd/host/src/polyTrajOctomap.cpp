@@ -5,7 +5,6 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include <chrono>
 #include <cmath>
 #include <iostream>
 
@@ -17,8 +16,6 @@ using std::cout;
 using std::endl;
 
 namespace trajPlanner {
-
-static double nowSec() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 polyTrajOctomap::polyTrajOctomap() : polyTrajOctomap(ros::NodeHandle()) {}
 
@@ -109,14 +106,12 @@ const std::vector<double>& polyTrajOctomap::timeKnots() {
     return pwlKnots_;
 }
 
-using vigo_host::appendXyz;
-
 bool polyTrajOctomap::sweepPoints(const std::vector<pose>& pts, std::vector<uint8_t>& flags) {
     flags.assign(pts.size(), 1);
     if (pts.empty()) return true;
     if (!syncDevice()) return false;
     std::vector<double> xyz;
-    appendXyz(pts, xyz);
+    vigo_host::appendXyz(pts, xyz);
     const bool ok = sweepXyz(xyz, flags);
     if (!ok) cout << "[Trajectory Planner INFO]: device box sweep failed: " << vigo_last_error(dev_) << endl;
     return ok;
@@ -167,27 +162,12 @@ bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, st
     return has;
 }
 
-// PO.cpp:634-656: t accumulates delT per sample; a colliding sample blames the first time-knot interval containing t
-// (inclusive)
-static bool collisionSegments(const uint8_t* flags, size_t n, const std::vector<double>& knots, double delT, std::set<int>& collisionSeg) {
-    double t = 0;
-    bool has = false;
-    for (size_t k = 0; k < n; ++k) {
-        if (flags[k]) {
-            has = true;
-            for (size_t i = 0; i + 1 < knots.size(); ++i)
-                if (t >= knots[i] && t <= knots[i + 1]) { collisionSeg.insert((int)i); break; }
-        }
-        t += delT;
-    }
-    return has;
-}
-
+// PO.cpp:634-656
 bool polyTrajOctomap::checkCollisionTraj(const std::vector<pose>& trajectory, double delT, std::set<int>& collisionSeg) {
     collisionSeg.clear();
     std::vector<uint8_t> f;
     sweepPoints(trajectory, f);
-    return collisionSegments(f.data(), f.size(), timeKnots(), delT, collisionSeg);
+    return vigo_host::collisionSegments(f.data(), f.size(), timeKnots(), delT, collisionSeg);
 }
 
 // ---- the fallback of PO.cpp:308-318, :373-383, :528-541: a fresh pwlTraj over the waypoints (its own 1.0 m/s and
@@ -222,7 +202,7 @@ polyTrajOctomap::PlanState polyTrajOctomap::begin(bool addingWaypoints) {
     PlanState s;
     s.addingWaypoints = addingWaypoints;
     if (!addingWaypoints) s.corridor.assign(path_.size() - 1, initR_);
-    s.t0 = nowSec();
+    s.t0 = vigo_host::nowSec();
     findValidTraj_ = false;
     lastIterations_ = 0;
     return s;
@@ -265,7 +245,7 @@ void polyTrajOctomap::finish(std::vector<pose>& trajectory, double delT) {
 // advance() on per-sample sweep flags of a host-sampled trajectory (collisionSegments, PO.cpp:634-656)
 bool polyTrajOctomap::advanceOnFlags(PlanState& s, const std::vector<uint8_t>& flags, double delT) {
     std::set<int> collisionSeg;
-    const bool collides = collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT, collisionSeg);
+    const bool collides = vigo_host::collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT, collisionSeg);
     return advance(s, collides, collisionSeg);
 }
 
@@ -277,7 +257,7 @@ void polyTrajOctomap::planOnHost(bool addingWaypoints, std::vector<pose>& trajec
     PlanState s = begin(addingWaypoints);
     std::vector<uint8_t> flags;
     do {
-        if (nowSec() - s.t0 >= timeout_) { cout << "[Trajectory Planner INFO]: Timeout." << endl; break; }
+        if (vigo_host::nowSec() - s.t0 >= timeout_) { cout << "[Trajectory Planner INFO]: Timeout." << endl; break; }
         solveOnHost(s);
         // with no polynomial to keep (the very first corridor was infeasible, and shrinking it cannot help; a degenerate
         // path such as coincident waypoints) there is nothing to sample: not found
@@ -307,8 +287,6 @@ void polyTrajOctomap::makePlan(std::vector<pose>& trajectory, double delT) {
     std::set<int> collisionSeg;
     findValidTraj_ = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
 }
-
-using vigo_host::installDeviceSolution;
 
 // makePlan() of many planners in lock-step: the planning loop above, with the QPs of each round grouped by (waypoint
 // count, mode) into ONE vigo_minsnap launch per group (corridor boxes for the corridor mode, none for the adding-
@@ -350,12 +328,10 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
     if (grp.empty()) return result;
     polyTrajOctomap* lead = ps[grp[0]];
     if (!lead->syncDevice()) return result;
-    const int D = 8;
     const size_t G = grp.size();
     std::vector<PlanState> st;
     std::vector<bool> active(G, true);
     for (size_t g = 0; g < G; ++g) st.push_back(ps[grp[g]]->begin(ps[grp[g]]->mode_));
-    static thread_local vigo_host::StagingBuf bWp, bCor, bCo, bKn, bSt;   // reused by every batch of this thread
     bool ok = true;
     while (ok) {
         std::vector<size_t> act;
@@ -368,7 +344,7 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
             if (solved[g0]) continue;
             solved[g0] = true;
             polyTrajOctomap* p0 = ps[grp[g0]];
-            const int W = (int)p0->path_.size(), K = W - 1;
+            const int W = (int)p0->path_.size();
             const bool adding = st[g0].addingWaypoints;
             // a shape beyond the device QP (more than 11 waypoints, or too many rows / too little LDS for this continuity
             // degree, vigo_minsnap_supported): the host QP, same algorithm
@@ -378,34 +354,20 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
                 const size_t g = act[a];
                 if (!solved[g] && (int)ps[grp[g]]->path_.size() == W && st[g].addingWaypoints == adding) { members.push_back(g); solved[g] = true; }
             }
-            const int T = (int)members.size();
-            std::vector<double> hWp, hCor, hCo((size_t)T * K * 3 * D);
-            std::vector<int32_t> hSt(T);
-            for (size_t g : members) {
-                appendXyz(ps[grp[g]]->path_, hWp);
-                if (!adding) hCor.insert(hCor.end(), st[g].corridor.begin(), st[g].corridor.end());
-            }
-            ok = bWp.upload(hWp.data(), hWp.size() * 8) && (adding || bCor.upload(hCor.data(), hCor.size() * 8)) &&
-                 bCo.alloc(hCo.size() * 8) && bKn.alloc((size_t)T * W * 8) && bSt.alloc((size_t)T * 4) &&
-                 vigo_minsnap(lead->dev_, T, W, 7, lead->diffDegree_, lead->continuityDegree_, lead->desiredVel_, lead->corridorRes_,
-                              (const double*)bWp.p, adding ? nullptr : (const double*)bCor.p, nullptr, (double*)bCo.p, (double*)bKn.p,
-                              (int32_t*)bSt.p) == VIGO_OK &&
-                 bCo.download(hCo.data(), hCo.size() * 8) && bSt.download(hSt.data(), (size_t)T * 4);
+            std::vector<vigo_host::QpMember> qp;
+            for (size_t g : members) qp.push_back({&ps[grp[g]]->path_, adding ? nullptr : &st[g].corridor, {}, 0, {}});
+            ok = vigo_host::minsnapGroupOnDevice(lead->dev_, lead->diffDegree_, lead->continuityDegree_, lead->desiredVel_, lead->corridorRes_, qp);
             // an infeasible corridor (-2) keeps the previous polynomial, like the reference; a numerical failure of the
             // device QP (-1: more than 1024 corridor boxes, say) is solved by the host QP, which has no such limit
-            for (int a = 0; ok && a < T; ++a) {
+            for (size_t a = 0; ok && a < members.size(); ++a) {
                 const size_t g = members[a];
-                if (hSt[a] == 0) installDeviceSolution(*ps[grp[g]]->trajSolver_, &hCo[(size_t)a * K * 3 * D], K);
-                else if (hSt[a] == -1) ps[grp[g]]->solveOnHost(st[g]);
+                if (qp[a].status == 0) ps[grp[g]]->trajSolver_->installSolution(qp[a].sol[0], qp[a].sol[1], qp[a].sol[2]);
+                else if (qp[a].status == -1) ps[grp[g]]->solveOnHost(st[g]);
             }
         }
         if (!ok) break;
-        // ---- every candidate's whole trajectory checked by ONE vigo_traj_corridor_check launch: the installed
-        // polynomials (device-QP coefficients as downloaded, host-QP ones, kept ones) with the solver's own knots, the
-        // step and the appended last waypoint; only the verdicts come back ----
-        std::vector<size_t> chk;
-        std::vector<int32_t> segOff(1, 0);
-        std::vector<double> hCo, hKn, hDt, hEp;
+        // ---- every candidate's whole trajectory checked by ONE vigo_traj_corridor_check launch ----
+        std::vector<vigo_host::TrajCheck> cand;
         for (size_t g : act) {
             polyTrajOctomap* p = ps[grp[g]];
             if (!p->trajSolver_->hasSolution()) {      // nothing to check (see planOnHost): not found
@@ -413,54 +375,32 @@ std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctom
                 active[g] = false;
                 continue;
             }
-            const std::vector<double>& kn = p->trajSolver_->getTimeKnot();
-            const int K = (int)kn.size() - 1;
-            for (int sgm = 0; sgm < K; ++sgm)
-                for (int c = 0; c < 3; ++c) {
-                    const std::vector<double>& sol = p->trajSolver_->getSolution(c);
-                    hCo.insert(hCo.end(), sol.begin() + (size_t)sgm * D, sol.begin() + (size_t)(sgm + 1) * D);
-                }
-            hKn.insert(hKn.end(), kn.begin(), kn.end());
-            hDt.push_back(p->delT_);
-            hEp.push_back(p->path_.back().x); hEp.push_back(p->path_.back().y); hEp.push_back(p->path_.back().z);
-            segOff.push_back(segOff.back() + K);
-            chk.push_back(g);
+            cand.push_back({g, p->trajSolver_.get(), p->delT_, p->path_.back(), 0, false, {}});
         }
-        const int Tc = (int)chk.size(), S = segOff.back();
-        if (Tc == 0) continue;
-        static thread_local vigo_host::StagingBuf cOff, cCo, cKn, cDt, cEp, cSt, cN, cFl, cFi, cSeg;
-        std::vector<int32_t> hStat(Tc);
-        std::vector<uint8_t> hFlag(Tc), hSeg(S);
         const double box[3] = {lead->collisionBox_[0], lead->collisionBox_[1], lead->collisionBox_[2]};
-        ok = cOff.upload(segOff.data(), segOff.size() * 4) && cCo.upload(hCo.data(), hCo.size() * 8) &&
-             cKn.upload(hKn.data(), hKn.size() * 8) && cDt.upload(hDt.data(), hDt.size() * 8) && cEp.upload(hEp.data(), hEp.size() * 8) &&
-             cSt.alloc((size_t)Tc * 4) && cN.alloc((size_t)Tc * 4) && cFl.alloc((size_t)Tc) && cFi.alloc((size_t)Tc * 4) &&
-             cSeg.alloc((size_t)S) &&
-             vigo_traj_corridor_check(lead->dev_, Tc, S, 7, (const int32_t*)cOff.p, (const double*)cCo.p, (const double*)cKn.p,
-                                      (const double*)cDt.p, (const double*)cEp.p, box, lead->mapRes_, VIGO_TRAJ_NONFINITE_COLLIDES,
-                                      (int32_t*)cSt.p, (int32_t*)cN.p, (uint8_t*)cFl.p, (int32_t*)cFi.p, nullptr,
-                                      (uint8_t*)cSeg.p) == VIGO_OK &&
-             cSt.download(hStat.data(), (size_t)Tc * 4) && cFl.download(hFlag.data(), (size_t)Tc) && cSeg.download(hSeg.data(), (size_t)S);
+        ok = vigo_host::checkTrajectoriesOnDevice(cand, [&](int T, int S, const int32_t* segOff, const double* co, const double* kn,
+                                                            const double* dt, const double* ep, int32_t* status, int32_t* n,
+                                                            uint8_t* flag, int32_t* first, uint8_t* seg) {
+            return vigo_traj_corridor_check(lead->dev_, T, S, 7, segOff, co, kn, dt, ep, box, lead->mapRes_, VIGO_TRAJ_NONFINITE_COLLIDES,
+                                            status, n, flag, first, nullptr, seg) == VIGO_OK;
+        });
         if (!ok) cout << "[Trajectory Planner INFO]: device trajectory check failed: " << vigo_last_error(lead->dev_) << endl;
-        for (int a = 0; ok && a < Tc; ++a) {
-            const size_t g = chk[a];
+        for (size_t a = 0; ok && a < cand.size(); ++a) {
+            const size_t g = cand[a].who;
             polyTrajOctomap* p = ps[grp[g]];
             bool more;
-            if (hStat[a] != VIGO_TRAJ_OK) {            // a trajectory the device entry rejects: sampled and swept on the host
+            if (cand[a].status != VIGO_TRAJ_OK) {   // a trajectory the device entry rejects: sampled and swept on the host
                 std::vector<pose>& traj = trajectories[grp[g]];
                 std::vector<uint8_t> flags;
                 std::vector<double> pts;
                 p->trajSolver_->getTrajectory(traj, p->delT_);
-                appendXyz(traj, pts);
+                vigo_host::appendXyz(traj, pts);
                 lead->sweepXyz(pts, flags);            // a failed sweep leaves every flag set: the loop goes on
                 more = p->advanceOnFlags(st[g], flags, p->delT_);
             } else {
-                std::set<int> collisionSeg;
-                for (int sgm = 0; sgm < segOff[a + 1] - segOff[a]; ++sgm)
-                    if (hSeg[segOff[a] + sgm]) collisionSeg.insert(sgm);
-                more = p->advance(st[g], hFlag[a] != 0, collisionSeg);
+                more = p->advance(st[g], cand[a].collides, cand[a].segments);
             }
-            if (!more || nowSec() - st[g].t0 >= p->timeout_ * (double)G) active[g] = false;
+            if (!more || vigo_host::nowSec() - st[g].t0 >= p->timeout_ * (double)G) active[g] = false;
         }
     }
     // the returned trajectories: sampled once, from the polynomial that was found valid; the PWL fallback otherwise
@@ -485,15 +425,7 @@ void polyTrajOctomap::makePlan(nav_msgs::Path& trajectory, double delT) {
 }
 
 void polyTrajOctomap::trajMsgConverter(const std::vector<pose>& trajectoryTemp, nav_msgs::Path& trajectory) {
-    trajectory.poses.clear();
-    for (const pose& p : trajectoryTemp) {
-        geometry_msgs::PoseStamped ps;
-        ps.header.frame_id = "map";
-        ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
-        ps.pose.orientation = quaternion_from_rpy(0, 0, p.yaw);
-        trajectory.poses.push_back(ps);
-    }
-    trajectory.header.frame_id = "map";
+    vigo_host::posesToPathMsg(trajectoryTemp, trajectory);
 }
 
 // PO.cpp:658-677
