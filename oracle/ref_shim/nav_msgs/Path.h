@@ -1,0 +1,2 @@
+// ref_shim/nav_msgs/Path.h — TEST INFRASTRUCTURE ONLY: the inert ROS stand-ins live in one file, ros/ros.h.
+#include <ros/ros.h>

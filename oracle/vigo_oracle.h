@@ -10,11 +10,13 @@
  *     include/trajectory_planner/solver/lbfgs.hpp compiled from /root/reference into
  *     oracle/_ref/libref_lbfgs.so (oracle/ref_lbfgs_harness.cpp), and by golden traces
  *     under tests/golden/ generated from it.
- *   - cost terms, B-spline evaluation, collision gates, corridor checker: restated from
- *     bsplineTraj.cpp / bspline.cpp / polyTrajOctomap.cpp, which cannot be built here
- *     (need Eigen, ROS, map_manager, octomap).  The reference ships no fixtures or
- *     assertions for them => PARITY UNPINNED by reference data; pinned only by closed-form
- *     known answers and finite-difference checks in tests/.
+ *   - cost terms, B-spline evaluation, collision gates, findCollisionSeg, the fit, whole solves: PINNED bit-for-bit against the
+ *     verbatim bspline.cpp / bsplineTraj.cpp compiled against the stand-in headers of oracle/ref_shim into
+ *     oracle/_ref/libref_bspline.so (oracle/ref_bspline_harness.cpp), and by tests/golden/bspline_ref.npz generated
+ *     from it.  Shim choices stay unpinned: the order of Eigen's three-element reductions ((x0+x1)+x2 assumed),
+ *     colPivHouseholderQr's pivot order.
+ *   - corridor checker (polyTrajOctomap.cpp, needs octomap): PARITY UNPINNED by reference data; pinned only by
+ *     closed-form known answers in tests/.
  *   - voxel map semantics (mapManager::occMap, octomap::OcTree): the dependency is not in
  *     /root/reference; the contract below is this build's own (include/vigo.h).
  */

@@ -1,8 +1,9 @@
 """Generates tests/golden/*.npz.  Run in the authoring container (needs /root/reference for the
 verbatim lbfgs.hpp shim oracle/_ref/libref_lbfgs.so):
 
-    python tests/golden/make_golden.py            (all three files)
+    python tests/golden/make_golden.py            (all four files; bspline_ref.npz first, so a missing library stops it early)
     python tests/golden/make_golden.py checks     (lbfgs_ref_checks.npz only)
+    python tests/golden/make_golden.py bspline_ref (bspline_ref.npz only; needs oracle/_ref/libref_bspline.so)
 
 lbfgs_ref.npz   small ViGO problems solved by the REFERENCE's own lbfgs_optimize
                 (solver/lbfgs.hpp, compiled verbatim) driving the oracle's cost restatement:
@@ -16,6 +17,9 @@ lbfgs_ref_checks.npz  the REFERENCE's lbfgs_optimize on the problems of tests/te
                 fx, sha-256 of x and of optData_.controlPoints; sha-256 of the seeded inputs) and
                 test_generic_objectives_and_parameter_errors_match_reference (status, evaluations, fx, x;
                 the codes of the parameter errors), so those tests hold where the shim cannot be built.
+bspline_ref.npz  the cases of tests/bspline_ref_cases.py (cost terms, solves, spline evaluation, gates, fit) and what
+                the COMPILED reference bspline.cpp / bsplineTraj.cpp (oracle/ref_bspline_harness.cpp over oracle/ref_shim)
+                computes on them, with the branch counts of the inputs; bulk arrays no kernel test needs as sha-256.
 The fixtures are data (inputs and expected outputs); no reference source text is stored.
 """
 import ctypes as C
@@ -82,8 +86,6 @@ def checks():
 
 
 def main():
-    if sys.argv[1:] == ["checks"]:
-        return checks()
     world = synth.make_box_world(synth.SEED_BASE + 2, n=128, n_boxes=60, centre_range=5.5, z_range=2.0)
     out = {}
     cases = [(12, 0, 50), (20, 2, 50), (32, 0, 50), (32, 1, 200), (40, 0, 50), (64, 2, 50)]
@@ -129,5 +131,26 @@ def main():
     checks()
 
 
+def bspline_ref():
+    import bspline_ref_cases as brc
+    assert ol.ref_bspline() is not None, "oracle/_ref/libref_bspline.so is not built"
+    d = brc.build_inputs()
+    counts = brc.branch_counts(d)
+    low = [k for k in brc.BRANCHES if counts.get(k, 0) < brc.MIN_HITS] + [k for k in brc.ON_BOUNDS if counts.get(k, 0) < 1]
+    assert not low, f"coverage condition not met: { {k: counts.get(k, 0) for k in low} }"
+    d["branch_names"] = np.array(sorted(counts))
+    d["branch_counts"] = np.array([counts[k] for k in sorted(counts)], dtype=np.int64)
+    d.update(brc.reference_outputs(d, order=0))
+    path = os.path.join(HERE, "bspline_ref.npz")
+    np.savez_compressed(path, **d)
+    print(f"wrote bspline_ref.npz: {os.path.getsize(path)} bytes; branch counts {counts}")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "checks":
+        checks()
+    elif len(sys.argv) > 1 and sys.argv[1] == "bspline_ref":
+        bspline_ref()
+    else:
+        bspline_ref()
+        main()

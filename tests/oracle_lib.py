@@ -1,5 +1,5 @@
-"""ctypes bindings of the CPU oracle (oracle/libvigo_oracle.so) and of the verbatim-reference
-L-BFGS shim (oracle/_ref/libref_lbfgs.so).  TEST INFRASTRUCTURE: imported by tests/,
+"""ctypes bindings of the CPU oracle (oracle/libvigo_oracle.so) and of the two verbatim-reference libraries
+(oracle/_ref/libref_lbfgs.so, oracle/_ref/libref_bspline.so).  TEST INFRASTRUCTURE: imported by tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg only."""
 import ctypes as C
 import os
@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "libvigo_oracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libref_lbfgs.so")
+REF_BSPLINE_SO = os.path.join(ORACLE_DIR, "_ref", "libref_bspline.so")
 
 import sys
 sys.path.insert(0, ROOT)
@@ -109,6 +110,169 @@ def ref():
                                          C.c_void_p]
         _ref = L
     return _ref
+
+
+_ref_bspline = None
+
+
+def ref_bspline():
+    """The verbatim reference bspline.cpp / astarOcc.cpp / bsplineTraj.cpp compiled against oracle/ref_shim
+    (oracle/ref_bspline_harness.cpp), or None when it was never built."""
+    global _ref_bspline
+    if _ref_bspline is None:
+        if not os.path.exists(REF_BSPLINE_SO):
+            return None
+        L = C.CDLL(REF_BSPLINE_SO)
+        vp = C.c_void_p
+        L.rbs_set_reduction_order.argtypes = [C.c_int]
+        L.rbs_create.restype = vp
+        L.rbs_create.argtypes = [_dp]
+        L.rbs_destroy.argtypes = [vp]
+        L.rbs_set_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, _up]
+        L.rbs_set_ctrl.argtypes = [vp, C.c_int, _dp]
+        L.rbs_get_ctrl.argtypes = [vp, _dp]
+        L.rbs_set_guides.argtypes = [vp, _ip, _dp]
+        L.rbs_set_obstacles.argtypes = [vp, C.c_int, _dp]
+        L.rbs_set_weights.argtypes = [vp, _dp]
+        L.rbs_term.restype = C.c_double
+        L.rbs_term.argtypes = [vp, C.c_int, _dp]
+        L.rbs_cost.restype = C.c_double
+        L.rbs_cost.argtypes = [vp, C.c_int, _dp, _dp]
+        L.rbs_optimize.restype = C.c_int
+        L.rbs_optimize.argtypes = [vp]
+        L.rbs_optimize_iters.restype = C.c_int
+        L.rbs_optimize_iters.argtypes = [vp, C.c_int, _dp, _dp]
+        L.rbs_bspline_at.argtypes = [C.c_int, _dp, C.c_double, C.c_int, C.c_double, _dp]
+        L.rbs_eval_traj.restype = C.c_int
+        L.rbs_eval_traj.argtypes = [vp, C.c_double, _dp, C.c_int]
+        L.rbs_fit.restype = C.c_int
+        L.rbs_fit.argtypes = [C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
+        for name in ("rbs_has_collision", "rbs_has_dynamic_collision"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [vp]
+        L.rbs_has_collision_pos.restype = C.c_int
+        L.rbs_has_collision_pos.argtypes = [vp, _dp]
+        L.rbs_find_collision_seg.restype = C.c_int
+        L.rbs_find_collision_seg.argtypes = [vp, _ip, C.c_int]
+        L.rbs_prologue.restype = C.c_int
+        L.rbs_prologue.argtypes = [vp, _ip, _ip, _dp, _ip, _dp, C.c_int]
+        _ref_bspline = L
+    return _ref_bspline
+
+
+class RefBsplineTraj:
+    """One trajPlanner::bsplineTraj of the compiled reference.  P: VigoParams (weights, thresholds, ts_ctrl, ...);
+    max_vel / max_obstacle_size / not_check_ratio have no VigoParams field."""
+
+    def __init__(self, P, vox, origin, res, max_vel=1.0, max_obstacle_size=(0.4, 0.4, 0.4), not_check_ratio=0.0):
+        self.L = ref_bspline()
+        p = np.array([P.ts, P.dthresh, max_vel, 1.0, P.w_distance, P.w_smoothness, P.w_feasibility, P.w_dynamic,
+                      float(P.plan_in_z), P.min_height, P.max_height, P.uncertain_factor, P.pred_horizon,
+                      P.dist_thresh_dynamic, 7.0, *max_obstacle_size, P.ts_ctrl, not_check_ratio], dtype=np.float64)
+        self.h = self.L.rbs_create(_d(p))
+        v = np.ascontiguousarray(vox, dtype=np.uint8)
+        o = np.ascontiguousarray(origin, dtype=np.float64)
+        self.L.rbs_set_map(self.h, v.shape[0], v.shape[1], v.shape[2], _d(o), float(res), _u(v))
+        self.N = 0
+
+    def close(self):
+        if self.h:
+            self.L.rbs_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_case(self, ctrl, goff=None, gpv=None, obs=None, w=None):
+        c = _c(ctrl, np.float64)
+        self.N = c.shape[0]
+        self.L.rbs_set_ctrl(self.h, self.N, _d(c))
+        if goff is not None and gpv is not None and len(gpv):
+            self.L.rbs_set_guides(self.h, _i(_c(goff, np.int32)), _d(_c(gpv, np.float64)))
+        o = np.zeros((0, 9)) if obs is None else _c(obs, np.float64)
+        self.L.rbs_set_obstacles(self.h, o.shape[0], _d(o))
+        if w is not None:
+            self.L.rbs_set_weights(self.h, _d(_c(w, np.float64)))
+
+    def ctrl(self):
+        out = np.zeros((self.N, 3))
+        self.L.rbs_get_ctrl(self.h, _d(out))
+        return out
+
+    def term(self, which):
+        g = np.zeros((self.N, 3))
+        return self.L.rbs_term(self.h, which, _d(g)), g
+
+    def cost(self, x):
+        xx = _c(x, np.float64)
+        g = np.zeros_like(xx)
+        return self.L.rbs_cost(self.h, xx.size, _d(xx), _d(g)), g
+
+    def optimize(self):
+        return self.L.rbs_optimize(self.h)
+
+    def optimize_iters(self, iters):
+        x, fx = np.zeros((self.N - 6, 3)), np.zeros(1)
+        st = self.L.rbs_optimize_iters(self.h, int(iters), _d(x), _d(fx))
+        return st, x, fx[0]
+
+    def eval_traj(self, dt=0.0, cap=1 << 16):
+        out = np.zeros((cap, 3))
+        n = self.L.rbs_eval_traj(self.h, float(dt), _d(out), cap)
+        return n, out[:min(n, cap)]
+
+    def has_collision(self):
+        pos = np.zeros(3)
+        return self.L.rbs_has_collision(self.h), self.L.rbs_has_collision_pos(self.h, _d(pos)), pos
+
+    def has_dynamic_collision(self):
+        return self.L.rbs_has_dynamic_collision(self.h)
+
+    def find_collision_seg(self, cap=256):
+        seg = np.zeros((cap, 2), dtype=np.int32)
+        n = self.L.rbs_find_collision_seg(self.h, _i(seg), cap)
+        return seg[:n].copy()
+
+    def prologue(self, cap=200000):
+        seg, poff, goff = np.zeros((cap, 2), dtype=np.int32), np.zeros(cap + 1, dtype=np.int32), np.zeros(self.N + 1, dtype=np.int32)
+        ppts, gpv = np.zeros((cap, 3)), np.zeros((cap, 6))
+        n = self.L.rbs_prologue(self.h, _i(seg), _i(poff), _d(ppts), _i(goff), _d(gpv), cap)
+        if n < 0:
+            return n, None, None, None, None
+        npath = n
+        return n, seg[:n].copy(), [ppts[poff[i]:poff[i + 1]].copy() for i in range(npath)], goff, gpv[:goff[self.N]].copy()
+
+
+def ref_bspline_at(ctrl, ts, deriv, t):
+    c = _c(ctrl, np.float64)
+    out = np.zeros(3)
+    ref_bspline().rbs_bspline_at(c.shape[0], _d(c), float(ts), int(deriv), float(t), _d(out))
+    return out
+
+
+def ref_bspline_fit(points, ts, cond):
+    """reference parameterizeToBspline -> (ctrl [K+2,3], A [(K+4),(K+2)], b [3,K+4])"""
+    pts, cd = _c(points, np.float64), _c(cond, np.float64)
+    K = pts.shape[0]
+    ctrl, A, b = np.zeros((K + 2, 3)), np.zeros((K + 4, K + 2)), np.zeros((3, K + 4))
+    rc = ref_bspline().rbs_fit(K, float(ts), _d(pts), _d(cd), _d(ctrl), _d(A), _d(b))
+    assert rc == 0
+    return ctrl, A, b
+
+
+def cost_grad_one(P, ctrl, goff, gpv, gunk, obs, w):
+    """oracle vgo_cost_grad on one trajectory -> (cost, grad_full [N,3], terms [4])"""
+    c = _c(ctrl, np.float64)
+    N = c.shape[0]
+    o = np.zeros((0, 9)) if obs is None else _c(obs, np.float64)
+    gf, terms = np.zeros((N, 3)), np.zeros(4)
+    go, gp, gu = _c(goff, np.int32), _c(gpv, np.float64), _c(gunk, np.uint8)
+    cost = oracle().vgo_cost_grad(C.byref(P), N, _d(c), _i(go), _d(gp), _u(gu), o.shape[0], _d(o), _d(_c(w, np.float64)), None,
+                                  _d(gf), _d(terms))
+    return cost, gf, terms
 
 
 def default_params() -> VigoParams:

@@ -5,7 +5,8 @@ optimizer's distance term gets.  A* inside it is tests/test_astar_restatement.py
 reference's oddities: the `i == endIdx - 1` corner case of findCollisionSeg (BT.cpp:428-432), the truncated PI_const, the
 0.1-step bisection of findGuidePointSemiCircle with its first-iteration `prevAngleDiff = 0`, the merge bookkeeping of
 pathSearch that drops the unmerged segments (BT.cpp:496-511).  The map is the in-tree dense grid (its own
-isInflatedOccupiedLine).  "Parity unpinned" by reference outputs, like the rest of the host path."""
+isInflatedOccupiedLine).  This restatement and the facade are themselves held to the COMPILED reference sources by
+tests/test_oracle_ref_bspline.py."""
 import ctypes as C
 import math
 import os
@@ -51,14 +52,14 @@ class DenseMap:
         return False
 
 
-def find_collision_seg(m, c):                                                           # BT.cpp:403-444
-    n = c.shape[0]
+def collision_segments(n, occ, occ_line, not_check_ratio=0.0):                          # BT.cpp:403-444
+    """findCollisionSeg over two predicates: occ(i) — control point i is inflated-occupied; occ_line(i) — the line from
+    control point i - 1 to i is (asked only where both ends are free)"""
     segs, prev = [], False
-    end_idx = int((n - DEG - 1) - 0.0 * (n - 2 * DEG))
+    end_idx = int((n - DEG - 1) - not_check_ratio * (n - 2 * DEG))
     start = DEG
     for i in range(DEG, end_idx + 1):
-        p = c[i]
-        hit = m.occ(p)
+        hit = bool(occ(i))
         if hit != prev:
             if hit:
                 start = i - 1
@@ -66,10 +67,14 @@ def find_collision_seg(m, c):                                                   
                 segs.append((start, i))
         if hit and i == end_idx - 1:
             segs.append((start, n - 1))
-        if i != DEG and not prev and not hit and m.occ_line(c[i - 1], p):
+        if i != DEG and not prev and not hit and occ_line(i):
             segs.append((i - 1, i))
         prev = hit
     return segs
+
+
+def find_collision_seg(m, c):
+    return collision_segments(c.shape[0], lambda i: m.occ(c[i]), lambda i: m.occ_line(c[i - 1], c[i]))
 
 
 def check_collision_line(m, p1, p2):                                                    # BT.h:196-204
