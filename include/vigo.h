@@ -472,6 +472,46 @@ int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t*
                           const double* knots, const double* delT, const double* endpoint, int32_t* out_status,
                           int32_t* out_n, uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg);
 
+/*
+ * Replaces: AStar::AstarSearch + AStar::getPath (path_search/astarOcc.cpp:120-244, astarOcc.h:41-85) for Q independent
+ * searches on the handle's grid snapshot: bit plane 0 (inflated-occupied) of voxel floor((p - origin) / res), outside the
+ * grid occupied, as vigo_query_points.
+ *   start, end   double[Q][3]   the two points handed to AstarSearch
+ *   step         the lattice spacing (the caller's map resolution); pool[3] (HOST pointer) the node pool's extent,
+ *                2 * int(max_obstacle_size / res) per axis in the reference (BT.cpp:187-195); min/max_height the band
+ * The rules of one search are those of the reference, statement by statement: the lattice centred on (start + end) / 2
+ * with index (int)((p - centre) / step + 0.5) + pool / 2; an end whose node is occupied walks away from the other end a
+ * step at a time until it is free (or leaves the pool: not found); the diagonal heuristic times 1 + 1/10000; the open
+ * set a binary heap with libstdc++'s push_heap / pop_heap ordered by the nodes' CURRENT f; the goal test when a node is
+ * popped; neighbours in dx, dy, dz order, nodes on the pool's border never entered; one push per node; a better path to
+ * an open node rewrites its g and parent where it sits in the heap.  Instead of the reference's 0.2 s wall clock a
+ * search has budgets: at most max_expansions pops, and the kernels' node table and heap (vigo_astar_capacity).
+ *   out_status  int32[Q]   VIGO_ASTAR_FOUND      out_len points in out_path, exactly getPath()'s, start side first
+ *                          VIGO_ASTAR_NOT_FOUND  an end outside the pool (adjustEnds false), or the open set ran empty
+ *                          VIGO_ASTAR_DEFERRED   a budget ran out: NO result either way — run the host search.  The
+ *                                                device never returns a path the host would not return.
+ *                          VIGO_ASTAR_PATH_TOO_LONG  found, but out_len > path_cap points: none written
+ *   out_len     int32[Q]   path points (0 unless found / too long)
+ *   out_path    double[Q][path_cap][3]
+ *   out_stats   int32[Q][3] or NULL: nodes popped, nodes pushed (the table's entries), the heap's largest size — of a
+ *               search that was not deferred, the host search's own counts
+ * A search's result does not depend on the batch it is in.
+ * How: one wavefront per search, table and heap in LDS; pop and sift on lane 0, the 26 neighbours of an expansion probed
+ * by 26 lanes (table, height band, map bit), then committed in the reference's order by lane 0.  Every search runs with
+ * a 2048-slot table first (five per CU); the ones that overflow it run again with 8192 slots (one per CU) in a second
+ * kernel of the same call.  Plain vector stores, no atomics.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle or array (out_stats may be NULL; every array when Q = 0), Q < 0, a pool
+ * axis < 3, step not finite or <= 0, path_cap < 2, max_expansions < 0; VIGO_ERR_UNSUPPORTED for a pool axis above
+ * VIGO_ASTAR_MAX_POOL_AXIS (node keys hold 10 bits per axis); VIGO_ERR_NO_GRID before a grid.  Q = 0 is a no-op.
+ */
+enum { VIGO_ASTAR_FOUND = 0, VIGO_ASTAR_NOT_FOUND = 1, VIGO_ASTAR_DEFERRED = 2, VIGO_ASTAR_PATH_TOO_LONG = 3 };
+enum { VIGO_ASTAR_MAX_POOL_AXIS = 1024 };
+int vigo_astar_search(vigo_handle_t h, int Q, const double* start, const double* end, double step, const int32_t pool[3],
+                      double min_height, double max_height, int max_expansions, int path_cap, int32_t* out_status,
+                      int32_t* out_len, double* out_path, int32_t* out_stats);
+/* The largest search vigo_astar_search holds: pushed nodes and open-set entries (host utility, no GPU). */
+int vigo_astar_capacity(int32_t* max_nodes, int32_t* max_heap);
+
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and
  *   run_first, run_len  int32[K]  segment i's samples are run_first[i] .. run_first[i] + run_len[i] - 1

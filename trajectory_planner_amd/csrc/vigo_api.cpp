@@ -172,7 +172,7 @@ int ensure_grid_storage(vigo_handle_t h, int nx, int ny, int nz) {
 
 extern "C" {
 
-int vigo_abi_version(void) { return 1; }
+int vigo_abi_version(void) { return 2; }
 double vigo_accumulated_time(double delT, int64_t k) { return vigo::accumulated_time(delT, k); }
 double vigo_clock_table_time(double delT, int64_t k_last, int64_t k) {
     if (k_last < 0 || k < 0 || k > k_last || k_last > (int64_t)1 << 30) return NAN;
@@ -738,6 +738,27 @@ int vigo_box_collision_points(vigo_handle_t h, int64_t M, const double* pts, con
             return fail(h, VIGO_ERR_UNSUPPORTED, "corridor checker needs a grid origin that is a multiple of res (octomap keys)");
     }
     VIGO_HIP(h, (hipError_t)vigo::launch_box_points(h->stream, h->grid, M, pts, box, map_res, out));
+    return VIGO_OK;
+}
+
+int vigo_astar_search(vigo_handle_t h, int Q, const double* start, const double* end, double step, const int32_t pool[3],
+                      double min_height, double max_height, int max_expansions, int path_cap, int32_t* out_status, int32_t* out_len,
+                      double* out_path, int32_t* out_stats) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (Q < 0 || !pool || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || !(step > 0.0) || !(step < 1e300) || path_cap < 2 || max_expansions < 0 ||
+        (Q > 0 && (!start || !end || !out_status || !out_len || !out_path)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_astar_search: bad argument");
+    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_astar_search: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_astar_search before vigo_set_grid");
+    if (Q == 0) return VIGO_OK;
+    VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, Q, start, end, step, pool, min_height, max_height, max_expansions, path_cap,
+                                               out_status, out_len, out_path, out_stats, h->launch));
+    return VIGO_OK;
+}
+int vigo_astar_capacity(int32_t* max_nodes, int32_t* max_heap) {
+    if (max_nodes) *max_nodes = vigo::astar_max_nodes();
+    if (max_heap) *max_heap = vigo::astar_max_heap();
     return VIGO_OK;
 }
 

@@ -97,6 +97,7 @@ inline size_t esdf_bricked_floats(int nx, int ny, int nz) {
 struct LaunchState {
     uint64_t lds_attr_set = 0;   // bit per k_optimize instantiation (vigo_solver.hip)
     bool minsnap_attr_set = false;
+    bool astar_attr_set = false;
     int simd_count = 0;          // 4 per CU; 0 = unknown
 };
 
@@ -190,6 +191,13 @@ bool minsnap_supported(int W, int deg, int diff, int cont);   // vigo_minsnap_su
 int launch_minsnap(hipStream_t s, int T, int W, int deg, int diff, int cont, double vel, double corridor_res,
                    const double* wp, const double* corridor, const double* conds, double* out_coeffs,
                    double* out_knots, int32_t* out_status, LaunchState& L);
+
+// batched A* (vigo_astar.hip): the largest search the kernels hold (pushed nodes, open-set entries)
+int astar_max_nodes();
+int astar_max_heap();
+int launch_astar(hipStream_t s, const GridView& g, int Q, const double* start, const double* end, double step, const int32_t pool[3],
+                 double min_h, double max_h, int max_expansions, int path_cap, int32_t* out_status, int32_t* out_len, double* out_path,
+                 int32_t* out_stats, LaunchState& L);
 
 }  // namespace vigo
 

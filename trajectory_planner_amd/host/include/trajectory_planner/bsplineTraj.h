@@ -114,6 +114,20 @@ public:
     static void setBatchPipelineThreshold(size_t planners);
     static void setDeviceResidentRebound(bool on);
     static bool deviceResidentRebound();
+    /* The A* searches of makePlanBatch's prologue as ONE vigo_astar_search launch per device group (plus one for the
+     * merged retries of the failures) instead of host searches on the worker threads.  Default false.  Same plans: a
+     * search the device defers (its budgets, setDeviceAstarBudget), and every search of a planner whose handle has no
+     * map snapshot, is run by the host A*.  The A* of a re-guide inside the rebound loop stays on the host. */
+    static void setDeviceAstar(bool on);
+    static bool deviceAstar();
+    /* max_expansions of those launches (pops per search before the device hands the search back); default 16384 */
+    static void setDeviceAstarBudget(int maxExpansions);
+    /* Process-wide running totals (measurements, tests; take the difference around a call): the prologue searches the
+     * device decided (found / not found) and those the host A* ran (deferred, path too long, no device, outside the
+     * snapshot), and the wall time of makePlanBatch prologues in seconds — summed over the parts when a call is
+     * split into pipelined parts, which run side by side. */
+    static void deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds);
+    const std::vector<std::vector<Eigen::Vector3d>>& getAstarPaths() const { return astarPaths_; }   /* added (tests) */
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
@@ -205,6 +219,10 @@ private:
     struct PlanBatch;
     static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold);
     static void planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb);
+    /* step 2 of the prologue for all planners with device searches; found[i]: planner i's pathSearch outcome */
+    struct AstarJob;
+    static void pathSearchBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found);
+    static void runAstarJobs(const std::vector<bsplineTraj*>& planners, std::vector<AstarJob>& jobs);
     static void reboundOnDevice(PlanBatch& pb, bool timing);
     static void reboundFromHost(PlanBatch& pb, bool timing);
     static void retireFinished(PlanBatch& pb);

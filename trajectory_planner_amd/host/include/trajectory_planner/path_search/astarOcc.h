@@ -22,6 +22,9 @@ public:
     bool AstarSearch(const double step_size, Eigen::Vector3d start_pt, Eigen::Vector3d end_pt);
     std::vector<Eigen::Vector3d> getPath();
     double timeLimit = 0.2;  /* seconds, astarOcc.cpp:231 */
+    /* added (tests, sizing of the device search): what the last AstarSearch did — nodes popped, nodes reached (blocked
+     * ones included), the open set's largest size, in-place score rewrites, nodes pushed.  Counters only: nothing reads them. */
+    struct Stats { int pops = 0, nodes = 0, heapPeak = 0, rewrites = 0, pushed = 0; } lastStats;
 
 private:
     struct Node {           // 24 bytes: the pool is walked at random, its size is what the search costs

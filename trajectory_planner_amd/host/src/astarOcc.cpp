@@ -68,6 +68,7 @@ bool AStar::AstarSearch(const double step_size, Eigen::Vector3d start_pt, Eigen:
     step_ = step_size;
     invStep_ = 1 / step_size;
     center_ = (start_pt + end_pt) / 2;
+    lastStats = Stats();
     int si[3], ei[3];
     if (!adjustEnds(start_pt, end_pt, si, ei)) return false;
 
@@ -81,12 +82,14 @@ bool AStar::AstarSearch(const double step_size, Eigen::Vector3d start_pt, Eigen:
     nodes_[s].state = 1;
     nodes_[s].parent = -1;
     open.push(s);
+    lastStats.nodes = lastStats.heapPeak = lastStats.pushed = 1;
     const int py = pool_(1), pz = pool_(2);
     const double stepLen[4] = {0.0, 1.0, std::sqrt(2.0), std::sqrt(3.0)};
     int iter = 0;
     while (!open.empty()) {
         const int cur = open.top();
         open.pop();
+        ++lastStats.pops;
         if (cur == goal) {
             pathIdx_.clear();
             for (int n = cur; n >= 0; n = nodes_[n].parent) pathIdx_.push_back(n);
@@ -105,7 +108,7 @@ bool AStar::AstarSearch(const double step_size, Eigen::Vector3d start_pt, Eigen:
                     Node& N = nodes_[nb];
                     const bool explored = N.round == round_;
                     if (explored && N.state == 2) continue;   // (a stale CLOSED of an earlier search only ever hides a blocked node)
-                    if (!explored) { N.round = round_; N.occ = 0; }
+                    if (!explored) { N.round = round_; N.occ = 0; ++lastStats.nodes; }
                     if (N.occ == 0) {
                         const Eigen::Vector3d pos = idx2coord(nx, ny, nz);
                         const bool blocked = pos(2) > maxHeight_ || pos(2) < minHeight_ || map_->isInflatedOccupied(pos);
@@ -120,10 +123,13 @@ bool AStar::AstarSearch(const double step_size, Eigen::Vector3d start_pt, Eigen:
                         N.g = g;
                         N.f = g + heuristic(nidx, ei);
                         open.push(nb);
+                        lastStats.heapPeak = std::max(lastStats.heapPeak, (int)open.size());
+                        ++lastStats.pushed;
                     } else if (g < N.g) {                 // open, better path: scores rewritten where the node sits in the heap
                         N.parent = cur;
                         N.g = g;
                         N.f = g + heuristic(nidx, ei);
+                        ++lastStats.rewrites;
                     }
                 }
         if ((++iter & 255) == 0 &&

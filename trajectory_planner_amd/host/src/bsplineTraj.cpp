@@ -433,6 +433,26 @@ void bsplineTraj::findCollisionSeg(const Eigen::MatrixXd& controlPoints, std::ve
     }
 }
 
+namespace {
+// BT.cpp:497-511: the segments after the merges of pathSearch
+void applyMerges(std::vector<std::pair<int, int>>& collisionSeg, const std::vector<int>& mergeIndices) {
+    if (mergeIndices.empty()) return;
+    const int collisionSegNum = int(collisionSeg.size());
+    int midx = 0;
+    std::vector<std::pair<int, int>> collisionSegTemp;
+    for (int i = 0; i < collisionSegNum; ++i) {
+        if (midx < int(mergeIndices.size()) && i == mergeIndices[midx]) {
+            collisionSegTemp.push_back({collisionSeg[i].first, collisionSeg[i + 1].second});
+            ++i;
+            ++midx;
+        } else {
+            collisionSeg.push_back(collisionSeg[i]);  // BT.cpp:507 pushes into the input...
+        }
+    }
+    collisionSeg = collisionSegTemp;  // ...and :510 overwrites it: unmerged segments are dropped
+}
+}  // namespace
+
 // BT.cpp:447-514 (merge bookkeeping reproduced as written, Appendix B of SURVEY.md)
 bool bsplineTraj::pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std::vector<std::vector<Eigen::Vector3d>>& paths) {
     paths.clear();
@@ -467,20 +487,7 @@ bool bsplineTraj::pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std
             return false;
         }
     }
-    if (!mergeIndices.empty()) {
-        int midx = 0;
-        std::vector<std::pair<int, int>> collisionSegTemp;
-        for (int i = 0; i < collisionSegNum; ++i) {
-            if (midx < int(mergeIndices.size()) && i == mergeIndices[midx]) {
-                collisionSegTemp.push_back({collisionSeg[i].first, collisionSeg[i + 1].second});
-                ++i;
-                ++midx;
-            } else {
-                collisionSeg.push_back(collisionSeg[i]);  // BT.cpp:507 pushes into the input...
-            }
-        }
-        collisionSeg = collisionSegTemp;  // ...and :510 overwrites it: unmerged segments are dropped
-    }
+    applyMerges(collisionSeg, mergeIndices);
     return true;
 }
 
@@ -1006,6 +1013,7 @@ namespace {
 using vigo_host::Companion;
 std::atomic<size_t> g_pipelineThreshold{2048};
 thread_local bool t_insidePipeline = false;
+std::atomic<long long> g_prologueNs{0}, g_astarDeviceDecided{0}, g_astarHostRun{0};
 }  // namespace
 void bsplineTraj::setBatchPipelineThreshold(size_t planners) { g_pipelineThreshold.store(planners); }
 
@@ -1031,6 +1039,7 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
     const double tp0 = wallSeconds();
     planPrologue(planners, pb);
     const double tp1 = wallSeconds();
+    g_prologueNs += (long long)((tp1 - tp0) * 1e9);
     // step 4: rebound loops.  The 30 ms budget of BT.cpp:633 is per makePlan() call in the
     // reference; a batch keeps it per round so one slow planner cannot starve the others.
     if (deviceResidentRebound()) reboundOnDevice(pb, timing);
@@ -1088,6 +1097,29 @@ std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>
 void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb) {
     const size_t P = planners.size();
     std::vector<uint8_t> prepared(P, 0);
+    if (deviceAstar()) {
+        // the same three steps with step 2 gathered over the planners: collision segments on the workers, the searches
+        // of all planners on the device (pathSearchBatch), guide assignment on the workers
+        std::vector<uint8_t> ready(P, 0), found(P, 0);
+        parallelFor(P, [&](size_t i) {
+            bsplineTraj* p = planners[i];
+            if (!p->init_ || !p->map_) return;
+            const double t0 = wallSeconds();
+            p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);       // step 1
+            pb.nsSeg += (long long)((wallSeconds() - t0) * 1e9);
+            ready[i] = 1;
+        });
+        const double t1 = wallSeconds();
+        pathSearchBatch(planners, ready, found);                                    // step 2
+        pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
+        parallelFor(P, [&](size_t i) {
+            if (!found[i]) return;
+            const double t2 = wallSeconds();
+            planners[i]->assignGuidePointsSemiCircle(planners[i]->astarPaths_, planners[i]->collisionSeg_);   // step 3
+            pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
+            prepared[i] = 1;
+        });
+    } else
     parallelFor(P, [&](size_t i) {
         bsplineTraj* p = planners[i];
         if (!p->init_ || !p->map_) return;
@@ -1114,6 +1146,202 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         pb.active.push_back(p);
         pb.activeIdx.push_back(i);
     }
+}
+
+namespace {
+std::atomic<bool> g_deviceAstar{false};
+std::atomic<int> g_deviceAstarBudget{16384};
+constexpr int kAstarPathCap = 128;   // path points a device search returns (a longer path is searched again by the host)
+}  // namespace
+void bsplineTraj::setDeviceAstar(bool on) { g_deviceAstar.store(on); }
+bool bsplineTraj::deviceAstar() { return g_deviceAstar.load(); }
+void bsplineTraj::setDeviceAstarBudget(int maxExpansions) { g_deviceAstarBudget.store(maxExpansions < 0 ? 0 : maxExpansions); }
+void bsplineTraj::deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds) {
+    if (deviceDecided) *deviceDecided = g_astarDeviceDecided.load();
+    if (hostRun) *hostRun = g_astarHostRun.load();
+    if (prologueSeconds) *prologueSeconds = g_prologueNs.load() * 1e-9;
+}
+
+// one AstarSearch(res, pStart, pEnd) of planner `planner`: from the start of segment `seg` to the end of segment `endSeg`
+struct bsplineTraj::AstarJob {
+    size_t planner;
+    int seg, endSeg;
+    Eigen::Vector3d s, e;
+    bool ok = false;                       // AstarSearch's return value
+    std::vector<Eigen::Vector3d> path;     // getPath()
+};
+
+// The jobs' searches: one vigo_astar_search per group of planners that share a snapshot, a node pool and a height band;
+// what the device does not decide (deferred, path too long, no device or snapshot) is searched by the planner's own
+// host A* on the workers.
+void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::vector<AstarJob>& jobs) {
+    if (jobs.empty()) return;
+    const size_t P = planners.size();
+    std::vector<uint8_t> decided(jobs.size(), 0);
+    std::vector<std::vector<size_t>> jobsOf(P);
+    for (size_t j = 0; j < jobs.size(); ++j) jobsOf[jobs[j].planner].push_back(j);
+    std::vector<size_t> owners;                       // the planners with jobs, in call order
+    for (size_t i = 0; i < P; ++i)
+        if (!jobsOf[i].empty()) owners.push_back(i);
+    auto same = [&](size_t a, size_t b) {
+        const bsplineTraj* x = planners[owners[a]];
+        const bsplineTraj* y = planners[owners[b]];
+        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
+               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
+    };
+    vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+        bsplineTraj* lead = planners[owners[members[0]]];
+        if (!lead->syncDevice()) return;
+        const double res = lead->map_->getRes();
+        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
+                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
+        if (pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS ||
+            pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+            return;
+        std::vector<size_t> idx;
+        std::vector<double> se[2];
+        for (size_t m : members)
+            for (size_t j : jobsOf[owners[m]]) {
+#ifdef VIGO_WITH_ROS
+                // The snapshot of this map type covers the planner's region only, and the device takes everything outside
+                // it for occupied while the host A* asks the map itself: a search whose node pool (pool / 2 + 1 nodes
+                // around the midpoint of its ends) is not inside the region stays with the host.
+                {
+                    const mapRegion& R = planners[owners[m]]->mapRegion_;
+                    bool inside = R.set;
+                    for (int k = 0; k < 3 && inside; ++k) {
+                        const double c = (jobs[j].s(k) + jobs[j].e(k)) / 2, half = (pool[k] / 2 + 1) * res;
+                        inside = c - half >= R.boxMin(k) && c + half <= R.boxMax(k);
+                    }
+                    if (!inside) continue;
+                }
+#endif
+                idx.push_back(j);
+                for (int k = 0; k < 3; ++k) { se[0].push_back(jobs[j].s(k)); se[1].push_back(jobs[j].e(k)); }
+            }
+        const int Q = (int)idx.size();
+        if (Q == 0) return;
+        static thread_local StagingBuf dS, dE, dStatus, dLen, dPath;
+        if (!dS.upload(se[0].data(), se[0].size() * 8) || !dE.upload(se[1].data(), se[1].size() * 8) || !dStatus.alloc((size_t)Q * 4) ||
+            !dLen.alloc((size_t)Q * 4) || !dPath.alloc((size_t)Q * kAstarPathCap * 24))
+            return;
+        if (vigo_astar_search(lead->dev_, Q, (const double*)dS.p, (const double*)dE.p, res, pool, lead->minHeight_, lead->maxHeight_,
+                              g_deviceAstarBudget.load(), kAstarPathCap, (int32_t*)dStatus.p, (int32_t*)dLen.p, (double*)dPath.p,
+                              nullptr) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_astar_search failed: " << vigo_last_error(lead->dev_) << endl;
+            return;
+        }
+        std::vector<int32_t> status(Q), len(Q);
+        std::vector<double> path((size_t)Q * kAstarPathCap * 3);
+        if (!vigo_host::threadSync() || !dStatus.download(status.data(), (size_t)Q * 4) || !dLen.download(len.data(), (size_t)Q * 4) ||
+            !dPath.download(path.data(), path.size() * 8))
+            return;
+        for (int q = 0; q < Q; ++q) {
+            AstarJob& J = jobs[idx[q]];
+            if (status[q] == VIGO_ASTAR_NOT_FOUND) {
+                decided[idx[q]] = 1;
+            } else if (status[q] == VIGO_ASTAR_FOUND && len[q] >= 1 && len[q] <= kAstarPathCap) {
+                const double* src = path.data() + (size_t)q * kAstarPathCap * 3;
+                J.path.resize(len[q]);
+                for (int i = 0; i < len[q]; ++i) J.path[i] = Eigen::Vector3d(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+                J.ok = true;
+                decided[idx[q]] = 1;
+            }
+        }
+    });
+    long long nDecided = 0;
+    for (uint8_t d : decided) nDecided += d;
+    g_astarDeviceDecided += nDecided;
+    g_astarHostRun += (long long)jobs.size() - nDecided;
+    parallelFor(owners.size(), [&](size_t o) {
+        bsplineTraj* p = planners[owners[o]];
+        for (size_t j : jobsOf[owners[o]]) {
+            if (decided[j]) continue;
+            AstarJob& J = jobs[j];
+            J.ok = p->pathSearch_->AstarSearch(p->map_->getRes(), J.s, J.e);
+            if (J.ok) J.path = p->pathSearch_->getPath();
+        }
+    });
+}
+
+// pathSearch (BT.cpp:447-514) for all planners at once.  Which searches a planner's loop makes depends on their outcomes
+// only through the merge rule: on a failure, pStart to the NEXT segment's end when the gap is <= 2, then that segment is
+// skipped.  A search is a function of its two ends alone, so the first-choice search of every segment goes into one
+// launch, the merged retries the failures ask for into a second one (taking every retry to succeed when looking for
+// the next: a retry that fails ends the planner's loop, and what was searched beyond it is not used), and the loop is
+// then replayed per planner on the results.  The price: the first launch also searches the segments the merge rule goes
+// on to skip and those behind a failure that ends a planner's loop — searches the host's loop never makes, long ones by
+// construction (a skipped segment's own search is one that may well fail), and worker time when the device defers
+// them.  It buys one launch instead of a launch per segment index; weigh it when the timings are taken.
+void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found) {
+    const size_t P = planners.size();
+    std::vector<AstarJob> first, retry;
+    std::vector<size_t> firstOf(P, 0);
+    for (size_t i = 0; i < P; ++i) {
+        if (!ready[i]) continue;
+        const bsplineTraj* p = planners[i];
+        firstOf[i] = first.size();
+        for (int k = 0; k < (int)p->collisionSeg_.size(); ++k) {
+            AstarJob J;
+            J.planner = i; J.seg = k; J.endSeg = k;
+            J.s = p->optData_.controlPoints.col(p->collisionSeg_[k].first);
+            J.e = p->optData_.controlPoints.col(p->collisionSeg_[k].second);
+            first.push_back(J);
+        }
+    }
+    runAstarJobs(planners, first);
+    std::vector<std::vector<size_t>> retryOf(P);
+    for (size_t i = 0; i < P; ++i) {
+        if (!ready[i]) continue;
+        const bsplineTraj* p = planners[i];
+        const int n = (int)p->collisionSeg_.size();
+        for (int k = 0; k < n; ++k) {
+            if (first[firstOf[i] + k].ok) continue;
+            if (k + 1 >= n || p->collisionSeg_[k + 1].first - p->collisionSeg_[k].second > 2) break;
+            AstarJob J;
+            J.planner = i; J.seg = k; J.endSeg = k + 1;
+            J.s = first[firstOf[i] + k].s;
+            J.e = p->optData_.controlPoints.col(p->collisionSeg_[k + 1].second);
+            retryOf[i].push_back(retry.size());
+            retry.push_back(J);
+            ++k;
+        }
+    }
+    runAstarJobs(planners, retry);
+    parallelFor(P, [&](size_t i) {
+        if (!ready[i]) return;
+        bsplineTraj* p = planners[i];
+        std::vector<std::pair<int, int>>& collisionSeg = p->collisionSeg_;
+        std::vector<std::vector<Eigen::Vector3d>>& paths = p->astarPaths_;
+        paths.clear();
+        std::vector<int> mergeIndices;
+        const int n = (int)collisionSeg.size();
+        size_t nextRetry = 0;
+        for (int k = 0; k < n; ++k) {
+            const AstarJob* J = &first[firstOf[i] + k];
+            if (!J->ok) {
+                J = nullptr;
+                if (k + 1 < n && collisionSeg[k + 1].first - collisionSeg[k].second <= 2) {
+                    const AstarJob& R = retry[retryOf[i][nextRetry++]];
+                    if (R.ok) {
+                        J = &R;
+                        mergeIndices.push_back(k);
+                    }
+                }
+                if (!J) {
+                    cout << "[BsplineTraj]: Path Search Error. Force return." << endl;
+                    return;
+                }
+            }
+            std::vector<Eigen::Vector3d> searchedPath = J->path;
+            searchedPath[0] = J->s;
+            searchedPath.push_back(J->e);
+            paths.push_back(searchedPath);
+            if (J->endSeg != k) ++k;
+        }
+        applyMerges(collisionSeg, mergeIndices);
+        found[i] = 1;
+    });
 }
 
 // The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,

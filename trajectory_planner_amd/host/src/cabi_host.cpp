@@ -18,6 +18,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "../../csrc/vigo_astar_core.hpp"
 #include "batchLayout.h"
 #include "workerPool.h"
 
@@ -134,6 +135,105 @@ int vigo_host_astar(const unsigned char* vox, const int* dims, const double* ori
     for (size_t i = 0; i < path.size(); ++i)
         for (int k = 0; k < 3; ++k) path_out[3 * i + k] = path[i](k);
     return (int)path.size();
+}
+
+// vigo_host_astar plus what the search did: stats[5] = nodes popped, nodes reached (blocked ones included), the open
+// set's largest size, in-place score rewrites, nodes pushed (AStar::lastStats); filled whatever the outcome
+int vigo_host_astar_stats(const unsigned char* vox, const int* dims, const double* origin, double res, const int* pool, double min_height,
+                          double max_height, double step, const double* start, const double* end, double* path_out, int cap, int* stats) {
+    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(m->voxels().data(), vox, m->voxels().size());
+    AStar a;
+    a.initGridMap(m, Eigen::Vector3i(pool[0], pool[1], pool[2]), min_height, max_height);
+    const bool ok = a.AstarSearch(step, Eigen::Vector3d(start[0], start[1], start[2]), Eigen::Vector3d(end[0], end[1], end[2]));
+    stats[0] = a.lastStats.pops; stats[1] = a.lastStats.nodes; stats[2] = a.lastStats.heapPeak; stats[3] = a.lastStats.rewrites;
+    stats[4] = a.lastStats.pushed;
+    if (!ok) return -1;
+    const std::vector<Eigen::Vector3d> path = a.getPath();
+    if ((int)path.size() > cap) return -2;
+    for (size_t i = 0; i < path.size(); ++i)
+        for (int k = 0; k < 3; ++k) path_out[3 * i + k] = path[i](k);
+    return (int)path.size();
+}
+
+// the same search by the device's search core (csrc/vigo_astar_core.hpp) compiled for the host: a table of
+// 1 << cap_log2 slots holding at most max_nodes nodes, a heap of heap_cap entries, max_expansions pops.  Returns the
+// status (VIGO_ASTAR_*: 0 found, 1 not found, 2 deferred, 3 path longer than path_cap), -1 for an argument the device
+// entry refuses; *len_out path points in path_out (written only when found), stats as vigo_host_astar_stats.
+int vigo_host_astar_core(const unsigned char* vox, const int* dims, const double* origin, double res, const int* pool, double min_height,
+                         double max_height, double step, const double* start, const double* end, int cap_log2, int max_nodes, int heap_cap,
+                         int max_expansions, int path_cap, double* path_out, int* len_out, int* stats) {
+    if (cap_log2 < 1 || cap_log2 > 30 || max_nodes < 1 || max_nodes >= (1 << cap_log2) || heap_cap < 1 || path_cap < 2 || !(step > 0)) return -1;
+    for (int a = 0; a < 3; ++a)
+        if (pool[a] < 3 || pool[a] > vigo::kAstarMaxPoolAxis) return -1;
+    const size_t n = (size_t)1 << cap_log2;
+    std::vector<int32_t> key(n, -1), heap((size_t)heap_cap);
+    std::vector<double> g(n);
+    std::vector<uint8_t> meta(n);
+    vigo::AstarStore<int32_t> S{};
+    S.key = key.data(); S.g = g.data(); S.meta = meta.data(); S.heap = heap.data();
+    S.cap_log2 = cap_log2; S.max_nodes = max_nodes; S.heap_cap = heap_cap;
+    const size_t ny = dims[1], nz = dims[2];
+    auto occ = [&](double x, double y, double z) -> bool {     // dense_occmap.h byteAt & 1: outside is occupied
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
+        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
+    };
+    const int st = vigo::astar_search(S, occ, start, end, step, pool, min_height, max_height, max_expansions, path_cap, path_out, len_out);
+    stats[0] = S.pops; stats[1] = S.n_nodes; stats[2] = S.heap_peak; stats[3] = S.rewrites;
+    return st;
+}
+
+// The A* searches of makePlan()'s prologue for n sets of control points [n][N][3] on one dense byte grid: the first-choice
+// search (segment start -> segment end) of every collision segment findCollisionSeg reports, run by the host A*.  cfg as
+// in vigo_host_bspline_prologue.  Per search q < cap (the return value counts them all; -1 on a bad argument):
+//   ends[q][6] start xyz, end xyz; owner[q] the planner; len[q] path points or -1; path[q][path_cap][3] (when it fits);
+//   stats[q][5] as vigo_host_astar_stats.  pool_out[3]: the planners' node pool.
+int vigo_host_prologue_searches(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int N, const double* ctrl,
+                                const double* cfg, int cap, int path_cap, double* ends, int* owner, int* len, double* path, int* stats,
+                                int* pool_out) {
+    if (n < 0 || N < 7 || !ctrl) return -1;
+    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(m->voxels().data(), vox, m->voxels().size());
+    ros::NodeHandle nh;
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    trajPlanner::bsplineTraj bt(nh);
+    bt.setMap(m);
+    const Eigen::Vector3i pool(2 * int(cfg[3] / res), 2 * int(cfg[4] / res), 2 * int(cfg[5] / res));   // setMap, BT.cpp:187-195
+    for (int a = 0; a < 3; ++a) pool_out[a] = pool(a);
+    AStar a;
+    a.initGridMap(m, pool, cfg[1], cfg[2]);
+    int q = 0;
+    for (int t = 0; t < n; ++t) {
+        Eigen::MatrixXd c(3, N);
+        for (int i = 0; i < N; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl[((size_t)t * N + i) * 3 + k];
+        std::vector<std::pair<int, int>> seg;
+        bt.findCollisionSeg(c, seg);
+        for (const auto& sg : seg) {
+            if (q < cap) {
+                const Eigen::Vector3d s = c.col(sg.first), e = c.col(sg.second);
+                for (int k = 0; k < 3; ++k) { ends[6 * q + k] = s(k); ends[6 * q + 3 + k] = e(k); }
+                owner[q] = t;
+                const bool ok = a.AstarSearch(res, s, e);
+                stats[5 * q] = a.lastStats.pops; stats[5 * q + 1] = a.lastStats.nodes; stats[5 * q + 2] = a.lastStats.heapPeak;
+                stats[5 * q + 3] = a.lastStats.rewrites; stats[5 * q + 4] = a.lastStats.pushed;
+                len[q] = -1;
+                if (ok) {
+                    const std::vector<Eigen::Vector3d> p = a.getPath();
+                    len[q] = (int)p.size();
+                    if (len[q] <= path_cap)
+                        for (size_t i = 0; i < p.size(); ++i)
+                            for (int k = 0; k < 3; ++k) path[((size_t)q * path_cap + i) * 3 + k] = p[i](k);
+                }
+            }
+            ++q;
+        }
+    }
+    return q;
 }
 
 // min-snap through n_wp waypoints (xyz triples); corridor == NULL: equality-constrained only.  conds: [4][3] initial
@@ -673,6 +773,99 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
 }
 
 }  // extern "C"
+
+// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch, `reps` times with the prologue's A* on the
+// host (mode 0) and `reps` times with setDeviceAstar(true) (mode 1), alternating, fresh planners every time.  n_maps > 1:
+// planner t plans on map t % n_maps, a separate map object each (separate device groups): copies of vox, the odd ones
+// of vox2 when that is given (same extents, other contents).  budget: the device
+// searches' max_expansions (setDeviceAstarBudget).  cfg as in vigo_host_bspline_prologue.  Outputs of each mode's LAST run,
+// [2] x ...: ok[n] makePlanBatch's flags, solver[n] the last L-BFGS status, ncp[n], ctrl[n][ncp_cap][3] (zero padded),
+// n_guides[n] + guides[cap][6] (point, direction; concatenated in planner order), n_path_pts[n] + paths[cap][3] (the A*
+// paths' points, concatenated), per run prologue_ms[2][reps] (summed over the parts of a call that makePlanBatch splits)
+// and total_ms[2][reps], and counts[2]: the searches of the LAST mode-1 run the device decided / the host ran.  Returns 0, -2 when a buffer is
+// too small, -1 on a bad argument.  Needs a GPU.
+extern "C" int vigo_host_plan_batch_astar(const unsigned char* vox, const unsigned char* vox2, const int* dims, const double* origin, double res, int n, int n_pts,
+                                          const double* path_xyz, const double* cfg, int n_maps, int budget, int reps, int ncp_cap, long long cap,
+                                          int* ok, int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, int* n_path_pts,
+                                          double* paths, double* prologue_ms, double* total_ms, long long* counts) {
+    using trajPlanner::bsplineTraj;
+    if (n < 1 || n_pts < 2 || n_maps < 1 || reps < 1 || !path_xyz) return -1;
+    std::vector<std::shared_ptr<mapManager::occMap>> maps;
+    for (int k = 0; k < n_maps; ++k) {
+        maps.push_back(std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res));
+        std::memcpy(maps.back()->voxels().data(), (vox2 && (k & 1)) ? vox2 : vox, maps.back()->voxels().size());
+    }
+    ros::NodeHandle nh;
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    nh.setParam("bspline_traj/max_path_length", 1000.0);
+    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
+    std::vector<nav_msgs::Path> in(n);
+    for (int t = 0; t < n; ++t)
+        for (int i = 0; i < n_pts; ++i) {
+            geometry_msgs::PoseStamped ps;
+            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
+            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
+            in[t].poses.push_back(ps);
+        }
+    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    int rc = 0;
+    bsplineTraj::setDeviceAstarBudget(budget);
+    for (int run = 0; run < 2 * reps && rc == 0; ++run) {
+        const int mode = run & 1, rep = run / 2;
+        std::vector<std::unique_ptr<bsplineTraj>> owners;
+        std::vector<bsplineTraj*> ps;
+        for (int t = 0; t < n; ++t) {
+            owners.emplace_back(new bsplineTraj(nh));
+            owners.back()->setMap(maps[t % n_maps]);
+            owners.back()->updateMaxVel(2.0);
+            owners.back()->updateMaxAcc(3.0);
+            ps.push_back(owners.back().get());
+        }
+        bsplineTraj::updatePathBatch(ps, in, cond);
+        bsplineTraj::setDeviceAstar(mode == 1);
+        long long dev0, host0, dev1, host1;
+        double pro0, pro1;
+        bsplineTraj::deviceAstarTotals(&dev0, &host0, &pro0);
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
+        total_ms[mode * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        bsplineTraj::deviceAstarTotals(&dev1, &host1, &pro1);
+        prologue_ms[mode * reps + rep] = (pro1 - pro0) * 1e3;
+        if (mode == 1) { counts[0] = dev1 - dev0; counts[1] = host1 - host0; }
+        bsplineTraj::setDeviceAstar(false);
+        if (rep + 1 < reps) continue;
+        long long g = 0, w = 0;
+        for (int t = 0; t < n && rc == 0; ++t) {
+            const size_t o = (size_t)mode * n + t;
+            const Eigen::MatrixXd c = ps[t]->getControlPoints();
+            ok[o] = res2[t] ? 1 : 0;
+            solver[o] = ps[t]->getLastSolverStatus();
+            ncp[o] = (int)c.cols();
+            if (c.cols() > ncp_cap) { rc = -2; break; }
+            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
+            std::vector<int32_t> off{0};
+            std::vector<double> pv;
+            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
+            n_guides[o] = (int)(pv.size() / 6);
+            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
+            std::memcpy(guides + ((size_t)mode * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
+            g += (long long)pv.size() / 6;
+            int pts = 0;
+            for (const auto& path : ps[t]->getAstarPaths())
+                for (const auto& v : path) {
+                    if (w + 1 > cap) { rc = -2; break; }
+                    for (int k = 0; k < 3; ++k) paths[((size_t)mode * cap + w) * 3 + k] = v(k);
+                    ++w; ++pts;
+                }
+            n_path_pts[o] = pts;
+        }
+    }
+    bsplineTraj::setDeviceAstarBudget(16384);
+    return rc;
+}
 
 // mapAdapter::rasterise (the generic route: four public map methods only) over the whole box of a dense map must give
 // back that map's inflated-occupied and unknown bits.  Returns the number of differing voxels (0 = agreement), -1 on

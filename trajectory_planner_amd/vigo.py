@@ -16,6 +16,7 @@ from ._lib import VigoParams
 PREC_F64 = 0
 PREC_F32 = 1
 PREC_F64_FAST = 2
+ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_DEFERRED, ASTAR_PATH_TOO_LONG = 0, 1, 2, 3   # vigo_astar_search's out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -436,6 +437,24 @@ class Vigo:
             C.c_void_p(flag.data_ptr()), C.c_void_p(first.data_ptr()), C.c_void_p(count.data_ptr()),
             C.c_void_p(seg.data_ptr())), "vigo_traj_point_check")
         return status, n, flag, first, count, seg
+
+    def astar_search(self, start, end, step, pool, min_height, max_height, max_expansions=1 << 20, path_cap=256, want_stats=True):
+        """vigo_astar_search: Q searches of the facade's host A* on the handle's grid -> (status int32 [Q], len int32 [Q],
+        path f64 [Q,path_cap,3], stats int32 [Q,3] or None); status ASTAR_FOUND / NOT_FOUND / DEFERRED / PATH_TOO_LONG"""
+        _shape(start, (None, 3), "start")
+        Q = start.shape[0]
+        _shape(end, (Q, 3), "end")
+        d = self.device
+        status = torch.full((Q,), -1, dtype=torch.int32, device=d)
+        length = torch.zeros(Q, dtype=torch.int32, device=d)
+        path = torch.zeros((Q, int(path_cap), 3), dtype=torch.float64, device=d)
+        stats = torch.zeros((Q, 3), dtype=torch.int32, device=d) if want_stats else None
+        self._check(self._lib.vigo_astar_search(
+            self._h, Q, _ptr(start, torch.float64, "start", d), _ptr(end, torch.float64, "end", d), float(step),
+            (C.c_int32 * 3)(*[int(v) for v in pool]), float(min_height), float(max_height), int(max_expansions), int(path_cap),
+            C.c_void_p(status.data_ptr()), C.c_void_p(length.data_ptr()), C.c_void_p(path.data_ptr()),
+            C.c_void_p(stats.data_ptr()) if want_stats else None), "vigo_astar_search")
+        return status, length, path, stats
 
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
