@@ -512,6 +512,46 @@ int vigo_astar_search(vigo_handle_t h, int Q, const double* start, const double*
 /* The largest search vigo_astar_search holds: pushed nodes and open-set entries (host utility, no GPU). */
 int vigo_astar_capacity(int32_t* max_nodes, int32_t* max_heap);
 
+/*
+ * Replaces: bsplineTraj::assignGuidePointsSemiCircle (BT.cpp:517-571) with shortcutPaths / shortcutPath (BT.h:206-257),
+ * checkCollisionLine (BT.h:196-204) and findGuidePointSemiCircle (BT.h:251-304) for B trajectories of N control points
+ * on the handle's grid snapshot (bit plane 0, outside the grid occupied, as vigo_query_points; the line checks walk
+ * a += res with the snapshot's res).
+ *   ctrl      double[B][N][3]
+ *   seg_off   int32[B+1]   CSR of collision segments per trajectory
+ *   seg       int32[S][2]  (first, second), AFTER pathSearch's merges; the caller applies the reference's
+ *                          min(collisionSeg.size(), paths.size()) bound: segment k goes with path k
+ *   path_off  int32[S+1]   CSR of path points per segment
+ *   path      double[P][3] paths as pathSearch leaves them: point 0 = ctrl[first], ctrl[second] appended
+ *   out_guide_off int32[B*N+1]     CSR of the pairs THIS step appends, per control point, in push order
+ *   out_guide_pv  double[pair_cap][6]  (point, direction)
+ *   out_guide_unk uint8[pair_cap] or NULL: isUnknown(point), as vigo_guides_unknown
+ *   out_status    int32[B]  VIGO_GUIDE_OK | VIGO_GUIDE_DEFERRED: a path of the trajectory has more points than the
+ *                           kernel's buffer (vigo_guide_capacity); the trajectory owns NO pairs — run the host step.
+ *                           The device never returns pairs the host twin of its code would not return.
+ * The rules are the reference's, statement by statement, quirks included: the guide point of a control point whose
+ * search fails is the previous one (zero for the very first), carried across control points and segments; a segment
+ * without interior points pushes one pair onto each of first-1 .. second+1 inside [3, N-4]; interior points outside
+ * [0, N) are skipped; a zero guidePoint - controlPoint gives a NaN direction.  The angle is atan2(|a x b|, a . b) with
+ * a portable fp64 atan2 (csrc/vigo_guide_core.hpp: vigo_atan2, within 2 ulp of libm's), so pairs equal those of the same
+ * header compiled for the host bit for bit, and those of the reference's libm arithmetic up to that difference.
+ * A trajectory's pairs do not depend on the batch it is in.
+ * How: the pair counts follow from the segments alone, so a one-workgroup kernel checks the lists and scans the
+ * offsets; its verdict is read back before anything else runs.  Then one wavefront per trajectory, path and shortcut
+ * in LDS; line-check samples, bracket tests and bisection steps spread over the lanes with ballots; pairs written in
+ * place with plain vector stores, no atomics.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle or array (out_guide_unk may be NULL; every array when B = 0), B < 0,
+ * N < 1, pair_cap < 0, offsets that decrease or start below 0, a segment with an empty path, a segment without
+ * interior points whose ends are not in [0, N), indices beyond +-2^24, and more pairs than pair_cap — in every such
+ * case nothing is written; VIGO_ERR_NO_GRID before a grid.  B = 0 is a no-op.
+ */
+enum { VIGO_GUIDE_OK = 0, VIGO_GUIDE_DEFERRED = 1 };
+int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
+                      const int32_t* path_off, const double* path, int64_t pair_cap, int32_t* out_guide_off,
+                      double* out_guide_pv, uint8_t* out_guide_unk, int32_t* out_status);
+/* The longest path (points of one segment) vigo_guide_assign holds (host utility, no GPU). */
+int vigo_guide_capacity(int32_t* max_path_points);
+
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and
  *   run_first, run_len  int32[K]  segment i's samples are run_first[i] .. run_first[i] + run_len[i] - 1

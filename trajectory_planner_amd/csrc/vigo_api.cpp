@@ -172,7 +172,7 @@ int ensure_grid_storage(vigo_handle_t h, int nx, int ny, int nz) {
 
 extern "C" {
 
-int vigo_abi_version(void) { return 2; }
+int vigo_abi_version(void) { return 3; }
 double vigo_accumulated_time(double delT, int64_t k) { return vigo::accumulated_time(delT, k); }
 double vigo_clock_table_time(double delT, int64_t k_last, int64_t k) {
     if (k_last < 0 || k < 0 || k > k_last || k_last > (int64_t)1 << 30) return NAN;
@@ -759,6 +759,35 @@ int vigo_astar_search(vigo_handle_t h, int Q, const double* start, const double*
 int vigo_astar_capacity(int32_t* max_nodes, int32_t* max_heap) {
     if (max_nodes) *max_nodes = vigo::astar_max_nodes();
     if (max_heap) *max_heap = vigo::astar_max_heap();
+    return VIGO_OK;
+}
+
+int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off,
+                      const double* path, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk,
+                      int32_t* out_status) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (B < 0 || N < 1 || pair_cap < 0 ||
+        (B > 0 && (!ctrl || !seg_off || !seg || !path_off || !path || !out_guide_off || !out_guide_pv || !out_status)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: bad argument");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_guide_assign before vigo_set_grid");
+    if (B == 0) return VIGO_OK;
+    int rc = ensure_scratch(h, 64);
+    if (rc) return rc;
+    long long* result = static_cast<long long*>(h->scratch);
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, seg_off, seg, path_off, (long long)pair_cap, out_guide_off, out_status,
+                                                       result));
+    long long host_result[2] = {0, 0};
+    VIGO_HIP(h, hipMemcpyAsync(host_result, result, sizeof(host_result), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    if (host_result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: offsets that decrease, a path without a point or a segment out of range");
+    if (host_result[0] > (long long)pair_cap || host_result[0] > 0x7fffffffLL)
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: the pairs do not fit pair_cap");
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, seg_off, seg, path_off, path, out_guide_off, out_guide_pv,
+                                                      out_guide_unk, out_status));
+    return VIGO_OK;
+}
+int vigo_guide_capacity(int32_t* max_path_points) {
+    if (max_path_points) *max_path_points = vigo::guide_path_capacity();
     return VIGO_OK;
 }
 

@@ -199,6 +199,15 @@ int launch_astar(hipStream_t s, const GridView& g, int Q, const double* start, c
                  double min_h, double max_h, int max_expansions, int path_cap, int32_t* out_status, int32_t* out_len, double* out_path,
                  int32_t* out_stats, LaunchState& L);
 
+// batched guide assignment (vigo_guides.hip): the offsets kernel fills result[2] = {pairs of the call, bad lists} and,
+// when the lists are good and the pairs fit, statuses and offsets; the assign kernel then writes the pairs in place
+int guide_path_capacity();
+int launch_guide_offsets(hipStream_t s, int B, int N, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off, long long pair_cap,
+                         int32_t* out_off, int32_t* out_status, long long* result);
+int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
+                        const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
+                        const int32_t* status);
+
 }  // namespace vigo
 
 struct vigo_context {

@@ -128,6 +128,17 @@ public:
      * split into pipelined parts, which run side by side. */
     static void deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds);
     const std::vector<std::vector<Eigen::Vector3d>>& getAstarPaths() const { return astarPaths_; }   /* added (tests) */
+    /* Step 3 of makePlanBatch's prologue (assignGuidePointsSemiCircle).  0 (default): the host step as it always was.
+     * 1: ONE vigo_guide_assign launch per device group; a planner the device defers (a path longer than
+     * vigo_guide_capacity), or whose group has no device or snapshot, runs the same code on the worker threads —
+     * csrc/vigo_guide_core.hpp with its portable atan2, the kernel's bit-exact twin — so a planner's guides do not depend
+     * on which side produced them.  2: every planner runs that twin on the workers (the emulation of 1).  Settings 1
+     * and 2 differ from 0 by the last places of atan2 (vigo.h: vigo_guide_assign).  The re-guide step inside the
+     * rebound loop stays on the host step whatever the setting. */
+    static void setDeviceGuides(int mode);
+    static int deviceGuides();
+    /* Process-wide running totals: the prologue trajectories whose guides the device produced / the workers' twin produced */
+    static void deviceGuideTotals(long long* deviceDecided, long long* hostRun);
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
@@ -223,6 +234,10 @@ private:
     struct AstarJob;
     static void pathSearchBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found);
     static void runAstarJobs(const std::vector<bsplineTraj*>& planners, std::vector<AstarJob>& jobs);
+    /* step 3 of the prologue under setDeviceGuides(1 | 2) for the planners with found[i] */
+    static void assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found);
+    void assignGuidesCore();
+    void packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const;
     static void reboundOnDevice(PlanBatch& pb, bool timing);
     static void reboundFromHost(PlanBatch& pb, bool timing);
     static void retireFinished(PlanBatch& pb);

@@ -23,6 +23,7 @@
 #include <set>
 
 #include "../../../include/vigo.h"
+#include "../../csrc/vigo_guide_core.hpp"
 #include "batchLayout.h"
 #include "devbuf.h"
 #include "workerPool.h"
@@ -1096,7 +1097,8 @@ std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>
 // planners are spread over the host cores.  Those that get through enter the rebound loop.
 void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb) {
     const size_t P = planners.size();
-    std::vector<uint8_t> prepared(P, 0);
+    std::vector<uint8_t> prepared(P, 0), hasPaths(P, 0);
+    const int guides = deviceGuides();
     if (deviceAstar()) {
         // the same three steps with step 2 gathered over the planners: collision segments on the workers, the searches
         // of all planners on the device (pathSearchBatch), guide assignment on the workers
@@ -1112,6 +1114,8 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         const double t1 = wallSeconds();
         pathSearchBatch(planners, ready, found);                                    // step 2
         pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
+        if (guides != 0) hasPaths = found;
+        else
         parallelFor(P, [&](size_t i) {
             if (!found[i]) return;
             const double t2 = wallSeconds();
@@ -1131,10 +1135,18 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         pb.nsSeg += (long long)((t1 - t0) * 1e9);
         pb.nsAstar += (long long)((t2 - t1) * 1e9);
         if (!found) return;
+        if (guides != 0) { hasPaths[i] = 1; return; }
         p->assignGuidePointsSemiCircle(p->astarPaths_, p->collisionSeg_);           // step 3
         pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
         prepared[i] = 1;
     });
+    if (guides != 0) {
+        // step 3 gathered over the planners (setDeviceGuides): the device, or its twin on the workers
+        const double t2 = wallSeconds();
+        assignGuidesBatch(planners, hasPaths);
+        pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
+        prepared = hasPaths;
+    }
     for (size_t i = 0; i < P; ++i) {
         bsplineTraj* p = planners[i];
         if (!p->init_ || !p->map_) continue;
@@ -1341,6 +1353,150 @@ void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, con
         }
         applyMerges(collisionSeg, mergeIndices);
         found[i] = 1;
+    });
+}
+
+namespace {
+std::atomic<int> g_deviceGuides{0};
+std::atomic<long long> g_guideDeviceDecided{0}, g_guideHostRun{0};
+}  // namespace
+void bsplineTraj::setDeviceGuides(int mode) { g_deviceGuides.store(mode == 1 || mode == 2 ? mode : 0); }
+int bsplineTraj::deviceGuides() { return g_deviceGuides.load(); }
+void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun) {
+    if (deviceDecided) *deviceDecided = g_guideDeviceDecided.load();
+    if (hostRun) *hostRun = g_guideHostRun.load();
+}
+
+// the planner's segments and paths as vigo_guide_assign takes them: the first min(collisionSeg.size(), paths.size()) of
+// both (BT.cpp:523), paths as CSR
+void bsplineTraj::packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const {
+    const size_t n = std::min(this->collisionSeg_.size(), this->astarPaths_.size());
+    for (size_t k = 0; k < n; ++k) {
+        seg.push_back(this->collisionSeg_[k].first);
+        seg.push_back(this->collisionSeg_[k].second);
+        for (const Eigen::Vector3d& v : this->astarPaths_[k])
+            for (int a = 0; a < 3; ++a) path.push_back(v(a));
+        pathOff.push_back((int32_t)(path.size() / 3));
+    }
+}
+
+// assignGuidePointsSemiCircle by the device's code (csrc/vigo_guide_core.hpp with vigo_atan2) on the planner's own map
+void bsplineTraj::assignGuidesCore() {
+    std::vector<int32_t> seg, pathOff{0};
+    std::vector<double> path;
+    this->packGuideInput(seg, pathOff, path);
+    const int N = this->optData_.controlPoints.cols();
+    std::vector<double> ctrl((size_t)N * 3);
+    for (int i = 0; i < N; ++i)
+        for (int a = 0; a < 3; ++a) ctrl[(size_t)i * 3 + a] = this->optData_.controlPoints(a, i);
+    size_t longest = 1;
+    for (size_t k = 0; k + 1 < pathOff.size(); ++k) {
+        if (pathOff[k + 1] - pathOff[k] < 1) return;     // (pathSearch leaves at least the two ends)
+        longest = std::max(longest, (size_t)(pathOff[k + 1] - pathOff[k]));
+    }
+    std::vector<vigo::G3> sc(longest);
+    auto* map = this->map_.get();
+    auto occ = [map](double x, double y, double z) { return map->isInflatedOccupied(Eigen::Vector3d(x, y, z)); };
+    vigo::guide_assign(occ, vigo::GuideAtan2{}, this->map_->getRes(), N, ctrl.data(), (int)(seg.size() / 2), seg.data(), pathOff.data(),
+                       path.data(), sc.data(), [this](int idx, const vigo::G3& p, const vigo::G3& d, const int32_t*) {
+                           this->optData_.guidePoints[idx].push_back(Eigen::Vector3d(p.v[0], p.v[1], p.v[2]));
+                           this->optData_.guideDirections[idx].push_back(Eigen::Vector3d(d.v[0], d.v[1], d.v[2]));
+                       });
+}
+
+// Step 3 for the planners with found[i].  Setting 1: one vigo_guide_assign per group of planners that share a snapshot
+// and a control-point count; the pairs come back as CSR per control point in push order and are appended to the planners'
+// lists.  Whatever the device did not produce (deferred, no device, a failed call), and everything under setting 2, is
+// computed by assignGuidesCore on the workers: the same code, the same pairs.
+void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found) {
+    const size_t P = planners.size();
+    std::vector<uint8_t> done(P, 0);
+    if (deviceGuides() == 1) {
+        std::vector<size_t> owners;
+        for (size_t i = 0; i < P; ++i)
+            if (found[i]) owners.push_back(i);
+        auto same = [&](size_t a, size_t b) {
+            const bsplineTraj* x = planners[owners[a]];
+            const bsplineTraj* y = planners[owners[b]];
+            return x->sameBatchKey(*y) && x->optData_.controlPoints.cols() == y->optData_.controlPoints.cols();
+        };
+        vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+            bsplineTraj* lead = planners[owners[members[0]]];
+            if (!lead->syncDevice()) return;
+            const int N = lead->optData_.controlPoints.cols();
+            std::vector<size_t> who;
+            std::vector<double> ctrl, path;
+            std::vector<int32_t> segOff{0}, seg, pathOff{0};
+            long long pairs = 0;
+            for (size_t m : members) {
+                const bsplineTraj* p = planners[owners[m]];
+                const size_t seg0 = seg.size() / 2;
+                p->packGuideInput(seg, pathOff, path);
+#ifdef VIGO_WITH_ROS
+                // the snapshot of this map type covers the planner's region only and takes everything outside it for
+                // occupied; the line checks stay inside the box of the path points: a planner with a path point outside
+                // the region keeps to its own map (the twin)
+                {
+                    const mapRegion& R = p->mapRegion_;
+                    bool inside = R.set;
+                    for (size_t q = (size_t)pathOff[seg0] * 3; q < path.size() && inside; ++q)
+                        inside = path[q] >= R.boxMin(int(q % 3)) && path[q] <= R.boxMax(int(q % 3));
+                    if (!inside) {
+                        seg.resize(seg0 * 2);
+                        path.resize((size_t)pathOff[seg0] * 3);
+                        pathOff.resize(seg0 + 1);
+                        continue;
+                    }
+                }
+#endif
+                for (size_t k = seg0; k < seg.size() / 2; ++k) pairs += vigo::guide_pushes_total(N, seg[2 * k], seg[2 * k + 1]);
+                segOff.push_back((int32_t)(seg.size() / 2));
+                for (int i = 0; i < N; ++i)
+                    for (int a = 0; a < 3; ++a) ctrl.push_back(p->optData_.controlPoints(a, i));
+                who.push_back(owners[m]);
+            }
+            const int B = (int)who.size();
+            if (B == 0) return;
+            if (seg.empty()) {                       // no segments anywhere: nothing to assign
+                for (size_t i : who) done[i] = 1;
+                return;
+            }
+            const long long cap = std::max<long long>(pairs, 1);
+            static thread_local StagingBuf dCtrl, dSegOff, dSeg, dPathOff, dPath, dOff, dPv, dStatus;
+            if (!dCtrl.upload(ctrl.data(), ctrl.size() * 8) || !dSegOff.upload(segOff.data(), segOff.size() * 4) ||
+                !dSeg.upload(seg.data(), seg.size() * 4) || !dPathOff.upload(pathOff.data(), pathOff.size() * 4) ||
+                !dPath.upload(path.data(), path.size() * 8) || !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)cap * 48) ||
+                !dStatus.alloc((size_t)B * 4))
+                return;
+            if (vigo_guide_assign(lead->dev_, B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
+                                  (const int32_t*)dPathOff.p, (const double*)dPath.p, cap, (int32_t*)dOff.p, (double*)dPv.p, nullptr,
+                                  (int32_t*)dStatus.p) != VIGO_OK) {
+                cout << "[BsplineTraj]: vigo_guide_assign failed: " << vigo_last_error(lead->dev_) << endl;
+                return;
+            }
+            std::vector<int32_t> off((size_t)B * N + 1), status(B);
+            if (!vigo_host::threadSync() || !dOff.download(off.data(), off.size() * 4) || !dStatus.download(status.data(), (size_t)B * 4)) return;
+            std::vector<double> pv((size_t)off.back() * 6);
+            if (off.back() < 0 || off.back() > cap || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
+            for (int b = 0; b < B; ++b) {
+                if (status[b] != VIGO_GUIDE_OK) continue;
+                bsplineTraj* p = planners[who[b]];
+                for (int i = 0; i < N; ++i)
+                    for (int g = off[(size_t)b * N + i]; g < off[(size_t)b * N + i + 1]; ++g) {
+                        const double* q = pv.data() + (size_t)g * 6;
+                        p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+                        p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
+                    }
+                done[who[b]] = 1;
+            }
+        });
+    }
+    long long nDone = 0, nFound = 0;
+    for (size_t i = 0; i < P; ++i) { nDone += done[i]; nFound += found[i] ? 1 : 0; }
+    g_guideDeviceDecided += nDone;
+    g_guideHostRun += nFound - nDone;
+    parallelFor(P, [&](size_t i) {
+        if (found[i] && !done[i]) planners[i]->assignGuidesCore();
     });
 }
 

@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "../../csrc/vigo_astar_core.hpp"
+#include "../../csrc/vigo_guide_core.hpp"
 #include "batchLayout.h"
 #include "workerPool.h"
 
@@ -866,6 +867,270 @@ extern "C" int vigo_host_plan_batch_astar(const unsigned char* vox, const unsign
     bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
 }
+
+// ---- guide assignment: the device's core on the host, the facade's own step, and the workloads of their tests ----------
+namespace {
+struct NudgedAtan2 {     // std::atan2 moved by `ulps` representable values (test-only neighbours of libm's result)
+    int ulps;
+    double operator()(double y, double x) const {
+        double r = std::atan2(y, x);
+        for (int k = 0; k < std::abs(ulps); ++k) r = std::nextafter(r, ulps > 0 ? HUGE_VAL : -HUGE_VAL);
+        return r;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// out[i] = vigo_atan2(y[i], x[i]) (csrc/vigo_guide_core.hpp)
+int vigo_host_atan2(long long n, const double* y, const double* x, double* out) {
+    if (n < 0 || (n > 0 && (!y || !x || !out))) return -1;
+    for (long long i = 0; i < n; ++i) out[i] = vigo::vigo_atan2(y[i], x[i]);
+    return 0;
+}
+
+// vigo_guide_assign on the host (csrc/vigo_guide_core.hpp) on a dense byte grid (bit 0 = inflated-occupied, bit 1 =
+// unknown; outside the grid both), inputs and outputs as the device entry.  mode 0: std::atan2 (the facade's
+// arithmetic); 1: vigo_atan2 (the device's twin); 2 / 3: std::atan2 nudged by +2 / -2 ulp (test-only neighbours).
+// path_cap: a trajectory with a longer path is DEFERRED (the device's rule with vigo_guide_capacity's value).
+// out_decision int32[pair_cap][3] or NULL: per pair the search's found flag, path segment and bisection step.
+// Returns 0; -1 for what the device entry answers with VIGO_ERR_INVALID_ARG (nothing is written).
+int vigo_host_guide_core(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                         const int* seg_off, const int* seg, const int* path_off, const double* path, int mode, int path_cap,
+                         long long pair_cap, int* out_off, double* out_pv, unsigned char* out_unk, int* out_status, int* out_decision) {
+    if (B < 0 || N < 1 || pair_cap < 0 || mode < 0 || mode > 3 || !(res > 0) ||
+        (B > 0 && (!ctrl || !seg_off || !seg || !path_off || !path || !out_off || !out_pv || !out_status)))
+        return -1;
+    if (B == 0) return 0;
+    if (seg_off[0] < 0) return -1;
+    std::vector<uint8_t> deferred(B, 0);
+    std::vector<long long> first_pair(B + 1, 0);
+    size_t longest = 1;
+    for (int b = 0; b < B; ++b) {
+        if (seg_off[b + 1] < seg_off[b]) return -1;
+        long long nb = 0;
+        for (int k = seg_off[b]; k < seg_off[b + 1]; ++k) {
+            const int len = path_off[k + 1] - path_off[k];
+            if (path_off[k] < 0 || len < 0 || !vigo::guide_segment_ok(N, seg[2 * k], seg[2 * k + 1], len)) return -1;
+            if (len > path_cap) deferred[b] = 1;
+            longest = std::max(longest, (size_t)len);
+            nb += vigo::guide_pushes_total(N, seg[2 * k], seg[2 * k + 1]);
+        }
+        first_pair[b + 1] = first_pair[b] + (deferred[b] ? 0 : nb);
+    }
+    if (first_pair[B] > pair_cap || first_pair[B] > 0x7fffffffLL) return -1;
+    const size_t ny = dims[1], nz = dims[2];
+    auto byteAt = [&](double x, double y, double z) -> unsigned {     // dense_occmap.h byteAt
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return 0xFFu;
+        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]];
+    };
+    auto occ = [&](double x, double y, double z) -> bool { return byteAt(x, y, z) & 1u; };
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        out_status[b] = deferred[b] ? vigo::kGuideDeferred : vigo::kGuideOk;
+        const int s0 = seg_off[b], s1 = seg_off[b + 1];
+        std::vector<int> cursor(N);
+        long long at = first_pair[b];
+        for (int i = 0; i < N; ++i) {
+            out_off[b * (size_t)N + i] = (int)at;
+            cursor[i] = (int)at;
+            if (!deferred[b])
+                for (int k = s0; k < s1; ++k) at += vigo::guide_pushes(N, seg[2 * k], seg[2 * k + 1], i);
+        }
+        if (deferred[b]) return;
+        std::vector<vigo::G3> sc(longest);
+        auto emit = [&](int idx, const vigo::G3& p, const vigo::G3& d, const int32_t* dec) {
+            const int g = cursor[idx]++;
+            for (int a = 0; a < 3; ++a) { out_pv[(size_t)g * 6 + a] = p.v[a]; out_pv[(size_t)g * 6 + 3 + a] = d.v[a]; }
+            if (out_unk) out_unk[g] = (byteAt(p.v[0], p.v[1], p.v[2]) >> 1) & 1u;
+            if (out_decision) for (int a = 0; a < 3; ++a) out_decision[(size_t)g * 3 + a] = dec[a];
+        };
+        const double* c = ctrl + b * (size_t)N * 3;
+        const int* sg = seg + 2 * (size_t)s0;
+        const int* po = path_off + s0;
+        // (the core indexes the paths from path_off[0] of the slice it is given: hand it the whole array and the slice's offsets)
+        if (mode == 1) vigo::guide_assign(occ, vigo::GuideAtan2{}, res, N, c, s1 - s0, sg, po, path, sc.data(), emit);
+        else if (mode == 0) vigo::guide_assign(occ, [](double y, double x) { return std::atan2(y, x); }, res, N, c, s1 - s0, sg, po, path, sc.data(), emit);
+        else vigo::guide_assign(occ, NudgedAtan2{mode == 2 ? 2 : -2}, res, N, c, s1 - s0, sg, po, path, sc.data(), emit);
+    });
+    out_off[(size_t)B * N] = (int)first_pair[B];
+    return 0;
+}
+
+// the FACADE's own step (bsplineTraj::assignGuidePointsSemiCircle) on the same inputs, one planner per trajectory with
+// these control points and empty lists: offsets [B*N+1] and pairs as above.  Returns 0, -1 on a bad argument, -2 when
+// the pairs do not fit pair_cap.
+int vigo_host_guide_facade(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                           const int* seg_off, const int* seg, const int* path_off, const double* path, long long pair_cap, int* out_off,
+                           double* out_pv) {
+    if (B < 0 || N < 7 || !ctrl || !seg_off || !seg || !path_off || !path || !out_off || !out_pv) return -1;
+    const double cfg[6] = {0.5, 0.7, 1.3, 5.0, 5.0, 3.0};      // (the step reads none of them)
+    PlannerPool pool;
+    initPool(pool, vox, dims, origin, res, cfg);
+    std::vector<std::vector<int32_t>> off(B);
+    std::vector<std::vector<double>> pv(B);
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        auto bt = pool.take();
+        Eigen::MatrixXd c(3, N);
+        for (int i = 0; i < N; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl[(b * N + i) * 3 + k];
+        bt->setControlPoints(c);
+        std::vector<std::pair<int, int>> sg;
+        std::vector<std::vector<Eigen::Vector3d>> paths;
+        for (int k = seg_off[b]; k < seg_off[b + 1]; ++k) {
+            sg.push_back({seg[2 * k], seg[2 * k + 1]});
+            paths.emplace_back();
+            for (int q = path_off[k]; q < path_off[k + 1]; ++q) paths.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
+        }
+        bt->assignGuidePointsSemiCircle(paths, sg);
+        off[b].assign(1, 0);
+        vigo_host::appendGuides(bt->getOptData(), N, off[b], pv[b]);
+        pool.give(std::move(bt));
+    });
+    long long g = 0;
+    for (int b = 0; b < B; ++b) {
+        for (int i = 0; i < N; ++i) out_off[(size_t)b * N + i] = (int)(g + off[b][i]);
+        g += off[b][N];
+    }
+    out_off[(size_t)B * N] = (int)g;
+    if (g > pair_cap) return -2;
+    long long w = 0;
+    for (int b = 0; b < B; ++b) { std::memcpy(out_pv + 6 * w, pv[b].data(), pv[b].size() * sizeof(double)); w += (long long)pv[b].size() / 6; }
+    return 0;
+}
+
+// What vigo_guide_assign is given in makePlan()'s prologue, by the host pipeline (findCollisionSeg -> pathSearch) for n
+// sets of control points [n][N][3] on one dense byte grid: seg_off[n+1], seg[seg_cap][2] (after the merges, with the
+// min(collisionSeg.size(), paths.size()) bound applied), path_off[seg_cap+1], path[pt_cap][3].  A trajectory whose A*
+// fails has no segments (status[t] = -2, as vigo_host_bspline_guides_batch).  cfg as in vigo_host_bspline_prologue.
+// Returns 0, -1 on a bad argument, -2 when a buffer is too small.
+int vigo_host_prologue_paths(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int N, const double* ctrl,
+                             const double* cfg, int seg_cap, long long pt_cap, int* status, int* seg_off, int* seg, int* path_off,
+                             double* path) {
+    if (n < 0 || N < 7 || !ctrl || !cfg || !status || !seg_off || !seg || !path_off || !path) return -1;
+    PlannerPool pool;
+    initPool(pool, vox, dims, origin, res, cfg);
+    std::vector<std::vector<std::pair<int, int>>> segs(n);
+    std::vector<std::vector<std::vector<Eigen::Vector3d>>> paths(n);
+    vigo_host::parallelFor((size_t)n, [&](size_t t) {
+        auto bt = pool.take();
+        Eigen::MatrixXd c(3, N);
+        for (int i = 0; i < N; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl[(t * N + i) * 3 + k];
+        bt->setControlPoints(c);
+        status[t] = 0;
+        bt->findCollisionSeg(c, segs[t]);
+        if (!bt->pathSearch(segs[t], paths[t])) {
+            status[t] = -2;
+            segs[t].clear();
+            paths[t].clear();
+        }
+        pool.give(std::move(bt));
+    });
+    long long s = 0, q = 0;
+    seg_off[0] = 0;
+    path_off[0] = 0;
+    for (int t = 0; t < n; ++t) {
+        const size_t m = std::min(segs[t].size(), paths[t].size());
+        for (size_t k = 0; k < m; ++k) {
+            if (s + 1 > seg_cap || q + (long long)paths[t][k].size() > pt_cap) return -2;
+            seg[2 * s] = segs[t][k].first;
+            seg[2 * s + 1] = segs[t][k].second;
+            for (const auto& v : paths[t][k]) { for (int a = 0; a < 3; ++a) path[3 * q + a] = v(a); ++q; }
+            ++s;
+            path_off[s] = (int)q;
+        }
+        seg_off[t + 1] = (int)s;
+    }
+    return 0;
+}
+
+// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
+// every run: first ONE run before any setter is touched (slot 0: the untouched default), then `reps` rounds of
+// setDeviceGuides(0), (1), (2) in turn (slots 1, 2, 3), each with setDeviceAstar(astar != 0).  Outputs per slot [4] x ...
+// of the slot's LAST run: ok[n], solver[n], ncp[n], ctrl[n][ncp_cap][3] (zero padded), n_guides[n] + guides[cap][6]
+// (point, direction; concatenated in planner order); per run prologue_ms[4][reps] and total_ms[4][reps] (slot 0: entry 0
+// only); counts[4][2]: the trajectories of the slot's last run whose guides the device produced / the workers' twin
+// produced.  cfg as in vigo_host_bspline_prologue.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
+int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
+                                const double* path_xyz, const double* cfg, int astar, int reps, int ncp_cap, long long cap, int* ok,
+                                int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, double* prologue_ms, double* total_ms,
+                                long long* counts) {
+    using trajPlanner::bsplineTraj;
+    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg) return -1;
+    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), vox, map->voxels().size());
+    ros::NodeHandle nh;
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    nh.setParam("bspline_traj/max_path_length", 1000.0);
+    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
+    std::vector<nav_msgs::Path> in(n);
+    for (int t = 0; t < n; ++t)
+        for (int i = 0; i < n_pts; ++i) {
+            geometry_msgs::PoseStamped ps;
+            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
+            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
+            in[t].poses.push_back(ps);
+        }
+    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    int rc = 0;
+    for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
+        const int slot = run == 0 ? 0 : 1 + (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
+        std::vector<std::unique_ptr<bsplineTraj>> owners;
+        std::vector<bsplineTraj*> ps;
+        for (int t = 0; t < n; ++t) {
+            owners.emplace_back(new bsplineTraj(nh));
+            owners.back()->setMap(map);
+            owners.back()->updateMaxVel(2.0);
+            owners.back()->updateMaxAcc(3.0);
+            ps.push_back(owners.back().get());
+        }
+        bsplineTraj::updatePathBatch(ps, in, cond);
+        if (run > 0) {
+            bsplineTraj::setDeviceAstar(astar != 0);
+            bsplineTraj::setDeviceGuides(slot - 1);
+        }
+        long long dev0, host0, dev1, host1;
+        double pro0, pro1;
+        bsplineTraj::deviceGuideTotals(&dev0, &host0);
+        bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
+        total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
+        bsplineTraj::deviceGuideTotals(&dev1, &host1);
+        prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
+        counts[2 * slot] = dev1 - dev0;
+        counts[2 * slot + 1] = host1 - host0;
+        if (run > 0) {
+            bsplineTraj::setDeviceAstar(false);
+            bsplineTraj::setDeviceGuides(0);
+        }
+        if (run > 0 && rep + 1 < reps) continue;
+        long long g = 0;
+        for (int t = 0; t < n && rc == 0; ++t) {
+            const size_t o = (size_t)slot * n + t;
+            const Eigen::MatrixXd c = ps[t]->getControlPoints();
+            ok[o] = res2[t] ? 1 : 0;
+            solver[o] = ps[t]->getLastSolverStatus();
+            ncp[o] = (int)c.cols();
+            if (c.cols() > ncp_cap) { rc = -2; break; }
+            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
+            std::vector<int32_t> off{0};
+            std::vector<double> pv;
+            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
+            n_guides[o] = (int)(pv.size() / 6);
+            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
+            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
+            g += (long long)pv.size() / 6;
+        }
+    }
+    return rc;
+}
+
+}  // extern "C"
 
 // mapAdapter::rasterise (the generic route: four public map methods only) over the whole box of a dense map must give
 // back that map's inflated-occupied and unknown bits.  Returns the number of differing voxels (0 = agreement), -1 on

@@ -17,6 +17,7 @@ PREC_F64 = 0
 PREC_F32 = 1
 PREC_F64_FAST = 2
 ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_DEFERRED, ASTAR_PATH_TOO_LONG = 0, 1, 2, 3   # vigo_astar_search's out_status
+GUIDE_OK, GUIDE_DEFERRED = 0, 1                                                  # vigo_guide_assign's out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -455,6 +456,24 @@ class Vigo:
             C.c_void_p(status.data_ptr()), C.c_void_p(length.data_ptr()), C.c_void_p(path.data_ptr()),
             C.c_void_p(stats.data_ptr()) if want_stats else None), "vigo_astar_search")
         return status, length, path, stats
+
+    def guide_assign(self, ctrl, seg_off, seg, path_off, path, pair_cap, want_unknown=True):
+        """vigo_guide_assign: the prologue's guide assignment for B trajectories (ctrl f64 [B,N,3]; seg_off int32 [B+1], seg int32
+        [S,2], path_off int32 [S+1], path f64 [P,3]) -> (guide_off int32 [B*N+1], guide_pv f64 [pair_cap,6], guide_unk uint8
+        [pair_cap] or None, status int32 [B]: GUIDE_OK / GUIDE_DEFERRED)"""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, N = ctrl.shape[0], ctrl.shape[1]
+        d = self.device
+        off = torch.zeros(B * N + 1, dtype=torch.int32, device=d)
+        pv = torch.zeros((max(int(pair_cap), 1), 6), dtype=torch.float64, device=d)
+        unk = torch.zeros(max(int(pair_cap), 1), dtype=torch.uint8, device=d) if want_unknown else None
+        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
+        self._check(self._lib.vigo_guide_assign(
+            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), _ptr(seg_off, torch.int32, "seg_off", d), _ptr(seg, torch.int32, "seg", d),
+            _ptr(path_off, torch.int32, "path_off", d), _ptr(path, torch.float64, "path", d), int(pair_cap), C.c_void_p(off.data_ptr()),
+            C.c_void_p(pv.data_ptr()), C.c_void_p(unk.data_ptr()) if want_unknown else None, C.c_void_p(status.data_ptr())),
+            "vigo_guide_assign")
+        return off, pv[:int(pair_cap)], (unk[:int(pair_cap)] if want_unknown else None), status[:B]
 
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
