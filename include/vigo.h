@@ -279,7 +279,8 @@ int vigo_traj_dynamic_collision(vigo_handle_t h, int B, int N, const double* ctr
  * Replaces the map queries of bsplineTraj::findCollisionSeg (BT.cpp:403-445):
  *   out_pt   uint8[B][N]  isInflatedOccupied(ctrl[i])
  *   out_line uint8[B][N]  isInflatedOccupiedLine(ctrl[i-1], ctrl[i]) (entry 0 = 0)
- * The segment bookkeeping itself stays on the host (it is a serial scan of these flags).
+ * The segment bookkeeping is a serial scan of these flags: on the host in the rebound loop, on the device in
+ * vigo_collision_segs / vigo_path_search.
  */
 int vigo_ctrl_occupancy(vigo_handle_t h, int B, int N, const double* ctrl,
                         uint8_t* out_pt, uint8_t* out_line);
@@ -551,6 +552,70 @@ int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const i
                       double* out_guide_pv, uint8_t* out_guide_unk, int32_t* out_status);
 /* The longest path (points of one segment) vigo_guide_assign holds (host utility, no GPU). */
 int vigo_guide_capacity(int32_t* max_path_points);
+
+/*
+ * Replaces: bsplineTraj::findCollisionSeg (BT.cpp:403-445) for B trajectories of N control points on the handle's grid
+ * snapshot — the segment bookkeeping that vigo_ctrl_occupancy leaves to the host.
+ *   ctrl             double[B][N][3]
+ *   not_check_ratio  the planner's notCheckRatio_, in [0, 1]
+ *   out_seg_off      int32[B+1]        CSR of the segments per trajectory
+ *   out_seg          int32[seg_cap][2] (first, second) in the order the reference pushes them
+ *   out_status       int32[B]          VIGO_PATHS_OK | VIGO_PATHS_DEFERRED: more than VIGO_MAX_COLLISION_SEGS segments;
+ *                                      the trajectory owns none — run the host step
+ * The rules are the reference's: control points 3 .. endIdx = int((N - 4) - not_check_ratio * (N - 6)) in order; a run of
+ * occupied points opens a segment at the point before it and closes it at the first free point; an occupied point at
+ * endIdx - 1 pushes (start, N - 1) — and when the point at endIdx is free the same start is pushed again, closed there:
+ * the duplicate is kept; two neighbouring free points whose line is occupied push (i - 1, i).  Point and line tests are
+ * vigo_ctrl_occupancy's (isInflatedOccupied / isInflatedOccupiedLine of the dense map contract).
+ * How: vigo_ctrl_occupancy's kernel for the flags, a one-workgroup kernel that counts and scans (its verdict is read
+ * back before anything is written), then one thread per trajectory repeats the scan and writes in place.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle or array (every array when B = 0), B < 0, N < 7, seg_cap < 0 or too
+ * small, not_check_ratio outside [0, 1] — nothing is written; VIGO_ERR_NO_GRID before a grid.  B = 0 is a no-op.
+ */
+enum { VIGO_PATHS_OK = 0, VIGO_PATHS_FAILED = 1, VIGO_PATHS_DEFERRED = 2 };
+int vigo_collision_segs(vigo_handle_t h, int B, int N, const double* ctrl, double not_check_ratio, int32_t* out_seg_off,
+                        int32_t* out_seg, int64_t seg_cap, int32_t* out_status);
+
+/*
+ * Replaces: bsplineTraj::pathSearch (BT.cpp:447-514) — the A* search per collision segment, the second-choice search to
+ * the next segment's end, searchedPath[0] = pStart, push_back(pEnd) and the merge bookkeeping — for B trajectories, on
+ * the segments of vigo_collision_segs(ctrl, not_check_ratio) when seg_off == seg == NULL, or on a caller's list
+ * (seg_off int32[B+1], seg int32[S][2], ends in [0, N): the re-guide step of the rebound loop searches a subset).
+ *   step, pool (HOST pointer), min/max_height, max_expansions, search_path_cap   the searches, as vigo_astar_search
+ *   out_status    int32[B]  VIGO_PATHS_OK        segments and paths are the host's, bit for bit
+ *                           VIGO_PATHS_FAILED    the reference's "Path Search Error. Force return.": a search failed
+ *                                                and so did its second choice (or there was none); no segments, no paths
+ *                           VIGO_PATHS_DEFERRED  a search the walk consulted came back VIGO_ASTAR_DEFERRED or
+ *                                                VIGO_ASTAR_PATH_TOO_LONG, or the trajectory has more than
+ *                                                VIGO_MAX_COLLISION_SEGS segments: no segments, no paths — run the host
+ *                                                steps.  The device never returns what the host would not return.
+ *   out_seg_off   int32[B+1], out_seg int32[seg_cap][2], out_path_off int32[seg_cap+1], out_path double[point_cap][3]:
+ *                 exactly vigo_guide_assign's seg_off / seg / path_off / path — the segments AFTER the merges with the
+ *                 reference's min(collisionSeg.size(), paths.size()) bound applied, path k the k-th path pushed.  Entries
+ *                 of out_path_off beyond the call's segments + 1 are not written.
+ *   out_counts    int32[B][2] or NULL: the searches run for the trajectory, and how many of them came back FOUND or
+ *                 NOT_FOUND
+ * The rules, quirks included: a path is the search's points with point 0 replaced by ctrl[first] and ctrl[second]
+ * appended; when segment i's search fails and the next segment starts at most 2 after its end, the search runs again to
+ * the next segment's end, the next segment is skipped and i is a merge; once ONE merge is taken the segments become the
+ * merged pairs (first of i, second of i + 1) ALONE — the unmerged ones are dropped while their paths stay, so segment k
+ * then goes with path k by position.  A second-choice search runs for every failed, eligible segment before the walk;
+ * one the walk does not consult does not change the status.  A trajectory's result does not depend on its batch.
+ * How: the kernels of vigo_collision_segs; every first-choice search in one vigo_astar_search launch; a one-workgroup
+ * kernel lists the second-choice searches; those in a second launch; a one-workgroup kernel walks each trajectory and
+ * scans segments and points; one wavefront per trajectory then compacts the searches' fixed-stride paths into the CSR
+ * output, a point per lane.  Three small reads come back in between (search counts, the totals held against seg_cap and
+ * point_cap); segments, ends and paths stay on the device.  Plain vector stores, no atomics.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle or array (out_counts may be NULL; seg_off and seg both or neither;
+ * every array when B = 0), B < 0, N < 7, offsets that decrease or start below 0, a segment end outside [0, N), seg_cap or
+ * point_cap negative or too small, not_check_ratio outside [0, 1] when the segments are scanned, and vigo_astar_search's
+ * checks of pool, step, search_path_cap and max_expansions (VIGO_ERR_UNSUPPORTED for a pool axis above
+ * VIGO_ASTAR_MAX_POOL_AXIS) — in every such case nothing is written; VIGO_ERR_NO_GRID before a grid.  B = 0 is a no-op.
+ */
+int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
+                     double not_check_ratio, double step, const int32_t pool[3], double min_height, double max_height,
+                     int max_expansions, int search_path_cap, int64_t seg_cap, int64_t point_cap, int32_t* out_status,
+                     int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off, double* out_path, int32_t* out_counts);
 
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and

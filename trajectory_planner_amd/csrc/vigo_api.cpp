@@ -281,6 +281,8 @@ int vigo_destroy(vigo_handle_t h) {
     if (h->fit_pinvT) (void)hipFree(h->fit_pinvT);
     if (h->times_dev) (void)hipFree(h->times_dev);
     if (h->scratch) (void)hipFree(h->scratch);
+    for (void* w : h->paths_ws)
+        if (w) (void)hipFree(w);
     if (h->rebound_idx) (void)hipFree(h->rebound_idx);
     if (h->dc_dev) (void)hipFree(h->dc_dev);
     for (int i = 0; i < vigo_context::kDcSlots; ++i)
@@ -788,6 +790,146 @@ int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const i
 }
 int vigo_guide_capacity(int32_t* max_path_points) {
     if (max_path_points) *max_path_points = vigo::guide_path_capacity();
+    return VIGO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the per-trajectory scratch of vigo_collision_segs / vigo_path_search, carved out of h->scratch
+int path_search_scratch(vigo_handle_t h, int B, int N, bool flags, vigo::PathSearchArgs& a) {
+    const size_t words = ((size_t)B + 2) & ~(size_t)1;        // (an even number of int32: every array stays 8-byte aligned)
+    const size_t flag_bytes = flags ? (((size_t)B * N + 7) & ~(size_t)7) : 0;
+    int rc = ensure_scratch(h, 64 + 9 * words * 4 + 2 * flag_bytes);
+    if (rc) return rc;
+    char* p = static_cast<char*>(h->scratch);
+    a.result = reinterpret_cast<long long*>(p);
+    int32_t* w = reinterpret_cast<int32_t*>(p + 64);
+    a.in_off = w;
+    a.n_in = w + words;
+    a.pre = w + 2 * words;
+    a.tstatus = w + 3 * words;
+    a.n_out = w + 4 * words;
+    a.oseg_off = w + 5 * words;
+    a.opt_off = w + 6 * words;
+    a.tcounts = w + 7 * words;                                 // [B][2]
+    uint8_t* f = reinterpret_cast<uint8_t*>(w + 9 * words);
+    a.pt = flags ? f : nullptr;
+    a.ln = flags ? f + flag_bytes : nullptr;
+    return VIGO_OK;
+}
+
+int ensure_paths_ws(vigo_handle_t h, int which, size_t bytes) {
+    if (bytes <= h->paths_ws_bytes[which]) return VIGO_OK;
+    if (h->paths_ws[which]) (void)hipFree(h->paths_ws[which]);
+    h->paths_ws[which] = nullptr;
+    h->paths_ws_bytes[which] = 0;
+    const size_t want = bytes + bytes / 4 + 4096;
+    VIGO_HIP(h, hipMalloc(&h->paths_ws[which], want));
+    h->paths_ws_bytes[which] = want;
+    return VIGO_OK;
+}
+
+// flags and segment counts of the call, read back: result[0] segments, result[1] a bad list
+int path_search_count(vigo_handle_t h, vigo::PathSearchArgs& a, long long result[2], const char* bad_list) {
+    if (!a.seg_in)
+        VIGO_HIP(h, (hipError_t)vigo::launch_ctrl_occupancy(h->stream, h->grid, a.B, a.N, a.ctrl, const_cast<uint8_t*>(a.pt), const_cast<uint8_t*>(a.ln)));
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_count(h->stream, a));
+    VIGO_HIP(h, hipMemcpyAsync(result, a.result, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    if (result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, bad_list);
+    return VIGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vigo_collision_segs(vigo_handle_t h, int B, int N, const double* ctrl, double not_check_ratio, int32_t* out_seg_off, int32_t* out_seg,
+                        int64_t seg_cap, int32_t* out_status) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (B < 0 || N < 7 || seg_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
+        (B > 0 && (!ctrl || !out_seg_off || !out_seg || !out_status)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_collision_segs: bad argument");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_collision_segs before vigo_set_grid");
+    if (B == 0) return VIGO_OK;
+    vigo::PathSearchArgs a{};
+    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio;
+    int rc = path_search_scratch(h, B, N, true, a);
+    if (rc) return rc;
+    long long result[2] = {0, 0};
+    rc = path_search_count(h, a, result, "vigo_collision_segs: bad list");
+    if (rc) return rc;
+    if (result[0] > (long long)seg_cap) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_collision_segs: the segments do not fit seg_cap");
+    a.out_seg_off = out_seg_off; a.out_status = out_status;
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, out_seg, nullptr, nullptr));
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_segs_out(h->stream, a));
+    return VIGO_OK;
+}
+
+int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, double not_check_ratio,
+                     double step, const int32_t pool[3], double min_height, double max_height, int max_expansions, int search_path_cap,
+                     int64_t seg_cap, int64_t point_cap, int32_t* out_status, int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off,
+                     double* out_path, int32_t* out_counts) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    const bool scan = !seg_off && !seg;
+    if (B < 0 || N < 7 || seg_cap < 0 || point_cap < 0 || (!scan && (!seg_off || !seg)) ||
+        (scan && !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0)) || !pool || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || !(step > 0.0) ||
+        !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 ||
+        (B > 0 && (!ctrl || !out_status || !out_seg_off || !out_seg || !out_path_off || !out_path)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: bad argument");
+    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_path_search: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_path_search before vigo_set_grid");
+    if (B == 0) return VIGO_OK;
+    vigo::PathSearchArgs a{};
+    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_off_in = seg_off; a.seg_in = seg;
+    a.search_path_cap = search_path_cap;
+    int rc = path_search_scratch(h, B, N, scan, a);
+    if (rc) return rc;
+    long long result[5] = {0, 0, 0, 0, 0};
+    rc = path_search_count(h, a, result, "vigo_path_search: offsets that decrease or start below 0, or a segment end outside [0, N)");
+    if (rc) return rc;
+    const size_t S = (size_t)result[0];
+    vigo::PathSearchWork w{};
+    if (S > 0) {
+        // [0]: per first-choice search 2 + 2 + 1 + 1 + 1 + 1 int32, 4 x 3 doubles and a path; everything 8-byte aligned
+        const size_t Se = (S + 1) & ~(size_t)1, path_doubles = S * (size_t)search_path_cap * 3;
+        rc = ensure_paths_ws(h, 0, Se * 8 * 4 + S * 12 * 8 + path_doubles * 8);
+        if (rc) return rc;
+        double* d = static_cast<double*>(h->paths_ws[0]);
+        w.start1 = d; w.end1 = d + 3 * S; w.start2 = d + 6 * S; w.end2 = d + 9 * S; w.path1 = d + 12 * S;
+        int32_t* i = reinterpret_cast<int32_t*>(d + 12 * S + path_doubles);
+        w.seg = i; w.mseg = i + 2 * Se; w.pick = i + 4 * Se; w.retry_of = i + 5 * Se; w.status1 = i + 6 * Se; w.len1 = i + 7 * Se;
+        VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, w.seg, w.start1, w.end1));
+        VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)S, w.start1, w.end1, step, pool, min_height, max_height, max_expansions,
+                                                   search_path_cap, w.status1, w.len1, w.path1, nullptr, h->launch));
+        VIGO_HIP(h, (hipError_t)vigo::launch_ps_retry(h->stream, a, w));
+        VIGO_HIP(h, hipMemcpyAsync(result + 2, a.result + 2, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+        VIGO_HIP(h, hipStreamSynchronize(h->stream));
+        const size_t Q2 = (size_t)result[2];
+        if (Q2 > 0) {
+            const size_t Qe = (Q2 + 1) & ~(size_t)1, path2_doubles = Q2 * (size_t)search_path_cap * 3;
+            rc = ensure_paths_ws(h, 1, path2_doubles * 8 + Qe * 2 * 4);
+            if (rc) return rc;
+            w.path2 = static_cast<double*>(h->paths_ws[1]);
+            w.status2 = reinterpret_cast<int32_t*>(w.path2 + path2_doubles);
+            w.len2 = w.status2 + Qe;
+            VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)Q2, w.start2, w.end2, step, pool, min_height, max_height,
+                                                       max_expansions, search_path_cap, w.status2, w.len2, w.path2, nullptr, h->launch));
+        }
+    }
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_decide(h->stream, a, w));
+    VIGO_HIP(h, hipMemcpyAsync(result + 3, a.result + 3, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    if (result[3] > (long long)seg_cap || result[3] >= 0x7fffffffLL)
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the segments do not fit seg_cap");
+    if (result[4] > (long long)point_cap || result[4] > 0x7fffffffLL)
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the path points do not fit point_cap");
+    a.out_status = out_status; a.out_seg_off = out_seg_off; a.out_seg = out_seg; a.out_path_off = out_path_off; a.out_path = out_path;
+    a.out_counts = out_counts;
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)result[3], (int)result[4]));
     return VIGO_OK;
 }
 

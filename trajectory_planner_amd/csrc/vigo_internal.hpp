@@ -208,6 +208,57 @@ int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const do
                         const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
                         const int32_t* status);
 
+// batched findCollisionSeg / pathSearch (vigo_pathsearch.hip).  Everything but the out_* members is device scratch of
+// the call; the kernels and what vigo_api.cpp reads back between them are listed in that file's header.
+struct PathSearchArgs {
+    int B, N;
+    const double* ctrl;
+    double not_check_ratio;
+    const int32_t* seg_off_in;   // the supplied list, or NULL: the scan over pt / ln
+    const int32_t* seg_in;
+    const uint8_t* pt;           // [B][N] vigo_ctrl_occupancy's flags
+    const uint8_t* ln;
+    int search_path_cap;
+    long long* result;           // [0] first-choice searches, [1] != 0: a bad list, [2] second-choice searches,
+                                 // [3] segments of the output, [4] its path points
+    int32_t* in_off;             // [B+1] first search / input segment of a trajectory
+    int32_t* n_in;               // [B]   its input segments (0 when pre)
+    int32_t* pre;                // [B]   != 0: more than VIGO_MAX_COLLISION_SEGS segments
+    int32_t* tstatus;            // [B]   k_ps_decide: status, segments, first output segment, first path point, counts
+    int32_t* n_out;
+    int32_t* oseg_off;
+    int32_t* opt_off;
+    int32_t* tcounts;            // [B][2]
+    int32_t* out_status;
+    int32_t* out_seg_off;
+    int32_t* out_seg;
+    int32_t* out_path_off;
+    double* out_path;
+    int32_t* out_counts;
+};
+struct PathSearchWork {          // sized by the searches of the call
+    int32_t* seg;                // [S][2] input segments
+    int32_t* mseg;               // [S][2] a trajectory's segments after the merges (at in_off)
+    int32_t* pick;               // [S]    its paths' searches (path_walk)
+    int32_t* retry_of;           // [S]    the second-choice search of a segment, or -1
+    double* start1;              // [S][3]
+    double* end1;
+    double* start2;              // [S][3] (Q2 <= S used)
+    double* end2;
+    int32_t* status1;            // [S]
+    int32_t* len1;
+    double* path1;               // [S][search_path_cap][3]
+    int32_t* status2;            // [Q2]
+    int32_t* len2;
+    double* path2;
+};
+int launch_ps_count(hipStream_t s, const PathSearchArgs& a);
+int launch_ps_fill(hipStream_t s, const PathSearchArgs& a, int32_t* dst_seg, double* start, double* end);
+int launch_ps_segs_out(hipStream_t s, const PathSearchArgs& a);
+int launch_ps_retry(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w);
+int launch_ps_decide(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w);
+int launch_ps_write(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w, int total_seg, int total_pts);
+
 }  // namespace vigo
 
 struct vigo_context {
@@ -251,4 +302,7 @@ struct vigo_context {
     // scratch (sample-time tables, corridor checkpoints, staging of *_host calls)
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
+    // vigo_path_search: the buffers sized by the call's first-choice ([0]) and second-choice ([1]) searches
+    void* paths_ws[2] = {nullptr, nullptr};
+    size_t paths_ws_bytes[2] = {0, 0};
 };

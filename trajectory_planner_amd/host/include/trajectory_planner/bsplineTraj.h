@@ -128,6 +128,7 @@ public:
      * split into pipelined parts, which run side by side. */
     static void deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds);
     const std::vector<std::vector<Eigen::Vector3d>>& getAstarPaths() const { return astarPaths_; }   /* added (tests) */
+    const std::vector<std::pair<int, int>>& getCollisionSeg() const { return collisionSeg_; }         /* added (tests) */
     /* Step 3 of makePlanBatch's prologue (assignGuidePointsSemiCircle).  0 (default): the host step as it always was.
      * 1: ONE vigo_guide_assign launch per device group; a planner the device defers (a path longer than
      * vigo_guide_capacity), or whose group has no device or snapshot, runs the same code on the worker threads —
@@ -139,6 +140,24 @@ public:
     static int deviceGuides();
     /* Process-wide running totals: the prologue trajectories whose guides the device produced / the workers' twin produced */
     static void deviceGuideTotals(long long* deviceDecided, long long* hostRun);
+    /* The whole prologue of makePlanBatch (steps 1-3) as ONE device chain per group of planners that share a batch key:
+     * control points up, vigo_path_search (findCollisionSeg, the A* searches, pathSearch's merge rules) and
+     * vigo_guide_assign on its output, one download; collisionSeg_, astarPaths_ and the guide pairs are then installed
+     * where the host steps put them.  Default false; when on, setDeviceAstar / setDeviceGuides are not consulted.  A
+     * planner either call defers, one whose merges leave more paths than segments (the device returns the bounded
+     * lists only), and every planner of a group without device or snapshot run host steps 1-3 on the workers with the
+     * guide step's bit-exact twin (as setDeviceGuides(1) does for what the device defers): a plan does not depend on
+     * which side ran it.  A planner whose path search FAILS on the device takes the "Fail because of A* failure" path
+     * after replaying host steps 1-2 on the workers: vigo_path_search returns nothing for it, and the host steps leave
+     * the scanned segments and the paths found before the failure in getCollisionSeg() / getAstarPaths(), so these
+     * read the same under every setting.  Searches run under setDeviceAstarBudget.  The re-guide step inside the
+     * rebound loop (findCollisionSeg, A*, guide assignment on the current control points) stays on the host. */
+    static void setDevicePrologue(bool on);
+    static bool devicePrologue();
+    /* Process-wide running totals: the prologue planners whose outcome the device chain decided (prepared, or failed:
+     * those replay host steps 1-2 for their lists and still count here) / those the host steps decided (deferred, lists
+     * cut by the bound, no device), and the wall time of the chains (upload to installed results) in seconds */
+    static void devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds);
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
@@ -237,6 +256,8 @@ private:
     /* step 3 of the prologue under setDeviceGuides(1 | 2) for the planners with found[i] */
     static void assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found);
     void assignGuidesCore();
+    /* steps 1-3 under setDevicePrologue(true); outcome[i]: 1 prepared, 2 failed (A*), 0 not a planner of the batch */
+    static void prologueOnDevice(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<uint8_t>& outcome);
     void packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const;
     static void reboundOnDevice(PlanBatch& pb, bool timing);
     static void reboundFromHost(PlanBatch& pb, bool timing);

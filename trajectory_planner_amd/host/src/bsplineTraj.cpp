@@ -24,6 +24,7 @@
 
 #include "../../../include/vigo.h"
 #include "../../csrc/vigo_guide_core.hpp"
+#include "../../csrc/vigo_pathsearch_core.hpp"
 #include "batchLayout.h"
 #include "devbuf.h"
 #include "workerPool.h"
@@ -1026,6 +1027,7 @@ struct bsplineTraj::PlanBatch {
     std::vector<bsplineTraj*> active;
     std::vector<size_t> activeIdx;
     std::atomic<long long> nsSeg{0}, nsAstar{0}, nsGuide{0};   // prologue CPU time summed over the worker threads
+    std::atomic<long long> nsChain{0};                         // setDevicePrologue: wall time of the device chains (all three steps)
     explicit PlanBatch(size_t P) : rb(P), result(P, false) {}
 };
 
@@ -1049,7 +1051,8 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
     planEpilogue(planners, pb.result);
     if (timing) {
         cout << "[BsplineTraj]: prologue CPU time summed over the workers: findCollisionSeg " << pb.nsSeg.load() * 1e-6 << " ms, A* "
-             << pb.nsAstar.load() * 1e-6 << " ms, guide assignment " << pb.nsGuide.load() * 1e-6 << " ms" << endl;
+             << pb.nsAstar.load() * 1e-6 << " ms, guide assignment " << pb.nsGuide.load() * 1e-6 << " ms; device chains (wall) "
+             << pb.nsChain.load() * 1e-6 << " ms" << endl;
         cout << "[BsplineTraj]: makePlanBatch of " << P << ": prologue " << (tp1 - tp0) * 1e3 << " ms, rebound loop " << (tp2 - tp1) * 1e3
              << " ms, epilogue " << (wallSeconds() - tp2) * 1e3 << " ms" << endl;
     }
@@ -1098,8 +1101,13 @@ std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>
 void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb) {
     const size_t P = planners.size();
     std::vector<uint8_t> prepared(P, 0), hasPaths(P, 0);
-    const int guides = deviceGuides();
-    if (deviceAstar()) {
+    const int guides = devicePrologue() ? 0 : deviceGuides();
+    if (devicePrologue()) {
+        // the three steps as one device chain per group; what the device does not decide runs the host steps there too
+        std::vector<uint8_t> outcome(P, 0);
+        prologueOnDevice(planners, pb, outcome);
+        for (size_t i = 0; i < P; ++i) prepared[i] = outcome[i] == 1;
+    } else if (deviceAstar()) {
         // the same three steps with step 2 gathered over the planners: collision segments on the workers, the searches
         // of all planners on the device (pathSearchBatch), guide assignment on the workers
         std::vector<uint8_t> ready(P, 0), found(P, 0);
@@ -1353,6 +1361,160 @@ void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, con
         }
         applyMerges(collisionSeg, mergeIndices);
         found[i] = 1;
+    });
+}
+
+namespace {
+std::atomic<bool> g_devicePrologue{false};
+std::atomic<long long> g_prologueDeviceDecided{0}, g_prologueHostRun{0}, g_prologueChainNs{0};
+}  // namespace
+void bsplineTraj::setDevicePrologue(bool on) { g_devicePrologue.store(on); }
+bool bsplineTraj::devicePrologue() { return g_devicePrologue.load(); }
+void bsplineTraj::devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds) {
+    if (deviceDecided) *deviceDecided = g_prologueDeviceDecided.load();
+    if (hostRun) *hostRun = g_prologueHostRun.load();
+    if (chainSeconds) *chainSeconds = g_prologueChainNs.load() * 1e-9;
+}
+
+// Steps 1-3 for all planners under setDevicePrologue(true).  Per group of planners that share a batch key and a node
+// pool: control points up, vigo_path_search on the scanned segments, vigo_guide_assign on its output (device pointers,
+// nothing repacked), then one round of downloads and the results installed per planner.  What is left (see the header)
+// runs findCollisionSeg -> pathSearch -> assignGuidesCore on the workers.
+// Buffer sizes: segCap = B * VIGO_MAX_COLLISION_SEGS is the entry's own bound.  pointCap = B * 2 * (kAstarPathCap + 1) and
+// pairCap = B * N * 4 are budgets, not bounds (the bounds, 48 full-length paths per planner and every path point a pair,
+// would be ~150 MB per 1024 planners): two full-length paths and four pairs per control point on AVERAGE over the
+// group, against 17 path points and 4.4 pairs per PLANNER on the pipeline batches.  A group over pointCap gets
+// VIGO_ERR_INVALID_ARG from vigo_path_search (nothing written, the message is printed) and runs the host steps as a
+// whole; a group over pairCap keeps the device's segments and paths and has the twin assign its guides.  Both are
+// correct and slow, and both show in devicePrologueTotals' hostRun.
+void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<uint8_t>& outcome) {
+    const size_t P = planners.size();
+    std::vector<uint8_t> needGuides(P, 0);            // segments and paths are installed, the pairs are not
+    std::vector<uint8_t> failedOnDevice(P, 0);        // the device's walk failed: the host's replay leaves the lists
+    std::vector<size_t> owners;
+    for (size_t i = 0; i < P; ++i)
+        if (planners[i]->init_ && planners[i]->map_) owners.push_back(i);
+    auto same = [&](size_t a, size_t b) {
+        const bsplineTraj* x = planners[owners[a]];
+        const bsplineTraj* y = planners[owners[b]];
+        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
+               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
+    };
+    const double tc0 = wallSeconds();
+    vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+        bsplineTraj* lead = planners[owners[members[0]]];
+        if (!lead->syncDevice()) return;
+        const double res = lead->map_->getRes();
+        const int N = lead->optData_.controlPoints.cols();
+        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
+                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
+        if (N < 7 || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS ||
+            pool[2] > VIGO_ASTAR_MAX_POOL_AXIS || !(lead->notCheckRatio_ >= 0.0 && lead->notCheckRatio_ <= 1.0))
+            return;
+        std::vector<size_t> who;
+        std::vector<double> ctrl;
+        for (size_t m : members) {
+            const bsplineTraj* p = planners[owners[m]];
+#ifdef VIGO_WITH_ROS
+            // The snapshot of this map type covers the planner's region only and takes everything outside it for
+            // occupied.  Every search's node pool (pool / 2 + 1 nodes around the midpoint of two control points) and
+            // with it every path point lies in the control points' box grown by that much: a planner whose grown box
+            // is not inside the region keeps to its own map.
+            {
+                const mapRegion& R = p->mapRegion_;
+                bool inside = R.set;
+                for (int k = 0; k < 3 && inside; ++k) {
+                    const double half = (pool[k] / 2 + 1) * res;
+                    for (int i = 0; i < N && inside; ++i)
+                        inside = p->optData_.controlPoints(k, i) - half >= R.boxMin(k) && p->optData_.controlPoints(k, i) + half <= R.boxMax(k);
+                }
+                if (!inside) continue;
+            }
+#endif
+            for (int i = 0; i < N; ++i)
+                for (int a = 0; a < 3; ++a) ctrl.push_back(p->optData_.controlPoints(a, i));
+            who.push_back(owners[m]);
+        }
+        const int B = (int)who.size();
+        if (B == 0) return;
+        const long long segCap = (long long)B * VIGO_MAX_COLLISION_SEGS, pointCap = (long long)B * 2 * (kAstarPathCap + 1),
+                        pairCap = (long long)B * N * 4;
+        static thread_local StagingBuf dCtrl, dStatus, dSegOff, dSeg, dPathOff, dPath, dCounts, dOff, dPv, dGStatus;
+        if (!dCtrl.upload(ctrl.data(), ctrl.size() * 8) || !dStatus.alloc((size_t)B * 4) || !dSegOff.alloc(((size_t)B + 1) * 4) ||
+            !dSeg.alloc((size_t)segCap * 8) || !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) ||
+            !dCounts.alloc((size_t)B * 8) || !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)pairCap * 48) || !dGStatus.alloc((size_t)B * 4))
+            return;
+        if (vigo_path_search(lead->dev_, B, N, (const double*)dCtrl.p, nullptr, nullptr, lead->notCheckRatio_, res, pool, lead->minHeight_,
+                             lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, segCap, pointCap, (int32_t*)dStatus.p,
+                             (int32_t*)dSegOff.p, (int32_t*)dSeg.p, (int32_t*)dPathOff.p, (double*)dPath.p, (int32_t*)dCounts.p) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_path_search failed: " << vigo_last_error(lead->dev_) << endl;
+            return;
+        }
+        const bool guided = vigo_guide_assign(lead->dev_, B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
+                                              (const int32_t*)dPathOff.p, (const double*)dPath.p, pairCap, (int32_t*)dOff.p, (double*)dPv.p,
+                                              nullptr, (int32_t*)dGStatus.p) == VIGO_OK;   // (not: the pairs do not fit — the twin assigns them)
+        std::vector<int32_t> status(B), segOff(B + 1), counts((size_t)B * 2), off((size_t)B * N + 1, 0), gstatus(B, VIGO_GUIDE_DEFERRED);
+        if (!vigo_host::threadSync() || !dStatus.download(status.data(), (size_t)B * 4) || !dSegOff.download(segOff.data(), ((size_t)B + 1) * 4) ||
+            !dCounts.download(counts.data(), counts.size() * 4))
+            return;
+        if (guided && (!dOff.download(off.data(), off.size() * 4) || !dGStatus.download(gstatus.data(), (size_t)B * 4))) return;
+        const int S = segOff[B];
+        if (S < 0 || S > segCap || off.back() < 0 || off.back() > pairCap) return;
+        std::vector<int32_t> seg((size_t)S * 2), pathOff((size_t)S + 1, 0);
+        if (S > 0 && (!dSeg.download(seg.data(), seg.size() * 4) || !dPathOff.download(pathOff.data(), pathOff.size() * 4))) return;
+        if (pathOff[S] < 0 || pathOff[S] > pointCap) return;
+        std::vector<double> path((size_t)pathOff[S] * 3), pv((size_t)off.back() * 6);
+        if ((!path.empty() && !dPath.download(path.data(), path.size() * 8)) || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
+        for (int b = 0; b < B; ++b) {
+            bsplineTraj* p = planners[who[b]];
+            // A failed walk owns nothing on the device, but the host steps leave the scanned segments and the paths found
+            // before the failure in collisionSeg_ / astarPaths_: the planner replays steps 1-2 on the workers below.
+            if (status[b] == VIGO_PATHS_FAILED) { failedOnDevice[who[b]] = 1; continue; }
+            const int nOut = segOff[b + 1] - segOff[b];
+            // the device returns the bounded lists only: a planner whose astarPaths_ is longer runs the host steps
+            if (status[b] != VIGO_PATHS_OK || vigo::paths_cut_by_bound(counts[2 * (size_t)b], nOut)) continue;
+            p->collisionSeg_.clear();
+            p->astarPaths_.clear();
+            for (int k = segOff[b]; k < segOff[b + 1]; ++k) {
+                p->collisionSeg_.push_back({seg[2 * (size_t)k], seg[2 * (size_t)k + 1]});
+                p->astarPaths_.emplace_back();
+                for (int q = pathOff[k]; q < pathOff[k + 1]; ++q)
+                    p->astarPaths_.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
+            }
+            if (gstatus[b] != VIGO_GUIDE_OK) { needGuides[who[b]] = 1; continue; }
+            for (int i = 0; i < N; ++i)
+                for (int g = off[(size_t)b * N + i]; g < off[(size_t)b * N + i + 1]; ++g) {
+                    const double* q = pv.data() + (size_t)g * 6;
+                    p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+                    p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
+                }
+            outcome[who[b]] = 1;
+        }
+    });
+    const long long chainNs = (long long)((wallSeconds() - tc0) * 1e9);
+    pb.nsChain += chainNs;
+    g_prologueChainNs += chainNs;
+    long long nDecided = 0;
+    for (size_t i : owners) nDecided += (outcome[i] != 0 && !needGuides[i]) || failedOnDevice[i];
+    g_prologueDeviceDecided += nDecided;
+    g_prologueHostRun += (long long)owners.size() - nDecided;
+    parallelFor(owners.size(), [&](size_t o) {
+        const size_t i = owners[o];
+        bsplineTraj* p = planners[i];
+        if (outcome[i] != 0) return;
+        if (!needGuides[i]) {
+            const double t0 = wallSeconds();
+            p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);           // step 1
+            const double t1 = wallSeconds();
+            const bool found = p->pathSearch(p->collisionSeg_, p->astarPaths_);         // step 2
+            pb.nsSeg += (long long)((t1 - t0) * 1e9);
+            pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
+            if (!found) { outcome[i] = 2; return; }
+        }
+        const double t2 = wallSeconds();
+        p->assignGuidesCore();                                                          // step 3, the device's code
+        pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
+        outcome[i] = 1;
     });
 }
 

@@ -20,6 +20,7 @@
 
 #include "../../csrc/vigo_astar_core.hpp"
 #include "../../csrc/vigo_guide_core.hpp"
+#include "../../csrc/vigo_pathsearch_core.hpp"
 #include "batchLayout.h"
 #include "workerPool.h"
 
@@ -1044,6 +1045,161 @@ int vigo_host_prologue_paths(const unsigned char* vox, const int* dims, const do
     return 0;
 }
 
+// vigo_collision_segs on the host (csrc/vigo_pathsearch_core.hpp) on a dense byte grid: outputs as the device entry.
+// Returns 0; -1 for what the device entry answers with VIGO_ERR_INVALID_ARG (nothing is written).
+int vigo_host_collision_segs_core(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                                  double not_check_ratio, long long seg_cap, int* out_seg_off, int* out_seg, int* out_status) {
+    if (B < 0 || N < 7 || seg_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) || !(res > 0) ||
+        (B > 0 && (!ctrl || !out_seg_off || !out_seg || !out_status)))
+        return -1;
+    if (B == 0) return 0;
+    const size_t ny = dims[1], nz = dims[2];
+    auto occ = [&](double x, double y, double z) -> bool {     // dense_occmap.h byteAt & 1: outside is occupied
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
+        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
+    };
+    std::vector<std::vector<int32_t>> segs(B);
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        const double* c = ctrl + b * (size_t)N * 3;
+        auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
+        auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+        segs[b].resize(2 * vigo::kPathsMaxSegs);
+        const int n = vigo::collision_segs(N, not_check_ratio, pt, ln, vigo::kPathsMaxSegs, segs[b].data());
+        if (n > vigo::kPathsMaxSegs) segs[b].assign(1, -1);        // (marks the deferred ones)
+        else segs[b].resize(2 * (size_t)n);
+    });
+    long long total = 0;
+    for (int b = 0; b < B; ++b) total += segs[b].size() == 1 ? 0 : (long long)segs[b].size() / 2;
+    if (total > seg_cap) return -1;
+    long long s = 0;
+    for (int b = 0; b < B; ++b) {
+        out_seg_off[b] = (int)s;
+        out_status[b] = segs[b].size() == 1 ? vigo::kPathsDeferred : vigo::kPathsOk;
+        if (segs[b].size() == 1) continue;
+        std::copy(segs[b].begin(), segs[b].end(), out_seg + 2 * s);
+        s += (long long)segs[b].size() / 2;
+    }
+    out_seg_off[B] = (int)s;
+    return 0;
+}
+
+// vigo_path_search on the host: csrc/vigo_pathsearch_core.hpp around vigo::astar_search (csrc/vigo_astar_core.hpp) with a
+// table of 1 << cap_log2 slots holding at most max_nodes nodes and a heap of heap_cap entries (vigo_astar_capacity's
+// values with cap_log2 = 13: the kernels' twin; large ones: no search is deferred for want of room).  Inputs and outputs
+// as the device entry.  Returns 0; -1 for what the device entry answers with VIGO_ERR_INVALID_ARG or
+// VIGO_ERR_UNSUPPORTED (nothing is written).
+int vigo_host_path_search_core(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                               const int* seg_off, const int* seg, double not_check_ratio, double step, const int* pool, double min_height,
+                               double max_height, int cap_log2, int max_nodes, int heap_cap, int max_expansions, int search_path_cap,
+                               long long seg_cap, long long point_cap, int* out_status, int* out_seg_off, int* out_seg, int* out_path_off,
+                               double* out_path, int* out_counts) {
+    const bool scan = !seg_off && !seg;
+    if (B < 0 || N < 7 || seg_cap < 0 || point_cap < 0 || (!scan && (!seg_off || !seg)) || (scan && !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0)) ||
+        !pool || !(step > 0.0) || !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 || !(res > 0) || cap_log2 < 1 || cap_log2 > 30 ||
+        max_nodes < 1 || max_nodes >= (1 << cap_log2) || heap_cap < 1 ||
+        (B > 0 && (!ctrl || !out_status || !out_seg_off || !out_seg || !out_path_off || !out_path)))
+        return -1;
+    for (int a = 0; a < 3; ++a)
+        if (pool[a] < 3 || pool[a] > vigo::kAstarMaxPoolAxis) return -1;
+    if (B == 0) return 0;
+    if (!scan) {
+        if (seg_off[0] < 0) return -1;
+        for (int b = 0; b < B; ++b) {
+            if (seg_off[b + 1] < seg_off[b]) return -1;
+            if (seg_off[b + 1] - seg_off[b] > vigo::kPathsMaxSegs) continue;
+            for (int k = seg_off[b]; k < seg_off[b + 1]; ++k)
+                if (seg[2 * k] < 0 || seg[2 * k] >= N || seg[2 * k + 1] < 0 || seg[2 * k + 1] >= N) return -1;
+        }
+    }
+    const size_t ny = dims[1], nz = dims[2];
+    auto occ = [&](double x, double y, double z) -> bool {
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
+        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
+    };
+    struct Search { int status = vigo::kAstarDeferred, len = 0; std::vector<double> path; };
+    struct Traj { int status = vigo::kPathsDeferred, run = 0, decided = 0; std::vector<int32_t> seg; std::vector<std::vector<double>> paths; };
+    std::vector<Traj> out(B);
+    const size_t slots = (size_t)1 << cap_log2;
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        static thread_local std::vector<int32_t> key, heap;
+        static thread_local std::vector<double> g;
+        static thread_local std::vector<uint8_t> meta;
+        key.resize(slots); heap.resize((size_t)heap_cap); g.resize(slots); meta.resize(slots);
+        const double* c = ctrl + b * (size_t)N * 3;
+        Traj& T = out[b];
+        std::vector<int32_t> in(2 * vigo::kPathsMaxSegs);
+        int n;
+        if (scan) {
+            auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
+            auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+            n = vigo::collision_segs(N, not_check_ratio, pt, ln, vigo::kPathsMaxSegs, in.data());
+        } else {
+            n = seg_off[b + 1] - seg_off[b];
+            if (n <= vigo::kPathsMaxSegs) std::copy(seg + 2 * (size_t)seg_off[b], seg + 2 * (size_t)seg_off[b + 1], in.begin());
+        }
+        if (n > vigo::kPathsMaxSegs) return;                       // deferred, owns nothing
+        auto search = [&](int first, int second) {
+            Search r;
+            r.path.resize((size_t)search_path_cap * 3);
+            std::fill(key.begin(), key.end(), -1);
+            vigo::AstarStore<int32_t> S{};
+            S.key = key.data(); S.g = g.data(); S.meta = meta.data(); S.heap = heap.data();
+            S.cap_log2 = cap_log2; S.max_nodes = max_nodes; S.heap_cap = heap_cap;
+            r.status = vigo::astar_search(S, occ, c + 3 * (size_t)first, c + 3 * (size_t)second, step, pool, min_height, max_height, max_expansions,
+                                          search_path_cap, r.path.data(), &r.len);
+            ++T.run;
+            T.decided += vigo::paths_search_decided(r.status) ? 1 : 0;
+            return r;
+        };
+        std::vector<Search> s1(n), s2(n);
+        for (int k = 0; k < n; ++k) s1[k] = search(in[2 * k], in[2 * k + 1]);
+        vigo::retry_list(n, in.data(), [&](int k) { return s1[k].status; }, [&](int k) { s2[k] = search(in[2 * k], in[2 * (k + 1) + 1]); });
+        std::vector<int32_t> mseg(2 * (size_t)n + 2), pick((size_t)n + 1);
+        int n_out = 0;
+        T.status = vigo::path_walk(n, in.data(), [&](int k) { return s1[k].status; }, [&](int k) { return s2[k].status; }, mseg.data(), pick.data(), &n_out);
+        T.seg.assign(mseg.begin(), mseg.begin() + 2 * (size_t)n_out);
+        for (int j = 0; j < n_out; ++j) {
+            const int k = pick[j] & ~vigo::kPathsSecond;
+            const bool second = (pick[j] & vigo::kPathsSecond) != 0;
+            const Search& r = second ? s2[k] : s1[k];
+            std::vector<double> p(r.path.begin(), r.path.begin() + 3 * (size_t)r.len);
+            const double* first = c + 3 * (size_t)in[2 * k];
+            const double* last = c + 3 * (size_t)in[2 * (second ? k + 1 : k) + 1];
+            for (int a = 0; a < 3; ++a) p[a] = first[a];
+            p.insert(p.end(), last, last + 3);
+            T.paths.push_back(std::move(p));
+        }
+    });
+    long long total_seg = 0, total_pts = 0;
+    for (const Traj& T : out) {
+        total_seg += (long long)T.seg.size() / 2;
+        for (const auto& p : T.paths) total_pts += (long long)p.size() / 3;
+    }
+    if (total_seg > seg_cap || total_pts > point_cap || total_pts > 0x7fffffffLL) return -1;
+    long long s = 0, q = 0;
+    for (int b = 0; b < B; ++b) {
+        const Traj& T = out[b];
+        out_status[b] = T.status;
+        out_seg_off[b] = (int)s;
+        if (out_counts) { out_counts[2 * b] = T.run; out_counts[2 * b + 1] = T.decided; }
+        for (size_t j = 0; j < T.paths.size(); ++j) {
+            out_seg[2 * s] = T.seg[2 * j];
+            out_seg[2 * s + 1] = T.seg[2 * j + 1];
+            out_path_off[s] = (int)q;
+            std::copy(T.paths[j].begin(), T.paths[j].end(), out_path + 3 * q);
+            q += (long long)T.paths[j].size() / 3;
+            ++s;
+        }
+    }
+    out_seg_off[B] = (int)s;
+    out_path_off[s] = (int)q;
+    return 0;
+}
+
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
 // every run: first ONE run before any setter is touched (slot 0: the untouched default), then `reps` rounds of
 // setDeviceGuides(0), (1), (2) in turn (slots 1, 2, 3), each with setDeviceAstar(astar != 0).  Outputs per slot [4] x ...
@@ -1127,6 +1283,111 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
             g += (long long)pv.size() / 6;
         }
     }
+    return rc;
+}
+
+// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
+// every run, `reps` rounds over the slots of `slots` (bit k: slot k runs) in turn:
+//   slot 0  setDevicePrologue(false), setDeviceAstar(false), setDeviceGuides(1)   the reference point of slot 1
+//   slot 1  setDevicePrologue(true)
+//   slot 2  setDevicePrologue(false), setDeviceAstar(true), setDeviceGuides(1)    the device pieces without the chain
+//   slot 3  every switch off                                                       the host prologue
+// budget: setDeviceAstarBudget.  Outputs per slot [4] x ... of the slot's LAST run: ok[n], solver[n], ncp[n],
+// ctrl[n][ncp_cap][3] (zero padded), n_seg[n] + segs[cap][2] (collisionSeg_, concatenated in planner order),
+// n_path_pts[n] + paths[cap][3] (astarPaths_' points), n_guides[n] + guides[cap][6]; per run prologue_ms[4][reps],
+// chain_ms[4][reps] (devicePrologueTotals' chain time) and total_ms[4][reps]; counts[4][2]: the planners of the slot's
+// last run the device chain decided / that ran the host steps.  Every switch is off on return.  Returns 0, -2 when a
+// buffer is too small, -1 on a bad argument.  Needs a GPU.
+int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
+                                  const double* path_xyz, const double* cfg, int slots, int budget, int reps, int ncp_cap, long long cap,
+                                  int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts, double* paths,
+                                  int* n_guides, double* guides, double* prologue_ms, double* chain_ms, double* total_ms, long long* counts) {
+    using trajPlanner::bsplineTraj;
+    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || (slots & 15) == 0) return -1;
+    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), vox, map->voxels().size());
+    ros::NodeHandle nh;
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    nh.setParam("bspline_traj/max_path_length", 1000.0);
+    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
+    std::vector<nav_msgs::Path> in(n);
+    for (int t = 0; t < n; ++t)
+        for (int i = 0; i < n_pts; ++i) {
+            geometry_msgs::PoseStamped ps;
+            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
+            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
+            in[t].poses.push_back(ps);
+        }
+    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    int rc = 0;
+    bsplineTraj::setDeviceAstarBudget(budget);
+    for (int rep = 0; rep < reps && rc == 0; ++rep)
+        for (int slot = 0; slot < 4 && rc == 0; ++slot) {
+            if (!((slots >> slot) & 1)) continue;
+            std::vector<std::unique_ptr<bsplineTraj>> owners;
+            std::vector<bsplineTraj*> ps;
+            for (int t = 0; t < n; ++t) {
+                owners.emplace_back(new bsplineTraj(nh));
+                owners.back()->setMap(map);
+                owners.back()->updateMaxVel(2.0);
+                owners.back()->updateMaxAcc(3.0);
+                ps.push_back(owners.back().get());
+            }
+            bsplineTraj::updatePathBatch(ps, in, cond);
+            bsplineTraj::setDevicePrologue(slot == 1);
+            bsplineTraj::setDeviceAstar(slot == 2);
+            bsplineTraj::setDeviceGuides(slot == 0 || slot == 2 ? 1 : 0);
+            long long dev0, host0, dev1, host1;
+            double pro0, pro1, ch0, ch1;
+            bsplineTraj::devicePrologueTotals(&dev0, &host0, &ch0);
+            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
+            const auto t0 = std::chrono::steady_clock::now();
+            const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
+            total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
+            bsplineTraj::devicePrologueTotals(&dev1, &host1, &ch1);
+            prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
+            chain_ms[slot * reps + rep] = (ch1 - ch0) * 1e3;
+            counts[2 * slot] = dev1 - dev0;
+            counts[2 * slot + 1] = host1 - host0;
+            bsplineTraj::setDevicePrologue(false);
+            bsplineTraj::setDeviceAstar(false);
+            bsplineTraj::setDeviceGuides(0);
+            if (rep + 1 < reps) continue;
+            long long g = 0, w = 0, sg = 0;
+            for (int t = 0; t < n && rc == 0; ++t) {
+                const size_t o = (size_t)slot * n + t;
+                const Eigen::MatrixXd c = ps[t]->getControlPoints();
+                ok[o] = res2[t] ? 1 : 0;
+                solver[o] = ps[t]->getLastSolverStatus();
+                ncp[o] = (int)c.cols();
+                if (c.cols() > ncp_cap) { rc = -2; break; }
+                for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
+                std::vector<int32_t> off{0};
+                std::vector<double> pv;
+                vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
+                n_guides[o] = (int)(pv.size() / 6);
+                if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
+                std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
+                g += (long long)pv.size() / 6;
+                const auto& cs = ps[t]->getCollisionSeg();
+                n_seg[o] = (int)cs.size();
+                if (sg + (long long)cs.size() > cap) { rc = -2; break; }
+                for (const auto& s : cs) { segs[((size_t)slot * cap + sg) * 2] = s.first; segs[((size_t)slot * cap + sg) * 2 + 1] = s.second; ++sg; }
+                int pts = 0;
+                for (const auto& path : ps[t]->getAstarPaths())
+                    for (const auto& v : path) {
+                        if (w + 1 > cap) { rc = -2; break; }
+                        for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
+                        ++w; ++pts;
+                    }
+                n_path_pts[o] = pts;
+            }
+        }
+    bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
 }
 

@@ -18,6 +18,7 @@ PREC_F32 = 1
 PREC_F64_FAST = 2
 ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_DEFERRED, ASTAR_PATH_TOO_LONG = 0, 1, 2, 3   # vigo_astar_search's out_status
 GUIDE_OK, GUIDE_DEFERRED = 0, 1                                                  # vigo_guide_assign's out_status
+PATHS_OK, PATHS_FAILED, PATHS_DEFERRED = 0, 1, 2                                 # vigo_collision_segs' / vigo_path_search's out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -474,6 +475,46 @@ class Vigo:
             C.c_void_p(pv.data_ptr()), C.c_void_p(unk.data_ptr()) if want_unknown else None, C.c_void_p(status.data_ptr())),
             "vigo_guide_assign")
         return off, pv[:int(pair_cap)], (unk[:int(pair_cap)] if want_unknown else None), status[:B]
+
+    def collision_segs(self, ctrl, not_check_ratio=0.0, seg_cap=None):
+        """vigo_collision_segs: findCollisionSeg for B trajectories (ctrl f64 [B,N,3]) -> (seg_off int32 [B+1], seg int32
+        [seg_cap,2], status int32 [B]: PATHS_OK / PATHS_DEFERRED); seg_cap defaults to B * 48"""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, N = ctrl.shape[0], ctrl.shape[1]
+        cap = B * 48 if seg_cap is None else int(seg_cap)
+        d = self.device
+        seg_off = torch.zeros(B + 1, dtype=torch.int32, device=d)
+        seg = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=d)
+        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
+        self._check(self._lib.vigo_collision_segs(self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), float(not_check_ratio),
+                                                  C.c_void_p(seg_off.data_ptr()), C.c_void_p(seg.data_ptr()), cap,
+                                                  C.c_void_p(status.data_ptr())), "vigo_collision_segs")
+        return seg_off, seg[:cap], status[:B]
+
+    def path_search(self, ctrl, step, pool, min_height, max_height, seg_off=None, seg=None, not_check_ratio=0.0, max_expansions=1 << 20,
+                    search_path_cap=256, seg_cap=None, point_cap=None, want_counts=True):
+        """vigo_path_search: pathSearch for B trajectories (ctrl f64 [B,N,3]) on the scanned segments, or on a supplied list
+        (seg_off int32 [B+1], seg int32 [S,2]) -> (status int32 [B]: PATHS_OK / PATHS_FAILED / PATHS_DEFERRED, seg_off int32
+        [B+1], seg int32 [seg_cap,2], path_off int32 [seg_cap+1], path f64 [point_cap,3], counts int32 [B,2] or None): the
+        seg_off / seg / path_off / path of guide_assign.  seg_cap defaults to B * 48, point_cap to seg_cap * (search_path_cap + 1)"""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, N = ctrl.shape[0], ctrl.shape[1]
+        scap = B * 48 if seg_cap is None else int(seg_cap)
+        pcap = min(scap * (int(search_path_cap) + 1), 1 << 24) if point_cap is None else int(point_cap)
+        d = self.device
+        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
+        o_seg_off = torch.zeros(B + 1, dtype=torch.int32, device=d)
+        o_seg = torch.zeros((max(scap, 1), 2), dtype=torch.int32, device=d)
+        o_path_off = torch.zeros(max(scap, 0) + 1, dtype=torch.int32, device=d)
+        o_path = torch.zeros((max(pcap, 1), 3), dtype=torch.float64, device=d)
+        counts = torch.zeros((max(B, 1), 2), dtype=torch.int32, device=d) if want_counts else None
+        self._check(self._lib.vigo_path_search(
+            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), None if seg_off is None else _ptr(seg_off, torch.int32, "seg_off", d),
+            None if seg is None else _ptr(seg, torch.int32, "seg", d), float(not_check_ratio), float(step),
+            (C.c_int32 * 3)(*[int(v) for v in pool]), float(min_height), float(max_height), int(max_expansions), int(search_path_cap), scap, pcap,
+            C.c_void_p(status.data_ptr()), C.c_void_p(o_seg_off.data_ptr()), C.c_void_p(o_seg.data_ptr()), C.c_void_p(o_path_off.data_ptr()),
+            C.c_void_p(o_path.data_ptr()), C.c_void_p(counts.data_ptr()) if want_counts else None), "vigo_path_search")
+        return status[:B], o_seg_off, o_seg[:scap], o_path_off, o_path[:pcap], (counts[:B] if want_counts else None)
 
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
