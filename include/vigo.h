@@ -617,6 +617,59 @@ int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const in
                      int max_expansions, int search_path_cap, int64_t seg_cap, int64_t point_cap, int32_t* out_status,
                      int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off, double* out_path, int32_t* out_counts);
 
+/* ---- the re-guide step of the rebound loop ------------------------------------------------ */
+
+/*
+ * Replaces: the `if (hasCollision)` block of bsplineTraj::optimizeTrajectory's loop (BT.cpp:656-679) for the
+ * trajectories vigo_rebound_rounds left VIGO_RB_NEEDS_HOST because isReguideRequired (BT.cpp:573-608) said yes: the
+ * re-guide segment list, vigo_path_search on that list, vigo_guide_assign on its output, the new pairs appended to the
+ * trajectory's guide lists, and the state transition — so that the next vigo_rebound_rounds call takes ctrl, the merged
+ * CSR, weights and state as they are.  The rules are csrc/vigo_reguide_core.hpp.
+ * Trajectory b is worked on when state[b].status == VIGO_RB_NEEDS_HOST, gate_static != 0 and fail_count < 4; every
+ * other one is VIGO_REGUIDE_SKIPPED: its pairs are copied unchanged, its state is not touched.  The forced A* of
+ * failCount >= 4 (BT.cpp:640-654) STAYS WITH THE HOST: it precedes isReguideRequired and changes the guides that step
+ * reads.  So does the 30 ms budget of BT.cpp:633.
+ *   ctrl, guide_off / guide_pv / guide_unk   the current control points and guide CSR as vigo_rebound_rounds takes them
+ *                       (all three guide arrays NULL: no guides; guide_unk alone NULL: the flags of the old pairs are
+ *                       queried from the snapshot)
+ *   weights             double[B][4] in/out
+ *   not_check_ratio     as vigo_rebound_rounds; dthresh of isControlPointRequireNewGuide is the handle's parameter
+ *   step .. search_path_cap   as vigo_path_search
+ *   state               vigo_rebound_state_t[B] in/out
+ *   out_guide_off int32[B*N+1], out_guide_pv double[pair_cap][6], out_guide_unk uint8[pair_cap] (may be NULL)
+ *                       the MERGED CSR: per control point the old pairs, then the pairs this step pushed, in push order
+ *   out_path_seg_off int32[B+1], out_path_off int32[seg_cap+1], out_path double[point_cap][3]   (NULL together)
+ *                       astarPaths_ of the step as vigo_path_search returns paths: of every trajectory whose search
+ *                       succeeded (the VIGO_REGUIDE_DONE ones, and those the guide step then deferred or whose
+ *                       merges were cut, which the caller ignores — but seg_cap and point_cap must hold them too:
+ *                       size both for every eligible trajectory, or the call is VIGO_ERR_INVALID_ARG)
+ *   out_status int32[B] VIGO_REGUIDE_DONE          collisionSeg_ (state.seg, n_seg) = the new segments, guides appended
+ *                       VIGO_REGUIDE_SEARCH_FAILED the new segments, guides unchanged, weights[0] *= 2, ++fail_count
+ *                       VIGO_REGUIDE_NOT_REQUIRED  an empty list (a caller-made state): the same transition
+ *                         — these three: gate_dynamic != 0 -> weights[3] *= 2; status = VIGO_RB_ACTIVE; solve_first = 1
+ *                       VIGO_REGUIDE_DEFERRED      the search or the guide step deferred the trajectory, its merges
+ *                                                  left more paths than segments, or there are more than
+ *                                                  VIGO_MAX_COLLISION_SEGS new segments: state untouched (it stays
+ *                                                  NEEDS_HOST), pairs copied unchanged — run the host step
+ *                       VIGO_REGUIDE_SKIPPED       not eligible
+ * A trajectory's result does not depend on its batch.  The call synchronises with the host for the counts
+ * vigo_path_search and vigo_guide_assign read (three and one) and for the merged total (one).
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle or array (the guide inputs, out_guide_unk and the path outputs as
+ * above; every array when B = 0), B < 0, N < 7, negative or too small pair_cap / seg_cap / point_cap, guide offsets that
+ * decrease or start below 0, not_check_ratio outside [0, 1], the checks of vigo_path_search on pool, step,
+ * search_path_cap and max_expansions (VIGO_ERR_UNSUPPORTED for a pool axis above VIGO_ASTAR_MAX_POOL_AXIS or more than
+ * 2^20 trajectories; VIGO_ERR_UNSUPPORTED_N above VIGO_MAX_CTRL_POINTS) — in every such case nothing is written;
+ * VIGO_ERR_NO_GRID before a grid.  B = 0 is a no-op.
+ */
+enum { VIGO_REGUIDE_DONE = 0, VIGO_REGUIDE_SEARCH_FAILED = 1, VIGO_REGUIDE_NOT_REQUIRED = 2, VIGO_REGUIDE_DEFERRED = 3, VIGO_REGUIDE_SKIPPED = 4 };
+int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl,
+                         const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                         double* weights, double not_check_ratio, double step, const int32_t pool[3],
+                         double min_height, double max_height, int max_expansions, int search_path_cap,
+                         vigo_rebound_state_t* state, int64_t pair_cap, int32_t* out_guide_off,
+                         double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap, int64_t point_cap,
+                         int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status);
+
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and
  *   run_first, run_len  int32[K]  segment i's samples are run_first[i] .. run_first[i] + run_len[i] - 1

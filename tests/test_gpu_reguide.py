@@ -1,0 +1,214 @@
+"""-m gpu: vigo_rebound_reguide (csrc/vigo_reguide.hip) against its host twin — csrc/vigo_reguide_core.hpp around the
+path-search and guide twins with vigo_atan2 under the shipped capacities (vigo_host_rebound_reguide_core) — bit for bit
+on the crafted cases and the derived batch of tests/reguide_cases.py: state structs byte for byte, weights, the merged
+CSR (off, pv, unk), out_status, paths.  The output buffers are pre-filled: nothing is written beyond the totals, nothing at
+all on an argument error.  A trajectory's result does not depend on its batch.  The outputs go straight into
+vigo_rebound_rounds."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import reguide_cases as rc
+from gpu_util import to_dev
+from trajectory_planner_amd import _lib
+
+pytestmark = pytest.mark.gpu
+FILL = -7
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return rc.host_lib()
+
+
+@pytest.fixture(scope="module")
+def derived():
+    return rc.derived_batch(128)
+
+
+def _dev(v, c, pair_cap=None, seg_cap=None, point_cap=None, with_guides=True, with_unk=True, want_paths=True):
+    """-> (Result as the twin's, the device tensors (ctrl, off, pv, unk, weights, state))"""
+    d = v.device
+    v.set_grid(to_dev(c.vox, d), c.origin, c.res)
+    ctrl, weights, state = to_dev(c.ctrl, d), to_dev(c.weights, d), to_dev(c.state, d)
+    goff = to_dev(c.goff, d) if with_guides else None
+    gpv = to_dev(np.concatenate([c.gpv.reshape(-1, 6), np.zeros((1, 6))]), d) if with_guides else None
+    gunk = to_dev(np.concatenate([c.gunk(), np.zeros(1, dtype=np.uint8)]), d) if with_guides and with_unk else None
+    pcap = rc.pair_room(c) if pair_cap is None else pair_cap
+    scap = c.B * rc.MAX_SEGS if seg_cap is None else seg_cap
+    ptcap = min(scap * (rc.CAP + 1), 1 << 21) if point_cap is None else point_cap
+    out = v.rebound_reguide(ctrl, goff, gpv, gunk, weights, state, c.res if c.step is None else c.step, c.pool, c.cfg[1], c.cfg[2], pcap,
+                            not_check_ratio=c.ncr, search_path_cap=rc.CAP, seg_cap=scap, point_cap=ptcap, want_paths=want_paths, fill=FILL)
+    torch.cuda.synchronize()
+    status, off, pv, unk, pso, po, pa = [None if t is None else t.cpu().numpy() for t in out]
+    raw = dict(off=off, pv=pv, unk=unk, status=status, path_seg_off=pso, path_off=po, path=pa)
+    G = int(off[-1])
+    S = int(pso[c.B]) if want_paths else 0
+    r = rc.Result(0, status, state.cpu().numpy(), weights.cpu().numpy(), off, pv[:G], unk[:G], pso, po[:S + 1] if want_paths else None,
+                  pa[:po[S]] if want_paths else None, raw)
+    return r, (ctrl, out[1], out[2], out[3], weights, state)
+
+
+def _same(r, t, label):
+    assert np.array_equal(r.status, t.status), (label, r.status, t.status)
+    assert r.state.tobytes() == t.state.tobytes(), label
+    assert np.array_equal(rc.bits(r.weights), rc.bits(t.weights)), label
+    assert np.array_equal(r.off, t.off) and r.pv.shape == t.pv.shape and np.array_equal(rc.bits(r.pv), rc.bits(t.pv)) and np.array_equal(r.unk, t.unk), label
+    assert np.array_equal(r.path_seg_off, t.path_seg_off) and np.array_equal(r.path_off, t.path_off), label
+    assert r.path.shape == t.path.shape and np.array_equal(rc.bits(r.path), rc.bits(t.path)), label
+    # nothing beyond the totals
+    G, S = int(r.off[-1]), int(r.path_seg_off[-1])
+    assert (r.raw["pv"][G:] == float(FILL)).all() and (r.raw["unk"][G:] == (FILL & 0xFF)).all(), label
+    assert (r.raw["path_off"][S + 1:] == FILL).all() and (r.raw["path"][int(r.path_off[S]):] == float(FILL)).all(), label
+
+
+def _equal_twin(v, lib, c, label=None):
+    t = rc.twin(lib, c, 1, rc.shipped())
+    assert t.rc == 0
+    r, dev = _dev(v, c)
+    _same(r, t, label or c.name)
+    return r, t, dev
+
+
+def test_crafted_cases_equal_the_twin(vigo_handle, lib):
+    seen = set()
+    cases = rc.crafted_cases() + [rc.long_path_case()]
+    assert {c.N for c in cases} >= {7, 32, 120}
+    for c in cases:
+        r, t, _ = _equal_twin(vigo_handle, lib, c)
+        if c.expect is not None:
+            assert int(r.status[0]) == c.expect, c.name
+        seen.add(int(r.status[0]))
+    assert seen == {rc.DONE, rc.SEARCH_FAILED, rc.NOT_REQUIRED, rc.DEFERRED, rc.SKIPPED}
+    # no guides at all, and guides without their unknown flags (queried from the snapshot): the same results
+    c = cases[1]
+    r, _ = _dev(vigo_handle, c, with_guides=False)
+    bare = rc.Case(c.name, c.vox, c.origin, c.res, c.cfg, c.ctrl, np.zeros_like(c.goff), c.gpv[:0], c.weights, c.state)
+    _same(r, rc.twin(lib, bare, 1, rc.shipped()), "no guides")
+    r, _ = _dev(vigo_handle, c, with_unk=False)
+    _same(r, rc.twin(lib, c, 1, rc.shipped()), "no unknown flags")
+
+
+def test_derived_batch_equals_the_twin_and_does_not_depend_on_the_batch(vigo_handle, lib, derived):
+    v, c = vigo_handle, derived
+    r, t, _ = _equal_twin(v, lib, c)
+    print(f"\n{c.name}: done / failed / not required / deferred / skipped {[int((r.status == k).sum()) for k in range(5)]}; "
+          f"{int(r.off[-1]) - len(c.gpv)} pairs appended, {len(r.path)} path points: device == twin")
+    assert (r.status == rc.DONE).sum() >= 8 and (r.status == rc.NOT_REQUIRED).sum() >= 8
+    N = c.N
+
+    def same_traj(r1, b1, b):
+        assert r1.status[b1] == r.status[b] and r1.state[b1].tobytes() == r.state[b].tobytes(), b
+        assert np.array_equal(rc.bits(r1.weights[b1]), rc.bits(r.weights[b])), b
+        assert all(x.shape == y.shape and np.array_equal(rc.bits(x), rc.bits(y)) for x, y in zip(r1.pairs_of(b1, N), r.pairs_of(b, N))), b
+        a, e = r1.paths_of(b1), r.paths_of(b)
+        assert len(a) == len(e) and all(np.array_equal(rc.bits(x), rc.bits(y)) for x, y in zip(a, e)), b
+
+    done = [int(b) for b in np.nonzero(r.status == rc.DONE)[0]]
+    picks = sorted({done[0], done[-1], int(np.nonzero(r.status == rc.NOT_REQUIRED)[0][0]), 0, c.B - 1})
+    for b in picks:                                       # alone
+        r1, _ = _dev(v, c.subset([b]))
+        same_traj(r1, 0, b)
+    perm = np.random.default_rng(5).permutation(c.B)      # shuffled
+    r2, _ = _dev(v, c.subset(perm))
+    for k, b in enumerate(perm):
+        same_traj(r2, k, int(b))
+    mixed = c.subset([0, done[0], 1, done[-1], 2])        # between ineligible neighbours
+    mixed.state[[0, 2, 4], rc.S_STATUS] = rc.RB_ACTIVE
+    r3, _ = _dev(v, mixed)
+    assert list(r3.status[[0, 2, 4]]) == [rc.SKIPPED] * 3 and np.array_equal(r3.state[[0, 2, 4]], mixed.state[[0, 2, 4]])
+    same_traj(r3, 1, done[0])
+    same_traj(r3, 3, done[-1])
+
+
+def test_outputs_go_straight_into_rebound_rounds(vigo_handle, lib, derived):
+    v, c = vigo_handle, derived.subset(range(48))
+    d = v.device
+    r, dev = _dev(v, c)
+    ctrl, off, pv, unk, weights, state = dev
+    assert (r.state[:, rc.S_SOLVE_FIRST] == 1).all() and (r.state[:, rc.S_STATUS] == rc.RB_ACTIVE).all()
+    gate_dt = c.res / 1.0 / 2.0
+    v.rebound_rounds(ctrl, off, pv, unk, None, None, weights, gate_dt, state, max_rounds=1)
+    # the same call fed the twin's outputs
+    t = rc.twin(lib, c, 1, rc.shipped())
+    G = int(t.off[-1])
+    ctrl2, w2, st2 = to_dev(c.ctrl, d), to_dev(t.weights, d), to_dev(t.state, d)
+    v.rebound_rounds(ctrl2, to_dev(t.off, d), to_dev(np.concatenate([t.pv, np.zeros((1, 6))]), d), to_dev(np.concatenate([t.unk, np.zeros(1, dtype=np.uint8)]), d),
+                     None, None, w2, gate_dt, st2, max_rounds=1)
+    torch.cuda.synchronize()
+    assert G == int(r.off[-1])
+    a, b = ctrl.cpu().numpy(), ctrl2.cpu().numpy()
+    assert np.array_equal(rc.bits(a), rc.bits(b)) and not np.array_equal(rc.bits(a), rc.bits(c.ctrl))
+    sa, sb = state.cpu().numpy(), st2.cpu().numpy()
+    assert sa.tobytes() == sb.tobytes() and np.array_equal(rc.bits(weights.cpu().numpy()), rc.bits(w2.cpu().numpy()))
+    assert (sa[:, rc.S_ROUNDS] == c.state[:, rc.S_ROUNDS] + 1).all()              # the solve was made, then one gate pass
+    assert ((sa[:, rc.S_SOLVE_FIRST] == 0) | (sa[:, rc.S_STATUS] == rc.RB_ACTIVE)).all() and (sa[:, rc.S_LBFGS] != c.state[:, rc.S_LBFGS]).all()
+
+
+def test_error_contract_writes_nothing(vigo_handle, lib):
+    v = vigo_handle
+    L = _lib.load()
+    d = v.device
+    c = rc.concat([rc.crafted_cases()[1]] * 3, "three copies")
+    good, _ = _dev(v, c)
+    G, S, P = int(good.off[-1]), int(good.path_seg_off[-1]), len(good.path)
+    assert (good.status == rc.DONE).all() and G > len(c.gpv) and S == 3
+    B, N = c.B, c.N
+    ctrl, weights, state = to_dev(c.ctrl, d), to_dev(c.weights, d), to_dev(c.state, d)
+    goff, gpv, gunk = to_dev(c.goff, d), to_dev(c.gpv, d), to_dev(c.gunk(), d)
+    bad_goff = c.goff.copy()
+    bad_goff[N + 16] = bad_goff[N + 15] - 1
+    t_bad = to_dev(bad_goff, d)
+    pair_cap, seg_cap, point_cap = G + 4, 8, 8 * (rc.CAP + 1)
+    o_st = torch.full((B,), 77, dtype=torch.int32, device=d)
+    o_off = torch.full((B * N + 1,), 77, dtype=torch.int32, device=d)
+    o_pv = torch.full((pair_cap, 6), 77.0, dtype=torch.float64, device=d)
+    o_unk = torch.full((pair_cap,), 77, dtype=torch.uint8, device=d)
+    p_so = torch.full((B + 1,), 77, dtype=torch.int32, device=d)
+    p_po = torch.full((seg_cap + 1,), 77, dtype=torch.int32, device=d)
+    p_pa = torch.full((point_cap, 3), 77.0, dtype=torch.float64, device=d)
+    pool = (C.c_int32 * 3)(*c.pool)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+
+    def call(h=None, B_=B, N_=N, ctrl_=ctrl, goff_=goff, gpv_=gpv, gunk_=gunk, w_=weights, ncr=0.0, step=c.res, pool_=pool, max_exp=1 << 20, cap=rc.CAP,
+             state_=state, pair_cap_=pair_cap, off_=o_off, pv_=o_pv, seg_cap_=seg_cap, point_cap_=point_cap, pso_=p_so, po_=p_po, pa_=p_pa, st_=o_st):
+        return L.vigo_rebound_reguide(v._h if h is None else h, B_, N_, p(ctrl_), p(goff_), p(gpv_), p(gunk_), p(w_), ncr, step, pool_, float(c.cfg[1]),
+                                      float(c.cfg[2]), max_exp, cap, p(state_), pair_cap_, p(off_), p(pv_), p(o_unk), seg_cap_, point_cap_, p(pso_),
+                                      p(po_), p(pa_), p(st_))
+
+    def untouched():
+        torch.cuda.synchronize()
+        return (all(bool((t == 77).all()) for t in (o_st, o_off, o_pv, o_unk, p_so, p_po, p_pa)) and
+                np.array_equal(state.cpu().numpy(), c.state) and np.array_equal(weights.cpu().numpy(), c.weights))
+
+    INVALID, NO_GRID, UNSUPPORTED_N, UNSUPPORTED = -1, -5, -4, -6
+    assert L.vigo_rebound_reguide(None, B, N, p(ctrl), p(goff), p(gpv), p(gunk), p(weights), 0.0, c.res, pool, 0.7, 1.3, 100, rc.CAP, p(state), pair_cap,
+                                  p(o_off), p(o_pv), p(o_unk), seg_cap, point_cap, p(p_so), p(p_po), p(p_pa), p(o_st)) == INVALID
+    hostile = [dict(B_=-1), dict(N_=6), dict(ctrl_=None), dict(w_=None), dict(state_=None), dict(off_=None), dict(pv_=None), dict(st_=None),
+               dict(goff_=None), dict(gpv_=None), dict(pso_=None), dict(po_=None), dict(pa_=None), dict(pool_=None), dict(pool_=(C.c_int32 * 3)(2, 16, 8)),
+               dict(ncr=-0.1), dict(ncr=1.5), dict(ncr=float("nan")), dict(step=0.0), dict(step=float("inf")), dict(cap=1), dict(max_exp=-1),
+               dict(pair_cap_=-1), dict(seg_cap_=-1), dict(point_cap_=-1), dict(pair_cap_=G - 1), dict(pair_cap_=0), dict(seg_cap_=S - 1),
+               dict(point_cap_=P - 1), dict(goff_=t_bad)]
+    for kw in hostile:
+        assert call(**kw) == INVALID and untouched(), kw
+    assert call(N_=257) == UNSUPPORTED_N and untouched()
+    assert call(pool_=(C.c_int32 * 3)(16, 2048, 8)) == UNSUPPORTED and untouched()
+    assert call(B_=0, ctrl_=None, w_=None, state_=None, off_=None, pv_=None, st_=None, goff_=None, gpv_=None, gunk_=None) == 0 and untouched()
+    from trajectory_planner_amd.vigo import Vigo
+    fresh = Vigo(0)
+    try:
+        assert call(h=fresh._h) == NO_GRID and untouched()
+    finally:
+        fresh.close()
+    # exactly enough room; and the paths left out
+    assert call(pair_cap_=G, seg_cap_=S, point_cap_=P) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(o_off.cpu().numpy(), good.off) and np.array_equal(rc.bits(o_pv.cpu().numpy()[:G]), rc.bits(good.pv))
+    assert np.array_equal(rc.bits(p_pa.cpu().numpy()[:P]), rc.bits(good.path)) and bool((p_pa[P:] == 77.0).all()) and bool((o_pv[G:] == 77.0).all())
+    state2, w2 = to_dev(c.state, d), to_dev(c.weights, d)
+    o_off.fill_(77)
+    assert call(state_=state2, w_=w2, pso_=None, po_=None, pa_=None, seg_cap_=0, point_cap_=0) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(o_off.cpu().numpy(), good.off) and state2.cpu().numpy().tobytes() == good.state.tobytes()

@@ -92,6 +92,8 @@ PROTOTYPES = {
     "vigo_guide_capacity": (_i, [C.POINTER(C.c_int32)]),
     "vigo_collision_segs": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _i64, _vp]),
     "vigo_path_search": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vigo_rebound_reguide": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+                                  _vp, _vp, _vp, _vp]),
     "vigo_traj_sample_runs": (_i, [_i, _vp, _d, _vp, _vp, _vp]),
     "vigo_poly_sample": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "vigo_accumulated_time": (_d, [_d, _i64]),

@@ -283,6 +283,8 @@ int vigo_destroy(vigo_handle_t h) {
     if (h->scratch) (void)hipFree(h->scratch);
     for (void* w : h->paths_ws)
         if (w) (void)hipFree(w);
+    for (void* w : h->reguide_ws)
+        if (w) (void)hipFree(w);
     if (h->rebound_idx) (void)hipFree(h->rebound_idx);
     if (h->dc_dev) (void)hipFree(h->dc_dev);
     for (int i = 0; i < vigo_context::kDcSlots; ++i)
@@ -831,6 +833,17 @@ int ensure_paths_ws(vigo_handle_t h, int which, size_t bytes) {
     return VIGO_OK;
 }
 
+int ensure_reguide_ws(vigo_handle_t h, int which, size_t bytes) {
+    if (bytes <= h->reguide_ws_bytes[which]) return VIGO_OK;
+    if (h->reguide_ws[which]) (void)hipFree(h->reguide_ws[which]);
+    h->reguide_ws[which] = nullptr;
+    h->reguide_ws_bytes[which] = 0;
+    const size_t want = bytes + bytes / 4 + 4096;
+    VIGO_HIP(h, hipMalloc(&h->reguide_ws[which], want));
+    h->reguide_ws_bytes[which] = want;
+    return VIGO_OK;
+}
+
 // flags and segment counts of the call, read back: result[0] segments, result[1] a bad list
 int path_search_count(vigo_handle_t h, vigo::PathSearchArgs& a, long long result[2], const char* bad_list) {
     if (!a.seg_in)
@@ -839,6 +852,46 @@ int path_search_count(vigo_handle_t h, vigo::PathSearchArgs& a, long long result
     VIGO_HIP(h, hipMemcpyAsync(result, a.result, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     VIGO_HIP(h, hipStreamSynchronize(h->stream));
     if (result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, bad_list);
+    return VIGO_OK;
+}
+
+// the searches of a call whose lists are counted (path_search_count): first choices, the retries the failures ask for,
+// the walk; result[2..4] read back
+int path_search_searches(vigo_handle_t h, vigo::PathSearchArgs& a, vigo::PathSearchWork& w, double step, const int32_t pool[3], double min_height,
+                         double max_height, int max_expansions, long long result[5]) {
+    const int search_path_cap = a.search_path_cap;
+    int rc;
+    const size_t S = (size_t)result[0];
+    if (S > 0) {
+        // [0]: per first-choice search 2 + 2 + 1 + 1 + 1 + 1 int32, 4 x 3 doubles and a path; everything 8-byte aligned
+        const size_t Se = (S + 1) & ~(size_t)1, path_doubles = S * (size_t)search_path_cap * 3;
+        rc = ensure_paths_ws(h, 0, Se * 8 * 4 + S * 12 * 8 + path_doubles * 8);
+        if (rc) return rc;
+        double* d = static_cast<double*>(h->paths_ws[0]);
+        w.start1 = d; w.end1 = d + 3 * S; w.start2 = d + 6 * S; w.end2 = d + 9 * S; w.path1 = d + 12 * S;
+        int32_t* i = reinterpret_cast<int32_t*>(d + 12 * S + path_doubles);
+        w.seg = i; w.mseg = i + 2 * Se; w.pick = i + 4 * Se; w.retry_of = i + 5 * Se; w.status1 = i + 6 * Se; w.len1 = i + 7 * Se;
+        VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, w.seg, w.start1, w.end1));
+        VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)S, w.start1, w.end1, step, pool, min_height, max_height, max_expansions,
+                                                   search_path_cap, w.status1, w.len1, w.path1, nullptr, h->launch));
+        VIGO_HIP(h, (hipError_t)vigo::launch_ps_retry(h->stream, a, w));
+        VIGO_HIP(h, hipMemcpyAsync(result + 2, a.result + 2, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+        VIGO_HIP(h, hipStreamSynchronize(h->stream));
+        const size_t Q2 = (size_t)result[2];
+        if (Q2 > 0) {
+            const size_t Qe = (Q2 + 1) & ~(size_t)1, path2_doubles = Q2 * (size_t)search_path_cap * 3;
+            rc = ensure_paths_ws(h, 1, path2_doubles * 8 + Qe * 2 * 4);
+            if (rc) return rc;
+            w.path2 = static_cast<double*>(h->paths_ws[1]);
+            w.status2 = reinterpret_cast<int32_t*>(w.path2 + path2_doubles);
+            w.len2 = w.status2 + Qe;
+            VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)Q2, w.start2, w.end2, step, pool, min_height, max_height,
+                                                       max_expansions, search_path_cap, w.status2, w.len2, w.path2, nullptr, h->launch));
+        }
+    }
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_decide(h->stream, a, w));
+    VIGO_HIP(h, hipMemcpyAsync(result + 3, a.result + 3, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
     return VIGO_OK;
 }
 
@@ -891,38 +944,9 @@ int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const in
     long long result[5] = {0, 0, 0, 0, 0};
     rc = path_search_count(h, a, result, "vigo_path_search: offsets that decrease or start below 0, or a segment end outside [0, N)");
     if (rc) return rc;
-    const size_t S = (size_t)result[0];
     vigo::PathSearchWork w{};
-    if (S > 0) {
-        // [0]: per first-choice search 2 + 2 + 1 + 1 + 1 + 1 int32, 4 x 3 doubles and a path; everything 8-byte aligned
-        const size_t Se = (S + 1) & ~(size_t)1, path_doubles = S * (size_t)search_path_cap * 3;
-        rc = ensure_paths_ws(h, 0, Se * 8 * 4 + S * 12 * 8 + path_doubles * 8);
-        if (rc) return rc;
-        double* d = static_cast<double*>(h->paths_ws[0]);
-        w.start1 = d; w.end1 = d + 3 * S; w.start2 = d + 6 * S; w.end2 = d + 9 * S; w.path1 = d + 12 * S;
-        int32_t* i = reinterpret_cast<int32_t*>(d + 12 * S + path_doubles);
-        w.seg = i; w.mseg = i + 2 * Se; w.pick = i + 4 * Se; w.retry_of = i + 5 * Se; w.status1 = i + 6 * Se; w.len1 = i + 7 * Se;
-        VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, w.seg, w.start1, w.end1));
-        VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)S, w.start1, w.end1, step, pool, min_height, max_height, max_expansions,
-                                                   search_path_cap, w.status1, w.len1, w.path1, nullptr, h->launch));
-        VIGO_HIP(h, (hipError_t)vigo::launch_ps_retry(h->stream, a, w));
-        VIGO_HIP(h, hipMemcpyAsync(result + 2, a.result + 2, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-        VIGO_HIP(h, hipStreamSynchronize(h->stream));
-        const size_t Q2 = (size_t)result[2];
-        if (Q2 > 0) {
-            const size_t Qe = (Q2 + 1) & ~(size_t)1, path2_doubles = Q2 * (size_t)search_path_cap * 3;
-            rc = ensure_paths_ws(h, 1, path2_doubles * 8 + Qe * 2 * 4);
-            if (rc) return rc;
-            w.path2 = static_cast<double*>(h->paths_ws[1]);
-            w.status2 = reinterpret_cast<int32_t*>(w.path2 + path2_doubles);
-            w.len2 = w.status2 + Qe;
-            VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)Q2, w.start2, w.end2, step, pool, min_height, max_height,
-                                                       max_expansions, search_path_cap, w.status2, w.len2, w.path2, nullptr, h->launch));
-        }
-    }
-    VIGO_HIP(h, (hipError_t)vigo::launch_ps_decide(h->stream, a, w));
-    VIGO_HIP(h, hipMemcpyAsync(result + 3, a.result + 3, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    rc = path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result);
+    if (rc) return rc;
     if (result[3] > (long long)seg_cap || result[3] >= 0x7fffffffLL)
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the segments do not fit seg_cap");
     if (result[4] > (long long)point_cap || result[4] > 0x7fffffffLL)
@@ -930,6 +954,106 @@ int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const in
     a.out_status = out_status; a.out_seg_off = out_seg_off; a.out_seg = out_seg; a.out_path_off = out_path_off; a.out_path = out_path;
     a.out_counts = out_counts;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)result[3], (int)result[4]));
+    return VIGO_OK;
+}
+
+int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* guide_off, const double* guide_pv,
+                         const uint8_t* guide_unk, double* weights, double not_check_ratio, double step, const int32_t pool[3],
+                         double min_height, double max_height, int max_expansions, int search_path_cap, vigo_rebound_state_t* state,
+                         int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap,
+                         int64_t point_cap, int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    const bool no_guides = !guide_off && !guide_pv && !guide_unk;
+    const bool no_paths = !out_path_seg_off && !out_path_off && !out_path;
+    if (B < 0 || N < 7 || pair_cap < 0 || seg_cap < 0 || point_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
+        (!no_guides && (!guide_off || !guide_pv)) || (!no_paths && (!out_path_seg_off || !out_path_off || !out_path)) || !pool || pool[0] < 3 ||
+        pool[1] < 3 || pool[2] < 3 || !(step > 0.0) || !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 ||
+        (B > 0 && (!ctrl || !weights || !state || !out_guide_off || !out_guide_pv || !out_status)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: bad argument");
+    if (N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [7, VIGO_MAX_CTRL_POINTS]");
+    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
+    if (B > (1 << 20)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than 2^20 trajectories in a call");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_rebound_reguide before vigo_set_grid");
+    if (B == 0) return VIGO_OK;
+    constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
+    // [0]: 64 bytes of result words, nine per-trajectory int32 arrays, the lists and the new segments at a fixed stride,
+    // the offsets of this step's pairs; every array 8-byte aligned
+    const size_t words = ((size_t)B + 2) & ~(size_t)1, gwords = ((size_t)B * N + 2) & ~(size_t)1;
+    int rc = ensure_reguide_ws(h, 0, 64 + 4 * (9 * words + 4 * (size_t)kSegs * B + gwords));
+    if (rc) return rc;
+    vigo::ReguideArgs r{};
+    r.B = B; r.N = N; r.ctrl = ctrl; r.guide_off = guide_off; r.guide_pv = guide_pv; r.guide_unk = guide_unk; r.weights = weights; r.state = state;
+    r.dthresh = h->params.dthresh; r.not_check_ratio = not_check_ratio;
+    r.result = static_cast<long long*>(h->reguide_ws[0]);
+    int32_t* w0 = reinterpret_cast<int32_t*>(static_cast<char*>(h->reguide_ws[0]) + 64);
+    r.kind = w0; r.n_list = w0 + words; r.n_new = w0 + 2 * words; r.outcome = w0 + 3 * words;
+    int32_t* ps_status = w0 + 4 * words;
+    int32_t* ps_seg_off = w0 + 5 * words;
+    int32_t* g_status = w0 + 6 * words;
+    int32_t* ps_counts = w0 + 7 * words;
+    r.list = w0 + 9 * words;
+    r.new_seg = r.list + 2 * (size_t)kSegs * B;
+    int32_t* g_off = r.new_seg + 2 * (size_t)kSegs * B;
+    // vigo_path_search's chain on the lists (a trajectory that is not worked on has an empty one)
+    vigo::PathSearchArgs a{};
+    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_in = r.list; a.seg_cnt_in = r.n_list; a.seg_stride_in = kSegs;
+    a.search_path_cap = search_path_cap;
+    rc = path_search_scratch(h, B, N, false, a);
+    if (rc) return rc;
+    VIGO_HIP(h, hipMemsetAsync(r.result, 0, 64, h->stream));
+    VIGO_HIP(h, (hipError_t)vigo::launch_reguide_list(h->stream, h->grid, r));
+    long long bad_off = 0;
+    VIGO_HIP(h, hipMemcpyAsync(&bad_off, r.result, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    long long result[5] = {0, 0, 0, 0, 0};
+    rc = path_search_count(h, a, result, "vigo_rebound_reguide: a re-guide list out of range");
+    if (rc) return rc;
+    if (bad_off != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: guide offsets that decrease or start below 0");
+    vigo::PathSearchWork w{};
+    rc = path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result);
+    if (rc) return rc;
+    const long long total_seg = result[3], total_pts = result[4];
+    if (total_pts > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: more than 2^31 path points");
+    if (!no_paths && (total_seg > (long long)seg_cap || total_pts > (long long)point_cap))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the paths do not fit seg_cap / point_cap");
+    // [1]: the searches' paths, segments and path offsets
+    const size_t seg_words = (2 * (size_t)total_seg + 2) & ~(size_t)1, po_words = ((size_t)total_seg + 2) & ~(size_t)1;
+    rc = ensure_reguide_ws(h, 1, 3 * (size_t)total_pts * 8 + 8 + 4 * (seg_words + po_words));
+    if (rc) return rc;
+    double* ps_path = static_cast<double*>(h->reguide_ws[1]);
+    int32_t* ps_seg = reinterpret_cast<int32_t*>(ps_path + 3 * (size_t)total_pts + 1);
+    int32_t* ps_path_off = ps_seg + seg_words;
+    a.out_status = ps_status; a.out_seg_off = ps_seg_off; a.out_seg = ps_seg; a.out_path_off = ps_path_off; a.out_path = ps_path; a.out_counts = ps_counts;
+    VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)total_seg, (int)total_pts));
+    // vigo_guide_assign's pair on that output: the pairs THIS step appends
+    long long* g_result = r.result + 2;
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, ps_seg_off, ps_seg, ps_path_off, 0x7fffffffLL, g_off, g_status, g_result));
+    long long g_host[2] = {0, 0};
+    VIGO_HIP(h, hipMemcpyAsync(g_host, g_result, sizeof(g_host), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    if (g_host[1] != 0 || g_host[0] > 0x7fffffffLL) return fail(h, VIGO_ERR_HIP, "vigo_rebound_reguide: the path search's output is no input of the guide step");
+    // [2]: those pairs and their unknown flags
+    const size_t P = (size_t)g_host[0];
+    rc = ensure_reguide_ws(h, 2, P * 48 + P + 8);
+    if (rc) return rc;
+    double* g_pv = static_cast<double*>(h->reguide_ws[2]);
+    uint8_t* g_unk = reinterpret_cast<uint8_t*>(g_pv + 6 * P);
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, ps_seg_off, ps_seg, ps_path_off, ps_path, g_off, g_pv, g_unk, g_status));
+    r.ps_status = ps_status; r.ps_seg_off = ps_seg_off; r.ps_counts = ps_counts; r.g_status = g_status; r.g_off = g_off; r.g_pv = g_pv; r.g_unk = g_unk;
+    r.pair_cap = (long long)pair_cap;
+    r.out_guide_off = out_guide_off; r.out_guide_pv = out_guide_pv; r.out_guide_unk = out_guide_unk; r.out_status = out_status;
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge_offsets(h->stream, r));
+    long long merged = 0;
+    VIGO_HIP(h, hipMemcpyAsync(&merged, r.result + 1, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    if (merged > (long long)pair_cap || merged > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the merged pairs do not fit pair_cap");
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge(h->stream, h->grid, r));
+    if (!no_paths) {
+        VIGO_HIP(h, hipMemcpyAsync(out_path_seg_off, ps_seg_off, ((size_t)B + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
+        VIGO_HIP(h, hipMemcpyAsync(out_path_off, ps_path_off, ((size_t)total_seg + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (total_pts > 0) VIGO_HIP(h, hipMemcpyAsync(out_path, ps_path, (size_t)total_pts * 24, hipMemcpyDeviceToDevice, h->stream));
+    }
+    VIGO_HIP(h, (hipError_t)vigo::launch_reguide_commit(h->stream, r));
     return VIGO_OK;
 }
 

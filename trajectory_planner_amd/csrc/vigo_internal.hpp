@@ -216,6 +216,8 @@ struct PathSearchArgs {
     double not_check_ratio;
     const int32_t* seg_off_in;   // the supplied list, or NULL: the scan over pt / ln
     const int32_t* seg_in;
+    const int32_t* seg_cnt_in;   // not NULL: trajectory b's list is seg_cnt_in[b] segments at seg_in[b * seg_stride_in]
+    int seg_stride_in;           // (seg_off_in is not read; B * seg_stride_in fits an int)
     const uint8_t* pt;           // [B][N] vigo_ctrl_occupancy's flags
     const uint8_t* ln;
     int search_path_cap;
@@ -258,6 +260,42 @@ int launch_ps_segs_out(hipStream_t s, const PathSearchArgs& a);
 int launch_ps_retry(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w);
 int launch_ps_decide(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w);
 int launch_ps_write(hipStream_t s, const PathSearchArgs& a, const PathSearchWork& w, int total_seg, int total_pts);
+
+// the re-guide step of the rebound loop (vigo_reguide.hip); the kernels and what vigo_api.cpp reads back between them
+// are listed in that file's header.  Everything but the out_* members and the caller's inputs is device scratch.
+struct ReguideArgs {
+    int B, N;
+    const double* ctrl;
+    const int32_t* guide_off;    // the current CSR, or NULL: no guides
+    const double* guide_pv;
+    const uint8_t* guide_unk;    // may be NULL: the merged flags of the old pairs are then queried
+    double* weights;
+    vigo_rebound_state_t* state;
+    double dthresh, not_check_ratio;
+    long long* result;           // [0] != 0: guide_off decreases or starts below 0, [1] the merged pairs
+    int32_t* kind;               // [B]  k_reguide_list: kReguideSkipped / kReguideDeferred / -1 (eligible, rules run)
+    int32_t* n_list;             // [B]  segments of the re-guide list
+    int32_t* list;               // [B][VIGO_MAX_COLLISION_SEGS][2]
+    int32_t* n_new;              // [B]  the new collisionSeg_
+    int32_t* new_seg;            // [B][VIGO_MAX_COLLISION_SEGS][2]
+    const int32_t* ps_status;    // [B]  vigo_path_search's outputs on the list
+    const int32_t* ps_seg_off;   // [B+1]
+    const int32_t* ps_counts;    // [B][2]
+    const int32_t* g_status;     // [B]  vigo_guide_assign's outputs on those
+    const int32_t* g_off;        // [B*N+1]
+    const double* g_pv;
+    const uint8_t* g_unk;
+    int32_t* outcome;            // [B]  k_guide_merge_offsets: kReguide*
+    long long pair_cap;
+    int32_t* out_guide_off;
+    double* out_guide_pv;
+    uint8_t* out_guide_unk;
+    int32_t* out_status;
+};
+int launch_reguide_list(hipStream_t s, const GridView& g, const ReguideArgs& a);
+int launch_guide_merge_offsets(hipStream_t s, const ReguideArgs& a);
+int launch_guide_merge(hipStream_t s, const GridView& g, const ReguideArgs& a);
+int launch_reguide_commit(hipStream_t s, const ReguideArgs& a);
 
 }  // namespace vigo
 
@@ -305,4 +343,7 @@ struct vigo_context {
     // vigo_path_search: the buffers sized by the call's first-choice ([0]) and second-choice ([1]) searches
     void* paths_ws[2] = {nullptr, nullptr};
     size_t paths_ws_bytes[2] = {0, 0};
+    // vigo_rebound_reguide: [0] per trajectory and control point, [1] the searches' segments and paths, [2] the new pairs
+    void* reguide_ws[3] = {nullptr, nullptr, nullptr};
+    size_t reguide_ws_bytes[3] = {0, 0, 0};
 };

@@ -41,6 +41,12 @@ __device__ __forceinline__ long long scan1024(long long* s, long long v, long lo
     return s[tid];
 }
 
+// the supplied list of trajectory b: CSR (seg_off_in), or seg_cnt_in[b] segments at a fixed stride (vigo_reguide.hip)
+__device__ __forceinline__ int ps_list_first(const PathSearchArgs& A, int b) { return A.seg_cnt_in ? b * A.seg_stride_in : A.seg_off_in[b]; }
+__device__ __forceinline__ int ps_list_end(const PathSearchArgs& A, int b) {
+    return A.seg_cnt_in ? b * A.seg_stride_in + A.seg_cnt_in[b] : A.seg_off_in[b + 1];
+}
+
 struct FlagOcc {
     const uint8_t* f;
     __device__ bool operator()(int i) const { return f[i] != 0; }
@@ -59,7 +65,7 @@ __global__ void __launch_bounds__(1024) k_ps_count(PathSearchArgs A) {
     for (int b = lo; b < hi && !bad; ++b) {
         int nb = 0;
         if (A.seg_in) {
-            const int s0 = A.seg_off_in[b], s1 = A.seg_off_in[b + 1];
+            const int s0 = ps_list_first(A, b), s1 = ps_list_end(A, b);
             if (s0 < 0 || s1 < s0) { bad = true; break; }
             nb = s1 - s0;
             if (nb <= kPathsMaxSegs)
@@ -96,7 +102,7 @@ __global__ void __launch_bounds__(256) k_ps_fill(PathSearchArgs A, int32_t* dst_
     const int q0 = A.in_off[b], n = A.n_in[b];
     int32_t* seg = dst_seg + 2 * (size_t)q0;
     if (A.seg_in) {
-        const int32_t* src = A.seg_in + 2 * (size_t)A.seg_off_in[b];
+        const int32_t* src = A.seg_in + 2 * (size_t)ps_list_first(A, b);
         for (int k = 0; k < 2 * n; ++k) seg[k] = src[k];
     } else if (n > 0) {
         collision_segs(A.N, A.not_check_ratio, FlagOcc{A.pt + (size_t)b * A.N}, FlagOcc{A.ln + (size_t)b * A.N}, n, seg);

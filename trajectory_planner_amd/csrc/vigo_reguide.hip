@@ -1,0 +1,198 @@
+// vigo_reguide.hip — vigo_rebound_reguide: the re-guide step of the rebound loop (the `if (hasCollision)` block of
+// BT.cpp:656-679; host/src/bsplineTraj.cpp: reboundStep) for the trajectories vigo_rebound_rounds left VIGO_RB_NEEDS_HOST,
+// the rules of vigo_reguide_core.hpp around the path search of vigo_pathsearch.hip and the guide step of vigo_guides.hip
+// (both unchanged: the re-guide list is a caller-supplied list to the first, its output the input of the second).
+//
+// The kernels of one call, in stream order (vigo_api.cpp reads back the words marked <-):
+//   k_reguide_list          a wave per trajectory   eligibility; the map queries of findCollisionSeg one control point per
+//                                                   lane; lane 0 walks reguide_rules over the flags in LDS: the new
+//                                                   segments and the re-guide list, at a fixed stride  <- bad guide_off
+//   k_ps_* / k_astar        vigo_path_search's chain on the lists                      <- its three counts
+//   k_guide_offsets / k_guide_assign   vigo_guide_assign's pair on its output          <- the new pairs
+//   k_guide_merge_offsets   one workgroup           the outcome of every trajectory (reguide_outcome), its pairs per
+//                                                   control point (old + appended), scanned; the offsets are written
+//                                                   only when the total fits pair_cap            <- the merged pairs
+//   k_guide_merge           a wave per trajectory   the merged CSR, a pair per lane: old pairs, then this step's
+//   k_reguide_commit        a thread per trajectory reguide_commit: state, weights, out_status
+// Nothing of the caller's is written before k_guide_merge_offsets has passed.  Plain vector stores, no atomics.
+#include "vigo_reguide_core.hpp"
+#include "vigo_guide_core.hpp"
+#include "vigo_grid.hpp"
+
+namespace vigo {
+namespace {
+
+constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
+static_assert(kSegs == kPathsMaxSegs, "the state holds what the path search takes");
+
+struct FlagAt {
+    const uint8_t* f;
+    __device__ bool operator()(int i) const { return f[i] != 0; }
+};
+
+__global__ void __launch_bounds__(64) k_reguide_list(GridView g, ReguideArgs A) {
+    __shared__ uint8_t s_pt[VIGO_MAX_CTRL_POINTS], s_ln[VIGO_MAX_CTRL_POINTS];
+    const int b = blockIdx.x, lane = threadIdx.x, N = A.N;
+    const int32_t* off = A.guide_off ? A.guide_off + (size_t)b * N : nullptr;
+    if (off) {                                            // (every trajectory's offsets: the merge copies them all)
+        bool bad = b == 0 && lane == 0 && off[0] < 0;
+        for (int i = lane; i < N; i += 64) bad = bad || off[i + 1] < off[i];
+        if (bad) A.result[0] = 1;                         // (the same value from whoever sees one)
+    }
+    const vigo_rebound_state_t& st = A.state[b];
+    if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) {
+        if (lane == 0) { A.kind[b] = kReguideSkipped; A.n_list[b] = 0; A.n_new[b] = 0; }
+        return;
+    }
+    const double* c = A.ctrl + (size_t)b * N * 3;
+    auto occ = [&g](double x, double y, double z) { return grid_plane_pos(g, 0, x, y, z) != 0u; };
+    for (int i = lane; i < N; i += 64) {
+        s_pt[i] = occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]) ? 1 : 0;
+        s_ln[i] = (i > 0 && line_occupied(occ, g.res, c + 3 * (i - 1), c + 3 * i)) ? 1 : 0;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    int32_t seg[2 * kSegs];
+    uint8_t listed[kSegs];
+    int n_list = 0;
+    const int n_prev = min(max(st.n_seg, 0), kSegs);      // (device data: never index beyond the array)
+    const double dthresh = A.dthresh;
+    const double* pv = A.guide_pv;
+    auto need_guide = [&](int i) {
+        if (!off || !pv) return true;
+        const int j0 = off[i], j1 = off[i + 1];
+        if (j0 < 0) return true;                          // (a bad list: the call is refused, read nothing)
+        for (int j = j0; j < j1; ++j)
+            if (!reguide_guide_far(dthresh, c + 3 * i, pv + 6 * (size_t)j)) return false;
+        return true;
+    };
+    const int n = reguide_rules(N, A.not_check_ratio, FlagAt{s_pt}, FlagAt{s_ln}, n_prev, st.seg, need_guide, kSegs, seg, listed, &n_list);
+    if (n > kSegs) {
+        A.kind[b] = kReguideDeferred; A.n_list[b] = 0; A.n_new[b] = 0;
+        return;
+    }
+    int32_t* dst_new = A.new_seg + 2 * (size_t)kSegs * b;
+    int32_t* dst_list = A.list + 2 * (size_t)kSegs * b;
+    int m = 0;
+    for (int k = 0; k < n; ++k) {
+        dst_new[2 * k] = seg[2 * k];
+        dst_new[2 * k + 1] = seg[2 * k + 1];
+        if (listed[k]) {
+            dst_list[2 * m] = seg[2 * k];
+            dst_list[2 * m + 1] = seg[2 * k + 1];
+            ++m;
+        }
+    }
+    A.kind[b] = -1;
+    A.n_list[b] = m;
+    A.n_new[b] = n;
+}
+
+__global__ void __launch_bounds__(1024) k_guide_merge_offsets(ReguideArgs A) {
+    __shared__ long long s_cnt[1024];
+    const int tid = threadIdx.x, N = A.N;
+    const int per = (A.B + 1023) / 1024;
+    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    auto old_pairs = [&](size_t at) { return A.guide_off ? A.guide_off[at + 1] - A.guide_off[at] : 0; };
+    // pass 1: the outcomes and the pairs of my trajectories
+    long long n = 0;
+    for (int b = lo; b < hi; ++b) {
+        const int kind = A.kind[b], ps = A.ps_status[b];
+        const bool cut = ps == kPathsOk && paths_cut_by_bound(A.ps_counts[2 * b], A.ps_seg_off[b + 1] - A.ps_seg_off[b]);
+        const int outcome = reguide_outcome(kind != kReguideSkipped, kind == kReguideDeferred, A.n_list[b], ps, cut, A.g_status[b] == kGuideDeferred);
+        A.outcome[b] = outcome;
+        if (A.guide_off) n += (long long)A.guide_off[(size_t)(b + 1) * N] - A.guide_off[(size_t)b * N];
+        if (outcome == kReguideDone) n += (long long)A.g_off[(size_t)(b + 1) * N] - A.g_off[(size_t)b * N];
+    }
+    s_cnt[tid] = n;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {            // inclusive scan
+        const long long v = tid >= off ? s_cnt[tid - off] : 0;
+        __syncthreads();
+        s_cnt[tid] += v;
+        __syncthreads();
+    }
+    const long long total = s_cnt[1023];
+    if (tid == 0) A.result[1] = total;
+    if (total > A.pair_cap || total > 0x7fffffffLL) return;                   // nothing else is written
+    // pass 2: the merged offsets of my trajectories
+    long long at = s_cnt[tid] - n;
+    for (int b = lo; b < hi; ++b) {
+        const bool done = A.outcome[b] == kReguideDone;
+        for (int i = 0; i < N; ++i) {
+            const size_t q = (size_t)b * N + i;
+            A.out_guide_off[q] = (int32_t)at;
+            at += old_pairs(q) + (done ? A.g_off[q + 1] - A.g_off[q] : 0);
+        }
+    }
+    if (tid == 1023) A.out_guide_off[(size_t)A.B * N] = (int32_t)total;
+}
+
+__global__ void __launch_bounds__(64) k_guide_merge(GridView g, ReguideArgs A) {
+    const int b = blockIdx.x, lane = threadIdx.x, N = A.N;
+    const int32_t* out_off = A.out_guide_off + (size_t)b * N;
+    const bool done = A.outcome[b] == kReguideDone;       // (one value for all lanes; the offsets hold new pairs only then)
+    for (int q = out_off[0] + lane; q < out_off[N]; q += 64) {
+        int lo = 0, hi = N - 1;                           // the control point of slot q: the last i with out_off[i] <= q
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (out_off[mid] <= q) lo = mid; else hi = mid - 1;
+        }
+        const size_t at = (size_t)b * N + lo;
+        const int j = q - out_off[lo];
+        const int n_old = A.guide_off ? A.guide_off[at + 1] - A.guide_off[at] : 0;
+        const double* src;
+        unsigned unk = 0;
+        if (j < n_old) {
+            const size_t s = (size_t)A.guide_off[at] + j;
+            src = A.guide_pv + 6 * s;
+            if (A.out_guide_unk) unk = A.guide_unk ? A.guide_unk[s] : grid_plane_pos(g, 1, src[0], src[1], src[2]);
+        } else {
+            if (!done) continue;                          // (cannot be: the slot would not exist)
+            const size_t s = (size_t)A.g_off[at] + (j - n_old);
+            src = A.g_pv + 6 * s;
+            if (A.out_guide_unk) unk = A.g_unk[s];
+        }
+        double* dst = A.out_guide_pv + 6 * (size_t)q;
+        for (int a = 0; a < 6; ++a) dst[a] = src[a];
+        if (A.out_guide_unk) A.out_guide_unk[q] = (uint8_t)unk;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_reguide_commit(ReguideArgs A) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= A.B) return;
+    const int outcome = A.outcome[b];
+    A.out_status[b] = outcome;
+    if (outcome == kReguideDeferred || outcome == kReguideSkipped) return;
+    vigo_rebound_state_t& st = A.state[b];
+    const int n = A.n_new[b];                             // <= kSegs (k_reguide_list)
+    const int32_t* src = A.new_seg + 2 * (size_t)kSegs * b;
+    st.n_seg = n;                                         // collisionSeg_ = the new segments (BT.cpp:575)
+    for (int k = 0; k < 2 * n; ++k) st.seg[k] = src[k];
+    reguide_commit(outcome, st.gate_dynamic != 0, A.weights + 4 * (size_t)b, &st.fail_count, &st.status, &st.solve_first);
+}
+
+}  // namespace
+
+int launch_reguide_list(hipStream_t s, const GridView& g, const ReguideArgs& a) {
+    hipLaunchKernelGGL(k_reguide_list, dim3(a.B), dim3(64), 0, s, g, a);
+    return (int)hipGetLastError();
+}
+
+int launch_guide_merge_offsets(hipStream_t s, const ReguideArgs& a) {
+    hipLaunchKernelGGL(k_guide_merge_offsets, dim3(1), dim3(1024), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+int launch_guide_merge(hipStream_t s, const GridView& g, const ReguideArgs& a) {
+    hipLaunchKernelGGL(k_guide_merge, dim3(a.B), dim3(64), 0, s, g, a);
+    return (int)hipGetLastError();
+}
+
+int launch_reguide_commit(hipStream_t s, const ReguideArgs& a) {
+    hipLaunchKernelGGL(k_reguide_commit, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace vigo

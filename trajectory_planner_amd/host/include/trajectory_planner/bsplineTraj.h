@@ -117,7 +117,7 @@ public:
     /* The A* searches of makePlanBatch's prologue as ONE vigo_astar_search launch per device group (plus one for the
      * merged retries of the failures) instead of host searches on the worker threads.  Default false.  Same plans: a
      * search the device defers (its budgets, setDeviceAstarBudget), and every search of a planner whose handle has no
-     * map snapshot, is run by the host A*.  The A* of a re-guide inside the rebound loop stays on the host. */
+     * map snapshot, is run by the host A*.  The A* of a re-guide inside the rebound loop is setDeviceReguide's. */
     static void setDeviceAstar(bool on);
     static bool deviceAstar();
     /* max_expansions of those launches (pops per search before the device hands the search back); default 16384 */
@@ -135,7 +135,7 @@ public:
      * csrc/vigo_guide_core.hpp with its portable atan2, the kernel's bit-exact twin — so a planner's guides do not depend
      * on which side produced them.  2: every planner runs that twin on the workers (the emulation of 1).  Settings 1
      * and 2 differ from 0 by the last places of atan2 (vigo.h: vigo_guide_assign).  The re-guide step inside the
-     * rebound loop stays on the host step whatever the setting. */
+     * rebound loop does not consult this setting: it is setDeviceReguide's. */
     static void setDeviceGuides(int mode);
     static int deviceGuides();
     /* Process-wide running totals: the prologue trajectories whose guides the device produced / the workers' twin produced */
@@ -151,13 +151,39 @@ public:
      * after replaying host steps 1-2 on the workers: vigo_path_search returns nothing for it, and the host steps leave
      * the scanned segments and the paths found before the failure in getCollisionSeg() / getAstarPaths(), so these
      * read the same under every setting.  Searches run under setDeviceAstarBudget.  The re-guide step inside the
-     * rebound loop (findCollisionSeg, A*, guide assignment on the current control points) stays on the host. */
+     * rebound loop (findCollisionSeg, A*, guide assignment on the current control points) is not part of the chain:
+     * setDeviceReguide puts it on the device. */
     static void setDevicePrologue(bool on);
     static bool devicePrologue();
     /* Process-wide running totals: the prologue planners whose outcome the device chain decided (prepared, or failed:
      * those replay host steps 1-2 for their lists and still count here) / those the host steps decided (deferred, lists
      * cut by the bound, no device), and the wall time of the chains (upload to installed results) in seconds */
     static void devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds);
+    /* The re-guide step of the device-resident rebound loop (the `if (hasCollision)` block of BT.cpp:656-679) for the
+     * planners vigo_rebound_rounds hands back with a static collision and failCount < 4.  0 (default): reboundStep on
+     * the workers, as it always was.  1: ONE vigo_rebound_reguide call per device group on the group's staged batch;
+     * collisionSeg_, the appended guide pairs, astarPaths_, the weights, failCount and needOptimize are installed from
+     * its outputs (through the host: the batch is packed again for the next vigo_rebound_rounds call).  A planner the
+     * call defers, and every planner of a group without device or snapshot, runs the same step on the workers with the
+     * guide step's bit-exact twin (csrc/vigo_guide_core.hpp with its portable atan2), so a plan does not depend on
+     * which side ran the step.  2: every such planner runs that twin on the workers (the emulation of 1).  Settings 1
+     * and 2 differ from 0 by the last places of atan2.  The forced A* of failCount >= 4 (BT.cpp:640-654), a planner
+     * with a dynamic collision only, and the 30 ms budget's exit stay with reboundStep on the host under every
+     * setting.  Searches run under setDeviceAstarBudget.  Only consulted when deviceResidentRebound(). */
+    static void setDeviceReguide(int mode);
+    static int deviceReguide();
+    /* Process-wide running totals: the re-guide steps vigo_rebound_reguide decided / the workers' twin ran */
+    static void deviceReguideTotals(long long* deviceDecided, long long* hostRun);
+    /* added (tests, cabi_host.cpp: vigo_host_plan_batch_reguide): the inputs of every step the workers' twin runs are
+     * appended to *log (NULL: off, the default), so the same steps can be put to the kernels' host twin afterwards */
+    struct ReguideStepRecord {
+        int N;
+        std::vector<double> ctrl, gpv;
+        std::vector<int32_t> goff, seg;          /* seg: collisionSeg_ as (first, second) pairs */
+        int failCount, gateDynamic;
+        double weights[4];
+    };
+    static void setReguideStepLog(std::vector<ReguideStepRecord>* log);
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
@@ -197,6 +223,13 @@ public:
     /* added (workload tools, cabi_host.cpp): take these control points as the planner's current ones with empty guide
      * lists — the state updatePath() leaves (BT.cpp:315-322) — so the host steps of the rebound loop can be replayed on them */
     void setControlPoints(const Eigen::MatrixXd& controlPoints) { installControlPoints(controlPoints, {}); }
+    /* added (tests, cabi_host.cpp: vigo_host_reguide_facade): the state the rebound loop carries between two rounds —
+     * collisionSeg_, the guide pairs per control point (after setControlPoints), the two weights the loop doubles — and
+     * ONE pass of the loop body (reboundStep) on it with the given gate results; failCount in/out */
+    void setLoopState(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& guidePoints,
+                      const std::vector<std::vector<Eigen::Vector3d>>& guideDirections, double weightDistance, double weightDynamicObstacle);
+    void runLoopBody(bool hasCollision, bool hasDynamicCollision, int& failCount, bool& needOptimize, bool& done);
+    void getLoopWeights(double& weightDistance, double& weightDynamicObstacle) const { weightDistance = weightDistance_; weightDynamicObstacle = weightDynamicObstacle_; }
     bool isCurrTrajValid();
     bool isCurrTrajValid(Eigen::Vector3d& firstCollisionPos);
     int getLastSolverStatus() const { return lastStatus_; }
@@ -256,6 +289,12 @@ private:
     /* step 3 of the prologue under setDeviceGuides(1 | 2) for the planners with found[i] */
     static void assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found);
     void assignGuidesCore();
+    void assignGuidesCoreOn(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& paths);
+    /* setDeviceReguide(1): the eligible planners of `active` through vigo_rebound_reguide; the ones it decided get
+     * devStatus VIGO_RB_ACTIVE.  (2, and what 1 left: reguideStepCore on the workers) */
+    static void reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& devOk);
+    static bool reguideEligible(const Rebound& r);
+    void reguideStepCore(Rebound& r);
     /* steps 1-3 under setDevicePrologue(true); outcome[i]: 1 prepared, 2 failed (A*), 0 not a planner of the batch */
     static void prologueOnDevice(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<uint8_t>& outcome);
     void packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const;

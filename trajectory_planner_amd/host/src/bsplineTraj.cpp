@@ -994,6 +994,27 @@ void bsplineTraj::reboundStep(Rebound& r, bool hasCollision, bool hasDynamicColl
     r.needOptimize = true;
 }
 
+void bsplineTraj::setLoopState(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& guidePoints,
+                               const std::vector<std::vector<Eigen::Vector3d>>& guideDirections, double weightDistance, double weightDynamicObstacle) {
+    this->collisionSeg_ = collisionSeg;
+    for (size_t i = 0; i < guidePoints.size() && i < this->optData_.guidePoints.size(); ++i) {
+        this->optData_.guidePoints[i] = guidePoints[i];
+        this->optData_.guideDirections[i] = guideDirections[i];
+    }
+    this->weightDistance_ = weightDistance;
+    this->weightDynamicObstacle_ = weightDynamicObstacle;
+}
+
+void bsplineTraj::runLoopBody(bool hasCollision, bool hasDynamicCollision, int& failCount, bool& needOptimize, bool& done) {
+    Rebound r;
+    reboundBegin(r);
+    r.failCount = failCount;
+    reboundStep(r, hasCollision, hasDynamicCollision, false);
+    failCount = r.failCount;
+    needOptimize = r.needOptimize;
+    done = r.done;
+}
+
 // BT.cpp:611-685 for one planner
 bool bsplineTraj::optimizeTrajectory() {
     std::vector<bsplineTraj*> one{this};
@@ -1529,24 +1550,32 @@ void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun
     if (hostRun) *hostRun = g_guideHostRun.load();
 }
 
-// the planner's segments and paths as vigo_guide_assign takes them: the first min(collisionSeg.size(), paths.size()) of
-// both (BT.cpp:523), paths as CSR
-void bsplineTraj::packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const {
-    const size_t n = std::min(this->collisionSeg_.size(), this->astarPaths_.size());
+// segments and paths as vigo_guide_assign takes them: the first min(collisionSeg.size(), paths.size()) of both
+// (BT.cpp:523), paths as CSR
+static void packGuideLists(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& paths,
+                           std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) {
+    const size_t n = std::min(collisionSeg.size(), paths.size());
     for (size_t k = 0; k < n; ++k) {
-        seg.push_back(this->collisionSeg_[k].first);
-        seg.push_back(this->collisionSeg_[k].second);
-        for (const Eigen::Vector3d& v : this->astarPaths_[k])
+        seg.push_back(collisionSeg[k].first);
+        seg.push_back(collisionSeg[k].second);
+        for (const Eigen::Vector3d& v : paths[k])
             for (int a = 0; a < 3; ++a) path.push_back(v(a));
         pathOff.push_back((int32_t)(path.size() / 3));
     }
 }
 
+// the planner's own
+void bsplineTraj::packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const {
+    packGuideLists(this->collisionSeg_, this->astarPaths_, seg, pathOff, path);
+}
+
 // assignGuidePointsSemiCircle by the device's code (csrc/vigo_guide_core.hpp with vigo_atan2) on the planner's own map
-void bsplineTraj::assignGuidesCore() {
+void bsplineTraj::assignGuidesCore() { this->assignGuidesCoreOn(this->collisionSeg_, this->astarPaths_); }
+
+void bsplineTraj::assignGuidesCoreOn(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& paths) {
     std::vector<int32_t> seg, pathOff{0};
     std::vector<double> path;
-    this->packGuideInput(seg, pathOff, path);
+    packGuideLists(collisionSeg, paths, seg, pathOff, path);
     const int N = this->optData_.controlPoints.cols();
     std::vector<double> ctrl((size_t)N * 3);
     for (int i = 0; i < N; ++i)
@@ -1662,9 +1691,187 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
     });
 }
 
+namespace {
+std::atomic<int> g_deviceReguide{0};
+std::atomic<long long> g_reguideDeviceDecided{0}, g_reguideHostRun{0};
+std::mutex g_reguideLogMutex;
+std::vector<bsplineTraj::ReguideStepRecord>* g_reguideLog = nullptr;
+}  // namespace
+void bsplineTraj::setDeviceReguide(int mode) { g_deviceReguide.store(mode == 1 || mode == 2 ? mode : 0); }
+int bsplineTraj::deviceReguide() { return g_deviceReguide.load(); }
+void bsplineTraj::deviceReguideTotals(long long* deviceDecided, long long* hostRun) {
+    if (deviceDecided) *deviceDecided = g_reguideDeviceDecided.load();
+    if (hostRun) *hostRun = g_reguideHostRun.load();
+}
+void bsplineTraj::setReguideStepLog(std::vector<ReguideStepRecord>* log) {
+    std::lock_guard<std::mutex> lock(g_reguideLogMutex);
+    g_reguideLog = log;
+}
+
+// the planners vigo_rebound_reguide works on (vigo.h): what is left of the NEEDS_HOST ones is the forced A* of
+// failCount >= 4 and the planners with a dynamic collision only
+bool bsplineTraj::reguideEligible(const Rebound& r) { return r.devStatus == VIGO_RB_NEEDS_HOST && r.gateStatic && r.failCount < 4; }
+
+// reboundStep for such a planner with the guide step's twin in place of assignGuidePointsSemiCircle: what
+// vigo_rebound_reguide computes (csrc/vigo_reguide_core.hpp restates isReguideRequired, vigo_path_search the host's
+// pathSearch), without its capacities
+void bsplineTraj::reguideStepCore(Rebound& r) {
+    if (g_reguideLog) {
+        ReguideStepRecord rec;
+        rec.N = this->optData_.controlPoints.cols();
+        rec.ctrl.assign(this->optData_.controlPoints.data(), this->optData_.controlPoints.data() + 3 * (size_t)rec.N);
+        rec.goff.assign(1, 0);
+        vigo_host::appendGuides(this->optData_, rec.N, rec.goff, rec.gpv);
+        for (const auto& s : this->collisionSeg_) { rec.seg.push_back(s.first); rec.seg.push_back(s.second); }
+        rec.failCount = r.failCount;
+        rec.gateDynamic = r.gateDynamic ? 1 : 0;
+        const double w[4] = {this->weightDistance_, this->weightSmoothness_, this->weightFeasibility_, this->weightDynamicObstacle_};
+        std::copy(w, w + 4, rec.weights);
+        std::lock_guard<std::mutex> lock(g_reguideLogMutex);
+        if (g_reguideLog) g_reguideLog->push_back(std::move(rec));
+    }
+    std::vector<std::pair<int, int>> reguideCollisionSeg;
+    std::vector<std::vector<Eigen::Vector3d>> paths;
+    if (this->isReguideRequired(reguideCollisionSeg) && this->pathSearch(reguideCollisionSeg, paths)) {
+        this->astarPaths_ = paths;
+        this->assignGuidesCoreOn(reguideCollisionSeg, paths);
+    } else {
+        this->weightDistance_ *= 2.0;
+        ++r.failCount;
+    }
+    if (r.gateDynamic) this->weightDynamicObstacle_ *= 2.0;
+    r.needOptimize = true;
+}
+
+// setDeviceReguide(1): per group of planners that share a batch key and a node pool, the eligible ones as one staged
+// batch (control points, guide CSR, weights, state) through vigo_rebound_reguide, one round of downloads, the results
+// installed per planner.  pairCap: the old pairs plus four new ones per control point on average over the group, and
+// pointCap two full-length paths per planner, are budgets as in prologueOnDevice: a group over either gets
+// VIGO_ERR_INVALID_ARG (nothing written, the message is printed) and runs the twin on the workers.
+void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& devOk) {
+    std::vector<bsplineTraj*>& active = pb.active;
+    std::vector<size_t> owners;
+    for (size_t a = 0; a < active.size(); ++a)
+        if (devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) && active[a]->collisionSeg_.size() <= (size_t)VIGO_MAX_COLLISION_SEGS) owners.push_back(a);
+    auto same = [&](size_t a, size_t b) {
+        const bsplineTraj* x = active[owners[a]];
+        const bsplineTraj* y = active[owners[b]];
+        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
+               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
+    };
+    long long nDecided = 0;
+    vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+        bsplineTraj* lead = active[owners[members[0]]];
+        if (!lead->syncDevice()) return;
+        const double res = lead->map_->getRes();
+        const int N = lead->optData_.controlPoints.cols();
+        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
+                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
+        if (N < 7 || N > VIGO_MAX_CTRL_POINTS || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS ||
+            pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS || !(lead->notCheckRatio_ >= 0.0 && lead->notCheckRatio_ <= 1.0))
+            return;
+        std::vector<size_t> who;
+        HostBatch hb(N);
+        std::vector<vigo_rebound_state_t> state;
+        for (size_t m : members) {
+            const size_t a = owners[m];
+            const bsplineTraj* p = active[a];
+#ifdef VIGO_WITH_ROS
+            // as in prologueOnDevice: a planner whose control points' box, grown by the node pool, is not inside the
+            // region the snapshot covers keeps to its own map
+            {
+                const mapRegion& R = p->mapRegion_;
+                bool inside = R.set;
+                for (int k = 0; k < 3 && inside; ++k) {
+                    const double half = (pool[k] / 2 + 1) * res;
+                    for (int i = 0; i < N && inside; ++i)
+                        inside = p->optData_.controlPoints(k, i) - half >= R.boxMin(k) && p->optData_.controlPoints(k, i) + half <= R.boxMax(k);
+                }
+                if (!inside) continue;
+            }
+#endif
+            const Rebound& r = pb.rb[pb.activeIdx[a]];
+            hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
+            vigo_rebound_state_t st;
+            std::memset(&st, 0, sizeof(st));
+            st.status = VIGO_RB_NEEDS_HOST;
+            st.lbfgs_status = p->lastStatus_;
+            st.fail_count = r.failCount;
+            st.gate_static = 1;
+            st.gate_dynamic = r.gateDynamic ? 1 : 0;
+            st.n_seg = (int32_t)p->collisionSeg_.size();
+            for (int q = 0; q < st.n_seg; ++q) { st.seg[2 * q] = p->collisionSeg_[q].first; st.seg[2 * q + 1] = p->collisionSeg_[q].second; }
+            state.push_back(st);
+            who.push_back(a);
+        }
+        const int B = (int)who.size();
+        if (B == 0) return;
+        const long long segCap = (long long)B * VIGO_MAX_COLLISION_SEGS, pointCap = (long long)B * 2 * (kAstarPathCap + 1),
+                        pairCap = (long long)hb.guides() + (long long)B * N * 4;
+        static thread_local StagingBuf dState, dOff, dPv, dPathSegOff, dPathOff, dPath, dStatus;
+        DeviceBatch d;
+        if (!uploadBatch(lead->dev_, hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t)) ||
+            !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)pairCap * 48) || !dPathSegOff.alloc(((size_t)B + 1) * 4) ||
+            !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) || !dStatus.alloc((size_t)B * 4))
+            return;
+        if (vigo_rebound_reguide(lead->dev_, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
+  lead->notCheckRatio_, res, pool, lead->minHeight_,
+                                 lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, (vigo_rebound_state_t*)dState.p, pairCap,
+                                 (int32_t*)dOff.p, (double*)dPv.p, nullptr, segCap, pointCap, (int32_t*)dPathSegOff.p, (int32_t*)dPathOff.p,
+                                 (double*)dPath.p, (int32_t*)dStatus.p) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_rebound_reguide failed: " << vigo_last_error(lead->dev_) << endl;
+            return;
+        }
+        std::vector<int32_t> status(B), off((size_t)B * N + 1), pathSegOff(B + 1);
+        if (!vigo_host::threadSync() || !dStatus.download(status.data(), (size_t)B * 4) || !dOff.download(off.data(), off.size() * 4) ||
+            !dPathSegOff.download(pathSegOff.data(), pathSegOff.size() * 4) ||
+            !dState.download(state.data(), state.size() * sizeof(vigo_rebound_state_t)) ||
+            !vigo_host::download(hb.weights.data(), d.weights, hb.weights.size() * 8))
+            return;
+        const int S = pathSegOff[B];
+        if (S < 0 || S > segCap || off.back() < 0 || off.back() > pairCap) return;
+        std::vector<int32_t> pathOff((size_t)S + 1, 0);
+        if (S > 0 && !dPathOff.download(pathOff.data(), pathOff.size() * 4)) return;
+        if (pathOff[S] < 0 || pathOff[S] > pointCap) return;
+        std::vector<double> path((size_t)pathOff[S] * 3), pv((size_t)off.back() * 6);
+        if ((!path.empty() && !dPath.download(path.data(), path.size() * 8)) || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
+        for (int b = 0; b < B; ++b) {
+            if (status[b] != VIGO_REGUIDE_DONE && status[b] != VIGO_REGUIDE_SEARCH_FAILED && status[b] != VIGO_REGUIDE_NOT_REQUIRED) continue;
+            bsplineTraj* p = active[who[b]];
+            Rebound& r = pb.rb[pb.activeIdx[who[b]]];
+            const vigo_rebound_state_t& st = state[b];
+            p->collisionSeg_.clear();
+            for (int q = 0; q < st.n_seg; ++q) p->collisionSeg_.push_back({st.seg[2 * q], st.seg[2 * q + 1]});
+            if (status[b] == VIGO_REGUIDE_DONE) {
+                p->astarPaths_.clear();
+                for (int k = pathSegOff[b]; k < pathSegOff[b + 1]; ++k) {
+                    p->astarPaths_.emplace_back();
+                    for (int q = pathOff[k]; q < pathOff[k + 1]; ++q)
+                        p->astarPaths_.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
+                }
+                // the merged CSR holds a control point's old pairs first: what follows them is this step's
+                for (int i = 0; i < N; ++i)
+                    for (int g = off[(size_t)b * N + i] + (int)p->optData_.guidePoints[i].size(); g < off[(size_t)b * N + i + 1]; ++g) {
+                        const double* q = pv.data() + (size_t)g * 6;
+                        p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+                        p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
+                    }
+            }
+            p->weightDistance_ = hb.weights[4 * (size_t)b + 0];
+            p->weightDynamicObstacle_ = hb.weights[4 * (size_t)b + 3];
+            r.failCount = st.fail_count;
+            r.needOptimize = st.solve_first != 0;
+            r.devStatus = st.status;                   // VIGO_RB_ACTIVE: the step is done
+            ++nDecided;
+        }
+    });
+    g_reguideDeviceDecided += nDecided;
+}
+
 // The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,
 // weight doubling and re-solve are queued for up to kRounds rounds without a host round trip; the host only sees
-// the planners that are done, need A* (re-guide, or failCount >= 4) or ran out of queued rounds.
+// the planners that are done, need A* (re-guide, or failCount >= 4) or ran out of queued rounds.  Under
+// setDeviceReguide the re-guide step is vigo_rebound_reguide's (or its twin's on the workers).
 void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
     const int kRounds = 4;   // failCount reaches 4 after at most four device rounds: then every round needs A*
     std::vector<bsplineTraj*>& active = pb.active;
@@ -1701,13 +1908,22 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
                 r.gateDynamic = dyn[a] != 0;
             }
         }
+        // the re-guide step of the planners the device takes (setDeviceReguide); out of time, every planner leaves below
+        const int reguide = timedOut ? 0 : deviceReguide();
+        if (reguide == 1) reguideOnDevice(pb, devOk);
         size_t nHost = 0;
-        for (size_t a = 0; a < active.size(); ++a) nHost += pb.rb[pb.activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
+        long long nTwin = 0;
+        for (size_t a = 0; a < active.size(); ++a) {
+            nHost += pb.rb[pb.activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
+            nTwin += reguide != 0 && devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) ? 1 : 0;
+        }
+        g_reguideHostRun += nTwin;
         parallelFor(active.size(), [&](size_t a) {
             Rebound& r = pb.rb[pb.activeIdx[a]];
             bsplineTraj* p = active[a];
             if (!devOk[a]) { p->reboundFinish(r, false); return; }             // no device: nothing to plan with
             if (r.devStatus == VIGO_RB_DONE) p->reboundFinish(r, true);          // BT.cpp:628-631
+            else if (reguide != 0 && reguideEligible(r)) p->reguideStepCore(r);  // what the device left, or setting 2: its twin
             else if (r.devStatus == VIGO_RB_NEEDS_HOST) p->reboundStep(r, r.gateStatic, r.gateDynamic, timedOut);   // A* and the rest of the pass
             // (still active: its next step is the gate, or the optimize() the device left for the next call)
         });

@@ -18,9 +18,11 @@
 #include <cstring>
 #include <mutex>
 
+#include "../../../include/vigo.h"
 #include "../../csrc/vigo_astar_core.hpp"
 #include "../../csrc/vigo_guide_core.hpp"
 #include "../../csrc/vigo_pathsearch_core.hpp"
+#include "../../csrc/vigo_reguide_core.hpp"
 #include "batchLayout.h"
 #include "workerPool.h"
 
@@ -1200,6 +1202,235 @@ int vigo_host_path_search_core(const unsigned char* vox, const int* dims, const 
     return 0;
 }
 
+}  // extern "C"
+
+// ---- the re-guide step of the rebound loop: the device's rules on the host, and the facade's own step ---------------------
+extern "C" {
+
+// vigo_rebound_reguide on the host: csrc/vigo_reguide_core.hpp around vigo_host_path_search_core and
+// vigo_host_guide_core on a dense byte grid, inputs and outputs as the device entry (dthresh: the handle's parameter
+// there).  cap_log2 / max_nodes / heap_cap as vigo_host_path_search_core, guide_path_cap and mode as
+// vigo_host_guide_core's path_cap and mode: with vigo_astar_capacity's and vigo_guide_capacity's values and mode 1 this
+// is the kernels' bit-exact twin; with large ones and mode 0 it is the facade's arithmetic.  (More than
+// VIGO_MAX_COLLISION_SEGS new segments are DEFERRED under every setting: the state does not hold them.)
+// Returns 0; -1 for what the device entry answers with VIGO_ERR_INVALID_ARG / _UNSUPPORTED (nothing is written).
+int vigo_host_rebound_reguide_core(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                                   const int* guide_off, const double* guide_pv, const unsigned char* guide_unk, double* weights,
+                                   double not_check_ratio, double dthresh, double step, const int* pool, double min_height, double max_height,
+                                   int cap_log2, int max_nodes, int heap_cap, int max_expansions, int search_path_cap, int guide_path_cap, int mode,
+                                   vigo_rebound_state_t* state, long long pair_cap, int* out_guide_off, double* out_guide_pv,
+                                   unsigned char* out_guide_unk, long long seg_cap, long long point_cap, int* out_path_seg_off, int* out_path_off,
+                                   double* out_path, int* out_status) {
+    const bool no_guides = !guide_off && !guide_pv && !guide_unk;
+    const bool no_paths = !out_path_seg_off && !out_path_off && !out_path;
+    if (B < 0 || N < 7 || N > VIGO_MAX_CTRL_POINTS || pair_cap < 0 || seg_cap < 0 || point_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
+        (!no_guides && (!guide_off || !guide_pv)) || (!no_paths && (!out_path_seg_off || !out_path_off || !out_path)) || !pool || !(step > 0.0) ||
+        !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 || !(res > 0) || mode < 0 || mode > 3 ||
+        (B > 0 && (!ctrl || !weights || !state || !out_guide_off || !out_guide_pv || !out_status)))
+        return -1;
+    for (int a = 0; a < 3; ++a)
+        if (pool[a] < 3 || pool[a] > vigo::kAstarMaxPoolAxis) return -1;
+    if (B == 0) return 0;
+    if (guide_off) {
+        if (guide_off[0] < 0) return -1;
+        for (size_t q = 0; q < (size_t)B * N; ++q)
+            if (guide_off[q + 1] < guide_off[q]) return -1;
+    }
+    const size_t ny = dims[1], nz = dims[2];
+    auto byteAt = [&](double x, double y, double z) -> unsigned {
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return 0xFFu;
+        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]];
+    };
+    auto occ = [&](double x, double y, double z) -> bool { return byteAt(x, y, z) & 1u; };
+    constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
+    // the rules: the new segments and the re-guide list of every trajectory that is worked on
+    std::vector<int> kind(B), n_list(B, 0), n_new(B, 0);
+    std::vector<int32_t> new_seg((size_t)B * 2 * kSegs), list((size_t)B * 2 * kSegs);
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        const vigo_rebound_state_t& st = state[b];
+        if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) { kind[b] = vigo::kReguideSkipped; return; }
+        const double* c = ctrl + b * (size_t)N * 3;
+        auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
+        auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+        auto need_guide = [&](int i) {
+            if (!guide_off || !guide_pv) return true;
+            for (int j = guide_off[b * N + i]; j < guide_off[b * N + i + 1]; ++j)
+                if (!vigo::reguide_guide_far(dthresh, c + 3 * i, guide_pv + 6 * (size_t)j)) return false;
+            return true;
+        };
+        int32_t seg[2 * kSegs];
+        uint8_t listed[kSegs];
+        int m = 0;
+        const int n_prev = std::min(std::max(st.n_seg, 0), kSegs);
+        const int n = vigo::reguide_rules(N, not_check_ratio, pt, ln, n_prev, st.seg, need_guide, kSegs, seg, listed, &m);
+        if (n > kSegs) { kind[b] = vigo::kReguideDeferred; return; }
+        kind[b] = -1;
+        n_new[b] = n;
+        std::copy(seg, seg + 2 * n, new_seg.begin() + b * 2 * kSegs);
+        int32_t* dst = list.data() + b * 2 * kSegs;
+        for (int k = 0; k < n; ++k)
+            if (listed[k]) { dst[2 * n_list[b]] = seg[2 * k]; dst[2 * n_list[b] + 1] = seg[2 * k + 1]; ++n_list[b]; }
+    });
+    // the path search on the lists, the guide step on its output
+    std::vector<int> l_off(B + 1, 0), l_seg(2, 0);
+    for (int b = 0; b < B; ++b) {
+        l_off[b + 1] = l_off[b] + n_list[b];
+        l_seg.insert(l_seg.end() - 2, list.begin() + (size_t)b * 2 * kSegs, list.begin() + (size_t)b * 2 * kSegs + 2 * n_list[b]);
+    }
+    const long long S = l_off[B], pts_room = S * ((long long)search_path_cap + 1);
+    std::vector<int> ps_status(B), ps_seg_off(B + 1), ps_seg(2 * (size_t)S + 2), ps_path_off((size_t)S + 1), ps_counts(2 * (size_t)B);
+    std::vector<double> ps_path(3 * (size_t)pts_room + 3);
+    if (vigo_host_path_search_core(vox, dims, origin, res, B, N, ctrl, l_off.data(), l_seg.data(), not_check_ratio, step, pool, min_height, max_height,
+                                   cap_log2, max_nodes, heap_cap, max_expansions, search_path_cap, S, pts_room, ps_status.data(), ps_seg_off.data(),
+                                   ps_seg.data(), ps_path_off.data(), ps_path.data(), ps_counts.data()) != 0)
+        return -1;
+    const long long total_seg = ps_seg_off[B], total_pts = ps_path_off[total_seg];
+    if (!no_paths && (total_seg > seg_cap || total_pts > point_cap)) return -1;
+    long long pairs_room = 0;
+    for (long long k = 0; k < total_seg; ++k) pairs_room += vigo::guide_pushes_total(N, ps_seg[2 * k], ps_seg[2 * k + 1]);
+    std::vector<int> g_off((size_t)B * N + 1), g_status(B);
+    std::vector<double> g_pv(6 * (size_t)pairs_room + 6);
+    std::vector<unsigned char> g_unk((size_t)pairs_room + 1);
+    if (vigo_host_guide_core(vox, dims, origin, res, B, N, ctrl, ps_seg_off.data(), ps_seg.data(), ps_path_off.data(), ps_path.data(), mode, guide_path_cap,
+                             pairs_room, g_off.data(), g_pv.data(), g_unk.data(), g_status.data(), nullptr) != 0)
+        return -1;
+    // the outcomes and the merged offsets
+    std::vector<int> outcome(B);
+    long long total = 0;
+    for (int b = 0; b < B; ++b) {
+        const bool cut = ps_status[b] == vigo::kPathsOk && vigo::paths_cut_by_bound(ps_counts[2 * b], ps_seg_off[b + 1] - ps_seg_off[b]);
+        outcome[b] = vigo::reguide_outcome(kind[b] != vigo::kReguideSkipped, kind[b] == vigo::kReguideDeferred, n_list[b], ps_status[b], cut,
+                                           g_status[b] == vigo::kGuideDeferred);
+        if (guide_off) total += guide_off[(size_t)(b + 1) * N] - guide_off[(size_t)b * N];
+        if (outcome[b] == vigo::kReguideDone) total += g_off[(size_t)(b + 1) * N] - g_off[(size_t)b * N];
+    }
+    if (total > pair_cap || total > 0x7fffffffLL) return -1;
+    long long at = 0;
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < N; ++i) {
+            const size_t q = (size_t)b * N + i;
+            out_guide_off[q] = (int)at;
+            auto put = [&](const double* src, unsigned unk) {
+                std::copy(src, src + 6, out_guide_pv + 6 * at);
+                if (out_guide_unk) out_guide_unk[at] = (unsigned char)unk;
+                ++at;
+            };
+            if (guide_off)
+                for (int j = guide_off[q]; j < guide_off[q + 1]; ++j) {
+                    const double* src = guide_pv + 6 * (size_t)j;
+                    put(src, guide_unk ? guide_unk[j] : ((byteAt(src[0], src[1], src[2]) >> 1) & 1u));
+                }
+            if (outcome[b] == vigo::kReguideDone)
+                for (int j = g_off[q]; j < g_off[q + 1]; ++j) put(g_pv.data() + 6 * (size_t)j, g_unk[j]);
+        }
+    out_guide_off[(size_t)B * N] = (int)at;
+    if (!no_paths) {
+        std::copy(ps_seg_off.begin(), ps_seg_off.end(), out_path_seg_off);
+        std::copy(ps_path_off.begin(), ps_path_off.begin() + total_seg + 1, out_path_off);
+        std::copy(ps_path.begin(), ps_path.begin() + 3 * total_pts, out_path);
+    }
+    for (int b = 0; b < B; ++b) {
+        out_status[b] = outcome[b];
+        if (outcome[b] == vigo::kReguideDeferred || outcome[b] == vigo::kReguideSkipped) continue;
+        vigo_rebound_state_t& st = state[b];
+        st.n_seg = n_new[b];
+        std::copy(new_seg.begin() + (size_t)b * 2 * kSegs, new_seg.begin() + (size_t)b * 2 * kSegs + 2 * n_new[b], st.seg);
+        vigo::reguide_commit(outcome[b], st.gate_dynamic != 0, weights + 4 * (size_t)b, &st.fail_count, &st.status, &st.solve_first);
+    }
+    return 0;
+}
+
+// the header's rules alone on flags: pt / ln uint8[N], prev int[n_prev][2], need uint8[N] (isControlPointRequireNewGuide
+// per control point) -> the number of new segments, out_seg[cap][2], out_listed[cap], *out_n_list
+int vigo_host_reguide_rules(int N, double not_check_ratio, const unsigned char* pt, const unsigned char* ln, int n_prev, const int* prev,
+                            const unsigned char* need, int cap, int* out_seg, unsigned char* out_listed, int* out_n_list) {
+    return vigo::reguide_rules(N, not_check_ratio, [&](int i) { return pt[i] != 0; }, [&](int i) { return ln[i] != 0; }, n_prev, prev,
+                               [&](int i) { return need[i] != 0; }, cap, out_seg, out_listed, out_n_list);
+}
+
+// The FACADE's own step on the same inputs: one planner per trajectory on a dense byte grid with these control points,
+// collisionSeg_ (state[b].n_seg, seg), guide pairs (guide_off / guide_pv, or NULL), the weights and failCount
+// (state[b].fail_count), then bsplineTraj::reboundStep(r, true, state[b].gate_dynamic != 0, false) — the existing host
+// code, unchanged.  Out: weights; state[b].fail_count, n_seg (the true count) and seg (the first
+// VIGO_MAX_COLLISION_SEGS); the planner's guide pairs as CSR; astarPaths_ as CSR (path_seg_off[B+1], path_off, path);
+// need_optimize[B].  cfg as in vigo_host_bspline_prologue.  Returns 0, -1 on a bad argument, -2 when a buffer is too small.
+int vigo_host_reguide_facade(const unsigned char* vox, const int* dims, const double* origin, double res, int B, int N, const double* ctrl,
+                             const int* guide_off, const double* guide_pv, double* weights, const double* cfg, vigo_rebound_state_t* state,
+                             long long pair_cap, int* out_guide_off, double* out_guide_pv, long long seg_cap, long long point_cap,
+                             int* out_path_seg_off, int* out_path_off, double* out_path, int* out_need_optimize) {
+    if (B < 0 || N < 7 || !ctrl || !weights || !cfg || !state || !out_guide_off || !out_guide_pv || !out_path_seg_off || !out_path_off || !out_path ||
+        !out_need_optimize || (!guide_off != !guide_pv))
+        return -1;
+    PlannerPool pool;
+    initPool(pool, vox, dims, origin, res, cfg);
+    std::vector<std::vector<int32_t>> off(B);
+    std::vector<std::vector<double>> pv(B);
+    std::vector<std::vector<std::vector<Eigen::Vector3d>>> paths(B);
+    vigo_host::parallelFor((size_t)B, [&](size_t b) {
+        auto bt = pool.take();
+        bt->clear();
+        Eigen::MatrixXd c(3, N);
+        for (int i = 0; i < N; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl[(b * N + i) * 3 + k];
+        bt->setControlPoints(c);
+        vigo_rebound_state_t& st = state[b];
+        std::vector<std::pair<int, int>> sg;
+        for (int k = 0; k < st.n_seg && k < VIGO_MAX_COLLISION_SEGS; ++k) sg.push_back({st.seg[2 * k], st.seg[2 * k + 1]});
+        std::vector<std::vector<Eigen::Vector3d>> gp(N), gd(N);
+        if (guide_off)
+            for (int i = 0; i < N; ++i)
+                for (int j = guide_off[b * N + i]; j < guide_off[b * N + i + 1]; ++j) {
+                    const double* q = guide_pv + 6 * (size_t)j;
+                    gp[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+                    gd[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
+                }
+        double save_d, save_o;
+        bt->getLoopWeights(save_d, save_o);
+        bt->setLoopState(sg, gp, gd, weights[4 * b + 0], weights[4 * b + 3]);
+        int failCount = st.fail_count;
+        bool needOptimize = false, done = false;
+        bt->runLoopBody(true, st.gate_dynamic != 0, failCount, needOptimize, done);
+        bt->getLoopWeights(weights[4 * b + 0], weights[4 * b + 3]);
+        st.fail_count = failCount;
+        out_need_optimize[b] = needOptimize ? 1 : 0;
+        const auto& ns = bt->getCollisionSeg();
+        st.n_seg = (int32_t)ns.size();
+        for (size_t k = 0; k < ns.size() && k < (size_t)VIGO_MAX_COLLISION_SEGS; ++k) { st.seg[2 * k] = ns[k].first; st.seg[2 * k + 1] = ns[k].second; }
+        off[b].assign(1, 0);
+        vigo_host::appendGuides(bt->getOptData(), N, off[b], pv[b]);
+        paths[b] = bt->getAstarPaths();
+        bt->setLoopState({}, {}, {}, save_d, save_o);
+        pool.give(std::move(bt));
+    });
+    long long g = 0, s = 0, q = 0;
+    for (int b = 0; b < B; ++b) {
+        for (int i = 0; i < N; ++i) out_guide_off[(size_t)b * N + i] = (int)(g + off[b][i]);
+        g += off[b][N];
+        s += (long long)paths[b].size();
+        for (const auto& p : paths[b]) q += (long long)p.size();
+    }
+    out_guide_off[(size_t)B * N] = (int)g;
+    if (g > pair_cap || s > seg_cap || q > point_cap) return -2;
+    long long w = 0;
+    for (int b = 0; b < B; ++b) { std::memcpy(out_guide_pv + 6 * w, pv[b].data(), pv[b].size() * sizeof(double)); w += (long long)pv[b].size() / 6; }
+    s = 0; q = 0;
+    for (int b = 0; b < B; ++b) {
+        out_path_seg_off[b] = (int)s;
+        for (const auto& p : paths[b]) {
+            out_path_off[s++] = (int)q;
+            for (const auto& v : p) { for (int a = 0; a < 3; ++a) out_path[3 * q + a] = v(a); ++q; }
+        }
+    }
+    out_path_seg_off[B] = (int)s;
+    out_path_off[s] = (int)q;
+    return 0;
+}
+
+}  // extern "C"
+
+extern "C" {
+
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
 // every run: first ONE run before any setter is touched (slot 0: the untouched default), then `reps` rounds of
 // setDeviceGuides(0), (1), (2) in turn (slots 1, 2, 3), each with setDeviceAstar(astar != 0).  Outputs per slot [4] x ...
@@ -1389,6 +1620,143 @@ int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, con
         }
     bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
+}
+
+// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
+// every run: first ONE run before setDeviceReguide is touched (slot 3: the untouched default), then `reps` rounds over
+//   slot 0  setDeviceReguide(2)   the reference point of slot 1: every re-guide step by the workers' twin
+//   slot 1  setDeviceReguide(1)   vigo_rebound_reguide
+//   slot 2  setDeviceReguide(0)
+// in turn (slots: bit k set = slot k runs; slot 3 always does).  budget: setDeviceAstarBudget.  Outputs per slot [4] x ...
+// of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl, n_seg + segs, n_path_pts + paths,
+// n_guides + guides; per run total_ms[4][reps] (slot 3: entry 0 only); counts[4][2]: deviceReguideTotals' device-decided
+// and worker-run steps of the slot's last run.  twin[2]: the steps slot 0's last run logged, and how many of them the
+// kernels' host twin (vigo_host_rebound_reguide_core, mode 1) under the capacities caps[4] = (cap_log2, max_nodes,
+// heap_cap, guide_path_cap) does not answer with VIGO_REGUIDE_DEFERRED — the share the device can decide.  Every switch
+// is off on return.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
+int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
+                                 const double* path_xyz, const double* cfg, int slots, int budget, int reps, const int* caps, int ncp_cap,
+                                 long long cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts,
+                                 double* paths, int* n_guides, double* guides, double* total_ms, long long* counts, long long* twin) {
+    using trajPlanner::bsplineTraj;
+    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || !caps || !twin) return -1;
+    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), vox, map->voxels().size());
+    ros::NodeHandle nh;
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    nh.setParam("bspline_traj/max_path_length", 1000.0);
+    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
+    std::vector<nav_msgs::Path> in(n);
+    for (int t = 0; t < n; ++t)
+        for (int i = 0; i < n_pts; ++i) {
+            geometry_msgs::PoseStamped ps;
+            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
+            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
+            in[t].poses.push_back(ps);
+        }
+    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    int rc = 0;
+    twin[0] = twin[1] = 0;
+    bsplineTraj::setDeviceAstarBudget(budget);
+    for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
+        const int slot = run == 0 ? 3 : (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
+        if (run > 0 && !((slots >> slot) & 1)) continue;
+        const bool last = run == 0 || rep + 1 == reps;
+        std::vector<std::unique_ptr<bsplineTraj>> owners;
+        std::vector<bsplineTraj*> ps;
+        for (int t = 0; t < n; ++t) {
+            owners.emplace_back(new bsplineTraj(nh));
+            owners.back()->setMap(map);
+            owners.back()->updateMaxVel(2.0);
+            owners.back()->updateMaxAcc(3.0);
+            ps.push_back(owners.back().get());
+        }
+        bsplineTraj::updatePathBatch(ps, in, cond);
+        std::vector<bsplineTraj::ReguideStepRecord> log;
+        if (run > 0) bsplineTraj::setDeviceReguide(2 - slot);
+        if (slot == 0 && last) bsplineTraj::setReguideStepLog(&log);
+        long long dev0, host0, dev1, host1;
+        bsplineTraj::deviceReguideTotals(&dev0, &host0);
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
+        total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        bsplineTraj::deviceReguideTotals(&dev1, &host1);
+        bsplineTraj::setReguideStepLog(nullptr);
+        if (run > 0) bsplineTraj::setDeviceReguide(0);
+        if (!last) continue;
+        counts[2 * slot] = dev1 - dev0;
+        counts[2 * slot + 1] = host1 - host0;
+        // the logged steps, one by one (a trajectory's result does not depend on its batch), by the kernels' twin
+        twin[0] += (long long)log.size();
+        const int pool[3] = {2 * int(cfg[3] / res), 2 * int(cfg[4] / res), 2 * int(cfg[5] / res)};
+        std::vector<int> deferred(log.size(), 0);
+        vigo_host::parallelFor(log.size(), [&](size_t k) {
+            bsplineTraj::ReguideStepRecord& R = log[k];
+            vigo_rebound_state_t st;
+            std::memset(&st, 0, sizeof(st));
+            st.status = VIGO_RB_NEEDS_HOST;
+            st.gate_static = 1;
+            st.gate_dynamic = R.gateDynamic;
+            st.fail_count = R.failCount;
+            st.n_seg = (int)std::min<size_t>(R.seg.size() / 2, VIGO_MAX_COLLISION_SEGS);
+            std::copy(R.seg.begin(), R.seg.begin() + 2 * st.n_seg, st.seg);
+            if (R.seg.size() / 2 > (size_t)VIGO_MAX_COLLISION_SEGS) { deferred[k] = 1; return; }   // (the facade keeps these off the device)
+            const long long pairCap = (long long)R.gpv.size() / 6 + (long long)R.N * (VIGO_MAX_COLLISION_SEGS + 4);
+            std::vector<int> off((size_t)R.N + 1);
+            std::vector<double> pv((size_t)pairCap * 6 + 6);
+            R.gpv.resize(R.gpv.size() + 6);
+            int status = VIGO_REGUIDE_DEFERRED;
+            const int r = vigo_host_rebound_reguide_core(vox, dims, origin, res, 1, R.N, R.ctrl.data(), R.goff.data(), R.gpv.data(), nullptr, R.weights, 0.0,
+                                                         cfg[0], res, pool, cfg[1], cfg[2], caps[0], caps[1], caps[2], budget, 128, caps[3], 1, &st,
+                                                         pairCap, off.data(), pv.data(), nullptr, 0, 0, nullptr, nullptr, nullptr, &status);
+            deferred[k] = (r != 0 || status == VIGO_REGUIDE_DEFERRED) ? 1 : 0;
+        });
+        for (size_t k = 0; k < log.size(); ++k) twin[1] += deferred[k] ? 0 : 1;
+        long long g = 0, w = 0, sg = 0;
+        for (int t = 0; t < n && rc == 0; ++t) {
+            const size_t o = (size_t)slot * n + t;
+            const Eigen::MatrixXd c = ps[t]->getControlPoints();
+            ok[o] = res2[t] ? 1 : 0;
+            solver[o] = ps[t]->getLastSolverStatus();
+            ncp[o] = (int)c.cols();
+            if (c.cols() > ncp_cap) { rc = -2; break; }
+            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
+            std::vector<int32_t> off{0};
+            std::vector<double> pv;
+            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
+            n_guides[o] = (int)(pv.size() / 6);
+            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
+            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
+            g += (long long)pv.size() / 6;
+            const auto& cs = ps[t]->getCollisionSeg();
+            n_seg[o] = (int)cs.size();
+            if (sg + (long long)cs.size() > cap) { rc = -2; break; }
+            for (const auto& sgm : cs) { segs[((size_t)slot * cap + sg) * 2] = sgm.first; segs[((size_t)slot * cap + sg) * 2 + 1] = sgm.second; ++sg; }
+            int pts = 0;
+            for (const auto& path : ps[t]->getAstarPaths())
+                for (const auto& v : path) {
+                    if (w + 1 > cap) { rc = -2; break; }
+                    for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
+                    ++w; ++pts;
+                }
+            n_path_pts[o] = pts;
+        }
+    }
+    bsplineTraj::setDeviceReguide(0);
+    bsplineTraj::setReguideStepLog(nullptr);
+    bsplineTraj::setDeviceAstarBudget(16384);
+    return rc;
+}
+
+// the facade's opt-in switches as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
+// deviceReguide (0: everything off, the default)
+int vigo_host_switches() {
+    using trajPlanner::bsplineTraj;
+    return (bsplineTraj::deviceAstar() ? 1 : 0) | (bsplineTraj::deviceGuides() << 1) | (bsplineTraj::devicePrologue() ? 8 : 0) |
+           (bsplineTraj::deviceReguide() << 4);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ PREC_F32 = 1
 PREC_F64_FAST = 2
 ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_DEFERRED, ASTAR_PATH_TOO_LONG = 0, 1, 2, 3   # vigo_astar_search's out_status
 GUIDE_OK, GUIDE_DEFERRED = 0, 1                                                  # vigo_guide_assign's out_status
+REGUIDE_DONE, REGUIDE_SEARCH_FAILED, REGUIDE_NOT_REQUIRED, REGUIDE_DEFERRED, REGUIDE_SKIPPED = 0, 1, 2, 3, 4   # vigo_rebound_reguide's out_status
 PATHS_OK, PATHS_FAILED, PATHS_DEFERRED = 0, 1, 2                                 # vigo_collision_segs' / vigo_path_search's out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
@@ -515,6 +516,40 @@ class Vigo:
             C.c_void_p(status.data_ptr()), C.c_void_p(o_seg_off.data_ptr()), C.c_void_p(o_seg.data_ptr()), C.c_void_p(o_path_off.data_ptr()),
             C.c_void_p(o_path.data_ptr()), C.c_void_p(counts.data_ptr()) if want_counts else None), "vigo_path_search")
         return status[:B], o_seg_off, o_seg[:scap], o_path_off, o_path[:pcap], (counts[:B] if want_counts else None)
+
+    def rebound_reguide(self, ctrl, guide_off, guide_pv, guide_unk, weights, state, step, pool, min_height, max_height, pair_cap,
+                        not_check_ratio=0.0, max_expansions=1 << 20, search_path_cap=256, seg_cap=None, point_cap=None, want_paths=True,
+                        want_unknown=True, fill=0):
+        """vigo_rebound_reguide: the re-guide step of the rebound loop for the NEEDS_HOST trajectories of a batch (ctrl f64
+        [B,N,3]; the current guide CSR guide_off int32 [B*N+1] / guide_pv f64 [G,6] / guide_unk uint8 [G], or None: no guides).
+        weights [B,4] and state [B, REBOUND_STATE_INTS] (int32) are updated in place.  -> (status int32 [B]: REGUIDE_*, the
+        merged CSR off int32 [B*N+1], pv f64 [pair_cap,6], unk uint8 [pair_cap] or None, and the paths path_seg_off int32
+        [B+1], path_off int32 [seg_cap+1], path f64 [point_cap,3] or three None).  seg_cap defaults to B * 48, point_cap to
+        seg_cap * (search_path_cap + 1); the output buffers are pre-filled with `fill`."""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, N = ctrl.shape[0], ctrl.shape[1]
+        _shape(state, (B, self.REBOUND_STATE_INTS), "state")
+        _shape(weights, (B, 4), "weights")
+        scap = B * 48 if seg_cap is None else int(seg_cap)
+        pcap = min(scap * (int(search_path_cap) + 1), 1 << 24) if point_cap is None else int(point_cap)
+        cap = int(pair_cap)
+        d = self.device
+        status = torch.full((max(B, 1),), fill, dtype=torch.int32, device=d)
+        o_off = torch.full((B * N + 1,), fill, dtype=torch.int32, device=d)
+        o_pv = torch.full((max(cap, 1), 6), float(fill), dtype=torch.float64, device=d)
+        o_unk = torch.full((max(cap, 1),), fill & 0xFF, dtype=torch.uint8, device=d) if want_unknown else None
+        p_so = torch.full((B + 1,), fill, dtype=torch.int32, device=d) if want_paths else None
+        p_po = torch.full((max(scap, 0) + 1,), fill, dtype=torch.int32, device=d) if want_paths else None
+        p_pa = torch.full((max(pcap, 1), 3), float(fill), dtype=torch.float64, device=d) if want_paths else None
+        opt = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self._lib.vigo_rebound_reguide(
+            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), None if guide_off is None else _ptr(guide_off, torch.int32, "guide_off", d),
+            None if guide_pv is None else _ptr(guide_pv, torch.float64, "guide_pv", d),
+            None if guide_unk is None else _ptr(guide_unk, torch.uint8, "guide_unk", d), _ptr(weights, torch.float64, "weights", d),
+            float(not_check_ratio), float(step), (C.c_int32 * 3)(*[int(v) for v in pool]), float(min_height), float(max_height), int(max_expansions),
+            int(search_path_cap), _ptr(state, torch.int32, "state", d), cap, opt(o_off), opt(o_pv), opt(o_unk), scap, pcap, opt(p_so), opt(p_po),
+            opt(p_pa), opt(status)), "vigo_rebound_reguide")
+        return status[:B], o_off, o_pv[:cap], (o_unk[:cap] if want_unknown else None), p_so, p_po, (p_pa[:pcap] if want_paths else None)
 
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
