@@ -1,6 +1,6 @@
 """The proof obligations behind the corridor checker's span certificates (csrc/vigo_corridor.hip, SpanConst),
-checked on the CPU against the oracle's own samples — a numpy restatement of the kernel's constants, independent of the
-device code:
+checked on the CPU against the oracle's own samples — a numpy restatement of the kernel's constants (tests/corridor_restatement.py),
+independent of the device code:
 
   interval  every sample's float position (oracle sampler, exact-power chain, PS.cpp:1026-1056 + pose2Octomap) lies in
             [(float)(p - R), (float)(p + R)], p = the fast form at ONE clock value of the span, R = 2 E + L * dt;
@@ -17,68 +17,7 @@ import pytest
 
 import oracle_lib as ol
 from trajectory_planner_amd import synth
-
-U40 = 1.0 + 2.0 ** -40
-
-
-def bernstein_abs_max_of_derivative(c, Tu):
-    deg = len(c) - 1
-    best = 0.0
-    for i in range(deg):
-        bi, ratio, pw = c[1], 1.0, 1.0
-        for k in range(1, i + 1):
-            ratio *= (i - k + 1) / (deg - k)
-            pw *= Tu
-            bi += ratio * ((k + 1) * c[k + 1]) * pw
-        best = max(best, abs(bi))
-    return best
-
-
-def segment_constants(c, n, dT, box_a, map_res):
-    """per axis: E, base, lipd, nlo, nhi, thr — the arithmetic of k_corridor's prologue"""
-    deg = len(c) - 1
-    Tu = (n - 1) * dT * (1.0 + 2.0 ** -20)
-    Tm = abs(Tu)
-    A = sum(abs(c[d]) * Tm ** d for d in range(deg + 1))
-    A1 = sum((d + 1) * abs(c[d + 1]) * Tm ** d for d in range(deg))
-    E = 2.0 ** -46 * A + 2.0 ** -1000
-    L = bernstein_abs_max_of_derivative(c, Tu) + 2.0 ** -40 * A1
-    drift = n * 2.0 ** -52 * (Tm + abs(dT))
-    base = (2.0 * E + L * drift) * U40
-    lipd = L * abs(dT) * U40
-    h = box_a / 2
-    Mx = A * (1.0 + 2.0 ** -20) + abs(h)
-    dl = 2.0 ** -50 * (Mx + abs(h))
-    ql, qh = (box_a - dl) / map_res, (box_a + dl) / map_res
-    ql -= abs(ql) * 2.0 ** -50
-    qh += abs(qh) * 2.0 ** -50
-    nlo, nhi = int(ql), int(qh)
-    thr = -1.0
-    if nhi == nlo + 1:
-        cnt = lambda d: int(d / map_res)
-        cc = nhi * map_res
-        for _ in range(8):
-            if cnt(np.nextafter(cc, -np.inf)) >= nhi:
-                cc = float(np.nextafter(cc, -np.inf))
-        while cnt(cc) < nhi:
-            cc = float(np.nextafter(cc, np.inf))
-        assert cnt(cc) >= nhi > cnt(float(np.nextafter(cc, -np.inf)))
-        thr = cc
-    return Tu, E, base, lipd, nlo, nhi, thr
-
-
-def fast_form(c, t):
-    x, pw = 0.0, 1.0
-    for d in range(len(c)):
-        x += c[d] * pw
-        pw *= t
-    return x
-
-
-def keys_of(f, h, i, map_res, rf):
-    """lattice point i of an axis from the pose's float: (float)(f - h + i * map_res), floor(rf * q) (vectorised)"""
-    q = (f.astype(np.float64) - h + i * map_res).astype(np.float32)
-    return q, np.floor(rf * q.astype(np.float64)).astype(np.int64)
+from corridor_restatement import U40, fast_form, keys_of, segment_constants
 
 
 @pytest.mark.parametrize("seed,n,box,map_res,res", [(1, 6000, (0.4, 0.4, 0.2), 0.2, 0.1), (2, 10000, (0.6, 0.3, 0.2), 0.1, 0.1),

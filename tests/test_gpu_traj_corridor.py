@@ -14,6 +14,7 @@ import oracle_lib as ol
 from gpu_util import to_dev
 from trajectory_planner_amd import synth
 from trajectory_planner_amd._lib import load
+from traj_corridor_util import pack, restate, runs_status  # noqa: F401  (runs_status: tests/test_gpu_traj_point.py takes it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,70 +46,6 @@ def wide_world(seed=7, n=256, res=0.1):
     return synth.World(vox, np.array([-12.8, -12.8, -0.5]), res, np.zeros((0, 6)))
 
 
-def restate(g, seg_off, coeffs, knots, delT, endpoint, nonfinite, exact=True, device_sweep=None):
-    """The five rules in Python: (status, n, flag, first, count, seg mask).  Statuses other than 0 come from
-    vigo_traj_sample_runs (pinned against the literal loop by tests/test_traj_runs.py): the loop cannot run there.
-    exact=False, device_sweep=Vigo: the facade's present route instead (libm pow, vigo_box_collision_points)."""
-    O = ol.oracle()
-    T = len(seg_off) - 1
-    S, _, d1 = coeffs.shape
-    deg = d1 - 1
-    out = dict(status=np.zeros(T, np.int32), n=np.zeros(T, np.int32), flag=np.zeros(T, np.uint8),
-               first=np.full(T, -1, np.int32), count=np.zeros(T, np.int32), seg=np.zeros(S, np.uint8))
-    box = np.ascontiguousarray(BOX)
-    p = np.zeros(3)
-    with ol.pow_mode(exact):
-        for t in range(T):
-            a, b = int(seg_off[t]), int(seg_off[t + 1])
-            K = b - a
-            k = [float(x) for x in knots[a + t:a + t + K + 1]]
-            d = float(delT[t])
-            st = runs_status(k, d)
-            out["status"][t] = st
-            if st:
-                continue
-            poses, segs = [], []
-            tt = 0.0
-            while tt < k[-1]:                                  # rule 1
-                s = next((i for i in range(K) if k[i] <= tt <= k[i + 1]), -1)   # rule 2
-                if s < 0:
-                    poses.append((0.0, 0.0, 0.0))
-                else:
-                    c = np.ascontiguousarray(coeffs[a + s])
-                    O.vgo_poly_pos(deg, ol._d(c[0]), ol._d(c[1]), ol._d(c[2]), tt - k[s], ol._d(p))
-                    poses.append(tuple(p))
-                segs.append(s)
-                tt += d
-            poses.append(tuple(float(x) for x in endpoint[t]))   # rule 3
-            segs.append(next((i for i in range(K) if k[i] <= tt <= k[i + 1]), -1))
-            if device_sweep is not None:
-                hit = device_sweep.box_collision_points(to_dev(np.array(poses), device_sweep.device), BOX, RES).cpu().numpy()
-            else:
-                hit = [O.vgo_box_collision(C.byref(g), q[0], q[1], q[2], ol._d(box), RES) for q in poses]   # rule 4
-            first, count = -1, 0
-            for j, (q, s) in enumerate(zip(poses, segs)):
-                h = bool(hit[j]) or (nonfinite and not all(math.isfinite(x) for x in q))
-                if h:
-                    count += 1
-                    first = j if first < 0 else first
-                    if s >= 0:
-                        out["seg"][a + s] = 1                  # rule 5
-            out["n"][t] = len(poses)
-            out["flag"][t] = count > 0
-            out["first"][t] = first
-            out["count"][t] = count
-    return out
-
-
-def runs_status(k, d):
-    kk = np.ascontiguousarray(k, dtype=np.float64)
-    K = len(kk) - 1
-    buf = np.zeros(max(K, 1), np.int32)
-    n = C.c_int32()
-    return load().vigo_traj_sample_runs(K, kk.ctypes.data_as(C.c_void_p), float(d), buf.ctypes.data_as(C.c_void_p),
-                                        buf.ctypes.data_as(C.c_void_p), C.byref(n))
-
-
 def device(v, seg_off, coeffs, knots, delT, endpoint, nonfinite):
     r = v.traj_corridor_check(to_dev(seg_off, v.device), to_dev(coeffs, v.device), to_dev(knots, v.device),
                               to_dev(delT, v.device), to_dev(endpoint, v.device), BOX, RES, nonfinite_collides=nonfinite)
@@ -119,16 +56,6 @@ def assert_same(got, ref, ctx=""):
     for key in ("status", "n", "flag", "first", "count", "seg"):
         assert np.array_equal(got[key], ref[key]), (ctx, key, np.nonzero(got[key] != ref[key])[0][:10],
                                                     got[key][:16], ref[key][:16])
-
-
-def pack(trajs):
-    """[(knots, coeffs [K,3,d+1], delT, endpoint)] -> the entry's CSR layout"""
-    seg_off = np.cumsum([0] + [len(c) for _, c, _, _ in trajs]).astype(np.int32)
-    coeffs = np.concatenate([c for _, c, _, _ in trajs]) if seg_off[-1] else np.zeros((0, 3, 8))
-    knots = np.concatenate([np.asarray(k, np.float64) for k, _, _, _ in trajs])
-    delT = np.array([d for _, _, d, _ in trajs], np.float64)
-    endpoint = np.array([e for _, _, _, e in trajs], np.float64)
-    return seg_off, np.ascontiguousarray(coeffs, dtype=np.float64), knots, delT, endpoint
 
 
 def random_trajs(seed, T, deg, n_samples, kmax=12):
