@@ -271,6 +271,7 @@ private:
     bool termCost(int term, const Eigen::MatrixXd& controlPoints, double& cost, Eigen::MatrixXd& gradient);
     void reboundFinish(Rebound& r, bool ok);
     bool sameBatchKey(const bsplineTraj& o) const;                  // may share a device batch with o
+    struct SearchGroup;                                             // ... and what its device A* searches share on top
     void fillParams(vigo_params_s* P) const;
     static void solveBatch(const std::vector<bsplineTraj*>& ps);   // one vigo_optimize for all
     /* up to maxRounds rounds of the loop on the device for one group; fills rb[i]->devStatus / gate flags and the

@@ -1,6 +1,6 @@
 // batchLayout.h — internal to the host facades: bsplineTraj's optData flattened into the batch layouts of include/vigo.h
-// (control points column by column; guide pairs and dynamic obstacles as CSR lists, offsets + flat list), and the order
-// in which planners are grouped into device batches.
+// (control points column by column; guide pairs and dynamic obstacles as CSR lists, offsets + flat list), what comes
+// back in those layouts installed into a planner, and the order in which planners are grouped into device batches.
 #ifndef VIGO_HOST_BATCH_LAYOUT_H
 #define VIGO_HOST_BATCH_LAYOUT_H
 #include <trajectory_planner/bsplineTraj.h>
@@ -24,6 +24,33 @@ inline void appendGuides(const trajPlanner::optData& od, int N, std::vector<int3
         }
         off.push_back((int32_t)(pv.size() / 6));
     }
+}
+
+// appendGuides' inverse for one planner: of the pairs off[i] .. off[i + 1] of control point i (off: the planner's N + 1
+// offsets into pv) those after the first skip_i are appended to its lists.  skip_i is 0, or with skipHeld the number of
+// pairs the control point holds already (a CSR that repeats the held pairs before the new ones).
+inline void installGuides(trajPlanner::optData& od, int N, const int32_t* off, const double* pv, bool skipHeld = false) {
+    for (int i = 0; i < N; ++i)
+        for (int g = off[i] + (skipHeld ? (int)od.guidePoints[i].size() : 0); g < off[i + 1]; ++g) {
+            const double* q = pv + (size_t)g * 6;
+            od.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+            od.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
+        }
+}
+
+// the paths of the segments s0 .. s1-1 of a CSR (pathOff: offsets into path's xyz triples) in place of a planner's paths
+inline void installPaths(std::vector<std::vector<Eigen::Vector3d>>& paths, int s0, int s1, const int32_t* pathOff, const double* path) {
+    paths.clear();
+    for (int k = s0; k < s1; ++k) {
+        paths.emplace_back();
+        for (int q = pathOff[k]; q < pathOff[k + 1]; ++q)
+            paths.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
+    }
+}
+
+// a planner's control points (3 x N, column by column) appended to ctrl as [N][3]
+inline void appendCtrl(const Eigen::MatrixXd& controlPoints, std::vector<double>& ctrl) {
+    ctrl.insert(ctrl.end(), controlPoints.data(), controlPoints.data() + 3 * (size_t)controlPoints.cols());
 }
 
 // the dynamic obstacles (position, velocity, size: 9 doubles each) appended to obs

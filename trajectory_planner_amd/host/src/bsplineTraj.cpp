@@ -102,14 +102,40 @@ void bsplineTraj::initParam() {
     else maxObstacleSize_ = Eigen::Vector3d(mos[0], mos[1], mos[2]);
 }
 
+// What the device searches of a group of planners share, from the group's lead: the map's resolution, the A* node pool
+// setMap sizes from maxObstacleSize_ (BT.cpp:187-195), the control-point count.
+struct bsplineTraj::SearchGroup {
+    double res;
+    int32_t pool[3];
+    double half[3];        // reach of a search's node pool around the midpoint of its ends: pool / 2 + 1 nodes
+    int N;
+    double notCheckRatio;
+    explicit SearchGroup(const bsplineTraj& lead)
+        : res(lead.map_->getRes()), N(lead.optData_.controlPoints.cols()), notCheckRatio(lead.notCheckRatio_) {
+        for (int k = 0; k < 3; ++k) {
+            pool[k] = 2 * int(lead.maxObstacleSize_(k) / res);
+            half[k] = (pool[k] / 2 + 1) * res;
+        }
+    }
+    // the ranges the device entries take: the pool's always, with `scan` vigo_path_search's for the segment scan too
+    bool valid(bool scan) const {
+        for (int k = 0; k < 3; ++k)
+            if (pool[k] < 3 || pool[k] > VIGO_ASTAR_MAX_POOL_AXIS) return false;
+        return !scan || (N >= 7 && notCheckRatio >= 0.0 && notCheckRatio <= 1.0);
+    }
+    // x and y may share such a group: a device batch and a node pool
+    static bool same(const bsplineTraj& x, const bsplineTraj& y) {
+        return x.sameBatchKey(y) && x.maxObstacleSize_(0) == y.maxObstacleSize_(0) && x.maxObstacleSize_(1) == y.maxObstacleSize_(1) &&
+               x.maxObstacleSize_(2) == y.maxObstacleSize_(2);
+    }
+};
+
 // BT.cpp:187-195
 void bsplineTraj::setMap(const std::shared_ptr<mapManager::occMap>& map) {
     this->map_ = map;
     this->pathSearch_.reset(new AStar);
-    int maxGridX = 2 * int(this->maxObstacleSize_(0) / this->map_->getRes());
-    int maxGridY = 2 * int(this->maxObstacleSize_(1) / this->map_->getRes());
-    int maxGridZ = 2 * int(this->maxObstacleSize_(2) / this->map_->getRes());
-    this->pathSearch_->initGridMap(map, Eigen::Vector3i(maxGridX, maxGridY, maxGridZ), this->minHeight_, this->maxHeight_);
+    const SearchGroup g(*this);
+    this->pathSearch_->initGridMap(map, Eigen::Vector3i(g.pool[0], g.pool[1], g.pool[2]), this->minHeight_, this->maxHeight_);
     this->mapStamp_ = 0;  // force a new device snapshot
 }
 
@@ -746,8 +772,7 @@ void bsplineTraj::gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uin
         std::vector<double> ctrl, obs;
         std::vector<int32_t> ooff{0};
         for (size_t b : idx) {
-            const double* c = ps[b]->optData_.controlPoints.data();
-            ctrl.insert(ctrl.end(), c, c + 3 * N);
+            vigo_host::appendCtrl(ps[b]->optData_.controlPoints, ctrl);
             vigo_host::appendObstacles(ps[b]->optData_, obs);
             ooff.push_back((int32_t)(obs.size() / 9));
         }
@@ -1036,9 +1061,44 @@ namespace {
 using vigo_host::Companion;
 std::atomic<size_t> g_pipelineThreshold{2048};
 thread_local bool t_insidePipeline = false;
-std::atomic<long long> g_prologueNs{0}, g_astarDeviceDecided{0}, g_astarHostRun{0};
+
+// one opt-in device stage of makePlanBatch: its setting, and over the process how many of its work items the device
+// decided and how many ran on the host instead
+struct StageSwitch {
+    std::atomic<int> mode{0};
+    std::atomic<long long> deviceDecided{0}, hostRun{0};
+    void totals(long long* decided, long long* host) const {
+        if (decided) *decided = deviceDecided.load();
+        if (host) *host = hostRun.load();
+    }
+};
+StageSwitch g_astar, g_guides, g_prologue, g_reguide;
+std::atomic<long long> g_prologueNs{0}, g_prologueChainNs{0};
+std::atomic<int> g_deviceAstarBudget{16384};
+constexpr int kAstarPathCap = 128;   // path points a device search returns (a longer path is searched again by the host)
+int onOffOrTwin(int mode) { return mode == 1 || mode == 2 ? mode : 0; }
 }  // namespace
 void bsplineTraj::setBatchPipelineThreshold(size_t planners) { g_pipelineThreshold.store(planners); }
+
+void bsplineTraj::setDeviceAstar(bool on) { g_astar.mode.store(on); }
+bool bsplineTraj::deviceAstar() { return g_astar.mode.load() != 0; }
+void bsplineTraj::setDeviceAstarBudget(int maxExpansions) { g_deviceAstarBudget.store(maxExpansions < 0 ? 0 : maxExpansions); }
+void bsplineTraj::deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds) {
+    g_astar.totals(deviceDecided, hostRun);
+    if (prologueSeconds) *prologueSeconds = g_prologueNs.load() * 1e-9;
+}
+void bsplineTraj::setDeviceGuides(int mode) { g_guides.mode.store(onOffOrTwin(mode)); }
+int bsplineTraj::deviceGuides() { return g_guides.mode.load(); }
+void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun) { g_guides.totals(deviceDecided, hostRun); }
+void bsplineTraj::setDevicePrologue(bool on) { g_prologue.mode.store(on); }
+bool bsplineTraj::devicePrologue() { return g_prologue.mode.load() != 0; }
+void bsplineTraj::devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds) {
+    g_prologue.totals(deviceDecided, hostRun);
+    if (chainSeconds) *chainSeconds = g_prologueChainNs.load() * 1e-9;
+}
+void bsplineTraj::setDeviceReguide(int mode) { g_reguide.mode.store(onOffOrTwin(mode)); }
+int bsplineTraj::deviceReguide() { return g_reguide.mode.load(); }
+void bsplineTraj::deviceReguideTotals(long long* deviceDecided, long long* hostRun) { g_reguide.totals(deviceDecided, hostRun); }
 
 // one unsplit makePlanBatch call: per planner (index into the call's planners) its loop state and result; the planners
 // still in the loop, in call order, with their indices
@@ -1050,6 +1110,17 @@ struct bsplineTraj::PlanBatch {
     std::atomic<long long> nsSeg{0}, nsAstar{0}, nsGuide{0};   // prologue CPU time summed over the worker threads
     std::atomic<long long> nsChain{0};                         // setDevicePrologue: wall time of the device chains (all three steps)
     explicit PlanBatch(size_t P) : rb(P), result(P, false) {}
+    // step 1 of planner p and, with `search`, step 2 on the calling worker, timed; false: its A* failed
+    bool hostSteps(bsplineTraj* p, bool search) {
+        const double t0 = wallSeconds();
+        p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);           // step 1
+        const double t1 = wallSeconds();
+        nsSeg += (long long)((t1 - t0) * 1e9);
+        if (!search) return true;
+        const bool found = p->pathSearch(p->collisionSeg_, p->astarPaths_);         // step 2
+        nsAstar += (long long)((wallSeconds() - t1) * 1e9);
+        return found;
+    }
 };
 
 // BT.cpp:333-385 for many planners at once: host prologue per planner, then the rebound loops in
@@ -1128,47 +1199,35 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         std::vector<uint8_t> outcome(P, 0);
         prologueOnDevice(planners, pb, outcome);
         for (size_t i = 0; i < P; ++i) prepared[i] = outcome[i] == 1;
-    } else if (deviceAstar()) {
-        // the same three steps with step 2 gathered over the planners: collision segments on the workers, the searches
-        // of all planners on the device (pathSearchBatch), guide assignment on the workers
-        std::vector<uint8_t> ready(P, 0), found(P, 0);
-        parallelFor(P, [&](size_t i) {
-            bsplineTraj* p = planners[i];
-            if (!p->init_ || !p->map_) return;
-            const double t0 = wallSeconds();
-            p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);       // step 1
-            pb.nsSeg += (long long)((wallSeconds() - t0) * 1e9);
-            ready[i] = 1;
-        });
-        const double t1 = wallSeconds();
-        pathSearchBatch(planners, ready, found);                                    // step 2
-        pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
-        if (guides != 0) hasPaths = found;
-        else
-        parallelFor(P, [&](size_t i) {
-            if (!found[i]) return;
+    } else {
+        // The host steps, per planner on the workers, all three in one pass.  setDeviceAstar gathers step 2 over the
+        // planners (pathSearchBatch: the searches of all of them on the device): steps 1 and 3 are then a pass each
+        // around it.  setDeviceGuides gathers step 3 (below).
+        const bool gathered = deviceAstar();
+        std::vector<uint8_t> ready(P, 0);
+        auto assignGuides = [&](size_t i) {
             const double t2 = wallSeconds();
             planners[i]->assignGuidePointsSemiCircle(planners[i]->astarPaths_, planners[i]->collisionSeg_);   // step 3
             pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
             prepared[i] = 1;
+        };
+        parallelFor(P, [&](size_t i) {
+            bsplineTraj* p = planners[i];
+            if (!p->init_ || !p->map_ || !pb.hostSteps(p, !gathered)) return;
+            if (gathered) ready[i] = 1;
+            else if (guides != 0) hasPaths[i] = 1;
+            else assignGuides(i);
         });
-    } else
-    parallelFor(P, [&](size_t i) {
-        bsplineTraj* p = planners[i];
-        if (!p->init_ || !p->map_) return;
-        const double t0 = wallSeconds();
-        p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);           // step 1
-        const double t1 = wallSeconds();
-        const bool found = p->pathSearch(p->collisionSeg_, p->astarPaths_);         // step 2
-        const double t2 = wallSeconds();
-        pb.nsSeg += (long long)((t1 - t0) * 1e9);
-        pb.nsAstar += (long long)((t2 - t1) * 1e9);
-        if (!found) return;
-        if (guides != 0) { hasPaths[i] = 1; return; }
-        p->assignGuidePointsSemiCircle(p->astarPaths_, p->collisionSeg_);           // step 3
-        pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
-        prepared[i] = 1;
-    });
+        if (gathered) {
+            const double t1 = wallSeconds();
+            pathSearchBatch(planners, ready, hasPaths);                                 // step 2
+            pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
+            if (guides == 0)
+                parallelFor(P, [&](size_t i) {
+                    if (hasPaths[i]) assignGuides(i);
+                });
+        }
+    }
     if (guides != 0) {
         // step 3 gathered over the planners (setDeviceGuides): the device, or its twin on the workers
         const double t2 = wallSeconds();
@@ -1189,19 +1248,26 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
     }
 }
 
+#ifdef VIGO_WITH_ROS
 namespace {
-std::atomic<bool> g_deviceAstar{false};
-std::atomic<int> g_deviceAstarBudget{16384};
-constexpr int kAstarPathCap = 128;   // path points a device search returns (a longer path is searched again by the host)
-}  // namespace
-void bsplineTraj::setDeviceAstar(bool on) { g_deviceAstar.store(on); }
-bool bsplineTraj::deviceAstar() { return g_deviceAstar.load(); }
-void bsplineTraj::setDeviceAstarBudget(int maxExpansions) { g_deviceAstarBudget.store(maxExpansions < 0 ? 0 : maxExpansions); }
-void bsplineTraj::deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds) {
-    if (deviceDecided) *deviceDecided = g_astarDeviceDecided.load();
-    if (hostRun) *hostRun = g_astarHostRun.load();
-    if (prologueSeconds) *prologueSeconds = g_prologueNs.load() * 1e-9;
+// The snapshot of this map type covers the planner's region only, and the device takes everything outside it for occupied
+// while the host asks the map itself: what a device stage may read has to lie inside the region.  This is the test:
+// the axis-aligned box of the n points xyz (triples), grown by half[k] along axis k, lies inside R, bounds included.
+// (No region set, or a NaN coordinate: it does not.  No points: it does.)
+bool boxInRegion(const mapRegion& R, const double* xyz, size_t n, const double half[3]) {
+    if (!R.set) return false;
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (size_t q = 0; q < 3 * n; ++q) {
+        const double v = xyz[q];
+        if (v < lo[q % 3] || std::isnan(v)) lo[q % 3] = v;       // (a NaN stays: nothing compares below or above it)
+        if (v > hi[q % 3] || std::isnan(v)) hi[q % 3] = v;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!(lo[k] - half[k] >= R.boxMin(k) && hi[k] + half[k] <= R.boxMax(k))) return false;
+    return true;
 }
+}  // namespace
+#endif
 
 // one AstarSearch(res, pStart, pEnd) of planner `planner`: from the start of segment `seg` to the end of segment `endSeg`
 struct bsplineTraj::AstarJob {
@@ -1224,38 +1290,20 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
     std::vector<size_t> owners;                       // the planners with jobs, in call order
     for (size_t i = 0; i < P; ++i)
         if (!jobsOf[i].empty()) owners.push_back(i);
-    auto same = [&](size_t a, size_t b) {
-        const bsplineTraj* x = planners[owners[a]];
-        const bsplineTraj* y = planners[owners[b]];
-        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
-               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
-    };
+    auto same = [&](size_t a, size_t b) { return SearchGroup::same(*planners[owners[a]], *planners[owners[b]]); };
     vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
         bsplineTraj* lead = planners[owners[members[0]]];
         if (!lead->syncDevice()) return;
-        const double res = lead->map_->getRes();
-        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
-                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
-        if (pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS ||
-            pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
-            return;
+        const SearchGroup g(*lead);
+        if (!g.valid(false)) return;
         std::vector<size_t> idx;
         std::vector<double> se[2];
         for (size_t m : members)
             for (size_t j : jobsOf[owners[m]]) {
 #ifdef VIGO_WITH_ROS
-                // The snapshot of this map type covers the planner's region only, and the device takes everything outside
-                // it for occupied while the host A* asks the map itself: a search whose node pool (pool / 2 + 1 nodes
-                // around the midpoint of its ends) is not inside the region stays with the host.
-                {
-                    const mapRegion& R = planners[owners[m]]->mapRegion_;
-                    bool inside = R.set;
-                    for (int k = 0; k < 3 && inside; ++k) {
-                        const double c = (jobs[j].s(k) + jobs[j].e(k)) / 2, half = (pool[k] / 2 + 1) * res;
-                        inside = c - half >= R.boxMin(k) && c + half <= R.boxMax(k);
-                    }
-                    if (!inside) continue;
-                }
+                // a search whose node pool (around the midpoint of its ends) is not inside the region stays with the host
+                const double mid[3] = {(jobs[j].s(0) + jobs[j].e(0)) / 2, (jobs[j].s(1) + jobs[j].e(1)) / 2, (jobs[j].s(2) + jobs[j].e(2)) / 2};
+                if (!boxInRegion(planners[owners[m]]->mapRegion_, mid, 1, g.half)) continue;
 #endif
                 idx.push_back(j);
                 for (int k = 0; k < 3; ++k) { se[0].push_back(jobs[j].s(k)); se[1].push_back(jobs[j].e(k)); }
@@ -1266,7 +1314,7 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
         if (!dS.upload(se[0].data(), se[0].size() * 8) || !dE.upload(se[1].data(), se[1].size() * 8) || !dStatus.alloc((size_t)Q * 4) ||
             !dLen.alloc((size_t)Q * 4) || !dPath.alloc((size_t)Q * kAstarPathCap * 24))
             return;
-        if (vigo_astar_search(lead->dev_, Q, (const double*)dS.p, (const double*)dE.p, res, pool, lead->minHeight_, lead->maxHeight_,
+        if (vigo_astar_search(lead->dev_, Q, (const double*)dS.p, (const double*)dE.p, g.res, g.pool, lead->minHeight_, lead->maxHeight_,
                               g_deviceAstarBudget.load(), kAstarPathCap, (int32_t*)dStatus.p, (int32_t*)dLen.p, (double*)dPath.p,
                               nullptr) != VIGO_OK) {
             cout << "[BsplineTraj]: vigo_astar_search failed: " << vigo_last_error(lead->dev_) << endl;
@@ -1292,8 +1340,8 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
     });
     long long nDecided = 0;
     for (uint8_t d : decided) nDecided += d;
-    g_astarDeviceDecided += nDecided;
-    g_astarHostRun += (long long)jobs.size() - nDecided;
+    g_astar.deviceDecided += nDecided;
+    g_astar.hostRun += (long long)jobs.size() - nDecided;
     parallelFor(owners.size(), [&](size_t o) {
         bsplineTraj* p = planners[owners[o]];
         for (size_t j : jobsOf[owners[o]]) {
@@ -1386,16 +1434,18 @@ void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, con
 }
 
 namespace {
-std::atomic<bool> g_devicePrologue{false};
-std::atomic<long long> g_prologueDeviceDecided{0}, g_prologueHostRun{0}, g_prologueChainNs{0};
-}  // namespace
-void bsplineTraj::setDevicePrologue(bool on) { g_devicePrologue.store(on); }
-bool bsplineTraj::devicePrologue() { return g_devicePrologue.load(); }
-void bsplineTraj::devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds) {
-    if (deviceDecided) *deviceDecided = g_prologueDeviceDecided.load();
-    if (hostRun) *hostRun = g_prologueHostRun.load();
-    if (chainSeconds) *chainSeconds = g_prologueChainNs.load() * 1e-9;
+// The tail of a stage's downloads, once its S segments and nPairs guide pairs are known to fit their buffers: the S + 1
+// path offsets (S > 0; else the one offset is 0), checked against pointCap, then the path points and the pairs there are.
+bool downloadPathsAndPairs(int S, long long pointCap, long long nPairs, const StagingBuf& dPathOff, const StagingBuf& dPath, const StagingBuf& dPv,
+                           std::vector<int32_t>& pathOff, std::vector<double>& path, std::vector<double>& pv) {
+    pathOff.assign((size_t)S + 1, 0);
+    if (S > 0 && !dPathOff.download(pathOff.data(), pathOff.size() * 4)) return false;
+    if (pathOff[S] < 0 || pathOff[S] > pointCap) return false;
+    path.resize((size_t)pathOff[S] * 3);
+    pv.resize((size_t)nPairs * 6);
+    return (path.empty() || dPath.download(path.data(), path.size() * 8)) && (pv.empty() || dPv.download(pv.data(), pv.size() * 8));
 }
+}  // namespace
 
 // Steps 1-3 for all planners under setDevicePrologue(true).  Per group of planners that share a batch key and a node
 // pool: control points up, vigo_path_search on the scanned segments, vigo_guide_assign on its output (device pointers,
@@ -1415,45 +1465,25 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
     std::vector<size_t> owners;
     for (size_t i = 0; i < P; ++i)
         if (planners[i]->init_ && planners[i]->map_) owners.push_back(i);
-    auto same = [&](size_t a, size_t b) {
-        const bsplineTraj* x = planners[owners[a]];
-        const bsplineTraj* y = planners[owners[b]];
-        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
-               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
-    };
+    auto same = [&](size_t a, size_t b) { return SearchGroup::same(*planners[owners[a]], *planners[owners[b]]); };
     const double tc0 = wallSeconds();
     vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
         bsplineTraj* lead = planners[owners[members[0]]];
         if (!lead->syncDevice()) return;
-        const double res = lead->map_->getRes();
-        const int N = lead->optData_.controlPoints.cols();
-        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
-                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
-        if (N < 7 || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS ||
-            pool[2] > VIGO_ASTAR_MAX_POOL_AXIS || !(lead->notCheckRatio_ >= 0.0 && lead->notCheckRatio_ <= 1.0))
-            return;
+        const SearchGroup g(*lead);
+        const int N = g.N;
+        if (!g.valid(true)) return;
         std::vector<size_t> who;
         std::vector<double> ctrl;
         for (size_t m : members) {
             const bsplineTraj* p = planners[owners[m]];
 #ifdef VIGO_WITH_ROS
-            // The snapshot of this map type covers the planner's region only and takes everything outside it for
-            // occupied.  Every search's node pool (pool / 2 + 1 nodes around the midpoint of two control points) and
-            // with it every path point lies in the control points' box grown by that much: a planner whose grown box
-            // is not inside the region keeps to its own map.
-            {
-                const mapRegion& R = p->mapRegion_;
-                bool inside = R.set;
-                for (int k = 0; k < 3 && inside; ++k) {
-                    const double half = (pool[k] / 2 + 1) * res;
-                    for (int i = 0; i < N && inside; ++i)
-                        inside = p->optData_.controlPoints(k, i) - half >= R.boxMin(k) && p->optData_.controlPoints(k, i) + half <= R.boxMax(k);
-                }
-                if (!inside) continue;
-            }
+            // Every search's node pool (around the midpoint of two control points) and with it every path point lies in
+            // the control points' box grown by the pool's reach: a planner whose grown box is not inside the region
+            // keeps to its own map.
+            if (!boxInRegion(p->mapRegion_, p->optData_.controlPoints.data(), N, g.half)) continue;
 #endif
-            for (int i = 0; i < N; ++i)
-                for (int a = 0; a < 3; ++a) ctrl.push_back(p->optData_.controlPoints(a, i));
+            vigo_host::appendCtrl(p->optData_.controlPoints, ctrl);
             who.push_back(owners[m]);
         }
         const int B = (int)who.size();
@@ -1465,7 +1495,7 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             !dSeg.alloc((size_t)segCap * 8) || !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) ||
             !dCounts.alloc((size_t)B * 8) || !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)pairCap * 48) || !dGStatus.alloc((size_t)B * 4))
             return;
-        if (vigo_path_search(lead->dev_, B, N, (const double*)dCtrl.p, nullptr, nullptr, lead->notCheckRatio_, res, pool, lead->minHeight_,
+        if (vigo_path_search(lead->dev_, B, N, (const double*)dCtrl.p, nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
                              lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, segCap, pointCap, (int32_t*)dStatus.p,
                              (int32_t*)dSegOff.p, (int32_t*)dSeg.p, (int32_t*)dPathOff.p, (double*)dPath.p, (int32_t*)dCounts.p) != VIGO_OK) {
             cout << "[BsplineTraj]: vigo_path_search failed: " << vigo_last_error(lead->dev_) << endl;
@@ -1481,11 +1511,10 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
         if (guided && (!dOff.download(off.data(), off.size() * 4) || !dGStatus.download(gstatus.data(), (size_t)B * 4))) return;
         const int S = segOff[B];
         if (S < 0 || S > segCap || off.back() < 0 || off.back() > pairCap) return;
-        std::vector<int32_t> seg((size_t)S * 2), pathOff((size_t)S + 1, 0);
-        if (S > 0 && (!dSeg.download(seg.data(), seg.size() * 4) || !dPathOff.download(pathOff.data(), pathOff.size() * 4))) return;
-        if (pathOff[S] < 0 || pathOff[S] > pointCap) return;
-        std::vector<double> path((size_t)pathOff[S] * 3), pv((size_t)off.back() * 6);
-        if ((!path.empty() && !dPath.download(path.data(), path.size() * 8)) || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
+        std::vector<int32_t> seg((size_t)S * 2), pathOff;
+        std::vector<double> path, pv;
+        if (S > 0 && !dSeg.download(seg.data(), seg.size() * 4)) return;
+        if (!downloadPathsAndPairs(S, pointCap, off.back(), dPathOff, dPath, dPv, pathOff, path, pv)) return;
         for (int b = 0; b < B; ++b) {
             bsplineTraj* p = planners[who[b]];
             // A failed walk owns nothing on the device, but the host steps leave the scanned segments and the paths found
@@ -1495,20 +1524,10 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             // the device returns the bounded lists only: a planner whose astarPaths_ is longer runs the host steps
             if (status[b] != VIGO_PATHS_OK || vigo::paths_cut_by_bound(counts[2 * (size_t)b], nOut)) continue;
             p->collisionSeg_.clear();
-            p->astarPaths_.clear();
-            for (int k = segOff[b]; k < segOff[b + 1]; ++k) {
-                p->collisionSeg_.push_back({seg[2 * (size_t)k], seg[2 * (size_t)k + 1]});
-                p->astarPaths_.emplace_back();
-                for (int q = pathOff[k]; q < pathOff[k + 1]; ++q)
-                    p->astarPaths_.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
-            }
+            for (int k = segOff[b]; k < segOff[b + 1]; ++k) p->collisionSeg_.push_back({seg[2 * (size_t)k], seg[2 * (size_t)k + 1]});
+            vigo_host::installPaths(p->astarPaths_, segOff[b], segOff[b + 1], pathOff.data(), path.data());
             if (gstatus[b] != VIGO_GUIDE_OK) { needGuides[who[b]] = 1; continue; }
-            for (int i = 0; i < N; ++i)
-                for (int g = off[(size_t)b * N + i]; g < off[(size_t)b * N + i + 1]; ++g) {
-                    const double* q = pv.data() + (size_t)g * 6;
-                    p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
-                    p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
-                }
+            vigo_host::installGuides(p->optData_, N, off.data() + (size_t)b * N, pv.data());
             outcome[who[b]] = 1;
         }
     });
@@ -1517,37 +1536,18 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
     g_prologueChainNs += chainNs;
     long long nDecided = 0;
     for (size_t i : owners) nDecided += (outcome[i] != 0 && !needGuides[i]) || failedOnDevice[i];
-    g_prologueDeviceDecided += nDecided;
-    g_prologueHostRun += (long long)owners.size() - nDecided;
+    g_prologue.deviceDecided += nDecided;
+    g_prologue.hostRun += (long long)owners.size() - nDecided;
     parallelFor(owners.size(), [&](size_t o) {
         const size_t i = owners[o];
         bsplineTraj* p = planners[i];
         if (outcome[i] != 0) return;
-        if (!needGuides[i]) {
-            const double t0 = wallSeconds();
-            p->findCollisionSeg(p->optData_.controlPoints, p->collisionSeg_);           // step 1
-            const double t1 = wallSeconds();
-            const bool found = p->pathSearch(p->collisionSeg_, p->astarPaths_);         // step 2
-            pb.nsSeg += (long long)((t1 - t0) * 1e9);
-            pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
-            if (!found) { outcome[i] = 2; return; }
-        }
+        if (!needGuides[i] && !pb.hostSteps(p, true)) { outcome[i] = 2; return; }       // steps 1-2
         const double t2 = wallSeconds();
         p->assignGuidesCore();                                                          // step 3, the device's code
         pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
         outcome[i] = 1;
     });
-}
-
-namespace {
-std::atomic<int> g_deviceGuides{0};
-std::atomic<long long> g_guideDeviceDecided{0}, g_guideHostRun{0};
-}  // namespace
-void bsplineTraj::setDeviceGuides(int mode) { g_deviceGuides.store(mode == 1 || mode == 2 ? mode : 0); }
-int bsplineTraj::deviceGuides() { return g_deviceGuides.load(); }
-void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun) {
-    if (deviceDecided) *deviceDecided = g_guideDeviceDecided.load();
-    if (hostRun) *hostRun = g_guideHostRun.load();
 }
 
 // segments and paths as vigo_guide_assign takes them: the first min(collisionSeg.size(), paths.size()) of both
@@ -1577,9 +1577,8 @@ void bsplineTraj::assignGuidesCoreOn(const std::vector<std::pair<int, int>>& col
     std::vector<double> path;
     packGuideLists(collisionSeg, paths, seg, pathOff, path);
     const int N = this->optData_.controlPoints.cols();
-    std::vector<double> ctrl((size_t)N * 3);
-    for (int i = 0; i < N; ++i)
-        for (int a = 0; a < 3; ++a) ctrl[(size_t)i * 3 + a] = this->optData_.controlPoints(a, i);
+    std::vector<double> ctrl;
+    vigo_host::appendCtrl(this->optData_.controlPoints, ctrl);
     size_t longest = 1;
     for (size_t k = 0; k + 1 < pathOff.size(); ++k) {
         if (pathOff[k + 1] - pathOff[k] < 1) return;     // (pathSearch leaves at least the two ends)
@@ -1624,26 +1623,20 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
                 const size_t seg0 = seg.size() / 2;
                 p->packGuideInput(seg, pathOff, path);
 #ifdef VIGO_WITH_ROS
-                // the snapshot of this map type covers the planner's region only and takes everything outside it for
-                // occupied; the line checks stay inside the box of the path points: a planner with a path point outside
-                // the region keeps to its own map (the twin)
-                {
-                    const mapRegion& R = p->mapRegion_;
-                    bool inside = R.set;
-                    for (size_t q = (size_t)pathOff[seg0] * 3; q < path.size() && inside; ++q)
-                        inside = path[q] >= R.boxMin(int(q % 3)) && path[q] <= R.boxMax(int(q % 3));
-                    if (!inside) {
-                        seg.resize(seg0 * 2);
-                        path.resize((size_t)pathOff[seg0] * 3);
-                        pathOff.resize(seg0 + 1);
-                        continue;
-                    }
+                // the line checks stay inside the box of the path points: a planner with a path point outside the region
+                // keeps to its own map (the twin), and what was packed of it is taken back
+                const size_t pt0 = (size_t)pathOff[seg0];
+                const double none[3] = {0.0, 0.0, 0.0};
+                if (!boxInRegion(p->mapRegion_, path.data() + pt0 * 3, path.size() / 3 - pt0, none)) {
+                    seg.resize(seg0 * 2);
+                    path.resize(pt0 * 3);
+                    pathOff.resize(seg0 + 1);
+                    continue;
                 }
 #endif
                 for (size_t k = seg0; k < seg.size() / 2; ++k) pairs += vigo::guide_pushes_total(N, seg[2 * k], seg[2 * k + 1]);
                 segOff.push_back((int32_t)(seg.size() / 2));
-                for (int i = 0; i < N; ++i)
-                    for (int a = 0; a < 3; ++a) ctrl.push_back(p->optData_.controlPoints(a, i));
+                vigo_host::appendCtrl(p->optData_.controlPoints, ctrl);
                 who.push_back(owners[m]);
             }
             const int B = (int)who.size();
@@ -1671,38 +1664,24 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
             if (off.back() < 0 || off.back() > cap || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
             for (int b = 0; b < B; ++b) {
                 if (status[b] != VIGO_GUIDE_OK) continue;
-                bsplineTraj* p = planners[who[b]];
-                for (int i = 0; i < N; ++i)
-                    for (int g = off[(size_t)b * N + i]; g < off[(size_t)b * N + i + 1]; ++g) {
-                        const double* q = pv.data() + (size_t)g * 6;
-                        p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
-                        p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
-                    }
+                vigo_host::installGuides(planners[who[b]]->optData_, N, off.data() + (size_t)b * N, pv.data());
                 done[who[b]] = 1;
             }
         });
     }
     long long nDone = 0, nFound = 0;
     for (size_t i = 0; i < P; ++i) { nDone += done[i]; nFound += found[i] ? 1 : 0; }
-    g_guideDeviceDecided += nDone;
-    g_guideHostRun += nFound - nDone;
+    g_guides.deviceDecided += nDone;
+    g_guides.hostRun += nFound - nDone;
     parallelFor(P, [&](size_t i) {
         if (found[i] && !done[i]) planners[i]->assignGuidesCore();
     });
 }
 
 namespace {
-std::atomic<int> g_deviceReguide{0};
-std::atomic<long long> g_reguideDeviceDecided{0}, g_reguideHostRun{0};
 std::mutex g_reguideLogMutex;
 std::vector<bsplineTraj::ReguideStepRecord>* g_reguideLog = nullptr;
 }  // namespace
-void bsplineTraj::setDeviceReguide(int mode) { g_deviceReguide.store(mode == 1 || mode == 2 ? mode : 0); }
-int bsplineTraj::deviceReguide() { return g_deviceReguide.load(); }
-void bsplineTraj::deviceReguideTotals(long long* deviceDecided, long long* hostRun) {
-    if (deviceDecided) *deviceDecided = g_reguideDeviceDecided.load();
-    if (hostRun) *hostRun = g_reguideHostRun.load();
-}
 void bsplineTraj::setReguideStepLog(std::vector<ReguideStepRecord>* log) {
     std::lock_guard<std::mutex> lock(g_reguideLogMutex);
     g_reguideLog = log;
@@ -1753,23 +1732,14 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
     std::vector<size_t> owners;
     for (size_t a = 0; a < active.size(); ++a)
         if (devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) && active[a]->collisionSeg_.size() <= (size_t)VIGO_MAX_COLLISION_SEGS) owners.push_back(a);
-    auto same = [&](size_t a, size_t b) {
-        const bsplineTraj* x = active[owners[a]];
-        const bsplineTraj* y = active[owners[b]];
-        return x->sameBatchKey(*y) && x->maxObstacleSize_(0) == y->maxObstacleSize_(0) && x->maxObstacleSize_(1) == y->maxObstacleSize_(1) &&
-               x->maxObstacleSize_(2) == y->maxObstacleSize_(2);
-    };
+    auto same = [&](size_t a, size_t b) { return SearchGroup::same(*active[owners[a]], *active[owners[b]]); };
     long long nDecided = 0;
     vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
         bsplineTraj* lead = active[owners[members[0]]];
         if (!lead->syncDevice()) return;
-        const double res = lead->map_->getRes();
-        const int N = lead->optData_.controlPoints.cols();
-        const int32_t pool[3] = {2 * int(lead->maxObstacleSize_(0) / res), 2 * int(lead->maxObstacleSize_(1) / res),
-                                 2 * int(lead->maxObstacleSize_(2) / res)};            // setMap, BT.cpp:187-195
-        if (N < 7 || N > VIGO_MAX_CTRL_POINTS || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || pool[0] > VIGO_ASTAR_MAX_POOL_AXIS ||
-            pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS || !(lead->notCheckRatio_ >= 0.0 && lead->notCheckRatio_ <= 1.0))
-            return;
+        const SearchGroup g(*lead);
+        const int N = g.N;
+        if (!g.valid(true) || N > VIGO_MAX_CTRL_POINTS) return;
         std::vector<size_t> who;
         HostBatch hb(N);
         std::vector<vigo_rebound_state_t> state;
@@ -1777,18 +1747,9 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             const size_t a = owners[m];
             const bsplineTraj* p = active[a];
 #ifdef VIGO_WITH_ROS
-            // as in prologueOnDevice: a planner whose control points' box, grown by the node pool, is not inside the
-            // region the snapshot covers keeps to its own map
-            {
-                const mapRegion& R = p->mapRegion_;
-                bool inside = R.set;
-                for (int k = 0; k < 3 && inside; ++k) {
-                    const double half = (pool[k] / 2 + 1) * res;
-                    for (int i = 0; i < N && inside; ++i)
-                        inside = p->optData_.controlPoints(k, i) - half >= R.boxMin(k) && p->optData_.controlPoints(k, i) + half <= R.boxMax(k);
-                }
-                if (!inside) continue;
-            }
+            // as in prologueOnDevice: a planner whose control points' box, grown by the node pool's reach, is not inside
+            // the region keeps to its own map
+            if (!boxInRegion(p->mapRegion_, p->optData_.controlPoints.data(), N, g.half)) continue;
 #endif
             const Rebound& r = pb.rb[pb.activeIdx[a]];
             hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
@@ -1815,7 +1776,7 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) || !dStatus.alloc((size_t)B * 4))
             return;
         if (vigo_rebound_reguide(lead->dev_, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
-  lead->notCheckRatio_, res, pool, lead->minHeight_,
+                                 lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
                                  lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, (vigo_rebound_state_t*)dState.p, pairCap,
                                  (int32_t*)dOff.p, (double*)dPv.p, nullptr, segCap, pointCap, (int32_t*)dPathSegOff.p, (int32_t*)dPathOff.p,
                                  (double*)dPath.p, (int32_t*)dStatus.p) != VIGO_OK) {
@@ -1830,11 +1791,9 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             return;
         const int S = pathSegOff[B];
         if (S < 0 || S > segCap || off.back() < 0 || off.back() > pairCap) return;
-        std::vector<int32_t> pathOff((size_t)S + 1, 0);
-        if (S > 0 && !dPathOff.download(pathOff.data(), pathOff.size() * 4)) return;
-        if (pathOff[S] < 0 || pathOff[S] > pointCap) return;
-        std::vector<double> path((size_t)pathOff[S] * 3), pv((size_t)off.back() * 6);
-        if ((!path.empty() && !dPath.download(path.data(), path.size() * 8)) || (!pv.empty() && !dPv.download(pv.data(), pv.size() * 8))) return;
+        std::vector<int32_t> pathOff;
+        std::vector<double> path, pv;
+        if (!downloadPathsAndPairs(S, pointCap, off.back(), dPathOff, dPath, dPv, pathOff, path, pv)) return;
         for (int b = 0; b < B; ++b) {
             if (status[b] != VIGO_REGUIDE_DONE && status[b] != VIGO_REGUIDE_SEARCH_FAILED && status[b] != VIGO_REGUIDE_NOT_REQUIRED) continue;
             bsplineTraj* p = active[who[b]];
@@ -1843,19 +1802,9 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             p->collisionSeg_.clear();
             for (int q = 0; q < st.n_seg; ++q) p->collisionSeg_.push_back({st.seg[2 * q], st.seg[2 * q + 1]});
             if (status[b] == VIGO_REGUIDE_DONE) {
-                p->astarPaths_.clear();
-                for (int k = pathSegOff[b]; k < pathSegOff[b + 1]; ++k) {
-                    p->astarPaths_.emplace_back();
-                    for (int q = pathOff[k]; q < pathOff[k + 1]; ++q)
-                        p->astarPaths_.back().push_back(Eigen::Vector3d(path[3 * (size_t)q], path[3 * (size_t)q + 1], path[3 * (size_t)q + 2]));
-                }
+                vigo_host::installPaths(p->astarPaths_, pathSegOff[b], pathSegOff[b + 1], pathOff.data(), path.data());
                 // the merged CSR holds a control point's old pairs first: what follows them is this step's
-                for (int i = 0; i < N; ++i)
-                    for (int g = off[(size_t)b * N + i] + (int)p->optData_.guidePoints[i].size(); g < off[(size_t)b * N + i + 1]; ++g) {
-                        const double* q = pv.data() + (size_t)g * 6;
-                        p->optData_.guidePoints[i].push_back(Eigen::Vector3d(q[0], q[1], q[2]));
-                        p->optData_.guideDirections[i].push_back(Eigen::Vector3d(q[3], q[4], q[5]));
-                    }
+                vigo_host::installGuides(p->optData_, N, off.data() + (size_t)b * N, pv.data(), true);
             }
             p->weightDistance_ = hb.weights[4 * (size_t)b + 0];
             p->weightDynamicObstacle_ = hb.weights[4 * (size_t)b + 3];
@@ -1865,7 +1814,7 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             ++nDecided;
         }
     });
-    g_reguideDeviceDecided += nDecided;
+    g_reguide.deviceDecided += nDecided;
 }
 
 // The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,
@@ -1917,7 +1866,7 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
             nHost += pb.rb[pb.activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
             nTwin += reguide != 0 && devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) ? 1 : 0;
         }
-        g_reguideHostRun += nTwin;
+        g_reguide.hostRun += nTwin;
         parallelFor(active.size(), [&](size_t a) {
             Rebound& r = pb.rb[pb.activeIdx[a]];
             bsplineTraj* p = active[a];

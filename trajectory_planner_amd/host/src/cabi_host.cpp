@@ -26,6 +26,41 @@
 #include "batchLayout.h"
 #include "workerPool.h"
 
+namespace {
+
+// a dense map of nx * ny * nz voxel bytes (vigo.h voxel contract)
+std::shared_ptr<mapManager::occMap> denseMap(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels) {
+    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
+    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    return map;
+}
+
+// cfg[6] of the entry points below: distance_threshold, min_height, max_height, max_obstacle_size[3]
+void setBsplineParams(ros::NodeHandle& nh, const double* cfg) {
+    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
+    nh.setParam("bspline_traj/min_height", cfg[1]);
+    nh.setParam("bspline_traj/max_height", cfg[2]);
+    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+}
+
+// the A* node pool of a planner with these parameters on a map of resolution res (bsplineTraj::setMap, BT.cpp:187-195)
+void nodePool(const double* cfg, double res, int pool[3]) {
+    for (int a = 0; a < 3; ++a) pool[a] = 2 * int(cfg[3 + a] / res);
+}
+
+// n_pts poses at the xyz triples q
+nav_msgs::Path pathFromXyz(const double* q, int n_pts) {
+    nav_msgs::Path path;
+    for (int i = 0; i < n_pts; ++i) {
+        geometry_msgs::PoseStamped ps;
+        ps.pose.position.x = q[3 * i]; ps.pose.position.y = q[3 * i + 1]; ps.pose.position.z = q[3 * i + 2];
+        path.poses.push_back(ps);
+    }
+    return path;
+}
+
+}  // namespace
+
 extern "C" {
 
 // returns 0 on success; info: nodes_header, nodes_parsed, bytes, occupied, free, nx, ny, nz; origin[3]; res
@@ -76,23 +111,12 @@ int vigo_host_pcd_load(const char* path, double res, const double* inflate, int 
 int vigo_host_bspline_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n_path, const double* path_xyz,
                                const double* cfg, double* ctrl_out, int* n_ctrl, int* seg_out, int* n_seg, int* guide_off, double* guide_out,
                                int* path_off, double* path_out, int cap) {
-    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(m->voxels().data(), vox, m->voxels().size());
     ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    setBsplineParams(nh, cfg);
     nh.setParam("bspline_traj/max_path_length", 1000.0);
     trajPlanner::bsplineTraj bt(nh);
-    bt.setMap(m);
-    nav_msgs::Path path;
-    for (int i = 0; i < n_path; ++i) {
-        geometry_msgs::PoseStamped ps;
-        ps.pose.position.x = path_xyz[3 * i]; ps.pose.position.y = path_xyz[3 * i + 1]; ps.pose.position.z = path_xyz[3 * i + 2];
-        path.poses.push_back(ps);
-    }
-    if (!bt.updatePath(path, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)))) return -1;
+    bt.setMap(denseMap(dims[0], dims[1], dims[2], origin, res, vox));
+    if (!bt.updatePath(pathFromXyz(path_xyz, n_path), std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)))) return -1;
     const Eigen::MatrixXd c = bt.getControlPoints();
     const int N = (int)c.cols();
     if (3 * N > cap) return -2;
@@ -129,8 +153,7 @@ int vigo_host_bspline_prologue(const unsigned char* vox, const int* dims, const 
 // (xyz triples, start side first), -1 when no path is found, -2 when path_out is too small
 int vigo_host_astar(const unsigned char* vox, const int* dims, const double* origin, double res, const int* pool, double min_height,
                     double max_height, double step, const double* start, const double* end, double* path_out, int cap) {
-    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(m->voxels().data(), vox, m->voxels().size());
+    auto m = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
     AStar a;
     a.initGridMap(m, Eigen::Vector3i(pool[0], pool[1], pool[2]), min_height, max_height);
     if (!a.AstarSearch(step, Eigen::Vector3d(start[0], start[1], start[2]), Eigen::Vector3d(end[0], end[1], end[2]))) return -1;
@@ -145,8 +168,7 @@ int vigo_host_astar(const unsigned char* vox, const int* dims, const double* ori
 // set's largest size, in-place score rewrites, nodes pushed (AStar::lastStats); filled whatever the outcome
 int vigo_host_astar_stats(const unsigned char* vox, const int* dims, const double* origin, double res, const int* pool, double min_height,
                           double max_height, double step, const double* start, const double* end, double* path_out, int cap, int* stats) {
-    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(m->voxels().data(), vox, m->voxels().size());
+    auto m = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
     AStar a;
     a.initGridMap(m, Eigen::Vector3i(pool[0], pool[1], pool[2]), min_height, max_height);
     const bool ok = a.AstarSearch(step, Eigen::Vector3d(start[0], start[1], start[2]), Eigen::Vector3d(end[0], end[1], end[2]));
@@ -198,17 +220,13 @@ int vigo_host_prologue_searches(const unsigned char* vox, const int* dims, const
                                 const double* cfg, int cap, int path_cap, double* ends, int* owner, int* len, double* path, int* stats,
                                 int* pool_out) {
     if (n < 0 || N < 7 || !ctrl) return -1;
-    auto m = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(m->voxels().data(), vox, m->voxels().size());
+    auto m = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
     ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    setBsplineParams(nh, cfg);
     trajPlanner::bsplineTraj bt(nh);
     bt.setMap(m);
-    const Eigen::Vector3i pool(2 * int(cfg[3] / res), 2 * int(cfg[4] / res), 2 * int(cfg[5] / res));   // setMap, BT.cpp:187-195
-    for (int a = 0; a < 3; ++a) pool_out[a] = pool(a);
+    nodePool(cfg, res, pool_out);
+    const Eigen::Vector3i pool(pool_out[0], pool_out[1], pool_out[2]);
     AStar a;
     a.initGridMap(m, pool, cfg[1], cfg[2]);
     int q = 0;
@@ -359,8 +377,7 @@ int vigo_host_minsnap_eval(int n_wp, const double* wp, int deg, int diff, int co
 // seconds of makePlan.  Needs the GPU (the box sweep of every sample runs there); -1 on failure.
 int vigo_host_poly_plan(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int n_wp,
                         const double* wp, const double* cfg, double* traj_out, int traj_cap, double* info_out) {
-    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
     ros::NodeHandle nh;
     nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
     nh.setParam("map_resolution", cfg[3]);
@@ -405,8 +422,7 @@ int vigo_host_poly_plan_batch_ex(int nx, int ny, int nz, const double* origin, d
                                  int traj_cap, double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out,
                                  double* secs_out) {
     if (P < 0 || !wp_off || !wp || !cfg || !mode || traj_cap < 0 || !traj_out || !info_out) return -1;
-    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
     auto make = [&](int i) {
         ros::NodeHandle nh;
         nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
@@ -491,12 +507,7 @@ static std::unique_ptr<trajPlanner::polyTrajOccMap> makeOccPlanner(const std::sh
     p->setMap(map);
     if (!std::isnan(cfg[14])) p->updateDesiredVel(cfg[14]);
     if (!std::isnan(cfg[15])) p->updateDesiredAcc(cfg[15]);
-    nav_msgs::Path path;
-    for (int i = 0; i < n_wp; ++i) {
-        geometry_msgs::PoseStamped ps;
-        ps.pose.position.x = wp[3 * i]; ps.pose.position.y = wp[3 * i + 1]; ps.pose.position.z = wp[3 * i + 2];
-        path.poses.push_back(ps);
-    }
+    const nav_msgs::Path path = pathFromXyz(wp, n_wp);
     if (conds) {
         std::vector<Eigen::Vector3d> c;
         for (int k = 0; k < 4; ++k) c.push_back(Eigen::Vector3d(conds[3 * k], conds[3 * k + 1], conds[3 * k + 2]));
@@ -505,12 +516,6 @@ static std::unique_ptr<trajPlanner::polyTrajOccMap> makeOccPlanner(const std::sh
         p->updatePath(path);
     }
     return p;
-}
-
-static std::shared_ptr<mapManager::occMap> denseMap(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels) {
-    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
-    return map;
 }
 
 static void copyXyz(const std::vector<trajPlanner::pose>& traj, int cap, double* out) {
@@ -610,10 +615,7 @@ int vigo_host_occ_seed_chain(int nx, int ny, int nz, const double* origin, doubl
     auto map = denseMap(nx, ny, nz, origin, res, voxels);
     const double vel = std::isnan(poly_cfg[3]) ? 1.0 : poly_cfg[3], acc = std::isnan(poly_cfg[4]) ? 1.0 : poly_cfg[4];
     ros::NodeHandle bnh;
-    bnh.setParam("bspline_traj/distance_threshold", bsp_cfg[0]);
-    bnh.setParam("bspline_traj/min_height", bsp_cfg[1]);
-    bnh.setParam("bspline_traj/max_height", bsp_cfg[2]);
-    bnh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{bsp_cfg[3], bsp_cfg[4], bsp_cfg[5]});
+    setBsplineParams(bnh, bsp_cfg);
     bnh.setParam("bspline_traj/max_path_length", 1000.0);
     const std::vector<Eigen::Vector3d> cond(4, Eigen::Vector3d(0, 0, 0));
     std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> polys;
@@ -698,12 +700,8 @@ struct PlannerPool {
 };
 
 void initPool(PlannerPool& pool, const unsigned char* vox, const int* dims, const double* origin, double res, const double* cfg) {
-    pool.map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(pool.map->voxels().data(), vox, pool.map->voxels().size());
-    pool.nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    pool.nh.setParam("bspline_traj/min_height", cfg[1]);
-    pool.nh.setParam("bspline_traj/max_height", cfg[2]);
-    pool.nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
+    pool.map = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
+    setBsplineParams(pool.nh, cfg);
     pool.nh.setParam("bspline_traj/max_path_length", 1000.0);
 }
 }  // namespace
@@ -736,14 +734,7 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
             for (int i = 0; i < N; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl_in[((size_t)t * N + i) * 3 + k];
             bt->setControlPoints(c);
         } else {
-            nav_msgs::Path path;
-            for (int i = 0; i < n_pts; ++i) {
-                geometry_msgs::PoseStamped ps;
-                const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
-                ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
-                path.poses.push_back(ps);
-            }
-            have = bt->updatePath(path, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0))) && bt->getControlPoints().cols() == N;
+            have = bt->updatePath(pathFromXyz(path_xyz + (size_t)t * n_pts * 3, n_pts), std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0))) && bt->getControlPoints().cols() == N;
         }
         if (!have) {
             status[t] = -1;
@@ -778,6 +769,103 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
 
 }  // extern "C"
 
+// ---- one driver behind the four vigo_host_plan_batch_* entry points: what they plan on, fresh planners per run, one
+// timed makePlanBatch, the results of a slot's last run.  What is left in each entry point is its slot schedule, the
+// switches a slot sets, and the totals it reads around the call.
+namespace {
+using trajPlanner::bsplineTraj;
+
+// built once per call: n_maps dense maps, a separate map object each (separate device groups): copies of vox, the odd
+// ones of vox2 when that is given; the planners' parameters (cfg as in vigo_host_bspline_prologue); the n input paths of
+// n_pts poses; zero start / end conditions
+struct BatchFixture {
+    std::vector<std::shared_ptr<mapManager::occMap>> maps;
+    ros::NodeHandle nh;
+    std::vector<nav_msgs::Path> in;
+    std::vector<std::vector<Eigen::Vector3d>> cond;
+    BatchFixture(const unsigned char* vox, const unsigned char* vox2, int n_maps, const int* dims, const double* origin, double res, const double* cfg,
+                 int n, int n_pts, const double* path_xyz)
+        : cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0))) {
+        for (int k = 0; k < n_maps; ++k) maps.push_back(denseMap(dims[0], dims[1], dims[2], origin, res, (vox2 && (k & 1)) ? vox2 : vox));
+        setBsplineParams(nh, cfg);
+        nh.setParam("bspline_traj/max_path_length", 1000.0);
+        nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
+        for (int t = 0; t < n; ++t) in.push_back(pathFromXyz(path_xyz + (size_t)t * n_pts * 3, n_pts));
+    }
+};
+
+// new planners for one run, planner t on map t % n_maps, through updatePathBatch
+struct FreshPlanners {
+    std::vector<std::unique_ptr<bsplineTraj>> owners;
+    std::vector<bsplineTraj*> ps;
+};
+FreshPlanners freshPlanners(const BatchFixture& fx) {
+    FreshPlanners fp;
+    for (size_t t = 0; t < fx.in.size(); ++t) {
+        fp.owners.emplace_back(new bsplineTraj(fx.nh));
+        fp.owners.back()->setMap(fx.maps[t % fx.maps.size()]);
+        fp.owners.back()->updateMaxVel(2.0);
+        fp.owners.back()->updateMaxAcc(3.0);
+        fp.ps.push_back(fp.owners.back().get());
+    }
+    bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
+    return fp;
+}
+
+// makePlanBatch's flags, its wall time in ms
+std::vector<bool> timedPlan(const std::vector<bsplineTraj*>& ps, double& ms) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<bool> planned = bsplineTraj::makePlanBatch(ps);
+    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return planned;
+}
+
+// The n planners' results as slot `slot` of the entry points' outputs: ok[n] makePlanBatch's flags, solver[n] the last
+// L-BFGS status, ncp[n], ctrl[n][ncp_cap][3] (zero padded by the caller), and each where its pointer is not NULL, per slot
+// concatenated in planner order: n_guides[n] + guides[cap][6] (point, direction), n_seg[n] + segs[cap][2]
+// (collisionSeg_), n_path_pts[n] + paths[cap][3] (astarPaths_' points).  Returns 0, -2 when ncp_cap or cap is too small.
+int dumpSlot(const std::vector<bsplineTraj*>& ps, const std::vector<bool>& planned, int slot, int ncp_cap, long long cap, int* ok, int* solver,
+             int* ncp, double* ctrl, int* n_guides, double* guides, int* n_seg, int* segs, int* n_path_pts, double* paths) {
+    const size_t n = ps.size();
+    long long g = 0, w = 0, sg = 0;
+    for (size_t t = 0; t < n; ++t) {
+        const size_t o = (size_t)slot * n + t;
+        const Eigen::MatrixXd c = ps[t]->getControlPoints();
+        ok[o] = planned[t] ? 1 : 0;
+        solver[o] = ps[t]->getLastSolverStatus();
+        ncp[o] = (int)c.cols();
+        if (c.cols() > ncp_cap) return -2;
+        for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
+        if (guides) {
+            std::vector<int32_t> off{0};
+            std::vector<double> pv;
+            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
+            n_guides[o] = (int)(pv.size() / 6);
+            if (g + (long long)pv.size() / 6 > cap) return -2;
+            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
+            g += (long long)pv.size() / 6;
+        }
+        if (segs) {
+            const auto& cs = ps[t]->getCollisionSeg();
+            n_seg[o] = (int)cs.size();
+            if (sg + (long long)cs.size() > cap) return -2;
+            for (const auto& s : cs) { segs[((size_t)slot * cap + sg) * 2] = s.first; segs[((size_t)slot * cap + sg) * 2 + 1] = s.second; ++sg; }
+        }
+        if (paths) {
+            int pts = 0;
+            for (const auto& path : ps[t]->getAstarPaths())
+                for (const auto& v : path) {
+                    if (w + 1 > cap) return -2;
+                    for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
+                    ++w; ++pts;
+                }
+            n_path_pts[o] = pts;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch, `reps` times with the prologue's A* on the
 // host (mode 0) and `reps` times with setDeviceAstar(true) (mode 1), alternating, fresh planners every time.  n_maps > 1:
 // planner t plans on map t % n_maps, a separate map object each (separate device groups): copies of vox, the odd ones
@@ -792,80 +880,23 @@ extern "C" int vigo_host_plan_batch_astar(const unsigned char* vox, const unsign
                                           const double* path_xyz, const double* cfg, int n_maps, int budget, int reps, int ncp_cap, long long cap,
                                           int* ok, int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, int* n_path_pts,
                                           double* paths, double* prologue_ms, double* total_ms, long long* counts) {
-    using trajPlanner::bsplineTraj;
     if (n < 1 || n_pts < 2 || n_maps < 1 || reps < 1 || !path_xyz) return -1;
-    std::vector<std::shared_ptr<mapManager::occMap>> maps;
-    for (int k = 0; k < n_maps; ++k) {
-        maps.push_back(std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res));
-        std::memcpy(maps.back()->voxels().data(), (vox2 && (k & 1)) ? vox2 : vox, maps.back()->voxels().size());
-    }
-    ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
-    nh.setParam("bspline_traj/max_path_length", 1000.0);
-    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
-    std::vector<nav_msgs::Path> in(n);
-    for (int t = 0; t < n; ++t)
-        for (int i = 0; i < n_pts; ++i) {
-            geometry_msgs::PoseStamped ps;
-            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
-            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
-            in[t].poses.push_back(ps);
-        }
-    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    const BatchFixture fx(vox, vox2, n_maps, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
     bsplineTraj::setDeviceAstarBudget(budget);
     for (int run = 0; run < 2 * reps && rc == 0; ++run) {
         const int mode = run & 1, rep = run / 2;
-        std::vector<std::unique_ptr<bsplineTraj>> owners;
-        std::vector<bsplineTraj*> ps;
-        for (int t = 0; t < n; ++t) {
-            owners.emplace_back(new bsplineTraj(nh));
-            owners.back()->setMap(maps[t % n_maps]);
-            owners.back()->updateMaxVel(2.0);
-            owners.back()->updateMaxAcc(3.0);
-            ps.push_back(owners.back().get());
-        }
-        bsplineTraj::updatePathBatch(ps, in, cond);
+        const FreshPlanners fp = freshPlanners(fx);
         bsplineTraj::setDeviceAstar(mode == 1);
         long long dev0, host0, dev1, host1;
         double pro0, pro1;
         bsplineTraj::deviceAstarTotals(&dev0, &host0, &pro0);
-        const auto t0 = std::chrono::steady_clock::now();
-        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
-        total_ms[mode * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[mode * reps + rep]);
         bsplineTraj::deviceAstarTotals(&dev1, &host1, &pro1);
         prologue_ms[mode * reps + rep] = (pro1 - pro0) * 1e3;
         if (mode == 1) { counts[0] = dev1 - dev0; counts[1] = host1 - host0; }
         bsplineTraj::setDeviceAstar(false);
-        if (rep + 1 < reps) continue;
-        long long g = 0, w = 0;
-        for (int t = 0; t < n && rc == 0; ++t) {
-            const size_t o = (size_t)mode * n + t;
-            const Eigen::MatrixXd c = ps[t]->getControlPoints();
-            ok[o] = res2[t] ? 1 : 0;
-            solver[o] = ps[t]->getLastSolverStatus();
-            ncp[o] = (int)c.cols();
-            if (c.cols() > ncp_cap) { rc = -2; break; }
-            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
-            std::vector<int32_t> off{0};
-            std::vector<double> pv;
-            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
-            n_guides[o] = (int)(pv.size() / 6);
-            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
-            std::memcpy(guides + ((size_t)mode * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
-            g += (long long)pv.size() / 6;
-            int pts = 0;
-            for (const auto& path : ps[t]->getAstarPaths())
-                for (const auto& v : path) {
-                    if (w + 1 > cap) { rc = -2; break; }
-                    for (int k = 0; k < 3; ++k) paths[((size_t)mode * cap + w) * 3 + k] = v(k);
-                    ++w; ++pts;
-                }
-            n_path_pts[o] = pts;
-        }
+        if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, mode, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, n_path_pts, paths);
     }
     bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
@@ -1442,39 +1473,12 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
                                 const double* path_xyz, const double* cfg, int astar, int reps, int ncp_cap, long long cap, int* ok,
                                 int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, double* prologue_ms, double* total_ms,
                                 long long* counts) {
-    using trajPlanner::bsplineTraj;
     if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg) return -1;
-    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), vox, map->voxels().size());
-    ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
-    nh.setParam("bspline_traj/max_path_length", 1000.0);
-    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
-    std::vector<nav_msgs::Path> in(n);
-    for (int t = 0; t < n; ++t)
-        for (int i = 0; i < n_pts; ++i) {
-            geometry_msgs::PoseStamped ps;
-            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
-            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
-            in[t].poses.push_back(ps);
-        }
-    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
     for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
         const int slot = run == 0 ? 0 : 1 + (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
-        std::vector<std::unique_ptr<bsplineTraj>> owners;
-        std::vector<bsplineTraj*> ps;
-        for (int t = 0; t < n; ++t) {
-            owners.emplace_back(new bsplineTraj(nh));
-            owners.back()->setMap(map);
-            owners.back()->updateMaxVel(2.0);
-            owners.back()->updateMaxAcc(3.0);
-            ps.push_back(owners.back().get());
-        }
-        bsplineTraj::updatePathBatch(ps, in, cond);
+        const FreshPlanners fp = freshPlanners(fx);
         if (run > 0) {
             bsplineTraj::setDeviceAstar(astar != 0);
             bsplineTraj::setDeviceGuides(slot - 1);
@@ -1483,9 +1487,7 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
         double pro0, pro1;
         bsplineTraj::deviceGuideTotals(&dev0, &host0);
         bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
-        const auto t0 = std::chrono::steady_clock::now();
-        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
-        total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
         bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
         bsplineTraj::deviceGuideTotals(&dev1, &host1);
         prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
@@ -1495,24 +1497,7 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
             bsplineTraj::setDeviceAstar(false);
             bsplineTraj::setDeviceGuides(0);
         }
-        if (run > 0 && rep + 1 < reps) continue;
-        long long g = 0;
-        for (int t = 0; t < n && rc == 0; ++t) {
-            const size_t o = (size_t)slot * n + t;
-            const Eigen::MatrixXd c = ps[t]->getControlPoints();
-            ok[o] = res2[t] ? 1 : 0;
-            solver[o] = ps[t]->getLastSolverStatus();
-            ncp[o] = (int)c.cols();
-            if (c.cols() > ncp_cap) { rc = -2; break; }
-            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
-            std::vector<int32_t> off{0};
-            std::vector<double> pv;
-            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
-            n_guides[o] = (int)(pv.size() / 6);
-            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
-            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
-            g += (long long)pv.size() / 6;
-        }
+        if (run == 0 || rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, nullptr, nullptr);
     }
     return rc;
 }
@@ -1533,41 +1518,14 @@ int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, con
                                   const double* path_xyz, const double* cfg, int slots, int budget, int reps, int ncp_cap, long long cap,
                                   int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts, double* paths,
                                   int* n_guides, double* guides, double* prologue_ms, double* chain_ms, double* total_ms, long long* counts) {
-    using trajPlanner::bsplineTraj;
     if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || (slots & 15) == 0) return -1;
-    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), vox, map->voxels().size());
-    ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
-    nh.setParam("bspline_traj/max_path_length", 1000.0);
-    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
-    std::vector<nav_msgs::Path> in(n);
-    for (int t = 0; t < n; ++t)
-        for (int i = 0; i < n_pts; ++i) {
-            geometry_msgs::PoseStamped ps;
-            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
-            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
-            in[t].poses.push_back(ps);
-        }
-    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
     bsplineTraj::setDeviceAstarBudget(budget);
     for (int rep = 0; rep < reps && rc == 0; ++rep)
         for (int slot = 0; slot < 4 && rc == 0; ++slot) {
             if (!((slots >> slot) & 1)) continue;
-            std::vector<std::unique_ptr<bsplineTraj>> owners;
-            std::vector<bsplineTraj*> ps;
-            for (int t = 0; t < n; ++t) {
-                owners.emplace_back(new bsplineTraj(nh));
-                owners.back()->setMap(map);
-                owners.back()->updateMaxVel(2.0);
-                owners.back()->updateMaxAcc(3.0);
-                ps.push_back(owners.back().get());
-            }
-            bsplineTraj::updatePathBatch(ps, in, cond);
+            const FreshPlanners fp = freshPlanners(fx);
             bsplineTraj::setDevicePrologue(slot == 1);
             bsplineTraj::setDeviceAstar(slot == 2);
             bsplineTraj::setDeviceGuides(slot == 0 || slot == 2 ? 1 : 0);
@@ -1575,9 +1533,7 @@ int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, con
             double pro0, pro1, ch0, ch1;
             bsplineTraj::devicePrologueTotals(&dev0, &host0, &ch0);
             bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
-            const auto t0 = std::chrono::steady_clock::now();
-            const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
-            total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
             bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
             bsplineTraj::devicePrologueTotals(&dev1, &host1, &ch1);
             prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
@@ -1587,36 +1543,7 @@ int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, con
             bsplineTraj::setDevicePrologue(false);
             bsplineTraj::setDeviceAstar(false);
             bsplineTraj::setDeviceGuides(0);
-            if (rep + 1 < reps) continue;
-            long long g = 0, w = 0, sg = 0;
-            for (int t = 0; t < n && rc == 0; ++t) {
-                const size_t o = (size_t)slot * n + t;
-                const Eigen::MatrixXd c = ps[t]->getControlPoints();
-                ok[o] = res2[t] ? 1 : 0;
-                solver[o] = ps[t]->getLastSolverStatus();
-                ncp[o] = (int)c.cols();
-                if (c.cols() > ncp_cap) { rc = -2; break; }
-                for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
-                std::vector<int32_t> off{0};
-                std::vector<double> pv;
-                vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
-                n_guides[o] = (int)(pv.size() / 6);
-                if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
-                std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
-                g += (long long)pv.size() / 6;
-                const auto& cs = ps[t]->getCollisionSeg();
-                n_seg[o] = (int)cs.size();
-                if (sg + (long long)cs.size() > cap) { rc = -2; break; }
-                for (const auto& s : cs) { segs[((size_t)slot * cap + sg) * 2] = s.first; segs[((size_t)slot * cap + sg) * 2 + 1] = s.second; ++sg; }
-                int pts = 0;
-                for (const auto& path : ps[t]->getAstarPaths())
-                    for (const auto& v : path) {
-                        if (w + 1 > cap) { rc = -2; break; }
-                        for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
-                        ++w; ++pts;
-                    }
-                n_path_pts[o] = pts;
-            }
+            if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
         }
     bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
@@ -1638,26 +1565,8 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
                                  const double* path_xyz, const double* cfg, int slots, int budget, int reps, const int* caps, int ncp_cap,
                                  long long cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts,
                                  double* paths, int* n_guides, double* guides, double* total_ms, long long* counts, long long* twin) {
-    using trajPlanner::bsplineTraj;
     if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || !caps || !twin) return -1;
-    auto map = std::make_shared<mapManager::occMap>(dims[0], dims[1], dims[2], Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), vox, map->voxels().size());
-    ros::NodeHandle nh;
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
-    nh.setParam("bspline_traj/max_path_length", 1000.0);
-    nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
-    std::vector<nav_msgs::Path> in(n);
-    for (int t = 0; t < n; ++t)
-        for (int i = 0; i < n_pts; ++i) {
-            geometry_msgs::PoseStamped ps;
-            const double* q = path_xyz + ((size_t)t * n_pts + i) * 3;
-            ps.pose.position.x = q[0]; ps.pose.position.y = q[1]; ps.pose.position.z = q[2];
-            in[t].poses.push_back(ps);
-        }
-    const std::vector<std::vector<Eigen::Vector3d>> cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
     twin[0] = twin[1] = 0;
     bsplineTraj::setDeviceAstarBudget(budget);
@@ -1665,24 +1574,13 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
         const int slot = run == 0 ? 3 : (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
         if (run > 0 && !((slots >> slot) & 1)) continue;
         const bool last = run == 0 || rep + 1 == reps;
-        std::vector<std::unique_ptr<bsplineTraj>> owners;
-        std::vector<bsplineTraj*> ps;
-        for (int t = 0; t < n; ++t) {
-            owners.emplace_back(new bsplineTraj(nh));
-            owners.back()->setMap(map);
-            owners.back()->updateMaxVel(2.0);
-            owners.back()->updateMaxAcc(3.0);
-            ps.push_back(owners.back().get());
-        }
-        bsplineTraj::updatePathBatch(ps, in, cond);
+        const FreshPlanners fp = freshPlanners(fx);
         std::vector<bsplineTraj::ReguideStepRecord> log;
         if (run > 0) bsplineTraj::setDeviceReguide(2 - slot);
         if (slot == 0 && last) bsplineTraj::setReguideStepLog(&log);
         long long dev0, host0, dev1, host1;
         bsplineTraj::deviceReguideTotals(&dev0, &host0);
-        const auto t0 = std::chrono::steady_clock::now();
-        const std::vector<bool> res2 = bsplineTraj::makePlanBatch(ps);
-        total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
         bsplineTraj::deviceReguideTotals(&dev1, &host1);
         bsplineTraj::setReguideStepLog(nullptr);
         if (run > 0) bsplineTraj::setDeviceReguide(0);
@@ -1691,7 +1589,8 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
         counts[2 * slot + 1] = host1 - host0;
         // the logged steps, one by one (a trajectory's result does not depend on its batch), by the kernels' twin
         twin[0] += (long long)log.size();
-        const int pool[3] = {2 * int(cfg[3] / res), 2 * int(cfg[4] / res), 2 * int(cfg[5] / res)};
+        int pool[3];
+        nodePool(cfg, res, pool);
         std::vector<int> deferred(log.size(), 0);
         vigo_host::parallelFor(log.size(), [&](size_t k) {
             bsplineTraj::ReguideStepRecord& R = log[k];
@@ -1715,35 +1614,7 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
             deferred[k] = (r != 0 || status == VIGO_REGUIDE_DEFERRED) ? 1 : 0;
         });
         for (size_t k = 0; k < log.size(); ++k) twin[1] += deferred[k] ? 0 : 1;
-        long long g = 0, w = 0, sg = 0;
-        for (int t = 0; t < n && rc == 0; ++t) {
-            const size_t o = (size_t)slot * n + t;
-            const Eigen::MatrixXd c = ps[t]->getControlPoints();
-            ok[o] = res2[t] ? 1 : 0;
-            solver[o] = ps[t]->getLastSolverStatus();
-            ncp[o] = (int)c.cols();
-            if (c.cols() > ncp_cap) { rc = -2; break; }
-            for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
-            std::vector<int32_t> off{0};
-            std::vector<double> pv;
-            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
-            n_guides[o] = (int)(pv.size() / 6);
-            if (g + (long long)pv.size() / 6 > cap) { rc = -2; break; }
-            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
-            g += (long long)pv.size() / 6;
-            const auto& cs = ps[t]->getCollisionSeg();
-            n_seg[o] = (int)cs.size();
-            if (sg + (long long)cs.size() > cap) { rc = -2; break; }
-            for (const auto& sgm : cs) { segs[((size_t)slot * cap + sg) * 2] = sgm.first; segs[((size_t)slot * cap + sg) * 2 + 1] = sgm.second; ++sg; }
-            int pts = 0;
-            for (const auto& path : ps[t]->getAstarPaths())
-                for (const auto& v : path) {
-                    if (w + 1 > cap) { rc = -2; break; }
-                    for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
-                    ++w; ++pts;
-                }
-            n_path_pts[o] = pts;
-        }
+        rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
     }
     bsplineTraj::setDeviceReguide(0);
     bsplineTraj::setReguideStepLog(nullptr);
@@ -1766,8 +1637,7 @@ int vigo_host_switches() {
 // failure; dims_out receives the rasterised grid's extents.
 extern "C" long long vigo_host_rasterise_check(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels,
                                                const double* box_min, const double* box_max, int* dims_out) {
-    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
     trajPlanner::mapRegion region;
     region.set = true;
     region.boxMin = Eigen::Vector3d(box_min[0], box_min[1], box_min[2]);

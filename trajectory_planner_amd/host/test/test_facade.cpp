@@ -16,6 +16,8 @@
 #include <set>
 #include <thread>
 
+#include "../src/batchLayout.h"
+
 using trajPlanner::bsplineTraj;
 
 static int fails = 0;
@@ -69,6 +71,34 @@ static nav_msgs::Path straight(double x0, double y0, double x1, double y1, doubl
 }
 
 int main() {
+    // ---- the facades' batch layouts (host only): what installGuides puts into a planner, appendGuides reads back ----
+    {
+        const int N = 5;
+        const std::vector<int32_t> off{0, 2, 2, 3, 3, 4};          // control points 1 and 3 have no pairs
+        std::vector<double> pv(6 * 4);
+        for (size_t q = 0; q < pv.size(); ++q) pv[q] = 0.25 * (double)q - 1.0;
+        trajPlanner::optData od;
+        od.guidePoints.resize(N);
+        od.guideDirections.resize(N);
+        vigo_host::installGuides(od, N, off.data(), pv.data());
+        std::vector<int32_t> off2{0};
+        std::vector<double> pv2;
+        vigo_host::appendGuides(od, N, off2, pv2);
+        CHECK(off2 == off && pv2 == pv, "installGuides is appendGuides' inverse");
+        // a merged CSR, the held pairs first: one new pair for control points 1 and 2, only those are appended
+        const std::vector<int32_t> offM{0, 2, 3, 5, 5, 6};
+        std::vector<double> pvM(pv.begin(), pv.begin() + 12);
+        for (int q = 0; q < 6; ++q) pvM.push_back(7.0 + q);
+        pvM.insert(pvM.end(), pv.begin() + 12, pv.begin() + 18);
+        for (int q = 0; q < 6; ++q) pvM.push_back(-7.0 - q);
+        pvM.insert(pvM.end(), pv.begin() + 18, pv.end());
+        vigo_host::installGuides(od, N, offM.data(), pvM.data(), true);
+        off2.assign(1, 0);
+        pv2.clear();
+        vigo_host::appendGuides(od, N, off2, pv2);
+        CHECK(off2 == offM && pv2 == pvM, "installGuides with skipHeld appends only what follows the held pairs");
+    }
+
     auto map = makeMap();
     const std::vector<Eigen::Vector3d> cond(4, Eigen::Vector3d(0, 0, 0));
 
