@@ -127,7 +127,8 @@ int vigo_get_params(vigo_handle_t h, vigo_params_t* p);
 int vigo_set_precision(vigo_handle_t h, int vigo_precision);
 /* Text of the last HIP/runtime failure on this handle (never NULL). */
 const char* vigo_last_error(vigo_handle_t h);
-/* Library/ABI version, and whether the code object was built for gfx950. */
+/* Library/ABI version (raised when entry points are added; nothing was removed or changed so far: 4 adds
+ * vigo_build_esdf / vigo_esdf_from_voxels_host), and whether the code object was built for gfx950. */
 int vigo_abi_version(void);
 const char* vigo_build_arch(void);
 /* "solver:<12 hex> all:<12 hex>": digests of the library's compiled code (host code and gfx950 code objects; the first
@@ -733,6 +734,36 @@ int vigo_esdf_query(vigo_handle_t h, int64_t Q, const double* pts,
  * x then y then z, gradient differences * inv_res.  Own definition (no reference counterpart); oracle twin
  * vgo_esdf_query_f32.  Differs from the fp64 entry by fp32 rounding only (~1e-6 relative). */
 int vigo_esdf_query_f32(vigo_handle_t h, int64_t Q, const float* pts, float* out_dist_grad);
+
+/* ---- ESDF build (no reference counterpart) --------------------------
+ * vigo_build_esdf builds the signed Euclidean distance field of the handle's current voxel snapshot on the device and
+ * installs it as the handle's ESDF (what vigo_set_esdf does with a finished lattice): dims, origin and res are the
+ * grid's, any earlier field is replaced, vigo_esdf_query* read it from then on.  Stream-ordered on the handle's stream;
+ * the workspace (8 bytes per voxel) belongs to the handle, grows on demand and is freed by vigo_destroy.
+ *   plane            0 = inflated-occupied, 2 = occupied: the SITES are the voxels whose bit is set in that plane of
+ *                    the snapshot; unknown_is_site != 0 ORs the unknown plane in
+ *   out_lattice_dev  float[nx][ny][nz] (row-major, z fastest) or NULL: the same field as a plain lattice
+ * The transform is the EXACT Euclidean distance transform in integer voxel units (csrc/vigo_esdf_core.hpp):
+ *   d2_site[v] = min dx^2 + dy^2 + dz^2 from voxel v to a site (0 on a site), d2_free[v] the same to a non-site voxel
+ *   of the lattice (0 on a non-site);
+ *   value[v]   = (float)((sqrt((double)d2_site) - sqrt((double)d2_free)) * res), every operation rounded once:
+ *                positive outside, negative inside, sampled at voxel centres (u = (p - origin) / res - 0.5 of the query).
+ * Padding rule: the bits of a z-row's last word beyond nz belong to neither the sites nor their complement — no distance
+ * is ever measured to them, whatever a vigo_set_grid_packed caller left there.
+ * Empty-set rule: where a set is empty (no site at all, or no non-site voxel), its squared distance is
+ * nx^2 + ny^2 + nz^2 everywhere: finite, and larger than anything attainable inside the lattice.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle, a plane other than 0 or 2, a grid with an axis < 2; VIGO_ERR_NO_GRID
+ * before any vigo_set_grid*; VIGO_ERR_UNSUPPORTED for nx^2 + ny^2 + nz^2 > 2^30 (int32 squared distances) or more than
+ * 2^33 voxels; VIGO_ERR_HIP with vigo_last_error(). */
+int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_lattice_dev);
+/* The host twin: the same rule compiled for the CPU, on a byte grid uint8[nx][ny][nz] (bit `plane` — and bit 1 with
+ * unknown_is_site — marks a site) -> out_lattice_host float[nx][ny][nz].  Host-only like vigo_accumulated_time (no GPU,
+ * no handle); bit-identical to vigo_build_esdf's lattice for the same voxels.  VIGO_ERR_INVALID_ARG for a NULL pointer,
+ * a plane other than 0 or 2, a dimension < 2, res not finite or <= 0; VIGO_ERR_UNSUPPORTED for the same two size
+ * limits, and for a lattice whose working memory (8 bytes per voxel and the packed words) the host cannot allocate.
+ * Nothing is written on an error. */
+int vigo_esdf_from_voxels_host(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site,
+                               double res, float* out_lattice_host);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host-side sources (no HIP) under AddressSanitizer + UBSan: the .bt reader on every map given on the command
-# line, 300 random min-snap QPs (with and without corridors, feasible and infeasible), B-spline fits/evaluations, A* searches, pwlTraj plans, soft-constraint QPs.
+# line, 300 random min-snap QPs (with and without corridors, feasible and infeasible), B-spline fits/evaluations, A* searches, pwlTraj plans, soft-constraint QPs, the ESDF build's host twin on hostile sizes.
 #   bash tools/sanitize_host.sh /root/reference/map/*.bt
 # (GPU sanitizers are not available on the pool; the device code is covered by the parity tests and the fuzz sweep.)
 set -e

@@ -3,6 +3,7 @@
 #include <trajectory_planner/bspline.h>
 #include <trajectory_planner/path_search/astarOcc.h>
 #include <trajectory_planner/piecewiseLinearTraj.h>
+#include "../trajectory_planner_amd/csrc/vigo_esdf_core.hpp"   // the ESDF build's host twin (header-only, no HIP)
 #include <cmath>
 #include <cstdio>
 #include <random>
@@ -131,6 +132,38 @@ int main(int argc, char** argv) {
             if (!sv.solve()) ++fails;
             (void)sv.getVel(0.3); (void)sv.getAcc(0.3); (void)sv.getPos(0.3);
         }
+    }
+    // the ESDF build's host twin (vigo_esdf_from_voxels_host) on hostile sizes: the minimum, one bit into a second word,
+    // exact words, long thin axes, every fill incl. the empty sets; refused arguments must not touch the buffers
+    {
+        const int shapes[][3] = {{2, 2, 2}, {5, 7, 33}, {3, 4, 64}, {9, 70, 31}, {2, 3, 300}, {3, 300, 2}, {300, 2, 3}, {2, 2, 97}, {17, 2, 32}};
+        for (const auto& sh : shapes) {
+            const size_t n = (size_t)sh[0] * sh[1] * sh[2];
+            for (int fill = 0; fill < 5; ++fill) {
+                std::vector<uint8_t> vox(n, 0);
+                const double frac[5] = {0.0, 1.0, 0.02, 0.5, 0.98};
+                for (size_t i = 0; i < n; ++i) vox[i] = (uint8_t)(((U(rng) + 1) / 2 < frac[fill] ? 4 : 0) | ((U(rng) > 0.8) ? 2 : 0) | ((U(rng) > 0.5) ? 1 : 0));
+                std::vector<float> out(n, 0.0f);
+                for (int plane = 0; plane <= 2; plane += 2)
+                    for (int unk = 0; unk <= 1; ++unk) {
+                        if (vigo::esdf_from_voxels(sh[0], sh[1], sh[2], vox.data(), plane, unk, 0.1, out.data()) != 0) ++fails;
+                        for (size_t i = 0; i < n; ++i) {
+                            const bool site = (vox[i] & ((1u << plane) | (unk ? 2u : 0u))) != 0;
+                            if (!std::isfinite(out[i]) || out[i] == 0.0f || (out[i] < 0) != site) { ++fails; break; }
+                        }
+                    }
+            }
+        }
+        std::vector<uint8_t> vox(8, 4);
+        std::vector<float> out(8, 7.0f);
+        if (vigo::esdf_from_voxels(2, 2, 2, vox.data(), 1, 0, 0.1, out.data()) != -1) ++fails;
+        if (vigo::esdf_from_voxels(1, 2, 2, vox.data(), 2, 0, 0.1, out.data()) != -1) ++fails;
+        if (vigo::esdf_from_voxels(2, 2, 2, nullptr, 2, 0, 0.1, out.data()) != -1) ++fails;
+        if (vigo::esdf_from_voxels(2, 2, 2, vox.data(), 2, 0, 0.1, nullptr) != -1) ++fails;
+        if (vigo::esdf_from_voxels(2, 40000, 2, vox.data(), 2, 0, 0.1, out.data()) != -6) ++fails;
+        if (vigo::esdf_from_voxels(16384, 16384, 16384, vox.data(), 2, 0, 0.1, out.data()) != -6) ++fails;   // > 2^33 voxels
+        if (vigo::esdf_from_voxels(2, 2, 2, vox.data(), 2, 0, std::nan(""), out.data()) != -1) ++fails;
+        for (float f : out) if (f != 7.0f) ++fails;
     }
     std::printf("%s\n", fails ? "FAILED" : "sanitizer run complete, no failures");
     return fails;

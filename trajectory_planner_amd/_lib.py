@@ -104,6 +104,8 @@ PROTOTYPES = {
     "vigo_set_esdf": (_i, [_vp, _i, _i, _i, _d3, _d, _vp]),
     "vigo_esdf_query": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "vigo_esdf_query_f32": (_i, [_vp, _i64, _vp, _vp]),
+    "vigo_build_esdf": (_i, [_vp, _i, _i, _vp]),
+    "vigo_esdf_from_voxels_host": (_i, [_i, _i, _i, _vp, _i, _i, _d, _vp]),
 }
 
 _lib = None

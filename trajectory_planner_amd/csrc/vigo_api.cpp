@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "vigo_esdf_core.hpp"
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_internal.hpp"
@@ -168,11 +169,33 @@ int ensure_grid_storage(vigo_handle_t h, int nx, int ny, int nz) {
     return VIGO_OK;
 }
 
+// the lattice (row-major float[nx][ny][nz], device) becomes the handle's ESDF: one 128-B line per cell group
+int install_esdf(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const float* dist_dev) {
+    size_t bytes = vigo::esdf_bricked_floats(nx, ny, nz) * sizeof(float);   // 3.56x the lattice (one line per cell group)
+    if (bytes > h->esdf_capacity) {
+        if (h->esdf) (void)hipFree(h->esdf);
+        h->esdf = nullptr;
+        h->esdf_capacity = 0;
+        h->has_esdf = false;                 // the earlier field is gone: if the allocation fails, queries say so
+        h->esdf_view.dist = nullptr;
+        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->esdf), bytes));
+        h->esdf_capacity = bytes;
+    }
+    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_brick(h->stream, nx, ny, nz, dist_dev, h->esdf));   // row-major -> one line per cell group
+    h->esdf_view.dist = h->esdf;
+    h->esdf_view.nx = nx; h->esdf_view.ny = ny; h->esdf_view.nz = nz;
+    h->esdf_view.nby = vigo::esdf_bricks_along(ny); h->esdf_view.nbz = vigo::esdf_bricks_along(nz);
+    h->esdf_view.res = res;
+    for (int a = 0; a < 3; ++a) h->esdf_view.origin[a] = origin[a];
+    h->has_esdf = true;
+    return VIGO_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int vigo_abi_version(void) { return 3; }
+int vigo_abi_version(void) { return 4; }
 double vigo_accumulated_time(double delT, int64_t k) { return vigo::accumulated_time(delT, k); }
 double vigo_clock_table_time(double delT, int64_t k_last, int64_t k) {
     if (k_last < 0 || k < 0 || k > k_last || k_last > (int64_t)1 << 30) return NAN;
@@ -278,6 +301,7 @@ int vigo_destroy(vigo_handle_t h) {
     (void)hipSetDevice(h->device);
     if (h->grid_planes) (void)hipFree(h->grid_planes);
     if (h->esdf) (void)hipFree(h->esdf);
+    if (h->esdf_ws) (void)hipFree(h->esdf_ws);
     if (h->fit_pinvT) (void)hipFree(h->fit_pinvT);
     if (h->times_dev) (void)hipFree(h->times_dev);
     if (h->scratch) (void)hipFree(h->scratch);
@@ -1062,22 +1086,35 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
 int vigo_set_esdf(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const float* dist_dev) {
     if (!h || !dist_dev || !origin || nx < 2 || ny < 2 || nz < 2 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_esdf: bad argument");
     if ((long long)nx * ny * nz > (1LL << 33)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_esdf: lattice too large");
-    size_t bytes = vigo::esdf_bricked_floats(nx, ny, nz) * sizeof(float);   // 3.56x the lattice (one line per cell group)
-    if (bytes > h->esdf_capacity) {
-        if (h->esdf) (void)hipFree(h->esdf);
-        h->esdf = nullptr;
-        h->esdf_capacity = 0;
-        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->esdf), bytes));
-        h->esdf_capacity = bytes;
+    return install_esdf(h, nx, ny, nz, origin, res, dist_dev);
+}
+
+int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_lattice_dev) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_build_esdf before vigo_set_grid");
+    const GridView& g = h->grid;
+    if ((plane != 0 && plane != 2) || g.nx < 2 || g.ny < 2 || g.nz < 2)
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_build_esdf: plane is not 0 or 2, or a grid axis < 2");
+    if (vigo::esdf_empty_d2(g.nx, g.ny, g.nz) == 0)
+        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_build_esdf: nx^2 + ny^2 + nz^2 > 2^30 or more than 2^33 voxels");
+    const size_t bytes = vigo::esdf_build_ws_bytes(g.nx, g.ny, g.nz);
+    if (bytes > h->esdf_ws_bytes) {
+        if (h->esdf_ws) (void)hipFree(h->esdf_ws);
+        h->esdf_ws = nullptr;
+        h->esdf_ws_bytes = 0;
+        VIGO_HIP(h, hipMalloc(&h->esdf_ws, bytes));
+        h->esdf_ws_bytes = bytes;
     }
-    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_brick(h->stream, nx, ny, nz, dist_dev, h->esdf));   // row-major -> one line per cell group
-    h->esdf_view.dist = h->esdf;
-    h->esdf_view.nx = nx; h->esdf_view.ny = ny; h->esdf_view.nz = nz;
-    h->esdf_view.nby = vigo::esdf_bricks_along(ny); h->esdf_view.nbz = vigo::esdf_bricks_along(nz);
-    h->esdf_view.res = res;
-    for (int a = 0; a < 3; ++a) h->esdf_view.origin[a] = origin[a];
-    h->has_esdf = true;
-    return VIGO_OK;
+    int32_t* a = static_cast<int32_t*>(h->esdf_ws);
+    int32_t* b = a + (size_t)g.nx * g.ny * g.nz;
+    float* lattice = out_lattice_dev ? out_lattice_dev : reinterpret_cast<float*>(a);
+    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_build(h->stream, g, plane, unknown_is_site != 0, a, b, lattice));
+    return install_esdf(h, g.nx, g.ny, g.nz, g.origin, g.res, lattice);
+}
+
+int vigo_esdf_from_voxels_host(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site, double res,
+                               float* out_lattice_host) {
+    return vigo::esdf_from_voxels(nx, ny, nz, voxels_host, plane, unknown_is_site, res, out_lattice_host);
 }
 
 int vigo_esdf_query(vigo_handle_t h, int64_t Q, const double* pts, double* out_dist, double* out_grad) {

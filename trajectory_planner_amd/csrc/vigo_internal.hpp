@@ -177,6 +177,10 @@ int launch_esdf_query(hipStream_t s, const EsdfView& e, int64_t Q, const double*
 int launch_esdf_query_f32(hipStream_t s, const EsdfView& e, int64_t Q, const float* pts, float* out4);
 // row-major [nx][ny][nz] -> the bricked layout of EsdfView
 int launch_esdf_brick(hipStream_t s, int nx, int ny, int nz, const float* src, float* dst);
+// the ESDF build (vigo_esdf_build.hip): the snapshot's plane (0 or 2, OR the unknown plane) -> the row-major float
+// lattice; a, b: the two int32 buffers of esdf_build_ws_bytes, lattice may be a
+size_t esdf_build_ws_bytes(int nx, int ny, int nz);
+int launch_esdf_build(hipStream_t s, const GridView& g, int plane, int unknown_is_site, int32_t* a, int32_t* b, float* lattice);
 // batched B-spline fit (vigo_fit.hip): one-off device factorisation per (K, ts), then the fit
 size_t fit_work_doubles(int K);
 size_t fit_pinv_doubles(int K);
@@ -323,6 +327,9 @@ struct vigo_context {
     size_t esdf_capacity = 0;
     vigo::EsdfView esdf_view{};
     bool has_esdf = false;
+    // vigo_build_esdf: the passes' two int32 buffers (vigo_esdf_build.hip), grown on demand
+    void* esdf_ws = nullptr;
+    size_t esdf_ws_bytes = 0;
     // least-squares operator of the B-spline fit for (fit_K, fit_ts), transposed (vigo_fit.hip)
     double* fit_pinvT = nullptr;
     size_t fit_capacity = 0;   // doubles

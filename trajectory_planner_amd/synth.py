@@ -279,6 +279,22 @@ def edt_esdf(world: World):
     return np.ascontiguousarray(d.astype(np.float32)), np.array(world.origin, dtype=np.float64)
 
 
+def host_esdf(world: World, plane: int = 2, unknown_is_site: bool = False):
+    """The same field by the library's host twin of the device build (vigo_esdf_from_voxels_host: the exact integer
+    EDT of csrc/vigo_esdf_core.hpp compiled for the CPU; no GPU).  plane 2 = occupied, 0 = inflated-occupied.
+    Returns (float32 [nx,ny,nz], origin); equals edt_esdf bit for bit on plane 2."""
+    import ctypes as C
+    from . import _lib
+    vox = np.ascontiguousarray(world.voxels, dtype=np.uint8)
+    nx, ny, nz = vox.shape
+    out = np.empty((nx, ny, nz), dtype=np.float32)
+    rc = _lib.load().vigo_esdf_from_voxels_host(nx, ny, nz, vox.ctypes.data_as(C.c_void_p), int(plane), 1 if unknown_is_site else 0,
+                                                float(world.res), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"vigo_esdf_from_voxels_host failed ({rc})")
+    return out, np.array(world.origin, dtype=np.float64)
+
+
 # ---- guides from the planner's own host pipeline (product code: libtrajectory_planner_vigo.so) ---------------------------
 # cfg/bspline_interactive/bspline_planner_param.yaml: distance_threshold, min_height, max_height, max_obstacle_size
 PIPELINE_CFG = np.array([0.5, 0.7, 1.3, 5.0, 5.0, 3.0])

@@ -582,6 +582,19 @@ class Vigo:
         self._check(self._lib.vigo_set_esdf(self._h, nx, ny, nz, (C.c_double * 3)(*origin), float(res),
                                             _ptr(dist, torch.float32, "dist", self.device)), "vigo_set_esdf")
 
+    def build_esdf(self, plane: int = 2, unknown_is_site: bool = False, return_lattice: bool = False):
+        """vigo_build_esdf: the signed Euclidean distance field of the current snapshot (sites: plane 2 = occupied or
+        0 = inflated-occupied, with the unknown voxels when unknown_is_site), built on the device and installed as the
+        handle's ESDF.  return_lattice: also the row-major float32 [nx,ny,nz] lattice."""
+        lattice = None
+        if return_lattice:
+            if self._grid_meta is None:
+                raise VigoError("build_esdf(return_lattice=True) before set_grid")
+            lattice = torch.empty(self._grid_meta[:3], dtype=torch.float32, device=self.device)
+        self._check(self._lib.vigo_build_esdf(self._h, int(plane), 1 if unknown_is_site else 0,
+                                              None if lattice is None else C.c_void_p(lattice.data_ptr())), "vigo_build_esdf")
+        return lattice
+
     def esdf_query(self, pts: torch.Tensor):
         _shape(pts, (None, 3), "pts")
         q = pts.shape[0]
