@@ -10,9 +10,11 @@
 #include "vigo_esdf_core.hpp"
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
-#include "vigo_internal.hpp"
+#include "vigo_handle.hpp"
 #include "vigo_traj_runs.hpp"
+#include "vigo_ws_layout.hpp"
 
+using vigo::DevBuffer;
 using vigo::DevConst;
 using vigo::GridView;
 using vigo::SolveArgs;
@@ -38,15 +40,50 @@ int fail(vigo_handle_t h, int code, const char* what, hipError_t e = hipSuccess)
         hipError_t e_ = (call);                                                \
         if (e_ != hipSuccess) return fail((h), VIGO_ERR_HIP, #call, e_);       \
     } while (0)
+#define VIGO_TRY(call)                                                         \
+    do {                                                                       \
+        const int rc_ = (call);                                                \
+        if (rc_ != VIGO_OK) return rc_;                                        \
+    } while (0)
 
-int ensure_scratch(vigo_handle_t h, size_t bytes) {
-    if (bytes <= h->scratch_bytes) return VIGO_OK;
-    if (h->scratch) (void)hipFree(h->scratch);
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    VIGO_HIP(h, hipMalloc(&h->scratch, want));
-    h->scratch_bytes = want;
+// Buffer `id` of the handle holds at least `need` bytes afterwards; when it has to grow, to `alloc` bytes (contents are
+// not kept).  A failed allocation leaves it empty.  Callers whose cache lives in the buffer invalidate it first.
+int reserve(vigo_handle_t h, vigo::BufId id, size_t need, size_t alloc) {
+    static const char* const what[] = {
+        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(times)", "hipMalloc(scratch)",
+        "hipMalloc(paths_ws[0])", "hipMalloc(paths_ws[1])", "hipMalloc(reguide_ws[0])", "hipMalloc(reguide_ws[1])",
+        "hipMalloc(reguide_ws[2])", "hipMalloc(rebound)"};
+    static_assert(sizeof(what) / sizeof(what[0]) == vigo::kBufCount, "one name per BufId, in its order");
+    DevBuffer& b = h->buf[id];
+    if (need <= b.bytes) return VIGO_OK;
+    if (b.ptr) (void)hipFree(b.ptr);
+    b = DevBuffer{};
+    (void)hipGetLastError();
+    const hipError_t e = hipMalloc(&b.ptr, alloc);
+    if (e != hipSuccess) {
+        b.ptr = nullptr;
+        return fail(h, VIGO_ERR_HIP, what[id], e);
+    }
+    b.bytes = alloc;
+    return VIGO_OK;
+}
+// the per-call workspaces are reused at nearby sizes: a quarter of slack keeps a slowly growing batch from reallocating
+int reserve_slack(vigo_handle_t h, vigo::BufId id, size_t need) { return reserve(h, id, need, need + need / 4 + 4096); }
+int ensure_scratch(vigo_handle_t h, size_t bytes) { return reserve_slack(h, vigo::kBufScratch, bytes); }
+// a workspace laid out by `layout` (vigo_ws_layout.hpp) in buffer `id`: measured on a null base, reserved, carved
+enum Growth { kExact, kSlack };
+template <class Layout>
+int carve(vigo_handle_t h, vigo::BufId id, Growth g, Layout layout) {
+    const size_t need = layout(nullptr);
+    const int rc = g == kSlack ? reserve_slack(h, id, need) : reserve(h, id, need, need);
+    if (rc == VIGO_OK) layout(h->buf[id].ptr);
+    return rc;
+}
+
+// a few result words back on the host: the copy and the wait for it
+int read_back(vigo_handle_t h, void* dst, const void* src, size_t bytes) {
+    VIGO_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    VIGO_HIP(h, hipStreamSynchronize(h->stream));
     return VIGO_OK;
 }
 
@@ -60,19 +97,36 @@ int check_solve_args(vigo_handle_t h, int B, int N, const void* ctrl) {
 // The list arguments shared by the solve entry points and the dynamic gate.  Offsets (or a shared count)
 // without the list they index mean "no guides" / "no obstacles" — callers keep all-zero CSR offsets around
 // when a batch happens to have none — and the kernels never dereference the missing list.
-int check_list_args(vigo_handle_t h, const void* guide_off, const void* guide_pv, const void* obs_off, const void* obs, int n_obs_shared) {
-    (void)guide_off; (void)guide_pv; (void)obs_off; (void)obs;
+int check_list_args(vigo_handle_t h, int n_obs_shared) {
     if (n_obs_shared < 0) return fail(h, VIGO_ERR_INVALID_ARG, "n_obs_shared < 0");
     return VIGO_OK;
 }
 
+// the common fields of the solve entry points' SolveArgs
+SolveArgs solve_args(int B, int N, double* ctrl, const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                     const int32_t* obs_off, const double* obs, int n_obs_shared, const double* weights) {
+    SolveArgs a{};
+    a.B = B; a.N = N;
+    a.ctrl = ctrl;
+    a.guide_off = guide_off; a.guide_pv = guide_pv; a.guide_unk = guide_unk;
+    a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
+    a.weights = weights;
+    return a;
+}
+
+// the L-BFGS history of a solve workgroup fits the LDS of a CU
+bool lds_fits(vigo_handle_t h, int N) { return vigo::optimize_lds_requirement(N, h->params.mem_size, h->precision) <= (size_t)160 * 1024; }
+const char* const kLdsMsg = "the L-BFGS history of N control points x mem_size does not fit the 160 KiB LDS of a CU";
+
+// the control points a spline gate evaluates (the solver's own range starts at 7: check_solve_args)
+bool gate_N_ok(int N) { return N >= 4 && N <= VIGO_MAX_CTRL_POINTS; }
+const char* const kGateNMsg = "N outside [4, VIGO_MAX_CTRL_POINTS]";
+
 // Sample times of `for (t = 0; t <= tmax; t += dt)` (BT.h:313, :347): t_k is the k-fold floating point
 // accumulation, reproduced exactly by vigo::accumulated_time (closed form per binade).  The sample count T is
 // found on the host by bisection over that closed form (monotone in k), the table is filled by a device kernel
-// and cached in the handle per (dt, tmax): the gates run without a host round trip.
-// number of samples of `for (t = 0; t <= tmax; t += dt)` (the accumulated clock, exactly): bisection over the closed form,
-// monotone in k.  -1: more than 2^24 samples.
-static int count_sample_times(double dt, double tmax) {
+// and cached in the handle per (dt, tmax): the gates run without a host round trip.  -1: more than 2^24 samples.
+int count_sample_times(double dt, double tmax) {
     if (!(tmax >= 0.0)) return 0;
     const int64_t cap = (int64_t)1 << 24;
     if (vigo::accumulated_time(dt, cap) <= tmax) return -1;
@@ -92,28 +146,21 @@ int upload_sample_times(vigo_handle_t h, double tmax, double dt, int* out_T, con
             h->times_stream = h->stream;
         }
         *out_T = h->times_T;
-        *out_dev = h->times_dev;
+        *out_dev = h->buf[vigo::kBufTimes].as<double>();
         return VIGO_OK;
     }
     const int T = count_sample_times(dt, tmax);
     if (T < 0) return fail(h, VIGO_ERR_INVALID_ARG, "too many samples");
-    if ((size_t)T > h->times_cap) {
-        if (h->times_dev) (void)hipFree(h->times_dev);
-        h->times_dev = nullptr;
-        h->times_cap = 0;
-        h->times_T = -1;
-        const size_t want = (size_t)T + 64;
-        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->times_dev), want * sizeof(double)));
-        h->times_cap = want;
-    }
-    h->times_T = -1;
-    VIGO_HIP(h, (hipError_t)vigo::launch_fill_sample_times(h->stream, dt, T, h->times_dev));
+    h->times_T = -1;                                   // no clock cached while the buffer is regrown or refilled
+    VIGO_TRY(reserve(h, vigo::kBufTimes, (size_t)T * sizeof(double), ((size_t)T + 64) * sizeof(double)));
+    double* times = h->buf[vigo::kBufTimes].as<double>();
+    VIGO_HIP(h, (hipError_t)vigo::launch_fill_sample_times(h->stream, dt, T, times));
     h->times_dt = dt;
     h->times_tmax = tmax;
     h->times_T = T;
     h->times_stream = h->stream;
     *out_T = T;
-    *out_dev = h->times_dev;
+    *out_dev = times;
     return VIGO_OK;
 }
 
@@ -141,7 +188,7 @@ bool geometry_ok(const double origin[3], double res) {
 
 void fill_grid_view(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res) {
     GridView& g = h->grid;
-    g.planes = h->grid_planes;
+    g.planes = h->buf[vigo::kBufGrid].as<uint32_t>();
     g.nx = nx; g.ny = ny; g.nz = nz;
     g.nzw = (nz + 31) / 32;
     g.plane_words = (size_t)nx * ny * g.nzw;
@@ -158,31 +205,45 @@ void fill_grid_view(vigo_handle_t h, int nx, int ny, int nz, const double origin
 }
 
 int ensure_grid_storage(vigo_handle_t h, int nx, int ny, int nz) {
-    size_t need = vigo_grid_packed_bytes(nx, ny, nz);
-    if (need > h->grid_capacity_bytes) {
-        if (h->grid_planes) (void)hipFree(h->grid_planes);
-        h->grid_planes = nullptr;
-        h->grid_capacity_bytes = 0;
-        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->grid_planes), need));
-        h->grid_capacity_bytes = need;
+    const size_t need = vigo_grid_packed_bytes(nx, ny, nz);
+    return reserve(h, vigo::kBufGrid, need, need);
+}
+
+// the corridor checker's lattice is octomap's: keys are whole multiples of res from the origin
+bool key_lattice_ok(const GridView& g) {
+    for (int a = 0; a < 3; ++a) {
+        double q = g.origin[a] / g.res;
+        if (fabs(q - floor(q + 0.5)) > 1e-6) return false;
     }
-    return VIGO_OK;
+    return true;
+}
+const char* const kKeyLatticeMsg = "corridor checker needs a grid origin that is a multiple of res (octomap keys)";
+
+// the whole-trajectory checkers take the trajectories *chunk at a time: the scratch holds their workspace afterwards
+int traj_scratch(vigo_handle_t h, int T, int S, int* chunk) {
+    *chunk = T < VIGO_TRAJ_CHUNK ? (T > 0 ? T : 1) : VIGO_TRAJ_CHUNK;
+    return ensure_scratch(h, vigo::traj_ws_bytes(S, *chunk));
+}
+
+// the arguments vigo_astar_search and the entry points that run it share; astar_pool_fits: the VIGO_ASTAR_MAX_POOL_AXIS limit
+bool astar_args_ok(const int32_t pool[3], double step, int path_cap, int max_expansions) {
+    return pool && pool[0] >= 3 && pool[1] >= 3 && pool[2] >= 3 && step > 0.0 && step < 1e300 && path_cap >= 2 && max_expansions >= 0;
+}
+bool astar_pool_fits(const int32_t pool[3]) {
+    return pool[0] <= VIGO_ASTAR_MAX_POOL_AXIS && pool[1] <= VIGO_ASTAR_MAX_POOL_AXIS && pool[2] <= VIGO_ASTAR_MAX_POOL_AXIS;
 }
 
 // the lattice (row-major float[nx][ny][nz], device) becomes the handle's ESDF: one 128-B line per cell group
 int install_esdf(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const float* dist_dev) {
     size_t bytes = vigo::esdf_bricked_floats(nx, ny, nz) * sizeof(float);   // 3.56x the lattice (one line per cell group)
-    if (bytes > h->esdf_capacity) {
-        if (h->esdf) (void)hipFree(h->esdf);
-        h->esdf = nullptr;
-        h->esdf_capacity = 0;
-        h->has_esdf = false;                 // the earlier field is gone: if the allocation fails, queries say so
+    if (bytes > h->buf[vigo::kBufEsdf].bytes) {
+        h->has_esdf = false;                 // the earlier field goes with its buffer: if the allocation fails, queries say so
         h->esdf_view.dist = nullptr;
-        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->esdf), bytes));
-        h->esdf_capacity = bytes;
     }
-    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_brick(h->stream, nx, ny, nz, dist_dev, h->esdf));   // row-major -> one line per cell group
-    h->esdf_view.dist = h->esdf;
+    VIGO_TRY(reserve(h, vigo::kBufEsdf, bytes, bytes));
+    float* esdf = h->buf[vigo::kBufEsdf].as<float>();
+    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_brick(h->stream, nx, ny, nz, dist_dev, esdf));   // row-major -> one line per cell group
+    h->esdf_view.dist = esdf;
     h->esdf_view.nx = nx; h->esdf_view.ny = ny; h->esdf_view.nz = nz;
     h->esdf_view.nby = vigo::esdf_bricks_along(ny); h->esdf_view.nbz = vigo::esdf_bricks_along(nz);
     h->esdf_view.res = res;
@@ -299,17 +360,8 @@ int vigo_create(vigo_handle_t* out, int device_ordinal) {
 int vigo_destroy(vigo_handle_t h) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
-    if (h->grid_planes) (void)hipFree(h->grid_planes);
-    if (h->esdf) (void)hipFree(h->esdf);
-    if (h->esdf_ws) (void)hipFree(h->esdf_ws);
-    if (h->fit_pinvT) (void)hipFree(h->fit_pinvT);
-    if (h->times_dev) (void)hipFree(h->times_dev);
-    if (h->scratch) (void)hipFree(h->scratch);
-    for (void* w : h->paths_ws)
-        if (w) (void)hipFree(w);
-    for (void* w : h->reguide_ws)
-        if (w) (void)hipFree(w);
-    if (h->rebound_idx) (void)hipFree(h->rebound_idx);
+    for (const DevBuffer& b : h->buf)
+        if (b.ptr) (void)hipFree(b.ptr);
     if (h->dc_dev) (void)hipFree(h->dc_dev);
     for (int i = 0; i < vigo_context::kDcSlots; ++i)
         if (h->dc_event[i]) (void)hipEventDestroy(h->dc_event[i]);
@@ -400,18 +452,16 @@ int vigo_inflate_grid(vigo_handle_t h, int nx, int ny, int nz, uint8_t* voxels_d
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_inflate_grid: bad argument");
     if (rz > 31) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_inflate_grid: rz > 31 voxels");
     const size_t nw = (size_t)nx * ny * ((nz + 31) / 32);
-    int rc = ensure_scratch(h, 2 * nw * sizeof(uint32_t));
-    if (rc) return rc;
-    uint32_t* t = static_cast<uint32_t*>(h->scratch);
-    VIGO_HIP(h, (hipError_t)vigo::launch_inflate(h->stream, nx, ny, nz, voxels_dev, t, t + nw, rx, ry, rz));
+    uint32_t *planeA, *planeB;
+    VIGO_TRY(carve(h, vigo::kBufScratch, kSlack, [&](void* p) { return vigo::ws_pair(p, nw, planeA, planeB); }));
+    VIGO_HIP(h, (hipError_t)vigo::launch_inflate(h->stream, nx, ny, nz, voxels_dev, planeA, planeB, rx, ry, rz));
     return VIGO_OK;
 }
 
 int vigo_set_grid(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const uint8_t* voxels_dev) {
     if (!h || !voxels_dev || !origin || nx <= 0 || ny <= 0 || nz <= 0 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_grid: bad argument");
-    int rc = ensure_grid_storage(h, nx, ny, nz);
-    if (rc) return rc;
-    VIGO_HIP(h, (hipError_t)vigo::launch_pack_grid(h->stream, nx, ny, nz, voxels_dev, h->grid_planes));
+    VIGO_TRY(ensure_grid_storage(h, nx, ny, nz));
+    VIGO_HIP(h, (hipError_t)vigo::launch_pack_grid(h->stream, nx, ny, nz, voxels_dev, h->buf[vigo::kBufGrid].as<uint32_t>()));
     fill_grid_view(h, nx, ny, nz, origin, res);
     return VIGO_OK;
 }
@@ -419,20 +469,18 @@ int vigo_set_grid(vigo_handle_t h, int nx, int ny, int nz, const double origin[3
 int vigo_set_grid_host(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const uint8_t* voxels_host) {
     if (!h || !voxels_host || !origin || nx <= 0 || ny <= 0 || nz <= 0 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_grid_host: bad argument");
     size_t bytes = (size_t)nx * ny * nz;
-    int rc = ensure_scratch(h, bytes);
-    if (rc) return rc;
-    VIGO_HIP(h, hipMemcpyAsync(h->scratch, voxels_host, bytes, hipMemcpyHostToDevice, h->stream));
-    rc = vigo_set_grid(h, nx, ny, nz, origin, res, static_cast<const uint8_t*>(h->scratch));
-    if (rc) return rc;
+    VIGO_TRY(ensure_scratch(h, bytes));
+    uint8_t* staged = h->buf[vigo::kBufScratch].as<uint8_t>();
+    VIGO_HIP(h, hipMemcpyAsync(staged, voxels_host, bytes, hipMemcpyHostToDevice, h->stream));
+    VIGO_TRY(vigo_set_grid(h, nx, ny, nz, origin, res, staged));
     VIGO_HIP(h, hipStreamSynchronize(h->stream));
     return VIGO_OK;
 }
 
 int vigo_set_grid_packed(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const uint32_t* packed_dev) {
     if (!h || !packed_dev || !origin || nx <= 0 || ny <= 0 || nz <= 0 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_grid_packed: bad argument");
-    int rc = ensure_grid_storage(h, nx, ny, nz);
-    if (rc) return rc;
-    VIGO_HIP(h, hipMemcpyAsync(h->grid_planes, packed_dev, vigo_grid_packed_bytes(nx, ny, nz), hipMemcpyDeviceToDevice, h->stream));
+    VIGO_TRY(ensure_grid_storage(h, nx, ny, nz));
+    VIGO_HIP(h, hipMemcpyAsync(h->buf[vigo::kBufGrid].ptr, packed_dev, vigo_grid_packed_bytes(nx, ny, nz), hipMemcpyDeviceToDevice, h->stream));
     fill_grid_view(h, nx, ny, nz, origin, res);
     return VIGO_OK;
 }
@@ -462,13 +510,11 @@ int vigo_check_lists(vigo_handle_t h, int B, int N, const int32_t* guide_off, in
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || N < 1 || G < 0 || O < 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_check_lists: bad argument");
     if (B == 0 || (!guide_off && !obs_off)) return 0;
-    int rc = ensure_scratch(h, 64);
-    if (rc) return rc;
-    int* bad = static_cast<int*>(h->scratch);
+    VIGO_TRY(ensure_scratch(h, 64));
+    int* bad = h->buf[vigo::kBufScratch].as<int>();
     VIGO_HIP(h, (hipError_t)vigo::launch_check_lists(h->stream, B, N, guide_off, G, obs_off, O, bad));
     int host_bad = 0;
-    VIGO_HIP(h, hipMemcpyAsync(&host_bad, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    VIGO_TRY(read_back(h, &host_bad, bad, sizeof(int)));
     return host_bad;
 }
 
@@ -478,16 +524,9 @@ int vigo_cost_grad(vigo_handle_t h, int B, int N, const double* ctrl, const int3
                    const double* guide_pv, const uint8_t* guide_unk, const int32_t* obs_off,
                    const double* obs, int n_obs_shared, const double* weights, double* out_cost,
                    double* out_grad, double* out_terms) {
-    int rc = check_solve_args(h, B, N, ctrl);
-    if (rc) return rc;
-    rc = check_list_args(h, guide_off, guide_pv, obs_off, obs, n_obs_shared);
-    if (rc) return rc;
-    SolveArgs a{};
-    a.B = B; a.N = N;
-    a.ctrl = const_cast<double*>(ctrl);
-    a.guide_off = guide_off; a.guide_pv = guide_pv; a.guide_unk = guide_unk;
-    a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
-    a.weights = weights;
+    VIGO_TRY(check_solve_args(h, B, N, ctrl));
+    VIGO_TRY(check_list_args(h, n_obs_shared));
+    SolveArgs a = solve_args(B, N, const_cast<double*>(ctrl), guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
     a.out_cost = out_cost; a.out_grad = out_grad; a.out_terms = out_terms;
     VIGO_HIP(h, (hipError_t)vigo::launch_cost_grad(h->stream, a, h->dc, h->dc_dev, h->precision));
     return VIGO_OK;
@@ -497,20 +536,12 @@ int vigo_optimize(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* gu
                   const double* guide_pv, const uint8_t* guide_unk, const int32_t* obs_off,
                   const double* obs, int n_obs_shared, const double* weights, double* out_x,
                   int32_t* out_status, double* out_fx, int32_t* out_iters, int32_t* out_evals) {
-    int rc = check_solve_args(h, B, N, ctrl);
-    if (rc) return rc;
-    rc = check_list_args(h, guide_off, guide_pv, obs_off, obs, n_obs_shared);
-    if (rc) return rc;
-    SolveArgs a{};
-    a.B = B; a.N = N;
-    a.ctrl = ctrl;
-    a.guide_off = guide_off; a.guide_pv = guide_pv; a.guide_unk = guide_unk;
-    a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
-    a.weights = weights;
+    VIGO_TRY(check_solve_args(h, B, N, ctrl));
+    VIGO_TRY(check_list_args(h, n_obs_shared));
+    SolveArgs a = solve_args(B, N, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
     a.out_x = out_x; a.out_status = out_status; a.out_fx = out_fx;
     a.out_iters = out_iters; a.out_evals = out_evals;
-    if (vigo::optimize_lds_requirement(N, h->params.mem_size, h->precision) > (size_t)160 * 1024)
-        return fail(h, VIGO_ERR_UNSUPPORTED_N, "the L-BFGS history of N control points x mem_size does not fit the 160 KiB LDS of a CU");
+    if (!lds_fits(h, N)) return fail(h, VIGO_ERR_UNSUPPORTED_N, kLdsMsg);
     VIGO_HIP(h, (hipError_t)vigo::launch_optimize(h->stream, a, h->dc, h->dc_dev, h->precision, h->launch));
     return VIGO_OK;
 }
@@ -518,38 +549,22 @@ int vigo_optimize(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* gu
 int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* guide_off, const double* guide_pv,
                         const uint8_t* guide_unk, const int32_t* obs_off, const double* obs, int n_obs_shared, double* weights,
                         double gate_dt, double not_check_ratio, int max_rounds, vigo_rebound_state_t* state) {
-    int rc = check_solve_args(h, B, N, ctrl);
-    if (rc) return rc;
-    rc = check_list_args(h, guide_off, guide_pv, obs_off, obs, n_obs_shared);
-    if (rc) return rc;
+    VIGO_TRY(check_solve_args(h, B, N, ctrl));
+    VIGO_TRY(check_list_args(h, n_obs_shared));
     if (B > 0 && (!weights || !state)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_rounds: weights and state are required");
     if (max_rounds < 0 || max_rounds > 64 || !(not_check_ratio >= 0.0 && not_check_ratio < 1.0))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_rounds: max_rounds outside [0, 64] or not_check_ratio outside [0, 1)");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_rebound_rounds before vigo_set_grid");
-    if (vigo::optimize_lds_requirement(N, h->params.mem_size, h->precision) > (size_t)160 * 1024)
-        return fail(h, VIGO_ERR_UNSUPPORTED_N, "the L-BFGS history of N control points x mem_size does not fit the 160 KiB LDS of a CU");
+    if (!lds_fits(h, N)) return fail(h, VIGO_ERR_UNSUPPORTED_N, kLdsMsg);
     if (B == 0) return VIGO_OK;
     int T = 0;
     const double* times = nullptr;
-    rc = upload_sample_times(h, (N - 3) * h->params.ts_ctrl, gate_dt, &T, &times);
-    if (rc) return rc;
-    // compacted active set: B indices + the count (its own allocation: the scratch buffer serves other entry points)
-    if ((size_t)B + 16 > h->rebound_cap) {
-        if (h->rebound_idx) (void)hipFree(h->rebound_idx);
-        h->rebound_idx = nullptr;
-        h->rebound_cap = 0;
-        VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->rebound_idx), ((size_t)B + 16) * sizeof(int32_t) + 64));
-        h->rebound_cap = (size_t)B + 16;
-    }
-    int32_t* idx = h->rebound_idx + 16;
-    int32_t* count = h->rebound_idx;          // flags[0]; flags[1], flags[2]: "a trajectory waits for the host"
+    VIGO_TRY(upload_sample_times(h, (N - 3) * h->params.ts_ctrl, gate_dt, &T, &times));
+    // compacted active set: count = flags[0]; flags[1], flags[2]: "a trajectory waits for the host"
+    int32_t *count, *idx;
+    VIGO_TRY(carve(h, vigo::kBufRebound, kExact, [&](void* p) { return vigo::ws_rebound(p, B, count, idx); }));
     VIGO_HIP(h, hipMemsetAsync(count, 0, 16 * sizeof(int32_t), h->stream));
-    SolveArgs a{};
-    a.B = B; a.N = N;
-    a.ctrl = ctrl;
-    a.guide_off = guide_off; a.guide_pv = guide_pv; a.guide_unk = guide_unk;
-    a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
-    a.weights = weights;
+    SolveArgs a = solve_args(B, N, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
     a.active_idx = idx; a.active_count = count;
     a.out_status = &state[0].lbfgs_status;
     a.status_stride = (int)(sizeof(vigo_rebound_state_t) / sizeof(int32_t));
@@ -586,23 +601,15 @@ int vigo_bspline_fit(vigo_handle_t h, int B, int K, double ts, const double* poi
     if (K < 4 || K + 2 > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "K outside [4, VIGO_MAX_CTRL_POINTS - 2]");
     if (h->fit_K != K || h->fit_ts != ts) {
         // one-off per (K, ts): factorise A on the device, keep the least-squares operator
-        const size_t need = vigo::fit_pinv_doubles(K);
-        if (need > h->fit_capacity) {
-            if (h->fit_pinvT) (void)hipFree(h->fit_pinvT);
-            h->fit_pinvT = nullptr;
-            h->fit_capacity = 0;
-            h->fit_K = 0;
-            VIGO_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->fit_pinvT), need * sizeof(double)));
-            h->fit_capacity = need;
-        }
-        int rc = ensure_scratch(h, vigo::fit_work_doubles(K) * sizeof(double));
-        if (rc) return rc;
-        h->fit_K = 0;
-        VIGO_HIP(h, (hipError_t)vigo::launch_fit_setup(h->stream, K, ts, static_cast<double*>(h->scratch), h->fit_pinvT));
+        const size_t need = vigo::fit_pinv_doubles(K) * sizeof(double);
+        h->fit_K = 0;                                   // no operator cached while the buffer is regrown or refilled
+        VIGO_TRY(reserve(h, vigo::kBufFit, need, need));
+        VIGO_TRY(ensure_scratch(h, vigo::fit_work_doubles(K) * sizeof(double)));
+        VIGO_HIP(h, (hipError_t)vigo::launch_fit_setup(h->stream, K, ts, h->buf[vigo::kBufScratch].as<double>(), h->buf[vigo::kBufFit].as<double>()));
         h->fit_K = K;
         h->fit_ts = ts;
     }
-    VIGO_HIP(h, (hipError_t)vigo::launch_bspline_fit(h->stream, B, K, h->fit_pinvT, points, conds, ctrl_out));
+    VIGO_HIP(h, (hipError_t)vigo::launch_bspline_fit(h->stream, B, K, h->buf[vigo::kBufFit].as<double>(), points, conds, ctrl_out));
     return VIGO_OK;
 }
 
@@ -611,7 +618,7 @@ int vigo_bspline_eval(vigo_handle_t h, int B, int N, const double* ctrl, int der
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || T < 0 || deriv < 0 || deriv > 2 || ((B > 0 && T > 0) && (!ctrl || !times || !out)))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_bspline_eval: bad argument");
-    if (N < 4 || N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [4, VIGO_MAX_CTRL_POINTS]");
+    if (!gate_N_ok(N)) return fail(h, VIGO_ERR_UNSUPPORTED_N, kGateNMsg);
     VIGO_HIP(h, (hipError_t)vigo::launch_bspline_eval(h->stream, B, N, ctrl, h->params.ts_ctrl, deriv, T, times, out));
     return VIGO_OK;
 }
@@ -620,13 +627,12 @@ int vigo_traj_collision(vigo_handle_t h, int B, int N, const double* ctrl, doubl
                         uint8_t* out_flag, int32_t* out_first) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || (B > 0 && (!ctrl || !out_flag))) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_collision: bad argument");
-    if (N < 4 || N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [4, VIGO_MAX_CTRL_POINTS]");
+    if (!gate_N_ok(N)) return fail(h, VIGO_ERR_UNSUPPORTED_N, kGateNMsg);
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_collision before vigo_set_grid");
     int T = 0;
     const double* times = nullptr;
     double duration = (N - 3) * h->params.ts_ctrl;  // knots(N), BS.cpp:27
-    int rc = upload_sample_times(h, (1.0 - 0.0) * duration, dt, &T, &times);
-    if (rc) return rc;
+    VIGO_TRY(upload_sample_times(h, (1.0 - 0.0) * duration, dt, &T, &times));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_collision(h->stream, h->grid, B, N, ctrl, h->params.ts_ctrl, T, times, out_flag, out_first));
     return VIGO_OK;
 }
@@ -636,14 +642,12 @@ int vigo_traj_dynamic_collision(vigo_handle_t h, int B, int N, const double* ctr
                                 uint8_t* out_flag) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || (B > 0 && (!ctrl || !out_flag)) || n_obs_shared < 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_dynamic_collision: bad argument");
-    if (N < 4 || N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [4, VIGO_MAX_CTRL_POINTS]");
-    int rc = check_list_args(h, nullptr, nullptr, obs_off, obs, n_obs_shared);
-    if (rc) return rc;
+    if (!gate_N_ok(N)) return fail(h, VIGO_ERR_UNSUPPORTED_N, kGateNMsg);
+    VIGO_TRY(check_list_args(h, n_obs_shared));
     int T = 0;
     const double* times = nullptr;
     double duration = (N - 3) * h->params.ts_ctrl;
-    rc = upload_sample_times(h, duration, dt, &T, &times);
-    if (rc) return rc;
+    VIGO_TRY(upload_sample_times(h, duration, dt, &T, &times));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_dynamic_collision(h->stream, B, N, ctrl, h->params.ts_ctrl, T, times, obs_off, obs, n_obs_shared, out_flag));
     return VIGO_OK;
 }
@@ -684,21 +688,15 @@ int vigo_corridor_check(vigo_handle_t h, int S, int deg, const double* coeffs, c
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_corridor_check: bad argument");
     if (!sweep_box_ok(box, map_res)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_corridor_check: collision box not finite or more than 32768 lattice points per pose");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_corridor_check before vigo_set_grid");
-    for (int a = 0; a < 3; ++a) {
-        double q = h->grid.origin[a] / h->grid.res;
-        if (fabs(q - floor(q + 0.5)) > 1e-6)
-            return fail(h, VIGO_ERR_UNSUPPORTED, "corridor checker needs a grid origin that is a multiple of res (octomap keys)");
-    }
+    if (!key_lattice_ok(h->grid)) return fail(h, VIGO_ERR_UNSUPPORTED, kKeyLatticeMsg);
     if (S == 0) return VIGO_OK;
     // scratch: the first pass' work list for the second, then (up to 16384 segments: 42 MB) the segments' clock tables
-    const size_t todo_bytes = ((size_t)S * sizeof(int) + 255) & ~(size_t)255;
     const size_t clock_bytes = S <= 16384 ? vigo::corridor_clock_ws_bytes(S) : 0;
-    int rc = ensure_scratch(h, todo_bytes + clock_bytes);
-    if (rc != VIGO_OK) return rc;
-    char* ws = static_cast<char*>(h->scratch);
+    int* todo;
+    void* clock_ws;
+    VIGO_TRY(carve(h, vigo::kBufScratch, kSlack, [&](void* p) { return vigo::ws_corridor(p, S, clock_bytes, todo, clock_ws); }));
     VIGO_HIP(h, (hipError_t)vigo::launch_corridor_check2(h->stream, h->grid, S, deg, coeffs, n_samp, delT, box, map_res, out_flag,
-                                                         out_first, out_count, reinterpret_cast<int*>(ws),
-                                                         clock_bytes ? ws + todo_bytes : nullptr));
+                                                         out_first, out_count, todo, clock_ws));
     return VIGO_OK;
 }
 
@@ -713,18 +711,13 @@ int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_corridor_check: bad argument");
     if (!sweep_box_ok(box, map_res)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_traj_corridor_check: collision box not finite or more than 32768 lattice points per pose");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_corridor_check before vigo_set_grid");
-    for (int a = 0; a < 3; ++a) {
-        double q = h->grid.origin[a] / h->grid.res;
-        if (fabs(q - floor(q + 0.5)) > 1e-6)
-            return fail(h, VIGO_ERR_UNSUPPORTED, "corridor checker needs a grid origin that is a multiple of res (octomap keys)");
-    }
+    if (!key_lattice_ok(h->grid)) return fail(h, VIGO_ERR_UNSUPPORTED, kKeyLatticeMsg);
     if (T == 0 && S == 0) return VIGO_OK;
-    const int chunk = T < VIGO_TRAJ_CHUNK ? (T > 0 ? T : 1) : VIGO_TRAJ_CHUNK;
-    int rc = ensure_scratch(h, vigo::traj_ws_bytes(S, chunk));
-    if (rc != VIGO_OK) return rc;
+    int chunk;
+    VIGO_TRY(traj_scratch(h, T, S, &chunk));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_corridor(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, delT, endpoint, box,
                                                        map_res, (flags & VIGO_TRAJ_NONFINITE_COLLIDES) ? 1 : 0, out_status, out_n,
-                                                       out_flag, out_first, out_count, out_seg, h->scratch, chunk));
+                                                       out_flag, out_first, out_count, out_seg, h->buf[vigo::kBufScratch].ptr, chunk));
     return VIGO_OK;
 }
 
@@ -738,11 +731,10 @@ int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t*
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_point_check: bad argument");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_point_check before vigo_set_grid");
     if (T == 0 && S == 0) return VIGO_OK;
-    const int chunk = T < VIGO_TRAJ_CHUNK ? (T > 0 ? T : 1) : VIGO_TRAJ_CHUNK;
-    int rc = ensure_scratch(h, vigo::traj_ws_bytes(S, chunk));
-    if (rc != VIGO_OK) return rc;
+    int chunk;
+    VIGO_TRY(traj_scratch(h, T, S, &chunk));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_point(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, delT, endpoint, out_status,
-                                                    out_n, out_flag, out_first, out_count, out_seg, h->scratch, chunk));
+                                                    out_n, out_flag, out_first, out_count, out_seg, h->buf[vigo::kBufScratch].ptr, chunk));
     return VIGO_OK;
 }
 
@@ -760,11 +752,7 @@ int vigo_box_collision_points(vigo_handle_t h, int64_t M, const double* pts, con
     if (M < 0 || !box || !(map_res > 0) || (M > 0 && (!pts || !out))) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_box_collision_points: bad argument");
     if (!sweep_box_ok(box, map_res)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_box_collision_points: collision box not finite or more than 32768 lattice points per pose");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_box_collision_points before vigo_set_grid");
-    for (int a = 0; a < 3; ++a) {
-        double q = h->grid.origin[a] / h->grid.res;
-        if (fabs(q - floor(q + 0.5)) > 1e-6)
-            return fail(h, VIGO_ERR_UNSUPPORTED, "corridor checker needs a grid origin that is a multiple of res (octomap keys)");
-    }
+    if (!key_lattice_ok(h->grid)) return fail(h, VIGO_ERR_UNSUPPORTED, kKeyLatticeMsg);
     VIGO_HIP(h, (hipError_t)vigo::launch_box_points(h->stream, h->grid, M, pts, box, map_res, out));
     return VIGO_OK;
 }
@@ -773,10 +761,10 @@ int vigo_astar_search(vigo_handle_t h, int Q, const double* start, const double*
                       double min_height, double max_height, int max_expansions, int path_cap, int32_t* out_status, int32_t* out_len,
                       double* out_path, int32_t* out_stats) {
     if (!h) return VIGO_ERR_INVALID_ARG;
-    if (Q < 0 || !pool || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || !(step > 0.0) || !(step < 1e300) || path_cap < 2 || max_expansions < 0 ||
+    if (Q < 0 || !astar_args_ok(pool, step, path_cap, max_expansions) ||
         (Q > 0 && (!start || !end || !out_status || !out_len || !out_path)))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_astar_search: bad argument");
-    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+    if (!astar_pool_fits(pool))
         return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_astar_search: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_astar_search before vigo_set_grid");
     if (Q == 0) return VIGO_OK;
@@ -799,14 +787,12 @@ int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const i
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: bad argument");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_guide_assign before vigo_set_grid");
     if (B == 0) return VIGO_OK;
-    int rc = ensure_scratch(h, 64);
-    if (rc) return rc;
-    long long* result = static_cast<long long*>(h->scratch);
+    VIGO_TRY(ensure_scratch(h, 64));
+    long long* result = h->buf[vigo::kBufScratch].as<long long>();
     VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, seg_off, seg, path_off, (long long)pair_cap, out_guide_off, out_status,
                                                        result));
     long long host_result[2] = {0, 0};
-    VIGO_HIP(h, hipMemcpyAsync(host_result, result, sizeof(host_result), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    VIGO_TRY(read_back(h, host_result, result, sizeof(host_result)));
     if (host_result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: offsets that decrease, a path without a point or a segment out of range");
     if (host_result[0] > (long long)pair_cap || host_result[0] > 0x7fffffffLL)
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: the pairs do not fit pair_cap");
@@ -823,49 +809,9 @@ int vigo_guide_capacity(int32_t* max_path_points) {
 
 namespace {
 
-// the per-trajectory scratch of vigo_collision_segs / vigo_path_search, carved out of h->scratch
+// the per-trajectory scratch of vigo_collision_segs / vigo_path_search, carved out of the scratch buffer
 int path_search_scratch(vigo_handle_t h, int B, int N, bool flags, vigo::PathSearchArgs& a) {
-    const size_t words = ((size_t)B + 2) & ~(size_t)1;        // (an even number of int32: every array stays 8-byte aligned)
-    const size_t flag_bytes = flags ? (((size_t)B * N + 7) & ~(size_t)7) : 0;
-    int rc = ensure_scratch(h, 64 + 9 * words * 4 + 2 * flag_bytes);
-    if (rc) return rc;
-    char* p = static_cast<char*>(h->scratch);
-    a.result = reinterpret_cast<long long*>(p);
-    int32_t* w = reinterpret_cast<int32_t*>(p + 64);
-    a.in_off = w;
-    a.n_in = w + words;
-    a.pre = w + 2 * words;
-    a.tstatus = w + 3 * words;
-    a.n_out = w + 4 * words;
-    a.oseg_off = w + 5 * words;
-    a.opt_off = w + 6 * words;
-    a.tcounts = w + 7 * words;                                 // [B][2]
-    uint8_t* f = reinterpret_cast<uint8_t*>(w + 9 * words);
-    a.pt = flags ? f : nullptr;
-    a.ln = flags ? f + flag_bytes : nullptr;
-    return VIGO_OK;
-}
-
-int ensure_paths_ws(vigo_handle_t h, int which, size_t bytes) {
-    if (bytes <= h->paths_ws_bytes[which]) return VIGO_OK;
-    if (h->paths_ws[which]) (void)hipFree(h->paths_ws[which]);
-    h->paths_ws[which] = nullptr;
-    h->paths_ws_bytes[which] = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    VIGO_HIP(h, hipMalloc(&h->paths_ws[which], want));
-    h->paths_ws_bytes[which] = want;
-    return VIGO_OK;
-}
-
-int ensure_reguide_ws(vigo_handle_t h, int which, size_t bytes) {
-    if (bytes <= h->reguide_ws_bytes[which]) return VIGO_OK;
-    if (h->reguide_ws[which]) (void)hipFree(h->reguide_ws[which]);
-    h->reguide_ws[which] = nullptr;
-    h->reguide_ws_bytes[which] = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    VIGO_HIP(h, hipMalloc(&h->reguide_ws[which], want));
-    h->reguide_ws_bytes[which] = want;
-    return VIGO_OK;
+    return carve(h, vigo::kBufScratch, kSlack, [&](void* p) { return vigo::ws_path_search_scratch(p, B, N, flags, a); });
 }
 
 // flags and segment counts of the call, read back: result[0] segments, result[1] a bad list
@@ -873,8 +819,7 @@ int path_search_count(vigo_handle_t h, vigo::PathSearchArgs& a, long long result
     if (!a.seg_in)
         VIGO_HIP(h, (hipError_t)vigo::launch_ctrl_occupancy(h->stream, h->grid, a.B, a.N, a.ctrl, const_cast<uint8_t*>(a.pt), const_cast<uint8_t*>(a.ln)));
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_count(h->stream, a));
-    VIGO_HIP(h, hipMemcpyAsync(result, a.result, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    VIGO_TRY(read_back(h, result, a.result, 2 * sizeof(long long)));
     if (result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, bad_list);
     return VIGO_OK;
 }
@@ -884,39 +829,23 @@ int path_search_count(vigo_handle_t h, vigo::PathSearchArgs& a, long long result
 int path_search_searches(vigo_handle_t h, vigo::PathSearchArgs& a, vigo::PathSearchWork& w, double step, const int32_t pool[3], double min_height,
                          double max_height, int max_expansions, long long result[5]) {
     const int search_path_cap = a.search_path_cap;
-    int rc;
     const size_t S = (size_t)result[0];
     if (S > 0) {
-        // [0]: per first-choice search 2 + 2 + 1 + 1 + 1 + 1 int32, 4 x 3 doubles and a path; everything 8-byte aligned
-        const size_t Se = (S + 1) & ~(size_t)1, path_doubles = S * (size_t)search_path_cap * 3;
-        rc = ensure_paths_ws(h, 0, Se * 8 * 4 + S * 12 * 8 + path_doubles * 8);
-        if (rc) return rc;
-        double* d = static_cast<double*>(h->paths_ws[0]);
-        w.start1 = d; w.end1 = d + 3 * S; w.start2 = d + 6 * S; w.end2 = d + 9 * S; w.path1 = d + 12 * S;
-        int32_t* i = reinterpret_cast<int32_t*>(d + 12 * S + path_doubles);
-        w.seg = i; w.mseg = i + 2 * Se; w.pick = i + 4 * Se; w.retry_of = i + 5 * Se; w.status1 = i + 6 * Se; w.len1 = i + 7 * Se;
+        VIGO_TRY(carve(h, vigo::kBufPaths0, kSlack, [&](void* p) { return vigo::ws_first_searches(p, S, search_path_cap, w); }));
         VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, w.seg, w.start1, w.end1));
         VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)S, w.start1, w.end1, step, pool, min_height, max_height, max_expansions,
                                                    search_path_cap, w.status1, w.len1, w.path1, nullptr, h->launch));
         VIGO_HIP(h, (hipError_t)vigo::launch_ps_retry(h->stream, a, w));
-        VIGO_HIP(h, hipMemcpyAsync(result + 2, a.result + 2, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-        VIGO_HIP(h, hipStreamSynchronize(h->stream));
+        VIGO_TRY(read_back(h, result + 2, a.result + 2, sizeof(long long)));
         const size_t Q2 = (size_t)result[2];
         if (Q2 > 0) {
-            const size_t Qe = (Q2 + 1) & ~(size_t)1, path2_doubles = Q2 * (size_t)search_path_cap * 3;
-            rc = ensure_paths_ws(h, 1, path2_doubles * 8 + Qe * 2 * 4);
-            if (rc) return rc;
-            w.path2 = static_cast<double*>(h->paths_ws[1]);
-            w.status2 = reinterpret_cast<int32_t*>(w.path2 + path2_doubles);
-            w.len2 = w.status2 + Qe;
+            VIGO_TRY(carve(h, vigo::kBufPaths1, kSlack, [&](void* p) { return vigo::ws_second_searches(p, Q2, search_path_cap, w); }));
             VIGO_HIP(h, (hipError_t)vigo::launch_astar(h->stream, h->grid, (int)Q2, w.start2, w.end2, step, pool, min_height, max_height,
                                                        max_expansions, search_path_cap, w.status2, w.len2, w.path2, nullptr, h->launch));
         }
     }
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_decide(h->stream, a, w));
-    VIGO_HIP(h, hipMemcpyAsync(result + 3, a.result + 3, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
-    return VIGO_OK;
+    return read_back(h, result + 3, a.result + 3, 2 * sizeof(long long));
 }
 
 }  // namespace
@@ -933,11 +862,9 @@ int vigo_collision_segs(vigo_handle_t h, int B, int N, const double* ctrl, doubl
     if (B == 0) return VIGO_OK;
     vigo::PathSearchArgs a{};
     a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio;
-    int rc = path_search_scratch(h, B, N, true, a);
-    if (rc) return rc;
+    VIGO_TRY(path_search_scratch(h, B, N, true, a));
     long long result[2] = {0, 0};
-    rc = path_search_count(h, a, result, "vigo_collision_segs: bad list");
-    if (rc) return rc;
+    VIGO_TRY(path_search_count(h, a, result, "vigo_collision_segs: bad list"));
     if (result[0] > (long long)seg_cap) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_collision_segs: the segments do not fit seg_cap");
     a.out_seg_off = out_seg_off; a.out_status = out_status;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, out_seg, nullptr, nullptr));
@@ -952,25 +879,21 @@ int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const in
     if (!h) return VIGO_ERR_INVALID_ARG;
     const bool scan = !seg_off && !seg;
     if (B < 0 || N < 7 || seg_cap < 0 || point_cap < 0 || (!scan && (!seg_off || !seg)) ||
-        (scan && !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0)) || !pool || pool[0] < 3 || pool[1] < 3 || pool[2] < 3 || !(step > 0.0) ||
-        !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 ||
+        (scan && !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0)) || !astar_args_ok(pool, step, search_path_cap, max_expansions) ||
         (B > 0 && (!ctrl || !out_status || !out_seg_off || !out_seg || !out_path_off || !out_path)))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: bad argument");
-    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+    if (!astar_pool_fits(pool))
         return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_path_search: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_path_search before vigo_set_grid");
     if (B == 0) return VIGO_OK;
     vigo::PathSearchArgs a{};
     a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_off_in = seg_off; a.seg_in = seg;
     a.search_path_cap = search_path_cap;
-    int rc = path_search_scratch(h, B, N, scan, a);
-    if (rc) return rc;
+    VIGO_TRY(path_search_scratch(h, B, N, scan, a));
     long long result[5] = {0, 0, 0, 0, 0};
-    rc = path_search_count(h, a, result, "vigo_path_search: offsets that decrease or start below 0, or a segment end outside [0, N)");
-    if (rc) return rc;
+    VIGO_TRY(path_search_count(h, a, result, "vigo_path_search: offsets that decrease or start below 0, or a segment end outside [0, N)"));
     vigo::PathSearchWork w{};
-    rc = path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result);
-    if (rc) return rc;
+    VIGO_TRY(path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result));
     if (result[3] > (long long)seg_cap || result[3] >= 0x7fffffffLL)
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the segments do not fit seg_cap");
     if (result[4] > (long long)point_cap || result[4] > 0x7fffffffLL)
@@ -990,92 +913,68 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
     const bool no_guides = !guide_off && !guide_pv && !guide_unk;
     const bool no_paths = !out_path_seg_off && !out_path_off && !out_path;
     if (B < 0 || N < 7 || pair_cap < 0 || seg_cap < 0 || point_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
-        (!no_guides && (!guide_off || !guide_pv)) || (!no_paths && (!out_path_seg_off || !out_path_off || !out_path)) || !pool || pool[0] < 3 ||
-        pool[1] < 3 || pool[2] < 3 || !(step > 0.0) || !(step < 1e300) || search_path_cap < 2 || max_expansions < 0 ||
+        (!no_guides && (!guide_off || !guide_pv)) || (!no_paths && (!out_path_seg_off || !out_path_off || !out_path)) ||
+        !astar_args_ok(pool, step, search_path_cap, max_expansions) ||
         (B > 0 && (!ctrl || !weights || !state || !out_guide_off || !out_guide_pv || !out_status)))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: bad argument");
     if (N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [7, VIGO_MAX_CTRL_POINTS]");
-    if (pool[0] > VIGO_ASTAR_MAX_POOL_AXIS || pool[1] > VIGO_ASTAR_MAX_POOL_AXIS || pool[2] > VIGO_ASTAR_MAX_POOL_AXIS)
+    if (!astar_pool_fits(pool))
         return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
     if (B > (1 << 20)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than 2^20 trajectories in a call");
     if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_rebound_reguide before vigo_set_grid");
     if (B == 0) return VIGO_OK;
     constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
-    // [0]: 64 bytes of result words, nine per-trajectory int32 arrays, the lists and the new segments at a fixed stride,
-    // the offsets of this step's pairs; every array 8-byte aligned
-    const size_t words = ((size_t)B + 2) & ~(size_t)1, gwords = ((size_t)B * N + 2) & ~(size_t)1;
-    int rc = ensure_reguide_ws(h, 0, 64 + 4 * (9 * words + 4 * (size_t)kSegs * B + gwords));
-    if (rc) return rc;
     vigo::ReguideArgs r{};
+    vigo::ReguideStage st{};
+    VIGO_TRY(carve(h, vigo::kBufReguide0, kSlack, [&](void* p) { return vigo::ws_reguide(p, B, N, kSegs, r, st); }));
     r.B = B; r.N = N; r.ctrl = ctrl; r.guide_off = guide_off; r.guide_pv = guide_pv; r.guide_unk = guide_unk; r.weights = weights; r.state = state;
     r.dthresh = h->params.dthresh; r.not_check_ratio = not_check_ratio;
-    r.result = static_cast<long long*>(h->reguide_ws[0]);
-    int32_t* w0 = reinterpret_cast<int32_t*>(static_cast<char*>(h->reguide_ws[0]) + 64);
-    r.kind = w0; r.n_list = w0 + words; r.n_new = w0 + 2 * words; r.outcome = w0 + 3 * words;
-    int32_t* ps_status = w0 + 4 * words;
-    int32_t* ps_seg_off = w0 + 5 * words;
-    int32_t* g_status = w0 + 6 * words;
-    int32_t* ps_counts = w0 + 7 * words;
-    r.list = w0 + 9 * words;
-    r.new_seg = r.list + 2 * (size_t)kSegs * B;
-    int32_t* g_off = r.new_seg + 2 * (size_t)kSegs * B;
     // vigo_path_search's chain on the lists (a trajectory that is not worked on has an empty one)
     vigo::PathSearchArgs a{};
     a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_in = r.list; a.seg_cnt_in = r.n_list; a.seg_stride_in = kSegs;
     a.search_path_cap = search_path_cap;
-    rc = path_search_scratch(h, B, N, false, a);
-    if (rc) return rc;
+    VIGO_TRY(path_search_scratch(h, B, N, false, a));
     VIGO_HIP(h, hipMemsetAsync(r.result, 0, 64, h->stream));
     VIGO_HIP(h, (hipError_t)vigo::launch_reguide_list(h->stream, h->grid, r));
     long long bad_off = 0;
     VIGO_HIP(h, hipMemcpyAsync(&bad_off, r.result, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     long long result[5] = {0, 0, 0, 0, 0};
-    rc = path_search_count(h, a, result, "vigo_rebound_reguide: a re-guide list out of range");
+    const int rc = path_search_count(h, a, result, "vigo_rebound_reguide: a re-guide list out of range");
+    if (rc == VIGO_ERR_HIP) (void)hipStreamSynchronize(h->stream);   // (it may have failed before its own wait: bad_off's copy must have landed)
     if (rc) return rc;
     if (bad_off != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: guide offsets that decrease or start below 0");
     vigo::PathSearchWork w{};
-    rc = path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result);
-    if (rc) return rc;
+    VIGO_TRY(path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result));
     const long long total_seg = result[3], total_pts = result[4];
     if (total_pts > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: more than 2^31 path points");
     if (!no_paths && (total_seg > (long long)seg_cap || total_pts > (long long)point_cap))
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the paths do not fit seg_cap / point_cap");
-    // [1]: the searches' paths, segments and path offsets
-    const size_t seg_words = (2 * (size_t)total_seg + 2) & ~(size_t)1, po_words = ((size_t)total_seg + 2) & ~(size_t)1;
-    rc = ensure_reguide_ws(h, 1, 3 * (size_t)total_pts * 8 + 8 + 4 * (seg_words + po_words));
-    if (rc) return rc;
-    double* ps_path = static_cast<double*>(h->reguide_ws[1]);
-    int32_t* ps_seg = reinterpret_cast<int32_t*>(ps_path + 3 * (size_t)total_pts + 1);
-    int32_t* ps_path_off = ps_seg + seg_words;
-    a.out_status = ps_status; a.out_seg_off = ps_seg_off; a.out_seg = ps_seg; a.out_path_off = ps_path_off; a.out_path = ps_path; a.out_counts = ps_counts;
+    VIGO_TRY(carve(h, vigo::kBufReguide1, kSlack, [&](void* p) { return vigo::ws_reguide_paths(p, total_seg, total_pts, a); }));
+    a.out_status = st.ps_status; a.out_seg_off = st.ps_seg_off; a.out_counts = st.ps_counts;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)total_seg, (int)total_pts));
     // vigo_guide_assign's pair on that output: the pairs THIS step appends
     long long* g_result = r.result + 2;
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, ps_seg_off, ps_seg, ps_path_off, 0x7fffffffLL, g_off, g_status, g_result));
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, st.ps_seg_off, a.out_seg, a.out_path_off, 0x7fffffffLL, st.g_off, st.g_status, g_result));
     long long g_host[2] = {0, 0};
-    VIGO_HIP(h, hipMemcpyAsync(g_host, g_result, sizeof(g_host), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    VIGO_TRY(read_back(h, g_host, g_result, sizeof(g_host)));
     if (g_host[1] != 0 || g_host[0] > 0x7fffffffLL) return fail(h, VIGO_ERR_HIP, "vigo_rebound_reguide: the path search's output is no input of the guide step");
-    // [2]: those pairs and their unknown flags
     const size_t P = (size_t)g_host[0];
-    rc = ensure_reguide_ws(h, 2, P * 48 + P + 8);
-    if (rc) return rc;
-    double* g_pv = static_cast<double*>(h->reguide_ws[2]);
-    uint8_t* g_unk = reinterpret_cast<uint8_t*>(g_pv + 6 * P);
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, ps_seg_off, ps_seg, ps_path_off, ps_path, g_off, g_pv, g_unk, g_status));
-    r.ps_status = ps_status; r.ps_seg_off = ps_seg_off; r.ps_counts = ps_counts; r.g_status = g_status; r.g_off = g_off; r.g_pv = g_pv; r.g_unk = g_unk;
+    double* g_pv;
+    uint8_t* g_unk;
+    VIGO_TRY(carve(h, vigo::kBufReguide2, kSlack, [&](void* p) { return vigo::ws_reguide_pairs(p, P, g_pv, g_unk); }));
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, st.ps_seg_off, a.out_seg, a.out_path_off, a.out_path, st.g_off, g_pv, g_unk, st.g_status));
+    r.ps_status = st.ps_status; r.ps_seg_off = st.ps_seg_off; r.ps_counts = st.ps_counts; r.g_status = st.g_status; r.g_off = st.g_off; r.g_pv = g_pv; r.g_unk = g_unk;
     r.pair_cap = (long long)pair_cap;
     r.out_guide_off = out_guide_off; r.out_guide_pv = out_guide_pv; r.out_guide_unk = out_guide_unk; r.out_status = out_status;
     VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge_offsets(h->stream, r));
     long long merged = 0;
-    VIGO_HIP(h, hipMemcpyAsync(&merged, r.result + 1, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    VIGO_TRY(read_back(h, &merged, r.result + 1, sizeof(long long)));
     if (merged > (long long)pair_cap || merged > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the merged pairs do not fit pair_cap");
     VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge(h->stream, h->grid, r));
     if (!no_paths) {
-        VIGO_HIP(h, hipMemcpyAsync(out_path_seg_off, ps_seg_off, ((size_t)B + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
-        VIGO_HIP(h, hipMemcpyAsync(out_path_off, ps_path_off, ((size_t)total_seg + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (total_pts > 0) VIGO_HIP(h, hipMemcpyAsync(out_path, ps_path, (size_t)total_pts * 24, hipMemcpyDeviceToDevice, h->stream));
+        VIGO_HIP(h, hipMemcpyAsync(out_path_seg_off, st.ps_seg_off, ((size_t)B + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
+        VIGO_HIP(h, hipMemcpyAsync(out_path_off, a.out_path_off, ((size_t)total_seg + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (total_pts > 0) VIGO_HIP(h, hipMemcpyAsync(out_path, a.out_path, (size_t)total_pts * 24, hipMemcpyDeviceToDevice, h->stream));
     }
     VIGO_HIP(h, (hipError_t)vigo::launch_reguide_commit(h->stream, r));
     return VIGO_OK;
@@ -1097,16 +996,9 @@ int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_
         return fail(h, VIGO_ERR_INVALID_ARG, "vigo_build_esdf: plane is not 0 or 2, or a grid axis < 2");
     if (vigo::esdf_empty_d2(g.nx, g.ny, g.nz) == 0)
         return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_build_esdf: nx^2 + ny^2 + nz^2 > 2^30 or more than 2^33 voxels");
-    const size_t bytes = vigo::esdf_build_ws_bytes(g.nx, g.ny, g.nz);
-    if (bytes > h->esdf_ws_bytes) {
-        if (h->esdf_ws) (void)hipFree(h->esdf_ws);
-        h->esdf_ws = nullptr;
-        h->esdf_ws_bytes = 0;
-        VIGO_HIP(h, hipMalloc(&h->esdf_ws, bytes));
-        h->esdf_ws_bytes = bytes;
-    }
-    int32_t* a = static_cast<int32_t*>(h->esdf_ws);
-    int32_t* b = a + (size_t)g.nx * g.ny * g.nz;
+    const size_t voxels = (size_t)g.nx * g.ny * g.nz;
+    int32_t *a, *b;
+    VIGO_TRY(carve(h, vigo::kBufEsdfWs, kExact, [&](void* p) { return vigo::ws_pair(p, voxels, a, b); }));   // = esdf_build_ws_bytes(): 1 GiB at 512^3
     float* lattice = out_lattice_dev ? out_lattice_dev : reinterpret_cast<float*>(a);
     VIGO_HIP(h, (hipError_t)vigo::launch_esdf_build(h->stream, g, plane, unknown_is_site != 0, a, b, lattice));
     return install_esdf(h, g.nx, g.ny, g.nz, g.origin, g.res, lattice);

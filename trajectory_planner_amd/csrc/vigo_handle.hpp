@@ -1,0 +1,70 @@
+// vigo_handle.hpp — what a vigo_handle_t points to.  Only vigo_api.cpp includes this: the handle is opaque to the kernel
+// files and to everything above the ABI.
+#pragma once
+
+#include <string>
+
+#include "vigo_internal.hpp"
+
+namespace vigo {
+
+// A grow-only device allocation.  reserve() (vigo_api.cpp) is the only code that allocates one, vigo_destroy's loop over
+// vigo_context::buf the only code that frees one for good.
+struct DevBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T* as() const { return static_cast<T*>(ptr); }
+};
+
+// The handle's buffers, with what they grow to (reserve()'s callers) and what a growth invalidates:
+enum BufId {
+    kBufGrid,        // the packed voxel snapshot: exact size
+    kBufEsdf,        // the bricked ESDF: exact size; growing drops has_esdf and esdf_view.dist until the new field is in
+    kBufEsdfWs,      // vigo_build_esdf's two int32 buffers (vigo_esdf_build.hip): exact size (1 GiB at 512^3)
+    kBufFit,         // least-squares operator of the B-spline fit, transposed (vigo_fit.hip): exact size; growing clears fit_K
+    kBufTimes,       // the gates' sample clock: T + 64 doubles; growing clears times_T
+    kBufScratch,     // per-call scratch of most entry points and staging of the *_host calls: need + 25 % + 4 KiB
+    kBufPaths0,      // vigo_path_search: sized by the call's first-choice and (kBufPaths1) second-choice searches,
+    kBufPaths1,      //   need + 25 % + 4 KiB
+    kBufReguide0,    // vigo_rebound_reguide: per trajectory and control point, (1) the searches' segments and paths,
+    kBufReguide1,    //   (2) the new pairs; need + 25 % + 4 KiB
+    kBufReguide2,
+    kBufRebound,     // vigo_rebound_rounds: flags + compacted indices, B + 16 int32 + 64 bytes (its own allocation: the
+                     //   scratch buffer serves other entry points between the rounds' launches)
+    kBufCount
+};
+
+}  // namespace vigo
+
+// Everything an entry point keeps between calls.  Device memory is either fixed-size and made by vigo_create (dc_dev,
+// dc_stage, the events) or one of buf[]; the caches below (grid, esdf_view, fit_*, times_*) describe what a buffer holds.
+struct vigo_context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    vigo_params_t params;
+    vigo::DevConst dc;
+    vigo::DevConst* dc_dev = nullptr;  // device copy, refreshed by vigo_set_params IN STREAM ORDER (see there)
+    // pinned staging ring for those refreshes: slot i may be rewritten once dc_event[i] (its last copy) is done
+    static constexpr int kDcSlots = 4;
+    vigo::DevConst* dc_stage = nullptr;   // hipHostMalloc'ed [kDcSlots]
+    hipEvent_t dc_event[kDcSlots] = {};
+    int dc_next = 0;
+    int precision = VIGO_PREC_F64;
+    vigo::LaunchState launch;
+    std::string last_error;
+    vigo::DevBuffer buf[vigo::kBufCount];
+    // voxel snapshot (kBufGrid)
+    vigo::GridView grid{};
+    bool has_grid = false;
+    // esdf (kBufEsdf)
+    vigo::EsdfView esdf_view{};
+    bool has_esdf = false;
+    // kBufFit holds the operator for (fit_K, fit_ts); fit_K == 0: none
+    int fit_K = 0;
+    double fit_ts = 0.0;
+    // kBufTimes holds the clock of (times_dt, times_tmax), filled on times_stream; times_T < 0: none
+    double times_dt = -1.0, times_tmax = -1.0;
+    int times_T = -1;
+    hipStream_t times_stream = nullptr;
+};

@@ -1,10 +1,10 @@
 // vigo_internal.hpp — host-side types shared by the C-ABI layer and the kernel launchers.
-// Not part of the public boundary (that is include/vigo.h).
+// Not part of the public boundary (that is include/vigo.h).  The handle itself (vigo_handle.hpp) is not in here: the kernel
+// files cannot depend on it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string>
 
 #include "../../include/vigo.h"
 
@@ -302,55 +302,3 @@ int launch_guide_merge(hipStream_t s, const GridView& g, const ReguideArgs& a);
 int launch_reguide_commit(hipStream_t s, const ReguideArgs& a);
 
 }  // namespace vigo
-
-struct vigo_context {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    vigo_params_t params;
-    vigo::DevConst dc;
-    vigo::DevConst* dc_dev = nullptr;  // device copy, refreshed by vigo_set_params IN STREAM ORDER (see there)
-    // pinned staging ring for those refreshes: slot i may be rewritten once dc_event[i] (its last copy) is done
-    static constexpr int kDcSlots = 4;
-    vigo::DevConst* dc_stage = nullptr;   // hipHostMalloc'ed [kDcSlots]
-    hipEvent_t dc_event[kDcSlots] = {};
-    int dc_next = 0;
-    int precision = VIGO_PREC_F64;
-    vigo::LaunchState launch;
-    std::string last_error;
-    // voxel snapshot
-    uint32_t* grid_planes = nullptr;
-    size_t grid_capacity_bytes = 0;
-    vigo::GridView grid{};
-    bool has_grid = false;
-    // esdf
-    float* esdf = nullptr;
-    size_t esdf_capacity = 0;
-    vigo::EsdfView esdf_view{};
-    bool has_esdf = false;
-    // vigo_build_esdf: the passes' two int32 buffers (vigo_esdf_build.hip), grown on demand
-    void* esdf_ws = nullptr;
-    size_t esdf_ws_bytes = 0;
-    // least-squares operator of the B-spline fit for (fit_K, fit_ts), transposed (vigo_fit.hip)
-    double* fit_pinvT = nullptr;
-    size_t fit_capacity = 0;   // doubles
-    int fit_K = 0;
-    double fit_ts = 0.0;
-    // sample clock of the gates, cached per (dt, tmax): filled on the device, no host round trip per call
-    double* times_dev = nullptr;
-    size_t times_cap = 0;      // doubles
-    double times_dt = -1.0, times_tmax = -1.0;
-    int times_T = -1;
-    hipStream_t times_stream = nullptr;
-    // vigo_rebound_rounds: count (16 ints, first used) + compacted indices
-    int32_t* rebound_idx = nullptr;
-    size_t rebound_cap = 0;    // trajectories
-    // scratch (sample-time tables, corridor checkpoints, staging of *_host calls)
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    // vigo_path_search: the buffers sized by the call's first-choice ([0]) and second-choice ([1]) searches
-    void* paths_ws[2] = {nullptr, nullptr};
-    size_t paths_ws_bytes[2] = {0, 0};
-    // vigo_rebound_reguide: [0] per trajectory and control point, [1] the searches' segments and paths, [2] the new pairs
-    void* reguide_ws[3] = {nullptr, nullptr, nullptr};
-    size_t reguide_ws_bytes[3] = {0, 0, 0};
-};
