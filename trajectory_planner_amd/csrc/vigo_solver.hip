@@ -13,6 +13,9 @@
 //   * a trajectory whose control points all lie at one height (and no z planning) cannot move in z by more than
 //     rounding noise: the LEVEL RULE (include/vigo.h) holds its z fixed, and waves of such trajectories run the
 //     D = 2 instantiation of the solve kernel, which carries x and y only — 2/3 of the history, dots and stencils.
+//     On fp64 reference-order batches of at most one trajectory per SIMD (N <= 32) every level trajectory gets a wave
+//     of its own instead, one COORDINATE per lane (the D = 1 instantiation, "AXIS" below): twice the waves on a chip
+//     that was half idle, every loop-carried vector one double per lane.
 //   * per-trajectory sums (cost terms, dot products) are: a per-point partial, the lane's
 //     points added in index order, then a butterfly all-reduce inside the group,
 //     v += lane[i ^ m], m = 1,2,..,GROUP/2 — a fixed tree, so results are deterministic and
@@ -158,6 +161,25 @@ __device__ __forceinline__ double xor32_sum2(double a, double b) {
     auto h = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
     return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
 }
+// AXIS layout (k_optimize with D == 1): lane l < 32 holds coordinate 0 of control point l, lane l + 32 coordinate 1
+// of the same point.  v_permlane32_swap of a value with a copy of itself hands EVERY lane both: x = what the lower
+// half holds, y = what the upper half holds, so x + y is the same add, operands in the same order, in both lanes.
+__device__ __forceinline__ void xy_parts(double a, double b, double& x, double& y) {   // a == b bitwise, in two registers
+    const int alo = __double2loint(a), ahi = __double2hiint(a), blo = __double2loint(b), bhi = __double2hiint(b);
+    auto l = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
+    auto h = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
+    x = __hiloint2double(h[0], l[0]);
+    y = __hiloint2double(h[1], l[1]);
+}
+__device__ __forceinline__ void xy_both(double v, double& x, double& y) { xy_parts(v, v, x, y); }
+__device__ __forceinline__ double mul_f64_again(double a, double b) {   // as add_f64_again: the copy the swap needs
+    double r;
+    asm volatile("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// a0 * b0 + a1 * b1 of a point whose two coordinates sit on lanes l and l + 32: dot3<false, T, 2> across the pair
+__device__ __forceinline__ double dot_xy(double a, double b) { return xor32_sum2(a * b, mul_f64_again(a, b)); }
+
 template <int GROUP, int K>
 __device__ __forceinline__ void group_sum(double (&v)[K]) {
     static_assert(GROUP == 16 || GROUP == 32 || GROUP == 64, "group is a DPP row, half a wave or a wave");
@@ -241,10 +263,15 @@ __device__ __forceinline__ double dot3(const T (&a)[3], const T (&b)[3]) {
 // lane partial of a dot product: the lane's first point, then its other points in index order
 template <bool FAST, typename T, int PPL, int D = 3>
 __device__ __forceinline__ double dot_lane(const T (&a)[PPL][3], const T (&b)[PPL][3]) {
-    double s = dot3<FAST, T, D>(a[0], b[0]);
+    if constexpr (D == 1) {   // AXIS: the lane's one coordinate, then the xor-32 exchange — the add dot3<.., 2> does
+        static_assert(!FAST && PPL == 1, "the axis-per-lane layout is reference order, one point per lane pair");
+        return dot_xy((double)a[0][0], (double)b[0][0]);
+    } else {
+        double s = dot3<FAST, T, D>(a[0], b[0]);
 #pragma unroll
-    for (int q = 1; q < PPL; ++q) s += dot3<FAST, T, D>(a[q], b[q]);
-    return s;
+        for (int q = 1; q < PPL; ++q) s += dot3<FAST, T, D>(a[q], b[q]);
+        return s;
+    }
 }
 
 // ys of a history pair as the two-loop uses it (LB:1300, :1312 divide by it).  FAST keeps only the
@@ -324,15 +351,13 @@ struct LaneProblem {
 
 // One guide pair's contribution, BT.cpp:839-895.  e == dthresh takes the cubic branch (first
 // else-if wins); the "too far" branch is never scaled by the unknown factor.
-template <bool FAST, typename T>
-__device__ __forceinline__ void guide_pair_term(const DevConst& K, const T (&c)[3], T px, T py, T pz, T vx,
-                                                T vy, T vz, bool unk, double& cd, T (&Gd)[3]) {
-    const T dth = (T)K.dth, da = (T)K.da, db = (T)K.db, dcc = (T)K.dc, uf = (T)K.unc_factor;
-    const T dist = FAST ? fmaT(c[2] - pz, vz, fmaT(c[1] - py, vy, (c[0] - px) * vx))
-                        : ((c[0] - px) * vx + (c[1] - py) * vy) + (c[2] - pz) * vz;
+// the penalty at signed distance `dist` from the pair's plane: cost ct, gradient factor k along the pair's direction,
+// and whether the unknown factor scales both; false in the no-penalty band
+template <typename T>
+__device__ __forceinline__ bool guide_penalty(const DevConst& K, T dist, bool unk, T& ct, T& k, bool& scale) {
+    const T dth = (T)K.dth, da = (T)K.da, db = (T)K.db, dcc = (T)K.dc;
     const T e = dth - dist;
-    T ct, k;
-    bool scale = false;
+    scale = false;
     if (e <= -dth) {
         const T ne = -e;
         ct = (ne * ne) * ne;
@@ -346,13 +371,41 @@ __device__ __forceinline__ void guide_pair_term(const DevConst& K, const T (&c)[
         k = -((T(2) * da) * e + db);
         scale = unk;
     } else {
-        return;  // -dthresh < e <= 0 (or NaN): no penalty
+        return false;  // -dthresh < e <= 0 (or NaN): no penalty
     }
+    return true;
+}
+template <bool FAST, typename T>
+__device__ __forceinline__ void guide_pair_term(const DevConst& K, const T (&c)[3], T px, T py, T pz, T vx,
+                                                T vy, T vz, bool unk, double& cd, T (&Gd)[3]) {
+    const T uf = (T)K.unc_factor;
+    const T dist = FAST ? fmaT(c[2] - pz, vz, fmaT(c[1] - py, vy, (c[0] - px) * vx))
+                        : ((c[0] - px) * vx + (c[1] - py) * vy) + (c[2] - pz) * vz;
+    T ct, k;
+    bool scale;
+    if (!guide_penalty<T>(K, dist, unk, ct, k, scale)) return;
     T gx = k * vx, gy = k * vy, gz = k * vz;
     if (scale) { ct *= uf; gx *= uf; gy *= uf; gz *= uf; }
     if (!K.plan_in_z) gz = T(0.0);
     cd += (double)ct;
     Gd[0] += gx; Gd[1] += gy; Gd[2] += gz;
+}
+// The same term in the AXIS layout (level trajectory, reference order): c, p, v are THIS lane's coordinate of the
+// point, of the pair's position and of its direction.  Each lane forms its own product, the xor-32 exchange adds the
+// two in the order above, the z product follows; both lanes of a point then hold the same dist, take the same branch
+// and count the same cost (callers reduce it over one half of the wave only), and each scales its own v for the gradient.
+// Must be reached by both lanes of a point together: the exchange reads the partner lane.
+__device__ __forceinline__ void guide_pair_term_axis(const DevConst& K, double c, double cz, double p, double pz, double v,
+                                                     double vz, bool unk, double& cd, double& Gd) {
+    const double uf = K.unc_factor;
+    const double dist = dot_xy(c - p, v) + (cz - pz) * vz;
+    double ct, k;
+    bool scale;
+    if (!guide_penalty<double>(K, dist, unk, ct, k, scale)) return;
+    double gc = k * v;
+    if (scale) { ct *= uf; gc *= uf; }
+    cd += ct;
+    Gd += gc;
 }
 
 // One dynamic obstacle's contribution to one control point, BT.cpp:1011-1059: the obstacle at its
@@ -409,6 +462,67 @@ __device__ __forceinline__ void obstacle_term_tab(const DevConst& K, const T (&c
     }
 }
 
+// The smoothness and feasibility stencils of ONE coordinate, C = that coordinate of the lane's points: jerk, velocity
+// and acceleration terms (jj, vv, aa: the cost partials of the term whose first point is the lane's) and the gradient
+// columns Gs, Gf of the lane's points.  no_terms: the z coordinate of a level trajectory in the general kernel.
+template <typename T, int PPL, bool FAST>
+__device__ __forceinline__ void stencil_axis(const DevConst& K, const T (&C)[PPL], bool no_terms, double (&jj)[PPL],
+                                             double (&vv)[PPL], double (&aa)[PPL], T (&Gs)[PPL], T (&Gf)[PPL]) {
+    const T ts = (T)K.ts_ctrl, tis = (T)K.ts_inv_sqr;
+    auto excess = [](T v) -> T { return v > T(1.0) ? v - T(1.0) : (v < T(-1.0) ? v + T(1.0) : T(0.0)); };
+    T P1[PPL], P2[PPL], P3[PPL];
+    seq_next<T, PPL>(C, P1);
+    seq_next<T, PPL>(P1, P2);
+    seq_next<T, PPL>(P2, P3);
+    T gt0[PPL], gv[PPL], ga[PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        // smoothness, BT.cpp:934-950
+        T J0 = FAST ? fmaT(T(3), P1[q], fmaT(T(-3), P2[q], P3[q])) - C[q]
+                    : ((P3[q] - 3 * P2[q]) + 3 * P1[q]) - C[q];
+        if (no_terms) J0 = T(0);                                       // level rule: no z terms
+        gt0[q] = T(2.0) * J0;                                          // gradTemp
+        jj[q] = (double)(J0 * J0);
+        // feasibility, BT.cpp:952-999 (limits hard-coded to 1.0, :955-956)
+        T evP = excess((P1[q] - C[q]) / ts);                           // velocity i
+        T eaP = excess((FAST ? fmaT(T(-2), P1[q], P2[q]) + C[q]
+                             : (P2[q] - 2 * P1[q]) + C[q]) * tis);     // acceleration i
+        if (no_terms) { evP = T(0); eaP = T(0); }
+        // gradient(j,i+1) += 2(v-vmax)/ts*tsInvSqr, gradient(j,i) += the negation (exactly)
+        gv[q] = (T(2) * evP) / ts * tis;
+        // gradient(j,i), (j,i+2) += 2(a-amax)*tsInvSqr; gradient(j,i+1) += -4(..) = -2x that (exactly)
+        ga[q] = (T(2) * eaP) * tis;
+        vv[q] = (double)((evP * evP) * tis);
+        aa[q] = (double)(eaP * eaP);
+    }
+    T gt1[PPL], gt2[PPL], gt3[PPL], gvM[PPL], gaM1[PPL], gaM2[PPL];
+    seq_prev<T, PPL>(gt0, gt1);
+    seq_prev<T, PPL>(gt1, gt2);
+    seq_prev<T, PPL>(gt2, gt3);
+    seq_prev<T, PPL>(gv, gvM);
+    seq_prev<T, PPL>(ga, gaM1);
+    seq_prev<T, PPL>(gaM1, gaM2);
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        T acc = gt3[q];                    // i-3: col(i+3) += gradTemp
+        if (FAST) {
+            acc = fmaT(T(-3.0), gt2[q], acc);
+            acc = fmaT(T(3.0), gt1[q], acc);
+        } else {
+            acc += T(-3.0) * gt2[q];       // i-2: col(i+2) += -3*gradTemp
+            acc += T(3.0) * gt1[q];        // i-1: col(i+1) += 3*gradTemp
+        }
+        acc += -gt0[q];                    // i  : col(i)   += -gradTemp
+        Gs[q] = acc;
+        T fcc = gvM[q];                    // i-1: gradient(j,i+1)
+        fcc += -gv[q];                     // i  : gradient(j,i)
+        fcc += gaM2[q];                    // i-2: gradient(j,i+2)
+        fcc += -(T(2) * gaM1[q]);          // i-1: gradient(j,i+1)
+        fcc += ga[q];                      // i  : gradient(j,i)
+        Gf[q] = fcc;
+    }
+}
+
 // ---- cost + gradient at the points held in c (BT.cpp:802-821) ---------------------------
 // T is the element type of points/gradients; sums are fp64.  g receives the weighted gradient
 // of the free points, 0 elsewhere.  ONE 7-value group reduction returns
@@ -438,8 +552,6 @@ __device__ __forceinline__ double eval_cost_grad(const DevConst& K, const LanePr
     // SAME expressions evaluated at the points below, fetched with register renames / DPP shifts —
     // identical bits, no recomputation (and half the fp64 divisions by ts).
     {
-        const T ts = (T)K.ts_ctrl, tis = (T)K.ts_inv_sqr;
-        auto excess = [](T v) -> T { return v > T(1.0) ? v - T(1.0) : (v < T(-1.0) ? v + T(1.0) : T(0.0)); };
         double jj[PPL][3], vv[PPL][3], aa[PPL][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -448,59 +560,13 @@ __device__ __forceinline__ double eval_cost_grad(const DevConst& K, const LanePr
                 for (int q = 0; q < PPL; ++q) { jj[q][a] = vv[q][a] = aa[q][a] = 0.0; Gs[q][a] = Gf[q][a] = T(0); }
                 continue;
             }
-            T C[PPL], P1[PPL], P2[PPL], P3[PPL];
+            T C[PPL], GsA[PPL], GfA[PPL];
+            double jjA[PPL], vvA[PPL], aaA[PPL];
 #pragma unroll
             for (int q = 0; q < PPL; ++q) C[q] = c[q][a];
-            seq_next<T, PPL>(C, P1);
-            seq_next<T, PPL>(P1, P2);
-            seq_next<T, PPL>(P2, P3);
-            T gt0[PPL], gv[PPL], ga[PPL];
+            stencil_axis<T, PPL, FAST>(K, C, a == 2 && Q.level, jjA, vvA, aaA, GsA, GfA);
 #pragma unroll
-            for (int q = 0; q < PPL; ++q) {
-                // smoothness, BT.cpp:934-950
-                T J0 = FAST ? fmaT(T(3), P1[q], fmaT(T(-3), P2[q], P3[q])) - C[q]
-                            : ((P3[q] - 3 * P2[q]) + 3 * P1[q]) - C[q];
-                if (a == 2 && Q.level) J0 = T(0);                              // level rule: no z terms
-                gt0[q] = T(2.0) * J0;                                          // gradTemp
-                jj[q][a] = (double)(J0 * J0);
-                // feasibility, BT.cpp:952-999 (limits hard-coded to 1.0, :955-956)
-                T evP = excess((P1[q] - C[q]) / ts);                           // velocity i
-                T eaP = excess((FAST ? fmaT(T(-2), P1[q], P2[q]) + C[q]
-                                     : (P2[q] - 2 * P1[q]) + C[q]) * tis);     // acceleration i
-                if (a == 2 && Q.level) { evP = T(0); eaP = T(0); }
-                // gradient(j,i+1) += 2(v-vmax)/ts*tsInvSqr, gradient(j,i) += the negation (exactly)
-                gv[q] = (T(2) * evP) / ts * tis;
-                // gradient(j,i), (j,i+2) += 2(a-amax)*tsInvSqr; gradient(j,i+1) += -4(..) = -2x that (exactly)
-                ga[q] = (T(2) * eaP) * tis;
-                vv[q][a] = (double)((evP * evP) * tis);
-                aa[q][a] = (double)(eaP * eaP);
-            }
-            T gt1[PPL], gt2[PPL], gt3[PPL], gvM[PPL], gaM1[PPL], gaM2[PPL];
-            seq_prev<T, PPL>(gt0, gt1);
-            seq_prev<T, PPL>(gt1, gt2);
-            seq_prev<T, PPL>(gt2, gt3);
-            seq_prev<T, PPL>(gv, gvM);
-            seq_prev<T, PPL>(ga, gaM1);
-            seq_prev<T, PPL>(gaM1, gaM2);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) {
-                T acc = gt3[q];                    // i-3: col(i+3) += gradTemp
-                if (FAST) {
-                    acc = fmaT(T(-3.0), gt2[q], acc);
-                    acc = fmaT(T(3.0), gt1[q], acc);
-                } else {
-                    acc += T(-3.0) * gt2[q];       // i-2: col(i+2) += -3*gradTemp
-                    acc += T(3.0) * gt1[q];        // i-1: col(i+1) += 3*gradTemp
-                }
-                acc += -gt0[q];                    // i  : col(i)   += -gradTemp
-                Gs[q][a] = acc;
-                T fcc = gvM[q];                    // i-1: gradient(j,i+1)
-                fcc += -gv[q];                     // i  : gradient(j,i)
-                fcc += gaM2[q];                    // i-2: gradient(j,i+2)
-                fcc += -(T(2) * gaM1[q]);          // i-1: gradient(j,i+1)
-                fcc += ga[q];                      // i  : gradient(j,i)
-                Gf[q][a] = fcc;
-            }
+            for (int q = 0; q < PPL; ++q) { jj[q][a] = jjA[q]; vv[q][a] = vvA[q]; aa[q][a] = aaA[q]; Gs[q][a] = GsA[q]; Gf[q][a] = GfA[q]; }
         }
 #pragma unroll
         for (int q = 0; q < PPL; ++q) {
@@ -610,6 +676,72 @@ __device__ __forceinline__ double eval_cost_grad(const DevConst& K, const LanePr
     return ((Q.w[0] * part[0] + Q.w[1] * part[1]) + Q.w[2] * part[2]) + Q.w[3] * part[3];
 }
 
+// The same evaluation in the AXIS layout: a level trajectory (fp64 reference order, no obstacles) on one whole wave,
+// lane l < 32 holding coordinate 0 of control point l and lane l + 32 coordinate 1 (axis = lane >> 5).  c[0][0], d[0][0],
+// g[0][0] are the lane's coordinate, c[0][2] the point's z (both lanes hold it; it never moves); Q.gq[j][0] / [3] hold
+// the lane's coordinate of the register-held pairs (axis_guides()).  The stencils run on the lane's axis alone, inside its
+// half of the wave.  Wherever eval_cost_grad<.., D = 2> adds the x term and the y term of a point, the xor-32 exchange
+// hands both lanes both terms and they add them in that order; what follows (the exact-zero z terms, the 32-lane tree)
+// is then the same in both halves, which end with the same bits in every sum — and so with the same line-search scalars.
+__device__ __forceinline__ double eval_cost_grad_axis(const DevConst& K, const LaneProblem<double, 1>& Q, int axis,
+                                                      const double (&c)[1][3], const double (&d)[1][3], double (&g)[1][3],
+                                                      double (&sums)[7]) {
+    using LP = LaneProblem<double, 1>;
+    const int N = Q.N, p = Q.p0;
+    const double C[1] = {c[0][0]};
+    const double cz = c[0][2];
+    double jj[1], vv[1], aa[1], Gs[1], Gf[1];
+    stencil_axis<double, 1, false>(K, C, false, jj, vv, aa, Gs, Gf);
+    double j0, j1, v0, v1, a0, a1;
+    xy_both(jj[0], j0, j1);
+    xy_both(vv[0], v0, v1);
+    xy_both(aa[0], a0, a1);
+    // (the trailing zeros are the z terms of eval_cost_grad<.., D = 2>, kept where it adds them)
+    double pt_s = 0.0, pt_f = 0.0, pt_d = 0.0;
+    if (Q.has_pt[0] && p <= N - 4) pt_s = sum3(j0, j1, 0.0);
+    if (Q.has_pt[0] && p <= N - 2) pt_f = (v0 + v1) + 0.0;
+    if (Q.has_pt[0] && p <= N - 3) { pt_f += a0; pt_f += a1; pt_f += 0.0; }
+
+    // ---- guide-point distance: both lanes of a point enter together (interior and the pair range are per point) ----
+    double Gd = 0.0;
+    if (Q.interior[0]) {
+        double cd = 0.0;
+        const int cnt = Q.g_end[0] - Q.g_begin[0];
+#pragma unroll
+        for (int j = 0; j < LP::kGuideRegs; ++j) {
+            if (j < cnt) guide_pair_term_axis(K, C[0], cz, Q.gq[j][0], Q.gq[j][2], Q.gq[j][3], Q.gq[j][5], Q.gqu[j], cd, Gd);
+        }
+        for (int j = Q.g_begin[0] + LP::kGuideRegs; j < Q.g_end[0]; ++j) {
+            const double* pv = Q.gpv + 6 * (size_t)j;
+            guide_pair_term_axis(K, C[0], cz, pv[axis], pv[2], pv[3 + axis], pv[5], Q.gunk ? (Q.gunk[j] != 0) : false, cd, Gd);
+        }
+        pt_d = cd;
+    }
+
+    const double w0 = Q.w[0], w1 = Q.w[1], w2 = Q.w[2], w3 = Q.w[3];
+    const double Go = 0.0;
+    g[0][0] = !Q.interior[0] ? 0.0 : ((w0 * Gd + w1 * Gs[0]) + w2 * Gf[0]) + w3 * Go;
+    g[0][1] = g[0][2] = 0.0;
+    double p6[6];
+    p6[0] = pt_d; p6[1] = pt_s; p6[2] = pt_f;
+    p6[3] = dot_xy(g[0][0], d[0][0]);
+    const double xx = dot_xy(C[0], C[0]) + cz * cz;                          // (x.x: the level coordinate counts)
+    p6[4] = Q.interior[0] ? xx : 0.0;
+    p6[5] = dot_xy(g[0][0], g[0][0]);
+    group_sum<32, 6>(p6);
+    sums[0] = p6[0]; sums[1] = p6[1]; sums[2] = p6[2]; sums[3] = 0.0; sums[4] = p6[3]; sums[5] = p6[4]; sums[6] = p6[5];
+    return ((Q.w[0] * sums[0] + Q.w[1] * sums[1]) + Q.w[2] * sums[2]) + Q.w[3] * sums[3];
+}
+
+// AXIS layout: keep this lane's coordinate of the register-held guide pairs where eval_cost_grad_axis() reads it
+__device__ __forceinline__ void axis_guides(LaneProblem<double, 1>& Q, int axis) {
+#pragma unroll
+    for (int j = 0; j < LaneProblem<double, 1>::kGuideDim; ++j) {
+        Q.gq[j][0] = axis ? Q.gq[j][1] : Q.gq[j][0];
+        Q.gq[j][3] = axis ? Q.gq[j][4] : Q.gq[j][3];
+    }
+}
+
 template <typename T, int GROUP, int PPL>
 __device__ __forceinline__ void load_problem(const SolveArgs& A, const DevConst& K, int b, int lane_in_group,
                                              LaneProblem<T, PPL>& Q) {
@@ -697,6 +829,15 @@ __device__ __forceinline__ void store_points(const SolveArgs& A, int b, const La
             dst[0] = (double)x[q][0]; dst[1] = (double)x[q][1]; dst[2] = (double)x[q][2];
         }
     }
+}
+
+// AXIS layout (k_optimize, D == 1): each lane stores the coordinate it holds, the lane of coordinate 0 the point's z too
+// (as it was loaded — the level rule — unless a two-loop coefficient was not finite, see dz in k_optimize)
+__device__ __forceinline__ void store_point_axis(const SolveArgs& A, int b, const LaneProblem<double, 1>& Q, int axis, double v, double z) {
+    if (!Q.has_pt[0]) return;
+    double* dst = A.ctrl + ((size_t)b * A.N + Q.p0) * 3;
+    dst[axis] = v;
+    if (axis == 0) dst[2] = z;
 }
 
 // ---- standalone cost/gradient kernel (vigo_cost_grad) ----------------------------------
@@ -880,11 +1021,20 @@ __device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd
 template <typename T, int GROUP, int PPL, bool FAST, int WPS = 1, bool OBS = true, int D = 3, int RH = (PPL == 1 ? 1 : 0)>
 __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevConst* __restrict__ Kp) {
     static_assert(PPL == 1 ? (RH >= 1 && RH <= 6) : RH == 0, "register-held history only with one point per lane");
+    // AXIS (D == 1): a level trajectory on a whole wave, one COORDINATE per lane — lane l < 32 holds coordinate 0 of
+    // control point l, lane l + 32 coordinate 1 of the same point (GROUP = 32 is then the lanes of one axis).  Every
+    // loop-carried vector is one double per lane, an axpy one instruction, a history record {s, y} of one axis; a
+    // dot product is one product, the xor-32 exchange (the add dot3<.., 2> does) and the 32-lane tree, so both halves
+    // hold the same bits in every scalar and nothing diverges inside the wave.  fp64 reference order, no obstacles.
+    constexpr bool AXIS = D == 1;
+    static_assert(!AXIS || (std::is_same<T, double>::value && GROUP == 32 && PPL == 1 && !FAST && !OBS),
+                  "the axis-per-lane layout: fp64 reference order, N <= 32, no obstacles");
     const DevConst& K = *Kp;  // uniform address: scalar loads at the use sites, not 100+ live SGPRs
-    constexpr int TPB = kWave / GROUP;
+    constexpr int TPB = AXIS ? 1 : kWave / GROUP;   // trajectories per wave
+    constexpr int COLS = kWave / GROUP;             // history columns per free control point index: trajectories, or axes
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int N = A.N, NI = N - 6;
-    const int ROW = TPB * NI;
+    const int ROW = COLS * NI;
     // one more column per slot that holds zeros for good: the history of every control point that is NOT free (the
     // three fixed points at either end, lanes beyond N).  Their s and y are identically zero, so the two-loop needs
     // no per-step select to keep their d at zero (two v_cndmask on the dependent chain of each of its 32 steps).
@@ -904,8 +1054,9 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     double* ys_tab = reinterpret_cast<double*>(lds_raw + (size_t)ms * slotB);   // alphas, obstacle table
 
     const int lane = threadIdx.x;
-    const int grp = lane / GROUP;
-    int b = blockIdx.x * TPB + grp;
+    const int grp = lane / GROUP;            // the lane's trajectory within the wave; AXIS: its axis
+    const int tg = AXIS ? 0 : grp;           // the lane's trajectory within the wave
+    int b = blockIdx.x * TPB + tg;
     if (A.active_idx) {                       // vigo_rebound_rounds: the compacted active set
         if (b >= *A.active_count) return;
         b = A.active_idx[b];
@@ -919,8 +1070,12 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     // elsewhere (their g, d, s, y are identically zero so they never move).
     T x[PPL][3];
     load_points<T, PPL>(A, b, Q, x);
-    set_level<T, GROUP, PPL>(K, Q, x);
-    {
+    set_level<T, GROUP, PPL>(K, Q, x);       // (AXIS: both halves hold the point's z and get the same answer)
+    if constexpr (AXIS) {
+        if (!Q.level) return;                // solved by the general kernel, which follows
+        x[0][0] = grp ? x[0][1] : x[0][0];
+        axis_guides(Q, grp);
+    } else {
         // A solve is launched as ONE general kernel (D = 3), or — calls without obstacles, one point per lane — as the
         // D = 2 instantiation, which carries only x and y through the recursion (two thirds of the history in LDS, of
         // the dot products and of the stencils), followed by the general kernel: a wave whose trajectories are ALL
@@ -931,6 +1086,15 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         if (D == 2 && !wave_level) return;
         if (D == 3 && A.level_waves_elsewhere && wave_level) return;
     }
+    // level_waves_elsewhere == 2: EVERY level trajectory has been solved by the axis-per-lane launch, also one that
+    // shares this wave with a trajectory that is not level.  Its group leaves below, once the zero column is written
+    // (the lanes that write it may be its own), and the other group goes on alone — as it already does whenever its
+    // line search takes more evaluations than its partner's.  Every wave-wide operation from there on acts on the
+    // active lanes only and is used that way: the DPP rows and v_permlane16_swap of the reductions stay inside a
+    // group; readfirstlane(bound) and readfirstlane(last) read the first ACTIVE lane, and the __any over `last` and
+    // over the two-loop's range flag see the remaining group alone, as they see one trajectory in the last wave of
+    // an odd batch; the single-wave __syncthreads does not wait for lanes that have returned.
+    const bool solved_elsewhere = D == 3 && A.level_waves_elsewhere == 2 && Q.level;
 #if VIGO_PROFILE_SECTIONS
     long long tick_ = (long long)__builtin_readcyclecounter();
     double t_eval = 0, t_ls = 0, t_upd = 0, t_two = 0, t_tail = 0, t_pre = 0, t_trial = 0, t_cal = 0;
@@ -949,8 +1113,9 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         *reinterpret_cast<HPair<T, D>*>(lds_raw + (size_t)slot * slotB + (size_t)ROW * sizeof(HPair<T, D>)) = zero;
     }
     __syncthreads();   // one wave per workgroup: orders the zero column before the first history read
-    YS* ys_l = reinterpret_cast<YS*>(lds_raw + (size_t)ROWP * sizeof(HPair<T, D>)) + grp;   // slot 0; slot k at + k * slotB bytes
-    double* al_l = ys_tab + grp;
+    if (solved_elsewhere) return;
+    YS* ys_l = reinterpret_cast<YS*>(lds_raw + (size_t)ROWP * sizeof(HPair<T, D>)) + tg;   // slot 0; slot k at + k * slotB bytes
+    double* al_l = ys_tab + tg;
     auto hist_at = [&](int q, int slot) -> HPair<T, D>& {
         return *reinterpret_cast<HPair<T, D>*>(reinterpret_cast<char*>(hl[q]) + (size_t)slot * slotB);
     };
@@ -999,6 +1164,12 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int j = 0; j < kRH; ++j) sR[j][q][a] = yR[j][q][a] = T(0);
+    // AXIS: the z coordinate.  Under the level rule its g, s and y are exact zeros and its d is -0 through every step of a
+    // two-loop whose coefficients are finite, so z + step * d is z: nothing to carry.  A coefficient that is NOT finite
+    // (ys = 0, see below) makes that d a NaN (0 * inf) in the general kernel and in the oracle, and the next trial point's
+    // z with it.  The d of a control point that is not free goes through the same operations on the same zeros: dz is
+    // lane 0's, taken once per iteration, and the trial point's z is formed from it as the general kernel forms it.
+    T dz = T(-0.0);
     double sums[7];
     int evals = 0;
     int ret = LBERR_UNKNOWN;
@@ -1019,6 +1190,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
             for (int q = 0; q < PPL; ++q)
 #pragma unroll
                 for (int a = 0; a < D; ++a) { xp[q][a] = x[q][a]; gp[q][a] = g[q][a]; }  // LB:1172-1173
+            if constexpr (AXIS) xp[0][2] = x[0][2];
             dginit = sums[4];  // g.d for the d just built (reduced at the end of the two-loop below)
             if (step <= 0.) { ls = LBERR_INVALIDPARAMETERS; run = false; }
             else if (0 < dginit) { ls = LBERR_INCREASEGRADIENT; run = false; }
@@ -1052,10 +1224,13 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 #pragma unroll
                     for (int a = 0; a < D; ++a)
                         x[q][a] = FAST ? fmaT((T)step, d[q][a], xp[q][a]) : xp[q][a] + (T)step * d[q][a];
+                if constexpr (AXIS) x[0][2] = xp[0][2] + (T)step * (Q.interior[0] ? dz : T(0));
             }
 
             VIGO_TICK(t_pre);
-            fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(K, Q, x, d, g, sums);  // the only evaluation site (LB:828, :1132)
+            // the only evaluation site (LB:828, :1132)
+            if constexpr (AXIS) fx = eval_cost_grad_axis(K, Q, grp, x, d, g, sums);
+            else fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(K, Q, x, d, g, sums);
             VIGO_TICK(t_eval);
             ++evals;
             if (first) break;
@@ -1122,11 +1297,13 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         if (ls < 0) {
             // LB:1189-1197.  optData_.controlPoints keeps the last trial (BT.cpp:803): write it
             // out now, then revert x like the reference does.
-            store_points<T, PPL>(A, b, Q, x);
+            if constexpr (AXIS) store_point_axis(A, b, Q, grp, x[0][0], x[0][2]);
+            else store_points<T, PPL>(A, b, Q, x);
 #pragma unroll
             for (int q = 0; q < PPL; ++q)
 #pragma unroll
                 for (int a = 0; a < D; ++a) { x[q][a] = xp[q][a]; g[q][a] = gp[q][a]; }
+            if constexpr (AXIS) x[0][2] = xp[0][2];
             ret = ls;
             break;
         }
@@ -1152,7 +1329,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         double ysyy[2] = {dot_lane<FAST, T, PPL, D>(yv, sv), dot_lane<FAST, T, PPL, D>(yv, yv)};
         // (level trajectory: the z product the general kernel adds here is (+0) * (+0); it turns a lane partial of -0 into
         // +0, and the sign of a zero ys decides the sign of the infinities the reference then divides into being)
-        if (D == 2) ysyy[0] += 0.0;
+        if (D <= 2) ysyy[0] += 0.0;    // (AXIS: after the exchange add, where the D = 2 kernel has it)
         group_sum<GROUP, 2>(ysyy);
         const double ys = ysyy[0], yy = ysyy[1];
         // the two-loop divides by ys of each pair (LB:1300, :1312); FAST keeps its reciprocal instead
@@ -1353,6 +1530,9 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         // points that are not free into NaN (0 * inf) — and through their lanes' partials every later dot product of
         // that two-loop, which oracle/vigo_oracle.c's emulation mirrors.  Those points never move: their d is reset
         // here, once per iteration instead of in every step.
+        if constexpr (AXIS)   // (lane 0 holds control point 0, which is never free; every lane of the wave is active here)
+            dz = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(d[0][0])),
+                                  __builtin_amdgcn_readfirstlane(__double2loint(d[0][0])));
 #pragma unroll
         for (int q = 0; q < PPL; ++q)
 #pragma unroll
@@ -1396,12 +1576,20 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     }
 
     // results.  On success / convergence / iteration cap the last evaluated point is x itself.
-    if (ret >= 0 || ret == LBERR_MAXIMUMITERATION) store_points<T, PPL>(A, b, Q, x);
+    if (ret >= 0 || ret == LBERR_MAXIMUMITERATION) {
+        if constexpr (AXIS) store_point_axis(A, b, Q, grp, x[0][0], x[0][2]);
+        else store_points<T, PPL>(A, b, Q, x);
+    }
 #pragma unroll
     for (int q = 0; q < PPL; ++q) {
         if (Q.interior[q] && A.out_x) {
             double* dst = A.out_x + ((size_t)b * NI + (Q.p0 + q - 3)) * 3;
-            dst[0] = (double)x[q][0]; dst[1] = (double)x[q][1]; dst[2] = (double)x[q][2];
+            if constexpr (AXIS) {   // each lane its coordinate; z as loaded, by the lane of coordinate 0
+                dst[grp] = (double)x[q][0];
+                if (grp == 0) dst[2] = (double)x[q][2];
+            } else {
+                dst[0] = (double)x[q][0]; dst[1] = (double)x[q][1]; dst[2] = (double)x[q][2];
+            }
         }
     }
 #if VIGO_PROFILE_SECTIONS
@@ -1411,7 +1599,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         o[7] = t_pre; o[8] = t_trial; o[9] = t_cal;
     }
 #endif
-    if (lane % GROUP == 0) {
+    if (lane % (kWave / TPB) == 0) {   // the first lane of each trajectory
         if (A.out_status) A.out_status[(size_t)b * (A.status_stride ? A.status_stride : 1)] = ret;
         if (A.out_fx) A.out_fx[b] = fx;
         if (A.out_iters) A.out_iters[b] = k;
@@ -1421,10 +1609,11 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 
 template <typename T, int GROUP, bool FAST, int D = 3>
 size_t optimize_lds_bytes(int N, int m, int ppl, bool with_obstacles, int rh = 1) {
-    const int TPB = kWave / GROUP;
+    const int TPB = D == 1 ? 1 : kWave / GROUP;   // D == 1, the axis-per-lane layout: one trajectory per wave ...
+    const int COLS = kWave / GROUP;               // ... and a 16-byte record per free control point and AXIS
     const int ms = ppl == 1 ? (m > rh + 1 ? m - (rh + 1) : 0) : m;   // REG1: ages 0 .. rh live in registers
     // per slot: one record per free control point + the zero column, then {ys, 1/ys} per trajectory (see k_optimize)
-    const size_t slot = ((size_t)TPB * (N - 6) + 1) * sizeof(HPair<T, D>) + (((size_t)TPB * sizeof(YSv<FAST>) + 15) & ~(size_t)15);
+    const size_t slot = ((size_t)COLS * (N - 6) + 1) * sizeof(HPair<T, D>) + (((size_t)TPB * sizeof(YSv<FAST>) + 15) & ~(size_t)15);
     size_t h = (size_t)ms * slot;
     h += (size_t)m * TPB * sizeof(double);        // the alphas of the general two-loop
     if (with_obstacles) h += (size_t)TPB * kObsTabDoubles<GROUP> * sizeof(double);
@@ -1524,6 +1713,20 @@ static int raise_dynamic_lds(LaunchState& L, int slot, KernelT kernel) {
 // 3: 1.61, 5: 1.54).  32 < N <= 64 (one per wave): 5 pairs, 26.8 -> 19.2 KB, six -> eight: 1.85 -> 1.54 ms at 8192 x 64
 // (4 pairs, seven waves: 1.71; 6 pairs: 1.57).  Same arithmetic, same bits.
 constexpr int kLevelRH = 4, kLevelRH64 = 5;
+// dev builds only (-DVIGO_EXP_AXIS_SWITCH=1, tools/exp_solver.py): VIGO_EXP_AXIS=0 in the environment, read at every
+// launch, keeps the axis-per-lane level kernel out of the dispatch, so that one process times both — never defined
+// in the shipped library
+#ifndef VIGO_EXP_AXIS_SWITCH
+#define VIGO_EXP_AXIS_SWITCH 0
+#endif
+static inline bool axis_dispatch_on() {
+#if VIGO_EXP_AXIS_SWITCH
+    const char* e = getenv("VIGO_EXP_AXIS");
+    return !(e && e[0] == '0');
+#else
+    return true;
+#endif
+}
 template <typename T, int GROUP, int PPL, bool FAST, bool OBS>
 static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevConst& k, const DevConst* kd, LaunchState& L) {
     const int tpb = kWave / GROUP;
@@ -1544,7 +1747,7 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
     };
     // Calls that can hold level trajectories (no z planning) and have an instantiation for them are two launches: FIRST the
     // level kernel, whose waves with a trajectory that is not level exit at once, THEN the general kernel, whose waves
-    // of level trajectories do.  The order matters: each launch decides from the control points it finds; a level
+    // of level trajectories do (after the axis-per-lane launch: whose GROUPS of a level trajectory do).  The order matters: each launch decides from the control points it finds; a level
     // trajectory's z is untouched by the first launch, so the second still sees it level and skips it — the other way
     // round, a trajectory just outside the band that the general solve smooths into it would be solved a second time.
     constexpr bool kHasLevel = PPL == 1 && !OBS;
@@ -1562,7 +1765,21 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
             constexpr int kRH = GROUP == 32 ? kLevelRH : kLevelRH64;
             constexpr bool kHasRH = std::is_same<T, double>::value && kRH > 1;
             bool done = false;
+            // fp64 reference order, N <= 32, a batch with at most one trajectory per SIMD (two per wave leave half the
+            // chip idle): the axis-per-lane instantiation, ONE trajectory per wave, solves every level trajectory of
+            // the batch; the general kernel then skips them one by one (level_waves_elsewhere == 2).  Its LDS
+            // (<= 12.2 KB) is below the static limit: no attribute to raise.
+            if constexpr (std::is_same<T, double>::value && !FAST && GROUP == 32) {
+                if (L.simd_count > 0 && a.B <= L.simd_count && axis_dispatch_on()) {
+                    const size_t lds1 = optimize_lds_bytes<T, GROUP, FAST, 1>(a.N, k.mem_size, PPL, false);
+                    hipLaunchKernelGGL((k_optimize<T, GROUP, PPL, FAST, 1, OBS, 1>), dim3(a.B), block, lds1, s, a, kd);
+                    e = (int)hipGetLastError();
+                    a.level_waves_elsewhere = 2;
+                    done = true;
+                }
+            }
             if constexpr (kHasRH) {
+              if (!done) {
                 const size_t lds3 = optimize_lds_bytes<T, GROUP, FAST, 2>(a.N, k.mem_size, PPL, false, kRH);
                 if ((int)grid.x > simds && lds2 > kLdsPerWorkgroup / 8 && kLdsPerWorkgroup / lds3 > kLdsPerWorkgroup / lds2) {
                     // (more than four waves per CU put two on a SIMD: the register-capped build, 256 VGPRs)
@@ -1570,6 +1787,7 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
                     e = go(&k_optimize<T, GROUP, PPL, FAST, kWps, OBS, 2, kRH>, 60 + (FAST ? 1 : 0) + (GROUP == 64 ? 2 : 0), lds3);
                     done = true;
                 }
+              }
             }
             if (!done) {
                 if ((int)grid.x > simds && lds2 <= kLdsPerWorkgroup / 8) e = go(&k_optimize<T, GROUP, PPL, FAST, 2, OBS, 2>, slot2 + 1, lds2);
@@ -1589,8 +1807,10 @@ static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevCons
 
 template <typename T, bool FAST, bool OBS>
 static int launch_optimize_p(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, LaunchState& L) {
-    // (one trajectory per wave for N <= 32 — 64 x 1 with half the lanes idle, no divergence between
-    // the two line searches — measured slower: 0.462 vs 0.445 ms at B = 1024, 6.40 vs 3.60 ms at B = 16384)
+    // (one trajectory per wave for N <= 32 as 64 x 1 — one control point per lane, half the lanes idle, a sixth butterfly
+    // level in every reduction and no instruction saved — measured slower: 0.462 vs 0.445 ms at B = 1024, 6.40 vs
+    // 3.60 ms at B = 16384.  One trajectory per wave with one COORDINATE per lane is a different thing: the AXIS
+    // instantiation of k_optimize, which launch_optimize_t takes for level trajectories on batches of up to one per SIMD)
     switch (shape_for(a.N)) {
         // (a 16-lane x 2-point shape saves one butterfly level but measured 22 % slower: 1.76 M vs 2.26 M/s)
         case 0: return launch_optimize_t<T, 32, 1, FAST, OBS>(s, a, k, kd, L);
