@@ -23,11 +23,6 @@ namespace {
 
 constexpr int kAstarRetry = 4;   // (between the two kernels) the small table overflowed
 
-struct GridOcc {
-    GridView g;
-    __device__ bool operator()(double x, double y, double z) const { return grid_plane_pos(g, 0, x, y, z) != 0u; }
-};
-
 struct AstarArgs {
     int Q;
     const double* start;

@@ -1,6 +1,8 @@
-// vigo_grid.hpp — device-side access to the packed voxel snapshot (GridView) and the uniform
-// B-spline evaluation shared by the map/gate kernels.
+// vigo_grid.hpp — device-side access to the packed voxel snapshot (GridView), the uniform B-spline evaluation and the
+// two gates of the rebound loop (a wave per trajectory), shared by the map kernels and the rebound loop's.
 #pragma once
+
+#include <limits.h>
 
 #include "vigo_internal.hpp"
 
@@ -38,6 +40,12 @@ __device__ __forceinline__ unsigned grid_plane_pos(const GridView& g, int plane,
     const int iz = grid_index(z, g.origin[2], g.res, g.nz);
     return grid_plane_at(g, plane, ix, iy, iz);
 }
+
+// the point predicate of the core headers (A*, guides, the line walk): inflated-occupied, outside included
+struct GridOcc {
+    GridView g;
+    __device__ bool operator()(double x, double y, double z) const { return grid_plane_pos(g, 0, x, y, z) != 0u; }
+};
 
 // bspline::at (BS.cpp:32-58) for knots (i - degree) * ts, control point i = get(i)
 template <int DEGREE, typename Get>
@@ -88,6 +96,40 @@ __device__ __forceinline__ void traj_eval(const double* ctrl, int N, double ts, 
     if (deriv == 0) deboor<3>(N, ts, t, c0, out);
     else if (deriv == 1) deboor<2>(N - 1, ts, t, c1, out);
     else deboor<1>(N - 2, ts, t, c2, out);
+}
+
+// ---- the gates of the rebound loop, over the 64 lanes of a wave (lanes stride over the samples times[0 .. T)) -------
+// hasCollisionTrajectory (BT.h:307-325): the lane's first colliding sample, or INT_MAX.  (k ascends per lane: the
+// wave's minimum is the trajectory's first hit.)
+__device__ __forceinline__ int gate_static_first(const GridView& g, const double* c, int N, double ts, int T,
+                                                 const double* __restrict__ times, int lane) {
+    for (int k = lane; k < T; k += 64) {
+        double p[3];
+        traj_eval(c, N, ts, 0, times[k], p);
+        if (grid_plane_pos(g, 0, p[0], p[1], p[2])) return k;
+    }
+    return INT_MAX;
+}
+
+// hasDynamicCollisionTrajectory (BT.h:344-368): does one of the lane's samples lie inside an obstacle of trajectory b
+// (obs_off's range of obs[][9], or the n_obs_shared shared ones; none without obs — BT.cpp:621-626)
+__device__ __forceinline__ int gate_dynamic_hit(const double* c, int N, double ts, int T, const double* __restrict__ times,
+                                                const int32_t* __restrict__ obs_off, const double* __restrict__ obs,
+                                                int n_obs_shared, int b, int lane) {
+    const int o0 = (obs && obs_off) ? obs_off[b] : 0;
+    const int o1 = !obs ? 0 : (obs_off ? obs_off[b + 1] : n_obs_shared);
+    if (o1 <= o0) return 0;
+    for (int k = lane; k < T; k += 64) {
+        double p[3];
+        traj_eval(c, N, ts, 0, times[k], p);
+        for (int j = o0; j < o1; ++j) {
+            const double* o = obs + 9 * (size_t)j;
+            const double size = fmin(o[6] / 2, o[7] / 2);  // BT.h:358 (min, unlike the cost term)
+            const double dx = p[0] - o[0], dy = p[1] - o[1];
+            if (sqrt((dx * dx + dy * dy) + 0.0) - size < 0) return 1;
+        }
+    }
+    return 0;
 }
 
 }  // namespace vigo

@@ -16,14 +16,10 @@
 // The work is latency-bound (a chain of dependent fp64 divisions, square roots and atan2 per control point).
 #include "vigo_guide_core.hpp"
 #include "vigo_grid.hpp"
+#include "vigo_scan.hpp"
 
 namespace vigo {
 namespace {
-
-struct GuideOcc {
-    GridView g;
-    __device__ bool operator()(double x, double y, double z) const { return grid_plane_pos(g, 0, x, y, z) != 0u; }
-};
 
 struct GuideArgs {
     int B, N;
@@ -46,8 +42,7 @@ __global__ void __launch_bounds__(1024) k_guide_offsets(GuideArgs A) {
     const int tid = threadIdx.x;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    const int per = (A.B + 1023) / 1024;
-    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    const auto [lo, hi] = batch_slice(A.B);
     // pass 1: checks, deferral, the pairs of my trajectories
     long long n = 0;
     bool bad = false;
@@ -66,15 +61,8 @@ __global__ void __launch_bounds__(1024) k_guide_offsets(GuideArgs A) {
         n += deferred ? 0 : nb;
     }
     if (bad) s_bad = 1;
-    s_cnt[tid] = n;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {            // inclusive scan
-        const long long v = tid >= off ? s_cnt[tid - off] : 0;
-        __syncthreads();
-        s_cnt[tid] += v;
-        __syncthreads();
-    }
-    const long long total = s_cnt[1023];
+    long long total;
+    const long long mine_end = scan1024(s_cnt, n, &total);
     const bool good = s_bad == 0 && total <= A.pair_cap && total <= 0x7fffffffLL;
     if (tid == 0) {
         A.result[0] = total;
@@ -82,7 +70,7 @@ __global__ void __launch_bounds__(1024) k_guide_offsets(GuideArgs A) {
     }
     if (!good) return;                                    // nothing else is written
     // pass 2: statuses and offsets of my trajectories
-    long long at = s_cnt[tid] - n;
+    long long at = mine_end - n;
     for (int b = lo; b < hi; ++b) {
         const int s0 = A.seg_off[b], s1 = A.seg_off[b + 1];
         bool deferred = false;
@@ -137,7 +125,7 @@ __device__ bool find_guide_wave(int lane, int idx, int first, int second, const 
     return false;
 }
 
-__global__ void __launch_bounds__(64) k_guide_assign(GuideOcc occ, GuideArgs A) {
+__global__ void __launch_bounds__(64) k_guide_assign(GridOcc occ, GuideArgs A) {
     __shared__ G3 s_path[kGuidePathCap];
     __shared__ G3 s_sc[kGuidePathCap];
     const int lane = threadIdx.x;
@@ -241,7 +229,7 @@ int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const do
                         const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
                         const int32_t* status) {
     GuideArgs a{B, N, ctrl, seg_off, seg, path_off, path, 0, const_cast<int32_t*>(off), out_pv, out_unk, const_cast<int32_t*>(status), nullptr};
-    hipLaunchKernelGGL(k_guide_assign, dim3(B), dim3(64), 0, s, GuideOcc{g}, a);
+    hipLaunchKernelGGL(k_guide_assign, dim3(B), dim3(64), 0, s, GridOcc{g}, a);
     return (int)hipGetLastError();
 }
 

@@ -18,28 +18,14 @@
 //                                     fixed-stride paths compacted into the CSR output (point 0 replaced by ctrl[first],
 //                                     the end control point appended), a point per lane
 // The serial parts (a scan over a few dozen flags, a walk over a handful of segments) run one trajectory per thread; the
-// one-workgroup kernels are k_guide_offsets' shape (a 1024-thread scan).  Plain vector stores, no atomics.
+// one-workgroup kernels are k_guide_offsets' shape (vigo_scan.hpp: a slice of the batch per thread, a 1024-thread scan).
+// Plain vector stores, no atomics.
 #include "vigo_pathsearch_core.hpp"
 #include "vigo_internal.hpp"
+#include "vigo_scan.hpp"
 
 namespace vigo {
 namespace {
-
-// inclusive scan of v over the 1024 threads of the workgroup; returns this thread's inclusive value, *total the sum
-__device__ __forceinline__ long long scan1024(long long* s, long long v, long long* total) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                      // (the previous scan's readers are done)
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const long long u = tid >= off ? s[tid - off] : 0;
-        __syncthreads();
-        s[tid] += u;
-        __syncthreads();
-    }
-    *total = s[1023];
-    return s[tid];
-}
 
 // the supplied list of trajectory b: CSR (seg_off_in), or seg_cnt_in[b] segments at a fixed stride (vigo_reguide.hip)
 __device__ __forceinline__ int ps_list_first(const PathSearchArgs& A, int b) { return A.seg_cnt_in ? b * A.seg_stride_in : A.seg_off_in[b]; }
@@ -47,19 +33,13 @@ __device__ __forceinline__ int ps_list_end(const PathSearchArgs& A, int b) {
     return A.seg_cnt_in ? b * A.seg_stride_in + A.seg_cnt_in[b] : A.seg_off_in[b + 1];
 }
 
-struct FlagOcc {
-    const uint8_t* f;
-    __device__ bool operator()(int i) const { return f[i] != 0; }
-};
-
 __global__ void __launch_bounds__(1024) k_ps_count(PathSearchArgs A) {
     __shared__ long long s_cnt[1024];
     __shared__ int s_bad;
     const int tid = threadIdx.x;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    const int per = (A.B + 1023) / 1024;
-    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    const auto [lo, hi] = batch_slice(A.B);
     long long n = 0;
     bool bad = false;
     for (int b = lo; b < hi && !bad; ++b) {
@@ -127,8 +107,7 @@ __global__ void __launch_bounds__(256) k_ps_segs_out(PathSearchArgs A) {
 __global__ void __launch_bounds__(1024) k_ps_retry(PathSearchArgs A, PathSearchWork W) {
     __shared__ long long s_cnt[1024];
     const int tid = threadIdx.x;
-    const int per = (A.B + 1023) / 1024;
-    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    const auto [lo, hi] = batch_slice(A.B);
     long long n = 0;
     for (int b = lo; b < hi; ++b) {
         const int q0 = A.in_off[b];
@@ -158,8 +137,7 @@ __global__ void __launch_bounds__(1024) k_ps_retry(PathSearchArgs A, PathSearchW
 __global__ void __launch_bounds__(1024) k_ps_decide(PathSearchArgs A, PathSearchWork W) {
     __shared__ long long s_cnt[1024];
     const int tid = threadIdx.x;
-    const int per = (A.B + 1023) / 1024;
-    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    const auto [lo, hi] = batch_slice(A.B);
     long long n_seg = 0, n_pts = 0;
     for (int b = lo; b < hi; ++b) {
         const int q0 = A.in_off[b], n = A.n_in[b];

@@ -13,10 +13,11 @@
 //                    once one merge is taken the unmerged segments are dropped, so the trajectory keeps the merged
 //                    segments alone, and (the min(collisionSeg.size(), paths.size()) bound of BT.cpp:523) as many paths
 //                    from the front of the path list.
-//   line_occupied    isInflatedOccupiedLine of the dense map contract (include/vigo.h) over a point predicate.  HOST
-//                    TWIN ONLY: the kernels take the line flags from k_ctrl_occupancy (vigo_map.hip), which has its own
-//                    copy of this walk; the two copies are held together by the bit-for-bit parity tests of
-//                    tests/test_gpu_pathsearch.py, not by shared code.
+//   line_interior_occupied / line_occupied   isInflatedOccupiedLine of the dense map contract (include/vigo.h) over a
+//                    point predicate: the walk between the ends, and the ends first.  k_ctrl_occupancy (vigo_map.hip) and
+//                    the rebound loop's kernels (vigo_reguide.hip) have the ends' flags already and run the interior walk;
+//                    the host twins ask line_occupied.
+//   FlagOcc          occ(i) / line(i) of the rules here and in vigo_reguide_core.hpp, read from an array of flags.
 //   paths_cut_by_bound   for a caller that wants the unbounded path list: did the bound cut paths off a trajectory.
 //
 // Integer logic only, apart from endIdx and the line test; every fp64 expression is compiled without contraction.
@@ -79,19 +80,31 @@ VIGO_HD int collision_segs(int N, double not_check_ratio, const Occ& occ, const 
     return n;
 }
 
-// isInflatedOccupiedLine(q, p) over the point predicate occ(x, y, z): the end points, then int(dist / res) - 1 interior
-// steps of length res from q (standin/dense_occmap.h; vigo_ctrl_occupancy's line flag)
+// occ(i) / line(i) from the flags of k_ctrl_occupancy, or of a wave's LDS
+struct FlagOcc {
+    const uint8_t* f;
+    VIGO_HD bool operator()(int i) const { return f[i] != 0; }
+};
+
+// isInflatedOccupiedLine(q, p) between two FREE ends, over the point predicate occ(x, y, z): int(dist / res) - 1 interior
+// steps of length res from q (standin/dense_occmap.h).  A line no int counts the steps of (not finite, or absurdly long)
+// has no interior: both ends are inside a grid, it is never that long.
 template <class Occ>
-VIGO_HD bool line_occupied(const Occ& occ, double res, const double* q, const double* p) {
-    if (occ(q[0], q[1], q[2]) || occ(p[0], p[1], p[2])) return true;
+VIGO_HD bool line_interior_occupied(const Occ& occ, double res, const double* q, const double* p) {
     const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
     const double dist = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
     const double i0 = d0 / dist * res, i1 = d1 / dist * res, i2 = d2 / dist * res;
     const double fsteps = dist / res;
-    const int steps = fsteps < 2147483647.0 ? (int)fsteps : 0;      // (both ends are inside a grid: never that long)
+    const int steps = fsteps < 2147483647.0 ? (int)fsteps : 0;
     for (int s = 1; s < steps; ++s)
         if (occ(q[0] + s * i0, q[1] + s * i1, q[2] + s * i2)) return true;
     return false;
+}
+
+// the whole test: the end points first (vigo_ctrl_occupancy's line flag)
+template <class Occ>
+VIGO_HD bool line_occupied(const Occ& occ, double res, const double* q, const double* p) {
+    return occ(q[0], q[1], q[2]) || occ(p[0], p[1], p[2]) || line_interior_occupied(occ, res, q, p);
 }
 
 VIGO_HD bool paths_search_decided(int st) { return st == 0 || st == 1; }      // kAstarFound / kAstarNotFound

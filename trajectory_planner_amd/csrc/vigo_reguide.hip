@@ -1,9 +1,13 @@
-// vigo_reguide.hip — vigo_rebound_reguide: the re-guide step of the rebound loop (the `if (hasCollision)` block of
-// BT.cpp:656-679; host/src/bsplineTraj.cpp: reboundStep) for the trajectories vigo_rebound_rounds left VIGO_RB_NEEDS_HOST,
-// the rules of vigo_reguide_core.hpp around the path search of vigo_pathsearch.hip and the guide step of vigo_guides.hip
-// (both unchanged: the re-guide list is a caller-supplied list to the first, its output the input of the second).
+// vigo_reguide.hip — the rebound loop of bsplineTraj::optimizeTrajectory (BT.cpp:611-685) between two solves: the gate
+// + decision pass and the compaction of vigo_rebound_rounds, and vigo_rebound_reguide, the re-guide step (the
+// `if (hasCollision)` block of BT.cpp:656-679; host/src/bsplineTraj.cpp: reboundStep) for the trajectories the rounds
+// left VIGO_RB_NEEDS_HOST.  The rules are vigo_reguide_core.hpp's (reguide_rules is asked by both: the yes/no by
+// k_rebound_decide, the list by k_reguide_list), around the gates of vigo_grid.hpp, the path search of
+// vigo_pathsearch.hip and the guide step of vigo_guides.hip (both unchanged: the re-guide list is a caller-supplied list
+// to the first, its output the input of the second).
 //
-// The kernels of one call, in stream order (vigo_api.cpp reads back the words marked <-):
+// A round of vigo_rebound_rounds: k_rebound_decide (a wave per trajectory), k_rebound_compact (one workgroup), the solve.
+// The kernels of one vigo_rebound_reguide call, in stream order (vigo_api.cpp reads back the words marked <-):
 //   k_reguide_list          a wave per trajectory   eligibility; the map queries of findCollisionSeg one control point per
 //                                                   lane; lane 0 walks reguide_rules over the flags in LDS: the new
 //                                                   segments and the re-guide list, at a fixed stride  <- bad guide_off
@@ -18,6 +22,7 @@
 #include "vigo_reguide_core.hpp"
 #include "vigo_guide_core.hpp"
 #include "vigo_grid.hpp"
+#include "vigo_scan.hpp"
 
 namespace vigo {
 namespace {
@@ -25,10 +30,140 @@ namespace {
 constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
 static_assert(kSegs == kPathsMaxSegs, "the state holds what the path search takes");
 
-struct FlagAt {
-    const uint8_t* f;
-    __device__ bool operator()(int i) const { return f[i] != 0; }
+// the map queries of findCollisionSeg (BT.cpp:412, :435) for one trajectory over the lanes of its wave, a control point
+// per lane: s_pt[i] the point flag, then s_ln[i] the line (i - 1, i) from the flags of its ends.  Every lane calls it.
+__device__ __forceinline__ void ctrl_flags_wave(const GridView& g, const double* c, int N, int lane, uint8_t* s_pt, uint8_t* s_ln) {
+    for (int i = lane; i < N; i += 64) s_pt[i] = (uint8_t)grid_plane_pos(g, 0, c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+    __syncthreads();
+    for (int i = lane; i < N; i += 64) {
+        unsigned line = 0;
+        if (i > 0) {
+            line = s_pt[i - 1] | s_pt[i];
+            if (!line) line = line_interior_occupied(GridOcc{g}, g.res, c + 3 * (i - 1), c + 3 * i) ? 1u : 0u;
+        }
+        s_ln[i] = (uint8_t)line;
+    }
+    __syncthreads();
+}
+
+// isControlPointRequireNewGuide (BT.h:417-429) of control point i of one trajectory: off its guide offsets [N + 1] or
+// NULL, pv the pairs, c its control points.  A control point without guide arrays needs a guide.
+struct NeedGuide {
+    const int32_t* off;
+    const double* pv;
+    const double* c;
+    double dthresh;
+    __device__ bool operator()(int i) const {
+        if (!off || !pv) return true;
+        const int j0 = off[i], j1 = off[i + 1];
+        if (j0 < 0) return true;                          // (a bad list: the call is refused, read nothing)
+        for (int j = j0; j < j1; ++j)
+            if (!reguide_guide_far(dthresh, c + 3 * i, pv + 6 * (size_t)j)) return false;
+        return true;
+    }
 };
+
+// ---- vigo_rebound_rounds: gates + the loop body of bsplineTraj::optimizeTrajectory (BT.cpp:619-679) ----------
+// One 64-lane wave per ACTIVE trajectory.  The gates are the walks of vigo_grid.hpp (lanes stride over the samples); the
+// map queries of findCollisionSeg run one control point per lane; the segment bookkeeping, the comparison with the
+// previous segments and the guide test (reguide_rules) are a serial scan by lane 0 over a few dozen bytes in LDS.
+__global__ void __launch_bounds__(64) k_rebound_decide(GridView g, ReboundArgs A) {
+    __shared__ uint8_t s_pt[VIGO_MAX_CTRL_POINTS], s_ln[VIGO_MAX_CTRL_POINTS];
+    __shared__ int s_need_host;
+    const int b = blockIdx.x;
+    if (b >= A.B) return;
+    // a trajectory of an EARLIER round waits for the host (A*): the queued rounds that follow are no-ops for the whole
+    // batch, like the lock-step of the host-driven loop — the waiting trajectories are on the batch's critical path
+    if (A.flags[1] != 0) return;
+    vigo_rebound_state_t& st = A.state[b];
+    if (st.status != VIGO_RB_ACTIVE) return;
+    const int N = A.N, lane = threadIdx.x;
+    const double* c = A.ctrl + (size_t)b * N * 3;
+
+    const int col = __any(gate_static_first(g, c, N, A.ts_ctrl, A.T_static, A.times, lane) != INT_MAX) ? 1 : 0;
+    const int dyn = __any(gate_dynamic_hit(c, N, A.ts_ctrl, A.T, A.times, A.obs_off, A.obs, A.n_obs_shared, b, lane)) ? 1 : 0;
+    if (lane == 0) {
+        st.gate_static = col;
+        st.gate_dynamic = dyn;
+        st.rounds += 1;
+    }
+    if (!col && !dyn) {                                   // BT.cpp:628-631
+        if (lane == 0) st.status = VIGO_RB_DONE;
+        return;
+    }
+    if (st.fail_count >= 4) {                             // BT.cpp:640-654: forced A* re-guide, the host's
+        if (lane == 0) { st.status = VIGO_RB_NEEDS_HOST; A.flags[2] = 1; }
+        return;
+    }
+    if (col) {
+        ctrl_flags_wave(g, c, N, lane, s_pt, s_ln);
+        if (lane == 0) {
+            // isReguideRequired, BT.cpp:573-608: a trajectory with a re-guide list (or more segments than the state
+            // holds) asks for A*
+            int32_t seg[2 * kSegs];
+            uint8_t listed[kSegs];
+            int n_list = 0;
+            const int n_prev = min(max(st.n_seg, 0), kSegs);   // (device data: never index beyond the array)
+            const NeedGuide need_guide{A.guide_off ? A.guide_off + (size_t)b * N : nullptr, A.guide_pv, c, A.dthresh};
+            const int n = reguide_rules(N, A.not_check_ratio, FlagOcc{s_pt}, FlagOcc{s_ln}, n_prev, st.seg, need_guide, kSegs, seg, listed, &n_list);
+            const bool need_host = n > kSegs || n_list != 0;
+            s_need_host = need_host ? 1 : 0;
+            if (need_host) {
+                st.status = VIGO_RB_NEEDS_HOST;           // untouched state: the host repeats the step with its own A*
+                A.flags[2] = 1;
+            } else {
+                st.n_seg = n;                             // collisionSeg_ = the new segments (BT.cpp:575)
+                for (int k = 0; k < 2 * n; ++k) st.seg[k] = seg[k];
+                A.weights[4 * (size_t)b + 0] *= 2.0;      // BT.cpp:672
+                st.fail_count += 1;
+            }
+        }
+        __syncthreads();
+        if (s_need_host) return;
+    }
+    if (dyn && lane == 0) A.weights[4 * (size_t)b + 3] *= 2.0;   // BT.cpp:677-679
+}
+
+// ascending indices of the trajectories a launch works on: one block, a scan over per-thread counts
+// flags: [0] = count (out), [1] = "a trajectory waits for the host since an earlier round" (read by this round's
+// kernels), [2] = the same as raised by this round's decide pass; mode 1 publishes [2] into [1] for the next round
+__global__ void __launch_bounds__(1024) k_rebound_compact(int B, vigo_rebound_state_t* __restrict__ state, int mode,
+                                                          int32_t* __restrict__ idx, int32_t* __restrict__ flags) {
+    __shared__ int s_cnt[1024];
+    const int tid = threadIdx.x;
+    int32_t* count = flags;
+    if (mode == 1 && flags[1] != 0) {            // (uniform: every thread reads the same word)
+        if (tid == 0) *count = 0;
+        return;
+    }
+    const auto [lo, hi] = batch_slice(B);
+    if (mode == 1 && flags[2] != 0) {            // (uniform too)
+        // this round's decisions hand a trajectory to the host: the optimize() the still-active trajectories owe is
+        // deferred to the caller's next call (solve_first), where it shares ONE launch with the re-guided ones —
+        // two launches in a row would put two solve latencies on the batch's critical path
+        for (int b = lo; b < hi; ++b)
+            if (state[b].status == VIGO_RB_ACTIVE) state[b].solve_first = 1;
+        if (tid == 0) { *count = 0; flags[1] = 1; }
+        return;
+    }
+    auto wanted = [&](int b) {
+        return state[b].status == VIGO_RB_ACTIVE && (mode == 1 || state[b].solve_first != 0);
+    };
+    int n = 0;
+    for (int b = lo; b < hi; ++b) n += wanted(b) ? 1 : 0;
+    int total;
+    int at = scan1024(s_cnt, n, &total) - n;
+    for (int b = lo; b < hi; ++b) {
+        if (wanted(b)) {
+            idx[at++] = b;
+            if (mode == 0) state[b].solve_first = 0;
+        }
+    }
+    if (tid == 1023) {
+        *count = total;
+        if (mode == 1) flags[1] = flags[2];
+    }
+}
 
 __global__ void __launch_bounds__(64) k_reguide_list(GridView g, ReguideArgs A) {
     __shared__ uint8_t s_pt[VIGO_MAX_CTRL_POINTS], s_ln[VIGO_MAX_CTRL_POINTS];
@@ -40,33 +175,19 @@ __global__ void __launch_bounds__(64) k_reguide_list(GridView g, ReguideArgs A) 
         if (bad) A.result[0] = 1;                         // (the same value from whoever sees one)
     }
     const vigo_rebound_state_t& st = A.state[b];
-    if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) {
+    if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) {     // (the workgroup's)
         if (lane == 0) { A.kind[b] = kReguideSkipped; A.n_list[b] = 0; A.n_new[b] = 0; }
         return;
     }
     const double* c = A.ctrl + (size_t)b * N * 3;
-    auto occ = [&g](double x, double y, double z) { return grid_plane_pos(g, 0, x, y, z) != 0u; };
-    for (int i = lane; i < N; i += 64) {
-        s_pt[i] = occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]) ? 1 : 0;
-        s_ln[i] = (i > 0 && line_occupied(occ, g.res, c + 3 * (i - 1), c + 3 * i)) ? 1 : 0;
-    }
-    __syncthreads();
+    ctrl_flags_wave(g, c, N, lane, s_pt, s_ln);
     if (lane != 0) return;
     int32_t seg[2 * kSegs];
     uint8_t listed[kSegs];
     int n_list = 0;
     const int n_prev = min(max(st.n_seg, 0), kSegs);      // (device data: never index beyond the array)
-    const double dthresh = A.dthresh;
-    const double* pv = A.guide_pv;
-    auto need_guide = [&](int i) {
-        if (!off || !pv) return true;
-        const int j0 = off[i], j1 = off[i + 1];
-        if (j0 < 0) return true;                          // (a bad list: the call is refused, read nothing)
-        for (int j = j0; j < j1; ++j)
-            if (!reguide_guide_far(dthresh, c + 3 * i, pv + 6 * (size_t)j)) return false;
-        return true;
-    };
-    const int n = reguide_rules(N, A.not_check_ratio, FlagAt{s_pt}, FlagAt{s_ln}, n_prev, st.seg, need_guide, kSegs, seg, listed, &n_list);
+    const NeedGuide need_guide{off, A.guide_pv, c, A.dthresh};
+    const int n = reguide_rules(N, A.not_check_ratio, FlagOcc{s_pt}, FlagOcc{s_ln}, n_prev, st.seg, need_guide, kSegs, seg, listed, &n_list);
     if (n > kSegs) {
         A.kind[b] = kReguideDeferred; A.n_list[b] = 0; A.n_new[b] = 0;
         return;
@@ -91,8 +212,7 @@ __global__ void __launch_bounds__(64) k_reguide_list(GridView g, ReguideArgs A) 
 __global__ void __launch_bounds__(1024) k_guide_merge_offsets(ReguideArgs A) {
     __shared__ long long s_cnt[1024];
     const int tid = threadIdx.x, N = A.N;
-    const int per = (A.B + 1023) / 1024;
-    const int lo = min(A.B, tid * per), hi = min(A.B, lo + per);
+    const auto [lo, hi] = batch_slice(A.B);
     auto old_pairs = [&](size_t at) { return A.guide_off ? A.guide_off[at + 1] - A.guide_off[at] : 0; };
     // pass 1: the outcomes and the pairs of my trajectories
     long long n = 0;
@@ -104,19 +224,12 @@ __global__ void __launch_bounds__(1024) k_guide_merge_offsets(ReguideArgs A) {
         if (A.guide_off) n += (long long)A.guide_off[(size_t)(b + 1) * N] - A.guide_off[(size_t)b * N];
         if (outcome == kReguideDone) n += (long long)A.g_off[(size_t)(b + 1) * N] - A.g_off[(size_t)b * N];
     }
-    s_cnt[tid] = n;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {            // inclusive scan
-        const long long v = tid >= off ? s_cnt[tid - off] : 0;
-        __syncthreads();
-        s_cnt[tid] += v;
-        __syncthreads();
-    }
-    const long long total = s_cnt[1023];
+    long long total;
+    const long long mine_end = scan1024(s_cnt, n, &total);
     if (tid == 0) A.result[1] = total;
     if (total > A.pair_cap || total > 0x7fffffffLL) return;                   // nothing else is written
     // pass 2: the merged offsets of my trajectories
-    long long at = s_cnt[tid] - n;
+    long long at = mine_end - n;
     for (int b = lo; b < hi; ++b) {
         const bool done = A.outcome[b] == kReguideDone;
         for (int i = 0; i < N; ++i) {
@@ -174,6 +287,17 @@ __global__ void __launch_bounds__(256) k_reguide_commit(ReguideArgs A) {
 }
 
 }  // namespace
+
+int launch_rebound_decide(hipStream_t s, const GridView& g, const ReboundArgs& a) {
+    if (a.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rebound_decide, dim3(a.B), dim3(64), 0, s, g, a);
+    return (int)hipGetLastError();
+}
+
+int launch_rebound_compact(hipStream_t s, int B, vigo_rebound_state_t* state, int mode, int32_t* idx, int32_t* flags) {
+    hipLaunchKernelGGL(k_rebound_compact, dim3(1), dim3(1024), 0, s, B, state, mode, idx, flags);
+    return (int)hipGetLastError();
+}
 
 int launch_reguide_list(hipStream_t s, const GridView& g, const ReguideArgs& a) {
     hipLaunchKernelGGL(k_reguide_list, dim3(a.B), dim3(64), 0, s, g, a);

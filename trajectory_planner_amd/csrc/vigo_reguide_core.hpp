@@ -4,8 +4,8 @@
 // facade's own reboundStep and a Python restatement of isReguideRequired).
 //
 //   reguide_guide_far   isControlPointRequireNewGuide's test of ONE guide pair (BT.h:417-429): dthresh - dist > 0 keeps
-//                       the control point's guides.  The dot product in the order k_rebound_decide writes it
-//                       (vigo_map.hip), ((c - p) . d summed x, y, then z), compiled without contraction.
+//                       the control point's guides.  The dot product ((c - p) . d summed x, y, then z), compiled
+//                       without contraction.
 //   reguide_rules       isReguideRequired (BT.cpp:573-608; host/src/bsplineTraj.cpp:646-659): findCollisionSeg on the
 //                       current control points (collision_segs of vigo_pathsearch_core.hpp), compareCollisionSeg against
 //                       the previous segments (BT.h:379-403: the interior control points of every new segment, and BOTH
@@ -18,10 +18,9 @@
 //   reguide_outcome     what the step does with a trajectory, from the list, the search and the guide step.
 //   reguide_commit      the state transition of BT.cpp:656-679 for the outcomes that are not deferred.
 //
-// The yes/no of reguide_rules (a list that is not empty) equals k_rebound_decide's need_host for every input that has at
-// most kPathsMaxSegs new segments: both ask the same question of the same control points, the kernel stops at the first
-// yes.  The forced A* of failCount >= 4 (BT.cpp:640-654) is NOT here: it precedes isReguideRequired and changes the
-// guides that step reads, and stays with the host.
+// k_rebound_decide (vigo_reguide.hip) asks reguide_rules the yes/no: a list that is not empty, or more new segments than
+// the state holds, hands the trajectory to the host.  The forced A* of failCount >= 4 (BT.cpp:640-654) is NOT here: it
+// precedes isReguideRequired and changes the guides that step reads, and stays with the host.
 //
 // Integer logic and one fp64 dot product.
 #pragma once

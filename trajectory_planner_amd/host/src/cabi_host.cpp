@@ -59,6 +59,30 @@ nav_msgs::Path pathFromXyz(const double* q, int n_pts) {
     return path;
 }
 
+// a dense byte grid as the kernels' twins read it (standin/dense_occmap.h byteAt): posToIndex is floor((p - origin) / res),
+// the range test is made on the double, outside is 0xFF (occupied and unknown).  Called, it is the point predicate the
+// core headers take.
+struct DenseGrid {
+    const unsigned char* vox;
+    const int* dims;
+    const double* origin;
+    double res;
+    unsigned byteAt(double x, double y, double z) const {
+        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
+        for (int a = 0; a < 3; ++a)
+            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return 0xFFu;
+        return vox[((size_t)f[0] * dims[1] + (size_t)f[1]) * dims[2] + (size_t)f[2]];
+    }
+    bool occupied(double x, double y, double z) const { return byteAt(x, y, z) & 1u; }
+    bool operator()(double x, double y, double z) const { return occupied(x, y, z); }
+};
+
+// occ(i) / line(i) of collision_segs and reguide_rules for the control points c[N][3]
+auto ctrlFlags(const DenseGrid& g, const double* c) {
+    return std::make_pair([&g, c](int i) { return g.occupied(c[3 * i], c[3 * i + 1], c[3 * i + 2]); },
+                          [&g, c](int i) { return vigo::line_occupied(g, g.res, c + 3 * (i - 1), c + 3 * i); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -199,13 +223,7 @@ int vigo_host_astar_core(const unsigned char* vox, const int* dims, const double
     vigo::AstarStore<int32_t> S{};
     S.key = key.data(); S.g = g.data(); S.meta = meta.data(); S.heap = heap.data();
     S.cap_log2 = cap_log2; S.max_nodes = max_nodes; S.heap_cap = heap_cap;
-    const size_t ny = dims[1], nz = dims[2];
-    auto occ = [&](double x, double y, double z) -> bool {     // dense_occmap.h byteAt & 1: outside is occupied
-        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
-        for (int a = 0; a < 3; ++a)
-            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
-        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
-    };
+    const DenseGrid occ{vox, dims, origin, res};
     const int st = vigo::astar_search(S, occ, start, end, step, pool, min_height, max_height, max_expansions, path_cap, path_out, len_out);
     stats[0] = S.pops; stats[1] = S.n_nodes; stats[2] = S.heap_peak; stats[3] = S.rewrites;
     return st;
@@ -953,14 +971,7 @@ int vigo_host_guide_core(const unsigned char* vox, const int* dims, const double
         first_pair[b + 1] = first_pair[b] + (deferred[b] ? 0 : nb);
     }
     if (first_pair[B] > pair_cap || first_pair[B] > 0x7fffffffLL) return -1;
-    const size_t ny = dims[1], nz = dims[2];
-    auto byteAt = [&](double x, double y, double z) -> unsigned {     // dense_occmap.h byteAt
-        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
-        for (int a = 0; a < 3; ++a)
-            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return 0xFFu;
-        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]];
-    };
-    auto occ = [&](double x, double y, double z) -> bool { return byteAt(x, y, z) & 1u; };
+    const DenseGrid occ{vox, dims, origin, res};
     vigo_host::parallelFor((size_t)B, [&](size_t b) {
         out_status[b] = deferred[b] ? vigo::kGuideDeferred : vigo::kGuideOk;
         const int s0 = seg_off[b], s1 = seg_off[b + 1];
@@ -977,7 +988,7 @@ int vigo_host_guide_core(const unsigned char* vox, const int* dims, const double
         auto emit = [&](int idx, const vigo::G3& p, const vigo::G3& d, const int32_t* dec) {
             const int g = cursor[idx]++;
             for (int a = 0; a < 3; ++a) { out_pv[(size_t)g * 6 + a] = p.v[a]; out_pv[(size_t)g * 6 + 3 + a] = d.v[a]; }
-            if (out_unk) out_unk[g] = (byteAt(p.v[0], p.v[1], p.v[2]) >> 1) & 1u;
+            if (out_unk) out_unk[g] = (occ.byteAt(p.v[0], p.v[1], p.v[2]) >> 1) & 1u;
             if (out_decision) for (int a = 0; a < 3; ++a) out_decision[(size_t)g * 3 + a] = dec[a];
         };
         const double* c = ctrl + b * (size_t)N * 3;
@@ -1086,18 +1097,11 @@ int vigo_host_collision_segs_core(const unsigned char* vox, const int* dims, con
         (B > 0 && (!ctrl || !out_seg_off || !out_seg || !out_status)))
         return -1;
     if (B == 0) return 0;
-    const size_t ny = dims[1], nz = dims[2];
-    auto occ = [&](double x, double y, double z) -> bool {     // dense_occmap.h byteAt & 1: outside is occupied
-        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
-        for (int a = 0; a < 3; ++a)
-            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
-        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
-    };
+    const DenseGrid occ{vox, dims, origin, res};
     std::vector<std::vector<int32_t>> segs(B);
     vigo_host::parallelFor((size_t)B, [&](size_t b) {
         const double* c = ctrl + b * (size_t)N * 3;
-        auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
-        auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+        const auto [pt, ln] = ctrlFlags(occ, c);
         segs[b].resize(2 * vigo::kPathsMaxSegs);
         const int n = vigo::collision_segs(N, not_check_ratio, pt, ln, vigo::kPathsMaxSegs, segs[b].data());
         if (n > vigo::kPathsMaxSegs) segs[b].assign(1, -1);        // (marks the deferred ones)
@@ -1146,13 +1150,7 @@ int vigo_host_path_search_core(const unsigned char* vox, const int* dims, const 
                 if (seg[2 * k] < 0 || seg[2 * k] >= N || seg[2 * k + 1] < 0 || seg[2 * k + 1] >= N) return -1;
         }
     }
-    const size_t ny = dims[1], nz = dims[2];
-    auto occ = [&](double x, double y, double z) -> bool {
-        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
-        for (int a = 0; a < 3; ++a)
-            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return true;
-        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]] & 1u;
-    };
+    const DenseGrid occ{vox, dims, origin, res};
     struct Search { int status = vigo::kAstarDeferred, len = 0; std::vector<double> path; };
     struct Traj { int status = vigo::kPathsDeferred, run = 0, decided = 0; std::vector<int32_t> seg; std::vector<std::vector<double>> paths; };
     std::vector<Traj> out(B);
@@ -1167,8 +1165,7 @@ int vigo_host_path_search_core(const unsigned char* vox, const int* dims, const 
         std::vector<int32_t> in(2 * vigo::kPathsMaxSegs);
         int n;
         if (scan) {
-            auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
-            auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+            const auto [pt, ln] = ctrlFlags(occ, c);
             n = vigo::collision_segs(N, not_check_ratio, pt, ln, vigo::kPathsMaxSegs, in.data());
         } else {
             n = seg_off[b + 1] - seg_off[b];
@@ -1267,14 +1264,7 @@ int vigo_host_rebound_reguide_core(const unsigned char* vox, const int* dims, co
         for (size_t q = 0; q < (size_t)B * N; ++q)
             if (guide_off[q + 1] < guide_off[q]) return -1;
     }
-    const size_t ny = dims[1], nz = dims[2];
-    auto byteAt = [&](double x, double y, double z) -> unsigned {
-        const double f[3] = {std::floor((x - origin[0]) / res), std::floor((y - origin[1]) / res), std::floor((z - origin[2]) / res)};
-        for (int a = 0; a < 3; ++a)
-            if (!(f[a] >= 0.0 && f[a] < (double)dims[a])) return 0xFFu;
-        return vox[((size_t)f[0] * ny + (size_t)f[1]) * nz + (size_t)f[2]];
-    };
-    auto occ = [&](double x, double y, double z) -> bool { return byteAt(x, y, z) & 1u; };
+    const DenseGrid occ{vox, dims, origin, res};
     constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
     // the rules: the new segments and the re-guide list of every trajectory that is worked on
     std::vector<int> kind(B), n_list(B, 0), n_new(B, 0);
@@ -1283,8 +1273,7 @@ int vigo_host_rebound_reguide_core(const unsigned char* vox, const int* dims, co
         const vigo_rebound_state_t& st = state[b];
         if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) { kind[b] = vigo::kReguideSkipped; return; }
         const double* c = ctrl + b * (size_t)N * 3;
-        auto pt = [&](int i) { return occ(c[3 * i], c[3 * i + 1], c[3 * i + 2]); };
-        auto ln = [&](int i) { return vigo::line_occupied(occ, res, c + 3 * (i - 1), c + 3 * i); };
+        const auto [pt, ln] = ctrlFlags(occ, c);
         auto need_guide = [&](int i) {
             if (!guide_off || !guide_pv) return true;
             for (int j = guide_off[b * N + i]; j < guide_off[b * N + i + 1]; ++j)
@@ -1351,7 +1340,7 @@ int vigo_host_rebound_reguide_core(const unsigned char* vox, const int* dims, co
             if (guide_off)
                 for (int j = guide_off[q]; j < guide_off[q + 1]; ++j) {
                     const double* src = guide_pv + 6 * (size_t)j;
-                    put(src, guide_unk ? guide_unk[j] : ((byteAt(src[0], src[1], src[2]) >> 1) & 1u));
+                    put(src, guide_unk ? guide_unk[j] : ((occ.byteAt(src[0], src[1], src[2]) >> 1) & 1u));
                 }
             if (outcome[b] == vigo::kReguideDone)
                 for (int j = g_off[q]; j < g_off[q + 1]; ++j) put(g_pv.data() + 6 * (size_t)j, g_unk[j]);
