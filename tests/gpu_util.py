@@ -21,6 +21,16 @@ def rel_err_per_traj(a, ref):
     return np.abs(a - ref).reshape(B, -1).max(1) / np.abs(ref).reshape(B, -1).max(1)
 
 
+def is_level(ctrl):
+    """the level rule (include/vigo.h), per trajectory"""
+    zmin, zmax = ctrl[:, :, 2].min(1), ctrl[:, :, 2].max(1)
+    return (zmax - zmin) <= 2.0 ** -40 * np.maximum(1.0, np.maximum(np.abs(zmin), np.abs(zmax)))
+
+
+def simd_count():
+    return 4 * torch.cuda.get_device_properties(torch.device("cuda", 0)).multi_processor_count   # as vigo_create
+
+
 class emulation:
     """context manager: oracle in device-emulation mode for N control points (fast=True: of VIGO_PREC_F64_FAST)"""
 

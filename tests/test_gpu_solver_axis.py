@@ -11,22 +11,12 @@ import pytest
 import torch
 
 import oracle_lib as ol
-from gpu_util import batch_to_dev, emulation
+from gpu_util import batch_to_dev, emulation, is_level, simd_count
 from trajectory_planner_amd import synth
 from trajectory_planner_amd.vigo import default_params
 
 pytestmark = pytest.mark.gpu
 OUT = ("status", "iters", "evals", "x", "ctrl", "fx")
-
-
-def is_level(ctrl):
-    """the level rule (include/vigo.h), per trajectory"""
-    zmin, zmax = ctrl[:, :, 2].min(1), ctrl[:, :, 2].max(1)
-    return (zmax - zmin) <= 2.0 ** -40 * np.maximum(1.0, np.maximum(np.abs(zmin), np.abs(zmax)))
-
-
-def simd_count():
-    return 4 * torch.cuda.get_device_properties(torch.device("cuda", 0)).multi_processor_count   # as vigo_create
 
 
 def take(b, idx):

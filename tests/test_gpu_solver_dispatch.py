@@ -1,10 +1,12 @@
 """-m gpu: every k_optimize / k_cost_grad instantiation the launchers of vigo_solver.hip can select, each checked
 against the CPU oracle.
 
-  A  dispatch matrix (fp64, fp64 fast): one case per launch path of launch_optimize / launch_optimize_t — shape,
-     obstacle list or not, one or two waves per SIMD, the level (D = 2) launch with and without the register-held
-     history, the fast-mode redirect to the obstacle instantiation — solve and cost/gradient bit-exact against the
-     emulation-mode oracle.  A mirror of the dispatch rule asserts that each case reaches the cell it is named for.
+  A  dispatch matrix (fp64, fp64 fast): one case per launch path of plan_optimize (csrc/vigo_solver_plan.hpp) — shape,
+     obstacle list or not, one or two waves per SIMD, the axis-per-lane (D = 1) launch, the level (D = 2) launch with
+     and without the register-held history, the fast-mode redirect to the obstacle instantiation — solve and
+     cost/gradient bit-exact against the emulation-mode oracle.  The restatement of the dispatch rule in
+     solver_dispatch_rule.py, which test_solver_plan.py holds to the library's own plan, asserts that each case reaches
+     the cell it is named for.
   B  the solve kernel's LDS obstacle table at prediction horizons that hold 0, 1, some, 16 obstacles, an odd
      prediction count and a count of 1, always with more obstacles than fit; a shared obstacle list at B > 1.
   C  fp32 cost/gradient against the fp64 reference-order oracle at the fp32-rounded inputs, under a bound the test
@@ -18,7 +20,8 @@ import pytest
 import torch
 
 import oracle_lib as ol
-from gpu_util import batch_to_dev, emulation
+from gpu_util import batch_to_dev, emulation, is_level, simd_count
+from solver_dispatch_rule import CELLS, LDS, WAVE, cell_batch_size, kernel_name, launches, lds_bytes, obs_table_fit, shape_for
 from trajectory_planner_amd import synth
 from trajectory_planner_amd.vigo import PREC_F32, PREC_F64, PREC_F64_FAST, VigoError, default_params
 
@@ -27,111 +30,15 @@ MODES = {"f64": PREC_F64, "fast": PREC_F64_FAST, "f32": PREC_F32}
 OUT = ("status", "iters", "evals", "x", "ctrl", "fx")
 U32 = 2.0 ** -24                     # unit roundoff of fp32
 
-# ---- mirror of the launch rules of vigo_solver.hip ------------------------------------------------------------
-WAVE, LDS = 64, 160 * 1024           # kWave, kLdsPerWorkgroup
-OBS_TAB_OBS = 16                     # kObsTabObs
-LEVEL_RH = {32: 4, 64: 5}            # kLevelRH, kLevelRH64
 
-
-def obs_tab_entries(group):          # kObsTabEntries<GROUP>
-    return 88 if group == 32 else 33
-
-
-def shape_for(N):                    # (GROUP, PPL)
-    return (32, 1) if N <= 32 else ((64, 1) if N <= 64 else ((64, 2) if N <= 128 else (64, 4)))
-
-
-def lds_bytes(mode, N, m, D=3, obs=True, rh=1):
-    """optimize_lds_bytes<T, GROUP, FAST, D>(N, m, PPL, obs, rh)"""
-    group, ppl = shape_for(N)
-    tpb = WAVE // group
-    hpair = -(-2 * D * (4 if mode == "f32" else 8) // 16) * 16          # alignas(16) HPair<T, D>
-    ys = 8 if mode == "fast" else 16                                     # YSv<FAST>
-    ms = (m - (rh + 1) if m > rh + 1 else 0) if ppl == 1 else m
-    h = ms * ((tpb * (N - 6) + 1) * hpair + ((tpb * ys + 15) & ~15)) + m * tpb * 8
-    if obs:
-        h += tpb * (3 * obs_tab_entries(group) + OBS_TAB_OBS) * 8
-    return h
-
-
-def launches(mode, N, B, m, has_obs, plan_in_z, strict_z, simds):
-    """the k_optimize launches of one vigo_optimize call, in order, as (WPS, OBS, D, RH)"""
-    group, ppl = shape_for(N)
-    obs_inst = has_obs or (mode == "fast" and 32 < N <= 64 and B > simds and (plan_in_z or strict_z))
-    grid = -(-B // (WAVE // group))
-    out = []
-    if ppl == 1 and not obs_inst and not plan_in_z and not strict_z:
-        lds2 = lds_bytes(mode, N, m, D=2, obs=False)
-        lds3 = lds_bytes(mode, N, m, D=2, obs=False, rh=LEVEL_RH[group])
-        if mode != "f32" and grid > simds and lds2 > LDS // 8 and LDS // lds3 > LDS // lds2:
-            out.append((2, False, 2, LEVEL_RH[group]))
-        else:
-            out.append((2 if grid > simds and lds2 <= LDS // 8 else 1, False, 2, 1))
-    lds = lds_bytes(mode, N, m, obs=has_obs)
-    out.append((2 if ppl == 1 and grid > simds and lds <= LDS // 8 else 1, obs_inst, 3, 1 if ppl == 1 else 0))
-    return out
-
-
-def kernel_name(mode, N, wps, obs, D, rh):
-    group, ppl = shape_for(N)
-    t = "float" if mode == "f32" else "double"
-    b = lambda x: "true" if x else "false"
-    return f"k_optimize<{t}, {group}, {ppl}, {b(mode == 'fast')}, {wps}, {b(obs)}, {D}, {rh}>"
-
-
-def obs_table_fit(N, pred_num):
-    """obstacles per trajectory k_optimize stages in LDS"""
-    return min(OBS_TAB_OBS, obs_tab_entries(shape_for(N)[0]) // (pred_num // 2 + 1))
-
-
-def is_level(ctrl):
-    """the level rule (include/vigo.h), per trajectory"""
-    zmin, zmax = ctrl[:, :, 2].min(1), ctrl[:, :, 2].max(1)
-    return (zmax - zmin) <= 2.0 ** -40 * np.maximum(1.0, np.maximum(np.abs(zmin), np.abs(zmax)))
-
-
-def simd_count():
-    return 4 * torch.cuda.get_device_properties(torch.device("cuda", 0)).multi_processor_count   # as vigo_create
-
-
-# ---- A: the dispatch matrix ---------------------------------------------------------------------------------------
-# (cell, modes, N, batch: "small" or "wps2" = the smallest batch with more waves than SIMDs, mem_size, obstacles per
-#  trajectory, plan_in_z / strict_z, the launches expected as (WPS, OBS, D, RH))
-O, L = True, False
-CELLS = [
-    ("32x1-obs-wps1", "f64 fast f32", 20, "small", 16, 2, "", [(1, O, 3, 1)]),
-    ("32x1-obs-wps2", "f64 fast f32", 16, "wps2", 16, 2, "", [(2, O, 3, 1)]),
-    ("64x1-obs-wps1", "f64 fast f32", 50, "small", 16, 2, "", [(1, O, 3, 1)]),
-    ("64x1-obs-wps2", "f64 fast f32", 40, "wps2", 5, 2, "", [(2, O, 3, 1)]),
-    ("64x2-obs-wps1", "f64 fast f32", 100, "small", 16, 2, "", [(1, O, 3, 0)]),
-    ("64x4-obs-wps1", "f64 fast f32", 200, "small", 16, 2, "", [(1, O, 3, 0)]),
-    ("32x1-level-wps1", "f64 fast f32", 24, "small", 16, 0, "", [(1, L, 2, 1), (1, L, 3, 1)]),
-    ("32x1-level-wps2", "f64 fast f32", 16, "wps2", 16, 0, "", [(2, L, 2, 1), (2, L, 3, 1)]),
-    ("32x1-level-rh-wps2", "f64 fast", 32, "wps2", 16, 0, "", [(2, L, 2, 4), (1, L, 3, 1)]),
-    ("32x1-level-wps2-general-wps1", "f32", 32, "wps2", 16, 0, "", [(2, L, 2, 1), (1, L, 3, 1)]),
-    ("64x1-level-wps1", "f64 fast f32", 50, "small", 16, 0, "", [(1, L, 2, 1), (1, L, 3, 1)]),
-    ("64x1-level-wps2", "f64 fast f32", 40, "wps2", 5, 0, "", [(2, L, 2, 1), (2, L, 3, 1)]),
-    ("64x1-level-rh-wps2", "f64 fast", 64, "wps2", 16, 0, "", [(2, L, 2, 5), (1, L, 3, 1)]),
-    ("64x1-level-wps2-general-wps1", "f32", 64, "wps2", 16, 0, "", [(2, L, 2, 1), (1, L, 3, 1)]),
-    ("64x2-noobs-wps1", "f64 fast f32", 100, "small", 16, 0, "", [(1, L, 3, 0)]),
-    ("64x4-noobs-wps1", "f64 fast f32", 180, "small", 16, 0, "", [(1, L, 3, 0)]),
-    ("32x1-planz-noobs-wps2", "f64 fast f32", 16, "wps2", 16, 0, "plan_in_z", [(2, L, 3, 1)]),
-    ("64x1-strictz-noobs-wps1", "f64 fast f32", 50, "small", 16, 0, "strict_z", [(1, L, 3, 1)]),
-    ("64x1-planz-noobs-wps2", "f64 f32", 40, "wps2", 5, 0, "plan_in_z", [(2, L, 3, 1)]),
-    # f64_fast, 32 < N <= 64, more waves than SIMDs, plan_in_z or strict_z: the obstacle instantiation without a list
-    ("64x1-redirect-wps1", "fast", 50, "wps2", 16, 0, "strict_z", [(1, O, 3, 1)]),
-    ("64x1-redirect-wps2", "fast", 40, "wps2", 5, 0, "plan_in_z", [(2, O, 3, 1)]),
-]
-
-
+# ---- A: the dispatch matrix (CELLS, solver_dispatch_rule.py) ------------------------------------------------------
 def cell_params(modes):
     return [pytest.param(m, c, id=f"{m}-{c[0]}") for m in modes for c in CELLS if m in c[1].split()]
 
 
 def cell_batch(world, cell, simds):
-    name, _, N, bk, mem, n_obs, flags, _ = cell
-    tpb = WAVE // shape_for(N)[0]
-    B = tpb * simds + 1 if bk == "wps2" else 40
+    name, _, N, _, mem, n_obs, flags, _ = cell
+    B = cell_batch_size(cell, simds)
     # level and vertically jittered trajectories mixed, so that both launches of a level call have waves to solve
     b = synth.make_bspline_batch(world, B, N, 5000 + N + B + mem, start_range=3.0, n_obs=n_obs, z_jitter=0.02, z_share=0.3)
     P = default_params()
@@ -146,9 +53,11 @@ def check_cell(mode, cell, b, P, simds):
     name, _, N, _, mem, n_obs, flags, want = cell
     got = launches(mode, N, b.B, mem, n_obs > 0, P.plan_in_z, P.strict_z, simds)
     assert got == want, f"{mode}-{name}: the launch rule now selects {[kernel_name(mode, N, *k) for k in got]}"
+    level = is_level(b.ctrl)
+    if any(k[2] == 1 for k in want):
+        assert level.any() and not level.all(), "some trajectories level and some not"
     if any(k[2] == 2 for k in want):
         tpb = WAVE // shape_for(N)[0]
-        level = is_level(b.ctrl)
         wave_level = np.array([level[i:i + tpb].all() for i in range(0, b.B, tpb)])
         assert wave_level.any() and not wave_level.all(), "both launches of the level call must have waves to solve"
 

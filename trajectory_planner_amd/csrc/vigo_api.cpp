@@ -11,6 +11,7 @@
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_handle.hpp"
+#include "vigo_solver_plan.hpp"
 #include "vigo_traj_runs.hpp"
 #include "vigo_ws_layout.hpp"
 
@@ -115,7 +116,7 @@ SolveArgs solve_args(int B, int N, double* ctrl, const int32_t* guide_off, const
 }
 
 // the L-BFGS history of a solve workgroup fits the LDS of a CU
-bool lds_fits(vigo_handle_t h, int N) { return vigo::optimize_lds_requirement(N, h->params.mem_size, h->precision) <= (size_t)160 * 1024; }
+bool lds_fits(vigo_handle_t h, int N) { return vigo::optimize_lds_requirement(N, h->params.mem_size, h->precision) <= vigo::kLdsPerWorkgroup; }
 const char* const kLdsMsg = "the L-BFGS history of N control points x mem_size does not fit the 160 KiB LDS of a CU";
 
 // the control points a spline gate evaluates (the solver's own range starts at 7: check_solve_args)
@@ -349,7 +350,7 @@ int vigo_create(vigo_handle_t* out, int device_ordinal) {
         (void)vigo_destroy(h);
         return VIGO_ERR_HIP;
     }
-    // launch geometry of this handle's device (vigo_solver.hip decides one or two waves per SIMD from it)
+    // launch geometry of this handle's device (plan_optimize decides one or two waves per SIMD from it)
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0)
         h->launch.simd_count = 4 * cus;

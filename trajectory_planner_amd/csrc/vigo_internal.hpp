@@ -96,7 +96,7 @@ inline size_t esdf_bricked_floats(int nx, int ny, int nz) {
 // Per-handle (= per-device) launch state: which kernel instantiations already had their dynamic-LDS limit raised on
 // the handle's device, and that device's SIMD count.  Nothing of this kind is kept in function statics.
 struct LaunchState {
-    uint64_t lds_attr_set = 0;   // bit per k_optimize instantiation (vigo_solver.hip)
+    uint64_t lds_attr_set = 0;   // bit per k_optimize instantiation (its index in kOptimizeKeys, vigo_solver_plan.hpp)
     bool minsnap_attr_set = false;
     bool astar_attr_set = false;
     int simd_count = 0;          // 4 per CU; 0 = unknown
@@ -106,8 +106,6 @@ struct LaunchState {
 // k: host copy (launch geometry), kd: the same constants in device memory (read by the kernels)
 int launch_cost_grad(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision);
 int launch_optimize(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L);
-// LDS bytes one solve workgroup needs for N control points (must stay <= 160 KiB)
-size_t optimize_lds_requirement(int N, int mem_size, int precision);
 
 int launch_pack_grid(hipStream_t s, int nx, int ny, int nz, const uint8_t* vox, uint32_t* packed);
 int launch_inflate(hipStream_t s, int nx, int ny, int nz, uint8_t* vox, uint32_t* planeA, uint32_t* planeB, int rx, int ry, int rz);

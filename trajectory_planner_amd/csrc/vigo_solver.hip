@@ -29,22 +29,13 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "vigo_internal.hpp"
+#include "vigo_solver_plan.hpp"
 
 namespace vigo {
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kMaxMem = VIGO_MAX_MEM_SIZE;
-// Dynamic-obstacle table of the solve kernel: per trajectory, {predicted x, predicted y, threshold}
-// of up to kObsTabEntries (obstacle, predicted step) pairs plus the obstacles' sizes, staged in LDS
-// once per solve (they do not depend on the control points).  Sized so that the N = 32 and N = 64
-// shapes keep four waves per CU (<= 40 KiB per wave, history slots with their zero column included):
-// 8 obstacles x 11 predicted steps for two trajectories per wave, 3 x 11 for one.
-constexpr int kObsTabObs = 16;
-template <int GROUP> constexpr int kObsTabEntries = GROUP == 32 ? 88 : 33;
-template <int GROUP> constexpr int kObsTabDoubles = 3 * kObsTabEntries<GROUP> + kObsTabObs;
 
 // reference status codes, LB:20-80
 enum : int {
@@ -1016,7 +1007,7 @@ __device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd
 // OBS == false: the instantiation the launcher picks for calls without an obstacle list (A.obs == nullptr): no staging
 // code, no obstacle loop, six sums per evaluation instead of seven — the same bits, fewer live registers
 // RH = history pairs besides the newest that stay in registers (ages 1 .. RH; 0 for more than one point per lane: all in
-// LDS): 1 normally; 4 or 5 in the level instantiations launched on batches that fill the chip (kLevelRH below):
+// LDS): 1 normally; 4 or 5 in the level instantiations launched on batches that fill the chip (kLevelRH, vigo_solver_plan.hpp):
 // fewer ring slots in LDS are more resident waves per CU
 template <typename T, int GROUP, int PPL, bool FAST, int WPS = 1, bool OBS = true, int D = 3, int RH = (PPL == 1 ? 1 : 0)>
 __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevConst* __restrict__ Kp) {
@@ -1607,26 +1598,13 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     }
 }
 
-template <typename T, int GROUP, bool FAST, int D = 3>
-size_t optimize_lds_bytes(int N, int m, int ppl, bool with_obstacles, int rh = 1) {
-    const int TPB = D == 1 ? 1 : kWave / GROUP;   // D == 1, the axis-per-lane layout: one trajectory per wave ...
-    const int COLS = kWave / GROUP;               // ... and a 16-byte record per free control point and AXIS
-    const int ms = ppl == 1 ? (m > rh + 1 ? m - (rh + 1) : 0) : m;   // REG1: ages 0 .. rh live in registers
-    // per slot: one record per free control point + the zero column, then {ys, 1/ys} per trajectory (see k_optimize)
-    const size_t slot = ((size_t)COLS * (N - 6) + 1) * sizeof(HPair<T, D>) + (((size_t)TPB * sizeof(YSv<FAST>) + 15) & ~(size_t)15);
-    size_t h = (size_t)ms * slot;
-    h += (size_t)m * TPB * sizeof(double);        // the alphas of the general two-loop
-    if (with_obstacles) h += (size_t)TPB * kObsTabDoubles<GROUP> * sizeof(double);
-    return h;
-}
-
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-
 }  // namespace
 
 #ifndef VIGO_SOLVER_PART
 #define VIGO_SOLVER_PART 0
 #endif
+
+using SolveKernel = void (*)(SolveArgs, const DevConst*);
 
 #if VIGO_SOLVER_PART == 0
 DevConst make_dev_const(const vigo_params_t& P) {
@@ -1665,54 +1643,48 @@ DevConst make_dev_const(const vigo_params_t& P) {
     return K;
 }
 
-#endif  // VIGO_SOLVER_PART == 0
-
-// (GROUP, PPL) for N control points: 32 x 1 up to 32, then 64 x {1, 2, 4}
-static inline int shape_for(int N) { return N <= 32 ? 0 : (N <= 64 ? 1 : (N <= 128 ? 2 : 3)); }
-
-#if VIGO_SOLVER_PART == 0
-template <typename T, bool FAST>
-static int launch_cost_grad_t(hipStream_t s, const SolveArgs& a, const DevConst* kd) {
-    const int shape = shape_for(a.N);
-    const int tpb = shape == 0 ? 2 : 1;
-    dim3 grid((a.B + tpb - 1) / tpb), block(kWave);
-    switch (shape) {
-        case 0: hipLaunchKernelGGL((k_cost_grad<T, 32, 1, FAST>), grid, block, 0, s, a, kd); break;
-        case 1: hipLaunchKernelGGL((k_cost_grad<T, 64, 1, FAST>), grid, block, 0, s, a, kd); break;
-        case 2: hipLaunchKernelGGL((k_cost_grad<T, 64, 2, FAST>), grid, block, 0, s, a, kd); break;
-        default: hipLaunchKernelGGL((k_cost_grad<T, 64, 4, FAST>), grid, block, 0, s, a, kd); break;
-    }
+int launch_cost_grad(hipStream_t s, const SolveArgs& a, const DevConst&, const DevConst* kd, int precision) {
+    if (a.B <= 0) return hipSuccess;
+    // rows: fp32, fp64 fast, fp64; columns: the shapes 32 x 1, 64 x 1, 64 x 2, 64 x 4
+    static constexpr SolveKernel kernels[3][4] = {
+        {&k_cost_grad<float, 32, 1, false>, &k_cost_grad<float, 64, 1, false>, &k_cost_grad<float, 64, 2, false>, &k_cost_grad<float, 64, 4, false>},
+        {&k_cost_grad<double, 32, 1, true>, &k_cost_grad<double, 64, 1, true>, &k_cost_grad<double, 64, 2, true>, &k_cost_grad<double, 64, 4, true>},
+        {&k_cost_grad<double, 32, 1, false>, &k_cost_grad<double, 64, 1, false>, &k_cost_grad<double, 64, 2, false>, &k_cost_grad<double, 64, 4, false>}};
+    const Shape sh = shape_for(a.N);
+    const int tpb = kWave / sh.group;
+    const SolveKernel kernel = kernels[precision == VIGO_PREC_F32 ? 0 : (precision == VIGO_PREC_F64_FAST ? 1 : 2)]
+                                      [sh.ppl == 1 ? sh.group / 64 : sh.ppl / 2 + 1];
+    hipLaunchKernelGGL(kernel, dim3((a.B + tpb - 1) / tpb), dim3(kWave), 0, s, a, kd);
     return (int)hipGetLastError();
 }
-
-int launch_cost_grad(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision) {
-    (void)k;
-    if (a.B <= 0) return hipSuccess;
-    if (precision == VIGO_PREC_F32) return launch_cost_grad_t<float, false>(s, a, kd);
-    if (precision == VIGO_PREC_F64_FAST) return launch_cost_grad_t<double, true>(s, a, kd);
-    return launch_cost_grad_t<double, false>(s, a, kd);
-}
 #endif  // VIGO_SOLVER_PART == 0
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: the "already raised" flags live in the handle
-// (LaunchState, one per handle = per device), never in function statics, so a second device of the same process
-// gets its own.  SLOT numbers one k_optimize instantiation.
-template <typename KernelT>
-static int raise_dynamic_lds(LaunchState& L, int slot, KernelT kernel) {
-    if (L.lds_attr_set & (1ull << slot)) return (int)hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kLdsPerWorkgroup);
-    if (e != hipSuccess) return (int)e;
-    L.lds_attr_set |= 1ull << slot;
-    return (int)hipSuccess;
-}
+// This file is compiled TWICE (csrc/Makefile).  VIGO_SOLVER_PART == 1: only the k_optimize instantiations for calls WITH
+// an obstacle list, built with machine LICM (their inner obstacle loops want their invariants hoisted: 1.85 vs 1.92 ms on
+// config 5a); VIGO_SOLVER_PART == 0: everything else, built without it (-3 % on configs 2 and 4).
 
-// History pairs besides the newest that the level kernel keeps in registers on batches with more waves than SIMDs
-// (1 = as everywhere), where LDS decides how many waves a CU holds.  N <= 32 (two trajectories per wave): 4 pairs,
-// 24.4 -> 19.3 KB, six -> EIGHT waves per CU (256 VGPRs, no spills): 1.74 -> 1.47 ms at 16 384 x 32 (2 pairs: 1.60,
-// 3: 1.61, 5: 1.54).  32 < N <= 64 (one per wave): 5 pairs, 26.8 -> 19.2 KB, six -> eight: 1.85 -> 1.54 ms at 8192 x 64
-// (4 pairs, seven waves: 1.71; 6 pairs: 1.57).  Same arithmetic, same bits.
-constexpr int kLevelRH = 4, kLevelRH64 = 5;
+// The kernel table, expanded from kOptimizeKeys (vigo_solver_plan.hpp): row I is that key's instantiation in the part
+// that builds it, nullptr in the other.
+template <int I>
+static constexpr SolveKernel optimize_kernel_of() {
+    constexpr OptimizeKey k = kOptimizeKeys[I];
+    if constexpr (k.obs == (VIGO_SOLVER_PART == 1)) {
+        using T = std::conditional_t<k.precision == VIGO_PREC_F32, float, double>;
+        constexpr bool FAST = k.precision == VIGO_PREC_F64_FAST;
+        static_assert(sizeof(T) == elem_bytes_of(k.precision) && sizeof(HPair<T, k.d>) == hpair_bytes(sizeof(T), k.d) &&
+                          sizeof(YSv<FAST>) == ysv_bytes(FAST), "optimize_lds_bytes computes these sizes by arithmetic");
+        return &k_optimize<T, k.group, k.ppl, FAST, k.wps, k.obs, k.d, k.rh>;
+    }
+    return nullptr;
+}
+template <class Rows> struct OptimizeKernelTable;
+template <int... I> struct OptimizeKernelTable<std::integer_sequence<int, I...>> { static constexpr SolveKernel row[] = {optimize_kernel_of<I>()...}; };
+static SolveKernel optimize_kernel(int key) { return OptimizeKernelTable<std::make_integer_sequence<int, kOptimizeKeyCount>>::row[key]; }
+
+#if VIGO_SOLVER_PART == 1
+SolveKernel optimize_kernel_with_obstacles(int key) { return optimize_kernel(key); }
+#else
+SolveKernel optimize_kernel_with_obstacles(int key);
 // dev builds only (-DVIGO_EXP_AXIS_SWITCH=1, tools/exp_solver.py): VIGO_EXP_AXIS=0 in the environment, read at every
 // launch, keeps the axis-per-lane level kernel out of the dispatch, so that one process times both — never defined
 // in the shipped library
@@ -1727,135 +1699,31 @@ static inline bool axis_dispatch_on() {
     return true;
 #endif
 }
-template <typename T, int GROUP, int PPL, bool FAST, bool OBS>
-static int launch_optimize_t(hipStream_t s, const SolveArgs& a_in, const DevConst& k, const DevConst* kd, LaunchState& L) {
-    const int tpb = kWave / GROUP;
+
+// Executes plan_optimize's launches.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: the "already raised"
+// bits live in the handle (LaunchState, one per handle = per device), never in function statics, so a second device of
+// the same process gets its own.
+int launch_optimize(hipStream_t s, const SolveArgs& a_in, const DevConst& k, const DevConst* kd, int precision, LaunchState& L) {
+    static_assert(kOptimizeKeyCount <= 8 * (int)sizeof(L.lds_attr_set), "one bit per k_optimize instantiation");
+    if (a_in.B <= 0) return hipSuccess;
+    const OptimizePlan plan = plan_optimize(a_in.N, a_in.B, precision, a_in.obs != nullptr, k.plan_in_z != 0, k.strict_z != 0,
+                                            k.mem_size, L.simd_count, axis_dispatch_on());
+    if (plan.count < 0) return (int)hipErrorInvalidValue;
     SolveArgs a = a_in;
-    dim3 grid((a.B + tpb - 1) / tpb), block(kWave);
-    // slot = arithmetic (fp32 / fp64 / fp64 fast) x shape (GROUP, PPL) x waves per SIMD x with / without obstacles;
-    // the level instantiations (one point per lane, no obstacles) follow from 48 on
-    const int arith = std::is_same<T, float>::value ? 0 : (FAST ? 2 : 1);
-    const int shape = GROUP == 32 ? 0 : (PPL == 1 ? 1 : (PPL == 2 ? 2 : 3));
-    const int slot = (arith * 4 + shape) * 4;
-    // a solver wavefront per SIMD (4 per CU) is full occupancy for these kernels; unknown SIMD count: never switch
-    const int simds = L.simd_count > 0 ? L.simd_count : (1 << 30);
-    auto go = [&](auto kernel, int sl, size_t lds) -> int {
-        int e = raise_dynamic_lds(L, sl, kernel);
-        if (e != (int)hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, a, kd);
-        return (int)hipGetLastError();
-    };
-    // Calls that can hold level trajectories (no z planning) and have an instantiation for them are two launches: FIRST the
-    // level kernel, whose waves with a trajectory that is not level exit at once, THEN the general kernel, whose waves
-    // of level trajectories do (after the axis-per-lane launch: whose GROUPS of a level trajectory do).  The order matters: each launch decides from the control points it finds; a level
-    // trajectory's z is untouched by the first launch, so the second still sees it level and skips it — the other way
-    // round, a trajectory just outside the band that the general solve smooths into it would be solved a second time.
-    constexpr bool kHasLevel = PPL == 1 && !OBS;
-    const bool two = kHasLevel && !k.plan_in_z && !k.strict_z;
-    a.level_waves_elsewhere = two ? 1 : 0;
-    const size_t lds = optimize_lds_bytes<T, GROUP, FAST, 3>(a.N, k.mem_size, PPL, a.obs != nullptr);
-    if (lds > kLdsPerWorkgroup) return (int)hipErrorInvalidValue;  // refused earlier by vigo_optimize
-    int e = (int)hipSuccess;
-    if constexpr (kHasLevel) {
-        if (two) {
-            const size_t lds2 = optimize_lds_bytes<T, GROUP, FAST, 2>(a.N, k.mem_size, PPL, false);
-            const int slot2 = 48 + arith * 4 + shape * 2;
-            // fp64, two trajectories per wave, more waves than SIMDs: keep kLevelRH pairs besides the newest in
-            // registers when that buys a further resident wave per CU (N = 32, m = 16: 24.4 -> 22.7 KB, six -> seven)
-            constexpr int kRH = GROUP == 32 ? kLevelRH : kLevelRH64;
-            constexpr bool kHasRH = std::is_same<T, double>::value && kRH > 1;
-            bool done = false;
-            // fp64 reference order, N <= 32, a batch with at most one trajectory per SIMD (two per wave leave half the
-            // chip idle): the axis-per-lane instantiation, ONE trajectory per wave, solves every level trajectory of
-            // the batch; the general kernel then skips them one by one (level_waves_elsewhere == 2).  Its LDS
-            // (<= 12.2 KB) is below the static limit: no attribute to raise.
-            if constexpr (std::is_same<T, double>::value && !FAST && GROUP == 32) {
-                if (L.simd_count > 0 && a.B <= L.simd_count && axis_dispatch_on()) {
-                    const size_t lds1 = optimize_lds_bytes<T, GROUP, FAST, 1>(a.N, k.mem_size, PPL, false);
-                    hipLaunchKernelGGL((k_optimize<T, GROUP, PPL, FAST, 1, OBS, 1>), dim3(a.B), block, lds1, s, a, kd);
-                    e = (int)hipGetLastError();
-                    a.level_waves_elsewhere = 2;
-                    done = true;
-                }
-            }
-            if constexpr (kHasRH) {
-              if (!done) {
-                const size_t lds3 = optimize_lds_bytes<T, GROUP, FAST, 2>(a.N, k.mem_size, PPL, false, kRH);
-                if ((int)grid.x > simds && lds2 > kLdsPerWorkgroup / 8 && kLdsPerWorkgroup / lds3 > kLdsPerWorkgroup / lds2) {
-                    // (more than four waves per CU put two on a SIMD: the register-capped build, 256 VGPRs)
-                    constexpr int kWps = kRH >= 4 ? 2 : 1;
-                    e = go(&k_optimize<T, GROUP, PPL, FAST, kWps, OBS, 2, kRH>, 60 + (FAST ? 1 : 0) + (GROUP == 64 ? 2 : 0), lds3);
-                    done = true;
-                }
-              }
-            }
-            if (!done) {
-                if ((int)grid.x > simds && lds2 <= kLdsPerWorkgroup / 8) e = go(&k_optimize<T, GROUP, PPL, FAST, 2, OBS, 2>, slot2 + 1, lds2);
-                else e = go(&k_optimize<T, GROUP, PPL, FAST, 1, OBS, 2>, slot2, lds2);
-            }
-            if (e != (int)hipSuccess) return e;
+    for (int i = 0; i < plan.count; ++i) {
+        const PlannedLaunch& p = plan.launch[i];
+        const SolveKernel kernel = kOptimizeKeys[p.key].obs ? optimize_kernel_with_obstacles(p.key) : optimize_kernel(p.key);
+        const uint64_t bit = 1ull << p.key;
+        if (p.lds > kLdsStaticLimit && !(L.lds_attr_set & bit)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerWorkgroup);
+            if (e != hipSuccess) return (int)e;
+            L.lds_attr_set |= bit;
         }
+        a.level_waves_elsewhere = p.level_waves_elsewhere;
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(kWave), p.lds, s, a, kd);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     }
-    if (PPL == 1 && (int)grid.x > simds && lds <= kLdsPerWorkgroup / 8) {   // more waves than SIMDs and 8 fit a CU: two per SIMD
-        if constexpr (PPL == 1) e = go(&k_optimize<T, GROUP, PPL, FAST, 2, OBS, 3>, slot + (OBS ? 1 : 3), lds);
-        else e = (int)hipErrorInvalidValue;
-    } else {
-        e = go(&k_optimize<T, GROUP, PPL, FAST, 1, OBS, 3>, slot + (OBS ? 0 : 2), lds);
-    }
-    return e;
-}
-
-template <typename T, bool FAST, bool OBS>
-static int launch_optimize_p(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, LaunchState& L) {
-    // (one trajectory per wave for N <= 32 as 64 x 1 — one control point per lane, half the lanes idle, a sixth butterfly
-    // level in every reduction and no instruction saved — measured slower: 0.462 vs 0.445 ms at B = 1024, 6.40 vs
-    // 3.60 ms at B = 16384.  One trajectory per wave with one COORDINATE per lane is a different thing: the AXIS
-    // instantiation of k_optimize, which launch_optimize_t takes for level trajectories on batches of up to one per SIMD)
-    switch (shape_for(a.N)) {
-        // (a 16-lane x 2-point shape saves one butterfly level but measured 22 % slower: 1.76 M vs 2.26 M/s)
-        case 0: return launch_optimize_t<T, 32, 1, FAST, OBS>(s, a, k, kd, L);
-        case 1: return launch_optimize_t<T, 64, 1, FAST, OBS>(s, a, k, kd, L);
-        case 2: return launch_optimize_t<T, 64, 2, FAST, OBS>(s, a, k, kd, L);
-        default: return launch_optimize_t<T, 64, 4, FAST, OBS>(s, a, k, kd, L);
-    }
-}
-
-template <bool OBS>
-static int launch_optimize_o(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L) {
-    if (precision == VIGO_PREC_F32) return launch_optimize_p<float, false, OBS>(s, a, k, kd, L);
-    if (precision == VIGO_PREC_F64_FAST) return launch_optimize_p<double, true, OBS>(s, a, k, kd, L);
-    return launch_optimize_p<double, false, OBS>(s, a, k, kd, L);
-}
-
-// This file is compiled TWICE (csrc/Makefile).  VIGO_SOLVER_PART == 1: only the k_optimize instantiations for calls WITH
-// an obstacle list, built with machine LICM (their inner obstacle loops want their invariants hoisted: 1.85 vs 1.92 ms on
-// config 5a); VIGO_SOLVER_PART == 0: everything else, built without it (-3 % on configs 2 and 4).
-#if VIGO_SOLVER_PART == 1
-int launch_optimize_with_obstacles(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L) {
-    return launch_optimize_o<true>(s, a, k, kd, precision, L);
-}
-#else
-int launch_optimize_with_obstacles(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L);
-int launch_optimize(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L) {
-    if (a.B <= 0) return hipSuccess;
-    if (a.obs != nullptr) return launch_optimize_with_obstacles(s, a, k, kd, precision, L);
-    // Measured (tools/exp_solver.py, VIGO_EXP_MATRIX=1: N = 16 ... 200 x the three arithmetic modes): the instantiation
-    // without obstacle code is 4 - 18 % faster everywhere except f64_fast at 32 < N <= 64 on batches with more waves
-    // than SIMDs (8 % slower there): those keep the general kernel, which treats a missing list as no obstacles.
-    // (Only where the level instantiation cannot apply — z planning on: with it, level waves go to the D = 2 kernel, 20 %
-    // faster than either, and the corner is not worth keeping them from it.)
-    if (precision == VIGO_PREC_F64_FAST && a.N > 32 && a.N <= 64 && L.simd_count > 0 && a.B > L.simd_count && (k.plan_in_z || k.strict_z))
-        return launch_optimize_with_obstacles(s, a, k, kd, precision, L);
-    return launch_optimize_o<false>(s, a, k, kd, precision, L);
-}
-
-// bytes of LDS one trajectory-solve workgroup needs; the C ABI refuses N it cannot hold
-size_t optimize_lds_requirement(int N, int mem_size, int precision) {
-    const bool g32 = N <= 32;
-    const int ppl = N <= 64 ? 1 : (N <= 128 ? 2 : 4);
-    if (precision == VIGO_PREC_F32) return g32 ? optimize_lds_bytes<float, 32, false>(N, mem_size, ppl, true) : optimize_lds_bytes<float, 64, false>(N, mem_size, ppl, true);
-    if (precision == VIGO_PREC_F64_FAST) return g32 ? optimize_lds_bytes<double, 32, true>(N, mem_size, ppl, true) : optimize_lds_bytes<double, 64, true>(N, mem_size, ppl, true);
-    return g32 ? optimize_lds_bytes<double, 32, false>(N, mem_size, ppl, true) : optimize_lds_bytes<double, 64, false>(N, mem_size, ppl, true);
+    return (int)hipSuccess;
 }
 #endif  // VIGO_SOLVER_PART
 
