@@ -340,12 +340,39 @@ struct LaneProblem {
     double w[4];
 };
 
+// The constants an L-BFGS iteration uses, for the iteration loop of k_optimize and the helpers it calls — the type KC
+// below.  It is DevConst itself, in memory, wherever the kernel sits at the register limit (every instantiation but
+// AXIS): a uniform address, scalar loads at the use sites, not 100+ live SGPRs.  The AXIS kernel has a wave alone on
+// its SIMD and registers to spare, and there every one of those loads is a scalar-cache round trip that nothing else
+// covers (profiles/README.md): it reads the fields ONCE, at entry, into a HotConst.  The same field names, so one text
+// serves both; the same values, so the same bits.  Read from the device copy at every launch: vigo_set_params between
+// two solves takes effect as before.
+__device__ __forceinline__ void hold_in_reg(double& v) { asm volatile("" : "+v"(v)); }   // opaque from here on: the compiler
+__device__ __forceinline__ void hold_in_reg(int& v) { asm volatile("" : "+s"(v)); }      // cannot go back to memory for it
+struct HotConst {
+    double dth, da, db, dc, unc_factor;                          // distance term
+    double ts_ctrl, ts_inv_sqr;                                  // stencils
+    double g_epsilon, min_step, max_step, ftol, gtol, xtol;      // L-BFGS and the line search
+    int max_iterations, max_linesearch;
+    __device__ __forceinline__ explicit HotConst(const DevConst& K)
+        : dth(K.dth), da(K.da), db(K.db), dc(K.dc), unc_factor(K.unc_factor), ts_ctrl(K.ts_ctrl), ts_inv_sqr(K.ts_inv_sqr),
+          g_epsilon(K.g_epsilon), min_step(K.min_step), max_step(K.max_step), ftol(K.ftol), gtol(K.gtol), xtol(K.xtol),
+          max_iterations(K.max_iterations), max_linesearch(K.max_linesearch) {
+        hold_in_reg(dth); hold_in_reg(da); hold_in_reg(db); hold_in_reg(dc); hold_in_reg(unc_factor);
+        hold_in_reg(ts_ctrl); hold_in_reg(ts_inv_sqr);
+        hold_in_reg(g_epsilon); hold_in_reg(min_step); hold_in_reg(max_step); hold_in_reg(ftol); hold_in_reg(gtol); hold_in_reg(xtol);
+        hold_in_reg(max_iterations); hold_in_reg(max_linesearch);
+    }
+};
+template <bool HOT>
+using LoopConst = std::conditional_t<HOT, HotConst, const DevConst&>;
+
 // One guide pair's contribution, BT.cpp:839-895.  e == dthresh takes the cubic branch (first
 // else-if wins); the "too far" branch is never scaled by the unknown factor.
 // the penalty at signed distance `dist` from the pair's plane: cost ct, gradient factor k along the pair's direction,
 // and whether the unknown factor scales both; false in the no-penalty band
-template <typename T>
-__device__ __forceinline__ bool guide_penalty(const DevConst& K, T dist, bool unk, T& ct, T& k, bool& scale) {
+template <typename T, class KC>
+__device__ __forceinline__ bool guide_penalty(const KC& K, T dist, bool unk, T& ct, T& k, bool& scale) {
     const T dth = (T)K.dth, da = (T)K.da, db = (T)K.db, dcc = (T)K.dc;
     const T e = dth - dist;
     scale = false;
@@ -386,8 +413,9 @@ __device__ __forceinline__ void guide_pair_term(const DevConst& K, const T (&c)[
 // two in the order above, the z product follows; both lanes of a point then hold the same dist, take the same branch
 // and count the same cost (callers reduce it over one half of the wave only), and each scales its own v for the gradient.
 // Must be reached by both lanes of a point together: the exchange reads the partner lane.
-__device__ __forceinline__ void guide_pair_term_axis(const DevConst& K, double c, double cz, double p, double pz, double v,
-                                                     double vz, bool unk, double& cd, double& Gd) {
+template <class KC>
+__device__ __forceinline__ void guide_pair_term_axis(const KC& K, double c, double cz, double p, double pz, double v, double vz,
+                                                     bool unk, double& cd, double& Gd) {
     const double uf = K.unc_factor;
     const double dist = dot_xy(c - p, v) + (cz - pz) * vz;
     double ct, k;
@@ -456,8 +484,8 @@ __device__ __forceinline__ void obstacle_term_tab(const DevConst& K, const T (&c
 // The smoothness and feasibility stencils of ONE coordinate, C = that coordinate of the lane's points: jerk, velocity
 // and acceleration terms (jj, vv, aa: the cost partials of the term whose first point is the lane's) and the gradient
 // columns Gs, Gf of the lane's points.  no_terms: the z coordinate of a level trajectory in the general kernel.
-template <typename T, int PPL, bool FAST>
-__device__ __forceinline__ void stencil_axis(const DevConst& K, const T (&C)[PPL], bool no_terms, double (&jj)[PPL],
+template <typename T, int PPL, bool FAST, class KC>
+__device__ __forceinline__ void stencil_axis(const KC& K, const T (&C)[PPL], bool no_terms, double (&jj)[PPL],
                                              double (&vv)[PPL], double (&aa)[PPL], T (&Gs)[PPL], T (&Gf)[PPL]) {
     const T ts = (T)K.ts_ctrl, tis = (T)K.ts_inv_sqr;
     auto excess = [](T v) -> T { return v > T(1.0) ? v - T(1.0) : (v < T(-1.0) ? v + T(1.0) : T(0.0)); };
@@ -674,7 +702,8 @@ __device__ __forceinline__ double eval_cost_grad(const DevConst& K, const LanePr
 // half of the wave.  Wherever eval_cost_grad<.., D = 2> adds the x term and the y term of a point, the xor-32 exchange
 // hands both lanes both terms and they add them in that order; what follows (the exact-zero z terms, the 32-lane tree)
 // is then the same in both halves, which end with the same bits in every sum — and so with the same line-search scalars.
-__device__ __forceinline__ double eval_cost_grad_axis(const DevConst& K, const LaneProblem<double, 1>& Q, int axis,
+template <class KC>
+__device__ __forceinline__ double eval_cost_grad_axis(const KC& K, const LaneProblem<double, 1>& Q, int axis,
                                                       const double (&c)[1][3], const double (&d)[1][3], double (&g)[1][3],
                                                       double (&sums)[7]) {
     using LP = LaneProblem<double, 1>;
@@ -1036,6 +1065,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     constexpr int kYsSlotBytes = (TPB * (int)sizeof(YS) + 15) & ~15;
     const int slotB = ROWP * (int)sizeof(HPair<T, D>) + kYsSlotBytes;
     const int m = K.mem_size;
+    const LoopConst<AXIS> KL(K);   // what the iteration loop reads: K itself, or (AXIS) its fields held in registers
     // REG1 (one control point per lane): the two newest history pairs (ages 0 and 1) stay in
     // registers, LDS holds the older m - 2 — at N = 64, m = 16 that is 38.3 KB instead of 43.8 KB
     // per wave, i.e. four resident waves per CU (one per SIMD) instead of three.
@@ -1174,7 +1204,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         int count = 0, brackt = 0, stage1 = 1, uinfo = 0;
         double dginit = 0.0, finit = 0.0, dgtest = 0.0, width = 0.0, prev_width = 0.0;
         double xt = 0., xf = 0., xd = 0., yt = 0., yf = 0., yd = 0.;
-        const double stpmin = K.min_step, stpmax = K.max_step;
+        const double stpmin = KL.min_step, stpmax = KL.max_step;
         bool run = true;
         if (!first) {
 #pragma unroll
@@ -1186,7 +1216,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
             if (step <= 0.) { ls = LBERR_INVALIDPARAMETERS; run = false; }
             else if (0 < dginit) { ls = LBERR_INCREASEGRADIENT; run = false; }
             finit = fx;
-            dgtest = K.ftol * dginit;
+            dgtest = KL.ftol * dginit;
             width = stpmax - stpmin;
             prev_width = 2.0 * width;
             xt = yt = 0.;
@@ -1205,8 +1235,8 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
                 }
                 if (step < stpmin) step = stpmin;
                 if (stpmax < step) step = stpmax;
-                if ((brackt && ((step <= stmin || stmax <= step) || K.max_linesearch <= count + 1 || uinfo != 0)) ||
-                    (brackt && (stmax - stmin <= K.xtol * stmax))) {
+                if ((brackt && ((step <= stmin || stmax <= step) || KL.max_linesearch <= count + 1 || uinfo != 0)) ||
+                    (brackt && (stmax - stmin <= KL.xtol * stmax))) {
                     step = xt;
                 }
                 // x <- xp + step * d  (LB:824-825)
@@ -1220,8 +1250,8 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 
             VIGO_TICK(t_pre);
             // the only evaluation site (LB:828, :1132)
-            if constexpr (AXIS) fx = eval_cost_grad_axis(K, Q, grp, x, d, g, sums);
-            else fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(K, Q, x, d, g, sums);
+            if constexpr (AXIS) fx = eval_cost_grad_axis(KL, Q, grp, x, d, g, sums);
+            else fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(KL, Q, x, d, g, sums);
             VIGO_TICK(t_eval);
             ++evals;
             if (first) break;
@@ -1234,16 +1264,16 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
             // in reverse order and ONE branch (six exec-mask branches cost more issue slots than the compares)
             {
                 int code = 0;
-                if (fx <= ftest1 && fabs(dg) <= K.gtol * (-dginit)) code = count;                      // LB:862-866 (count >= 1)
-                if (K.max_linesearch <= count) code = LBERR_MAXIMUMLINESEARCH;                         // LB:857-860
-                if (brackt && (stmax - stmin) <= K.xtol * stmax) code = LBERR_WIDTHTOOSMALL;           // LB:852-855
+                if (fx <= ftest1 && fabs(dg) <= KL.gtol * (-dginit)) code = count;                      // LB:862-866 (count >= 1)
+                if (KL.max_linesearch <= count) code = LBERR_MAXIMUMLINESEARCH;                         // LB:857-860
+                if (brackt && (stmax - stmin) <= KL.xtol * stmax) code = LBERR_WIDTHTOOSMALL;           // LB:852-855
                 if (step == stpmin && (ftest1 < fx || dgtest <= dg)) code = LBERR_MINIMUMSTEP;         // LB:847-850
                 if (step == stpmax && fx <= ftest1 && dg <= dgtest) code = LBERR_MAXIMUMSTEP;          // LB:842-845
                 if (brackt && ((step <= stmin || stmax <= step) || uinfo != 0)) code = LBERR_ROUNDING_ERROR;   // LB:837-840
                 if (code != 0) { ls = code; break; }
             }
 
-            const double cmin = K.ftol <= K.gtol ? K.ftol : K.gtol;
+            const double cmin = KL.ftol <= KL.gtol ? KL.ftol : KL.gtol;
             if (stage1 && fx <= ftest1 && cmin * dginit <= dg) stage1 = 0;
 
             // LB:883-920: the interval update runs on the modified function while stage1 holds and
@@ -1276,7 +1306,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 #pragma unroll
                 for (int a = 0; a < D; ++a) d[q][a] = -g[q][a];  // LB:1144
             if (xnorm < 1.0) xnorm = 1.0;
-            if (gnorm / xnorm <= K.g_epsilon) { ret = LB_ALREADY_MINIMIZED; break; }  // LB:1154-1157
+            if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_ALREADY_MINIMIZED; break; }  // LB:1154-1157
             // d = -g: d.d = g.g and g.d = -(g.g) exactly (negation commutes with every rounding)
             step = 1.0 / sqrt(sums[6]);  // LB:1163
             sums[4] = -sums[6];
@@ -1288,7 +1318,10 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
         if (ls < 0) {
             // LB:1189-1197.  optData_.controlPoints keeps the last trial (BT.cpp:803): write it
             // out now, then revert x like the reference does.
-            if constexpr (AXIS) store_point_axis(A, b, Q, grp, x[0][0], x[0][2]);
+            // (AXIS: a control point that is not free is stored as it was.  The reference never writes it; here it has
+            // been through xp + step * 0, which a step that is not finite turns into NaN — a failed search can end on
+            // one, tests/test_gpu_solver_axis_params.py.  The other instantiations still store that NaN.)
+            if constexpr (AXIS) store_point_axis(A, b, Q, grp, Q.interior[0] ? x[0][0] : xp[0][0], Q.interior[0] ? x[0][2] : xp[0][2]);
             else store_points<T, PPL>(A, b, Q, x);
 #pragma unroll
             for (int q = 0; q < PPL; ++q)
@@ -1301,8 +1334,8 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 
         // convergence test, LB:1200-1225 (norms came with the last evaluation)
         if (xnorm < 1.0) xnorm = 1.0;
-        if (gnorm / xnorm <= K.g_epsilon) { ret = LB_CONVERGENCE; break; }
-        if (K.max_iterations != 0 && K.max_iterations < k + 1) { ret = LBERR_MAXIMUMITERATION; break; }
+        if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_CONVERGENCE; break; }
+        if (KL.max_iterations != 0 && KL.max_iterations < k + 1) { ret = LBERR_MAXIMUMITERATION; break; }
 
         // s, y, ys, yy — LB:1264-1276
         T sv[PPL][3], yv[PPL][3];
