@@ -18,7 +18,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--planners", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--lib", help="another build of libtrajectory_planner_vigo.so (A/B of two builds)")
     a = ap.parse_args()
+    if a.lib:
+        rc.LIB = os.path.abspath(a.lib)
     r = rc.plan_batch_reguide(a.planners, reps=a.reps)
     for name, slot in (("0 (host step)", rc.SLOT_HOST), ("1 (vigo_rebound_reguide)", rc.SLOT_DEVICE), ("2 (workers' twin)", rc.SLOT_TWIN)):
         t = r["total_ms"][slot]

@@ -52,7 +52,6 @@ private:
     bool planInZAxis_;
     double minHeight_, maxHeight_, uncertainAwareFactor_, predHorizon_, distThreshDynamic_, maxPathLength_;
     Eigen::Vector3d maxObstacleSize_;
-    std::shared_ptr<mapManager::occMap> map_;
     std::shared_ptr<AStar> pathSearch_;
     std::vector<std::pair<int, int>> collisionSeg_;
     std::vector<std::vector<Eigen::Vector3d>> astarPaths_;
@@ -61,10 +60,7 @@ private:
     std::vector<Eigen::Vector3d> inputPathVis_;
 
     // device
-    vigo_context* dev_ = nullptr;
-    uint64_t mapStamp_ = 0;            // mapAdapter's memo of the snapshot this planner's handle holds (0 = none)
-    mapRegion mapRegion_;
-    int deviceOrdinal_ = 0;            // HIP device of this planner's handle (setDevice)
+    DeviceLink link_;                  // the map, its snapshot on the handle, the handle (mapAdapter.h)
     int lastStatus_ = 0;
     bool syncDevice();   // params + map snapshot -> handle; false when no GPU / HIP failure
 

@@ -21,6 +21,7 @@
 #include <memory>
 
 struct vigo_context;
+struct vigo_params_s;
 
 namespace trajPlanner {
 
@@ -56,6 +57,48 @@ public:
     /* rasterisation of any occMap through its four public methods over `region` (what uploadSnapshot uploads for a
      * map it cannot read in bulk); dims and origin of the grid are returned */
     static bool rasterise(mapManager::occMap& map, const mapRegion& region, std::vector<uint8_t>& voxels, int dims[3], double origin[3]);
+};
+
+/* The link between ONE planner and its device handle, held by all three facades (bsplineTraj, polyTrajOctomap,
+ * polyTrajOccMap): the map and the box of it to snapshot, the memo of the snapshot the handle holds, the HIP device
+ * ordinal, and the handle itself, which it creates on demand and destroys.  It prints nothing: sync() says why it failed
+ * and each facade keeps its own console lines. */
+class DeviceLink {
+public:
+    enum Sync { kSynced = 0, kNoMap, kNoDevice, kNoHandle, kFailed };
+    DeviceLink() = default;
+    ~DeviceLink();
+    DeviceLink(const DeviceLink&) = delete;
+    DeviceLink& operator=(const DeviceLink&) = delete;
+
+    void setMap(const std::shared_ptr<mapManager::occMap>& map);                    // forces a new snapshot
+    void setRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);   // forces a new snapshot
+    /* the map changed: every handle that holds a snapshot of it is stale, not only this one (generation, above) */
+    void refresh();
+    /* One process per GPU is the deployment the back-end is built for (HIP_VISIBLE_DEVICES picks the card); a process
+     * that drives several cards gives each planner its ordinal before the planner's first device call.  The current
+     * ordinal: nothing happens.  Another: the link lets go of its handle; the next sync() creates one there and uploads
+     * the map again. */
+    void setDevice(int ordinal);
+    /* In this order: the ordinal's GPU made current on the calling thread (its stream and staging buffers are per
+     * thread and device), the handle created on demand, its launches and copies bound to the calling thread's stream
+     * (two host threads planning two batches then overlap on the device), `params` pushed when given, the map
+     * snapshotted again if it changed.  Without a map: kNoMap before anything else when `needMap`, else no snapshot. */
+    Sync sync(bool needMap, const vigo_params_s* params = nullptr);
+
+    vigo_context* handle() const { return dev_; }
+    const std::shared_ptr<mapManager::occMap>& map() const { return map_; }
+    const mapRegion& region() const { return region_; }
+    int ordinal() const { return ordinal_; }
+    /* two planners may share one handle's state: same device, same map object, same box of it */
+    bool sameTarget(const DeviceLink& o) const { return ordinal_ == o.ordinal_ && map_ == o.map_ && sameRegion(region_, o.region_); }
+
+private:
+    std::shared_ptr<mapManager::occMap> map_;
+    mapRegion region_;
+    uint64_t stamp_ = 0;   // uploadSnapshot's memo of the snapshot the handle holds (0 = none)
+    int ordinal_ = 0;
+    vigo_context* dev_ = nullptr;
 };
 
 }  // namespace trajPlanner

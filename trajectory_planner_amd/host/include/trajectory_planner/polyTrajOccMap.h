@@ -23,13 +23,16 @@
 #include <set>
 #include <vector>
 
-struct vigo_context;
+namespace vigo_host {
+template <class Planner> struct LockStepBatch;   // the lock-step loop of makePlanBatch (src/polyBatchLoop.h)
+struct QpMember;
+struct TrajCheck;
+}  // namespace vigo_host
 
 namespace trajPlanner {
 class polyTrajOccMap {
 private:
     ros::NodeHandle nh_;
-    std::shared_ptr<mapManager::occMap> map_;
     std::shared_ptr<trajPlanner::polyTrajSolver> trajSolver_;
     std::shared_ptr<trajPlanner::pwlTraj> pwlTrajSolver_;
     std::vector<pose> path_;
@@ -56,18 +59,39 @@ private:
     bool findValidTraj_ = false;
     int lastIterations_ = 0;
 
-    // the device back-end of makePlanBatch (mapAdapter.h)
-    vigo_context* dev_ = nullptr;
-    uint64_t mapStamp_ = 0;
-    mapRegion mapRegion_;
-    int deviceOrdinal_ = 0;
+    // the device back-end of makePlanBatch: the map, its snapshot on the handle, the handle (mapAdapter.h)
+    DeviceLink link_;
     bool syncDevice();
     /* the planning loop of PM.cpp:326-399 in steps, driven by makePlan and makePlanBatch (polyTrajOccMap.cpp) */
-    struct PlanState;
-    PlanState begin();
-    void solveOnHost(bool corridorConstraint, PlanState& s);
+    struct PlanState {
+        bool corridors = true;          // makePlan's corridorConstraint
+        std::vector<double> corridor;   // corridorSizeVec
+        int iters = 0;                  // countIter
+        double t0 = 0;
+    };
+    PlanState begin(bool corridorConstraint);
+    void solveOnHost(PlanState& s);
     bool advance(PlanState& s, bool collides, const std::set<int>& collisionSeg);
     void finish(std::vector<pose>& trajectory, bool valid);
+    /* this planner's rules in the lock-step loop of makePlanBatch (src/polyBatchLoop.h; each is stated at its definition) */
+    friend struct vigo_host::LockStepBatch<polyTrajOccMap>;
+    struct DeviceSteps;
+    static const polyTrajOccMap* batchReference(const std::vector<polyTrajOccMap*>& ps);
+    bool batchable(const polyTrajOccMap* ref) const;
+    bool planAlone(std::vector<pose>& trajectory, bool corridorConstraint, bool& told);
+    static void planWithoutDevice(const std::vector<polyTrajOccMap*>& ps, const std::vector<size_t>& grp, bool corridorConstraint,
+                                  std::vector<std::vector<pose>>& out, std::vector<bool>& result);
+    PlanState beginBatch(bool corridorConstraint) { return begin(corridorConstraint); }
+    bool timedOutBeforeRound(const PlanState& s, size_t G) const;
+    bool timedOutAfterRound(const PlanState&, size_t) const { return false; }
+    bool hostQpOnly() const { return softConstraint_; }
+    bool sameQpGroup(const PlanState& mine, const polyTrajOccMap& o, const PlanState& theirs) const;
+    vigo_host::QpMember qpMember(size_t who, const PlanState& s) const;
+    void takeQpResult(PlanState& s, const vigo_host::QpMember& m);
+    bool validWithoutCheck(PlanState& s);
+    void checkOnHost(polyTrajOccMap& lead, vigo_host::TrajCheck& c);
+    bool finishBatch(std::vector<pose>& trajectory, bool valid);
+    static const char* batchTag() { return "[minSnapTraj]: "; }
 
 public:
     polyTrajOccMap(const ros::NodeHandle& nh);

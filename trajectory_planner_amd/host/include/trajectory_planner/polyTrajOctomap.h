@@ -23,7 +23,11 @@
 #include <set>
 #include <vector>
 
-struct vigo_context;
+namespace vigo_host {
+template <class Planner> struct LockStepBatch;   // the lock-step loop of makePlanBatch (src/polyBatchLoop.h)
+struct QpMember;
+struct TrajCheck;
+}  // namespace vigo_host
 
 namespace trajPlanner {
 class polyTrajOctomap {
@@ -44,11 +48,7 @@ private:
     std::vector<double> pwlKnots_;             // its time knots (what timeKnots() hands out while it is the plan)
     bool findValidTraj_ = false;
     double initVel_[3] = {0, 0, 0}, initAcc_[3] = {0, 0, 0};
-    std::shared_ptr<mapManager::occMap> map_;
-    vigo_context* dev_ = nullptr;
-    uint64_t mapStamp_ = 0;             // mapAdapter's memo of the snapshot the handle holds (0 = none)
-    mapRegion mapRegion_;
-    int deviceOrdinal_ = 0;             // HIP device of the handle (setDevice)
+    DeviceLink link_;                   // the map, its snapshot on the handle, the handle (mapAdapter.h)
     int lastIterations_ = 0;
     bool syncDevice();
     bool sweepPoints(const std::vector<pose>& pts, std::vector<uint8_t>& flags);
@@ -56,18 +56,42 @@ private:
     void pwlPlan(std::vector<pose>& trajectory, double delT);
     const std::vector<double>& timeKnots();
     /* the planning loop of PO.cpp:259-545 in steps, driven by planOnHost and makePlanBatch (polyTrajOctomap.cpp) */
-    struct PlanState;
+    struct PlanState {
+        bool addingWaypoints;               // PO.cpp:259-386; else the corridor constraint, PO.cpp:388-545
+        std::vector<double> corridor;       // corridor radius per segment (corridor mode)
+        int iters = 0;
+        double t0 = 0;
+    };
     PlanState begin(bool addingWaypoints);
     void solveOnHost(PlanState& s);
     bool advance(PlanState& s, bool collides, const std::set<int>& collisionSeg);
     bool advanceOnFlags(PlanState& s, const std::vector<uint8_t>& flags, double delT);
     void finish(std::vector<pose>& trajectory, double delT);
     void planOnHost(bool addingWaypoints, std::vector<pose>& trajectory, double delT);
+    /* this planner's rules in the lock-step loop of makePlanBatch (src/polyBatchLoop.h; each is stated at its definition) */
+    friend struct vigo_host::LockStepBatch<polyTrajOctomap>;
+    struct DeviceSteps;
+    static const polyTrajOctomap* batchReference(const std::vector<polyTrajOctomap*>& ps) { return ps.empty() ? nullptr : ps[0]; }
+    bool batchable(const polyTrajOctomap* ref) const;
+    bool planAlone(std::vector<pose>& trajectory, bool, bool& toldSoft);
+    static void planWithoutDevice(const std::vector<polyTrajOctomap*>& ps, const std::vector<size_t>& grp, bool,
+                                  std::vector<std::vector<pose>>& out, std::vector<bool>& result);
+    PlanState beginBatch(bool) { return begin(mode_); }
+    bool timedOutBeforeRound(const PlanState&, size_t) const { return false; }
+    bool timedOutAfterRound(const PlanState& s, size_t G) const;
+    bool hostQpOnly() const { return false; }
+    bool sameQpGroup(const PlanState& mine, const polyTrajOctomap&, const PlanState& theirs) const { return theirs.addingWaypoints == mine.addingWaypoints; }
+    vigo_host::QpMember qpMember(size_t who, const PlanState& s) const;
+    void takeQpResult(PlanState& s, const vigo_host::QpMember& m);
+    bool validWithoutCheck(PlanState&) { return false; }
+    void checkOnHost(polyTrajOctomap& lead, vigo_host::TrajCheck& c);
+    bool finishBatch(std::vector<pose>& trajectory, bool valid);
+    static const char* batchTag() { return "[Trajectory Planner INFO]: "; }
 
 public:
     polyTrajOctomap();
     polyTrajOctomap(const ros::NodeHandle& nh);
-    ~polyTrajOctomap();
+    ~polyTrajOctomap() {}
     polyTrajOctomap(const polyTrajOctomap&) = delete;
     polyTrajOctomap& operator=(const polyTrajOctomap&) = delete;
 
@@ -104,11 +128,9 @@ public:
     }
     void insertWaypoint(const std::set<int>& seg);                     // PO.cpp:178-186
     /* re-snapshot the map on the next device call (the reference re-fetches /octomap_binary, PO.cpp:133-145) */
-    void updateMap() { mapAdapter::bumpGeneration(map_.get()); mapStamp_ = 0; }
+    void updateMap() { link_.refresh(); }
     /* not in the reference: the box of the map the device snapshot covers (mapAdapter.h; ignored by the dense map) */
-    void setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) {
-        mapRegion_.set = true; mapRegion_.boxMin = boxMin; mapRegion_.boxMax = boxMax; mapStamp_ = 0;
-    }
+    void setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
 
     /* not in the reference: HIP device ordinal of this planner's back-end handle (default 0), see bsplineTraj::setDevice */
     void setDevice(int ordinal);

@@ -68,9 +68,7 @@ bsplineTraj::bsplineTraj() {}
 
 bsplineTraj::bsplineTraj(const ros::NodeHandle& nh) : nh_(nh) { this->initParam(); }
 
-bsplineTraj::~bsplineTraj() {
-    if (dev_) vigo_destroy(dev_);
-}
+bsplineTraj::~bsplineTraj() {}
 
 void bsplineTraj::init(const ros::NodeHandle& nh) {
     this->nh_ = nh;
@@ -111,7 +109,7 @@ struct bsplineTraj::SearchGroup {
     int N;
     double notCheckRatio;
     explicit SearchGroup(const bsplineTraj& lead)
-        : res(lead.map_->getRes()), N(lead.optData_.controlPoints.cols()), notCheckRatio(lead.notCheckRatio_) {
+        : res(lead.link_.map()->getRes()), N(lead.optData_.controlPoints.cols()), notCheckRatio(lead.notCheckRatio_) {
         for (int k = 0; k < 3; ++k) {
             pool[k] = 2 * int(lead.maxObstacleSize_(k) / res);
             half[k] = (pool[k] / 2 + 1) * res;
@@ -132,34 +130,15 @@ struct bsplineTraj::SearchGroup {
 
 // BT.cpp:187-195
 void bsplineTraj::setMap(const std::shared_ptr<mapManager::occMap>& map) {
-    this->map_ = map;
+    link_.setMap(map);
     this->pathSearch_.reset(new AStar);
     const SearchGroup g(*this);
     this->pathSearch_->initGridMap(map, Eigen::Vector3i(g.pool[0], g.pool[1], g.pool[2]), this->minHeight_, this->maxHeight_);
-    this->mapStamp_ = 0;  // force a new device snapshot
 }
 
-void bsplineTraj::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) {
-    this->mapRegion_.set = true;
-    this->mapRegion_.boxMin = boxMin;
-    this->mapRegion_.boxMax = boxMax;
-    this->mapStamp_ = 0;
-}
-
-void bsplineTraj::refreshMap() {
-    mapAdapter::bumpGeneration(this->map_.get());   // every handle holding a snapshot of this map is stale, not only this planner's
-    this->mapStamp_ = 0;
-}
-
-// one process per GPU is the deployment the back-end is built for (HIP_VISIBLE_DEVICES picks the card); a process that
-// drives several cards gives each planner its ordinal before the planner's first device call.  A planner that already
-// holds a handle on another card lets go of it: the next call creates a new one there and uploads the map again.
-void bsplineTraj::setDevice(int ordinal) {
-    if (ordinal == deviceOrdinal_) return;
-    if (dev_) { vigo_destroy(dev_); dev_ = nullptr; }
-    mapStamp_ = 0;
-    deviceOrdinal_ = ordinal;
-}
+void bsplineTraj::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
+void bsplineTraj::refreshMap() { link_.refresh(); }
+void bsplineTraj::setDevice(int ordinal) { link_.setDevice(ordinal); }
 
 void bsplineTraj::updateMaxVel(double maxVel) { this->maxVel_ = maxVel; }
 void bsplineTraj::updateMaxAcc(double maxAcc) { this->maxAcc_ = maxAcc; }
@@ -190,7 +169,7 @@ void bsplineTraj::fillParams(vigo_params_s* Pp) const {
 // box of it to snapshot (setMapRegion), the same control-point count, gate step (maxVel_) and every parameter of fillParams() except the four weights, which
 // travel per trajectory.
 bool bsplineTraj::sameBatchKey(const bsplineTraj& o) const {
-    if (deviceOrdinal_ != o.deviceOrdinal_ || map_ != o.map_ || !sameRegion(mapRegion_, o.mapRegion_) || maxVel_ != o.maxVel_ || notCheckRatio_ != o.notCheckRatio_ ||
+    if (!link_.sameTarget(o.link_) || maxVel_ != o.maxVel_ || notCheckRatio_ != o.notCheckRatio_ ||
         optData_.controlPoints.cols() != o.optData_.controlPoints.cols())
         return false;
     vigo_params_t a, b;
@@ -200,28 +179,16 @@ bool bsplineTraj::sameBatchKey(const bsplineTraj& o) const {
     return std::memcmp(&a, &b, sizeof(a)) == 0;
 }
 
-// handle creation, parameter push and (re)snapshot of the map when it changed (mapAdapter)
+// handle creation, parameter push and (re)snapshot of the map when it changed (DeviceLink::sync); a planner without a map
+// still gets its handle and parameters
 bool bsplineTraj::syncDevice() {
-    // the planner's GPU is made current on the calling thread: its stream and staging buffers are per (thread, device)
-    if (hipSetDevice(deviceOrdinal_) != hipSuccess) {
-        cout << "[BsplineTraj]: HIP device " << deviceOrdinal_ << " is not available (there is no CPU fallback)." << endl;
-        return false;
-    }
-    if (!dev_) {
-        if (vigo_create(&dev_, deviceOrdinal_) != VIGO_OK) {
-            cout << "[BsplineTraj]: no HIP device for the ViGO back-end (there is no CPU fallback)." << endl;
-            dev_ = nullptr;
-            return false;
-        }
-    }
-    // launches and staging copies of this call go to the calling thread's stream (two host threads planning two
-    // batches then overlap on the device)
-    if (vigo_set_stream(dev_, vigo_host::threadStream()) != VIGO_OK) return false;
     vigo_params_t P;
     this->fillParams(&P);
-    if (vigo_set_params(dev_, &P) != VIGO_OK) return false;
-    if (map_ && !mapAdapter::uploadSnapshot(dev_, map_, mapRegion_, mapStamp_)) return false;
-    return true;
+    const DeviceLink::Sync r = link_.sync(false, &P);
+    if (r == DeviceLink::kNoDevice)
+        cout << "[BsplineTraj]: HIP device " << link_.ordinal() << " is not available (there is no CPU fallback)." << endl;
+    if (r == DeviceLink::kNoHandle) cout << "[BsplineTraj]: no HIP device for the ViGO back-end (there is no CPU fallback)." << endl;
+    return r == DeviceLink::kSynced;
 }
 
 // BT.cpp:207-245
@@ -293,10 +260,10 @@ bool bsplineTraj::prepareFitPointsWith(const nav_msgs::Path& adjustedPath, std::
     wrote = false;
     prevOut = prevIn;
     adjustedCurveFitPoints.clear();
-    if (adjustedPath.poses.empty() || !map_) return false;
+    if (adjustedPath.poses.empty() || !link_.map()) return false;
     Eigen::Vector3d goal(adjustedPath.poses.back().pose.position.x, adjustedPath.poses.back().pose.position.y,
                          adjustedPath.poses.back().pose.position.z);
-    if (this->map_->isInflatedOccupied(goal)) {
+    if (this->link_.map()->isInflatedOccupied(goal)) {
         cout << "[bsplineTraj]: Invalid goal position: " << goal(0) << " " << goal(1) << " " << goal(2) << endl;
         return false;
     }
@@ -387,8 +354,8 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
         }
         static thread_local StagingBuf dPts, dCond, dCtrl;
         if (!dPts.upload(pts.data(), pts.size() * 8) || !dCond.upload(cond.data(), cond.size() * 8) || !dCtrl.alloc(ctrl.size() * 8)) return;
-        if (vigo_bspline_fit(lead->dev_, B, K, ts, (const double*)dPts.p, (const double*)dCond.p, (double*)dCtrl.p) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_bspline_fit failed: " << vigo_last_error(lead->dev_) << endl;
+        if (vigo_bspline_fit(lead->link_.handle(), B, K, ts, (const double*)dPts.p, (const double*)dCond.p, (double*)dCtrl.p) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_bspline_fit failed: " << vigo_last_error(lead->link_.handle()) << endl;
             return;
         }
         if (!vigo_host::threadSync() || !dCtrl.download(ctrl.data(), ctrl.size() * 8)) return;
@@ -441,7 +408,7 @@ void bsplineTraj::findCollisionSeg(const Eigen::MatrixXd& controlPoints, std::ve
     int pairStartIdx = bsplineDegree, pairEndIdx = bsplineDegree;
     for (int i = bsplineDegree; i <= endIdx; ++i) {
         Eigen::Vector3d p = controlPoints.col(i);
-        bool hasCollision = this->map_->isInflatedOccupied(p);
+        bool hasCollision = this->link_.map()->isInflatedOccupied(p);
         if (hasCollision != previousHasCollision) {
             if (hasCollision) {
                 pairStartIdx = i - 1;
@@ -455,7 +422,7 @@ void bsplineTraj::findCollisionSeg(const Eigen::MatrixXd& controlPoints, std::ve
             collisionSeg.push_back({pairStartIdx, pairEndIdx});
         }
         if (i != bsplineDegree && !previousHasCollision && !hasCollision) {
-            if (this->map_->isInflatedOccupiedLine(controlPoints.col(i - 1), p)) collisionSeg.push_back({i - 1, i});
+            if (this->link_.map()->isInflatedOccupiedLine(controlPoints.col(i - 1), p)) collisionSeg.push_back({i - 1, i});
         }
         previousHasCollision = hasCollision;
     }
@@ -490,7 +457,7 @@ bool bsplineTraj::pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std
         std::pair<int, int> seg = collisionSeg[i];
         Eigen::Vector3d pStart = this->optData_.controlPoints.col(seg.first);
         Eigen::Vector3d pEnd = this->optData_.controlPoints.col(seg.second);
-        if (this->pathSearch_->AstarSearch(this->map_->getRes(), pStart, pEnd)) {
+        if (this->pathSearch_->AstarSearch(this->link_.map()->getRes(), pStart, pEnd)) {
             std::vector<Eigen::Vector3d> searchedPath = this->pathSearch_->getPath();
             searchedPath[0] = pStart;
             searchedPath.push_back(pEnd);
@@ -500,7 +467,7 @@ bool bsplineTraj::pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std
                 std::pair<int, int> nextSeg = collisionSeg[i + 1];
                 if (nextSeg.first - seg.second <= 2) {
                     Eigen::Vector3d pEnd2 = this->optData_.controlPoints.col(nextSeg.second);
-                    if (this->pathSearch_->AstarSearch(this->map_->getRes(), pStart, pEnd2)) {
+                    if (this->pathSearch_->AstarSearch(this->link_.map()->getRes(), pStart, pEnd2)) {
                         std::vector<Eigen::Vector3d> searchedPath = this->pathSearch_->getPath();
                         searchedPath[0] = pStart;
                         searchedPath.push_back(pEnd2);
@@ -521,9 +488,9 @@ bool bsplineTraj::pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std
 
 // BT.h:196-204
 bool bsplineTraj::checkCollisionLine(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2) {
-    for (double a = 0.0; a <= 1.0; a += this->map_->getRes()) {
+    for (double a = 0.0; a <= 1.0; a += this->link_.map()->getRes()) {
         Eigen::Vector3d pMid = a * p1 + (1 - a) * p2;
-        if (this->map_->isInflatedOccupied(pMid)) return true;
+        if (this->link_.map()->isInflatedOccupied(pMid)) return true;
     }
     return false;
 }
@@ -743,10 +710,10 @@ void bsplineTraj::solveBatch(const std::vector<bsplineTraj*>& ps) {
         }
         static thread_local StagingBuf dStatus;
         DeviceBatch d;
-        if (!uploadBatch(lead->dev_, hb, d) || !dStatus.alloc(hb.B * 4)) return;
-        if (vigo_optimize(lead->dev_, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr, (int32_t*)dStatus.p, nullptr,
+        if (!uploadBatch(lead->link_.handle(), hb, d) || !dStatus.alloc(hb.B * 4)) return;
+        if (vigo_optimize(lead->link_.handle(), hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr, (int32_t*)dStatus.p, nullptr,
                           nullptr, nullptr) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_optimize failed: " << vigo_last_error(lead->dev_) << endl;
+            cout << "[BsplineTraj]: vigo_optimize failed: " << vigo_last_error(lead->link_.handle()) << endl;
             return;
         }
         std::vector<int32_t> status(hb.B);
@@ -781,11 +748,11 @@ void bsplineTraj::gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uin
         if (!dCtrl.upload(ctrl.data(), ctrl.size() * 8) || !dFlag.alloc(B) || !dDyn.alloc(B) ||
             !dOoff.upload(ooff.data(), ooff.size() * 4) || !dObs.upload(obs.data(), obs.size() * 8))
             return;
-        const double dt = lead->map_->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
-        if (vigo_traj_collision(lead->dev_, B, N, (const double*)dCtrl.p, dt, (uint8_t*)dFlag.p, nullptr) != VIGO_OK) return;
+        const double dt = lead->link_.map()->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
+        if (vigo_traj_collision(lead->link_.handle(), B, N, (const double*)dCtrl.p, dt, (uint8_t*)dFlag.p, nullptr) != VIGO_OK) return;
         std::vector<uint8_t> f(B), d(B, 0);
         if (!obs.empty()) {
-            if (vigo_traj_dynamic_collision(lead->dev_, B, N, (const double*)dCtrl.p, dt, (const int32_t*)dOoff.p,
+            if (vigo_traj_dynamic_collision(lead->link_.handle(), B, N, (const double*)dCtrl.p, dt, (const int32_t*)dOoff.p,
                                             (const double*)dObs.p, 0, (uint8_t*)dDyn.p) != VIGO_OK)
                 return;
         }
@@ -836,9 +803,9 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
     }
     static thread_local StagingBuf dState;
     DeviceBatch d;
-    if (!uploadBatch(lead->dev_, hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t))) return false;
-    vigo_handle_t h = lead->dev_;
-    const double dt = lead->map_->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
+    if (!uploadBatch(lead->link_.handle(), hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t))) return false;
+    vigo_handle_t h = lead->link_.handle();
+    const double dt = lead->link_.map()->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
     if (vigo_rebound_rounds(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, dt, lead->notCheckRatio_, maxRounds,
                             (vigo_rebound_state_t*)dState.p) != VIGO_OK) {
         cout << "[BsplineTraj]: vigo_rebound_rounds failed: " << vigo_last_error(h) << endl;
@@ -896,7 +863,7 @@ double bsplineTraj::costFunction(const double* x, double* grad, const int n) {
     HostBatch hb(N);
     hb.add(optData_.controlPoints.data(), optData_, {weightDistance_, weightSmoothness_, weightFeasibility_, weightDynamicObstacle_});
     double cost = 0;
-    return costGrad(dev_, hb, cost, grad) ? cost : std::nan("");
+    return costGrad(link_.handle(), hb, cost, grad) ? cost : std::nan("");
 }
 
 // BT.cpp:796-800: the lbfgs_evaluate_t-shaped entry (instance pointer first)
@@ -917,7 +884,7 @@ bool bsplineTraj::termCost(int term, const Eigen::MatrixXd& controlPoints, doubl
     HostBatch hb(N);
     hb.add(controlPoints.data(), optData_, w);
     std::vector<double> g(3 * (N - 2 * bsplineDegree));
-    if (!costGrad(dev_, hb, cost, g.data())) return false;
+    if (!costGrad(link_.handle(), hb, cost, g.data())) return false;
     std::memcpy(gradient.data() + 3 * bsplineDegree, g.data(), g.size() * 8);
     return true;
 }
@@ -1213,7 +1180,7 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         };
         parallelFor(P, [&](size_t i) {
             bsplineTraj* p = planners[i];
-            if (!p->init_ || !p->map_ || !pb.hostSteps(p, !gathered)) return;
+            if (!p->init_ || !p->link_.map() || !pb.hostSteps(p, !gathered)) return;
             if (gathered) ready[i] = 1;
             else if (guides != 0) hasPaths[i] = 1;
             else assignGuides(i);
@@ -1237,7 +1204,7 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
     }
     for (size_t i = 0; i < P; ++i) {
         bsplineTraj* p = planners[i];
-        if (!p->init_ || !p->map_) continue;
+        if (!p->init_ || !p->link_.map()) continue;
         if (!prepared[i]) {
             cout << "[BsplineTraj]: Fail because of A* failure." << endl;
             continue;
@@ -1303,7 +1270,7 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
 #ifdef VIGO_WITH_ROS
                 // a search whose node pool (around the midpoint of its ends) is not inside the region stays with the host
                 const double mid[3] = {(jobs[j].s(0) + jobs[j].e(0)) / 2, (jobs[j].s(1) + jobs[j].e(1)) / 2, (jobs[j].s(2) + jobs[j].e(2)) / 2};
-                if (!boxInRegion(planners[owners[m]]->mapRegion_, mid, 1, g.half)) continue;
+                if (!boxInRegion(planners[owners[m]]->link_.region(), mid, 1, g.half)) continue;
 #endif
                 idx.push_back(j);
                 for (int k = 0; k < 3; ++k) { se[0].push_back(jobs[j].s(k)); se[1].push_back(jobs[j].e(k)); }
@@ -1314,10 +1281,10 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
         if (!dS.upload(se[0].data(), se[0].size() * 8) || !dE.upload(se[1].data(), se[1].size() * 8) || !dStatus.alloc((size_t)Q * 4) ||
             !dLen.alloc((size_t)Q * 4) || !dPath.alloc((size_t)Q * kAstarPathCap * 24))
             return;
-        if (vigo_astar_search(lead->dev_, Q, (const double*)dS.p, (const double*)dE.p, g.res, g.pool, lead->minHeight_, lead->maxHeight_,
+        if (vigo_astar_search(lead->link_.handle(), Q, (const double*)dS.p, (const double*)dE.p, g.res, g.pool, lead->minHeight_, lead->maxHeight_,
                               g_deviceAstarBudget.load(), kAstarPathCap, (int32_t*)dStatus.p, (int32_t*)dLen.p, (double*)dPath.p,
                               nullptr) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_astar_search failed: " << vigo_last_error(lead->dev_) << endl;
+            cout << "[BsplineTraj]: vigo_astar_search failed: " << vigo_last_error(lead->link_.handle()) << endl;
             return;
         }
         std::vector<int32_t> status(Q), len(Q);
@@ -1347,7 +1314,7 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
         for (size_t j : jobsOf[owners[o]]) {
             if (decided[j]) continue;
             AstarJob& J = jobs[j];
-            J.ok = p->pathSearch_->AstarSearch(p->map_->getRes(), J.s, J.e);
+            J.ok = p->pathSearch_->AstarSearch(p->link_.map()->getRes(), J.s, J.e);
             if (J.ok) J.path = p->pathSearch_->getPath();
         }
     });
@@ -1464,7 +1431,7 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
     std::vector<uint8_t> failedOnDevice(P, 0);        // the device's walk failed: the host's replay leaves the lists
     std::vector<size_t> owners;
     for (size_t i = 0; i < P; ++i)
-        if (planners[i]->init_ && planners[i]->map_) owners.push_back(i);
+        if (planners[i]->init_ && planners[i]->link_.map()) owners.push_back(i);
     auto same = [&](size_t a, size_t b) { return SearchGroup::same(*planners[owners[a]], *planners[owners[b]]); };
     const double tc0 = wallSeconds();
     vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
@@ -1481,7 +1448,7 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             // Every search's node pool (around the midpoint of two control points) and with it every path point lies in
             // the control points' box grown by the pool's reach: a planner whose grown box is not inside the region
             // keeps to its own map.
-            if (!boxInRegion(p->mapRegion_, p->optData_.controlPoints.data(), N, g.half)) continue;
+            if (!boxInRegion(p->link_.region(), p->optData_.controlPoints.data(), N, g.half)) continue;
 #endif
             vigo_host::appendCtrl(p->optData_.controlPoints, ctrl);
             who.push_back(owners[m]);
@@ -1495,13 +1462,13 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             !dSeg.alloc((size_t)segCap * 8) || !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) ||
             !dCounts.alloc((size_t)B * 8) || !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)pairCap * 48) || !dGStatus.alloc((size_t)B * 4))
             return;
-        if (vigo_path_search(lead->dev_, B, N, (const double*)dCtrl.p, nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
+        if (vigo_path_search(lead->link_.handle(), B, N, (const double*)dCtrl.p, nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
                              lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, segCap, pointCap, (int32_t*)dStatus.p,
                              (int32_t*)dSegOff.p, (int32_t*)dSeg.p, (int32_t*)dPathOff.p, (double*)dPath.p, (int32_t*)dCounts.p) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_path_search failed: " << vigo_last_error(lead->dev_) << endl;
+            cout << "[BsplineTraj]: vigo_path_search failed: " << vigo_last_error(lead->link_.handle()) << endl;
             return;
         }
-        const bool guided = vigo_guide_assign(lead->dev_, B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
+        const bool guided = vigo_guide_assign(lead->link_.handle(), B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
                                               (const int32_t*)dPathOff.p, (const double*)dPath.p, pairCap, (int32_t*)dOff.p, (double*)dPv.p,
                                               nullptr, (int32_t*)dGStatus.p) == VIGO_OK;   // (not: the pairs do not fit — the twin assigns them)
         std::vector<int32_t> status(B), segOff(B + 1), counts((size_t)B * 2), off((size_t)B * N + 1, 0), gstatus(B, VIGO_GUIDE_DEFERRED);
@@ -1585,9 +1552,9 @@ void bsplineTraj::assignGuidesCoreOn(const std::vector<std::pair<int, int>>& col
         longest = std::max(longest, (size_t)(pathOff[k + 1] - pathOff[k]));
     }
     std::vector<vigo::G3> sc(longest);
-    auto* map = this->map_.get();
+    auto* map = link_.map().get();
     auto occ = [map](double x, double y, double z) { return map->isInflatedOccupied(Eigen::Vector3d(x, y, z)); };
-    vigo::guide_assign(occ, vigo::GuideAtan2{}, this->map_->getRes(), N, ctrl.data(), (int)(seg.size() / 2), seg.data(), pathOff.data(),
+    vigo::guide_assign(occ, vigo::GuideAtan2{}, this->link_.map()->getRes(), N, ctrl.data(), (int)(seg.size() / 2), seg.data(), pathOff.data(),
                        path.data(), sc.data(), [this](int idx, const vigo::G3& p, const vigo::G3& d, const int32_t*) {
                            this->optData_.guidePoints[idx].push_back(Eigen::Vector3d(p.v[0], p.v[1], p.v[2]));
                            this->optData_.guideDirections[idx].push_back(Eigen::Vector3d(d.v[0], d.v[1], d.v[2]));
@@ -1627,7 +1594,7 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
                 // keeps to its own map (the twin), and what was packed of it is taken back
                 const size_t pt0 = (size_t)pathOff[seg0];
                 const double none[3] = {0.0, 0.0, 0.0};
-                if (!boxInRegion(p->mapRegion_, path.data() + pt0 * 3, path.size() / 3 - pt0, none)) {
+                if (!boxInRegion(p->link_.region(), path.data() + pt0 * 3, path.size() / 3 - pt0, none)) {
                     seg.resize(seg0 * 2);
                     path.resize(pt0 * 3);
                     pathOff.resize(seg0 + 1);
@@ -1652,10 +1619,10 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
                 !dPath.upload(path.data(), path.size() * 8) || !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)cap * 48) ||
                 !dStatus.alloc((size_t)B * 4))
                 return;
-            if (vigo_guide_assign(lead->dev_, B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
+            if (vigo_guide_assign(lead->link_.handle(), B, N, (const double*)dCtrl.p, (const int32_t*)dSegOff.p, (const int32_t*)dSeg.p,
                                   (const int32_t*)dPathOff.p, (const double*)dPath.p, cap, (int32_t*)dOff.p, (double*)dPv.p, nullptr,
                                   (int32_t*)dStatus.p) != VIGO_OK) {
-                cout << "[BsplineTraj]: vigo_guide_assign failed: " << vigo_last_error(lead->dev_) << endl;
+                cout << "[BsplineTraj]: vigo_guide_assign failed: " << vigo_last_error(lead->link_.handle()) << endl;
                 return;
             }
             std::vector<int32_t> off((size_t)B * N + 1), status(B);
@@ -1749,7 +1716,7 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
 #ifdef VIGO_WITH_ROS
             // as in prologueOnDevice: a planner whose control points' box, grown by the node pool's reach, is not inside
             // the region keeps to its own map
-            if (!boxInRegion(p->mapRegion_, p->optData_.controlPoints.data(), N, g.half)) continue;
+            if (!boxInRegion(p->link_.region(), p->optData_.controlPoints.data(), N, g.half)) continue;
 #endif
             const Rebound& r = pb.rb[pb.activeIdx[a]];
             hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
@@ -1771,16 +1738,16 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
                         pairCap = (long long)hb.guides() + (long long)B * N * 4;
         static thread_local StagingBuf dState, dOff, dPv, dPathSegOff, dPathOff, dPath, dStatus;
         DeviceBatch d;
-        if (!uploadBatch(lead->dev_, hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t)) ||
+        if (!uploadBatch(lead->link_.handle(), hb, d) || !dState.upload(state.data(), state.size() * sizeof(vigo_rebound_state_t)) ||
             !dOff.alloc(((size_t)B * N + 1) * 4) || !dPv.alloc((size_t)pairCap * 48) || !dPathSegOff.alloc(((size_t)B + 1) * 4) ||
             !dPathOff.alloc(((size_t)segCap + 1) * 4) || !dPath.alloc((size_t)pointCap * 24) || !dStatus.alloc((size_t)B * 4))
             return;
-        if (vigo_rebound_reguide(lead->dev_, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
+        if (vigo_rebound_reguide(lead->link_.handle(), B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
                                  lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
                                  lead->maxHeight_, g_deviceAstarBudget.load(), kAstarPathCap, (vigo_rebound_state_t*)dState.p, pairCap,
                                  (int32_t*)dOff.p, (double*)dPv.p, nullptr, segCap, pointCap, (int32_t*)dPathSegOff.p, (int32_t*)dPathOff.p,
                                  (double*)dPath.p, (int32_t*)dStatus.p) != VIGO_OK) {
-            cout << "[BsplineTraj]: vigo_rebound_reguide failed: " << vigo_last_error(lead->dev_) << endl;
+            cout << "[BsplineTraj]: vigo_rebound_reguide failed: " << vigo_last_error(lead->link_.handle()) << endl;
             return;
         }
         std::vector<int32_t> status(B), off((size_t)B * N + 1), pathSegOff(B + 1);
@@ -1966,14 +1933,14 @@ void bsplineTraj::adjustPathLengthWith(const std::vector<Eigen::Vector3d>& path,
         if (totalLength >= std::max(prevPathLength, this->maxPathLength_)) exceedLength = true;
         adjustedPath.push_back(p1);
         if (exceedLength) {
-            bool free = !this->map_->isInflatedOccupiedLine(p1, p2);
+            bool free = !this->link_.map()->isInflatedOccupiedLine(p1, p2);
             if (free && minLength >= 1.5) {
                 adjustedPath.push_back(p2);
                 prevOut = totalLength;
                 return;
             }
         }
-        if (this->map_->isInflatedOccupiedLine(p1, p2)) minLength = 0.0;
+        if (this->link_.map()->isInflatedOccupiedLine(p1, p2)) minLength = 0.0;
         else minLength += (p2 - p1).norm();
     }
     adjustedPath.push_back(path.back());
@@ -2022,7 +1989,7 @@ double bsplineTraj::getDuration() { return this->bspline_.getDuration(); }
 double bsplineTraj::getTimestep() { return this->ts_; }
 Eigen::MatrixXd bsplineTraj::getControlPoints() { return this->optData_.controlPoints; }
 
-std::vector<Eigen::Vector3d> bsplineTraj::evalTraj() { return this->evalTraj(this->map_->getRes() / this->maxVel_ / 2.0); }
+std::vector<Eigen::Vector3d> bsplineTraj::evalTraj() { return this->evalTraj(this->link_.map()->getRes() / this->maxVel_ / 2.0); }
 
 std::vector<Eigen::Vector3d> bsplineTraj::evalTraj(double dt) {
     std::vector<Eigen::Vector3d> traj;
@@ -2041,7 +2008,7 @@ bool bsplineTraj::isCurrTrajValid(Eigen::Vector3d& firstCollisionPos) {
     if (!this->init_) return false;
     std::vector<Eigen::Vector3d> trajectory = this->evalTraj();
     for (int i = 0; i < (1.0 - this->notCheckRatio_) * int(trajectory.size()); ++i) {
-        if (this->map_->isInflatedOccupied(trajectory[i])) {
+        if (this->link_.map()->isInflatedOccupied(trajectory[i])) {
             firstCollisionPos = trajectory[i];
             return false;
         }

@@ -59,6 +59,79 @@ nav_msgs::Path pathFromXyz(const double* q, int n_pts) {
     return path;
 }
 
+// cfg as vigo_host_poly_plan documents it; `mode`, the differential and the continuity degree are the caller's
+std::unique_ptr<trajPlanner::polyTrajOctomap> makePolyPlanner(const std::shared_ptr<mapManager::occMap>& map, const double* cfg,
+                                                               double mode, int diff, int cont, const std::vector<trajPlanner::pose>& path) {
+    static const char* keys[7] = {"map_resolution", "sample_delta_time", "desired_velocity", "initial_radius", "shrinking_factor",
+                                  "corridor_res", "maximum_iteration_num"};
+    ros::NodeHandle nh;
+    nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
+    for (int k = 0; k < 7; ++k) nh.setParam(keys[k], cfg[3 + k]);
+    nh.setParam("traj_timeout", cfg[10]);
+    nh.setParam("mode", mode);
+    nh.setParam("polynomial_degree", 7.0);
+    nh.setParam("differential_degree", (double)diff);
+    nh.setParam("continuity_degree", (double)cont);
+    std::unique_ptr<trajPlanner::polyTrajOctomap> p(new trajPlanner::polyTrajOctomap(nh));
+    p->setMap(map);
+    p->updatePath(path);
+    return p;
+}
+
+std::vector<trajPlanner::pose> posesFromXyz(const double* q, int n) {
+    std::vector<trajPlanner::pose> path;
+    for (int i = 0; i < n; ++i) path.push_back(trajPlanner::pose(q[3 * i], q[3 * i + 1], q[3 * i + 2]));
+    return path;
+}
+
+// the first `cap` positions as xyz triples
+void copyXyz(const std::vector<trajPlanner::pose>& traj, int cap, double* out) {
+    const int n = (int)traj.size() < cap ? (int)traj.size() : cap;
+    for (int k = 0; k < n; ++k) { out[3 * k] = traj[k].x; out[3 * k + 1] = traj[k].y; out[3 * k + 2] = traj[k].z; }
+}
+void copyXyz(const nav_msgs::Path& path, int cap, double* out) {
+    const int n = (int)path.poses.size() < cap ? (int)path.poses.size() : cap;
+    for (int k = 0; k < n; ++k) {
+        const geometry_msgs::Point& q = path.poses[k].pose.position;
+        out[3 * k] = q.x; out[3 * k + 1] = q.y; out[3 * k + 2] = q.z;
+    }
+}
+
+double secondsSince(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The two makePlanBatch test entries of the min-snap planners: P planners from make(i), warm(planner) outside the timed
+// region (the handle-creating device call, where the class has one), ONE timed batch(planners, trajectories, verdicts),
+// report(planner, verdict, trajectory, i, false); then, when the caller wants them, P twins planned alone — each made,
+// warmed, timed alone by solo(planner, trajectory) and reported with `true`.  secs_out[2] (may be NULL): seconds of the
+// batch, of the P solo plans.
+template <class Make, class Warm, class Batch, class Solo, class Report>
+void batchThenSoloTwins(int P, bool twins, double* secs_out, Make make, Warm warm, Batch batch, Solo solo, Report report) {
+    std::vector<decltype(make(0))> own;
+    std::vector<decltype(make(0).get())> ps;
+    for (int i = 0; i < P; ++i) { own.push_back(make(i)); ps.push_back(own.back().get()); }
+    if (P > 0) warm(*ps[0]);
+    std::vector<std::vector<trajPlanner::pose>> trajs;
+    std::vector<bool> r;
+    auto t0 = std::chrono::steady_clock::now();
+    batch(ps, trajs, r);
+    if (secs_out) secs_out[0] = secondsSince(t0);
+    for (int i = 0; i < P; ++i) report(*ps[i], (bool)r[i], trajs[i], i, false);
+    if (!twins) return;
+    double solo_secs = 0.0;
+    for (int i = 0; i < P; ++i) {
+        auto p = make(i);
+        std::vector<trajPlanner::pose> traj;
+        warm(*p);
+        t0 = std::chrono::steady_clock::now();
+        const bool ri = solo(*p, traj);
+        solo_secs += secondsSince(t0);
+        report(*p, ri, traj, i, true);
+    }
+    if (secs_out) secs_out[1] = solo_secs;
+}
+
 // a dense byte grid as the kernels' twins read it (standin/dense_occmap.h byteAt): posToIndex is floor((p - origin) / res),
 // the range test is made on the double, outside is 0xFF (occupied and unknown).  Called, it is the point predicate the
 // core headers take.
@@ -395,32 +468,14 @@ int vigo_host_minsnap_eval(int n_wp, const double* wp, int deg, int diff, int co
 // seconds of makePlan.  Needs the GPU (the box sweep of every sample runs there); -1 on failure.
 int vigo_host_poly_plan(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int n_wp,
                         const double* wp, const double* cfg, double* traj_out, int traj_cap, double* info_out) {
-    auto map = denseMap(nx, ny, nz, origin, res, voxels);
-    ros::NodeHandle nh;
-    nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
-    nh.setParam("map_resolution", cfg[3]);
-    nh.setParam("sample_delta_time", cfg[4]);
-    nh.setParam("desired_velocity", cfg[5]);
-    nh.setParam("initial_radius", cfg[6]);
-    nh.setParam("shrinking_factor", cfg[7]);
-    nh.setParam("corridor_res", cfg[8]);
-    nh.setParam("maximum_iteration_num", cfg[9]);
-    nh.setParam("traj_timeout", cfg[10]);
-    nh.setParam("mode", cfg[11]);
-    nh.setParam("polynomial_degree", 7.0);
-    nh.setParam("differential_degree", 4.0);
-    nh.setParam("continuity_degree", 4.0);
-    trajPlanner::polyTrajOctomap planner(nh);
-    planner.setMap(map);
-    std::vector<trajPlanner::pose> path, traj;
-    for (int i = 0; i < n_wp; ++i) path.push_back(trajPlanner::pose(wp[3 * i], wp[3 * i + 1], wp[3 * i + 2]));
-    if (planner.checkCollision(path.front())) { /* first device call: creates the handle, snapshots the map */ }
-    planner.updatePath(path);
+    auto p = makePolyPlanner(denseMap(nx, ny, nz, origin, res, voxels), cfg, cfg[11], 4, 4, posesFromXyz(wp, n_wp));
+    trajPlanner::polyTrajOctomap& planner = *p;
+    std::vector<trajPlanner::pose> traj;
+    if (planner.checkCollision(planner.getPath().front())) { /* first device call: creates the handle, snapshots the map */ }
     const auto t0 = std::chrono::steady_clock::now();
     planner.makePlan(traj, cfg[4]);
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const int n = (int)traj.size() < traj_cap ? (int)traj.size() : traj_cap;
-    for (int i = 0; i < n; ++i) { traj_out[3 * i] = traj[i].x; traj_out[3 * i + 1] = traj[i].y; traj_out[3 * i + 2] = traj[i].z; }
+    const double secs = secondsSince(t0);
+    copyXyz(traj, traj_cap, traj_out);
     info_out[0] = planner.isValid() ? 1.0 : 0.0;
     info_out[1] = planner.getIterations();
     info_out[2] = (double)traj.size();
@@ -440,61 +495,24 @@ int vigo_host_poly_plan_batch_ex(int nx, int ny, int nz, const double* origin, d
                                  int traj_cap, double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out,
                                  double* secs_out) {
     if (P < 0 || !wp_off || !wp || !cfg || !mode || traj_cap < 0 || !traj_out || !info_out) return -1;
+    typedef trajPlanner::polyTrajOctomap Planner;
     auto map = denseMap(nx, ny, nz, origin, res, voxels);
-    auto make = [&](int i) {
-        ros::NodeHandle nh;
-        nh.setParam("collision_box", std::vector<double>{cfg[0], cfg[1], cfg[2]});
-        nh.setParam("map_resolution", cfg[3]);
-        nh.setParam("sample_delta_time", cfg[4]);
-        nh.setParam("desired_velocity", cfg[5]);
-        nh.setParam("initial_radius", cfg[6]);
-        nh.setParam("shrinking_factor", cfg[7]);
-        nh.setParam("corridor_res", cfg[8]);
-        nh.setParam("maximum_iteration_num", cfg[9]);
-        nh.setParam("traj_timeout", cfg[10]);
-        nh.setParam("mode", (double)mode[i]);
-        nh.setParam("polynomial_degree", 7.0);
-        nh.setParam("differential_degree", (double)diff);
-        nh.setParam("continuity_degree", (double)cont);
-        std::unique_ptr<trajPlanner::polyTrajOctomap> p(new trajPlanner::polyTrajOctomap(nh));
-        p->setMap(map);
-        std::vector<trajPlanner::pose> path;
-        for (int k = wp_off[i]; k < wp_off[i + 1]; ++k) path.push_back(trajPlanner::pose(wp[3 * k], wp[3 * k + 1], wp[3 * k + 2]));
-        p->updatePath(path);
-        return p;
-    };
-    auto report = [&](trajPlanner::polyTrajOctomap& p, const std::vector<trajPlanner::pose>& traj, int i, double* tr, double* info) {
-        const int n = (int)traj.size() < traj_cap ? (int)traj.size() : traj_cap;
-        for (int k = 0; k < n; ++k) {
-            double* o = tr + ((size_t)i * traj_cap + k) * 3;
-            o[0] = traj[k].x; o[1] = traj[k].y; o[2] = traj[k].z;
-        }
-        info[4 * i] = p.isValid() ? 1.0 : 0.0;
-        info[4 * i + 1] = p.getIterations();
-        info[4 * i + 2] = (double)p.getPath().size();
-        info[4 * i + 3] = (double)traj.size();
-    };
-    std::vector<std::unique_ptr<trajPlanner::polyTrajOctomap>> own;
-    std::vector<trajPlanner::polyTrajOctomap*> ps;
-    for (int i = 0; i < P; ++i) { own.push_back(make(i)); ps.push_back(own.back().get()); }
-    if (P > 0 && ps[0]->checkCollision(ps[0]->getPath().front())) { /* first device call: handle and map snapshot */ }
-    std::vector<std::vector<trajPlanner::pose>> trajs;
-    auto t0 = std::chrono::steady_clock::now();
-    trajPlanner::polyTrajOctomap::makePlanBatch(ps, trajs);
-    if (secs_out) secs_out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < P; ++i) report(*ps[i], trajs[i], i, traj_out, info_out);
-    if (!solo_traj_out || !solo_info_out) return 0;
-    double solo_secs = 0.0;
-    for (int i = 0; i < P; ++i) {
-        auto p = make(i);
-        std::vector<trajPlanner::pose> traj;
-        if (p->checkCollision(p->getPath().front())) { /* handle and snapshot outside the timed call */ }
-        t0 = std::chrono::steady_clock::now();
-        p->makePlan(traj, cfg[4]);
-        solo_secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        report(*p, traj, i, solo_traj_out, solo_info_out);
-    }
-    if (secs_out) secs_out[1] = solo_secs;
+    batchThenSoloTwins(
+        P, solo_traj_out && solo_info_out, secs_out,
+        [&](int i) { return makePolyPlanner(map, cfg, (double)mode[i], diff, cont, posesFromXyz(wp + 3 * (size_t)wp_off[i], wp_off[i + 1] - wp_off[i])); },
+        [](Planner& p) { if (p.checkCollision(p.getPath().front())) { /* first device call: handle and map snapshot */ } },
+        [](const std::vector<Planner*>& ps, std::vector<std::vector<trajPlanner::pose>>& trajs, std::vector<bool>& r) {
+            r = Planner::makePlanBatch(ps, trajs);
+        },
+        [&](Planner& p, std::vector<trajPlanner::pose>& traj) { p.makePlan(traj, cfg[4]); return p.isValid(); },
+        [&](Planner& p, bool, const std::vector<trajPlanner::pose>& traj, int i, bool solo) {
+            double* info = (solo ? solo_info_out : info_out) + 4 * (size_t)i;
+            copyXyz(traj, traj_cap, (solo ? solo_traj_out : traj_out) + (size_t)i * traj_cap * 3);
+            info[0] = p.isValid() ? 1.0 : 0.0;
+            info[1] = p.getIterations();
+            info[2] = (double)p.getPath().size();
+            info[3] = (double)traj.size();
+        });
     return 0;
 }
 
@@ -536,11 +554,6 @@ static std::unique_ptr<trajPlanner::polyTrajOccMap> makeOccPlanner(const std::sh
     return p;
 }
 
-static void copyXyz(const std::vector<trajPlanner::pose>& traj, int cap, double* out) {
-    const int n = (int)traj.size() < cap ? (int)traj.size() : cap;
-    for (int k = 0; k < n; ++k) { out[3 * k] = traj[k].x; out[3 * k + 1] = traj[k].y; out[3 * k + 2] = traj[k].z; }
-}
-
 // One polyTrajOccMap on a dense byte grid, planned alone on the host (no GPU).  mode 1: makePlan(trajectory, true),
 // 0: makePlan(trajectory, false), 2: makePlan(trajectory) (no bool).  traj_out: the first traj_cap samples (xyz);
 // gt_dt > 0: getTrajectory(gt_dt) afterwards into gt_out (first traj_cap poses).  info_out[8]: makePlan's result,
@@ -563,10 +576,7 @@ int vigo_host_occ_plan(int nx, int ny, int nz, const double* origin, double res,
     if (gt_dt > 0 && gt_out) {
         const nav_msgs::Path g = p->getTrajectory(gt_dt);
         info_out[5] = (double)g.poses.size();
-        const int n = (int)g.poses.size() < traj_cap ? (int)g.poses.size() : traj_cap;
-        for (int k = 0; k < n; ++k) {
-            gt_out[3 * k] = g.poses[k].pose.position.x; gt_out[3 * k + 1] = g.poses[k].pose.position.y; gt_out[3 * k + 2] = g.poses[k].pose.position.z;
-        }
+        copyXyz(g, traj_cap, gt_out);
     }
     const Eigen::Vector3d e = p->getPos(p->getDuration());
     info_out[6] = e(0);
@@ -583,38 +593,28 @@ int vigo_host_occ_plan_batch(int nx, int ny, int nz, const double* origin, doubl
                              int traj_cap, double* traj_out, double* info_out, double* solo_traj_out, double* solo_info_out,
                              double* secs_out) {
     if (P < 0 || !wp_off || !wp || !cfg || traj_cap < 0 || !traj_out || !info_out) return -1;
+    typedef trajPlanner::polyTrajOccMap Planner;
     auto map = denseMap(nx, ny, nz, origin, res, voxels);
-    auto make = [&](int i) {
-        return makeOccPlanner(map, cfg + 16 * (size_t)i, wp_off[i + 1] - wp_off[i], wp + 3 * (size_t)wp_off[i],
-                              conds ? conds + 12 * (size_t)i : nullptr);
-    };
-    auto report = [&](trajPlanner::polyTrajOccMap& p, bool r, const std::vector<trajPlanner::pose>& traj, int i, double* tr, double* info) {
-        copyXyz(traj, traj_cap, tr + (size_t)i * traj_cap * 3);
-        info[5 * i] = r ? 1.0 : 0.0;
-        info[5 * i + 1] = p.getIterations();
-        info[5 * i + 2] = (double)traj.size();
-        info[5 * i + 3] = p.getDuration();
-        info[5 * i + 4] = p.getPos(p.getDuration())(0);
-    };
-    std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> own;
-    std::vector<trajPlanner::polyTrajOccMap*> ps;
-    for (int i = 0; i < P; ++i) { own.push_back(make(i)); ps.push_back(own.back().get()); }
-    std::vector<std::vector<trajPlanner::pose>> trajs;
-    auto t0 = std::chrono::steady_clock::now();
-    const std::vector<bool> r = trajPlanner::polyTrajOccMap::makePlanBatch(ps, corridor != 0, &trajs);
-    if (secs_out) secs_out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < P; ++i) report(*ps[i], r[i], trajs[i], i, traj_out, info_out);
-    if (!solo_traj_out || !solo_info_out) return 0;
-    double solo_secs = 0.0;
-    for (int i = 0; i < P; ++i) {
-        auto p = make(i);
-        std::vector<trajPlanner::pose> traj;
-        t0 = std::chrono::steady_clock::now();
-        const bool ri = p->makePlan(traj, corridor != 0);
-        solo_secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        report(*p, ri, traj, i, solo_traj_out, solo_info_out);
-    }
-    if (secs_out) secs_out[1] = solo_secs;
+    batchThenSoloTwins(
+        P, solo_traj_out && solo_info_out, secs_out,
+        [&](int i) {
+            return makeOccPlanner(map, cfg + 16 * (size_t)i, wp_off[i + 1] - wp_off[i], wp + 3 * (size_t)wp_off[i],
+                                  conds ? conds + 12 * (size_t)i : nullptr);
+        },
+        [](Planner&) { /* the solo plan runs on the host, and the batch's handle is made inside its timed call */ },
+        [&](const std::vector<Planner*>& ps, std::vector<std::vector<trajPlanner::pose>>& trajs, std::vector<bool>& r) {
+            r = Planner::makePlanBatch(ps, corridor != 0, &trajs);
+        },
+        [&](Planner& p, std::vector<trajPlanner::pose>& traj) { return p.makePlan(traj, corridor != 0); },
+        [&](Planner& p, bool r, const std::vector<trajPlanner::pose>& traj, int i, bool solo) {
+            double* info = (solo ? solo_info_out : info_out) + 5 * (size_t)i;
+            copyXyz(traj, traj_cap, (solo ? solo_traj_out : traj_out) + (size_t)i * traj_cap * 3);
+            info[0] = r ? 1.0 : 0.0;
+            info[1] = p.getIterations();
+            info[2] = (double)traj.size();
+            info[3] = p.getDuration();
+            info[4] = p.getPos(p.getDuration())(0);
+        });
     return 0;
 }
 
@@ -668,11 +668,7 @@ int vigo_host_occ_seed_chain(int nx, int ny, int nz, const double* origin, doubl
         }
         seed_dt[i] = dt;
         seed_n[i] = (int32_t)seeds[i].poses.size();
-        const int n = seed_n[i] < seed_cap ? seed_n[i] : seed_cap;
-        for (int k = 0; k < n; ++k) {
-            double* o = seed_out + ((size_t)i * seed_cap + k) * 3;
-            o[0] = seeds[i].poses[k].pose.position.x; o[1] = seeds[i].poses[k].pose.position.y; o[2] = seeds[i].poses[k].pose.position.z;
-        }
+        copyXyz(seeds[i], seed_cap, seed_out + (size_t)i * seed_cap * 3);
     }
     std::vector<bool> up(P), planned(P, false);
     if (solo) {

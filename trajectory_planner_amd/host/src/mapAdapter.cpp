@@ -2,6 +2,8 @@
 // fast path exists only in builds with this tree's stand-in map (no VIGO_WITH_ROS).
 #include <trajectory_planner/mapAdapter.h>
 
+#include <hip/hip_runtime_api.h>
+
 #include <cmath>
 #include <iostream>
 #include <map>
@@ -9,6 +11,7 @@
 #include <vector>
 
 #include "../../../include/vigo.h"
+#include "devbuf.h"
 
 namespace trajPlanner {
 
@@ -106,6 +109,47 @@ unsigned mapAdapter::nodeBits(const std::shared_ptr<mapManager::occMap>& map, co
     if (map->isInflatedOccupied(p)) v |= kOccupied;
     return v;
 #endif
+}
+
+DeviceLink::~DeviceLink() {
+    if (dev_) vigo_destroy(dev_);
+}
+
+void DeviceLink::setMap(const std::shared_ptr<mapManager::occMap>& map) {
+    map_ = map;
+    stamp_ = 0;
+}
+
+void DeviceLink::setRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) {
+    region_.set = true;
+    region_.boxMin = boxMin;
+    region_.boxMax = boxMax;
+    stamp_ = 0;
+}
+
+void DeviceLink::refresh() {
+    mapAdapter::bumpGeneration(map_.get());
+    stamp_ = 0;
+}
+
+void DeviceLink::setDevice(int ordinal) {
+    if (ordinal == ordinal_) return;
+    if (dev_) { vigo_destroy(dev_); dev_ = nullptr; }
+    stamp_ = 0;
+    ordinal_ = ordinal;
+}
+
+DeviceLink::Sync DeviceLink::sync(bool needMap, const vigo_params_s* params) {
+    if (needMap && !map_) return kNoMap;
+    if (hipSetDevice(ordinal_) != hipSuccess) return kNoDevice;
+    if (!dev_ && vigo_create(&dev_, ordinal_) != VIGO_OK) {
+        dev_ = nullptr;
+        return kNoHandle;
+    }
+    if (vigo_set_stream(dev_, vigo_host::threadStream()) != VIGO_OK) return kFailed;
+    if (params && vigo_set_params(dev_, params) != VIGO_OK) return kFailed;
+    if (map_ && !mapAdapter::uploadSnapshot(dev_, map_, region_, stamp_)) return kFailed;
+    return kSynced;
 }
 
 }  // namespace trajPlanner

@@ -1,64 +1,15 @@
-// polyBatch.h — internal to the host facades: what both min-snap planners (polyTrajOctomap, polyTrajOccMap) share.  The two
-// device steps of a makePlanBatch round (the QP of one group, the whole-trajectory check of every candidate) live here with
-// their staging buffers: the layout of those C ABI entries is known in ONE place; the lock-step loops stay in each class.
+// polyBatch.h — internal to the host facades: the two device steps of a makePlanBatch round of both min-snap planners
+// (polyTrajOctomap, polyTrajOccMap) — the QP of one group, the whole-trajectory check of every candidate — with their
+// staging buffers: the layout of those C ABI entries is known in ONE place.  The lock-step loop that drives them, and the
+// structs they fill, are polyBatchLoop.h's; each class's DeviceSteps binds its own entry point to them.
 #ifndef VIGO_HOST_POLY_BATCH_H
 #define VIGO_HOST_POLY_BATCH_H
-#include <trajectory_planner/polyTrajSolver.h>
-
-#include <chrono>
-#include <cstdint>
-#include <set>
-#include <vector>
-
-#include "../../../include/vigo.h"
 #include "devbuf.h"
+#include "polyBatchLoop.h"
 
 namespace vigo_host {
 
-inline double nowSec() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-inline void appendXyz(const std::vector<trajPlanner::pose>& pts, std::vector<double>& xyz) {
-    for (const trajPlanner::pose& q : pts) { xyz.push_back(q.x); xyz.push_back(q.y); xyz.push_back(q.z); }
-}
-
-// both planners' trajMsgConverter (PO.cpp:597-617, PM.cpp:554-571)
-inline void posesToPathMsg(const std::vector<trajPlanner::pose>& poses, nav_msgs::Path& msg) {
-    msg.poses.clear();
-    for (const trajPlanner::pose& p : poses) {
-        geometry_msgs::PoseStamped ps;
-        ps.header.frame_id = "map";
-        ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
-        ps.pose.orientation = trajPlanner::quaternion_from_rpy(0, 0, p.yaw);
-        msg.poses.push_back(ps);
-    }
-    msg.header.frame_id = "map";
-}
-
-// checkCollisionTraj(trajectory, delT, collisionSeg) of both planners (PO.cpp:634-656, PM.cpp:524-546) on per-sample flags:
-// t accumulates delT per sample; a colliding sample blames the first time-knot interval containing t (inclusive)
-inline bool collisionSegments(const uint8_t* flags, size_t n, const std::vector<double>& knots, double delT, std::set<int>& collisionSeg) {
-    double t = 0;
-    bool has = false;
-    for (size_t k = 0; k < n; ++k) {
-        if (flags[k]) {
-            has = true;
-            for (size_t i = 0; i + 1 < knots.size(); ++i)
-                if (t >= knots[i] && t <= knots[i + 1]) { collisionSeg.insert((int)i); break; }
-        }
-        t += delT;
-    }
-    return has;
-}
-
 // ---- the device QP of one group: T paths of the same waypoint count W, degree 7, in ONE vigo_minsnap launch ----
-struct QpMember {
-    const std::vector<trajPlanner::pose>* path;
-    const std::vector<double>* corridor;    // in: radius per segment; nullptr (for the whole group): no corridor boxes
-    const geometry_msgs::Twist* conds[4];   // in: start / end vel, start / end acc; nullptr (whole group): none passed, not zeros
-    int32_t status;                         // out: 0 solved, -1 numerical failure, -2 infeasible corridor
-    std::vector<double> sol[3];             // out: the solution per axis, as polyTrajSolver::installSolution takes it
-};
-
 // false on a failed copy or launch (the members' outputs are then not written).  The mode (corridors, conditions) is the
 // whole group's: member 0 decides it.
 inline bool minsnapGroupOnDevice(vigo_context* dev, int diffDegree, int continuityDegree, double desiredVel, double corridorRes,
@@ -96,16 +47,6 @@ inline bool minsnapGroupOnDevice(vigo_context* dev, int diffDegree, int continui
 }
 
 // ---- the whole-trajectory check of one round: every candidate in ONE launch of a vigo_traj_*_check entry ----
-struct TrajCheck {
-    size_t who;                            // the caller's own index of this candidate (not read here)
-    trajPlanner::polyTrajSolver* solver;   // in: the installed polynomial (device QP, host QP or a kept one) and its own knots
-    double delT;
-    trajPlanner::pose end;                 // in: the appended last waypoint
-    int32_t status;                        // out: VIGO_TRAJ_OK, or the entry rejects it: the caller checks it on the host
-    bool collides;
-    std::set<int> segments;                // out: collisionSeg
-};
-
 // launch(T, S, seg_off, coeffs, knots, delT, endpoint, out_status, out_n, out_flag, out_first, out_seg) makes the one call
 // with the device arrays both entries take, in their order in include/vigo.h (the entry and its own extra arguments stay
 // with the caller), and says whether it succeeded; only the verdicts come back.  False on a failed copy or launch.

@@ -4,13 +4,10 @@
 // collision checks on the device.
 #include <trajectory_planner/polyTrajOccMap.h>
 
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
 #include <iostream>
 
 #include "../../../include/vigo.h"
-#include "devbuf.h"
 #include "polyBatch.h"
 
 using std::cout;
@@ -27,9 +24,7 @@ polyTrajOccMap::polyTrajOccMap(const ros::NodeHandle& nh) : nh_(nh) {
     this->setDefaultInit();
 }
 
-polyTrajOccMap::~polyTrajOccMap() {
-    if (dev_) vigo_destroy(dev_);
-}
+polyTrajOccMap::~polyTrajOccMap() {}
 
 // PM.cpp:20-138: the keys under poly_traj/ and their defaults
 void polyTrajOccMap::initParam() {
@@ -50,41 +45,12 @@ void polyTrajOccMap::initParam() {
     if (!nh_.getParam("poly_traj/use_pwl_failsafe", usePWL_)) usePWL_ = false;
 }
 
-void polyTrajOccMap::setMap(const std::shared_ptr<mapManager::occMap>& map) {
-    map_ = map;
-    mapStamp_ = 0;
-}
-
-void polyTrajOccMap::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) {
-    mapRegion_.set = true;
-    mapRegion_.boxMin = boxMin;
-    mapRegion_.boxMax = boxMax;
-    mapStamp_ = 0;
-}
-
-void polyTrajOccMap::refreshMap() {
-    mapAdapter::bumpGeneration(map_.get());
-    mapStamp_ = 0;
-}
-
-// see bsplineTraj::setDevice
-void polyTrajOccMap::setDevice(int ordinal) {
-    if (ordinal == deviceOrdinal_) return;
-    if (dev_) { vigo_destroy(dev_); dev_ = nullptr; }
-    mapStamp_ = 0;
-    deviceOrdinal_ = ordinal;
-}
-
-bool polyTrajOccMap::syncDevice() {
-    if (!map_) return false;
-    if (hipSetDevice(deviceOrdinal_) != hipSuccess) return false;
-    if (!dev_ && vigo_create(&dev_, deviceOrdinal_) != VIGO_OK) {
-        dev_ = nullptr;
-        return false;
-    }
-    if (vigo_set_stream(dev_, vigo_host::threadStream()) != VIGO_OK) return false;
-    return mapAdapter::uploadSnapshot(dev_, map_, mapRegion_, mapStamp_);
-}
+// the device link (mapAdapter.h); this planner prints nothing about it, and does not sync without a map
+void polyTrajOccMap::setMap(const std::shared_ptr<mapManager::occMap>& map) { link_.setMap(map); }
+void polyTrajOccMap::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
+void polyTrajOccMap::refreshMap() { link_.refresh(); }
+void polyTrajOccMap::setDevice(int ordinal) { link_.setDevice(ordinal); }
+bool polyTrajOccMap::syncDevice() { return link_.sync(true) == DeviceLink::kSynced; }
 
 void polyTrajOccMap::initSolver() {   // PM.cpp:152-154
     trajSolver_.reset(new polyTrajSolver(polyDegree_, diffDegree_, continuityDegree_, desiredVel_));
@@ -142,14 +108,8 @@ void polyTrajOccMap::setDefaultInit() {
 
 // ---- the planning loop of PM.cpp:326-399 in steps: begin, per round the QP (solveOnHost or the device QP), the samples
 // and their check, advance(); finish.  makePlan and makePlanBatch keep their own time limits ----
-struct polyTrajOccMap::PlanState {
-    std::vector<double> corridor;   // corridorSizeVec
-    int iters = 0;                  // countIter
-    double t0 = 0;
-};
-
 // PM.cpp:334-346: a fresh solver for every plan (initSolver), the path and the four conditions, initial_radius everywhere
-polyTrajOccMap::PlanState polyTrajOccMap::begin() {
+polyTrajOccMap::PlanState polyTrajOccMap::begin(bool corridorConstraint) {
     initSolver();
     trajSolver_->updatePath(path_);
     trajSolver_->updateInitVel(initVel_.linear.x, initVel_.linear.y, initVel_.linear.z);
@@ -157,6 +117,7 @@ polyTrajOccMap::PlanState polyTrajOccMap::begin() {
     trajSolver_->updateInitAcc(initAcc_.linear.x, initAcc_.linear.y, initAcc_.linear.z);
     trajSolver_->updateEndAcc(endAcc_.linear.x, endAcc_.linear.y, endAcc_.linear.z);
     PlanState s;
+    s.corridors = corridorConstraint;
     s.corridor.assign(path_.size() - 1, initR_);
     s.t0 = vigo_host::nowSec();
     findValidTraj_ = false;
@@ -165,8 +126,8 @@ polyTrajOccMap::PlanState polyTrajOccMap::begin() {
 }
 
 // PM.cpp:355-360 (corridors) and :374 (none).  An infeasible corridor keeps the previous polynomial, like the reference.
-void polyTrajOccMap::solveOnHost(bool corridorConstraint, PlanState& s) {
-    if (corridorConstraint) {
+void polyTrajOccMap::solveOnHost(PlanState& s) {
+    if (s.corridors) {
         trajSolver_->setCorridorConstraint(s.corridor, corridorRes_);
         // PM.cpp:357-358: the bool is passed as the radius — x and y get 1.0 (or 0), z gets 0; constraint_radius is
         // never used (kept, not fixed)
@@ -223,14 +184,14 @@ bool polyTrajOccMap::makePlan(std::vector<pose>& trajectory, bool corridorConstr
         return true;
     }
     if (path_.empty()) return false;
-    PlanState s = begin();
+    PlanState s = begin(corridorConstraint);
     bool valid = false;
     while (ros::ok() && !valid) {
         if (vigo_host::nowSec() - s.t0 >= timeout_) {   // PM.cpp:349-353: tested at the top of each round
             cout << "[minSnapTraj]: Timeout!" << endl;
             break;
         }
-        solveOnHost(corridorConstraint, s);
+        solveOnHost(s);
         // no polynomial to sample (the very first QP failed: coincident waypoints, an infeasible first corridor)
         if (!trajSolver_->hasSolution()) break;
         trajSolver_->getTrajectory(trajectory, delT_);
@@ -255,7 +216,7 @@ bool polyTrajOccMap::checkCollisionTraj(const std::vector<pose>& trajectory, dou
     std::vector<uint8_t> flags;
     for (const pose& p : trajectory) {
         const Eigen::Vector3d pEig(p.x, p.y, p.z);
-        flags.push_back(map_ && map_->isInflatedOccupied(pEig) && map_->isUnknown(pEig));
+        flags.push_back(link_.map() && link_.map()->isInflatedOccupied(pEig) && link_.map()->isUnknown(pEig));
     }
     return vigo_host::collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT, collisionSeg);
 }
@@ -265,144 +226,104 @@ void polyTrajOccMap::adjustCorridorSize(const std::set<int>& collisionSeg, std::
     for (int collisionIdx : collisionSeg) corridorSizeVec[collisionIdx] = corridorSizeVec[collisionIdx] * fs_;
 }
 
-// makePlan(trajectory, corridorConstraint) of many planners in lock-step.  Per round: the time limit of every active
-// planner (timeout x planners in the batch, as polyTrajOctomap's batch), then its QP — ONE vigo_minsnap launch per
-// (waypoint count, differential / continuity degree, velocity, corridor_res) group; soft constraints (which the device QP
-// does not take), shapes vigo_minsnap_supported refuses and device statuses other than "solved" go to the host QP, which
-// decides them as the solo plan does — then ONE vigo_traj_point_check launch over every candidate (a trajectory it
-// rejects is sampled and checked on the host that round).  Planners the batch cannot take (fewer than two waypoints,
-// another polynomial degree than 7, another map, region or device than the first) plan alone; so does every planner when
-// the device cannot be reached.  A device failure during the batch ends it: the planners not yet valid fall back.
+// makePlan(trajectory, corridorConstraint) of many planners in lock-step: LockStepBatch (polyBatchLoop.h) with the rules
+// below and the device steps — ONE vigo_minsnap launch per QP group, ONE vigo_traj_point_check launch over every candidate
+// of a round.  A device failure during the batch ends it: the planners not yet valid end as "not found".
+struct polyTrajOccMap::DeviceSteps {
+    polyTrajOccMap* lead = nullptr;
+    bool ready(polyTrajOccMap* l) { lead = l; return l->syncDevice(); }
+    bool supported(int W, int diff, int cont) const { return vigo_minsnap_supported(W, 7, diff, cont) != 0; }
+    bool solve(int diff, int cont, double vel, double corridorRes, std::vector<vigo_host::QpMember>& qp) {
+        return vigo_host::minsnapGroupOnDevice(lead->link_.handle(), diff, cont, vel, corridorRes, qp);
+    }
+    bool check(std::vector<vigo_host::TrajCheck>& cand) {
+        vigo_context* dev = lead->link_.handle();
+        return vigo_host::checkTrajectoriesOnDevice(cand, [dev](int T, int S, const int32_t* segOff, const double* co, const double* kn,
+                                                                const double* dt, const double* ep, int32_t* status, int32_t* n,
+                                                                uint8_t* flag, int32_t* first, uint8_t* seg) {
+            return vigo_traj_point_check(dev, T, S, 7, segOff, co, kn, dt, ep, status, n, flag, first, nullptr, seg) == VIGO_OK;
+        });
+    }
+    const char* lastError() const { return vigo_last_error(lead->link_.handle()); }
+};
+
 std::vector<bool> polyTrajOccMap::makePlanBatch(const std::vector<polyTrajOccMap*>& ps, bool corridorConstraint,
                                                 std::vector<std::vector<pose>>* trajectories) {
-    const size_t P = ps.size();
-    std::vector<bool> result(P, false);
     std::vector<std::vector<pose>> local;
-    std::vector<std::vector<pose>>& out = trajectories ? *trajectories : local;
-    out.assign(P, {});
-    polyTrajOccMap* lead = nullptr;
-    std::vector<size_t> grp;
-    for (size_t i = 0; i < P; ++i) {
-        polyTrajOccMap* p = ps[i];
-        if (!lead && p->path_.size() >= 2 && p->polyDegree_ == 7 && p->map_) lead = p;
-        const bool batchable = lead && p->path_.size() >= 2 && p->polyDegree_ == 7 && p->map_ == lead->map_ &&
-                               sameRegion(p->mapRegion_, lead->mapRegion_) && p->deviceOrdinal_ == lead->deviceOrdinal_;
-        if (batchable) {
-            grp.push_back(i);
-        } else {
-            result[i] = p->makePlan(out[i], corridorConstraint);
-        }
+    DeviceSteps steps;
+    return vigo_host::LockStepBatch<polyTrajOccMap>::run(ps, corridorConstraint, trajectories ? *trajectories : local, steps);
+}
+
+// Who is batchable and who leads: the first planner with two or more waypoints, degree 7 and a map leads; the batch takes
+// those like it on the same device, map and box.  The others plan alone.
+const polyTrajOccMap* polyTrajOccMap::batchReference(const std::vector<polyTrajOccMap*>& ps) {
+    for (const polyTrajOccMap* p : ps)
+        if (p->path_.size() >= 2 && p->polyDegree_ == 7 && p->link_.map()) return p;
+    return nullptr;
+}
+bool polyTrajOccMap::batchable(const polyTrajOccMap* ref) const {
+    return ref && path_.size() >= 2 && polyDegree_ == 7 && link_.sameTarget(ref->link_);
+}
+bool polyTrajOccMap::planAlone(std::vector<pose>& trajectory, bool corridorConstraint, bool&) { return makePlan(trajectory, corridorConstraint); }
+
+// Without a device: one line, and every planner of the group plans alone.
+void polyTrajOccMap::planWithoutDevice(const std::vector<polyTrajOccMap*>& ps, const std::vector<size_t>& grp, bool corridorConstraint,
+                                       std::vector<std::vector<pose>>& out, std::vector<bool>& result) {
+    cout << "[minSnapTraj]: no device for the batch; the planners plan alone." << endl;
+    for (size_t i : grp) result[i] = ps[i]->makePlan(out[i], corridorConstraint);
+}
+
+// The time limit, timeout x (planners in the batch), is tested at the top of each round (PM.cpp:349-353).
+bool polyTrajOccMap::timedOutBeforeRound(const PlanState& s, size_t G) const {
+    if (vigo_host::nowSec() - s.t0 < timeout_ * (double)G) return false;
+    cout << "[minSnapTraj]: Timeout!" << endl;
+    return true;
+}
+
+// The QP group key beside the waypoint count: differential and continuity degree, velocity, corridor_res, and no soft
+// constraint — the device QP takes the waypoints as equalities, so a planner with one goes straight to the host QP
+// (hostQpOnly), as do the shapes vigo_minsnap_supported refuses.
+bool polyTrajOccMap::sameQpGroup(const PlanState&, const polyTrajOccMap& o, const PlanState&) const {
+    return !o.softConstraint_ && o.diffDegree_ == diffDegree_ && o.continuityDegree_ == continuityDegree_ && o.desiredVel_ == desiredVel_ &&
+           o.corridorRes_ == corridorRes_;
+}
+
+// The conditions handed to the QP: the four twists.
+vigo_host::QpMember polyTrajOccMap::qpMember(size_t who, const PlanState& s) const {
+    return {who, &path_, s.corridors ? &s.corridor : nullptr, {&initVel_, &endVel_, &initAcc_, &endAcc_}, 0, {}};
+}
+
+// A solved QP is installed (with the corridor boxes the host solve would have set); any other status (-1 numerical, -2
+// infeasible) goes to the host QP, which decides it as the solo plan does.
+void polyTrajOccMap::takeQpResult(PlanState& s, const vigo_host::QpMember& m) {
+    if (m.status == 0) {
+        if (s.corridors) trajSolver_->setCorridorConstraint(s.corridor, corridorRes_);
+        trajSolver_->installSolution(m.sol[0], m.sol[1], m.sol[2]);
+    } else {
+        solveOnHost(s);
     }
-    if (grp.empty()) return result;
-    if (!lead->syncDevice()) {
-        cout << "[minSnapTraj]: no device for the batch; the planners plan alone." << endl;
-        for (size_t i : grp) result[i] = ps[i]->makePlan(out[i], corridorConstraint);
-        return result;
-    }
-    const size_t G = grp.size();
-    std::vector<PlanState> st;
-    std::vector<bool> active(G, true), valid(G, false);
-    for (size_t g = 0; g < G; ++g) st.push_back(ps[grp[g]]->begin());
-    bool ok = true;
-    while (ok) {
-        std::vector<size_t> act;
-        for (size_t g = 0; g < G; ++g) {
-            if (!active[g]) continue;
-            polyTrajOccMap* p = ps[grp[g]];
-            if (vigo_host::nowSec() - st[g].t0 >= p->timeout_ * (double)G) {   // PM.cpp:349-353
-                cout << "[minSnapTraj]: Timeout!" << endl;
-                active[g] = false;
-                continue;
-            }
-            act.push_back(g);
-        }
-        if (act.empty()) break;
-        // ---- the QPs ----
-        std::vector<bool> solved(G, false);
-        for (size_t a0 = 0; a0 < act.size() && ok; ++a0) {
-            const size_t g0 = act[a0];
-            if (solved[g0]) continue;
-            solved[g0] = true;
-            polyTrajOccMap* p0 = ps[grp[g0]];
-            const int W = (int)p0->path_.size();
-            if (p0->softConstraint_ || !vigo_minsnap_supported(W, 7, p0->diffDegree_, p0->continuityDegree_)) {
-                p0->solveOnHost(corridorConstraint, st[g0]);
-                continue;
-            }
-            std::vector<size_t> members{g0};
-            for (size_t a = a0 + 1; a < act.size(); ++a) {
-                const size_t g = act[a];
-                const polyTrajOccMap* p = ps[grp[g]];
-                if (!solved[g] && !p->softConstraint_ && (int)p->path_.size() == W && p->diffDegree_ == p0->diffDegree_ &&
-                    p->continuityDegree_ == p0->continuityDegree_ && p->desiredVel_ == p0->desiredVel_ &&
-                    p->corridorRes_ == p0->corridorRes_) {
-                    members.push_back(g);
-                    solved[g] = true;
-                }
-            }
-            std::vector<vigo_host::QpMember> qp;
-            for (size_t g : members) {
-                const polyTrajOccMap* p = ps[grp[g]];
-                qp.push_back({&p->path_, corridorConstraint ? &st[g].corridor : nullptr, {&p->initVel_, &p->endVel_, &p->initAcc_, &p->endAcc_}, 0, {}});
-            }
-            ok = vigo_host::minsnapGroupOnDevice(lead->dev_, p0->diffDegree_, p0->continuityDegree_, p0->desiredVel_, p0->corridorRes_, qp);
-            for (size_t a = 0; ok && a < members.size(); ++a) {
-                const size_t g = members[a];
-                polyTrajOccMap* p = ps[grp[g]];
-                if (qp[a].status == 0) {
-                    if (corridorConstraint) p->trajSolver_->setCorridorConstraint(st[g].corridor, p->corridorRes_);
-                    p->trajSolver_->installSolution(qp[a].sol[0], qp[a].sol[1], qp[a].sol[2]);
-                } else {
-                    p->solveOnHost(corridorConstraint, st[g]);   // -1 numerical, -2 infeasible: the host QP decides
-                }
-            }
-        }
-        if (!ok) break;
-        // ---- without corridors: one solve, valid without any check (PM.cpp:373-377) ----
-        std::vector<vigo_host::TrajCheck> cand;
-        for (size_t g : act) {
-            polyTrajOccMap* p = ps[grp[g]];
-            active[g] = corridorConstraint;
-            if (!p->trajSolver_->hasSolution()) {   // nothing to sample (see makePlan): not found
-                active[g] = false;
-                continue;
-            }
-            if (!corridorConstraint) {
-                p->lastIterations_ = ++st[g].iters;
-                valid[g] = true;
-                continue;
-            }
-            cand.push_back({g, p->trajSolver_.get(), p->delT_, p->path_.back(), 0, false, {}});
-        }
-        // ---- every candidate checked whole by ONE vigo_traj_point_check launch; verdicts and segment masks come back ----
-        ok = vigo_host::checkTrajectoriesOnDevice(cand, [&](int T, int S, const int32_t* segOff, const double* co, const double* kn,
-                                                            const double* dt, const double* ep, int32_t* status, int32_t* n,
-                                                            uint8_t* flag, int32_t* first, uint8_t* seg) {
-            return vigo_traj_point_check(lead->dev_, T, S, 7, segOff, co, kn, dt, ep, status, n, flag, first, nullptr, seg) == VIGO_OK;
-        });
-        if (!ok) cout << "[minSnapTraj]: device trajectory check failed: " << vigo_last_error(lead->dev_) << endl;
-        for (size_t a = 0; ok && a < cand.size(); ++a) {
-            const size_t g = cand[a].who;
-            polyTrajOccMap* p = ps[grp[g]];
-            if (cand[a].status != VIGO_TRAJ_OK) {   // a trajectory the device entry rejects: sampled and checked on the host
-                std::vector<pose> traj;
-                p->trajSolver_->getTrajectory(traj, p->delT_);
-                cand[a].collides = p->checkCollisionTraj(traj, p->delT_, cand[a].segments);   // (clears the segments first)
-            }
-            valid[g] = !cand[a].collides;
-            active[g] = p->advance(st[g], cand[a].collides, cand[a].segments);
-        }
-    }
-    // the returned trajectories: sampled once, from the last polynomial (the reference returns the last candidate when
-    // none was valid), then the verdict and the fallback as in makePlan
-    for (size_t g = 0; g < G; ++g) {
-        polyTrajOccMap* p = ps[grp[g]];
-        std::vector<pose>& traj = out[grp[g]];
-        if (p->trajSolver_->hasSolution()) p->trajSolver_->getTrajectory(traj, p->delT_);
-        p->finish(traj, valid[g]);
-        result[grp[g]] = valid[g];
-    }
-    return result;
+}
+
+// The no-corridor round (PM.cpp:373-377): one solve, valid without any check.
+bool polyTrajOccMap::validWithoutCheck(PlanState& s) {
+    if (s.corridors) return false;
+    lastIterations_ = ++s.iters;
+    return true;
+}
+
+// A candidate the device check rejects is sampled and checked on the host that round, by the solo plan's rule.
+void polyTrajOccMap::checkOnHost(polyTrajOccMap&, vigo_host::TrajCheck& c) {
+    std::vector<pose> traj;
+    trajSolver_->getTrajectory(traj, delT_);
+    c.collides = checkCollisionTraj(traj, delT_, c.segments);   // (clears the segments first)
+}
+
+// The ending: the last polynomial sampled (the reference returns the last candidate when none was valid), then the verdict
+// and the fallback as in makePlan.
+bool polyTrajOccMap::finishBatch(std::vector<pose>& trajectory, bool valid) {
+    if (trajSolver_->hasSolution()) trajSolver_->getTrajectory(trajectory, delT_);
+    finish(trajectory, valid);
+    return valid;
 }
 
 // PM.cpp:554-571

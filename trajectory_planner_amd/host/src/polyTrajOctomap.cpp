@@ -3,8 +3,6 @@
 // getters); the box sweep of every trajectory sample runs on the device.
 #include <trajectory_planner/polyTrajOctomap.h>
 
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
 #include <iostream>
 
@@ -38,37 +36,16 @@ polyTrajOctomap::polyTrajOctomap(const ros::NodeHandle& nh) : nh_(nh) {
     if (softConstraint_ && !nh_.getParam("constraint_radius", softConstraintRadius_)) softConstraintRadius_ = 0.5;
 }
 
-polyTrajOctomap::~polyTrajOctomap() {
-    if (dev_) vigo_destroy(dev_);
-}
+void polyTrajOctomap::setMap(const std::shared_ptr<mapManager::occMap>& map) { link_.setMap(map); }
+void polyTrajOctomap::setDevice(int ordinal) { link_.setDevice(ordinal); }
 
-void polyTrajOctomap::setMap(const std::shared_ptr<mapManager::occMap>& map) {
-    map_ = map;
-    mapStamp_ = 0;
-}
-
+// the device link's sync (mapAdapter.h) with this planner's console lines; it does not sync without a map
 bool polyTrajOctomap::syncDevice() {
-    if (!map_) return false;
-    if (hipSetDevice(deviceOrdinal_) != hipSuccess) {    // this planner's GPU current on the calling thread (stream, staging)
-        cout << "[Trajectory Planner INFO]: HIP device " << deviceOrdinal_ << " is not available (no CPU fallback)." << endl;
-        return false;
-    }
-    if (!dev_ && vigo_create(&dev_, deviceOrdinal_) != VIGO_OK) {
-        cout << "[Trajectory Planner INFO]: no HIP device for the corridor checker (no CPU fallback)." << endl;
-        dev_ = nullptr;
-        return false;
-    }
-    // launches and staging copies of this call go to the calling thread's stream
-    if (vigo_set_stream(dev_, vigo_host::threadStream()) != VIGO_OK) return false;
-    return mapAdapter::uploadSnapshot(dev_, map_, mapRegion_, mapStamp_);
-}
-
-// see bsplineTraj::setDevice
-void polyTrajOctomap::setDevice(int ordinal) {
-    if (ordinal == deviceOrdinal_) return;
-    if (dev_) { vigo_destroy(dev_); dev_ = nullptr; }
-    mapStamp_ = 0;
-    deviceOrdinal_ = ordinal;
+    const DeviceLink::Sync r = link_.sync(true);
+    if (r == DeviceLink::kNoDevice)
+        cout << "[Trajectory Planner INFO]: HIP device " << link_.ordinal() << " is not available (no CPU fallback)." << endl;
+    if (r == DeviceLink::kNoHandle) cout << "[Trajectory Planner INFO]: no HIP device for the corridor checker (no CPU fallback)." << endl;
+    return r == DeviceLink::kSynced;
 }
 
 void polyTrajOctomap::updatePath(const nav_msgs::Path& path) {
@@ -113,7 +90,7 @@ bool polyTrajOctomap::sweepPoints(const std::vector<pose>& pts, std::vector<uint
     std::vector<double> xyz;
     vigo_host::appendXyz(pts, xyz);
     const bool ok = sweepXyz(xyz, flags);
-    if (!ok) cout << "[Trajectory Planner INFO]: device box sweep failed: " << vigo_last_error(dev_) << endl;
+    if (!ok) cout << "[Trajectory Planner INFO]: device box sweep failed: " << vigo_last_error(link_.handle()) << endl;
     return ok;
 }
 
@@ -126,7 +103,7 @@ bool polyTrajOctomap::sweepXyz(const std::vector<double>& xyz, std::vector<uint8
     static thread_local vigo_host::StagingBuf dP, dF;      // reused by every sweep of this thread
     const double box[3] = {collisionBox_[0], collisionBox_[1], collisionBox_[2]};
     const bool ok = dP.upload(xyz.data(), n * 24) && dF.alloc(n) &&
-                    vigo_box_collision_points(dev_, (int64_t)n, (const double*)dP.p, box, mapRes_, (uint8_t*)dF.p) == VIGO_OK &&
+                    vigo_box_collision_points(link_.handle(), (int64_t)n, (const double*)dP.p, box, mapRes_, (uint8_t*)dF.p) == VIGO_OK &&
                     dF.download(flags.data(), n);
     // A pose at NaN or infinity: the reference's sweep makes no pass there (the lattice count is the conversion of a
     // NaN, INT_MIN on x86 — the device entry point follows that, include/vigo.h) and would publish the trajectory.  The
@@ -145,8 +122,8 @@ bool polyTrajOctomap::checkCollision(const pose& p) {
 
 // PO.cpp:571-589 on the dense map (host: a single lookup)
 bool polyTrajOctomap::checkCollisionPoint(const pose& p, bool ignoreUnknown) {
-    if (!map_) return true;
-    const unsigned v = mapAdapter::nodeBits(map_, mapRegion_, (float)p.x, (float)p.y, (float)p.z);   // pose2Octomap + search()
+    if (!link_.map()) return true;
+    const unsigned v = mapAdapter::nodeBits(link_.map(), link_.region(), (float)p.x, (float)p.y, (float)p.z);   // pose2Octomap + search()
     if (v & mapAdapter::kOutside) return true;                  // beyond getMetricMin/Max
     if (v & mapAdapter::kUnknown) return !ignoreUnknown;        // no node there
     return (v & mapAdapter::kOccupied) != 0;                    // isNodeOccupied
@@ -186,13 +163,6 @@ void polyTrajOctomap::pwlPlan(std::vector<pose>& trajectory, double delT) {
 
 // ---- the planning loop of PO.cpp:259-545: per round the QP (solveOnHost, or the device QP in makePlanBatch), the
 // samples at delT, their box sweep, then advance(); the two callers keep their own time limits ----
-struct polyTrajOctomap::PlanState {
-    bool addingWaypoints;               // PO.cpp:259-386; else the corridor constraint, PO.cpp:388-545
-    std::vector<double> corridor;       // corridor radius per segment (corridor mode)
-    int iters = 0;
-    double t0 = 0;
-};
-
 polyTrajOctomap::PlanState polyTrajOctomap::begin(bool addingWaypoints) {
     setDefaultInit();
     trajSolver_.reset(new polyTrajSolver(polyDegree_, diffDegree_, continuityDegree_, desiredVel_));
@@ -288,129 +258,94 @@ void polyTrajOctomap::makePlan(std::vector<pose>& trajectory, double delT) {
     findValidTraj_ = !this->checkCollisionTraj(trajectory, delT, collisionSeg);
 }
 
-// makePlan() of many planners in lock-step: the planning loop above, with the QPs of each round grouped by (waypoint
-// count, mode) into ONE vigo_minsnap launch per group (corridor boxes for the corridor mode, none for the adding-
-// waypoint mode, whose paths grow as waypoints are inserted: the groups are re-formed every round), and every
-// candidate trajectory checked whole — samples, box sweep and segment attribution of checkCollisionTraj, PO.cpp:634-656
-// — by ONE vigo_traj_corridor_check launch (a trajectory it rejects is sampled and swept on the host that round).  The
-// returned trajectories are sampled on the host once, after the loop.  A path shape the device QP does not take (more
-// than 11 waypoints, or more rows or LDS than the continuity degree leaves room for: vigo_minsnap_supported) and a
-// device QP status of -1 are solved by the host QP inside the same round.  Time limit: timeout x (planners in the
-// batch), checked after a colliding round.  A failed device call ends the batch: every planner not yet valid falls back.
-std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctomap*>& ps, std::vector<std::vector<pose>>& trajectories) {
-    const size_t P = ps.size();
-    std::vector<bool> result(P, false);
-    trajectories.assign(P, {});
-    if (P == 0) return result;
-    // planners the batch cannot take (installed polynomial, a single waypoint, another polynomial degree, another
-    // map or sweep geometry than the first planner's, soft waypoint constraints — the device QP takes the waypoints
-    // as equalities) plan on their own
-    std::vector<size_t> grp;
-    bool toldSoft = false;
-    for (size_t i = 0; i < P; ++i) {
-        polyTrajOctomap* p = ps[i];
-        p->findValidTraj_ = false;
-        const bool batchable = p->extKnots_.empty() && p->path_.size() >= 2 && p->polyDegree_ == 7 && p->diffDegree_ == ps[0]->diffDegree_ &&
-                               p->continuityDegree_ == ps[0]->continuityDegree_ && p->desiredVel_ == ps[0]->desiredVel_ &&
-                               p->corridorRes_ == ps[0]->corridorRes_ && p->deviceOrdinal_ == ps[0]->deviceOrdinal_ && p->map_ == ps[0]->map_ && sameRegion(p->mapRegion_, ps[0]->mapRegion_) && p->collisionBox_ == ps[0]->collisionBox_ &&
-                               p->mapRes_ == ps[0]->mapRes_ && !p->softConstraint_;
-        if (batchable) grp.push_back(i);
-        else {
-            if (p->softConstraint_ && !toldSoft) {
-                // (once per call: such a planner leaves the batched device path — the device QP takes waypoints as equalities)
-                cout << "[Trajectory Planner INFO]: soft waypoint constraints: planned on the host path, outside the device batch." << endl;
-                toldSoft = true;
-            }
-            p->makePlan(trajectories[i], p->delT_);
-            result[i] = p->findValidTraj_;
-        }
+// makePlan() of many planners in lock-step: LockStepBatch (polyBatchLoop.h) with the rules below and the device steps —
+// ONE vigo_minsnap launch per QP group, and every candidate trajectory checked whole (samples, box sweep and segment
+// attribution of checkCollisionTraj, PO.cpp:634-656) by ONE vigo_traj_corridor_check launch with the lead's box and map
+// resolution.  A failed device call ends the batch: every planner not yet valid falls back.
+struct polyTrajOctomap::DeviceSteps {
+    polyTrajOctomap* lead = nullptr;
+    bool ready(polyTrajOctomap* l) { lead = l; return l->syncDevice(); }
+    bool supported(int W, int diff, int cont) const { return vigo_minsnap_supported(W, 7, diff, cont) != 0; }
+    bool solve(int diff, int cont, double vel, double corridorRes, std::vector<vigo_host::QpMember>& qp) {
+        return vigo_host::minsnapGroupOnDevice(lead->link_.handle(), diff, cont, vel, corridorRes, qp);
     }
-    if (grp.empty()) return result;
-    polyTrajOctomap* lead = ps[grp[0]];
-    if (!lead->syncDevice()) return result;
-    const size_t G = grp.size();
-    std::vector<PlanState> st;
-    std::vector<bool> active(G, true);
-    for (size_t g = 0; g < G; ++g) st.push_back(ps[grp[g]]->begin(ps[grp[g]]->mode_));
-    bool ok = true;
-    while (ok) {
-        std::vector<size_t> act;
-        for (size_t g = 0; g < G; ++g) if (active[g]) act.push_back(g);
-        if (act.empty()) break;
-        // ---- the QPs: one launch per (waypoint count, mode) among the active planners ----
-        std::vector<bool> solved(G, false);
-        for (size_t a0 = 0; a0 < act.size() && ok; ++a0) {
-            const size_t g0 = act[a0];
-            if (solved[g0]) continue;
-            solved[g0] = true;
-            polyTrajOctomap* p0 = ps[grp[g0]];
-            const int W = (int)p0->path_.size();
-            const bool adding = st[g0].addingWaypoints;
-            // a shape beyond the device QP (more than 11 waypoints, or too many rows / too little LDS for this continuity
-            // degree, vigo_minsnap_supported): the host QP, same algorithm
-            if (!vigo_minsnap_supported(W, 7, lead->diffDegree_, lead->continuityDegree_)) { p0->solveOnHost(st[g0]); continue; }
-            std::vector<size_t> members{g0};
-            for (size_t a = a0 + 1; a < act.size(); ++a) {
-                const size_t g = act[a];
-                if (!solved[g] && (int)ps[grp[g]]->path_.size() == W && st[g].addingWaypoints == adding) { members.push_back(g); solved[g] = true; }
-            }
-            std::vector<vigo_host::QpMember> qp;
-            for (size_t g : members) qp.push_back({&ps[grp[g]]->path_, adding ? nullptr : &st[g].corridor, {}, 0, {}});
-            ok = vigo_host::minsnapGroupOnDevice(lead->dev_, lead->diffDegree_, lead->continuityDegree_, lead->desiredVel_, lead->corridorRes_, qp);
-            // an infeasible corridor (-2) keeps the previous polynomial, like the reference; a numerical failure of the
-            // device QP (-1: more than 1024 corridor boxes, say) is solved by the host QP, which has no such limit
-            for (size_t a = 0; ok && a < members.size(); ++a) {
-                const size_t g = members[a];
-                if (qp[a].status == 0) ps[grp[g]]->trajSolver_->installSolution(qp[a].sol[0], qp[a].sol[1], qp[a].sol[2]);
-                else if (qp[a].status == -1) ps[grp[g]]->solveOnHost(st[g]);
-            }
-        }
-        if (!ok) break;
-        // ---- every candidate's whole trajectory checked by ONE vigo_traj_corridor_check launch ----
-        std::vector<vigo_host::TrajCheck> cand;
-        for (size_t g : act) {
-            polyTrajOctomap* p = ps[grp[g]];
-            if (!p->trajSolver_->hasSolution()) {      // nothing to check (see planOnHost): not found
-                trajectories[grp[g]].clear();
-                active[g] = false;
-                continue;
-            }
-            cand.push_back({g, p->trajSolver_.get(), p->delT_, p->path_.back(), 0, false, {}});
-        }
-        const double box[3] = {lead->collisionBox_[0], lead->collisionBox_[1], lead->collisionBox_[2]};
-        ok = vigo_host::checkTrajectoriesOnDevice(cand, [&](int T, int S, const int32_t* segOff, const double* co, const double* kn,
-                                                            const double* dt, const double* ep, int32_t* status, int32_t* n,
-                                                            uint8_t* flag, int32_t* first, uint8_t* seg) {
-            return vigo_traj_corridor_check(lead->dev_, T, S, 7, segOff, co, kn, dt, ep, box, lead->mapRes_, VIGO_TRAJ_NONFINITE_COLLIDES,
+    bool check(std::vector<vigo_host::TrajCheck>& cand) {
+        const polyTrajOctomap* l = lead;
+        const double box[3] = {l->collisionBox_[0], l->collisionBox_[1], l->collisionBox_[2]};
+        return vigo_host::checkTrajectoriesOnDevice(cand, [l, &box](int T, int S, const int32_t* segOff, const double* co, const double* kn,
+                                                                    const double* dt, const double* ep, int32_t* status, int32_t* n,
+                                                                    uint8_t* flag, int32_t* first, uint8_t* seg) {
+            return vigo_traj_corridor_check(l->link_.handle(), T, S, 7, segOff, co, kn, dt, ep, box, l->mapRes_, VIGO_TRAJ_NONFINITE_COLLIDES,
                                             status, n, flag, first, nullptr, seg) == VIGO_OK;
         });
-        if (!ok) cout << "[Trajectory Planner INFO]: device trajectory check failed: " << vigo_last_error(lead->dev_) << endl;
-        for (size_t a = 0; ok && a < cand.size(); ++a) {
-            const size_t g = cand[a].who;
-            polyTrajOctomap* p = ps[grp[g]];
-            bool more;
-            if (cand[a].status != VIGO_TRAJ_OK) {   // a trajectory the device entry rejects: sampled and swept on the host
-                std::vector<pose>& traj = trajectories[grp[g]];
-                std::vector<uint8_t> flags;
-                std::vector<double> pts;
-                p->trajSolver_->getTrajectory(traj, p->delT_);
-                vigo_host::appendXyz(traj, pts);
-                lead->sweepXyz(pts, flags);            // a failed sweep leaves every flag set: the loop goes on
-                more = p->advanceOnFlags(st[g], flags, p->delT_);
-            } else {
-                more = p->advance(st[g], cand[a].collides, cand[a].segments);
-            }
-            if (!more || vigo_host::nowSec() - st[g].t0 >= p->timeout_ * (double)G) active[g] = false;
-        }
     }
-    // the returned trajectories: sampled once, from the polynomial that was found valid; the PWL fallback otherwise
-    for (size_t g = 0; g < G; ++g) {
-        polyTrajOctomap* p = ps[grp[g]];
-        if (p->findValidTraj_) p->trajSolver_->getTrajectory(trajectories[grp[g]], p->delT_);
-        else p->pwlPlan(trajectories[grp[g]], p->delT_);
-        result[grp[g]] = p->findValidTraj_;
+    const char* lastError() const { return vigo_last_error(lead->link_.handle()); }
+};
+
+std::vector<bool> polyTrajOctomap::makePlanBatch(const std::vector<polyTrajOctomap*>& ps, std::vector<std::vector<pose>>& trajectories) {
+    DeviceSteps steps;
+    return vigo_host::LockStepBatch<polyTrajOctomap>::run(ps, false, trajectories, steps);   // (the mode is each planner's own)
+}
+
+// Who is batchable and who leads: everything is compared with the FIRST planner of the call (batchReference), the first
+// batchable one leads.  The batch cannot take an installed polynomial, a single waypoint, another polynomial degree,
+// another QP or sweep geometry, device, map or box than the first planner's, or soft waypoint constraints (the device QP
+// takes the waypoints as equalities): those plan on their own.
+bool polyTrajOctomap::batchable(const polyTrajOctomap* ref) const {
+    return extKnots_.empty() && path_.size() >= 2 && polyDegree_ == 7 && diffDegree_ == ref->diffDegree_ &&
+           continuityDegree_ == ref->continuityDegree_ && desiredVel_ == ref->desiredVel_ && corridorRes_ == ref->corridorRes_ &&
+           link_.sameTarget(ref->link_) && collisionBox_ == ref->collisionBox_ && mapRes_ == ref->mapRes_ && !softConstraint_;
+}
+bool polyTrajOctomap::planAlone(std::vector<pose>& trajectory, bool, bool& toldSoft) {
+    if (softConstraint_ && !toldSoft) {   // once per call
+        cout << "[Trajectory Planner INFO]: soft waypoint constraints: planned on the host path, outside the device batch." << endl;
+        toldSoft = true;
     }
-    return result;
+    makePlan(trajectory, delT_);
+    return findValidTraj_;
+}
+
+// Without a device the group is not planned: no trajectory, not valid (syncDevice has said why).
+void polyTrajOctomap::planWithoutDevice(const std::vector<polyTrajOctomap*>& ps, const std::vector<size_t>& grp, bool,
+                                        std::vector<std::vector<pose>>&, std::vector<bool>&) {
+    for (size_t i : grp) ps[i]->findValidTraj_ = false;
+}
+
+// The time limit, timeout x (planners in the batch), is tested after a colliding round.
+bool polyTrajOctomap::timedOutAfterRound(const PlanState& s, size_t G) const { return vigo_host::nowSec() - s.t0 >= timeout_ * (double)G; }
+
+// The QP group key beside the waypoint count is the mode (sameQpGroup): corridor boxes for the corridor mode, none for the
+// adding-waypoint mode.  No conditions are handed to the QP.
+vigo_host::QpMember polyTrajOctomap::qpMember(size_t who, const PlanState& s) const {
+    return {who, &path_, s.addingWaypoints ? nullptr : &s.corridor, {}, 0, {}};
+}
+
+// An infeasible corridor (-2) keeps the previous polynomial, like the reference; a numerical failure of the device QP
+// (-1: more than 1024 corridor boxes, say) is solved by the host QP, which has no such limit.
+void polyTrajOctomap::takeQpResult(PlanState& s, const vigo_host::QpMember& m) {
+    if (m.status == 0) trajSolver_->installSolution(m.sol[0], m.sol[1], m.sol[2]);
+    else if (m.status == -1) solveOnHost(s);
+}
+
+// A candidate the device check rejects is sampled on the host and swept on the lead's synced handle that round (a failed
+// sweep leaves every flag set: the loop goes on); the blame as advanceOnFlags.
+void polyTrajOctomap::checkOnHost(polyTrajOctomap& lead, vigo_host::TrajCheck& c) {
+    std::vector<pose> traj;
+    std::vector<uint8_t> flags;
+    std::vector<double> pts;
+    trajSolver_->getTrajectory(traj, delT_);
+    vigo_host::appendXyz(traj, pts);
+    lead.sweepXyz(pts, flags);
+    c.segments.clear();
+    c.collides = vigo_host::collisionSegments(flags.data(), flags.size(), trajSolver_->getTimeKnot(), delT_, c.segments);
+}
+
+// The ending: the polynomial that was found valid, sampled once; the PWL fallback otherwise.  (The loop's verdict is
+// findValidTraj_, which advance() keeps.)
+bool polyTrajOctomap::finishBatch(std::vector<pose>& trajectory, bool) {
+    if (findValidTraj_) trajSolver_->getTrajectory(trajectory, delT_);
+    else pwlPlan(trajectory, delT_);
+    return findValidTraj_;
 }
 
 void polyTrajOctomap::makePlan() {
