@@ -128,7 +128,8 @@ int vigo_set_precision(vigo_handle_t h, int vigo_precision);
 /* Text of the last HIP/runtime failure on this handle (never NULL). */
 const char* vigo_last_error(vigo_handle_t h);
 /* Library/ABI version (raised when entry points are added; nothing was removed or changed so far: 4 adds
- * vigo_build_esdf / vigo_esdf_from_voxels_host), and whether the code object was built for gfx950. */
+ * vigo_build_esdf / vigo_esdf_from_voxels_host; vigo_seed_capacity / vigo_seed_paths / vigo_seed_paths_host came in at 4
+ * as well — ask the library for the symbol), and whether the code object was built for gfx950. */
 int vigo_abi_version(void);
 const char* vigo_build_arch(void);
 /* "solver:<12 hex> all:<12 hex>": digests of the library's compiled code (host code and gfx950 code objects; the first
@@ -473,6 +474,71 @@ int vigo_traj_corridor_check(vigo_handle_t h, int T, int S, int deg, const int32
 int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
                           const double* knots, const double* delT, const double* endpoint, int32_t* out_status,
                           int32_t* out_n, uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg);
+
+/*
+ * Replaces: the seed-path stage of bspline_node's replan step (src/bspline_node.cpp:317-378) between the two planners,
+ * for T trajectories at once: polyTrajOccMap::getTrajectory(dt) (polyTrajOccMap.cpp:434-446, getPos
+ * polyTrajSolver.cpp:1058-1078), bsplineTraj::inputPathCheck with its dt *= 0.8 retries (bsplineTraj.cpp:207-245) and the
+ * map-dependent head of bsplineTraj::updatePath (bsplineTraj.cpp:247-312, adjustPathLengthDirect :754-793).
+ *   seg_off, coeffs, knots   as vigo_traj_point_check (vigo_minsnap's output concatenated is this layout)
+ *   duration                 double[T]  the planner's getDuration()
+ *   dt0                      double[T]  the first try's dt (bsplineTraj::getInitTs())
+ *   control_point_distance, max_path_length   double[T]  the planner's values
+ *   prev_in_seed, prev_in_fit   double[T]  the previous path length (adjustPathLengthDirect's function-static) the seed
+ *                            search / updatePath's head starts from; rule 3 takes max(prev, max_path_length)
+ *   max_tries                tries of the search (replaces the reference's 50 ms of wall time); point_cap: rows of
+ *                            out_seed / out_fit per trajectory
+ * The rules, for one trajectory with knots k[0..K] (csrc/vigo_seed_core.hpp):
+ *   1 clock    t_0 = 0, t_{j+1} = fl(t_j + dt), kept while t_j <= duration (inclusive; no endpoint is appended)
+ *   2 sample   getPos(min(t_j, duration)): the first i with k[i] <= t <= k[i+1], local time fl(t - k[i]), the terms summed
+ *              in d = 0..deg order, pow as vigo_exact_pow; a t in no interval gives (0, 0, 0)
+ *   3 adjust   adjustPathLengthDirect: the list ends after the first pair whose end lies at least max(prev,
+ *              max_path_length) from the first point (straight-line distance), whose line is free and which follows a
+ *              free stretch of at least 1.5 (an occupied line resets the stretch); prev becomes the last distance looked
+ *              at.  Lines: the ends, then int(dist / res) - 1 interior steps, on bit plane 0 of the handle's grid
+ *   4 spacing  a consecutive distance of the adjusted list above 1.5 * control_point_distance fails the try:
+ *              dt = fl(dt * 0.8), prev carried over, the next try
+ *   5 thin     a point is kept when at least 0.8 * control_point_distance from the last kept one, the last kept point is
+ *              repeated once: the seed.  final_time = (adjusted_count - 1) * dt
+ *   6 head     the seed's last pose inflated-occupied: refused; rule 3 on the seed from prev_in_fit; fewer than 4 points:
+ *              fillPath on the seed (2 poses -> 4 points, 3 -> 5, 4 or more -> the seed whole)
+ * Outputs per trajectory: out_status (VIGO_SEED_*), out_tries, out_dt (after a failed try it is already shrunk:
+ * dt0 * 0.8^tries for VIGO_SEED_NO_SPACING), out_final_time, out_seed_n and out_seed[t][point_cap][3] (the seed:
+ * adjustedInputPolyTraj), out_fit_n and out_fit[t][point_cap][3] (the curve-fit points), out_prev_seed / out_prev_fit
+ * (prev after the search / after the head).  VIGO_SEED_DEFERRED writes the status only; VIGO_SEED_BAD_INPUT zero
+ * counts, dt0 and the prev values as given.
+ * How: a wavefront per trajectory, samples and per-pair line flag / step / distance by the lanes into LDS, rule 3 and 5
+ * by one lane, rule 4 a wave-wide any.  No atomics.  vigo_seed_capacity: the samples of one try LDS holds.
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle, T < 0, S < 0, deg outside [0, 15], max_tries < 1, point_cap < 0, NULL
+ * arrays (coeffs may be NULL when S = 0; every per-trajectory array when T = 0; out_seed / out_fit when point_cap = 0);
+ * VIGO_ERR_NO_GRID before a grid.  On an error nothing is written.
+ */
+enum {
+    VIGO_SEED_OK = 0,
+    VIGO_SEED_NO_SPACING = 1,    /* every try failed rule 4: the seed is empty                                    */
+    VIGO_SEED_GOAL_OCCUPIED = 2, /* rule 6: the seed is returned, no fit points                                   */
+    VIGO_SEED_TOO_SHORT = 3,     /* a seed of at most one pose (no sample: duration < 0)                          */
+    VIGO_SEED_DEFERRED = 4,      /* a try beyond vigo_seed_capacity, or a list beyond point_cap: the host's       */
+    VIGO_SEED_BAD_INPUT = 5      /* offsets outside [0, S]; a knot, dt0 or duration not finite; dt0 <= 0; a stalled clock */
+};
+int vigo_seed_capacity(int32_t* max_samples);
+int vigo_seed_paths(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs, const double* knots,
+                    const double* duration, const double* dt0, const double* control_point_distance,
+                    const double* max_path_length, const double* prev_in_seed, const double* prev_in_fit, int max_tries,
+                    int point_cap, int32_t* out_status, int32_t* out_tries, double* out_dt, double* out_final_time,
+                    int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit, double* out_prev_seed,
+                    double* out_prev_fit);
+/* The same rules on the CPU, no GPU and no handle: HOST arrays, the map a dense byte grid voxels_host[nx][ny][nz] (bit 0
+ * inflated-occupied, outside occupied) with its origin and resolution.  pow_mode 0: the kernels' correctly rounded power
+ * (bit for bit vigo_seed_paths); 1: libm's pow, the facade's.  cap: the sample capacity (<= 0: vigo_seed_capacity's).
+ * Returns VIGO_OK or VIGO_ERR_INVALID_ARG (also for a grid axis < 1, a resolution not finite and > 0, pow_mode not 0 / 1). */
+int vigo_seed_paths_host(int nx, int ny, int nz, const double origin[3], double res, const uint8_t* voxels_host, int pow_mode,
+                         int cap, int T, int S, int deg, const int32_t* seg_off, const double* coeffs, const double* knots,
+                         const double* duration, const double* dt0, const double* control_point_distance,
+                         const double* max_path_length, const double* prev_in_seed, const double* prev_in_fit, int max_tries,
+                         int point_cap, int32_t* out_status, int32_t* out_tries, double* out_dt, double* out_final_time,
+                         int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit, double* out_prev_seed,
+                         double* out_prev_fit);
 
 /*
  * Replaces: AStar::AstarSearch + AStar::getPath (path_search/astarOcc.cpp:120-244, astarOcc.h:41-85) for Q independent

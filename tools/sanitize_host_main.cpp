@@ -4,6 +4,7 @@
 #include <trajectory_planner/path_search/astarOcc.h>
 #include <trajectory_planner/piecewiseLinearTraj.h>
 #include "../trajectory_planner_amd/csrc/vigo_esdf_core.hpp"   // the ESDF build's host twin (header-only, no HIP)
+#include "../trajectory_planner_amd/csrc/vigo_seed_core.hpp"   // the seed-path stage's rules and serial driver (header-only, no HIP)
 #include <cmath>
 #include <cstdio>
 #include <random>
@@ -164,6 +165,63 @@ int main(int argc, char** argv) {
         if (vigo::esdf_from_voxels(16384, 16384, 16384, vox.data(), 2, 0, 0.1, out.data()) != -6) ++fails;   // > 2^33 voxels
         if (vigo::esdf_from_voxels(2, 2, 2, vox.data(), 2, 0, std::nan(""), out.data()) != -1) ++fails;
         for (float f : out) if (f != 7.0f) ++fails;
+    }
+    // the seed-path stage's host twin (vigo_seed_paths_host is a loop over vigo::seed_one) on min-snap polynomials through
+    // random box worlds: both powers, capacities and point_caps that hold the lists and that do not, hostile inputs
+    {
+        long ran = 0, okc = 0, deferred = 0;
+        for (int trial = 0; trial < 120; ++trial) {
+            const int nx = 80, ny = 80, nz = 24;
+            std::vector<uint8_t> vox((size_t)nx * ny * nz, 0);
+            for (int b = 0; b < trial % 7; ++b) {
+                const int cx = 10 + (int)(30 * (U(rng) + 1)), cy = 10 + (int)(30 * (U(rng) + 1)), h = 1 + (int)(4 * std::fabs(U(rng)));
+                for (int x = std::max(0, cx - h); x < std::min(nx, cx + h); ++x)
+                    for (int y = std::max(0, cy - h); y < std::min(ny, cy + h); ++y)
+                        for (int z = 0; z < nz; ++z) vox[((size_t)x * ny + y) * nz + z] |= 1;
+            }
+            const vigo::SeedByteGrid occ{vox.data(), nx, ny, nz, {-4.0, -4.0, 0.0}, 0.1};
+            const int W = 2 + trial % 4;
+            std::vector<pose> path;
+            for (int i = 0; i < W; ++i) path.push_back(pose(-3.5 + 7.0 * i / (W - 1) + 0.2 * U(rng), 3.0 * U(rng), 1.0 + 0.3 * U(rng)));
+            polyTrajSolver s(7, 4, 4, 1.0);
+            s.updatePath(path);
+            if (!s.solve()) { ++fails; continue; }
+            std::vector<double> cf((size_t)(W - 1) * 3 * 8);
+            for (int sg = 0; sg < W - 1; ++sg)
+                for (int ax = 0; ax < 3; ++ax)
+                    for (int d = 0; d < 8; ++d) cf[((size_t)sg * 3 + ax) * 8 + d] = s.getSolution(ax)[(size_t)sg * 8 + d];
+            std::vector<double> knots = s.timeKnots();
+            const int caps[3] = {vigo::kSeedCapacity, 40, 7}, pcaps[3] = {128, 12, 0};
+            for (int variant = 0; variant < 12; ++variant) {
+                // variants 0-5: full size, the search run out (thin, fill and the head are reached); 6-8: a capacity or a
+                // point_cap that does not hold the lists; 9-11: hostile inputs at full size
+                const int cap = variant >= 6 && variant < 9 ? caps[variant - 5 < 3 ? variant - 5 : 2] : caps[0];
+                const int pcap = variant >= 6 && variant < 9 ? pcaps[variant - 6] : pcaps[0];
+                vigo::SeedIn in;
+                in.K = W - 1; in.deg = 7; in.knots = knots.data(); in.coeffs = cf.data();
+                in.duration = knots.back(); in.dt0 = 0.25; in.control_point_distance = 0.25;
+                in.max_path_length = variant & 1 ? 2.0 : 1000.0; in.prev_seed = variant & 2 ? 3.0 : 0.0; in.prev_fit = variant & 4 ? 2.5 : 0.0;
+                in.max_tries = variant < 6 ? 16 : 1 + variant; in.point_cap = pcap;
+                std::vector<double> kn2;
+                if (variant == 9) { kn2 = knots; kn2[1] = std::nan(""); in.knots = kn2.data(); }
+                if (variant == 10) in.dt0 = -1.0;
+                if (variant == 11) { in.duration = 1e18; in.dt0 = 1.0; }
+                std::vector<double> pts(3 * ((size_t)cap + 1)), step((size_t)cap), dist((size_t)cap), seed(3 * (size_t)pcap + 3), fit(3 * (size_t)pcap + 3);
+                std::vector<uint8_t> line((size_t)cap);
+                for (int mode = 0; mode < 2; ++mode) {
+                    vigo::SeedOut o;
+                    if (mode == 0) vigo::seed_one(in, occ, 0.1, vigo::SeedPowExact{}, cap, pts.data(), step.data(), dist.data(), line.data(), &o, seed.data(), fit.data());
+                    else vigo::seed_one(in, occ, 0.1, vigo::SeedPowLibm{}, cap, pts.data(), step.data(), dist.data(), line.data(), &o, seed.data(), fit.data());
+                    ++ran;
+                    if (o.status < vigo::kSeedOk || o.status > vigo::kSeedBadInput || o.seed_n > pcap || o.fit_n > pcap) ++fails;
+                    if (variant >= 9 && o.status != vigo::kSeedBadInput) ++fails;
+                    if (o.status == vigo::kSeedOk) { ++okc; if (o.fit_n < 4 || o.seed_n < 2) ++fails; }
+                    if (o.status == vigo::kSeedDeferred) ++deferred;
+                }
+            }
+        }
+        std::printf("seed paths: %ld runs, %ld ok, %ld deferred\n", ran, okc, deferred);
+        if (okc < ran / 4 || deferred == 0) ++fails;
     }
     std::printf("%s\n", fails ? "FAILED" : "sanitizer run complete, no failures");
     return fails;

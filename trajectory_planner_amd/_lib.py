@@ -86,6 +86,9 @@ PROTOTYPES = {
     "vigo_box_collision_points": (_i, [_vp, _i64, _vp, _d3, _d, _vp]),
     "vigo_traj_corridor_check": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d3, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vigo_traj_point_check": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vigo_seed_capacity": (_i, [C.POINTER(C.c_int32)]),
+    "vigo_seed_paths": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [_i, _i] + [_vp] * 10),
+    "vigo_seed_paths_host": (_i, [_i, _i, _i, _d3, _d, _vp, _i, _i, _i, _i, _i] + [_vp] * 9 + [_i, _i] + [_vp] * 10),
     "vigo_astar_search": (_i, [_vp, _i, _vp, _vp, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _vp, _vp, _vp, _vp]),
     "vigo_astar_capacity": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vigo_guide_assign": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -11,6 +11,7 @@
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_handle.hpp"
+#include "vigo_seed_core.hpp"
 #include "vigo_solver_plan.hpp"
 #include "vigo_traj_runs.hpp"
 #include "vigo_ws_layout.hpp"
@@ -736,6 +737,95 @@ int vigo_traj_point_check(vigo_handle_t h, int T, int S, int deg, const int32_t*
     VIGO_TRY(traj_scratch(h, T, S, &chunk));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_point(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, delT, endpoint, out_status,
                                                     out_n, out_flag, out_first, out_count, out_seg, h->buf[vigo::kBufScratch].ptr, chunk));
+    return VIGO_OK;
+}
+
+/* ---- seed paths (vigo_seed_core.hpp) ------------------------------------------------------ */
+
+namespace {
+bool seed_args_ok(int T, int S, int deg, const int32_t* seg_off, const double* coeffs, const double* knots, const double* duration,
+                  const double* dt0, const double* cpd, const double* max_len, const double* prev_seed, const double* prev_fit,
+                  int max_tries, int point_cap, const int32_t* out_status, const int32_t* out_tries, const double* out_dt,
+                  const double* out_final_time, const int32_t* out_seed_n, const double* out_seed, const int32_t* out_fit_n,
+                  const double* out_fit, const double* out_prev_seed, const double* out_prev_fit) {
+    if (T < 0 || S < 0 || deg < 0 || deg > vigo::kSeedMaxDeg || max_tries < 1 || point_cap < 0) return false;
+    if (T > 0 && (!seg_off || !knots || !duration || !dt0 || !cpd || !max_len || !prev_seed || !prev_fit || !out_status || !out_tries ||
+                  !out_dt || !out_final_time || !out_seed_n || !out_fit_n || !out_prev_seed || !out_prev_fit))
+        return false;
+    if (T > 0 && point_cap > 0 && (!out_seed || !out_fit)) return false;
+    return !(T > 0 && S > 0 && !coeffs);
+}
+}  // namespace
+
+int vigo_seed_capacity(int32_t* max_samples) {
+    if (!max_samples) return VIGO_ERR_INVALID_ARG;
+    *max_samples = vigo::kSeedCapacity;
+    return VIGO_OK;
+}
+
+int vigo_seed_paths(vigo_handle_t h, int T, int S, int deg, const int32_t* seg_off, const double* coeffs, const double* knots,
+                    const double* duration, const double* dt0, const double* control_point_distance,
+                    const double* max_path_length, const double* prev_in_seed, const double* prev_in_fit, int max_tries,
+                    int point_cap, int32_t* out_status, int32_t* out_tries, double* out_dt, double* out_final_time,
+                    int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit, double* out_prev_seed,
+                    double* out_prev_fit) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (!seed_args_ok(T, S, deg, seg_off, coeffs, knots, duration, dt0, control_point_distance, max_path_length, prev_in_seed, prev_in_fit,
+                      max_tries, point_cap, out_status, out_tries, out_dt, out_final_time, out_seed_n, out_seed, out_fit_n, out_fit,
+                      out_prev_seed, out_prev_fit))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_seed_paths: bad argument");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_seed_paths before vigo_set_grid");
+    if (T == 0) return VIGO_OK;
+    VIGO_HIP(h, (hipError_t)vigo::launch_seed_paths(h->stream, h->grid, T, S, deg, seg_off, coeffs, knots, duration, dt0,
+                                                    control_point_distance, max_path_length, prev_in_seed, prev_in_fit, max_tries,
+                                                    point_cap, out_status, out_tries, out_dt, out_final_time, out_seed_n, out_seed,
+                                                    out_fit_n, out_fit, out_prev_seed, out_prev_fit));
+    return VIGO_OK;
+}
+
+int vigo_seed_paths_host(int nx, int ny, int nz, const double origin[3], double res, const uint8_t* voxels_host, int pow_mode,
+                         int cap, int T, int S, int deg, const int32_t* seg_off, const double* coeffs, const double* knots,
+                         const double* duration, const double* dt0, const double* control_point_distance,
+                         const double* max_path_length, const double* prev_in_seed, const double* prev_in_fit, int max_tries,
+                         int point_cap, int32_t* out_status, int32_t* out_tries, double* out_dt, double* out_final_time,
+                         int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit, double* out_prev_seed,
+                         double* out_prev_fit) {
+    if (nx < 1 || ny < 1 || nz < 1 || !origin || !voxels_host || !(res > 0) || !vigo::seed_finite(res) || (pow_mode != 0 && pow_mode != 1) ||
+        !seed_args_ok(T, S, deg, seg_off, coeffs, knots, duration, dt0, control_point_distance, max_path_length, prev_in_seed, prev_in_fit,
+                      max_tries, point_cap, out_status, out_tries, out_dt, out_final_time, out_seed_n, out_seed, out_fit_n, out_fit,
+                      out_prev_seed, out_prev_fit))
+        return VIGO_ERR_INVALID_ARG;
+    if (cap <= 0) cap = vigo::kSeedCapacity;
+    const vigo::SeedByteGrid occ{voxels_host, nx, ny, nz, {origin[0], origin[1], origin[2]}, res};
+    std::vector<double> pts(3 * ((size_t)cap + 1)), step((size_t)cap), dist((size_t)cap), seed(3 * (size_t)point_cap + 3), fit(3 * (size_t)point_cap + 3);
+    std::vector<uint8_t> line((size_t)cap);
+    for (int t = 0; t < T; ++t) {
+        const int a = seg_off[t], b = seg_off[t + 1];
+        if (a < 0 || b < a || b > S) {
+            out_status[t] = vigo::kSeedBadInput;
+            out_tries[t] = 0; out_dt[t] = dt0[t]; out_final_time[t] = 0.0; out_seed_n[t] = 0; out_fit_n[t] = 0;
+            out_prev_seed[t] = prev_in_seed[t]; out_prev_fit[t] = prev_in_fit[t];
+            continue;
+        }
+        vigo::SeedIn in;
+        in.K = b - a; in.deg = deg;
+        in.knots = knots + (size_t)a + t;
+        in.coeffs = coeffs + (size_t)a * 3 * (deg + 1);
+        in.duration = duration[t]; in.dt0 = dt0[t];
+        in.control_point_distance = control_point_distance[t]; in.max_path_length = max_path_length[t];
+        in.prev_seed = prev_in_seed[t]; in.prev_fit = prev_in_fit[t];
+        in.max_tries = max_tries; in.point_cap = point_cap;
+        vigo::SeedOut o;
+        if (pow_mode == 0) vigo::seed_one(in, occ, res, vigo::SeedPowExact{}, cap, pts.data(), step.data(), dist.data(), line.data(), &o, seed.data(), fit.data());
+        else vigo::seed_one(in, occ, res, vigo::SeedPowLibm{}, cap, pts.data(), step.data(), dist.data(), line.data(), &o, seed.data(), fit.data());
+        out_status[t] = o.status;
+        if (o.status == vigo::kSeedDeferred) continue;
+        out_tries[t] = o.tries; out_dt[t] = o.dt; out_final_time[t] = o.final_time;
+        out_seed_n[t] = o.seed_n; out_fit_n[t] = o.fit_n;
+        out_prev_seed[t] = o.prev_seed; out_prev_fit[t] = o.prev_fit;
+        if (o.seed_n > 0) memcpy(out_seed + (size_t)t * point_cap * 3, seed.data(), sizeof(double) * 3 * (size_t)o.seed_n);
+        if (o.fit_n > 0) memcpy(out_fit + (size_t)t * point_cap * 3, fit.data(), sizeof(double) * 3 * (size_t)o.fit_n);
+    }
     return VIGO_OK;
 }
 

@@ -141,6 +141,13 @@ int launch_traj_corridor(hipStream_t s, const GridView& g, int T, int S, int deg
 int launch_traj_point(hipStream_t s, const GridView& g, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
                       const double* knots, const double* delT, const double* endpoint, int32_t* out_status, int32_t* out_n,
                       uint8_t* out_flag, int32_t* out_first, int32_t* out_count, uint8_t* out_seg, void* ws, int T_chunk);
+// the seed-path stage (vigo_seed_paths, vigo_seed.hip): a wave per trajectory, no workspace
+int launch_seed_paths(hipStream_t s, const GridView& g, int T, int S, int deg, const int32_t* seg_off, const double* coeffs,
+                      const double* knots, const double* duration, const double* dt0, const double* control_point_distance,
+                      const double* max_path_length, const double* prev_in_seed, const double* prev_in_fit, int max_tries,
+                      int point_cap, int32_t* out_status, int32_t* out_tries, double* out_dt, double* out_final_time,
+                      int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit, double* out_prev_seed,
+                      double* out_prev_fit);
 int launch_box_points(hipStream_t s, const GridView& g, int64_t M, const double* pts, const double box[3],
                       double map_res, uint8_t* out);
 // polyTrajSolver::getTrajectory for S segments: sample k of segment s at out[(s * stride + k) * 3] (fp64 and/or float)

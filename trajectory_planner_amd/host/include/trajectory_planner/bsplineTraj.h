@@ -39,6 +39,8 @@ struct optData {
     std::vector<Eigen::Vector3d> dynamicObstaclesSize;
 };
 
+class polyTrajOccMap;
+
 class bsplineTraj {
 private:
     ros::NodeHandle nh_;
@@ -183,6 +185,44 @@ public:
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
+    /* not in the reference: the seed-path stage of bspline_node's replan step (src/bspline_node.cpp:317-378) and
+     * updatePath for many planners at once — polys[i]'s plan sampled by getTrajectory(dt) from dt = getInitTs(), the
+     * inputPathCheck search (dt *= 0.8 per failed try, at most seedMaxTries() tries instead of the reference's 50 ms),
+     * then updatePath(seed, startEndConditions[i]).  Returns updatePath's verdicts; seeds[i], when given, receives
+     * adjustedInputPolyTraj (empty when no try passed), info[i] the search's outcome.  Same results as one planner after
+     * another in the reference's order: every planner's search, then every planner's updatePath.
+     * setDeviceSeed(false), the default: the searches and updatePath's head run on the host workers.  true: ONE
+     * vigo_seed_paths launch per device group and one download; a trajectory the launch defers or refuses, a poly
+     * planner flying its PWL fallback or without a polynomial, and a planner without a map snapshot take the host steps.
+     * The kernels' power is the correctly rounded one; libm's is that value or its neighbour (csrc/vigo_exact_pow.hpp;
+     * the rate is counted by tools/pow_rounding_rate.py): the seeds agree to that.  The fits run as updatePathBatch's, one vigo_bspline_fit launch per point count. */
+    struct SeedInfo {
+        bool found = false;      /* a try passed inputPathCheck */
+        int tries = 0;
+        double dt = 0.0, finalTime = 0.0;
+        bool wrote = false;      /* (internal) the search reached adjustPathLengthDirect; prevOut: what it left there */
+        double prevOut = 0.0;
+    };
+    static std::vector<bool> seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
+                                           const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
+                                           std::vector<nav_msgs::Path>* seeds = nullptr, std::vector<SeedInfo>* info = nullptr);
+    static void setDeviceSeed(bool on);
+    static bool deviceSeed();
+    static void setSeedMaxTries(int n);   /* default 16: dt has shrunk to 2.8 % of getInitTs() by then */
+    static int seedMaxTries();
+    /* Process-wide running totals: the planners whose seed and fit points vigo_seed_paths produced / the host steps did */
+    static void deviceSeedTotals(long long* deviceDecided, long long* hostRun);
+    /* added (tests, cabi_host.cpp: vigo_host_seed_steps): one planner's host steps of that stage with the previous path
+     * lengths passed in and out — the search from dt0, then updatePath's head on its seed */
+    struct SeedSteps {
+        SeedInfo search;
+        nav_msgs::Path seed;
+        bool fitOk = false, fitWrote = false;
+        double prevFitOut = 0.0;
+        std::vector<Eigen::Vector3d> fitPoints;
+    };
+    void seedSteps(polyTrajOccMap& poly, double dt0, int maxTries, double prevSeedIn, double prevFitIn, SeedSteps& out);
+    double getMaxPathLength() const { return maxPathLength_; }
     void clear();
     void findCollisionSeg(const Eigen::MatrixXd& controlPoints, std::vector<std::pair<int, int>>& collisionSeg);
     bool pathSearch(std::vector<std::pair<int, int>>& collisionSeg, std::vector<std::vector<Eigen::Vector3d>>& paths);
@@ -263,6 +303,18 @@ private:
     bool prepareFitPointsWith(const nav_msgs::Path& adjustedPath, std::vector<Eigen::Vector3d>& adjustedCurveFitPoints, double prevIn,
                               double& prevOut, bool& wrote);
     void adjustPathLengthWith(const std::vector<Eigen::Vector3d>& path, std::vector<Eigen::Vector3d>& adjustedPath, double prevIn, double& prevOut);
+    bool inputPathCheckWith(const nav_msgs::Path& path, nav_msgs::Path& adjustedPath, double dt, double& finalTime, double prevIn,
+                            double& prevOut, bool& wrote);
+    /* the inputPathCheck search of one planner: getTrajectory(dt) from dt0, dt *= 0.8 per failed try */
+    void seedSearchWith(polyTrajOccMap& poly, double dt0, int maxTries, double prevIn, SeedInfo& s, nav_msgs::Path& seed);
+    /* the launch of seedPathBatch under setDeviceSeed(true): fills the entries of the planners it decided (onDevice) */
+    struct SeedBatch;
+    static void seedOnDevice(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys, SeedBatch& sb);
+    /* the fit stage of updatePathBatch / seedPathBatch: one vigo_bspline_fit launch per group of equal point count and
+     * device target among the ready planners, control points installed; ok[i] set for the fitted ones */
+    static void fitGroups(const std::vector<bsplineTraj*>& planners, const std::vector<std::vector<Eigen::Vector3d>>& fitPts,
+                          const std::vector<bool>& ready, const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
+                          std::vector<bool>& ok);
     void installControlPoints(const Eigen::MatrixXd& controlPoints, const std::vector<Eigen::Vector3d>& adjustedCurveFitPoints);
     bool termCost(int term, const Eigen::MatrixXd& controlPoints, double& cost, Eigen::MatrixXd& gradient);
     void reboundFinish(Rebound& r, bool ok);

@@ -161,6 +161,10 @@ public:
     void adjustCorridorSize(const std::set<int>& collisionSeg, std::vector<double>& corridorSizeVec);
     void trajMsgConverter(const std::vector<pose>& trajectoryTemp, nav_msgs::Path& trajectory);
 
+    /* not in the reference (bsplineTraj::seedPathBatch): the polynomial getTrajectory / getPos sample — NULL before the
+     * first plan — and whether they fly the PWL fallback's duration instead of its own (use_pwl_failsafe and no valid plan) */
+    const polyTrajSolver* getSolver() const { return trajSolver_.get(); }
+    bool usesPwlFallback() const { return usePWL_ && !findValidTraj_; }
     /* not in the reference: the verdict and the QP solves of the last makePlan */
     bool isValid() const { return findValidTraj_; }
     int getIterations() const { return lastIterations_; }

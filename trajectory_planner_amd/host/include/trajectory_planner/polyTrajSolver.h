@@ -79,6 +79,7 @@ public:
     Eigen::Vector3d getAcc(double t);   /* PS.h:137 — the x component with the reference's exponent, see the .cpp */
     void getTrajectory(std::vector<pose>& trajectory, double delT);
     std::vector<double>& getTimeKnot();
+    const std::vector<double>& timeKnots() const { return desiredTime_; }   /* added: the same, of a const solver */
     const std::vector<double>& getSolution(int axis) const { return axis == 0 ? xSol_ : (axis == 1 ? ySol_ : zSol_); }
     int getPolyDegree() const { return polyDegree_; }
     void getCorridor(std::vector<std::vector<std::pair<double, pose>>>& segToTimePose, std::vector<double>& corridorSizeVec) const;

@@ -4,6 +4,7 @@
 // the numerics of optimize(), the collision gates and isUnknown(guide) run in libvigo_hip.so
 // through the C ABI of include/vigo.h.  Own implementation: host bookkeeping only.
 #include <trajectory_planner/bsplineTraj.h>
+#include <trajectory_planner/polyTrajOccMap.h>
 
 #include <hip/hip_runtime_api.h>
 
@@ -193,10 +194,23 @@ bool bsplineTraj::syncDevice() {
 
 // BT.cpp:207-245
 bool bsplineTraj::inputPathCheck(const nav_msgs::Path& path, nav_msgs::Path& adjustedPath, double dt, double& finalTime) {
+    bool wrote = false;
+    double prevOut = 0.0;
+    const bool ok = this->inputPathCheckWith(path, adjustedPath, dt, finalTime, g_prevPathLength.load(), prevOut, wrote);
+    if (wrote) g_prevPathLength.store(prevOut);
+    return ok;
+}
+
+// the same with the previous path length passed in and out (wrote: the call reached adjustPathLengthDirect)
+bool bsplineTraj::inputPathCheckWith(const nav_msgs::Path& path, nav_msgs::Path& adjustedPath, double dt, double& finalTime, double prevIn,
+                                     double& prevOut, bool& wrote) {
+    wrote = false;
+    prevOut = prevIn;
     if (path.poses.size() == 0) return true;
     std::vector<Eigen::Vector3d> curveFitPoints, adjustedCurveFitPoints;
     this->pathMsgToEigenPoints(path, curveFitPoints);
-    this->adjustPathLengthDirect(curveFitPoints, adjustedCurveFitPoints);
+    this->adjustPathLengthWith(curveFitPoints, adjustedCurveFitPoints, prevIn, prevOut);
+    wrote = true;
     for (size_t i = 0; i + 1 < adjustedCurveFitPoints.size(); ++i) {
         double dist = (adjustedCurveFitPoints[i] - adjustedCurveFitPoints[i + 1]).norm();
         if (dist > this->controlPointDistance_ * 1.5) return false;
@@ -336,8 +350,18 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
         ready[i] = okv[i] && fitPts[i].size() > 3;
     }
     g_prevPathLength.store(prev);
+    fitGroups(planners, fitPts, ready, startEndConditions, ok);
+    return ok;
+}
+
+// The fit stage of updatePathBatch and seedPathBatch: ONE vigo_bspline_fit launch per group of ready planners with equal
+// point count and knot span, the control points installed (BT.cpp:315-322).
+void bsplineTraj::fitGroups(const std::vector<bsplineTraj*>& planners, const std::vector<std::vector<Eigen::Vector3d>>& fitPts,
+                            const std::vector<bool>& ready, const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
+                            std::vector<bool>& ok) {
     auto sameFit = [&](size_t a, size_t b) {
-        return ready[a] && ready[b] && fitPts[a].size() == fitPts[b].size() && planners[a]->controlPointsTs_ == planners[b]->controlPointsTs_;
+        return ready[a] && ready[b] && fitPts[a].size() == fitPts[b].size() && planners[a]->controlPointsTs_ == planners[b]->controlPointsTs_ &&
+               planners[a]->link_.sameTarget(planners[b]->link_);   // the fit runs on the lead's handle: a lead without a device fails its own group only
     };
     vigo_host::forEachGroup(planners.size(), sameFit, [&](const std::vector<size_t>& grp) {
         bsplineTraj* lead = planners[grp[0]];
@@ -367,6 +391,213 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
         });
         for (int b = 0; b < B; ++b) ok[grp[b]] = true;
     });
+}
+
+// ---- the seed-path stage for many planners (bspline_node.cpp:317-378): seedPathBatch -------------------------------
+namespace {
+std::atomic<bool> g_deviceSeed{false};
+std::atomic<int> g_seedMaxTries{16};
+std::atomic<long long> g_seedDevice{0}, g_seedHost{0};
+constexpr int kSeedPointCap = 128;   // rows of the launch's seed / fit outputs per planner; a longer list is the host's
+}  // namespace
+
+void bsplineTraj::setDeviceSeed(bool on) { g_deviceSeed.store(on); }
+bool bsplineTraj::deviceSeed() { return g_deviceSeed.load(); }
+void bsplineTraj::setSeedMaxTries(int n) { g_seedMaxTries.store(n < 1 ? 1 : n); }
+int bsplineTraj::seedMaxTries() { return g_seedMaxTries.load(); }
+void bsplineTraj::deviceSeedTotals(long long* deviceDecided, long long* hostRun) {
+    if (deviceDecided) *deviceDecided = g_seedDevice.load();
+    if (hostRun) *hostRun = g_seedHost.load();
+}
+
+// bspline_node.cpp:338-352 for one planner, the loop ending on the try count
+void bsplineTraj::seedSearchWith(polyTrajOccMap& poly, double dt0, int maxTries, double prevIn, SeedInfo& s, nav_msgs::Path& seed) {
+    s = SeedInfo();
+    s.dt = dt0;
+    seed.poses.clear();
+    double prev = prevIn;
+    for (int k = 0; k < maxTries; ++k) {
+        ++s.tries;
+        const nav_msgs::Path input = poly.getTrajectory(s.dt);
+        bool wrote = false;
+        double prevOut = prev;
+        const bool ok = this->inputPathCheckWith(input, seed, s.dt, s.finalTime, prev, prevOut, wrote);
+        if (wrote) {
+            prev = prevOut;
+            s.wrote = true;
+        }
+        if (ok) {
+            s.found = true;
+            break;
+        }
+        s.dt *= 0.8;
+    }
+    s.prevOut = prev;
+}
+
+void bsplineTraj::seedSteps(polyTrajOccMap& poly, double dt0, int maxTries, double prevSeedIn, double prevFitIn, SeedSteps& out) {
+    out = SeedSteps();
+    this->seedSearchWith(poly, dt0, maxTries, prevSeedIn, out.search, out.seed);
+    out.fitOk = this->prepareFitPointsWith(out.seed, out.fitPoints, prevFitIn, out.prevFitOut, out.fitWrote);
+}
+
+// what seedPathBatch keeps per planner between its passes
+struct bsplineTraj::SeedBatch {
+    int maxTries;
+    std::vector<nav_msgs::Path> seed;
+    std::vector<SeedInfo> info;
+    std::vector<std::vector<Eigen::Vector3d>> fitPts;
+    std::vector<uint8_t> eligible, onDevice, okv, wroteFit;
+    std::vector<double> prevFitOut;
+    explicit SeedBatch(size_t n, int tries)
+        : maxTries(tries), seed(n), info(n), fitPts(n), eligible(n, 0), onDevice(n, 0), okv(n, 0), wroteFit(n, 0), prevFitOut(n, 0.0) {}
+};
+
+// ONE vigo_seed_paths launch per group of eligible planners that share a device batch and a polynomial degree, as if
+// every predecessor had left a previous path length of 0; one upload, one download.  A trajectory the launch defers or
+// refuses stays with the host steps.
+void bsplineTraj::seedOnDevice(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys, SeedBatch& sb) {
+    auto same = [&](size_t a, size_t b) {
+        return sb.eligible[a] && sb.eligible[b] && planners[a]->sameBatchKey(*planners[b]) &&
+               polys[a]->getSolver()->getPolyDegree() == polys[b]->getSolver()->getPolyDegree();
+    };
+    vigo_host::forEachGroup(planners.size(), same, [&](const std::vector<size_t>& grp) {
+        bsplineTraj* lead = planners[grp[0]];
+        const int deg = polys[grp[0]]->getSolver()->getPolyDegree();
+        if (deg < 0 || deg > 15 || !lead->syncDevice()) return;
+        const int T = (int)grp.size(), cap = kSeedPointCap;
+        std::vector<int32_t> segOff(1, 0);
+        for (size_t i : grp) segOff.push_back(segOff.back() + (int32_t)polys[i]->getSolver()->timeKnots().size() - 1);
+        const int S = segOff.back();
+        // the inputs as one block: per-trajectory scalars [6][T], knots [S + T], coefficients [S][3][deg + 1], offsets
+        const size_t nD = 6 * (size_t)T + (size_t)S + T + (size_t)S * 3 * (deg + 1);
+        std::vector<double> in(nD + (segOff.size() + 1) / 2);
+        double *duration = in.data(), *dt0 = duration + T, *cpd = dt0 + T, *maxLen = cpd + T, *prevSeed = maxLen + T, *prevFit = prevSeed + T;
+        double *knots = prevFit + T, *coeffs = knots + S + T;
+        std::memcpy(in.data() + nD, segOff.data(), segOff.size() * sizeof(int32_t));
+        for (int b = 0; b < T; ++b) {
+            bsplineTraj* p = planners[grp[b]];
+            const polyTrajSolver* sol = polys[grp[b]]->getSolver();
+            duration[b] = polys[grp[b]]->getDuration();
+            dt0[b] = p->getInitTs();
+            cpd[b] = p->controlPointDistance_;
+            maxLen[b] = p->maxPathLength_;
+            prevSeed[b] = 0.0;
+            prevFit[b] = 0.0;
+            const std::vector<double>& k = sol->timeKnots();
+            std::copy(k.begin(), k.end(), knots + segOff[b] + b);
+            for (int sgm = 0; sgm < segOff[b + 1] - segOff[b]; ++sgm)
+                for (int ax = 0; ax < 3; ++ax)
+                    std::copy(sol->getSolution(ax).begin() + (size_t)sgm * (deg + 1), sol->getSolution(ax).begin() + (size_t)(sgm + 1) * (deg + 1),
+                              coeffs + ((size_t)(segOff[b] + sgm) * 3 + ax) * (deg + 1));
+        }
+        // the outputs as one block: [4][T] ints, [4][T] doubles, seed and fit points [T][cap][3] each
+        const size_t outBytes = 16 * (size_t)T + 32 * (size_t)T + 2 * (size_t)T * cap * 24;
+        std::vector<double> out(outBytes / 8);
+        static thread_local StagingBuf dIn, dOut;
+        if (!dIn.upload(in.data(), in.size() * 8) || !dOut.alloc(outBytes)) return;
+        const double* di = (const double*)dIn.p;
+        int32_t* oi = (int32_t*)dOut.p;
+        double* od = (double*)dOut.p + 2 * (size_t)T;
+        if (vigo_seed_paths(lead->link_.handle(), T, S, deg, (const int32_t*)(di + nD), di + 6 * (size_t)T + S + T, di + 6 * (size_t)T, di, di + T,
+                            di + 2 * (size_t)T, di + 3 * (size_t)T, di + 4 * (size_t)T, di + 5 * (size_t)T, sb.maxTries, cap, oi, oi + T, od, od + T,
+                            oi + 2 * (size_t)T, od + 4 * (size_t)T, oi + 3 * (size_t)T, od + 4 * (size_t)T + (size_t)T * cap * 3, od + 2 * (size_t)T,
+                            od + 3 * (size_t)T) != VIGO_OK) {
+            cout << "[BsplineTraj]: vigo_seed_paths failed: " << vigo_last_error(lead->link_.handle()) << endl;
+            return;
+        }
+        if (!vigo_host::threadSync() || !dOut.download(out.data(), outBytes)) return;
+        const int32_t *status = (const int32_t*)out.data(), *tries = status + T, *seedN = tries + T, *fitN = seedN + T;
+        const double *dt = out.data() + 2 * (size_t)T, *finalTime = dt + T, *prevSeedOut = finalTime + T, *prevFitOut = prevSeedOut + T;
+        const double *seedPts = prevFitOut + T, *fitPts = seedPts + (size_t)T * cap * 3;
+        parallelFor((size_t)T, [&](size_t b) {
+            const size_t i = grp[b];
+            if (status[b] == VIGO_SEED_DEFERRED || status[b] == VIGO_SEED_BAD_INPUT) return;
+            SeedInfo& s = sb.info[i];
+            s = SeedInfo();
+            s.found = status[b] != VIGO_SEED_NO_SPACING;
+            s.tries = tries[b];
+            s.dt = dt[b];
+            s.finalTime = finalTime[b];
+            s.wrote = !(status[b] == VIGO_SEED_TOO_SHORT && seedN[b] == 0);
+            s.prevOut = prevSeedOut[b];
+            std::vector<Eigen::Vector3d> pts;
+            for (int q = 0; q < seedN[b]; ++q) {
+                const double* v = seedPts + ((size_t)b * cap + q) * 3;
+                pts.push_back(Eigen::Vector3d(v[0], v[1], v[2]));
+            }
+            sb.seed[i].poses.clear();
+            if (!pts.empty()) planners[i]->eigenPointsToPathMsg(pts, sb.seed[i]);
+            sb.fitPts[i].clear();
+            for (int q = 0; q < fitN[b]; ++q) {
+                const double* v = fitPts + ((size_t)b * cap + q) * 3;
+                sb.fitPts[i].push_back(Eigen::Vector3d(v[0], v[1], v[2]));
+            }
+            sb.okv[i] = status[b] == VIGO_SEED_OK ? 1 : 0;
+            sb.wroteFit[i] = sb.okv[i];
+            sb.prevFitOut[i] = prevFitOut[b];
+            sb.onDevice[i] = 1;
+        });
+    });
+}
+
+std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
+                                             const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
+                                             std::vector<nav_msgs::Path>* seeds, std::vector<SeedInfo>* info) {
+    const size_t n = planners.size();
+    std::vector<bool> ok(n, false);
+    if (polys.size() != n || startEndConditions.size() != n) return ok;
+    SeedBatch sb(n, g_seedMaxTries.load());
+    if (g_deviceSeed.load()) {
+        for (size_t i = 0; i < n; ++i) {
+            const polyTrajSolver* sol = polys[i]->getSolver();
+            sb.eligible[i] = startEndConditions[i].size() == 4 && planners[i]->link_.map() && sol && sol->hasSolution() &&
+                             !polys[i]->usesPwlFallback();
+        }
+        seedOnDevice(planners, polys, sb);
+    }
+    // The searches run as if every predecessor had left a previous path length not above the planner's own
+    // max_path_length — then the value does not enter (BT.cpp:762) — and a serial pass in the reference's order (every
+    // planner's search, then every planner's updatePath) hands the real value down and repeats, on the host and in
+    // order, the rare planner for which it does enter: updatePathBatch's scheme, over both phases.
+    parallelFor(n, [&](size_t i) {
+        if (!sb.onDevice[i]) planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.maxTries, 0.0, sb.info[i], sb.seed[i]);
+    });
+    double prev = g_prevPathLength.load();
+    std::vector<uint8_t> redone(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (sb.info[i].wrote && prev > planners[i]->maxPathLength_) {
+            planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.maxTries, prev, sb.info[i], sb.seed[i]);
+            redone[i] = 1;
+        }
+        if (sb.info[i].wrote) prev = sb.info[i].prevOut;
+    }
+    parallelFor(n, [&](size_t i) {
+        if ((sb.onDevice[i] && !redone[i]) || startEndConditions[i].size() != 4) return;
+        bool w = false;
+        sb.okv[i] = planners[i]->prepareFitPointsWith(sb.seed[i], sb.fitPts[i], 0.0, sb.prevFitOut[i], w) ? 1 : 0;
+        sb.wroteFit[i] = w ? 1 : 0;
+    });
+    std::vector<bool> ready(n, false);
+    for (size_t i = 0; i < n; ++i) {
+        if (startEndConditions[i].size() == 4 && sb.wroteFit[i] && prev > planners[i]->maxPathLength_) {
+            bool w = false;
+            sb.okv[i] = planners[i]->prepareFitPointsWith(sb.seed[i], sb.fitPts[i], prev, sb.prevFitOut[i], w) ? 1 : 0;
+            redone[i] = 1;
+        }
+        if (sb.wroteFit[i]) prev = sb.prevFitOut[i];
+        ready[i] = startEndConditions[i].size() == 4 && sb.okv[i] && sb.fitPts[i].size() > 3;
+        if (sb.onDevice[i] && !redone[i]) {
+            if (sb.okv[i]) planners[i]->clear();             // prepareFitPointsWith's clear() (BT.cpp:308), for the launch's own
+            g_seedDevice.fetch_add(1);
+        } else {
+            g_seedHost.fetch_add(1);
+        }
+    }
+    g_prevPathLength.store(prev);
+    fitGroups(planners, sb.fitPts, ready, startEndConditions, ok);
+    if (seeds) *seeds = sb.seed;
+    if (info) *info = sb.info;
     return ok;
 }
 

@@ -688,6 +688,253 @@ int vigo_host_occ_seed_chain(int nx, int ny, int nz, const double* origin, doubl
     return 0;
 }
 
+// The facade's own per-planner steps of the seed-path stage (bsplineTraj::seedSteps: getTrajectory(dt), the inputPathCheck
+// search ending on max_tries, prepareFitPointsWith) for P waypoint paths (wp_off CSR over wp) on one dense byte grid, each
+// polyTrajOccMap planned alone on the host with makePlan(false): no GPU.  poly_cfg[16] / bsp_cfg[6] as
+// vigo_host_occ_seed_chain; dt0[i] <= 0: getInitTs().  Per planner the polynomial the steps sampled — out_K segments,
+// out_knots[seg_cap + 1], out_coeffs[seg_cap][3][8] (vigo_traj_point_check's layout), out_duration, out_dt0 — and the
+// steps' results: out_flags[4] = found, tries, prepareFitPointsWith's verdict, whether it reached adjustPathLengthDirect;
+// out_vals[5] = dt, finalTime, previous path length after the search, after updatePath's head, control_point_distance;
+// the seed and the curve-fit points ([point_cap][3] rows each).  Returns 0, -1 for a bad argument, -2 when a list does
+// not fit its capacity.
+int vigo_host_seed_steps(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P, const int32_t* wp_off,
+                         const double* wp, const double* poly_cfg, const double* bsp_cfg, double max_path_length, const double* dt0,
+                         const double* prev_seed, const double* prev_fit, int max_tries, int seg_cap, int32_t* out_K, double* out_knots,
+                         double* out_coeffs, double* out_duration, double* out_dt0, int point_cap, int32_t* out_flags, double* out_vals,
+                         int32_t* out_seed_n, double* out_seed, int32_t* out_fit_n, double* out_fit) {
+    if (P < 0 || !wp_off || !wp || !poly_cfg || !bsp_cfg || !dt0 || !prev_seed || !prev_fit || max_tries < 1 || seg_cap < 1 || point_cap < 0 ||
+        !out_K || !out_knots || !out_coeffs || !out_duration || !out_dt0 || !out_flags || !out_vals || !out_seed_n || !out_seed || !out_fit_n || !out_fit)
+        return -1;
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    const double vel = std::isnan(poly_cfg[3]) ? 1.0 : poly_cfg[3], acc = std::isnan(poly_cfg[4]) ? 1.0 : poly_cfg[4];
+    ros::NodeHandle bnh;
+    setBsplineParams(bnh, bsp_cfg);
+    bnh.setParam("bspline_traj/max_path_length", max_path_length);
+    int rc = 0;
+    for (int i = 0; i < P; ++i) {
+        double c[16];
+        std::copy(poly_cfg, poly_cfg + 16, c);
+        c[14] = vel;
+        c[15] = acc;
+        const double zero[12] = {};
+        auto poly = makeOccPlanner(map, c, wp_off[i + 1] - wp_off[i], wp + 3 * (size_t)wp_off[i], zero);
+        poly->makePlan(false);
+        trajPlanner::bsplineTraj bsp(bnh);
+        bsp.setMap(map);
+        bsp.updateMaxVel(vel);
+        bsp.updateMaxAcc(acc);
+        const trajPlanner::polyTrajSolver* sol = poly->getSolver();
+        const int deg = sol ? sol->getPolyDegree() : 7;
+        const int K = sol && sol->hasSolution() ? (int)sol->timeKnots().size() - 1 : 0;
+        if (K > seg_cap || deg != 7) { rc = -2; out_K[i] = 0; continue; }
+        out_K[i] = K;
+        for (int k = 0; k <= K && K > 0; ++k) out_knots[(size_t)i * (seg_cap + 1) + k] = sol->timeKnots()[k];
+        for (int sg = 0; sg < K; ++sg)
+            for (int ax = 0; ax < 3; ++ax)
+                for (int d = 0; d < 8; ++d) out_coeffs[(((size_t)i * seg_cap + sg) * 3 + ax) * 8 + d] = sol->getSolution(ax)[(size_t)sg * 8 + d];
+        out_duration[i] = poly->getDuration();
+        out_dt0[i] = dt0[i] > 0.0 ? dt0[i] : bsp.getInitTs();
+        trajPlanner::bsplineTraj::SeedSteps st;
+        bsp.seedSteps(*poly, out_dt0[i], max_tries, prev_seed[i], prev_fit[i], st);
+        int32_t* f = out_flags + 4 * (size_t)i;
+        double* v = out_vals + 5 * (size_t)i;
+        f[0] = st.search.found ? 1 : 0; f[1] = st.search.tries; f[2] = st.fitOk ? 1 : 0; f[3] = st.fitWrote ? 1 : 0;
+        v[0] = st.search.dt; v[1] = st.search.finalTime; v[2] = st.search.prevOut; v[3] = st.prevFitOut; v[4] = bsp.getControlPointDist();
+        out_seed_n[i] = (int32_t)st.seed.poses.size();
+        out_fit_n[i] = (int32_t)st.fitPoints.size();
+        if (out_seed_n[i] > point_cap || out_fit_n[i] > point_cap) { rc = -2; continue; }
+        copyXyz(st.seed, point_cap, out_seed + (size_t)i * point_cap * 3);
+        for (int k = 0; k < out_fit_n[i]; ++k)
+            for (int a = 0; a < 3; ++a) out_fit[((size_t)i * point_cap + k) * 3 + a] = st.fitPoints[k](a);
+    }
+    return rc;
+}
+
+// bspline_node's per-click sequence for P start/goal pairs as vigo_host_occ_seed_chain, through the batched stage:
+// polyTrajOccMap::makePlanBatch(false), bsplineTraj::seedPathBatch under setDeviceSeed(device != 0) and makePlanBatch —
+// or, serial != 0, one planner after another in the reference's order with the public steps (every planner's
+// getTrajectory / inputPathCheck search ending on the try count, then every planner's updatePath and makePlan).
+// max_len[P]: each bsplineTraj's max_path_length; kind[P] (may be NULL): 0 plain, 1 the bsplineTraj is bound to a HIP
+// device that does not exist (no handle, no snapshot), 2 the polyTrajOccMap has use_pwl_failsafe set and is never
+// planned (it flies the PWL fallback's duration).  prev0: the previous path length the batch starts from.  Outputs
+// per pair: seed_out[seed_cap][3] with seed_n, seed_dt, seed_tries; status as vigo_host_occ_seed_chain; ctrl_n control
+// points in ctrl_out[ctrl_cap][3] as updatePath left them (before makePlan); totals[2]: the planners the launch /
+// the host steps decided; out_K / out_knots[seg_cap + 1] / out_coeffs[seg_cap][3][8] / out_duration (all four or none):
+// the polynomial each seed was sampled from, as vigo_host_seed_steps returns it.
+int vigo_host_seed_batch(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P, const double* se,
+                         const double* poly_cfg, const double* bsp_cfg, const double* max_len, const int32_t* kind, double prev0, int device,
+                         int serial, int max_tries, int seed_cap, double* seed_out, int32_t* seed_n, double* seed_dt, int32_t* seed_tries,
+                         int32_t* status, int ctrl_cap, double* ctrl_out, int32_t* ctrl_n, long long* totals, int seg_cap, int32_t* out_K,
+                         double* out_knots, double* out_coeffs, double* out_duration) {
+    if (P < 0 || !se || !poly_cfg || !bsp_cfg || !max_len || seed_cap < 0 || !seed_out || !seed_n || !seed_dt || !seed_tries || !status ||
+        ctrl_cap < 0 || !ctrl_out || !ctrl_n || max_tries < 1)
+        return -1;
+    using trajPlanner::bsplineTraj;
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    const double vel = std::isnan(poly_cfg[3]) ? 1.0 : poly_cfg[3], acc = std::isnan(poly_cfg[4]) ? 1.0 : poly_cfg[4];
+    const std::vector<Eigen::Vector3d> cond(4, Eigen::Vector3d(0, 0, 0));
+    std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> polys;
+    std::vector<std::unique_ptr<bsplineTraj>> bsps;
+    std::vector<trajPlanner::polyTrajOccMap*> pp, planned_polys;
+    std::vector<bsplineTraj*> bp;
+    for (int i = 0; i < P; ++i) {
+        const int k = kind ? kind[i] : 0;
+        double c[16];
+        std::copy(poly_cfg, poly_cfg + 16, c);
+        c[14] = vel;
+        c[15] = acc;
+        if (k == 2) c[13] = 1.0;   // use_pwl_failsafe
+        const double zero[12] = {};
+        polys.push_back(makeOccPlanner(map, c, 2, se + 6 * (size_t)i, zero));
+        pp.push_back(polys.back().get());
+        if (k != 2) planned_polys.push_back(pp.back());
+        ros::NodeHandle bnh;
+        setBsplineParams(bnh, bsp_cfg);
+        bnh.setParam("bspline_traj/max_path_length", max_len[i]);
+        bsps.emplace_back(new bsplineTraj(bnh));
+        bsps.back()->setMap(map);
+        bsps.back()->updateMaxVel(vel);
+        bsps.back()->updateMaxAcc(acc);
+        if (k == 1) bsps.back()->setDevice(63);
+        bp.push_back(bsps.back().get());
+    }
+    trajPlanner::polyTrajOccMap::makePlanBatch(planned_polys, false);
+    if (out_K && out_knots && out_coeffs && out_duration)
+        for (int i = 0; i < P; ++i) {
+            const trajPlanner::polyTrajSolver* sol = pp[i]->getSolver();
+            const int K = sol && sol->hasSolution() && sol->getPolyDegree() == 7 ? (int)sol->timeKnots().size() - 1 : 0;
+            if (K > seg_cap) return -2;
+            out_K[i] = K;
+            out_duration[i] = pp[i]->getDuration();
+            for (int k = 0; k <= K && K > 0; ++k) out_knots[(size_t)i * (seg_cap + 1) + k] = sol->timeKnots()[k];
+            for (int sg = 0; sg < K; ++sg)
+                for (int ax = 0; ax < 3; ++ax)
+                    for (int d = 0; d < 8; ++d) out_coeffs[(((size_t)i * seg_cap + sg) * 3 + ax) * 8 + d] = sol->getSolution(ax)[(size_t)sg * 8 + d];
+        }
+    // the previous path length is process-wide: a one-point path through adjustPathLengthDirect leaves 0 there, a second
+    // point prev0 away leaves prev0
+    {
+        std::vector<Eigen::Vector3d> two{Eigen::Vector3d(0, 0, 1), Eigen::Vector3d(prev0, 0, 1)}, out;
+        if (P > 0) bp[0]->adjustPathLengthDirect(two, out);
+    }
+    std::vector<nav_msgs::Path> seeds(P);
+    std::vector<bool> up(P, false), planned(P, false);
+    long long d0 = 0, h0 = 0, d1 = 0, h1 = 0;
+    bsplineTraj::deviceSeedTotals(&d0, &h0);
+    if (serial) {
+        for (int i = 0; i < P; ++i) {
+            double dt = bp[i]->getInitTs(), finalTime = 0.0;
+            int tries = 0;
+            while (tries < max_tries) {
+                ++tries;
+                const nav_msgs::Path input = pp[i]->getTrajectory(dt);
+                if (bp[i]->inputPathCheck(input, seeds[i], dt, finalTime)) break;
+                dt *= 0.8;
+            }
+            seed_dt[i] = dt;
+            seed_tries[i] = tries;
+        }
+        for (int i = 0; i < P; ++i) up[i] = bp[i]->updatePath(seeds[i], cond);
+    } else {
+        const bool was = bsplineTraj::deviceSeed();
+        const int wasTries = bsplineTraj::seedMaxTries();
+        bsplineTraj::setDeviceSeed(device != 0);
+        bsplineTraj::setSeedMaxTries(max_tries);
+        std::vector<bsplineTraj::SeedInfo> info;
+        up = bsplineTraj::seedPathBatch(bp, pp, std::vector<std::vector<Eigen::Vector3d>>(P, cond), &seeds, &info);
+        bsplineTraj::setDeviceSeed(was);
+        bsplineTraj::setSeedMaxTries(wasTries);
+        for (int i = 0; i < P; ++i) { seed_dt[i] = info[i].dt; seed_tries[i] = info[i].tries; }
+    }
+    bsplineTraj::deviceSeedTotals(&d1, &h1);
+    if (totals) { totals[0] = d1 - d0; totals[1] = h1 - h0; }
+    for (int i = 0; i < P; ++i) {
+        seed_n[i] = (int32_t)seeds[i].poses.size();
+        copyXyz(seeds[i], seed_cap, seed_out + (size_t)i * seed_cap * 3);
+        ctrl_n[i] = 0;
+        if (up[i]) {
+            const Eigen::MatrixXd c = bp[i]->getControlPoints();
+            ctrl_n[i] = (int32_t)c.cols();
+            for (int q = 0; q < c.cols() && q < ctrl_cap; ++q)
+                for (int a = 0; a < 3; ++a) ctrl_out[((size_t)i * ctrl_cap + q) * 3 + a] = c(a, q);
+        }
+    }
+    std::vector<bsplineTraj*> ready;
+    std::vector<int> idx;
+    for (int i = 0; i < P; ++i) if (up[i]) { ready.push_back(bp[i]); idx.push_back(i); }
+    const std::vector<bool> r = bsplineTraj::makePlanBatch(ready);
+    for (size_t k = 0; k < idx.size(); ++k) planned[idx[k]] = r[k];
+    for (int i = 0; i < P; ++i) status[i] = !up[i] ? 0 : planned[i] ? 2 : 1;
+    return 0;
+}
+
+// Wall time of the seed-path stage up to installed control points for P start/goal pairs (planners built and the min-snap
+// seeds planned once, before the clock): out_ms[reps][3], per repetition in this order
+//   0  what existed before seedPathBatch: the searches as a serial loop on the calling thread, then updatePathBatch
+//   1  seedPathBatch on the host workers (setDeviceSeed(false))
+//   2  seedPathBatch with the vigo_seed_paths launch (setDeviceSeed(true))
+// so that the three alternate.  totals[2]: the planners the launch / the host steps decided in the last repetition of 2.
+int vigo_host_seed_timing(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P, const double* se,
+                          const double* poly_cfg, const double* bsp_cfg, int max_tries, int reps, double* out_ms, long long* totals) {
+    if (P < 0 || !se || !poly_cfg || !bsp_cfg || max_tries < 1 || reps < 1 || !out_ms) return -1;
+    using trajPlanner::bsplineTraj;
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    const double vel = std::isnan(poly_cfg[3]) ? 1.0 : poly_cfg[3], acc = std::isnan(poly_cfg[4]) ? 1.0 : poly_cfg[4];
+    ros::NodeHandle bnh;
+    setBsplineParams(bnh, bsp_cfg);
+    bnh.setParam("bspline_traj/max_path_length", 1000.0);
+    const std::vector<std::vector<Eigen::Vector3d>> conds(P, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+    std::vector<std::unique_ptr<trajPlanner::polyTrajOccMap>> polys;
+    std::vector<std::unique_ptr<bsplineTraj>> bsps;
+    std::vector<trajPlanner::polyTrajOccMap*> pp;
+    std::vector<bsplineTraj*> bp;
+    for (int i = 0; i < P; ++i) {
+        double c[16];
+        std::copy(poly_cfg, poly_cfg + 16, c);
+        c[14] = vel;
+        c[15] = acc;
+        const double zero[12] = {};
+        polys.push_back(makeOccPlanner(map, c, 2, se + 6 * (size_t)i, zero));
+        pp.push_back(polys.back().get());
+        bsps.emplace_back(new bsplineTraj(bnh));
+        bsps.back()->setMap(map);
+        bsps.back()->updateMaxVel(vel);
+        bsps.back()->updateMaxAcc(acc);
+        bp.push_back(bsps.back().get());
+    }
+    trajPlanner::polyTrajOccMap::makePlanBatch(pp, false);
+    const bool was = bsplineTraj::deviceSeed();
+    const int wasTries = bsplineTraj::seedMaxTries();
+    bsplineTraj::setSeedMaxTries(max_tries);
+    for (int r = 0; r < reps; ++r)
+        for (int mode = 0; mode < 3; ++mode) {
+            long long d0 = 0, h0 = 0, d1 = 0, h1 = 0;
+            bsplineTraj::deviceSeedTotals(&d0, &h0);
+            const auto t0 = std::chrono::steady_clock::now();
+            if (mode == 0) {
+                std::vector<nav_msgs::Path> seeds(P);
+                for (int i = 0; i < P; ++i) {
+                    double dt = bp[i]->getInitTs(), finalTime = 0.0;
+                    for (int k = 0; k < max_tries; ++k) {
+                        const nav_msgs::Path input = pp[i]->getTrajectory(dt);
+                        if (bp[i]->inputPathCheck(input, seeds[i], dt, finalTime)) break;
+                        dt *= 0.8;
+                    }
+                }
+                (void)bsplineTraj::updatePathBatch(bp, seeds, conds);
+            } else {
+                bsplineTraj::setDeviceSeed(mode == 2);
+                (void)bsplineTraj::seedPathBatch(bp, pp, conds);
+            }
+            out_ms[3 * (size_t)r + mode] = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            bsplineTraj::deviceSeedTotals(&d1, &h1);
+            if (mode == 2 && totals) { totals[0] = d1 - d0; totals[1] = h1 - h0; }
+        }
+    bsplineTraj::setDeviceSeed(was);
+    bsplineTraj::setSeedMaxTries(wasTries);
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- the same prologue for MANY paths on ONE map (the workload generator of bench.py / tests: product code, no oracle) ----

@@ -20,6 +20,7 @@ ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_DEFERRED, ASTAR_PATH_TOO_LONG = 0, 1, 2, 3  
 GUIDE_OK, GUIDE_DEFERRED = 0, 1                                                  # vigo_guide_assign's out_status
 REGUIDE_DONE, REGUIDE_SEARCH_FAILED, REGUIDE_NOT_REQUIRED, REGUIDE_DEFERRED, REGUIDE_SKIPPED = 0, 1, 2, 3, 4   # vigo_rebound_reguide's out_status
 PATHS_OK, PATHS_FAILED, PATHS_DEFERRED = 0, 1, 2                                 # vigo_collision_segs' / vigo_path_search's out_status
+SEED_OK, SEED_NO_SPACING, SEED_GOAL_OCCUPIED, SEED_TOO_SHORT, SEED_DEFERRED, SEED_BAD_INPUT = 0, 1, 2, 3, 4, 5   # vigo_seed_paths' out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -440,6 +441,42 @@ class Vigo:
             C.c_void_p(flag.data_ptr()), C.c_void_p(first.data_ptr()), C.c_void_p(count.data_ptr()),
             C.c_void_p(seg.data_ptr())), "vigo_traj_point_check")
         return status, n, flag, first, count, seg
+
+    def seed_paths(self, seg_off, coeffs, knots, duration, dt0, control_point_distance, max_path_length, prev_in_seed=None,
+                   prev_in_fit=None, max_tries=16, point_cap=256):
+        """vigo_seed_paths: the seed-path stage between polyTrajOccMap and bsplineTraj for T trajectories.  seg_off [T+1]
+        i32, coeffs [S,3,deg+1] f64, knots [S+T] f64 as traj_point_check; duration, dt0, control_point_distance,
+        max_path_length, prev_in_seed, prev_in_fit [T] f64 (the prev arrays default to zeros) -> dict of status i32[T]
+        (SEED_*), tries i32[T], dt f64[T], final_time f64[T], seed_n i32[T], seed f64[T,point_cap,3], fit_n i32[T],
+        fit f64[T,point_cap,3], prev_seed f64[T], prev_fit f64[T].  Outputs start zeroed: a SEED_DEFERRED trajectory
+        keeps zeros."""
+        _shape(seg_off, (None,), "seg_off")
+        T = seg_off.shape[0] - 1
+        if T < 0:
+            raise ValueError("seg_off: needs T + 1 >= 1 entries")
+        _shape(coeffs, (None, 3, None), "coeffs")
+        S, _, d1 = coeffs.shape
+        _shape(knots, (S + T,), "knots")
+        d = self.device
+        if prev_in_seed is None:
+            prev_in_seed = torch.zeros(T, dtype=torch.float64, device=d)
+        if prev_in_fit is None:
+            prev_in_fit = torch.zeros(T, dtype=torch.float64, device=d)
+        per = {"duration": duration, "dt0": dt0, "control_point_distance": control_point_distance,
+               "max_path_length": max_path_length, "prev_in_seed": prev_in_seed, "prev_in_fit": prev_in_fit}
+        for name, a in per.items():
+            _shape(a, (T,), name)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=d)
+        f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=d)
+        out = {"status": i32(T), "tries": i32(T), "dt": f64(T), "final_time": f64(T), "seed_n": i32(T),
+               "seed": f64(T, point_cap, 3), "fit_n": i32(T), "fit": f64(T, point_cap, 3), "prev_seed": f64(T), "prev_fit": f64(T)}
+        self._check(self._lib.vigo_seed_paths(
+            self._h, T, S, d1 - 1, _ptr(seg_off, torch.int32, "seg_off", d), _ptr(coeffs, torch.float64, "coeffs", d),
+            _ptr(knots, torch.float64, "knots", d), *[_ptr(a, torch.float64, name, d) for name, a in per.items()],
+            int(max_tries), int(point_cap), *[C.c_void_p(out[k].data_ptr()) for k in
+                                              ("status", "tries", "dt", "final_time", "seed_n", "seed", "fit_n", "fit", "prev_seed", "prev_fit")]),
+            "vigo_seed_paths")
+        return out
 
     def astar_search(self, start, end, step, pool, min_height, max_height, max_expansions=1 << 20, path_cap=256, want_stats=True):
         """vigo_astar_search: Q searches of the facade's host A* on the handle's grid -> (status int32 [Q], len int32 [Q],
