@@ -8,11 +8,11 @@ cd "$(dirname "$0")/../trajectory_planner_amd/host"
 g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -o /tmp/vigo_san_test \
     ../../tools/sanitize_host_main.cpp src/octomapBt.cpp src/polyTrajSolver.cpp src/bspline.cpp src/astarOcc.cpp src/piecewiseLinearTraj.cpp
 /tmp/vigo_san_test "$@"
-# the facade's own steps of the seed-path stage (bsplineTraj.cpp needs the HIP headers and links libvigo_hip.so, built
+# the facade's own steps of the seed-path stage (bsplineTraj's sources need the HIP headers and link libvigo_hip.so, built
 # first by `make -C trajectory_planner_amd/csrc`; the steps themselves use neither, and no GPU)
 ROCM=${ROCM:-/opt/rocm}
 g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -Iinclude -I$ROCM/include -pthread \
-    -o /tmp/vigo_san_seed_facade ../../tools/sanitize_seed_facade_main.cpp src/bsplineTraj.cpp src/polyTrajOccMap.cpp src/polyTrajSolver.cpp \
+    -o /tmp/vigo_san_seed_facade ../../tools/sanitize_seed_facade_main.cpp src/bsplineTraj.cpp src/bsplineTrajSeed.cpp src/bsplineTrajBatch.cpp src/polyTrajOccMap.cpp src/polyTrajSolver.cpp \
     src/bspline.cpp src/astarOcc.cpp src/piecewiseLinearTraj.cpp src/mapAdapter.cpp -L../lib -lvigo_hip -L$ROCM/lib -lamdhip64 \
     -Wl,-rpath,"$PWD/../lib" -Wl,-rpath,$ROCM/lib
 /tmp/vigo_san_seed_facade

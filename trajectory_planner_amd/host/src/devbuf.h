@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <vector>
 
 namespace vigo_host {
 
@@ -69,11 +70,31 @@ struct DevBuf {
     bool download(void* dst, size_t bytes) const { return vigo_host::download(dst, p, bytes); }
 };
 
-// thread-lifetime staging buffer (declare `static thread_local`): grows on demand, is reused by every later call
-// of the thread — hipMalloc/hipFree per planning round cost more than the round's kernels — and is left to the
-// runtime's teardown instead of being freed after it
-struct StagingBuf : DevBuf {
-    StagingBuf() { keep = true; }
+// The typed face of a thread-lifetime staging buffer (declare `static thread_local`, one small struct per stage): every
+// extent is a count of T, stated once where the stage sizes the buffer, and a read-back of more elements than that is
+// refused before any HIP call.  The buffer grows on demand, is reused by every later call of the thread — hipMalloc /
+// hipFree per planning round cost more than the round's kernels — and is left to the runtime's teardown.
+template <class T>
+class Staged {
+public:
+    Staged() { buf_.keep = true; }
+    bool upload(const T* src, size_t count) { return sized(buf_.upload(src, count * sizeof(T)), count); }
+    bool upload(const std::vector<T>& src) { return upload(src.data(), src.size()); }
+    bool alloc(size_t count) { return sized(buf_.alloc(count * sizeof(T)), count); }
+    bool download(T* dst, size_t count) const { return count <= count_ && buf_.download(dst, count * sizeof(T)); }
+    bool download(std::vector<T>& dst) const { return download(dst.data(), dst.size()); }   // dst.size() elements
+    T* get() { return static_cast<T*>(buf_.p); }
+    const T* get() const { return static_cast<const T*>(buf_.p); }
+    size_t count() const { return count_; }                      // of the last upload / alloc: what a kernel may touch
+    size_t capacity() const { return buf_.n / sizeof(T); }       // never shrinks
+
+private:
+    bool sized(bool ok, size_t count) {
+        count_ = ok ? count : 0;
+        return ok;
+    }
+    DevBuf buf_;
+    size_t count_ = 0;
 };
 
 }  // namespace vigo_host

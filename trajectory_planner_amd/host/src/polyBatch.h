@@ -15,7 +15,11 @@ namespace vigo_host {
 inline bool minsnapGroupOnDevice(vigo_context* dev, int diffDegree, int continuityDegree, double desiredVel, double corridorRes,
                                  std::vector<QpMember>& members) {
     // reused by every batch of this thread, whichever planner class it serves: every call uploads before it launches
-    static thread_local StagingBuf bWp, bCor, bCnd, bCo, bKn, bSt;
+    struct Stage {
+        Staged<double> wp, corridor, conds, coeffs, knots;
+        Staged<int32_t> status;
+    };
+    static thread_local Stage st;
     if (members.empty()) return true;
     const int D = 8, T = (int)members.size(), W = (int)members[0].path->size(), K = W - 1;
     const bool corridors = members[0].corridor != nullptr, conds = members[0].conds[0] != nullptr;
@@ -28,13 +32,11 @@ inline bool minsnapGroupOnDevice(vigo_context* dev, int diffDegree, int continui
             hCnd.push_back(m.conds[c]->linear.x); hCnd.push_back(m.conds[c]->linear.y); hCnd.push_back(m.conds[c]->linear.z);
         }
     }
-    const bool ok = bWp.upload(hWp.data(), hWp.size() * 8) && (!corridors || bCor.upload(hCor.data(), hCor.size() * 8)) &&
-        (!conds || bCnd.upload(hCnd.data(), hCnd.size() * 8)) && bCo.alloc(hCo.size() * 8) && bKn.alloc((size_t)T * W * 8) &&
-        bSt.alloc((size_t)T * 4) &&
-        vigo_minsnap(dev, T, W, 7, diffDegree, continuityDegree, desiredVel, corridorRes, (const double*)bWp.p,
-                     corridors ? (const double*)bCor.p : nullptr, conds ? (const double*)bCnd.p : nullptr, (double*)bCo.p, (double*)bKn.p,
-                     (int32_t*)bSt.p) == VIGO_OK &&
-        bCo.download(hCo.data(), hCo.size() * 8) && bSt.download(hSt.data(), (size_t)T * 4);
+    const bool ok = st.wp.upload(hWp) && (!corridors || st.corridor.upload(hCor)) && (!conds || st.conds.upload(hCnd)) &&
+        st.coeffs.alloc(hCo.size()) && st.knots.alloc((size_t)T * W) && st.status.alloc(hSt.size()) &&
+        vigo_minsnap(dev, T, W, 7, diffDegree, continuityDegree, desiredVel, corridorRes, st.wp.get(), corridors ? st.corridor.get() : nullptr,
+                     conds ? st.conds.get() : nullptr, st.coeffs.get(), st.knots.get(), st.status.get()) == VIGO_OK &&
+        st.coeffs.download(hCo) && st.status.download(hSt);
     for (int a = 0; ok && a < T; ++a) {   // a member's block [K][3][8] of the coefficients -> its per-axis solutions
         members[a].status = hSt[a];
         for (int c = 0; c < 3; ++c) {
@@ -53,7 +55,12 @@ inline bool minsnapGroupOnDevice(vigo_context* dev, int diffDegree, int continui
 template <class Launch>
 inline bool checkTrajectoriesOnDevice(std::vector<TrajCheck>& cands, Launch launch) {
     // a set of its own: the QP step's coefficients buffer keeps the last group's, this one holds the whole round's
-    static thread_local StagingBuf cOff, cCo, cKn, cDt, cEp, cSt, cN, cFl, cFi, cSeg;
+    struct Stage {
+        Staged<int32_t> segOff, status, n, first;
+        Staged<double> coeffs, knots, delT, endpoint;
+        Staged<uint8_t> flag, seg;
+    };
+    static thread_local Stage st;
     const int D = 8, T = (int)cands.size();
     if (T == 0) return true;
     std::vector<int32_t> segOff(1, 0);
@@ -74,12 +81,11 @@ inline bool checkTrajectoriesOnDevice(std::vector<TrajCheck>& cands, Launch laun
     const int S = segOff.back();
     std::vector<int32_t> hStat(T);
     std::vector<uint8_t> hFlag(T), hSeg(S);
-    const bool ok = cOff.upload(segOff.data(), segOff.size() * 4) && cCo.upload(hCo.data(), hCo.size() * 8) &&
-        cKn.upload(hKn.data(), hKn.size() * 8) && cDt.upload(hDt.data(), hDt.size() * 8) && cEp.upload(hEp.data(), hEp.size() * 8) &&
-        cSt.alloc((size_t)T * 4) && cN.alloc((size_t)T * 4) && cFl.alloc((size_t)T) && cFi.alloc((size_t)T * 4) && cSeg.alloc((size_t)S) &&
-        launch(T, S, (const int32_t*)cOff.p, (const double*)cCo.p, (const double*)cKn.p, (const double*)cDt.p, (const double*)cEp.p,
-               (int32_t*)cSt.p, (int32_t*)cN.p, (uint8_t*)cFl.p, (int32_t*)cFi.p, (uint8_t*)cSeg.p) &&
-        cSt.download(hStat.data(), (size_t)T * 4) && cFl.download(hFlag.data(), (size_t)T) && cSeg.download(hSeg.data(), (size_t)S);
+    const bool ok = st.segOff.upload(segOff) && st.coeffs.upload(hCo) && st.knots.upload(hKn) && st.delT.upload(hDt) && st.endpoint.upload(hEp) &&
+        st.status.alloc(hStat.size()) && st.n.alloc((size_t)T) && st.flag.alloc(hFlag.size()) && st.first.alloc((size_t)T) && st.seg.alloc(hSeg.size()) &&
+        launch(T, S, st.segOff.get(), st.coeffs.get(), st.knots.get(), st.delT.get(), st.endpoint.get(), st.status.get(), st.n.get(), st.flag.get(),
+               st.first.get(), st.seg.get()) &&
+        st.status.download(hStat) && st.flag.download(hFlag) && st.seg.download(hSeg);
     for (int a = 0; ok && a < T; ++a) {
         cands[a].status = hStat[a];
         cands[a].collides = hFlag[a] != 0;

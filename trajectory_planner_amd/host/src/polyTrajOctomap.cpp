@@ -100,11 +100,15 @@ bool polyTrajOctomap::sweepXyz(const std::vector<double>& xyz, std::vector<uint8
     const size_t n = xyz.size() / 3;
     flags.assign(n, 1);
     if (n == 0) return true;
-    static thread_local vigo_host::StagingBuf dP, dF;      // reused by every sweep of this thread
+    struct Stage {
+        vigo_host::Staged<double> xyz;
+        vigo_host::Staged<uint8_t> flags;
+    };
+    static thread_local Stage st;      // reused by every sweep of this thread
     const double box[3] = {collisionBox_[0], collisionBox_[1], collisionBox_[2]};
-    const bool ok = dP.upload(xyz.data(), n * 24) && dF.alloc(n) &&
-                    vigo_box_collision_points(link_.handle(), (int64_t)n, (const double*)dP.p, box, mapRes_, (uint8_t*)dF.p) == VIGO_OK &&
-                    dF.download(flags.data(), n);
+    const bool ok = st.xyz.upload(xyz) && st.flags.alloc(flags.size()) &&
+                    vigo_box_collision_points(link_.handle(), (int64_t)n, st.xyz.get(), box, mapRes_, st.flags.get()) == VIGO_OK &&
+                    st.flags.download(flags);
     // A pose at NaN or infinity: the reference's sweep makes no pass there (the lattice count is the conversion of a
     // NaN, INT_MIN on x86 — the device entry point follows that, include/vigo.h) and would publish the trajectory.  The
     // facade refuses such a pose instead: a degenerate min-snap solution (coincident waypoints) then falls back to the

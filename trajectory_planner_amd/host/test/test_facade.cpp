@@ -16,7 +16,9 @@
 #include <set>
 #include <thread>
 
+#include "../../../include/vigo.h"
 #include "../src/batchLayout.h"
+#include "../src/devbuf.h"
 
 using trajPlanner::bsplineTraj;
 
@@ -953,6 +955,33 @@ int main() {
         std::printf("INFO stress: %d plans carried dynamic obstacles; device-resident vs host-driven rebound loop: %d of %d differ\n", obstaclePlans, loopMismatch, total);
         CHECK(loopMismatch == 0, "stress: device-resident rebound loop == host-driven loop on every planner (bit for bit)");
         CHECK(polyDirty == 0, "stress: every valid polyTrajOctomap plan keeps its poses out of occupied voxels");
+    }
+
+    // ---- the facades' typed staging buffers (devbuf.h): extents in elements, a read-back beyond them refused ----
+    // (last: the timed sections above run in the process state they always had)
+    {
+        vigo_host::Staged<int32_t> a;
+        const std::vector<int32_t> src{7, -8, 9};
+        std::vector<int32_t> back(3, 0), four(4, -1);
+        CHECK(a.upload(src) && a.count() == 3 && a.download(back) && back == src, "Staged<int32_t>: three elements round trip");
+        CHECK(!a.download(four) && four == std::vector<int32_t>(4, -1), "Staged: a download of more elements than it holds is refused, the destination untouched");
+        const int32_t* p3 = a.get();
+        const size_t cap3 = a.capacity();
+        CHECK(a.alloc(3) && a.alloc(2) && a.get() == p3 && a.capacity() == cap3 && cap3 == 3 && a.count() == 2, "Staged: alloc(2) after alloc(3) keeps pointer and capacity");
+        vigo_host::Staged<int32_t> fresh;
+        CHECK(fresh.upload(std::vector<int32_t>()) && fresh.get() == nullptr && fresh.capacity() == 0, "Staged: an empty upload into a fresh buffer allocates nothing");
+        vigo_host::Staged<double> d;
+        const std::vector<double> dsrc{0.25, -1e300};
+        std::vector<double> dback(2, 0.0);
+        CHECK(d.upload(dsrc) && d.download(dback) && dback == dsrc, "Staged<double>: two elements round trip");
+        vigo_host::Staged<vigo_rebound_state_t> r;
+        std::vector<vigo_rebound_state_t> rsrc(2), rback(2);
+        std::memset(rsrc.data(), 0, 2 * sizeof(vigo_rebound_state_t));
+        std::memset(rback.data(), 0xff, 2 * sizeof(vigo_rebound_state_t));
+        rsrc[0].status = 3; rsrc[0].n_seg = 1; rsrc[0].seg[1] = 17;
+        rsrc[1].fail_count = 5; rsrc[1].seg[2 * VIGO_MAX_COLLISION_SEGS - 1] = -2;
+        CHECK(r.upload(rsrc) && r.download(rback) && std::memcmp(rsrc.data(), rback.data(), 2 * sizeof(vigo_rebound_state_t)) == 0,
+              "Staged<vigo_rebound_state_t>: two elements round trip");
     }
 
     std::printf("%s (%d failures)\n", fails ? "FAILED" : "PASSED", fails);
