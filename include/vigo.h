@@ -336,6 +336,58 @@ int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl,
                         double* weights, double gate_dt, double not_check_ratio, int max_rounds,
                         vigo_rebound_state_t* state);
 
+/* ---- mixed control-point counts in one batch ------------------------------------------------ */
+
+/*
+ * vigo_cost_grad, vigo_optimize and vigo_rebound_rounds for trajectories of DIFFERENT length in one call.
+ *   Ns     the row stride, in control points, of every per-point array
+ *   n_pts  int32[B], device memory: trajectory b has n_pts[b] control points
+ * The layouts are those of the uniform entries with N replaced by Ns: ctrl double[B][Ns][3]; guide_off int32[B*Ns+1]
+ * with control point i of trajectory b at b*Ns + i; out_x / out_grad double[B][Ns-6][3]; everything per trajectory
+ * (obs_off, weights, state, out_cost, out_status, ...) as before.  Trajectory b uses the first n_pts[b] rows of its ctrl
+ * row, and the first n_pts[b] - 6 rows of its out_x / out_grad row are written.  Nothing beyond those is read for its
+ * value or written; guide_off is read at free control points only (entries b*Ns + 3 .. b*Ns + n_pts[b] - 3), as in the
+ * uniform entries — by vigo_rebound_rounds_mixed, as by vigo_rebound_rounds, also at any control point a collision
+ * segment names (entries b*Ns .. b*Ns + n_pts[b]).
+ *
+ * CONTRACT.  7 <= n_pts[b] <= Ns <= 64, and every count lies in the shape class of Ns: all <= 32 (two trajectories per
+ * wavefront), or all in 33 .. 64 (one).  A trajectory then runs in exactly the lane layout and reduction tree that a
+ * uniform call of its own count gives it, so EVERY OUTPUT OF A TRAJECTORY EQUALS, BIT FOR BIT, ITS OUTPUT IN A UNIFORM
+ * CALL OF ITS OWN COUNT — in the three arithmetic modes, under the level rule, plan_in_z and strict_z, with and without
+ * obstacles: a result depends neither on the batch a trajectory travels in nor on the lengths of its neighbours.
+ * Ns < 7 or Ns > 64 returns VIGO_ERR_UNSUPPORTED_N (such callers keep grouping by exact count); NULL n_pts with B > 0
+ * VIGO_ERR_INVALID_ARG.  A call is ONE launch of the general solve kernel (obstacle code, z carried and masked for a
+ * level trajectory), where the uniform entries pick a cheaper kernel for level or obstacle-free batches.
+ *
+ * A count that breaks the contract is device data and is caught per trajectory.  Nothing beyond the row is indexed, the
+ * bad trajectory's ctrl row and weights stay untouched, its wavefront partner and every other trajectory get the bits
+ * they would get without it, and it is reported as
+ *   vigo_optimize_mixed        out_status = LBFGSERR_INVALID_N (-1021, LB:36), nothing else written
+ *   vigo_cost_grad_mixed       out_cost = NaN, no gradient rows, no terms
+ *   vigo_rebound_rounds_mixed  an ACTIVE entry becomes status = VIGO_RB_NEEDS_HOST with lbfgs_status =
+ *                              LBFGSERR_INVALID_N, rounds left as it was, and WITHOUT the batch-wide wait: the other
+ *                              trajectories' rounds go on (the state of "the device cannot represent this planner")
+ * Otherwise vigo_rebound_rounds_mixed keeps the batch-wide rule of vigo_rebound_rounds: once a round hands a
+ * trajectory to the host, the optimize() every still-active trajectory owes is deferred to the next call.  The gates
+ * sample each trajectory over its own duration (n_pts[b] - 3) * ts_ctrl.
+ */
+int vigo_cost_grad_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl,
+                         const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                         const int32_t* obs_off, const double* obs, int n_obs_shared,
+                         const double* weights,
+                         double* out_cost, double* out_grad, double* out_terms);
+int vigo_optimize_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, double* ctrl,
+                        const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                        const int32_t* obs_off, const double* obs, int n_obs_shared,
+                        const double* weights,
+                        double* out_x, int32_t* out_status, double* out_fx,
+                        int32_t* out_iters, int32_t* out_evals);
+int vigo_rebound_rounds_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, double* ctrl,
+                              const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                              const int32_t* obs_off, const double* obs, int n_obs_shared,
+                              double* weights, double gate_dt, double not_check_ratio, int max_rounds,
+                              vigo_rebound_state_t* state);
+
 /* ---- min-snap QP and corridor collision checker ------------------------------------ */
 
 /*

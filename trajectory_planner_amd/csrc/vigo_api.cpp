@@ -96,6 +96,14 @@ int check_solve_args(vigo_handle_t h, int B, int N, const void* ctrl) {
     return VIGO_OK;
 }
 
+// the mixed-count entries: rows of Ns control points, one launch of the general kernel up to Ns = 64
+int check_mixed_args(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const void* ctrl) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (B < 0 || (B > 0 && (!ctrl || !n_pts))) return fail(h, VIGO_ERR_INVALID_ARG, "B < 0, ctrl == NULL or n_pts == NULL");
+    if (Ns < 7 || Ns > vigo::kMixedMaxStride) return fail(h, VIGO_ERR_UNSUPPORTED_N, "Ns outside [7, 64]: group such trajectories by their exact count");
+    return VIGO_OK;
+}
+
 // The list arguments shared by the solve entry points and the dynamic gate.  Offsets (or a shared count)
 // without the list they index mean "no guides" / "no obstacles" — callers keep all-zero CSR offsets around
 // when a batch happens to have none — and the kernels never dereference the missing list.
@@ -114,6 +122,12 @@ SolveArgs solve_args(int B, int N, double* ctrl, const int32_t* guide_off, const
     a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
     a.weights = weights;
     return a;
+}
+vigo::MixedSolveArgs mixed_args(const SolveArgs& a, const int32_t* n_pts) {
+    vigo::MixedSolveArgs m{};
+    static_cast<SolveArgs&>(m) = a;
+    m.n_pts = n_pts;
+    return m;
 }
 
 // the L-BFGS history of a solve workgroup fits the LDS of a CU
@@ -548,10 +562,38 @@ int vigo_optimize(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* gu
     return VIGO_OK;
 }
 
-int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* guide_off, const double* guide_pv,
-                        const uint8_t* guide_unk, const int32_t* obs_off, const double* obs, int n_obs_shared, double* weights,
-                        double gate_dt, double not_check_ratio, int max_rounds, vigo_rebound_state_t* state) {
-    VIGO_TRY(check_solve_args(h, B, N, ctrl));
+int vigo_cost_grad_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* guide_off,
+                         const double* guide_pv, const uint8_t* guide_unk, const int32_t* obs_off, const double* obs,
+                         int n_obs_shared, const double* weights, double* out_cost, double* out_grad, double* out_terms) {
+    VIGO_TRY(check_mixed_args(h, B, Ns, n_pts, ctrl));
+    VIGO_TRY(check_list_args(h, n_obs_shared));
+    SolveArgs a = solve_args(B, Ns, const_cast<double*>(ctrl), guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
+    a.out_cost = out_cost; a.out_grad = out_grad; a.out_terms = out_terms;
+    VIGO_HIP(h, (hipError_t)vigo::launch_cost_grad_mixed(h->stream, mixed_args(a, n_pts), h->dc_dev, h->precision));
+    return VIGO_OK;
+}
+
+int vigo_optimize_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, double* ctrl, const int32_t* guide_off,
+                        const double* guide_pv, const uint8_t* guide_unk, const int32_t* obs_off, const double* obs,
+                        int n_obs_shared, const double* weights, double* out_x, int32_t* out_status, double* out_fx,
+                        int32_t* out_iters, int32_t* out_evals) {
+    VIGO_TRY(check_mixed_args(h, B, Ns, n_pts, ctrl));
+    VIGO_TRY(check_list_args(h, n_obs_shared));
+    SolveArgs a = solve_args(B, Ns, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
+    a.out_x = out_x; a.out_status = out_status; a.out_fx = out_fx;
+    a.out_iters = out_iters; a.out_evals = out_evals;
+    VIGO_HIP(h, (hipError_t)vigo::launch_optimize_mixed(h->stream, mixed_args(a, n_pts), h->dc, h->dc_dev, h->precision, h->launch));
+    return VIGO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// vigo_rebound_rounds (n_pts == NULL: B trajectories of N control points) and vigo_rebound_rounds_mixed (rows of N, counts
+// n_pts): the same queue of launches, the solves by launch_optimize / launch_optimize_mixed
+int rebound_rounds(vigo_handle_t h, int B, int N, const int32_t* n_pts, double* ctrl, const int32_t* guide_off, const double* guide_pv,
+                   const uint8_t* guide_unk, const int32_t* obs_off, const double* obs, int n_obs_shared, double* weights,
+                   double gate_dt, double not_check_ratio, int max_rounds, vigo_rebound_state_t* state) {
     VIGO_TRY(check_list_args(h, n_obs_shared));
     if (B > 0 && (!weights || !state)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_rounds: weights and state are required");
     if (max_rounds < 0 || max_rounds > 64 || !(not_check_ratio >= 0.0 && not_check_ratio < 1.0))
@@ -561,10 +603,30 @@ int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl, const int32
     if (B == 0) return VIGO_OK;
     int T = 0;
     const double* times = nullptr;
+    // (mixed: the sample clock depends on gate_dt and k only, so the table of the longest duration serves every count)
     VIGO_TRY(upload_sample_times(h, (N - 3) * h->params.ts_ctrl, gate_dt, &T, &times));
+    auto static_samples = [&](int n, int all) {   // see T_static below
+        const int t = count_sample_times(gate_dt, (1.0 - not_check_ratio) * ((n - 3) * h->params.ts_ctrl));
+        return t < 0 || t > all ? all : t;
+    };
     // compacted active set: count = flags[0]; flags[1], flags[2]: "a trajectory waits for the host"
-    int32_t *count, *idx;
-    VIGO_TRY(carve(h, vigo::kBufRebound, kExact, [&](void* p) { return vigo::ws_rebound(p, B, count, idx); }));
+    int32_t *count, *idx, *count_tab = nullptr;
+    if (n_pts) {
+        VIGO_TRY(carve(h, vigo::kBufRebound, kExact, [&](void* p) { return vigo::ws_rebound_mixed(p, B, N, count, idx, count_tab); }));
+        // {T, T_static} of every count 7 .. N, by the host function that counts the uniform entry's samples
+        int32_t tab[2 * (vigo::kMixedMaxStride - 6)];
+        for (int n = 7; n <= N; ++n) {
+            int t = count_sample_times(gate_dt, (n - 3) * h->params.ts_ctrl);
+            if (t < 0 || t > T) t = T;
+            tab[2 * (n - 7)] = t;
+            tab[2 * (n - 7) + 1] = static_samples(n, t);
+        }
+        VIGO_HIP(h, hipMemcpyAsync(count_tab, tab, 2 * (size_t)(N - 6) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        VIGO_HIP(h, hipStreamSynchronize(h->stream));   // tab is on this stack frame
+        VIGO_HIP(h, (hipError_t)vigo::launch_rebound_check_counts(h->stream, B, N, n_pts, state));
+    } else {
+        VIGO_TRY(carve(h, vigo::kBufRebound, kExact, [&](void* p) { return vigo::ws_rebound(p, B, count, idx); }));
+    }
     VIGO_HIP(h, hipMemsetAsync(count, 0, 16 * sizeof(int32_t), h->stream));
     SolveArgs a = solve_args(B, N, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights);
     a.active_idx = idx; a.active_count = count;
@@ -578,20 +640,45 @@ int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl, const int32
     r.ts_ctrl = h->params.ts_ctrl; r.T = T; r.times = times;
     // the static gate stops at (1 - notCheckRatio_) * duration (BT.h:313); the dynamic one samples the whole
     // trajectory (evalTraj(), BT.h:345) — a prefix of the same clock
-    r.T_static = count_sample_times(gate_dt, (1.0 - not_check_ratio) * ((N - 3) * h->params.ts_ctrl));
-    if (r.T_static < 0 || r.T_static > T) r.T_static = T;
+    r.T_static = static_samples(N, T);
     r.dthresh = h->params.dthresh; r.not_check_ratio = not_check_ratio;
     r.flags = count;
+    r.n_pts = n_pts; r.count_tab = count_tab;
+    const vigo::MixedSolveArgs am = mixed_args(a, n_pts);
+    auto solve = [&]() {
+        return (hipError_t)(n_pts ? vigo::launch_optimize_mixed(h->stream, am, h->dc, h->dc_dev, h->precision, h->launch)
+                                  : vigo::launch_optimize(h->stream, a, h->dc, h->dc_dev, h->precision, h->launch));
+    };
     // the optimize() a trajectory still owes (BT.cpp:612 / after a host-side re-guide) ...
     VIGO_HIP(h, (hipError_t)vigo::launch_rebound_compact(h->stream, B, state, 0, idx, count));
-    VIGO_HIP(h, (hipError_t)vigo::launch_optimize(h->stream, a, h->dc, h->dc_dev, h->precision, h->launch));
+    VIGO_HIP(h, solve());
     // ... then the rounds: gates + decision, compaction of the still-active set, optimize
     for (int round = 0; round < max_rounds; ++round) {
         VIGO_HIP(h, (hipError_t)vigo::launch_rebound_decide(h->stream, h->grid, r));
         VIGO_HIP(h, (hipError_t)vigo::launch_rebound_compact(h->stream, B, state, 1, idx, count));
-        VIGO_HIP(h, (hipError_t)vigo::launch_optimize(h->stream, a, h->dc, h->dc_dev, h->precision, h->launch));
+        VIGO_HIP(h, solve());
     }
     return VIGO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int vigo_rebound_rounds(vigo_handle_t h, int B, int N, double* ctrl, const int32_t* guide_off, const double* guide_pv,
+                        const uint8_t* guide_unk, const int32_t* obs_off, const double* obs, int n_obs_shared, double* weights,
+                        double gate_dt, double not_check_ratio, int max_rounds, vigo_rebound_state_t* state) {
+    VIGO_TRY(check_solve_args(h, B, N, ctrl));
+    return rebound_rounds(h, B, N, nullptr, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights, gate_dt,
+                          not_check_ratio, max_rounds, state);
+}
+
+int vigo_rebound_rounds_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, double* ctrl, const int32_t* guide_off,
+                              const double* guide_pv, const uint8_t* guide_unk, const int32_t* obs_off, const double* obs,
+                              int n_obs_shared, double* weights, double gate_dt, double not_check_ratio, int max_rounds,
+                              vigo_rebound_state_t* state) {
+    VIGO_TRY(check_mixed_args(h, B, Ns, n_pts, ctrl));
+    return rebound_rounds(h, B, Ns, n_pts, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, n_obs_shared, weights, gate_dt,
+                          not_check_ratio, max_rounds, state);
 }
 
 /* ---- B-spline fit, evaluation and gates ------------------------------------------------- */

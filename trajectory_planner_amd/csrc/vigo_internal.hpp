@@ -63,6 +63,11 @@ struct SolveArgs {
     double* out_grad;
     double* out_terms;
 };
+// (vigo_*_mixed) the arguments of the MIXED instantiations: N is the row stride of ctrl, guide_off and the outputs,
+// trajectory b has n_pts[b] control points.  A type of its own: SolveArgs is what every other kernel was measured with
+struct MixedSolveArgs : SolveArgs {
+    const int32_t* n_pts;
+};
 
 // Packed voxel snapshot in HBM: three bit planes (inflated-occupied, unknown, occupied), each
 // nx*ny rows of nzw 32-bit words, z fastest (bit k of word w = voxel z = 32*w + k).
@@ -106,6 +111,9 @@ struct LaunchState {
 // k: host copy (launch geometry), kd: the same constants in device memory (read by the kernels)
 int launch_cost_grad(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision);
 int launch_optimize(hipStream_t s, const SolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L);
+// the mixed-count entries (a.n_pts set, a.N the row stride, 7 .. 64): one launch of the general kernel
+int launch_cost_grad_mixed(hipStream_t s, const MixedSolveArgs& a, const DevConst* kd, int precision);
+int launch_optimize_mixed(hipStream_t s, const MixedSolveArgs& a, const DevConst& k, const DevConst* kd, int precision, LaunchState& L);
 
 int launch_pack_grid(hipStream_t s, int nx, int ny, int nz, const uint8_t* vox, uint32_t* packed);
 int launch_inflate(hipStream_t s, int nx, int ny, int nz, uint8_t* vox, uint32_t* planeA, uint32_t* planeB, int rx, int ry, int rz);
@@ -170,7 +178,15 @@ struct ReboundArgs {
     const double* times;
     double dthresh, not_check_ratio;
     int32_t* flags;          // see k_rebound_compact
+    // (vigo_rebound_rounds_mixed) not NULL: trajectory b has n_pts[b] control points in a row of N, and its gates take
+    // {T, T_static} from count_tab[2 * (n_pts[b] - 7)] (one pair per count 7 .. N) instead of the two fields above;
+    // `times` then holds the clock of the longest duration, of which every count's samples are a prefix
+    const int32_t* n_pts;
+    const int32_t* count_tab;
 };
+// (vigo_rebound_rounds_mixed, before the first compaction) an ACTIVE trajectory whose count breaks the contract of the
+// mixed entries is handed to the host: status VIGO_RB_NEEDS_HOST, lbfgs_status LBFGSERR_INVALID_N, nothing else touched
+int launch_rebound_check_counts(hipStream_t s, int B, int Ns, const int32_t* n_pts, vigo_rebound_state_t* state);
 int launch_rebound_decide(hipStream_t s, const GridView& g, const ReboundArgs& a);
 // mode 0: status == ACTIVE && solve_first (clears solve_first); mode 1: status == ACTIVE.  Ascending order.
 int launch_rebound_compact(hipStream_t s, int B, vigo_rebound_state_t* state, int mode, int32_t* idx, int32_t* flags);

@@ -77,11 +77,15 @@ __global__ void __launch_bounds__(64) k_rebound_decide(GridView g, ReboundArgs A
     if (A.flags[1] != 0) return;
     vigo_rebound_state_t& st = A.state[b];
     if (st.status != VIGO_RB_ACTIVE) return;
-    const int N = A.N, lane = threadIdx.x;
-    const double* c = A.ctrl + (size_t)b * N * 3;
+    // (vigo_rebound_rounds_mixed) rows of A.N control points, n_pts[b] of them this trajectory's, and its gates' sample
+    // counts from the per-count table; k_rebound_check_counts has taken every count outside [7, A.N] out of the ACTIVE set
+    const int lane = threadIdx.x;
+    const int N = A.n_pts ? min(max(A.n_pts[b], 7), A.N) : A.N;   // (device data: never index beyond the row)
+    const int T = A.n_pts ? A.count_tab[2 * (N - 7)] : A.T, T_static = A.n_pts ? A.count_tab[2 * (N - 7) + 1] : A.T_static;
+    const double* c = A.ctrl + (size_t)b * A.N * 3;
 
-    const int col = __any(gate_static_first(g, c, N, A.ts_ctrl, A.T_static, A.times, lane) != INT_MAX) ? 1 : 0;
-    const int dyn = __any(gate_dynamic_hit(c, N, A.ts_ctrl, A.T, A.times, A.obs_off, A.obs, A.n_obs_shared, b, lane)) ? 1 : 0;
+    const int col = __any(gate_static_first(g, c, N, A.ts_ctrl, T_static, A.times, lane) != INT_MAX) ? 1 : 0;
+    const int dyn = __any(gate_dynamic_hit(c, N, A.ts_ctrl, T, A.times, A.obs_off, A.obs, A.n_obs_shared, b, lane)) ? 1 : 0;
     if (lane == 0) {
         st.gate_static = col;
         st.gate_dynamic = dyn;
@@ -104,7 +108,7 @@ __global__ void __launch_bounds__(64) k_rebound_decide(GridView g, ReboundArgs A
             uint8_t listed[kSegs];
             int n_list = 0;
             const int n_prev = min(max(st.n_seg, 0), kSegs);   // (device data: never index beyond the array)
-            const NeedGuide need_guide{A.guide_off ? A.guide_off + (size_t)b * N : nullptr, A.guide_pv, c, A.dthresh};
+            const NeedGuide need_guide{A.guide_off ? A.guide_off + (size_t)b * A.N : nullptr, A.guide_pv, c, A.dthresh};
             const int n = reguide_rules(N, A.not_check_ratio, FlagOcc{s_pt}, FlagOcc{s_ln}, n_prev, st.seg, need_guide, kSegs, seg, listed, &n_list);
             const bool need_host = n > kSegs || n_list != 0;
             s_need_host = need_host ? 1 : 0;
@@ -287,6 +291,23 @@ __global__ void __launch_bounds__(256) k_reguide_commit(ReguideArgs A) {
 }
 
 }  // namespace
+
+// vigo_rebound_rounds_mixed, before anything else: a count that breaks the contract (outside [7, Ns], or of the other
+// shape class than Ns) takes its ACTIVE trajectory out of the set — NEEDS_HOST with LBFGSERR_INVALID_N (-1021), no wait
+// flag: the host solves such a planner itself, the rest of the batch goes on
+__global__ void __launch_bounds__(256) k_rebound_check_counts(int B, int Ns, const int32_t* __restrict__ n_pts, vigo_rebound_state_t* __restrict__ state) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || state[b].status != VIGO_RB_ACTIVE) return;
+    const int n = n_pts[b];
+    if (n >= 7 && n <= Ns && (n <= 32) == (Ns <= 32)) return;
+    state[b].status = VIGO_RB_NEEDS_HOST;
+    state[b].lbfgs_status = -1021;
+}
+int launch_rebound_check_counts(hipStream_t s, int B, int Ns, const int32_t* n_pts, vigo_rebound_state_t* state) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rebound_check_counts, dim3((B + 255) / 256), dim3(256), 0, s, B, Ns, n_pts, state);
+    return (int)hipGetLastError();
+}
 
 int launch_rebound_decide(hipStream_t s, const GridView& g, const ReboundArgs& a) {
     if (a.B <= 0) return hipSuccess;

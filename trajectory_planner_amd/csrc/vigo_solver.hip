@@ -762,11 +762,25 @@ __device__ __forceinline__ void axis_guides(LaneProblem<double, 1>& Q, int axis)
     }
 }
 
-template <typename T, int GROUP, int PPL>
-__device__ __forceinline__ void load_problem(const SolveArgs& A, const DevConst& K, int b, int lane_in_group,
+// MIXED (vigo_*_mixed): A.N is the row STRIDE of ctrl, guide_off and the outputs, trajectory b has A.n_pts[b] control
+// points.  The count is device data: one outside [7, A.N], or of the other shape class than the launch's (shape_for:
+// GROUP lanes per trajectory), gives a problem WITHOUT points — Q.N = 0: no lane has a point, none is free, nothing of
+// the row is read or written — and false; the caller reports it and leaves.
+// (the count array is a field of MixedSolveArgs, not of SolveArgs: the kernel arguments of every other instantiation,
+// and with them the offsets their code loads from, stay what they were)
+template <bool MIXED> using SolveArgsOf = std::conditional_t<MIXED, MixedSolveArgs, SolveArgs>;
+template <typename T, int GROUP, int PPL, bool MIXED = false>
+__device__ __forceinline__ bool load_problem(const SolveArgsOf<MIXED>& A, const DevConst& K, int b, int lane_in_group,
                                              LaneProblem<T, PPL>& Q) {
     using LP = LaneProblem<T, PPL>;
-    const int N = A.N;
+    int N = A.N;
+    bool valid = true;
+    if constexpr (MIXED) {
+        static_assert(PPL == 1, "mixed counts: one control point per lane (Ns <= 64)");
+        const int n = A.n_pts[b];
+        valid = n >= 7 && n <= A.N && shape_for(n).group == GROUP;
+        N = valid ? n : 0;
+    }
     Q.N = N;
     Q.level = false;
     Q.p0 = lane_in_group * PPL;
@@ -779,8 +793,8 @@ __device__ __forceinline__ void load_problem(const SolveArgs& A, const DevConst&
         Q.interior[q] = (p >= 3) && (p <= N - 4);
         Q.g_begin[q] = Q.g_end[q] = 0;
         if (Q.interior[q] && A.guide_off && A.guide_pv) {   // offsets without pairs: no guides
-            Q.g_begin[q] = A.guide_off[(size_t)b * N + p];
-            Q.g_end[q] = A.guide_off[(size_t)b * N + p + 1];
+            Q.g_begin[q] = A.guide_off[(size_t)b * (MIXED ? A.N : N) + p];
+            Q.g_end[q] = A.guide_off[(size_t)b * (MIXED ? A.N : N) + p + 1];
         }
     }
 #pragma unroll
@@ -814,6 +828,7 @@ __device__ __forceinline__ void load_problem(const SolveArgs& A, const DevConst&
 #pragma unroll
         for (int q = 0; q < 4; ++q) Q.w[q] = K.w[q];
     }
+    return valid;
 }
 
 template <typename T, int PPL>
@@ -861,15 +876,18 @@ __device__ __forceinline__ void store_point_axis(const SolveArgs& A, int b, cons
 }
 
 // ---- standalone cost/gradient kernel (vigo_cost_grad) ----------------------------------
-template <typename T, int GROUP, int PPL, bool FAST>
-__global__ void __launch_bounds__(kWave) k_cost_grad(SolveArgs A, const DevConst* __restrict__ Kp) {
+template <typename T, int GROUP, int PPL, bool FAST, bool MIXED = false>
+__global__ void __launch_bounds__(kWave) k_cost_grad(SolveArgsOf<MIXED> A, const DevConst* __restrict__ Kp) {
     const DevConst& K = *Kp;  // uniform address: scalar loads at the use sites, not 100+ live SGPRs
     constexpr int TPB = kWave / GROUP;
     const int lane = threadIdx.x;
     const int b = blockIdx.x * TPB + lane / GROUP;
     if (b >= A.B) return;
     LaneProblem<T, PPL> Q;
-    load_problem<T, GROUP, PPL>(A, K, b, lane % GROUP, Q);
+    if (!load_problem<T, GROUP, PPL, MIXED>(A, K, b, lane % GROUP, Q)) {   // (MIXED) a bad count: NaN cost, nothing else
+        if (lane % GROUP == 0 && A.out_cost) A.out_cost[b] = __builtin_nan("");
+        return;
+    }
     T c[PPL][3], g[PPL][3], zero[PPL][3];
     load_points<T, PPL>(A, b, Q, c);
     set_level<T, GROUP, PPL>(K, Q, c);
@@ -1038,8 +1056,12 @@ __device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd
 // RH = history pairs besides the newest that stay in registers (ages 1 .. RH; 0 for more than one point per lane: all in
 // LDS): 1 normally; 4 or 5 in the level instantiations launched on batches that fill the chip (kLevelRH, vigo_solver_plan.hpp):
 // fewer ring slots in LDS are more resident waves per CU
-template <typename T, int GROUP, int PPL, bool FAST, int WPS = 1, bool OBS = true, int D = 3, int RH = (PPL == 1 ? 1 : 0)>
-__global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevConst* __restrict__ Kp) {
+// MIXED: trajectories of different counts in one launch (load_problem); A.N, the row stride, sizes the LDS layout.  Only
+// the general kernel has such an instantiation (D = 3, OBS): it treats a missing obstacle list as no obstacles and
+// solves a level trajectory with its z terms masked, the same bits as the kernels a uniform call launches for them.
+template <typename T, int GROUP, int PPL, bool FAST, int WPS = 1, bool OBS = true, int D = 3, int RH = (PPL == 1 ? 1 : 0), bool MIXED = false>
+__global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, const DevConst* __restrict__ Kp) {
+    static_assert(!MIXED || (D == 3 && OBS && PPL == 1), "mixed counts: the general kernel, one point per lane");
     static_assert(PPL == 1 ? (RH >= 1 && RH <= 6) : RH == 0, "register-held history only with one point per lane");
     // AXIS (D == 1): a level trajectory on a whole wave, one COORDINATE per lane — lane l < 32 holds coordinate 0 of
     // control point l, lane l + 32 coordinate 1 of the same point (GROUP = 32 is then the lanes of one axis).  Every
@@ -1086,7 +1108,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     }
 
     LaneProblem<T, PPL> Q;
-    load_problem<T, GROUP, PPL>(A, K, b, lane % GROUP, Q);
+    const bool valid_n = load_problem<T, GROUP, PPL, MIXED>(A, K, b, lane % GROUP, Q);
     // x holds this lane's control points: free variables where interior, fixed boundary points
     // elsewhere (their g, d, s, y are identically zero so they never move).
     T x[PPL][3];
@@ -1135,6 +1157,10 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
     }
     __syncthreads();   // one wave per workgroup: orders the zero column before the first history read
     if (solved_elsewhere) return;
+    if (MIXED && !valid_n) {   // a bad count: LBFGSERR_INVALID_N (LB:36) and nothing else; its group leaves as above
+        if (lane % GROUP == 0 && A.out_status) A.out_status[(size_t)b * (A.status_stride ? A.status_stride : 1)] = LBERR_INVALID_N;
+        return;
+    }
     YS* ys_l = reinterpret_cast<YS*>(lds_raw + (size_t)ROWP * sizeof(HPair<T, D>)) + tg;   // slot 0; slot k at + k * slotB bytes
     double* al_l = ys_tab + tg;
     auto hist_at = [&](int q, int slot) -> HPair<T, D>& {
@@ -1638,6 +1664,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgs A, const DevC
 #endif
 
 using SolveKernel = void (*)(SolveArgs, const DevConst*);
+using MixedSolveKernel = void (*)(MixedSolveArgs, const DevConst*);
 
 #if VIGO_SOLVER_PART == 0
 DevConst make_dev_const(const vigo_params_t& P) {
@@ -1701,7 +1728,7 @@ int launch_cost_grad(hipStream_t s, const SolveArgs& a, const DevConst&, const D
 template <int I>
 static constexpr SolveKernel optimize_kernel_of() {
     constexpr OptimizeKey k = kOptimizeKeys[I];
-    if constexpr (k.obs == (VIGO_SOLVER_PART == 1)) {
+    if constexpr (VIGO_SOLVER_PART <= 1 && k.obs == (VIGO_SOLVER_PART == 1)) {
         using T = std::conditional_t<k.precision == VIGO_PREC_F32, float, double>;
         constexpr bool FAST = k.precision == VIGO_PREC_F64_FAST;
         static_assert(sizeof(T) == elem_bytes_of(k.precision) && sizeof(HPair<T, k.d>) == hpair_bytes(sizeof(T), k.d) &&
@@ -1714,10 +1741,35 @@ template <class Rows> struct OptimizeKernelTable;
 template <int... I> struct OptimizeKernelTable<std::integer_sequence<int, I...>> { static constexpr SolveKernel row[] = {optimize_kernel_of<I>()...}; };
 static SolveKernel optimize_kernel(int key) { return OptimizeKernelTable<std::make_integer_sequence<int, kOptimizeKeyCount>>::row[key]; }
 
-#if VIGO_SOLVER_PART == 1
+// VIGO_SOLVER_PART == 2, a third object: the MIXED instantiations (vigo_*_mixed), one per row of kOptimizeMixedKeys, and
+// k_cost_grad's for the same arithmetics and groups.  No existing instantiation is built from different text for them.
+#if VIGO_SOLVER_PART == 2
+template <int I>
+static constexpr MixedSolveKernel optimize_mixed_kernel_of() {
+    constexpr OptimizeKey k = kOptimizeMixedKeys[I];
+    using T = std::conditional_t<k.precision == VIGO_PREC_F32, float, double>;
+    constexpr bool FAST = k.precision == VIGO_PREC_F64_FAST;
+    static_assert(sizeof(T) == elem_bytes_of(k.precision) && sizeof(HPair<T, k.d>) == hpair_bytes(sizeof(T), k.d) &&
+                      sizeof(YSv<FAST>) == ysv_bytes(FAST), "optimize_lds_bytes computes these sizes by arithmetic");
+    return &k_optimize<T, k.group, k.ppl, FAST, k.wps, k.obs, k.d, k.rh, true>;
+}
+template <class Rows> struct OptimizeMixedKernelTable;
+template <int... I> struct OptimizeMixedKernelTable<std::integer_sequence<int, I...>> { static constexpr MixedSolveKernel row[] = {optimize_mixed_kernel_of<I>()...}; };
+MixedSolveKernel optimize_mixed_kernel(int key) { return OptimizeMixedKernelTable<std::make_integer_sequence<int, kOptimizeMixedKeyCount>>::row[key]; }
+MixedSolveKernel cost_grad_mixed_kernel(int precision, int group) {
+    // rows: fp32, fp64 fast, fp64; columns: the shapes 32 x 1, 64 x 1
+    static constexpr MixedSolveKernel kernels[3][2] = {
+        {&k_cost_grad<float, 32, 1, false, true>, &k_cost_grad<float, 64, 1, false, true>},
+        {&k_cost_grad<double, 32, 1, true, true>, &k_cost_grad<double, 64, 1, true, true>},
+        {&k_cost_grad<double, 32, 1, false, true>, &k_cost_grad<double, 64, 1, false, true>}};
+    return kernels[precision == VIGO_PREC_F32 ? 0 : (precision == VIGO_PREC_F64_FAST ? 1 : 2)][group / 64];
+}
+#elif VIGO_SOLVER_PART == 1
 SolveKernel optimize_kernel_with_obstacles(int key) { return optimize_kernel(key); }
 #else
 SolveKernel optimize_kernel_with_obstacles(int key);
+MixedSolveKernel optimize_mixed_kernel(int key);
+MixedSolveKernel cost_grad_mixed_kernel(int precision, int group);
 // dev builds only (-DVIGO_EXP_AXIS_SWITCH=1, tools/exp_solver.py): VIGO_EXP_AXIS=0 in the environment, read at every
 // launch, keeps the axis-per-lane level kernel out of the dispatch, so that one process times both — never defined
 // in the shipped library
@@ -1757,6 +1809,27 @@ int launch_optimize(hipStream_t s, const SolveArgs& a_in, const DevConst& k, con
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     }
     return (int)hipSuccess;
+}
+
+// The mixed-count entries: a.N is the row stride Ns (7 .. 64, checked by the C ABI), a.n_pts the counts.  ONE launch of
+// the general kernel (plan_optimize_mixed); its LDS stays below the static limit, so no attribute is raised.
+int launch_cost_grad_mixed(hipStream_t s, const MixedSolveArgs& a, const DevConst* kd, int precision) {
+    if (a.B <= 0) return hipSuccess;
+    const Shape sh = shape_for(a.N);
+    if (sh.ppl != 1 || !a.n_pts) return (int)hipErrorInvalidValue;
+    const int tpb = kWave / sh.group;
+    hipLaunchKernelGGL(cost_grad_mixed_kernel(precision, sh.group), dim3((a.B + tpb - 1) / tpb), dim3(kWave), 0, s, a, kd);
+    return (int)hipGetLastError();
+}
+int launch_optimize_mixed(hipStream_t s, const MixedSolveArgs& a_in, const DevConst& k, const DevConst* kd, int precision, LaunchState& L) {
+    if (a_in.B <= 0) return hipSuccess;
+    const OptimizePlan plan = plan_optimize_mixed(a_in.N, a_in.B, precision, a_in.obs != nullptr, k.mem_size, L.simd_count);
+    if (plan.count != 1 || !a_in.n_pts) return (int)hipErrorInvalidValue;
+    const PlannedLaunch& p = plan.launch[0];
+    MixedSolveArgs a = a_in;
+    a.level_waves_elsewhere = p.level_waves_elsewhere;
+    hipLaunchKernelGGL(optimize_mixed_kernel(p.key), dim3(p.grid), dim3(kWave), p.lds, s, a, kd);
+    return (int)hipGetLastError();
 }
 #endif  // VIGO_SOLVER_PART
 

@@ -158,4 +158,42 @@ inline OptimizePlan plan_optimize(int N, int B, int precision, bool has_obstacle
     return p;
 }
 
+// ---- mixed control-point counts (vigo_*_mixed) --------------------------------------------------------------------
+// k_optimize<.., MIXED = true>: trajectories of different counts in one launch, rows strided by Ns.  Only the general
+// kernel (D = 3, OBS) is built that way — it treats a missing obstacle list as no obstacles and solves a level trajectory
+// with its z terms masked, the same bits as the level / no-obstacle kernels — for the two shapes with one point per lane.
+// A list of its own: kOptimizeKeys, its order and the bits of the "LDS limit raised" mask stay as they are; the index of a
+// key here is its row in the mixed kernel table of vigo_solver.hip (part 2 of that file).
+constexpr int kMixedMaxStride = 64;
+constexpr OptimizeKey kOptimizeMixedKeys[] = {
+    {kF32, 32, 1, 2, true, 3, 1}, {kF32, 32, 1, 1, true, 3, 1}, {kF32, 64, 1, 2, true, 3, 1}, {kF32, 64, 1, 1, true, 3, 1},
+    {kFast, 32, 1, 2, true, 3, 1}, {kFast, 32, 1, 1, true, 3, 1}, {kFast, 64, 1, 2, true, 3, 1}, {kFast, 64, 1, 1, true, 3, 1},
+    {kF64, 32, 1, 2, true, 3, 1}, {kF64, 32, 1, 1, true, 3, 1}, {kF64, 64, 1, 2, true, 3, 1}, {kF64, 64, 1, 1, true, 3, 1},
+};
+constexpr int kOptimizeMixedKeyCount = sizeof(kOptimizeMixedKeys) / sizeof(kOptimizeMixedKeys[0]);
+constexpr int optimize_mixed_key_index(int precision, int group, int wps) {   // -1: no such instantiation
+    for (int i = 0; i < kOptimizeMixedKeyCount; ++i) {
+        const OptimizeKey& c = kOptimizeMixedKeys[i];
+        if (c.precision == precision && c.group == group && c.wps == wps) return i;
+    }
+    return -1;
+}
+// every count of a mixed call lies in the shape class of its stride: all <= 32, or all in 33 .. 64
+constexpr bool mixed_count_ok(int n, int Ns) { return n >= 7 && n <= Ns && Ns <= kMixedMaxStride && shape_for(n).group == shape_for(Ns).group; }
+
+// The ONE launch of a vigo_optimize_mixed call of B > 0 trajectories in rows of Ns control points (key: the index into
+// kOptimizeMixedKeys); count -1: Ns outside [7, 64].  The LDS is sized by Ns and always holds the obstacle table, with a
+// list or without (has_obstacle_list does not enter: one kernel per (Ns, B, precision, mem_size), whatever the lists): at
+// most 40.9 KB, below the static limit, so no instantiation needs its limit raised.
+inline OptimizePlan plan_optimize_mixed(int Ns, int B, int precision, bool /*has_obstacle_list*/, int mem_size, int simd_count) {
+    if (Ns < 7 || Ns > kMixedMaxStride) return OptimizePlan{-1, {}};
+    const Shape sh = shape_for(Ns);
+    const int grid = (B + kWave / sh.group - 1) / (kWave / sh.group);
+    const bool crowded = grid > (simd_count > 0 ? simd_count : (1 << 30));
+    const size_t lds = optimize_lds_bytes(elem_bytes_of(precision), sh.group, precision == VIGO_PREC_F64_FAST, 3, Ns, mem_size, 1, true, 1);
+    const int key = optimize_mixed_key_index(precision, sh.group, crowded && lds <= kLdsPerWorkgroup / 8 ? 2 : 1);
+    if (key < 0 || lds > kLdsStaticLimit) return OptimizePlan{-1, {}};
+    return OptimizePlan{1, {PlannedLaunch{key, grid, lds, 0}, {}}};
+}
+
 }  // namespace vigo

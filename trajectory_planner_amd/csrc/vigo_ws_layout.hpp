@@ -59,6 +59,15 @@ inline size_t ws_rebound(void* base, size_t B, int32_t*& flags, int32_t*& idx) {
     return c.bytes();
 }
 
+// vigo_rebound_rounds_mixed: the same, then {T, T_static} of the gates for each count 7 .. Ns (Ns >= 7)
+inline size_t ws_rebound_mixed(void* base, size_t B, size_t Ns, int32_t*& flags, int32_t*& idx, int32_t*& count_tab) {
+    WsCarver c(base);
+    flags = c.take<int32_t>(16);
+    idx = c.take<int32_t>(B + 16);
+    count_tab = c.take<int32_t>(2 * (Ns - 6));
+    return c.bytes();
+}
+
 // the per-trajectory scratch of vigo_collision_segs / vigo_path_search; want_flags: room for vigo_ctrl_occupancy's flags
 template <class Args>
 size_t ws_path_search_scratch(void* base, size_t B, size_t N, bool want_flags, Args& a) {

@@ -182,6 +182,19 @@ public:
         double weights[4];
     };
     static void setReguideStepLog(std::vector<ReguideStepRecord>* log);
+    /* Planners of DIFFERENT control-point counts in one device batch of the solves (solveBatch) and of the
+     * device-resident rebound rounds (deviceRounds): vigo_optimize_mixed / vigo_rebound_rounds_mixed.  Off (default): one
+     * device batch per distinct count.  On: planners that share everything but the count (sameBatchKey's other terms)
+     * share a batch when their counts lie in one shape class of the kernels — all 7 .. 32, or all 33 .. 64; counts above
+     * 64 keep a batch per count.  A group whose counts are all equal calls the uniform entry, so a workload of one
+     * count runs the same kernels under either setting; a planner's result is the same bits under either setting
+     * (include/vigo.h, "mixed control-point counts").  Every other stage keeps its grouping by exact count: the opt-in
+     * device stages (A*, prologue chain, re-guide), the gates of gateBatch, costGrad and the host-driven loop's gates. */
+    static void setMixedBatches(bool on);
+    static bool mixedBatches();
+    /* Process-wide running totals, under either setting: the device batches solveBatch and deviceRounds opened, and the
+     * planners in them */
+    static void mixedBatchTotals(long long* deviceBatches, long long* planners);
     /* updatePath() for many planners at once: the least-squares fits run as one device launch */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
@@ -319,6 +332,8 @@ private:
     bool termCost(int term, const Eigen::MatrixXd& controlPoints, double& cost, Eigen::MatrixXd& gradient);
     void reboundFinish(Rebound& r, bool ok);
     bool sameBatchKey(const bsplineTraj& o) const;                  // may share a device batch with o
+    bool sameBatchKeyAnyCount(const bsplineTraj& o) const;          // ... but for the control-point count
+    bool sameSolveGroup(const bsplineTraj& o) const;                // ... a batch of solveBatch / deviceRounds (setMixedBatches)
     struct SearchGroup;                                             // ... and what its device A* searches share on top
     void fillParams(vigo_params_s* P) const;
     static void solveBatch(const std::vector<bsplineTraj*>& ps);   // one vigo_optimize for all

@@ -62,22 +62,34 @@ inline void appendObstacles(const trajPlanner::optData& od, std::vector<double>&
     }
 }
 
-// B trajectories of N control points each, added one planner at a time
+// B trajectories in rows of N control points each, added one planner at a time.  A planner of n < N control points (the
+// layout of the vigo_*_mixed entries, include/vigo.h) owns the first n points of its row: the rest is zeros, the padded
+// points have empty guide lists — control point i of trajectory b is entry b * N + i of goff either way — and npts holds n.
 struct HostBatch {
     int B = 0, N;
     std::vector<double> ctrl, gpv, obs, weights;
-    std::vector<int32_t> goff{0}, ooff{0};
-    explicit HostBatch(int n) : N(n) {}
-    // controlPoints: 3 x N column by column; w: (distance, smoothness, feasibility, dynamic)
-    void add(const double* controlPoints, const trajPlanner::optData& od, const std::array<double, 4>& w) {
-        ctrl.insert(ctrl.end(), controlPoints, controlPoints + 3 * N);
-        appendGuides(od, N, goff, gpv);
+    std::vector<int32_t> goff{0}, ooff{0}, npts;
+    explicit HostBatch(int stride) : N(stride) {}
+    // controlPoints: 3 x n column by column, n <= N; w: (distance, smoothness, feasibility, dynamic)
+    void add(const double* controlPoints, int n, const trajPlanner::optData& od, const std::array<double, 4>& w) {
+        ctrl.insert(ctrl.end(), controlPoints, controlPoints + 3 * n);
+        ctrl.resize(ctrl.size() + 3 * (size_t)(N - n), 0.0);
+        appendGuides(od, n, goff, gpv);
+        goff.resize(goff.size() + (size_t)(N - n), goff.back());
         appendObstacles(od, obs);
         ooff.push_back((int32_t)(obs.size() / 9));
         weights.insert(weights.end(), w.begin(), w.end());
+        npts.push_back(n);
         ++B;
     }
+    void add(const double* controlPoints, const trajPlanner::optData& od, const std::array<double, 4>& w) { add(controlPoints, N, od, w); }
     size_t guides() const { return gpv.size() / 6; }
+    bool uniform() const {                       // every trajectory fills its row: the batch of the uniform entries
+        for (int32_t n : npts)
+            if (n != N) return false;
+        return true;
+    }
+    const double* row(int b) const { return ctrl.data() + (size_t)b * 3 * N; }
 };
 
 // fn(members) for every group of the indices [0, n): the lead is the first index not in a group yet, the members are

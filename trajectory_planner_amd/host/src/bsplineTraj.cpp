@@ -107,9 +107,18 @@ void bsplineTraj::fillParams(vigo_params_s* Pp) const {
 // box of it to snapshot (setMapRegion), the same control-point count, gate step (maxVel_) and every parameter of fillParams() except the four weights, which
 // travel per trajectory.
 bool bsplineTraj::sameBatchKey(const bsplineTraj& o) const {
-    if (!link_.sameTarget(o.link_) || maxVel_ != o.maxVel_ || notCheckRatio_ != o.notCheckRatio_ ||
-        optData_.controlPoints.cols() != o.optData_.controlPoints.cols())
-        return false;
+    return optData_.controlPoints.cols() == o.optData_.controlPoints.cols() && sameBatchKeyAnyCount(o);
+}
+// the batches of the solves and of the device rounds: under setMixedBatches the count may differ inside a shape class of
+// the kernels (7 .. 32 | 33 .. 64: the contract of the vigo_*_mixed entries)
+bool bsplineTraj::sameSolveGroup(const bsplineTraj& o) const {
+    const long na = optData_.controlPoints.cols(), nb = o.optData_.controlPoints.cols();
+    if (na == nb || !mixedBatches()) return na == nb && sameBatchKeyAnyCount(o);
+    if (na < 7 || nb < 7 || na > 64 || nb > 64 || (na <= 32) != (nb <= 32)) return false;
+    return sameBatchKeyAnyCount(o);
+}
+bool bsplineTraj::sameBatchKeyAnyCount(const bsplineTraj& o) const {
+    if (!link_.sameTarget(o.link_) || maxVel_ != o.maxVel_ || notCheckRatio_ != o.notCheckRatio_) return false;
     vigo_params_t a, b;
     this->fillParams(&a);
     o.fillParams(&b);

@@ -77,37 +77,59 @@ bool uploadBatch(vigo_handle_t h, const HostBatch& hb, DeviceBatch& d) {
         !st.obs.upload(hb.obs) || !st.weights.upload(hb.weights))
         return false;
     if (G && vigo_guides_unknown(h, (int64_t)G, st.gpv.get(), st.gunk.get()) != VIGO_OK) return false;
+    const bool mixed = !hb.uniform();
+    if (mixed && !st.npts.upload(hb.npts)) return false;
     d = {st.ctrl.get(), st.goff.get(), G ? st.gpv.get() : nullptr, G ? st.gunk.get() : nullptr, st.ooff.get(),
-         hb.obs.empty() ? nullptr : st.obs.get(), st.weights.get()};
+         hb.obs.empty() ? nullptr : st.obs.get(), st.weights.get(), mixed ? st.npts.get() : nullptr};
     return true;
 }
 
+namespace {
+std::atomic<bool> g_mixedBatches{false};
+std::atomic<long long> g_solveBatches{0}, g_solvePlanners{0};
+}  // namespace
+void bsplineTraj::setMixedBatches(bool on) { g_mixedBatches.store(on); }
+bool bsplineTraj::mixedBatches() { return g_mixedBatches.load(); }
+void bsplineTraj::mixedBatchTotals(long long* deviceBatches, long long* planners) {
+    if (deviceBatches) *deviceBatches = g_solveBatches.load();
+    if (planners) *planners = g_solvePlanners.load();
+}
+
 void bsplineTraj::solveBatch(const std::vector<bsplineTraj*>& ps) {
-    // groups of equal N share a launch (vigo_optimize takes one N per call)
-    auto same = [&](size_t a, size_t b) { return ps[a]->sameBatchKey(*ps[b]); };
+    // groups of equal N share a launch (vigo_optimize takes one N per call); under setMixedBatches the counts of one shape
+    // class do (vigo_optimize_mixed), in rows of the group's largest count
+    auto same = [&](size_t a, size_t b) { return ps[a]->sameSolveGroup(*ps[b]); };
     vigo_host::forEachGroup(ps.size(), same, [&](const std::vector<size_t>& grp) {
         bsplineTraj* lead = ps[grp[0]];
-        const int N = lead->optData_.controlPoints.cols();
+        int N = 0;        // the row stride: the group's one count, or its largest
+        for (size_t k : grp) N = std::max(N, (int)ps[k]->optData_.controlPoints.cols());
         for (size_t k : grp) ps[k]->lastStatus_ = VIGO_ERR_HIP;
-        if (N < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
+        if (lead->optData_.controlPoints.cols() < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
+        g_solveBatches += 1;
+        g_solvePlanners += (long long)grp.size();
         HostBatch hb(N);
         for (size_t k : grp) {
             const bsplineTraj* p = ps[k];
-            hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
+            hb.add(p->optData_.controlPoints.data(), (int)p->optData_.controlPoints.cols(), p->optData_,
+                   {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
         }
         static thread_local Staged<int32_t> dStatus;
         vigo_handle_t h = lead->link_.handle();
         std::vector<int32_t> status(hb.B);
         DeviceBatch d;
         if (!uploadBatch(h, hb, d) || !dStatus.alloc(status.size())) return;
-        if (!deviceCallOk(vigo_optimize(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr, dStatus.get(), nullptr, nullptr,
-                                        nullptr),
-                          "vigo_optimize", h))
+        // (a group of one count: the uniform entry, exactly as without the switch)
+        if (d.npts ? !deviceCallOk(vigo_optimize_mixed(h, hb.B, N, d.npts, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr,
+                                                       dStatus.get(), nullptr, nullptr, nullptr),
+                                   "vigo_optimize_mixed", h)
+                   : !deviceCallOk(vigo_optimize(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, nullptr, dStatus.get(), nullptr,
+                                                 nullptr, nullptr),
+                                   "vigo_optimize", h))
             return;
         if (!vigo_host::threadSync() || !batchStage().ctrl.download(hb.ctrl) || !dStatus.download(status)) return;
         for (int b = 0; b < hb.B; ++b) {
             // optData_.controlPoints = the last evaluated point, as costFunction leaves it (BT.cpp:803)
-            std::memcpy(ps[grp[b]]->optData_.controlPoints.data(), hb.ctrl.data() + (size_t)b * 3 * N, sizeof(double) * 3 * N);
+            std::memcpy(ps[grp[b]]->optData_.controlPoints.data(), hb.row(b), sizeof(double) * 3 * hb.npts[b]);
             ps[grp[b]]->lastStatus_ = status[b];
         }
     });
@@ -166,15 +188,19 @@ bool bsplineTraj::deviceResidentRebound() { return g_deviceResidentRebound.load(
 // state, queue the rounds (vigo_rebound_rounds), bring back what the host part of the loop needs.
 bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds) {
     bsplineTraj* lead = grp[0];
-    const int N = lead->optData_.controlPoints.cols();
+    int N = 0;            // the row stride: the group's one count, or (setMixedBatches) its largest
+    for (const bsplineTraj* p : grp) N = std::max(N, (int)p->optData_.controlPoints.cols());
     std::vector<int> prevStatus(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) { prevStatus[k] = grp[k]->lastStatus_; grp[k]->lastStatus_ = VIGO_ERR_HIP; }
-    if (N < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return false;
+    if (lead->optData_.controlPoints.cols() < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return false;
+    g_solveBatches += 1;
+    g_solvePlanners += (long long)grp.size();
     HostBatch hb(N);
     std::vector<vigo_rebound_state_t> state(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) {
         bsplineTraj* p = grp[k];
-        hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
+        hb.add(p->optData_.controlPoints.data(), (int)p->optData_.controlPoints.cols(), p->optData_,
+               {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
         vigo_rebound_state_t& st = state[k];
         std::memset(&st, 0, sizeof(st));
         st.status = VIGO_RB_ACTIVE;
@@ -196,9 +222,12 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
     if (!uploadBatch(lead->link_.handle(), hb, d) || !dState.upload(state)) return false;
     vigo_handle_t h = lead->link_.handle();
     const double dt = lead->link_.map()->getRes() / lead->maxVel_ / 2.0;  // BT.h:312
-    if (!deviceCallOk(vigo_rebound_rounds(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, dt, lead->notCheckRatio_, maxRounds,
-                                          dState.get()),
-                      "vigo_rebound_rounds", h))
+    if (d.npts ? !deviceCallOk(vigo_rebound_rounds_mixed(h, hb.B, N, d.npts, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, dt,
+                                                         lead->notCheckRatio_, maxRounds, dState.get()),
+                               "vigo_rebound_rounds_mixed", h)
+               : !deviceCallOk(vigo_rebound_rounds(h, hb.B, N, d.ctrl, d.goff, d.gpv, d.gunk, d.ooff, d.obs, 0, d.weights, dt, lead->notCheckRatio_,
+                                                   maxRounds, dState.get()),
+                               "vigo_rebound_rounds", h))
         return false;
     // everything is read back here: the solveBatch of the overflow planners below reuses the staging buffers
     if (!vigo_host::threadSync() || !batchStage().ctrl.download(hb.ctrl) || !batchStage().weights.download(hb.weights) || !dState.download(state))
@@ -209,7 +238,7 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
         const vigo_rebound_state_t& st = state[k];
         if (st.rounds == 0 && st.status == VIGO_RB_NEEDS_HOST) { overflow.push_back(k); continue; }
         // optData_.controlPoints = the last evaluated point, as costFunction leaves it (BT.cpp:803)
-        std::memcpy(p->optData_.controlPoints.data(), hb.ctrl.data() + k * 3 * N, sizeof(double) * 3 * N);
+        std::memcpy(p->optData_.controlPoints.data(), hb.row((int)k), sizeof(double) * 3 * hb.npts[k]);
         p->weightDistance_ = hb.weights[4 * k + 0];
         p->weightDynamicObstacle_ = hb.weights[4 * k + 3];
         p->lastStatus_ = st.lbfgs_status;
@@ -878,12 +907,13 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
 void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
     const int kRounds = 4;   // failCount reaches 4 after at most four device rounds: then every round needs A*
     std::vector<bsplineTraj*>& active = pb.active;
-    auto same = [&](size_t a, size_t b) { return active[a]->sameBatchKey(*active[b]); };
+    auto same = [&](size_t a, size_t b) { return active[a]->sameSolveGroup(*active[b]); };
     const double t0 = wallSeconds();
     const double budget = 0.03 * std::max<size_t>(1, active.size());
     while (!active.empty()) {
         const double tr0 = wallSeconds();
-        // one device batch per group of planners the lead's handle state fits
+        // one device batch per group of planners the lead's handle state fits (setMixedBatches: whatever their counts,
+        // within a shape class)
         std::vector<uint8_t> devOk(active.size(), 0);
         vigo_host::forEachGroup(active.size(), same, [&](const std::vector<size_t>& members) {
             std::vector<bsplineTraj*> grp;

@@ -121,7 +121,7 @@ struct bsplineTraj::SearchGroup {
 // solveBatch, deviceRounds, reguideOnDevice): the thread's next upload overwrites them
 struct BatchStage {
     Staged<double> ctrl, gpv, obs, weights;
-    Staged<int32_t> goff, ooff;
+    Staged<int32_t> goff, ooff, npts;
     Staged<uint8_t> gunk;
 };
 BatchStage& batchStage();
@@ -135,6 +135,7 @@ struct DeviceBatch {
     const int32_t* ooff;
     const double* obs;
     double* weights;
+    const int32_t* npts;     // null: every trajectory fills its row (HostBatch::uniform), the uniform entries apply
 };
 
 // hb into the calling thread's staging buffers, then map_->isUnknown(guidePoint) (BT.cpp:841) for its guides, hoisted

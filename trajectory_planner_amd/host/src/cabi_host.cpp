@@ -1053,6 +1053,13 @@ struct BatchFixture {
         nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
         for (int t = 0; t < n; ++t) in.push_back(pathFromXyz(path_xyz + (size_t)t * n_pts * 3, n_pts));
     }
+    // ... the same with a pose list per planner: path t = poses path_off[t] .. path_off[t + 1] - 1 of path_xyz
+    BatchFixture(const unsigned char* vox, const int* dims, const double* origin, double res, const double* cfg, int n, const int* path_off,
+                 const double* path_xyz)
+        : BatchFixture(vox, nullptr, 1, dims, origin, res, cfg, 0, 0, path_xyz) {
+        cond.assign(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
+        for (int t = 0; t < n; ++t) in.push_back(pathFromXyz(path_xyz + (size_t)path_off[t] * 3, path_off[t + 1] - path_off[t]));
+    }
 };
 
 // new planners for one run, planner t on map t % n_maps, through updatePathBatch
@@ -1854,12 +1861,46 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
     return rc;
 }
 
+// n planners with a pose list each (path t: poses path_off[t] .. path_off[t + 1] - 1 of path_xyz, at least 2) through
+// updatePathBatch + makePlanBatch on one dense byte grid, fresh planners every run, `reps` rounds over
+//   slot 0  setMixedBatches(false)   one device batch per control-point count
+//   slot 1  setMixedBatches(true)    counts of one shape class share the batches of the solves and of the device rounds
+// in turn.  Outputs per slot [2] x ... of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl
+// (zero padded), n_seg + segs (collisionSeg_), n_guides + guides; per run total_ms[2][reps]; counts[2][2]:
+// mixedBatchTotals' device batches and planners of the slot's last run.  The switch is off on return.  Returns 0, -2
+// when a buffer is too small, -1 on a bad argument.  Needs a GPU.
+int vigo_host_plan_batch_mixed(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                               const double* path_xyz, const double* cfg, int reps, int ncp_cap, long long cap, int* ok, int* solver, int* ncp,
+                               double* ctrl, int* n_seg, int* segs, int* n_guides, double* guides, double* total_ms, long long* counts) {
+    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+    int rc = 0;
+    for (int rep = 0; rep < reps && rc == 0; ++rep)
+        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
+            const FreshPlanners fp = freshPlanners(fx);
+            bsplineTraj::setMixedBatches(slot == 1);
+            long long b0, p0, b1, p1;
+            bsplineTraj::mixedBatchTotals(&b0, &p0);
+            const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
+            bsplineTraj::mixedBatchTotals(&b1, &p1);
+            bsplineTraj::setMixedBatches(false);
+            if (rep + 1 < reps) continue;
+            counts[2 * slot] = b1 - b0;
+            counts[2 * slot + 1] = p1 - p0;
+            rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, nullptr, nullptr);
+        }
+    bsplineTraj::setMixedBatches(false);
+    return rc;
+}
+
 // the facade's opt-in switches as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
-// deviceReguide (0: everything off, the default)
+// deviceReguide, bit 6 mixedBatches (0: everything off, the default)
 int vigo_host_switches() {
     using trajPlanner::bsplineTraj;
     return (bsplineTraj::deviceAstar() ? 1 : 0) | (bsplineTraj::deviceGuides() << 1) | (bsplineTraj::devicePrologue() ? 8 : 0) |
-           (bsplineTraj::deviceReguide() << 4);
+           (bsplineTraj::deviceReguide() << 4) | (bsplineTraj::mixedBatches() ? 64 : 0);
 }
 
 }  // extern "C"

@@ -195,6 +195,62 @@ def make_bspline_batch(world: World, B: int, N: int, seed: int, start_range: flo
                  obs_off, obs, None, {"seed": seed, "K": K})
 
 
+@dataclass
+class PaddedBatch(Batch):
+    """Trajectories of different length in rows of Ns = ctrl.shape[1] control points (the layout of the vigo_*_mixed
+    entries): trajectory b owns the first n_pts[b] points of its row, control point i of it is entry b * Ns + i of
+    guide_off, and the padded points hold zeros and empty guide lists."""
+    n_pts: Optional[np.ndarray] = None     # [B] i32
+
+
+def pad_batches(batches, interleave: bool = False, Ns: Optional[int] = None):
+    """Concatenates uniform Batches of different N into one PaddedBatch with rows of Ns (default: the largest N) control
+    points: padded ctrl, re-based guide_off / obs_off, concatenated pairs and obstacles, n_pts.  Returns (padded, rows):
+    rows[k] = the output rows of batches[k]'s trajectories, in their order — consecutive ranges, or (interleave) dealt
+    round-robin over the batches, so that neighbouring rows (the two trajectories of a wavefront) differ in length.
+    Obstacles and weights are kept when ANY batch has them (no obstacles / the unit weights w for the others must be
+    given by the caller: a batch without weights among batches with them is an error)."""
+    Ns = max(b.N for b in batches) if Ns is None else Ns
+    assert all(b.N <= Ns for b in batches), "a batch has more control points than the row stride"
+    if interleave:
+        left = [list(range(b.B)) for b in batches]
+        order = []
+        while any(left):
+            order += [(k, q.pop(0)) for k, q in enumerate(left) if q]
+    else:
+        order = [(k, r) for k, b in enumerate(batches) for r in range(b.B)]
+    B = len(order)
+    rows = [np.array([i for i, (k, _) in enumerate(order) if k == kk], dtype=np.int64) for kk in range(len(batches))]
+    have_obs = any(b.obs is not None for b in batches)
+    have_w = any(b.weights is not None for b in batches)
+    assert not have_w or all(b.weights is not None for b in batches), "weights on some batches only"
+    ctrl = np.zeros((B, Ns, 3))
+    n_pts = np.zeros(B, dtype=np.int32)
+    counts = np.zeros((B, Ns), dtype=np.int64)
+    pv, unk, obs, obs_cnt = [], [], [], np.zeros(B, dtype=np.int64)
+    for i, (k, r) in enumerate(order):
+        b = batches[k]
+        n = b.N
+        ctrl[i, :n] = b.ctrl[r]
+        n_pts[i] = n
+        off = b.guide_off[r * n:(r + 1) * n + 1].astype(np.int64)
+        counts[i, :n] = np.diff(off)
+        pv.append(b.guide_pv[off[0]:off[-1]])
+        unk.append(b.guide_unk[off[0]:off[-1]])
+        if b.obs is not None:
+            o0, o1 = (int(b.obs_off[r]), int(b.obs_off[r + 1])) if b.obs_off is not None else (0, len(b.obs))
+            obs.append(b.obs[o0:o1])
+            obs_cnt[i] = o1 - o0
+    guide_off = np.zeros(B * Ns + 1, dtype=np.int32)
+    guide_off[1:] = np.cumsum(counts.reshape(-1))
+    obs_off = np.concatenate([[0], np.cumsum(obs_cnt)]).astype(np.int32) if have_obs else None
+    return PaddedBatch(ctrl, guide_off, np.ascontiguousarray(np.concatenate(pv).reshape(-1, 6)),
+                       np.concatenate(unk).astype(np.uint8), obs_off,
+                       np.ascontiguousarray(np.concatenate(obs).reshape(-1, 9)) if have_obs else None,
+                       np.stack([batches[k].weights[r] for k, r in order]) if have_w else None,
+                       {"Ns": Ns}, n_pts), rows
+
+
 def config2(B: int = 1024, N: int = 32, grid: int = 256, n_boxes: int = 200, world: Optional[World] = None,
             n_obs: int = 0):
     """BASELINE.json configs[1]: 1024 trajectories x 32 control points, 256^3 voxel grid."""

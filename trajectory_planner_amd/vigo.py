@@ -295,6 +295,84 @@ class Vigo:
                                                   float(not_check_ratio), int(max_rounds),
                                                   _ptr(state, torch.int32, "state", self.device)), "vigo_rebound_rounds")
 
+    # ---- mixed control-point counts: rows of Ns control points, n_pts[b] of them trajectory b's -------------------
+    def _mixed_ptrs(self, n_pts, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, weights):
+        """the uniform entries' pointers (ctrl [B,Ns,3], guide_off [B*Ns+1]) and n_pts int32 [B].  The counts are device
+        data: the kernels check them per trajectory (include/vigo.h, "mixed control-point counts")."""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, Ns = ctrl.shape[0], ctrl.shape[1]
+        if n_pts is not None:
+            _shape(n_pts, (B,), "n_pts")
+        return self._solve_ptrs(ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, weights) + (
+            _ptr(n_pts, torch.int32, "n_pts", self.device),)
+
+    def cost_grad_mixed(self, n_pts, ctrl, guide_off=None, guide_pv=None, guide_unk=None, obs_off=None, obs=None,
+                        weights=None, want_terms=True, out=None):
+        """vigo_cost_grad_mixed: returns (cost[B], grad[B,Ns-6,3], terms[B,4] or None); rows of grad beyond
+        n_pts[b] - 6 are not written.  out: caller-owned (cost, grad, terms) to write into."""
+        B, Ns, pc, po, ppv, pu, poo, pob, ns, pw, pn = self._mixed_ptrs(n_pts, ctrl, guide_off, guide_pv, guide_unk,
+                                                                         obs_off, obs, weights)
+        if out is not None:
+            cost, grad, terms = out
+            _shape(cost, (B,), "out cost"); _shape(grad, (B, max(Ns - 6, 0), 3), "out grad"); _shape(terms, (B, 4), "out terms")
+            for t, name in ((cost, "out cost"), (grad, "out grad"), (terms, "out terms")):
+                _ptr(t, torch.float64, name, self.device)
+        else:
+            cost = torch.zeros(B, dtype=torch.float64, device=self.device)
+            grad = torch.zeros(B, max(Ns - 6, 0), 3, dtype=torch.float64, device=self.device)
+            terms = torch.zeros(B, 4, dtype=torch.float64, device=self.device) if want_terms else None
+        self._check(self._lib.vigo_cost_grad_mixed(self._h, B, Ns, pn, pc, po, ppv, pu, poo, pob, ns, pw,
+                                                   C.c_void_p(cost.data_ptr()), C.c_void_p(grad.data_ptr()),
+                                                   C.c_void_p(terms.data_ptr()) if terms is not None else None),
+                    "vigo_cost_grad_mixed")
+        return cost, grad, terms
+
+    def optimize_mixed(self, n_pts, ctrl, guide_off=None, guide_pv=None, guide_unk=None, obs_off=None, obs=None,
+                       weights=None, inplace=False, out: Optional[SolveResult] = None) -> SolveResult:
+        """vigo_optimize_mixed.  ctrl [B,Ns,3] is cloned unless inplace=True; x is [B,Ns-6,3], its rows beyond
+        n_pts[b] - 6 (and every output of a trajectory with a bad count but its status) are not written: zeros, or
+        what the caller's `out` held."""
+        work = ctrl if inplace else ctrl.clone()
+        B, Ns, pc, po, ppv, pu, poo, pob, ns, pw, pn = self._mixed_ptrs(n_pts, work, guide_off, guide_pv, guide_unk,
+                                                                         obs_off, obs, weights)
+        d = self.device
+        if out is not None:
+            _shape(out.x, (B, max(Ns - 6, 0), 3), "out.x")
+            for name in ("status", "iters", "evals", "fx"):
+                _shape(getattr(out, name), (B,), f"out.{name}")
+            _ptr(out.x, torch.float64, "out.x", d)
+            _ptr(out.fx, torch.float64, "out.fx", d)
+            for name in ("status", "iters", "evals"):
+                _ptr(getattr(out, name), torch.int32, f"out.{name}", d)
+            out.ctrl = work
+        else:
+            out = SolveResult(
+                ctrl=work,
+                x=torch.zeros(B, max(Ns - 6, 0), 3, dtype=torch.float64, device=d),
+                status=torch.zeros(B, dtype=torch.int32, device=d),
+                fx=torch.zeros(B, dtype=torch.float64, device=d),
+                iters=torch.zeros(B, dtype=torch.int32, device=d),
+                evals=torch.zeros(B, dtype=torch.int32, device=d),
+            )
+        self._check(self._lib.vigo_optimize_mixed(self._h, B, Ns, pn, pc, po, ppv, pu, poo, pob, ns, pw,
+                                                  C.c_void_p(out.x.data_ptr()), C.c_void_p(out.status.data_ptr()),
+                                                  C.c_void_p(out.fx.data_ptr()), C.c_void_p(out.iters.data_ptr()),
+                                                  C.c_void_p(out.evals.data_ptr())), "vigo_optimize_mixed")
+        return out
+
+    def rebound_rounds_mixed(self, n_pts, ctrl, guide_off, guide_pv, guide_unk, obs_off, obs, weights, gate_dt, state,
+                             max_rounds=4, not_check_ratio=0.0):
+        """vigo_rebound_rounds_mixed: ctrl [B,Ns,3], weights [B,4] and state [B, REBOUND_STATE_INTS] are updated in place."""
+        B, Ns, pc, po, ppv, pu, poo, pob, ns, pw, pn = self._mixed_ptrs(n_pts, ctrl, guide_off, guide_pv, guide_unk,
+                                                                         obs_off, obs, weights)
+        if weights is None:
+            raise ValueError("weights [B,4] are required (the loop doubles them per trajectory)")
+        _shape(state, (B, self.REBOUND_STATE_INTS), "state")
+        self._check(self._lib.vigo_rebound_rounds_mixed(self._h, B, Ns, pn, pc, po, ppv, pu, poo, pob, ns, pw, float(gate_dt),
+                                                        float(not_check_ratio), int(max_rounds),
+                                                        _ptr(state, torch.int32, "state", self.device)),
+                    "vigo_rebound_rounds_mixed")
+
     # ---- spline fit, evaluation and gates -----------------------------------------------
     def bspline_fit(self, points, conds=None, ts=None):
         """bspline::parameterizeToBspline for a batch: points [B,K,3] (+ conds [B,4,3]) -> ctrl [B,K+2,3]"""
