@@ -301,6 +301,17 @@ __device__ __forceinline__ double over_ys(double a, const YSv<false>& y, double&
     return __builtin_fma(e, y.r, q);
 }
 
+// Which two-loop recursion k_optimize's `two_loop` runs: STEADY (value) = the history is full, straight-line code; MARK =
+// it divides by ys with Markstein's sequence and reports whether it has to be repeated with true divisions.
+template <bool STEADY, bool MARK>
+struct TwoLoopTag {
+    static constexpr bool value = STEADY;
+};
+template <bool FAST, bool STEADY>
+constexpr bool two_loop_mark(std::integral_constant<bool, STEADY>) { return STEADY && !FAST; }
+template <bool FAST, bool STEADY, bool MARK>
+constexpr bool two_loop_mark(TwoLoopTag<STEADY, MARK>) { return MARK; }
+
 // one L-BFGS history pair of one control point as it sits in LDS (48 B in fp64: three
 // conflict-free ds_read_b128 per lane, one address register)
 template <typename T, int D = 3>
@@ -1437,14 +1448,23 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
         // bound` is true at compile time, so the 32 steps are straight-line code — no exec-mask
         // blocks, no merge copies of the window registers, LDS fetches hoisted freely — and the
         // alphas stay in registers.  Same operations in the same order as the general path.
+        // MARK: the divisions by ys are Markstein's sequence on the stored reciprocal (over_ys); the result says whether
+        // the recursion has to be repeated with true divisions (a dividend outside 2^+-500, a NaN reciprocal or a NaN in d).
+        // A plain std::true_type / std::false_type tag: the steady-state recursion alone divides that way, unless FAST.
+        // A TwoLoopTag (AXIS) names both.
         auto two_loop = [&](auto steady_tag) -> bool {
             constexpr bool STEADY = decltype(steady_tag)::value;
-            constexpr bool MARK = STEADY && !FAST;
+            constexpr bool MARK = two_loop_mark<FAST>(decltype(steady_tag){});
             double amin = 1.0, amax = 1.0;
             // (general path: every live lane of the wave is in the same iteration, so the number of pairs is taken
             // through an SGPR — `age < bnd` becomes a scalar branch instead of a compare + exec-mask block per step)
             const int bnd = STEADY ? kMaxMem : __builtin_amdgcn_readfirstlane(bound);
-            double al_reg[STEADY ? kMaxMem : 1];
+            // the alphas stay in registers: STEADY, and (AXIS) the general path as well — the indices are literals after
+            // unrolling, the two paths are never live together, and al_l goes unused (the LDS layout keeps its place).
+            // (Measured and left off, profiles/README.md, round 6: the AXIS general path walking the ring by running byte
+            // offsets as the steady path does, wrapping at ms slots — 52 v_mul_lo_u32 fewer, and slower.)
+            constexpr bool REGAL = STEADY || AXIS;
+            double al_reg[REGAL ? kMaxMem : 1];
             // STEADY: the LDS ring (kMaxMem - RH - 1 slots) is walked with running byte offsets — one
             // add and a wrap per fetch instead of slot arithmetic and two quarter-rate multiplies
             constexpr int kRing = kMaxMem - (RH + 1);
@@ -1501,7 +1521,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
                     const int w = age % kWin;
                     double al = group_sum1<GROUP>(dot_lane<FAST, T, PPL, D>(Ps[w], d));
                     al = over_ys<MARK>(al, Pys[w], amin, amax);
-                    if (STEADY) al_reg[STEADY ? age : 0] = al;
+                    if (REGAL) al_reg[REGAL ? age : 0] = al;
                     else al_l[age * TPB] = al;         // alpha_j parks in LDS at a static offset
                     {
                         const T na = (T)(-al);     // (points that are not free hold y = 0: no select, see ROWP)
@@ -1539,7 +1559,7 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
                     const int w = age % kWin;
                     double beta = group_sum1<GROUP>(dot_lane<FAST, T, PPL, D>(Py[w], d));
                     beta = over_ys<MARK>(beta, Pys[w], amin, amax);
-                    const double cod = (STEADY ? al_reg[STEADY ? age : 0] : al_l[age * TPB]) - beta;
+                    const double cod = (REGAL ? al_reg[REGAL ? age : 0] : al_l[age * TPB]) - beta;
                     {
                         const T co = (T)cod;
 #pragma unroll
@@ -1562,7 +1582,18 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
             return bad;
         };
         VIGO_TICK(t_upd);
-        if (PPL == 1 && bound == kMaxMem && !__any(last != __builtin_amdgcn_readfirstlane(last))) {
+        if constexpr (AXIS) {
+            // Both recursions divide with Markstein's sequence — the warm-up iterations (history not yet full) on the
+            // general path — and share ONE true-division recursion, the general one, for the two-loops that report `bad`.
+            bool bad;
+            if (bound == kMaxMem && !__any(last != __builtin_amdgcn_readfirstlane(last))) bad = two_loop(TwoLoopTag<true, true>{});
+            else bad = two_loop(TwoLoopTag<false, true>{});
+            if (__any(bad)) {
+                asm volatile("" ::: "memory");
+                d[0][0] = -g[0][0];
+                two_loop(TwoLoopTag<false, false>{});
+            }
+        } else if (PPL == 1 && bound == kMaxMem && !__any(last != __builtin_amdgcn_readfirstlane(last))) {
             if (__any(two_loop(std::true_type{}))) {
                 // a dividend outside the range Markstein's sequence is proven for (or a NaN): the same
                 // recursion again from d = -g on the general path, which divides for real
