@@ -31,8 +31,18 @@
 #include <type_traits>
 #include <utility>
 
+#include "vigo_exact_div.hpp"
 #include "vigo_internal.hpp"
 #include "vigo_solver_plan.hpp"
+
+// dev switches of the axis kernel's two short forms (vigo_exact_div.hpp; profiles/README.md, round 7): the stencil's
+// divisions by ts_ctrl as Markstein's sequence, the convergence test behind the squared-norm filter
+#ifndef VIGO_AXIS_TS_MARK
+#define VIGO_AXIS_TS_MARK 1
+#endif
+#ifndef VIGO_AXIS_CONV_FILTER
+#define VIGO_AXIS_CONV_FILTER 1
+#endif
 
 namespace vigo {
 namespace {
@@ -365,6 +375,11 @@ struct HotConst {
     double ts_ctrl, ts_inv_sqr;                                  // stencils
     double g_epsilon, min_step, max_step, ftol, gtol, xtol;      // L-BFGS and the line search
     int max_iterations, max_linesearch;
+    // derived once at entry (vigo_exact_div.hpp): RN(1 / ts_ctrl) and the bound below which the velocity stencil's first
+    // dividend lets both of its divisions take Markstein's sequence (ConstDiv's lim2; NaN and 0 for a ts_ctrl outside
+    // 2^+-500); RN(g_epsilon^2) and whether the convergence filter may decide at all
+    double ts_rcp, ts_lim, g_eps2;
+    int conv_ok;
     __device__ __forceinline__ explicit HotConst(const DevConst& K)
         : dth(K.dth), da(K.da), db(K.db), dc(K.dc), unc_factor(K.unc_factor), ts_ctrl(K.ts_ctrl), ts_inv_sqr(K.ts_inv_sqr),
           g_epsilon(K.g_epsilon), min_step(K.min_step), max_step(K.max_step), ftol(K.ftol), gtol(K.gtol), xtol(K.xtol),
@@ -373,6 +388,11 @@ struct HotConst {
         hold_in_reg(ts_ctrl); hold_in_reg(ts_inv_sqr);
         hold_in_reg(g_epsilon); hold_in_reg(min_step); hold_in_reg(max_step); hold_in_reg(ftol); hold_in_reg(gtol); hold_in_reg(xtol);
         hold_in_reg(max_iterations); hold_in_reg(max_linesearch);
+        const ConstDiv cd = make_const_div(ts_ctrl);
+        const ConvFilter cf = make_conv_filter(g_epsilon);
+        ts_rcp = cd.r; ts_lim = cd.lim2; g_eps2 = cf.eps2;
+        conv_ok = __builtin_amdgcn_readfirstlane((int)cf.ok);   // (from g_epsilon in a vector register: the same in every lane)
+        hold_in_reg(ts_rcp); hold_in_reg(ts_lim); hold_in_reg(g_eps2); hold_in_reg(conv_ok);
     }
 };
 template <bool HOT>
@@ -492,6 +512,18 @@ __device__ __forceinline__ void obstacle_term_tab(const DevConst& K, const T (&c
     }
 }
 
+// The axis kernel's convergence test, G = g.g and X = x.x of the last evaluation (LB:1154-1157 on the first trip,
+// LB:1200-1225 per iteration): conv_filter decides from the squared norms wherever its guard band allows; undecided —
+// every lane holds the same sums, so the branch is the wave's — it is the reference expression, as in every other kernel.
+__device__ __forceinline__ bool axis_converged(const HotConst& K, double G, double X) {
+    const int f = conv_filter(G, X, ConvFilter{K.g_eps2, K.conv_ok != 0});
+    if (__builtin_expect(!__any(f < 0), 1)) return f != 0;
+    double xnorm = sqrt(X);
+    const double gnorm = sqrt(G);
+    if (xnorm < 1.0) xnorm = 1.0;
+    return gnorm / xnorm <= K.g_epsilon;
+}
+
 // The smoothness and feasibility stencils of ONE coordinate, C = that coordinate of the lane's points: jerk, velocity
 // and acceleration terms (jj, vv, aa: the cost partials of the term whose first point is the lane's) and the gradient
 // columns Gs, Gf of the lane's points.  no_terms: the z coordinate of a level trajectory in the general kernel.
@@ -514,12 +546,39 @@ __device__ __forceinline__ void stencil_axis(const KC& K, const T (&C)[PPL], boo
         gt0[q] = T(2.0) * J0;                                          // gradTemp
         jj[q] = (double)(J0 * J0);
         // feasibility, BT.cpp:952-999 (limits hard-coded to 1.0, :955-956)
-        T evP = excess((P1[q] - C[q]) / ts);                           // velocity i
+        // AXIS (HotConst, fp64): both divisions by ts_ctrl as ConstDiv's quotient (vigo_exact_div.hpp) on the reciprocal
+        // taken at entry, behind ONE wave-uniform test of the first dividend: usable2 answers for the second dividend
+        // too, which is 2 excess(the first quotient).  A wave with a lane that fails it (NaN, infinite, too large, or
+        // ts_ctrl outside 2^+-500) divides twice.  What each quotient may rely on:
+        //   the first feeds excess() alone, which asks only whether it passes 1 in magnitude and returns the literal
+        //   +0.0 otherwise — what ConstDiv guarantees for EVERY usable dividend, -0 and the ones below 2^-500 included
+        //   (the lanes without a point hold a zero here, and no zero sends the wave to the division);
+        //   the second dividend is +0.0, in almost every lane, or 2 (|v| - 1) with |v| > 1: never -0 and never below
+        //   2^-51 in magnitude, so its quotient has the division's bits, the sign of the zero included.
+        constexpr bool kMark = VIGO_AXIS_TS_MARK && std::is_same_v<KC, HotConst> && std::is_same_v<T, double>;
+        T evP, gq = T(0);                                              // velocity i; (2 evP) / ts
+        if constexpr (kMark) {
+            const ConstDiv cd{K.ts_ctrl, K.ts_rcp, K.ts_lim, K.ts_lim};
+            T a = P1[q] - C[q];
+            if (__builtin_expect(__any(!cd.usable2(a)), 0)) {
+                hold_in_reg(a);   // keeps the divisions behind the branch: hoisted and selected, they are issued every time
+                evP = excess(a / ts);
+                if (no_terms) evP = T(0);
+                gq = (T(2) * evP) / ts;
+            } else {
+                evP = excess(cd.quotient(a));
+                if (no_terms) evP = T(0);
+                gq = cd.quotient(T(2) * evP);
+            }
+        } else {
+            evP = excess((P1[q] - C[q]) / ts);
+        }
         T eaP = excess((FAST ? fmaT(T(-2), P1[q], P2[q]) + C[q]
                              : (P2[q] - 2 * P1[q]) + C[q]) * tis);     // acceleration i
         if (no_terms) { evP = T(0); eaP = T(0); }
         // gradient(j,i+1) += 2(v-vmax)/ts*tsInvSqr, gradient(j,i) += the negation (exactly)
-        gv[q] = (T(2) * evP) / ts * tis;
+        if constexpr (!kMark) gq = (T(2) * evP) / ts;
+        gv[q] = gq * tis;
         // gradient(j,i), (j,i+2) += 2(a-amax)*tsInvSqr; gradient(j,i+1) += -4(..) = -2x that (exactly)
         ga[q] = (T(2) * eaP) * tis;
         vv[q] = (double)((evP * evP) * tis);
@@ -1335,15 +1394,19 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
         }
 
         VIGO_TICK(t_ls);
-        double xnorm = sqrt(sums[5]), gnorm = sqrt(sums[6]);
+        double xnorm = sqrt(sums[5]), gnorm = sqrt(sums[6]);   // (AXIS: axis_converged() takes the roots, where it needs them)
         if (first) {
             first = false;
 #pragma unroll
             for (int q = 0; q < PPL; ++q)
 #pragma unroll
                 for (int a = 0; a < D; ++a) d[q][a] = -g[q][a];  // LB:1144
-            if (xnorm < 1.0) xnorm = 1.0;
-            if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_ALREADY_MINIMIZED; break; }  // LB:1154-1157
+            if constexpr (AXIS && VIGO_AXIS_CONV_FILTER) {
+                if (axis_converged(KL, sums[6], sums[5])) { ret = LB_ALREADY_MINIMIZED; break; }
+            } else {
+                if (xnorm < 1.0) xnorm = 1.0;
+                if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_ALREADY_MINIMIZED; break; }  // LB:1154-1157
+            }
             // d = -g: d.d = g.g and g.d = -(g.g) exactly (negation commutes with every rounding)
             step = 1.0 / sqrt(sums[6]);  // LB:1163
             sums[4] = -sums[6];
@@ -1370,8 +1433,12 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
         }
 
         // convergence test, LB:1200-1225 (norms came with the last evaluation)
-        if (xnorm < 1.0) xnorm = 1.0;
-        if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_CONVERGENCE; break; }
+        if constexpr (AXIS && VIGO_AXIS_CONV_FILTER) {
+            if (axis_converged(KL, sums[6], sums[5])) { ret = LB_CONVERGENCE; break; }
+        } else {
+            if (xnorm < 1.0) xnorm = 1.0;
+            if (gnorm / xnorm <= KL.g_epsilon) { ret = LB_CONVERGENCE; break; }
+        }
         if (KL.max_iterations != 0 && KL.max_iterations < k + 1) { ret = LBERR_MAXIMUMITERATION; break; }
 
         // s, y, ys, yy — LB:1264-1276
