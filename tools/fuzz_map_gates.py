@@ -2,11 +2,14 @@
 shapes (odd extents, z not a multiple of 32), origins, resolutions, control-point counts, sample steps, obstacle
 lists, fit sizes and inflation radii.  Covers vigo_query_points, vigo_guides_unknown, vigo_traj_collision,
 vigo_traj_dynamic_collision, vigo_ctrl_occupancy, vigo_bspline_eval, vigo_bspline_fit (1e-9 vs the oracle's
-pivoted QR), vigo_inflate_grid, vigo_pack_grid, vigo_box_collision_points and vigo_esdf_query.  Not part of the test suite; run on the GPU box:
+pivoted QR), vigo_inflate_grid, vigo_pack_grid, vigo_box_collision_points and vigo_esdf_query.  Resolutions, grid
+shapes, ts_ctrl, N and dt are drawn from the named families of tests/gate_cases.py (which the suite runs case by case)
+next to random ones.  Not part of the test suite; run on the GPU box:
 python tools/fuzz_map_gates.py [cases] [seed]"""
 import ctypes as C, json, os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np, torch
+import gate_cases as gc
 import oracle_lib as ol
 from gpu_util import to_dev
 from trajectory_planner_amd import sharding, synth
@@ -27,25 +30,17 @@ def fail(case, what, **kw):
 
 
 for case in range(cases):
-    dims = tuple(int(x) for x in rng.integers(3, 90, size=3))
-    res = float(rng.choice([0.1, 0.2, 0.05, 0.13]))
+    dims = tuple(int(x) for x in rng.integers(3, 90, size=3)) if rng.random() < 0.7 else gc.LOOKUP_SHAPES[rng.integers(len(gc.LOOKUP_SHAPES))]
+    res = float(rng.choice(gc.RESOLUTIONS))
     origin = np.round(rng.uniform(-6, 2, size=3) / res) * res if rng.random() < 0.5 else rng.uniform(-6, 2, size=3)
     vox = ((rng.random(dims) < 0.03).astype(np.uint8) * 4 | (rng.random(dims) < 0.1).astype(np.uint8) * 2).astype(np.uint8)
     r = tuple(int(x) for x in rng.integers(0, 4, size=3))
     P = default_params()
-    P.ts_ctrl = float(rng.choice([0.1, 0.25, 0.07]))
+    P.ts_ctrl = float(rng.choice(gc.TS_CTRL[:-1]))
     v = Vigo(0, P, 0)
     # inflation (bit0 from bit2) against a numpy dilation, then the inflated bytes become the snapshot
     inflated = v.inflate_grid(to_dev(vox, v.device), *r).cpu().numpy()
-    ref = (vox & 4) != 0
-    for axis, rr in enumerate(r):
-        acc = ref.copy()
-        for d in range(1, rr + 1):
-            a = [slice(None)] * 3; b = [slice(None)] * 3
-            a[axis] = slice(d, None); b[axis] = slice(None, -d)
-            acc[tuple(a)] |= ref[tuple(b)]
-            acc[tuple(b)] |= ref[tuple(a)]
-        ref = acc
+    ref = gc.dilate_reference((vox & 4) != 0, r)
     if not (np.array_equal((inflated & 1) != 0, ref) and np.array_equal(inflated & 6, vox & 6)):
         fail(case, "inflate", dims=dims, r=r)
     world = synth.World(np.ascontiguousarray(inflated), origin, res, np.zeros((0, 6)))
@@ -63,9 +58,9 @@ for case in range(cases):
     if not np.array_equal(v.guides_unknown(to_dev(np.concatenate([pts, pts], 1), v.device)).cpu().numpy(), synth.lookup(world, pts, 1)):
         fail(case, "guides_unknown", dims=dims)
     # gates
-    N = int(rng.choice([4, 5, 7, 12, 20, 32, 33, 64, 100]))
+    N = int(rng.choice(sorted(set(gc.GATE_N) | {4, 5, 32, 33, 64, 100})))
     B = int(rng.integers(1, 40))
-    dt = float(rng.choice([0.05, 0.025, 0.01, 0.11]))
+    dt = float(rng.choice(gc.GATE_DT))
     start = origin + rng.uniform(0.1, 0.9, size=(B, 3)) * ext
     stepv = rng.normal(size=(B, 3)) * [1, 1, 0.1]
     stepv *= rng.uniform(0.05, 0.3, size=(B, 1)) / np.linalg.norm(stepv, axis=1, keepdims=True)

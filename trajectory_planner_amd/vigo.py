@@ -145,6 +145,16 @@ class Vigo:
                                             _ptr(voxels, torch.uint8, "voxels", self.device)), "vigo_set_grid")
         self._grid_meta = (nx, ny, nz, tuple(float(v) for v in origin), float(res))
 
+    def set_grid_host(self, voxels, origin, res: float):
+        """vigo_set_grid_host: voxels a C-contiguous uint8 numpy array [nx,ny,nz] in host memory (staged and packed)."""
+        if voxels.dtype.name != "uint8" or voxels.ndim != 3 or not voxels.flags["C_CONTIGUOUS"]:
+            raise ValueError("voxels: expected a C-contiguous uint8 array [nx,ny,nz]")
+        nx, ny, nz = voxels.shape
+        o = (C.c_double * 3)(*origin)
+        self._check(self._lib.vigo_set_grid_host(self._h, nx, ny, nz, o, float(res), C.c_void_p(voxels.ctypes.data)),
+                    "vigo_set_grid_host")
+        self._grid_meta = (nx, ny, nz, tuple(float(v) for v in origin), float(res))
+
     def inflate_grid(self, voxels: torch.Tensor, rx: int, ry: int, rz: int) -> torch.Tensor:
         """in place: bit0 := OR of bit2 over the (2rx+1)(2ry+1)(2rz+1) voxel box"""
         nx, ny, nz = voxels.shape
