@@ -129,7 +129,7 @@ int vigo_set_precision(vigo_handle_t h, int vigo_precision);
 const char* vigo_last_error(vigo_handle_t h);
 /* Library/ABI version (raised when entry points are added; nothing was removed or changed so far: 4 adds
  * vigo_build_esdf / vigo_esdf_from_voxels_host; vigo_seed_capacity / vigo_seed_paths / vigo_seed_paths_host came in at 4
- * as well — ask the library for the symbol), and whether the code object was built for gfx950. */
+ * as well, and so did vigo_bspline_fit_mixed after them — ask the library for the symbol), and whether the code object was built for gfx950. */
 int vigo_abi_version(void);
 const char* vigo_build_arch(void);
 /* "solver:<12 hex> all:<12 hex>": digests of the library's compiled code (host code and gfx950 code objects; the first
@@ -255,6 +255,32 @@ int vigo_check_lists(vigo_handle_t h, int B, int N, const int32_t* guide_off, in
  */
 int vigo_bspline_fit(vigo_handle_t h, int B, int K, double ts, const double* points,
                      const double* conds, double* ctrl_out);
+
+/*
+ * The same fit for T paths of DIFFERENT point counts in one call: the head of the mixed chain, its output is the
+ * `ctrl double[B][Ns][3]` + `n_pts int32[B]` input of vigo_optimize_mixed / vigo_rebound_rounds_mixed.  All arrays device.
+ *   n_fit     int32[T]                    waypoints K_t of path t
+ *   status    int32[T] or NULL            path t is fitted only if status[t] == 0
+ *   points    double[T][point_stride][3]  the first K_t rows of row t are its waypoints; nothing beyond them is read
+ *   conds     double[T][4][3] or NULL     as vigo_bspline_fit
+ *   ctrl_out  double[T][Ns][3]            rows 0 .. K_t+1 of row t are written, nothing beyond them
+ *   out_n_pts int32[T]                    K_t + 2 for a fitted path, 0 for one that was not
+ * 7 <= Ns <= 64, point_stride >= 1.  A path is fitted when 4 <= K_t <= min(Ns - 2, point_stride) and its status, if
+ * given, is 0; one that is not keeps its ctrl_out row as it was.  The counts are device data and checked per path:
+ * nothing is indexed with a count out of range, and every other path gets the bits it would get without it.
+ * Rows 0 .. K_t+1 of a fitted path equal, value for value, what vigo_bspline_fit(h, 1, K_t, ts, ...) gives for that
+ * path alone: they depend neither on its position in the batch, nor on the batch size, nor on its neighbours' counts.
+ * (The handle keeps the operators of every K = 4 .. 62 at one ts, 0.7 MB, built at the first call with a new ts by the
+ * arithmetic of vigo_bspline_fit's own set-up; the paths are regrouped by count on the device, so the host needs no
+ * knowledge of which counts occur.)  The shape-class rule of the mixed solve entries (all counts <= 32 or all in
+ * 33 .. 64) stays the solver's: the fit does not impose it.  point_stride / n_fit / status match vigo_seed_paths's
+ * point_cap / out_fit_n / out_status: its out_fit is passed as it lies.
+ * VIGO_ERR_INVALID_ARG: NULL handle, T < 0, point_stride < 1, ts not finite and > 0, a NULL required array with T > 0;
+ * VIGO_ERR_UNSUPPORTED_N: Ns outside [7, 64]; on an error nothing is written.  T == 0: VIGO_OK, nothing launched.
+ */
+int vigo_bspline_fit_mixed(vigo_handle_t h, int T, int Ns, double ts, const int32_t* n_fit, const int32_t* status,
+                           const double* points, int point_stride, const double* conds, double* ctrl_out,
+                           int32_t* out_n_pts);
 
 /*
  * Replaces: bspline::at (BS.cpp:32-58) on bspline(3, ctrl, ts_ctrl) and its

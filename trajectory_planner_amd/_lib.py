@@ -79,6 +79,7 @@ PROTOTYPES = {
     "vigo_optimize_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vigo_rebound_rounds_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _d, _d, _i, _vp]),
     "vigo_bspline_fit": (_i, [_vp, _i, _i, _d, _vp, _vp, _vp]),
+    "vigo_bspline_fit_mixed": (_i, [_vp, _i, _i, _d, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "vigo_bspline_eval": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "vigo_traj_collision": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp]),
     "vigo_traj_dynamic_collision": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _i, _vp]),

@@ -10,6 +10,7 @@
 #include "vigo_esdf_core.hpp"
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
+#include "vigo_fit_plan.hpp"
 #include "vigo_handle.hpp"
 #include "vigo_seed_core.hpp"
 #include "vigo_solver_plan.hpp"
@@ -52,7 +53,7 @@ int fail(vigo_handle_t h, int code, const char* what, hipError_t e = hipSuccess)
 // not kept).  A failed allocation leaves it empty.  Callers whose cache lives in the buffer invalidate it first.
 int reserve(vigo_handle_t h, vigo::BufId id, size_t need, size_t alloc) {
     static const char* const what[] = {
-        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(times)", "hipMalloc(scratch)",
+        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(scratch)",
         "hipMalloc(paths_ws[0])", "hipMalloc(paths_ws[1])", "hipMalloc(reguide_ws[0])", "hipMalloc(reguide_ws[1])",
         "hipMalloc(reguide_ws[2])", "hipMalloc(rebound)"};
     static_assert(sizeof(what) / sizeof(what[0]) == vigo::kBufCount, "one name per BufId, in its order");
@@ -699,6 +700,36 @@ int vigo_bspline_fit(vigo_handle_t h, int B, int K, double ts, const double* poi
         h->fit_ts = ts;
     }
     VIGO_HIP(h, (hipError_t)vigo::launch_bspline_fit(h->stream, B, K, h->buf[vigo::kBufFit].as<double>(), points, conds, ctrl_out));
+    return VIGO_OK;
+}
+
+int vigo_bspline_fit_mixed(vigo_handle_t h, int T, int Ns, double ts, const int32_t* n_fit, const int32_t* status,
+                           const double* points, int point_stride, const double* conds, double* ctrl_out, int32_t* out_n_pts) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (T < 0 || !(ts > 0) || !isfinite(ts) || point_stride < 1 || (T > 0 && (!n_fit || !points || !ctrl_out || !out_n_pts)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_bspline_fit_mixed: bad argument");
+    if (Ns < vigo::kFitMixedMinStride || Ns > vigo::kFitMixedMaxStride)
+        return fail(h, VIGO_ERR_UNSUPPORTED_N, "vigo_bspline_fit_mixed: Ns outside [7, 64]");
+    if (T == 0) return VIGO_OK;
+    // one-off per ts: the operator of EVERY count, each by k_fit_setup's arithmetic — the host never learns which occur
+    const bool build = h->fit_table_ts != ts;
+    if (build) {
+        h->fit_table_ts = 0.0;                          // no table cached while the buffer is made or refilled
+        const size_t need = vigo::fit_table_doubles() * sizeof(double);
+        VIGO_TRY(reserve(h, vigo::kBufFitTable, need, need));
+    }
+    int32_t *perm, *tab;
+    double* work;
+    VIGO_TRY(carve(h, vigo::kBufScratch, kSlack, [&](void* p) {
+        return vigo::ws_fit_mixed(p, (size_t)T, 2 * (vigo::kFitBins + 1), build ? vigo::fit_table_work_doubles() : 0, perm, tab, work);
+    }));
+    double* table = h->buf[vigo::kBufFitTable].as<double>();
+    if (build) {
+        VIGO_HIP(h, (hipError_t)vigo::launch_fit_setup_table(h->stream, ts, work, table));
+        h->fit_table_ts = ts;
+    }
+    VIGO_HIP(h, (hipError_t)vigo::launch_bspline_fit_mixed(h->stream, T, Ns, point_stride, table, n_fit, status, points, conds, perm,
+                                                           tab, ctrl_out, out_n_pts));
     return VIGO_OK;
 }
 

@@ -15,7 +15,11 @@
 //                 (2K + 6) * 24 algorithmic bytes per path: 4.1 TB/s (51 % of peak) at 65 536
 //                 paths x 30 waypoints, 2.0 TB/s at 62 waypoints;
 //   k_bspline_fit_gen   more than 62 waypoints: VALU kernel, A+ streamed from L2.
+//   k_fit_setup_table / k_fit_mixed_plan / k_bspline_fit_mixed_mfma   paths of different K in one call
+//                 (vigo_bspline_fit_mixed): the operators of every K = 4 .. 62 in one table, the paths sorted by K on
+//                 the device (vigo_fit_plan.hpp), the product above per wave-group of one K — the uniform entry's bits.
 // fp64, explicit fused multiply-adds in index order: deterministic, batch-invariant.
+#include "vigo_fit_plan.hpp"
 #include "vigo_internal.hpp"
 
 namespace vigo {
@@ -50,9 +54,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return out;
 }
 
-// W: R x (C + R) row-major work matrix in global memory, [A | I] -> [R | Q'].
-__global__ void __launch_bounds__(kSetupThreads) k_fit_setup(int K, double ts, double* __restrict__ W,
-                                                             double* __restrict__ pinvT) {
+// W: R x (C + R) row-major work matrix in global memory, [A | I] -> [R | Q'].  One workgroup of kSetupThreads; the body of
+// k_fit_setup (the single cached operator) and of k_fit_setup_table (one workgroup per K): one arithmetic, the same bits.
+__device__ __forceinline__ void fit_setup(int K, double ts, double* __restrict__ W, double* __restrict__ pinvT) {
     const int R = K + 4, C = K + 2, Wc = C + R;
     const int tid = threadIdx.x;
     __shared__ double v[kMaxRows];
@@ -98,6 +102,18 @@ __global__ void __launch_bounds__(kSetupThreads) k_fit_setup(int K, double ts, d
             x[r] = s / W[(size_t)r * Wc + r];
         }
     }
+}
+
+__global__ void __launch_bounds__(kSetupThreads) k_fit_setup(int K, double ts, double* __restrict__ W,
+                                                             double* __restrict__ pinvT) {
+    fit_setup(K, ts, W, pinvT);
+}
+
+// the table of vigo_bspline_fit_mixed: workgroup k factorises K = k + 4 in its own slice of the work and of the table
+__global__ void __launch_bounds__(kSetupThreads) k_fit_setup_table(double ts, double* __restrict__ work,
+                                                                   double* __restrict__ table) {
+    const int K = kFitMixedMinK + (int)blockIdx.x;
+    fit_setup(K, ts, work + fit_table_work_offset(K), table + fit_table_offset(K));
 }
 
 // rhs row j of trajectory b: waypoint j (j < K) or boundary condition j - K (zero when conds == NULL)
@@ -169,6 +185,135 @@ __global__ void __launch_bounds__(256) k_bspline_fit_mfma(int B, int K, const do
     }
 }
 
+// ---- mixed point counts in one launch (vigo_bspline_fit_mixed) ---------------------------------
+// The paths are regrouped by K on the device (vigo_fit_plan.hpp): k_fit_mixed_plan sorts them into the 59 bins, stably,
+// and k_bspline_fit_mixed_mfma runs the product above on wave-groups of up to 5 paths of ONE K, with the operator of
+// that K from the handle's table.  The accumulation of an element is the uniform kernel's own (same k-step class, same
+// zero padding), so a path gets the bits vigo_bspline_fit gives it alone.
+constexpr int kPlanThreads = 1024, kPlanWaves = kPlanThreads / 64, kPlanUnroll = 8;
+
+// One workgroup.  Wave w owns the paths [w * per, (w + 1) * per) and walks them 64 at a time, twice: counting its
+// paths per bin, then — after the bins' and the waves' exclusive prefixes — writing each path's index to its place in the
+// sorted order.  Lanes of one bin are ranked with ballots, so a bin lists its paths in ascending index whatever the
+// timing: no atomics.  tab: path_prefix[kFitBins + 1] then group_prefix[kFitBins + 1].
+__global__ void __launch_bounds__(kPlanThreads) k_fit_mixed_plan(int T, int Ns, int point_stride,
+                                                                 const int32_t* __restrict__ n_fit,
+                                                                 const int32_t* __restrict__ status,
+                                                                 int32_t* __restrict__ perm, int32_t* __restrict__ tab,
+                                                                 int32_t* __restrict__ out_n_pts) {
+    __shared__ int wcnt[kPlanWaves][kFitBins];   // pass 1: paths of wave w in bin k; then: where its next one goes
+    __shared__ int cnt[kFitBins];
+    __shared__ int pre[2][kFitBins + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long per = ((long long)T + kPlanWaves - 1) / kPlanWaves;
+    const long long lo = min((long long)T, wave * per), hi = min((long long)T, lo + per);
+    const unsigned long long below = (1ull << lane) - 1;
+    for (int i = tid; i < kPlanWaves * kFitBins; i += kPlanThreads) (&wcnt[0][0])[i] = 0;
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+        for (long long base = lo; base < hi; base += 64 * kPlanUnroll) {
+            int bins[kPlanUnroll];   // the counts of kPlanUnroll x 64 paths in flight together: the walk is load latency
+#pragma unroll
+            for (int u = 0; u < kPlanUnroll; ++u) {
+                const long long t = base + 64 * u + lane;
+                bins[u] = -1;
+                if (t < hi) {
+                    bins[u] = fit_mixed_bin(n_fit[t], status ? status[t] : 0, Ns, point_stride);
+                    if (pass == 0) out_n_pts[t] = bins[u] < 0 ? 0 : bins[u] + kFitMixedMinK + 2;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kPlanUnroll; ++u) {
+                const long long t = base + 64 * u + lane;
+                const int bin = bins[u];
+                unsigned long long todo = __ballot(bin >= 0);
+                while (todo) {   // wave-uniform: one trip per distinct bin among the 64
+                    const int kb = __shfl(bin, __ffsll(todo) - 1);
+                    const unsigned long long mask = __ballot(bin == kb);
+                    if (pass == 1 && bin == kb) perm[pre[0][kb] + wcnt[wave][kb] + __popcll(mask & below)] = (int32_t)t;
+                    __builtin_amdgcn_wave_barrier();
+                    if (lane == 0) wcnt[wave][kb] += __popcll(mask);
+                    __builtin_amdgcn_wave_barrier();
+                    todo &= ~mask;
+                }
+            }
+        }
+        if (pass == 1) break;
+        __syncthreads();
+        if (tid < kFitBins) {   // the waves' counts -> their exclusive prefix within the bin
+            int run = 0;
+            for (int w = 0; w < kPlanWaves; ++w) {
+                const int c = wcnt[w][tid];
+                wcnt[w][tid] = run;
+                run += c;
+            }
+            cnt[tid] = run;
+        }
+        __syncthreads();
+        if (tid == 0) fit_plan_prefix(cnt, pre[0], pre[1]);
+        __syncthreads();
+        if (tid < 2 * (kFitBins + 1)) tab[tid] = (&pre[0][0])[tid];
+    }
+}
+
+// TILES, KSTEPS, SPLIT: as k_bspline_fit_mfma; KSTEPS 9 takes the wave-groups of the bins below kFitSmallBins, KSTEPS 17
+// the others.  The grid provides for fit_mixed_max_groups(T) wave-groups; what the counts leave unused exits.
+template <int TILES, int KSTEPS, int SPLIT>
+__global__ void __launch_bounds__(256) k_bspline_fit_mixed_mfma(int Ns, int point_stride, const double* __restrict__ table,
+                                                                const int32_t* __restrict__ perm,
+                                                                const int32_t* __restrict__ tab,
+                                                                const double* __restrict__ points,
+                                                                const double* __restrict__ conds, double* __restrict__ out) {
+    const int32_t* path_prefix = tab;
+    const int32_t* group_prefix = tab + kFitBins + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 15, kk = lane >> 4;
+    const int bl = n / 3, ax = n - 3 * bl;       // path within the group, axis
+    const int tile0 = (wave % SPLIT) * TILES;    // first row tile of this wave
+    const int g_lo = KSTEPS == 9 ? 0 : group_prefix[kFitSmallBins];
+    const int g_hi = KSTEPS == 9 ? group_prefix[kFitSmallBins] : group_prefix[kFitBins];
+    constexpr int GPB = 4 / SPLIT;               // groups per workgroup and trip
+    double Areg[TILES][KSTEPS] = {};
+    int have = 0;                                // the K whose operator Areg holds
+    for (long long gl = g_lo + (long long)blockIdx.x * GPB + wave / SPLIT; gl < g_hi; gl += (long long)gridDim.x * GPB) {
+        const FitGroup fg = fit_group_of(path_prefix, group_prefix, (int)gl);
+        const int K = __builtin_amdgcn_readfirstlane(fg.K), R = K + 4, C = K + 2;
+        if (K != have) {   // sorted bins: a wave's next group mostly shares its K
+            const double* pinvT = table + fit_table_offset(K);
+#pragma unroll
+            for (int t = 0; t < TILES; ++t)
+#pragma unroll
+                for (int s = 0; s < KSTEPS; ++s) {
+                    const int row = 16 * (tile0 + t) + n, j = 4 * s + kk;
+                    Areg[t][s] = (row < C && j < R) ? pinvT[(size_t)j * C + row] : 0.0;
+                }
+            have = K;
+        }
+        const bool live = (n < 15) && (bl < fg.members);
+        const size_t b = live ? (size_t)perm[fg.first + bl] : 0;
+        double Bv[KSTEPS];
+#pragma unroll
+        for (int s = 0; s < KSTEPS; ++s) {
+            const int j = 4 * s + kk;
+            double v = 0.0;
+            if (live && j < K) v = points[(b * point_stride + j) * 3 + ax];
+            else if (live && j < R && conds) v = conds[b * 12 + (j - K) * 3 + ax];
+            Bv[s] = v;
+        }
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+            v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Areg[t][s], Bv[s], acc, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * (tile0 + t) + kk + 4 * r;
+                if (live && row < C) out[(b * Ns + row) * 3 + ax] = acc[r];
+            }
+        }
+    }
+}
+
 // any K: one 256-thread workgroup per trajectory, rows strided, A+ read from L2 (same sums, same order)
 __global__ void __launch_bounds__(256) k_bspline_fit_gen(int B, int K, const double* __restrict__ pinvT,
                                                          const double* __restrict__ points,
@@ -215,6 +360,30 @@ int launch_bspline_fit(hipStream_t s, int B, int K, const double* pinvT, const d
         hipLaunchKernelGGL((k_bspline_fit_mfma<2, 17, 2>), dim3(mgrid(2)), dim3(256), 0, s, B, K, pinvT, points, conds, out);
     else
         hipLaunchKernelGGL(k_bspline_fit_gen, dim3(grid), dim3(256), 0, s, B, K, pinvT, points, conds, out);
+    return (int)hipGetLastError();
+}
+
+int launch_fit_setup_table(hipStream_t s, double ts, double* work, double* table) {
+    hipLaunchKernelGGL(k_fit_setup_table, dim3(kFitBins), dim3(kSetupThreads), 0, s, ts, work, table);
+    return (int)hipGetLastError();
+}
+
+int launch_bspline_fit_mixed(hipStream_t s, int T, int Ns, int point_stride, const double* table, const int32_t* n_fit,
+                             const int32_t* status, const double* points, const double* conds, int32_t* perm, int32_t* tab,
+                             double* out, int32_t* out_n_pts) {
+    if (T <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_mixed_plan, dim3(1), dim3(kPlanThreads), 0, s, T, Ns, point_stride, n_fit, status, perm, tab, out_n_pts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const long long groups = fit_mixed_max_groups(T);   // the counts stay on the device: surplus waves exit
+    auto mgrid = [groups](int gpb) { const long long need = (groups + gpb - 1) / gpb; return (int)(need < 2048 ? need : 2048); };
+    hipLaunchKernelGGL((k_bspline_fit_mixed_mfma<2, 9, 1>), dim3(mgrid(4)), dim3(256), 0, s, Ns, point_stride, table, perm, tab,
+                       points, conds, out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (Ns > 32)   // K + 2 <= Ns: no path of the 17-step class below that
+        hipLaunchKernelGGL((k_bspline_fit_mixed_mfma<2, 17, 2>), dim3(mgrid(2)), dim3(256), 0, s, Ns, point_stride, table, perm,
+                           tab, points, conds, out);
     return (int)hipGetLastError();
 }
 

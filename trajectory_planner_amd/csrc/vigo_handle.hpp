@@ -23,6 +23,8 @@ enum BufId {
     kBufEsdf,        // the bricked ESDF: exact size; growing drops has_esdf and esdf_view.dist until the new field is in
     kBufEsdfWs,      // vigo_build_esdf's two int32 buffers (vigo_esdf_build.hip): exact size (1 GiB at 512^3)
     kBufFit,         // least-squares operator of the B-spline fit, transposed (vigo_fit.hip): exact size; growing clears fit_K
+    kBufFitTable,    // the operators of K = 4 .. 62 at one ts for vigo_bspline_fit_mixed (vigo_fit_plan.hpp): exact size, 0.7 MB;
+                     //   a slot of its own, so filling it leaves kBufFit's operator and every other cache alone
     kBufTimes,       // the gates' sample clock: T + 64 doubles; growing clears times_T
     kBufScratch,     // per-call scratch of most entry points and staging of the *_host calls: need + 25 % + 4 KiB
     kBufPaths0,      // vigo_path_search: sized by the call's first-choice and (kBufPaths1) second-choice searches,
@@ -63,6 +65,8 @@ struct vigo_context {
     // kBufFit holds the operator for (fit_K, fit_ts); fit_K == 0: none
     int fit_K = 0;
     double fit_ts = 0.0;
+    // kBufFitTable holds the operators of every K at fit_table_ts; 0: none
+    double fit_table_ts = 0.0;
     // kBufTimes holds the clock of (times_dt, times_tmax), filled on times_stream; times_T < 0: none
     double times_dt = -1.0, times_tmax = -1.0;
     int times_T = -1;

@@ -209,6 +209,12 @@ size_t fit_pinv_doubles(int K);
 int launch_fit_setup(hipStream_t s, int K, double ts, double* work, double* pinvT);
 int launch_bspline_fit(hipStream_t s, int B, int K, const double* pinvT, const double* points,
                        const double* conds, double* out);
+// mixed point counts (vigo_fit_plan.hpp): the operators of K = 4 .. 62 into `table` (work: fit_table_work_doubles()),
+// then the regrouping and the product; perm int32[T] and tab int32[2 * (kFitBins + 1)] are the call's workspace
+int launch_fit_setup_table(hipStream_t s, double ts, double* work, double* table);
+int launch_bspline_fit_mixed(hipStream_t s, int T, int Ns, int point_stride, const double* table, const int32_t* n_fit,
+                             const int32_t* status, const double* points, const double* conds, int32_t* perm, int32_t* tab,
+                             double* out, int32_t* out_n_pts);
 
 // batched min-snap QP (vigo_minsnap.hip)
 size_t minsnap_lds_bytes(int W, int cont);

@@ -68,6 +68,16 @@ inline size_t ws_rebound_mixed(void* base, size_t B, size_t Ns, int32_t*& flags,
     return c.bytes();
 }
 
+// vigo_bspline_fit_mixed: the sorted order of the T paths, the two prefix tables of tab_ints words, and — in a call that
+// builds the operator table — the factorisations' work_doubles
+inline size_t ws_fit_mixed(void* base, size_t T, size_t tab_ints, size_t work_doubles, int32_t*& perm, int32_t*& tab, double*& work) {
+    WsCarver c(base);
+    perm = c.take<int32_t>(ws_even(T));
+    tab = c.take<int32_t>(ws_even(tab_ints));
+    work = work_doubles ? c.take<double>(work_doubles) : nullptr;
+    return c.bytes();
+}
+
 // the per-trajectory scratch of vigo_collision_segs / vigo_path_search; want_flags: room for vigo_ctrl_occupancy's flags
 template <class Args>
 size_t ws_path_search_scratch(void* base, size_t B, size_t N, bool want_flags, Args& a) {

@@ -208,7 +208,10 @@ public:
      * vigo_seed_paths launch per device group and one download; a trajectory the launch defers or refuses, a poly
      * planner flying its PWL fallback or without a polynomial, and a planner without a map snapshot take the host steps.
      * The kernels' power is the correctly rounded one; libm's is that value or its neighbour (csrc/vigo_exact_pow.hpp;
-     * the rate is counted by tools/pow_rounding_rate.py): the seeds agree to that.  The fits run as updatePathBatch's, one vigo_bspline_fit launch per point count. */
+     * the rate is counted by tools/pow_rounding_rate.py): the seeds agree to that.  The fits run as updatePathBatch's, one vigo_bspline_fit launch per point count.
+     * setMixedFit(false), the default: that.  true: the fit stage of updatePathBatch and seedPathBatch takes every ready
+     * planner of up to 62 points with ONE vigo_bspline_fit_mixed call per knot span, whatever the counts (planners with
+     * more points keep the per-count launches); the installed control points are the same, bit for bit. */
     struct SeedInfo {
         bool found = false;      /* a try passed inputPathCheck */
         int tries = 0;
@@ -221,6 +224,8 @@ public:
                                            std::vector<nav_msgs::Path>* seeds = nullptr, std::vector<SeedInfo>* info = nullptr);
     static void setDeviceSeed(bool on);
     static bool deviceSeed();
+    static void setMixedFit(bool on);     /* process-wide, default off */
+    static bool mixedFit();
     static void setSeedMaxTries(int n);   /* default 16: dt has shrunk to 2.8 % of getInitTs() by then */
     static int seedMaxTries();
     /* Process-wide running totals: the planners whose seed and fit points vigo_seed_paths produced / the host steps did */

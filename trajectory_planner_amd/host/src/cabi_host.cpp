@@ -868,6 +868,14 @@ int vigo_host_seed_batch(int nx, int ny, int nz, const double* origin, double re
     return 0;
 }
 
+// bsplineTraj::setMixedFit for the harness entries above and below (process-wide; returns what it was): a test flips it
+// around vigo_host_seed_batch, whose own arguments keep their meaning
+int vigo_host_set_mixed_fit(int on) {
+    const bool was = trajPlanner::bsplineTraj::mixedFit();
+    trajPlanner::bsplineTraj::setMixedFit(on != 0);
+    return was ? 1 : 0;
+}
+
 // Wall time of the seed-path stage up to installed control points for P start/goal pairs (planners built and the min-snap
 // seeds planned once, before the clock): out_ms[reps][3], per repetition in this order
 //   0  what existed before seedPathBatch: the searches as a serial loop on the calling thread, then updatePathBatch

@@ -48,6 +48,14 @@ inline size_t seedInBlock(void* base, size_t T, size_t S, size_t deg, SeedIn& f)
     return c.bytes();
 }
 
+// ... followed by the start / end conditions of the fit, [T][4][3], when the launch's fit points stay on the device
+// for vigo_bspline_fit_mixed (bsplineTraj::setMixedFit): the same block, one upload
+inline size_t seedInBlockWithConds(void* base, size_t T, size_t S, size_t deg, SeedIn& f, double*& conds) {
+    const size_t head = seedInBlock(base, T, S, deg, f);        // whole 8-byte words
+    conds = base ? reinterpret_cast<double*>(static_cast<char*>(base) + head) : nullptr;
+    return head + T * 12 * sizeof(double);
+}
+
 // cap: rows of the seed / fit points per trajectory
 struct SeedOut {
     int32_t *status, *tries, *seedN, *fitN;           // [T] each

@@ -396,6 +396,34 @@ class Vigo:
                                                C.c_void_p(out.data_ptr())), "vigo_bspline_fit")
         return out
 
+    def bspline_fit_mixed(self, points, n_fit, Ns, conds=None, status=None, ts=None, out=None):
+        """vigo_bspline_fit_mixed: points [T,point_stride,3] f64, of which the first n_fit[t] (i32 [T]) rows are path t's
+        (+ conds [T,4,3], status i32 [T]: only paths of status 0 are fitted) -> (ctrl [T,Ns,3], n_pts i32 [T]), the input
+        of optimize_mixed.  Rows of ctrl beyond n_fit[t] + 2, and the whole row of a path that is not fitted (n_pts 0),
+        are not written: zeros, or what the caller's out = (ctrl, n_pts) held."""
+        _shape(points, (None, None, 3), "points")
+        T, stride, _ = points.shape
+        Ns = int(Ns)
+        _shape(n_fit, (T,), "n_fit")
+        _shape(status, (T,), "status")
+        _shape(conds, (T, 4, 3), "conds")
+        ts = float(self.params.ts_ctrl if ts is None else ts)
+        d = self.device
+        if out is not None:
+            ctrl, n_pts = out
+            _shape(ctrl, (T, Ns, 3), "out ctrl"); _shape(n_pts, (T,), "out n_pts")
+            _ptr(ctrl, torch.float64, "out ctrl", d); _ptr(n_pts, torch.int32, "out n_pts", d)
+        else:
+            ctrl = torch.zeros(T, max(Ns, 0), 3, dtype=torch.float64, device=d)
+            n_pts = torch.zeros(T, dtype=torch.int32, device=d)
+        self._check(self._lib.vigo_bspline_fit_mixed(self._h, T, Ns, ts, _ptr(n_fit, torch.int32, "n_fit", d),
+                                                     _ptr(status, torch.int32, "status", d),
+                                                     _ptr(points, torch.float64, "points", d), stride,
+                                                     _ptr(conds, torch.float64, "conds", d),
+                                                     C.c_void_p(ctrl.data_ptr()), C.c_void_p(n_pts.data_ptr())),
+                    "vigo_bspline_fit_mixed")
+        return ctrl, n_pts
+
     def bspline_eval(self, ctrl, times, deriv=0):
         _shape(ctrl, (None, None, 3), "ctrl")
         B, N, _ = ctrl.shape
