@@ -129,7 +129,7 @@ int vigo_set_precision(vigo_handle_t h, int vigo_precision);
 const char* vigo_last_error(vigo_handle_t h);
 /* Library/ABI version (raised when entry points are added; nothing was removed or changed so far: 4 adds
  * vigo_build_esdf / vigo_esdf_from_voxels_host; vigo_seed_capacity / vigo_seed_paths / vigo_seed_paths_host came in at 4
- * as well, and so did vigo_bspline_fit_mixed after them — ask the library for the symbol), and whether the code object was built for gfx950. */
+ * as well, and so did vigo_bspline_fit_mixed and then vigo_traj_finish / vigo_traj_finish_host after them — ask the library for the symbol), and whether the code object was built for gfx950. */
 int vigo_abi_version(void);
 const char* vigo_build_arch(void);
 /* "solver:<12 hex> all:<12 hex>": digests of the library's compiled code (host code and gfx950 code objects; the first
@@ -312,6 +312,51 @@ int vigo_traj_dynamic_collision(vigo_handle_t h, int B, int N, const double* ctr
  */
 int vigo_ctrl_occupancy(vigo_handle_t h, int B, int N, const double* ctrl,
                         uint8_t* out_pt, uint8_t* out_line);
+
+/* ---- the end of a plan: reparameterisation factor and sampled path ------------------------ */
+
+/* out_status of vigo_traj_finish, per trajectory */
+typedef enum {
+    VIGO_FINISH_OK = 0,          /* everything written */
+    VIGO_FINISH_CAPACITY = 1,    /* n_samp > S_cap: out_n carries the true count; the first S_cap samples and the factor are written */
+    VIGO_FINISH_INVALID_N = 2    /* count outside 7 .. Ns: factor and maxima NaN, out_n = 0, no sample row touched */
+} vigo_finish_status_t;
+
+/*
+ * Replaces: steps 5-6 of bsplineTraj::makePlan() — bspline_ = bspline(3, controlPoints, controlPointsTs_) and
+ * linearFeasibilityReparam() (BT.cpp:1116-1137) — and the samples of evalTrajToMsg(dt) (BT.cpp:1502-1518, over evalTraj,
+ * BT.h:345) for B trajectories in ONE launch, a wavefront per trajectory, on the control-point rows as
+ * vigo_rebound_rounds / vigo_rebound_rounds_mixed leave them.  All arrays device.  ts_ctrl and ts are the handle's params.
+ *   n_pts      int32[B] or NULL         control points n_b of row b (NULL: every row has Ns)
+ *   ctrl       double[B][Ns][3]         the first n_b points of row b are read, nothing beyond them
+ *   limits     double[B][2]             max_vel, max_acc of trajectory b
+ *   out_factor double[B]                linearFactor_: min(max_vel / maxV, sqrt(max_acc / maxA)) by std::min's comparison, the
+ *                                       maxima of |velocity| and |acceleration| over `for (t = 0; t < duration; t += ts)`,
+ *                                       duration = (n_b - 3) * ts_ctrl; a NaN norm never replaces a maximum, and no division
+ *                                       is guarded: +inf for a trajectory that does not move
+ *   out_max    double[B][2] or NULL     maxV, maxA
+ *   out_n      int32[B]                 samples of `for (t = 0; t <= duration; t += sample_dt)`
+ *   out_pos    double[B][S_cap][3]      sample i: the position at the i-fold accumulated t; rows i >= out_n stay as they were
+ *   out_vel    double[B][S_cap][3] or NULL   the velocity at (double)i * sample_dt — the product clock evalTrajToMsg takes
+ *                                       its yaw from; atan2 and the quaternion stay with the caller (libm)
+ *   out_status int32[B]                 VIGO_FINISH_*
+ * Every value equals, bit for bit, what the reference's serial loops give for the trajectory alone: it depends neither on
+ * the batch nor on Ns nor on the neighbours' counts.  The counts are device data and checked per trajectory.  (A NaN
+ * coordinate of out_pos / out_vel is stored as the quiet NaN 0x7ff8000000000000: IEEE 754 leaves a NaN's sign and payload to
+ * the implementation, and x86 and gfx950 differ there.)
+ * VIGO_ERR_UNSUPPORTED_N: Ns < 7 or Ns > VIGO_MAX_CTRL_POINTS.  VIGO_ERR_INVALID_ARG: NULL handle, B < 0, S_cap < 1, a
+ * sample_dt / ts / ts_ctrl that is not finite and positive, a NULL required array with B > 0, more than 2^24 samples of a
+ * clock.  On an error nothing is written.  B == 0: VIGO_OK, nothing launched.  The two clock tables are cached in the handle
+ * per step and longest duration, in slots of their own (the gates' table is not evicted).
+ */
+int vigo_traj_finish(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const double* limits,
+                     double sample_dt, int S_cap, double* out_factor, double* out_max, int32_t* out_n, double* out_pos,
+                     double* out_vel, int32_t* out_status);
+/* The same rule on the host (csrc/vigo_finish_core.hpp compiled for the CPU; no handle, no GPU): host pointers, ts_ctrl and
+ * ts as arguments, the clocks by the plain `t += step` loops.  Same refusals, same statuses, same bits. */
+int vigo_traj_finish_host(double ts_ctrl, double ts, int B, int Ns, const int32_t* n_pts, const double* ctrl,
+                          const double* limits, double sample_dt, int S_cap, double* out_factor, double* out_max,
+                          int32_t* out_n, double* out_pos, double* out_vel, int32_t* out_status);
 
 /* ---- the rebound loop between two A* calls, device-resident ------------------------------ */
 

@@ -16,3 +16,9 @@ g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer -D__H
     src/bspline.cpp src/astarOcc.cpp src/piecewiseLinearTraj.cpp src/mapAdapter.cpp -L../lib -lvigo_hip -L$ROCM/lib -lamdhip64 \
     -Wl,-rpath,"$PWD/../lib" -Wl,-rpath,$ROCM/lib
 /tmp/vigo_san_seed_facade
+# the plan's last stage on the host (vigo_traj_finish_host: csrc/vigo_finish_core.hpp through the host side of
+# csrc/vigo_finish.hip, whose sources are HIP: hipcc compiles them, the sanitizers instrument the host code only; no GPU)
+HIPCC=${HIPCC:-$ROCM/bin/hipcc}
+$HIPCC --offload-arch=gfx950 -std=c++17 -g -O1 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
+    -I../../include -o /tmp/vigo_san_finish ../../tools/sanitize_finish_main.cpp -x hip ../csrc/vigo_finish.hip
+/tmp/vigo_san_finish

@@ -84,6 +84,8 @@ PROTOTYPES = {
     "vigo_traj_collision": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp]),
     "vigo_traj_dynamic_collision": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _i, _vp]),
     "vigo_ctrl_occupancy": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "vigo_traj_finish": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _i] + [_vp] * 6),
+    "vigo_traj_finish_host": (_i, [_d, _d, _i, _i, _vp, _vp, _vp, _d, _i] + [_vp] * 6),
     "vigo_minsnap": (_i, [_vp, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vigo_minsnap_supported": (_i, [_i, _i, _i, _i]),
     "vigo_corridor_check": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d3, _d, _vp, _vp, _vp]),

@@ -53,7 +53,7 @@ int fail(vigo_handle_t h, int code, const char* what, hipError_t e = hipSuccess)
 // not kept).  A failed allocation leaves it empty.  Callers whose cache lives in the buffer invalidate it first.
 int reserve(vigo_handle_t h, vigo::BufId id, size_t need, size_t alloc) {
     static const char* const what[] = {
-        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(scratch)",
+        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(finish_ts)", "hipMalloc(finish_dt)", "hipMalloc(scratch)",
         "hipMalloc(paths_ws[0])", "hipMalloc(paths_ws[1])", "hipMalloc(reguide_ws[0])", "hipMalloc(reguide_ws[1])",
         "hipMalloc(reguide_ws[2])", "hipMalloc(rebound)"};
     static_assert(sizeof(what) / sizeof(what[0]) == vigo::kBufCount, "one name per BufId, in its order");
@@ -176,6 +176,49 @@ int upload_sample_times(vigo_handle_t h, double tmax, double dt, int* out_T, con
     h->times_tmax = tmax;
     h->times_T = T;
     h->times_stream = h->stream;
+    *out_T = T;
+    *out_dev = times;
+    return VIGO_OK;
+}
+
+// The strict sibling: samples of `for (t = 0; t < tmax; t += dt)` (BT.cpp:1122).  -1: more than 2^24.
+int count_sample_times_strict(double dt, double tmax) {
+    if (!(tmax > 0.0)) return 0;
+    const int64_t cap = (int64_t)1 << 24;
+    if (vigo::accumulated_time(dt, cap) < tmax) return -1;
+    int64_t lo = 0, hi = cap;                       // t_lo < tmax <= t_hi
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (vigo::accumulated_time(dt, mid) < tmax) lo = mid; else hi = mid;
+    }
+    return (int)hi;                                 // samples k = 0 .. lo
+}
+
+// vigo_traj_finish's clocks, cached per (dt, tmax) like the gates' but in slots of their own (which: 0 the strict `<`
+// clock of ts in kBufFinishTs, 1 the `<=` clock of the sample step in kBufFinishDt): a plan batch between two gate
+// calls does not evict the gates' table, nor the other way round
+int upload_finish_clock(vigo_handle_t h, int which, double tmax, double dt, int* out_T, const double** out_dev) {
+    vigo_context::ClockSlot& c = h->finish_clock[which];
+    const vigo::BufId id = which == 0 ? vigo::kBufFinishTs : vigo::kBufFinishDt;
+    if (c.T >= 0 && c.dt == dt && c.tmax == tmax) {
+        if (c.stream != h->stream) {                   // filled on another stream: make sure it has landed
+            VIGO_HIP(h, hipStreamSynchronize(c.stream));
+            c.stream = h->stream;
+        }
+        *out_T = c.T;
+        *out_dev = h->buf[id].as<double>();
+        return VIGO_OK;
+    }
+    const int T = which == 0 ? count_sample_times_strict(dt, tmax) : count_sample_times(dt, tmax);
+    if (T < 0) return fail(h, VIGO_ERR_INVALID_ARG, "too many samples");
+    c.T = -1;                                          // no clock cached while the buffer is regrown or refilled
+    VIGO_TRY(reserve(h, id, (size_t)T * sizeof(double), ((size_t)T + 64) * sizeof(double)));
+    double* times = h->buf[id].as<double>();
+    VIGO_HIP(h, (hipError_t)vigo::launch_fill_sample_times(h->stream, dt, T, times));
+    c.dt = dt;
+    c.tmax = tmax;
+    c.T = T;
+    c.stream = h->stream;
     *out_T = T;
     *out_dev = times;
     return VIGO_OK;
@@ -769,6 +812,27 @@ int vigo_traj_dynamic_collision(vigo_handle_t h, int B, int N, const double* ctr
     double duration = (N - 3) * h->params.ts_ctrl;
     VIGO_TRY(upload_sample_times(h, duration, dt, &T, &times));
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_dynamic_collision(h->stream, B, N, ctrl, h->params.ts_ctrl, T, times, obs_off, obs, n_obs_shared, out_flag));
+    return VIGO_OK;
+}
+
+int vigo_traj_finish(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const double* limits, double sample_dt,
+                     int S_cap, double* out_factor, double* out_max, int32_t* out_n, double* out_pos, double* out_vel, int32_t* out_status) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    const double ts = h->params.ts, ts_ctrl = h->params.ts_ctrl;
+    if (B < 0 || S_cap < 1 || !(sample_dt > 0.0) || !isfinite(sample_dt) || !(ts > 0.0) || !isfinite(ts) || !(ts_ctrl > 0.0) || !isfinite(ts_ctrl) ||
+        (B > 0 && (!ctrl || !limits || !out_factor || !out_n || !out_pos || !out_status)))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_finish: bad argument");
+    if (Ns < 7 || Ns > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "Ns outside [7, VIGO_MAX_CTRL_POINTS]");
+    if (B == 0) return VIGO_OK;
+    vigo::FinishArgs a{};
+    a.B = B; a.Ns = Ns; a.n_pts = n_pts; a.ctrl = ctrl; a.limits = limits;
+    a.ts_ctrl = ts_ctrl; a.sample_dt = sample_dt; a.S_cap = S_cap;
+    // (the clocks depend on the step and k only: the tables of the longest duration serve every count)
+    const double longest = (Ns - 3) * ts_ctrl;
+    VIGO_TRY(upload_finish_clock(h, 0, longest, ts, &a.T_ts, &a.times_ts));
+    VIGO_TRY(upload_finish_clock(h, 1, longest, sample_dt, &a.T_dt, &a.times_dt));
+    a.out_factor = out_factor; a.out_max = out_max; a.out_n = out_n; a.out_pos = out_pos; a.out_vel = out_vel; a.out_status = out_status;
+    VIGO_HIP(h, (hipError_t)vigo::launch_traj_finish(h->stream, a));
     return VIGO_OK;
 }
 

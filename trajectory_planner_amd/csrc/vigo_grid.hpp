@@ -48,8 +48,9 @@ struct GridOcc {
 };
 
 // bspline::at (BS.cpp:32-58) for knots (i - degree) * ts, control point i = get(i)
+// (deboor and traj_eval are host functions too: the host twin of vigo_finish_core.hpp evaluates with this one copy)
 template <int DEGREE, typename Get>
-__device__ __forceinline__ void deboor(int ncp, double ts, double t, Get get, double (&out)[3]) {
+__host__ __device__ __forceinline__ void deboor(int ncp, double ts, double t, Get get, double (&out)[3]) {
     auto knot = [ts](int i) -> double { return (i - DEGREE) * ts; };
     const int knotsNum = ncp - 1 + DEGREE + 1 + 1;
     const double duration = knot(knotsNum - DEGREE - 1);
@@ -74,7 +75,7 @@ __device__ __forceinline__ void deboor(int ncp, double ts, double t, Get get, do
 
 // value (deriv 0) / velocity (1) / acceleration (2) of the cubic spline over ctrl[N][3]
 // (bspline(3, ctrl, ts) and its getDerivative() chain, BS.cpp:64-72)
-__device__ __forceinline__ void traj_eval(const double* ctrl, int N, double ts, int deriv, double t, double (&out)[3]) {
+__host__ __device__ __forceinline__ void traj_eval(const double* ctrl, int N, double ts, int deriv, double t, double (&out)[3]) {
     auto c0 = [ctrl](int i, double (&o)[3]) {
         o[0] = ctrl[3 * i]; o[1] = ctrl[3 * i + 1]; o[2] = ctrl[3 * i + 2];
     };

@@ -26,6 +26,8 @@ enum BufId {
     kBufFitTable,    // the operators of K = 4 .. 62 at one ts for vigo_bspline_fit_mixed (vigo_fit_plan.hpp): exact size, 0.7 MB;
                      //   a slot of its own, so filling it leaves kBufFit's operator and every other cache alone
     kBufTimes,       // the gates' sample clock: T + 64 doubles; growing clears times_T
+    kBufFinishTs,    // vigo_traj_finish's two clocks (the `t += ts` one and the `t += sample_dt` one), slots of their own so
+    kBufFinishDt,    //   the gates' table stays cached: T + 64 doubles; growing clears the slot's finish_clock[].T
     kBufScratch,     // per-call scratch of most entry points and staging of the *_host calls: need + 25 % + 4 KiB
     kBufPaths0,      // vigo_path_search: sized by the call's first-choice and (kBufPaths1) second-choice searches,
     kBufPaths1,      //   need + 25 % + 4 KiB
@@ -71,4 +73,10 @@ struct vigo_context {
     double times_dt = -1.0, times_tmax = -1.0;
     int times_T = -1;
     hipStream_t times_stream = nullptr;
+    // kBufFinishTs / kBufFinishDt hold the clock of (dt, tmax) — [0]: samples t < tmax, [1]: samples t <= tmax; T < 0: none
+    struct ClockSlot {
+        double dt = -1.0, tmax = -1.0;
+        int T = -1;
+        hipStream_t stream = nullptr;
+    } finish_clock[2];
 };

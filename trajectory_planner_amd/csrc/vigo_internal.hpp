@@ -216,6 +216,25 @@ int launch_bspline_fit_mixed(hipStream_t s, int T, int Ns, int point_stride, con
                              const int32_t* status, const double* points, const double* conds, int32_t* perm, int32_t* tab,
                              double* out, int32_t* out_n_pts);
 
+// the end of a plan (vigo_finish.hip, the rule of vigo_finish_core.hpp): a wave per trajectory.  times_ts[T_ts]: the
+// `t += ts` clock below the longest duration (Ns - 3) * ts_ctrl; times_dt[T_dt]: the `t += sample_dt` clock up to it
+struct FinishArgs {
+    int B, Ns;
+    const int32_t* n_pts;        // NULL: every row has Ns control points
+    const double* ctrl;          // [B][Ns][3]
+    const double* limits;        // [B][2] max_vel, max_acc
+    double ts_ctrl, sample_dt;
+    int S_cap, T_ts, T_dt;
+    const double *times_ts, *times_dt;
+    double* out_factor;          // [B]
+    double* out_max;             // [B][2] or NULL
+    int32_t* out_n;              // [B]
+    double* out_pos;             // [B][S_cap][3]
+    double* out_vel;             // [B][S_cap][3] or NULL
+    int32_t* out_status;         // [B]
+};
+int launch_traj_finish(hipStream_t s, const FinishArgs& a);
+
 // batched min-snap QP (vigo_minsnap.hip)
 size_t minsnap_lds_bytes(int W, int cont);
 int minsnap_max_waypoints();

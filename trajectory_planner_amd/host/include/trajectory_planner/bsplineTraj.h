@@ -105,6 +105,25 @@ public:
     /* Planners are grouped by control-point count, map object and every hot-path parameter (the yaml values, maxVel):
      * each group is one batch on the device.  Returns per-planner success like makePlan(). */
     static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners);
+    /* not in the reference: the batched makePlan(nav_msgs::Path&, bool) — trajectories[i] receives what planner i's
+     * evalTrajToMsg(yaw) gives after the plan; a planner that fails gets an empty path */
+    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw = true);
+    /* Steps 5-6 of makePlan() (the spline object, linearFeasibilityReparam) and, for the overload above, the samples of
+     * evalTrajToMsg.  Off (default): per planner on the host workers, as it always was.  On: ONE vigo_traj_finish call
+     * per device group — planners that share a device target, ts_ and controlPointsTs_ (the sample step is ts_), whatever
+     * their control-point counts: rows are padded to the group's largest count; linearFactor_, bspline_ and the path
+     * are installed from its downloads, the yaw from the downloaded velocity with libm's atan2 as evalTrajToMsg takes it.
+     * A planner without a device, one of more than VIGO_MAX_CTRL_POINTS control points, a row the call reports over
+     * capacity (the facade sizes at most 2048 samples per trajectory) or with an invalid count, and every planner of a
+     * group whose call failed take the host route.  The result is the same bits either way. */
+    static void setDeviceEpilogue(bool on);
+    static bool deviceEpilogue();
+    /* Process-wide running totals: the planners whose epilogue the device call decided / those of calls under the
+     * switch that took the host route, and the vigo_traj_finish calls made (one per device group) */
+    static void deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups);
+    /* added (workload tools, cabi_host.cpp: vigo_host_finish_timing): that stage alone on the planners' current control
+     * points, as makePlanBatch runs it for planners that all succeeded; trajectories may be NULL */
+    static void finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw = true);
     /* The rebound loop of BT.cpp:611-685 runs on the device between two A* calls (vigo_rebound_rounds, default) or
      * round by round from the host (the round-1 path, kept for comparison: identical control points). */
     /* makePlanBatch of at least this many planners runs as two to four pipelined parts of >= half this size (all but the
@@ -349,7 +368,9 @@ private:
     /* the steps of makePlanBatch: the split into pipelined parts; for one part the prologue (steps 1-3), the rebound loop
      * on the device or driven from the host, the move of finished planners out of the loop, the epilogue (steps 5-6) */
     struct PlanBatch;
-    static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold);
+    /* paths: NULL, or one per planner (the overload with trajectories) */
+    static std::vector<bool> planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw);
+    static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold, nav_msgs::Path* paths, bool yaw);
     static void planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb);
     /* step 2 of the prologue for all planners with device searches; found[i]: planner i's pathSearch outcome */
     struct AstarJob;
@@ -370,7 +391,9 @@ private:
     static void reboundOnDevice(PlanBatch& pb, bool timing);
     static void reboundFromHost(PlanBatch& pb, bool timing);
     static void retireFinished(PlanBatch& pb);
-    static void planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result);
+    static void planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw);
+    /* setDeviceEpilogue(true): the planners with todo[i] through vigo_traj_finish; todo[i] is cleared for those it finished */
+    static void finishOnDevice(const std::vector<bsplineTraj*>& planners, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw);
 };
 }  // namespace trajPlanner
 #endif

@@ -72,13 +72,17 @@ struct HostBatch {
     explicit HostBatch(int stride) : N(stride) {}
     // controlPoints: 3 x n column by column, n <= N; w: (distance, smoothness, feasibility, dynamic)
     void add(const double* controlPoints, int n, const trajPlanner::optData& od, const std::array<double, 4>& w) {
-        ctrl.insert(ctrl.end(), controlPoints, controlPoints + 3 * n);
-        ctrl.resize(ctrl.size() + 3 * (size_t)(N - n), 0.0);
+        addRow(controlPoints, n);
         appendGuides(od, n, goff, gpv);
         goff.resize(goff.size() + (size_t)(N - n), goff.back());
         appendObstacles(od, obs);
         ooff.push_back((int32_t)(obs.size() / 9));
         weights.insert(weights.end(), w.begin(), w.end());
+    }
+    // the row and its count alone, for a stage that reads neither lists nor weights (the finish stage)
+    void addRow(const double* controlPoints, int n) {
+        ctrl.insert(ctrl.end(), controlPoints, controlPoints + 3 * n);
+        ctrl.resize(ctrl.size() + 3 * (size_t)(N - n), 0.0);
         npts.push_back(n);
         ++B;
     }

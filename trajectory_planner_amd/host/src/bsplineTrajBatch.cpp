@@ -266,10 +266,17 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
 
 // BT.cpp:333-385 for many planners at once: host prologue per planner, then the rebound loops in
 // lock-step so each optimize() round is one launch over all still-active planners.
-std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners) {
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners) { return planBatch(planners, nullptr, true); }
+
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw) {
+    trajectories.assign(planners.size(), nav_msgs::Path());
+    return planBatch(planners, trajectories.data(), yaw);
+}
+
+std::vector<bool> bsplineTraj::planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw) {
     const size_t P = planners.size();
     const size_t threshold = g_pipelineThreshold.load();
-    if (!t_insidePipeline && threshold > 0 && P >= threshold && P >= 2) return makePlanPipelined(planners, threshold);
+    if (!t_insidePipeline && threshold > 0 && P >= threshold && P >= 2) return makePlanPipelined(planners, threshold, paths, yaw);
     PlanBatch pb(P);
     const bool timing = getenv("VIGO_FACADE_TIMING") != nullptr;
     const double tp0 = wallSeconds();
@@ -281,7 +288,7 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
     if (deviceResidentRebound()) reboundOnDevice(pb, timing);
     else reboundFromHost(pb, timing);
     const double tp2 = wallSeconds();
-    planEpilogue(planners, pb.result);
+    planEpilogue(planners, pb.result, paths, yaw);
     if (timing) {
         cout << "[BsplineTraj]: prologue CPU time summed over the workers: findCollisionSeg " << pb.nsSeg.load() * 1e-6 << " ms, A* "
              << pb.nsAstar.load() * 1e-6 << " ms, guide assignment " << pb.nsGuide.load() * 1e-6 << " ms; device chains (wall) "
@@ -297,7 +304,7 @@ std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& pl
 // single-wave solves, ~10 ms per 1024 planners) the others' host work (A*, guide assignment) and device rounds
 // proceed — what a caller otherwise gets only by planning from several threads of its own.  Planners are independent
 // (per-trajectory results do not depend on which batch carries them), so the plans are those of the unsplit call.
-std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold) {
+std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold, nav_msgs::Path* paths, bool yaw) {
     constexpr size_t kMaxParts = 4;
     static thread_local Companion companions[kMaxParts - 1];
     const size_t P = planners.size();
@@ -305,21 +312,23 @@ std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>
     const size_t parts = std::min(kMaxParts, std::max<size_t>(2, P / per));
     std::vector<std::vector<bsplineTraj*>> piece(parts);
     std::vector<std::vector<bool>> res(parts);
+    std::vector<nav_msgs::Path*> out(parts, nullptr);      // a part's paths: its stretch of the call's
     for (size_t k = 0; k < parts; ++k) {
         const size_t lo = P * k / parts, hi = P * (k + 1) / parts;
         piece[k].assign(planners.begin() + lo, planners.begin() + hi);
         res[k].assign(hi - lo, false);
+        if (paths) out[k] = paths + lo;
     }
     for (size_t k = 1; k < parts; ++k) {
-        companions[k - 1].start([&piece, &res, k]() {
+        companions[k - 1].start([&piece, &res, &out, yaw, k]() {
             t_insidePipeline = true;
-            res[k] = bsplineTraj::makePlanBatch(piece[k]);
+            res[k] = bsplineTraj::planBatch(piece[k], out[k], yaw);
         });
     }
     // the jobs hold piece and res: every part has ended before an exception leaves (the first one in part order)
     std::exception_ptr err;
     t_insidePipeline = true;
-    try { res[0] = bsplineTraj::makePlanBatch(piece[0]); } catch (...) { err = std::current_exception(); }
+    try { res[0] = bsplineTraj::planBatch(piece[0], out[0], yaw); } catch (...) { err = std::current_exception(); }
     t_insidePipeline = false;
     for (size_t k = 1; k < parts; ++k)
         try { companions[k - 1].wait(); } catch (...) { if (!err) err = std::current_exception(); }
@@ -1017,15 +1026,121 @@ void bsplineTraj::retireFinished(PlanBatch& pb) {
     pb.activeIdx.swap(nextIdx);
 }
 
-// steps 5-6 for the planners that succeeded
-void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result) {
-    std::vector<uint8_t> okv(result.begin(), result.end());
+namespace {
+StageSwitch g_epilogue;
+std::atomic<long long> g_epilogueGroups{0};
+constexpr int kFinishSampleCap = 2048;   // samples per trajectory the stage's buffers are sized for (a 7 m path at ts 0.1: ~110)
+struct FinishStage {
+    Staged<double> ctrl, limits, factor, pos, vel;
+    Staged<int32_t> npts, n, status;
+};
+}  // namespace
+void bsplineTraj::setDeviceEpilogue(bool on) { g_epilogue.mode.store(on); }
+bool bsplineTraj::deviceEpilogue() { return g_epilogue.mode.load() != 0; }
+void bsplineTraj::deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups) {
+    g_epilogue.totals(deviceDecided, hostRun);
+    if (deviceGroups) *deviceGroups = g_epilogueGroups.load();
+}
+
+// setDeviceEpilogue(true): per group of planners that share a device target, ts_ and controlPointsTs_ (the sample step
+// of evalTrajToMsg(yaw) is ts_) — whatever their counts — the rows padded to the group's largest count, one
+// vigo_traj_finish, one download; linearFactor_, bspline_ and the path installed.  What the call does not decide stays in todo.
+void bsplineTraj::finishOnDevice(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw) {
+    std::vector<size_t> owners;
+    for (size_t i = 0; i < ps.size(); ++i)
+        if (todo[i]) owners.push_back(i);
+    auto same = [&](size_t a, size_t b) {
+        const bsplineTraj *x = ps[owners[a]], *y = ps[owners[b]];
+        return x->link_.sameTarget(y->link_) && x->ts_ == y->ts_ && x->controlPointsTs_ == y->controlPointsTs_;
+    };
+    vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+        bsplineTraj* lead = ps[owners[members[0]]];
+        std::vector<size_t> who;
+        int Ns = 0;
+        for (size_t m : members) {
+            const int n = (int)ps[owners[m]]->optData_.controlPoints.cols();
+            if (n < 7 || n > VIGO_MAX_CTRL_POINTS) continue;
+            who.push_back(owners[m]);
+            Ns = std::max(Ns, n);
+        }
+        if (who.empty() || !lead->syncDevice()) return;
+        const double dt = lead->ts_;
+        // the samples of the longest row, as far as the buffers go: a row with more is reported CAPACITY and stays with the host
+        int S_cap = 1;
+        if (paths) {
+            S_cap = 0;
+            const double longest = (Ns - 3) * lead->controlPointsTs_;
+            if (!(dt > 0.0)) return;
+            for (double t = 0.0; t <= longest && S_cap < kFinishSampleCap; t += dt) ++S_cap;
+        }
+        const bool wantVel = paths && yaw;
+        HostBatch hb(Ns);
+        std::vector<double> limits;
+        for (size_t i : who) {
+            hb.addRow(ps[i]->optData_.controlPoints.data(), (int)ps[i]->optData_.controlPoints.cols());
+            limits.push_back(ps[i]->maxVel_);
+            limits.push_back(ps[i]->maxAcc_);
+        }
+        const size_t B = who.size(), rows = B * (size_t)S_cap * 3;
+        static thread_local FinishStage st;
+        if (!st.ctrl.upload(hb.ctrl) || !st.limits.upload(limits) || (!hb.uniform() && !st.npts.upload(hb.npts)) || !st.factor.alloc(B) ||
+            !st.n.alloc(B) || !st.status.alloc(B) || !st.pos.alloc(rows) || (wantVel && !st.vel.alloc(rows)))
+            return;
+        vigo_handle_t h = lead->link_.handle();
+        g_epilogueGroups += 1;
+        if (!deviceCallOk(vigo_traj_finish(h, (int)B, Ns, hb.uniform() ? nullptr : st.npts.get(), st.ctrl.get(), st.limits.get(), dt, S_cap,
+                                           st.factor.get(), nullptr, st.n.get(), st.pos.get(), wantVel ? st.vel.get() : nullptr, st.status.get()),
+                          "vigo_traj_finish", h))
+            return;
+        std::vector<double> factor(B), pos(paths ? rows : 0), vel(wantVel ? rows : 0);
+        std::vector<int32_t> n(B), status(B);
+        if (!vigo_host::threadSync() || !st.factor.download(factor) || !st.n.download(n) || !st.status.download(status) ||
+            (paths && !st.pos.download(pos)) || (wantVel && !st.vel.download(vel)))
+            return;
+        parallelFor(B, [&](size_t b) {
+            // without paths one sample row is all the call was given: CAPACITY then says nothing about the factor
+            if (status[b] != VIGO_FINISH_OK && !(status[b] == VIGO_FINISH_CAPACITY && !paths)) return;
+            bsplineTraj* p = ps[who[b]];
+            p->bspline_ = trajPlanner::bspline(bsplineDegree, p->optData_.controlPoints, p->controlPointsTs_);  // step 5
+            p->linearFactor_ = factor[b];                                                                    // step 6
+            if (paths) {
+                std::vector<Eigen::Vector3d> pts;
+                const double* q = pos.data() + b * (size_t)S_cap * 3;
+                for (int i = 0; i < n[b]; ++i) pts.push_back(Eigen::Vector3d(q[3 * i], q[3 * i + 1], q[3 * i + 2]));
+                nav_msgs::Path& traj = paths[who[b]];
+                p->eigenPointsToPathMsg(pts, traj);
+                const double* v = wantVel ? vel.data() + b * (size_t)S_cap * 3 : nullptr;
+                for (int i = 0; v && i < n[b]; ++i)   // BT.cpp:1512, on the velocity the device evaluated at (double)i * dt
+                    traj.poses[i].pose.orientation = trajPlanner::quaternion_from_rpy(0, 0, std::atan2(v[3 * i + 1], v[3 * i]));
+            }
+            todo[who[b]] = 0;
+        });
+    });
+}
+
+// steps 5-6 for the planners that succeeded, and with `paths` their evalTrajToMsg(yaw)
+void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw) {
+    std::vector<uint8_t> todo(result.begin(), result.end());   // the planners the host route below still owes
+    if (deviceEpilogue()) {
+        long long want = 0, left = 0;
+        for (uint8_t t : todo) want += t;
+        finishOnDevice(planners, todo, paths, yaw);
+        for (uint8_t t : todo) left += t;
+        g_epilogue.deviceDecided += want - left;
+        g_epilogue.hostRun += left;
+    }
     parallelFor(planners.size(), [&](size_t i) {
-        if (!okv[i]) return;
+        if (!todo[i]) return;
         bsplineTraj* p = planners[i];
         p->bspline_ = trajPlanner::bspline(bsplineDegree, p->optData_.controlPoints, p->controlPointsTs_);  // step 5
         p->linearFeasibilityReparam();                                                                  // step 6
+        if (paths) paths[i] = p->evalTrajToMsg(yaw);
     });
+}
+
+void bsplineTraj::finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw) {
+    if (trajectories) trajectories->assign(planners.size(), nav_msgs::Path());
+    planEpilogue(planners, std::vector<bool>(planners.size(), true), trajectories ? trajectories->data() : nullptr, yaw);
 }
 
 }  // namespace trajPlanner

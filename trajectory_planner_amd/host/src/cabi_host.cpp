@@ -1903,12 +1903,126 @@ int vigo_host_plan_batch_mixed(const unsigned char* vox, const int* dims, const 
     return rc;
 }
 
+// n planners with a pose list each (as vigo_host_plan_batch_mixed) through updatePathBatch + makePlanBatch on one dense
+// byte grid, fresh planners every run, `reps` rounds over
+//   slot 0  setDeviceEpilogue(false)   steps 5-6 and evalTrajToMsg per planner on the host
+//   slot 1  setDeviceEpilogue(true)    one vigo_traj_finish per device group
+// in turn.  with_paths != 0: the overload makePlanBatch(planners, trajectories, yaw != 0); 0: makePlanBatch(planners), no
+// poses.  Planner no_device (< 0: none) sits on a device ordinal that does not exist; planner small_step (< 0: none) gets
+// bspline_traj/timestep = step, a group of its own.  Outputs per slot [2] x ... of the slot's LAST run: ok[n],
+// factor[n] (linearFactor_), n_poses[n], pos[n][pose_cap][3] and quat[n][pose_cap][4] (x, y, z, w; zero padded by the
+// caller); totals[2][3]: deviceEpilogueTotals' device-decided planners, host-route planners and device groups of that
+// run; per run total_ms[2][reps].  The switch is off on return.  Returns 0, -2 when pose_cap is too small, -1 on a bad
+// argument.  Needs a GPU.
+int vigo_host_plan_batch_finish(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                const double* path_xyz, const double* cfg, int no_device, int small_step, double step, int with_paths, int yaw,
+                                int reps, int pose_cap, int* ok, double* factor, int* n_poses, double* pos, double* quat, long long* totals,
+                                double* total_ms) {
+    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg || no_device >= n || small_step >= n || (small_step >= 0 && !(step > 0.0))) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+    ros::NodeHandle nhStep;                    // (a copy of a NodeHandle shares its parameters: copy the map itself)
+    *nhStep.params = *fx.nh.params;
+    if (small_step >= 0) nhStep.setParam("bspline_traj/timestep", step);
+    int rc = 0;
+    for (int rep = 0; rep < reps && rc == 0; ++rep)
+        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
+            FreshPlanners fp;
+            for (int t = 0; t < n; ++t) {
+                fp.owners.emplace_back(new bsplineTraj(t == small_step ? nhStep : fx.nh));
+                if (t == no_device) fp.owners.back()->setDevice(63);
+                fp.owners.back()->setMap(fx.maps[0]);
+                fp.owners.back()->updateMaxVel(2.0);
+                fp.owners.back()->updateMaxAcc(3.0);
+                fp.ps.push_back(fp.owners.back().get());
+            }
+            bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
+            bsplineTraj::setDeviceEpilogue(slot == 1);
+            long long d0, h0, g0, d1, h1, g1;
+            bsplineTraj::deviceEpilogueTotals(&d0, &h0, &g0);
+            std::vector<nav_msgs::Path> traj;
+            const auto t0 = std::chrono::steady_clock::now();
+            const std::vector<bool> planned = with_paths ? bsplineTraj::makePlanBatch(fp.ps, traj, yaw != 0) : bsplineTraj::makePlanBatch(fp.ps);
+            total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            bsplineTraj::deviceEpilogueTotals(&d1, &h1, &g1);
+            bsplineTraj::setDeviceEpilogue(false);
+            if (rep + 1 < reps) continue;
+            totals[3 * slot] = d1 - d0; totals[3 * slot + 1] = h1 - h0; totals[3 * slot + 2] = g1 - g0;
+            for (int t = 0; t < n && rc == 0; ++t) {
+                const size_t o = (size_t)slot * n + t;
+                ok[o] = planned[t] ? 1 : 0;
+                factor[o] = fp.ps[t]->getLinearFactor();
+                n_poses[o] = with_paths ? (int)traj[t].poses.size() : 0;
+                if (n_poses[o] > pose_cap) { rc = -2; break; }
+                for (int i = 0; i < n_poses[o]; ++i) {
+                    const auto& ps = traj[t].poses[i].pose;
+                    double* p = pos + (o * pose_cap + i) * 3;
+                    double* q = quat + (o * pose_cap + i) * 4;
+                    p[0] = ps.position.x; p[1] = ps.position.y; p[2] = ps.position.z;
+                    q[0] = ps.orientation.x; q[1] = ps.orientation.y; q[2] = ps.orientation.z; q[3] = ps.orientation.w;
+                }
+            }
+        }
+    bsplineTraj::setDeviceEpilogue(false);
+    return rc;
+}
+
+// The epilogue stage alone (bsplineTraj::finishBatch: steps 5-6 and evalTrajToMsg) for n planners on one dense byte grid
+// with the control points ctrl[n][Ns][3], n_pts[n] of them each: `reps` rounds, setDeviceEpilogue off then on in each,
+// wall time in ms[reps][2].  *mismatch: planners whose linearFactor_, pose count, positions or quaternions of the last
+// round differ between the two.  The switch is off on return.  Returns 0, -1 on a bad argument.  Needs a GPU.
+int vigo_host_finish_timing(const unsigned char* vox, const int* dims, const double* origin, double res, const double* cfg, int n, int Ns,
+                            const int* n_pts, const double* ctrl, int reps, double* ms, long long* mismatch) {
+    if (n < 1 || Ns < 7 || reps < 1 || !n_pts || !ctrl || !cfg || !ms || !mismatch) return -1;
+    const std::shared_ptr<mapManager::occMap> map = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
+    ros::NodeHandle nh;
+    setBsplineParams(nh, cfg);
+    std::vector<std::unique_ptr<bsplineTraj>> owners;
+    std::vector<bsplineTraj*> ps;
+    for (int t = 0; t < n; ++t) {
+        if (n_pts[t] < 7 || n_pts[t] > Ns) return -1;
+        owners.emplace_back(new bsplineTraj(nh));
+        owners.back()->setMap(map);
+        owners.back()->updateMaxVel(2.0);
+        owners.back()->updateMaxAcc(3.0);
+        Eigen::MatrixXd c(3, n_pts[t]);
+        for (int i = 0; i < n_pts[t]; ++i) for (int k = 0; k < 3; ++k) c(k, i) = ctrl[((size_t)t * Ns + i) * 3 + k];
+        owners.back()->setControlPoints(c);
+        ps.push_back(owners.back().get());
+    }
+    std::vector<nav_msgs::Path> traj[2];
+    std::vector<double> factor[2];
+    for (int rep = 0; rep < reps; ++rep)
+        for (int slot = 0; slot < 2; ++slot) {
+            bsplineTraj::setDeviceEpilogue(slot == 1);
+            const auto t0 = std::chrono::steady_clock::now();
+            bsplineTraj::finishBatch(ps, &traj[slot]);
+            ms[2 * rep + slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            bsplineTraj::setDeviceEpilogue(false);
+            factor[slot].clear();
+            for (bsplineTraj* p : ps) factor[slot].push_back(p->getLinearFactor());
+        }
+    *mismatch = 0;
+    for (int t = 0; t < n; ++t) {
+        bool same = std::memcmp(&factor[0][t], &factor[1][t], sizeof(double)) == 0 && traj[0][t].poses.size() == traj[1][t].poses.size();
+        for (size_t i = 0; same && i < traj[0][t].poses.size(); ++i) {
+            const auto &a = traj[0][t].poses[i].pose, &b = traj[1][t].poses[i].pose;
+            const double va[7] = {a.position.x, a.position.y, a.position.z, a.orientation.x, a.orientation.y, a.orientation.z, a.orientation.w};
+            const double vb[7] = {b.position.x, b.position.y, b.position.z, b.orientation.x, b.orientation.y, b.orientation.z, b.orientation.w};
+            same = std::memcmp(va, vb, sizeof(va)) == 0;
+        }
+        *mismatch += same ? 0 : 1;
+    }
+    return 0;
+}
+
 // the facade's opt-in switches as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
-// deviceReguide, bit 6 mixedBatches (0: everything off, the default)
+// deviceReguide, bit 6 mixedBatches, bit 7 deviceEpilogue (0: everything off, the default)
 int vigo_host_switches() {
     using trajPlanner::bsplineTraj;
     return (bsplineTraj::deviceAstar() ? 1 : 0) | (bsplineTraj::deviceGuides() << 1) | (bsplineTraj::devicePrologue() ? 8 : 0) |
-           (bsplineTraj::deviceReguide() << 4) | (bsplineTraj::mixedBatches() ? 64 : 0);
+           (bsplineTraj::deviceReguide() << 4) | (bsplineTraj::mixedBatches() ? 64 : 0) | (bsplineTraj::deviceEpilogue() ? 128 : 0);
 }
 
 }  // extern "C"

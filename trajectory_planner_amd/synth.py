@@ -351,6 +351,32 @@ def host_esdf(world: World, plane: int = 2, unknown_is_site: bool = False):
     return out, np.array(world.origin, dtype=np.float64)
 
 
+def host_traj_finish(ts_ctrl, ts, ctrl, limits, sample_dt, S_cap, n_pts=None, out=None, want_max=True, want_vel=True):
+    """Vigo.traj_finish's result by the library's host twin (vigo_traj_finish_host: csrc/vigo_finish_core.hpp compiled
+    for the CPU; no GPU), numpy in and out: ctrl [B,Ns,3], limits [B,2], n_pts int32 [B] or None -> dict of factor, max,
+    n, pos, vel, status.  out = (pos, vel): the arrays the samples are written into (rows that are not written keep
+    what they held).  Returns the library's code instead of the dict when the call is refused."""
+    import ctypes as C
+    from . import _lib
+    ctrl = np.ascontiguousarray(ctrl, dtype=np.float64)
+    B, Ns = ctrl.shape[0], ctrl.shape[1]
+    limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(B, 2)
+    npts = None if n_pts is None else np.ascontiguousarray(n_pts, dtype=np.int32)
+    if out is not None:
+        pos, vel = out
+    else:
+        pos = np.zeros((B, max(int(S_cap), 0), 3))
+        vel = np.zeros((B, max(int(S_cap), 0), 3)) if want_vel else None
+    factor, mx = np.zeros(B), (np.zeros((B, 2)) if want_max else None)
+    n, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    rc = _lib.load().vigo_traj_finish_host(float(ts_ctrl), float(ts), B, Ns, p(npts), p(ctrl), p(limits), float(sample_dt), int(S_cap),
+                                           p(factor), p(mx), p(n), p(pos), p(vel), p(status))
+    if rc != 0:
+        return rc
+    return {"factor": factor, "max": mx, "n": n, "pos": pos, "vel": vel, "status": status}
+
+
 # ---- guides from the planner's own host pipeline (product code: libtrajectory_planner_vigo.so) ---------------------------
 # cfg/bspline_interactive/bspline_planner_param.yaml: distance_threshold, min_height, max_height, max_obstacle_size
 PIPELINE_CFG = np.array([0.5, 0.7, 1.3, 5.0, 5.0, 3.0])

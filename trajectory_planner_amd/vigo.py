@@ -21,6 +21,7 @@ GUIDE_OK, GUIDE_DEFERRED = 0, 1                                                 
 REGUIDE_DONE, REGUIDE_SEARCH_FAILED, REGUIDE_NOT_REQUIRED, REGUIDE_DEFERRED, REGUIDE_SKIPPED = 0, 1, 2, 3, 4   # vigo_rebound_reguide's out_status
 PATHS_OK, PATHS_FAILED, PATHS_DEFERRED = 0, 1, 2                                 # vigo_collision_segs' / vigo_path_search's out_status
 SEED_OK, SEED_NO_SPACING, SEED_GOAL_OCCUPIED, SEED_TOO_SHORT, SEED_DEFERRED, SEED_BAD_INPUT = 0, 1, 2, 3, 4, 5   # vigo_seed_paths' out_status
+FINISH_OK, FINISH_CAPACITY, FINISH_INVALID_N = 0, 1, 2   # vigo_traj_finish's out_status
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -443,6 +444,38 @@ class Vigo:
                                                   float(dt), C.c_void_p(flag.data_ptr()),
                                                   C.c_void_p(first.data_ptr())), "vigo_traj_collision")
         return flag, first
+
+    def traj_finish(self, ctrl, limits, sample_dt, S_cap, n_pts=None, out=None, want_max=True, want_vel=True):
+        """vigo_traj_finish: the end of a plan for ctrl [B,Ns,3] f64 (row b holds n_pts[b] control points, i32 [B]; None:
+        Ns each) with limits [B,2] f64 = max_vel, max_acc -> dict of factor f64[B] (linearFactor_), max f64[B,2] (maxV,
+        maxA; None without want_max), n i32[B] (samples of the `t <= duration; t += sample_dt` loop), pos f64[B,S_cap,3],
+        vel f64[B,S_cap,3] (at i * sample_dt; None without want_vel), status i32[B] (FINISH_*).  Sample rows beyond n, and
+        every row of an INVALID_N trajectory, are not written: zeros, or what the caller's out = (pos, vel) held."""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, Ns, _ = ctrl.shape
+        S_cap = int(S_cap)
+        _shape(limits, (B, 2), "limits")
+        _shape(n_pts, (B,), "n_pts")
+        d = self.device
+        if out is not None:
+            pos, vel = out
+            _shape(pos, (B, S_cap, 3), "out pos"); _ptr(pos, torch.float64, "out pos", d)
+            if vel is not None:
+                _shape(vel, (B, S_cap, 3), "out vel"); _ptr(vel, torch.float64, "out vel", d)
+        else:
+            pos = torch.zeros(B, max(S_cap, 0), 3, dtype=torch.float64, device=d)
+            vel = torch.zeros(B, max(S_cap, 0), 3, dtype=torch.float64, device=d) if want_vel else None
+        factor = torch.zeros(B, dtype=torch.float64, device=d)
+        mx = torch.zeros(B, 2, dtype=torch.float64, device=d) if want_max else None
+        n = torch.zeros(B, dtype=torch.int32, device=d)
+        status = torch.zeros(B, dtype=torch.int32, device=d)
+        self._check(self._lib.vigo_traj_finish(self._h, B, Ns, _ptr(n_pts, torch.int32, "n_pts", d),
+                                               _ptr(ctrl, torch.float64, "ctrl", d), _ptr(limits, torch.float64, "limits", d),
+                                               float(sample_dt), S_cap, C.c_void_p(factor.data_ptr()),
+                                               None if mx is None else C.c_void_p(mx.data_ptr()), C.c_void_p(n.data_ptr()),
+                                               C.c_void_p(pos.data_ptr()), None if vel is None else C.c_void_p(vel.data_ptr()),
+                                               C.c_void_p(status.data_ptr())), "vigo_traj_finish")
+        return {"factor": factor, "max": mx, "n": n, "pos": pos, "vel": vel, "status": status}
 
     def traj_dynamic_collision(self, ctrl, dt, obs_off=None, obs=None):
         _shape(ctrl, (None, None, 3), "ctrl")
