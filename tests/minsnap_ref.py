@@ -1,6 +1,8 @@
 """numpy statement of the min-snap QP of polyTrajSolver (PS.cpp:241-846) used by the tests: the
 matrices in normalised segment time, polynomial evaluation, and an algorithm-independent optimality
 check (KKT conditions) for a candidate solution."""
+import math
+
 import numpy as np
 
 
@@ -122,7 +124,8 @@ def corridor_rows(wp, T, corridor, cres, deg=7):
         t = 0.0
         while t <= 1.0:
             r = np.zeros(K * D)
-            r[i * D:(i + 1) * D] = t ** np.arange(D)
+            r[i * D:(i + 1) * D] = [math.pow(t, d) for d in range(D)]   # libm's pow, as PS.cpp:570: numpy's array power
+            #                                                              differs from it in the last bit at some t
             rows.append(r)
             cen.append(wp[i] + (wp[i + 1] - wp[i]) * t)
             rad.append(corridor[i])

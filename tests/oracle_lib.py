@@ -1,5 +1,5 @@
-"""ctypes bindings of the CPU oracle (oracle/libvigo_oracle.so) and of the two verbatim-reference libraries
-(oracle/_ref/libref_lbfgs.so, oracle/_ref/libref_bspline.so).  TEST INFRASTRUCTURE: imported by tests/,
+"""ctypes bindings of the CPU oracle (oracle/libvigo_oracle.so) and of the three verbatim-reference libraries
+(oracle/_ref/libref_lbfgs.so, oracle/_ref/libref_bspline.so, oracle/_ref/libref_poly.so).  TEST INFRASTRUCTURE: imported by tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg only."""
 import ctypes as C
 import os
@@ -244,6 +244,88 @@ class RefBsplineTraj:
             return n, None, None, None, None
         npath = n
         return n, seg[:n].copy(), [ppts[poff[i]:poff[i + 1]].copy() for i in range(npath)], goff, gpv[:goff[self.N]].copy()
+
+
+REF_POLY_SO = os.path.join(ORACLE_DIR, "_ref", "libref_poly.so")
+# the stand-in OSQP's question: (n, m, P [n][n], q [n], A [m][n], l [m], u [m], x_out [n]) -> 0 solved, else a solver error
+QP_HOOK_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp)
+REF_POLY_UNDEFINED = -99
+_ref_poly = None
+
+
+def ref_poly():
+    """The verbatim reference polyTrajSolver.cpp / polyTrajOccMap.cpp / piecewiseLinearTraj.cpp compiled against
+    oracle/ref_shim (oracle/ref_poly_harness.cpp), or None when it was never built."""
+    global _ref_poly
+    if _ref_poly is None:
+        if not os.path.exists(REF_POLY_SO):
+            return None
+        L = C.CDLL(REF_POLY_SO)
+        vp = C.c_void_p
+        L.rps_set_hook.argtypes = [QP_HOOK_FN]
+        L.rps_duplicate_inserts.restype = C.c_long
+        L.rps_log_count.restype = C.c_int
+        L.rps_log_shape.argtypes = [C.c_int, _ip]
+        L.rps_log_get.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.rps_solver_create.restype = vp
+        L.rps_solver_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
+        L.rps_solver_destroy.argtypes = [vp]
+        L.rps_solver_set_path.argtypes = [vp, C.c_int, _dp]
+        for name in ("rps_solver_continuity", "rps_solver_constraints", "rps_solver_solve"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [vp]
+        L.rps_solver_set_conds.argtypes = [vp, _dp]
+        L.rps_solver_set_soft.argtypes = [vp, C.c_int, _dp]
+        L.rps_solver_set_corridor.argtypes = [vp, C.c_int, _dp, C.c_double]
+        L.rps_solver_corridor_order.restype = C.c_int
+        L.rps_solver_corridor_order.argtypes = [vp, _ip, _dp, _dp, C.c_int]
+        L.rps_solver_knots.restype = C.c_int
+        L.rps_solver_knots.argtypes = [vp, _dp, C.c_int]
+        L.rps_solver_solution.restype = C.c_int
+        L.rps_solver_solution.argtypes = [vp, C.c_int, _dp, C.c_int]
+        L.rps_solver_trajectory.restype = C.c_int
+        L.rps_solver_trajectory.argtypes = [vp, C.c_double, _dp, C.c_int]
+        L.rps_solver_eval.argtypes = [vp, C.c_int, _dp, _dp]
+        L.rps_occ_create.restype = vp
+        L.rps_occ_create.argtypes = [_dp]
+        L.rps_occ_destroy.argtypes = [vp]
+        L.rps_occ_set_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, _up]
+        L.rps_occ_set_path.argtypes = [vp, C.c_int, _dp, _dp]
+        L.rps_occ_make_plan.restype = C.c_int
+        L.rps_occ_make_plan.argtypes = [vp, C.c_int, _dp, C.c_int, _ip]
+        L.rps_occ_rounds.restype = C.c_int
+        L.rps_occ_rounds.argtypes = [vp, C.c_int, _dp, C.c_int]
+        L.rps_occ_round_traj.restype = C.c_int
+        L.rps_occ_round_traj.argtypes = [vp, C.c_int, _dp, C.c_int]
+        L.rps_occ_duration.restype = C.c_double
+        L.rps_occ_duration.argtypes = [vp]
+        L.rps_occ_valid.restype = C.c_int
+        L.rps_occ_valid.argtypes = [vp]
+        L.rps_occ_solver.restype = vp
+        L.rps_occ_solver.argtypes = [vp]
+        L.rps_occ_trajectory.restype = C.c_int
+        L.rps_occ_trajectory.argtypes = [vp, C.c_double, _dp, C.c_int]
+        L.rps_occ_eval.argtypes = [vp, C.c_int, _dp, _dp]
+        L.rps_occ_check.restype = C.c_int
+        L.rps_occ_check.argtypes = [vp, C.c_int, _dp, C.c_double, _ip, C.c_int, _ip]
+        L.rps_pwl.restype = C.c_int
+        L.rps_pwl.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_int, _dp, _ip, _dp, C.c_int, _dp, _dp]
+        _ref_poly = L
+    return _ref_poly
+
+
+def ref_poly_log(L):
+    """the QPs the stand-in OSQP was given since rps_log_clear: [dict(n, m, tag, status, P, q, A, l, u, x)]"""
+    out = []
+    for i in range(L.rps_log_count()):
+        sh = np.zeros(4, dtype=np.int32)
+        L.rps_log_shape(i, _i(sh))
+        n, m = int(sh[0]), int(sh[1])
+        r = dict(n=n, m=m, tag=int(sh[2]), status=int(sh[3]), P=np.zeros((n, n)), q=np.zeros(n), A=np.zeros((m, n)),
+                 l=np.zeros(m), u=np.zeros(m), x=np.zeros(n))
+        L.rps_log_get(i, _d(r["P"]), _d(r["q"]), _d(r["A"]), _d(r["l"]), _d(r["u"]), _d(r["x"]))
+        out.append(r)
+    return out
 
 
 def ref_bspline_at(ctrl, ts, deriv, t):

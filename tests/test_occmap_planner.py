@@ -111,8 +111,9 @@ def restate(vox, wp, corridor=True, conds=None, **kw):
     soft = np.array([1.0, 1.0, 0.0]) if c["soft_constraint"] else None   # PM.cpp:357-358: the bool as the radius
     delT, fs, max_iter = float(c["sample_delta_time"]), float(c["shrinking_factor"]), int(c["maximum_iteration_num"])
     wp = np.asarray(wp, np.float64)
-    prev, iters, valid, traj, kn = None, 0, False, [], None
+    prev, iters, valid, traj, kn, rounds = None, 0, False, [], None, []
     while True:
+        rounds.append(list(corr))
         co, mask, kn = qp(wp, deg, diff, cont, vel, np.array(corr) if corridor else None, float(c["corridor_res"]),
                           soft if corridor else None, conds)
         if prev is not None:                                 # an axis whose QP fails keeps its previous polynomial
@@ -140,7 +141,7 @@ def restate(vox, wp, corridor=True, conds=None, **kw):
             corr[s] = corr[s] * fs
         if iters > max_iter:
             break
-    return dict(valid=valid, iters=iters, traj=np.array(traj), co=prev, kn=kn, deg=deg)
+    return dict(valid=valid, iters=iters, traj=np.array(traj), co=prev, kn=kn, deg=deg, rounds=rounds[:iters])
 
 
 def restated_get_trajectory(r, dt):

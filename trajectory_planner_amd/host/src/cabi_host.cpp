@@ -461,6 +461,38 @@ int vigo_host_minsnap_eval(int n_wp, const double* wp, int deg, int diff, int co
     return 0;
 }
 
+// polyTrajSolver's accessors on GIVEN coefficients (no QP): updatePath(wp) at velocity vel gives the knots (knots_out,
+// n_wp doubles), installSolution takes coeffs (3 blocks of (n_wp-1)(deg+1), un-normalised local time), then getPose /
+// getPos / getVel / getAcc at n_t times: out[n_t][13] = pose x, y, z, yaw, position, velocity, acceleration, and
+// getTrajectory(traj, delT) into traj_out (first cap poses x, y, z, yaw; delT <= 0: not sampled).  Returns the number of
+// trajectory poses.
+int vigo_host_poly_eval(int n_wp, const double* wp, int deg, double vel, const double* coeffs, int n_t, const double* t, double* out,
+                        double* knots_out, double delT, double* traj_out, int cap) {
+    if (n_wp < 2 || !wp || deg < 0 || !coeffs || n_t < 0 || (n_t > 0 && (!t || !out)) || !knots_out) return -1;
+    std::vector<trajPlanner::pose> path;
+    for (int i = 0; i < n_wp; ++i) path.push_back(trajPlanner::pose(wp[3 * i], wp[3 * i + 1], wp[3 * i + 2]));
+    trajPlanner::polyTrajSolver s(deg, 4, 4, vel);
+    s.updatePath(path);
+    const size_t n = (size_t)(n_wp - 1) * (deg + 1);
+    s.installSolution(std::vector<double>(coeffs, coeffs + n), std::vector<double>(coeffs + n, coeffs + 2 * n),
+                      std::vector<double>(coeffs + 2 * n, coeffs + 3 * n));
+    std::memcpy(knots_out, s.getTimeKnot().data(), sizeof(double) * n_wp);
+    for (int k = 0; k < n_t; ++k) {
+        const trajPlanner::pose p = s.getPose(t[k]);
+        const Eigen::Vector3d x = s.getPos(t[k]), v = s.getVel(t[k]), a = s.getAcc(t[k]);
+        double* o = out + 13 * (size_t)k;
+        o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.yaw;
+        for (int q = 0; q < 3; ++q) { o[4 + q] = x(q); o[7 + q] = v(q); o[10 + q] = a(q); }
+    }
+    if (!(delT > 0) || !traj_out) return 0;
+    std::vector<trajPlanner::pose> traj;
+    s.getTrajectory(traj, delT);
+    for (size_t i = 0; i < traj.size() && (int)i < cap; ++i) {
+        traj_out[4 * i] = traj[i].x; traj_out[4 * i + 1] = traj[i].y; traj_out[4 * i + 2] = traj[i].z; traj_out[4 * i + 3] = traj[i].yaw;
+    }
+    return (int)traj.size();
+}
+
 // BASELINE configs[0]: one polyTrajOctomap::makePlan() (cfg/planner_interactive.yaml values passed in
 // `cfg`: box[3], map_resolution, sample_delta_time, desired_velocity, initial_radius, shrinking_factor,
 // corridor_res, maximum_iteration_num, traj_timeout, mode) on a dense byte grid (vigo.h voxel
@@ -582,6 +614,26 @@ int vigo_host_occ_plan(int nx, int ny, int nz, const double* origin, double res,
     info_out[6] = e(0);
     info_out[7] = e(1);
     return 0;
+}
+
+// The same plan, then the planner's accessors at n_t times: out[n_t][16] = getPose's position (3) and orientation
+// (x, y, z, w), getPos, getVel, getAcc — through polyTrajOccMap's clamp to getDuration() and its switch to the PWL when
+// use_pwl_failsafe is set and no plan was valid.  Returns makePlan's result (0 / 1), -1 on bad arguments.
+int vigo_host_occ_plan_eval(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int n_wp,
+                            const double* wp, const double* cfg, const double* conds, int mode, int n_t, const double* t, double* out) {
+    if (n_wp < 2 || !wp || !cfg || n_t < 0 || (n_t > 0 && (!t || !out))) return -1;
+    auto p = makeOccPlanner(denseMap(nx, ny, nz, origin, res, voxels), cfg, n_wp, wp, conds);
+    std::vector<trajPlanner::pose> traj;
+    const bool r = mode == 2 ? p->makePlan(traj) : p->makePlan(traj, mode != 0);
+    for (int k = 0; k < n_t; ++k) {
+        double* o = out + 16 * (size_t)k;
+        const geometry_msgs::PoseStamped ps = p->getPose(t[k]);
+        o[0] = ps.pose.position.x; o[1] = ps.pose.position.y; o[2] = ps.pose.position.z;
+        o[3] = ps.pose.orientation.x; o[4] = ps.pose.orientation.y; o[5] = ps.pose.orientation.z; o[6] = ps.pose.orientation.w;
+        const Eigen::Vector3d x = p->getPos(t[k]), v = p->getVel(t[k]), a = p->getAcc(t[k]);
+        for (int q = 0; q < 3; ++q) { o[7 + q] = x(q); o[10 + q] = v(q); o[13 + q] = a(q); }
+    }
+    return r ? 1 : 0;
 }
 
 // polyTrajOccMap::makePlanBatch of P planners on one map (path i = wp[wp_off[i] .. wp_off[i+1]), cfg [P][16] and conds
