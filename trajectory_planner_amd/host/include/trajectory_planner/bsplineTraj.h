@@ -102,97 +102,9 @@ public:
 
     bool makePlan();
     bool makePlan(nav_msgs::Path& trajectory, bool yaw = true);
-    /* Planners are grouped by control-point count, map object and every hot-path parameter (the yaml values, maxVel):
-     * each group is one batch on the device.  Returns per-planner success like makePlan(). */
-    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners);
-    /* not in the reference: the batched makePlan(nav_msgs::Path&, bool) — trajectories[i] receives what planner i's
-     * evalTrajToMsg(yaw) gives after the plan; a planner that fails gets an empty path */
-    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw = true);
-    /* Steps 5-6 of makePlan() (the spline object, linearFeasibilityReparam) and, for the overload above, the samples of
-     * evalTrajToMsg.  Off (default): per planner on the host workers, as it always was.  On: ONE vigo_traj_finish call
-     * per device group — planners that share a device target, ts_ and controlPointsTs_ (the sample step is ts_), whatever
-     * their control-point counts: rows are padded to the group's largest count; linearFactor_, bspline_ and the path
-     * are installed from its downloads, the yaw from the downloaded velocity with libm's atan2 as evalTrajToMsg takes it.
-     * A planner without a device, one of more than VIGO_MAX_CTRL_POINTS control points, a row the call reports over
-     * capacity (the facade sizes at most 2048 samples per trajectory) or with an invalid count, and every planner of a
-     * group whose call failed take the host route.  The result is the same bits either way. */
-    static void setDeviceEpilogue(bool on);
-    static bool deviceEpilogue();
-    /* Process-wide running totals: the planners whose epilogue the device call decided / those of calls under the
-     * switch that took the host route, and the vigo_traj_finish calls made (one per device group) */
-    static void deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups);
-    /* added (workload tools, cabi_host.cpp: vigo_host_finish_timing): that stage alone on the planners' current control
-     * points, as makePlanBatch runs it for planners that all succeeded; trajectories may be NULL */
-    static void finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw = true);
-    /* The rebound loop of BT.cpp:611-685 runs on the device between two A* calls (vigo_rebound_rounds, default) or
-     * round by round from the host (the round-1 path, kept for comparison: identical control points). */
-    /* makePlanBatch of at least this many planners runs as two to four pipelined parts of >= half this size (all but the
-     * first on companion host threads with their own handles and HIP streams); 0 = never.  Default 2048.  Same plans. */
-    static void setBatchPipelineThreshold(size_t planners);
-    static void setDeviceResidentRebound(bool on);
-    static bool deviceResidentRebound();
-    /* The A* searches of makePlanBatch's prologue as ONE vigo_astar_search launch per device group (plus one for the
-     * merged retries of the failures) instead of host searches on the worker threads.  Default false.  Same plans: a
-     * search the device defers (its budgets, setDeviceAstarBudget), and every search of a planner whose handle has no
-     * map snapshot, is run by the host A*.  The A* of a re-guide inside the rebound loop is setDeviceReguide's. */
-    static void setDeviceAstar(bool on);
-    static bool deviceAstar();
-    /* max_expansions of those launches (pops per search before the device hands the search back); default 16384 */
-    static void setDeviceAstarBudget(int maxExpansions);
-    /* Process-wide running totals (measurements, tests; take the difference around a call): the prologue searches the
-     * device decided (found / not found) and those the host A* ran (deferred, path too long, no device, outside the
-     * snapshot), and the wall time of makePlanBatch prologues in seconds — summed over the parts when a call is
-     * split into pipelined parts, which run side by side. */
-    static void deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds);
-    const std::vector<std::vector<Eigen::Vector3d>>& getAstarPaths() const { return astarPaths_; }   /* added (tests) */
-    const std::vector<std::pair<int, int>>& getCollisionSeg() const { return collisionSeg_; }         /* added (tests) */
-    /* Step 3 of makePlanBatch's prologue (assignGuidePointsSemiCircle).  0 (default): the host step as it always was.
-     * 1: ONE vigo_guide_assign launch per device group; a planner the device defers (a path longer than
-     * vigo_guide_capacity), or whose group has no device or snapshot, runs the same code on the worker threads —
-     * csrc/vigo_guide_core.hpp with its portable atan2, the kernel's bit-exact twin — so a planner's guides do not depend
-     * on which side produced them.  2: every planner runs that twin on the workers (the emulation of 1).  Settings 1
-     * and 2 differ from 0 by the last places of atan2 (vigo.h: vigo_guide_assign).  The re-guide step inside the
-     * rebound loop does not consult this setting: it is setDeviceReguide's. */
-    static void setDeviceGuides(int mode);
-    static int deviceGuides();
-    /* Process-wide running totals: the prologue trajectories whose guides the device produced / the workers' twin produced */
-    static void deviceGuideTotals(long long* deviceDecided, long long* hostRun);
-    /* The whole prologue of makePlanBatch (steps 1-3) as ONE device chain per group of planners that share a batch key:
-     * control points up, vigo_path_search (findCollisionSeg, the A* searches, pathSearch's merge rules) and
-     * vigo_guide_assign on its output, one download; collisionSeg_, astarPaths_ and the guide pairs are then installed
-     * where the host steps put them.  Default false; when on, setDeviceAstar / setDeviceGuides are not consulted.  A
-     * planner either call defers, one whose merges leave more paths than segments (the device returns the bounded
-     * lists only), and every planner of a group without device or snapshot run host steps 1-3 on the workers with the
-     * guide step's bit-exact twin (as setDeviceGuides(1) does for what the device defers): a plan does not depend on
-     * which side ran it.  A planner whose path search FAILS on the device takes the "Fail because of A* failure" path
-     * after replaying host steps 1-2 on the workers: vigo_path_search returns nothing for it, and the host steps leave
-     * the scanned segments and the paths found before the failure in getCollisionSeg() / getAstarPaths(), so these
-     * read the same under every setting.  Searches run under setDeviceAstarBudget.  The re-guide step inside the
-     * rebound loop (findCollisionSeg, A*, guide assignment on the current control points) is not part of the chain:
-     * setDeviceReguide puts it on the device. */
-    static void setDevicePrologue(bool on);
-    static bool devicePrologue();
-    /* Process-wide running totals: the prologue planners whose outcome the device chain decided (prepared, or failed:
-     * those replay host steps 1-2 for their lists and still count here) / those the host steps decided (deferred, lists
-     * cut by the bound, no device), and the wall time of the chains (upload to installed results) in seconds */
-    static void devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds);
-    /* The re-guide step of the device-resident rebound loop (the `if (hasCollision)` block of BT.cpp:656-679) for the
-     * planners vigo_rebound_rounds hands back with a static collision and failCount < 4.  0 (default): reboundStep on
-     * the workers, as it always was.  1: ONE vigo_rebound_reguide call per device group on the group's staged batch;
-     * collisionSeg_, the appended guide pairs, astarPaths_, the weights, failCount and needOptimize are installed from
-     * its outputs (through the host: the batch is packed again for the next vigo_rebound_rounds call).  A planner the
-     * call defers, and every planner of a group without device or snapshot, runs the same step on the workers with the
-     * guide step's bit-exact twin (csrc/vigo_guide_core.hpp with its portable atan2), so a plan does not depend on
-     * which side ran the step.  2: every such planner runs that twin on the workers (the emulation of 1).  Settings 1
-     * and 2 differ from 0 by the last places of atan2.  The forced A* of failCount >= 4 (BT.cpp:640-654), a planner
-     * with a dynamic collision only, and the 30 ms budget's exit stay with reboundStep on the host under every
-     * setting.  Searches run under setDeviceAstarBudget.  Only consulted when deviceResidentRebound(). */
-    static void setDeviceReguide(int mode);
-    static int deviceReguide();
-    /* Process-wide running totals: the re-guide steps vigo_rebound_reguide decided / the workers' twin ran */
-    static void deviceReguideTotals(long long* deviceDecided, long long* hostRun);
-    /* added (tests, cabi_host.cpp: vigo_host_plan_batch_reguide): the inputs of every step the workers' twin runs are
-     * appended to *log (NULL: off, the default), so the same steps can be put to the kernels' host twin afterwards */
+
+    /* added (tests, cabi_host.cpp: vigo_host_plan_batch_reguide): the inputs of one re-guide step the workers' twin runs
+     * (BatchOptions::reguideStepLog), so the same steps can be put to the kernels' host twin afterwards */
     struct ReguideStepRecord {
         int N;
         std::vector<double> ctrl, gpv;
@@ -200,37 +112,156 @@ public:
         int failCount, gateDynamic;
         double weights[4];
     };
-    static void setReguideStepLog(std::vector<ReguideStepRecord>* log);
-    /* Planners of DIFFERENT control-point counts in one device batch of the solves (solveBatch) and of the
-     * device-resident rebound rounds (deviceRounds): vigo_optimize_mixed / vigo_rebound_rounds_mixed.  Off (default): one
-     * device batch per distinct count.  On: planners that share everything but the count (sameBatchKey's other terms)
-     * share a batch when their counts lie in one shape class of the kernels — all 7 .. 32, or all 33 .. 64; counts above
-     * 64 keep a batch per count.  A group whose counts are all equal calls the uniform entry, so a workload of one
-     * count runs the same kernels under either setting; a planner's result is the same bits under either setting
-     * (include/vigo.h, "mixed control-point counts").  Every other stage keeps its grouping by exact count: the opt-in
-     * device stages (A*, prologue chain, re-guide), the gates of gateBatch, costGrad and the host-driven loop's gates. */
-    static void setMixedBatches(bool on);
-    static bool mixedBatches();
-    /* Process-wide running totals, under either setting: the device batches solveBatch and deviceRounds opened, and the
-     * planners in them */
-    static void mixedBatchTotals(long long* deviceBatches, long long* planners);
-    /* updatePath() for many planners at once: the least-squares fits run as one device launch */
+
+    /* ---- the batch calls: makePlanBatch, finishBatch, updatePathBatch, seedPathBatch ------------------------------
+     * Which opt-in device stages a batch call uses is a value of the call: a BatchOptions.  The call reads it once, at
+     * entry (normalized()), and hands it by value to everything it runs, the companion threads of a pipelined call
+     * included; what its stages did comes back as the call's own BatchStats.  Two calls on two host threads, each with
+     * its own planners, therefore neither change each other's route nor see each other's counts.  Under every option a
+     * planner's result is the same bits, except where a field says otherwise (the last places of atan2). */
+    struct BatchOptions {
+        /* The A* searches of makePlanBatch's prologue as ONE vigo_astar_search launch per device group (plus one for the
+         * merged retries of the failures) instead of host searches on the worker threads.  Same plans: a search the
+         * device defers (its budgets, deviceAstarBudget), and every search of a planner whose handle has no map
+         * snapshot, is run by the host A*.  The A* of a re-guide inside the rebound loop is deviceReguide's. */
+        bool deviceAstar = false;
+        /* max_expansions of the device searches of every stage (pops per search before the device hands the search
+         * back); negative values count as 0 */
+        int deviceAstarBudget = 16384;
+        /* Step 3 of makePlanBatch's prologue (assignGuidePointsSemiCircle).  0: the host step as it always was.
+         * 1: ONE vigo_guide_assign launch per device group; a planner the device defers (a path longer than
+         * vigo_guide_capacity), or whose group has no device or snapshot, runs the same code on the worker threads —
+         * csrc/vigo_guide_core.hpp with its portable atan2, the kernel's bit-exact twin — so a planner's guides do not
+         * depend on which side produced them.  2: every planner runs that twin on the workers (the emulation of 1).
+         * Settings 1 and 2 differ from 0 by the last places of atan2 (vigo.h: vigo_guide_assign); any other value
+         * counts as 0.  The re-guide step inside the rebound loop does not consult this field: it is deviceReguide's. */
+        int deviceGuides = 0;
+        /* The whole prologue of makePlanBatch (steps 1-3) as ONE device chain per group of planners that share a batch
+         * key: control points up, vigo_path_search (findCollisionSeg, the A* searches, pathSearch's merge rules) and
+         * vigo_guide_assign on its output, one download; collisionSeg_, astarPaths_ and the guide pairs are then
+         * installed where the host steps put them.  When on, deviceAstar / deviceGuides are not consulted.  A planner
+         * either call defers, one whose merges leave more paths than segments (the device returns the bounded lists
+         * only), and every planner of a group without device or snapshot run host steps 1-3 on the workers with the
+         * guide step's bit-exact twin (as deviceGuides = 1 does for what the device defers): a plan does not depend on
+         * which side ran it.  A planner whose path search FAILS on the device takes the "Fail because of A* failure"
+         * path after replaying host steps 1-2 on the workers: vigo_path_search returns nothing for it, and the host
+         * steps leave the scanned segments and the paths found before the failure in getCollisionSeg() /
+         * getAstarPaths(), so these read the same under every setting.  Searches run under deviceAstarBudget.  The
+         * re-guide step inside the rebound loop is not part of the chain: deviceReguide puts it on the device. */
+        bool devicePrologue = false;
+        /* The re-guide step of the device-resident rebound loop (the `if (hasCollision)` block of BT.cpp:656-679) for
+         * the planners vigo_rebound_rounds hands back with a static collision and failCount < 4.  0: reboundStep on the
+         * workers, as it always was.  1: ONE vigo_rebound_reguide call per device group on the group's staged batch;
+         * collisionSeg_, the appended guide pairs, astarPaths_, the weights, failCount and needOptimize are installed
+         * from its outputs (through the host: the batch is packed again for the next vigo_rebound_rounds call).  A
+         * planner the call defers, and every planner of a group without device or snapshot, runs the same step on the
+         * workers with the guide step's bit-exact twin, so a plan does not depend on which side ran the step.  2: every
+         * such planner runs that twin on the workers (the emulation of 1).  Settings 1 and 2 differ from 0 by the last
+         * places of atan2; any other value counts as 0.  The forced A* of failCount >= 4 (BT.cpp:640-654), a planner
+         * with a dynamic collision only, and the 30 ms budget's exit stay with reboundStep on the host under every
+         * setting.  Searches run under deviceAstarBudget.  Only consulted when deviceResidentRebound. */
+        int deviceReguide = 0;
+        /* The rebound loop of BT.cpp:611-685 runs on the device between two A* calls (vigo_rebound_rounds), or, when
+         * false, round by round from the host (the round-1 path, kept for comparison: identical control points) */
+        bool deviceResidentRebound = true;
+        /* Planners of DIFFERENT control-point counts in one device batch of the solves and of the device-resident
+         * rebound rounds: vigo_optimize_mixed / vigo_rebound_rounds_mixed.  Off: one device batch per distinct count.
+         * On: planners that share everything but the count share a batch when their counts lie in one shape class of the
+         * kernels — all 7 .. 32, or all 33 .. 64; counts above 64 keep a batch per count.  A group whose counts are all
+         * equal calls the uniform entry, so a workload of one count runs the same kernels under either setting
+         * (include/vigo.h, "mixed control-point counts").  Every other stage keeps its grouping by exact count: the
+         * opt-in device stages (A*, prologue chain, re-guide), the gates, costGrad and the host-driven loop's gates. */
+        bool mixedBatches = false;
+        /* Steps 5-6 of makePlan() (the spline object, linearFeasibilityReparam) and, for the calls with trajectories, the
+         * samples of evalTrajToMsg.  Off: per planner on the host workers, as it always was.  On: ONE vigo_traj_finish
+         * call per device group — planners that share a device target, ts_ and controlPointsTs_ (the sample step is
+         * ts_), whatever their control-point counts: rows are padded to the group's largest count; linearFactor_,
+         * bspline_ and the path are installed from its downloads, the yaw from the downloaded velocity with libm's atan2
+         * as evalTrajToMsg takes it.  A planner without a device, one of more than VIGO_MAX_CTRL_POINTS control points,
+         * a row the call reports over capacity (the facade sizes at most 2048 samples per trajectory) or with an invalid
+         * count, and every planner of a group whose call failed take the host route. */
+        bool deviceEpilogue = false;
+        /* makePlanBatch of at least this many planners runs as two to four pipelined parts of >= half this size (all but
+         * the first on companion host threads with their own handles and HIP streams); 0 = never.  Same plans. */
+        size_t pipelineThreshold = 2048;
+        /* seedPathBatch.  Off: the searches and updatePath's head run on the host workers.  On: ONE vigo_seed_paths
+         * launch per device group and one download; a trajectory the launch defers or refuses, a poly planner flying its
+         * PWL fallback or without a polynomial, and a planner without a map snapshot take the host steps.  The kernels'
+         * power is the correctly rounded one; libm's is that value or its neighbour (csrc/vigo_exact_pow.hpp; the rate
+         * is counted by tools/pow_rounding_rate.py): the seeds agree to that. */
+        bool deviceSeed = false;
+        /* The fit stage of updatePathBatch and seedPathBatch.  Off: one vigo_bspline_fit launch per point count.  On:
+         * every ready planner of up to 62 points takes ONE vigo_bspline_fit_mixed call per knot span, whatever the
+         * counts (planners with more points keep the per-count launches); the installed control points are the same. */
+        bool mixedFit = false;
+        /* tries of seedPathBatch's inputPathCheck search per planner (instead of the reference's 50 ms): dt has shrunk to
+         * 2.8 % of getInitTs() by the 16th; values below 1 count as 1 */
+        int seedMaxTries = 16;
+        /* tests: the inputs of every re-guide step the workers' twin runs are appended to *reguideStepLog (NULL: off);
+         * the vector belongs to this call alone while it runs */
+        std::vector<ReguideStepRecord>* reguideStepLog = nullptr;
+
+        /* the options as a call takes them: the out-of-range values folded as the fields say */
+        BatchOptions normalized() const {
+            BatchOptions o = *this;
+            if (o.deviceAstarBudget < 0) o.deviceAstarBudget = 0;
+            if (o.deviceGuides != 1 && o.deviceGuides != 2) o.deviceGuides = 0;
+            if (o.deviceReguide != 1 && o.deviceReguide != 2) o.deviceReguide = 0;
+            if (o.seedMaxTries < 1) o.seedMaxTries = 1;
+            return o;
+        }
+    };
+    /* What the stages of one call did.  Per opt-in stage: the work items the device decided / those that took the host
+     * route while the stage was selected (deferred, over a capacity, no device or snapshot; for deviceGuides and
+     * deviceReguide also everything under setting 2). */
+    struct BatchStats {
+        long long astarDecided = 0, astarHost = 0;         /* prologue searches (deviceAstar) */
+        long long guidesDecided = 0, guidesHost = 0;       /* prologue trajectories (deviceGuides) */
+        long long prologueDecided = 0, prologueHost = 0;   /* prologue planners (devicePrologue); a planner that failed on the device counts as decided */
+        long long reguideDecided = 0, reguideHost = 0;     /* re-guide steps (deviceReguide) */
+        long long epilogueDecided = 0, epilogueHost = 0;   /* planners (deviceEpilogue) */
+        long long seedDecided = 0, seedHost = 0;           /* seedPathBatch's planners, under either setting of deviceSeed */
+        long long epilogueGroups = 0;                      /* vigo_traj_finish calls made (one per device group) */
+        long long solveBatches = 0, solvePlanners = 0;     /* device batches the solves and device rounds opened, under either setting of mixedBatches, and the planners in them */
+        double prologueSeconds = 0.0;                      /* wall time of makePlanBatch's prologue, summed over the parts of a pipelined call, which run side by side */
+        double chainSeconds = 0.0;                         /* ... of devicePrologue's chains (upload to installed results) */
+        BatchStats& operator+=(const BatchStats& o) {
+            astarDecided += o.astarDecided; astarHost += o.astarHost;
+            guidesDecided += o.guidesDecided; guidesHost += o.guidesHost;
+            prologueDecided += o.prologueDecided; prologueHost += o.prologueHost;
+            reguideDecided += o.reguideDecided; reguideHost += o.reguideHost;
+            epilogueDecided += o.epilogueDecided; epilogueHost += o.epilogueHost;
+            seedDecided += o.seedDecided; seedHost += o.seedHost;
+            epilogueGroups += o.epilogueGroups;
+            solveBatches += o.solveBatches; solvePlanners += o.solvePlanners;
+            prologueSeconds += o.prologueSeconds; chainSeconds += o.chainSeconds;
+            return *this;
+        }
+    };
+
+    /* Planners are grouped by control-point count, map object and every hot-path parameter (the yaml values, maxVel):
+     * each group is one batch on the device.  Returns per-planner success like makePlan().  *stats, when given, receives
+     * what this call's stages did. */
+    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners, const BatchOptions& options, BatchStats* stats = nullptr);
+    /* not in the reference: the batched makePlan(nav_msgs::Path&, bool) — trajectories[i] receives what planner i's
+     * evalTrajToMsg(yaw) gives after the plan; a planner that fails gets an empty path */
+    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw,
+                                           const BatchOptions& options, BatchStats* stats = nullptr);
+    /* added (workload tools, cabi_host.cpp: vigo_host_finish_timing): the epilogue stage alone on the planners' current
+     * control points, as makePlanBatch runs it for planners that all succeeded; trajectories may be NULL */
+    static void finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw, const BatchOptions& options,
+                            BatchStats* stats = nullptr);
+    /* updatePath() for many planners at once: the least-squares fits run as device launches (mixedFit) */
     static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
-                                             const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
+                                             const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions, const BatchOptions& options,
+                                             BatchStats* stats = nullptr);
     /* not in the reference: the seed-path stage of bspline_node's replan step (src/bspline_node.cpp:317-378) and
      * updatePath for many planners at once — polys[i]'s plan sampled by getTrajectory(dt) from dt = getInitTs(), the
-     * inputPathCheck search (dt *= 0.8 per failed try, at most seedMaxTries() tries instead of the reference's 50 ms),
-     * then updatePath(seed, startEndConditions[i]).  Returns updatePath's verdicts; seeds[i], when given, receives
+     * inputPathCheck search (dt *= 0.8 per failed try, at most seedMaxTries tries), then
+     * updatePath(seed, startEndConditions[i]).  Returns updatePath's verdicts; seeds[i], when given, receives
      * adjustedInputPolyTraj (empty when no try passed), info[i] the search's outcome.  Same results as one planner after
-     * another in the reference's order: every planner's search, then every planner's updatePath.
-     * setDeviceSeed(false), the default: the searches and updatePath's head run on the host workers.  true: ONE
-     * vigo_seed_paths launch per device group and one download; a trajectory the launch defers or refuses, a poly
-     * planner flying its PWL fallback or without a polynomial, and a planner without a map snapshot take the host steps.
-     * The kernels' power is the correctly rounded one; libm's is that value or its neighbour (csrc/vigo_exact_pow.hpp;
-     * the rate is counted by tools/pow_rounding_rate.py): the seeds agree to that.  The fits run as updatePathBatch's, one vigo_bspline_fit launch per point count.
-     * setMixedFit(false), the default: that.  true: the fit stage of updatePathBatch and seedPathBatch takes every ready
-     * planner of up to 62 points with ONE vigo_bspline_fit_mixed call per knot span, whatever the counts (planners with
-     * more points keep the per-count launches); the installed control points are the same, bit for bit. */
+     * another in the reference's order: every planner's search, then every planner's updatePath.  Stages: deviceSeed,
+     * mixedFit. */
     struct SeedInfo {
         bool found = false;      /* a try passed inputPathCheck */
         int tries = 0;
@@ -239,17 +270,60 @@ public:
         double prevOut = 0.0;
     };
     static std::vector<bool> seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
+                                           const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions, const BatchOptions& options,
+                                           BatchStats* stats = nullptr, std::vector<nav_msgs::Path>* seeds = nullptr, std::vector<SeedInfo>* info = nullptr);
+
+    /* ---- the process default ----------------------------------------------------------------------------------------
+     * The overloads without options take a snapshot of ONE process-wide BatchOptions, guarded by a lock, when they are
+     * called; the setters below each write one field of it (see that field) and the getters read it.  A setter changes
+     * the calls that start after it, on any thread, and none that is running.  Every batch call, with or without
+     * options, adds its BatchStats to one process-wide total when it returns: the *Totals functions read that, and a
+     * difference taken around a call is that call's stats as long as no other thread's call returns in between. */
+    static BatchOptions defaultBatchOptions();
+    static BatchStats batchTotals();
+    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners);
+    static std::vector<bool> makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw = true);
+    static void finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw = true);
+    static std::vector<bool> updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
+                                             const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions);
+    static std::vector<bool> seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
                                            const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
                                            std::vector<nav_msgs::Path>* seeds = nullptr, std::vector<SeedInfo>* info = nullptr);
-    static void setDeviceSeed(bool on);
+    static void setDeviceAstar(bool on);                       /* BatchOptions::deviceAstar */
+    static bool deviceAstar();
+    static void setDeviceAstarBudget(int maxExpansions);       /* BatchOptions::deviceAstarBudget */
+    static void setDeviceGuides(int mode);                     /* BatchOptions::deviceGuides */
+    static int deviceGuides();
+    static void setDevicePrologue(bool on);                    /* BatchOptions::devicePrologue */
+    static bool devicePrologue();
+    static void setDeviceReguide(int mode);                    /* BatchOptions::deviceReguide */
+    static int deviceReguide();
+    static void setReguideStepLog(std::vector<ReguideStepRecord>* log);   /* BatchOptions::reguideStepLog: every later call without options appends */
+    static void setDeviceResidentRebound(bool on);             /* BatchOptions::deviceResidentRebound */
+    static bool deviceResidentRebound();
+    static void setMixedBatches(bool on);                      /* BatchOptions::mixedBatches */
+    static bool mixedBatches();
+    static void setDeviceEpilogue(bool on);                    /* BatchOptions::deviceEpilogue */
+    static bool deviceEpilogue();
+    static void setBatchPipelineThreshold(size_t planners);    /* BatchOptions::pipelineThreshold */
+    static void setDeviceSeed(bool on);                        /* BatchOptions::deviceSeed */
     static bool deviceSeed();
-    static void setMixedFit(bool on);     /* process-wide, default off */
+    static void setMixedFit(bool on);                          /* BatchOptions::mixedFit */
     static bool mixedFit();
-    static void setSeedMaxTries(int n);   /* default 16: dt has shrunk to 2.8 % of getInitTs() by then */
+    static void setSeedMaxTries(int n);                        /* BatchOptions::seedMaxTries */
     static int seedMaxTries();
-    /* Process-wide running totals: the planners whose seed and fit points vigo_seed_paths produced / the host steps did */
+    /* Process-wide running totals (BatchStats' fields of the same names; take the difference around a call) */
+    static void deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds);
+    static void deviceGuideTotals(long long* deviceDecided, long long* hostRun);
+    static void devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds);
+    static void deviceReguideTotals(long long* deviceDecided, long long* hostRun);
+    static void deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups);
+    static void mixedBatchTotals(long long* deviceBatches, long long* planners);
     static void deviceSeedTotals(long long* deviceDecided, long long* hostRun);
-    /* added (tests, cabi_host.cpp: vigo_host_seed_steps): one planner's host steps of that stage with the previous path
+
+    const std::vector<std::vector<Eigen::Vector3d>>& getAstarPaths() const { return astarPaths_; }   /* added (tests) */
+    const std::vector<std::pair<int, int>>& getCollisionSeg() const { return collisionSeg_; }         /* added (tests) */
+    /* added (tests, cabi_host.cpp: vigo_host_seed_steps): one planner's host steps of the seed stage with the previous path
      * lengths passed in and out — the search from dt0, then updatePath's head on its seed */
     struct SeedSteps {
         SeedInfo search;
@@ -344,56 +418,60 @@ private:
                             double& prevOut, bool& wrote);
     /* the inputPathCheck search of one planner: getTrajectory(dt) from dt0, dt *= 0.8 per failed try */
     void seedSearchWith(polyTrajOccMap& poly, double dt0, int maxTries, double prevIn, SeedInfo& s, nav_msgs::Path& seed);
-    /* the launch of seedPathBatch under setDeviceSeed(true): fills the entries of the planners it decided (onDevice) */
+    /* the launch of seedPathBatch under deviceSeed: fills the entries of the planners it decided (onDevice) */
     struct SeedBatch;
     static void seedOnDevice(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys, SeedBatch& sb);
     /* the fit stage of updatePathBatch / seedPathBatch: one vigo_bspline_fit launch per group of equal point count and
-     * device target among the ready planners, control points installed; ok[i] set for the fitted ones */
+     * device target among the ready planners (mixedFit: see there), control points installed; ok[i] set for the fitted ones */
     static void fitGroups(const std::vector<bsplineTraj*>& planners, const std::vector<std::vector<Eigen::Vector3d>>& fitPts,
                           const std::vector<bool>& ready, const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
-                          std::vector<bool>& ok);
+                          std::vector<bool>& ok, bool mixedFit);
     void installControlPoints(const Eigen::MatrixXd& controlPoints, const std::vector<Eigen::Vector3d>& adjustedCurveFitPoints);
     bool termCost(int term, const Eigen::MatrixXd& controlPoints, double& cost, Eigen::MatrixXd& gradient);
     void reboundFinish(Rebound& r, bool ok);
     bool sameBatchKey(const bsplineTraj& o) const;                  // may share a device batch with o
     bool sameBatchKeyAnyCount(const bsplineTraj& o) const;          // ... but for the control-point count
-    bool sameSolveGroup(const bsplineTraj& o) const;                // ... a batch of solveBatch / deviceRounds (setMixedBatches)
+    bool sameSolveGroup(const bsplineTraj& o, bool mixed) const;    // ... a batch of solveBatch / deviceRounds (mixedBatches)
     struct SearchGroup;                                             // ... and what its device A* searches share on top
     void fillParams(vigo_params_s* P) const;
-    static void solveBatch(const std::vector<bsplineTraj*>& ps);   // one vigo_optimize for all
+    static void solveBatch(const std::vector<bsplineTraj*>& ps, const BatchOptions& o, BatchStats& stats);   // one vigo_optimize for all
     /* up to maxRounds rounds of the loop on the device for one group; fills rb[i]->devStatus / gate flags and the
      * planners' control points, weights, failCount, collisionSeg_.  false: device failure (nothing usable) */
-    static bool deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds);
+    static bool deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds, const BatchOptions& o,
+                             BatchStats& stats);
     static void gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& col, std::vector<uint8_t>& dyn);
     /* the steps of makePlanBatch: the split into pipelined parts; for one part the prologue (steps 1-3), the rebound loop
      * on the device or driven from the host, the move of finished planners out of the loop, the epilogue (steps 5-6) */
     struct PlanBatch;
-    /* paths: NULL, or one per planner (the overload with trajectories) */
-    static std::vector<bool> planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw);
-    static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold, nav_msgs::Path* paths, bool yaw);
+    /* paths: NULL, or one per planner (the calls with trajectories); o: normalized; stats: the call's, added to */
+    static std::vector<bool> planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o, BatchStats& stats);
+    static std::vector<bool> makePlanPipelined(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o,
+                                               BatchStats& stats);
+    static std::vector<bool> planPart(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o, BatchStats& stats);
     static void planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb);
     /* step 2 of the prologue for all planners with device searches; found[i]: planner i's pathSearch outcome */
     struct AstarJob;
-    static void pathSearchBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found);
-    static void runAstarJobs(const std::vector<bsplineTraj*>& planners, std::vector<AstarJob>& jobs);
-    /* step 3 of the prologue under setDeviceGuides(1 | 2) for the planners with found[i] */
-    static void assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found);
+    static void pathSearchBatch(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found);
+    static void runAstarJobs(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<AstarJob>& jobs);
+    /* step 3 of the prologue under deviceGuides = 1 | 2 for the planners with found[i] */
+    static void assignGuidesBatch(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, const std::vector<uint8_t>& found);
     void assignGuidesCore();
     void assignGuidesCoreOn(const std::vector<std::pair<int, int>>& collisionSeg, const std::vector<std::vector<Eigen::Vector3d>>& paths);
-    /* setDeviceReguide(1): the eligible planners of `active` through vigo_rebound_reguide; the ones it decided get
-     * devStatus VIGO_RB_ACTIVE.  (2, and what 1 left: reguideStepCore on the workers) */
+    /* deviceReguide = 1: the eligible planners of `active` through vigo_rebound_reguide; the ones it decided get
+     * devStatus VIGO_RB_ACTIVE.  (2, and what 1 left: reguideStepCore on the workers, which logs to pb's reguideStepLog) */
     static void reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& devOk);
     static bool reguideEligible(const Rebound& r);
-    void reguideStepCore(Rebound& r);
-    /* steps 1-3 under setDevicePrologue(true); outcome[i]: 1 prepared, 2 failed (A*), 0 not a planner of the batch */
+    void reguideStepCore(Rebound& r, PlanBatch& pb);
+    /* steps 1-3 under devicePrologue; outcome[i]: 1 prepared, 2 failed (A*), 0 not a planner of the batch */
     static void prologueOnDevice(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<uint8_t>& outcome);
     void packGuideInput(std::vector<int32_t>& seg, std::vector<int32_t>& pathOff, std::vector<double>& path) const;
     static void reboundOnDevice(PlanBatch& pb, bool timing);
     static void reboundFromHost(PlanBatch& pb, bool timing);
     static void retireFinished(PlanBatch& pb);
-    static void planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw);
-    /* setDeviceEpilogue(true): the planners with todo[i] through vigo_traj_finish; todo[i] is cleared for those it finished */
-    static void finishOnDevice(const std::vector<bsplineTraj*>& planners, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw);
+    static void planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw,
+                             const BatchOptions& o, BatchStats& stats);
+    /* deviceEpilogue: the planners with todo[i] through vigo_traj_finish; todo[i] is cleared for those it finished */
+    static void finishOnDevice(const std::vector<bsplineTraj*>& planners, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw, BatchStats& stats);
 };
 }  // namespace trajPlanner
 #endif

@@ -109,11 +109,11 @@ void bsplineTraj::fillParams(vigo_params_s* Pp) const {
 bool bsplineTraj::sameBatchKey(const bsplineTraj& o) const {
     return optData_.controlPoints.cols() == o.optData_.controlPoints.cols() && sameBatchKeyAnyCount(o);
 }
-// the batches of the solves and of the device rounds: under setMixedBatches the count may differ inside a shape class of
-// the kernels (7 .. 32 | 33 .. 64: the contract of the vigo_*_mixed entries)
-bool bsplineTraj::sameSolveGroup(const bsplineTraj& o) const {
+// the batches of the solves and of the device rounds: with `mixed` (BatchOptions::mixedBatches) the count may differ inside
+// a shape class of the kernels (7 .. 32 | 33 .. 64: the contract of the vigo_*_mixed entries)
+bool bsplineTraj::sameSolveGroup(const bsplineTraj& o, bool mixed) const {
     const long na = optData_.controlPoints.cols(), nb = o.optData_.controlPoints.cols();
-    if (na == nb || !mixedBatches()) return na == nb && sameBatchKeyAnyCount(o);
+    if (na == nb || !mixed) return na == nb && sameBatchKeyAnyCount(o);
     if (na < 7 || nb < 7 || na > 64 || nb > 64 || (na <= 32) != (nb <= 32)) return false;
     return sameBatchKeyAnyCount(o);
 }
@@ -566,7 +566,9 @@ bool costGrad(vigo_handle_t h, const HostBatch& hb, double& cost, double* grad) 
 // BT.cpp:687-718
 int bsplineTraj::optimize() {
     std::vector<bsplineTraj*> one{this};
-    solveBatch(one);
+    BatchStats stats;
+    solveBatch(one, BatchOptions(), stats);     // (one planner: no option bears on its solve)
+    reportBatchStats(stats, nullptr);
     return lastStatus_;
 }
 
@@ -728,14 +730,17 @@ bool bsplineTraj::optimizeTrajectory() {
     // makePlanBatch's inner loop without the A* prologue
     Rebound r;
     reboundBegin(r);
-    solveBatch(one);
+    const BatchOptions o;                       // (one planner, the host-driven loop: no option bears on it)
+    BatchStats stats;
+    solveBatch(one, o, stats);
     const double t0 = wallSeconds();
     while (!r.done) {
         std::vector<uint8_t> col, dyn;
         gateBatch(one, col, dyn);
         reboundStep(r, col[0] != 0, dyn[0] != 0, wallSeconds() - t0 > 0.03);
-        if (!r.done && r.needOptimize) solveBatch(one);
+        if (!r.done && r.needOptimize) solveBatch(one, o, stats);
     }
+    reportBatchStats(stats, nullptr);
     return r.ok;
 }
 

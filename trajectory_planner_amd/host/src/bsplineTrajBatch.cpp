@@ -19,46 +19,93 @@ namespace trajPlanner {
 
 namespace {
 using vigo_host::Companion;
-std::atomic<size_t> g_pipelineThreshold{2048};
-thread_local bool t_insidePipeline = false;
-
-// one opt-in device stage of makePlanBatch: its setting, and over the process how many of its work items the device
-// decided and how many ran on the host instead
-struct StageSwitch {
-    std::atomic<int> mode{0};
-    std::atomic<long long> deviceDecided{0}, hostRun{0};
-    void totals(long long* decided, long long* host) const {
-        if (decided) *decided = deviceDecided.load();
-        if (host) *host = hostRun.load();
-    }
-};
-StageSwitch g_astar, g_guides, g_prologue, g_reguide;
-std::atomic<long long> g_prologueNs{0}, g_prologueChainNs{0};
-std::atomic<int> g_deviceAstarBudget{16384};
 constexpr int kAstarPathCap = 128;   // path points a device search returns (a longer path is searched again by the host)
-int onOffOrTwin(int mode) { return mode == 1 || mode == 2 ? mode : 0; }
-}  // namespace
-void bsplineTraj::setBatchPipelineThreshold(size_t planners) { g_pipelineThreshold.store(planners); }
 
-void bsplineTraj::setDeviceAstar(bool on) { g_astar.mode.store(on); }
-bool bsplineTraj::deviceAstar() { return g_astar.mode.load() != 0; }
-void bsplineTraj::setDeviceAstarBudget(int maxExpansions) { g_deviceAstarBudget.store(maxExpansions < 0 ? 0 : maxExpansions); }
+// ---- the process default and the process totals (bsplineTraj.h): all there is of process-wide state of the batch calls.
+// The calls below touch it at their two ends only: the overloads without options copy the default, every call adds its
+// stats when it returns.
+std::mutex g_batchMutex;
+bsplineTraj::BatchOptions g_batchDefaults;   // (g_batchMutex) kept normalized
+bsplineTraj::BatchStats g_batchTotals;       // (g_batchMutex)
+
+template <class Edit>
+void editDefaults(Edit edit) {
+    std::lock_guard<std::mutex> lock(g_batchMutex);
+    edit(g_batchDefaults);
+    g_batchDefaults = g_batchDefaults.normalized();
+}
+template <class T>
+void put(T* out, T v) {
+    if (out) *out = v;
+}
+}  // namespace
+
+bsplineTraj::BatchOptions bsplineTraj::defaultBatchOptions() {
+    std::lock_guard<std::mutex> lock(g_batchMutex);
+    return g_batchDefaults;
+}
+bsplineTraj::BatchStats bsplineTraj::batchTotals() {
+    std::lock_guard<std::mutex> lock(g_batchMutex);
+    return g_batchTotals;
+}
+void reportBatchStats(const bsplineTraj::BatchStats& st, bsplineTraj::BatchStats* out) {
+    put(out, st);
+    std::lock_guard<std::mutex> lock(g_batchMutex);
+    g_batchTotals += st;
+}
+
+void bsplineTraj::setDeviceAstar(bool on) { editDefaults([=](BatchOptions& o) { o.deviceAstar = on; }); }
+void bsplineTraj::setDeviceAstarBudget(int maxExpansions) { editDefaults([=](BatchOptions& o) { o.deviceAstarBudget = maxExpansions; }); }
+void bsplineTraj::setDeviceGuides(int mode) { editDefaults([=](BatchOptions& o) { o.deviceGuides = mode; }); }
+void bsplineTraj::setDevicePrologue(bool on) { editDefaults([=](BatchOptions& o) { o.devicePrologue = on; }); }
+void bsplineTraj::setDeviceReguide(int mode) { editDefaults([=](BatchOptions& o) { o.deviceReguide = mode; }); }
+void bsplineTraj::setReguideStepLog(std::vector<ReguideStepRecord>* log) { editDefaults([=](BatchOptions& o) { o.reguideStepLog = log; }); }
+void bsplineTraj::setDeviceResidentRebound(bool on) { editDefaults([=](BatchOptions& o) { o.deviceResidentRebound = on; }); }
+void bsplineTraj::setMixedBatches(bool on) { editDefaults([=](BatchOptions& o) { o.mixedBatches = on; }); }
+void bsplineTraj::setDeviceEpilogue(bool on) { editDefaults([=](BatchOptions& o) { o.deviceEpilogue = on; }); }
+void bsplineTraj::setBatchPipelineThreshold(size_t planners) { editDefaults([=](BatchOptions& o) { o.pipelineThreshold = planners; }); }
+void bsplineTraj::setDeviceSeed(bool on) { editDefaults([=](BatchOptions& o) { o.deviceSeed = on; }); }
+void bsplineTraj::setMixedFit(bool on) { editDefaults([=](BatchOptions& o) { o.mixedFit = on; }); }
+void bsplineTraj::setSeedMaxTries(int n) { editDefaults([=](BatchOptions& o) { o.seedMaxTries = n; }); }
+bool bsplineTraj::deviceAstar() { return defaultBatchOptions().deviceAstar; }
+int bsplineTraj::deviceGuides() { return defaultBatchOptions().deviceGuides; }
+bool bsplineTraj::devicePrologue() { return defaultBatchOptions().devicePrologue; }
+int bsplineTraj::deviceReguide() { return defaultBatchOptions().deviceReguide; }
+bool bsplineTraj::deviceResidentRebound() { return defaultBatchOptions().deviceResidentRebound; }
+bool bsplineTraj::mixedBatches() { return defaultBatchOptions().mixedBatches; }
+bool bsplineTraj::deviceEpilogue() { return defaultBatchOptions().deviceEpilogue; }
+bool bsplineTraj::deviceSeed() { return defaultBatchOptions().deviceSeed; }
+bool bsplineTraj::mixedFit() { return defaultBatchOptions().mixedFit; }
+int bsplineTraj::seedMaxTries() { return defaultBatchOptions().seedMaxTries; }
+
 void bsplineTraj::deviceAstarTotals(long long* deviceDecided, long long* hostRun, double* prologueSeconds) {
-    g_astar.totals(deviceDecided, hostRun);
-    if (prologueSeconds) *prologueSeconds = g_prologueNs.load() * 1e-9;
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.astarDecided), put(hostRun, t.astarHost), put(prologueSeconds, t.prologueSeconds);
 }
-void bsplineTraj::setDeviceGuides(int mode) { g_guides.mode.store(onOffOrTwin(mode)); }
-int bsplineTraj::deviceGuides() { return g_guides.mode.load(); }
-void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun) { g_guides.totals(deviceDecided, hostRun); }
-void bsplineTraj::setDevicePrologue(bool on) { g_prologue.mode.store(on); }
-bool bsplineTraj::devicePrologue() { return g_prologue.mode.load() != 0; }
+void bsplineTraj::deviceGuideTotals(long long* deviceDecided, long long* hostRun) {
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.guidesDecided), put(hostRun, t.guidesHost);
+}
 void bsplineTraj::devicePrologueTotals(long long* deviceDecided, long long* hostRun, double* chainSeconds) {
-    g_prologue.totals(deviceDecided, hostRun);
-    if (chainSeconds) *chainSeconds = g_prologueChainNs.load() * 1e-9;
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.prologueDecided), put(hostRun, t.prologueHost), put(chainSeconds, t.chainSeconds);
 }
-void bsplineTraj::setDeviceReguide(int mode) { g_reguide.mode.store(onOffOrTwin(mode)); }
-int bsplineTraj::deviceReguide() { return g_reguide.mode.load(); }
-void bsplineTraj::deviceReguideTotals(long long* deviceDecided, long long* hostRun) { g_reguide.totals(deviceDecided, hostRun); }
+void bsplineTraj::deviceReguideTotals(long long* deviceDecided, long long* hostRun) {
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.reguideDecided), put(hostRun, t.reguideHost);
+}
+void bsplineTraj::deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups) {
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.epilogueDecided), put(hostRun, t.epilogueHost), put(deviceGroups, t.epilogueGroups);
+}
+void bsplineTraj::mixedBatchTotals(long long* deviceBatches, long long* planners) {
+    const BatchStats t = batchTotals();
+    put(deviceBatches, t.solveBatches), put(planners, t.solvePlanners);
+}
+void bsplineTraj::deviceSeedTotals(long long* deviceDecided, long long* hostRun) {
+    const BatchStats t = batchTotals();
+    put(deviceDecided, t.seedDecided), put(hostRun, t.seedHost);
+}
 
 // ---- device calls ---------------------------------------------------------------------
 
@@ -84,29 +131,18 @@ bool uploadBatch(vigo_handle_t h, const HostBatch& hb, DeviceBatch& d) {
     return true;
 }
 
-namespace {
-std::atomic<bool> g_mixedBatches{false};
-std::atomic<long long> g_solveBatches{0}, g_solvePlanners{0};
-}  // namespace
-void bsplineTraj::setMixedBatches(bool on) { g_mixedBatches.store(on); }
-bool bsplineTraj::mixedBatches() { return g_mixedBatches.load(); }
-void bsplineTraj::mixedBatchTotals(long long* deviceBatches, long long* planners) {
-    if (deviceBatches) *deviceBatches = g_solveBatches.load();
-    if (planners) *planners = g_solvePlanners.load();
-}
-
-void bsplineTraj::solveBatch(const std::vector<bsplineTraj*>& ps) {
-    // groups of equal N share a launch (vigo_optimize takes one N per call); under setMixedBatches the counts of one shape
+void bsplineTraj::solveBatch(const std::vector<bsplineTraj*>& ps, const BatchOptions& o, BatchStats& stats) {
+    // groups of equal N share a launch (vigo_optimize takes one N per call); under mixedBatches the counts of one shape
     // class do (vigo_optimize_mixed), in rows of the group's largest count
-    auto same = [&](size_t a, size_t b) { return ps[a]->sameSolveGroup(*ps[b]); };
+    auto same = [&](size_t a, size_t b) { return ps[a]->sameSolveGroup(*ps[b], o.mixedBatches); };
     vigo_host::forEachGroup(ps.size(), same, [&](const std::vector<size_t>& grp) {
         bsplineTraj* lead = ps[grp[0]];
         int N = 0;        // the row stride: the group's one count, or its largest
         for (size_t k : grp) N = std::max(N, (int)ps[k]->optData_.controlPoints.cols());
         for (size_t k : grp) ps[k]->lastStatus_ = VIGO_ERR_HIP;
         if (lead->optData_.controlPoints.cols() < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return;
-        g_solveBatches += 1;
-        g_solvePlanners += (long long)grp.size();
+        stats.solveBatches += 1;
+        stats.solvePlanners += (long long)grp.size();
         HostBatch hb(N);
         for (size_t k : grp) {
             const bsplineTraj* p = ps[k];
@@ -178,23 +214,18 @@ void bsplineTraj::gateBatch(const std::vector<bsplineTraj*>& ps, std::vector<uin
     });
 }
 
-namespace {
-std::atomic<bool> g_deviceResidentRebound{true};
-}
-void bsplineTraj::setDeviceResidentRebound(bool on) { g_deviceResidentRebound.store(on); }
-bool bsplineTraj::deviceResidentRebound() { return g_deviceResidentRebound.load(); }
-
 // BT.cpp:611-685 between two A* calls, on the device, for one group of planners (one batch): upload the planners'
 // state, queue the rounds (vigo_rebound_rounds), bring back what the host part of the loop needs.
-bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds) {
+bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::vector<Rebound*>& rb, int maxRounds, const BatchOptions& o,
+                               BatchStats& stats) {
     bsplineTraj* lead = grp[0];
-    int N = 0;            // the row stride: the group's one count, or (setMixedBatches) its largest
+    int N = 0;            // the row stride: the group's one count, or (mixedBatches) its largest
     for (const bsplineTraj* p : grp) N = std::max(N, (int)p->optData_.controlPoints.cols());
     std::vector<int> prevStatus(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) { prevStatus[k] = grp[k]->lastStatus_; grp[k]->lastStatus_ = VIGO_ERR_HIP; }
     if (lead->optData_.controlPoints.cols() < 7 || N > VIGO_MAX_CTRL_POINTS || !lead->syncDevice()) return false;
-    g_solveBatches += 1;
-    g_solvePlanners += (long long)grp.size();
+    stats.solveBatches += 1;
+    stats.solvePlanners += (long long)grp.size();
     HostBatch hb(N);
     std::vector<vigo_rebound_state_t> state(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) {
@@ -254,7 +285,7 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
     for (size_t k : overflow) {
         std::vector<bsplineTraj*> one{grp[k]};
         Rebound& r = *rb[k];
-        if (r.needOptimize) solveBatch(one);
+        if (r.needOptimize) solveBatch(one, o, stats);
         std::vector<uint8_t> col, dyn;
         gateBatch(one, col, dyn);
         r.gateStatic = col[0] != 0;
@@ -266,29 +297,51 @@ bool bsplineTraj::deviceRounds(const std::vector<bsplineTraj*>& grp, const std::
 
 // BT.cpp:333-385 for many planners at once: host prologue per planner, then the rebound loops in
 // lock-step so each optimize() round is one launch over all still-active planners.
-std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners) { return planBatch(planners, nullptr, true); }
-
-std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw) {
-    trajectories.assign(planners.size(), nav_msgs::Path());
-    return planBatch(planners, trajectories.data(), yaw);
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners, const BatchOptions& options, BatchStats* stats) {
+    BatchStats st;
+    std::vector<bool> result = planBatch(planners, nullptr, true, options.normalized(), st);
+    reportBatchStats(st, stats);
+    return result;
 }
 
-std::vector<bool> bsplineTraj::planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw) {
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw,
+                                             const BatchOptions& options, BatchStats* stats) {
+    trajectories.assign(planners.size(), nav_msgs::Path());
+    BatchStats st;
+    std::vector<bool> result = planBatch(planners, trajectories.data(), yaw, options.normalized(), st);
+    reportBatchStats(st, stats);
+    return result;
+}
+
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners) { return makePlanBatch(planners, defaultBatchOptions()); }
+
+std::vector<bool> bsplineTraj::makePlanBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>& trajectories, bool yaw) {
+    return makePlanBatch(planners, trajectories, yaw, defaultBatchOptions());
+}
+
+std::vector<bool> bsplineTraj::planBatch(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o,
+                                         BatchStats& stats) {
     const size_t P = planners.size();
-    const size_t threshold = g_pipelineThreshold.load();
-    if (!t_insidePipeline && threshold > 0 && P >= threshold && P >= 2) return makePlanPipelined(planners, threshold, paths, yaw);
-    PlanBatch pb(P);
+    if (o.pipelineThreshold > 0 && P >= o.pipelineThreshold && P >= 2) return makePlanPipelined(planners, paths, yaw, o, stats);
+    return planPart(planners, paths, yaw, o, stats);
+}
+
+// one unsplit batch: a whole call, or one part of a pipelined one
+std::vector<bool> bsplineTraj::planPart(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o,
+                                        BatchStats& stats) {
+    const size_t P = planners.size();
+    PlanBatch pb(P, o);
     const bool timing = getenv("VIGO_FACADE_TIMING") != nullptr;
     const double tp0 = wallSeconds();
     planPrologue(planners, pb);
     const double tp1 = wallSeconds();
-    g_prologueNs += (long long)((tp1 - tp0) * 1e9);
+    pb.stats.prologueSeconds += tp1 - tp0;
     // step 4: rebound loops.  The 30 ms budget of BT.cpp:633 is per makePlan() call in the
     // reference; a batch keeps it per round so one slow planner cannot starve the others.
-    if (deviceResidentRebound()) reboundOnDevice(pb, timing);
+    if (o.deviceResidentRebound) reboundOnDevice(pb, timing);
     else reboundFromHost(pb, timing);
     const double tp2 = wallSeconds();
-    planEpilogue(planners, pb.result, paths, yaw);
+    planEpilogue(planners, pb.result, paths, yaw, o, pb.stats);
     if (timing) {
         cout << "[BsplineTraj]: prologue CPU time summed over the workers: findCollisionSeg " << pb.nsSeg.load() * 1e-6 << " ms, A* "
              << pb.nsAstar.load() * 1e-6 << " ms, guide assignment " << pb.nsGuide.load() * 1e-6 << " ms; device chains (wall) "
@@ -296,6 +349,7 @@ std::vector<bool> bsplineTraj::planBatch(const std::vector<bsplineTraj*>& planne
         cout << "[BsplineTraj]: makePlanBatch of " << P << ": prologue " << (tp1 - tp0) * 1e3 << " ms, rebound loop " << (tp2 - tp1) * 1e3
              << " ms, epilogue " << (wallSeconds() - tp2) * 1e3 << " ms" << endl;
     }
+    stats += pb.stats;
     return pb.result;
 }
 
@@ -304,37 +358,42 @@ std::vector<bool> bsplineTraj::planBatch(const std::vector<bsplineTraj*>& planne
 // single-wave solves, ~10 ms per 1024 planners) the others' host work (A*, guide assignment) and device rounds
 // proceed — what a caller otherwise gets only by planning from several threads of its own.  Planners are independent
 // (per-trajectory results do not depend on which batch carries them), so the plans are those of the unsplit call.
-std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>& planners, size_t threshold, nav_msgs::Path* paths, bool yaw) {
+// Every part runs under the call's options — with a step log of its own, appended to the call's in part order — and
+// counts into stats of its own, summed when all have ended.
+std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>& planners, nav_msgs::Path* paths, bool yaw, const BatchOptions& o,
+                                                 BatchStats& stats) {
     constexpr size_t kMaxParts = 4;
     static thread_local Companion companions[kMaxParts - 1];
     const size_t P = planners.size();
-    const size_t per = threshold / 2 > 0 ? threshold / 2 : 1;
+    const size_t per = o.pipelineThreshold / 2 > 0 ? o.pipelineThreshold / 2 : 1;
     const size_t parts = std::min(kMaxParts, std::max<size_t>(2, P / per));
     std::vector<std::vector<bsplineTraj*>> piece(parts);
     std::vector<std::vector<bool>> res(parts);
     std::vector<nav_msgs::Path*> out(parts, nullptr);      // a part's paths: its stretch of the call's
+    std::vector<BatchOptions> opt(parts, o);
+    std::vector<BatchStats> partStats(parts);
+    std::vector<std::vector<ReguideStepRecord>> log(parts);
     for (size_t k = 0; k < parts; ++k) {
         const size_t lo = P * k / parts, hi = P * (k + 1) / parts;
         piece[k].assign(planners.begin() + lo, planners.begin() + hi);
         res[k].assign(hi - lo, false);
         if (paths) out[k] = paths + lo;
+        if (o.reguideStepLog) opt[k].reguideStepLog = &log[k];
     }
-    for (size_t k = 1; k < parts; ++k) {
-        companions[k - 1].start([&piece, &res, &out, yaw, k]() {
-            t_insidePipeline = true;
-            res[k] = bsplineTraj::planBatch(piece[k], out[k], yaw);
-        });
-    }
+    for (size_t k = 1; k < parts; ++k)
+        companions[k - 1].start([&piece, &res, &out, &opt, &partStats, yaw, k]() { res[k] = bsplineTraj::planPart(piece[k], out[k], yaw, opt[k], partStats[k]); });
     // the jobs hold piece and res: every part has ended before an exception leaves (the first one in part order)
     std::exception_ptr err;
-    t_insidePipeline = true;
-    try { res[0] = bsplineTraj::planBatch(piece[0], out[0], yaw); } catch (...) { err = std::current_exception(); }
-    t_insidePipeline = false;
+    try { res[0] = bsplineTraj::planPart(piece[0], out[0], yaw, opt[0], partStats[0]); } catch (...) { err = std::current_exception(); }
     for (size_t k = 1; k < parts; ++k)
         try { companions[k - 1].wait(); } catch (...) { if (!err) err = std::current_exception(); }
     if (err) std::rethrow_exception(err);
     std::vector<bool> all;
-    for (size_t k = 0; k < parts; ++k) all.insert(all.end(), res[k].begin(), res[k].end());
+    for (size_t k = 0; k < parts; ++k) {
+        all.insert(all.end(), res[k].begin(), res[k].end());
+        stats += partStats[k];
+        if (o.reguideStepLog) o.reguideStepLog->insert(o.reguideStepLog->end(), log[k].begin(), log[k].end());
+    }
     return all;
 }
 
@@ -343,17 +402,17 @@ std::vector<bool> bsplineTraj::makePlanPipelined(const std::vector<bsplineTraj*>
 void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBatch& pb) {
     const size_t P = planners.size();
     std::vector<uint8_t> prepared(P, 0), hasPaths(P, 0);
-    const int guides = devicePrologue() ? 0 : deviceGuides();
-    if (devicePrologue()) {
+    const int guides = pb.o.devicePrologue ? 0 : pb.o.deviceGuides;
+    if (pb.o.devicePrologue) {
         // the three steps as one device chain per group; what the device does not decide runs the host steps there too
         std::vector<uint8_t> outcome(P, 0);
         prologueOnDevice(planners, pb, outcome);
         for (size_t i = 0; i < P; ++i) prepared[i] = outcome[i] == 1;
     } else {
-        // The host steps, per planner on the workers, all three in one pass.  setDeviceAstar gathers step 2 over the
+        // The host steps, per planner on the workers, all three in one pass.  deviceAstar gathers step 2 over the
         // planners (pathSearchBatch: the searches of all of them on the device): steps 1 and 3 are then a pass each
-        // around it.  setDeviceGuides gathers step 3 (below).
-        const bool gathered = deviceAstar();
+        // around it.  deviceGuides gathers step 3 (below).
+        const bool gathered = pb.o.deviceAstar;
         std::vector<uint8_t> ready(P, 0);
         auto assignGuides = [&](size_t i) {
             const double t2 = wallSeconds();
@@ -370,7 +429,7 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         });
         if (gathered) {
             const double t1 = wallSeconds();
-            pathSearchBatch(planners, ready, hasPaths);                                 // step 2
+            pathSearchBatch(planners, pb, ready, hasPaths);                                 // step 2
             pb.nsAstar += (long long)((wallSeconds() - t1) * 1e9);
             if (guides == 0)
                 parallelFor(P, [&](size_t i) {
@@ -379,9 +438,9 @@ void bsplineTraj::planPrologue(const std::vector<bsplineTraj*>& planners, PlanBa
         }
     }
     if (guides != 0) {
-        // step 3 gathered over the planners (setDeviceGuides): the device, or its twin on the workers
+        // step 3 gathered over the planners (deviceGuides): the device, or its twin on the workers
         const double t2 = wallSeconds();
-        assignGuidesBatch(planners, hasPaths);
+        assignGuidesBatch(planners, pb, hasPaths);
         pb.nsGuide += (long long)((wallSeconds() - t2) * 1e9);
         prepared = hasPaths;
     }
@@ -408,7 +467,7 @@ struct AstarStage {
 // The jobs' searches: one vigo_astar_search per group of planners that share a snapshot, a node pool and a height band;
 // what the device does not decide (deferred, path too long, no device or snapshot) is searched by the planner's own
 // host A* on the workers.
-void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::vector<AstarJob>& jobs) {
+void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<AstarJob>& jobs) {
     if (jobs.empty()) return;
     const size_t P = planners.size();
     std::vector<uint8_t> decided(jobs.size(), 0);
@@ -437,7 +496,7 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
         if (!st.start.upload(start) || !st.end.upload(end) || !st.status.alloc(status.size()) || !st.len.alloc(len.size()) || !st.path.alloc(path.size()))
             return;
         if (!deviceCallOk(vigo_astar_search(h, Q, st.start.get(), st.end.get(), g.res, g.pool, lead->minHeight_, lead->maxHeight_,
-                                            g_deviceAstarBudget.load(), kAstarPathCap, st.status.get(), st.len.get(), st.path.get(), nullptr),
+                                            pb.o.deviceAstarBudget, kAstarPathCap, st.status.get(), st.len.get(), st.path.get(), nullptr),
                           "vigo_astar_search", h))
             return;
         if (!vigo_host::threadSync() || !st.status.download(status) || !st.len.download(len) || !st.path.download(path)) return;
@@ -456,8 +515,8 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
     });
     long long nDecided = 0;
     for (uint8_t d : decided) nDecided += d;
-    g_astar.deviceDecided += nDecided;
-    g_astar.hostRun += (long long)jobs.size() - nDecided;
+    pb.stats.astarDecided += nDecided;
+    pb.stats.astarHost += (long long)jobs.size() - nDecided;
     parallelFor(owners.size(), [&](size_t o) {
         bsplineTraj* p = planners[owners[o]];
         for (size_t j : jobsOf[owners[o]]) {
@@ -478,7 +537,8 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, std::v
 // on to skip and those behind a failure that ends a planner's loop — searches the host's loop never makes, long ones by
 // construction (a skipped segment's own search is one that may well fail), and worker time when the device defers
 // them.  It buys one launch instead of a launch per segment index; weigh it when the timings are taken.
-void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& ready, std::vector<uint8_t>& found) {
+void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, const std::vector<uint8_t>& ready,
+                                  std::vector<uint8_t>& found) {
     const size_t P = planners.size();
     std::vector<AstarJob> first, retry;
     std::vector<size_t> firstOf(P, 0);
@@ -494,7 +554,7 @@ void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, con
             first.push_back(J);
         }
     }
-    runAstarJobs(planners, first);
+    runAstarJobs(planners, pb, first);
     std::vector<std::vector<size_t>> retryOf(P);
     for (size_t i = 0; i < P; ++i) {
         if (!ready[i]) continue;
@@ -512,7 +572,7 @@ void bsplineTraj::pathSearchBatch(const std::vector<bsplineTraj*>& planners, con
             ++k;
         }
     }
-    runAstarJobs(planners, retry);
+    runAstarJobs(planners, pb, retry);
     parallelFor(P, [&](size_t i) {
         if (!ready[i]) return;
         bsplineTraj* p = planners[i];
@@ -580,7 +640,7 @@ struct ReguideStage {
 };
 }  // namespace
 
-// Steps 1-3 for all planners under setDevicePrologue(true).  Per group of planners that share a batch key and a node
+// Steps 1-3 for all planners under devicePrologue.  Per group of planners that share a batch key and a node
 // pool: control points up, vigo_path_search on the scanned segments, vigo_guide_assign on its output (device pointers,
 // nothing repacked), then one round of downloads and the results installed per planner.  What is left (see the header)
 // runs findCollisionSeg -> pathSearch -> assignGuidesCore on the workers.
@@ -590,7 +650,7 @@ struct ReguideStage {
 // group, against 17 path points and 4.4 pairs per PLANNER on the pipeline batches.  A group over pointCap gets
 // VIGO_ERR_INVALID_ARG from vigo_path_search (nothing written, the message is printed) and runs the host steps as a
 // whole; a group over pairCap keeps the device's segments and paths and has the twin assign its guides.  Both are
-// correct and slow, and both show in devicePrologueTotals' hostRun.
+// correct and slow, and both show in the stats' prologueHost.
 void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, std::vector<uint8_t>& outcome) {
     const size_t P = planners.size();
     std::vector<uint8_t> needGuides(P, 0);            // segments and paths are installed, the pairs are not
@@ -613,7 +673,7 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             !st.off.alloc(off.size()) || !st.pv.alloc((size_t)pairCap * 6) || !st.gstatus.alloc(gstatus.size()))
             return;
         if (!deviceCallOk(vigo_path_search(h, B, N, st.ctrl.get(), nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_,
-                                           g_deviceAstarBudget.load(), kAstarPathCap, segCap, pointCap, st.status.get(), st.segOff.get(), st.seg.get(),
+                                           pb.o.deviceAstarBudget, kAstarPathCap, segCap, pointCap, st.status.get(), st.segOff.get(), st.seg.get(),
                                            st.pathOff.get(), st.path.get(), st.counts.get()),
                           "vigo_path_search", h))
             return;
@@ -645,11 +705,11 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
     });
     const long long chainNs = (long long)((wallSeconds() - tc0) * 1e9);
     pb.nsChain += chainNs;
-    g_prologueChainNs += chainNs;
+    pb.stats.chainSeconds += chainNs * 1e-9;
     long long nDecided = 0;
     for (size_t i : owners) nDecided += (outcome[i] != 0 && !needGuides[i]) || failedOnDevice[i];
-    g_prologue.deviceDecided += nDecided;
-    g_prologue.hostRun += (long long)owners.size() - nDecided;
+    pb.stats.prologueDecided += nDecided;
+    pb.stats.prologueHost += (long long)owners.size() - nDecided;
     parallelFor(owners.size(), [&](size_t o) {
         const size_t i = owners[o];
         bsplineTraj* p = planners[i];
@@ -710,10 +770,10 @@ void bsplineTraj::assignGuidesCoreOn(const std::vector<std::pair<int, int>>& col
 // and a control-point count; the pairs come back as CSR per control point in push order and are appended to the planners'
 // lists.  Whatever the device did not produce (deferred, no device, a failed call), and everything under setting 2, is
 // computed by assignGuidesCore on the workers: the same code, the same pairs.
-void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, const std::vector<uint8_t>& found) {
+void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, PlanBatch& pb, const std::vector<uint8_t>& found) {
     const size_t P = planners.size();
     std::vector<uint8_t> done(P, 0);
-    if (deviceGuides() == 1) {
+    if (pb.o.deviceGuides == 1) {
         std::vector<size_t> owners;
         for (size_t i = 0; i < P; ++i)
             if (found[i]) owners.push_back(i);
@@ -780,20 +840,11 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, c
     }
     long long nDone = 0, nFound = 0;
     for (size_t i = 0; i < P; ++i) { nDone += done[i]; nFound += found[i] ? 1 : 0; }
-    g_guides.deviceDecided += nDone;
-    g_guides.hostRun += nFound - nDone;
+    pb.stats.guidesDecided += nDone;
+    pb.stats.guidesHost += nFound - nDone;
     parallelFor(P, [&](size_t i) {
         if (found[i] && !done[i]) planners[i]->assignGuidesCore();
     });
-}
-
-namespace {
-std::mutex g_reguideLogMutex;
-std::vector<bsplineTraj::ReguideStepRecord>* g_reguideLog = nullptr;
-}  // namespace
-void bsplineTraj::setReguideStepLog(std::vector<ReguideStepRecord>* log) {
-    std::lock_guard<std::mutex> lock(g_reguideLogMutex);
-    g_reguideLog = log;
 }
 
 // the planners vigo_rebound_reguide works on (vigo.h): what is left of the NEEDS_HOST ones is the forced A* of
@@ -803,8 +854,8 @@ bool bsplineTraj::reguideEligible(const Rebound& r) { return r.devStatus == VIGO
 // reboundStep for such a planner with the guide step's twin in place of assignGuidePointsSemiCircle: what
 // vigo_rebound_reguide computes (csrc/vigo_reguide_core.hpp restates isReguideRequired, vigo_path_search the host's
 // pathSearch), without its capacities
-void bsplineTraj::reguideStepCore(Rebound& r) {
-    if (g_reguideLog) {
+void bsplineTraj::reguideStepCore(Rebound& r, PlanBatch& pb) {
+    if (pb.o.reguideStepLog) {
         ReguideStepRecord rec;
         rec.N = this->optData_.controlPoints.cols();
         rec.ctrl.assign(this->optData_.controlPoints.data(), this->optData_.controlPoints.data() + 3 * (size_t)rec.N);
@@ -815,8 +866,8 @@ void bsplineTraj::reguideStepCore(Rebound& r) {
         rec.gateDynamic = r.gateDynamic ? 1 : 0;
         const double w[4] = {this->weightDistance_, this->weightSmoothness_, this->weightFeasibility_, this->weightDynamicObstacle_};
         std::copy(w, w + 4, rec.weights);
-        std::lock_guard<std::mutex> lock(g_reguideLogMutex);
-        if (g_reguideLog) g_reguideLog->push_back(std::move(rec));
+        std::lock_guard<std::mutex> lock(pb.logMutex);
+        pb.o.reguideStepLog->push_back(std::move(rec));
     }
     std::vector<std::pair<int, int>> reguideCollisionSeg;
     std::vector<std::vector<Eigen::Vector3d>> paths;
@@ -831,7 +882,7 @@ void bsplineTraj::reguideStepCore(Rebound& r) {
     r.needOptimize = true;
 }
 
-// setDeviceReguide(1): per group of planners that share a batch key and a node pool, the eligible ones as one staged
+// deviceReguide = 1: per group of planners that share a batch key and a node pool, the eligible ones as one staged
 // batch (control points, guide CSR, weights, state) through vigo_rebound_reguide, one round of downloads, the results
 // installed per planner.  pairCap: the old pairs plus four new ones per control point on average over the group, and
 // pointCap two full-length paths per planner, are budgets as in prologueOnDevice: a group over either gets
@@ -873,7 +924,7 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             !dv.status.alloc(status.size()))
             return;
         if (!deviceCallOk(vigo_rebound_reguide(h, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
-                                               lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_, g_deviceAstarBudget.load(),
+                                               lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_, pb.o.deviceAstarBudget,
                                                kAstarPathCap, dv.state.get(), pairCap, dv.off.get(), dv.pv.get(), nullptr, segCap, pointCap,
                                                dv.pathSegOff.get(), dv.pathOff.get(), dv.path.get(), dv.status.get()),
                           "vigo_rebound_reguide", h))
@@ -906,22 +957,22 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             ++nDecided;
         }
     });
-    g_reguide.deviceDecided += nDecided;
+    pb.stats.reguideDecided += nDecided;
 }
 
 // The loop runs on the device between two A* calls (vigo_rebound_rounds): gates, success exit, isReguideRequired,
 // weight doubling and re-solve are queued for up to kRounds rounds without a host round trip; the host only sees
 // the planners that are done, need A* (re-guide, or failCount >= 4) or ran out of queued rounds.  Under
-// setDeviceReguide the re-guide step is vigo_rebound_reguide's (or its twin's on the workers).
+// deviceReguide the re-guide step is vigo_rebound_reguide's (or its twin's on the workers).
 void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
     const int kRounds = 4;   // failCount reaches 4 after at most four device rounds: then every round needs A*
     std::vector<bsplineTraj*>& active = pb.active;
-    auto same = [&](size_t a, size_t b) { return active[a]->sameSolveGroup(*active[b]); };
+    auto same = [&](size_t a, size_t b) { return active[a]->sameSolveGroup(*active[b], pb.o.mixedBatches); };
     const double t0 = wallSeconds();
     const double budget = 0.03 * std::max<size_t>(1, active.size());
     while (!active.empty()) {
         const double tr0 = wallSeconds();
-        // one device batch per group of planners the lead's handle state fits (setMixedBatches: whatever their counts,
+        // one device batch per group of planners the lead's handle state fits (mixedBatches: whatever their counts,
         // within a shape class)
         std::vector<uint8_t> devOk(active.size(), 0);
         vigo_host::forEachGroup(active.size(), same, [&](const std::vector<size_t>& members) {
@@ -931,7 +982,7 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
                 grp.push_back(active[m]);
                 grb.push_back(&pb.rb[pb.activeIdx[m]]);
             }
-            const bool ok = deviceRounds(grp, grb, kRounds);
+            const bool ok = deviceRounds(grp, grb, kRounds, pb.o, pb.stats);
             for (size_t m : members) devOk[m] = ok ? 1 : 0;
         });
         const double tr1 = wallSeconds();
@@ -950,8 +1001,8 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
                 r.gateDynamic = dyn[a] != 0;
             }
         }
-        // the re-guide step of the planners the device takes (setDeviceReguide); out of time, every planner leaves below
-        const int reguide = timedOut ? 0 : deviceReguide();
+        // the re-guide step of the planners the device takes (deviceReguide); out of time, every planner leaves below
+        const int reguide = timedOut ? 0 : pb.o.deviceReguide;
         if (reguide == 1) reguideOnDevice(pb, devOk);
         size_t nHost = 0;
         long long nTwin = 0;
@@ -959,13 +1010,13 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
             nHost += pb.rb[pb.activeIdx[a]].devStatus == VIGO_RB_NEEDS_HOST ? 1 : 0;
             nTwin += reguide != 0 && devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) ? 1 : 0;
         }
-        g_reguide.hostRun += nTwin;
+        pb.stats.reguideHost += nTwin;
         parallelFor(active.size(), [&](size_t a) {
             Rebound& r = pb.rb[pb.activeIdx[a]];
             bsplineTraj* p = active[a];
             if (!devOk[a]) { p->reboundFinish(r, false); return; }             // no device: nothing to plan with
             if (r.devStatus == VIGO_RB_DONE) p->reboundFinish(r, true);          // BT.cpp:628-631
-            else if (reguide != 0 && reguideEligible(r)) p->reguideStepCore(r);  // what the device left, or setting 2: its twin
+            else if (reguide != 0 && reguideEligible(r)) p->reguideStepCore(r, pb);  // what the device left, or setting 2: its twin
             else if (r.devStatus == VIGO_RB_NEEDS_HOST) p->reboundStep(r, r.gateStatic, r.gateDynamic, timedOut);   // A* and the rest of the pass
             // (still active: its next step is the gate, or the optimize() the device left for the next call)
         });
@@ -982,7 +1033,7 @@ void bsplineTraj::reboundOnDevice(PlanBatch& pb, bool timing) {
 void bsplineTraj::reboundFromHost(PlanBatch& pb, bool timing) {
     std::vector<bsplineTraj*>& active = pb.active;
     double tr0 = wallSeconds();
-    solveBatch(active);
+    solveBatch(active, pb.o, pb.stats);
     if (timing) cout << "[BsplineTraj]:   first solve of " << active.size() << ": " << (wallSeconds() - tr0) * 1e3 << " ms" << endl;
     const double t0 = wallSeconds();
     const double budget = 0.03 * std::max<size_t>(1, active.size());
@@ -1001,7 +1052,7 @@ void bsplineTraj::reboundFromHost(PlanBatch& pb, bool timing) {
         for (size_t a = 0; a < active.size(); ++a)
             if (pb.rb[pb.activeIdx[a]].needOptimize) solve.push_back(active[a]);
         const double tr2 = wallSeconds();
-        solveBatch(solve);
+        solveBatch(solve, pb.o, pb.stats);
         if (timing)
             cout << "[BsplineTraj]:   round of " << n << ": gates " << (tr1 - tr0) * 1e3 << " ms, rebound step " << (tr2 - tr1) * 1e3
                  << " ms, solve of " << solve.size() << " " << (wallSeconds() - tr2) * 1e3 << " ms" << endl;
@@ -1027,25 +1078,17 @@ void bsplineTraj::retireFinished(PlanBatch& pb) {
 }
 
 namespace {
-StageSwitch g_epilogue;
-std::atomic<long long> g_epilogueGroups{0};
 constexpr int kFinishSampleCap = 2048;   // samples per trajectory the stage's buffers are sized for (a 7 m path at ts 0.1: ~110)
 struct FinishStage {
     Staged<double> ctrl, limits, factor, pos, vel;
     Staged<int32_t> npts, n, status;
 };
 }  // namespace
-void bsplineTraj::setDeviceEpilogue(bool on) { g_epilogue.mode.store(on); }
-bool bsplineTraj::deviceEpilogue() { return g_epilogue.mode.load() != 0; }
-void bsplineTraj::deviceEpilogueTotals(long long* deviceDecided, long long* hostRun, long long* deviceGroups) {
-    g_epilogue.totals(deviceDecided, hostRun);
-    if (deviceGroups) *deviceGroups = g_epilogueGroups.load();
-}
 
-// setDeviceEpilogue(true): per group of planners that share a device target, ts_ and controlPointsTs_ (the sample step
+// deviceEpilogue: per group of planners that share a device target, ts_ and controlPointsTs_ (the sample step
 // of evalTrajToMsg(yaw) is ts_) — whatever their counts — the rows padded to the group's largest count, one
 // vigo_traj_finish, one download; linearFactor_, bspline_ and the path installed.  What the call does not decide stays in todo.
-void bsplineTraj::finishOnDevice(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw) {
+void bsplineTraj::finishOnDevice(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw, BatchStats& stats) {
     std::vector<size_t> owners;
     for (size_t i = 0; i < ps.size(); ++i)
         if (todo[i]) owners.push_back(i);
@@ -1087,7 +1130,7 @@ void bsplineTraj::finishOnDevice(const std::vector<bsplineTraj*>& ps, std::vecto
             !st.n.alloc(B) || !st.status.alloc(B) || !st.pos.alloc(rows) || (wantVel && !st.vel.alloc(rows)))
             return;
         vigo_handle_t h = lead->link_.handle();
-        g_epilogueGroups += 1;
+        stats.epilogueGroups += 1;
         if (!deviceCallOk(vigo_traj_finish(h, (int)B, Ns, hb.uniform() ? nullptr : st.npts.get(), st.ctrl.get(), st.limits.get(), dt, S_cap,
                                            st.factor.get(), nullptr, st.n.get(), st.pos.get(), wantVel ? st.vel.get() : nullptr, st.status.get()),
                           "vigo_traj_finish", h))
@@ -1119,15 +1162,16 @@ void bsplineTraj::finishOnDevice(const std::vector<bsplineTraj*>& ps, std::vecto
 }
 
 // steps 5-6 for the planners that succeeded, and with `paths` their evalTrajToMsg(yaw)
-void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw) {
+void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const std::vector<bool>& result, nav_msgs::Path* paths, bool yaw,
+                               const BatchOptions& o, BatchStats& stats) {
     std::vector<uint8_t> todo(result.begin(), result.end());   // the planners the host route below still owes
-    if (deviceEpilogue()) {
+    if (o.deviceEpilogue) {
         long long want = 0, left = 0;
         for (uint8_t t : todo) want += t;
-        finishOnDevice(planners, todo, paths, yaw);
+        finishOnDevice(planners, todo, paths, yaw, stats);
         for (uint8_t t : todo) left += t;
-        g_epilogue.deviceDecided += want - left;
-        g_epilogue.hostRun += left;
+        stats.epilogueDecided += want - left;
+        stats.epilogueHost += left;
     }
     parallelFor(planners.size(), [&](size_t i) {
         if (!todo[i]) return;
@@ -1138,9 +1182,16 @@ void bsplineTraj::planEpilogue(const std::vector<bsplineTraj*>& planners, const 
     });
 }
 
-void bsplineTraj::finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw) {
+void bsplineTraj::finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw, const BatchOptions& options,
+                              BatchStats* stats) {
     if (trajectories) trajectories->assign(planners.size(), nav_msgs::Path());
-    planEpilogue(planners, std::vector<bool>(planners.size(), true), trajectories ? trajectories->data() : nullptr, yaw);
+    BatchStats st;
+    planEpilogue(planners, std::vector<bool>(planners.size(), true), trajectories ? trajectories->data() : nullptr, yaw, options.normalized(), st);
+    reportBatchStats(st, stats);
+}
+
+void bsplineTraj::finishBatch(const std::vector<bsplineTraj*>& planners, std::vector<nav_msgs::Path>* trajectories, bool yaw) {
+    finishBatch(planners, trajectories, yaw, defaultBatchOptions());
 }
 
 }  // namespace trajPlanner

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cmath>
 #include <iostream>
+#include <mutex>
 
 #include "../../../include/vigo.h"
 #include "batchLayout.h"
@@ -37,6 +38,9 @@ inline bool deviceCallOk(int rc, const char* entry, vigo_handle_t h) {
     if (rc != VIGO_OK) std::cout << "[BsplineTraj]: " << entry << " failed: " << vigo_last_error(h) << std::endl;
     return rc == VIGO_OK;
 }
+
+// the end of every batch call: its stats to the caller, when asked for, and onto the process totals (bsplineTraj::batchTotals)
+void reportBatchStats(const bsplineTraj::BatchStats& st, bsplineTraj::BatchStats* out);
 
 // BT.cpp:497-511: the segments after the merges of pathSearch
 void applyMerges(std::vector<std::pair<int, int>>& collisionSeg, const std::vector<int>& mergeIndices);
@@ -143,16 +147,19 @@ struct DeviceBatch {
 // kernels): the thread's next upload overwrites them, so what a call reads back is read back before that.
 bool uploadBatch(vigo_handle_t h, const HostBatch& hb, DeviceBatch& d);
 
-// one unsplit makePlanBatch call: per planner (index into the call's planners) its loop state and result; the planners
-// still in the loop, in call order, with their indices
+// one unsplit makePlanBatch call: its options, what its stages did so far (written by the calling thread only), per planner
+// (index into the call's planners) its loop state and result; the planners still in the loop, in call order, with their indices
 struct bsplineTraj::PlanBatch {
+    const BatchOptions o;
+    BatchStats stats;
+    std::mutex logMutex;                                       // o.reguideStepLog: the workers append
     std::vector<Rebound> rb;
     std::vector<bool> result;
     std::vector<bsplineTraj*> active;
     std::vector<size_t> activeIdx;
     std::atomic<long long> nsSeg{0}, nsAstar{0}, nsGuide{0};   // prologue CPU time summed over the worker threads
-    std::atomic<long long> nsChain{0};                         // setDevicePrologue: wall time of the device chains (all three steps)
-    explicit PlanBatch(size_t P) : rb(P), result(P, false) {}
+    std::atomic<long long> nsChain{0};                         // devicePrologue: wall time of the device chains (all three steps)
+    PlanBatch(size_t P, const BatchOptions& options) : o(options), rb(P), result(P, false) {}
     // step 1 of planner p and, with `search`, step 2 on the calling worker, timed; false: its A* failed
     bool hostSteps(bsplineTraj* p, bool search) {
         const double t0 = wallSeconds();

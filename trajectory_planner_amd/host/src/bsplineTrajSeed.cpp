@@ -19,7 +19,14 @@ namespace trajPlanner {
 // per group of equal waypoint count (bspline::parameterizeToBspline, bspline.cpp:74-138, batched).
 std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
                                                const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions) {
+    return updatePathBatch(planners, paths, startEndConditions, defaultBatchOptions());
+}
+
+std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<nav_msgs::Path>& paths,
+                                               const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions, const BatchOptions& options,
+                                               BatchStats* stats) {
     std::vector<bool> ok(planners.size(), false);
+    if (stats) *stats = BatchStats();           // (none of this call's stages counts anything)
     if (paths.size() != planners.size() || startEndConditions.size() != planners.size()) return ok;
     std::vector<std::vector<Eigen::Vector3d>> fitPts(planners.size());
     std::vector<bool> ready(planners.size(), false);
@@ -45,7 +52,7 @@ std::vector<bool> bsplineTraj::updatePathBatch(const std::vector<bsplineTraj*>& 
         ready[i] = okv[i] && fitPts[i].size() > 3;
     }
     g_prevPathLength.store(prev);
-    fitGroups(planners, fitPts, ready, startEndConditions, ok);
+    fitGroups(planners, fitPts, ready, startEndConditions, ok, options.mixedFit);
     return ok;
 }
 
@@ -58,21 +65,16 @@ struct MixedFitStage {
     Staged<double> pts, cond, ctrl;
     Staged<int32_t> nfit, npts;
 };
-std::atomic<bool> g_mixedFit{false};
 constexpr int kMixedFitMaxStride = 64;   // vigo_bspline_fit_mixed's largest Ns: K + 2 control points beyond it keep the per-count route
 }  // namespace
 
-void bsplineTraj::setMixedFit(bool on) { g_mixedFit.store(on); }
-bool bsplineTraj::mixedFit() { return g_mixedFit.load(); }
-
 // The fit stage of updatePathBatch and seedPathBatch, the control points installed (BT.cpp:315-322).  Per count: ONE
-// vigo_bspline_fit launch per group of ready planners with equal point count and knot span.  With setMixedFit(true) the
+// vigo_bspline_fit launch per group of ready planners with equal point count and knot span.  With `mixed` (mixedFit) the
 // ready planners of up to 62 points group by knot span alone and take ONE vigo_bspline_fit_mixed call on a padded block:
 // the same control points, bit for bit (include/vigo.h); planners with more points keep the per-count route.
 void bsplineTraj::fitGroups(const std::vector<bsplineTraj*>& planners, const std::vector<std::vector<Eigen::Vector3d>>& fitPts,
                             const std::vector<bool>& ready, const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
-                            std::vector<bool>& ok) {
-    const bool mixed = g_mixedFit.load();
+                            std::vector<bool>& ok, bool mixed) {
     auto viaMixed = [&](size_t a) { return mixed && ready[a] && fitPts[a].size() + 2 <= (size_t)kMixedFitMaxStride; };
     auto sameSpan = [&](size_t a, size_t b) {
         return planners[a]->controlPointsTs_ == planners[b]->controlPointsTs_ &&
@@ -153,20 +155,8 @@ void bsplineTraj::fitGroups(const std::vector<bsplineTraj*>& planners, const std
 
 // ---- the seed-path stage for many planners (bspline_node.cpp:317-378): seedPathBatch -------------------------------
 namespace {
-std::atomic<bool> g_deviceSeed{false};
-std::atomic<int> g_seedMaxTries{16};
-std::atomic<long long> g_seedDevice{0}, g_seedHost{0};
 constexpr int kSeedPointCap = 128;   // rows of the launch's seed / fit outputs per planner; a longer list is the host's
 }  // namespace
-
-void bsplineTraj::setDeviceSeed(bool on) { g_deviceSeed.store(on); }
-bool bsplineTraj::deviceSeed() { return g_deviceSeed.load(); }
-void bsplineTraj::setSeedMaxTries(int n) { g_seedMaxTries.store(n < 1 ? 1 : n); }
-int bsplineTraj::seedMaxTries() { return g_seedMaxTries.load(); }
-void bsplineTraj::deviceSeedTotals(long long* deviceDecided, long long* hostRun) {
-    if (deviceDecided) *deviceDecided = g_seedDevice.load();
-    if (hostRun) *hostRun = g_seedHost.load();
-}
 
 // bspline_node.cpp:338-352 for one planner, the loop ending on the try count
 void bsplineTraj::seedSearchWith(polyTrajOccMap& poly, double dt0, int maxTries, double prevIn, SeedInfo& s, nav_msgs::Path& seed) {
@@ -199,25 +189,25 @@ void bsplineTraj::seedSteps(polyTrajOccMap& poly, double dt0, int maxTries, doub
     out.fitOk = this->prepareFitPointsWith(out.seed, out.fitPoints, prevFitIn, out.prevFitOut, out.fitWrote);
 }
 
-// what seedPathBatch keeps per planner between its passes
+// one seedPathBatch call: its options, and what it keeps per planner between its passes
 struct bsplineTraj::SeedBatch {
-    int maxTries;
+    const BatchOptions o;
     std::vector<nav_msgs::Path> seed;
     std::vector<SeedInfo> info;
     std::vector<std::vector<Eigen::Vector3d>> fitPts;
     std::vector<uint8_t> eligible, onDevice, okv, wroteFit;
     std::vector<double> prevFitOut;
-    // setMixedFit: the control points vigo_bspline_fit_mixed made of the launch's own fit points ([K + 2][3]; empty: none)
+    // mixedFit: the control points vigo_bspline_fit_mixed made of the launch's own fit points ([K + 2][3]; empty: none)
     const std::vector<std::vector<Eigen::Vector3d>>* conds = nullptr;
     std::vector<std::vector<double>> devCtrl;
-    explicit SeedBatch(size_t n, int tries)
-        : maxTries(tries), seed(n), info(n), fitPts(n), eligible(n, 0), onDevice(n, 0), okv(n, 0), wroteFit(n, 0), prevFitOut(n, 0.0), devCtrl(n) {}
+    SeedBatch(size_t n, const BatchOptions& options)
+        : o(options), seed(n), info(n), fitPts(n), eligible(n, 0), onDevice(n, 0), okv(n, 0), wroteFit(n, 0), prevFitOut(n, 0.0), devCtrl(n) {}
 };
 
 namespace {
 struct SeedStage {
     Staged<double> in, out;   // the two blocks of seedBlock.h, as whole doubles
-    Staged<double> ctrl;      // setMixedFit: [T][kMixedFitMaxStride][3] of vigo_bspline_fit_mixed ...
+    Staged<double> ctrl;      // mixedFit: [T][kMixedFitMaxStride][3] of vigo_bspline_fit_mixed ...
     Staged<int32_t> npts;     // ... and its counts
     Staged<double> cut;       // ... the seed, fit and control-point rows cut to the group's largest counts, packed for ONE download
 };
@@ -232,7 +222,7 @@ bool cutRows(double* dst, const double* src, size_t T, size_t srcRows, size_t ro
 // ONE vigo_seed_paths launch per group of eligible planners that share a device batch and a polynomial degree, as if
 // every predecessor had left a previous path length of 0; one upload, one download.  A trajectory the launch defers or
 // refuses stays with the host steps.
-// With setMixedFit(true) the conditions travel up with the inputs and vigo_bspline_fit_mixed runs on the launch's own
+// With mixedFit the conditions travel up with the inputs and vigo_bspline_fit_mixed runs on the launch's own
 // out_fit / out_fit_n / out_status, nothing downloaded in between; what comes down is the per-planner scalars, then the
 // control points and the seed / fit rows cut to the group's largest counts instead of point_cap rows each.
 void bsplineTraj::seedOnDevice(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys, SeedBatch& sb) {
@@ -252,7 +242,7 @@ void bsplineTraj::seedOnDevice(const std::vector<bsplineTraj*>& planners, const 
         // the inputs as one block, the outputs as another (seedBlock.h): `in` is the host's view, filled here
         vigo_host::SeedIn in, dIn;
         vigo_host::SeedOut out, dOut;
-        const bool chain = g_mixedFit.load() && sb.conds;
+        const bool chain = sb.o.mixedFit && sb.conds;
         double *conds = nullptr, *dConds = nullptr;
         std::vector<double> inBlock((chain ? vigo_host::seedInBlockWithConds(nullptr, T, S, deg, in, conds) : vigo_host::seedInBlock(nullptr, T, S, deg, in)) /
                                     sizeof(double));
@@ -289,7 +279,7 @@ void bsplineTraj::seedOnDevice(const std::vector<bsplineTraj*>& planners, const 
         else vigo_host::seedInBlock(st.in.get(), T, S, deg, dIn);
         vigo_host::seedOutBlock(st.out.get(), T, cap, dOut);
         if (!deviceCallOk(vigo_seed_paths(h, T, S, deg, dIn.segOff, dIn.coeffs, dIn.knots, dIn.duration, dIn.dt0, dIn.controlPointDistance,
-                                          dIn.maxPathLength, dIn.prevSeed, dIn.prevFit, sb.maxTries, cap, dOut.status, dOut.tries, dOut.dt,
+                                          dIn.maxPathLength, dIn.prevSeed, dIn.prevFit, sb.o.seedMaxTries, cap, dOut.status, dOut.tries, dOut.dt,
                                           dOut.finalTime, dOut.seedN, dOut.seed, dOut.fitN, dOut.fit, dOut.prevSeed, dOut.prevFit),
                           "vigo_seed_paths", h))
             return;
@@ -369,12 +359,22 @@ void bsplineTraj::seedOnDevice(const std::vector<bsplineTraj*>& planners, const 
 std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
                                              const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions,
                                              std::vector<nav_msgs::Path>* seeds, std::vector<SeedInfo>* info) {
+    return seedPathBatch(planners, polys, startEndConditions, defaultBatchOptions(), nullptr, seeds, info);
+}
+
+std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
+                                             const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions, const BatchOptions& options,
+                                             BatchStats* stats, std::vector<nav_msgs::Path>* seeds, std::vector<SeedInfo>* info) {
     const size_t n = planners.size();
     std::vector<bool> ok(n, false);
-    if (polys.size() != n || startEndConditions.size() != n) return ok;
-    SeedBatch sb(n, g_seedMaxTries.load());
+    BatchStats st;
+    if (polys.size() != n || startEndConditions.size() != n) {
+        reportBatchStats(st, stats);
+        return ok;
+    }
+    SeedBatch sb(n, options.normalized());
     sb.conds = &startEndConditions;
-    if (g_deviceSeed.load()) {
+    if (sb.o.deviceSeed) {
         for (size_t i = 0; i < n; ++i) {
             const polyTrajSolver* sol = polys[i]->getSolver();
             sb.eligible[i] = startEndConditions[i].size() == 4 && planners[i]->link_.map() && sol && sol->hasSolution() &&
@@ -387,13 +387,13 @@ std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& pl
     // planner's search, then every planner's updatePath) hands the real value down and repeats, on the host and in
     // order, the rare planner for which it does enter: updatePathBatch's scheme, over both phases.
     parallelFor(n, [&](size_t i) {
-        if (!sb.onDevice[i]) planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.maxTries, 0.0, sb.info[i], sb.seed[i]);
+        if (!sb.onDevice[i]) planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.o.seedMaxTries, 0.0, sb.info[i], sb.seed[i]);
     });
     double prev = g_prevPathLength.load();
     std::vector<uint8_t> redone(n, 0);
     for (size_t i = 0; i < n; ++i) {
         if (sb.info[i].wrote && prev > planners[i]->maxPathLength_) {
-            planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.maxTries, prev, sb.info[i], sb.seed[i]);
+            planners[i]->seedSearchWith(*polys[i], planners[i]->getInitTs(), sb.o.seedMaxTries, prev, sb.info[i], sb.seed[i]);
             redone[i] = 1;
         }
         if (sb.info[i].wrote) prev = sb.info[i].prevOut;
@@ -415,9 +415,9 @@ std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& pl
         ready[i] = startEndConditions[i].size() == 4 && sb.okv[i] && sb.fitPts[i].size() > 3;
         if (sb.onDevice[i] && !redone[i]) {
             if (sb.okv[i]) planners[i]->clear();             // prepareFitPointsWith's clear() (BT.cpp:308), for the launch's own
-            g_seedDevice.fetch_add(1);
+            ++st.seedDecided;
         } else {
-            g_seedHost.fetch_add(1);
+            ++st.seedHost;
         }
     }
     g_prevPathLength.store(prev);
@@ -437,9 +437,10 @@ std::vector<bool> bsplineTraj::seedPathBatch(const std::vector<bsplineTraj*>& pl
         std::memcpy(controlPoints.data(), sb.devCtrl[i].data(), sizeof(double) * sb.devCtrl[i].size());
         planners[i]->installControlPoints(controlPoints, sb.fitPts[i]);
     });
-    fitGroups(planners, sb.fitPts, ready, startEndConditions, ok);
+    fitGroups(planners, sb.fitPts, ready, startEndConditions, ok, sb.o.mixedFit);
     if (seeds) *seeds = sb.seed;
     if (info) *info = sb.info;
+    reportBatchStats(st, stats);
     return ok;
 }
 

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <future>
 #include <mutex>
 
 #include "../../../include/vigo.h"
@@ -871,8 +872,7 @@ int vigo_host_seed_batch(int nx, int ny, int nz, const double* origin, double re
     }
     std::vector<nav_msgs::Path> seeds(P);
     std::vector<bool> up(P, false), planned(P, false);
-    long long d0 = 0, h0 = 0, d1 = 0, h1 = 0;
-    bsplineTraj::deviceSeedTotals(&d0, &h0);
+    bsplineTraj::BatchStats st;
     if (serial) {
         for (int i = 0; i < P; ++i) {
             double dt = bp[i]->getInitTs(), finalTime = 0.0;
@@ -888,18 +888,15 @@ int vigo_host_seed_batch(int nx, int ny, int nz, const double* origin, double re
         }
         for (int i = 0; i < P; ++i) up[i] = bp[i]->updatePath(seeds[i], cond);
     } else {
-        const bool was = bsplineTraj::deviceSeed();
-        const int wasTries = bsplineTraj::seedMaxTries();
-        bsplineTraj::setDeviceSeed(device != 0);
-        bsplineTraj::setSeedMaxTries(max_tries);
+        // the process default (a test sets its mixedFit through vigo_host_set_mixed_fit) with this entry's own arguments
+        bsplineTraj::BatchOptions o = bsplineTraj::defaultBatchOptions();
+        o.deviceSeed = device != 0;
+        o.seedMaxTries = max_tries;
         std::vector<bsplineTraj::SeedInfo> info;
-        up = bsplineTraj::seedPathBatch(bp, pp, std::vector<std::vector<Eigen::Vector3d>>(P, cond), &seeds, &info);
-        bsplineTraj::setDeviceSeed(was);
-        bsplineTraj::setSeedMaxTries(wasTries);
+        up = bsplineTraj::seedPathBatch(bp, pp, std::vector<std::vector<Eigen::Vector3d>>(P, cond), o, &st, &seeds, &info);
         for (int i = 0; i < P; ++i) { seed_dt[i] = info[i].dt; seed_tries[i] = info[i].tries; }
     }
-    bsplineTraj::deviceSeedTotals(&d1, &h1);
-    if (totals) { totals[0] = d1 - d0; totals[1] = h1 - h0; }
+    if (totals) { totals[0] = st.seedDecided; totals[1] = st.seedHost; }
     for (int i = 0; i < P; ++i) {
         seed_n[i] = (int32_t)seeds[i].poses.size();
         copyXyz(seeds[i], seed_cap, seed_out + (size_t)i * seed_cap * 3);
@@ -920,8 +917,8 @@ int vigo_host_seed_batch(int nx, int ny, int nz, const double* origin, double re
     return 0;
 }
 
-// bsplineTraj::setMixedFit for the harness entries above and below (process-wide; returns what it was): a test flips it
-// around vigo_host_seed_batch, whose own arguments keep their meaning
+// bsplineTraj::setMixedFit, the process default, for the harness entries above and below (returns what it was): a test
+// flips it around vigo_host_seed_batch, whose own arguments keep their meaning
 int vigo_host_set_mixed_fit(int on) {
     const bool was = trajPlanner::bsplineTraj::mixedFit();
     trajPlanner::bsplineTraj::setMixedFit(on != 0);
@@ -931,8 +928,8 @@ int vigo_host_set_mixed_fit(int on) {
 // Wall time of the seed-path stage up to installed control points for P start/goal pairs (planners built and the min-snap
 // seeds planned once, before the clock): out_ms[reps][3], per repetition in this order
 //   0  what existed before seedPathBatch: the searches as a serial loop on the calling thread, then updatePathBatch
-//   1  seedPathBatch on the host workers (setDeviceSeed(false))
-//   2  seedPathBatch with the vigo_seed_paths launch (setDeviceSeed(true))
+//   1  seedPathBatch on the host workers (deviceSeed off)
+//   2  seedPathBatch with the vigo_seed_paths launch (deviceSeed on)
 // so that the three alternate.  totals[2]: the planners the launch / the host steps decided in the last repetition of 2.
 int vigo_host_seed_timing(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, int P, const double* se,
                           const double* poly_cfg, const double* bsp_cfg, int max_tries, int reps, double* out_ms, long long* totals) {
@@ -963,13 +960,11 @@ int vigo_host_seed_timing(int nx, int ny, int nz, const double* origin, double r
         bp.push_back(bsps.back().get());
     }
     trajPlanner::polyTrajOccMap::makePlanBatch(pp, false);
-    const bool was = bsplineTraj::deviceSeed();
-    const int wasTries = bsplineTraj::seedMaxTries();
-    bsplineTraj::setSeedMaxTries(max_tries);
+    bsplineTraj::BatchOptions o = bsplineTraj::defaultBatchOptions();     // (mixedFit as vigo_host_set_mixed_fit left it)
+    o.seedMaxTries = max_tries;
     for (int r = 0; r < reps; ++r)
         for (int mode = 0; mode < 3; ++mode) {
-            long long d0 = 0, h0 = 0, d1 = 0, h1 = 0;
-            bsplineTraj::deviceSeedTotals(&d0, &h0);
+            bsplineTraj::BatchStats st;
             const auto t0 = std::chrono::steady_clock::now();
             if (mode == 0) {
                 std::vector<nav_msgs::Path> seeds(P);
@@ -983,15 +978,12 @@ int vigo_host_seed_timing(int nx, int ny, int nz, const double* origin, double r
                 }
                 (void)bsplineTraj::updatePathBatch(bp, seeds, conds);
             } else {
-                bsplineTraj::setDeviceSeed(mode == 2);
-                (void)bsplineTraj::seedPathBatch(bp, pp, conds);
+                o.deviceSeed = mode == 2;
+                (void)bsplineTraj::seedPathBatch(bp, pp, conds, o, &st);
             }
             out_ms[3 * (size_t)r + mode] = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            bsplineTraj::deviceSeedTotals(&d1, &h1);
-            if (mode == 2 && totals) { totals[0] = d1 - d0; totals[1] = h1 - h0; }
+            if (mode == 2 && totals) { totals[0] = st.seedDecided; totals[1] = st.seedHost; }
         }
-    bsplineTraj::setDeviceSeed(was);
-    bsplineTraj::setSeedMaxTries(wasTries);
     return 0;
 }
 
@@ -1090,9 +1082,9 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
 
 }  // extern "C"
 
-// ---- one driver behind the four vigo_host_plan_batch_* entry points: what they plan on, fresh planners per run, one
-// timed makePlanBatch, the results of a slot's last run.  What is left in each entry point is its slot schedule, the
-// switches a slot sets, and the totals it reads around the call.
+// ---- one driver behind the vigo_host_plan_batch_* entry points: what they plan on, fresh planners per run, one timed
+// makePlanBatch, the results of a slot's last run.  What is left in each entry point is its slot schedule, the
+// BatchOptions of a slot, and the fields of the call's BatchStats it reports.
 namespace {
 using trajPlanner::bsplineTraj;
 
@@ -1140,10 +1132,19 @@ FreshPlanners freshPlanners(const BatchFixture& fx) {
     return fp;
 }
 
-// makePlanBatch's flags, its wall time in ms
+// makePlanBatch's flags, its wall time in ms: the overload without options (the process default), for the slots that
+// leave the default untouched and read the process totals around the call ...
 std::vector<bool> timedPlan(const std::vector<bsplineTraj*>& ps, double& ms) {
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<bool> planned = bsplineTraj::makePlanBatch(ps);
+    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return planned;
+}
+// ... and a call under its own options, what its stages did in st; traj: the overload with trajectories
+std::vector<bool> timedPlan(const std::vector<bsplineTraj*>& ps, const bsplineTraj::BatchOptions& o, double& ms, bsplineTraj::BatchStats& st,
+                            std::vector<nav_msgs::Path>* traj = nullptr, bool yaw = true) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<bool> planned = traj ? bsplineTraj::makePlanBatch(ps, *traj, yaw, o, &st) : bsplineTraj::makePlanBatch(ps, o, &st);
     ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return planned;
 }
@@ -1192,13 +1193,31 @@ int dumpSlot(const std::vector<bsplineTraj*>& ps, const std::vector<bool>& plann
     }
     return 0;
 }
+
+// ... and the n trajectories of the overload with trajectories: n_poses[n], pos[n][pose_cap][3], quat[n][pose_cap][4]
+// (x, y, z, w; zero padded by the caller).  Returns 0, -2 when pose_cap is too small.
+int dumpPoses(const std::vector<nav_msgs::Path>& traj, size_t n, int slot, int pose_cap, int* n_poses, double* pos, double* quat) {
+    for (size_t t = 0; t < n; ++t) {
+        const size_t o = (size_t)slot * n + t;
+        n_poses[o] = t < traj.size() ? (int)traj[t].poses.size() : 0;
+        if (n_poses[o] > pose_cap) return -2;
+        for (int i = 0; i < n_poses[o]; ++i) {
+            const auto& ps = traj[t].poses[i].pose;
+            double* p = pos + (o * pose_cap + i) * 3;
+            double* q = quat + (o * pose_cap + i) * 4;
+            p[0] = ps.position.x; p[1] = ps.position.y; p[2] = ps.position.z;
+            q[0] = ps.orientation.x; q[1] = ps.orientation.y; q[2] = ps.orientation.z; q[3] = ps.orientation.w;
+        }
+    }
+    return 0;
+}
 }  // namespace
 
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch, `reps` times with the prologue's A* on the
-// host (mode 0) and `reps` times with setDeviceAstar(true) (mode 1), alternating, fresh planners every time.  n_maps > 1:
+// host (mode 0) and `reps` times with deviceAstar on (mode 1), alternating, fresh planners every time.  n_maps > 1:
 // planner t plans on map t % n_maps, a separate map object each (separate device groups): copies of vox, the odd ones
 // of vox2 when that is given (same extents, other contents).  budget: the device
-// searches' max_expansions (setDeviceAstarBudget).  cfg as in vigo_host_bspline_prologue.  Outputs of each mode's LAST run,
+// searches' max_expansions (deviceAstarBudget).  cfg as in vigo_host_bspline_prologue.  Outputs of each mode's LAST run,
 // [2] x ...: ok[n] makePlanBatch's flags, solver[n] the last L-BFGS status, ncp[n], ctrl[n][ncp_cap][3] (zero padded),
 // n_guides[n] + guides[cap][6] (point, direction; concatenated in planner order), n_path_pts[n] + paths[cap][3] (the A*
 // paths' points, concatenated), per run prologue_ms[2][reps] (summed over the parts of a call that makePlanBatch splits)
@@ -1211,22 +1230,18 @@ extern "C" int vigo_host_plan_batch_astar(const unsigned char* vox, const unsign
     if (n < 1 || n_pts < 2 || n_maps < 1 || reps < 1 || !path_xyz) return -1;
     const BatchFixture fx(vox, vox2, n_maps, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
-    bsplineTraj::setDeviceAstarBudget(budget);
+    bsplineTraj::BatchOptions o;
+    o.deviceAstarBudget = budget;
     for (int run = 0; run < 2 * reps && rc == 0; ++run) {
         const int mode = run & 1, rep = run / 2;
         const FreshPlanners fp = freshPlanners(fx);
-        bsplineTraj::setDeviceAstar(mode == 1);
-        long long dev0, host0, dev1, host1;
-        double pro0, pro1;
-        bsplineTraj::deviceAstarTotals(&dev0, &host0, &pro0);
-        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[mode * reps + rep]);
-        bsplineTraj::deviceAstarTotals(&dev1, &host1, &pro1);
-        prologue_ms[mode * reps + rep] = (pro1 - pro0) * 1e3;
-        if (mode == 1) { counts[0] = dev1 - dev0; counts[1] = host1 - host0; }
-        bsplineTraj::setDeviceAstar(false);
+        o.deviceAstar = mode == 1;
+        bsplineTraj::BatchStats st;
+        const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[mode * reps + rep], st);
+        prologue_ms[mode * reps + rep] = st.prologueSeconds * 1e3;
+        if (mode == 1) { counts[0] = st.astarDecided; counts[1] = st.astarHost; }
         if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, mode, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, n_path_pts, paths);
     }
-    bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
 }
 
@@ -1762,8 +1777,8 @@ int vigo_host_reguide_facade(const unsigned char* vox, const int* dims, const do
 extern "C" {
 
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
-// every run: first ONE run before any setter is touched (slot 0: the untouched default), then `reps` rounds of
-// setDeviceGuides(0), (1), (2) in turn (slots 1, 2, 3), each with setDeviceAstar(astar != 0).  Outputs per slot [4] x ...
+// every run: first ONE run through the overload without options (slot 0: the untouched process default), then `reps`
+// rounds of deviceGuides = 0, 1, 2 in turn (slots 1, 2, 3), each with deviceAstar = (astar != 0).  Outputs per slot [4] x ...
 // of the slot's LAST run: ok[n], solver[n], ncp[n], ctrl[n][ncp_cap][3] (zero padded), n_guides[n] + guides[cap][6]
 // (point, direction; concatenated in planner order); per run prologue_ms[4][reps] and total_ms[4][reps] (slot 0: entry 0
 // only); counts[4][2]: the trajectories of the slot's last run whose guides the device produced / the workers' twin
@@ -1778,24 +1793,26 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
     for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
         const int slot = run == 0 ? 0 : 1 + (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
         const FreshPlanners fp = freshPlanners(fx);
-        if (run > 0) {
-            bsplineTraj::setDeviceAstar(astar != 0);
-            bsplineTraj::setDeviceGuides(slot - 1);
+        std::vector<bool> planned;
+        bsplineTraj::BatchStats st;
+        if (run == 0) {
+            long long dev0, host0;
+            double pro0;
+            bsplineTraj::deviceGuideTotals(&dev0, &host0);
+            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
+            planned = timedPlan(fp.ps, total_ms[0]);
+            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &st.prologueSeconds);
+            bsplineTraj::deviceGuideTotals(&st.guidesDecided, &st.guidesHost);
+            st.prologueSeconds -= pro0; st.guidesDecided -= dev0; st.guidesHost -= host0;
+        } else {
+            bsplineTraj::BatchOptions o;
+            o.deviceAstar = astar != 0;
+            o.deviceGuides = slot - 1;
+            planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
         }
-        long long dev0, host0, dev1, host1;
-        double pro0, pro1;
-        bsplineTraj::deviceGuideTotals(&dev0, &host0);
-        bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
-        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
-        bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
-        bsplineTraj::deviceGuideTotals(&dev1, &host1);
-        prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
-        counts[2 * slot] = dev1 - dev0;
-        counts[2 * slot + 1] = host1 - host0;
-        if (run > 0) {
-            bsplineTraj::setDeviceAstar(false);
-            bsplineTraj::setDeviceGuides(0);
-        }
+        prologue_ms[slot * reps + rep] = st.prologueSeconds * 1e3;
+        counts[2 * slot] = st.guidesDecided;
+        counts[2 * slot + 1] = st.guidesHost;
         if (run == 0 || rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, nullptr, nullptr);
     }
     return rc;
@@ -1803,15 +1820,15 @@ int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const
 
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
 // every run, `reps` rounds over the slots of `slots` (bit k: slot k runs) in turn:
-//   slot 0  setDevicePrologue(false), setDeviceAstar(false), setDeviceGuides(1)   the reference point of slot 1
-//   slot 1  setDevicePrologue(true)
-//   slot 2  setDevicePrologue(false), setDeviceAstar(true), setDeviceGuides(1)    the device pieces without the chain
-//   slot 3  every switch off                                                       the host prologue
-// budget: setDeviceAstarBudget.  Outputs per slot [4] x ... of the slot's LAST run: ok[n], solver[n], ncp[n],
+//   slot 0  deviceGuides = 1                       the reference point of slot 1
+//   slot 1  devicePrologue
+//   slot 2  deviceAstar, deviceGuides = 1          the device pieces without the chain
+//   slot 3  default options                        the host prologue
+// budget: deviceAstarBudget.  Outputs per slot [4] x ... of the slot's LAST run: ok[n], solver[n], ncp[n],
 // ctrl[n][ncp_cap][3] (zero padded), n_seg[n] + segs[cap][2] (collisionSeg_, concatenated in planner order),
 // n_path_pts[n] + paths[cap][3] (astarPaths_' points), n_guides[n] + guides[cap][6]; per run prologue_ms[4][reps],
-// chain_ms[4][reps] (devicePrologueTotals' chain time) and total_ms[4][reps]; counts[4][2]: the planners of the slot's
-// last run the device chain decided / that ran the host steps.  Every switch is off on return.  Returns 0, -2 when a
+// chain_ms[4][reps] (the stats' chain time) and total_ms[4][reps]; counts[4][2]: the planners of the slot's
+// last run the device chain decided / that ran the host steps.  Returns 0, -2 when a
 // buffer is too small, -1 on a bad argument.  Needs a GPU.
 int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
                                   const double* path_xyz, const double* cfg, int slots, int budget, int reps, int ncp_cap, long long cap,
@@ -1820,46 +1837,38 @@ int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, con
     if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || (slots & 15) == 0) return -1;
     const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
-    bsplineTraj::setDeviceAstarBudget(budget);
     for (int rep = 0; rep < reps && rc == 0; ++rep)
         for (int slot = 0; slot < 4 && rc == 0; ++slot) {
             if (!((slots >> slot) & 1)) continue;
             const FreshPlanners fp = freshPlanners(fx);
-            bsplineTraj::setDevicePrologue(slot == 1);
-            bsplineTraj::setDeviceAstar(slot == 2);
-            bsplineTraj::setDeviceGuides(slot == 0 || slot == 2 ? 1 : 0);
-            long long dev0, host0, dev1, host1;
-            double pro0, pro1, ch0, ch1;
-            bsplineTraj::devicePrologueTotals(&dev0, &host0, &ch0);
-            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
-            const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
-            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro1);
-            bsplineTraj::devicePrologueTotals(&dev1, &host1, &ch1);
-            prologue_ms[slot * reps + rep] = (pro1 - pro0) * 1e3;
-            chain_ms[slot * reps + rep] = (ch1 - ch0) * 1e3;
-            counts[2 * slot] = dev1 - dev0;
-            counts[2 * slot + 1] = host1 - host0;
-            bsplineTraj::setDevicePrologue(false);
-            bsplineTraj::setDeviceAstar(false);
-            bsplineTraj::setDeviceGuides(0);
+            bsplineTraj::BatchOptions o;
+            o.deviceAstarBudget = budget;
+            o.devicePrologue = slot == 1;
+            o.deviceAstar = slot == 2;
+            o.deviceGuides = slot == 0 || slot == 2 ? 1 : 0;
+            bsplineTraj::BatchStats st;
+            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
+            prologue_ms[slot * reps + rep] = st.prologueSeconds * 1e3;
+            chain_ms[slot * reps + rep] = st.chainSeconds * 1e3;
+            counts[2 * slot] = st.prologueDecided;
+            counts[2 * slot + 1] = st.prologueHost;
             if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
         }
-    bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
 }
 
 // n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
-// every run: first ONE run before setDeviceReguide is touched (slot 3: the untouched default), then `reps` rounds over
-//   slot 0  setDeviceReguide(2)   the reference point of slot 1: every re-guide step by the workers' twin
-//   slot 1  setDeviceReguide(1)   vigo_rebound_reguide
-//   slot 2  setDeviceReguide(0)
-// in turn (slots: bit k set = slot k runs; slot 3 always does).  budget: setDeviceAstarBudget.  Outputs per slot [4] x ...
+// every run: first ONE run through the overload without options (slot 3: the untouched process default), then `reps`
+// rounds over
+//   slot 0  deviceReguide = 2   the reference point of slot 1: every re-guide step by the workers' twin
+//   slot 1  deviceReguide = 1   vigo_rebound_reguide
+//   slot 2  deviceReguide = 0
+// in turn (slots: bit k set = slot k runs; slot 3 always does).  budget: deviceAstarBudget.  Outputs per slot [4] x ...
 // of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl, n_seg + segs, n_path_pts + paths,
-// n_guides + guides; per run total_ms[4][reps] (slot 3: entry 0 only); counts[4][2]: deviceReguideTotals' device-decided
-// and worker-run steps of the slot's last run.  twin[2]: the steps slot 0's last run logged, and how many of them the
+// n_guides + guides; per run total_ms[4][reps] (slot 3: entry 0 only); counts[4][2]: the device-decided
+// and worker-run re-guide steps of the slot's last run.  twin[2]: the steps slot 0's last run logged, and how many of them the
 // kernels' host twin (vigo_host_rebound_reguide_core, mode 1) under the capacities caps[4] = (cap_log2, max_nodes,
-// heap_cap, guide_path_cap) does not answer with VIGO_REGUIDE_DEFERRED — the share the device can decide.  Every switch
-// is off on return.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
+// heap_cap, guide_path_cap) does not answer with VIGO_REGUIDE_DEFERRED — the share the device can decide.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
 int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
                                  const double* path_xyz, const double* cfg, int slots, int budget, int reps, const int* caps, int ncp_cap,
                                  long long cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts,
@@ -1868,24 +1877,30 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
     const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
     int rc = 0;
     twin[0] = twin[1] = 0;
-    bsplineTraj::setDeviceAstarBudget(budget);
     for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
         const int slot = run == 0 ? 3 : (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
         if (run > 0 && !((slots >> slot) & 1)) continue;
         const bool last = run == 0 || rep + 1 == reps;
         const FreshPlanners fp = freshPlanners(fx);
         std::vector<bsplineTraj::ReguideStepRecord> log;
-        if (run > 0) bsplineTraj::setDeviceReguide(2 - slot);
-        if (slot == 0 && last) bsplineTraj::setReguideStepLog(&log);
-        long long dev0, host0, dev1, host1;
-        bsplineTraj::deviceReguideTotals(&dev0, &host0);
-        const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
-        bsplineTraj::deviceReguideTotals(&dev1, &host1);
-        bsplineTraj::setReguideStepLog(nullptr);
-        if (run > 0) bsplineTraj::setDeviceReguide(0);
+        std::vector<bool> planned;
+        bsplineTraj::BatchStats st;
+        if (run == 0) {
+            long long dev0, host0;
+            bsplineTraj::deviceReguideTotals(&dev0, &host0);
+            planned = timedPlan(fp.ps, total_ms[slot * reps]);
+            bsplineTraj::deviceReguideTotals(&st.reguideDecided, &st.reguideHost);
+            st.reguideDecided -= dev0; st.reguideHost -= host0;
+        } else {
+            bsplineTraj::BatchOptions o;
+            o.deviceAstarBudget = budget;
+            o.deviceReguide = 2 - slot;
+            if (slot == 0 && last) o.reguideStepLog = &log;
+            planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
+        }
         if (!last) continue;
-        counts[2 * slot] = dev1 - dev0;
-        counts[2 * slot + 1] = host1 - host0;
+        counts[2 * slot] = st.reguideDecided;
+        counts[2 * slot + 1] = st.reguideHost;
         // the logged steps, one by one (a trajectory's result does not depend on its batch), by the kernels' twin
         twin[0] += (long long)log.size();
         int pool[3];
@@ -1915,19 +1930,16 @@ int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, cons
         for (size_t k = 0; k < log.size(); ++k) twin[1] += deferred[k] ? 0 : 1;
         rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
     }
-    bsplineTraj::setDeviceReguide(0);
-    bsplineTraj::setReguideStepLog(nullptr);
-    bsplineTraj::setDeviceAstarBudget(16384);
     return rc;
 }
 
 // n planners with a pose list each (path t: poses path_off[t] .. path_off[t + 1] - 1 of path_xyz, at least 2) through
 // updatePathBatch + makePlanBatch on one dense byte grid, fresh planners every run, `reps` rounds over
-//   slot 0  setMixedBatches(false)   one device batch per control-point count
-//   slot 1  setMixedBatches(true)    counts of one shape class share the batches of the solves and of the device rounds
+//   slot 0  mixedBatches off   one device batch per control-point count
+//   slot 1  mixedBatches on    counts of one shape class share the batches of the solves and of the device rounds
 // in turn.  Outputs per slot [2] x ... of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl
 // (zero padded), n_seg + segs (collisionSeg_), n_guides + guides; per run total_ms[2][reps]; counts[2][2]:
-// mixedBatchTotals' device batches and planners of the slot's last run.  The switch is off on return.  Returns 0, -2
+// the device batches the solves and rounds opened and the planners in them, of the slot's last run.  Returns 0, -2
 // when a buffer is too small, -1 on a bad argument.  Needs a GPU.
 int vigo_host_plan_batch_mixed(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
                                const double* path_xyz, const double* cfg, int reps, int ncp_cap, long long cap, int* ok, int* solver, int* ncp,
@@ -1940,31 +1952,28 @@ int vigo_host_plan_batch_mixed(const unsigned char* vox, const int* dims, const 
     for (int rep = 0; rep < reps && rc == 0; ++rep)
         for (int slot = 0; slot < 2 && rc == 0; ++slot) {
             const FreshPlanners fp = freshPlanners(fx);
-            bsplineTraj::setMixedBatches(slot == 1);
-            long long b0, p0, b1, p1;
-            bsplineTraj::mixedBatchTotals(&b0, &p0);
-            const std::vector<bool> planned = timedPlan(fp.ps, total_ms[slot * reps + rep]);
-            bsplineTraj::mixedBatchTotals(&b1, &p1);
-            bsplineTraj::setMixedBatches(false);
+            bsplineTraj::BatchOptions o;
+            o.mixedBatches = slot == 1;
+            bsplineTraj::BatchStats st;
+            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
             if (rep + 1 < reps) continue;
-            counts[2 * slot] = b1 - b0;
-            counts[2 * slot + 1] = p1 - p0;
+            counts[2 * slot] = st.solveBatches;
+            counts[2 * slot + 1] = st.solvePlanners;
             rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, nullptr, nullptr);
         }
-    bsplineTraj::setMixedBatches(false);
     return rc;
 }
 
 // n planners with a pose list each (as vigo_host_plan_batch_mixed) through updatePathBatch + makePlanBatch on one dense
 // byte grid, fresh planners every run, `reps` rounds over
-//   slot 0  setDeviceEpilogue(false)   steps 5-6 and evalTrajToMsg per planner on the host
-//   slot 1  setDeviceEpilogue(true)    one vigo_traj_finish per device group
+//   slot 0  deviceEpilogue off   steps 5-6 and evalTrajToMsg per planner on the host
+//   slot 1  deviceEpilogue on    one vigo_traj_finish per device group
 // in turn.  with_paths != 0: the overload makePlanBatch(planners, trajectories, yaw != 0); 0: makePlanBatch(planners), no
 // poses.  Planner no_device (< 0: none) sits on a device ordinal that does not exist; planner small_step (< 0: none) gets
 // bspline_traj/timestep = step, a group of its own.  Outputs per slot [2] x ... of the slot's LAST run: ok[n],
 // factor[n] (linearFactor_), n_poses[n], pos[n][pose_cap][3] and quat[n][pose_cap][4] (x, y, z, w; zero padded by the
-// caller); totals[2][3]: deviceEpilogueTotals' device-decided planners, host-route planners and device groups of that
-// run; per run total_ms[2][reps].  The switch is off on return.  Returns 0, -2 when pose_cap is too small, -1 on a bad
+// caller); totals[2][3]: the epilogue's device-decided planners, host-route planners and device groups of that
+// run; per run total_ms[2][reps].  Returns 0, -2 when pose_cap is too small, -1 on a bad
 // argument.  Needs a GPU.
 int vigo_host_plan_batch_finish(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
                                 const double* path_xyz, const double* cfg, int no_device, int small_step, double step, int with_paths, int yaw,
@@ -1990,40 +1999,26 @@ int vigo_host_plan_batch_finish(const unsigned char* vox, const int* dims, const
                 fp.ps.push_back(fp.owners.back().get());
             }
             bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
-            bsplineTraj::setDeviceEpilogue(slot == 1);
-            long long d0, h0, g0, d1, h1, g1;
-            bsplineTraj::deviceEpilogueTotals(&d0, &h0, &g0);
+            bsplineTraj::BatchOptions o;
+            o.deviceEpilogue = slot == 1;
+            bsplineTraj::BatchStats st;
             std::vector<nav_msgs::Path> traj;
-            const auto t0 = std::chrono::steady_clock::now();
-            const std::vector<bool> planned = with_paths ? bsplineTraj::makePlanBatch(fp.ps, traj, yaw != 0) : bsplineTraj::makePlanBatch(fp.ps);
-            total_ms[slot * reps + rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            bsplineTraj::deviceEpilogueTotals(&d1, &h1, &g1);
-            bsplineTraj::setDeviceEpilogue(false);
+            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st, with_paths ? &traj : nullptr, yaw != 0);
             if (rep + 1 < reps) continue;
-            totals[3 * slot] = d1 - d0; totals[3 * slot + 1] = h1 - h0; totals[3 * slot + 2] = g1 - g0;
-            for (int t = 0; t < n && rc == 0; ++t) {
-                const size_t o = (size_t)slot * n + t;
-                ok[o] = planned[t] ? 1 : 0;
-                factor[o] = fp.ps[t]->getLinearFactor();
-                n_poses[o] = with_paths ? (int)traj[t].poses.size() : 0;
-                if (n_poses[o] > pose_cap) { rc = -2; break; }
-                for (int i = 0; i < n_poses[o]; ++i) {
-                    const auto& ps = traj[t].poses[i].pose;
-                    double* p = pos + (o * pose_cap + i) * 3;
-                    double* q = quat + (o * pose_cap + i) * 4;
-                    p[0] = ps.position.x; p[1] = ps.position.y; p[2] = ps.position.z;
-                    q[0] = ps.orientation.x; q[1] = ps.orientation.y; q[2] = ps.orientation.z; q[3] = ps.orientation.w;
-                }
+            totals[3 * slot] = st.epilogueDecided; totals[3 * slot + 1] = st.epilogueHost; totals[3 * slot + 2] = st.epilogueGroups;
+            for (int t = 0; t < n; ++t) {
+                ok[(size_t)slot * n + t] = planned[t] ? 1 : 0;
+                factor[(size_t)slot * n + t] = fp.ps[t]->getLinearFactor();
             }
+            rc = dumpPoses(traj, (size_t)n, slot, pose_cap, n_poses, pos, quat);     // (without paths: traj is empty)
         }
-    bsplineTraj::setDeviceEpilogue(false);
     return rc;
 }
 
 // The epilogue stage alone (bsplineTraj::finishBatch: steps 5-6 and evalTrajToMsg) for n planners on one dense byte grid
-// with the control points ctrl[n][Ns][3], n_pts[n] of them each: `reps` rounds, setDeviceEpilogue off then on in each,
+// with the control points ctrl[n][Ns][3], n_pts[n] of them each: `reps` rounds, deviceEpilogue off then on in each,
 // wall time in ms[reps][2].  *mismatch: planners whose linearFactor_, pose count, positions or quaternions of the last
-// round differ between the two.  The switch is off on return.  Returns 0, -1 on a bad argument.  Needs a GPU.
+// round differ between the two.  Returns 0, -1 on a bad argument.  Needs a GPU.
 int vigo_host_finish_timing(const unsigned char* vox, const int* dims, const double* origin, double res, const double* cfg, int n, int Ns,
                             const int* n_pts, const double* ctrl, int reps, double* ms, long long* mismatch) {
     if (n < 1 || Ns < 7 || reps < 1 || !n_pts || !ctrl || !cfg || !ms || !mismatch) return -1;
@@ -2047,11 +2042,11 @@ int vigo_host_finish_timing(const unsigned char* vox, const int* dims, const dou
     std::vector<double> factor[2];
     for (int rep = 0; rep < reps; ++rep)
         for (int slot = 0; slot < 2; ++slot) {
-            bsplineTraj::setDeviceEpilogue(slot == 1);
+            bsplineTraj::BatchOptions o;
+            o.deviceEpilogue = slot == 1;
             const auto t0 = std::chrono::steady_clock::now();
-            bsplineTraj::finishBatch(ps, &traj[slot]);
+            bsplineTraj::finishBatch(ps, &traj[slot], true, o);
             ms[2 * rep + slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            bsplineTraj::setDeviceEpilogue(false);
             factor[slot].clear();
             for (bsplineTraj* p : ps) factor[slot].push_back(p->getLinearFactor());
         }
@@ -2069,7 +2064,129 @@ int vigo_host_finish_timing(const unsigned char* vox, const int* dims, const dou
     return 0;
 }
 
-// the facade's opt-in switches as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
+// One makePlanBatch(planners, trajectories, yaw = true) of n planners with a pose list each (as
+// vigo_host_plan_batch_mixed) under the options `mask` names in vigo_host_switches' bit layout, with deviceAstarBudget
+// = budget, by one of two routes:
+//   via_setters == 0  the options are passed to the call; the process default is not touched
+//   via_setters == 1  the options are set as the process default through the setters, the overload without options is
+//                     called, and the setters put the default back
+//   via_setters == 2  (mask must be 0) the overload without options and no setter called: the untouched default
+// Outputs, slot 0: dumpSlot's ok, solver, ncp, ctrl (zero padded), n_seg + segs, n_guides + guides, dumpPoses' n_poses,
+// pos, quat; stats[15]: the count fields of the call's BatchStats in the order of their declaration (the second route has
+// no BatchStats of the call: there, the process totals' difference); seconds[2]: prologueSeconds, chainSeconds likewise;
+// totals[15]: what the process totals' counts moved by around the call; total_ms[1].
+// second_mask >= 0 (via_setters must be 0): TWO calls at the same time on two threads, each with a map object, planners
+// and handles of its own built from the same arguments — the first under mask into slot 0, the second under second_mask
+// into slot 1 of every output ([2] x ... as above; totals then spans both).  Returns 0, -2 when a buffer is too small, -1
+// on a bad argument, -3 when a call threw.  Needs a GPU.
+}  // extern "C"
+
+namespace {
+constexpr int kStatCounts = 15;
+void statCounts(const bsplineTraj::BatchStats& s, long long* out) {
+    const long long v[kStatCounts] = {s.astarDecided,   s.astarHost,    s.guidesDecided,   s.guidesHost,  s.prologueDecided,
+                                      s.prologueHost,   s.reguideDecided, s.reguideHost,   s.epilogueDecided, s.epilogueHost,
+                                      s.seedDecided,    s.seedHost,     s.epilogueGroups,  s.solveBatches, s.solvePlanners};
+    std::copy(v, v + kStatCounts, out);
+}
+bsplineTraj::BatchOptions optionsOfMask(int mask, int budget) {
+    bsplineTraj::BatchOptions o;
+    o.deviceAstar = (mask & 1) != 0;
+    o.deviceGuides = (mask >> 1) & 3;
+    o.devicePrologue = (mask & 8) != 0;
+    o.deviceReguide = (mask >> 4) & 3;
+    o.mixedBatches = (mask & 64) != 0;
+    o.deviceEpilogue = (mask & 128) != 0;
+    o.deviceAstarBudget = budget;
+    return o;
+}
+// the fields optionsOfMask writes, as the process default, through their setters
+void setDefaults(const bsplineTraj::BatchOptions& o) {
+    bsplineTraj::setDeviceAstar(o.deviceAstar);
+    bsplineTraj::setDeviceGuides(o.deviceGuides);
+    bsplineTraj::setDevicePrologue(o.devicePrologue);
+    bsplineTraj::setDeviceReguide(o.deviceReguide);
+    bsplineTraj::setMixedBatches(o.mixedBatches);
+    bsplineTraj::setDeviceEpilogue(o.deviceEpilogue);
+    bsplineTraj::setDeviceAstarBudget(o.deviceAstarBudget);
+}
+}  // namespace
+
+extern "C" {
+
+int vigo_host_plan_batch_options(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                 const double* path_xyz, const double* cfg, int mask, int budget, int via_setters, int second_mask, int ncp_cap,
+                                 long long cap, int pose_cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_guides,
+                                 double* guides, int* n_poses, double* pos, double* quat, long long* stats, double* seconds, long long* totals,
+                                 double* total_ms) {
+    if (n < 1 || !path_off || !path_xyz || !cfg || mask < 0 || (second_mask >= 0 && via_setters) || via_setters < 0 || via_setters > 2 ||
+        (via_setters == 2 && mask != 0))
+        return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    const int calls = second_mask >= 0 ? 2 : 1;
+    const bsplineTraj::BatchOptions o[2] = {optionsOfMask(mask, budget), optionsOfMask(std::max(second_mask, 0), budget)};
+    std::vector<std::unique_ptr<BatchFixture>> fx;
+    for (int c = 0; c < calls; ++c) fx.emplace_back(new BatchFixture(vox, dims, origin, res, cfg, n, path_off, path_xyz));
+    FreshPlanners fp[2];
+    std::vector<bool> planned[2];
+    std::vector<nav_msgs::Path> traj[2];
+    bsplineTraj::BatchStats st[2];
+    bool threw[2] = {false, false};
+    const bsplineTraj::BatchStats before = bsplineTraj::batchTotals();     // (making the planners below counts nothing)
+    if (calls == 1) {
+        fp[0] = freshPlanners(*fx[0]);
+        if (via_setters) {
+            if (via_setters == 1) setDefaults(o[0]);
+            const auto c0 = std::chrono::steady_clock::now();
+            planned[0] = bsplineTraj::makePlanBatch(fp[0].ps, traj[0], true);
+            total_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+            if (via_setters == 1) setDefaults(bsplineTraj::BatchOptions());
+        } else {
+            planned[0] = timedPlan(fp[0].ps, o[0], total_ms[0], st[0], &traj[0]);
+        }
+    } else {
+        // each thread makes its planners (their handles with them), waits for the other to have done so, and plans
+        std::promise<void> ready[2];
+        std::shared_future<void> other[2] = {ready[1].get_future().share(), ready[0].get_future().share()};
+        auto run = [&](int c) {
+            try {
+                fp[c] = freshPlanners(*fx[c]);
+            } catch (...) { threw[c] = true; }
+            ready[c].set_value();
+            other[c].wait();
+            if (threw[0] || threw[1]) return;
+            try {
+                planned[c] = timedPlan(fp[c].ps, o[c], total_ms[c], st[c], &traj[c]);
+            } catch (...) { threw[c] = true; }
+        };
+        std::thread a(run, 0), b(run, 1);
+        a.join();
+        b.join();
+        if (threw[0] || threw[1]) return -3;
+    }
+    const bsplineTraj::BatchStats after = bsplineTraj::batchTotals();
+    long long c0[kStatCounts], c1[kStatCounts];
+    statCounts(before, c0);
+    statCounts(after, c1);
+    for (int k = 0; k < kStatCounts; ++k) totals[k] = c1[k] - c0[k];
+    if (via_setters) {
+        st[0].prologueSeconds = after.prologueSeconds - before.prologueSeconds;
+        st[0].chainSeconds = after.chainSeconds - before.chainSeconds;
+    }
+    int rc = 0;
+    for (int c = 0; c < calls && rc == 0; ++c) {
+        if (via_setters) std::copy(totals, totals + kStatCounts, stats);
+        else statCounts(st[c], stats + c * kStatCounts);
+        seconds[2 * c] = st[c].prologueSeconds;
+        seconds[2 * c + 1] = st[c].chainSeconds;
+        rc = dumpSlot(fp[c].ps, planned[c], c, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, nullptr, nullptr);
+        if (rc == 0) rc = dumpPoses(traj[c], (size_t)n, c, pose_cap, n_poses, pos, quat);
+    }
+    return rc;
+}
+
+// the facade's opt-in switches of the process default (bsplineTraj::defaultBatchOptions) as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
 // deviceReguide, bit 6 mixedBatches, bit 7 deviceEpilogue (0: everything off, the default)
 int vigo_host_switches() {
     using trajPlanner::bsplineTraj;
