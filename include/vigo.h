@@ -168,6 +168,34 @@ int vigo_set_grid_packed(vigo_handle_t h, int nx, int ny, int nz, const double o
 /* Metric bounds used by the corridor checker's out-of-bounds test
  * (octomap getMetricMin/Max, PO.cpp:572-577).  Default: the grid box. */
 int vigo_set_metric_bounds(vigo_handle_t h, const double bmin[3], const double bmax[3]);
+/* Update a box of the snapshot IN PLACE: lo = first voxel of the box in the snapshot's lattice, n = its extent,
+ * voxels = uint8[n[0]][n[1]][n[2]] (z fastest) under the byte contract above.  Stream-ordered on the handle's stream;
+ * the _host form stages through the handle's scratch and synchronises, like vigo_set_grid_host.
+ *   inflate_r == NULL (raw): for every voxel of the box the three plane bits become bits 0, 1, 2 of its byte; no other
+ *     bit of the snapshot changes (the padding of a z-row's last word stays clear).  After any sequence of raw updates
+ *     the snapshot equals, word for word, vigo_set_grid of the byte grid with the boxes written into it.
+ *   inflate_r = {rx, ry, rz}: planes 1 and 2 as above, bit 0 of the input bytes is ignored; bit 0 of every voxel of the
+ *     box grown by r per axis (clipped to the grid) becomes the box dilation of the new occupied plane — the rule of
+ *     vigo_inflate_grid, nothing outside the grid — and is kept elsewhere.  If plane 0 was the r-dilation of plane 2
+ *     before the call it is so afterwards: the result of vigo_inflate_grid + vigo_set_grid on the whole updated grid,
+ *     for work proportional to the box grown by 2r.
+ * Untouched: grid dims, origin and res, the bounds of vigo_set_metric_bounds, the cached sample times — and the
+ * handle's ESDF: a field built by vigo_build_esdf is STALE until it is built again.
+ * Errors (nothing is written): VIGO_ERR_INVALID_ARG — NULL handle, lo, n or voxels, a negative lo, n or radius, lo + n
+ * beyond the grid; VIGO_ERR_NO_GRID — before any vigo_set_grid*; VIGO_ERR_UNSUPPORTED — rz > 31 (vigo_inflate_grid's
+ * limit).  An n[a] == 0 is VIGO_OK with nothing launched. */
+int vigo_update_grid_region(vigo_handle_t h, const int32_t lo[3], const int32_t n[3],
+                            const uint8_t* voxels_dev, const int32_t inflate_r[3]);
+int vigo_update_grid_region_host(vigo_handle_t h, const int32_t lo[3], const int32_t n[3],
+                                 const uint8_t* voxels_host, const int32_t inflate_r[3]);
+/* Copy the handle's current snapshot (vigo_grid_packed_bytes of its dims) into a caller-owned device buffer,
+ * stream-ordered: what a rank broadcasts after region updates. */
+int vigo_get_grid_packed(vigo_handle_t h, uint32_t* packed_dev);
+/* The host twin of vigo_update_grid_region on a byte grid uint8[nx][ny][nz], in place: no GPU, no handle; the same
+ * codes for the same arguments (csrc/vigo_grid_update_core.hpp). */
+int vigo_grid_region_apply_host(int nx, int ny, int nz, uint8_t* voxels_host_inout,
+                                const int32_t lo[3], const int32_t n[3],
+                                const uint8_t* region_voxels_host, const int32_t inflate_r[3]);
 
 /* Point queries, Q points double[Q][3] -> uint8[Q].
  * which: 0 = isInflatedOccupied, 1 = isUnknown  (BT.cpp:412,841). */

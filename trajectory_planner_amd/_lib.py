@@ -69,6 +69,10 @@ PROTOTYPES = {
     "vigo_pack_grid": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "vigo_set_grid_packed": (_i, [_vp, _i, _i, _i, _d3, _d, _vp]),
     "vigo_set_metric_bounds": (_i, [_vp, _d3, _d3]),
+    "vigo_update_grid_region": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vigo_update_grid_region_host": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vigo_get_grid_packed": (_i, [_vp, _vp]),
+    "vigo_grid_region_apply_host": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "vigo_query_points": (_i, [_vp, _i, _i64, _vp, _vp]),
     "vigo_guides_unknown": (_i, [_vp, _i64, _vp, _vp]),
     "vigo_check_lists": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i64]),

@@ -11,6 +11,7 @@
 #include "vigo_exact_pow.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_fit_plan.hpp"
+#include "vigo_grid_update_core.hpp"
 #include "vigo_handle.hpp"
 #include "vigo_seed_core.hpp"
 #include "vigo_solver_plan.hpp"
@@ -543,6 +544,61 @@ int vigo_set_grid_packed(vigo_handle_t h, int nx, int ny, int nz, const double o
     VIGO_HIP(h, hipMemcpyAsync(h->buf[vigo::kBufGrid].ptr, packed_dev, vigo_grid_packed_bytes(nx, ny, nz), hipMemcpyDeviceToDevice, h->stream));
     fill_grid_view(h, nx, ny, nz, origin, res);
     return VIGO_OK;
+}
+
+}  // extern "C"
+namespace {
+int region_code(vigo::RegionCheck c) {
+    return c == vigo::kRegionInvalid ? VIGO_ERR_INVALID_ARG : c == vigo::kRegionUnsupported ? VIGO_ERR_UNSUPPORTED : VIGO_OK;
+}
+// both forms of vigo_update_grid_region: every refusal comes before the first copy or launch.  Grid dims, origin, res, the
+// metric bounds, the ESDF and the cached clocks are not touched.
+int update_grid_region(vigo_handle_t h, const char* who, const int32_t lo[3], const int32_t n[3], const uint8_t* vox, bool on_host,
+                       const int32_t* r) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (!lo || !n || !vox) return fail(h, VIGO_ERR_INVALID_ARG, (std::string(who) + ": NULL argument").c_str());
+    for (int a = 0; a < 3; ++a)
+        if (lo[a] < 0 || n[a] < 0 || (r && r[a] < 0)) return fail(h, VIGO_ERR_INVALID_ARG, (std::string(who) + ": negative lo, n or radius").c_str());
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (std::string(who) + " before vigo_set_grid").c_str());
+    const GridView& g = h->grid;
+    const vigo::RegionCheck rc = vigo::region_check(g.nx, g.ny, g.nz, lo, n, r);
+    if (rc == vigo::kRegionInvalid) return fail(h, VIGO_ERR_INVALID_ARG, (std::string(who) + ": lo + n beyond the grid").c_str());
+    if (rc == vigo::kRegionUnsupported) return fail(h, VIGO_ERR_UNSUPPORTED, (std::string(who) + ": rz > 31 voxels").c_str());
+    if (rc == vigo::kRegionEmpty) return VIGO_OK;
+    const vigo::RegionPlan p = vigo::region_plan(g.nx, g.ny, g.nz, lo, n, r);
+    const size_t bytes = (size_t)n[0] * n[1] * n[2];
+    uint8_t* staged;
+    uint32_t *planeA, *planeB;
+    VIGO_TRY(carve(h, vigo::kBufScratch, kSlack,
+                   [&](void* b) { return vigo::ws_grid_update(b, on_host ? bytes : 0, vigo::region_window_words(p), staged, planeA, planeB); }));
+    if (on_host) VIGO_HIP(h, hipMemcpyAsync(staged, vox, bytes, hipMemcpyHostToDevice, h->stream));
+    VIGO_HIP(h, (hipError_t)vigo::launch_grid_region(h->stream, p, on_host ? staged : vox, h->buf[vigo::kBufGrid].as<uint32_t>(), g.plane_words,
+                                                     planeA, planeB));
+    if (on_host) VIGO_HIP(h, hipStreamSynchronize(h->stream));
+    return VIGO_OK;
+}
+}  // namespace
+extern "C" {
+
+int vigo_update_grid_region(vigo_handle_t h, const int32_t lo[3], const int32_t n[3], const uint8_t* voxels_dev, const int32_t inflate_r[3]) {
+    return update_grid_region(h, "vigo_update_grid_region", lo, n, voxels_dev, false, inflate_r);
+}
+
+int vigo_update_grid_region_host(vigo_handle_t h, const int32_t lo[3], const int32_t n[3], const uint8_t* voxels_host, const int32_t inflate_r[3]) {
+    return update_grid_region(h, "vigo_update_grid_region_host", lo, n, voxels_host, true, inflate_r);
+}
+
+int vigo_get_grid_packed(vigo_handle_t h, uint32_t* packed_dev) {
+    if (!h || !packed_dev) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_get_grid_packed: bad argument");
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_get_grid_packed before vigo_set_grid");
+    VIGO_HIP(h, hipMemcpyAsync(packed_dev, h->buf[vigo::kBufGrid].ptr, vigo_grid_packed_bytes(h->grid.nx, h->grid.ny, h->grid.nz), hipMemcpyDeviceToDevice, h->stream));
+    return VIGO_OK;
+}
+
+int vigo_grid_region_apply_host(int nx, int ny, int nz, uint8_t* voxels_host_inout, const int32_t lo[3], const int32_t n[3],
+                                const uint8_t* region_voxels_host, const int32_t inflate_r[3]) {
+    if (nx <= 0 || ny <= 0 || nz <= 0 || !voxels_host_inout || !lo || !n || !region_voxels_host) return VIGO_ERR_INVALID_ARG;
+    return region_code(vigo::grid_region_apply(nx, ny, nz, voxels_host_inout, lo, n, region_voxels_host, inflate_r));
 }
 
 int vigo_set_metric_bounds(vigo_handle_t h, const double bmin[3], const double bmax[3]) {

@@ -117,6 +117,11 @@ int launch_optimize_mixed(hipStream_t s, const MixedSolveArgs& a, const DevConst
 
 int launch_pack_grid(hipStream_t s, int nx, int ny, int nz, const uint8_t* vox, uint32_t* packed);
 int launch_inflate(hipStream_t s, int nx, int ny, int nz, uint8_t* vox, uint32_t* planeA, uint32_t* planeB, int rx, int ry, int rz);
+// vigo_grid_update.hip: the box' bytes into the planes in place; in inflate mode plane 0 again on the grown box, through
+// the two compact window planes of region_window_words(p) words each
+struct RegionPlan;
+int launch_grid_region(hipStream_t s, const RegionPlan& p, const uint8_t* vox, uint32_t* planes, size_t plane_words,
+                       uint32_t* planeA, uint32_t* planeB);
 int launch_query_points(hipStream_t s, const GridView& g, int which, int64_t Q, const double* pts,
                         int pt_stride, uint8_t* out);
 int launch_bspline_eval(hipStream_t s, int B, int N, const double* ctrl, double ts_ctrl, int deriv,

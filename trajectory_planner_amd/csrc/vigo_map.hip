@@ -9,6 +9,7 @@
 // ~120-240 lookups scattered over a 7 m path, fewer words than staging its bounding volume in
 // LDS would read.  The LDS-tiled path is the corridor checker (vigo_corridor_core.hpp), where one
 // segment makes ~10^5 lookups inside a small volume.
+#include "vigo_dilate_bits.hpp"
 #include "vigo_exact_time.hpp"
 #include "vigo_grid.hpp"
 #include "vigo_pathsearch_core.hpp"
@@ -83,31 +84,7 @@ __global__ void k_pack_bit(int nz, int nzw, size_t n_words, int bit, const uint8
     }
     plane[wi] = b;
 }
-// z: out word = OR over |d| <= r of the row shifted by d bits (r <= 31: one neighbour word each side)
-__global__ void k_dilate_bits_z(int nz, int nzw, size_t n_words, int r, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
-    const size_t wi = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (wi >= n_words) return;
-    const int w = (int)(wi % nzw);
-    const uint64_t lo = w > 0 ? in[wi - 1] : 0u, mid = in[wi], hi = w + 1 < nzw ? in[wi + 1] : 0u;
-    uint32_t acc = (uint32_t)mid;
-    for (int d = 1; d <= r; ++d) {
-        acc |= (uint32_t)(((mid << 32 | lo) >> (32 - d)) & 0xffffffffu);   // voxels z - d land on z
-        acc |= (uint32_t)(((hi << 32 | mid) >> d) & 0xffffffffu);          // voxels z + d land on z
-    }
-    const int valid = nz - 32 * w;                                          // bits past nz stay clear
-    if (valid < 32) acc &= (1u << valid) - 1u;
-    out[wi] = acc;
-}
-// y (stride nzw words, length ny) or x (stride ny * nzw, length nx): OR of whole words
-__global__ void k_dilate_bits_rows(size_t n_words, size_t stride, int len, int r, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
-    const size_t wi = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (wi >= n_words) return;
-    const int c = (int)((wi / stride) % (size_t)len);
-    const int lo = c - r < 0 ? -c : -r, hi = c + r >= len ? len - 1 - c : r;
-    uint32_t acc = 0;
-    for (int d = lo; d <= hi; ++d) acc |= in[(ptrdiff_t)wi + (ptrdiff_t)d * (ptrdiff_t)stride];
-    out[wi] = acc;
-}
+// (the dilation kernels k_dilate_bits_z / k_dilate_bits_rows: vigo_dilate_bits.hpp, shared with vigo_grid_update.hip)
 // one plane word (32 voxels) per thread: bit0 of the 32 bytes from the word's bits
 __global__ void k_merge_bit0(int nz, int nzw, size_t n_words, const uint32_t* __restrict__ plane, uint8_t* __restrict__ vox) {
     const size_t wi = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

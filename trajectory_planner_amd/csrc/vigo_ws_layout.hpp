@@ -43,6 +43,17 @@ size_t ws_pair(void* base, size_t n, T*& first, T*& second) {
     return c.bytes();
 }
 
+// vigo_update_grid_region: the box' bytes as the *_host form stages them (none in the device-pointer form; whole 16-byte
+// lines, so the buffer's alignment carries over to the planes and the box' rows keep k_pack_grid's aligned loads), then
+// the two compact planes of window_words each that inflate mode dilates in (none in raw mode)
+inline size_t ws_grid_update(void* base, size_t staged_bytes, size_t window_words, uint8_t*& staged, uint32_t*& planeA, uint32_t*& planeB) {
+    WsCarver c(base);
+    staged = staged_bytes ? c.take<uint8_t>((staged_bytes + 15) & ~(size_t)15) : nullptr;
+    planeA = window_words ? c.take<uint32_t>(window_words) : nullptr;
+    planeB = window_words ? c.take<uint32_t>(window_words) : nullptr;
+    return c.bytes();
+}
+
 // vigo_corridor_check: the first pass' work list for the second (whole 256-byte lines), then the segments' clock tables
 inline size_t ws_corridor(void* base, size_t S, size_t clock_bytes, int*& todo, void*& clock_ws) {
     WsCarver c(base);

@@ -89,6 +89,8 @@ public:
      * access, see mapAdapter.h; ignored by the in-tree dense map) and the request to re-snapshot a map that changed */
     void setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);
     void refreshMap();
+    /* ... that changed inside this metric box only: a snapshot that was current gets the box alone (mapAdapter.h) */
+    void refreshMap(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);
     /* not in the reference: the HIP device ordinal this planner's back-end handle lives on (default 0); call it before
      * the first plan, or later to move the planner (the handle is re-created and the map uploaded again) */
     void setDevice(int ordinal);

@@ -12,13 +12,21 @@
  *
  * Builds without map_manager (this tree's dense stand-in, standin/dense_occmap.h) take a fast path: the stand-in's
  * own bytes are uploaded as they are and its `version` counter tells when they changed — no region, no refresh call.
+ *
+ * When the map's owner says WHICH box changed (the dense map's markChanged(lo, n); refreshMap(boxMin, boxMax) /
+ * updateMap(boxMin, boxMax) on a live map), a handle whose snapshot is only such changes behind gets the boxes alone,
+ * through vigo_update_grid_region_host: the dense map's bytes of the box as they are, a live map rasterised over the box
+ * only.  Anything else — a first upload, a bare ++version, refreshMap() without a box, more than 16 changes behind, boxes
+ * that together hold no fewer voxels than the grid — replaces the snapshot whole as before.
  */
 #ifndef TRAJECTORY_PLANNER_MAP_ADAPTER_H
 #define TRAJECTORY_PLANNER_MAP_ADAPTER_H
 #include <trajectory_planner/compat.h>
+#include <trajectory_planner/dirtyJournal.h>
 
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 struct vigo_context;
 struct vigo_params_s;
@@ -50,6 +58,19 @@ public:
      * still re-rasterises).  Generations start at 1; a stamp of 0 never matches. */
     static uint64_t generation(const mapManager::occMap* map);
     static void bumpGeneration(const mapManager::occMap* map);
+    /* ... and the same with the metric box outside which the map did not change: the generation moves AND the map's
+     * journal (one per map object, next to its generation) gets the box, in voxels of the lattice of whole multiples of
+     * res from zero that every region's snapshot lies on: lo = floor(boxMin / res), n = ceil(boxMax / res) - lo.  A box
+     * that is not finite or is empty counts as a bump without a box. */
+    static void bumpGeneration(mapManager::occMap* map, const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);
+    /* the boxes of every generation in (since, now] of a live map: DirtyJournal::changesSince on the map's journal */
+    static bool changesSince(const mapManager::occMap* map, uint64_t since, uint64_t now, std::vector<DirtyBox>& out);
+    /* process-wide counts of what uploadSnapshot sent, behind the generation table's lock: snapshots replaced whole,
+     * boxes sent by the region route, and the voxels in those boxes */
+    struct SnapshotTotals {
+        long long fullSnapshots = 0, regionUpdates = 0, regionVoxels = 0;
+    };
+    static SnapshotTotals snapshotTotals();
     /* octomap-style node lookup for polyTrajOctomap::checkCollisionPoint (PO.cpp:571-589): kOutside beyond the metric
      * bounds, else bit1 = no node (unknown), bit2 = occupied */
     enum : unsigned { kUnknown = 2u, kOccupied = 4u, kOutside = 0x80u };
@@ -57,6 +78,15 @@ public:
     /* rasterisation of any occMap through its four public methods over `region` (what uploadSnapshot uploads for a
      * map it cannot read in bulk); dims and origin of the grid are returned */
     static bool rasterise(mapManager::occMap& map, const mapRegion& region, std::vector<uint8_t>& voxels, int dims[3], double origin[3]);
+    /* the same over the sub-box [subMin, subMax] only, on the lattice rasterise() uses for `region` (origin
+     * floor(boxMin / res) * res): the voxels the sub-box touches, clipped to the region's grid, come back as
+     * bytes[n[0]][n[1]][n[2]] with their first voxel lo — the arguments of vigo_update_grid_region_host.  An empty clip is
+     * a no-op: true with n = {0, 0, 0}.  false: no region, or a resolution or box rasterise() refuses. */
+    static bool rasteriseBox(mapManager::occMap& map, const mapRegion& region, const Eigen::Vector3d& subMin, const Eigen::Vector3d& subMax,
+                             std::vector<uint8_t>& bytes, int lo[3], int n[3]);
+    /* ... and over a box given in voxels of the zero-based lattice (a journal entry of a live map) */
+    static bool rasteriseKeys(mapManager::occMap& map, const mapRegion& region, const int keyLo[3], const int keyN[3],
+                              std::vector<uint8_t>& bytes, int lo[3], int n[3]);
 };
 
 /* The link between ONE planner and its device handle, held by all three facades (bsplineTraj, polyTrajOctomap,
@@ -75,6 +105,9 @@ public:
     void setRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);   // forces a new snapshot
     /* the map changed: every handle that holds a snapshot of it is stale, not only this one (generation, above) */
     void refresh();
+    /* ... and only inside this metric box: handles that were current before get the box alone (mapAdapter.h, top).  On the
+     * in-tree dense map this is markChanged() of the voxels the box touches. */
+    void refresh(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);
     /* One process per GPU is the deployment the back-end is built for (HIP_VISIBLE_DEVICES picks the card); a process
      * that drives several cards gives each planner its ordinal before the planner's first device call.  The current
      * ordinal: nothing happens.  Another: the link lets go of its handle; the next sync() creates one there and uploads

@@ -144,6 +144,7 @@ public:
      * map that changed, the HIP device of the back-end handle (default 0) — makePlanBatch only */
     void setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);
     void refreshMap();
+    void refreshMap(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax);   // ... inside this metric box only
     void setDevice(int ordinal);
 
     // visualization (no ROS here: nothing is published)

@@ -129,6 +129,8 @@ public:
     void insertWaypoint(const std::set<int>& seg);                     // PO.cpp:178-186
     /* re-snapshot the map on the next device call (the reference re-fetches /octomap_binary, PO.cpp:133-145) */
     void updateMap() { link_.refresh(); }
+    /* ... when the map changed inside this metric box only: a snapshot that was current gets the box alone (mapAdapter.h) */
+    void updateMap(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.refresh(boxMin, boxMax); }
     /* not in the reference: the box of the map the device snapshot covers (mapAdapter.h; ignored by the dense map) */
     void setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
 

@@ -8,6 +8,7 @@
  */
 #ifndef TRAJECTORY_PLANNER_DENSE_OCCMAP_H
 #define TRAJECTORY_PLANNER_DENSE_OCCMAP_H
+#include <trajectory_planner/dirtyJournal.h>
 #include <trajectory_planner/standin/mini_eigen.h>
 
 #include <cmath>
@@ -55,11 +56,21 @@ public:
     }
     /* bumped by the owner whenever voxels() changes, so planners re-snapshot */
     uint64_t version = 1;
+    /* ... or, when the owner knows the box [lo, lo + n) of voxels outside which nothing changed since the last bump: the
+     * bump with a journal entry.  Planners whose snapshot is one or a few such entries behind send only the boxes
+     * (mapAdapter::uploadSnapshot); a bare ++version in between leaves a hole in the journal, and the hole sends the whole
+     * grid as before. */
+    void markChanged(const int lo[3], const int n[3]) {
+        ++version;
+        journal_.record(version, lo, n);
+    }
+    const trajPlanner::DirtyJournal& journal() const { return journal_; }
 private:
     int nx_, ny_, nz_;
     Eigen::Vector3d origin_;
     double res_;
     std::vector<uint8_t> vox_;
+    trajPlanner::DirtyJournal journal_;
 };
 }  // namespace mapManager
 #endif

@@ -76,6 +76,7 @@ void bsplineTraj::setMap(const std::shared_ptr<mapManager::occMap>& map) {
 
 void bsplineTraj::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
 void bsplineTraj::refreshMap() { link_.refresh(); }
+void bsplineTraj::refreshMap(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.refresh(boxMin, boxMax); }
 void bsplineTraj::setDevice(int ordinal) { link_.setDevice(ordinal); }
 
 void bsplineTraj::updateMaxVel(double maxVel) { this->maxVel_ = maxVel; }

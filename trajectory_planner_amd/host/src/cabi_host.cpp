@@ -2222,3 +2222,138 @@ extern "C" long long vigo_host_rasterise_check(int nx, int ny, int nz, const dou
             }
     return bad;
 }
+
+// mapAdapter::rasteriseBox against a whole rasterisation, CPU only: the dense map is rasterised over the region
+// [box_min, box_max] (grid A), the edit (edit_n bytes at voxel edit_lo of the dense map's own lattice) is written into the
+// map, rasteriseBox runs over [sub_min, sub_max] and its bytes are patched into A (vigo_grid_region_apply_host, raw mode);
+// the map is then rasterised whole again (grid B).  dims_out: the grids' extents, lo_out / n_out: what rasteriseBox
+// returned, patched / whole: A and B, cap bytes each.  Returns 0, -1 when a step failed, -2 when cap is too small.
+extern "C" int vigo_host_rasterise_box(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels, const double* box_min,
+                                       const double* box_max, const int* edit_lo, const int* edit_n, const unsigned char* edit_bytes,
+                                       const double* sub_min, const double* sub_max, long long cap, int* dims_out, int* lo_out, int* n_out,
+                                       unsigned char* patched, unsigned char* whole) {
+    auto map = denseMap(nx, ny, nz, origin, res, voxels);
+    trajPlanner::mapRegion region;
+    region.set = true;
+    region.boxMin = Eigen::Vector3d(box_min[0], box_min[1], box_min[2]);
+    region.boxMax = Eigen::Vector3d(box_max[0], box_max[1], box_max[2]);
+    std::vector<uint8_t> a, b, bytes;
+    int dims[3], lo[3], n[3];
+    double o[3];
+    if (!trajPlanner::mapAdapter::rasterise(*map, region, a, dims, o)) return -1;
+    for (int k = 0; k < 3; ++k)
+        if (edit_lo[k] < 0 || edit_n[k] < 0 || edit_lo[k] + edit_n[k] > (k == 0 ? nx : k == 1 ? ny : nz)) return -1;
+    for (int ix = 0; ix < edit_n[0]; ++ix)
+        for (int iy = 0; iy < edit_n[1]; ++iy)
+            for (int iz = 0; iz < edit_n[2]; ++iz)
+                map->at(edit_lo[0] + ix, edit_lo[1] + iy, edit_lo[2] + iz) = edit_bytes[((size_t)ix * edit_n[1] + iy) * edit_n[2] + iz];
+    if (!trajPlanner::mapAdapter::rasteriseBox(*map, region, Eigen::Vector3d(sub_min[0], sub_min[1], sub_min[2]),
+                                               Eigen::Vector3d(sub_max[0], sub_max[1], sub_max[2]), bytes, lo, n))
+        return -1;
+    if (bytes.size() != (size_t)n[0] * n[1] * n[2]) return -1;
+    if (!bytes.empty() && vigo_grid_region_apply_host(dims[0], dims[1], dims[2], a.data(), lo, n, bytes.data(), nullptr) != VIGO_OK) return -1;
+    if (!trajPlanner::mapAdapter::rasterise(*map, region, b, dims, o)) return -1;
+    for (int k = 0; k < 3; ++k) { dims_out[k] = dims[k]; lo_out[k] = lo[k]; n_out[k] = n[k]; }
+    if ((long long)a.size() > cap) return -2;
+    std::memcpy(patched, a.data(), a.size());
+    std::memcpy(whole, b.data(), b.size());
+    return 0;
+}
+
+// trajPlanner::DirtyJournal on its own, CPU only: n_rec entries (version[k], a box whose every lo is version[k] and every n
+// is k) are recorded in turn, then changesSince(since, now) is asked.  Returns -1 when it is false, else the number of
+// entries, with versions_out / n_out (cap values each) the entries' version and n[0].
+extern "C" int vigo_host_dirty_journal(int n_rec, const unsigned long long* version, unsigned long long since, unsigned long long now, int cap,
+                                       unsigned long long* versions_out, int* n_out) {
+    trajPlanner::DirtyJournal j;
+    for (int k = 0; k < n_rec; ++k) {
+        const int lo[3] = {(int)version[k], (int)version[k], (int)version[k]}, n[3] = {k, k, k};
+        j.record(version[k], lo, n);
+    }
+    std::vector<trajPlanner::DirtyBox> out;
+    if (!j.changesSince(since, now, out)) return -1;
+    if ((int)out.size() > cap) return -2;
+    for (size_t k = 0; k < out.size(); ++k) {
+        if (out[k].lo[0] != (int)out[k].version || out[k].lo[2] != (int)out[k].version || out[k].n[0] != out[k].n[1]) return -3;
+        versions_out[k] = out[k].version;
+        n_out[k] = out[k].n[0];
+    }
+    return (int)out.size();
+}
+
+// A map that changes under planners that share it: n planners with a pose list each (as vigo_host_plan_batch_options) on
+// ONE dense map plan by makePlanBatch(planners) under the options of `mask`, after the first upload (round 0) and after
+// each of E edits (round e + 1): edit e writes the bytes edit_bytes[edit_off[e] ..) as the box edit_n[e] at voxel
+// edit_lo[e] into the map and then tells the planners by mode 0: a bare ++version, mode 1: markChanged(lo, n).  The
+// planners (and their handles) live through all rounds; every round starts from updatePathBatch on the same paths.
+// Outputs per round r as slot r of dumpSlot: ok, solver, ncp [E+1][n], ctrl [E+1][n][ncp_cap][3] (zero padded by the
+// caller); totals[3]: what mapAdapter::snapshotTotals moved by over the call (full snapshots, region updates, region
+// voxels); round_ms[E+1]: the wall time of the round's makePlanBatch, the snapshot refresh included.  Returns 0, -1 on a
+// bad argument, -2 when ncp_cap is too small, -3 when a call threw.  Needs a GPU.
+extern "C" int vigo_host_map_update_replan(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                           const double* path_xyz, const double* cfg, int mask, int E, const int* edit_lo, const int* edit_n,
+                                           const long long* edit_off, const unsigned char* edit_bytes, int mode, int ncp_cap, int* ok,
+                                           int* solver, int* ncp, double* ctrl, long long* totals, double* round_ms) {
+    if (n < 1 || !path_off || !path_xyz || !cfg || mask < 0 || E < 0 || (mode != 0 && mode != 1)) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    for (int e = 0; e < E; ++e)
+        for (int a = 0; a < 3; ++a)
+            if (edit_lo[3 * e + a] < 0 || edit_n[3 * e + a] < 0 || edit_lo[3 * e + a] + edit_n[3 * e + a] > dims[a]) return -1;
+    try {
+        BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+        const trajPlanner::mapAdapter::SnapshotTotals before = trajPlanner::mapAdapter::snapshotTotals();   // (the planners' first fit uploads)
+        FreshPlanners fp = freshPlanners(fx);
+        mapManager::occMap& map = *fx.maps[0];
+        const bsplineTraj::BatchOptions o = optionsOfMask(mask, 16384);
+        for (int r = 0; r <= E; ++r) {
+            if (r > 0) {
+                const int e = r - 1;
+                const int *lo = edit_lo + 3 * e, *en = edit_n + 3 * e;
+                const unsigned char* src = edit_bytes + edit_off[e];
+                for (int ix = 0; ix < en[0]; ++ix)
+                    for (int iy = 0; iy < en[1]; ++iy)
+                        for (int iz = 0; iz < en[2]; ++iz) map.at(lo[0] + ix, lo[1] + iy, lo[2] + iz) = src[((size_t)ix * en[1] + iy) * en[2] + iz];
+                if (mode == 1) map.markChanged(lo, en);
+                else ++map.version;
+                bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
+            }
+            bsplineTraj::BatchStats st;
+            const std::vector<bool> planned = timedPlan(fp.ps, o, round_ms[r], st);
+            const int rc = dumpSlot(fp.ps, planned, r, ncp_cap, 0, ok, solver, ncp, ctrl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            if (rc != 0) return rc;
+        }
+        const trajPlanner::mapAdapter::SnapshotTotals after = trajPlanner::mapAdapter::snapshotTotals();
+        totals[0] = after.fullSnapshots - before.fullSnapshots;
+        totals[1] = after.regionUpdates - before.regionUpdates;
+        totals[2] = after.regionVoxels - before.regionVoxels;
+    } catch (...) {
+        return -3;
+    }
+    return 0;
+}
+
+// The facade's snapshot refresh alone, timed: a DeviceLink on a dense map is synced once (the first upload), then `reps`
+// times the owner announces a change of the box [lo, lo + n) — mode 0: ++version, mode 1: markChanged(lo, n) — and the
+// next sync() is timed into ms[rep] (wall clock; sync() returns when the snapshot is on the device).  totals[3]: what
+// mapAdapter::snapshotTotals moved by over the reps.  Returns 0, -1 when a sync failed.  Needs a GPU.
+extern "C" int vigo_host_snapshot_refresh(const unsigned char* vox, const int* dims, const double* origin, double res, const int* lo, const int* n,
+                                          int mode, int reps, double* ms, long long* totals) {
+    auto map = denseMap(dims[0], dims[1], dims[2], origin, res, vox);
+    trajPlanner::DeviceLink link;
+    link.setMap(map);
+    if (link.sync(true) != trajPlanner::DeviceLink::kSynced) return -1;
+    const trajPlanner::mapAdapter::SnapshotTotals before = trajPlanner::mapAdapter::snapshotTotals();
+    for (int rep = 0; rep < reps; ++rep) {
+        if (mode == 1) map->markChanged(lo, n);
+        else ++map->version;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (link.sync(true) != trajPlanner::DeviceLink::kSynced) return -1;
+        ms[rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    const trajPlanner::mapAdapter::SnapshotTotals after = trajPlanner::mapAdapter::snapshotTotals();
+    totals[0] = after.fullSnapshots - before.fullSnapshots;
+    totals[1] = after.regionUpdates - before.regionUpdates;
+    totals[2] = after.regionVoxels - before.regionVoxels;
+    return 0;
+}

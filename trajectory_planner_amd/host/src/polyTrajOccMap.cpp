@@ -49,6 +49,7 @@ void polyTrajOccMap::initParam() {
 void polyTrajOccMap::setMap(const std::shared_ptr<mapManager::occMap>& map) { link_.setMap(map); }
 void polyTrajOccMap::setMapRegion(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.setRegion(boxMin, boxMax); }
 void polyTrajOccMap::refreshMap() { link_.refresh(); }
+void polyTrajOccMap::refreshMap(const Eigen::Vector3d& boxMin, const Eigen::Vector3d& boxMax) { link_.refresh(boxMin, boxMax); }
 void polyTrajOccMap::setDevice(int ordinal) { link_.setDevice(ordinal); }
 bool polyTrajOccMap::syncDevice() { return link_.sync(true) == DeviceLink::kSynced; }
 

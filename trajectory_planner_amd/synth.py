@@ -351,6 +351,23 @@ def host_esdf(world: World, plane: int = 2, unknown_is_site: bool = False):
     return out, np.array(world.origin, dtype=np.float64)
 
 
+def host_grid_region_apply(voxels, lo, box, inflate_r=None):
+    """The library's host twin of vigo_update_grid_region (vigo_grid_region_apply_host, csrc/vigo_grid_update_core.hpp; no
+    GPU): a copy of the byte grid `voxels` [nx,ny,nz] with `box` [n0,n1,n2] written at `lo` — raw when inflate_r is None,
+    else bit 0 re-inflated from bit 2 on the box grown by inflate_r.  Returns (return code, new grid); the grid is the
+    input's copy unchanged when the code is not 0."""
+    import ctypes as C
+    from . import _lib
+    out = np.array(voxels, dtype=np.uint8, order="C")
+    box = np.ascontiguousarray(box, dtype=np.uint8)
+    nx, ny, nz = out.shape
+    i3 = lambda v: (C.c_int32 * 3)(*[int(x) for x in v])
+    r = None if inflate_r is None else i3(inflate_r)
+    rc = _lib.load().vigo_grid_region_apply_host(nx, ny, nz, out.ctypes.data_as(C.c_void_p), i3(lo), i3(box.shape),
+                                                 C.c_void_p(box.ctypes.data or 1), r)
+    return rc, out
+
+
 def host_traj_finish(ts_ctrl, ts, ctrl, limits, sample_dt, S_cap, n_pts=None, out=None, want_max=True, want_vel=True):
     """Vigo.traj_finish's result by the library's host twin (vigo_traj_finish_host: csrc/vigo_finish_core.hpp compiled
     for the CPU; no GPU), numpy in and out: ctrl [B,Ns,3], limits [B,2], n_pts int32 [B] or None -> dict of factor, max,

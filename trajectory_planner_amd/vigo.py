@@ -186,6 +186,41 @@ class Vigo:
         self._check(self._lib.vigo_set_metric_bounds(self._h, (C.c_double * 3)(*bmin), (C.c_double * 3)(*bmax)),
                     "vigo_set_metric_bounds")
 
+    @staticmethod
+    def _int3(v, name: str):
+        v = [int(x) for x in v]
+        if len(v) != 3:
+            raise ValueError(f"{name}: expected three integers")
+        return (C.c_int32 * 3)(*v)
+
+    def update_grid_region(self, lo, voxels: torch.Tensor, inflate_r=None):
+        """vigo_update_grid_region: the box of voxels.shape at lo written into the snapshot in place, stream-ordered.
+        voxels: uint8 [n0,n1,n2] on the GPU.  inflate_r None: raw (bits 0..2 of the bytes); (rx,ry,rz): bit 0 is ignored and
+        plane 0 is re-inflated from the occupied plane on the box grown by r.  A field built by build_esdf is stale afterwards."""
+        if voxels.dim() != 3:
+            raise ValueError("voxels: expected [n0,n1,n2]")
+        r = None if inflate_r is None else self._int3(inflate_r, "inflate_r")
+        p = _ptr(voxels, torch.uint8, "voxels", self.device) if voxels.numel() else C.c_void_p(voxels.data_ptr() or 1)
+        self._check(self._lib.vigo_update_grid_region(self._h, self._int3(lo, "lo"), self._int3(voxels.shape, "n"), p, r),
+                    "vigo_update_grid_region")
+
+    def update_grid_region_host(self, lo, voxels, inflate_r=None):
+        """vigo_update_grid_region_host: the same from a C-contiguous uint8 numpy array [n0,n1,n2] (staged; synchronises)."""
+        if voxels.dtype.name != "uint8" or voxels.ndim != 3 or not voxels.flags["C_CONTIGUOUS"]:
+            raise ValueError("voxels: expected a C-contiguous uint8 array [n0,n1,n2]")
+        r = None if inflate_r is None else self._int3(inflate_r, "inflate_r")
+        self._check(self._lib.vigo_update_grid_region_host(self._h, self._int3(lo, "lo"), self._int3(voxels.shape, "n"),
+                                                           C.c_void_p(voxels.ctypes.data or 1), r), "vigo_update_grid_region_host")
+
+    def get_grid_packed(self) -> torch.Tensor:
+        """vigo_get_grid_packed: a copy of the handle's current snapshot (int32 tensor, the format of pack_grid)."""
+        if self._grid_meta is None:
+            raise VigoError("get_grid_packed before set_grid")
+        nx, ny, nz = self._grid_meta[:3]
+        packed = torch.empty(self._lib.vigo_grid_packed_bytes(nx, ny, nz) // 4, dtype=torch.int32, device=self.device)
+        self._check(self._lib.vigo_get_grid_packed(self._h, C.c_void_p(packed.data_ptr())), "vigo_get_grid_packed")
+        return packed
+
     def query_points(self, pts: torch.Tensor, which: int = 0) -> torch.Tensor:
         _shape(pts, (None, 3), "pts")
         q = pts.shape[0]
