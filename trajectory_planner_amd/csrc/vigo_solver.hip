@@ -43,6 +43,14 @@
 #ifndef VIGO_AXIS_CONV_FILTER
 #define VIGO_AXIS_CONV_FILTER 1
 #endif
+// dev switches of the axis kernel's paired reductions (pair_tree32 below; profiles/README.md, round 8): two sums in one
+// 32-lane tree, one per half of the wave, in the evaluation's six sums and in the update's ys and yy
+#ifndef VIGO_AXIS_PAIR_EVAL
+#define VIGO_AXIS_PAIR_EVAL 1
+#endif
+#ifndef VIGO_AXIS_PAIR_UPDATE
+#define VIGO_AXIS_PAIR_UPDATE 1
+#endif
 
 namespace vigo {
 namespace {
@@ -211,6 +219,50 @@ __device__ __forceinline__ double group_sum1(double v) {
     double a[1] = {v};
     group_sum<GROUP, 1>(a);
     return a[0];
+}
+
+// AXIS layout: TWO sums in one 32-lane tree.  There the xor-32 exchange of a dot product comes BEFORE the tree, so lanes
+// l and l + 32 enter group_sum<32, K> with the same partial and the two halves of the wave run the same tree on the same
+// operands — every tree twice.  Here the lower half carries the partials of sum A and the upper half those of sum B:
+// v[q] = [A partial of point l | B partial of point l].  The five levels are those of group_sum<32, K>, control for
+// control: the quad_perm and mirror patterns read inside the reader's own 16-lane row, v_permlane16_swap exchanges rows
+// 0/1 and rows 2/3, and a half is rows 0-1 or rows 2-3 — so no lane reads a lane of the other half and each half runs
+// exactly the tree it runs in group_sum, on the operands it has there: the same bits.  Only then the xor-32 exchange
+// (xy_parts, on the twice-issued last add) hands every lane both totals: a[q] = what the lower half holds, b[q] = the upper.
+template <int K>
+__device__ __forceinline__ void pair_tree32(double (&v)[K], double (&a)[K], double (&b)[K]) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] += dpp_f64<0xB1>(v[q]);   // quad_perm:[1,0,3,2]
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] += dpp_f64<0x4E>(v[q]);   // quad_perm:[2,3,0,1]
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] += dpp_f64<0x141>(v[q]);  // row_half_mirror
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        const double t = dpp_f64<0x140>(v[q]);                 // row_mirror
+        double p0, p1;
+        xor16_parts(v[q] + t, add_f64_again(v[q], t), p0, p1);
+        xy_parts(p0 + p1, add_f64_again(p0, p1), a[q], b[q]);
+    }
+}
+// The packed partials of two dot products of the AXIS layout, from the per-lane products u (sum A) and w (sum B) of a
+// lane's coordinate: v_permlane32_swap gives [u of x | w of x] and [u of y | w of y], and their sum is
+// [u_x + u_y | w_x + w_y] — in each half the add dot_xy() does, operands in the same order, for the sum that half carries.
+__device__ __forceinline__ double pack_xy(double u, double w) {
+    const int ulo = __double2loint(u), uhi = __double2hiint(u), wlo = __double2loint(w), whi = __double2hiint(w);
+    auto l = __builtin_amdgcn_permlane32_swap(ulo, wlo, false, false);
+    auto h = __builtin_amdgcn_permlane32_swap(uhi, whi, false, false);
+    return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
+}
+// ys = y . s and yy = y . y of the update (LB:1264-1276) in the AXIS layout as one pair, y and s the lane's coordinate:
+// what dot_lane<.., 1>, the + 0.0 of the level trajectory's z product and group_sum<32, 2> compute, ys in the lower half
+// and yy in the upper.  The + 0.0 follows the exchange add, as it does there, and is applied to both halves: yy's
+// partial is a sum of two squares, +0 or above or NaN, never -0, and x + 0.0 is x for every such x.
+__device__ __forceinline__ void ys_yy_axis(double y, double s, double& ys, double& yy) {
+    double v[1] = {pack_xy(y * s, y * y) + 0.0}, a[1], b[1];
+    pair_tree32<1>(v, a, b);
+    ys = a[0];
+    yy = b[0];
 }
 
 // min and max of a value over the lanes of a group (the same xor butterfly; order is irrelevant for min / max)
@@ -772,6 +824,8 @@ __device__ __forceinline__ double eval_cost_grad(const DevConst& K, const LanePr
 // half of the wave.  Wherever eval_cost_grad<.., D = 2> adds the x term and the y term of a point, the xor-32 exchange
 // hands both lanes both terms and they add them in that order; what follows (the exact-zero z terms, the 32-lane tree)
 // is then the same in both halves, which end with the same bits in every sum — and so with the same line-search scalars.
+// VIGO_AXIS_PAIR_EVAL: the six sums go through three trees as pairs, one sum per half (pair_tree32), whose last exchange
+// hands every lane both totals: the same bits in every sum, in both halves, as before.
 template <class KC>
 __device__ __forceinline__ double eval_cost_grad_axis(const KC& K, const LaneProblem<double, 1>& Q, int axis,
                                                       const double (&c)[1][3], const double (&d)[1][3], double (&g)[1][3],
@@ -782,15 +836,27 @@ __device__ __forceinline__ double eval_cost_grad_axis(const KC& K, const LanePro
     const double cz = c[0][2];
     double jj[1], vv[1], aa[1], Gs[1], Gf[1];
     stencil_axis<double, 1, false>(K, C, false, jj, vv, aa, Gs, Gf);
-    double j0, j1, v0, v1, a0, a1;
-    xy_both(jj[0], j0, j1);
-    xy_both(vv[0], v0, v1);
-    xy_both(aa[0], a0, a1);
     // (the trailing zeros are the z terms of eval_cost_grad<.., D = 2>, kept where it adds them)
     double pt_s = 0.0, pt_f = 0.0, pt_d = 0.0;
-    if (Q.has_pt[0] && p <= N - 4) pt_s = sum3(j0, j1, 0.0);
-    if (Q.has_pt[0] && p <= N - 2) pt_f = (v0 + v1) + 0.0;
-    if (Q.has_pt[0] && p <= N - 3) { pt_f += a0; pt_f += a1; pt_f += 0.0; }
+    double pt_sf = 0.0;   // PAIR_EVAL: [pt_s | pt_f], the smoothness partial in the lower half, the feasibility one in the upper
+    if constexpr (VIGO_AXIS_PAIR_EVAL) {
+        // pack_xy(jj, vv) = [j0 + j1 | v0 + v1]: the first add of sum3(j0, j1, 0.0) and of (v0 + v1) + 0.0, each in the half
+        // that carries it; the + 0.0 that follows is the same statement in both.  The acceleration terms belong to pt_f
+        // alone: they are added in the upper half only, after the velocity terms, in the order below.
+        double a0, a1;
+        xy_both(aa[0], a0, a1);
+        const double t = pack_xy(jj[0], vv[0]) + 0.0;
+        if (Q.has_pt[0] && p <= (axis ? N - 2 : N - 4)) pt_sf = t;
+        if (axis && Q.has_pt[0] && p <= N - 3) { pt_sf += a0; pt_sf += a1; pt_sf += 0.0; }
+    } else {
+        double j0, j1, v0, v1, a0, a1;
+        xy_both(jj[0], j0, j1);
+        xy_both(vv[0], v0, v1);
+        xy_both(aa[0], a0, a1);
+        if (Q.has_pt[0] && p <= N - 4) pt_s = sum3(j0, j1, 0.0);
+        if (Q.has_pt[0] && p <= N - 2) pt_f = (v0 + v1) + 0.0;
+        if (Q.has_pt[0] && p <= N - 3) { pt_f += a0; pt_f += a1; pt_f += 0.0; }
+    }
 
     // ---- guide-point distance: both lanes of a point enter together (interior and the pair range are per point) ----
     double Gd = 0.0;
@@ -812,14 +878,27 @@ __device__ __forceinline__ double eval_cost_grad_axis(const KC& K, const LanePro
     const double Go = 0.0;
     g[0][0] = !Q.interior[0] ? 0.0 : ((w0 * Gd + w1 * Gs[0]) + w2 * Gf[0]) + w3 * Go;
     g[0][1] = g[0][2] = 0.0;
-    double p6[6];
-    p6[0] = pt_d; p6[1] = pt_s; p6[2] = pt_f;
-    p6[3] = dot_xy(g[0][0], d[0][0]);
-    const double xx = dot_xy(C[0], C[0]) + cz * cz;                          // (x.x: the level coordinate counts)
-    p6[4] = Q.interior[0] ? xx : 0.0;
-    p6[5] = dot_xy(g[0][0], g[0][0]);
-    group_sum<32, 6>(p6);
-    sums[0] = p6[0]; sums[1] = p6[1]; sums[2] = p6[2]; sums[3] = 0.0; sums[4] = p6[3]; sums[5] = p6[4]; sums[6] = p6[5];
+    if constexpr (VIGO_AXIS_PAIR_EVAL) {
+        const double xx = dot_xy(C[0], C[0]) + cz * cz;                      // (x.x: the level coordinate counts)
+        // six sums as three pairs, one sum per half of the wave (pair_tree32): [pt_d | x.x], [pt_s | pt_f], [g.d | g.g].
+        // pt_d and x.x are the same in both lanes of a point: each half keeps the one it carries.  g.d and g.g are
+        // dot_xy() of per-lane products: pack_xy() forms both exchange adds at once.
+        double v3[3], lo[3], hi[3];
+        v3[0] = axis ? (Q.interior[0] ? xx : 0.0) : pt_d;
+        v3[1] = pt_sf;
+        v3[2] = pack_xy(g[0][0] * d[0][0], g[0][0] * g[0][0]);
+        pair_tree32<3>(v3, lo, hi);
+        sums[0] = lo[0]; sums[1] = lo[1]; sums[2] = hi[1]; sums[3] = 0.0; sums[4] = lo[2]; sums[5] = hi[0]; sums[6] = hi[2];
+    } else {
+        double p6[6];
+        p6[0] = pt_d; p6[1] = pt_s; p6[2] = pt_f;
+        p6[3] = dot_xy(g[0][0], d[0][0]);
+        const double xx = dot_xy(C[0], C[0]) + cz * cz;                      // (x.x: the level coordinate counts)
+        p6[4] = Q.interior[0] ? xx : 0.0;
+        p6[5] = dot_xy(g[0][0], g[0][0]);
+        group_sum<32, 6>(p6);
+        sums[0] = p6[0]; sums[1] = p6[1]; sums[2] = p6[2]; sums[3] = 0.0; sums[4] = p6[3]; sums[5] = p6[4]; sums[6] = p6[5];
+    }
     return ((Q.w[0] * sums[0] + Q.w[1] * sums[1]) + Q.w[2] * sums[2]) + Q.w[3] * sums[3];
 }
 
@@ -1454,11 +1533,17 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
                 hist_at(q, end) = hp;
             }
         }
-        double ysyy[2] = {dot_lane<FAST, T, PPL, D>(yv, sv), dot_lane<FAST, T, PPL, D>(yv, yv)};
-        // (level trajectory: the z product the general kernel adds here is (+0) * (+0); it turns a lane partial of -0 into
-        // +0, and the sign of a zero ys decides the sign of the infinities the reference then divides into being)
-        if (D <= 2) ysyy[0] += 0.0;    // (AXIS: after the exchange add, where the D = 2 kernel has it)
-        group_sum<GROUP, 2>(ysyy);
+        double ysyy[2];
+        if constexpr (AXIS && VIGO_AXIS_PAIR_UPDATE) {
+            ys_yy_axis(yv[0][0], sv[0][0], ysyy[0], ysyy[1]);   // the same two sums, one per half of the wave in one tree
+        } else {
+            ysyy[0] = dot_lane<FAST, T, PPL, D>(yv, sv);
+            ysyy[1] = dot_lane<FAST, T, PPL, D>(yv, yv);
+            // (level trajectory: the z product the general kernel adds here is (+0) * (+0); it turns a lane partial of -0 into
+            // +0, and the sign of a zero ys decides the sign of the infinities the reference then divides into being)
+            if (D <= 2) ysyy[0] += 0.0;    // (AXIS: after the exchange add, where the D = 2 kernel has it)
+            group_sum<GROUP, 2>(ysyy);
+        }
         const double ys = ysyy[0], yy = ysyy[1];
         // the two-loop divides by ys of each pair (LB:1300, :1312); FAST keeps its reciprocal instead
         const YS ys_div = make_ys(ys, static_cast<YS*>(nullptr));
