@@ -33,6 +33,7 @@
 
 #include "vigo_exact_div.hpp"
 #include "vigo_internal.hpp"
+#include "vigo_linesearch.hpp"
 #include "vigo_solver_plan.hpp"
 
 // dev switches of the axis kernel's two short forms (vigo_exact_div.hpp; profiles/README.md, round 7): the stencil's
@@ -51,40 +52,21 @@
 #ifndef VIGO_AXIS_PAIR_UPDATE
 #define VIGO_AXIS_PAIR_UPDATE 1
 #endif
+// dev switches of the axis kernel's line search (vigo_linesearch.hpp; profiles/README.md, round 9).  Any of them takes the
+// axis kernel's search from the header, with a trial's set-up at the end of the trial before it, so that the first trial's
+// set-up is text of its own in which brackt = 0 and xt = 0 are constants: FIRST_SETUP = 2, the shipped setting (+1.0 %).
+// Measured and rejected, both off: FIRST_TESTS, the exit tests of a search's first trial behind a wave-uniform branch,
+// without the bracket's (no gain of its own on top of the moved set-up, and one SGPR spill); FIRST_SETUP = 1, the bracket
+// state formed only once that trial is rejected (the copies it puts on every later trial cost more than it saves).
+#ifndef VIGO_AXIS_LS_FIRST_TESTS
+#define VIGO_AXIS_LS_FIRST_TESTS 0
+#endif
+#ifndef VIGO_AXIS_LS_FIRST_SETUP
+#define VIGO_AXIS_LS_FIRST_SETUP 2
+#endif
 
 namespace vigo {
 namespace {
-
-// reference status codes, LB:20-80
-enum : int {
-    LB_CONVERGENCE = 0,
-    LB_STOP = 1,
-    LB_ALREADY_MINIMIZED = 2,
-    LBERR_UNKNOWN = -1024,
-    LBERR_LOGIC,
-    LBERR_CANCELED,
-    LBERR_INVALID_N,
-    LBERR_INVALID_MEMSIZE,
-    LBERR_INVALID_GEPSILON,
-    LBERR_INVALID_TESTPERIOD,
-    LBERR_INVALID_DELTA,
-    LBERR_INVALID_MINSTEP,
-    LBERR_INVALID_MAXSTEP,
-    LBERR_INVALID_FDECCOEFF,
-    LBERR_INVALID_SCURVCOEFF,
-    LBERR_INVALID_XTOL,
-    LBERR_INVALID_MAXLINESEARCH,
-    LBERR_OUTOFINTERVAL,
-    LBERR_INCORRECT_TMINMAX,
-    LBERR_ROUNDING_ERROR,
-    LBERR_MINIMUMSTEP,
-    LBERR_MAXIMUMSTEP,
-    LBERR_MAXIMUMLINESEARCH,
-    LBERR_MAXIMUMITERATION,
-    LBERR_WIDTHTOOSMALL,
-    LBERR_INVALIDPARAMETERS,
-    LBERR_INCREASEGRADIENT
-};
 
 // ---- cross-lane primitives -----------------------------------------------------------
 
@@ -422,6 +404,10 @@ struct LaneProblem {
 // two solves takes effect as before.
 __device__ __forceinline__ void hold_in_reg(double& v) { asm volatile("" : "+v"(v)); }   // opaque from here on: the compiler
 __device__ __forceinline__ void hold_in_reg(int& v) { asm volatile("" : "+s"(v)); }      // cannot go back to memory for it
+// v becomes a register of unspecified content, at no cost: for a variable of an iteration's scope that is written before
+// it is read, but not on every path — without this its value of the iteration before stays live across the whole loop
+__device__ __forceinline__ void fresh_reg(double& v) { asm volatile("" : "=v"(v)); }
+__device__ __forceinline__ void fresh_reg(int& v) { asm volatile("" : "=s"(v)); }
 struct HotConst {
     double dth, da, db, dc, unc_factor;                          // distance term
     double ts_ctrl, ts_inv_sqr;                                  // stencils
@@ -1060,116 +1046,6 @@ __global__ void __launch_bounds__(kWave) k_cost_grad(SolveArgsOf<MIXED> A, const
     }
 }
 
-// ---- More-Thuente helpers (per-lane scalar code, group-uniform values) -------------------
-
-// LB:308-324
-__device__ __forceinline__ double cubic_min(double u, double fu, double du, double v, double fv, double dv) {
-    double d = v - u;
-    double theta = (fu - fv) * 3 / d + du + dv;
-    double p = fabs(theta), q = fabs(du), r = fabs(dv);
-    double s = p >= q ? p : q;
-    s = s >= r ? s : r;
-    double a = theta / s;
-    double gamm = s * sqrt(a * a - (du / s) * (dv / s));
-    if (v < u) gamm = -gamm;
-    p = gamm - du + theta;
-    q = gamm - du + gamm + dv;
-    r = p / q;
-    return u + r * d;
-}
-// LB:338-366
-__device__ __forceinline__ double cubic_min_bounded(double u, double fu, double du, double v, double fv,
-                                                    double dv, double xmin, double xmax) {
-    double d = v - u;
-    double theta = (fu - fv) * 3 / d + du + dv;
-    double p = fabs(theta), q = fabs(du), r = fabs(dv);
-    double s = p >= q ? p : q;
-    s = s >= r ? s : r;
-    double a = theta / s;
-    double gamm = a * a - (du / s) * (dv / s);
-    gamm = gamm > 0 ? s * sqrt(gamm) : 0;
-    if (u < v) gamm = -gamm;
-    p = gamm - dv + theta;
-    q = gamm - dv + gamm + du;
-    r = p / q;
-    if (r < 0. && gamm != 0.) return v - r * d;
-    if (a < 0) return xmax;
-    return xmin;
-}
-// LB:377-379
-__device__ __forceinline__ double quad_min(double u, double fu, double du, double v, double fv) {
-    double a = v - u;
-    return u + du / ((fu - fv) / a + du) / 2 * a;
-}
-// LB:389-391
-__device__ __forceinline__ double quad_min_secant(double u, double du, double v, double dv) {
-    double a = u - v;
-    return v + dv / (dv - du) * a;
-}
-
-// LB:506-714 on scalars held in registers: (xt,xf,xd) best point, (yt,yf,yd) other end,
-// (tt,tf,td) trial; tt receives the new trial step.
-__device__ __forceinline__ int trial_interval(double& xt, double& xf, double& xd, double& yt, double& yf,
-                                              double& yd, double& tt, const double tf, const double td,
-                                              const double tmin, const double tmax, int& brackt) {
-    int bound;
-    const int dsign = td * (xd / fabs(xd)) < 0.;
-    double mc, mq, newt;
-    if (brackt) {
-        const double lo = xt <= yt ? xt : yt;
-        const double hi = xt >= yt ? xt : yt;
-        if (tt <= lo || hi <= tt) return LBERR_OUTOFINTERVAL;
-        if (0. <= xd * (tt - xt)) return LBERR_INCREASEGRADIENT;
-        if (tmax < tmin) return LBERR_INCORRECT_TMINMAX;
-    }
-    if (xf < tf) {
-        brackt = 1;
-        bound = 1;
-        mc = cubic_min(xt, xf, xd, tt, tf, td);
-        mq = quad_min(xt, xf, xd, tt, tf);
-        newt = (fabs(mc - xt) < fabs(mq - xt)) ? mc : mc + 0.5 * (mq - mc);
-    } else if (dsign) {
-        brackt = 1;
-        bound = 0;
-        mc = cubic_min(xt, xf, xd, tt, tf, td);
-        mq = quad_min_secant(xt, xd, tt, td);
-        newt = (fabs(mc - tt) > fabs(mq - tt)) ? mc : mq;
-    } else if (fabs(td) < fabs(xd)) {
-        bound = 1;
-        mc = cubic_min_bounded(xt, xf, xd, tt, tf, td, tmin, tmax);
-        mq = quad_min_secant(xt, xd, tt, td);
-        if (brackt) newt = (fabs(tt - mc) < fabs(tt - mq)) ? mc : mq;
-        else        newt = (fabs(tt - mc) > fabs(tt - mq)) ? mc : mq;
-    } else {
-        bound = 0;
-        if (brackt)       newt = cubic_min(tt, tf, td, yt, yf, yd);
-        else if (xt < tt) newt = tmax;
-        else              newt = tmin;
-    }
-    {
-        // LB:664-684 as value selects (pointer-style conditional copies end up in scratch)
-        const bool higher = xf < tf;
-        const bool y_from_x = !higher && dsign;
-        const double nyt = higher ? tt : (y_from_x ? xt : yt);
-        const double nyf = higher ? tf : (y_from_x ? xf : yf);
-        const double nyd = higher ? td : (y_from_x ? xd : yd);
-        const double nxt = higher ? xt : tt;
-        const double nxf = higher ? xf : tf;
-        const double nxd = higher ? xd : td;
-        xt = nxt; xf = nxf; xd = nxd;
-        yt = nyt; yf = nyf; yd = nyd;
-    }
-    if (tmax < newt) newt = tmax;
-    if (newt < tmin) newt = tmin;
-    if (brackt && bound) {
-        mq = xt + 0.66 * (yt - xt);
-        if (xt < yt) { if (mq < newt) newt = mq; }
-        else         { if (newt < mq) newt = mq; }
-    }
-    tt = newt;
-    return 0;
-}
-
 // ---- whole-solve kernel (vigo_optimize): BT.cpp:687-718 + LB:1024-1349 -------------------
 // LDS: hist[slot][ROW] of HPair<T> with ROW = TPB*(N-6) columns (each lane reads and writes only
 //      the columns of its own points: LDS is a per-lane register extension here, no cross-lane
@@ -1376,99 +1252,168 @@ __global__ void __launch_bounds__(kWave, WPS) k_optimize(SolveArgsOf<MIXED> A, c
     for (;;) {  // one trip per L-BFGS iteration; trip 0 only evaluates the start point (LB:1132)
         // ---------------- line_search_morethuente, LB:716-937 ----------------
         int ls = 0;
-        int count = 0, brackt = 0, stage1 = 1, uinfo = 0;
-        double dginit = 0.0, finit = 0.0, dgtest = 0.0, width = 0.0, prev_width = 0.0;
-        double xt = 0., xf = 0., xd = 0., yt = 0., yf = 0., yd = 0.;
-        const double stpmin = KL.min_step, stpmax = KL.max_step;
-        bool run = true;
-        if (!first) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q)
-#pragma unroll
-                for (int a = 0; a < D; ++a) { xp[q][a] = x[q][a]; gp[q][a] = g[q][a]; }  // LB:1172-1173
-            if constexpr (AXIS) xp[0][2] = x[0][2];
-            dginit = sums[4];  // g.d for the d just built (reduced at the end of the two-loop below)
-            if (step <= 0.) { ls = LBERR_INVALIDPARAMETERS; run = false; }
-            else if (0 < dginit) { ls = LBERR_INCREASEGRADIENT; run = false; }
-            finit = fx;
-            dgtest = KL.ftol * dginit;
-            width = stpmax - stpmin;
-            prev_width = 2.0 * width;
-            xt = yt = 0.;
-            xf = yf = finit;
-            xd = yd = dginit;
-        }
-        while (run) {
-            double stmin = 0., stmax = 0.;
+        if constexpr (AXIS && (VIGO_AXIS_LS_FIRST_TESTS || VIGO_AXIS_LS_FIRST_SETUP)) {
+            // The search of vigo_linesearch.hpp, the same statements as the else arm's, with the set-up of a trial moved
+            // to the end of the trial before it (still ONE evaluation site): the first trial's set-up, ahead of the loop,
+            // is then the two clamps and stmax.  Behind switches that are off (measured and rejected), a first-trial path
+            // after the evaluation — every scalar is the same in every lane, so __any() of a lane's condition is that
+            // condition and the branch the wave's.  FIRST_TESTS: the first trial's exits are the four that need no bracket.
+            // FIRST_SETUP = 1: interval ends, widths and the bracket's six doubles are formed by ls_first_reject, from the
+            // step kept as it was before the clamps.
+            constexpr bool kTests = VIGO_AXIS_LS_FIRST_TESTS, kDefer = VIGO_AXIS_LS_FIRST_SETUP == 1;
+            const LsParams P{KL.min_step, KL.max_step, KL.ftol, KL.gtol, KL.xtol, KL.max_linesearch};
+            LsState S;   // (fresh: 17 values would otherwise stay live across the two-loop, 35 more registers and AGPR copies)
+            fresh_reg(S.dginit); fresh_reg(S.finit); fresh_reg(S.dgtest); fresh_reg(S.width); fresh_reg(S.prev_width);
+            fresh_reg(S.xt); fresh_reg(S.xf); fresh_reg(S.xd); fresh_reg(S.yt); fresh_reg(S.yf); fresh_reg(S.yd);
+            fresh_reg(S.stmin); fresh_reg(S.stmax);
+            fresh_reg(S.count); fresh_reg(S.brackt); fresh_reg(S.stage1); fresh_reg(S.uinfo);
+            double step0 = step;
+            auto move_x = [&]() {   // x <- xp + step * d  (LB:824-825)
+                x[0][0] = xp[0][0] + step * d[0][0];
+                x[0][2] = xp[0][2] + step * (Q.interior[0] ? dz : 0.0);
+            };
+            bool run = true;
             if (!first) {
-                if (brackt) {
-                    stmin = xt <= yt ? xt : yt;
-                    stmax = xt >= yt ? xt : yt;
-                } else {
-                    stmin = xt;
-                    stmax = step + 4.0 * (step - xt);
+                xp[0][0] = x[0][0]; gp[0][0] = g[0][0];  // LB:1172-1173
+                xp[0][2] = x[0][2];
+                // sums[4]: g.d for the d just built (reduced at the end of the two-loop below)
+                ls = kDefer ? ls_first_begin(P, S, step, fx, sums[4]) : ls_begin(P, S, step, fx, sums[4]);
+                run = ls == 0;
+                if (run) {
+                    if constexpr (kDefer) ls_first_setup(P, step);
+                    else ls_setup(P, S, step);   // (brackt = 0, xt = 0 are constants here: the clamps and stmax are left)
+                    move_x();
                 }
-                if (step < stpmin) step = stpmin;
-                if (stpmax < step) step = stpmax;
-                if ((brackt && ((step <= stmin || stmax <= step) || KL.max_linesearch <= count + 1 || uinfo != 0)) ||
-                    (brackt && (stmax - stmin <= KL.xtol * stmax))) {
-                    step = xt;
+            }
+            while (run) {
+                VIGO_TICK(t_pre);
+                fx = eval_cost_grad_axis(KL, Q, grp, x, d, g, sums);   // the only evaluation site (LB:828, :1132)
+                VIGO_TICK(t_eval);
+                ++evals;
+                if (first) break;
+
+                const double dg = sums[4];
+                const double ftest1 = ls_ftest1(S, step);
+                ++S.count;
+                if ((kTests || kDefer) && S.count == 1) {   // a scalar branch
+                    if constexpr (kTests) {
+                        const int code = ls_first_exit_code(P, S, step, fx, dg, ftest1);
+                        if (__any(code != 0)) { ls = code; break; }
+                    }
+                    if constexpr (kDefer) {
+                        hold_in_reg(step0);   // keeps the state behind the branch
+                        ls_first_reject(P, S, step0);
+                        // (... and its copies out of the block the accepted trial leaves through)
+                        hold_in_reg(S.xt); hold_in_reg(S.xf); hold_in_reg(S.xd); hold_in_reg(S.yt); hold_in_reg(S.yf); hold_in_reg(S.yd);
+                        hold_in_reg(S.width); hold_in_reg(S.prev_width); hold_in_reg(S.stmin); hold_in_reg(S.stmax);
+                        hold_in_reg(S.brackt); hold_in_reg(S.stage1); hold_in_reg(S.uinfo);
+                    }
                 }
-                // x <- xp + step * d  (LB:824-825)
+                if (!kTests || S.count != 1) {
+                    const int code = ls_exit_code(P, S, step, fx, dg, ftest1);
+                    if (code != 0) { ls = code; break; }
+                }
+                VIGO_TICK(t_ls);
+                ls_update(P, S, step, fx, dg, ftest1);
+                VIGO_TICK(t_trial);
+                ls_setup(P, S, step);
+                move_x();
+            }
+        } else {
+            int count = 0, brackt = 0, stage1 = 1, uinfo = 0;
+            double dginit = 0.0, finit = 0.0, dgtest = 0.0, width = 0.0, prev_width = 0.0;
+            double xt = 0., xf = 0., xd = 0., yt = 0., yf = 0., yd = 0.;
+            const double stpmin = KL.min_step, stpmax = KL.max_step;
+            bool run = true;
+            if (!first) {
 #pragma unroll
                 for (int q = 0; q < PPL; ++q)
 #pragma unroll
-                    for (int a = 0; a < D; ++a)
-                        x[q][a] = FAST ? fmaT((T)step, d[q][a], xp[q][a]) : xp[q][a] + (T)step * d[q][a];
-                if constexpr (AXIS) x[0][2] = xp[0][2] + (T)step * (Q.interior[0] ? dz : T(0));
+                    for (int a = 0; a < D; ++a) { xp[q][a] = x[q][a]; gp[q][a] = g[q][a]; }  // LB:1172-1173
+                if constexpr (AXIS) xp[0][2] = x[0][2];
+                dginit = sums[4];  // g.d for the d just built (reduced at the end of the two-loop below)
+                if (step <= 0.) { ls = LBERR_INVALIDPARAMETERS; run = false; }
+                else if (0 < dginit) { ls = LBERR_INCREASEGRADIENT; run = false; }
+                finit = fx;
+                dgtest = KL.ftol * dginit;
+                width = stpmax - stpmin;
+                prev_width = 2.0 * width;
+                xt = yt = 0.;
+                xf = yf = finit;
+                xd = yd = dginit;
             }
+            while (run) {
+                double stmin = 0., stmax = 0.;
+                if (!first) {
+                    if (brackt) {
+                        stmin = xt <= yt ? xt : yt;
+                        stmax = xt >= yt ? xt : yt;
+                    } else {
+                        stmin = xt;
+                        stmax = step + 4.0 * (step - xt);
+                    }
+                    if (step < stpmin) step = stpmin;
+                    if (stpmax < step) step = stpmax;
+                    if ((brackt && ((step <= stmin || stmax <= step) || KL.max_linesearch <= count + 1 || uinfo != 0)) ||
+                        (brackt && (stmax - stmin <= KL.xtol * stmax))) {
+                        step = xt;
+                    }
+                    // x <- xp + step * d  (LB:824-825)
+#pragma unroll
+                    for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                        for (int a = 0; a < D; ++a)
+                            x[q][a] = FAST ? fmaT((T)step, d[q][a], xp[q][a]) : xp[q][a] + (T)step * d[q][a];
+                    if constexpr (AXIS) x[0][2] = xp[0][2] + (T)step * (Q.interior[0] ? dz : T(0));
+                }
 
-            VIGO_TICK(t_pre);
-            // the only evaluation site (LB:828, :1132)
-            if constexpr (AXIS) fx = eval_cost_grad_axis(KL, Q, grp, x, d, g, sums);
-            else fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(KL, Q, x, d, g, sums);
-            VIGO_TICK(t_eval);
-            ++evals;
-            if (first) break;
+                VIGO_TICK(t_pre);
+                // the only evaluation site (LB:828, :1132)
+                if constexpr (AXIS) fx = eval_cost_grad_axis(KL, Q, grp, x, d, g, sums);
+                else fx = eval_cost_grad<T, GROUP, PPL, FAST, OBS, D>(KL, Q, x, d, g, sums);
+                VIGO_TICK(t_eval);
+                ++evals;
+                if (first) break;
 
-            const double dg = sums[4];
-            const double ftest1 = finit + step * dgtest;
-            ++count;
+                const double dg = sums[4];
+                const double ftest1 = finit + step * dgtest;
+                ++count;
 
-            // LB:832-866: six exits tested in order, the first that holds wins.  Evaluated as one select chain
-            // in reverse order and ONE branch (six exec-mask branches cost more issue slots than the compares)
-            {
-                int code = 0;
-                if (fx <= ftest1 && fabs(dg) <= KL.gtol * (-dginit)) code = count;                      // LB:862-866 (count >= 1)
-                if (KL.max_linesearch <= count) code = LBERR_MAXIMUMLINESEARCH;                         // LB:857-860
-                if (brackt && (stmax - stmin) <= KL.xtol * stmax) code = LBERR_WIDTHTOOSMALL;           // LB:852-855
-                if (step == stpmin && (ftest1 < fx || dgtest <= dg)) code = LBERR_MINIMUMSTEP;         // LB:847-850
-                if (step == stpmax && fx <= ftest1 && dg <= dgtest) code = LBERR_MAXIMUMSTEP;          // LB:842-845
-                if (brackt && ((step <= stmin || stmax <= step) || uinfo != 0)) code = LBERR_ROUNDING_ERROR;   // LB:837-840
-                if (code != 0) { ls = code; break; }
-            }
+                // LB:832-866: six exits tested in order, the first that holds wins.  Evaluated as one select chain
+                // in reverse order and ONE branch (six exec-mask branches cost more issue slots than the compares)
+                {
+                    int code = 0;
+                    if (fx <= ftest1 && fabs(dg) <= KL.gtol * (-dginit)) code = count;                      // LB:862-866 (count >= 1)
+                    if (KL.max_linesearch <= count) code = LBERR_MAXIMUMLINESEARCH;                         // LB:857-860
+                    if (brackt && (stmax - stmin) <= KL.xtol * stmax) code = LBERR_WIDTHTOOSMALL;           // LB:852-855
+                    if (step == stpmin && (ftest1 < fx || dgtest <= dg)) code = LBERR_MINIMUMSTEP;         // LB:847-850
+                    if (step == stpmax && fx <= ftest1 && dg <= dgtest) code = LBERR_MAXIMUMSTEP;          // LB:842-845
+                    if (brackt && ((step <= stmin || stmax <= step) || uinfo != 0)) code = LBERR_ROUNDING_ERROR;   // LB:837-840
+                    if (code != 0) { ls = code; break; }
+                }
 
-            const double cmin = KL.ftol <= KL.gtol ? KL.ftol : KL.gtol;
-            if (stage1 && fx <= ftest1 && cmin * dginit <= dg) stage1 = 0;
+                const double cmin = KL.ftol <= KL.gtol ? KL.ftol : KL.gtol;
+                if (stage1 && fx <= ftest1 && cmin * dginit <= dg) stage1 = 0;
 
-            // LB:883-920: the interval update runs on the modified function while stage1 holds and
-            // the decrease is insufficient; one call site, operands selected here.
-            const bool mod = stage1 && ftest1 < fx && fx <= xf;
-            double axf = mod ? xf - xt * dgtest : xf, axd = mod ? xd - dgtest : xd;
-            double ayf = mod ? yf - yt * dgtest : yf, ayd = mod ? yd - dgtest : yd;
-            const double atf = mod ? fx - step * dgtest : fx, atd = mod ? dg - dgtest : dg;
-            VIGO_TICK(t_ls);
-            uinfo = trial_interval(xt, axf, axd, yt, ayf, ayd, step, atf, atd, stmin, stmax, brackt);
-            VIGO_TICK(t_trial);
-            xf = mod ? axf + xt * dgtest : axf;
-            yf = mod ? ayf + yt * dgtest : ayf;
-            xd = mod ? axd + dgtest : axd;
-            yd = mod ? ayd + dgtest : ayd;
+                // LB:883-920: the interval update runs on the modified function while stage1 holds and
+                // the decrease is insufficient; one call site, operands selected here.
+                const bool mod = stage1 && ftest1 < fx && fx <= xf;
+                double axf = mod ? xf - xt * dgtest : xf, axd = mod ? xd - dgtest : xd;
+                double ayf = mod ? yf - yt * dgtest : yf, ayd = mod ? yd - dgtest : yd;
+                const double atf = mod ? fx - step * dgtest : fx, atd = mod ? dg - dgtest : dg;
+                VIGO_TICK(t_ls);
+                uinfo = trial_interval(xt, axf, axd, yt, ayf, ayd, step, atf, atd, stmin, stmax, brackt);
+                VIGO_TICK(t_trial);
+                xf = mod ? axf + xt * dgtest : axf;
+                yf = mod ? ayf + yt * dgtest : ayf;
+                xd = mod ? axd + dgtest : axd;
+                yd = mod ? ayd + dgtest : ayd;
 
-            if (brackt) {
-                if (0.66 * prev_width <= fabs(yt - xt)) step = xt + 0.5 * (yt - xt);
-                prev_width = width;
-                width = fabs(yt - xt);
+                if (brackt) {
+                    if (0.66 * prev_width <= fabs(yt - xt)) step = xt + 0.5 * (yt - xt);
+                    prev_width = width;
+                    width = fabs(yt - xt);
+                }
             }
         }
 
