@@ -47,7 +47,7 @@ def kernels(obj):   # demangled kernel name -> (instructions, digest)
             close()
             # "void vigo::(anonymous namespace)::k_x<...>(vigo::SolveArgs, ...)" -> "k_x<...>"
             name, body = re.sub(r"^void vigo::\(anonymous namespace\)::|\((vigo::SolveArgs|std::conditional<).*$", "", m.group(1)), []
-        elif name and line.strip():
+        elif name and line.strip() and line.strip() != "...":   # ("...": zero fill up to the next symbol's alignment, no code)
             body.append(re.sub(r"\s*//.*$", "", line).strip())   # (the comment holds the address and the encoding)
     close()
     return out

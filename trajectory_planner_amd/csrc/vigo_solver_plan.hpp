@@ -158,6 +158,28 @@ inline OptimizePlan plan_optimize(int N, int B, int precision, bool has_obstacle
     return p;
 }
 
+// ---- the two launches of a small batch as one (k_optimize_fused) --------------------------------------------------
+// A plan whose FIRST launch is the axis-per-lane kernel (D = 1; then the second is the general kernel of 32 x 1 with
+// level_waves_elsewhere == 2, and B <= simd_count) runs as ONE launch of k_optimize_fused: B one-wave workgroups, each
+// classifies its trajectory once and runs the axis body on a level one, the general body on any other, alone on lanes
+// 0 .. 31.  Every other plan runs as planned.  A rule over the plan: plan_optimize, kOptimizeKeys and the bits of the
+// "LDS limit raised" mask stay as they are; the fused kernel is no row of a table (one instantiation, vigo_solver.hip).
+// LDS of the general body on ONE trajectory of N <= 32 control points, fp64 reference order, no obstacle table: per
+// history slot in LDS (m - 2 of them) one 48-byte record per free control point plus the zero column and {ys, 1/ys},
+// then m alphas — 14 x (27 x 48 + 16) + 128 = 18 496 B at N = 32, m = 16.
+constexpr size_t solo_lds_bytes(int N, int m) {
+    const int ms = m > 2 ? m - 2 : 0;
+    return (size_t)ms * (((size_t)(N - 6) + 1) * hpair_bytes(8, 3) + ysv_bytes(false)) + (size_t)m * sizeof(double);
+}
+// fuse: the plan's launches run as one; grid workgroups of one wave with lds bytes, the larger of the two bodies' layouts
+// (at most kLdsPerWorkgroup / 8 for every N <= 32 and mem_size <= kMaxMem: two batches in flight keep two waves on a SIMD)
+struct FusedLaunch { bool fuse; int grid; size_t lds; };
+inline FusedLaunch fuse_optimize(const OptimizePlan& p, int N, int mem_size) {
+    if (p.count != 2 || kOptimizeKeys[p.launch[0].key].d != 1) return FusedLaunch{false, 0, 0};
+    const size_t axis = p.launch[0].lds, solo = solo_lds_bytes(N, mem_size);
+    return FusedLaunch{true, p.launch[0].grid, axis > solo ? axis : solo};
+}
+
 // ---- mixed control-point counts (vigo_*_mixed) --------------------------------------------------------------------
 // k_optimize<.., MIXED = true>: trajectories of different counts in one launch, rows strided by Ns.  Only the general
 // kernel (D = 3, OBS) is built that way — it treats a missing obstacle list as no obstacles and solves a level trajectory
