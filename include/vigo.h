@@ -129,7 +129,8 @@ int vigo_set_precision(vigo_handle_t h, int vigo_precision);
 const char* vigo_last_error(vigo_handle_t h);
 /* Library/ABI version (raised when entry points are added; nothing was removed or changed so far: 4 adds
  * vigo_build_esdf / vigo_esdf_from_voxels_host; vigo_seed_capacity / vigo_seed_paths / vigo_seed_paths_host came in at 4
- * as well, and so did vigo_bspline_fit_mixed and then vigo_traj_finish / vigo_traj_finish_host after them — ask the library for the symbol), and whether the code object was built for gfx950. */
+ * as well, and so did vigo_bspline_fit_mixed, then vigo_traj_finish / vigo_traj_finish_host, then vigo_build_esdf_tracked / vigo_update_esdf and
+ * their host twins after them — ask the library for the symbol), and whether the code object was built for gfx950. */
 int vigo_abi_version(void);
 const char* vigo_build_arch(void);
 /* "solver:<12 hex> all:<12 hex>": digests of the library's compiled code (host code and gfx950 code objects; the first
@@ -180,7 +181,9 @@ int vigo_set_metric_bounds(vigo_handle_t h, const double bmin[3], const double b
  *     before the call it is so afterwards: the result of vigo_inflate_grid + vigo_set_grid on the whole updated grid,
  *     for work proportional to the box grown by 2r.
  * Untouched: grid dims, origin and res, the bounds of vigo_set_metric_bounds, the cached sample times — and the
- * handle's ESDF: a field built by vigo_build_esdf is STALE until it is built again.
+ * handle's ESDF: a field built by vigo_build_esdf is STALE until it is built again.  After vigo_build_esdf_tracked the
+ * box joins the handle's pending box instead, and vigo_update_esdf refreshes the field for work that follows the change
+ * (see "ESDF region update" below).
  * Errors (nothing is written): VIGO_ERR_INVALID_ARG — NULL handle, lo, n or voxels, a negative lo, n or radius, lo + n
  * beyond the grid; VIGO_ERR_NO_GRID — before any vigo_set_grid*; VIGO_ERR_UNSUPPORTED — rz > 31 (vigo_inflate_grid's
  * limit).  An n[a] == 0 is VIGO_OK with nothing launched. */
@@ -981,6 +984,49 @@ int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_
  * Nothing is written on an error. */
 int vigo_esdf_from_voxels_host(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site,
                                double res, float* out_lattice_host);
+
+/* ---- ESDF region update (no reference counterpart; DESIGN.md §3.5b "Region update") ------
+ * vigo_build_esdf_tracked is vigo_build_esdf — the same arguments, codes, lattice bits and installed field — and KEEPS
+ * what an update needs in a handle buffer of its own: the z-pass and y-pass results (int32 each), the row-major float
+ * lattice, two byte flags per line and two counters.  That is 12 bytes per voxel plus nx * nz + ny * nz flag bytes:
+ * 201 MB (192 MiB) at 256^3 and 1.6 GB (1.5 GiB) at 512^3, grown on demand, freed by vigo_destroy; vigo_build_esdf's own
+ * workspace is not used.  From this call on the handle is TRACKING: it remembers plane and unknown_is_site and holds a
+ * PENDING BOX, host integers, empty after the build.
+ *   While tracking, vigo_update_grid_region and vigo_update_grid_region_host add their box to the pending box as a
+ *   bounding-box union — with inflate_r the box grown by r and clipped to the grid, which covers every plane the call may
+ *   have changed; an n[a] == 0 adds nothing.  Nothing those entries launch or return changes.  ONE bounding box, not a
+ *   list: a caller with far-apart boxes calls vigo_update_esdf between them.
+ *   Tracking ends with vigo_set_grid, vigo_set_grid_host, vigo_set_grid_packed, vigo_build_esdf, vigo_set_esdf and a failed
+ *   allocation of the tracking buffer; not with parameters, metric bounds, the stream or the precision.
+ * vigo_update_esdf brings the kept results, the lattice and the installed field to what vigo_build_esdf_tracked would
+ * produce on the current snapshot, bit for bit, and clears the pending box.  The transform is separable: a y line depends
+ * on its own z-pass line only, an x line on its own y-pass line only, so only lines whose input changed are recomputed —
+ * no truncation radius, no approximation.  Work: the z pass over the box' footprint columns, the y pass over the box'
+ * slab of x where the z pass changed a value, the x pass and the re-tiling on the (y, z) lines where the y pass changed
+ * one — at most one whole x pass (a site added to an empty column changes whole y lines: DESIGN.md §3.5b).  Stream-ordered
+ * on the handle's stream.
+ *   out_lattice_dev  float[nx][ny][nz] or NULL: the whole row-major lattice is also copied there
+ *   stats            NULL, or filled after a synchronise of the stream (without it the call makes no host round trip):
+ *                    the pending box the call worked on and the lines the y pass and the x pass recomputed
+ * Errors: VIGO_ERR_INVALID_ARG for a NULL handle; VIGO_ERR_NO_GRID, with a vigo_last_error text, when the handle is not
+ * tracking.  An empty pending box is VIGO_OK with nothing launched but the optional copy; the stats are then zeros. */
+typedef struct {
+    int32_t box_lo[3], box_n[3];   /* the pending box this call worked on (n = 0: nothing pending) */
+    int64_t y_lines, x_lines;      /* lines recomputed by the y pass / the x pass */
+} vigo_esdf_update_stats_t;
+int vigo_build_esdf_tracked(vigo_handle_t h, int plane, int unknown_is_site, float* out_lattice_dev);
+int vigo_update_esdf(vigo_handle_t h, float* out_lattice_dev, vigo_esdf_update_stats_t* stats_or_NULL);
+/* The host twins (no GPU, no handle; csrc/vigo_esdf_core.hpp compiled for the CPU).  _tracked: vigo_esdf_from_voxels_host
+ * with the z-pass and y-pass results in a_out, b_out (int32[nx][ny][nz] each).  vigo_esdf_update_host: a, b and the
+ * lattice of the grid BEFORE the box [lo, lo + n) changed become those of new_voxels_host, the whole byte grid after it;
+ * for a pending box of several updates pass their bounding box.  Codes as vigo_esdf_from_voxels_host; also
+ * VIGO_ERR_INVALID_ARG for a NULL lo, n, a, b or lattice, a negative lo or n, lo + n beyond the lattice.  An n[a] == 0 is
+ * VIGO_OK, nothing changes and the stats are zeros.  Nothing is written on an error. */
+int vigo_esdf_from_voxels_host_tracked(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site,
+                                       double res, int32_t* a_out, int32_t* b_out, float* out_lattice_host);
+int vigo_esdf_update_host(int nx, int ny, int nz, const uint8_t* new_voxels_host, int plane, int unknown_is_site,
+                          double res, const int32_t lo[3], const int32_t n[3], int32_t* a_inout, int32_t* b_inout,
+                          float* lattice_inout, vigo_esdf_update_stats_t* stats_or_NULL);
 
 #ifdef __cplusplus
 }

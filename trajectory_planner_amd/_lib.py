@@ -43,6 +43,15 @@ class VigoParams(C.Structure):
     ]
 
 
+class VigoEsdfUpdateStats(C.Structure):
+    """vigo_esdf_update_stats_t (include/vigo.h)."""
+
+    _fields_ = [("box_lo", C.c_int32 * 3), ("box_n", C.c_int32 * 3), ("y_lines", C.c_int64), ("x_lines", C.c_int64)]
+
+    def as_dict(self):
+        return {"box_lo": tuple(self.box_lo), "box_n": tuple(self.box_n), "y_lines": int(self.y_lines), "x_lines": int(self.x_lines)}
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _i64 = C.c_int64
@@ -119,6 +128,10 @@ PROTOTYPES = {
     "vigo_esdf_query_f32": (_i, [_vp, _i64, _vp, _vp]),
     "vigo_build_esdf": (_i, [_vp, _i, _i, _vp]),
     "vigo_esdf_from_voxels_host": (_i, [_i, _i, _i, _vp, _i, _i, _d, _vp]),
+    "vigo_build_esdf_tracked": (_i, [_vp, _i, _i, _vp]),
+    "vigo_update_esdf": (_i, [_vp, _vp, C.POINTER(VigoEsdfUpdateStats)]),
+    "vigo_esdf_from_voxels_host_tracked": (_i, [_i, _i, _i, _vp, _i, _i, _d, _vp, _vp, _vp]),
+    "vigo_esdf_update_host": (_i, [_i, _i, _i, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, C.POINTER(VigoEsdfUpdateStats)]),
 }
 
 _lib = None

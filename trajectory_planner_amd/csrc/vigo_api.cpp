@@ -54,7 +54,7 @@ int fail(vigo_handle_t h, int code, const char* what, hipError_t e = hipSuccess)
 // not kept).  A failed allocation leaves it empty.  Callers whose cache lives in the buffer invalidate it first.
 int reserve(vigo_handle_t h, vigo::BufId id, size_t need, size_t alloc) {
     static const char* const what[] = {
-        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(finish_ts)", "hipMalloc(finish_dt)", "hipMalloc(scratch)",
+        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(esdf_track)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(finish_ts)", "hipMalloc(finish_dt)", "hipMalloc(scratch)",
         "hipMalloc(paths_ws[0])", "hipMalloc(paths_ws[1])", "hipMalloc(reguide_ws[0])", "hipMalloc(reguide_ws[1])",
         "hipMalloc(reguide_ws[2])", "hipMalloc(rebound)"};
     static_assert(sizeof(what) / sizeof(what[0]) == vigo::kBufCount, "one name per BufId, in its order");
@@ -313,6 +313,37 @@ int install_esdf(vigo_handle_t h, int nx, int ny, int nz, const double origin[3]
     return VIGO_OK;
 }
 
+// the checks vigo_build_esdf and vigo_build_esdf_tracked share
+int check_esdf_build(vigo_handle_t h, const char* who, int plane) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (std::string(who) + " before vigo_set_grid").c_str());
+    const GridView& g = h->grid;
+    if ((plane != 0 && plane != 2) || g.nx < 2 || g.ny < 2 || g.nz < 2)
+        return fail(h, VIGO_ERR_INVALID_ARG, (std::string(who) + ": plane is not 0 or 2, or a grid axis < 2").c_str());
+    if (vigo::esdf_empty_d2(g.nx, g.ny, g.nz) == 0)
+        return fail(h, VIGO_ERR_UNSUPPORTED, (std::string(who) + ": nx^2 + ny^2 + nz^2 > 2^30 or more than 2^33 voxels").c_str());
+    return VIGO_OK;
+}
+
+// tracking ends where the snapshot or the field stops being what vigo_build_esdf_tracked left and the updates kept
+void end_esdf_tracking(vigo_handle_t h) {
+    h->esdf_tracking = false;
+    for (int a = 0; a < 3; ++a) h->esdf_pending_lo[a] = h->esdf_pending_n[a] = 0;
+}
+
+// a region update's box [lo, e) joins the pending box: the bounding box of both
+void add_pending_box(vigo_handle_t h, const int lo[3], const int e[3]) {
+    int32_t* plo = h->esdf_pending_lo;
+    int32_t* pn = h->esdf_pending_n;
+    const bool empty = pn[0] == 0;
+    for (int a = 0; a < 3; ++a) {
+        const int a0 = empty || lo[a] < plo[a] ? lo[a] : plo[a];
+        const int e0 = empty || e[a] > plo[a] + pn[a] ? e[a] : plo[a] + pn[a];
+        plo[a] = a0;
+        pn[a] = e0 - a0;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -521,6 +552,7 @@ int vigo_inflate_grid(vigo_handle_t h, int nx, int ny, int nz, uint8_t* voxels_d
 
 int vigo_set_grid(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const uint8_t* voxels_dev) {
     if (!h || !voxels_dev || !origin || nx <= 0 || ny <= 0 || nz <= 0 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_grid: bad argument");
+    end_esdf_tracking(h);
     VIGO_TRY(ensure_grid_storage(h, nx, ny, nz));
     VIGO_HIP(h, (hipError_t)vigo::launch_pack_grid(h->stream, nx, ny, nz, voxels_dev, h->buf[vigo::kBufGrid].as<uint32_t>()));
     fill_grid_view(h, nx, ny, nz, origin, res);
@@ -540,6 +572,7 @@ int vigo_set_grid_host(vigo_handle_t h, int nx, int ny, int nz, const double ori
 
 int vigo_set_grid_packed(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const uint32_t* packed_dev) {
     if (!h || !packed_dev || !origin || nx <= 0 || ny <= 0 || nz <= 0 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_grid_packed: bad argument");
+    end_esdf_tracking(h);
     VIGO_TRY(ensure_grid_storage(h, nx, ny, nz));
     VIGO_HIP(h, hipMemcpyAsync(h->buf[vigo::kBufGrid].ptr, packed_dev, vigo_grid_packed_bytes(nx, ny, nz), hipMemcpyDeviceToDevice, h->stream));
     fill_grid_view(h, nx, ny, nz, origin, res);
@@ -566,6 +599,10 @@ int update_grid_region(vigo_handle_t h, const char* who, const int32_t lo[3], co
     if (rc == vigo::kRegionUnsupported) return fail(h, VIGO_ERR_UNSUPPORTED, (std::string(who) + ": rz > 31 voxels").c_str());
     if (rc == vigo::kRegionEmpty) return VIGO_OK;
     const vigo::RegionPlan p = vigo::region_plan(g.nx, g.ny, g.nz, lo, n, r);
+    if (h->esdf_tracking) {                   // host bookkeeping for vigo_update_esdf: every plane this call may change
+        const int box_e[3] = {lo[0] + n[0], lo[1] + n[1], lo[2] + n[2]};
+        add_pending_box(h, r ? p.a1 : p.lo, r ? p.e1 : box_e);
+    }
     const size_t bytes = (size_t)n[0] * n[1] * n[2];
     uint8_t* staged;
     uint32_t *planeA, *planeB;
@@ -1314,17 +1351,14 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
 int vigo_set_esdf(vigo_handle_t h, int nx, int ny, int nz, const double origin[3], double res, const float* dist_dev) {
     if (!h || !dist_dev || !origin || nx < 2 || ny < 2 || nz < 2 || !geometry_ok(origin, res)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_esdf: bad argument");
     if ((long long)nx * ny * nz > (1LL << 33)) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_set_esdf: lattice too large");
+    end_esdf_tracking(h);
     return install_esdf(h, nx, ny, nz, origin, res, dist_dev);
 }
 
 int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_lattice_dev) {
-    if (!h) return VIGO_ERR_INVALID_ARG;
-    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_build_esdf before vigo_set_grid");
+    VIGO_TRY(check_esdf_build(h, "vigo_build_esdf", plane));
+    end_esdf_tracking(h);
     const GridView& g = h->grid;
-    if ((plane != 0 && plane != 2) || g.nx < 2 || g.ny < 2 || g.nz < 2)
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_build_esdf: plane is not 0 or 2, or a grid axis < 2");
-    if (vigo::esdf_empty_d2(g.nx, g.ny, g.nz) == 0)
-        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_build_esdf: nx^2 + ny^2 + nz^2 > 2^30 or more than 2^33 voxels");
     const size_t voxels = (size_t)g.nx * g.ny * g.nz;
     int32_t *a, *b;
     VIGO_TRY(carve(h, vigo::kBufEsdfWs, kExact, [&](void* p) { return vigo::ws_pair(p, voxels, a, b); }));   // = esdf_build_ws_bytes(): 1 GiB at 512^3
@@ -1333,9 +1367,72 @@ int vigo_build_esdf(vigo_handle_t h, int plane, int unknown_is_site, float* out_
     return install_esdf(h, g.nx, g.ny, g.nz, g.origin, g.res, lattice);
 }
 
+int vigo_build_esdf_tracked(vigo_handle_t h, int plane, int unknown_is_site, float* out_lattice_dev) {
+    VIGO_TRY(check_esdf_build(h, "vigo_build_esdf_tracked", plane));
+    end_esdf_tracking(h);                                         // until everything below is in place
+    const GridView& g = h->grid;
+    const size_t voxels = (size_t)g.nx * g.ny * g.nz;
+    vigo::EsdfTrackWs& w = h->esdf_track;
+    VIGO_TRY(carve(h, vigo::kBufEsdfTrack, kExact,
+                   [&](void* p) { return vigo::ws_esdf_track(p, voxels, (size_t)g.nx * g.nz, (size_t)g.ny * g.nz, w); }));
+    VIGO_HIP(h, (hipError_t)vigo::launch_esdf_build(h->stream, g, plane, unknown_is_site != 0, w.a, w.b, w.lattice));
+    if (out_lattice_dev) VIGO_HIP(h, hipMemcpyAsync(out_lattice_dev, w.lattice, voxels * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    VIGO_TRY(install_esdf(h, g.nx, g.ny, g.nz, g.origin, g.res, w.lattice));
+    h->esdf_tracking = true;
+    h->esdf_track_plane = plane;
+    h->esdf_track_unknown = unknown_is_site != 0;
+    return VIGO_OK;
+}
+
+int vigo_update_esdf(vigo_handle_t h, float* out_lattice_dev, vigo_esdf_update_stats_t* stats) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (!h->esdf_tracking) return fail(h, VIGO_ERR_NO_GRID, "vigo_update_esdf: the handle is not tracking (no vigo_build_esdf_tracked since the last whole-snapshot call, vigo_build_esdf or vigo_set_esdf)");
+    const GridView& g = h->grid;
+    const vigo::EsdfTrackWs& w = h->esdf_track;
+    if (stats) *stats = vigo_esdf_update_stats_t{};
+    const bool pending = h->esdf_pending_n[0] != 0;
+    if (pending) {
+        if (stats)
+            for (int a = 0; a < 3; ++a) { stats->box_lo[a] = h->esdf_pending_lo[a]; stats->box_n[a] = h->esdf_pending_n[a]; }
+        VIGO_HIP(h, (hipError_t)vigo::launch_esdf_region_update(h->stream, g, h->esdf_pending_lo, h->esdf_pending_n, h->esdf_track_plane,
+                                                                h->esdf_track_unknown, w, h->buf[vigo::kBufEsdf].as<float>(), stats != nullptr));
+        for (int a = 0; a < 3; ++a) h->esdf_pending_lo[a] = h->esdf_pending_n[a] = 0;
+    }
+    if (out_lattice_dev)
+        VIGO_HIP(h, hipMemcpyAsync(out_lattice_dev, w.lattice, (size_t)g.nx * g.ny * g.nz * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (stats && pending) {
+        unsigned long long counts[2];
+        VIGO_TRY(read_back(h, counts, w.counters, sizeof counts));
+        stats->y_lines = (int64_t)counts[0];
+        stats->x_lines = (int64_t)counts[1];
+    }
+    return VIGO_OK;
+}
+
 int vigo_esdf_from_voxels_host(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site, double res,
                                float* out_lattice_host) {
     return vigo::esdf_from_voxels(nx, ny, nz, voxels_host, plane, unknown_is_site, res, out_lattice_host);
+}
+
+int vigo_esdf_from_voxels_host_tracked(int nx, int ny, int nz, const uint8_t* voxels_host, int plane, int unknown_is_site, double res,
+                                       int32_t* a_out, int32_t* b_out, float* out_lattice_host) {
+    return vigo::esdf_from_voxels_tracked(nx, ny, nz, voxels_host, plane, unknown_is_site, res, a_out, b_out, out_lattice_host);
+}
+
+int vigo_esdf_update_host(int nx, int ny, int nz, const uint8_t* new_voxels_host, int plane, int unknown_is_site, double res,
+                          const int32_t lo[3], const int32_t n[3], int32_t* a_inout, int32_t* b_inout, float* lattice_inout,
+                          vigo_esdf_update_stats_t* stats) {
+    int64_t y_lines = 0, x_lines = 0;
+    const int rc = vigo::esdf_update(nx, ny, nz, new_voxels_host, plane, unknown_is_site, res, lo, n, a_inout, b_inout, lattice_inout,
+                                     &y_lines, &x_lines);
+    if (rc != 0 || !stats) return rc;
+    *stats = vigo_esdf_update_stats_t{};
+    if (n[0] != 0 && n[1] != 0 && n[2] != 0) {
+        for (int a = 0; a < 3; ++a) { stats->box_lo[a] = lo[a]; stats->box_n[a] = n[a]; }
+        stats->y_lines = y_lines;
+        stats->x_lines = x_lines;
+    }
+    return rc;
 }
 
 int vigo_esdf_query(vigo_handle_t h, int64_t Q, const double* pts, double* out_dist, double* out_grad) {

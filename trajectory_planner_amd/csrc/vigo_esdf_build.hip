@@ -16,6 +16,18 @@
 //
 // Workspace: two int32 buffers of nx * ny * nz (8 bytes per voxel); the float lattice reuses the first when the caller
 // wants none.  It belongs to the handle (vigo_api.cpp: vigo_build_esdf grows it, vigo_destroy frees it).
+//
+// vigo_update_esdf (launch_esdf_region_update): after a box of the snapshot changed, the same three passes on the lines
+// the change reaches, on the A, B and lattice a tracked build kept — flags, not lists, say which lines (the rule and its
+// per-thread functions: vigo_esdf_core.hpp, "Region update") — and the bricked field's values on those lines rewritten:
+//
+//   k_esdf_region_z      box footprint x nz threads; a value that differs from A is stored and flags its y line
+//   k_esdf_region_y      box slab x ny x nz threads; flagged lines only; a value that differs from B flags its x line
+//   k_esdf_region_x      the whole lattice; flagged lines only, the output value into the lattice
+//   k_esdf_region_brick  the whole bricked field; the values whose source is on a flagged x line
+//
+// The count of flagged lines is known to the device only, so the last two launch over everything and unflagged waves
+// leave at once: no host round trip, the same one route.
 #include "vigo_esdf_core.hpp"
 #include "vigo_internal.hpp"
 
@@ -48,7 +60,55 @@ __global__ void __launch_bounds__(kEsdfBlock) k_esdf_line(size_t total, size_t s
     else out[v] = s;
 }
 
+// the region update: one region function of vigo_esdf_core.hpp per thread; t runs z fastest in all four, so a wave's
+// flag bytes, values and stores are consecutive along z, and a wave whose lanes are all unflagged leaves after one load
+__global__ void __launch_bounds__(kEsdfRegionBlock) k_esdf_region_z(EsdfRegion r, const uint32_t* __restrict__ site_plane,
+                                                                    const uint32_t* __restrict__ unk_plane, int32_t* __restrict__ a,
+                                                                    uint8_t* __restrict__ fy) {
+    esdf_region_z(r, (size_t)blockIdx.x * kEsdfRegionBlock + threadIdx.x, site_plane, unk_plane, a, fy);
+}
+__global__ void __launch_bounds__(kEsdfRegionBlock) k_esdf_region_y(EsdfRegion r, const int32_t* __restrict__ a, int32_t* __restrict__ b,
+                                                                    const uint8_t* __restrict__ fy, uint8_t* __restrict__ fx) {
+    esdf_region_y(r, (size_t)blockIdx.x * kEsdfRegionBlock + threadIdx.x, a, b, fy, fx);
+}
+__global__ void __launch_bounds__(kEsdfRegionBlock) k_esdf_region_x(EsdfRegion r, const int32_t* __restrict__ b, float* __restrict__ lattice,
+                                                                    const uint8_t* __restrict__ fx, double res) {
+    esdf_region_x(r, (size_t)blockIdx.x * kEsdfRegionBlock + threadIdx.x, b, lattice, fx, res);
+}
+__global__ void __launch_bounds__(kEsdfRegionBlock) k_esdf_region_brick(EsdfRegion r, int nby, int nbz, const uint8_t* __restrict__ fx,
+                                                                        const float* __restrict__ lattice, float* __restrict__ bricked) {
+    esdf_region_brick(r, (size_t)blockIdx.x * kEsdfRegionBlock + threadIdx.x, nby, nbz, fx, lattice, bricked);
+}
+// the set flags among n, added to *count: one ballot and one atomic add per wave (only when the caller asked for stats)
+__global__ void __launch_bounds__(kEsdfRegionBlock) k_esdf_flag_count(const uint8_t* __restrict__ flags, size_t n, unsigned long long* count) {
+    const size_t t = (size_t)blockIdx.x * kEsdfRegionBlock + threadIdx.x;
+    const unsigned long long set = __ballot(t < n && flags[t] != 0);
+    if ((threadIdx.x & 63) == 0 && set) atomicAdd(count, (unsigned long long)__popcll(set));
+}
+
 }  // namespace
+
+int launch_esdf_region_update(hipStream_t s, const GridView& g, const int32_t lo[3], const int32_t n[3], int plane, int unknown_is_site,
+                              const EsdfTrackWs& w, float* bricked, bool count) {
+    const EsdfRegion r = esdf_region(g.nx, g.ny, g.nz, lo, n);
+    if (r.E == 0) return (int)hipErrorInvalidValue;
+    const size_t n_fy = (size_t)n[0] * g.nz, n_fx = (size_t)g.ny * g.nz;
+    const hipError_t e = hipMemsetAsync(w.counters, 0, w.clear_bytes, s);   // the counts and both flag arrays, ahead of the passes
+    if (e != hipSuccess) return (int)e;
+    const dim3 block(kEsdfRegionBlock);
+    const auto grid = [](size_t threads) { return dim3((unsigned)esdf_region_grid(threads)); };
+    const uint32_t* unk = unknown_is_site ? g.planes + g.plane_words : nullptr;
+    hipLaunchKernelGGL(k_esdf_region_z, grid(esdf_region_z_threads(r)), block, 0, s, r, g.planes + (size_t)plane * g.plane_words, unk, w.a, w.fy);
+    hipLaunchKernelGGL(k_esdf_region_y, grid(esdf_region_y_threads(r)), block, 0, s, r, w.a, w.b, w.fy, w.fx);
+    hipLaunchKernelGGL(k_esdf_region_x, grid(esdf_region_x_threads(r)), block, 0, s, r, w.b, w.lattice, w.fx, g.res);
+    hipLaunchKernelGGL(k_esdf_region_brick, grid(esdf_bricked_floats(g.nx, g.ny, g.nz)), block, 0, s, r, esdf_bricks_along(g.ny),
+                       esdf_bricks_along(g.nz), w.fx, w.lattice, bricked);
+    if (count) {
+        hipLaunchKernelGGL(k_esdf_flag_count, grid(n_fy), block, 0, s, w.fy, n_fy, w.counters);
+        hipLaunchKernelGGL(k_esdf_flag_count, grid(n_fx), block, 0, s, w.fx, n_fx, w.counters + 1);
+    }
+    return (int)hipGetLastError();
+}
 
 size_t esdf_build_ws_bytes(int nx, int ny, int nz) { return 2 * (size_t)nx * ny * nz * sizeof(int32_t); }
 

@@ -1,7 +1,9 @@
 // vigo_esdf_core.hpp — the rule of the ESDF build (vigo_build_esdf, vigo_esdf_from_voxels_host): the EXACT Euclidean
 // distance transform of the voxel snapshot in integer voxel units, as the kernels of vigo_esdf_build.hip run it and
 // the host compiles too (esdf_from_voxels below is the host twin, the same functions in plain loops;
-// tests/test_esdf_build_core.py pins it against the all-pairs definition and scipy's EDT).
+// tests/test_esdf_build_core.py pins it against the all-pairs definition and scipy's EDT).  The region update
+// (vigo_update_esdf, vigo_esdf_update_host) is further down: the same three value functions on the lines a changed box
+// reaches.
 //
 // Definitions (include/vigo.h, vigo_build_esdf):
 //   sites      the voxels whose bit is set in the chosen plane (0 inflated-occupied, 2 occupied), OR the unknown
@@ -135,30 +137,121 @@ VIGO_HD float esdf_compose(int32_t s, double res) {
     return (float)((sqrt((double)d2_site) - sqrt((double)d2_free)) * res);
 }
 
-// The host twin (vigo_esdf_from_voxels_host): the byte grid's plane bit — OR the unknown bit — packed like the
-// snapshot (bit k of word w = voxel z = 32 w + k), then the three passes above in plain loops.  0, or -1 for a bad
-// argument, -6 for a lattice beyond kEsdfMaxEmptyD2 or kEsdfMaxVoxels, or one whose working memory (8 bytes per voxel
-// and the packed words) the host cannot allocate (VIGO_ERR_INVALID_ARG / VIGO_ERR_UNSUPPORTED); nothing is written
-// then, and no exception leaves the function: its caller is extern "C".
-inline int esdf_from_voxels(int nx, int ny, int nz, const uint8_t* vox, int plane, int unknown_is_site, double res, float* out) {
-    if (!vox || !out || (plane != 0 && plane != 2) || nx < 2 || ny < 2 || nz < 2 || !(res > 0.0) || !(res < INFINITY)) return -1;
-    const int32_t E = esdf_empty_d2(nx, ny, nz);
-    if (E == 0) return -6;
-    const int nzw = (nz + 31) / 32;
-    const size_t rows = (size_t)nx * ny, total = rows * nz;
-    const unsigned pick = (1u << plane) | (unknown_is_site ? 2u : 0u);
-    std::vector<uint32_t> words;
-    std::vector<int32_t> a, b;
-    try {
-        words.assign(rows * nzw, 0u);
-        a.resize(total);
-        b.resize(total);
-    } catch (const std::bad_alloc&) {
-        return -6;
+// ---- Region update (vigo_update_esdf, vigo_esdf_update_host) ---------------------------------------------------------
+// The three passes keep their results: A (z pass), B (y pass), L (the lattice).  A y-pass line (x, ., z) depends on its
+// own A line and nothing else, an x-pass line (., y, z) on its own B line — so after the sites of a box changed, a line
+// whose input did not change needs no work, and what is recomputed equals a whole rebuild bit for bit.  Flags carry
+// "the pass before changed a value on this line": fy[(x - lo_x) * nz + z] for the y lines of the box' slab, fx[y * nz + z]
+// for the x lines.  A flag is set if and only if such a value changed; every writer stores 1.  No pass scans the array
+// it writes (z: words -> A, y: A -> B, x: B -> L; the compare reads the old value at the address it stores to), so
+// threads of a pass never race.  One function per thread and pass: the kernels of vigo_esdf_build.hip are one call each,
+// over esdf_region_grid() blocks of kEsdfRegionBlock (the surplus threads of the last block leave at the first line),
+// esdf_update below is the same calls in plain loops, tests/esdf_update_check.cpp walks them thread index by thread index.
+struct EsdfRegion {
+    int nx, ny, nz, nzw;
+    int lo[3], n[3];      // the box [lo, lo + n) inside the lattice, every n > 0
+    int32_t E;
+};
+// what a tracked build keeps for the updates (carved by ws_esdf_track of vigo_ws_layout.hpp): 12 bytes per voxel, then
+// the two line counts and the flags — one run of clear_bytes from `counters` on, cleared ahead of the passes
+struct EsdfTrackWs {
+    int32_t *a, *b;                  // nx * ny * nz each
+    float* lattice;                  // nx * ny * nz, row-major
+    unsigned long long* counters;    // y_lines, x_lines of the last update that was asked for them
+    uint8_t *fy, *fx;                // nx * nz (a box uses its first n[0] * nz), ny * nz
+    size_t clear_bytes;
+};
+constexpr int kEsdfRegionBlock = 256;
+VIGO_HD size_t esdf_region_grid(size_t threads) { return (threads + kEsdfRegionBlock - 1) / kEsdfRegionBlock; }
+// threads of the passes: the box' columns x nz; its slab of x x ny x nz; the whole lattice
+VIGO_HD size_t esdf_region_z_threads(const EsdfRegion& r) { return (size_t)r.n[0] * r.n[1] * r.nz; }
+VIGO_HD size_t esdf_region_y_threads(const EsdfRegion& r) { return (size_t)r.n[0] * r.ny * r.nz; }
+VIGO_HD size_t esdf_region_x_threads(const EsdfRegion& r) { return (size_t)r.nx * r.ny * r.nz; }
+
+inline EsdfRegion esdf_region(int nx, int ny, int nz, const int32_t lo[3], const int32_t n[3]) {
+    EsdfRegion r{};
+    r.nx = nx; r.ny = ny; r.nz = nz; r.nzw = (nz + 31) / 32;
+    for (int a = 0; a < 3; ++a) { r.lo[a] = lo[a]; r.n[a] = n[a]; }
+    r.E = esdf_empty_d2(nx, ny, nz);
+    return r;
+}
+
+// z pass, thread t: voxel z of column (x, y) of the box' footprint — every z, not only the box' own — from the current
+// packed words (unk_plane: ORed in, or nullptr)
+VIGO_HD void esdf_region_z(const EsdfRegion& r, size_t t, const uint32_t* site_plane, const uint32_t* unk_plane, int32_t* a, uint8_t* fy) {
+    if (t >= esdf_region_z_threads(r)) return;
+    const int z = (int)(t % (size_t)r.nz);
+    const size_t col = t / (size_t)r.nz;
+    const int xi = (int)(col / r.n[1]), y = r.lo[1] + (int)(col % r.n[1]);
+    const size_t row = (size_t)(r.lo[0] + xi) * r.ny + y;
+    const uint32_t* sp = site_plane + row * r.nzw;
+    const uint32_t* up = unk_plane ? unk_plane + row * r.nzw : nullptr;
+    const int32_t v = esdf_z_value([sp, up](int w) { return up ? (sp[w] | up[w]) : sp[w]; }, r.nz, r.nzw, z, r.E);
+    int32_t* at = a + row * r.nz + z;
+    if (*at != v) {
+        *at = v;
+        fy[(size_t)xi * r.nz + z] = 1;
     }
+}
+
+// y pass, thread t: element y of line (x, ., z) of the box' slab, if the z pass flagged the line
+VIGO_HD void esdf_region_y(const EsdfRegion& r, size_t t, const int32_t* a, int32_t* b, const uint8_t* fy, uint8_t* fx) {
+    if (t >= esdf_region_y_threads(r)) return;
+    const int z = (int)(t % (size_t)r.nz);
+    const size_t q = t / (size_t)r.nz;
+    const int y = (int)(q % r.ny), xi = (int)(q / r.ny);
+    if (!fy[(size_t)xi * r.nz + z]) return;
+    const size_t nz = (size_t)r.nz, first = (size_t)(r.lo[0] + xi) * r.ny * nz + z;
+    const int32_t* line = a + first;
+    const int32_t v = esdf_line_value([line, nz](int j) { return line[(size_t)j * nz]; }, r.ny, y);
+    int32_t* at = b + first + (size_t)y * nz;
+    if (*at != v) {
+        *at = v;
+        fx[(size_t)y * nz + z] = 1;
+    }
+}
+
+// x pass, thread t = voxel t of the lattice: element x of line (., y, z), if the y pass flagged the line
+VIGO_HD void esdf_region_x(const EsdfRegion& r, size_t t, const int32_t* b, float* lattice, const uint8_t* fx, double res) {
+    if (t >= esdf_region_x_threads(r)) return;
+    const size_t sx = (size_t)r.ny * r.nz, q = t % sx;
+    if (!fx[q]) return;
+    const int32_t* line = b + q;
+    lattice[t] = esdf_compose(esdf_line_value([line, sx](int j) { return line[(size_t)j * sx]; }, r.nx, (int)(t / sx)), res);
+}
+
+// re-tile, thread i = float i of the bricked field (EsdfView, vigo_internal.hpp: line (x, by, bz) of nby x nbz lines per x
+// holds [x, x + 1] x [3 by, 3 by + 3] x [3 bz, 3 bz + 3], z fastest): rewritten if its source lies on a flagged x line
+VIGO_HD void esdf_region_brick(const EsdfRegion& r, size_t i, int nby, int nbz, const uint8_t* fx, const float* lattice, float* bricked) {
+    if (i >= (size_t)(r.nx - 1) * nby * nbz * 32) return;
+    const size_t line = i >> 5;
+    const int k = (int)(i & 31);
+    const int bz = (int)(line % nbz), by = (int)((line / nbz) % nby);
+    const int x = (int)(line / ((size_t)nbz * nby)) + (k >> 4), y = by * 3 + ((k >> 2) & 3), z = bz * 3 + (k & 3);
+    if (x < r.nx && y < r.ny && z < r.nz && fx[(size_t)y * r.nz + z]) bricked[i] = lattice[((size_t)x * r.ny + y) * r.nz + z];
+}
+
+// the byte grid's plane bit — OR the unknown bit — packed like the snapshot (bit k of word w = voxel z = 32 w + k)
+inline void esdf_pack_sites(const uint8_t* vox, size_t rows, int nz, int nzw, unsigned pick, uint32_t* words) {
     for (size_t row = 0; row < rows; ++row)
         for (int z = 0; z < nz; ++z)
             if (vox[row * nz + z] & pick) words[row * nzw + (z >> 5)] |= 1u << (z & 31);
+}
+
+// the three passes in plain loops on a checked lattice; a, b: nx * ny * nz each.  0, or -6 when the packed words cannot
+// be allocated
+inline int esdf_passes(int nx, int ny, int nz, const uint8_t* vox, int plane, int unknown_is_site, double res, int32_t E,
+                       int32_t* a, int32_t* b, float* out) {
+    const int nzw = (nz + 31) / 32;
+    const size_t rows = (size_t)nx * ny;
+    const unsigned pick = (1u << plane) | (unknown_is_site ? 2u : 0u);
+    std::vector<uint32_t> words;
+    try {
+        words.assign(rows * nzw, 0u);
+    } catch (const std::bad_alloc&) {
+        return -6;
+    }
+    esdf_pack_sites(vox, rows, nz, nzw, pick, words.data());
     for (size_t row = 0; row < rows; ++row) {
         const uint32_t* rw = &words[row * nzw];
         for (int z = 0; z < nz; ++z) a[row * nz + z] = esdf_z_value([rw](int w) { return rw[w]; }, nz, nzw, z, E);
@@ -175,6 +268,68 @@ inline int esdf_from_voxels(int nx, int ny, int nz, const uint8_t* vox, int plan
             const int32_t* line = &b[r];
             out[(size_t)x * sx + r] = esdf_compose(esdf_line_value([line, sx](int j) { return line[(size_t)j * sx]; }, nx, x), res);
         }
+    return 0;
+}
+
+// what the host twins refuse before they look at the lattice's size
+inline bool esdf_host_args_ok(int nx, int ny, int nz, int plane, double res) {
+    return (plane == 0 || plane == 2) && nx >= 2 && ny >= 2 && nz >= 2 && res > 0.0 && res < INFINITY;
+}
+
+// The host twin (vigo_esdf_from_voxels_host): the three passes above in plain loops.  0, or -1 for a bad argument, -6 for
+// a lattice beyond kEsdfMaxEmptyD2 or kEsdfMaxVoxels, or one whose working memory (8 bytes per voxel and the packed
+// words) the host cannot allocate (VIGO_ERR_INVALID_ARG / VIGO_ERR_UNSUPPORTED); nothing is written then, and no
+// exception leaves the function: its caller is extern "C".
+inline int esdf_from_voxels(int nx, int ny, int nz, const uint8_t* vox, int plane, int unknown_is_site, double res, float* out) {
+    if (!vox || !out || !esdf_host_args_ok(nx, ny, nz, plane, res)) return -1;
+    const int32_t E = esdf_empty_d2(nx, ny, nz);
+    if (E == 0) return -6;
+    std::vector<int32_t> a, b;
+    try {
+        a.resize((size_t)nx * ny * nz);
+        b.resize(a.size());
+    } catch (const std::bad_alloc&) {
+        return -6;
+    }
+    return esdf_passes(nx, ny, nz, vox, plane, unknown_is_site, res, E, a.data(), b.data(), out);
+}
+
+// vigo_esdf_from_voxels_host_tracked: the same, and the caller keeps A and B (what esdf_update works on)
+inline int esdf_from_voxels_tracked(int nx, int ny, int nz, const uint8_t* vox, int plane, int unknown_is_site, double res,
+                                    int32_t* a, int32_t* b, float* out) {
+    if (!vox || !a || !b || !out || !esdf_host_args_ok(nx, ny, nz, plane, res)) return -1;
+    const int32_t E = esdf_empty_d2(nx, ny, nz);
+    return E == 0 ? -6 : esdf_passes(nx, ny, nz, vox, plane, unknown_is_site, res, E, a, b, out);
+}
+
+// vigo_esdf_update_host: A, B and the lattice of the grid before the box [lo, lo + n) changed become those of `vox`, the
+// whole grid after it, by the region functions in plain loops; *y_lines, *x_lines: the flagged lines.  An n of 0 changes
+// nothing.  -1 also for a box that is negative or leaves the lattice.
+inline int esdf_update(int nx, int ny, int nz, const uint8_t* vox, int plane, int unknown_is_site, double res, const int32_t lo[3],
+                       const int32_t n[3], int32_t* a, int32_t* b, float* lattice, int64_t* y_lines, int64_t* x_lines) {
+    if (!vox || !lo || !n || !a || !b || !lattice || !esdf_host_args_ok(nx, ny, nz, plane, res)) return -1;
+    const int dims[3] = {nx, ny, nz};
+    for (int k = 0; k < 3; ++k)
+        if (lo[k] < 0 || n[k] < 0 || (int64_t)lo[k] + n[k] > dims[k]) return -1;
+    if (esdf_empty_d2(nx, ny, nz) == 0) return -6;
+    *y_lines = *x_lines = 0;
+    if (n[0] == 0 || n[1] == 0 || n[2] == 0) return 0;
+    const EsdfRegion r = esdf_region(nx, ny, nz, lo, n);
+    std::vector<uint32_t> words;
+    std::vector<uint8_t> fy, fx;
+    try {
+        words.assign((size_t)nx * ny * r.nzw, 0u);
+        fy.assign((size_t)n[0] * nz, 0);
+        fx.assign((size_t)ny * nz, 0);
+    } catch (const std::bad_alloc&) {
+        return -6;
+    }
+    esdf_pack_sites(vox, (size_t)nx * ny, nz, r.nzw, (1u << plane) | (unknown_is_site ? 2u : 0u), words.data());
+    for (size_t t = 0; t < esdf_region_z_threads(r); ++t) esdf_region_z(r, t, words.data(), nullptr, a, fy.data());
+    for (size_t t = 0; t < esdf_region_y_threads(r); ++t) esdf_region_y(r, t, a, b, fy.data(), fx.data());
+    for (size_t t = 0; t < esdf_region_x_threads(r); ++t) esdf_region_x(r, t, b, lattice, fx.data(), res);
+    for (uint8_t f : fy) *y_lines += f;
+    for (uint8_t f : fx) *x_lines += f;
     return 0;
 }
 

@@ -4,6 +4,7 @@
 
 #include <string>
 
+#include "vigo_esdf_core.hpp"
 #include "vigo_internal.hpp"
 
 namespace vigo {
@@ -22,6 +23,8 @@ enum BufId {
     kBufGrid,        // the packed voxel snapshot: exact size
     kBufEsdf,        // the bricked ESDF: exact size; growing drops has_esdf and esdf_view.dist until the new field is in
     kBufEsdfWs,      // vigo_build_esdf's two int32 buffers (vigo_esdf_build.hip): exact size (1 GiB at 512^3)
+    kBufEsdfTrack,   // vigo_build_esdf_tracked's A, B, lattice, counts and flags (ws_esdf_track): exact size, 12 bytes per voxel
+                     //   and the flags (1.5 GiB at 512^3); a failed growth ends the tracking
     kBufFit,         // least-squares operator of the B-spline fit, transposed (vigo_fit.hip): exact size; growing clears fit_K
     kBufFitTable,    // the operators of K = 4 .. 62 at one ts for vigo_bspline_fit_mixed (vigo_fit_plan.hpp): exact size, 0.7 MB;
                      //   a slot of its own, so filling it leaves kBufFit's operator and every other cache alone
@@ -64,6 +67,13 @@ struct vigo_context {
     // esdf (kBufEsdf)
     vigo::EsdfView esdf_view{};
     bool has_esdf = false;
+    // tracking (kBufEsdfTrack): from vigo_build_esdf_tracked until a whole-snapshot call, vigo_build_esdf or vigo_set_esdf.
+    // esdf_track points into the buffer; the pending box is the bounding box of the region updates since the last
+    // vigo_update_esdf, host integers, empty while an esdf_pending_n is 0
+    bool esdf_tracking = false;
+    int esdf_track_plane = 0, esdf_track_unknown = 0;
+    vigo::EsdfTrackWs esdf_track{};
+    int32_t esdf_pending_lo[3] = {}, esdf_pending_n[3] = {};
     // kBufFit holds the operator for (fit_K, fit_ts); fit_K == 0: none
     int fit_K = 0;
     double fit_ts = 0.0;

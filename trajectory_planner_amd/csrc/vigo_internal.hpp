@@ -208,6 +208,11 @@ int launch_esdf_brick(hipStream_t s, int nx, int ny, int nz, const float* src, f
 // lattice; a, b: the two int32 buffers of esdf_build_ws_bytes, lattice may be a
 size_t esdf_build_ws_bytes(int nx, int ny, int nz);
 int launch_esdf_build(hipStream_t s, const GridView& g, int plane, int unknown_is_site, int32_t* a, int32_t* b, float* lattice);
+// the region update on what a tracked build kept (w: EsdfTrackWs of vigo_esdf_core.hpp): the checked, non-empty box
+// [lo, lo + n) of the snapshot changed; bricked: the installed field; count: also the flagged lines into w.counters
+struct EsdfTrackWs;
+int launch_esdf_region_update(hipStream_t s, const GridView& g, const int32_t lo[3], const int32_t n[3], int plane, int unknown_is_site,
+                              const EsdfTrackWs& w, float* bricked, bool count);
 // batched B-spline fit (vigo_fit.hip): one-off device factorisation per (K, ts), then the fit
 size_t fit_work_doubles(int K);
 size_t fit_pinv_doubles(int K);

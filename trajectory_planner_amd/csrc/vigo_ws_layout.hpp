@@ -43,6 +43,22 @@ size_t ws_pair(void* base, size_t n, T*& first, T*& second) {
     return c.bytes();
 }
 
+// vigo_build_esdf_tracked (Ws = EsdfTrackWs of vigo_esdf_core.hpp): the passes' results A, B and the float lattice of
+// `voxels` each — no padding between them, as in ws_pair: 1.5 GiB at 512^3 — then the two line counts and the flag arrays
+// of nx * nz and ny * nz bytes as ONE run, which vigo_update_esdf clears with one memset of clear_bytes
+template <class Ws>
+size_t ws_esdf_track(void* base, size_t voxels, size_t fy_bytes, size_t fx_bytes, Ws& w) {
+    WsCarver c(base);
+    w.a = c.take<int32_t>(3 * voxels);
+    w.b = w.a ? w.a + voxels : nullptr;
+    w.lattice = w.a ? reinterpret_cast<float*>(w.a + 2 * voxels) : nullptr;
+    w.counters = c.take<unsigned long long>(2);
+    w.fy = c.take<uint8_t>(fy_bytes + fx_bytes);
+    w.fx = w.fy ? w.fy + fy_bytes : nullptr;
+    w.clear_bytes = 2 * sizeof(unsigned long long) + fy_bytes + fx_bytes;
+    return c.bytes();
+}
+
 // vigo_update_grid_region: the box' bytes as the *_host form stages them (none in the device-pointer form; whole 16-byte
 // lines, so the buffer's alignment carries over to the planes and the box' rows keep k_pack_grid's aligned loads), then
 // the two compact planes of window_words each that inflate mode dilates in (none in raw mode)

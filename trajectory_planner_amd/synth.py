@@ -351,6 +351,41 @@ def host_esdf(world: World, plane: int = 2, unknown_is_site: bool = False):
     return out, np.array(world.origin, dtype=np.float64)
 
 
+def host_esdf_tracked(voxels, plane: int = 2, unknown_is_site: bool = False, res: float = 0.1):
+    """vigo_esdf_from_voxels_host_tracked on a byte grid [nx,ny,nz]: the host twin of Vigo.build_esdf(tracked=True), no GPU.
+    Returns (return code, a, b, lattice): the z-pass and y-pass results (int32) and the float32 lattice — what
+    host_esdf_update works on."""
+    import ctypes as C
+    from . import _lib
+    vox = np.ascontiguousarray(voxels, dtype=np.uint8)
+    nx, ny, nz = vox.shape
+    a, b = np.zeros(vox.shape, dtype=np.int32), np.zeros(vox.shape, dtype=np.int32)
+    lat = np.zeros(vox.shape, dtype=np.float32)
+    rc = _lib.load().vigo_esdf_from_voxels_host_tracked(nx, ny, nz, vox.ctypes.data_as(C.c_void_p), int(plane), 1 if unknown_is_site else 0,
+                                                        float(res), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                                        lat.ctypes.data_as(C.c_void_p))
+    return rc, a, b, lat
+
+
+def host_esdf_update(new_voxels, lo, n, a, b, lattice, plane: int = 2, unknown_is_site: bool = False, res: float = 0.1):
+    """vigo_esdf_update_host, the host twin of Vigo.update_esdf (no GPU): a, b, lattice of host_esdf_tracked on the grid
+    before the box [lo, lo + n) changed are brought, IN PLACE, to those of new_voxels (the whole grid after the change).
+    Returns (return code, dict of box_lo, box_n, y_lines, x_lines)."""
+    import ctypes as C
+    from . import _lib
+    vox = np.ascontiguousarray(new_voxels, dtype=np.uint8)
+    nx, ny, nz = vox.shape
+    for arr, dt in ((a, np.int32), (b, np.int32), (lattice, np.float32)):
+        if arr.dtype != dt or arr.shape != vox.shape or not arr.flags["C_CONTIGUOUS"] or not arr.flags["WRITEABLE"]:
+            raise ValueError("a, b, lattice: expected writeable C-contiguous int32, int32, float32 arrays of the grid's shape")
+    i3 = lambda v: (C.c_int32 * 3)(*[int(x) for x in v])
+    st = _lib.VigoEsdfUpdateStats()
+    rc = _lib.load().vigo_esdf_update_host(nx, ny, nz, vox.ctypes.data_as(C.c_void_p), int(plane), 1 if unknown_is_site else 0, float(res),
+                                           i3(lo), i3(n), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                           lattice.ctypes.data_as(C.c_void_p), C.byref(st))
+    return rc, st.as_dict()
+
+
 def host_grid_region_apply(voxels, lo, box, inflate_r=None):
     """The library's host twin of vigo_update_grid_region (vigo_grid_region_apply_host, csrc/vigo_grid_update_core.hpp; no
     GPU): a copy of the byte grid `voxels` [nx,ny,nz] with `box` [n0,n1,n2] written at `lo` — raw when inflate_r is None,

@@ -196,7 +196,9 @@ class Vigo:
     def update_grid_region(self, lo, voxels: torch.Tensor, inflate_r=None):
         """vigo_update_grid_region: the box of voxels.shape at lo written into the snapshot in place, stream-ordered.
         voxels: uint8 [n0,n1,n2] on the GPU.  inflate_r None: raw (bits 0..2 of the bytes); (rx,ry,rz): bit 0 is ignored and
-        plane 0 is re-inflated from the occupied plane on the box grown by r.  A field built by build_esdf is stale afterwards."""
+        plane 0 is re-inflated from the occupied plane on the box grown by r.  A field built by build_esdf is stale afterwards:
+        build it again, or build it with build_esdf(tracked=True) once and call update_esdf() after the region updates — the
+        boxes are collected in the handle's pending box and the field is refreshed for work that follows the change."""
         if voxels.dim() != 3:
             raise ValueError("voxels: expected [n0,n1,n2]")
         r = None if inflate_r is None else self._int3(inflate_r, "inflate_r")
@@ -803,17 +805,36 @@ class Vigo:
         self._check(self._lib.vigo_set_esdf(self._h, nx, ny, nz, (C.c_double * 3)(*origin), float(res),
                                             _ptr(dist, torch.float32, "dist", self.device)), "vigo_set_esdf")
 
-    def build_esdf(self, plane: int = 2, unknown_is_site: bool = False, return_lattice: bool = False):
+    def build_esdf(self, plane: int = 2, unknown_is_site: bool = False, return_lattice: bool = False, tracked: bool = False):
         """vigo_build_esdf: the signed Euclidean distance field of the current snapshot (sites: plane 2 = occupied or
         0 = inflated-occupied, with the unknown voxels when unknown_is_site), built on the device and installed as the
-        handle's ESDF.  return_lattice: also the row-major float32 [nx,ny,nz] lattice."""
+        handle's ESDF.  return_lattice: also the row-major float32 [nx,ny,nz] lattice.  tracked: vigo_build_esdf_tracked —
+        the same field, and the handle keeps what update_esdf needs (12 bytes per voxel) and collects the boxes of
+        update_grid_region / update_grid_region_host from now on."""
         lattice = None
         if return_lattice:
             if self._grid_meta is None:
                 raise VigoError("build_esdf(return_lattice=True) before set_grid")
             lattice = torch.empty(self._grid_meta[:3], dtype=torch.float32, device=self.device)
-        self._check(self._lib.vigo_build_esdf(self._h, int(plane), 1 if unknown_is_site else 0,
-                                              None if lattice is None else C.c_void_p(lattice.data_ptr())), "vigo_build_esdf")
+        fn, name = (self._lib.vigo_build_esdf_tracked, "vigo_build_esdf_tracked") if tracked else (self._lib.vigo_build_esdf, "vigo_build_esdf")
+        self._check(fn(self._h, int(plane), 1 if unknown_is_site else 0, None if lattice is None else C.c_void_p(lattice.data_ptr())), name)
+        return lattice
+
+    def update_esdf(self, return_lattice: bool = False, stats: bool = False):
+        """vigo_update_esdf: after build_esdf(tracked=True), the installed field brought up to the snapshot as the region
+        updates since the last call left it — bit for bit what a rebuild gives — stream-ordered.  return_lattice: the whole
+        row-major float32 [nx,ny,nz] lattice; stats: a dict of box_lo, box_n (the pending box worked on), y_lines, x_lines
+        (synchronises the stream).  Returns None, the lattice, the dict, or (lattice, dict)."""
+        lattice = None
+        if return_lattice:
+            if self._grid_meta is None:
+                raise VigoError("update_esdf(return_lattice=True) before set_grid")
+            lattice = torch.empty(self._grid_meta[:3], dtype=torch.float32, device=self.device)
+        st = _lib.VigoEsdfUpdateStats() if stats else None
+        self._check(self._lib.vigo_update_esdf(self._h, None if lattice is None else C.c_void_p(lattice.data_ptr()),
+                                               None if st is None else C.byref(st)), "vigo_update_esdf")
+        if stats:
+            return (lattice, st.as_dict()) if return_lattice else st.as_dict()
         return lattice
 
     def esdf_query(self, pts: torch.Tensor):
