@@ -39,6 +39,14 @@
  *   weights     double[B][4]         (distance, smoothness, feasibility, dynamic) per
  *                                       trajectory; NULL => the handle's params.  The rebound
  *                                       loop doubles them per trajectory (BT.cpp:667,672,678).
+ * The *_mixed entries take trajectories of DIFFERENT control-point counts in one call: rows of Ns
+ * control points, ctrl double[B][Ns][3], and n_pts int32[B] (device memory), the count of each;
+ * guide_off is then int32[B*Ns + 1] with control point (b,i) at b*Ns + i and the control points
+ * beyond a count owning empty ranges.  The fit (vigo_bspline_fit_mixed), the prologue
+ * (vigo_collision_segs_mixed, vigo_path_search_mixed, vigo_guide_assign_mixed), the solves
+ * (vigo_cost_grad_mixed, vigo_optimize_mixed), the rebound rounds (vigo_rebound_rounds_mixed), the
+ * re-guide step (vigo_rebound_reguide_mixed) and the finish (vigo_traj_finish) pass these arrays to
+ * one another as they lie.
  */
 #ifndef VIGO_H
 #define VIGO_H
@@ -890,6 +898,61 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl,
                          vigo_rebound_state_t* state, int64_t pair_cap, int32_t* out_guide_off,
                          double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap, int64_t point_cap,
                          int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status);
+
+/* ---- prologue and re-guide for mixed control-point counts ---------------------------------- */
+
+/*
+ * vigo_collision_segs, vigo_path_search, vigo_guide_assign and vigo_rebound_reguide for a batch whose trajectories have
+ * DIFFERENT control-point counts, in the layouts of vigo_bspline_fit_mixed / vigo_optimize_mixed /
+ * vigo_rebound_rounds_mixed, so that every array passes between those calls and these as it lies:
+ *   Ns        the row stride, 7 .. VIGO_MAX_CTRL_POINTS (no shape-class rule: nothing here depends on a lane layout)
+ *   n_pts     int32[B] in DEVICE memory: trajectory b has n_pts[b] control points, 7 .. Ns
+ *   ctrl      double[B][Ns][3]; rows are padded.  The control points i >= n_pts[b] are never read for their value: they
+ *             may hold anything, NaN included
+ *   guide CSRs (out_guide_off of vigo_guide_assign_mixed; guide_off and out_guide_off of vigo_rebound_reguide_mixed)
+ *             int32[B*Ns+1], control point i of trajectory b at b*Ns + i.  In every CSR these calls write, the control
+ *             points i >= n_pts[b] own an EMPTY range, so the output is a valid CSR over all B*Ns+1 entries and
+ *             vigo_optimize_mixed / vigo_rebound_rounds_mixed take it unchanged
+ *   segment and path CSRs   per trajectory and per segment, as in the uniform entries
+ * Every other argument is its uniform sibling's.
+ * Contract: every output of a trajectory — segments in push order with the duplicate-segment quirk, search counts,
+ * paths, pairs per control point in push order, unknown flags, statuses; for the re-guide state, weights and the merged
+ * CSR — equals, bit for bit, its output in the uniform call of its own count on it alone.  A result does not depend on
+ * the batch, on the neighbours' counts or on what lies in a row beyond the count.  The count is the trajectory's own
+ * wherever the reference's rules name N: endIdx and the closing segment (start, N - 1) of findCollisionSeg, the
+ * [3, N - 4] clip and the [0, N) skip of the guide pushes, the rules of the re-guide list, the end-in-range checks of a
+ * caller's segments.
+ * A count outside [7, Ns] is device data and is caught per trajectory, as vigo_rebound_rounds_mixed does: nothing beyond
+ * the row is indexed, every other trajectory gets the bits it would get without it, and the trajectory itself reads
+ *   vigo_collision_segs_mixed, vigo_path_search_mixed   VIGO_PATHS_DEFERRED, no segments, no searches (out_counts 0, 0)
+ *   vigo_guide_assign_mixed                             VIGO_GUIDE_DEFERRED, no pairs
+ *   vigo_rebound_reguide_mixed                          VIGO_REGUIDE_DEFERRED, state untouched
+ * (the segments a caller supplies for such a trajectory are not held against a count; offsets must still not decrease).
+ * The merged CSR of the re-guide copies the old pairs of every (b, i) unchanged, whatever the count.
+ * How: the uniform entries' kernels — there is one copy of each; the uniform entries run them with n_pts == NULL.  The
+ * count check is part of the one-workgroup count-and-scan kernels whose verdicts are read back anyway: a call
+ * synchronises with the host exactly as often as its uniform sibling.
+ * Errors: those of the uniform entry with N replaced by Ns, and nothing is written in any such case; Ns outside
+ * [7, VIGO_MAX_CTRL_POINTS] is VIGO_ERR_UNSUPPORTED_N; n_pts == NULL with B > 0 is VIGO_ERR_INVALID_ARG; for the re-guide
+ * guide_off must not decrease over all B*Ns+1 entries.  B = 0 is a no-op.
+ */
+int vigo_collision_segs_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, double not_check_ratio,
+                              int32_t* out_seg_off, int32_t* out_seg, int64_t seg_cap, int32_t* out_status);
+int vigo_path_search_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                           const int32_t* seg, double not_check_ratio, double step, const int32_t pool[3], double min_height,
+                           double max_height, int max_expansions, int search_path_cap, int64_t seg_cap, int64_t point_cap,
+                           int32_t* out_status, int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off, double* out_path,
+                           int32_t* out_counts);
+int vigo_guide_assign_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                            const int32_t* seg, const int32_t* path_off, const double* path, int64_t pair_cap,
+                            int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk, int32_t* out_status);
+int vigo_rebound_reguide_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl,
+                               const int32_t* guide_off, const double* guide_pv, const uint8_t* guide_unk,
+                               double* weights, double not_check_ratio, double step, const int32_t pool[3],
+                               double min_height, double max_height, int max_expansions, int search_path_cap,
+                               vigo_rebound_state_t* state, int64_t pair_cap, int32_t* out_guide_off,
+                               double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap, int64_t point_cap,
+                               int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status);
 
 /* Rules 1-3 of vigo_traj_corridor_check for one trajectory, on the host (no GPU), with the very code its first kernel
  * runs: knots double[K+1] -> status (VIGO_TRAJ_OK .. VIGO_TRAJ_TOO_LONG; VIGO_ERR_INVALID_ARG for NULLs or K < 0) and

@@ -116,6 +116,12 @@ PROTOTYPES = {
     "vigo_path_search": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vigo_rebound_reguide": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
                                   _vp, _vp, _vp, _vp]),
+    "vigo_guide_assign_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "vigo_collision_segs_mixed": (_i, [_vp, _i, _i, _vp, _vp, _d, _vp, _vp, _i64, _vp]),
+    "vigo_path_search_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "vigo_rebound_reguide_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, C.POINTER(C.c_int32), _d, _d, _i, _i, _vp, _i64, _vp, _vp, _vp,
+                                        _i64, _i64, _vp, _vp, _vp, _vp]),
     "vigo_traj_sample_runs": (_i, [_i, _vp, _d, _vp, _vp, _vp]),
     "vigo_poly_sample": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "vigo_accumulated_time": (_d, [_d, _i64]),

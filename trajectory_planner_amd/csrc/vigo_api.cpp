@@ -1144,27 +1144,58 @@ int vigo_astar_capacity(int32_t* max_nodes, int32_t* max_heap) {
     return VIGO_OK;
 }
 
-int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off,
-                      const double* path, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk,
-                      int32_t* out_status) {
+}  // extern "C"
+
+namespace {
+
+// what a *_mixed prologue entry checks before its uniform body: the handle, the counts' pointer, the row stride
+int check_mixed_rows(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const char* who) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    if (B > 0 && !n_pts) return fail(h, VIGO_ERR_INVALID_ARG, (std::string(who) + ": n_pts == NULL").c_str());
+    if (Ns < 7 || Ns > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, (std::string(who) + ": Ns outside [7, VIGO_MAX_CTRL_POINTS]").c_str());
+    return VIGO_OK;
+}
+
+// vigo_guide_assign (n_pts == NULL) and vigo_guide_assign_mixed (rows of N control points, n_pts[b] of them the trajectory's)
+int guide_assign(vigo_handle_t h, const std::string& who, int B, int N, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                 const int32_t* seg, const int32_t* path_off, const double* path, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv,
+                 uint8_t* out_guide_unk, int32_t* out_status) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || N < 1 || pair_cap < 0 ||
         (B > 0 && (!ctrl || !seg_off || !seg || !path_off || !path || !out_guide_off || !out_guide_pv || !out_status)))
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: bad argument");
-    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_guide_assign before vigo_set_grid");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": bad argument").c_str());
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (who + " before vigo_set_grid").c_str());
     if (B == 0) return VIGO_OK;
     VIGO_TRY(ensure_scratch(h, 64));
     long long* result = h->buf[vigo::kBufScratch].as<long long>();
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, seg_off, seg, path_off, (long long)pair_cap, out_guide_off, out_status,
-                                                       result));
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, n_pts, seg_off, seg, path_off, (long long)pair_cap, out_guide_off,
+                                                       out_status, result));
     long long host_result[2] = {0, 0};
     VIGO_TRY(read_back(h, host_result, result, sizeof(host_result)));
-    if (host_result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: offsets that decrease, a path without a point or a segment out of range");
+    if (host_result[1] != 0) return fail(h, VIGO_ERR_INVALID_ARG, (who + ": offsets that decrease, a path without a point or a segment out of range").c_str());
     if (host_result[0] > (long long)pair_cap || host_result[0] > 0x7fffffffLL)
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_guide_assign: the pairs do not fit pair_cap");
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, seg_off, seg, path_off, path, out_guide_off, out_guide_pv,
-                                                      out_guide_unk, out_status));
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the pairs do not fit pair_cap").c_str());
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, n_pts, ctrl, seg_off, seg, path_off, path, out_guide_off,
+                                                      out_guide_pv, out_guide_unk, out_status));
     return VIGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vigo_guide_assign(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off,
+                      const double* path, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk,
+                      int32_t* out_status) {
+    return guide_assign(h, "vigo_guide_assign", B, N, nullptr, ctrl, seg_off, seg, path_off, path, pair_cap, out_guide_off, out_guide_pv,
+                        out_guide_unk, out_status);
+}
+int vigo_guide_assign_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
+                            const int32_t* path_off, const double* path, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv,
+                            uint8_t* out_guide_unk, int32_t* out_status) {
+    VIGO_TRY(check_mixed_rows(h, B, Ns, n_pts, "vigo_guide_assign_mixed"));
+    return guide_assign(h, "vigo_guide_assign_mixed", B, Ns, n_pts, ctrl, seg_off, seg, path_off, path, pair_cap, out_guide_off, out_guide_pv,
+                        out_guide_unk, out_status);
 }
 int vigo_guide_capacity(int32_t* max_path_points) {
     if (max_path_points) *max_path_points = vigo::guide_path_capacity();
@@ -1214,67 +1245,65 @@ int path_search_searches(vigo_handle_t h, vigo::PathSearchArgs& a, vigo::PathSea
     return read_back(h, result + 3, a.result + 3, 2 * sizeof(long long));
 }
 
-}  // namespace
-
-extern "C" {
-
-int vigo_collision_segs(vigo_handle_t h, int B, int N, const double* ctrl, double not_check_ratio, int32_t* out_seg_off, int32_t* out_seg,
-                        int64_t seg_cap, int32_t* out_status) {
+// the bodies of the uniform entries (n_pts == NULL) and of their _mixed forms (rows of N control points, n_pts[b] of them
+// the trajectory's; check_mixed_rows has passed): the same checks, the same kernels, the same read-backs
+int collision_segs(vigo_handle_t h, const std::string& who, int B, int N, const int32_t* n_pts, const double* ctrl, double not_check_ratio,
+                   int32_t* out_seg_off, int32_t* out_seg, int64_t seg_cap, int32_t* out_status) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     if (B < 0 || N < 7 || seg_cap < 0 || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
         (B > 0 && (!ctrl || !out_seg_off || !out_seg || !out_status)))
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_collision_segs: bad argument");
-    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_collision_segs before vigo_set_grid");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": bad argument").c_str());
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (who + " before vigo_set_grid").c_str());
     if (B == 0) return VIGO_OK;
     vigo::PathSearchArgs a{};
-    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio;
+    a.B = B; a.N = N; a.n_pts = n_pts; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio;
     VIGO_TRY(path_search_scratch(h, B, N, true, a));
     long long result[2] = {0, 0};
-    VIGO_TRY(path_search_count(h, a, result, "vigo_collision_segs: bad list"));
-    if (result[0] > (long long)seg_cap) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_collision_segs: the segments do not fit seg_cap");
+    VIGO_TRY(path_search_count(h, a, result, (who + ": bad list").c_str()));
+    if (result[0] > (long long)seg_cap) return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the segments do not fit seg_cap").c_str());
     a.out_seg_off = out_seg_off; a.out_status = out_status;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_fill(h->stream, a, out_seg, nullptr, nullptr));
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_segs_out(h->stream, a));
     return VIGO_OK;
 }
 
-int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, double not_check_ratio,
-                     double step, const int32_t pool[3], double min_height, double max_height, int max_expansions, int search_path_cap,
-                     int64_t seg_cap, int64_t point_cap, int32_t* out_status, int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off,
-                     double* out_path, int32_t* out_counts) {
+int path_search(vigo_handle_t h, const std::string& who, int B, int N, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                const int32_t* seg, double not_check_ratio, double step, const int32_t pool[3], double min_height, double max_height,
+                int max_expansions, int search_path_cap, int64_t seg_cap, int64_t point_cap, int32_t* out_status, int32_t* out_seg_off,
+                int32_t* out_seg, int32_t* out_path_off, double* out_path, int32_t* out_counts) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     const bool scan = !seg_off && !seg;
     if (B < 0 || N < 7 || seg_cap < 0 || point_cap < 0 || (!scan && (!seg_off || !seg)) ||
         (scan && !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0)) || !astar_args_ok(pool, step, search_path_cap, max_expansions) ||
         (B > 0 && (!ctrl || !out_status || !out_seg_off || !out_seg || !out_path_off || !out_path)))
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: bad argument");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": bad argument").c_str());
     if (!astar_pool_fits(pool))
-        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_path_search: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
-    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_path_search before vigo_set_grid");
+        return fail(h, VIGO_ERR_UNSUPPORTED, (who + ": more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis").c_str());
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (who + " before vigo_set_grid").c_str());
     if (B == 0) return VIGO_OK;
     vigo::PathSearchArgs a{};
-    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_off_in = seg_off; a.seg_in = seg;
+    a.B = B; a.N = N; a.n_pts = n_pts; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_off_in = seg_off; a.seg_in = seg;
     a.search_path_cap = search_path_cap;
     VIGO_TRY(path_search_scratch(h, B, N, scan, a));
     long long result[5] = {0, 0, 0, 0, 0};
-    VIGO_TRY(path_search_count(h, a, result, "vigo_path_search: offsets that decrease or start below 0, or a segment end outside [0, N)"));
+    VIGO_TRY(path_search_count(h, a, result, (who + ": offsets that decrease or start below 0, or a segment end outside [0, N)").c_str()));
     vigo::PathSearchWork w{};
     VIGO_TRY(path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result));
     if (result[3] > (long long)seg_cap || result[3] >= 0x7fffffffLL)
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the segments do not fit seg_cap");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the segments do not fit seg_cap").c_str());
     if (result[4] > (long long)point_cap || result[4] > 0x7fffffffLL)
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_path_search: the path points do not fit point_cap");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the path points do not fit point_cap").c_str());
     a.out_status = out_status; a.out_seg_off = out_seg_off; a.out_seg = out_seg; a.out_path_off = out_path_off; a.out_path = out_path;
     a.out_counts = out_counts;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)result[3], (int)result[4]));
     return VIGO_OK;
 }
 
-int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* guide_off, const double* guide_pv,
-                         const uint8_t* guide_unk, double* weights, double not_check_ratio, double step, const int32_t pool[3],
-                         double min_height, double max_height, int max_expansions, int search_path_cap, vigo_rebound_state_t* state,
-                         int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap,
-                         int64_t point_cap, int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status) {
+int rebound_reguide(vigo_handle_t h, const std::string& who, int B, int N, const int32_t* n_pts, const double* ctrl, const int32_t* guide_off,
+                    const double* guide_pv, const uint8_t* guide_unk, double* weights, double not_check_ratio, double step, const int32_t pool[3],
+                    double min_height, double max_height, int max_expansions, int search_path_cap, vigo_rebound_state_t* state,
+                    int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap,
+                    int64_t point_cap, int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status) {
     if (!h) return VIGO_ERR_INVALID_ARG;
     const bool no_guides = !guide_off && !guide_pv && !guide_unk;
     const bool no_paths = !out_path_seg_off && !out_path_off && !out_path;
@@ -1282,22 +1311,22 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
         (!no_guides && (!guide_off || !guide_pv)) || (!no_paths && (!out_path_seg_off || !out_path_off || !out_path)) ||
         !astar_args_ok(pool, step, search_path_cap, max_expansions) ||
         (B > 0 && (!ctrl || !weights || !state || !out_guide_off || !out_guide_pv || !out_status)))
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: bad argument");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": bad argument").c_str());
     if (N > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, "N outside [7, VIGO_MAX_CTRL_POINTS]");
     if (!astar_pool_fits(pool))
-        return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis");
-    if (B > (1 << 20)) return fail(h, VIGO_ERR_UNSUPPORTED, "vigo_rebound_reguide: more than 2^20 trajectories in a call");
-    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_rebound_reguide before vigo_set_grid");
+        return fail(h, VIGO_ERR_UNSUPPORTED, (who + ": more than VIGO_ASTAR_MAX_POOL_AXIS nodes along a pool axis").c_str());
+    if (B > (1 << 20)) return fail(h, VIGO_ERR_UNSUPPORTED, (who + ": more than 2^20 trajectories in a call").c_str());
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, (who + " before vigo_set_grid").c_str());
     if (B == 0) return VIGO_OK;
     constexpr int kSegs = VIGO_MAX_COLLISION_SEGS;
     vigo::ReguideArgs r{};
     vigo::ReguideStage st{};
     VIGO_TRY(carve(h, vigo::kBufReguide0, kSlack, [&](void* p) { return vigo::ws_reguide(p, B, N, kSegs, r, st); }));
-    r.B = B; r.N = N; r.ctrl = ctrl; r.guide_off = guide_off; r.guide_pv = guide_pv; r.guide_unk = guide_unk; r.weights = weights; r.state = state;
+    r.B = B; r.N = N; r.n_pts = n_pts; r.ctrl = ctrl; r.guide_off = guide_off; r.guide_pv = guide_pv; r.guide_unk = guide_unk; r.weights = weights; r.state = state;
     r.dthresh = h->params.dthresh; r.not_check_ratio = not_check_ratio;
     // vigo_path_search's chain on the lists (a trajectory that is not worked on has an empty one)
     vigo::PathSearchArgs a{};
-    a.B = B; a.N = N; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_in = r.list; a.seg_cnt_in = r.n_list; a.seg_stride_in = kSegs;
+    a.B = B; a.N = N; a.n_pts = n_pts; a.ctrl = ctrl; a.not_check_ratio = not_check_ratio; a.seg_in = r.list; a.seg_cnt_in = r.n_list; a.seg_stride_in = kSegs;
     a.search_path_cap = search_path_cap;
     VIGO_TRY(path_search_scratch(h, B, N, false, a));
     VIGO_HIP(h, hipMemsetAsync(r.result, 0, 64, h->stream));
@@ -1305,37 +1334,37 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
     long long bad_off = 0;
     VIGO_HIP(h, hipMemcpyAsync(&bad_off, r.result, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     long long result[5] = {0, 0, 0, 0, 0};
-    const int rc = path_search_count(h, a, result, "vigo_rebound_reguide: a re-guide list out of range");
+    const int rc = path_search_count(h, a, result, (who + ": a re-guide list out of range").c_str());
     if (rc == VIGO_ERR_HIP) (void)hipStreamSynchronize(h->stream);   // (it may have failed before its own wait: bad_off's copy must have landed)
     if (rc) return rc;
-    if (bad_off != 0) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: guide offsets that decrease or start below 0");
+    if (bad_off != 0) return fail(h, VIGO_ERR_INVALID_ARG, (who + ": guide offsets that decrease or start below 0").c_str());
     vigo::PathSearchWork w{};
     VIGO_TRY(path_search_searches(h, a, w, step, pool, min_height, max_height, max_expansions, result));
     const long long total_seg = result[3], total_pts = result[4];
-    if (total_pts > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: more than 2^31 path points");
+    if (total_pts > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, (who + ": more than 2^31 path points").c_str());
     if (!no_paths && (total_seg > (long long)seg_cap || total_pts > (long long)point_cap))
-        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the paths do not fit seg_cap / point_cap");
+        return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the paths do not fit seg_cap / point_cap").c_str());
     VIGO_TRY(carve(h, vigo::kBufReguide1, kSlack, [&](void* p) { return vigo::ws_reguide_paths(p, total_seg, total_pts, a); }));
     a.out_status = st.ps_status; a.out_seg_off = st.ps_seg_off; a.out_counts = st.ps_counts;
     VIGO_HIP(h, (hipError_t)vigo::launch_ps_write(h->stream, a, w, (int)total_seg, (int)total_pts));
     // vigo_guide_assign's pair on that output: the pairs THIS step appends
     long long* g_result = r.result + 2;
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, st.ps_seg_off, a.out_seg, a.out_path_off, 0x7fffffffLL, st.g_off, st.g_status, g_result));
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_offsets(h->stream, B, N, n_pts, st.ps_seg_off, a.out_seg, a.out_path_off, 0x7fffffffLL, st.g_off, st.g_status, g_result));
     long long g_host[2] = {0, 0};
     VIGO_TRY(read_back(h, g_host, g_result, sizeof(g_host)));
-    if (g_host[1] != 0 || g_host[0] > 0x7fffffffLL) return fail(h, VIGO_ERR_HIP, "vigo_rebound_reguide: the path search's output is no input of the guide step");
+    if (g_host[1] != 0 || g_host[0] > 0x7fffffffLL) return fail(h, VIGO_ERR_HIP, (who + ": the path search's output is no input of the guide step").c_str());
     const size_t P = (size_t)g_host[0];
     double* g_pv;
     uint8_t* g_unk;
     VIGO_TRY(carve(h, vigo::kBufReguide2, kSlack, [&](void* p) { return vigo::ws_reguide_pairs(p, P, g_pv, g_unk); }));
-    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, ctrl, st.ps_seg_off, a.out_seg, a.out_path_off, a.out_path, st.g_off, g_pv, g_unk, st.g_status));
+    VIGO_HIP(h, (hipError_t)vigo::launch_guide_assign(h->stream, h->grid, B, N, n_pts, ctrl, st.ps_seg_off, a.out_seg, a.out_path_off, a.out_path, st.g_off, g_pv, g_unk, st.g_status));
     r.ps_status = st.ps_status; r.ps_seg_off = st.ps_seg_off; r.ps_counts = st.ps_counts; r.g_status = st.g_status; r.g_off = st.g_off; r.g_pv = g_pv; r.g_unk = g_unk;
     r.pair_cap = (long long)pair_cap;
     r.out_guide_off = out_guide_off; r.out_guide_pv = out_guide_pv; r.out_guide_unk = out_guide_unk; r.out_status = out_status;
     VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge_offsets(h->stream, r));
     long long merged = 0;
     VIGO_TRY(read_back(h, &merged, r.result + 1, sizeof(long long)));
-    if (merged > (long long)pair_cap || merged > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_rebound_reguide: the merged pairs do not fit pair_cap");
+    if (merged > (long long)pair_cap || merged > 0x7fffffffLL) return fail(h, VIGO_ERR_INVALID_ARG, (who + ": the merged pairs do not fit pair_cap").c_str());
     VIGO_HIP(h, (hipError_t)vigo::launch_guide_merge(h->stream, h->grid, r));
     if (!no_paths) {
         VIGO_HIP(h, hipMemcpyAsync(out_path_seg_off, st.ps_seg_off, ((size_t)B + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -1344,6 +1373,57 @@ int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, cons
     }
     VIGO_HIP(h, (hipError_t)vigo::launch_reguide_commit(h->stream, r));
     return VIGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vigo_collision_segs(vigo_handle_t h, int B, int N, const double* ctrl, double not_check_ratio, int32_t* out_seg_off, int32_t* out_seg,
+                        int64_t seg_cap, int32_t* out_status) {
+    return collision_segs(h, "vigo_collision_segs", B, N, nullptr, ctrl, not_check_ratio, out_seg_off, out_seg, seg_cap, out_status);
+}
+int vigo_collision_segs_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, double not_check_ratio,
+                              int32_t* out_seg_off, int32_t* out_seg, int64_t seg_cap, int32_t* out_status) {
+    VIGO_TRY(check_mixed_rows(h, B, Ns, n_pts, "vigo_collision_segs_mixed"));
+    return collision_segs(h, "vigo_collision_segs_mixed", B, Ns, n_pts, ctrl, not_check_ratio, out_seg_off, out_seg, seg_cap, out_status);
+}
+
+int vigo_path_search(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg, double not_check_ratio,
+                     double step, const int32_t pool[3], double min_height, double max_height, int max_expansions, int search_path_cap,
+                     int64_t seg_cap, int64_t point_cap, int32_t* out_status, int32_t* out_seg_off, int32_t* out_seg, int32_t* out_path_off,
+                     double* out_path, int32_t* out_counts) {
+    return path_search(h, "vigo_path_search", B, N, nullptr, ctrl, seg_off, seg, not_check_ratio, step, pool, min_height, max_height,
+                       max_expansions, search_path_cap, seg_cap, point_cap, out_status, out_seg_off, out_seg, out_path_off, out_path, out_counts);
+}
+int vigo_path_search_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
+                           double not_check_ratio, double step, const int32_t pool[3], double min_height, double max_height, int max_expansions,
+                           int search_path_cap, int64_t seg_cap, int64_t point_cap, int32_t* out_status, int32_t* out_seg_off, int32_t* out_seg,
+                           int32_t* out_path_off, double* out_path, int32_t* out_counts) {
+    VIGO_TRY(check_mixed_rows(h, B, Ns, n_pts, "vigo_path_search_mixed"));
+    return path_search(h, "vigo_path_search_mixed", B, Ns, n_pts, ctrl, seg_off, seg, not_check_ratio, step, pool, min_height, max_height,
+                       max_expansions, search_path_cap, seg_cap, point_cap, out_status, out_seg_off, out_seg, out_path_off, out_path, out_counts);
+}
+
+int vigo_rebound_reguide(vigo_handle_t h, int B, int N, const double* ctrl, const int32_t* guide_off, const double* guide_pv,
+                         const uint8_t* guide_unk, double* weights, double not_check_ratio, double step, const int32_t pool[3],
+                         double min_height, double max_height, int max_expansions, int search_path_cap, vigo_rebound_state_t* state,
+                         int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv, uint8_t* out_guide_unk, int64_t seg_cap,
+                         int64_t point_cap, int32_t* out_path_seg_off, int32_t* out_path_off, double* out_path, int32_t* out_status) {
+    return rebound_reguide(h, "vigo_rebound_reguide", B, N, nullptr, ctrl, guide_off, guide_pv, guide_unk, weights, not_check_ratio, step, pool,
+                           min_height, max_height, max_expansions, search_path_cap, state, pair_cap, out_guide_off, out_guide_pv, out_guide_unk,
+                           seg_cap, point_cap, out_path_seg_off, out_path_off, out_path, out_status);
+}
+int vigo_rebound_reguide_mixed(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, const int32_t* guide_off,
+                               const double* guide_pv, const uint8_t* guide_unk, double* weights, double not_check_ratio, double step,
+                               const int32_t pool[3], double min_height, double max_height, int max_expansions, int search_path_cap,
+                               vigo_rebound_state_t* state, int64_t pair_cap, int32_t* out_guide_off, double* out_guide_pv,
+                               uint8_t* out_guide_unk, int64_t seg_cap, int64_t point_cap, int32_t* out_path_seg_off, int32_t* out_path_off,
+                               double* out_path, int32_t* out_status) {
+    VIGO_TRY(check_mixed_rows(h, B, Ns, n_pts, "vigo_rebound_reguide_mixed"));
+    return rebound_reguide(h, "vigo_rebound_reguide_mixed", B, Ns, n_pts, ctrl, guide_off, guide_pv, guide_unk, weights, not_check_ratio, step,
+                           pool, min_height, max_height, max_expansions, search_path_cap, state, pair_cap, out_guide_off, out_guide_pv,
+                           out_guide_unk, seg_cap, point_cap, out_path_seg_off, out_path_off, out_path, out_status);
 }
 
 /* ---- ESDF ----------------------------------------------------------------------------------- */

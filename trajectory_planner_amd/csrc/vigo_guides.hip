@@ -15,6 +15,7 @@
 // place: its slot is the control point's offset plus the pushes of the earlier segments.  Plain vector stores, no atomics.
 // The work is latency-bound (a chain of dependent fp64 divisions, square roots and atan2 per control point).
 #include "vigo_guide_core.hpp"
+#include "vigo_rows_core.hpp"
 #include "vigo_grid.hpp"
 #include "vigo_scan.hpp"
 
@@ -23,6 +24,7 @@ namespace {
 
 struct GuideArgs {
     int B, N;
+    const int32_t* n_pts;  // (vigo_guide_assign_mixed) not NULL: N is the row stride, trajectory b has n_pts[b] control points
     const double* ctrl;
     const int32_t* seg_off;
     const int32_t* seg;
@@ -50,13 +52,14 @@ __global__ void __launch_bounds__(1024) k_guide_offsets(GuideArgs A) {
     for (int b = lo; b < hi && !bad; ++b) {
         const int s0 = A.seg_off[b], s1 = A.seg_off[b + 1];
         if (s0 < 0 || s1 < s0) { bad = true; break; }
-        bool deferred = false;
+        const int N = row_count(A.n_pts, b, A.N);         // (a bad count: DEFERRED, its segments are not judged by it)
+        bool deferred = N < 0;
         long long nb = 0;
         for (int k = s0; k < s1; ++k) {
             const int p0 = A.path_off[k], p1 = A.path_off[k + 1];
-            if (p0 < 0 || p1 < p0 || !guide_segment_ok(A.N, A.seg[2 * k], A.seg[2 * k + 1], p1 - p0)) { bad = true; break; }
+            if (p0 < 0 || p1 < p0 || (N > 0 && !guide_segment_ok(N, A.seg[2 * k], A.seg[2 * k + 1], p1 - p0))) { bad = true; break; }
             if (p1 - p0 > kGuidePathCap) deferred = true;
-            nb += guide_pushes_total(A.N, A.seg[2 * k], A.seg[2 * k + 1]);
+            if (N > 0) nb += guide_pushes_total(N, A.seg[2 * k], A.seg[2 * k + 1]);
         }
         n += deferred ? 0 : nb;
     }
@@ -73,15 +76,16 @@ __global__ void __launch_bounds__(1024) k_guide_offsets(GuideArgs A) {
     long long at = mine_end - n;
     for (int b = lo; b < hi; ++b) {
         const int s0 = A.seg_off[b], s1 = A.seg_off[b + 1];
-        bool deferred = false;
+        const int N = row_count(A.n_pts, b, A.N);
+        bool deferred = N < 0;
         for (int k = s0; k < s1; ++k)
             if (A.path_off[k + 1] - A.path_off[k] > kGuidePathCap) deferred = true;
         A.status[b] = deferred ? kGuideDeferred : kGuideOk;
-        for (int i = 0; i < A.N; ++i) {
-            A.off[(size_t)b * A.N + i] = (int32_t)at;
-            if (!deferred)
-                for (int k = s0; k < s1; ++k) at += guide_pushes(A.N, A.seg[2 * k], A.seg[2 * k + 1], i);
-        }
+        at = row_offsets(A.N, deferred ? 0 : N, at, A.off + (size_t)b * A.N, [&](int i) {
+            int n_i = 0;
+            for (int k = s0; k < s1; ++k) n_i += guide_pushes(N, A.seg[2 * k], A.seg[2 * k + 1], i);
+            return n_i;
+        });
     }
     if (tid == 1023) A.off[(size_t)A.B * A.N] = (int32_t)total;
 }
@@ -131,9 +135,9 @@ __global__ void __launch_bounds__(64) k_guide_assign(GridOcc occ, GuideArgs A) {
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
     if (A.status[b] != kGuideOk) return;                  // (the workgroup's: one value for all lanes)
-    const int N = A.N;
-    const double* ctrl = A.ctrl + (size_t)b * N * 3;
-    const int32_t* off = A.off + (size_t)b * N;
+    const int N = row_count(A.n_pts, b, A.N);             // > 0: k_guide_offsets defers a bad count
+    const double* ctrl = A.ctrl + (size_t)b * A.N * 3;
+    const int32_t* off = A.off + (size_t)b * A.N;
     const int s0 = A.seg_off[b], s1 = A.seg_off[b + 1];
     const double res = occ.g.res;
     const int ns = guide_line_samples(res);
@@ -218,17 +222,17 @@ __global__ void __launch_bounds__(64) k_guide_assign(GridOcc occ, GuideArgs A) {
 
 int guide_path_capacity() { return kGuidePathCap; }
 
-int launch_guide_offsets(hipStream_t s, int B, int N, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off, long long pair_cap,
-                         int32_t* out_off, int32_t* out_status, long long* result) {
-    GuideArgs a{B, N, nullptr, seg_off, seg, path_off, nullptr, pair_cap, out_off, nullptr, nullptr, out_status, result};
+int launch_guide_offsets(hipStream_t s, int B, int N, const int32_t* n_pts, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off,
+                         long long pair_cap, int32_t* out_off, int32_t* out_status, long long* result) {
+    GuideArgs a{B, N, n_pts, nullptr, seg_off, seg, path_off, nullptr, pair_cap, out_off, nullptr, nullptr, out_status, result};
     hipLaunchKernelGGL(k_guide_offsets, dim3(1), dim3(1024), 0, s, a);
     return (int)hipGetLastError();
 }
 
-int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
-                        const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
+int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                        const int32_t* seg, const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
                         const int32_t* status) {
-    GuideArgs a{B, N, ctrl, seg_off, seg, path_off, path, 0, const_cast<int32_t*>(off), out_pv, out_unk, const_cast<int32_t*>(status), nullptr};
+    GuideArgs a{B, N, n_pts, ctrl, seg_off, seg, path_off, path, 0, const_cast<int32_t*>(off), out_pv, out_unk, const_cast<int32_t*>(status), nullptr};
     hipLaunchKernelGGL(k_guide_assign, dim3(B), dim3(64), 0, s, GridOcc{g}, a);
     return (int)hipGetLastError();
 }

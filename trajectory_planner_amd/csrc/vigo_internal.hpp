@@ -261,18 +261,20 @@ int launch_astar(hipStream_t s, const GridView& g, int Q, const double* start, c
                  int32_t* out_stats, LaunchState& L);
 
 // batched guide assignment (vigo_guides.hip): the offsets kernel fills result[2] = {pairs of the call, bad lists} and,
-// when the lists are good and the pairs fit, statuses and offsets; the assign kernel then writes the pairs in place
+// when the lists are good and the pairs fit, statuses and offsets; the assign kernel then writes the pairs in place.
+// n_pts not NULL (the _mixed entries): N is the row stride of ctrl and of the offsets, trajectory b has n_pts[b] points
 int guide_path_capacity();
-int launch_guide_offsets(hipStream_t s, int B, int N, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off, long long pair_cap,
+int launch_guide_offsets(hipStream_t s, int B, int N, const int32_t* n_pts, const int32_t* seg_off, const int32_t* seg, const int32_t* path_off, long long pair_cap,
                          int32_t* out_off, int32_t* out_status, long long* result);
-int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const double* ctrl, const int32_t* seg_off, const int32_t* seg,
-                        const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
+int launch_guide_assign(hipStream_t s, const GridView& g, int B, int N, const int32_t* n_pts, const double* ctrl, const int32_t* seg_off,
+                        const int32_t* seg, const int32_t* path_off, const double* path, const int32_t* off, double* out_pv, uint8_t* out_unk,
                         const int32_t* status);
 
 // batched findCollisionSeg / pathSearch (vigo_pathsearch.hip).  Everything but the out_* members is device scratch of
 // the call; the kernels and what vigo_api.cpp reads back between them are listed in that file's header.
 struct PathSearchArgs {
     int B, N;
+    const int32_t* n_pts;        // (the _mixed entries) not NULL: N is the row stride, trajectory b has n_pts[b] control points
     const double* ctrl;
     double not_check_ratio;
     const int32_t* seg_off_in;   // the supplied list, or NULL: the scan over pt / ln
@@ -326,6 +328,7 @@ int launch_ps_write(hipStream_t s, const PathSearchArgs& a, const PathSearchWork
 // are listed in that file's header.  Everything but the out_* members and the caller's inputs is device scratch.
 struct ReguideArgs {
     int B, N;
+    const int32_t* n_pts;        // (vigo_rebound_reguide_mixed) not NULL: N is the row stride, trajectory b has n_pts[b] control points
     const double* ctrl;
     const int32_t* guide_off;    // the current CSR, or NULL: no guides
     const double* guide_pv;

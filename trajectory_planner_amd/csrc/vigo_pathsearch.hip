@@ -21,6 +21,7 @@
 // one-workgroup kernels are k_guide_offsets' shape (vigo_scan.hpp: a slice of the batch per thread, a 1024-thread scan).
 // Plain vector stores, no atomics.
 #include "vigo_pathsearch_core.hpp"
+#include "vigo_rows_core.hpp"
 #include "vigo_internal.hpp"
 #include "vigo_scan.hpp"
 
@@ -43,20 +44,22 @@ __global__ void __launch_bounds__(1024) k_ps_count(PathSearchArgs A) {
     long long n = 0;
     bool bad = false;
     for (int b = lo; b < hi && !bad; ++b) {
+        // (the _mixed entries) the trajectory's own count in a row of A.N; a bad count defers it: no segment, no search
+        const int N = row_count(A.n_pts, b, A.N);
         int nb = 0;
         if (A.seg_in) {
             const int s0 = ps_list_first(A, b), s1 = ps_list_end(A, b);
             if (s0 < 0 || s1 < s0) { bad = true; break; }
             nb = s1 - s0;
-            if (nb <= kPathsMaxSegs)
+            if (nb <= kPathsMaxSegs && N > 0)
                 for (int k = s0; k < s1; ++k) {
                     const int f = A.seg_in[2 * k], e = A.seg_in[2 * k + 1];
-                    if (f < 0 || f >= A.N || e < 0 || e >= A.N) { bad = true; break; }
+                    if (f < 0 || f >= N || e < 0 || e >= N) { bad = true; break; }
                 }
-        } else {
-            nb = collision_segs(A.N, A.not_check_ratio, FlagOcc{A.pt + (size_t)b * A.N}, FlagOcc{A.ln + (size_t)b * A.N}, 0, nullptr);
+        } else if (N > 0) {
+            nb = collision_segs(N, A.not_check_ratio, FlagOcc{A.pt + (size_t)b * A.N}, FlagOcc{A.ln + (size_t)b * A.N}, 0, nullptr);
         }
-        const bool over = nb > kPathsMaxSegs;
+        const bool over = nb > kPathsMaxSegs || N < 0;
         A.pre[b] = over ? 1 : 0;
         A.n_in[b] = over ? 0 : nb;
         n += over ? 0 : nb;
@@ -84,8 +87,8 @@ __global__ void __launch_bounds__(256) k_ps_fill(PathSearchArgs A, int32_t* dst_
     if (A.seg_in) {
         const int32_t* src = A.seg_in + 2 * (size_t)ps_list_first(A, b);
         for (int k = 0; k < 2 * n; ++k) seg[k] = src[k];
-    } else if (n > 0) {
-        collision_segs(A.N, A.not_check_ratio, FlagOcc{A.pt + (size_t)b * A.N}, FlagOcc{A.ln + (size_t)b * A.N}, n, seg);
+    } else if (n > 0) {                                   // (a bad count has none: k_ps_count)
+        collision_segs(row_count(A.n_pts, b, A.N), A.not_check_ratio, FlagOcc{A.pt + (size_t)b * A.N}, FlagOcc{A.ln + (size_t)b * A.N}, n, seg);
     }
     if (!start) return;
     const double* c = A.ctrl + (size_t)b * A.N * 3;

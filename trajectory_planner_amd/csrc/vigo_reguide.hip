@@ -21,6 +21,7 @@
 // Nothing of the caller's is written before k_guide_merge_offsets has passed.  Plain vector stores, no atomics.
 #include "vigo_reguide_core.hpp"
 #include "vigo_guide_core.hpp"
+#include "vigo_rows_core.hpp"
 #include "vigo_grid.hpp"
 #include "vigo_scan.hpp"
 
@@ -171,19 +172,25 @@ __global__ void __launch_bounds__(1024) k_rebound_compact(int B, vigo_rebound_st
 
 __global__ void __launch_bounds__(64) k_reguide_list(GridView g, ReguideArgs A) {
     __shared__ uint8_t s_pt[VIGO_MAX_CTRL_POINTS], s_ln[VIGO_MAX_CTRL_POINTS];
-    const int b = blockIdx.x, lane = threadIdx.x, N = A.N;
-    const int32_t* off = A.guide_off ? A.guide_off + (size_t)b * N : nullptr;
-    if (off) {                                            // (every trajectory's offsets: the merge copies them all)
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int32_t* off = A.guide_off ? A.guide_off + (size_t)b * A.N : nullptr;
+    if (off) {                                            // (every trajectory's offsets, the whole row: the merge copies them all)
         bool bad = b == 0 && lane == 0 && off[0] < 0;
-        for (int i = lane; i < N; i += 64) bad = bad || off[i + 1] < off[i];
+        for (int i = lane; i < A.N; i += 64) bad = bad || off[i + 1] < off[i];
         if (bad) A.result[0] = 1;                         // (the same value from whoever sees one)
+    }
+    // (vigo_rebound_reguide_mixed) the trajectory's own count in a row of A.N; a bad count defers it, state untouched
+    const int N = row_count(A.n_pts, b, A.N);
+    if (N < 0) {                                          // (the workgroup's)
+        if (lane == 0) { A.kind[b] = kReguideDeferred; A.n_list[b] = 0; A.n_new[b] = 0; }
+        return;
     }
     const vigo_rebound_state_t& st = A.state[b];
     if (!(st.status == VIGO_RB_NEEDS_HOST && st.gate_static != 0 && st.fail_count < 4)) {     // (the workgroup's)
         if (lane == 0) { A.kind[b] = kReguideSkipped; A.n_list[b] = 0; A.n_new[b] = 0; }
         return;
     }
-    const double* c = A.ctrl + (size_t)b * N * 3;
+    const double* c = A.ctrl + (size_t)b * A.N * 3;
     ctrl_flags_wave(g, c, N, lane, s_pt, s_ln);
     if (lane != 0) return;
     int32_t seg[2 * kSegs];
@@ -233,14 +240,14 @@ __global__ void __launch_bounds__(1024) k_guide_merge_offsets(ReguideArgs A) {
     if (tid == 0) A.result[1] = total;
     if (total > A.pair_cap || total > 0x7fffffffLL) return;                   // nothing else is written
     // pass 2: the merged offsets of my trajectories
+    // (every control point of the row, whatever the count: the old pairs are copied, the padding's ranges are empty)
     long long at = mine_end - n;
     for (int b = lo; b < hi; ++b) {
         const bool done = A.outcome[b] == kReguideDone;
-        for (int i = 0; i < N; ++i) {
+        at = row_offsets(N, N, at, A.out_guide_off + (size_t)b * N, [&](int i) {
             const size_t q = (size_t)b * N + i;
-            A.out_guide_off[q] = (int32_t)at;
-            at += old_pairs(q) + (done ? A.g_off[q + 1] - A.g_off[q] : 0);
-        }
+            return old_pairs(q) + (done ? A.g_off[q + 1] - A.g_off[q] : 0);
+        });
     }
     if (tid == 1023) A.out_guide_off[(size_t)A.B * N] = (int32_t)total;
 }
@@ -250,11 +257,7 @@ __global__ void __launch_bounds__(64) k_guide_merge(GridView g, ReguideArgs A) {
     const int32_t* out_off = A.out_guide_off + (size_t)b * N;
     const bool done = A.outcome[b] == kReguideDone;       // (one value for all lanes; the offsets hold new pairs only then)
     for (int q = out_off[0] + lane; q < out_off[N]; q += 64) {
-        int lo = 0, hi = N - 1;                           // the control point of slot q: the last i with out_off[i] <= q
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (out_off[mid] <= q) lo = mid; else hi = mid - 1;
-        }
+        const int lo = row_slot_owner(out_off, N, q);     // the control point of slot q, searched over the whole row
         const size_t at = (size_t)b * N + lo;
         const int j = q - out_off[lo];
         const int n_old = A.guide_off ? A.guide_off[at + 1] - A.guide_off[at] : 0;

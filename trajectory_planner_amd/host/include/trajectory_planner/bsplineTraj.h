@@ -171,9 +171,19 @@ public:
          * On: planners that share everything but the count share a batch when their counts lie in one shape class of the
          * kernels — all 7 .. 32, or all 33 .. 64; counts above 64 keep a batch per count.  A group whose counts are all
          * equal calls the uniform entry, so a workload of one count runs the same kernels under either setting
-         * (include/vigo.h, "mixed control-point counts").  Every other stage keeps its grouping by exact count: the
-         * opt-in device stages (A*, prologue chain, re-guide), the gates, costGrad and the host-driven loop's gates. */
+         * (include/vigo.h, "mixed control-point counts").  The gates, costGrad and the host-driven loop's gates keep their
+         * grouping by exact count; so do the opt-in device stages (A*, guide launch, prologue chain, re-guide) unless
+         * mixedPrologue regroups them. */
         bool mixedBatches = false;
+        /* The opt-in device stages around the solves — the devicePrologue chain, the deviceGuides = 1 launch, the
+         * deviceAstar launches and the deviceReguide = 1 call — group their planners as the mixed solves do
+         * (sameSolveGroup(other, true): everything but the count shared, the counts in one shape class, 7 .. 32 or
+         * 33 .. 64) instead of by exact count.  Rows are padded to the group's largest count and the stage calls its
+         * _mixed entry (vigo_path_search_mixed, vigo_guide_assign_mixed, vigo_rebound_reguide_mixed; the A* launch has no
+         * count at all); a group whose counts are all equal calls the uniform entry, as mixedBatches does.  Deferred,
+         * failed and no-device planners take the host routes they take when this is off, and a plan does not depend on
+         * the setting: fewer device groups open (BatchStats::prologueGroups, reguideGroups). */
+        bool mixedPrologue = false;
         /* Steps 5-6 of makePlan() (the spline object, linearFeasibilityReparam) and, for the calls with trajectories, the
          * samples of evalTrajToMsg.  Off: per planner on the host workers, as it always was.  On: ONE vigo_traj_finish
          * call per device group — planners that share a device target, ts_ and controlPointsTs_ (the sample step is
@@ -227,6 +237,8 @@ public:
         long long solveBatches = 0, solvePlanners = 0;     /* device batches the solves and device rounds opened, under either setting of mixedBatches, and the planners in them */
         double prologueSeconds = 0.0;                      /* wall time of makePlanBatch's prologue, summed over the parts of a pipelined call, which run side by side */
         double chainSeconds = 0.0;                         /* ... of devicePrologue's chains (upload to installed results) */
+        long long prologueGroups = 0;                      /* device groups the prologue's stages opened (devicePrologue chains, deviceGuides = 1 and deviceAstar launches), under either setting of mixedPrologue */
+        long long reguideGroups = 0;                       /* ... and the deviceReguide = 1 calls */
         BatchStats& operator+=(const BatchStats& o) {
             astarDecided += o.astarDecided; astarHost += o.astarHost;
             guidesDecided += o.guidesDecided; guidesHost += o.guidesHost;
@@ -237,6 +249,7 @@ public:
             epilogueGroups += o.epilogueGroups;
             solveBatches += o.solveBatches; solvePlanners += o.solvePlanners;
             prologueSeconds += o.prologueSeconds; chainSeconds += o.chainSeconds;
+            prologueGroups += o.prologueGroups; reguideGroups += o.reguideGroups;
             return *this;
         }
     };
@@ -305,6 +318,8 @@ public:
     static bool deviceResidentRebound();
     static void setMixedBatches(bool on);                      /* BatchOptions::mixedBatches */
     static bool mixedBatches();
+    static void setMixedPrologue(bool on);                     /* BatchOptions::mixedPrologue */
+    static bool mixedPrologue();
     static void setDeviceEpilogue(bool on);                    /* BatchOptions::deviceEpilogue */
     static bool deviceEpilogue();
     static void setBatchPipelineThreshold(size_t planners);    /* BatchOptions::pipelineThreshold */

@@ -62,6 +62,7 @@ void bsplineTraj::setDeviceReguide(int mode) { editDefaults([=](BatchOptions& o)
 void bsplineTraj::setReguideStepLog(std::vector<ReguideStepRecord>* log) { editDefaults([=](BatchOptions& o) { o.reguideStepLog = log; }); }
 void bsplineTraj::setDeviceResidentRebound(bool on) { editDefaults([=](BatchOptions& o) { o.deviceResidentRebound = on; }); }
 void bsplineTraj::setMixedBatches(bool on) { editDefaults([=](BatchOptions& o) { o.mixedBatches = on; }); }
+void bsplineTraj::setMixedPrologue(bool on) { editDefaults([=](BatchOptions& o) { o.mixedPrologue = on; }); }
 void bsplineTraj::setDeviceEpilogue(bool on) { editDefaults([=](BatchOptions& o) { o.deviceEpilogue = on; }); }
 void bsplineTraj::setBatchPipelineThreshold(size_t planners) { editDefaults([=](BatchOptions& o) { o.pipelineThreshold = planners; }); }
 void bsplineTraj::setDeviceSeed(bool on) { editDefaults([=](BatchOptions& o) { o.deviceSeed = on; }); }
@@ -73,6 +74,7 @@ bool bsplineTraj::devicePrologue() { return defaultBatchOptions().devicePrologue
 int bsplineTraj::deviceReguide() { return defaultBatchOptions().deviceReguide; }
 bool bsplineTraj::deviceResidentRebound() { return defaultBatchOptions().deviceResidentRebound; }
 bool bsplineTraj::mixedBatches() { return defaultBatchOptions().mixedBatches; }
+bool bsplineTraj::mixedPrologue() { return defaultBatchOptions().mixedPrologue; }
 bool bsplineTraj::deviceEpilogue() { return defaultBatchOptions().deviceEpilogue; }
 bool bsplineTraj::deviceSeed() { return defaultBatchOptions().deviceSeed; }
 bool bsplineTraj::mixedFit() { return defaultBatchOptions().mixedFit; }
@@ -476,7 +478,8 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, PlanBa
     std::vector<size_t> owners;                       // the planners with jobs, in call order
     for (size_t i = 0; i < P; ++i)
         if (!jobsOf[i].empty()) owners.push_back(i);
-    SearchGroup::forEach(planners, owners, false, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
+    // (the searches have no control-point count: under mixedPrologue the planners of a shape class share the launch)
+    SearchGroup::forEach(planners, owners, false, pb.o.mixedPrologue, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
         std::vector<size_t> idx;
         std::vector<double> start, end;
         for (size_t i : who)
@@ -495,6 +498,7 @@ void bsplineTraj::runAstarJobs(const std::vector<bsplineTraj*>& planners, PlanBa
         std::vector<double> path((size_t)Q * kAstarPathCap * 3);
         if (!st.start.upload(start) || !st.end.upload(end) || !st.status.alloc(status.size()) || !st.len.alloc(len.size()) || !st.path.alloc(path.size()))
             return;
+        pb.stats.prologueGroups += 1;
         if (!deviceCallOk(vigo_astar_search(h, Q, st.start.get(), st.end.get(), g.res, g.pool, lead->minHeight_, lead->maxHeight_,
                                             pb.o.deviceAstarBudget, kAstarPathCap, st.status.get(), st.len.get(), st.path.get(), nullptr),
                           "vigo_astar_search", h))
@@ -625,12 +629,12 @@ bool downloadPathsAndPairs(int S, long long pointCap, long long nPairs, const St
 // what prologueOnDevice stages per group: vigo_path_search's outputs are vigo_guide_assign's inputs, in place
 struct PrologueStage {
     Staged<double> ctrl, path, pv;                                   // [B][N][3]; [pointCap][3]; [pairCap][6]
-    Staged<int32_t> status, segOff, seg, pathOff, counts, off, gstatus;
+    Staged<int32_t> status, segOff, seg, pathOff, counts, off, gstatus, npts;   // npts [B]: a group of mixed counts only
 };
 // ... assignGuidesBatch, which uploads the lists the planners hold
 struct GuideStage {
     Staged<double> ctrl, path, pv;
-    Staged<int32_t> segOff, seg, pathOff, off, status;
+    Staged<int32_t> segOff, seg, pathOff, off, status, npts;
 };
 // ... and reguideOnDevice on top of uploadBatch's set
 struct ReguideStage {
@@ -641,7 +645,8 @@ struct ReguideStage {
 }  // namespace
 
 // Steps 1-3 for all planners under devicePrologue.  Per group of planners that share a batch key and a node
-// pool: control points up, vigo_path_search on the scanned segments, vigo_guide_assign on its output (device pointers,
+// pool (mixedPrologue: whatever their counts inside a shape class — rows padded to the group's largest count, the _mixed
+// entries; a group of one count calls the uniform ones): control points up, vigo_path_search on the scanned segments, vigo_guide_assign on its output (device pointers,
 // nothing repacked), then one round of downloads and the results installed per planner.  What is left (see the header)
 // runs findCollisionSeg -> pathSearch -> assignGuidesCore on the workers.
 // Buffer sizes: segCap = B * VIGO_MAX_COLLISION_SEGS is the entry's own bound.  pointCap = B * 2 * (kAstarPathCap + 1) and
@@ -659,10 +664,11 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
     for (size_t i = 0; i < P; ++i)
         if (planners[i]->init_ && planners[i]->link_.map()) owners.push_back(i);
     const double tc0 = wallSeconds();
-    SearchGroup::forEach(planners, owners, true, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
+    SearchGroup::forEach(planners, owners, true, pb.o.mixedPrologue, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
         const int N = g.N, B = (int)who.size();
-        std::vector<double> ctrl;
-        for (size_t i : who) vigo_host::appendCtrl(planners[i]->optData_.controlPoints, ctrl);
+        HostBatch rows(N);
+        for (size_t i : who) rows.addRow(planners[i]->optData_.controlPoints.data(), (int)planners[i]->optData_.controlPoints.cols());
+        const std::vector<double>& ctrl = rows.ctrl;
         const long long segCap = (long long)B * VIGO_MAX_COLLISION_SEGS, pointCap = (long long)B * 2 * (kAstarPathCap + 1),
                         pairCap = (long long)B * N * 4;
         static thread_local PrologueStage st;
@@ -670,15 +676,25 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
         std::vector<int32_t> status(B), segOff(B + 1), counts((size_t)B * 2), off((size_t)B * N + 1, 0), gstatus(B, VIGO_GUIDE_DEFERRED);
         if (!st.ctrl.upload(ctrl) || !st.status.alloc(status.size()) || !st.segOff.alloc(segOff.size()) || !st.seg.alloc((size_t)segCap * 2) ||
             !st.pathOff.alloc((size_t)segCap + 1) || !st.path.alloc((size_t)pointCap * 3) || !st.counts.alloc(counts.size()) ||
-            !st.off.alloc(off.size()) || !st.pv.alloc((size_t)pairCap * 6) || !st.gstatus.alloc(gstatus.size()))
+            !st.off.alloc(off.size()) || !st.pv.alloc((size_t)pairCap * 6) || !st.gstatus.alloc(gstatus.size()) ||
+            (!g.uniform && !st.npts.upload(rows.npts)))
             return;
-        if (!deviceCallOk(vigo_path_search(h, B, N, st.ctrl.get(), nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_,
-                                           pb.o.deviceAstarBudget, kAstarPathCap, segCap, pointCap, st.status.get(), st.segOff.get(), st.seg.get(),
-                                           st.pathOff.get(), st.path.get(), st.counts.get()),
-                          "vigo_path_search", h))
+        pb.stats.prologueGroups += 1;
+        if (g.uniform ? !deviceCallOk(vigo_path_search(h, B, N, st.ctrl.get(), nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool, lead->minHeight_,
+                                                       lead->maxHeight_, pb.o.deviceAstarBudget, kAstarPathCap, segCap, pointCap, st.status.get(),
+                                                       st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(), st.counts.get()),
+                                      "vigo_path_search", h)
+                      : !deviceCallOk(vigo_path_search_mixed(h, B, N, st.npts.get(), st.ctrl.get(), nullptr, nullptr, lead->notCheckRatio_, g.res, g.pool,
+                                                             lead->minHeight_, lead->maxHeight_, pb.o.deviceAstarBudget, kAstarPathCap, segCap, pointCap,
+                                                             st.status.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(),
+                                                             st.counts.get()),
+                                      "vigo_path_search_mixed", h))
             return;
-        const bool guided = vigo_guide_assign(h, B, N, st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(), pairCap,
-                                              st.off.get(), st.pv.get(), nullptr, st.gstatus.get()) == VIGO_OK;   // (not: the pairs do not fit — the twin assigns them)
+        // (not VIGO_OK: the pairs do not fit — the twin assigns them)
+        const bool guided = (g.uniform ? vigo_guide_assign(h, B, N, st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(), pairCap,
+                                                           st.off.get(), st.pv.get(), nullptr, st.gstatus.get())
+                                       : vigo_guide_assign_mixed(h, B, N, st.npts.get(), st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(),
+                                                                 st.path.get(), pairCap, st.off.get(), st.pv.get(), nullptr, st.gstatus.get())) == VIGO_OK;
         if (!vigo_host::threadSync() || !st.status.download(status) || !st.segOff.download(segOff) || !st.counts.download(counts)) return;
         if (guided && (!st.off.download(off) || !st.gstatus.download(gstatus))) return;
         const int S = segOff[B];
@@ -699,7 +715,7 @@ void bsplineTraj::prologueOnDevice(const std::vector<bsplineTraj*>& planners, Pl
             for (int k = segOff[b]; k < segOff[b + 1]; ++k) p->collisionSeg_.push_back({seg[2 * (size_t)k], seg[2 * (size_t)k + 1]});
             vigo_host::installPaths(p->astarPaths_, segOff[b], segOff[b + 1], pathOff.data(), path.data());
             if (gstatus[b] != VIGO_GUIDE_OK) { needGuides[who[b]] = 1; continue; }
-            vigo_host::installGuides(p->optData_, N, off.data() + (size_t)b * N, pv.data());
+            vigo_host::installGuides(p->optData_, rows.npts[b], off.data() + (size_t)b * N, pv.data());
             outcome[who[b]] = 1;
         }
     });
@@ -780,14 +796,16 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, P
         auto same = [&](size_t a, size_t b) {
             const bsplineTraj* x = planners[owners[a]];
             const bsplineTraj* y = planners[owners[b]];
-            return x->sameBatchKey(*y) && x->optData_.controlPoints.cols() == y->optData_.controlPoints.cols();
+            return x->sameSolveGroup(*y, pb.o.mixedPrologue);      // (one count per group, or with mixedPrologue a shape class)
         };
         vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
             bsplineTraj* lead = planners[owners[members[0]]];
             if (!lead->syncDevice()) return;
-            const int N = lead->optData_.controlPoints.cols();
+            int N = 0;                                    // the row stride: the group's one count, or its largest
+            for (size_t m : members) N = std::max(N, (int)planners[owners[m]]->optData_.controlPoints.cols());
+            HostBatch rows(N);
             std::vector<size_t> who;
-            std::vector<double> ctrl, path;
+            std::vector<double> path;
             std::vector<int32_t> segOff{0}, seg, pathOff{0};
             long long pairs = 0;
             for (size_t m : members) {
@@ -806,9 +824,10 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, P
                     continue;
                 }
 #endif
-                for (size_t k = seg0; k < seg.size() / 2; ++k) pairs += vigo::guide_pushes_total(N, seg[2 * k], seg[2 * k + 1]);
+                const int n = (int)p->optData_.controlPoints.cols();
+                for (size_t k = seg0; k < seg.size() / 2; ++k) pairs += vigo::guide_pushes_total(n, seg[2 * k], seg[2 * k + 1]);
                 segOff.push_back((int32_t)(seg.size() / 2));
-                vigo_host::appendCtrl(p->optData_.controlPoints, ctrl);
+                rows.addRow(p->optData_.controlPoints.data(), n);
                 who.push_back(owners[m]);
             }
             const int B = (int)who.size();
@@ -821,19 +840,24 @@ void bsplineTraj::assignGuidesBatch(const std::vector<bsplineTraj*>& planners, P
             static thread_local GuideStage st;
             vigo_handle_t h = lead->link_.handle();
             std::vector<int32_t> off((size_t)B * N + 1), status(B);
-            if (!st.ctrl.upload(ctrl) || !st.segOff.upload(segOff) || !st.seg.upload(seg) || !st.pathOff.upload(pathOff) || !st.path.upload(path) ||
-                !st.off.alloc(off.size()) || !st.pv.alloc((size_t)cap * 6) || !st.status.alloc(status.size()))
+            const bool uniform = rows.uniform();
+            if (!st.ctrl.upload(rows.ctrl) || !st.segOff.upload(segOff) || !st.seg.upload(seg) || !st.pathOff.upload(pathOff) || !st.path.upload(path) ||
+                !st.off.alloc(off.size()) || !st.pv.alloc((size_t)cap * 6) || !st.status.alloc(status.size()) || (!uniform && !st.npts.upload(rows.npts)))
                 return;
-            if (!deviceCallOk(vigo_guide_assign(h, B, N, st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(), cap, st.off.get(),
-                                                st.pv.get(), nullptr, st.status.get()),
-                              "vigo_guide_assign", h))
+            pb.stats.prologueGroups += 1;
+            if (uniform ? !deviceCallOk(vigo_guide_assign(h, B, N, st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(), st.path.get(), cap,
+                                                          st.off.get(), st.pv.get(), nullptr, st.status.get()),
+                                        "vigo_guide_assign", h)
+                        : !deviceCallOk(vigo_guide_assign_mixed(h, B, N, st.npts.get(), st.ctrl.get(), st.segOff.get(), st.seg.get(), st.pathOff.get(),
+                                                                st.path.get(), cap, st.off.get(), st.pv.get(), nullptr, st.status.get()),
+                                        "vigo_guide_assign_mixed", h))
                 return;
             if (!vigo_host::threadSync() || !st.off.download(off) || !st.status.download(status)) return;
             std::vector<double> pv((size_t)off.back() * 6);
             if (off.back() < 0 || off.back() > cap || (!pv.empty() && !st.pv.download(pv))) return;
             for (int b = 0; b < B; ++b) {
                 if (status[b] != VIGO_GUIDE_OK) continue;
-                vigo_host::installGuides(planners[who[b]]->optData_, N, off.data() + (size_t)b * N, pv.data());
+                vigo_host::installGuides(planners[who[b]]->optData_, rows.npts[b], off.data() + (size_t)b * N, pv.data());
                 done[who[b]] = 1;
             }
         });
@@ -893,15 +917,16 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
     for (size_t a = 0; a < active.size(); ++a)
         if (devOk[a] && reguideEligible(pb.rb[pb.activeIdx[a]]) && active[a]->collisionSeg_.size() <= (size_t)VIGO_MAX_COLLISION_SEGS) owners.push_back(a);
     long long nDecided = 0;
-    SearchGroup::forEach(active, owners, true, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
-        const int N = g.N, B = (int)who.size();
+    SearchGroup::forEach(active, owners, true, pb.o.mixedPrologue, [&](bsplineTraj* lead, const SearchGroup& g, const std::vector<size_t>& who) {
+        const int N = g.N, B = (int)who.size();           // (mixedPrologue: rows of the group's largest count, as deviceRounds stages them)
         if (N > VIGO_MAX_CTRL_POINTS) return;
         HostBatch hb(N);
         std::vector<vigo_rebound_state_t> state;
         for (size_t a : who) {
             const bsplineTraj* p = active[a];
             const Rebound& r = pb.rb[pb.activeIdx[a]];
-            hb.add(p->optData_.controlPoints.data(), p->optData_, {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
+            hb.add(p->optData_.controlPoints.data(), (int)p->optData_.controlPoints.cols(), p->optData_,
+                   {p->weightDistance_, p->weightSmoothness_, p->weightFeasibility_, p->weightDynamicObstacle_});
             vigo_rebound_state_t st;
             std::memset(&st, 0, sizeof(st));
             st.status = VIGO_RB_NEEDS_HOST;
@@ -923,11 +948,18 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             !dv.pathSegOff.alloc(pathSegOff.size()) || !dv.pathOff.alloc((size_t)segCap + 1) || !dv.path.alloc((size_t)pointCap * 3) ||
             !dv.status.alloc(status.size()))
             return;
-        if (!deviceCallOk(vigo_rebound_reguide(h, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,   // (no pairs at all: "no guides")
-                                               lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_, pb.o.deviceAstarBudget,
-                                               kAstarPathCap, dv.state.get(), pairCap, dv.off.get(), dv.pv.get(), nullptr, segCap, pointCap,
-                                               dv.pathSegOff.get(), dv.pathOff.get(), dv.path.get(), dv.status.get()),
-                          "vigo_rebound_reguide", h))
+        pb.stats.reguideGroups += 1;
+        // (no pairs at all: "no guides")
+        if (d.npts ? !deviceCallOk(vigo_rebound_reguide_mixed(h, B, N, d.npts, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,
+                                                              lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_, pb.o.deviceAstarBudget,
+                                                              kAstarPathCap, dv.state.get(), pairCap, dv.off.get(), dv.pv.get(), nullptr, segCap, pointCap,
+                                                              dv.pathSegOff.get(), dv.pathOff.get(), dv.path.get(), dv.status.get()),
+                                   "vigo_rebound_reguide_mixed", h)
+                   : !deviceCallOk(vigo_rebound_reguide(h, B, N, d.ctrl, d.gpv ? d.goff : nullptr, d.gpv, d.gunk, d.weights,
+                                                        lead->notCheckRatio_, g.res, g.pool, lead->minHeight_, lead->maxHeight_, pb.o.deviceAstarBudget,
+                                                        kAstarPathCap, dv.state.get(), pairCap, dv.off.get(), dv.pv.get(), nullptr, segCap, pointCap,
+                                                        dv.pathSegOff.get(), dv.pathOff.get(), dv.path.get(), dv.status.get()),
+                                   "vigo_rebound_reguide", h))
             return;
         if (!vigo_host::threadSync() || !dv.status.download(status) || !dv.off.download(off) || !dv.pathSegOff.download(pathSegOff) ||
             !dv.state.download(state) || !batchStage().weights.download(hb.weights))
@@ -947,7 +979,7 @@ void bsplineTraj::reguideOnDevice(PlanBatch& pb, const std::vector<uint8_t>& dev
             if (status[b] == VIGO_REGUIDE_DONE) {
                 vigo_host::installPaths(p->astarPaths_, pathSegOff[b], pathSegOff[b + 1], pathOff.data(), path.data());
                 // the merged CSR holds a control point's old pairs first: what follows them is this step's
-                vigo_host::installGuides(p->optData_, N, off.data() + (size_t)b * N, pv.data(), true);
+                vigo_host::installGuides(p->optData_, hb.npts[b], off.data() + (size_t)b * N, pv.data(), true);
             }
             p->weightDistance_ = hb.weights[4 * (size_t)b + 0];
             p->weightDynamicObstacle_ = hb.weights[4 * (size_t)b + 3];

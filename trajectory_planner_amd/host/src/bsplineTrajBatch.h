@@ -65,12 +65,14 @@ inline bool boxInRegion(const mapRegion& R, const double* xyz, size_t n, const d
 #endif
 
 // What the device searches of a group of planners share, from the group's lead: the map's resolution, the A* node pool
-// setMap sizes from maxObstacleSize_ (BT.cpp:187-195), the control-point count.
+// setMap sizes from maxObstacleSize_ (BT.cpp:187-195), the control-point count (the row stride: under mixedPrologue the
+// largest count of the planners the group takes).
 struct bsplineTraj::SearchGroup {
     double res;
     int32_t pool[3];
     double half[3];        // reach of a search's node pool around the midpoint of its ends: pool / 2 + 1 nodes
     int N;
+    bool uniform = true;   // every planner of the group has N control points: the uniform entries apply
     double notCheckRatio;
     explicit SearchGroup(const bsplineTraj& lead)
         : res(lead.link_.map()->getRes()), N(lead.optData_.controlPoints.cols()), notCheckRatio(lead.notCheckRatio_) {
@@ -85,9 +87,10 @@ struct bsplineTraj::SearchGroup {
             if (pool[k] < 3 || pool[k] > VIGO_ASTAR_MAX_POOL_AXIS) return false;
         return !scan || (N >= 7 && notCheckRatio >= 0.0 && notCheckRatio <= 1.0);
     }
-    // x and y may share such a group: a device batch and a node pool
-    static bool same(const bsplineTraj& x, const bsplineTraj& y) {
-        return x.sameBatchKey(y) && x.maxObstacleSize_(0) == y.maxObstacleSize_(0) && x.maxObstacleSize_(1) == y.maxObstacleSize_(1) &&
+    // x and y may share such a group: a device batch and a node pool; `mixed` (BatchOptions::mixedPrologue): whatever
+    // their counts inside a shape class, as the mixed solves group them
+    static bool same(const bsplineTraj& x, const bsplineTraj& y, bool mixed = false) {
+        return x.sameSolveGroup(y, mixed) && x.maxObstacleSize_(0) == y.maxObstacleSize_(0) && x.maxObstacleSize_(1) == y.maxObstacleSize_(1) &&
                x.maxObstacleSize_(2) == y.maxObstacleSize_(2);
     }
     // May the device search for p among the n points xyz?  Every node pool around a midpoint of two of them, and with it
@@ -104,19 +107,28 @@ struct bsplineTraj::SearchGroup {
     // The opening of a device stage over ps[owners[..]]: fn(lead, g, who) per group (`same`) whose lead syncs its device
     // and whose ranges are valid(scan), who = the group's entries of owners in order — with `scan` (the stage reads the
     // planners' control points) those with their control points inReach.  A group that fails any of this, or is left
-    // empty, is skipped: its planners stay with the host steps.
+    // empty, is skipped: its planners stay with the host steps.  `mixed`: groups of mixed counts (same); g.N is then the
+    // largest count of `who` and g.uniform says whether the counts differ at all.
     template <class Fn>
-    static void forEach(const std::vector<bsplineTraj*>& ps, const std::vector<size_t>& owners, bool scan, Fn fn) {
-        auto sameGroup = [&](size_t a, size_t b) { return same(*ps[owners[a]], *ps[owners[b]]); };
+    static void forEach(const std::vector<bsplineTraj*>& ps, const std::vector<size_t>& owners, bool scan, bool mixed, Fn fn) {
+        auto sameGroup = [&](size_t a, size_t b) { return same(*ps[owners[a]], *ps[owners[b]], mixed); };
         vigo_host::forEachGroup(owners.size(), sameGroup, [&](const std::vector<size_t>& members) {
             bsplineTraj* lead = ps[owners[members[0]]];
             if (!lead->syncDevice()) return;
-            const SearchGroup g(*lead);
+            SearchGroup g(*lead);
             if (!g.valid(scan)) return;
             std::vector<size_t> who;
-            for (size_t m : members)
-                if (!scan || g.inReach(*ps[owners[m]], ps[owners[m]]->optData_.controlPoints.data(), g.N)) who.push_back(owners[m]);
-            if (!who.empty()) fn(lead, g, who);
+            for (size_t m : members) {
+                const Eigen::MatrixXd& c = ps[owners[m]]->optData_.controlPoints;
+                if (!scan || g.inReach(*ps[owners[m]], c.data(), (size_t)c.cols())) who.push_back(owners[m]);
+            }
+            if (who.empty()) return;
+            for (size_t i : who) {
+                const int n = (int)ps[i]->optData_.controlPoints.cols();
+                g.uniform = g.uniform && n == (int)ps[who[0]]->optData_.controlPoints.cols();
+                g.N = i == who[0] ? n : std::max(g.N, n);
+            }
+            fn(lead, g, who);
         });
     }
 };

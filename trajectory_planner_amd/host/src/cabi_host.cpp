@@ -2186,6 +2186,50 @@ int vigo_host_plan_batch_options(const unsigned char* vox, const int* dims, cons
     return rc;
 }
 
+// n planners with a pose list each (as vigo_host_plan_batch_options, whose mask bits and budget these are) through
+// updatePathBatch + makePlanBatch(planners, trajectories, yaw) on one dense byte grid, fresh planners every run, `reps`
+// rounds over
+//   slot 0  the options of `mask`, mixedPrologue off   the opt-in stages group by exact count
+//   slot 1  the same options, mixedPrologue on         ... as the mixed solves do, and call the _mixed entries
+// in turn.  Outputs per slot [2] x ... of the slot's LAST run as vigo_host_plan_batch_options': ok, solver, ncp, ctrl,
+// n_seg + segs, n_guides + guides, n_poses + pos + quat, and n_path_pts + paths (astarPaths_); counts[2][8] of that run:
+// prologueGroups, reguideGroups, prologueDecided, prologueHost, reguideDecided, reguideHost, guidesDecided + astarDecided,
+// solveBatches; per run seconds[2][reps][3]: prologueSeconds, chainSeconds, the call's wall time.  Returns 0, -2 when a
+// buffer is too small, -1 on a bad argument.  Needs a GPU.
+int vigo_host_plan_batch_mixed_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                        const double* path_xyz, const double* cfg, int mask, int budget, int reps, int ncp_cap, long long cap,
+                                        int pose_cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_guides,
+                                        double* guides, int* n_path_pts, double* paths, int* n_poses, double* pos, double* quat, long long* counts,
+                                        double* seconds) {
+    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg || mask < 0) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+    int rc = 0;
+    for (int rep = 0; rep < reps && rc == 0; ++rep)
+        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
+            const FreshPlanners fp = freshPlanners(fx);
+            bsplineTraj::BatchOptions o = optionsOfMask(mask, budget);
+            o.mixedPrologue = slot == 1;
+            bsplineTraj::BatchStats st;
+            std::vector<nav_msgs::Path> traj;
+            double ms = 0.0;
+            const std::vector<bool> planned = timedPlan(fp.ps, o, ms, st, &traj);
+            double* sec = seconds + ((size_t)slot * reps + rep) * 3;
+            sec[0] = st.prologueSeconds; sec[1] = st.chainSeconds; sec[2] = ms * 1e-3;
+            if (rep + 1 < reps) continue;
+            const long long v[8] = {st.prologueGroups, st.reguideGroups, st.prologueDecided, st.prologueHost, st.reguideDecided, st.reguideHost,
+                                    st.guidesDecided + st.astarDecided, st.solveBatches};
+            std::copy(v, v + 8, counts + 8 * slot);
+            rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
+            if (rc == 0) rc = dumpPoses(traj, (size_t)n, slot, pose_cap, n_poses, pos, quat);
+        }
+    return rc;
+}
+
+// BatchOptions::mixedPrologue of the process default, as it stands (0: off, the default)
+int vigo_host_mixed_prologue_default() { return trajPlanner::bsplineTraj::mixedPrologue() ? 1 : 0; }
+
 // the facade's opt-in switches of the process default (bsplineTraj::defaultBatchOptions) as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
 // deviceReguide, bit 6 mixedBatches, bit 7 deviceEpilogue (0: everything off, the default)
 int vigo_host_switches() {

@@ -682,74 +682,103 @@ class Vigo:
             C.c_void_p(stats.data_ptr()) if want_stats else None), "vigo_astar_search")
         return status, length, path, stats
 
-    def guide_assign(self, ctrl, seg_off, seg, path_off, path, pair_cap, want_unknown=True):
+    def _rows_call(self, name, n_pts, ctrl):
+        """(entry, its name, leading arguments) of a prologue entry: the uniform one, or with n_pts (int32 [B], device) its
+        _mixed form, where ctrl is [B,Ns,3] and the counts are device data the kernels check per trajectory"""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, N = ctrl.shape[0], ctrl.shape[1]
+        if n_pts is None:
+            return getattr(self._lib, name), name, (self._h, B, N)
+        _shape(n_pts, (B,), "n_pts")
+        return getattr(self._lib, name + "_mixed"), name + "_mixed", (self._h, B, N, _ptr(n_pts, torch.int32, "n_pts", self.device))
+
+    def guide_assign(self, ctrl, seg_off, seg, path_off, path, pair_cap, want_unknown=True, fill=None, _n_pts=None):
         """vigo_guide_assign: the prologue's guide assignment for B trajectories (ctrl f64 [B,N,3]; seg_off int32 [B+1], seg int32
         [S,2], path_off int32 [S+1], path f64 [P,3]) -> (guide_off int32 [B*N+1], guide_pv f64 [pair_cap,6], guide_unk uint8
         [pair_cap] or None, status int32 [B]: GUIDE_OK / GUIDE_DEFERRED)"""
-        _shape(ctrl, (None, None, 3), "ctrl")
+        fn, who, lead = self._rows_call("vigo_guide_assign", _n_pts, ctrl)
         B, N = ctrl.shape[0], ctrl.shape[1]
         d = self.device
-        off = torch.zeros(B * N + 1, dtype=torch.int32, device=d)
-        pv = torch.zeros((max(int(pair_cap), 1), 6), dtype=torch.float64, device=d)
-        unk = torch.zeros(max(int(pair_cap), 1), dtype=torch.uint8, device=d) if want_unknown else None
-        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
-        self._check(self._lib.vigo_guide_assign(
-            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), _ptr(seg_off, torch.int32, "seg_off", d), _ptr(seg, torch.int32, "seg", d),
+        f = 0 if fill is None else int(fill)
+        off = torch.full((B * N + 1,), f, dtype=torch.int32, device=d)
+        pv = torch.full((max(int(pair_cap), 1), 6), float(f), dtype=torch.float64, device=d)
+        unk = torch.full((max(int(pair_cap), 1),), f & 0xFF, dtype=torch.uint8, device=d) if want_unknown else None
+        status = torch.full((max(B, 1),), -1 if fill is None else f, dtype=torch.int32, device=d)
+        self._check(fn(
+            *lead, _ptr(ctrl, torch.float64, "ctrl", d), _ptr(seg_off, torch.int32, "seg_off", d), _ptr(seg, torch.int32, "seg", d),
             _ptr(path_off, torch.int32, "path_off", d), _ptr(path, torch.float64, "path", d), int(pair_cap), C.c_void_p(off.data_ptr()),
             C.c_void_p(pv.data_ptr()), C.c_void_p(unk.data_ptr()) if want_unknown else None, C.c_void_p(status.data_ptr())),
-            "vigo_guide_assign")
+            who)
         return off, pv[:int(pair_cap)], (unk[:int(pair_cap)] if want_unknown else None), status[:B]
 
-    def collision_segs(self, ctrl, not_check_ratio=0.0, seg_cap=None):
+    def guide_assign_mixed(self, n_pts, ctrl, seg_off, seg, path_off, path, pair_cap, want_unknown=True, fill=None):
+        """vigo_guide_assign_mixed: guide_assign on rows of Ns control points (ctrl f64 [B,Ns,3]) of which n_pts[b] (int32 [B],
+        device) are trajectory b's; guide_off is int32 [B*Ns+1], the padding's ranges empty: optimize_mixed takes it as it is"""
+        return self.guide_assign(ctrl, seg_off, seg, path_off, path, pair_cap, want_unknown, fill, _n_pts=n_pts)
+
+    def collision_segs(self, ctrl, not_check_ratio=0.0, seg_cap=None, fill=None, _n_pts=None):
         """vigo_collision_segs: findCollisionSeg for B trajectories (ctrl f64 [B,N,3]) -> (seg_off int32 [B+1], seg int32
         [seg_cap,2], status int32 [B]: PATHS_OK / PATHS_DEFERRED); seg_cap defaults to B * 48"""
-        _shape(ctrl, (None, None, 3), "ctrl")
-        B, N = ctrl.shape[0], ctrl.shape[1]
+        fn, who, lead = self._rows_call("vigo_collision_segs", _n_pts, ctrl)
+        B = ctrl.shape[0]
         cap = B * 48 if seg_cap is None else int(seg_cap)
         d = self.device
-        seg_off = torch.zeros(B + 1, dtype=torch.int32, device=d)
-        seg = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=d)
-        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
-        self._check(self._lib.vigo_collision_segs(self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), float(not_check_ratio),
-                                                  C.c_void_p(seg_off.data_ptr()), C.c_void_p(seg.data_ptr()), cap,
-                                                  C.c_void_p(status.data_ptr())), "vigo_collision_segs")
+        f = 0 if fill is None else int(fill)
+        seg_off = torch.full((B + 1,), f, dtype=torch.int32, device=d)
+        seg = torch.full((max(cap, 1), 2), f, dtype=torch.int32, device=d)
+        status = torch.full((max(B, 1),), -1 if fill is None else f, dtype=torch.int32, device=d)
+        self._check(fn(*lead, _ptr(ctrl, torch.float64, "ctrl", d), float(not_check_ratio), C.c_void_p(seg_off.data_ptr()),
+                       C.c_void_p(seg.data_ptr()), cap, C.c_void_p(status.data_ptr())), who)
         return seg_off, seg[:cap], status[:B]
 
+    def collision_segs_mixed(self, n_pts, ctrl, not_check_ratio=0.0, seg_cap=None, fill=None):
+        """vigo_collision_segs_mixed: collision_segs on rows of Ns control points (ctrl f64 [B,Ns,3]) of which n_pts[b] (int32
+        [B], device) are trajectory b's; a count outside [7, Ns] reads PATHS_DEFERRED"""
+        return self.collision_segs(ctrl, not_check_ratio, seg_cap, fill, _n_pts=n_pts)
+
     def path_search(self, ctrl, step, pool, min_height, max_height, seg_off=None, seg=None, not_check_ratio=0.0, max_expansions=1 << 20,
-                    search_path_cap=256, seg_cap=None, point_cap=None, want_counts=True):
+                    search_path_cap=256, seg_cap=None, point_cap=None, want_counts=True, fill=None, _n_pts=None):
         """vigo_path_search: pathSearch for B trajectories (ctrl f64 [B,N,3]) on the scanned segments, or on a supplied list
         (seg_off int32 [B+1], seg int32 [S,2]) -> (status int32 [B]: PATHS_OK / PATHS_FAILED / PATHS_DEFERRED, seg_off int32
         [B+1], seg int32 [seg_cap,2], path_off int32 [seg_cap+1], path f64 [point_cap,3], counts int32 [B,2] or None): the
         seg_off / seg / path_off / path of guide_assign.  seg_cap defaults to B * 48, point_cap to seg_cap * (search_path_cap + 1)"""
-        _shape(ctrl, (None, None, 3), "ctrl")
-        B, N = ctrl.shape[0], ctrl.shape[1]
+        fn, who, lead = self._rows_call("vigo_path_search", _n_pts, ctrl)
+        B = ctrl.shape[0]
         scap = B * 48 if seg_cap is None else int(seg_cap)
         pcap = min(scap * (int(search_path_cap) + 1), 1 << 24) if point_cap is None else int(point_cap)
         d = self.device
-        status = torch.full((max(B, 1),), -1, dtype=torch.int32, device=d)
-        o_seg_off = torch.zeros(B + 1, dtype=torch.int32, device=d)
-        o_seg = torch.zeros((max(scap, 1), 2), dtype=torch.int32, device=d)
-        o_path_off = torch.zeros(max(scap, 0) + 1, dtype=torch.int32, device=d)
-        o_path = torch.zeros((max(pcap, 1), 3), dtype=torch.float64, device=d)
-        counts = torch.zeros((max(B, 1), 2), dtype=torch.int32, device=d) if want_counts else None
-        self._check(self._lib.vigo_path_search(
-            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), None if seg_off is None else _ptr(seg_off, torch.int32, "seg_off", d),
+        f = 0 if fill is None else int(fill)
+        status = torch.full((max(B, 1),), -1 if fill is None else f, dtype=torch.int32, device=d)
+        o_seg_off = torch.full((B + 1,), f, dtype=torch.int32, device=d)
+        o_seg = torch.full((max(scap, 1), 2), f, dtype=torch.int32, device=d)
+        o_path_off = torch.full((max(scap, 0) + 1,), f, dtype=torch.int32, device=d)
+        o_path = torch.full((max(pcap, 1), 3), float(f), dtype=torch.float64, device=d)
+        counts = torch.full((max(B, 1), 2), f, dtype=torch.int32, device=d) if want_counts else None
+        self._check(fn(
+            *lead, _ptr(ctrl, torch.float64, "ctrl", d), None if seg_off is None else _ptr(seg_off, torch.int32, "seg_off", d),
             None if seg is None else _ptr(seg, torch.int32, "seg", d), float(not_check_ratio), float(step),
             (C.c_int32 * 3)(*[int(v) for v in pool]), float(min_height), float(max_height), int(max_expansions), int(search_path_cap), scap, pcap,
             C.c_void_p(status.data_ptr()), C.c_void_p(o_seg_off.data_ptr()), C.c_void_p(o_seg.data_ptr()), C.c_void_p(o_path_off.data_ptr()),
-            C.c_void_p(o_path.data_ptr()), C.c_void_p(counts.data_ptr()) if want_counts else None), "vigo_path_search")
+            C.c_void_p(o_path.data_ptr()), C.c_void_p(counts.data_ptr()) if want_counts else None), who)
         return status[:B], o_seg_off, o_seg[:scap], o_path_off, o_path[:pcap], (counts[:B] if want_counts else None)
+
+    def path_search_mixed(self, n_pts, ctrl, step, pool, min_height, max_height, seg_off=None, seg=None, not_check_ratio=0.0,
+                          max_expansions=1 << 20, search_path_cap=256, seg_cap=None, point_cap=None, want_counts=True, fill=None):
+        """vigo_path_search_mixed: path_search on rows of Ns control points (ctrl f64 [B,Ns,3]) of which n_pts[b] (int32 [B],
+        device) are trajectory b's; its outputs are the seg_off / seg / path_off / path of guide_assign_mixed"""
+        return self.path_search(ctrl, step, pool, min_height, max_height, seg_off, seg, not_check_ratio, max_expansions, search_path_cap,
+                                seg_cap, point_cap, want_counts, fill, _n_pts=n_pts)
 
     def rebound_reguide(self, ctrl, guide_off, guide_pv, guide_unk, weights, state, step, pool, min_height, max_height, pair_cap,
                         not_check_ratio=0.0, max_expansions=1 << 20, search_path_cap=256, seg_cap=None, point_cap=None, want_paths=True,
-                        want_unknown=True, fill=0):
+                        want_unknown=True, fill=0, _n_pts=None):
         """vigo_rebound_reguide: the re-guide step of the rebound loop for the NEEDS_HOST trajectories of a batch (ctrl f64
         [B,N,3]; the current guide CSR guide_off int32 [B*N+1] / guide_pv f64 [G,6] / guide_unk uint8 [G], or None: no guides).
         weights [B,4] and state [B, REBOUND_STATE_INTS] (int32) are updated in place.  -> (status int32 [B]: REGUIDE_*, the
         merged CSR off int32 [B*N+1], pv f64 [pair_cap,6], unk uint8 [pair_cap] or None, and the paths path_seg_off int32
         [B+1], path_off int32 [seg_cap+1], path f64 [point_cap,3] or three None).  seg_cap defaults to B * 48, point_cap to
         seg_cap * (search_path_cap + 1); the output buffers are pre-filled with `fill`."""
-        _shape(ctrl, (None, None, 3), "ctrl")
+        fn, who, lead = self._rows_call("vigo_rebound_reguide", _n_pts, ctrl)
         B, N = ctrl.shape[0], ctrl.shape[1]
         _shape(state, (B, self.REBOUND_STATE_INTS), "state")
         _shape(weights, (B, 4), "weights")
@@ -765,14 +794,23 @@ class Vigo:
         p_po = torch.full((max(scap, 0) + 1,), fill, dtype=torch.int32, device=d) if want_paths else None
         p_pa = torch.full((max(pcap, 1), 3), float(fill), dtype=torch.float64, device=d) if want_paths else None
         opt = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self._lib.vigo_rebound_reguide(
-            self._h, B, N, _ptr(ctrl, torch.float64, "ctrl", d), None if guide_off is None else _ptr(guide_off, torch.int32, "guide_off", d),
+        self._check(fn(
+            *lead, _ptr(ctrl, torch.float64, "ctrl", d), None if guide_off is None else _ptr(guide_off, torch.int32, "guide_off", d),
             None if guide_pv is None else _ptr(guide_pv, torch.float64, "guide_pv", d),
             None if guide_unk is None else _ptr(guide_unk, torch.uint8, "guide_unk", d), _ptr(weights, torch.float64, "weights", d),
             float(not_check_ratio), float(step), (C.c_int32 * 3)(*[int(v) for v in pool]), float(min_height), float(max_height), int(max_expansions),
             int(search_path_cap), _ptr(state, torch.int32, "state", d), cap, opt(o_off), opt(o_pv), opt(o_unk), scap, pcap, opt(p_so), opt(p_po),
-            opt(p_pa), opt(status)), "vigo_rebound_reguide")
+            opt(p_pa), opt(status)), who)
         return status[:B], o_off, o_pv[:cap], (o_unk[:cap] if want_unknown else None), p_so, p_po, (p_pa[:pcap] if want_paths else None)
+
+    def rebound_reguide_mixed(self, n_pts, ctrl, guide_off, guide_pv, guide_unk, weights, state, step, pool, min_height, max_height,
+                              pair_cap, not_check_ratio=0.0, max_expansions=1 << 20, search_path_cap=256, seg_cap=None, point_cap=None,
+                              want_paths=True, want_unknown=True, fill=0):
+        """vigo_rebound_reguide_mixed: rebound_reguide on rows of Ns control points (ctrl f64 [B,Ns,3]) of which n_pts[b] (int32
+        [B], device) are trajectory b's; both guide CSRs are int32 [B*Ns+1], as rebound_rounds_mixed takes them"""
+        return self.rebound_reguide(ctrl, guide_off, guide_pv, guide_unk, weights, state, step, pool, min_height, max_height, pair_cap,
+                                    not_check_ratio, max_expansions, search_path_cap, seg_cap, point_cap, want_paths, want_unknown, fill,
+                                    _n_pts=n_pts)
 
     def poly_sample(self, coeffs, n_samp, delT, stride, want_f64=True, want_f32=False):
         """vigo_poly_sample: positions of polyTrajSolver::getTrajectory for S segments ->
