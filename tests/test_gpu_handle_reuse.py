@@ -2,16 +2,22 @@
 One handle runs a sequence in which every buffer is used at a small size, grown, used at the small size again, and
 handed from one entry point to the next; after every call the outputs are compared bit for bit with the same call on a
 handle created only for it.  The odd batch sizes (1, 3, 33) are the smallest at which a workspace array that lost its
-alignment or its last element would show."""
+alignment or its last element would show.  The steps are interleaved so that the scratch buffer changes owner between the
+fit set-up, the mixed fit, the corridor entries, the searches and the host grid setter, and so that the cached tables (fit
+operator, fit table, the gates' and the finish stage's clocks), the exactly carved rebound and ESDF workspaces and the
+solver's LDS attribute are each used small, grown and small again."""
 import numpy as np
 import pytest
 import torch
 
 import corridor_cases as cc
+import mixed_cases as mc
 import pathsearch_cases as pc
 import reguide_cases as rc
+import stream_cases as sc
 from gpu_util import to_dev
-from trajectory_planner_amd.vigo import Vigo
+from trajectory_planner_amd import synth
+from trajectory_planner_amd.vigo import Vigo, default_params
 
 pytestmark = pytest.mark.gpu
 CAP = 512                                                         # search_path_cap, as in the path-search and re-guide tests
@@ -72,6 +78,140 @@ def _inflate(v):
     return _host([v.inflate_grid(to_dev(vox, v.device), 1, 1, 1)])
 
 
+# ---- steps on the inputs of tests/stream_cases.py -------------------------------------------------------------------------
+def _under(change, step):
+    """the step under changed parameters; the defaults are back afterwards, for the steps that take them as they are"""
+    def run(v):
+        P = default_params()
+        if change is not None:
+            change(P)
+        v.set_params(P)
+        try:
+            return step(v)
+        finally:
+            v.set_params(default_params())
+    return run
+
+
+def _row(name):
+    """the call of a row of the stream-order table on its real inputs, under the row's parameters"""
+    row = sc.by_name(name)
+
+    return _under(row.params, lambda v: _host(row.call(v, {k: to_dev(a, v.device) for k, a in row.real.items()})))
+
+
+def _fit_mixed(Ns, ts=None):
+    rng = np.random.default_rng(Ns)
+    pts = rng.uniform(-2.0, 2.0, size=(5, Ns - 2, 3))
+    n_fit = np.array([5, Ns - 2, 9, Ns - 2, 6], dtype=np.int32)
+
+    return lambda v: _host(v.bspline_fit_mixed(to_dev(pts, v.device), to_dev(n_fit, v.device), Ns, ts=ts))
+
+
+def _finish(dt):
+    row = sc.by_name("traj_finish")
+
+    def run(v):
+        d = v.device
+        r = v.traj_finish(to_dev(row.real["ctrl"], d), to_dev(row.real["limits"], d), dt, 64, n_pts=to_dev(row.real["n_pts"], d))
+        return _host([r[k] for k in ("factor", "max", "n", "pos", "vel", "status")])
+    return _under(row.params, run)
+
+
+def _solve_iterations(P):
+    P.max_iterations = 20
+
+
+def _optimize(B, N):
+    world = sc.small_worlds()[0]
+    b = synth.make_bspline_batch(world, B, N, 500 + N, start_range=3.0, n_obs=1)
+
+    def run(v):
+        a = sc.batch_arrays(b)
+        t = {k: to_dev(x, v.device) for k, x in a.items()}
+        r = v.optimize(t["ctrl"], t["guide_off"], t["guide_pv"], t["guide_unk"], t["obs_off"], t["obs"])
+        return _host([r.ctrl, r.x, r.status, r.fx, r.iters, r.evals])
+    return _under(_solve_iterations, run)
+
+
+def _rebound_batches():
+    """33 trajectories of 16 control points, and 33 of 7, 16 and 12 in rows of 16, each with weights and the state makePlan's
+    first step leaves -> (uniform, mixed) as the arrays of sc.batch_arrays"""
+    world = sc.small_worlds()[0]
+    P0 = default_params()
+    b = mc.rich_guides(world, synth.make_bspline_batch(world, 33, 16, 808, start_range=3.0, n_obs=1), 9)
+    wu = mc.random_weights(P0)(np.random.default_rng(1), 33)
+    su = mc.initial_state(world, synth.PaddedBatch(b.ctrl, b.guide_off, b.guide_pv, b.guide_unk, b.obs_off, b.obs, None, {}, np.full(33, 16, np.int32)),
+                          np.random.default_rng(2))
+    parts = mc.make_parts(world, 32, 1717, n_obs=1, counts=((7, 11), (16, 11), (12, 11)), weights=mc.random_weights(P0))
+    pb, _ = synth.pad_batches(parts, interleave=True, Ns=16)
+    sm = mc.initial_state(world, pb, np.random.default_rng(3))
+    return (b, wu, su), (pb, pb.weights, sm)
+
+
+def _rebound(batch, B, mixed):
+    b, w, st = batch
+    a = sc.batch_arrays(b, range(B), weights=w, state=st, n_pts=b.n_pts if mixed else None)
+    world = sc.small_worlds()[0]
+
+    def run(v):
+        d = v.device
+        v.set_grid(to_dev(world.voxels, d), world.origin, world.res)
+        t = {k: to_dev(x, d) for k, x in a.items()}
+        args = (t["ctrl"], t["guide_off"], t["guide_pv"], t["guide_unk"], t["obs_off"], t["obs"], t["weights"], 0.1, t["state"])
+        if mixed:
+            v.rebound_rounds_mixed(t["n_pts"], *args, max_rounds=2)
+        else:
+            v.rebound_rounds(*args, max_rounds=2)
+        return _host([t["ctrl"], t["weights"], t["state"]])
+    return _under(_solve_iterations, run)
+
+
+def _segments_search_guides(v):
+    """collision_segs -> path_search on that list -> guide_assign, on the device tensors as they lie"""
+    _, case, _ = sc.prologue_cases()
+    d = v.device
+    v.set_grid(to_dev(case.vox, d), case.origin, case.res)
+    ctrl = to_dev(case.padded(), d)
+    so, sg, st = v.collision_segs(ctrl, case.ncr, seg_cap=case.B * 48, fill=-7)
+    search = v.path_search(ctrl, case.res, case.pool, case.cfg[1], case.cfg[2], seg_off=so, seg=sg, not_check_ratio=case.ncr, search_path_cap=CAP,
+                           seg_cap=case.B * 48, point_cap=sc.PROLOGUE_POINT_CAP, fill=-7)
+    guides = v.guide_assign(ctrl, search[1], search[2], search[3], search[4], case.B * (case.Ns + 4 * 48) + 8, fill=-7)
+    return _host([so, sg, st] + list(search) + list(guides))
+
+
+def _minsnap(T):
+    rng = np.random.default_rng(40 + T)
+    wp = np.cumsum(rng.uniform(0.4, 1.2, size=(T, 4, 3)) * np.array([1.0, 0.5, 0.1]), axis=1) + np.array([0.0, 0.0, 1.0])
+    return lambda v: _host(v.minsnap(to_dev(wp, v.device)))
+
+
+def _set_grid_host(v):
+    world = sc.small_worlds()[1]
+    v.set_grid_host(world.voxels, world.origin, world.res)
+    return _host([v.get_grid_packed()])
+
+
+def _esdf_sequence(v):
+    """a tracked build, a region update and its refresh on 24 x 70 x 31 voxels; then a smaller world, built untracked: the ESDF
+    workspace is first larger than the world needs and then replaced"""
+    rng = np.random.default_rng(61)
+    big = ((rng.random((24, 70, 31)) < 0.03).astype(np.uint8) * 4)
+    small = ((rng.random((9, 20, 33)) < 0.05).astype(np.uint8) * 4)
+    box = ((rng.random((5, 9, 11)) < 0.3).astype(np.uint8) * 4)
+    d = v.device
+    pts = to_dev(rng.uniform(0.0, 1.0, size=(65, 3)) * np.array([0.9, 2.0, 3.1]), d)
+    v.set_grid(to_dev(big, d), (0.0, 0.0, 0.0), 0.1)
+    out = [v.build_esdf(return_lattice=True, tracked=True)]
+    v.update_grid_region((3, 40, 7), to_dev(box, d))
+    out.append(v.update_esdf(return_lattice=True))
+    out += list(v.esdf_query(pts))
+    v.set_grid(to_dev(small, d), (0.0, 0.0, 0.0), 0.1)
+    out.append(v.build_esdf(return_lattice=True))
+    out += list(v.esdf_query(pts))
+    return _host(out)
+
+
 def test_entry_points_sharing_one_handle_equal_fresh_handles():
     crafted = dict(pc.crafted_workloads())
     one = crafted["a merge taken while another segment stays unmerged"]   # B = 1: four searches, second choices among them
@@ -87,6 +227,22 @@ def test_entry_points_sharing_one_handle_equal_fresh_handles():
              ("trajectory gate", _traj_collision(many)), ("fit, K = 8", _fit(8)), ("fit, K = 40", _fit(40)),
              ("trajectory gate after the fits", _traj_collision(many)), ("inflate 8 x 8 x 40", _inflate),
              ("path search, B = 1 at the end", _path_search(one))]
+    uniform, mixed = _rebound_batches()
+    steps += [("mixed fit, Ns = 16", _fit_mixed(16)), ("corridor check after the mixed fit", _corridor(corridor, 5)),
+              ("mixed fit, Ns = 64", _fit_mixed(64)), ("A* searches", _row("astar_search")), ("mixed fit, Ns = 16 again", _fit_mixed(16)),
+              ("grid from host memory", _set_grid_host), ("mixed fit, another ts", _fit_mixed(16, ts=0.15)), ("fit, K = 8 after the table", _fit(8)),
+              ("finish, sample_dt 0.1", _finish(0.1)), ("trajectory gate between the finishes", _traj_collision(many)), ("finish, sample_dt 0.07", _finish(0.07)),
+              ("finish, sample_dt 0.1 again", _finish(0.1)),
+              ("solve, B = 1, N = 8", _optimize(1, 8)), ("solve, B = 3, N = 200", _optimize(3, 200)), ("solve, B = 1, N = 8 again", _optimize(1, 8)),
+              ("mixed solve", _row("optimize_mixed")),
+              ("rebound rounds, B = 3", _rebound(uniform, 3, False)), ("rebound rounds, B = 33", _rebound(uniform, 33, False)),
+              ("rebound rounds, B = 3 again", _rebound(uniform, 3, False)),
+              ("mixed rebound rounds, B = 3", _rebound(mixed, 3, True)), ("mixed rebound rounds, B = 33", _rebound(mixed, 33, True)),
+              ("seed paths", _row("seed_paths")), ("segments, search, guides", _segments_search_guides),
+              ("min-snap, T = 1", _minsnap(1)), ("min-snap, T = 33", _minsnap(33)), ("min-snap, T = 1 again", _minsnap(1)),
+              ("trajectory corridor check", _row("traj_corridor_check")), ("trajectory point check", _row("traj_point_check")),
+              ("polynomial samples", _row("poly_sample")), ("ESDF: tracked, updated, rebuilt on a smaller world", _esdf_sequence),
+              ("fit, K = 40 at the end", _fit(40)), ("segments, search, guides at the end", _segments_search_guides)]
     shared = Vigo(0)
     seen = {}
     try:
@@ -110,3 +266,23 @@ def test_entry_points_sharing_one_handle_equal_fresh_handles():
     assert (seen["re-guide, B = 3"][0] == rc.DONE).any()
     assert seen["fit, K = 40"][0].shape == (5, 42, 3) and seen["inflate 8 x 8 x 40"][0].sum() > 0
     assert all(a.tobytes() == b.tobytes() for a, b in zip(seen["trajectory gate"], seen["trajectory gate after the fits"]))
+    # the added steps: a grown fit table, a rebuilt one, both finish clocks, the raised LDS attribute, a regrown rebound buffer, a
+    # merged search, the ESDF on both worlds
+    ctrl64, n64 = seen["mixed fit, Ns = 64"]
+    assert ctrl64.shape == (5, 64, 3) and n64.tolist() == [7, 64, 11, 64, 8] and np.abs(ctrl64[1, 63]).sum() > 0
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(seen["mixed fit, Ns = 16"], seen["mixed fit, Ns = 16 again"]))
+    assert seen["mixed fit, another ts"][0].tobytes() != seen["mixed fit, Ns = 16"][0].tobytes()
+    assert seen["finish, sample_dt 0.07"][2].tolist() != seen["finish, sample_dt 0.1"][2].tolist()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(seen["finish, sample_dt 0.1"], seen["finish, sample_dt 0.1 again"]))
+    assert seen["solve, B = 3, N = 200"][0].shape == (3, 200, 3) and (seen["solve, B = 3, N = 200"][4] > 0).all()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(seen["solve, B = 1, N = 8"], seen["solve, B = 1, N = 8 again"]))
+    for label in ("rebound rounds, B = 33", "mixed rebound rounds, B = 33"):
+        state = seen[label][2]
+        assert state.shape == (33, Vigo.REBOUND_STATE_INTS) and (state[:, 5] > 0).any(), label                # rounds were played
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(seen["rebound rounds, B = 3"], seen["rebound rounds, B = 3 again"]))
+    chain = seen["segments, search, guides"]
+    assert int(chain[0][-1]) >= 3 and (chain[8][:, 0] >= 2).any() and int(chain[9][-1]) > 0                  # segments, a merged search, guide pairs
+    assert seen["min-snap, T = 33"][2].shape == (33,) and (seen["min-snap, T = 33"][2] == 0).any()
+    built, updated = seen["ESDF: tracked, updated, rebuilt on a smaller world"][:2]
+    assert built.shape == (24, 70, 31) and built.tobytes() != updated.tobytes()
+    assert seen["ESDF: tracked, updated, rebuilt on a smaller world"][4].shape == (9, 20, 33)
