@@ -140,6 +140,12 @@ PROTOTYPES = {
     "vigo_esdf_update_host": (_i, [_i, _i, _i, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, C.POINTER(VigoEsdfUpdateStats)]),
 }
 
+# the same for every symbol include/vigo_validate.h declares
+VALIDATE_PROTOTYPES = {
+    "vigo_traj_validate": (_i, [_vp, _i, _i, _vp, _vp, _d, _d, _i, _vp, _vp, _i] + [_vp] * 6),
+    "vigo_traj_validate_host": (_i, [_i, _i, _i, _d3, _d, _vp, _d, _i, _i, _vp, _vp, _d, _d, _i, _vp, _vp, _i] + [_vp] * 6),
+}
+
 _lib = None
 
 
@@ -154,7 +160,7 @@ def load():
             "(or __graft_entry__.build()); there is no CPU fallback for the hot path"
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(VALIDATE_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

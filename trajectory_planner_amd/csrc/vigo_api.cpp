@@ -16,7 +16,10 @@
 #include "vigo_seed_core.hpp"
 #include "vigo_solver_plan.hpp"
 #include "vigo_traj_runs.hpp"
+#include "vigo_validate_core.hpp"
 #include "vigo_ws_layout.hpp"
+
+#include "../../include/vigo_validate.h"
 
 using vigo::DevBuffer;
 using vigo::DevConst;
@@ -54,7 +57,7 @@ int fail(vigo_handle_t h, int code, const char* what, hipError_t e = hipSuccess)
 // not kept).  A failed allocation leaves it empty.  Callers whose cache lives in the buffer invalidate it first.
 int reserve(vigo_handle_t h, vigo::BufId id, size_t need, size_t alloc) {
     static const char* const what[] = {
-        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(esdf_track)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(finish_ts)", "hipMalloc(finish_dt)", "hipMalloc(scratch)",
+        "hipMalloc(grid)", "hipMalloc(esdf)", "hipMalloc(esdf_ws)", "hipMalloc(esdf_track)", "hipMalloc(fit)", "hipMalloc(fit_table)", "hipMalloc(times)", "hipMalloc(finish_ts)", "hipMalloc(finish_dt)", "hipMalloc(validate_clock)", "hipMalloc(validate_tab)", "hipMalloc(scratch)",
         "hipMalloc(paths_ws[0])", "hipMalloc(paths_ws[1])", "hipMalloc(reguide_ws[0])", "hipMalloc(reguide_ws[1])",
         "hipMalloc(reguide_ws[2])", "hipMalloc(rebound)"};
     static_assert(sizeof(what) / sizeof(what[0]) == vigo::kBufCount, "one name per BufId, in its order");
@@ -144,17 +147,8 @@ const char* const kGateNMsg = "N outside [4, VIGO_MAX_CTRL_POINTS]";
 // accumulation, reproduced exactly by vigo::accumulated_time (closed form per binade).  The sample count T is
 // found on the host by bisection over that closed form (monotone in k), the table is filled by a device kernel
 // and cached in the handle per (dt, tmax): the gates run without a host round trip.  -1: more than 2^24 samples.
-int count_sample_times(double dt, double tmax) {
-    if (!(tmax >= 0.0)) return 0;
-    const int64_t cap = (int64_t)1 << 24;
-    if (vigo::accumulated_time(dt, cap) <= tmax) return -1;
-    int64_t lo = 0, hi = cap;                       // t_lo <= tmax < t_hi
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (vigo::accumulated_time(dt, mid) <= tmax) lo = mid; else hi = mid;
-    }
-    return (int)hi;                                 // samples k = 0 .. lo
-}
+// (vigo_exact_time.hpp has the function: the host twin of vigo_validate_core.hpp counts with the same copy)
+using vigo::count_sample_times;
 
 int upload_sample_times(vigo_handle_t h, double tmax, double dt, int* out_T, const double** out_dev) {
     if (!(dt > 0.0)) return fail(h, VIGO_ERR_INVALID_ARG, "dt must be > 0");
@@ -198,9 +192,14 @@ int count_sample_times_strict(double dt, double tmax) {
 // vigo_traj_finish's clocks, cached per (dt, tmax) like the gates' but in slots of their own (which: 0 the strict `<`
 // clock of ts in kBufFinishTs, 1 the `<=` clock of the sample step in kBufFinishDt): a plan batch between two gate
 // calls does not evict the gates' table, nor the other way round
+int upload_clock_slot(vigo_handle_t h, vigo_context::ClockSlot& c, vigo::BufId id, bool strict, double tmax, double dt, int* out_T,
+                      const double** out_dev);
 int upload_finish_clock(vigo_handle_t h, int which, double tmax, double dt, int* out_T, const double** out_dev) {
-    vigo_context::ClockSlot& c = h->finish_clock[which];
-    const vigo::BufId id = which == 0 ? vigo::kBufFinishTs : vigo::kBufFinishDt;
+    return upload_clock_slot(h, h->finish_clock[which], which == 0 ? vigo::kBufFinishTs : vigo::kBufFinishDt, which == 0, tmax, dt, out_T, out_dev);
+}
+// (vigo_traj_validate's clock is the third such slot: the `<=` clock of its dt in kBufValidateClock)
+int upload_clock_slot(vigo_handle_t h, vigo_context::ClockSlot& c, vigo::BufId id, bool strict, double tmax, double dt, int* out_T,
+                      const double** out_dev) {
     if (c.T >= 0 && c.dt == dt && c.tmax == tmax) {
         if (c.stream != h->stream) {                   // filled on another stream: make sure it has landed
             VIGO_HIP(h, hipStreamSynchronize(c.stream));
@@ -210,7 +209,7 @@ int upload_finish_clock(vigo_handle_t h, int which, double tmax, double dt, int*
         *out_dev = h->buf[id].as<double>();
         return VIGO_OK;
     }
-    const int T = which == 0 ? count_sample_times_strict(dt, tmax) : count_sample_times(dt, tmax);
+    const int T = strict ? count_sample_times_strict(dt, tmax) : count_sample_times(dt, tmax);
     if (T < 0) return fail(h, VIGO_ERR_INVALID_ARG, "too many samples");
     c.T = -1;                                          // no clock cached while the buffer is regrown or refilled
     VIGO_TRY(reserve(h, id, (size_t)T * sizeof(double), ((size_t)T + 64) * sizeof(double)));
@@ -222,6 +221,43 @@ int upload_finish_clock(vigo_handle_t h, int which, double tmax, double dt, int*
     c.stream = h->stream;
     *out_T = T;
     *out_dev = times;
+    return VIGO_OK;
+}
+
+// vigo_traj_validate's {S, C} of every count 4 .. Ns (validate_counts), cached per (dt, ts_ctrl, ratio, rule, Ns) in one of
+// kValidateSlots device tables.  A new key is computed into the pinned stage of the next slot in turn and copied in
+// stream order; the host waits only if that slot's previous copy, kValidateSlots keys ago, has not left the stage yet.
+int upload_validate_tab(vigo_handle_t h, double dt, double ratio, int rule, int Ns, const int32_t** out_dev) {
+    const size_t per = (size_t)vigo::validate_tab_entries(VIGO_MAX_CTRL_POINTS);
+    const double ts_ctrl = h->params.ts_ctrl;
+    VIGO_TRY(reserve(h, vigo::kBufValidateTab, vigo_context::kValidateSlots * per * sizeof(int32_t), vigo_context::kValidateSlots * per * sizeof(int32_t)));
+    int32_t* dev = h->buf[vigo::kBufValidateTab].as<int32_t>();
+    for (int i = 0; i < vigo_context::kValidateSlots; ++i) {
+        const vigo_context::ValidateKey& k = h->validate_key[i];
+        if (k.Ns == Ns && k.rule == rule && k.dt == dt && k.ts_ctrl == ts_ctrl && k.ratio == ratio) {
+            *out_dev = dev + i * per;
+            return VIGO_OK;
+        }
+    }
+    if (!h->validate_stage) {
+        for (int i = 0; i < vigo_context::kValidateSlots; ++i)
+            if (!h->validate_event[i]) VIGO_HIP(h, hipEventCreateWithFlags(&h->validate_event[i], hipEventDisableTiming));
+        VIGO_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->validate_stage), vigo_context::kValidateSlots * per * sizeof(int32_t)));
+    }
+    const int slot = h->validate_next;
+    // (the longest count first: it has the most samples, and a refusal must leave the slot's key alone)
+    int32_t probe[2];
+    if (!vigo::validate_counts(dt, ts_ctrl, ratio, rule, Ns, &probe[0], &probe[1])) return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_validate: too many samples");
+    VIGO_HIP(h, hipEventSynchronize(h->validate_event[slot]));
+    h->validate_key[slot].Ns = 0;                      // no table cached while the slot is refilled
+    int32_t* tab = h->validate_stage + slot * per;
+    for (int n = vigo::kValidateMinN; n <= Ns; ++n)
+        (void)vigo::validate_counts(dt, ts_ctrl, ratio, rule, n, &tab[2 * (n - vigo::kValidateMinN)], &tab[2 * (n - vigo::kValidateMinN) + 1]);
+    VIGO_HIP(h, hipMemcpyAsync(dev + slot * per, tab, (size_t)vigo::validate_tab_entries(Ns) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    VIGO_HIP(h, hipEventRecord(h->validate_event[slot], h->stream));
+    h->validate_key[slot] = vigo_context::ValidateKey{dt, ts_ctrl, ratio, rule, Ns};
+    h->validate_next = (slot + 1) % vigo_context::kValidateSlots;
+    *out_dev = dev + slot * per;
     return VIGO_OK;
 }
 
@@ -458,6 +494,9 @@ int vigo_destroy(vigo_handle_t h) {
     for (int i = 0; i < vigo_context::kDcSlots; ++i)
         if (h->dc_event[i]) (void)hipEventDestroy(h->dc_event[i]);
     if (h->dc_stage) (void)hipHostFree(h->dc_stage);
+    for (int i = 0; i < vigo_context::kValidateSlots; ++i)
+        if (h->validate_event[i]) (void)hipEventDestroy(h->validate_event[i]);
+    if (h->validate_stage) (void)hipHostFree(h->validate_stage);
     delete h;
     return VIGO_OK;
 }
@@ -926,6 +965,30 @@ int vigo_traj_finish(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const
     VIGO_TRY(upload_finish_clock(h, 1, longest, sample_dt, &a.T_dt, &a.times_dt));
     a.out_factor = out_factor; a.out_max = out_max; a.out_n = out_n; a.out_pos = out_pos; a.out_vel = out_vel; a.out_status = out_status;
     VIGO_HIP(h, (hipError_t)vigo::launch_traj_finish(h->stream, a));
+    return VIGO_OK;
+}
+
+int vigo_traj_validate(vigo_handle_t h, int B, int Ns, const int32_t* n_pts, const double* ctrl, double dt, double not_check_ratio, int rule,
+                       const int32_t* obs_off, const double* obs, int n_obs_shared, int32_t* out_status, int32_t* out_first, double* out_pos,
+                       int32_t* out_dyn_first, int32_t* out_invalid, int32_t* out_n_invalid) {
+    if (!h) return VIGO_ERR_INVALID_ARG;
+    const double ts_ctrl = h->params.ts_ctrl;
+    if (B < 0 || !vigo::finish_step_ok(dt) || !vigo::finish_step_ok(ts_ctrl) || !(not_check_ratio >= 0.0 && not_check_ratio <= 1.0) ||
+        (rule != VIGO_VALIDATE_BY_TIME && rule != VIGO_VALIDATE_BY_INDEX) || n_obs_shared < 0 || (B > 0 && (!ctrl || !out_status || !out_first)) ||
+        (!out_invalid != !out_n_invalid))
+        return fail(h, VIGO_ERR_INVALID_ARG, "vigo_traj_validate: bad argument");
+    if (Ns < vigo::kValidateMinN || Ns > VIGO_MAX_CTRL_POINTS) return fail(h, VIGO_ERR_UNSUPPORTED_N, kGateNMsg);
+    if (!h->has_grid) return fail(h, VIGO_ERR_NO_GRID, "vigo_traj_validate before vigo_set_grid");
+    if (B == 0) return VIGO_OK;
+    vigo::ValidateArgs a{};
+    a.B = B; a.Ns = Ns; a.n_pts = n_pts; a.ctrl = ctrl; a.ts_ctrl = ts_ctrl;
+    VIGO_TRY(upload_validate_tab(h, dt, not_check_ratio, rule, Ns, &a.count_tab));
+    // (the clock depends on dt and k only: the table of the longest duration serves every count)
+    VIGO_TRY(upload_clock_slot(h, h->validate_clock, vigo::kBufValidateClock, false, (Ns - 3) * ts_ctrl, dt, &a.T, &a.times));
+    a.obs_off = obs_off; a.obs = obs; a.n_obs_shared = n_obs_shared;
+    a.out_status = out_status; a.out_first = out_first; a.out_pos = out_pos; a.out_dyn_first = out_dyn_first;
+    a.out_invalid = out_invalid; a.out_n_invalid = out_n_invalid;
+    VIGO_HIP(h, (hipError_t)vigo::launch_traj_validate(h->stream, h->grid, a));
     return VIGO_OK;
 }
 

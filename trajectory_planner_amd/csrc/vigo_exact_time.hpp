@@ -64,6 +64,20 @@ VIGO_HD double accumulated_time(double d, int64_t k) {
     return t;
 }
 
+// Samples of `for (t = 0; t <= tmax; t += dt)` (BT.h:313, :347), t_k the accumulated clock above: by bisection over the
+// closed form (monotone in k).  -1: more than 2^24 samples.
+inline int count_sample_times(double dt, double tmax) {
+    if (!(tmax >= 0.0)) return 0;
+    const int64_t cap = (int64_t)1 << 24;
+    if (accumulated_time(dt, cap) <= tmax) return -1;
+    int64_t lo = 0, hi = cap;                       // t_lo <= tmax < t_hi
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (accumulated_time(dt, mid) <= tmax) lo = mid; else hi = mid;
+    }
+    return (int)hi;                                 // samples k = 0 .. lo
+}
+
 // ---- the sample clock as a table (k_corridor) ---------------------------------------------------------------
 // accumulated_time(d, k) costs O(#binades) steps with a 64-bit division each — about as much as four samples.  All
 // samples of a segment share d, so ONE thread writes the closed form down while it computes the last clock value: the

@@ -112,6 +112,14 @@ __device__ __forceinline__ int gate_static_first(const GridView& g, const double
     return INT_MAX;
 }
 
+// the point test of hasDynamicCollisionTrajectory (BT.h:352-365): p inside the obstacle o[9] (host too: the host twin of
+// vigo_validate_core.hpp tests with this one copy)
+__host__ __device__ __forceinline__ bool dyn_point_hit(const double (&p)[3], const double* o) {
+    const double size = fmin(o[6] / 2, o[7] / 2);  // BT.h:358 (min, unlike the cost term)
+    const double dx = p[0] - o[0], dy = p[1] - o[1];
+    return sqrt((dx * dx + dy * dy) + 0.0) - size < 0;
+}
+
 // hasDynamicCollisionTrajectory (BT.h:344-368): does one of the lane's samples lie inside an obstacle of trajectory b
 // (obs_off's range of obs[][9], or the n_obs_shared shared ones; none without obs — BT.cpp:621-626)
 __device__ __forceinline__ int gate_dynamic_hit(const double* c, int N, double ts, int T, const double* __restrict__ times,
@@ -124,10 +132,7 @@ __device__ __forceinline__ int gate_dynamic_hit(const double* c, int N, double t
         double p[3];
         traj_eval(c, N, ts, 0, times[k], p);
         for (int j = o0; j < o1; ++j) {
-            const double* o = obs + 9 * (size_t)j;
-            const double size = fmin(o[6] / 2, o[7] / 2);  // BT.h:358 (min, unlike the cost term)
-            const double dx = p[0] - o[0], dy = p[1] - o[1];
-            if (sqrt((dx * dx + dy * dy) + 0.0) - size < 0) return 1;
+            if (dyn_point_hit(p, obs + 9 * (size_t)j)) return 1;
         }
     }
     return 0;

@@ -31,6 +31,9 @@ enum BufId {
     kBufTimes,       // the gates' sample clock: T + 64 doubles; growing clears times_T
     kBufFinishTs,    // vigo_traj_finish's two clocks (the `t += ts` one and the `t += sample_dt` one), slots of their own so
     kBufFinishDt,    //   the gates' table stays cached: T + 64 doubles; growing clears the slot's finish_clock[].T
+    kBufValidateClock,  // vigo_traj_validate's clock, a slot of its own like the two above: T + 64 doubles; growing clears
+                        //   validate_clock.T
+    kBufValidateTab, // vigo_traj_validate's per-count tables: kValidateSlots * validate_tab_entries(VIGO_MAX_CTRL_POINTS) int32, fixed
     kBufScratch,     // per-call scratch of most entry points and staging of the *_host calls: need + 25 % + 4 KiB
     kBufPaths0,      // vigo_path_search: sized by the call's first-choice and (kBufPaths1) second-choice searches,
     kBufPaths1,      //   need + 25 % + 4 KiB
@@ -89,4 +92,16 @@ struct vigo_context {
         int T = -1;
         hipStream_t stream = nullptr;
     } finish_clock[2];
+    // kBufValidateClock holds vigo_traj_validate's clock (samples t <= tmax)
+    ClockSlot validate_clock;
+    // vigo_traj_validate's {S, C} tables, one per key (dt, ts_ctrl, ratio, rule, Ns): slot i of kBufValidateTab is filled in
+    // stream order from slot i of the pinned validate_stage, which may be rewritten once validate_event[i] (its copy) is done
+    static constexpr int kValidateSlots = 4;
+    struct ValidateKey {
+        double dt = -1.0, ts_ctrl = -1.0, ratio = -1.0;
+        int rule = -1, Ns = 0;                   // Ns == 0: the slot is empty
+    } validate_key[kValidateSlots];
+    int32_t* validate_stage = nullptr;           // hipHostMalloc'ed on first use, [kValidateSlots][validate_tab_entries(256)]
+    hipEvent_t validate_event[kValidateSlots] = {};
+    int validate_next = 0;
 };

@@ -245,6 +245,29 @@ struct FinishArgs {
 };
 int launch_traj_finish(hipStream_t s, const FinishArgs& a);
 
+// plan validation (vigo_validate.hip, the rule of vigo_validate_core.hpp): a wave per trajectory, then the ascending list of
+// the invalid rows.  times[T]: the `t += dt` clock up to the longest duration (Ns - 3) * ts_ctrl; count_tab: {S, C} of
+// every count 4 .. Ns (validate_tab_entries(Ns) int32)
+struct ValidateArgs {
+    int B, Ns;
+    const int32_t* n_pts;        // NULL: every row has Ns control points
+    const double* ctrl;          // [B][Ns][3]
+    double ts_ctrl;
+    int T;
+    const double* times;
+    const int32_t* count_tab;
+    const int32_t* obs_off;
+    const double* obs;
+    int n_obs_shared;
+    int32_t* out_status;         // [B]
+    int32_t* out_first;          // [B]
+    double* out_pos;             // [B][3] or NULL
+    int32_t* out_dyn_first;      // [B] or NULL
+    int32_t* out_invalid;        // [B] and [1], or both NULL
+    int32_t* out_n_invalid;
+};
+int launch_traj_validate(hipStream_t s, const GridView& g, const ValidateArgs& a);
+
 // batched min-snap QP (vigo_minsnap.hip)
 size_t minsnap_lds_bytes(int W, int cont);
 int minsnap_max_waypoints();

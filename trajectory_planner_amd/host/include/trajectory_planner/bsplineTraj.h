@@ -239,6 +239,8 @@ public:
         double chainSeconds = 0.0;                         /* ... of devicePrologue's chains (upload to installed results) */
         long long prologueGroups = 0;                      /* device groups the prologue's stages opened (devicePrologue chains, deviceGuides = 1 and deviceAstar launches), under either setting of mixedPrologue */
         long long reguideGroups = 0;                       /* ... and the deviceReguide = 1 calls */
+        long long validateDecided = 0, validateHost = 0;   /* isCurrTrajValidBatch's initialised planners: answered by vigo_traj_validate / by the per-planner route */
+        long long validateGroups = 0;                      /* vigo_traj_validate calls made (one per device group, whatever the counts in it) */
         BatchStats& operator+=(const BatchStats& o) {
             astarDecided += o.astarDecided; astarHost += o.astarHost;
             guidesDecided += o.guidesDecided; guidesHost += o.guidesHost;
@@ -250,6 +252,7 @@ public:
             solveBatches += o.solveBatches; solvePlanners += o.solvePlanners;
             prologueSeconds += o.prologueSeconds; chainSeconds += o.chainSeconds;
             prologueGroups += o.prologueGroups; reguideGroups += o.reguideGroups;
+            validateDecided += o.validateDecided; validateHost += o.validateHost; validateGroups += o.validateGroups;
             return *this;
         }
     };
@@ -287,6 +290,19 @@ public:
     static std::vector<bool> seedPathBatch(const std::vector<bsplineTraj*>& planners, const std::vector<polyTrajOccMap*>& polys,
                                            const std::vector<std::vector<Eigen::Vector3d>>& startEndConditions, const BatchOptions& options,
                                            BatchStats* stats = nullptr, std::vector<nav_msgs::Path>* seeds = nullptr, std::vector<SeedInfo>* info = nullptr);
+
+    /* not in the reference: isCurrTrajValid(firstCollisionPos) and hasDynamicCollisionTrajectory(controlPoints) for every
+     * plan a service holds, after a map change.  Element i is what planners[i]->isCurrTrajValid(pos) returns — the index
+     * rule of BT.h:329 with the planner's notCheckRatio_ and the gate step res / maxVel_ / 2 — and (*firstCollisionPos)[i]
+     * is written only where that call would write it (the vector is resized to the planners, entries it holds are kept);
+     * (*dynamicCollision)[i] is hasDynamicCollisionTrajectory on the planner's control points, false without obstacles.
+     * Planners that share a device target, maxVel_ and notCheckRatio_ share ONE vigo_traj_validate (include/vigo_validate.h)
+     * whatever their control-point counts, in rows of the group's largest count.  A planner that is not initialised is
+     * invalid with no device work; planners without a device, of more than VIGO_MAX_CTRL_POINTS control points or whose
+     * device call fails take the per-planner route, with the same answer (BatchStats::validateDecided / validateHost /
+     * validateGroups). */
+    static std::vector<bool> isCurrTrajValidBatch(const std::vector<bsplineTraj*>& planners, std::vector<Eigen::Vector3d>* firstCollisionPos = nullptr,
+                                                  std::vector<bool>* dynamicCollision = nullptr, BatchStats* stats = nullptr);
 
     /* ---- the process default ----------------------------------------------------------------------------------------
      * The overloads without options take a snapshot of ONE process-wide BatchOptions, guarded by a lock, when they are
@@ -489,6 +505,8 @@ private:
                              const BatchOptions& o, BatchStats& stats);
     /* deviceEpilogue: the planners with todo[i] through vigo_traj_finish; todo[i] is cleared for those it finished */
     static void finishOnDevice(const std::vector<bsplineTraj*>& planners, std::vector<uint8_t>& todo, nav_msgs::Path* paths, bool yaw, BatchStats& stats);
+    static void validateOnDevice(const std::vector<bsplineTraj*>& planners, std::vector<uint8_t>& todo, std::vector<bool>& valid,
+                                 std::vector<Eigen::Vector3d>* firstCollisionPos, std::vector<bool>* dynamicCollision, BatchStats& stats);
 };
 }  // namespace trajPlanner
 #endif

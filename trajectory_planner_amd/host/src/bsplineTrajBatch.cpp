@@ -1226,4 +1226,91 @@ void bsplineTraj::finishBatch(const std::vector<bsplineTraj*>& planners, std::ve
     finishBatch(planners, trajectories, yaw, defaultBatchOptions());
 }
 
+namespace {
+struct ValidateStage {
+    Staged<double> ctrl, obs, pos;
+    Staged<int32_t> npts, ooff, status, first;
+};
+}  // namespace
+
+// isCurrTrajValidBatch's device stage: per group of planners that share a device target, maxVel_ (the gate step) and
+// notCheckRatio_ — whatever their counts — the rows padded to the group's largest count, the obstacle lists as one CSR, one
+// vigo_traj_validate under the index rule, one download.  What the call does not decide stays in todo.
+void bsplineTraj::validateOnDevice(const std::vector<bsplineTraj*>& ps, std::vector<uint8_t>& todo, std::vector<bool>& valid,
+                                   std::vector<Eigen::Vector3d>* firstCollisionPos, std::vector<bool>* dynamicCollision, BatchStats& stats) {
+    std::vector<size_t> owners;
+    for (size_t i = 0; i < ps.size(); ++i)
+        if (todo[i]) owners.push_back(i);
+    auto same = [&](size_t a, size_t b) { return ps[owners[a]]->sameBatchKeyAnyCount(*ps[owners[b]]); };
+    vigo_host::forEachGroup(owners.size(), same, [&](const std::vector<size_t>& members) {
+        std::vector<size_t> who;
+        int Ns = 0;
+        for (size_t m : members) {
+            const int n = (int)ps[owners[m]]->optData_.controlPoints.cols();
+            if (n < 4 || n > VIGO_MAX_CTRL_POINTS) continue;
+            who.push_back(owners[m]);
+            Ns = std::max(Ns, n);
+        }
+        if (who.empty()) return;
+        bsplineTraj* lead = ps[who[0]];
+        if (!lead->syncDevice() || !lead->link_.map()) return;
+        HostBatch hb(Ns);
+        for (size_t i : who) {
+            hb.addRow(ps[i]->optData_.controlPoints.data(), (int)ps[i]->optData_.controlPoints.cols());
+            vigo_host::appendObstacles(ps[i]->optData_, hb.obs);
+            hb.ooff.push_back((int32_t)(hb.obs.size() / 9));
+        }
+        const size_t B = who.size();
+        static thread_local ValidateStage st;
+        if (!st.ctrl.upload(hb.ctrl) || (!hb.uniform() && !st.npts.upload(hb.npts)) || !st.ooff.upload(hb.ooff) || !st.obs.upload(hb.obs) ||
+            !st.status.alloc(B) || !st.first.alloc(B) || !st.pos.alloc(3 * B))
+            return;
+        vigo_handle_t h = lead->link_.handle();
+        const double dt = lead->link_.map()->getRes() / lead->maxVel_ / 2.0;  // BT.h:312, evalTraj()'s step
+        stats.validateGroups += 1;
+        if (!deviceCallOk(vigo_traj_validate(h, (int)B, Ns, hb.uniform() ? nullptr : st.npts.get(), st.ctrl.get(), dt, lead->notCheckRatio_,
+                                             VIGO_VALIDATE_BY_INDEX, st.ooff.get(), hb.obs.empty() ? nullptr : st.obs.get(), 0, st.status.get(),
+                                             st.first.get(), st.pos.get(), nullptr, nullptr, nullptr),
+                          "vigo_traj_validate", h))
+            return;
+        std::vector<int32_t> status(B);
+        std::vector<double> pos(3 * B);
+        if (!vigo_host::threadSync() || !st.status.download(status) || !st.pos.download(pos)) return;
+        for (size_t b = 0; b < B; ++b) {
+            if (status[b] & VIGO_VALID_BAD_COUNT) continue;
+            const size_t i = who[b];
+            valid[i] = !(status[b] & VIGO_VALID_STATIC);
+            if (!valid[i] && firstCollisionPos) (*firstCollisionPos)[i] = Eigen::Vector3d(pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
+            if (dynamicCollision) (*dynamicCollision)[i] = (status[b] & VIGO_VALID_DYNAMIC) != 0;
+            todo[i] = 0;
+        }
+    });
+}
+
+std::vector<bool> bsplineTraj::isCurrTrajValidBatch(const std::vector<bsplineTraj*>& planners, std::vector<Eigen::Vector3d>* firstCollisionPos,
+                                                    std::vector<bool>* dynamicCollision, BatchStats* stats) {
+    const size_t n = planners.size();
+    std::vector<bool> valid(n, false);
+    if (firstCollisionPos && firstCollisionPos->size() != n) firstCollisionPos->resize(n, Eigen::Vector3d(0.0, 0.0, 0.0));
+    if (dynamicCollision) dynamicCollision->assign(n, false);
+    BatchStats st;
+    std::vector<uint8_t> todo(n, 0);    // the planners the per-planner route below still owes
+    long long want = 0, left = 0;
+    for (size_t i = 0; i < n; ++i) todo[i] = planners[i]->init_ ? 1 : 0, want += todo[i];
+    validateOnDevice(planners, todo, valid, firstCollisionPos, dynamicCollision, st);
+    for (size_t i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        ++left;
+        bsplineTraj* p = planners[i];
+        Eigen::Vector3d hit;
+        valid[i] = p->isCurrTrajValid(hit);
+        if (!valid[i] && firstCollisionPos) (*firstCollisionPos)[i] = hit;
+        if (dynamicCollision) (*dynamicCollision)[i] = p->hasDynamicCollisionTrajectory(p->optData_.controlPoints);
+    }
+    st.validateDecided = want - left;
+    st.validateHost = left;
+    reportBatchStats(st, stats);
+    return valid;
+}
+
 }  // namespace trajPlanner

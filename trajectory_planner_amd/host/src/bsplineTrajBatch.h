@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "../../../include/vigo.h"
+#include "../../../include/vigo_validate.h"
 #include "batchLayout.h"
 #include "devbuf.h"
 #include "workerPool.h"

@@ -2401,3 +2401,142 @@ extern "C" int vigo_host_snapshot_refresh(const unsigned char* vox, const int* d
     totals[2] = after.regionVoxels - before.regionVoxels;
     return 0;
 }
+
+namespace {
+// n planners on the fixture's one map, each fitted to its pose list by updatePath (held plans: nothing is planned); planner
+// `no_device` is bound to a card that does not exist, planner `not_init` never gets a path (either -1: none); planner t's
+// dynamic obstacles are rows obs_off[t] .. obs_off[t + 1] - 1 of obs[][9] (position, velocity, size), obs_off NULL: none
+FreshPlanners heldPlanners(const BatchFixture& fx, int no_device, int not_init, const int* obs_off, const double* obs) {
+    FreshPlanners fp;
+    for (size_t t = 0; t < fx.in.size(); ++t) {
+        fp.owners.emplace_back(new bsplineTraj(fx.nh));
+        bsplineTraj& p = *fp.owners.back();
+        p.setMap(fx.maps[0]);
+        p.updateMaxVel(2.0);
+        p.updateMaxAcc(3.0);
+        if ((int)t == no_device) p.setDevice(63);
+        if ((int)t != not_init) p.updatePath(fx.in[t], fx.cond[t]);
+        if (obs_off && obs_off[t + 1] > obs_off[t]) {
+            std::vector<Eigen::Vector3d> pos, vel, size;
+            for (int j = obs_off[t]; j < obs_off[t + 1]; ++j) {
+                const double* o = obs + 9 * (size_t)j;
+                pos.push_back(Eigen::Vector3d(o[0], o[1], o[2]));
+                vel.push_back(Eigen::Vector3d(o[3], o[4], o[5]));
+                size.push_back(Eigen::Vector3d(o[6], o[7], o[8]));
+            }
+            p.updateDynamicObstacles(pos, vel, size);
+        }
+        fp.ps.push_back(&p);
+    }
+    return fp;
+}
+
+// both routes on the planners as they stand, into slot 0 (isCurrTrajValidBatch) and slot 1 (the per-planner loop:
+// isCurrTrajValid(pos), hasDynamicCollisionTrajectory) of valid[2][n], pos[2][n][3] (an entry is written only where the
+// route writes it), dyn[2][n]; stats[3]: the batch call's validateDecided, validateHost, validateGroups
+void validateBothRoutes(const std::vector<bsplineTraj*>& ps, int* valid, double* pos, int* dyn, long long* stats) {
+    const size_t n = ps.size();
+    std::vector<Eigen::Vector3d> hit(n);
+    for (size_t t = 0; t < n; ++t) hit[t] = Eigen::Vector3d(pos[3 * t], pos[3 * t + 1], pos[3 * t + 2]);
+    std::vector<bool> dynamic;
+    bsplineTraj::BatchStats st;
+    const std::vector<bool> ok = bsplineTraj::isCurrTrajValidBatch(ps, &hit, &dynamic, &st);
+    for (size_t t = 0; t < n; ++t) {
+        valid[t] = ok[t] ? 1 : 0;
+        dyn[t] = dynamic[t] ? 1 : 0;
+        for (int a = 0; a < 3; ++a) pos[3 * t + a] = hit[t](a);
+        Eigen::Vector3d one(pos[3 * (n + t)], pos[3 * (n + t) + 1], pos[3 * (n + t) + 2]);
+        valid[n + t] = ps[t]->isCurrTrajValid(one) ? 1 : 0;
+        dyn[n + t] = ps[t]->hasDynamicCollisionTrajectory(ps[t]->getControlPoints()) ? 1 : 0;
+        for (int a = 0; a < 3; ++a) pos[3 * (n + t) + a] = one(a);
+    }
+    stats[0] = st.validateDecided;
+    stats[1] = st.validateHost;
+    stats[2] = st.validateGroups;
+}
+}  // namespace
+
+// Held plans validated in one call: n planners with a pose list each (as vigo_host_plan_batch_options) on ONE dense map,
+// made by heldPlanners (no_device, not_init, obs_off / obs as there).  Outputs: validateBothRoutes' valid, pos, dyn (pos
+// prefilled by the caller) and stats; ncp[n] the planners' control-point counts; totals[3]: what the same three fields of
+// bsplineTraj::batchTotals() moved by over the batch call; ms[reps][2] (reps may be 0): the wall time of the batch form and
+// of the per-planner loop, run again in turn.  Returns 0, -1 on a bad argument, -3 when a call threw.  Needs a GPU.
+extern "C" int vigo_host_validate_batch(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                        const double* path_xyz, const double* cfg, int no_device, int not_init, const int* obs_off, const double* obs,
+                                        int* valid, double* pos, int* dyn, int* ncp, long long* stats, long long* totals, int reps, double* ms) {
+    if (n < 1 || !path_off || !path_xyz || !cfg || !valid || !pos || !dyn || !ncp || !stats || !totals || reps < 0 || (reps > 0 && !ms)) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    try {
+        BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+        FreshPlanners fp = heldPlanners(fx, no_device, not_init, obs_off, obs);
+        for (int t = 0; t < n; ++t) ncp[t] = (int)fp.ps[t]->getControlPoints().cols();
+        const bsplineTraj::BatchStats before = bsplineTraj::batchTotals();
+        validateBothRoutes(fp.ps, valid, pos, dyn, stats);
+        const bsplineTraj::BatchStats after = bsplineTraj::batchTotals();
+        totals[0] = after.validateDecided - before.validateDecided;
+        totals[1] = after.validateHost - before.validateHost;
+        totals[2] = after.validateGroups - before.validateGroups;
+        // (workload tools) the two routes again, alternating, wall clock per route: the answers above stand
+        for (int rep = 0; rep < reps; ++rep) {
+            std::vector<Eigen::Vector3d> hit(fp.ps.size());
+            std::vector<bool> dynamic;
+            auto t0 = std::chrono::steady_clock::now();
+            (void)bsplineTraj::isCurrTrajValidBatch(fp.ps, &hit, &dynamic);
+            ms[2 * rep] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            t0 = std::chrono::steady_clock::now();
+            for (bsplineTraj* p : fp.ps) {
+                Eigen::Vector3d one;
+                (void)p->isCurrTrajValid(one);
+                (void)p->hasDynamicCollisionTrajectory(p->getControlPoints());
+            }
+            ms[2 * rep + 1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+    } catch (...) {
+        return -3;
+    }
+    return 0;
+}
+
+// A map that changes under held plans: the planners of vigo_host_validate_batch (all with a device, all initialised, no
+// obstacles) are validated by both routes after the first upload (round 0) and after each of E edits (round e + 1), edit e
+// written and announced as in vigo_host_map_update_replan (mode 0: ++version, mode 1: markChanged(lo, n)).  Outputs per
+// round r: valid[E+1][2][n], pos[E+1][2][n][3] (prefilled by the caller), dyn[E+1][2][n], stats[E+1][3]; totals[3]: what
+// mapAdapter::snapshotTotals moved by over the call.  Returns 0, -1 on a bad argument, -3 when a call threw.  Needs a GPU.
+extern "C" int vigo_host_map_update_validate(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
+                                             const double* path_xyz, const double* cfg, int E, const int* edit_lo, const int* edit_n,
+                                             const long long* edit_off, const unsigned char* edit_bytes, int mode, int* valid, double* pos, int* dyn,
+                                             long long* stats, long long* totals) {
+    if (n < 1 || !path_off || !path_xyz || !cfg || E < 0 || (mode != 0 && mode != 1) || !valid || !pos || !dyn || !stats || !totals) return -1;
+    for (int t = 0; t < n; ++t)
+        if (path_off[t + 1] - path_off[t] < 2) return -1;
+    for (int e = 0; e < E; ++e)
+        for (int a = 0; a < 3; ++a)
+            if (edit_lo[3 * e + a] < 0 || edit_n[3 * e + a] < 0 || edit_lo[3 * e + a] + edit_n[3 * e + a] > dims[a]) return -1;
+    try {
+        BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
+        const trajPlanner::mapAdapter::SnapshotTotals before = trajPlanner::mapAdapter::snapshotTotals();
+        FreshPlanners fp = heldPlanners(fx, -1, -1, nullptr, nullptr);
+        mapManager::occMap& map = *fx.maps[0];
+        for (int r = 0; r <= E; ++r) {
+            if (r > 0) {
+                const int e = r - 1;
+                const int *lo = edit_lo + 3 * e, *en = edit_n + 3 * e;
+                const unsigned char* src = edit_bytes + edit_off[e];
+                for (int ix = 0; ix < en[0]; ++ix)
+                    for (int iy = 0; iy < en[1]; ++iy)
+                        for (int iz = 0; iz < en[2]; ++iz) map.at(lo[0] + ix, lo[1] + iy, lo[2] + iz) = src[((size_t)ix * en[1] + iy) * en[2] + iz];
+                if (mode == 1) map.markChanged(lo, en);
+                else ++map.version;
+            }
+            validateBothRoutes(fp.ps, valid + (size_t)r * 2 * n, pos + (size_t)r * 6 * n, dyn + (size_t)r * 2 * n, stats + 3 * r);
+        }
+        const trajPlanner::mapAdapter::SnapshotTotals after = trajPlanner::mapAdapter::snapshotTotals();
+        totals[0] = after.fullSnapshots - before.fullSnapshots;
+        totals[1] = after.regionUpdates - before.regionUpdates;
+        totals[2] = after.regionVoxels - before.regionVoxels;
+    } catch (...) {
+        return -3;
+    }
+    return 0;
+}

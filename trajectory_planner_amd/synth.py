@@ -429,6 +429,39 @@ def host_traj_finish(ts_ctrl, ts, ctrl, limits, sample_dt, S_cap, n_pts=None, ou
     return {"factor": factor, "max": mx, "n": n, "pos": pos, "vel": vel, "status": status}
 
 
+def host_traj_validate(world, ts_ctrl, ctrl, dt, n_pts=None, not_check_ratio=0.0, rule=0, obs_off=None, obs=None, want_list=True, out=None,
+                       want_pos=True, want_dyn=True):
+    """Vigo.traj_validate's result by the library's host twin (vigo_traj_validate_host: csrc/vigo_validate_core.hpp
+    compiled for the CPU; no GPU), numpy in and out, on world.voxels / origin / res: ctrl [B,Ns,3], n_pts int32 [B] or None,
+    obs_off int32 [B+1] or None (obs [O,9] is then shared) -> dict of status, first, pos, dyn_first, invalid, n_invalid.
+    out = (pos, invalid): the arrays those are written into (rows that are not written keep what they held).  Returns the
+    library's code instead of the dict when the call is refused."""
+    import ctypes as C
+    from . import _lib
+    ctrl = np.ascontiguousarray(ctrl, dtype=np.float64)
+    B, Ns = ctrl.shape[0], ctrl.shape[1]
+    vox = np.ascontiguousarray(world.voxels, dtype=np.uint8)
+    origin = np.ascontiguousarray(world.origin, dtype=np.float64)
+    npts = None if n_pts is None else np.ascontiguousarray(n_pts, dtype=np.int32)
+    off = None if obs_off is None else np.ascontiguousarray(obs_off, dtype=np.int32)
+    ob = None if obs is None else np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 9)
+    pos = np.zeros((B, 3)) if want_pos else None
+    invalid = np.zeros(B, dtype=np.int32) if want_list else None
+    if out is not None:
+        pos, invalid = out
+    status, first = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    dyn = np.zeros(B, dtype=np.int32) if want_dyn else None
+    n_invalid = np.zeros(1, dtype=np.int32) if invalid is not None else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    ns = len(ob) if (ob is not None and off is None) else 0
+    rc = _lib.load().vigo_traj_validate_host(vox.shape[0], vox.shape[1], vox.shape[2], origin.ctypes.data_as(C.POINTER(C.c_double)), float(world.res),
+                                             p(vox), float(ts_ctrl), B, Ns, p(npts), p(ctrl), float(dt), float(not_check_ratio), int(rule),
+                                             p(off), p(ob), ns, p(status), p(first), p(pos), p(dyn), p(invalid), p(n_invalid))
+    if rc != 0:
+        return rc
+    return {"status": status, "first": first, "pos": pos, "dyn_first": dyn, "invalid": invalid, "n_invalid": n_invalid}
+
+
 # ---- guides from the planner's own host pipeline (product code: libtrajectory_planner_vigo.so) ---------------------------
 # cfg/bspline_interactive/bspline_planner_param.yaml: distance_threshold, min_height, max_height, max_obstacle_size
 PIPELINE_CFG = np.array([0.5, 0.7, 1.3, 5.0, 5.0, 3.0])

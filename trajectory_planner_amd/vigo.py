@@ -22,6 +22,8 @@ REGUIDE_DONE, REGUIDE_SEARCH_FAILED, REGUIDE_NOT_REQUIRED, REGUIDE_DEFERRED, REG
 PATHS_OK, PATHS_FAILED, PATHS_DEFERRED = 0, 1, 2                                 # vigo_collision_segs' / vigo_path_search's out_status
 SEED_OK, SEED_NO_SPACING, SEED_GOAL_OCCUPIED, SEED_TOO_SHORT, SEED_DEFERRED, SEED_BAD_INPUT = 0, 1, 2, 3, 4, 5   # vigo_seed_paths' out_status
 FINISH_OK, FINISH_CAPACITY, FINISH_INVALID_N = 0, 1, 2   # vigo_traj_finish's out_status
+VALID_STATIC, VALID_DYNAMIC, VALID_BAD_COUNT = 1, 2, 4   # vigo_traj_validate's out_status bits (include/vigo_validate.h)
+VALIDATE_BY_TIME, VALIDATE_BY_INDEX = 0, 1               # ... and its rules
 
 # lbfgs.hpp:20-80 status codes worth naming
 LBFGS_CONVERGENCE = 0
@@ -513,6 +515,43 @@ class Vigo:
                                                C.c_void_p(pos.data_ptr()), None if vel is None else C.c_void_p(vel.data_ptr()),
                                                C.c_void_p(status.data_ptr())), "vigo_traj_finish")
         return {"factor": factor, "max": mx, "n": n, "pos": pos, "vel": vel, "status": status}
+
+    def traj_validate(self, ctrl, dt, n_pts=None, not_check_ratio=0.0, rule=0, obs_off=None, obs=None, want_list=True, out=None,
+                      want_pos=True, want_dyn=True):
+        """vigo_traj_validate (include/vigo_validate.h): are the held plans ctrl [B,Ns,3] f64 (row b holds n_pts[b] control
+        points, i32 [B]; None: Ns each) still valid on the current map -> dict of status i32[B] (VALID_* bits, 0 = valid),
+        first i32[B] (first colliding static sample or -1), pos f64[B,3] (its position; None without want_pos),
+        dyn_first i32[B] (first sample inside an obstacle or -1; None without want_dyn), invalid i32[B] and n_invalid
+        i32[1] (the rows with a status, ascending, and their number; None without want_list).  rule 0: the static check
+        covers t <= (1 - not_check_ratio) * duration, rule 1: the samples k < (1 - not_check_ratio) * S.  Rows of pos
+        without a static hit and entries of invalid beyond n_invalid are not written: zeros, or what the caller's
+        out = (pos, invalid) held.  Stream-ordered, no host round trip."""
+        _shape(ctrl, (None, None, 3), "ctrl")
+        B, Ns, _ = ctrl.shape
+        _shape(n_pts, (B,), "n_pts")
+        _shape(obs, (None, 9), "obs")
+        if obs_off is not None and obs_off.numel() != B + 1:
+            raise ValueError("obs_off must have B+1 entries")
+        d = self.device
+        pos = torch.zeros(B, 3, dtype=torch.float64, device=d) if want_pos else None
+        invalid = torch.zeros(B, dtype=torch.int32, device=d) if want_list else None
+        if out is not None:
+            pos, invalid = out
+            if pos is not None:
+                _shape(pos, (B, 3), "out pos"); _ptr(pos, torch.float64, "out pos", d)
+            if invalid is not None:
+                _shape(invalid, (B,), "out invalid"); _ptr(invalid, torch.int32, "out invalid", d)
+        status = torch.zeros(B, dtype=torch.int32, device=d)
+        first = torch.zeros(B, dtype=torch.int32, device=d)
+        dyn = torch.zeros(B, dtype=torch.int32, device=d) if want_dyn else None
+        n_invalid = torch.zeros(1, dtype=torch.int32, device=d) if invalid is not None else None
+        ns = obs.shape[0] if (obs is not None and obs_off is None) else 0
+        opt = lambda t: None if t is None else C.c_void_p(t.data_ptr() or 1)       # (an empty tensor has no address: B == 0 reads nothing)
+        self._check(self._lib.vigo_traj_validate(self._h, B, Ns, _ptr(n_pts, torch.int32, "n_pts", d), _ptr(ctrl, torch.float64, "ctrl", d),
+                                                 float(dt), float(not_check_ratio), int(rule), _ptr(obs_off, torch.int32, "obs_off", d),
+                                                 _ptr(obs, torch.float64, "obs", d), ns, opt(status), opt(first), opt(pos), opt(dyn),
+                                                 opt(invalid), opt(n_invalid)), "vigo_traj_validate")
+        return {"status": status, "first": first, "pos": pos, "dyn_first": dyn, "invalid": invalid, "n_invalid": n_invalid}
 
     def traj_dynamic_collision(self, ctrl, dt, obs_off=None, obs=None):
         _shape(ctrl, (None, None, 3), "ctrl")
