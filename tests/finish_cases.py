@@ -271,29 +271,16 @@ def by_name(name):
 
 # ---- the facade's stage (host/src/cabi_host.cpp) -----------------------------------------------------------------------
 def plan_batch_finish(world, path_off, xyz, no_device=-1, small_step=-1, step=0.0, with_paths=True, yaw=True, reps=1, pose_cap=160, cfg=None):
-    """vigo_host_plan_batch_finish: makePlanBatch (with_paths: the overload that returns trajectories) with
-    setDeviceEpilogue off (slot 0) and on (slot 1) -> dict of per-slot arrays; totals[slot] = (planners the device call
-    decided, planners on the host route, device groups).  Needs a GPU."""
-    import ctypes as C
-    import os
-    from trajectory_planner_amd import synth
-    lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "trajectory_planner_amd", "lib", "libtrajectory_planner_vigo.so"))
+    """makePlanBatch (with_paths: the overload that returns trajectories) with setDeviceEpilogue off (slot 0) and on (slot
+    1), `reps` rounds over off, then on -> dict of per-slot arrays; totals[slot] = (planners the device call decided,
+    planners on the host route, device groups).  Planner no_device sits on a device ordinal that does not exist, planner
+    small_step gets bspline_traj/timestep = step, a group of its own (< 0: none).  Needs a GPU."""
+    import plan_batch as pb
     n = len(path_off) - 1
-    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG if cfg is None else cfg, dtype=np.float64)
-    ok, n_poses = np.zeros((2, n), dtype=np.int32), np.zeros((2, n), dtype=np.int32)
-    factor, pos, quat = np.zeros((2, n)), np.zeros((2, n, pose_cap, 3)), np.zeros((2, n, pose_cap, 4))
-    totals, ms = np.zeros((2, 3), dtype=np.int64), np.zeros((2, reps))
-    off, xyz = np.ascontiguousarray(path_off, dtype=np.int32), np.ascontiguousarray(xyz, dtype=np.float64)
-    f = lib.vigo_host_plan_batch_finish
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, ip, dp,
-                  dp, lp, dp]
-    rc = f(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), float(world.res), n, off.ctypes.data_as(ip),
-           xyz.ctypes.data_as(dp), cfg.ctypes.data_as(dp), int(no_device), int(small_step), float(step), int(bool(with_paths)), int(bool(yaw)), int(reps),
-           int(pose_cap), ok.ctypes.data_as(ip), factor.ctypes.data_as(dp), n_poses.ctypes.data_as(ip), pos.ctypes.data_as(dp), quat.ctypes.data_as(dp),
-           totals.ctypes.data_as(lp), ms.ctypes.data_as(dp))
-    assert rc == 0, rc
-    lib.vigo_host_switches.restype = C.c_int
-    return dict(ok=ok, factor=factor, n_poses=n_poses, pos=pos, quat=quat, totals=totals, total_ms=ms, switches=int(lib.vigo_host_switches()))
+    device, timestep = np.full(n, -1), np.full(n, np.nan)
+    device[[no_device] if no_device >= 0 else []] = 63
+    timestep[[small_step] if small_step >= 0 else []] = step
+    r = pb.plan_batch(world, path_off, xyz, [(0, 16384, pb.BY_CALL), (pb.EPILOGUE, 16384, pb.BY_CALL)], [0, 1] * reps, outputs=("ok", "factor", "poses"),
+                      cfg=cfg, with_paths=with_paths, yaw=yaw, planner_device=device, planner_timestep=timestep, pose_cap=pose_cap)
+    return dict(totals=pb.stat(r, "epilogueDecided", "epilogueHost", "epilogueGroups"), total_ms=r["slot_seconds"][:, :, 2] * 1e3, switches=r["switches"],
+                **{k: r[k] for k in ("ok", "factor", "n_poses", "pos", "quat")})

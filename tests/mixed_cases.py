@@ -267,28 +267,9 @@ def pose_lists(world, poses, seed=23):
 
 
 def plan_batch_mixed(world, path_off, xyz, reps=1, cfg=synth.PIPELINE_CFG):
-    """vigo_host_plan_batch_mixed (host/src/cabi_host.cpp): makePlanBatch with setMixedBatches off (slot 0) and on (slot 1)
-    -> dict of per-slot arrays"""
-    import os
-    lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "trajectory_planner_amd", "lib", "libtrajectory_planner_vigo.so"))
-    n = len(path_off) - 1
-    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(cfg, dtype=np.float64)
-    ncp_cap, room = 96, 256 * n
-    ok, solver, ncp, ns, ng = (np.zeros((2, n), dtype=np.int32) for _ in range(5))
-    ctrl, segs, guides = np.zeros((2, n, ncp_cap, 3)), np.zeros((2, room, 2), dtype=np.int32), np.zeros((2, room, 6))
-    tot, counts = np.zeros((2, reps)), np.zeros((2, 2), dtype=np.int64)
-    lib.vigo_host_plan_batch_mixed.restype = C.c_int
-    lib.vigo_host_plan_batch_mixed.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.c_longlong, ip, ip, ip, dp, ip, ip,
-                                               ip, dp, dp, lp]
-    off = np.ascontiguousarray(path_off, dtype=np.int32)
-    rc = lib.vigo_host_plan_batch_mixed(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), float(world.res), n,
-                                        off.ctypes.data_as(ip), xyz.ctypes.data_as(dp), cfg.ctypes.data_as(dp), reps, ncp_cap, room,
-                                        ok.ctypes.data_as(ip), solver.ctypes.data_as(ip), ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp),
-                                        ns.ctypes.data_as(ip), segs.ctypes.data_as(ip), ng.ctypes.data_as(ip), guides.ctypes.data_as(dp),
-                                        tot.ctypes.data_as(dp), counts.ctypes.data_as(lp))
-    assert rc == 0, rc
-    lib.vigo_host_switches.restype = C.c_int
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_seg=ns, segs=segs, n_guides=ng, guides=guides, total_ms=tot, counts=counts,
-                switches=int(lib.vigo_host_switches()))
+    """makePlanBatch with setMixedBatches off (slot 0) and on (slot 1), `reps` rounds over off, then on -> dict of per-slot
+    arrays; counts[slot] = (device batches the solves and rounds opened, planners in them)"""
+    import plan_batch as pb
+    r = pb.plan_batch(world, path_off, xyz, [(0, 16384, pb.BY_CALL), (pb.MIXED_BATCHES, 16384, pb.BY_CALL)], [0, 1] * reps, cfg=cfg)
+    return dict(total_ms=r["slot_seconds"][:, :, 2] * 1e3, counts=pb.stat(r, "solveBatches", "solvePlanners"), switches=r["switches"],
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_seg", "segs", "n_guides", "guides")})

@@ -16,7 +16,6 @@ A trajectory of 7 control points can own no segment (endIdx = 3: the scan looks 
 and endIdx - 1 < 3), nor can one of 8 under not_check_ratio 0.3 (endIdx = 3 again); those rows are in the batch all the
 same.  Rows are interleaved over the counts, B is odd.  Cases are named and seeded (the seed jitters every line off the
 voxel boundaries)."""
-import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -24,6 +23,7 @@ import numpy as np
 
 import pathsearch_cases as pc
 import reguide_cases as rc
+from plan_batch import ASTAR as M_ASTAR, GUIDES1 as M_GUIDES1, MIXED_BATCHES as M_MIXED_BATCHES, PROLOGUE as M_PROLOGUE, REGUIDE1 as M_REGUIDE1  # noqa: F401
 
 COUNTS = (7, 8, 12, 31, 32, 33, 40, 64, 65, 120)
 NCRS = (0.0, 0.3)
@@ -254,39 +254,16 @@ def reguide_rows(lib, case):
 
 
 # ---- makePlanBatch under mixedPrologue (needs a GPU) -----------------------------------------------------------------
-# the mask bits of vigo_host_plan_batch_options (host/src/cabi_host.cpp: optionsOfMask)
-M_ASTAR, M_GUIDES1, M_PROLOGUE, M_REGUIDE1, M_MIXED_BATCHES = 1, 2, 8, 16, 64
+# of plan_batch.STAT_NAMES; guidesAstarDecided: the sum of the two
 COUNT_NAMES = ("prologueGroups", "reguideGroups", "prologueDecided", "prologueHost", "reguideDecided", "reguideHost", "guidesAstarDecided", "solveBatches")
 
 
 def plan_batch_mixed_prologue(world, path_off, xyz, mask, reps=1, budget=16384, cfg=None):
-    """vigo_host_plan_batch_mixed_prologue: makePlanBatch under the options of `mask` with mixedPrologue off (slot 0) and on
-    (slot 1), fresh planners every run -> dict of per-slot arrays; seconds [2, reps, 3]: prologue, chains, the whole call"""
-    from trajectory_planner_amd import synth
-    lib = C.CDLL(pc.LIB)
-    n = len(path_off) - 1
-    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG if cfg is None else cfg, dtype=np.float64)
-    ncp_cap, room, pose_cap = 96, 256 * n, 512
-    ok, solver, ncp, ns, ng, npp, nposes = (np.zeros((2, n), dtype=np.int32) for _ in range(7))
-    ctrl, segs, guides, paths = np.zeros((2, n, ncp_cap, 3)), np.zeros((2, room, 2), dtype=np.int32), np.zeros((2, room, 6)), np.zeros((2, room, 3))
-    pos, quat = np.zeros((2, n, pose_cap, 3)), np.zeros((2, n, pose_cap, 4))
-    counts, seconds = np.zeros((2, 8), dtype=np.int64), np.zeros((2, reps, 3))
-    fn = lib.vigo_host_plan_batch_mixed_prologue
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, ip, ip, ip, dp, ip, ip,
-                   ip, dp, ip, dp, ip, dp, dp, lp, dp]
-    off = np.ascontiguousarray(path_off, dtype=np.int32)
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-    r = fn(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), float(world.res), n, off.ctypes.data_as(ip),
-           xyz.ctypes.data_as(dp), cfg.ctypes.data_as(dp), int(mask), int(budget), int(reps), ncp_cap, room, pose_cap, ok.ctypes.data_as(ip),
-           solver.ctypes.data_as(ip), ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp), ns.ctypes.data_as(ip), segs.ctypes.data_as(ip),
-           ng.ctypes.data_as(ip), guides.ctypes.data_as(dp), npp.ctypes.data_as(ip), paths.ctypes.data_as(dp), nposes.ctypes.data_as(ip),
-           pos.ctypes.data_as(dp), quat.ctypes.data_as(dp), counts.ctypes.data_as(lp), seconds.ctypes.data_as(dp))
-    assert r == 0, r
-    lib.vigo_host_switches.restype = C.c_int
-    lib.vigo_host_mixed_prologue_default.restype = C.c_int
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_seg=ns, segs=segs, n_guides=ng, guides=guides, n_path_pts=npp, paths=paths, n_poses=nposes,
-                pos=pos, quat=quat, counts={k: counts[:, i] for i, k in enumerate(COUNT_NAMES)}, seconds=seconds,
-                switches=int(lib.vigo_host_switches()), mixed_prologue_default=int(lib.vigo_host_mixed_prologue_default()))
+    """makePlanBatch under the options of `mask` with mixedPrologue off (slot 0) and on (slot 1), `reps` rounds over off,
+    then on, fresh planners every run -> dict of per-slot arrays; seconds [2, reps, 3]: prologue, chains, the whole call"""
+    import plan_batch as pb
+    r = pb.plan_batch(world, path_off, xyz, [(mask, budget, pb.BY_CALL), (mask | pb.MIXED_PROLOGUE, budget, pb.BY_CALL)], [0, 1] * reps,
+                      outputs=("ok", "solver", "ncp", "ctrl", "segs", "guides", "paths", "poses"), cfg=cfg, with_paths=True, pose_cap=512)
+    counts = {k: pb.stat(r, "guidesDecided") + pb.stat(r, "astarDecided") if k == "guidesAstarDecided" else pb.stat(r, k) for k in COUNT_NAMES}
+    return dict(counts=counts, seconds=r["slot_seconds"], switches=r["switches"], mixed_prologue_default=(r["switches"] >> 8) & 1,
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_seg", "segs", "n_guides", "guides", "n_path_pts", "paths", "n_poses", "pos", "quat")})

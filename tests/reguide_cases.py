@@ -392,33 +392,18 @@ def pipeline_paths(P, N=32, seed=11):
     return world, np.ascontiguousarray(np.concatenate(out)[:P])
 
 
-SLOT_TWIN, SLOT_DEVICE, SLOT_HOST, SLOT_UNTOUCHED = 0, 1, 2, 3    # vigo_host_plan_batch_reguide: setDeviceReguide(2), (1), (0), never called
+SLOT_TWIN, SLOT_DEVICE, SLOT_HOST, SLOT_UNTOUCHED = 0, 1, 2, 3    # setDeviceReguide(2), (1), (0), never called
 
 
 def plan_batch_reguide(P, slots=0b111, budget=16384, reps=1):
-    """vigo_host_plan_batch_reguide on P planners of the pipeline world -> dict of per-slot arrays"""
-    from trajectory_planner_amd import synth
-    lib = C.CDLL(LIB)
+    """P planners of the pipeline world: SLOT_UNTOUCHED once, first, then `reps` rounds over the slots of `slots` (bit k: slot
+    k runs) among the first three; twin: the re-guide steps SLOT_TWIN's last run logged, and how many of them the kernels'
+    host twin decides under the shipped capacities -> dict of per-slot arrays"""
+    import plan_batch as pb
     world, pts = pipeline_paths(P)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG, dtype=np.float64)
     cap = shipped()
-    caps = (C.c_int * 4)(cap["cap_log2"], cap["max_nodes"], cap["heap_cap"], cap["guide_path_cap"])
-    ncp_cap, room = 64, 256 * P
-    ok, solver, ncp, ns, npp, ng = (np.zeros((4, P), dtype=np.int32) for _ in range(6))
-    ctrl, segs, paths, guides = np.zeros((4, P, ncp_cap, 3)), np.zeros((4, room, 2), dtype=np.int32), np.zeros((4, room, 3)), np.zeros((4, room, 6))
-    tot, counts, twin_n = np.zeros((4, reps)), np.zeros((4, 2), dtype=np.int64), np.zeros(2, dtype=np.int64)
-    lp = C.POINTER(C.c_longlong)
-    lib.vigo_host_plan_batch_reguide.restype = C.c_int
-    lib.vigo_host_plan_batch_reguide.argtypes = [C.c_void_p, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_int,
-                                                 C.c_longlong, _ip, _ip, _ip, _dp, _ip, _ip, _ip, _dp, _ip, _dp, _dp, lp, lp]
-    rc = lib.vigo_host_plan_batch_reguide(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(_dp), float(world.res), P,
-                                          pts.shape[1], pts.ctypes.data_as(_dp), cfg.ctypes.data_as(_dp), slots, budget, reps, caps, ncp_cap, room,
-                                          ok.ctypes.data_as(_ip), solver.ctypes.data_as(_ip), ncp.ctypes.data_as(_ip), ctrl.ctypes.data_as(_dp),
-                                          ns.ctypes.data_as(_ip), segs.ctypes.data_as(_ip), npp.ctypes.data_as(_ip), paths.ctypes.data_as(_dp),
-                                          ng.ctypes.data_as(_ip), guides.ctypes.data_as(_dp), tot.ctypes.data_as(_dp), counts.ctypes.data_as(lp),
-                                          twin_n.ctypes.data_as(lp))
-    assert rc == 0
-    lib.vigo_host_switches.restype = C.c_int
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_seg=ns, segs=segs, n_path_pts=npp, paths=paths, n_guides=ng, guides=guides, total_ms=tot,
-                counts=counts, twin=twin_n, switches=int(lib.vigo_host_switches()))
+    r = pb.plan_batch(world, *pb.uniform_paths(pts), [(m, budget, pb.BY_CALL) for m in (pb.REGUIDE2, pb.REGUIDE1, 0)] + [(0, budget, pb.UNTOUCHED)],
+                      [SLOT_UNTOUCHED] + [s for s in range(3) if (slots >> s) & 1] * reps, outputs=("ok", "solver", "ncp", "ctrl", "segs", "paths", "guides"),
+                      replay_slot=SLOT_TWIN if slots & 1 else -1, caps=[cap[k] for k in ("cap_log2", "max_nodes", "heap_cap", "guide_path_cap")], ncp_cap=64, lib=LIB)
+    return dict(total_ms=r["slot_seconds"][:, :, 2] * 1e3, counts=pb.stat(r, "reguideDecided", "reguideHost"), twin=r["twin"], switches=r["switches"],
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_seg", "segs", "n_path_pts", "paths", "n_guides", "guides")})

@@ -3,12 +3,14 @@ the search's own counts (pops, pushed nodes, heap peak) bit for bit on the craft
 every prologue search of the pipeline batch, with at most 2 % of those deferred — its argument checks, its independence
 of the batch, and bsplineTraj::makePlanBatch with setDeviceAstar(true) against the same call with the host A*."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import astar_cases as ac
+import plan_batch as pb
 from gpu_util import to_dev
 from trajectory_planner_amd import _lib, synth
 from trajectory_planner_amd.vigo import ASTAR_DEFERRED, ASTAR_FOUND, ASTAR_NOT_FOUND, ASTAR_PATH_TOO_LONG
@@ -164,26 +166,14 @@ def _facade_paths(P):
 
 
 def _plan_twice(P, n_maps=1, budget=16384, reps=1, second_world=None):
-    lib = ac.host_lib()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    """slot 0: the prologue's A* on the host, slot 1: deviceAstar; alternating, `reps` times"""
     vox, origin = _facade_world()
-    vox2 = np.ascontiguousarray(_facade_world(**second_world)[0]) if second_world else None
-    pts = np.ascontiguousarray(_facade_paths(P))
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG, dtype=np.float64)
-    ncp_cap, cap = 64, 64 * P
-    ok, solver, ncp, ng, npp = (np.zeros((2, P), dtype=np.int32) for _ in range(5))
-    ctrl, guides, paths = np.zeros((2, P, ncp_cap, 3)), np.zeros((2, cap, 6)), np.zeros((2, cap, 3))
-    pro, tot, counts = np.zeros((2, reps)), np.zeros((2, reps)), np.zeros(2, dtype=np.int64)
-    lib.vigo_host_plan_batch_astar.restype = C.c_int
-    lib.vigo_host_plan_batch_astar.argtypes = [C.c_void_p, C.c_void_p, ip, dp, C.c_double, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
-                                               ip, ip, ip, dp, ip, dp, ip, dp, dp, dp, C.POINTER(C.c_longlong)]
-    rc = lib.vigo_host_plan_batch_astar(vox.ctypes.data_as(C.c_void_p), vox2.ctypes.data_as(C.c_void_p) if second_world else None, (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), 0.1, P, pts.shape[1],
-                                        pts.ctypes.data_as(dp), cfg.ctypes.data_as(dp), n_maps, budget, reps, ncp_cap, cap, ok.ctypes.data_as(ip),
-                                        solver.ctypes.data_as(ip), ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp), ng.ctypes.data_as(ip),
-                                        guides.ctypes.data_as(dp), npp.ctypes.data_as(ip), paths.ctypes.data_as(dp), pro.ctypes.data_as(dp),
-                                        tot.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_longlong)))
-    assert rc == 0
-    return dict(device_decided=int(counts[0]), host_run=int(counts[1]), ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_guides=ng, guides=guides, n_path_pts=npp, paths=paths, prologue_ms=pro, total_ms=tot)
+    r = pb.plan_batch(SimpleNamespace(voxels=vox, origin=origin, res=0.1), *pb.uniform_paths(_facade_paths(P)),
+                      [(0, budget, pb.BY_CALL), (pb.ASTAR, budget, pb.BY_CALL)], [0, 1] * reps, outputs=("ok", "solver", "ncp", "ctrl", "guides", "paths"),
+                      vox2=_facade_world(**second_world)[0] if second_world else None, n_maps=n_maps, ncp_cap=64, room=64 * P)
+    decided, host = pb.stat(r, "astarDecided", "astarHost")[1]
+    return dict(device_decided=int(decided), host_run=int(host), prologue_ms=r["slot_seconds"][:, :, 0] * 1e3, total_ms=r["slot_seconds"][:, :, 2] * 1e3,
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_guides", "guides", "n_path_pts", "paths")})
 
 
 def _same_plans(r, label, device_share, first_world=slice(None)):

@@ -1,4 +1,4 @@
-"""-m gpu: bsplineTraj's per-call BatchOptions / BatchStats through vigo_host_plan_batch_options: ONE
+"""-m gpu: bsplineTraj's per-call BatchOptions / BatchStats through vigo_host_plan_batch: ONE
 makePlanBatch(planners, trajectories, yaw) per run, under the options a switch mask names (vigo_host_switches' bits).
 
 Every mask runs by two routes — the options passed to the call, and the same options set as the process default through
@@ -15,24 +15,18 @@ classes, six counts, two planners per count.  Every mask must give the stage it 
 count > 0, asserted), and mixed batches must open fewer solve batches than default options.  12 planners were enough for
 every stage: measured on an MI355X, 9 of them plan, the prologue makes 15 A* searches (14 decided by the device, one by
 the host), the straight paths reach 8 re-guide steps, and the solves and rounds open 34 device batches, 20 when mixed."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
 import mixed_cases as mc
-from trajectory_planner_amd import synth
+import plan_batch as pb
+from plan_batch import STAT_NAMES as FIELDS
 
 pytestmark = pytest.mark.gpu
-LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "trajectory_planner_amd", "lib", "libtrajectory_planner_vigo.so")
 POSES = [6, 10, 18, 28, 38, 44]
 ASTAR, GUIDES1, GUIDES2, PROLOGUE, REGUIDE1, REGUIDE2, MIXED, EPILOGUE = 1, 2, 4, 8, 16, 32, 64, 128
 ALL = ASTAR | GUIDES1 | REGUIDE1 | MIXED | EPILOGUE
 MASKS = [ASTAR, GUIDES1, GUIDES2, PROLOGUE, REGUIDE1, REGUIDE2, MIXED, EPILOGUE, ALL]
-# BatchStats' count fields in vigo_host_plan_batch_options' order
-FIELDS = ["astarDecided", "astarHost", "guidesDecided", "guidesHost", "prologueDecided", "prologueHost", "reguideDecided", "reguideHost",
-          "epilogueDecided", "epilogueHost", "seedDecided", "seedHost", "epilogueGroups", "solveBatches", "solvePlanners"]
 # the stage a mask bit selects -> its (decided, host-run) counts
 STAGE = {ASTAR: ("astarDecided", "astarHost"), GUIDES1: ("guidesDecided", "guidesHost"), GUIDES2: ("guidesDecided", "guidesHost"),
          PROLOGUE: ("prologueDecided", "prologueHost"), REGUIDE1: ("reguideDecided", "reguideHost"), REGUIDE2: ("reguideDecided", "reguideHost"),
@@ -46,33 +40,14 @@ def bits(a):
 
 
 def plan(world, off, xyz, mask, via_setters=0, second_mask=-1, budget=16384):
-    """vigo_host_plan_batch_options -> dict of arrays [2, ...] (slot 1: the second thread's call), stats / totals as dicts"""
-    lib = C.CDLL(LIB)
-    n = len(off) - 1
-    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG, dtype=np.float64)
-    off, xyz = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(xyz, dtype=np.float64)
-    ncp_cap, room, pose_cap = 96, 256 * n, 256
-    ok, solver, ncp, ns, ng, npo = (np.zeros((2, n), dtype=np.int32) for _ in range(6))
-    ctrl, segs, guides = np.zeros((2, n, ncp_cap, 3)), np.zeros((2, room, 2), dtype=np.int32), np.zeros((2, room, 6))
-    pos, quat = np.zeros((2, n, pose_cap, 3)), np.zeros((2, n, pose_cap, 4))
-    stats, seconds, totals, ms = np.zeros((2, len(FIELDS)), dtype=np.int64), np.zeros((2, 2)), np.zeros(len(FIELDS), dtype=np.int64), np.zeros(2)
-    lib.vigo_host_plan_batch_options.restype = C.c_int
-    lib.vigo_host_plan_batch_options.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_longlong, C.c_int, ip, ip, ip, dp, ip, ip, ip, dp, ip, dp, dp, lp, dp, lp, dp]
-    r = lib.vigo_host_plan_batch_options(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), float(world.res), n,
-                                         off.ctypes.data_as(ip), xyz.ctypes.data_as(dp), cfg.ctypes.data_as(dp), mask, budget, int(via_setters),
-                                         second_mask, ncp_cap, room, pose_cap, ok.ctypes.data_as(ip), solver.ctypes.data_as(ip),
-                                         ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp), ns.ctypes.data_as(ip), segs.ctypes.data_as(ip),
-                                         ng.ctypes.data_as(ip), guides.ctypes.data_as(dp), npo.ctypes.data_as(ip), pos.ctypes.data_as(dp),
-                                         quat.ctypes.data_as(dp), stats.ctypes.data_as(lp), seconds.ctypes.data_as(dp), totals.ctypes.data_as(lp),
-                                         ms.ctypes.data_as(dp))
-    assert r == 0, r
-    lib.vigo_host_switches.restype = C.c_int
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_seg=ns, segs=segs, n_guides=ng, guides=guides, n_poses=npo, pos=pos, quat=quat,
-                stats=[dict(zip(FIELDS, (int(x) for x in s))) for s in stats], totals=dict(zip(FIELDS, (int(x) for x in totals))),
-                seconds=seconds, total_ms=ms, switches=int(lib.vigo_host_switches()))
+    """one makePlanBatch(planners, trajectories, yaw = true) under `mask` by the route via_setters (plan_batch's routes), or,
+    second_mask >= 0, two at the same time -> dict of arrays [2, ...] (slot 1: the second thread's call), stats / totals as dicts"""
+    both = second_mask >= 0
+    r = pb.plan_batch(world, off, xyz, [(mask, budget, via_setters), (max(second_mask, 0), budget, pb.BY_CALL)], [0, 1] if both else [0], concurrent=both,
+                      outputs=("ok", "solver", "ncp", "ctrl", "segs", "guides", "poses"), with_paths=True, pose_cap=256)
+    return dict(stats=[dict(zip(FIELDS, (int(x) for x in s))) for s in r["stats"]], totals=dict(zip(FIELDS, (int(x) for x in r["totals"]))),
+                seconds=r["slot_seconds"][:, 0, :2], total_ms=r["slot_seconds"][:, 0, 2] * 1e3, switches=r["switches"],
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_seg", "segs", "n_guides", "guides", "n_poses", "pos", "quat")})
 
 
 def same_plans(a, sa, b, sb, label):

@@ -1,5 +1,5 @@
 """-m gpu: bsplineTraj::makePlanBatch(planners, trajectories, yaw) under setDeviceEpilogue through
-vigo_host_plan_batch_finish, on the 48-planner, ten-count workload of tests/test_gpu_mixed_facade.py.  With the switch on,
+vigo_host_plan_batch, on the 48-planner, ten-count workload of tests/test_gpu_mixed_facade.py.  With the switch on,
 steps 5-6 and the sampled paths of every planner that planned come from ONE vigo_traj_finish call for all ten counts;
 each planner must end with what the host epilogue and evalTrajToMsg give it — ok flag, linearFactor_, pose count,
 positions and quaternions bit for bit.  One planner has no device, one has a sample step so small that its path

@@ -2,14 +2,16 @@
 compiled for the host (vigo_host_guide_core, mode 1) — bit for bit: offsets, pairs (compared as uint64: the NaNs of a zero
 diff must match too), the unknown flags against vigo_guides_unknown, statuses, on every workload of tests/guide_cases.py;
 a trajectory's pairs must not depend on its batch.  Then the entry's error contract, and bsplineTraj::makePlanBatch under
-setDeviceGuides(0 | 1 | 2) through vigo_host_plan_batch_guides, with the prologue timings."""
+setDeviceGuides(0 | 1 | 2) through vigo_host_plan_batch, with the prologue timings."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import guide_cases as gc
+import plan_batch as pb
 from gpu_util import to_dev
 from trajectory_planner_amd import _lib, synth
 from trajectory_planner_amd.vigo import GUIDE_DEFERRED, GUIDE_OK
@@ -137,26 +139,14 @@ def test_error_contract_writes_nothing(vigo_handle):
 
 # ---- the facade ----------------------------------------------------------------------------------------------------
 def _plan(P, astar, reps):
+    """slot 0: the untouched default, once, first; then `reps` rounds over slots 1, 2, 3: deviceGuides 0, 1, 2"""
     from test_gpu_astar import _facade_paths, _facade_world
-    lib = gc.host_lib()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     vox, origin = _facade_world()
-    pts = np.ascontiguousarray(_facade_paths(P))
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG, dtype=np.float64)
-    ncp_cap, cap = 64, 64 * P
-    ok, solver, ncp, ng = (np.zeros((4, P), dtype=np.int32) for _ in range(4))
-    ctrl, guides = np.zeros((4, P, ncp_cap, 3)), np.zeros((4, cap, 6))
-    pro, tot, counts = np.zeros((4, reps)), np.zeros((4, reps)), np.zeros((4, 2), dtype=np.int64)
-    lib.vigo_host_plan_batch_guides.restype = C.c_int
-    lib.vigo_host_plan_batch_guides.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_longlong, ip, ip, ip,
-                                                dp, ip, dp, dp, dp, C.POINTER(C.c_longlong)]
-    rc = lib.vigo_host_plan_batch_guides(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), 0.1, P, pts.shape[1],
-                                         pts.ctypes.data_as(dp), cfg.ctypes.data_as(dp), astar, reps, ncp_cap, cap, ok.ctypes.data_as(ip),
-                                         solver.ctypes.data_as(ip), ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp), ng.ctypes.data_as(ip),
-                                         guides.ctypes.data_as(dp), pro.ctypes.data_as(dp), tot.ctypes.data_as(dp),
-                                         counts.ctypes.data_as(C.POINTER(C.c_longlong)))
-    assert rc == 0
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_guides=ng, guides=guides, prologue_ms=pro, total_ms=tot, counts=counts)
+    slots = [(0, 16384, pb.UNTOUCHED)] + [((pb.ASTAR if astar else 0) | guides << 1, 16384, pb.BY_CALL) for guides in (0, 1, 2)]
+    r = pb.plan_batch(SimpleNamespace(voxels=vox, origin=origin, res=0.1), *pb.uniform_paths(_facade_paths(P)), slots, [0] + [1, 2, 3] * reps,
+                      outputs=("ok", "solver", "ncp", "ctrl", "guides"), ncp_cap=64, room=64 * P)
+    return dict(prologue_ms=r["slot_seconds"][:, :, 0] * 1e3, total_ms=r["slot_seconds"][:, :, 2] * 1e3, counts=pb.stat(r, "guidesDecided", "guidesHost"),
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_guides", "guides")})
 
 
 def test_make_plan_batch_under_the_three_settings():

@@ -1,4 +1,4 @@
-"""-m gpu: bsplineTraj::makePlanBatch under setMixedBatches through vigo_host_plan_batch_mixed: 48 planners of the small
+"""-m gpu: bsplineTraj::makePlanBatch under setMixedBatches through vigo_host_plan_batch: 48 planners of the small
 world whose paths give many different control-point counts.  With the switch on, the solves and the device-resident rebound
 rounds take planners of different counts in one device batch (vigo_optimize_mixed / vigo_rebound_rounds_mixed); every
 planner must end with the plan it gets with the switch off — ok flag, solver status, control points bit for bit,

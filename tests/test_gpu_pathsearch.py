@@ -3,7 +3,7 @@ csrc/vigo_pathsearch_core.hpp around the device's search core under the shipped 
 — bit for bit on every workload of tests/pathsearch_cases.py: statuses, seg_off, seg, path_off, path (as uint64),
 counts; a trajectory alone equals itself inside the batch.  The outputs chain into vigo_guide_assign as device tensors.
 Then the error contract, and bsplineTraj::makePlanBatch under setDevicePrologue(true) against the parent's behaviour
-(setDeviceGuides(1), host A*) through vigo_host_plan_batch_prologue, with the prologue timings printed: the ok flags,
+(setDeviceGuides(1), host A*) through vigo_host_plan_batch, with the prologue timings printed: the ok flags,
 collision segments, A* paths, control points, guides and solver statuses are compared on every planner."""
 import ctypes as C
 
@@ -13,6 +13,7 @@ import torch
 
 import guide_cases as gc
 import pathsearch_cases as pc
+import plan_batch as pb
 from gpu_util import to_dev
 from trajectory_planner_amd import _lib, synth
 from trajectory_planner_amd.vigo import GUIDE_OK, PATHS_DEFERRED, PATHS_FAILED, PATHS_OK
@@ -196,27 +197,15 @@ def _pipeline_paths(P, N=32, seed=11):
 
 
 def _plan(P, slots, budget=16384, reps=1):
-    lib = pc.host_lib()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    """`reps` rounds over the slots of `slots` (bit k: slot k runs): 0 deviceGuides = 1 (the reference point of slot 1), 1
+    devicePrologue, 2 deviceAstar + deviceGuides = 1 (the device pieces without the chain), 3 the host prologue"""
     world, pts = _pipeline_paths(P)
-    vox, origin = np.ascontiguousarray(world.voxels), np.ascontiguousarray(world.origin, dtype=np.float64)
-    cfg = np.ascontiguousarray(synth.PIPELINE_CFG, dtype=np.float64)
-    ncp_cap, cap = 64, 256 * P
-    ok, solver, ncp, ns, npp, ng = (np.zeros((4, P), dtype=np.int32) for _ in range(6))
-    ctrl, segs, paths, guides = np.zeros((4, P, ncp_cap, 3)), np.zeros((4, cap, 2), dtype=np.int32), np.zeros((4, cap, 3)), np.zeros((4, cap, 6))
-    pro, chain, tot, counts = np.zeros((4, reps)), np.zeros((4, reps)), np.zeros((4, reps)), np.zeros((4, 2), dtype=np.int64)
-    lib.vigo_host_plan_batch_prologue.restype = C.c_int
-    lib.vigo_host_plan_batch_prologue.argtypes = [C.c_void_p, ip, dp, C.c_double, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
-                                                  ip, ip, ip, dp, ip, ip, ip, dp, ip, dp, dp, dp, dp, C.POINTER(C.c_longlong)]
-    rc = lib.vigo_host_plan_batch_prologue(vox.ctypes.data_as(C.c_void_p), (C.c_int * 3)(*vox.shape), origin.ctypes.data_as(dp), float(world.res), P,
-                                           pts.shape[1], pts.ctypes.data_as(dp), cfg.ctypes.data_as(dp), slots, budget, reps, ncp_cap, cap,
-                                           ok.ctypes.data_as(ip), solver.ctypes.data_as(ip), ncp.ctypes.data_as(ip), ctrl.ctypes.data_as(dp),
-                                           ns.ctypes.data_as(ip), segs.ctypes.data_as(ip), npp.ctypes.data_as(ip), paths.ctypes.data_as(dp),
-                                           ng.ctypes.data_as(ip), guides.ctypes.data_as(dp), pro.ctypes.data_as(dp), chain.ctypes.data_as(dp),
-                                           tot.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_longlong)))
-    assert rc == 0
-    return dict(ok=ok, solver=solver, ncp=ncp, ctrl=ctrl, n_seg=ns, segs=segs, n_path_pts=npp, paths=paths, n_guides=ng, guides=guides,
-                prologue_ms=pro, chain_ms=chain, total_ms=tot, counts=counts)
+    masks = (pb.GUIDES1, pb.PROLOGUE, pb.ASTAR | pb.GUIDES1, 0)
+    r = pb.plan_batch(world, *pb.uniform_paths(pts), [(m, budget, pb.BY_CALL) for m in masks], [s for s in range(4) if (slots >> s) & 1] * reps,
+                      outputs=("ok", "solver", "ncp", "ctrl", "segs", "paths", "guides"), ncp_cap=64)
+    ms = r["slot_seconds"] * 1e3
+    return dict(prologue_ms=ms[:, :, 0], chain_ms=ms[:, :, 1], total_ms=ms[:, :, 2], counts=pb.stat(r, "prologueDecided", "prologueHost"),
+                **{k: r[k] for k in ("ok", "solver", "ncp", "ctrl", "n_seg", "segs", "n_path_pts", "paths", "n_guides", "guides")})
 
 
 def _same_plans(r, label, device_share):

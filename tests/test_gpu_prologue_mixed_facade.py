@@ -1,4 +1,4 @@
-"""-m gpu: bsplineTraj::makePlanBatch under BatchOptions::mixedPrologue through vigo_host_plan_batch_mixed_prologue: the 48
+"""-m gpu: bsplineTraj::makePlanBatch under BatchOptions::mixedPrologue through vigo_host_plan_batch: the 48
 planners and ten control-point counts of tests/test_gpu_mixed_facade.py.  With the option on, the devicePrologue chain,
 the deviceGuides = 1 and deviceAstar launches and the deviceReguide = 1 call group their planners as the mixed solves do and
 call the _mixed entries; every planner must end with the plan it gets with the option off — ok flag, solver status,

@@ -1,4 +1,4 @@
-"""-m gpu: bsplineTraj::makePlanBatch under setDeviceReguide through vigo_host_plan_batch_reguide, 256 planners of the
+"""-m gpu: bsplineTraj::makePlanBatch under setDeviceReguide through vigo_host_plan_batch, 256 planners of the
 pipeline world.  Setting 1 (vigo_rebound_reguide per device group, what it defers by the workers' twin) against setting 2
 (every re-guide step by the workers' twin): ok flags, solver statuses, control points, collisionSeg_, astarPaths_ and
 guides of every planner bit for bit; the step counts; the device-decided steps equal to what the kernels' host twin

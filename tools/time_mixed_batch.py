@@ -3,7 +3,7 @@
             world and trajectories), B = 1024 and 16 384: the price of the general-only plan — one launch of the general
             kernel where the uniform entry picks the level / no-obstacle kernels.  Host clock around call + synchronise,
             the two entries alternating in one process, medians of --reps after --warmup.
-  plan_*    bsplineTraj::makePlanBatch through vigo_host_plan_batch_mixed on --planners planners whose control-point
+  plan_*    bsplineTraj::makePlanBatch through vigo_host_plan_batch on --planners planners whose control-point
             counts are spread over 8 .. 40 (most of them short, as the seed stage leaves them), setMixedBatches off
             against on, alternating, fresh planners every run; device batches opened per run under either setting.
 Prints one JSON line; --out appends it to a file.  Run on the GPU box."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """makePlanBatch with BatchOptions::mixedPrologue off against on: P planners over the ten control-point counts of
 tests/test_gpu_mixed_facade.py under devicePrologue + deviceReguide = 1 + mixedBatches, both settings in ONE process,
-interleaved run by run on fresh planners (vigo_host_plan_batch_mixed_prologue), the first `--warmup` rounds discarded.
+interleaved run by run on fresh planners (vigo_host_plan_batch), the first `--warmup` rounds discarded.
 "off" is the behaviour before the option existed: the baseline.  Prints the median and the spread (min .. max) of
 prologueSeconds, chainSeconds and the call's wall time per setting, the group counts, and one JSON line.
 

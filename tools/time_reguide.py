@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Wall time of bsplineTraj::makePlanBatch on the 1024-planner pipeline workload with the rebound loop's re-guide step on
 the host (setDeviceReguide(0)), on the device (1) and on the workers' twin (2): `reps` alternating rounds through
-vigo_host_plan_batch_reguide, the first one a warm-up, the median of the rest.  Prints the device / worker step totals.
+vigo_host_plan_batch, the first one a warm-up, the median of the rest.  Prints the device / worker step totals.
 Needs a GPU.  (profiles/README.md, "Device re-guide", holds a run of this.)"""
 import argparse
 import os

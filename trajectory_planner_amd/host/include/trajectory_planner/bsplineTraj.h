@@ -105,7 +105,7 @@ public:
     bool makePlan();
     bool makePlan(nav_msgs::Path& trajectory, bool yaw = true);
 
-    /* added (tests, cabi_host.cpp: vigo_host_plan_batch_reguide): the inputs of one re-guide step the workers' twin runs
+    /* added (tests, cabiPlanBatch.cpp: vigo_host_plan_batch): the inputs of one re-guide step the workers' twin runs
      * (BatchOptions::reguideStepLog), so the same steps can be put to the kernels' host twin afterwards */
     struct ReguideStepRecord {
         int N;

@@ -16,7 +16,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <future>
 #include <mutex>
 
 #include "../../../include/vigo.h"
@@ -25,40 +24,11 @@
 #include "../../csrc/vigo_pathsearch_core.hpp"
 #include "../../csrc/vigo_reguide_core.hpp"
 #include "batchLayout.h"
+#include "cabiPlanBatch.h"
 #include "workerPool.h"
 
 namespace {
-
-// a dense map of nx * ny * nz voxel bytes (vigo.h voxel contract)
-std::shared_ptr<mapManager::occMap> denseMap(int nx, int ny, int nz, const double* origin, double res, const unsigned char* voxels) {
-    auto map = std::make_shared<mapManager::occMap>(nx, ny, nz, Eigen::Vector3d(origin[0], origin[1], origin[2]), res);
-    std::memcpy(map->voxels().data(), voxels, (size_t)nx * ny * nz);
-    return map;
-}
-
-// cfg[6] of the entry points below: distance_threshold, min_height, max_height, max_obstacle_size[3]
-void setBsplineParams(ros::NodeHandle& nh, const double* cfg) {
-    nh.setParam("bspline_traj/distance_threshold", cfg[0]);
-    nh.setParam("bspline_traj/min_height", cfg[1]);
-    nh.setParam("bspline_traj/max_height", cfg[2]);
-    nh.setParam("bspline_traj/max_obstacle_size", std::vector<double>{cfg[3], cfg[4], cfg[5]});
-}
-
-// the A* node pool of a planner with these parameters on a map of resolution res (bsplineTraj::setMap, BT.cpp:187-195)
-void nodePool(const double* cfg, double res, int pool[3]) {
-    for (int a = 0; a < 3; ++a) pool[a] = 2 * int(cfg[3 + a] / res);
-}
-
-// n_pts poses at the xyz triples q
-nav_msgs::Path pathFromXyz(const double* q, int n_pts) {
-    nav_msgs::Path path;
-    for (int i = 0; i < n_pts; ++i) {
-        geometry_msgs::PoseStamped ps;
-        ps.pose.position.x = q[3 * i]; ps.pose.position.y = q[3 * i + 1]; ps.pose.position.z = q[3 * i + 2];
-        path.poses.push_back(ps);
-    }
-    return path;
-}
+using namespace cabi;
 
 // cfg as vigo_host_poly_plan documents it; `mode`, the differential and the continuity degree are the caller's
 std::unique_ptr<trajPlanner::polyTrajOctomap> makePolyPlanner(const std::shared_ptr<mapManager::occMap>& map, const double* cfg,
@@ -1082,169 +1052,6 @@ int vigo_host_bspline_guides_batch(const unsigned char* vox, const int* dims, co
 
 }  // extern "C"
 
-// ---- one driver behind the vigo_host_plan_batch_* entry points: what they plan on, fresh planners per run, one timed
-// makePlanBatch, the results of a slot's last run.  What is left in each entry point is its slot schedule, the
-// BatchOptions of a slot, and the fields of the call's BatchStats it reports.
-namespace {
-using trajPlanner::bsplineTraj;
-
-// built once per call: n_maps dense maps, a separate map object each (separate device groups): copies of vox, the odd
-// ones of vox2 when that is given; the planners' parameters (cfg as in vigo_host_bspline_prologue); the n input paths of
-// n_pts poses; zero start / end conditions
-struct BatchFixture {
-    std::vector<std::shared_ptr<mapManager::occMap>> maps;
-    ros::NodeHandle nh;
-    std::vector<nav_msgs::Path> in;
-    std::vector<std::vector<Eigen::Vector3d>> cond;
-    BatchFixture(const unsigned char* vox, const unsigned char* vox2, int n_maps, const int* dims, const double* origin, double res, const double* cfg,
-                 int n, int n_pts, const double* path_xyz)
-        : cond(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0))) {
-        for (int k = 0; k < n_maps; ++k) maps.push_back(denseMap(dims[0], dims[1], dims[2], origin, res, (vox2 && (k & 1)) ? vox2 : vox));
-        setBsplineParams(nh, cfg);
-        nh.setParam("bspline_traj/max_path_length", 1000.0);
-        nh.setParam("bspline_traj/plan_in_z_axis", 0.0);
-        for (int t = 0; t < n; ++t) in.push_back(pathFromXyz(path_xyz + (size_t)t * n_pts * 3, n_pts));
-    }
-    // ... the same with a pose list per planner: path t = poses path_off[t] .. path_off[t + 1] - 1 of path_xyz
-    BatchFixture(const unsigned char* vox, const int* dims, const double* origin, double res, const double* cfg, int n, const int* path_off,
-                 const double* path_xyz)
-        : BatchFixture(vox, nullptr, 1, dims, origin, res, cfg, 0, 0, path_xyz) {
-        cond.assign(n, std::vector<Eigen::Vector3d>(4, Eigen::Vector3d(0, 0, 0)));
-        for (int t = 0; t < n; ++t) in.push_back(pathFromXyz(path_xyz + (size_t)path_off[t] * 3, path_off[t + 1] - path_off[t]));
-    }
-};
-
-// new planners for one run, planner t on map t % n_maps, through updatePathBatch
-struct FreshPlanners {
-    std::vector<std::unique_ptr<bsplineTraj>> owners;
-    std::vector<bsplineTraj*> ps;
-};
-FreshPlanners freshPlanners(const BatchFixture& fx) {
-    FreshPlanners fp;
-    for (size_t t = 0; t < fx.in.size(); ++t) {
-        fp.owners.emplace_back(new bsplineTraj(fx.nh));
-        fp.owners.back()->setMap(fx.maps[t % fx.maps.size()]);
-        fp.owners.back()->updateMaxVel(2.0);
-        fp.owners.back()->updateMaxAcc(3.0);
-        fp.ps.push_back(fp.owners.back().get());
-    }
-    bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
-    return fp;
-}
-
-// makePlanBatch's flags, its wall time in ms: the overload without options (the process default), for the slots that
-// leave the default untouched and read the process totals around the call ...
-std::vector<bool> timedPlan(const std::vector<bsplineTraj*>& ps, double& ms) {
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<bool> planned = bsplineTraj::makePlanBatch(ps);
-    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return planned;
-}
-// ... and a call under its own options, what its stages did in st; traj: the overload with trajectories
-std::vector<bool> timedPlan(const std::vector<bsplineTraj*>& ps, const bsplineTraj::BatchOptions& o, double& ms, bsplineTraj::BatchStats& st,
-                            std::vector<nav_msgs::Path>* traj = nullptr, bool yaw = true) {
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<bool> planned = traj ? bsplineTraj::makePlanBatch(ps, *traj, yaw, o, &st) : bsplineTraj::makePlanBatch(ps, o, &st);
-    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return planned;
-}
-
-// The n planners' results as slot `slot` of the entry points' outputs: ok[n] makePlanBatch's flags, solver[n] the last
-// L-BFGS status, ncp[n], ctrl[n][ncp_cap][3] (zero padded by the caller), and each where its pointer is not NULL, per slot
-// concatenated in planner order: n_guides[n] + guides[cap][6] (point, direction), n_seg[n] + segs[cap][2]
-// (collisionSeg_), n_path_pts[n] + paths[cap][3] (astarPaths_' points).  Returns 0, -2 when ncp_cap or cap is too small.
-int dumpSlot(const std::vector<bsplineTraj*>& ps, const std::vector<bool>& planned, int slot, int ncp_cap, long long cap, int* ok, int* solver,
-             int* ncp, double* ctrl, int* n_guides, double* guides, int* n_seg, int* segs, int* n_path_pts, double* paths) {
-    const size_t n = ps.size();
-    long long g = 0, w = 0, sg = 0;
-    for (size_t t = 0; t < n; ++t) {
-        const size_t o = (size_t)slot * n + t;
-        const Eigen::MatrixXd c = ps[t]->getControlPoints();
-        ok[o] = planned[t] ? 1 : 0;
-        solver[o] = ps[t]->getLastSolverStatus();
-        ncp[o] = (int)c.cols();
-        if (c.cols() > ncp_cap) return -2;
-        for (int i = 0; i < (int)c.cols(); ++i) for (int k = 0; k < 3; ++k) ctrl[(o * ncp_cap + i) * 3 + k] = c(k, i);
-        if (guides) {
-            std::vector<int32_t> off{0};
-            std::vector<double> pv;
-            vigo_host::appendGuides(ps[t]->getOptData(), (int)c.cols(), off, pv);
-            n_guides[o] = (int)(pv.size() / 6);
-            if (g + (long long)pv.size() / 6 > cap) return -2;
-            std::memcpy(guides + ((size_t)slot * cap + g) * 6, pv.data(), pv.size() * sizeof(double));
-            g += (long long)pv.size() / 6;
-        }
-        if (segs) {
-            const auto& cs = ps[t]->getCollisionSeg();
-            n_seg[o] = (int)cs.size();
-            if (sg + (long long)cs.size() > cap) return -2;
-            for (const auto& s : cs) { segs[((size_t)slot * cap + sg) * 2] = s.first; segs[((size_t)slot * cap + sg) * 2 + 1] = s.second; ++sg; }
-        }
-        if (paths) {
-            int pts = 0;
-            for (const auto& path : ps[t]->getAstarPaths())
-                for (const auto& v : path) {
-                    if (w + 1 > cap) return -2;
-                    for (int k = 0; k < 3; ++k) paths[((size_t)slot * cap + w) * 3 + k] = v(k);
-                    ++w; ++pts;
-                }
-            n_path_pts[o] = pts;
-        }
-    }
-    return 0;
-}
-
-// ... and the n trajectories of the overload with trajectories: n_poses[n], pos[n][pose_cap][3], quat[n][pose_cap][4]
-// (x, y, z, w; zero padded by the caller).  Returns 0, -2 when pose_cap is too small.
-int dumpPoses(const std::vector<nav_msgs::Path>& traj, size_t n, int slot, int pose_cap, int* n_poses, double* pos, double* quat) {
-    for (size_t t = 0; t < n; ++t) {
-        const size_t o = (size_t)slot * n + t;
-        n_poses[o] = t < traj.size() ? (int)traj[t].poses.size() : 0;
-        if (n_poses[o] > pose_cap) return -2;
-        for (int i = 0; i < n_poses[o]; ++i) {
-            const auto& ps = traj[t].poses[i].pose;
-            double* p = pos + (o * pose_cap + i) * 3;
-            double* q = quat + (o * pose_cap + i) * 4;
-            p[0] = ps.position.x; p[1] = ps.position.y; p[2] = ps.position.z;
-            q[0] = ps.orientation.x; q[1] = ps.orientation.y; q[2] = ps.orientation.z; q[3] = ps.orientation.w;
-        }
-    }
-    return 0;
-}
-}  // namespace
-
-// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch, `reps` times with the prologue's A* on the
-// host (mode 0) and `reps` times with deviceAstar on (mode 1), alternating, fresh planners every time.  n_maps > 1:
-// planner t plans on map t % n_maps, a separate map object each (separate device groups): copies of vox, the odd ones
-// of vox2 when that is given (same extents, other contents).  budget: the device
-// searches' max_expansions (deviceAstarBudget).  cfg as in vigo_host_bspline_prologue.  Outputs of each mode's LAST run,
-// [2] x ...: ok[n] makePlanBatch's flags, solver[n] the last L-BFGS status, ncp[n], ctrl[n][ncp_cap][3] (zero padded),
-// n_guides[n] + guides[cap][6] (point, direction; concatenated in planner order), n_path_pts[n] + paths[cap][3] (the A*
-// paths' points, concatenated), per run prologue_ms[2][reps] (summed over the parts of a call that makePlanBatch splits)
-// and total_ms[2][reps], and counts[2]: the searches of the LAST mode-1 run the device decided / the host ran.  Returns 0, -2 when a buffer is
-// too small, -1 on a bad argument.  Needs a GPU.
-extern "C" int vigo_host_plan_batch_astar(const unsigned char* vox, const unsigned char* vox2, const int* dims, const double* origin, double res, int n, int n_pts,
-                                          const double* path_xyz, const double* cfg, int n_maps, int budget, int reps, int ncp_cap, long long cap,
-                                          int* ok, int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, int* n_path_pts,
-                                          double* paths, double* prologue_ms, double* total_ms, long long* counts) {
-    if (n < 1 || n_pts < 2 || n_maps < 1 || reps < 1 || !path_xyz) return -1;
-    const BatchFixture fx(vox, vox2, n_maps, dims, origin, res, cfg, n, n_pts, path_xyz);
-    int rc = 0;
-    bsplineTraj::BatchOptions o;
-    o.deviceAstarBudget = budget;
-    for (int run = 0; run < 2 * reps && rc == 0; ++run) {
-        const int mode = run & 1, rep = run / 2;
-        const FreshPlanners fp = freshPlanners(fx);
-        o.deviceAstar = mode == 1;
-        bsplineTraj::BatchStats st;
-        const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[mode * reps + rep], st);
-        prologue_ms[mode * reps + rep] = st.prologueSeconds * 1e3;
-        if (mode == 1) { counts[0] = st.astarDecided; counts[1] = st.astarHost; }
-        if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, mode, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, n_path_pts, paths);
-    }
-    return rc;
-}
-
 // ---- guide assignment: the device's core on the host, the facade's own step, and the workloads of their tests ----------
 namespace {
 struct NudgedAtan2 {     // std::atan2 moved by `ulps` representable values (test-only neighbours of libm's result)
@@ -1776,245 +1583,6 @@ int vigo_host_reguide_facade(const unsigned char* vox, const int* dims, const do
 
 extern "C" {
 
-// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
-// every run: first ONE run through the overload without options (slot 0: the untouched process default), then `reps`
-// rounds of deviceGuides = 0, 1, 2 in turn (slots 1, 2, 3), each with deviceAstar = (astar != 0).  Outputs per slot [4] x ...
-// of the slot's LAST run: ok[n], solver[n], ncp[n], ctrl[n][ncp_cap][3] (zero padded), n_guides[n] + guides[cap][6]
-// (point, direction; concatenated in planner order); per run prologue_ms[4][reps] and total_ms[4][reps] (slot 0: entry 0
-// only); counts[4][2]: the trajectories of the slot's last run whose guides the device produced / the workers' twin
-// produced.  cfg as in vigo_host_bspline_prologue.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
-int vigo_host_plan_batch_guides(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
-                                const double* path_xyz, const double* cfg, int astar, int reps, int ncp_cap, long long cap, int* ok,
-                                int* solver, int* ncp, double* ctrl, int* n_guides, double* guides, double* prologue_ms, double* total_ms,
-                                long long* counts) {
-    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg) return -1;
-    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
-    int rc = 0;
-    for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
-        const int slot = run == 0 ? 0 : 1 + (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
-        const FreshPlanners fp = freshPlanners(fx);
-        std::vector<bool> planned;
-        bsplineTraj::BatchStats st;
-        if (run == 0) {
-            long long dev0, host0;
-            double pro0;
-            bsplineTraj::deviceGuideTotals(&dev0, &host0);
-            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &pro0);
-            planned = timedPlan(fp.ps, total_ms[0]);
-            bsplineTraj::deviceAstarTotals(nullptr, nullptr, &st.prologueSeconds);
-            bsplineTraj::deviceGuideTotals(&st.guidesDecided, &st.guidesHost);
-            st.prologueSeconds -= pro0; st.guidesDecided -= dev0; st.guidesHost -= host0;
-        } else {
-            bsplineTraj::BatchOptions o;
-            o.deviceAstar = astar != 0;
-            o.deviceGuides = slot - 1;
-            planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
-        }
-        prologue_ms[slot * reps + rep] = st.prologueSeconds * 1e3;
-        counts[2 * slot] = st.guidesDecided;
-        counts[2 * slot + 1] = st.guidesHost;
-        if (run == 0 || rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, nullptr, nullptr, nullptr, nullptr);
-    }
-    return rc;
-}
-
-// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
-// every run, `reps` rounds over the slots of `slots` (bit k: slot k runs) in turn:
-//   slot 0  deviceGuides = 1                       the reference point of slot 1
-//   slot 1  devicePrologue
-//   slot 2  deviceAstar, deviceGuides = 1          the device pieces without the chain
-//   slot 3  default options                        the host prologue
-// budget: deviceAstarBudget.  Outputs per slot [4] x ... of the slot's LAST run: ok[n], solver[n], ncp[n],
-// ctrl[n][ncp_cap][3] (zero padded), n_seg[n] + segs[cap][2] (collisionSeg_, concatenated in planner order),
-// n_path_pts[n] + paths[cap][3] (astarPaths_' points), n_guides[n] + guides[cap][6]; per run prologue_ms[4][reps],
-// chain_ms[4][reps] (the stats' chain time) and total_ms[4][reps]; counts[4][2]: the planners of the slot's
-// last run the device chain decided / that ran the host steps.  Returns 0, -2 when a
-// buffer is too small, -1 on a bad argument.  Needs a GPU.
-int vigo_host_plan_batch_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
-                                  const double* path_xyz, const double* cfg, int slots, int budget, int reps, int ncp_cap, long long cap,
-                                  int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts, double* paths,
-                                  int* n_guides, double* guides, double* prologue_ms, double* chain_ms, double* total_ms, long long* counts) {
-    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || (slots & 15) == 0) return -1;
-    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
-    int rc = 0;
-    for (int rep = 0; rep < reps && rc == 0; ++rep)
-        for (int slot = 0; slot < 4 && rc == 0; ++slot) {
-            if (!((slots >> slot) & 1)) continue;
-            const FreshPlanners fp = freshPlanners(fx);
-            bsplineTraj::BatchOptions o;
-            o.deviceAstarBudget = budget;
-            o.devicePrologue = slot == 1;
-            o.deviceAstar = slot == 2;
-            o.deviceGuides = slot == 0 || slot == 2 ? 1 : 0;
-            bsplineTraj::BatchStats st;
-            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
-            prologue_ms[slot * reps + rep] = st.prologueSeconds * 1e3;
-            chain_ms[slot * reps + rep] = st.chainSeconds * 1e3;
-            counts[2 * slot] = st.prologueDecided;
-            counts[2 * slot + 1] = st.prologueHost;
-            if (rep + 1 == reps) rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
-        }
-    return rc;
-}
-
-// n planners (path t: n_pts poses, xyz) through updatePathBatch + makePlanBatch on one dense byte grid, fresh planners
-// every run: first ONE run through the overload without options (slot 3: the untouched process default), then `reps`
-// rounds over
-//   slot 0  deviceReguide = 2   the reference point of slot 1: every re-guide step by the workers' twin
-//   slot 1  deviceReguide = 1   vigo_rebound_reguide
-//   slot 2  deviceReguide = 0
-// in turn (slots: bit k set = slot k runs; slot 3 always does).  budget: deviceAstarBudget.  Outputs per slot [4] x ...
-// of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl, n_seg + segs, n_path_pts + paths,
-// n_guides + guides; per run total_ms[4][reps] (slot 3: entry 0 only); counts[4][2]: the device-decided
-// and worker-run re-guide steps of the slot's last run.  twin[2]: the steps slot 0's last run logged, and how many of them the
-// kernels' host twin (vigo_host_rebound_reguide_core, mode 1) under the capacities caps[4] = (cap_log2, max_nodes,
-// heap_cap, guide_path_cap) does not answer with VIGO_REGUIDE_DEFERRED — the share the device can decide.  Returns 0, -2 when a buffer is too small, -1 on a bad argument.  Needs a GPU.
-int vigo_host_plan_batch_reguide(const unsigned char* vox, const int* dims, const double* origin, double res, int n, int n_pts,
-                                 const double* path_xyz, const double* cfg, int slots, int budget, int reps, const int* caps, int ncp_cap,
-                                 long long cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_path_pts,
-                                 double* paths, int* n_guides, double* guides, double* total_ms, long long* counts, long long* twin) {
-    if (n < 1 || n_pts < 2 || reps < 1 || !path_xyz || !cfg || !caps || !twin) return -1;
-    const BatchFixture fx(vox, nullptr, 1, dims, origin, res, cfg, n, n_pts, path_xyz);
-    int rc = 0;
-    twin[0] = twin[1] = 0;
-    for (int run = 0; run < 1 + 3 * reps && rc == 0; ++run) {
-        const int slot = run == 0 ? 3 : (run - 1) % 3, rep = run == 0 ? 0 : (run - 1) / 3;
-        if (run > 0 && !((slots >> slot) & 1)) continue;
-        const bool last = run == 0 || rep + 1 == reps;
-        const FreshPlanners fp = freshPlanners(fx);
-        std::vector<bsplineTraj::ReguideStepRecord> log;
-        std::vector<bool> planned;
-        bsplineTraj::BatchStats st;
-        if (run == 0) {
-            long long dev0, host0;
-            bsplineTraj::deviceReguideTotals(&dev0, &host0);
-            planned = timedPlan(fp.ps, total_ms[slot * reps]);
-            bsplineTraj::deviceReguideTotals(&st.reguideDecided, &st.reguideHost);
-            st.reguideDecided -= dev0; st.reguideHost -= host0;
-        } else {
-            bsplineTraj::BatchOptions o;
-            o.deviceAstarBudget = budget;
-            o.deviceReguide = 2 - slot;
-            if (slot == 0 && last) o.reguideStepLog = &log;
-            planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
-        }
-        if (!last) continue;
-        counts[2 * slot] = st.reguideDecided;
-        counts[2 * slot + 1] = st.reguideHost;
-        // the logged steps, one by one (a trajectory's result does not depend on its batch), by the kernels' twin
-        twin[0] += (long long)log.size();
-        int pool[3];
-        nodePool(cfg, res, pool);
-        std::vector<int> deferred(log.size(), 0);
-        vigo_host::parallelFor(log.size(), [&](size_t k) {
-            bsplineTraj::ReguideStepRecord& R = log[k];
-            vigo_rebound_state_t st;
-            std::memset(&st, 0, sizeof(st));
-            st.status = VIGO_RB_NEEDS_HOST;
-            st.gate_static = 1;
-            st.gate_dynamic = R.gateDynamic;
-            st.fail_count = R.failCount;
-            st.n_seg = (int)std::min<size_t>(R.seg.size() / 2, VIGO_MAX_COLLISION_SEGS);
-            std::copy(R.seg.begin(), R.seg.begin() + 2 * st.n_seg, st.seg);
-            if (R.seg.size() / 2 > (size_t)VIGO_MAX_COLLISION_SEGS) { deferred[k] = 1; return; }   // (the facade keeps these off the device)
-            const long long pairCap = (long long)R.gpv.size() / 6 + (long long)R.N * (VIGO_MAX_COLLISION_SEGS + 4);
-            std::vector<int> off((size_t)R.N + 1);
-            std::vector<double> pv((size_t)pairCap * 6 + 6);
-            R.gpv.resize(R.gpv.size() + 6);
-            int status = VIGO_REGUIDE_DEFERRED;
-            const int r = vigo_host_rebound_reguide_core(vox, dims, origin, res, 1, R.N, R.ctrl.data(), R.goff.data(), R.gpv.data(), nullptr, R.weights, 0.0,
-                                                         cfg[0], res, pool, cfg[1], cfg[2], caps[0], caps[1], caps[2], budget, 128, caps[3], 1, &st,
-                                                         pairCap, off.data(), pv.data(), nullptr, 0, 0, nullptr, nullptr, nullptr, &status);
-            deferred[k] = (r != 0 || status == VIGO_REGUIDE_DEFERRED) ? 1 : 0;
-        });
-        for (size_t k = 0; k < log.size(); ++k) twin[1] += deferred[k] ? 0 : 1;
-        rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
-    }
-    return rc;
-}
-
-// n planners with a pose list each (path t: poses path_off[t] .. path_off[t + 1] - 1 of path_xyz, at least 2) through
-// updatePathBatch + makePlanBatch on one dense byte grid, fresh planners every run, `reps` rounds over
-//   slot 0  mixedBatches off   one device batch per control-point count
-//   slot 1  mixedBatches on    counts of one shape class share the batches of the solves and of the device rounds
-// in turn.  Outputs per slot [2] x ... of the slot's LAST run as vigo_host_plan_batch_prologue's: ok, solver, ncp, ctrl
-// (zero padded), n_seg + segs (collisionSeg_), n_guides + guides; per run total_ms[2][reps]; counts[2][2]:
-// the device batches the solves and rounds opened and the planners in them, of the slot's last run.  Returns 0, -2
-// when a buffer is too small, -1 on a bad argument.  Needs a GPU.
-int vigo_host_plan_batch_mixed(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
-                               const double* path_xyz, const double* cfg, int reps, int ncp_cap, long long cap, int* ok, int* solver, int* ncp,
-                               double* ctrl, int* n_seg, int* segs, int* n_guides, double* guides, double* total_ms, long long* counts) {
-    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg) return -1;
-    for (int t = 0; t < n; ++t)
-        if (path_off[t + 1] - path_off[t] < 2) return -1;
-    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
-    int rc = 0;
-    for (int rep = 0; rep < reps && rc == 0; ++rep)
-        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
-            const FreshPlanners fp = freshPlanners(fx);
-            bsplineTraj::BatchOptions o;
-            o.mixedBatches = slot == 1;
-            bsplineTraj::BatchStats st;
-            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st);
-            if (rep + 1 < reps) continue;
-            counts[2 * slot] = st.solveBatches;
-            counts[2 * slot + 1] = st.solvePlanners;
-            rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, nullptr, nullptr);
-        }
-    return rc;
-}
-
-// n planners with a pose list each (as vigo_host_plan_batch_mixed) through updatePathBatch + makePlanBatch on one dense
-// byte grid, fresh planners every run, `reps` rounds over
-//   slot 0  deviceEpilogue off   steps 5-6 and evalTrajToMsg per planner on the host
-//   slot 1  deviceEpilogue on    one vigo_traj_finish per device group
-// in turn.  with_paths != 0: the overload makePlanBatch(planners, trajectories, yaw != 0); 0: makePlanBatch(planners), no
-// poses.  Planner no_device (< 0: none) sits on a device ordinal that does not exist; planner small_step (< 0: none) gets
-// bspline_traj/timestep = step, a group of its own.  Outputs per slot [2] x ... of the slot's LAST run: ok[n],
-// factor[n] (linearFactor_), n_poses[n], pos[n][pose_cap][3] and quat[n][pose_cap][4] (x, y, z, w; zero padded by the
-// caller); totals[2][3]: the epilogue's device-decided planners, host-route planners and device groups of that
-// run; per run total_ms[2][reps].  Returns 0, -2 when pose_cap is too small, -1 on a bad
-// argument.  Needs a GPU.
-int vigo_host_plan_batch_finish(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
-                                const double* path_xyz, const double* cfg, int no_device, int small_step, double step, int with_paths, int yaw,
-                                int reps, int pose_cap, int* ok, double* factor, int* n_poses, double* pos, double* quat, long long* totals,
-                                double* total_ms) {
-    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg || no_device >= n || small_step >= n || (small_step >= 0 && !(step > 0.0))) return -1;
-    for (int t = 0; t < n; ++t)
-        if (path_off[t + 1] - path_off[t] < 2) return -1;
-    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
-    ros::NodeHandle nhStep;                    // (a copy of a NodeHandle shares its parameters: copy the map itself)
-    *nhStep.params = *fx.nh.params;
-    if (small_step >= 0) nhStep.setParam("bspline_traj/timestep", step);
-    int rc = 0;
-    for (int rep = 0; rep < reps && rc == 0; ++rep)
-        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
-            FreshPlanners fp;
-            for (int t = 0; t < n; ++t) {
-                fp.owners.emplace_back(new bsplineTraj(t == small_step ? nhStep : fx.nh));
-                if (t == no_device) fp.owners.back()->setDevice(63);
-                fp.owners.back()->setMap(fx.maps[0]);
-                fp.owners.back()->updateMaxVel(2.0);
-                fp.owners.back()->updateMaxAcc(3.0);
-                fp.ps.push_back(fp.owners.back().get());
-            }
-            bsplineTraj::updatePathBatch(fp.ps, fx.in, fx.cond);
-            bsplineTraj::BatchOptions o;
-            o.deviceEpilogue = slot == 1;
-            bsplineTraj::BatchStats st;
-            std::vector<nav_msgs::Path> traj;
-            const std::vector<bool> planned = timedPlan(fp.ps, o, total_ms[slot * reps + rep], st, with_paths ? &traj : nullptr, yaw != 0);
-            if (rep + 1 < reps) continue;
-            totals[3 * slot] = st.epilogueDecided; totals[3 * slot + 1] = st.epilogueHost; totals[3 * slot + 2] = st.epilogueGroups;
-            for (int t = 0; t < n; ++t) {
-                ok[(size_t)slot * n + t] = planned[t] ? 1 : 0;
-                factor[(size_t)slot * n + t] = fp.ps[t]->getLinearFactor();
-            }
-            rc = dumpPoses(traj, (size_t)n, slot, pose_cap, n_poses, pos, quat);     // (without paths: traj is empty)
-        }
-    return rc;
-}
-
 // The epilogue stage alone (bsplineTraj::finishBatch: steps 5-6 and evalTrajToMsg) for n planners on one dense byte grid
 // with the control points ctrl[n][Ns][3], n_pts[n] of them each: `reps` rounds, deviceEpilogue off then on in each,
 // wall time in ms[reps][2].  *mismatch: planners whose linearFactor_, pose count, positions or quaternions of the last
@@ -2062,180 +1630,6 @@ int vigo_host_finish_timing(const unsigned char* vox, const int* dims, const dou
         *mismatch += same ? 0 : 1;
     }
     return 0;
-}
-
-// One makePlanBatch(planners, trajectories, yaw = true) of n planners with a pose list each (as
-// vigo_host_plan_batch_mixed) under the options `mask` names in vigo_host_switches' bit layout, with deviceAstarBudget
-// = budget, by one of two routes:
-//   via_setters == 0  the options are passed to the call; the process default is not touched
-//   via_setters == 1  the options are set as the process default through the setters, the overload without options is
-//                     called, and the setters put the default back
-//   via_setters == 2  (mask must be 0) the overload without options and no setter called: the untouched default
-// Outputs, slot 0: dumpSlot's ok, solver, ncp, ctrl (zero padded), n_seg + segs, n_guides + guides, dumpPoses' n_poses,
-// pos, quat; stats[15]: the count fields of the call's BatchStats in the order of their declaration (the second route has
-// no BatchStats of the call: there, the process totals' difference); seconds[2]: prologueSeconds, chainSeconds likewise;
-// totals[15]: what the process totals' counts moved by around the call; total_ms[1].
-// second_mask >= 0 (via_setters must be 0): TWO calls at the same time on two threads, each with a map object, planners
-// and handles of its own built from the same arguments — the first under mask into slot 0, the second under second_mask
-// into slot 1 of every output ([2] x ... as above; totals then spans both).  Returns 0, -2 when a buffer is too small, -1
-// on a bad argument, -3 when a call threw.  Needs a GPU.
-}  // extern "C"
-
-namespace {
-constexpr int kStatCounts = 15;
-void statCounts(const bsplineTraj::BatchStats& s, long long* out) {
-    const long long v[kStatCounts] = {s.astarDecided,   s.astarHost,    s.guidesDecided,   s.guidesHost,  s.prologueDecided,
-                                      s.prologueHost,   s.reguideDecided, s.reguideHost,   s.epilogueDecided, s.epilogueHost,
-                                      s.seedDecided,    s.seedHost,     s.epilogueGroups,  s.solveBatches, s.solvePlanners};
-    std::copy(v, v + kStatCounts, out);
-}
-bsplineTraj::BatchOptions optionsOfMask(int mask, int budget) {
-    bsplineTraj::BatchOptions o;
-    o.deviceAstar = (mask & 1) != 0;
-    o.deviceGuides = (mask >> 1) & 3;
-    o.devicePrologue = (mask & 8) != 0;
-    o.deviceReguide = (mask >> 4) & 3;
-    o.mixedBatches = (mask & 64) != 0;
-    o.deviceEpilogue = (mask & 128) != 0;
-    o.deviceAstarBudget = budget;
-    return o;
-}
-// the fields optionsOfMask writes, as the process default, through their setters
-void setDefaults(const bsplineTraj::BatchOptions& o) {
-    bsplineTraj::setDeviceAstar(o.deviceAstar);
-    bsplineTraj::setDeviceGuides(o.deviceGuides);
-    bsplineTraj::setDevicePrologue(o.devicePrologue);
-    bsplineTraj::setDeviceReguide(o.deviceReguide);
-    bsplineTraj::setMixedBatches(o.mixedBatches);
-    bsplineTraj::setDeviceEpilogue(o.deviceEpilogue);
-    bsplineTraj::setDeviceAstarBudget(o.deviceAstarBudget);
-}
-}  // namespace
-
-extern "C" {
-
-int vigo_host_plan_batch_options(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
-                                 const double* path_xyz, const double* cfg, int mask, int budget, int via_setters, int second_mask, int ncp_cap,
-                                 long long cap, int pose_cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_guides,
-                                 double* guides, int* n_poses, double* pos, double* quat, long long* stats, double* seconds, long long* totals,
-                                 double* total_ms) {
-    if (n < 1 || !path_off || !path_xyz || !cfg || mask < 0 || (second_mask >= 0 && via_setters) || via_setters < 0 || via_setters > 2 ||
-        (via_setters == 2 && mask != 0))
-        return -1;
-    for (int t = 0; t < n; ++t)
-        if (path_off[t + 1] - path_off[t] < 2) return -1;
-    const int calls = second_mask >= 0 ? 2 : 1;
-    const bsplineTraj::BatchOptions o[2] = {optionsOfMask(mask, budget), optionsOfMask(std::max(second_mask, 0), budget)};
-    std::vector<std::unique_ptr<BatchFixture>> fx;
-    for (int c = 0; c < calls; ++c) fx.emplace_back(new BatchFixture(vox, dims, origin, res, cfg, n, path_off, path_xyz));
-    FreshPlanners fp[2];
-    std::vector<bool> planned[2];
-    std::vector<nav_msgs::Path> traj[2];
-    bsplineTraj::BatchStats st[2];
-    bool threw[2] = {false, false};
-    const bsplineTraj::BatchStats before = bsplineTraj::batchTotals();     // (making the planners below counts nothing)
-    if (calls == 1) {
-        fp[0] = freshPlanners(*fx[0]);
-        if (via_setters) {
-            if (via_setters == 1) setDefaults(o[0]);
-            const auto c0 = std::chrono::steady_clock::now();
-            planned[0] = bsplineTraj::makePlanBatch(fp[0].ps, traj[0], true);
-            total_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-            if (via_setters == 1) setDefaults(bsplineTraj::BatchOptions());
-        } else {
-            planned[0] = timedPlan(fp[0].ps, o[0], total_ms[0], st[0], &traj[0]);
-        }
-    } else {
-        // each thread makes its planners (their handles with them), waits for the other to have done so, and plans
-        std::promise<void> ready[2];
-        std::shared_future<void> other[2] = {ready[1].get_future().share(), ready[0].get_future().share()};
-        auto run = [&](int c) {
-            try {
-                fp[c] = freshPlanners(*fx[c]);
-            } catch (...) { threw[c] = true; }
-            ready[c].set_value();
-            other[c].wait();
-            if (threw[0] || threw[1]) return;
-            try {
-                planned[c] = timedPlan(fp[c].ps, o[c], total_ms[c], st[c], &traj[c]);
-            } catch (...) { threw[c] = true; }
-        };
-        std::thread a(run, 0), b(run, 1);
-        a.join();
-        b.join();
-        if (threw[0] || threw[1]) return -3;
-    }
-    const bsplineTraj::BatchStats after = bsplineTraj::batchTotals();
-    long long c0[kStatCounts], c1[kStatCounts];
-    statCounts(before, c0);
-    statCounts(after, c1);
-    for (int k = 0; k < kStatCounts; ++k) totals[k] = c1[k] - c0[k];
-    if (via_setters) {
-        st[0].prologueSeconds = after.prologueSeconds - before.prologueSeconds;
-        st[0].chainSeconds = after.chainSeconds - before.chainSeconds;
-    }
-    int rc = 0;
-    for (int c = 0; c < calls && rc == 0; ++c) {
-        if (via_setters) std::copy(totals, totals + kStatCounts, stats);
-        else statCounts(st[c], stats + c * kStatCounts);
-        seconds[2 * c] = st[c].prologueSeconds;
-        seconds[2 * c + 1] = st[c].chainSeconds;
-        rc = dumpSlot(fp[c].ps, planned[c], c, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, nullptr, nullptr);
-        if (rc == 0) rc = dumpPoses(traj[c], (size_t)n, c, pose_cap, n_poses, pos, quat);
-    }
-    return rc;
-}
-
-// n planners with a pose list each (as vigo_host_plan_batch_options, whose mask bits and budget these are) through
-// updatePathBatch + makePlanBatch(planners, trajectories, yaw) on one dense byte grid, fresh planners every run, `reps`
-// rounds over
-//   slot 0  the options of `mask`, mixedPrologue off   the opt-in stages group by exact count
-//   slot 1  the same options, mixedPrologue on         ... as the mixed solves do, and call the _mixed entries
-// in turn.  Outputs per slot [2] x ... of the slot's LAST run as vigo_host_plan_batch_options': ok, solver, ncp, ctrl,
-// n_seg + segs, n_guides + guides, n_poses + pos + quat, and n_path_pts + paths (astarPaths_); counts[2][8] of that run:
-// prologueGroups, reguideGroups, prologueDecided, prologueHost, reguideDecided, reguideHost, guidesDecided + astarDecided,
-// solveBatches; per run seconds[2][reps][3]: prologueSeconds, chainSeconds, the call's wall time.  Returns 0, -2 when a
-// buffer is too small, -1 on a bad argument.  Needs a GPU.
-int vigo_host_plan_batch_mixed_prologue(const unsigned char* vox, const int* dims, const double* origin, double res, int n, const int* path_off,
-                                        const double* path_xyz, const double* cfg, int mask, int budget, int reps, int ncp_cap, long long cap,
-                                        int pose_cap, int* ok, int* solver, int* ncp, double* ctrl, int* n_seg, int* segs, int* n_guides,
-                                        double* guides, int* n_path_pts, double* paths, int* n_poses, double* pos, double* quat, long long* counts,
-                                        double* seconds) {
-    if (n < 1 || reps < 1 || !path_off || !path_xyz || !cfg || mask < 0) return -1;
-    for (int t = 0; t < n; ++t)
-        if (path_off[t + 1] - path_off[t] < 2) return -1;
-    const BatchFixture fx(vox, dims, origin, res, cfg, n, path_off, path_xyz);
-    int rc = 0;
-    for (int rep = 0; rep < reps && rc == 0; ++rep)
-        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
-            const FreshPlanners fp = freshPlanners(fx);
-            bsplineTraj::BatchOptions o = optionsOfMask(mask, budget);
-            o.mixedPrologue = slot == 1;
-            bsplineTraj::BatchStats st;
-            std::vector<nav_msgs::Path> traj;
-            double ms = 0.0;
-            const std::vector<bool> planned = timedPlan(fp.ps, o, ms, st, &traj);
-            double* sec = seconds + ((size_t)slot * reps + rep) * 3;
-            sec[0] = st.prologueSeconds; sec[1] = st.chainSeconds; sec[2] = ms * 1e-3;
-            if (rep + 1 < reps) continue;
-            const long long v[8] = {st.prologueGroups, st.reguideGroups, st.prologueDecided, st.prologueHost, st.reguideDecided, st.reguideHost,
-                                    st.guidesDecided + st.astarDecided, st.solveBatches};
-            std::copy(v, v + 8, counts + 8 * slot);
-            rc = dumpSlot(fp.ps, planned, slot, ncp_cap, cap, ok, solver, ncp, ctrl, n_guides, guides, n_seg, segs, n_path_pts, paths);
-            if (rc == 0) rc = dumpPoses(traj, (size_t)n, slot, pose_cap, n_poses, pos, quat);
-        }
-    return rc;
-}
-
-// BatchOptions::mixedPrologue of the process default, as it stands (0: off, the default)
-int vigo_host_mixed_prologue_default() { return trajPlanner::bsplineTraj::mixedPrologue() ? 1 : 0; }
-
-// the facade's opt-in switches of the process default (bsplineTraj::defaultBatchOptions) as they stand: bit 0 deviceAstar, bits 1-2 deviceGuides, bit 3 devicePrologue, bits 4-5
-// deviceReguide, bit 6 mixedBatches, bit 7 deviceEpilogue (0: everything off, the default)
-int vigo_host_switches() {
-    using trajPlanner::bsplineTraj;
-    return (bsplineTraj::deviceAstar() ? 1 : 0) | (bsplineTraj::deviceGuides() << 1) | (bsplineTraj::devicePrologue() ? 8 : 0) |
-           (bsplineTraj::deviceReguide() << 4) | (bsplineTraj::mixedBatches() ? 64 : 0) | (bsplineTraj::deviceEpilogue() ? 128 : 0);
 }
 
 }  // extern "C"
@@ -2325,7 +1719,7 @@ extern "C" int vigo_host_dirty_journal(int n_rec, const unsigned long long* vers
     return (int)out.size();
 }
 
-// A map that changes under planners that share it: n planners with a pose list each (as vigo_host_plan_batch_options) on
+// A map that changes under planners that share it: n planners with a pose list each (as vigo_host_plan_batch) on
 // ONE dense map plan by makePlanBatch(planners) under the options of `mask`, after the first upload (round 0) and after
 // each of E edits (round e + 1): edit e writes the bytes edit_bytes[edit_off[e] ..) as the box edit_n[e] at voxel
 // edit_lo[e] into the map and then tells the planners by mode 0: a bare ++version, mode 1: markChanged(lo, n).  The
@@ -2350,6 +1744,8 @@ extern "C" int vigo_host_map_update_replan(const unsigned char* vox, const int* 
         FreshPlanners fp = freshPlanners(fx);
         mapManager::occMap& map = *fx.maps[0];
         const bsplineTraj::BatchOptions o = optionsOfMask(mask, 16384);
+        vigo_host_plan_batch_job_t out{};
+        out.ncp_cap = ncp_cap; out.ok = ok; out.solver = solver; out.ncp = ncp; out.ctrl = ctrl;
         for (int r = 0; r <= E; ++r) {
             if (r > 0) {
                 const int e = r - 1;
@@ -2364,7 +1760,7 @@ extern "C" int vigo_host_map_update_replan(const unsigned char* vox, const int* 
             }
             bsplineTraj::BatchStats st;
             const std::vector<bool> planned = timedPlan(fp.ps, o, round_ms[r], st);
-            const int rc = dumpSlot(fp.ps, planned, r, ncp_cap, 0, ok, solver, ncp, ctrl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            const int rc = dumpSlot(fp.ps, planned, r, out);
             if (rc != 0) return rc;
         }
         const trajPlanner::mapAdapter::SnapshotTotals after = trajPlanner::mapAdapter::snapshotTotals();
@@ -2456,7 +1852,7 @@ void validateBothRoutes(const std::vector<bsplineTraj*>& ps, int* valid, double*
 }
 }  // namespace
 
-// Held plans validated in one call: n planners with a pose list each (as vigo_host_plan_batch_options) on ONE dense map,
+// Held plans validated in one call: n planners with a pose list each (as vigo_host_plan_batch) on ONE dense map,
 // made by heldPlanners (no_device, not_init, obs_off / obs as there).  Outputs: validateBothRoutes' valid, pos, dyn (pos
 // prefilled by the caller) and stats; ncp[n] the planners' control-point counts; totals[3]: what the same three fields of
 // bsplineTraj::batchTotals() moved by over the batch call; ms[reps][2] (reps may be 0): the wall time of the batch form and
